@@ -8,7 +8,13 @@ selection and slot-map/score-row compaction — so the cache stays at `budget` s
 synthetic N(0,1) fp16 (resident in HBM before the timed region), weights do not exist on this
 path.  The metric is BASELINE.json's: decode tokens/s (path only) + HBM GB/s of the kernels.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, pre-warms, warms up, times the K steps and prints the line: the contract keys, `config` and the
+`roofline` of the timed launches.  `--dump-outputs DIR` writes what the last timed step returned to its caller (the
+attention output and the evicted cache indices) as DIR/<name>.npy; the inputs are seeded, so two builds can be compared
+output for output.  Everything else below (other configurations, CPU baseline, live PMC traffic, device probes) runs
+only with `--full`.
 
 N > 1 is launched by torch.distributed.run, one rank per GPU.  Eviction state is per (layer, head), so layers
 shard as contiguous blocks with no data-path collective.  `--scaling strong` (default): the ONE
@@ -16,8 +22,8 @@ Llama2-7B-shaped model is split over the ranks, 32/N layers each — a full pipe
 sequence's token each step; the stage's real output ([1, Hq*D] fp16, the attention output of its last layer) goes to
 the next rank by an RCCL point-to-point pair per step, and a stage launches step i+1 only after the activation of step i
 has arrived (`--handoff overlap` posts it behind the next launch instead).  `--scaling weak` (also reported as a second
-key at N > 1): every rank owns a whole 32-layer block.  The rank-0 line carries `roofline` (dominant kernel, HIP
-events),
+key at N > 1, with `--full`): every rank owns a whole 32-layer block.  The rank-0 line carries `roofline` (dominant
+kernel, HIP events) and, with `--full`,
 `cpu_baseline` (the oracle timed on the host cores of the same box, bounded sample), `strided_prefill` (configs[1] and
 the
 wider strides of Bench-P), `dense_prefix` (the unscored causal prefix, MFMA-bound) and `boundary_kernels` (gather /
@@ -121,9 +127,21 @@ def cpu_baseline(args, budget, policy, seconds=10.0):
 
 
 
-def decode_run(args, dev, rank, world, scaling, DS, want_seq):
+def dump_outputs(dump_dir, arrays, rank, world):
+    """What the caller of the timed path received in its last step, as DIR/<name>.npy (one file set per rank at N > 1):
+    fp16 outputs widened to float32, int32 indices to float64 (exact)."""
+    import numpy as np
+    os.makedirs(dump_dir, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach().cpu()
+        a = a.double() if not a.is_floating_point() else a.float()
+        np.save(os.path.join(dump_dir, f"{name}{f'.rank{rank}' if world > 1 else ''}.npy"), a.numpy())
+
+
+def decode_run(args, dev, rank, world, scaling, DS, want_seq, dump_dir=None):
     """One timed Bench-D run.  scaling 'strong': the `--layers`-layer model is split over the ranks (this rank owns its
-    LayerShard block); 'weak': every rank owns `--layers` layers."""
+    LayerShard block); 'weak': every rank owns `--layers` layers.  ``dump_dir``: write the outputs of the last timed step
+    there (dump_outputs)."""
     from easykv_amd import KVBank, StepPlan
     Hq, D, budget = args.heads, args.head_dim, args.budget
     H = args.kv_heads or Hq
@@ -165,7 +183,7 @@ def decode_run(args, dev, rank, world, scaling, DS, want_seq):
     outs = [torch.empty(L, Hq, 1, D, dtype=torch.float16, device=dev) for _ in range(2)]
     hidden_in = [torch.zeros(k, Hq * D, dtype=torch.float16, device=dev) for _ in range(2)]
     hidden_out = [torch.zeros(k, Hq * D, dtype=torch.float16, device=dev) for _ in range(2)]
-    ids = torch.empty(L, H, 1, dtype=torch.int32, device=dev)
+    ids = torch.full((L, H, 1), -1, dtype=torch.int32, device=dev)     # (defined contents for --dump-outputs)
     plan = StepPlan(policy=args.policy, phase="decode", evict=True, score_off=0, budget=budget, n_split=args.n_split)
     if args.policy == "recency":
         plan.range_start = 0
@@ -181,7 +199,7 @@ def decode_run(args, dev, rank, world, scaling, DS, want_seq):
     st = {"i": 0}
 
     def step(i, timed_idx=None, handoff=True):
-        out = outs[st["i"] & 1]
+        out = st["out"] = outs[st["i"] & 1]
         if handoff and sync_handoff:
             # a pipeline stage consumes the previous stage's activation: the launch is ordered behind its arrival
             for req in pending:
@@ -221,19 +239,15 @@ def decode_run(args, dev, rank, world, scaling, DS, want_seq):
                 pending[:] = DS.ring_handoff_async(send, hidden_in[st["i"] & 1], shard, pending)
         st["i"] += 1
 
-    # Clock / state pre-warm (untimed, before the W warmup steps): the same step for --prewarm-s seconds of wall time.
-    # A cold
-    # GPU needs tens of ms of load before its clocks settle, and the roco state needs ~1000 steps to reach the steady
-    # state the
-    # policy lives in (low-mean tokens outside the feasible set accumulate), so neither depends on how small W is.
-    n_pre = 0
-    if args.prewarm_s > 0:
-        torch.cuda.synchronize()
-        t_pre = time.perf_counter()
-        while time.perf_counter() - t_pre < args.prewarm_s:
-            for _ in range(16):
-                step(n_pre % n_total, handoff=False)     # rank-local: the ranks run different numbers of pre-warm steps
-                n_pre += 1
+    # Clock / state pre-warm (untimed, before the W warmup steps): --prewarm-steps runs of the same step.  A cold GPU
+    # needs tens of ms of load before its clocks settle, and the roco state needs ~1000 steps to reach the steady state
+    # the policy lives in (low-mean tokens outside the feasible set accumulate), so neither depends on how small W is.
+    # A step count, not a wall time: the state the timed steps start from, and so their outputs, must not depend on
+    # how fast the build or the box is.
+    n_pre = args.prewarm_steps
+    for i in range(n_pre):
+        step(i % n_total, handoff=False)
+        if i % 16 == 15 or i == n_pre - 1:
             torch.cuda.synchronize()
     for i in range(args.warmup):
         step(i)
@@ -275,6 +289,8 @@ def decode_run(args, dev, rank, world, scaling, DS, want_seq):
     pending.clear()
     DS.barrier(dev)
     elapsed = DS.max_over_ranks(time.perf_counter() - t0, dev)
+    if dump_dir is not None:      # before anything below runs the step again
+        dump_outputs(dump_dir, {"attn_out": st["out"], "evict_ids": ids}, rank, world)
     slot_rows = bool(any(getattr(bank, "_slot_rows", [False])))      # layout of the score rows the timed steps ran on
     if graph is not None:   # per-kernel durations: a short eager pass with HIP events
         for i in range(args.steps):
@@ -372,8 +388,13 @@ def main():
         help="torch.distributed backend (nccl = RCCL; gloo only for smoke tests)")
     ap.add_argument("--same-device", action="store_true",
         help="debug: every rank uses cuda:0 (multi-rank smoke test on a 1-GPU box)")
-    ap.add_argument("--prewarm-s", type=float, default=1.0,
-        help="untimed pre-warm of clocks and score state before the warmup steps (seconds)")
+    ap.add_argument("--prewarm-steps", type=int, default=4096,
+        help="untimed pre-warm of clocks and score state before the warmup steps (steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+        help="write the outputs of the last timed step as DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--full", action="store_true",
+        help="also run the secondary figures: the other scaling mode and the prefill pipeline (N > 1), per-layer "
+             "launches, other configurations, CPU baseline, live PMC traffic and device bandwidth probes (N = 1)")
     ap.add_argument("--identity-layout", action="store_true",
         help="start from a fresh bank's identity slot map (position order == "
                     "address order) instead of the scattered steady-state layout")
@@ -408,9 +429,10 @@ def main():
     # who is there: one all-reduce of ones over the backend (RCCL when nccl) and the device every rank runs on
     ranks_seen = int(round(DS.sum_over_ranks(1.0, dev)))
     devices = [int(x) for x in DS.all_gather_floats(float(dev.index or 0), dev)]
-    r = decode_run(args, dev, rank, world, args.scaling, DS, want_seq=(rank == 0 and world == 1))
+    r = decode_run(args, dev, rank, world, args.scaling, DS, want_seq=(args.full and rank == 0 and world == 1),
+                   dump_dir=args.dump_outputs)
     second = None
-    if world > 1 and not args.no_second_scaling and not args.graph:
+    if args.full and world > 1 and not args.no_second_scaling and not args.graph:
         other = "weak" if args.scaling == "strong" else "strong"
         r2 = decode_run(args, dev, rank, world, other, DS, want_seq=False)
         tokens2 = args.steps * (world if other == "weak" else 1)      # (single-sequence, like `value`)
@@ -421,7 +443,7 @@ def main():
                   "note": "weak: every rank owns a whole 32-layer block (aggregate layer-parallel throughput)" if other == "weak" else
                           "strong: the 32-layer model split over the ranks"}
     pipe = None
-    if world > 1 and not args.no_prefill and not args.graph and args.layers >= world:
+    if args.full and world > 1 and not args.no_prefill and not args.graph and args.layers >= world:
         pipe = prefill_pipeline(args, dev, rank, world, DS)
     if rank == 0:
         L, H, T, lpl, fused, ev = r["L"], r["H"], r["T"], r["lpl"], r["fused"], r["ev"]
@@ -484,7 +506,7 @@ def main():
         if fused:
             traffic, traffic_src = latest_pmc_summary(args.layers, Hq, H, D, budget, args.policy,
                 lpl) if world == 1 else (None, None)
-            if world == 1 and not args.no_live_pmc:
+            if args.full and world == 1 and not args.no_live_pmc:
                 passthrough = ["--layers", str(args.layers), "--heads", str(args.heads), "--kv-heads",
                     str(args.kv_heads),
                                "--head-dim", str(args.head_dim), "--budget", str(args.budget), "--policy", args.policy]
@@ -499,7 +521,7 @@ def main():
                                 "unit": "GB/s", "frac": gbs / HBM_PEAK_GBS, "traffic": traffic,
                                     "traffic_source": traffic_src,
                                 "bytes_per_launch": b["total"] * lc0, "avg_launch_us": t_attn * 1e6}
-            if world == 1:
+            if args.full and world == 1:
                 copy = device_copy_gbs(dev)
                 line["roofline"]["device_copy_gbs"] = copy      # measured read+write copy bandwidth of this GPU
                 line["roofline"]["frac_of_device_copy"] = gbs / copy
@@ -526,10 +548,10 @@ def main():
                                      "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": step_gbs / HBM_PEAK_GBS,
                                      "bytes_per_step_launches": b["total"] * lc0, "avg_us": (t_attn + t_score) * 1e6,
                                      "score_select_us": t_score * 1e6}
-        if world == 1 and not args.no_prefill and not args.graph and (args.layers, Hq, H, D) == (32, 32, 32, 128):
+        if args.full and world == 1 and not args.no_prefill and not args.graph and (args.layers, Hq, H, D) == (32, 32, 32, 128):
             line["stage_workloads"] = stage_workloads(args, dev, budget, args.policy)
             line["streaming_decode"] = streaming_decode(args, dev, budget, args.policy)
-        if world == 1 and not args.no_prefill and not args.graph:
+        if args.full and world == 1 and not args.no_prefill and not args.graph:
             line["strided_prefill"] = strided_prefill(args, dev)
             sp = line["strided_prefill"]
             if not args.no_live_pmc and sp.get("one_launch") and (args.layers, Hq, H, D, args.policy) == (32, 32, 32,
@@ -582,9 +604,9 @@ def main():
             line["dense_prefix_scored"] = [dense_prefix_scored(args, dev, 1216, 8, 16,
                 "configs[2]: S=4096 stride=16 budget=0.3"),
                                            dense_prefix_scored(args, dev, 4906, 0, 96, "S=9994 stride=96 budget=0.5")]
-        if world == 1 and not args.no_boundary and not args.graph:
+        if args.full and world == 1 and not args.no_boundary and not args.graph:
             line["boundary_kernels"] = boundary_kernels(args, dev)
-        if not args.no_cpu_baseline and world == 1:     # reported baseline: rank 0 at N = 1 only
+        if args.full and not args.no_cpu_baseline and world == 1:     # reported baseline: rank 0 at N = 1 only
             line["cpu_baseline"] = cpu_baseline(args, budget, args.policy if args.policy in ("roco", "h2o_head",
                 "tova") else "roco")
         if "strided_prefill_more" in line and (args.layers, Hq, H, D) == (32, 32, 32, 128):

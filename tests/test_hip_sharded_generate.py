@@ -277,7 +277,8 @@ def test_bench_two_ranks_same_device_end_to_end(scaling):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "24", "--warmup", "4",
-           "--backend", "gloo", "--same-device", "--prewarm-s", "0.05", "--scaling", scaling, "--layers", "8", "--budget", "256"]
+           "--backend", "gloo", "--same-device", "--prewarm-steps", "256", "--scaling", scaling, "--layers", "8", "--budget", "256",
+           "--full"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run(cmd, cwd=root, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -307,7 +308,7 @@ def test_bench_starts_its_own_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--same-device", "--backend", "gloo", "--steps", "24", "--warmup", "4",
-           "--prewarm-s", "0.05", "--layers", "8", "--budget", "256", "--no-prefill", "--no-second-scaling"]
+           "--prewarm-steps", "256", "--layers", "8", "--budget", "256", "--no-prefill", "--no-second-scaling"]
     for k in (1, 2):
         r = subprocess.run(cmd + (["--seqs-per-launch", "2"] if k == 2 else []), cwd=root, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
                            text=True, timeout=600)

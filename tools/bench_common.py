@@ -89,7 +89,7 @@ def prewarm(step, seconds, dev):
     """Untimed pre-warm of a secondary figure: the same step for `seconds` of wall time.  A launch shape timed right after its first
     use runs at lower clocks for hundreds of milliseconds (docs/TUNING.md §3.5 'a measurement trap': configs[3] 903 us per
     step behind 8
-    warm-up steps, 857-863 us behind >= 25 ms of them) — the headline run has had --prewarm-s since round 1."""
+    warm-up steps, 857-863 us behind >= 25 ms of them) — the headline run is pre-warmed as well (--prewarm-steps)."""
     t_end = time.perf_counter() + seconds
     while time.perf_counter() < t_end:
         for _ in range(8):
@@ -190,9 +190,8 @@ def live_pmc(extra_args, kernel_substr, timeout_s=150, script=None):
     for ctr in ("FETCH_SIZE", "WRITE_SIZE"):
         d = tempfile.mkdtemp(prefix="ekv_pmc_", dir="/tmp")
         cmd = [rp, "--pmc", ctr, "--output-format", "csv", "-d", d, "--", sys.executable]
-        cmd += ([script] if script else [os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--steps", "16", "--warmup",
-            "4", "--prewarm-s", "0.05",
-                                         "--no-prefill", "--no-boundary", "--no-live-pmc"]) + extra_args
+        cmd += ([script] if script else [os.path.join(ROOT, "bench.py"), "--steps", "16", "--warmup", "4", "--prewarm-steps",
+                                         "256"]) + extra_args
         try:
             subprocess.run(cmd, cwd="/tmp", env=dict(os.environ, TMPDIR="/tmp"), stdout=subprocess.DEVNULL,
                 stderr=subprocess.DEVNULL,

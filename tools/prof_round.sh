@@ -15,9 +15,9 @@ run_pmc() {   # name, counter, command...
   mkdir -p $OUT/$name
   cp $(find /tmp/p_$name -name "*counter_collection.csv" | head -1) $OUT/$name/ 2>/dev/null
 }
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_trace -- python $R/bench.py --steps 512 --no-cpu-baseline --no-live-pmc > $OUT/bench_under_trace.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_trace -- python $R/bench.py --full --steps 512 --no-cpu-baseline --no-live-pmc > $OUT/bench_under_trace.log 2>&1
 mkdir -p $OUT/trace; cp $(find /tmp/p_trace -name "*kernel_stats.csv" | head -1) $OUT/trace/
-D="python $R/bench.py --no-cpu-baseline --no-live-pmc --steps 16 --warmup 4 --prewarm-s 0.05 --no-prefill --no-boundary"
+D="python $R/bench.py --steps 16 --warmup 4 --prewarm-steps 256"
 run_pmc decode_fetch FETCH_SIZE $D
 run_pmc decode_write WRITE_SIZE $D
 for cfg in "c2 4096 8 24" "s64 4096 64 12" "c4 9994 96 8"; do
@@ -44,5 +44,5 @@ if [ -f $R/easykv_amd/csrc/variants/lib_resprof.so ]; then
   EASYKV_HIP_LIB=$R/easykv_amd/csrc/variants/lib_resprof.so timeout 300 python $R/tools/experiments/exp_resident_prof.py > $OUT/resident_stamps.txt 2>&1
 fi
 cd $R
-timeout 900 python bench.py > $OUT/bench_line.json 2> $OUT/bench_line.err
+timeout 900 python bench.py --full > $OUT/bench_line.json 2> $OUT/bench_line.err
 ls $OUT

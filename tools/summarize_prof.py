@@ -60,8 +60,8 @@ def main(src, tag):
                     w.writerow([r[k] for k in ("Name", "Calls", "TotalDurationNs", "AverageNs", "Percentage", "MinNs", "MaxNs", "StdDev")])
                     kernels[r["Name"]] = dict(calls=int(r["Calls"]), avg_us=float(r["AverageNs"]) / 1e3, min_us=float(r["MinNs"]) / 1e3,
                                               max_us=float(r["MaxNs"]) / 1e3)
-    dec = dict(command="rocprofv3 --kernel-trace --stats -- python bench.py --steps 512 --no-cpu-baseline ; rocprofv3 --pmc FETCH_SIZE|WRITE_SIZE "
-                       "-- python bench.py --no-cpu-baseline --steps 16 --warmup 4 --prewarm-s 0.05 --no-prefill --no-boundary",
+    dec = dict(command="rocprofv3 --kernel-trace --stats -- python bench.py --full --steps 512 --no-cpu-baseline ; rocprofv3 --pmc FETCH_SIZE|WRITE_SIZE "
+                       "-- python bench.py --steps 16 --warmup 4 --prewarm-steps 256",
                kernels=kernels, pmc=combine(src, "decode"))
     ut = os.path.join(src, "bench_under_trace.log")      # the traced process's own bench line: its avg_launch_us is what the trace's average must agree with
     if os.path.exists(ut):
