@@ -113,30 +113,25 @@ bool ekv_wide_tail_supported(int W, int n_wg) {
 
 // Kernel launches of ekv_launch_attn_chunk below for the same arguments: the query rotation of the 16x16 RoPE path, one launch per
 // pass of the wide kernel (`passes` bits), two for the 16x16 two-pass scheme.  Keep next to the launch code.
-int ekv_attn_chunk_launches(const EkvAttnArgs& a, int head_dim, bool two_pass, int passes) {
-  const bool rope = a.rope_cos != nullptr;
-  const bool wide = ekv_chunk_wide(head_dim, a.n_q_heads / a.n_kv_heads, a.q_len, rope, two_pass, a.logits != nullptr);
+int ekv_attn_chunk_launches(bool wide, bool rope, bool two_pass, int passes) {
   if (wide) return ((passes & 1) ? 1 : 0) + ((two_pass && (passes & 2)) ? 1 : 0);
   return (rope ? 1 : 0) + (two_pass ? 2 : 1);
 }
 
-hipError_t ekv_launch_attn_chunk(const EkvAttnArgs& a, int head_dim, int layer_count, bool two_pass, hipStream_t s,
+hipError_t ekv_launch_attn_chunk(const EkvAttnArgs& a, int head_dim, int layer_count, bool wide, bool two_pass, hipStream_t s,
                                  const EkvScoreArgs* fuse_sc, int passes, const EkvScoreArgs* tail_sc) {
-  if (two_pass && fuse_sc != nullptr) return hipErrorInvalidValue;
-  if (tail_sc != nullptr && !(two_pass && (passes & 2))) return hipErrorInvalidValue;
+  if (two_pass && (fuse_sc != nullptr || a.stats == nullptr || a.colsum == nullptr)) return hipErrorInvalidValue;
+  if (tail_sc != nullptr && !(wide && two_pass && (passes & 2))) return hipErrorInvalidValue;
   int qb_rows, n_qblocks, qpw;
   ekv_chunk_blocks(a.n_q_heads / a.n_kv_heads, a.q_len, &qb_rows, &n_qblocks, &qpw);
-  if (qb_rows != a.qb_rows || n_qblocks != a.n_qblocks) return hipErrorInvalidValue;
   const bool rope = a.rope_cos != nullptr;
-  const bool wide = ekv_chunk_wide(head_dim, a.n_q_heads / a.n_kv_heads, a.q_len, rope, two_pass, a.logits != nullptr);
   if (rope && !wide) {      // (the wide-block kernel rotates its query rows itself, in the lane that holds them)
     if (a.q_rot_hi == nullptr || a.q_rot_lo == nullptr) return hipErrorInvalidValue;
     const int n_rows = a.n_q_heads * a.q_len, rpb = 256 / (head_dim / 4);
     hipLaunchKernelGGL(ekv_rope_q_kernel, dim3((n_rows + rpb - 1) / rpb, layer_count), dim3(256), 0, s, a, head_dim, n_rows);
   }
   if (wide) {
-    if (fuse_sc != nullptr || (two_pass && (a.stats == nullptr || a.colsum == nullptr || a.n_col_parts < 1 || a.n_col_parts > n_qblocks))) return hipErrorInvalidValue;
-    if (!two_pass && a.stats != nullptr) return hipErrorInvalidValue;      // (mode 0 writes row statistics whenever the array is there)
+    if (fuse_sc != nullptr || (!two_pass && a.stats != nullptr)) return hipErrorInvalidValue;      // (mode 0 writes row statistics whenever the array is there)
     const int nwq = qpw == 4 ? 4 : 2;
     // one pass over K and V (output, and for a scored step every row's softmax statistics), then — scored steps — the column-sum
     // pass over K
@@ -159,8 +154,6 @@ hipError_t ekv_launch_attn_chunk(const EkvAttnArgs& a, int head_dim, int layer_c
 #undef EKW_GO
     return e;
   }
-  if (tail_sc != nullptr) return hipErrorInvalidValue;
-  if (two_pass && (a.stats == nullptr || a.colsum == nullptr || a.n_col_parts != ekv_chunk_col_parts(qpw, rope) * n_qblocks)) return hipErrorInvalidValue;
 #define EKV_GO(d, m) ekv_launch_attn_chunk_d##d##_m##m(a, kernel_code(qpw, rope, m), layer_count, s, fuse_sc)
   hipError_t e = hipSuccess;
   switch (head_dim) {

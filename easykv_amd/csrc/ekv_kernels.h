@@ -6,27 +6,54 @@
 
 #include "../../include/easykv_hip.h"
 
-// Workspace carve-up for one ekv_step_attend call.
-struct EkvWs {
-  float* logits;    // [layer_count][Hq][q_len][t_pad]   raw q.k/sm_div of every live position
-  float* partials;  // [layer_count][Hq][q_len][n_split][D+2]   (m, l, o[D]) per key-range split
-  float* tova_row;  // [layer_count][t_pad]   head-averaged last-query row (tova_head_mean)
-  float* big_rows;  // [layer_count][H][3][t_pad] working copies of the score rows when they exceed one CU's LDS, else null
-  float* stats;     // two-pass chunk steps (see EkvAttnArgs)
-  float* colsum;
-  int32_t two_pass, n_col_parts;
-  float* row_stats;
-  int32_t fold_in_kernel;   // chunk step whose attention kernel writes the final output itself (no partials, no fold)
-  int32_t wide;             // chunk step on the wide-query-block kernel (ekv_attn_wide.inc): ONE partial per split, ONE column-sum row
-  int32_t resident;         // whole scored chunk step on the logits-resident kernel (ekv_attn_resident.inc): one launch, unsplit
-  int32_t fused_nw;     // waves per workgroup the fused decode kernel would use for this launch (4 or 8)
-  __half* q_keep;   // deferred wide two-pass chunk steps: [layer_count][Hq][q_len][D] raw queries kept for the flush's column-sum pass
-  __half* q_rot;    // rope_on_read chunk steps: [2][layer_count][Hq][q_len][D] rotated queries, fp16 hi then lo
+// One kernel launch sequence entry of a step (EkvStepPlan::list), in issue order.
+enum EkvLaunchKind : int32_t {
+  EKV_RUN_FUSED_DECODE,   // ekv_launch_decode_fused: the whole decode step
+  EKV_RUN_CHUNK_LDS,      // ekv_launch_chunk_lds: the whole small-row chunk step
+  EKV_RUN_RESIDENT,       // ekv_launch_attn_resident: the whole logits-resident chunk step
+  EKV_RUN_DECODE,         // ekv_launch_attn_decode: split decode attention
+  EKV_RUN_CHUNK,          // ekv_launch_attn_chunk
+  EKV_RUN_FLUSH,          // ekv_launch_attn_chunk: the deferred column-sum pass of all layers, from the kept queries
+  EKV_RUN_FOLD, EKV_RUN_RANGE, EKV_RUN_DECODE_SCORE, EKV_RUN_TOVA_MEAN, EKV_RUN_SCORE_SELECT
+};
+struct EkvLaunch {
+  int32_t kind, kernel_count;
+  int32_t skip_fold;   // EkvScoreArgs.skip_fold of this launch
+  int32_t passes;      // EKV_RUN_CHUNK / _FLUSH: pass bits of ekv_launch_attn_chunk
+  int32_t fuse, tail;  // ... the scorer runs as the tail of the 16x16 one-pass kernel / of the wide column-sum pass
+};
+
+// Everything ekv_step_attend decides about a step, from the bank and step descriptors alone (ekv_plan_step): nothing is
+// dereferenced.  ekv_step_attend, ekv_step_check, ekv_step_plan, ekv_step_info and ekv_workspace_bytes all read it.
+struct EkvStepPlan {
   int32_t t_pad, n_split, rows_per_split;
   int32_t n_partials;   // partials per query row the scorer folds (chunk kernels emit 2 per split)
-  int32_t qb_rows, n_qblocks;
-  size_t bytes;
+  int32_t qb_rows, n_qblocks, n_col_parts;
+  int32_t fused_nw;     // waves per workgroup of the fused decode kernel for this launch (4 or 8)
+  int32_t l_pad, phys_extent;   // see EkvAttnArgs
+  int32_t two_pass;
+  int32_t wide;             // chunk step on the wide-query-block kernel (ekv_attn_wide.inc): ONE partial per split, ONE column-sum row
+  int32_t resident;         // whole scored chunk step on the logits-resident kernel (ekv_attn_resident.inc): one launch, unsplit
+  int32_t fold_in_kernel;   // chunk step whose attention kernel writes the final output itself (no partials, no fold)
+  int32_t fold_in_decode;   // split decode step whose last-arriving split of a head folds the partials (ekv_bank.arrive)
+  int32_t flush_unsplit;    // deferred flush: the column-sum pass runs unsplit over the one pass's key-range statistics
+  int32_t slot_rows, slot_tail_ok;   // fused decode step on the slot-indexed score rows (EKV_PHASE_SLOT_ROWS / _TAIL_OK)
+  int32_t strides[6];       // q, kv, out row strides (token, head) in elements, the dense layout filled in
+  // Workspace: byte offsets of this call's slices (a deferred call's layout spans every deferred layer), -1 = not in the layout
+  int64_t logits;     // [layer_count][Hq][q_len][t_pad]   raw q.k/sm_div of every live position
+  int64_t partials;   // [layer_count][Hq][q_len][n_partials][D+2]   (m, l, o[D]) per key-range split
+  int64_t tova_row;   // [layer_count][t_pad]   head-averaged last-query row (tova_head_mean)
+  int64_t big_rows;   // [layer_count][H][3][t_pad] working copies of the score rows when they exceed one CU's LDS
+  int64_t stats, colsum, row_stats;   // see EkvAttnArgs
+  int64_t q_keep;     // deferred wide two-pass chunk steps: [layer_count][Hq][q_len][D] raw queries kept for the flush's column-sum pass
+  int64_t q_rot;      // rope_on_read chunk steps on the 16x16 kernel: [2][layer_count][Hq][q_len][D] rotated queries, fp16 hi then lo
+  size_t bytes;       // workspace the call needs
+  int32_t one_launch;   // the whole step is ONE launch
+  int32_t n_launches;   // kernel launches of the call: the sum of list[].kernel_count
+  int32_t n_list;
+  EkvLaunch list[6];
 };
+int ekv_plan_step(const ekv_bank* bank, const ekv_step* step, EkvStepPlan* plan);
 
 struct EkvAttnArgs {
   const __half* k;
@@ -98,15 +125,14 @@ struct EkvScoreArgs {
   int32_t slot_tail_ok;   // EKV_PHASE_SLOT_TAIL_OK: the newest `tail` entries are known to have consecutive births
 };
 
-EkvWs ekv_plan_workspace(const ekv_bank* bank, const ekv_step* step, void* base);
-
 hipError_t ekv_launch_attn_decode(const EkvAttnArgs& a, int head_dim, int layer_count, hipStream_t s);
 // passes (wide-block kernel, two-pass scheme): bit 0 = the one pass (output + row statistics), bit 1 = the column-sum pass
 // tail_sc (wide-block kernel, two passes, passes & 2): the step's scorer runs as the tail of the column-sum pass (ekv_wide_tail.h)
-hipError_t ekv_launch_attn_chunk(const EkvAttnArgs& a, int head_dim, int layer_count, bool two_pass, hipStream_t s,
-                                 const EkvScoreArgs* fuse_sc = nullptr, int passes = 3, const EkvScoreArgs* tail_sc = nullptr);
-// kernel launches ekv_launch_attn_chunk issues for these arguments (the dry run's count; lives next to the launch code)
-int ekv_attn_chunk_launches(const EkvAttnArgs& a, int head_dim, bool two_pass, int passes);
+// wide: the wide-block kernel (ekv_chunk_wide, decided by the planner)
+hipError_t ekv_launch_attn_chunk(const EkvAttnArgs& a, int head_dim, int layer_count, bool wide, bool two_pass, hipStream_t s,
+                                 const EkvScoreArgs* fuse_sc, int passes, const EkvScoreArgs* tail_sc);
+// kernel launches ekv_launch_attn_chunk issues for these arguments (lives next to the launch code)
+int ekv_attn_chunk_launches(bool wide, bool rope, bool two_pass, int passes);
 // can the scorer of a two-pass wide step run as the tail of its column-sum pass: W score columns, n_wg workgroups per head
 bool ekv_wide_tail_supported(int W, int n_wg);
 // logits-resident scored chunk step (ekv_attn_resident.inc): the whole step of an unsplit head in ONE launch, K and V read once
@@ -123,7 +149,6 @@ hipError_t ekv_launch_score_select(const EkvScoreArgs& a, int layer_count, hipSt
 bool ekv_attn_decode_supported(int head_dim, int rep);
 int ekv_decode_fused_nw(int n_heads_in_launch);
 bool ekv_decode_fused_supported(int head_dim, int rep, int n_slots, int t_pad, int l_pad, int n_evict, int cap, int nw);
-int ekv_fused_logit_pad(const ekv_bank* bank, const ekv_step* st, int t_pad);
 hipError_t ekv_launch_decode_fused(const EkvAttnArgs& a, const EkvScoreArgs& sc, int head_dim, int layer_count, int nw, hipStream_t s);
 bool ekv_attn_chunk_supported(int head_dim, int rep, int q_len);
 void ekv_chunk_blocks(int rep, int q_len, int* qb_rows, int* n_qblocks, int* qpw);

@@ -97,3 +97,45 @@ def test_resident_step_against_the_oracle(hq, h, n, t_prev):
         pbar = p.reshape(1, h, rep, n, T).mean(2)                     # GQA fold (easykv/easykv.py:173-186), then the column sums (:443-457)
         torch.testing.assert_close(a.score_sum[layer, :, :T].cpu(), pbar.sum(2)[0], rtol=2e-5, atol=1e-6)
         torch.testing.assert_close(a.score_sq[layer, :, :T].cpu(), (pbar ** 2).sum(2)[0], rtol=4e-5, atol=1e-7)
+
+
+def _dump_one_step(hq, h, n, t_prev, path):
+    """One resident-shaped step on a fresh bank (child process: the A/B switches are read once per process)."""
+    import numpy as np
+    from easykv_amd import StepPlan
+    L, d, T = 3, 128, t_prev + n
+    g = torch.Generator().manual_seed(5 * hq + n + t_prev)
+    k = torch.randn(L, h, T, d, generator=g).half()
+    v = torch.randn(L, h, T, d, generator=g).half()
+    q = torch.randn(L, hq, n, d, generator=g).half()
+    a = _bank(L, hq, h, d, T, n, t_prev, k, v, False, 5)
+    plan = StepPlan(policy="roco", phase="prefill", accumulate=True, evict=True, budget=T, recent=int(T * 0.1), sink=4, stride=n)
+    info = a.step_info(plan, n)
+    out, ids = a.attend(plan, q.cuda(), k[:, :, t_prev:].cuda().contiguous(), v[:, :, t_prev:].cuda().contiguous())
+    np.savez(path, out=out.float().cpu().numpy(), ids=ids.cpu().numpy(), fused=info["fused"], score_sum=a.score_sum.cpu().numpy(),
+             slot_of_pos=a.slot_of_pos.cpu().numpy())
+
+
+@pytest.mark.parametrize("hq,h,n,t_prev", [(8, 2, 4, 700), (8, 2, 8, 2056)])
+def test_resident_shape_without_the_wide_tail(hq, h, n, t_prev, tmp_path):
+    """With EKV_NO_WIDE_TAIL=1 (the A/B switch of the wide-kernel scorer tail, which is also the resident kernel's scorer) a
+    resident-shaped step of 16 / 32 rows is planned as an ordinary step and runs: same victims and outputs as the resident step."""
+    import os
+    import subprocess
+    import sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    res = {}
+    for name, extra in (("default", {}), ("no_tail", {"EKV_NO_WIDE_TAIL": "1"})):
+        env = {k: v for k, v in os.environ.items() if not k.startswith("EKV_")}
+        env.update(extra)
+        path = str(tmp_path / f"{name}.npz")
+        code = f"import tests.test_hip_resident as t; t._dump_one_step({hq}, {h}, {n}, {t_prev}, {path!r})"
+        r = subprocess.run([sys.executable, "-c", code], cwd=root, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        res[name] = np.load(path)
+    a, b = res["default"], res["no_tail"]
+    assert int(a["fused"]) == 1 and int(b["fused"]) == 0
+    assert np.abs(a["out"] - b["out"]).max() <= 1e-3
+    assert np.array_equal(a["ids"], b["ids"]) and np.array_equal(a["slot_of_pos"], b["slot_of_pos"])
+    torch.testing.assert_close(torch.from_numpy(b["score_sum"]), torch.from_numpy(a["score_sum"]), rtol=2e-5, atol=1e-6)
