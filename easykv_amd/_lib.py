@@ -8,6 +8,8 @@ from __future__ import annotations
 import ctypes as C
 import os
 
+import torch
+
 from ._build import LIB
 
 # policy codes (include/easykv_hip.h)
@@ -17,9 +19,14 @@ PHASE_SLOT_ROWS = 16      # ekv_step.phases bit: the layers' score rows are in t
 POLICY_CODES = {"full": POLICY_NONE, "h2o_head": POLICY_H2O_HEAD, "roco": POLICY_ROCO, "tova": POLICY_TOVA,
                 "recency": POLICY_RANGE, "random": POLICY_RANGE}
 
+# element type of a step's 16-bit tensors (the bank's k / v, q, k_new, v_new, out): the *_typed calls
+DTYPE_F16, DTYPE_BF16 = 0, 1
+DTYPE_CODES = {torch.float16: DTYPE_F16, torch.bfloat16: DTYPE_BF16}
+
 EXPORTS = ("ekv_abi_version", "ekv_strerror", "ekv_workspace_bytes", "ekv_step_plan", "ekv_bank_reset", "ekv_state_init",
            "ekv_step_attend", "ekv_gather_ordered", "ekv_scatter_rows", "ekv_compact_inplace", "ekv_step_check", "ekv_step_info",
-           "ekv_rows_to_slots", "ekv_rows_to_order")
+           "ekv_rows_to_slots", "ekv_rows_to_order", "ekv_workspace_bytes_typed", "ekv_step_check_typed", "ekv_step_info_typed",
+           "ekv_step_attend_typed")
 
 
 class Bank(C.Structure):
@@ -74,8 +81,13 @@ def load():
     lib.ekv_step_info.argtypes = [C.POINTER(Bank), C.POINTER(Step), C.POINTER(C.c_int32), C.c_int32]
     lib.ekv_rows_to_slots.argtypes = [C.POINTER(Bank), i32, i32, i32, vp]
     lib.ekv_rows_to_order.argtypes = [C.POINTER(Bank), i32, i32, i32, vp]
+    lib.ekv_workspace_bytes_typed.argtypes = [C.POINTER(Bank), C.POINTER(Step), i32]
+    lib.ekv_step_check_typed.argtypes = [C.POINTER(Bank), C.POINTER(Step), i32]
+    lib.ekv_step_info_typed.argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, C.POINTER(C.c_int32), C.c_int32]
+    lib.ekv_step_attend_typed.argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
     for name in EXPORTS[3:]:
         getattr(lib, name).restype = C.c_int
+    lib.ekv_workspace_bytes_typed.restype = C.c_size_t
     if lib.ekv_abi_version() != 8:
         raise EkvError("ABI version mismatch")
     _lib = lib

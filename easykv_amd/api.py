@@ -86,16 +86,22 @@ class BudgetedKVCache:
 
     ``layer_begin`` / ``layer_count``: the contiguous block of the model's layers THIS process owns (layer sharding,
     SURVEY.md §8e: the reference spreads layers over GPUs with ``device_map='auto'``, test_passkey.py:25-35; here one process
-    per GPU owns a block, easykv_amd/dist.py).  The bank holds only those layers; :meth:`attend` takes GLOBAL layer indices."""
+    per GPU owns a block, easykv_amd/dist.py).  The bank holds only those layers; :meth:`attend` takes GLOBAL layer indices.
+
+    ``dtype``: element type of the K/V bank, torch.float16 (None = the default) or torch.bfloat16; q / k / v of another dtype are
+    converted to it and the attention output comes back in it.  A bf16 bank has no RoPE-on-read build (``streaming``)."""
 
     def __init__(self, n_layers, n_q_heads, n_kv_heads, head_dim, cap, device, streaming=False, rope=None,
-                 record=False, layer_begin=0, layer_count=None, rope_base=10000.0):
+                 record=False, layer_begin=0, layer_count=None, rope_base=10000.0, dtype=None):
         self.layer_begin = layer_begin
         self.layer_count = n_layers - layer_begin if layer_count is None else layer_count
         if not (0 <= self.layer_begin and self.layer_count >= 1 and self.layer_begin + self.layer_count <= n_layers):
             raise ValueError(f"layer block [{layer_begin}, {layer_begin}+{layer_count}) outside the model's {n_layers} layers")
         self.n_model_layers = n_layers
-        self.bank = KVBank(self.layer_count, n_q_heads, n_kv_heads, head_dim, cap, device=device)
+        dtype = torch.float16 if dtype is None else dtype
+        if dtype is torch.bfloat16 and streaming:
+            raise ValueError("a bf16 K/V bank has no RoPE-on-read build: streaming=True needs kv_dtype='float16'")
+        self.bank = KVBank(self.layer_count, n_q_heads, n_kv_heads, head_dim, cap, device=device, dtype=dtype)
         self.plan = StepPlan(policy="full", phase="prefill", accumulate=False)
         self.streaming = streaming
         self.positions = None    # true position ids of the forward in flight (set by the driver)
@@ -175,13 +181,14 @@ class BudgetedKVCache:
         self.n_attend += 1
         plan = self.plan
         n = q.shape[2]
-        # fp16 rows are read IN PLACE at their strides (ABI 8): HF hands over [1, H, n, D] transposed views of the projections'
-        # [1, n, H * D] output — three copy kernels per layer in front of every chunk step until round 5.  Other dtypes are converted;
-        # layouts the kernels cannot address are copied dense by KVBank.attend.
-        q, k, v = (t if t.dtype == torch.float16 else t.to(torch.float16) for t in (q, k, v))
+        # rows of the bank's dtype are read IN PLACE at their strides (ABI 8): HF hands over [1, H, n, D] transposed views of the
+        # projections' [1, n, H * D] output — three copy kernels per layer in front of every chunk step until round 5.  Other dtypes are
+        # converted; layouts the kernels cannot address are copied dense by KVBank.attend.
+        dt = self.bank.dtype
+        q, k, v = (t if t.dtype == dt else t.to(dt) for t in (q, k, v))
         # the output is written token-major ([1, n, Hq, D]) and returned as its [1, Hq, n, D] view: the transpose(1, 2) every caller
         # applies next (easykv_amd.hf, llama_patch.py:230-232) is then a dense tensor, no copy in front of o_proj
-        out = torch.empty(1, n, q.shape[1], q.shape[3], dtype=torch.float16, device=q.device).transpose(1, 2) if n > 1 else None
+        out = torch.empty(1, n, q.shape[1], q.shape[3], dtype=dt, device=q.device).transpose(1, 2) if n > 1 else None
         if self.score_prefix and n > PREFIX_BLOCK and not self._prefix_in_one_step(plan, n, layer_idx):
             # keep_attention: the dense prefix must also feed the score rows (easykv/easykv.py:173-186).  ONE launch pair per layer
             # when the LIBRARY says the step runs as the two-pass scheme on the wide-block kernel (ekv_step_info: the query blocks
@@ -245,6 +252,19 @@ def _dims(self):
     return n_layers, hq, h, d
 
 
+def _kv_dtype(model, key):
+    """generation_config['kv_dtype'] -> torch dtype of the K/V bank."""
+    if key == "float16":
+        return torch.float16
+    if key == "bfloat16":
+        return torch.bfloat16
+    if key == "auto":
+        params = getattr(model, "parameters", None)
+        p = next(iter(params()), None) if callable(params) else None
+        return torch.bfloat16 if p is not None and p.dtype == torch.bfloat16 else torch.float16
+    raise ValueError(f"generation_config['kv_dtype'] must be 'float16', 'bfloat16' or 'auto', not {key!r}")
+
+
 # ------------------------------------------------------------------------------------------------
 # generate
 # ------------------------------------------------------------------------------------------------
@@ -266,6 +286,10 @@ def generate(self, input_ids, generation_config, kv_mode="encoding", stride=1, r
     # extension key: capture the steady-state forwards — the evicting decode step and, round 6, the evicting strided chunk of the
     # prefill — in a hipGraph each (GraphedForward)
     use_graph = cfg.get("hipgraph", False)
+    # extension key: element type of the K/V bank — "float16" (default), "bfloat16", or "auto" (bf16 when the model's parameters are)
+    kv_dtype = _kv_dtype(self, cfg.get("kv_dtype", "float16"))
+    if kv_dtype is torch.bfloat16 and streaming:
+        raise ValueError("generation_config['kv_dtype'] = bfloat16 with streaming=True: RoPE-on-read has no bf16 build (use float16)")
     n_layers, hq, h, d = _dims(self)
     dev = torch.device(self.device)
     if input_ids.dim() != 2 or input_ids.shape[0] != 1:
@@ -330,7 +354,7 @@ def generate(self, input_ids, generation_config, kv_mode="encoding", stride=1, r
             from . import hf
             hf_rope = hf.rope_tables_from_model(self, max(cap + 8, length + max_new_tokens + 1) + 64, d, dev)
         cache = BudgetedKVCache(n_layers, hq, h, d, cap + 8, dev, streaming=streaming, record=record, rope=hf_rope,
-                                layer_begin=l_begin, layer_count=l_count, rope_base=rope_base)
+                                layer_begin=l_begin, layer_count=l_count, rope_base=rope_base, dtype=kv_dtype)
         cache.unrotate = hf_rope if hf_stream else None
         return cache
 

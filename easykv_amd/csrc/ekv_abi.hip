@@ -260,17 +260,19 @@ const char* ekv_strerror(int code) {
   }
 }
 
-size_t ekv_workspace_bytes(const ekv_bank* bank, const ekv_step* step) {
+size_t ekv_workspace_bytes_typed(const ekv_bank* bank, const ekv_step* step, int32_t dtype) {
   EkvStepPlan P;
-  (void)ekv_plan_step(bank, step, &P);
+  (void)ekv_plan_step(bank, step, dtype, &P);
   return P.bytes;
 }
+
+size_t ekv_workspace_bytes(const ekv_bank* bank, const ekv_step* step) { return ekv_workspace_bytes_typed(bank, step, EKV_DTYPE_F16); }
 
 int ekv_step_plan(const ekv_bank* bank, const ekv_step* st, int32_t* n_split, int32_t* fused) {
   if (int e = check_bank(bank)) return e;
   if (!st || !n_split || !fused) return EKV_E_ARG;
   EkvStepPlan P;
-  const int rc = ekv_plan_step(bank, st, &P);
+  const int rc = ekv_plan_step(bank, st, EKV_DTYPE_F16, &P);
   *n_split = P.n_split;
   // one launch for the whole step: the fused decode kernel, the logits-in-LDS or logits-resident chunk kernel, or a chunk step whose
   // scorer runs as the tail of the attention kernel; a step the call would refuse plans as 0
@@ -278,16 +280,21 @@ int ekv_step_plan(const ekv_bank* bank, const ekv_step* st, int32_t* n_split, in
   return EKV_OK;
 }
 
-int ekv_step_info(const ekv_bank* bank, const ekv_step* st, int32_t* info, int32_t n_info) {
+int ekv_step_info_typed(const ekv_bank* bank, const ekv_step* st, int32_t dtype, int32_t* info, int32_t n_info) {
+  if (dtype != EKV_DTYPE_F16 && dtype != EKV_DTYPE_BF16) return EKV_E_ARG;
   if (int e = check_bank(bank)) return e;
   if (!st || !info || n_info < 1) return EKV_E_ARG;
   EkvStepPlan P;
-  const bool ok = ekv_plan_step(bank, st, &P) == EKV_OK;
+  const bool ok = ekv_plan_step(bank, st, dtype, &P) == EKV_OK;
   const int32_t v[EKV_STEP_INFO_N] = {P.n_split, ok ? P.one_launch : 0, P.two_pass, P.wide, P.n_qblocks, P.qb_rows, P.n_col_parts,
                                       P.fold_in_kernel, ok ? P.n_launches : 0};
   for (int i = 0; i < n_info && i < EKV_STEP_INFO_N; ++i) info[i] = v[i];
   for (int i = EKV_STEP_INFO_N; i < n_info; ++i) info[i] = 0;
   return EKV_OK;
+}
+
+int ekv_step_info(const ekv_bank* bank, const ekv_step* st, int32_t* info, int32_t n_info) {
+  return ekv_step_info_typed(bank, st, EKV_DTYPE_F16, info, n_info);
 }
 
 int ekv_bank_reset(const ekv_bank* bank, void* stream) {
@@ -371,7 +378,7 @@ static EkvScoreArgs score_args(const ekv_bank* bank, const ekv_step* st, const E
 // The whole dispatch of ekv_step_attend for a step: argument / shape / capability checks (the return code of the call, in the
 // order the call reports them), the tiling, the workspace layout and the launch sequence.  The tiling and the layout are filled in
 // for every step that has something to tile, also when the step is refused (ekv_workspace_bytes and ekv_step_info report them).
-int ekv_plan_step(const ekv_bank* bank, const ekv_step* step, EkvStepPlan* P) {
+static int plan_step_impl(const ekv_bank* bank, const ekv_step* step, EkvStepPlan* P) {
   *P = EkvStepPlan{};
   const int bank_rc = check_bank(bank);
   if (!bank || !step) return bank_rc ? bank_rc : EKV_E_ARG;
@@ -670,12 +677,28 @@ int ekv_plan_step(const ekv_bank* bank, const ekv_step* step, EkvStepPlan* P) {
   return EKV_OK;
 }
 
+// The element type only picks the kernel instances: a bf16 step is planned as the fp16 step.  RoPE-on-read keeps hi / lo fp16 planes
+// of the rotated keys and queries (ekv_attn_wide.inc, ekv_rope_q_kernel) and has no bf16 build.
+int ekv_plan_step(const ekv_bank* bank, const ekv_step* step, int32_t dtype, EkvStepPlan* P) {
+  if (dtype != EKV_DTYPE_F16 && dtype != EKV_DTYPE_BF16) {
+    *P = EkvStepPlan{};
+    return EKV_E_ARG;
+  }
+  const int rc = plan_step_impl(bank, step, P);
+  P->bf16 = dtype == EKV_DTYPE_BF16;
+  if (rc == EKV_OK && P->bf16 && step->rope_on_read) {
+    P->one_launch = P->n_launches = P->n_list = 0;
+    return EKV_E_UNSUPPORTED;
+  }
+  return rc;
+}
+
 // Body of ekv_step_attend: the plan, the pointers, then its launch sequence.
-static int step_attend_impl(const ekv_bank* bank, const ekv_step* st, const void* q, const void* k_new, const void* v_new,
-                            void* out, int32_t* evict_ids, const float* rope_cos, const float* rope_sin, void* workspace,
-                            size_t workspace_bytes, void* stream) {
+static int step_attend_impl(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const void* q, const void* k_new,
+                            const void* v_new, void* out, int32_t* evict_ids, const float* rope_cos, const float* rope_sin,
+                            void* workspace, size_t workspace_bytes, void* stream) {
   EkvStepPlan P;
-  if (int e = ekv_plan_step(bank, st, &P)) return e;
+  if (int e = ekv_plan_step(bank, st, dtype, &P)) return e;
   if (!q || !k_new || !v_new || !out || !workspace || (st->rope_on_read && (!rope_cos || !rope_sin))) return EKV_E_ARG;
   if (P.bytes > workspace_bytes) return EKV_E_WORKSPACE;
   hipStream_t s = static_cast<hipStream_t>(stream);
@@ -743,18 +766,19 @@ static int step_attend_impl(const ekv_bank* bank, const ekv_step* st, const void
     sa.slot_tail_ok = P.slot_tail_ok;
   }
 
+  const bool bf16 = P.bf16 != 0;
   drop_stale_error();
   for (int i = 0; i < P.n_list; ++i) {
     const EkvLaunch& L = P.list[i];
     sa.skip_fold = L.skip_fold;
     hipError_t e = hipSuccess;
     switch (L.kind) {
-      case EKV_RUN_FUSED_DECODE: e = ekv_launch_decode_fused(aa, sa, D, lc, P.fused_nw, s); break;
-      case EKV_RUN_CHUNK_LDS: e = ekv_launch_chunk_lds(aa, sa, D, lc, s); break;
-      case EKV_RUN_RESIDENT: e = ekv_launch_attn_resident(aa, sa, lc, s); break;
-      case EKV_RUN_DECODE: e = ekv_launch_attn_decode(aa, D, lc, s); break;
+      case EKV_RUN_FUSED_DECODE: e = ekv_launch_decode_fused(aa, sa, D, lc, P.fused_nw, s, bf16); break;
+      case EKV_RUN_CHUNK_LDS: e = ekv_launch_chunk_lds(aa, sa, D, lc, s, bf16); break;
+      case EKV_RUN_RESIDENT: e = ekv_launch_attn_resident(aa, sa, lc, s, bf16); break;
+      case EKV_RUN_DECODE: e = ekv_launch_attn_decode(aa, D, lc, s, bf16); break;
       case EKV_RUN_CHUNK:
-        e = ekv_launch_attn_chunk(aa, D, lc, P.wide, P.two_pass, s, L.fuse ? &sa : nullptr, L.passes, L.tail ? &sa : nullptr);
+        e = ekv_launch_attn_chunk(aa, D, lc, P.wide, P.two_pass, s, L.fuse ? &sa : nullptr, L.passes, L.tail ? &sa : nullptr, bf16);
         break;
       case EKV_RUN_FLUSH: {
         EkvAttnArgs a2 = aa;
@@ -767,18 +791,18 @@ static int step_attend_impl(const ekv_bank* bank, const ekv_step* st, const void
           a2.n_split = 1;
           a2.rows_per_split = P.t_pad;
         }
-        e = ekv_launch_attn_chunk(a2, D, lc, P.wide, true, s, nullptr, L.passes, L.tail ? &sa : nullptr);
+        e = ekv_launch_attn_chunk(a2, D, lc, P.wide, true, s, nullptr, L.passes, L.tail ? &sa : nullptr, bf16);
         break;
       }
-      case EKV_RUN_FOLD: e = ekv_launch_fold(sa, lc, s); break;
+      case EKV_RUN_FOLD: e = ekv_launch_fold(sa, lc, s, bf16); break;
       case EKV_RUN_RANGE:
         hipLaunchKernelGGL(ekv_range_evict_kernel, dim3(bank->n_kv_heads, lc), dim3(256), (size_t)st->n_evict * 4, s, bank->slot_of_pos,
                            evict_ids, bank->n_kv_heads, bank->cap, st->layer_begin, st->n_slots, st->range_start, st->n_evict);
         e = hipGetLastError();
         break;
-      case EKV_RUN_DECODE_SCORE: e = ekv_launch_decode_score(sa, lc, s); break;
+      case EKV_RUN_DECODE_SCORE: e = ekv_launch_decode_score(sa, lc, s, bf16); break;
       case EKV_RUN_TOVA_MEAN: e = ekv_launch_tova_headmean(sa, lc, s); break;
-      case EKV_RUN_SCORE_SELECT: e = ekv_launch_score_select(sa, lc, s); break;
+      case EKV_RUN_SCORE_SELECT: e = ekv_launch_score_select(sa, lc, s, bf16); break;
     }
     if (e != hipSuccess) return EKV_E_LAUNCH;
   }
@@ -790,13 +814,22 @@ extern "C" {
 int ekv_step_attend(const ekv_bank* bank, const ekv_step* st, const void* q, const void* k_new, const void* v_new,
                     void* out, int32_t* evict_ids, const float* rope_cos, const float* rope_sin, void* workspace,
                     size_t workspace_bytes, void* stream) {
-  return step_attend_impl(bank, st, q, k_new, v_new, out, evict_ids, rope_cos, rope_sin, workspace, workspace_bytes, stream);
+  return step_attend_impl(bank, st, EKV_DTYPE_F16, q, k_new, v_new, out, evict_ids, rope_cos, rope_sin, workspace, workspace_bytes,
+                          stream);
 }
 
-int ekv_step_check(const ekv_bank* bank, const ekv_step* st) {
-  EkvStepPlan P;
-  return ekv_plan_step(bank, st, &P);
+int ekv_step_attend_typed(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const void* q, const void* k_new,
+                          const void* v_new, void* out, int32_t* evict_ids, const float* rope_cos, const float* rope_sin,
+                          void* workspace, size_t workspace_bytes, void* stream) {
+  return step_attend_impl(bank, st, dtype, q, k_new, v_new, out, evict_ids, rope_cos, rope_sin, workspace, workspace_bytes, stream);
 }
+
+int ekv_step_check_typed(const ekv_bank* bank, const ekv_step* st, int32_t dtype) {
+  EkvStepPlan P;
+  return ekv_plan_step(bank, st, dtype, &P);
+}
+
+int ekv_step_check(const ekv_bank* bank, const ekv_step* st) { return ekv_step_check_typed(bank, st, EKV_DTYPE_F16); }
 
 int ekv_gather_ordered(const ekv_bank* bank, int32_t layer_begin, int32_t layer_count, int32_t n_slots, void* k_out,
                        void* v_out, void* stream) {

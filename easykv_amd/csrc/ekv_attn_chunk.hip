@@ -15,6 +15,14 @@ EKW_DECL(64, 0) EKW_DECL(64, 2) EKW_DECL(128, 0) EKW_DECL(128, 2)
 #define EKW_DECL(d, m) hipError_t ekv_launch_attn_wide_rope_d##d##_m##m(const EkvAttnArgs&, int, int, hipStream_t, const EkvScoreArgs*);
 EKW_DECL(64, 0) EKW_DECL(64, 2) EKW_DECL(128, 0) EKW_DECL(128, 2)
 #undef EKW_DECL
+// bf16 instances (plain keys only)
+#define EKV_DECL(d, m) hipError_t ekv_launch_attn_chunk_d##d##_m##m##_bf16(const EkvAttnArgs&, int, int, hipStream_t, const EkvScoreArgs*);
+EKV_DECL(32, 0) EKV_DECL(32, 1) EKV_DECL(32, 2) EKV_DECL(64, 0) EKV_DECL(64, 1) EKV_DECL(64, 2)
+EKV_DECL(96, 0) EKV_DECL(96, 1) EKV_DECL(96, 2) EKV_DECL(128, 0) EKV_DECL(128, 1) EKV_DECL(128, 2)
+#undef EKV_DECL
+#define EKW_DECL(d, m) hipError_t ekv_launch_attn_wide_d##d##_m##m##_bf16(const EkvAttnArgs&, int, int, hipStream_t, const EkvScoreArgs*);
+EKW_DECL(64, 0) EKW_DECL(64, 2) EKW_DECL(128, 0) EKW_DECL(128, 2)
+#undef EKW_DECL
 
 // Two-pass scheme (16x16 kernel: statistics pass + exact pass with in-kernel column sums, ekv_attn_chunk.inc; wide-block kernel: one
 // pass for output + row statistics, then a K-only column-sum pass, ekv_attn_wide.inc) for scored chunk
@@ -119,12 +127,13 @@ int ekv_attn_chunk_launches(bool wide, bool rope, bool two_pass, int passes) {
 }
 
 hipError_t ekv_launch_attn_chunk(const EkvAttnArgs& a, int head_dim, int layer_count, bool wide, bool two_pass, hipStream_t s,
-                                 const EkvScoreArgs* fuse_sc, int passes, const EkvScoreArgs* tail_sc) {
+                                 const EkvScoreArgs* fuse_sc, int passes, const EkvScoreArgs* tail_sc, bool bf16) {
   if (two_pass && (fuse_sc != nullptr || a.stats == nullptr || a.colsum == nullptr)) return hipErrorInvalidValue;
   if (tail_sc != nullptr && !(wide && two_pass && (passes & 2))) return hipErrorInvalidValue;
   int qb_rows, n_qblocks, qpw;
   ekv_chunk_blocks(a.n_q_heads / a.n_kv_heads, a.q_len, &qb_rows, &n_qblocks, &qpw);
   const bool rope = a.rope_cos != nullptr;
+  if (bf16 && rope) return hipErrorInvalidValue;   // (no bf16 RoPE-on-read build)
   if (rope && !wide) {      // (the wide-block kernel rotates its query rows itself, in the lane that holds them)
     if (a.q_rot_hi == nullptr || a.q_rot_lo == nullptr) return hipErrorInvalidValue;
     const int n_rows = a.n_q_heads * a.q_len, rpb = 256 / (head_dim / 4);
@@ -135,7 +144,8 @@ hipError_t ekv_launch_attn_chunk(const EkvAttnArgs& a, int head_dim, int layer_c
     const int nwq = qpw == 4 ? 4 : 2;
     // one pass over K and V (output, and for a scored step every row's softmax statistics), then — scored steps — the column-sum
     // pass over K
-#define EKW_GO(d, m, aa, shape, t) (rope ? ekv_launch_attn_wide_rope_d##d##_m##m(aa, shape, layer_count, s, t) : ekv_launch_attn_wide_d##d##_m##m(aa, shape, layer_count, s, t))
+#define EKW_GO(d, m, aa, shape, t) (bf16 ? ekv_launch_attn_wide_d##d##_m##m##_bf16(aa, shape, layer_count, s, t) :                  \
+                                   rope ? ekv_launch_attn_wide_rope_d##d##_m##m(aa, shape, layer_count, s, t) : ekv_launch_attn_wide_d##d##_m##m(aa, shape, layer_count, s, t))
     hipError_t e = hipSuccess;
     if (passes & 1) {
       // a launch of at most one workgroup per CU (a layer-per-call model) runs 65..128-row blocks on 128-key tiles, 8 waves
@@ -154,7 +164,8 @@ hipError_t ekv_launch_attn_chunk(const EkvAttnArgs& a, int head_dim, int layer_c
 #undef EKW_GO
     return e;
   }
-#define EKV_GO(d, m) ekv_launch_attn_chunk_d##d##_m##m(a, kernel_code(qpw, rope, m), layer_count, s, fuse_sc)
+#define EKV_GO(d, m) (bf16 ? ekv_launch_attn_chunk_d##d##_m##m##_bf16(a, kernel_code(qpw, rope, m), layer_count, s, fuse_sc)  \
+                          : ekv_launch_attn_chunk_d##d##_m##m(a, kernel_code(qpw, rope, m), layer_count, s, fuse_sc))
   hipError_t e = hipSuccess;
   switch (head_dim) {
     case 32: e = two_pass ? EKV_GO(32, 1) : EKV_GO(32, 0); if (two_pass && e == hipSuccess) e = EKV_GO(32, 2); break;
@@ -174,6 +185,9 @@ size_t ekv_chunk_lds_bytes_d128(int, int, int);
 hipError_t ekv_launch_chunk_lds_d32(const EkvAttnArgs&, const EkvScoreArgs&, int, hipStream_t);
 hipError_t ekv_launch_chunk_lds_d64(const EkvAttnArgs&, const EkvScoreArgs&, int, hipStream_t);
 hipError_t ekv_launch_chunk_lds_d128(const EkvAttnArgs&, const EkvScoreArgs&, int, hipStream_t);
+hipError_t ekv_launch_chunk_lds_d32_bf16(const EkvAttnArgs&, const EkvScoreArgs&, int, hipStream_t);
+hipError_t ekv_launch_chunk_lds_d64_bf16(const EkvAttnArgs&, const EkvScoreArgs&, int, hipStream_t);
+hipError_t ekv_launch_chunk_lds_d128_bf16(const EkvAttnArgs&, const EkvScoreArgs&, int, hipStream_t);
 
 // Eligible: a scored, accumulating chunk step (plain keys, score rows over the whole cache) with at most 8 GQA-folded query
 // rows whose logits fit LDS next to a second workgroup of the CU (<= 80 KB), one victim set per head.
@@ -192,11 +206,11 @@ bool ekv_chunk_lds_supported(const ekv_bank* bank, const ekv_step* st, int phys_
   return lds <= 80 * 1024;
 }
 
-hipError_t ekv_launch_chunk_lds(const EkvAttnArgs& a, const EkvScoreArgs& sc, int head_dim, int layer_count, hipStream_t s) {
+hipError_t ekv_launch_chunk_lds(const EkvAttnArgs& a, const EkvScoreArgs& sc, int head_dim, int layer_count, hipStream_t s, bool bf16) {
   switch (head_dim) {
-    case 32: return ekv_launch_chunk_lds_d32(a, sc, layer_count, s);
-    case 64: return ekv_launch_chunk_lds_d64(a, sc, layer_count, s);
-    case 128: return ekv_launch_chunk_lds_d128(a, sc, layer_count, s);
+    case 32: return (bf16 ? ekv_launch_chunk_lds_d32_bf16 : ekv_launch_chunk_lds_d32)(a, sc, layer_count, s);
+    case 64: return (bf16 ? ekv_launch_chunk_lds_d64_bf16 : ekv_launch_chunk_lds_d64)(a, sc, layer_count, s);
+    case 128: return (bf16 ? ekv_launch_chunk_lds_d128_bf16 : ekv_launch_chunk_lds_d128)(a, sc, layer_count, s);
   }
   return hipErrorInvalidValue;
 }

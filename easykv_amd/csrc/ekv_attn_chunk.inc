@@ -1,5 +1,6 @@
-// K2: strided-prefill chunk attention (q_len = n > 1) over the retained slots, MFMA 16x16x32 f16.
-// Compiled once per EKV_D by the ekv_attn_chunk_d*.hip stubs.
+// K2: strided-prefill chunk attention (q_len = n > 1) over the retained slots, MFMA 16x16x32 f16 / bf16.
+// Compiled once per (EKV_D, EKV_CHUNK_MODE, element type) by the ekv_attn_chunk_d*.hip stubs; the bf16 instances (EKV_BF16)
+// build plain keys only (the hi / lo fp16 planes of RoPE-on-read are fp16 by design).
 //
 // Replaces easykv/llama_patch.py:198-222 (mistral_patch.py:144-169) for q_len = stride (and the dense
 // prefix prefill, q_len = r_idx), the K/V append of DynamicCache.update (llama_patch.py:193-196) and,
@@ -31,6 +32,9 @@
 
 #include "ekv_common.h"
 #include "ekv_kernels.h"
+#if EKV_BF16   // (bf16 instances: the same kernel under a tagged name)
+#define ekv_attn_chunk_kernel ekv_attn_chunk_kernel_bf16
+#endif
 
 #if EKV_CHUNK_MODE == 0
 // FUSE: an unsplit head's scorer (exact softmax of the exported logits, accumulate, select, compaction) runs as the tail of the
@@ -114,16 +118,16 @@ __global__ void __launch_bounds__(64 * NW, (NW == 16 || (NW == 8 && EKV_CHUNK_MO
   constexpr int PS = D + 2;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   int32_t* s_slot = reinterpret_cast<int32_t*>(smem);
-  _Float16* sK = reinterpret_cast<_Float16*>(smem + ekv_align((size_t)a.rows_per_split * 4, 16));
-  _Float16* sV = sK + kKT * RS;
-  _Float16* sKl = sV + (MODE == 1 ? 0 : kKT * RS);   // (the statistics pass stages no V tile)  ROPE only: low part of the rotated keys (k' = hi + lo, ~2^-21 relative)
+  ekv_e* sK = reinterpret_cast<ekv_e*>(smem + ekv_align((size_t)a.rows_per_split * 4, 16));
+  ekv_e* sV = sK + kKT * RS;
+  ekv_e* sKl = sV + (MODE == 1 ? 0 : kKT * RS);   // (the statistics pass stages no V tile)  ROPE only: low part of the rotated keys (k' = hi + lo, ~2^-21 relative)
   // The query block lives in LDS (or, for the 1-tile variant, in registers) for the whole kernel.  Loading the Q operands
   // from global memory inside the tile loop is doubly bad: vmcnt retires in order, so waiting for a Q operand also waits
   // for the K/V tile prefetched just before it (no overlap left), and a 128-row block does not even fit L1.
   constexpr bool Q_LDS = EKV_Q_LDS(QPW, ROPE, NW);   // otherwise the Q operands stay in registers (Q_REG below)
   constexpr int QROWS = 16 * QPW * NWQ;
-  _Float16* sQh = sKl + (ROPE ? kKT * RS : 0);
-  _Float16* sQl = sQh + QROWS * RS;   // ROPE only
+  ekv_e* sQh = sKl + (ROPE ? kKT * RS : 0);
+  ekv_e* sQl = sQh + QROWS * RS;   // ROPE only
 
   const int n = a.q_len, T = a.n_slots;
   const int rep = a.n_q_heads / a.n_kv_heads;
@@ -326,8 +330,8 @@ __global__ void __launch_bounds__(64 * NW, (NW == 16 || (NW == 8 && EKV_CHUNK_MO
         for (int e = 0; e < 8; ++e) {
           const float rh = (sub < PPR / 2) ? -(float)o8[e] : (float)o8[e];
           const float kr = (float)x[e] * cs[e] + rh * sn[e];
-          y[e] = (_Float16)kr;
-          yl[e] = (_Float16)(kr - (float)y[e]);
+          y[e] = (ekv_e)kr;
+          yl[e] = (ekv_e)(kr - (float)y[e]);
         }
         kv = __builtin_bit_cast(uint4, y);
         if (live) *reinterpret_cast<uint4*>(sKl + row * RS + sub * 8) = __builtin_bit_cast(uint4, yl);
@@ -373,13 +377,13 @@ __global__ void __launch_bounds__(64 * NW, (NW == 16 || (NW == 8 && EKV_CHUNK_MO
               bq = qreg[t][kb];
               if (ROPE) bql = qreg_lo[t][kb];
             }
-            S[t][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a0, bq, S[t][0], 0, 0, 0);
-            S[t][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1, bq, S[t][1], 0, 0, 0);
+            S[t][0] = EKV_MFMA_16x16x32(a0, bq, S[t][0], 0, 0, 0);
+            S[t][1] = EKV_MFMA_16x16x32(a1, bq, S[t][1], 0, 0, 0);
             if (ROPE) {   // (kh + kl).(qh + ql) ~= kh.qh + kh.ql + kl.qh
-              S[t][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a0, bql, S[t][0], 0, 0, 0);
-              S[t][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1, bql, S[t][1], 0, 0, 0);
-              S[t][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(l0, bq, S[t][0], 0, 0, 0);
-              S[t][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(l1, bq, S[t][1], 0, 0, 0);
+              S[t][0] = EKV_MFMA_16x16x32(a0, bql, S[t][0], 0, 0, 0);
+              S[t][1] = EKV_MFMA_16x16x32(a1, bql, S[t][1], 0, 0, 0);
+              S[t][0] = EKV_MFMA_16x16x32(l0, bq, S[t][0], 0, 0, 0);
+              S[t][1] = EKV_MFMA_16x16x32(l1, bq, S[t][1], 0, 0, 0);
             }
           }
         }
@@ -444,11 +448,11 @@ __global__ void __launch_bounds__(64 * NW, (NW == 16 || (NW == 8 && EKV_CHUNK_MO
             const ekv_f2 arg = __builtin_elementwise_fma(ekv_f2{sv[e], sv[e + 1]}, c2, nm2);
             const ekv_f2 p2 = ekv_f2{__builtin_amdgcn_exp2f(arg[0]), __builtin_amdgcn_exp2f(arg[1])} * il2;
             lsv += p2;
-            bP[e] = (_Float16)p2[0];
-            bP[e + 1] = (_Float16)p2[1];
+            bP[e] = (ekv_e)p2[0];
+            bP[e + 1] = (ekv_e)p2[1];
             if (EKV_CHUNK_PSPLIT) {
-              bPl[e] = (_Float16)(p2[0] - (float)bP[e]);
-              bPl[e + 1] = (_Float16)(p2[1] - (float)bP[e + 1]);
+              bPl[e] = (ekv_e)(p2[0] - (float)bP[e]);
+              bPl[e + 1] = (ekv_e)(p2[1] - (float)bP[e + 1]);
             }
             // sum over the rep query heads of the query: they sit in adjacent lanes (c = i*rep + r)
             ekv_f2 vb = p2;
@@ -480,11 +484,11 @@ __global__ void __launch_bounds__(64 * NW, (NW == 16 || (NW == 8 && EKV_CHUNK_MO
             const ekv_f2 arg = __builtin_elementwise_fma(ekv_f2{sv[e], sv[e + 1]}, c2, nm2);
             const ekv_f2 p2 = {__builtin_amdgcn_exp2f(arg[0]), __builtin_amdgcn_exp2f(arg[1])};
             lsv += p2;
-            bP[e] = (_Float16)p2[0];
-            bP[e + 1] = (_Float16)p2[1];
+            bP[e] = (ekv_e)p2[0];
+            bP[e + 1] = (ekv_e)p2[1];
             if (EKV_CHUNK_PSPLIT) {
-              bPl[e] = (_Float16)(p2[0] - (float)bP[e]);
-              bPl[e + 1] = (_Float16)(p2[1] - (float)bP[e + 1]);
+              bPl[e] = (ekv_e)(p2[0] - (float)bP[e]);
+              bPl[e + 1] = (ekv_e)(p2[1] - (float)bP[e + 1]);
             }
           }
           l_run[t] = l_run[t] * alpha + (lsv[0] + lsv[1]);
@@ -513,16 +517,16 @@ __global__ void __launch_bounds__(64 * NW, (NW == 16 || (NW == 8 && EKV_CHUNK_MO
           // two transposing LDS reads (ds_read_b64_tr_b16: the 16 lanes of group g fetch the 4-key x 16-column block of rows
           // 4g .. 4g+3 row-wise, 8 bytes each, and lane c receives column c) instead of eight ds_read_u16 gathers
           typedef short ekv_s4 __attribute__((ext_vector_type(4)));
-          typedef _Float16 ekv_h4 __attribute__((ext_vector_type(4)));
-          const _Float16* vp = sV + (kg + 4 * g + (c >> 2)) * RS + db * 16 + 4 * (c & 3);
+          typedef ekv_e ekv_h4 __attribute__((ext_vector_type(4)));
+          const ekv_e* vp = sV + (kg + 4 * g + (c >> 2)) * RS + db * 16 + 4 * (c & 3);
           const ekv_h4 v_lo = __builtin_bit_cast(ekv_h4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) ekv_s4*)vp));
           const ekv_h4 v_hi = __builtin_bit_cast(ekv_h4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) ekv_s4*)(vp + 16 * RS)));
           const ekv_h8 aV = {v_lo[0], v_lo[1], v_lo[2], v_lo[3], v_hi[0], v_hi[1], v_hi[2], v_hi[3]};
 #pragma unroll
           for (int t = 0; t < QPW; ++t) {
             if ((wq + NWQ * t) * 16 >= NR) continue;   // wave-uniform
-            oacc[t][db] = __builtin_amdgcn_mfma_f32_16x16x32_f16(aV, bPs[t], oacc[t][db], 0, 0, 0);
-            if (EKV_CHUNK_PSPLIT) oacc[t][db] = __builtin_amdgcn_mfma_f32_16x16x32_f16(aV, bPls[t], oacc[t][db], 0, 0, 0);
+            oacc[t][db] = EKV_MFMA_16x16x32(aV, bPs[t], oacc[t][db], 0, 0, 0);
+            if (EKV_CHUNK_PSPLIT) oacc[t][db] = EKV_MFMA_16x16x32(aV, bPls[t], oacc[t][db], 0, 0, 0);
           }
         }
       }
@@ -631,10 +635,10 @@ __global__ void __launch_bounds__(64 * NW, (NW == 16 || (NW == 8 && EKV_CHUNK_MO
         __half* orow = a.out_direct + (size_t)ll * a.n_q_heads * n * D + (size_t)(h * rep + row_r[t]) * a.o_hs + (size_t)row_i[t] * a.o_ts;
 #pragma unroll
         for (int db = 0; db < DB; ++db) {
-          __half2 lo = __floats2half2_rn((oacc[t][db][0] * w0 + mine[2 + db * 4 + 0] * w1) * inv,
-                                         (oacc[t][db][1] * w0 + mine[2 + db * 4 + 1] * w1) * inv);
-          __half2 hi = __floats2half2_rn((oacc[t][db][2] * w0 + mine[2 + db * 4 + 2] * w1) * inv,
-                                         (oacc[t][db][3] * w0 + mine[2 + db * 4 + 3] * w1) * inv);
+          __half2 lo = ekv_to_e2((oacc[t][db][0] * w0 + mine[2 + db * 4 + 0] * w1) * inv,
+                                 (oacc[t][db][1] * w0 + mine[2 + db * 4 + 1] * w1) * inv);
+          __half2 hi = ekv_to_e2((oacc[t][db][2] * w0 + mine[2 + db * 4 + 2] * w1) * inv,
+                                 (oacc[t][db][3] * w0 + mine[2 + db * 4 + 3] * w1) * inv);
           uint2 pk;
           pk.x = __builtin_bit_cast(unsigned int, lo);
           pk.y = __builtin_bit_cast(unsigned int, hi);
@@ -716,16 +720,18 @@ hipError_t launch_k(const EkvAttnArgs& a, int layer_count, hipStream_t s, const 
 #define EKV_CAT(a, b) EKV_CAT_(a, b)
 
 // rows per query block = rep * qb_rows <= 32 * qpw
-#define EKV_CAT3(a, b, c, d) a##b##c##d
-#define EKV_CAT4(a, b, c, d) EKV_CAT3(a, b, c, d)
-hipError_t EKV_CAT4(ekv_launch_attn_chunk_d, EKV_D, _m, EKV_CHUNK_MODE)(const EkvAttnArgs& a, int qpw, int layer_count, hipStream_t s,
-                                                                        const EkvScoreArgs* fuse_sc) {
+#define EKV_CAT3(a, b, c, d, t) a##b##c##d##t
+#define EKV_CAT4(a, b, c, d, t) EKV_CAT3(a, b, c, d, t)
+hipError_t EKV_CAT4(ekv_launch_attn_chunk_d, EKV_D, _m, EKV_CHUNK_MODE, EKV_DT_TAG)(const EkvAttnArgs& a, int qpw, int layer_count, hipStream_t s,
+                                                                                    const EkvScoreArgs* fuse_sc) {
   const bool rope = a.rope_cos != nullptr;
+  constexpr bool R = !EKV_BF16;   // (RoPE-on-read builds: fp16 only)
+  if (rope && !R) return hipErrorInvalidValue;
   switch (qpw) {
-    case 1: return rope ? launch_k<1, true, 4>(a, layer_count, s, fuse_sc) : launch_k<1, false, 4>(a, layer_count, s, fuse_sc);
-    case 2: return rope ? launch_k<2, true, 4>(a, layer_count, s, fuse_sc) : launch_k<2, false, 4>(a, layer_count, s, fuse_sc);
+    case 1: return rope ? launch_k<1, R, 4>(a, layer_count, s, fuse_sc) : launch_k<1, false, 4>(a, layer_count, s, fuse_sc);
+    case 2: return rope ? launch_k<2, R, 4>(a, layer_count, s, fuse_sc) : launch_k<2, false, 4>(a, layer_count, s, fuse_sc);
     case 4: if (fuse_sc != nullptr) return hipErrorInvalidValue;   // the fused scorer is the 256-thread build
-      return rope ? launch_k<2, true, 8>(a, layer_count, s, nullptr) : launch_k<2, false, 8>(a, layer_count, s, nullptr);   // 8 waves x 2 tiles
+      return rope ? launch_k<2, R, 8>(a, layer_count, s, nullptr) : launch_k<2, false, 8>(a, layer_count, s, nullptr);   // 8 waves x 2 tiles
 #if EKV_CHUNK_MODE == 0
     case 8: if (fuse_sc != nullptr || rope) return hipErrorInvalidValue;   // 16 waves x 1 tile: four waves per SIMD (ekv_attn_chunk.hip)
       return launch_k<1, false, 16>(a, layer_count, s, nullptr);

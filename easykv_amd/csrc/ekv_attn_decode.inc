@@ -18,6 +18,10 @@
 // Compiled once per (EKV_D, EKV_ROPE) by the ekv_attn_decode_d*.hip stubs so the objects build in parallel.
 #include "ekv_decode_stream.h"
 #include "ekv_decode_tail.h"
+#if EKV_BF16   // (bf16 instances: the same kernels under tagged names)
+#define ekv_attn_decode_kernel ekv_attn_decode_kernel_bf16
+#define ekv_decode_fused_kernel ekv_decode_fused_kernel_bf16
+#endif
 #ifndef EKV_SPLIT_KU
 #define EKV_SPLIT_KU 8
 #endif
@@ -120,7 +124,7 @@ __global__ void __launch_bounds__(256) ekv_attn_decode_kernel(const EkvAttnArgs 
   for (int idx = tid; idx < nrep * D; idx += 256) {      // (the in-kernel fold is only used with ONE query-head group per KV head)
     const int r = idx / D, d = idx % D;
     const size_t row = (size_t)ll * a.n_q_heads + hq0 + r;
-    a.out_direct[row * D + d] = __float2half(ekv_fold_partials_buf_auto(rsrc, (unsigned)((hq0 + r) * a.n_split * Gm::PS), a.n_split, Gm::PS, d));
+    a.out_direct[row * D + d] = ekv_to_e(ekv_fold_partials_buf_auto(rsrc, (unsigned)((hq0 + r) * a.n_split * Gm::PS), a.n_split, Gm::PS, d));
   }
 }
 
@@ -236,7 +240,7 @@ __global__ void __launch_bounds__(64 * NW, (NW >= 8 ? (REP == 1 ? 2 : 1) : (SLOT
     const int r = idx / D, d = idx % D;
     float mm, ls, os;
     ekv_decode_reduce<D, REP, NW>(s_part, r, d, mm, ls, os);
-    sc.out[((size_t)ll * a.n_q_heads + h * nrep + r) * D + d] = __float2half(os / ls);
+    sc.out[((size_t)ll * a.n_q_heads + h * nrep + r) * D + d] = ekv_to_e(os / ls);
   }
 
   // scratch of the roco select: histogram behind the dead-row bits; the candidate list reuses the wave partials (dead by now,
@@ -324,9 +328,9 @@ hipError_t launch_fused(const EkvAttnArgs& a, const EkvScoreArgs& sc, int layer_
 
 }  // namespace
 
-#define EKV_CAT_(a, b, c) a##b##_##c
-#define EKV_CAT(a, b, c) EKV_CAT_(a, b, c)
-#define EKV_SYM(name) EKV_CAT(name, EKV_D, EKV_ROPE_TAG)
+#define EKV_CAT_(a, b, c, t) a##b##_##c##t
+#define EKV_CAT(a, b, c, t) EKV_CAT_(a, b, c, t)
+#define EKV_SYM(name) EKV_CAT(name, EKV_D, EKV_ROPE_TAG, EKV_DT_TAG)
 
 hipError_t EKV_SYM(ekv_launch_attn_decode_d)(const EkvAttnArgs& a, int rep, int layer_count, hipStream_t s) {
   if (rep < 1) return hipErrorInvalidValue;
@@ -349,6 +353,7 @@ hipError_t EKV_SYM(ekv_launch_decode_fused_d)(const EkvAttnArgs& a, const EkvSco
   }
 }
 
+#if !EKV_BF16   // (the LDS layout does not depend on the element type)
 size_t EKV_SYM(ekv_fused_lds_d)(int rep, int t_pad, int l_pad, int nw) {
   switch (rep) {
     case 1: return nw == 8 ? fused_lds<1, 8>(t_pad, l_pad, 3) : fused_lds<1, 4>(t_pad, l_pad, 3);
@@ -357,3 +362,4 @@ size_t EKV_SYM(ekv_fused_lds_d)(int rep, int t_pad, int l_pad, int nw) {
     default: return nw == 8 ? fused_lds<8, 8>(t_pad, l_pad, 3) : fused_lds<8, 4>(t_pad, l_pad, 3);
   }
 }
+#endif

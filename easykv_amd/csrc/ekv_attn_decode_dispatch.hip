@@ -28,23 +28,33 @@ size_t ekv_fused_lds_d128_plain(int, int, int, int);
 hipError_t ekv_launch_attn_decode_d128_rope(const EkvAttnArgs&, int, int, hipStream_t);
 hipError_t ekv_launch_decode_fused_d128_rope(const EkvAttnArgs&, const EkvScoreArgs&, int, int, int, hipStream_t);
 size_t ekv_fused_lds_d128_rope(int, int, int, int);
+hipError_t ekv_launch_attn_decode_d32_plain_bf16(const EkvAttnArgs&, int, int, hipStream_t);
+hipError_t ekv_launch_decode_fused_d32_plain_bf16(const EkvAttnArgs&, const EkvScoreArgs&, int, int, int, hipStream_t);
+hipError_t ekv_launch_attn_decode_d64_plain_bf16(const EkvAttnArgs&, int, int, hipStream_t);
+hipError_t ekv_launch_decode_fused_d64_plain_bf16(const EkvAttnArgs&, const EkvScoreArgs&, int, int, int, hipStream_t);
+hipError_t ekv_launch_attn_decode_d96_plain_bf16(const EkvAttnArgs&, int, int, hipStream_t);
+hipError_t ekv_launch_decode_fused_d96_plain_bf16(const EkvAttnArgs&, const EkvScoreArgs&, int, int, int, hipStream_t);
+hipError_t ekv_launch_attn_decode_d128_plain_bf16(const EkvAttnArgs&, int, int, hipStream_t);
+hipError_t ekv_launch_decode_fused_d128_plain_bf16(const EkvAttnArgs&, const EkvScoreArgs&, int, int, int, hipStream_t);
 
 // any GQA factor (repeat_kv, llama_patch.py:19-29): factors <= 8 on the build of the next power of two, wider ones in groups of 8
 bool ekv_attn_decode_supported(int head_dim, int rep) {
   return (head_dim == 32 || head_dim == 64 || head_dim == 96 || head_dim == 128) && rep >= 1;
 }
 
-#define EKV_DISPATCH(fn, ...)                                                    \
-  switch (head_dim) {                                                            \
-    case 32: return rope ? fn##32_rope(__VA_ARGS__) : fn##32_plain(__VA_ARGS__);  \
-    case 64: return rope ? fn##64_rope(__VA_ARGS__) : fn##64_plain(__VA_ARGS__);  \
-    case 96: return rope ? fn##96_rope(__VA_ARGS__) : fn##96_plain(__VA_ARGS__);  \
-    case 128: return rope ? fn##128_rope(__VA_ARGS__) : fn##128_plain(__VA_ARGS__); \
+// (bf16: plain keys only — the planner refuses RoPE-on-read steps of a bf16 bank)
+#define EKV_DISPATCH(fn, ...)                                                                                      \
+  switch (head_dim) {                                                                                              \
+    case 32: return bf16 ? fn##32_plain_bf16(__VA_ARGS__) : rope ? fn##32_rope(__VA_ARGS__) : fn##32_plain(__VA_ARGS__);    \
+    case 64: return bf16 ? fn##64_plain_bf16(__VA_ARGS__) : rope ? fn##64_rope(__VA_ARGS__) : fn##64_plain(__VA_ARGS__);    \
+    case 96: return bf16 ? fn##96_plain_bf16(__VA_ARGS__) : rope ? fn##96_rope(__VA_ARGS__) : fn##96_plain(__VA_ARGS__);    \
+    case 128: return bf16 ? fn##128_plain_bf16(__VA_ARGS__) : rope ? fn##128_rope(__VA_ARGS__) : fn##128_plain(__VA_ARGS__); \
   }
 
-hipError_t ekv_launch_attn_decode(const EkvAttnArgs& a, int head_dim, int layer_count, hipStream_t s) {
+hipError_t ekv_launch_attn_decode(const EkvAttnArgs& a, int head_dim, int layer_count, hipStream_t s, bool bf16) {
   const int rep = a.n_q_heads / a.n_kv_heads;
   const bool rope = a.rope_cos != nullptr;
+  if (bf16 && rope) return hipErrorInvalidValue;
   EKV_DISPATCH(ekv_launch_attn_decode_d, a, rep, layer_count, s)
   return hipErrorInvalidValue;
 }
@@ -71,9 +81,10 @@ bool ekv_decode_fused_supported(int head_dim, int rep, int n_slots, int t_pad, i
 }
 
 hipError_t ekv_launch_decode_fused(const EkvAttnArgs& a, const EkvScoreArgs& sc, int head_dim, int layer_count, int nw,
-                                   hipStream_t s) {
+                                   hipStream_t s, bool bf16) {
   const int rep = a.n_q_heads / a.n_kv_heads;
   const bool rope = a.rope_cos != nullptr;
+  if (bf16 && rope) return hipErrorInvalidValue;
   EKV_DISPATCH(ekv_launch_decode_fused_d, a, sc, rep, layer_count, nw, s)
   return hipErrorInvalidValue;
 }

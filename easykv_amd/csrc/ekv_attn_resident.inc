@@ -41,6 +41,9 @@
 
 #include "ekv_common.h"
 #include "ekv_kernels.h"
+#if EKV_BF16   // (bf16 instance: the same kernel under a tagged name)
+#define ekv_attn_resident_kernel ekv_attn_resident_kernel_bf16
+#endif
 
 #define EKV_SS_NT 512
 #define EKV_SS_DEVICE_ONLY
@@ -52,7 +55,7 @@ namespace {
 typedef float ekr_f16v __attribute__((ext_vector_type(16)));
 typedef short ekr_s4 __attribute__((ext_vector_type(4)));
 typedef float ekr_f4 __attribute__((ext_vector_type(4)));
-typedef _Float16 ekr_h4 __attribute__((ext_vector_type(4)));
+typedef ekv_e ekr_h4 __attribute__((ext_vector_type(4)));
 
 constexpr int R_D = 128, R_NT = 512, R_TK = 128, R_NB = 3, R_MAXT = 10;      // R_MAXT: 32 x 32 logit blocks a wave keeps (160 registers)
 constexpr int R_RS = 2 * R_D;                         // bytes per K / V row in LDS (unpadded, XOR-swizzled 16-byte chunks)
@@ -233,7 +236,7 @@ __global__ void __launch_bounds__(R_NT, 1) ekv_attn_resident_kernel(const EkvAtt
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks) {
         const ekv_h8 kf = *reinterpret_cast<const ekv_h8*>(kbase + (((2 * ks + hi) ^ ksw_l) << 4));
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(qreg[ks], kf, acc, 0, 0, 0);      // S[q][key]
+        acc = EKV_MFMA_32x32x16(qreg[ks], kf, acc, 0, 0, 0);      // S[q][key]
       }
       // register r <-> row rbase + (r&3) + 8*(r>>2) + 4*hi, key = lane.  Tiles that reach the chunk's own positions or the end of the
       // range take the causal / range mask: key j is visible to token i iff j <= t_new + i
@@ -305,7 +308,7 @@ __global__ void __launch_bounds__(R_NT, 1) ekv_attn_resident_kernel(const EkvAtt
         }
 #pragma unroll
         for (int q4 = 0; q4 < 4; ++q4)
-          *reinterpret_cast<ekr_h4*>(pw + 16 * q4) = ekr_h4{(_Float16)s[b][4 * q4], (_Float16)s[b][4 * q4 + 1], (_Float16)s[b][4 * q4 + 2], (_Float16)s[b][4 * q4 + 3]};
+          *reinterpret_cast<ekr_h4*>(pw + 16 * q4) = ekr_h4{(ekv_e)s[b][4 * q4], (ekv_e)s[b][4 * q4 + 1], (ekv_e)s[b][4 * q4 + 2], (ekv_e)s[b][4 * q4 + 3]};
       }
       // (the P^T tile does not depend on the stream: written before the wait for the V tile)
       if (u + 1 < n_items) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
@@ -327,7 +330,7 @@ __global__ void __launch_bounds__(R_NT, 1) ekv_attn_resident_kernel(const EkvAtt
         const ekr_h4 p_hi = __builtin_bit_cast(ekr_h4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) ekr_s4*)(pp + 8 * PSTR)));
         const ekv_h8 aV = {v_lo[0], v_lo[1], v_lo[2], v_lo[3], v_hi[0], v_hi[1], v_hi[2], v_hi[3]};
         const ekv_h8 bP = {p_lo[0], p_lo[1], p_lo[2], p_lo[3], p_hi[0], p_hi[1], p_hi[2], p_hi[3]};
-        oacc = __builtin_amdgcn_mfma_f32_32x32x16_f16(aV, bP, oacc, 0, 0, 0);
+        oacc = EKV_MFMA_32x32x16(aV, bP, oacc, 0, 0, 0);
       }
     }
   }
@@ -479,8 +482,8 @@ __global__ void __launch_bounds__(R_NT, 1) ekv_attn_resident_kernel(const EkvAtt
       __half* orow = a.out_direct + (size_t)ll * a.n_q_heads * n * D + (size_t)(h * rep + rowE % rep) * a.o_hs + (size_t)(rowE / rep) * a.o_ts;
 #pragma unroll
       for (int q4 = 0; q4 < 4; ++q4) {
-        const __half2 lo = __floats2half2_rn(oacc[4 * q4] * il, oacc[4 * q4 + 1] * il);
-        const __half2 hh = __floats2half2_rn(oacc[4 * q4 + 2] * il, oacc[4 * q4 + 3] * il);
+        const __half2 lo = ekv_to_e2(oacc[4 * q4] * il, oacc[4 * q4 + 1] * il);
+        const __half2 hh = ekv_to_e2(oacc[4 * q4 + 2] * il, oacc[4 * q4 + 3] * il);
         uint2 pk;
         pk.x = __builtin_bit_cast(unsigned int, lo);
         pk.y = __builtin_bit_cast(unsigned int, hh);
@@ -514,21 +517,7 @@ hipError_t launch_resident_rep(const EkvAttnArgs& a, const EkvScoreArgs& sc, int
   return lng ? launch_resident<REP, true>(a, sc, layer_count, s) : launch_resident<REP, false>(a, sc, layer_count, s);
 }
 
-}  // namespace
-
-// Which steps: a whole scored chunk step (roco / h2o_head, accumulating) of an unsplit head on plain keys, head_dim 128, GQA factor
-// 1 / 2 / 4 / 8, 9..64 folded rows in one query block (fewer: the logits-in-LDS kernel) against at most 1280 keys, or at most 32 rows against
-// at most 2560 keys.
-bool ekv_attn_resident_supported(int head_dim, int rep, int q_len, int n_slots, int W) {
-  static const bool off = [] { const char* e = std::getenv("EKV_NO_RESIDENT"); return e != nullptr && e[0] == '1'; }();     // (A/B switch)
-  static const int min_rows = [] { const char* e = std::getenv("EKV_RESIDENT_MIN_ROWS"); return e != nullptr ? std::atoi(e) : 9; }();      // (A/B switch; see the header)
-  const int rows = rep * q_len;
-  const bool shape = (rows <= 64 && n_slots <= RL<false>::TMAX) || (rows <= 32 && n_slots <= RL<true>::TMAX);      // (LONG = false / true)
-  return !off && head_dim == R_D && (rep == 1 || rep == 2 || rep == 4 || rep == 8) && rows >= min_rows && shape && n_slots >= q_len && W >= 1 &&
-         W <= n_slots && ekw_tail_lds_bytes(W) <= (size_t)RL<false>::OFF_P;
-}
-
-hipError_t ekv_launch_attn_resident(const EkvAttnArgs& a, const EkvScoreArgs& sc, int layer_count, hipStream_t s) {
+hipError_t launch_resident_any(const EkvAttnArgs& a, const EkvScoreArgs& sc, int layer_count, hipStream_t s) {
   if (a.out_direct == nullptr) return hipErrorInvalidValue;
   switch (a.n_q_heads / a.n_kv_heads) {
     case 1: return launch_resident_rep<1>(a, sc, layer_count, s);
@@ -538,3 +527,29 @@ hipError_t ekv_launch_attn_resident(const EkvAttnArgs& a, const EkvScoreArgs& sc
     default: return hipErrorInvalidValue;
   }
 }
+
+}  // namespace
+
+// Which steps: a whole scored chunk step (roco / h2o_head, accumulating) of an unsplit head on plain keys, head_dim 128, GQA factor
+// 1 / 2 / 4 / 8, 9..64 folded rows in one query block (fewer: the logits-in-LDS kernel) against at most 1280 keys, or at most 32 rows against
+// at most 2560 keys.
+#if EKV_BF16
+hipError_t ekv_launch_attn_resident_bf16(const EkvAttnArgs& a, const EkvScoreArgs& sc, int layer_count, hipStream_t s) {
+  return launch_resident_any(a, sc, layer_count, s);
+}
+#else
+hipError_t ekv_launch_attn_resident_bf16(const EkvAttnArgs& a, const EkvScoreArgs& sc, int layer_count, hipStream_t s);
+
+bool ekv_attn_resident_supported(int head_dim, int rep, int q_len, int n_slots, int W) {
+  static const bool off = [] { const char* e = std::getenv("EKV_NO_RESIDENT"); return e != nullptr && e[0] == '1'; }();     // (A/B switch)
+  static const int min_rows = [] { const char* e = std::getenv("EKV_RESIDENT_MIN_ROWS"); return e != nullptr ? std::atoi(e) : 9; }();      // (A/B switch; see the header)
+  const int rows = rep * q_len;
+  const bool shape = (rows <= 64 && n_slots <= RL<false>::TMAX) || (rows <= 32 && n_slots <= RL<true>::TMAX);      // (LONG = false / true)
+  return !off && head_dim == R_D && (rep == 1 || rep == 2 || rep == 4 || rep == 8) && rows >= min_rows && shape && n_slots >= q_len && W >= 1 &&
+         W <= n_slots && ekw_tail_lds_bytes(W) <= (size_t)RL<false>::OFF_P;
+}
+
+hipError_t ekv_launch_attn_resident(const EkvAttnArgs& a, const EkvScoreArgs& sc, int layer_count, hipStream_t s, bool bf16) {
+  return bf16 ? ekv_launch_attn_resident_bf16(a, sc, layer_count, s) : launch_resident_any(a, sc, layer_count, s);
+}
+#endif

@@ -52,6 +52,10 @@
 
 #include "ekv_common.h"
 #include "ekv_kernels.h"
+#if EKV_BF16   // (bf16 instances, plain keys only: the same kernel under a tagged name)
+static_assert(!EKV_WIDE_ROPE, "RoPE-on-read keeps hi / lo fp16 planes: no bf16 build");
+#define ekv_attn_wide_kernel ekv_attn_wide_kernel_bf16
+#endif
 
 #define EKW_HAS_TAIL (EKV_WIDE_MODE == 2 && !EKV_WIDE_ROPE)      // (RoPE-on-read steps keep the stand-alone scorer: ekv_wide_tail.h)
 #if EKW_HAS_TAIL
@@ -67,7 +71,7 @@ namespace {
 typedef float ekv_f16v __attribute__((ext_vector_type(16)));
 typedef short ekv_s4 __attribute__((ext_vector_type(4)));
 typedef float ekv_f4w __attribute__((ext_vector_type(4)));
-typedef _Float16 ekv_h4 __attribute__((ext_vector_type(4)));
+typedef ekv_e ekv_h4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ float ekw_max3(float x, float y, float z) {
   float r;
@@ -332,10 +336,10 @@ __global__ void __launch_bounds__(64 * NWQ * NWK, EKV_WIDE_MODE == 2 ? (EKV_WIDE
             const float cv = e < 4 ? c0[e & 3] : c1[e & 3], sv = e < 4 ? s0[e & 3] : s1[e & 3];
             const float lo_ = (float)x[e] * cv + (-(float)y[e]) * sv;
             const float hi_ = (float)y[e] * cv + (float)x[e] * sv;
-            xh[e] = (_Float16)lo_;
-            xl[e] = (_Float16)(lo_ - (float)xh[e]);
-            yh[e] = (_Float16)hi_;
-            yl[e] = (_Float16)(hi_ - (float)yh[e]);
+            xh[e] = (ekv_e)lo_;
+            xl[e] = (ekv_e)(lo_ - (float)xh[e]);
+            yh[e] = (ekv_e)hi_;
+            yl[e] = (ekv_e)(hi_ - (float)yh[e]);
           }
           qreg[ks] = xh;
           qlo[ks] = xl;
@@ -520,10 +524,10 @@ __global__ void __launch_bounds__(64 * NWQ * NWK, EKV_WIDE_MODE == 2 ? (EKV_WIDE
             const float sv = kRotCls ? sv0 * rot_sgn : sv0;
             const float lo_ = (float)x[e] * cv + (-(float)y[e]) * sv;
             const float hi_ = (float)y[e] * cv + (float)x[e] * sv;
-            xh[e] = (_Float16)lo_;
-            xl[e] = (_Float16)(lo_ - (float)xh[e]);
-            yh[e] = (_Float16)hi_;
-            yl[e] = (_Float16)(hi_ - (float)yh[e]);
+            xh[e] = (ekv_e)lo_;
+            xl[e] = (ekv_e)(lo_ - (float)xh[e]);
+            yh[e] = (ekv_e)hi_;
+            yl[e] = (ekv_e)(hi_ - (float)yh[e]);
           }
           *reinterpret_cast<ekv_h8*>(krow + plow * 16) = xh;
           *reinterpret_cast<ekv_h8*>(krow + (plow ^ HC) * 16) = yh;
@@ -602,23 +606,23 @@ __global__ void __launch_bounds__(64 * NWQ * NWK, EKV_WIDE_MODE == 2 ? (EKV_WIDE
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
-          if (MODE == 2) s[kb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(qreg[ks], kfv[ks], s[kb], 0, 0, 0);
-          else s[kb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kfv[ks], qreg[ks], s[kb], 0, 0, 0);
+          if (MODE == 2) s[kb] = EKV_MFMA_32x32x16(qreg[ks], kfv[ks], s[kb], 0, 0, 0);
+          else s[kb] = EKV_MFMA_32x32x16(kfv[ks], qreg[ks], s[kb], 0, 0, 0);
         }
 #else
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
           const ekv_h8 kf = *reinterpret_cast<const ekv_h8*>(kbase + (((2 * ((EKW_DM & 8) ? 0 : ks) + hi) ^ ksw_l) << 4));
-          if (MODE == 2) s[kb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(qreg[ks], kf, s[kb], 0, 0, 0);   // S[q][key]
-          else s[kb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qreg[ks], s[kb], 0, 0, 0);            // S^T[key][q]
+          if (MODE == 2) s[kb] = EKV_MFMA_32x32x16(qreg[ks], kf, s[kb], 0, 0, 0);   // S[q][key]
+          else s[kb] = EKV_MFMA_32x32x16(kf, qreg[ks], s[kb], 0, 0, 0);            // S^T[key][q]
           if (ROPE && EKW_EXP != 7) {   // (kh + kl).(qh + ql) ~= kh.qh + kl.qh + kh.ql
             const ekv_h8 kl = *reinterpret_cast<const ekv_h8*>(sKlo + (kg + 32 * kb + c31) * RSK + (((2 * ks + hi) ^ ksw_l) << 4));
             if (MODE == 2) {
-              s[kb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(qreg[ks], kl, s[kb], 0, 0, 0);
-              s[kb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(qlo[ks], kf, s[kb], 0, 0, 0);
+              s[kb] = EKV_MFMA_32x32x16(qreg[ks], kl, s[kb], 0, 0, 0);
+              s[kb] = EKV_MFMA_32x32x16(qlo[ks], kf, s[kb], 0, 0, 0);
             } else {
-              s[kb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kl, qreg[ks], s[kb], 0, 0, 0);
-              s[kb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qlo[ks], s[kb], 0, 0, 0);
+              s[kb] = EKV_MFMA_32x32x16(kl, qreg[ks], s[kb], 0, 0, 0);
+              s[kb] = EKV_MFMA_32x32x16(kf, qlo[ks], s[kb], 0, 0, 0);
             }
           }
         }
@@ -636,7 +640,7 @@ __global__ void __launch_bounds__(64 * NWQ * NWK, EKV_WIDE_MODE == 2 ? (EKV_WIDE
 #pragma unroll
           for (int db = 0; db < DB; ++db)
 #pragma unroll
-            for (int m = 0; m < 2; ++m) oacc[db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(aV, bP[kb][m], oacc[db], 0, 0, 0);
+            for (int m = 0; m < 2; ++m) oacc[db] = EKV_MFMA_32x32x16(aV, bP[kb][m], oacc[db], 0, 0, 0);
           EKW_PRIO(0);
           return;
         }
@@ -649,7 +653,7 @@ __global__ void __launch_bounds__(64 * NWQ * NWK, EKV_WIDE_MODE == 2 ? (EKV_WIDE
             const ekv_h4 v_lo = __builtin_bit_cast(ekv_h4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) ekv_s4*)(vp)));
             const ekv_h4 v_hi = __builtin_bit_cast(ekv_h4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) ekv_s4*)(vp + v_r1 * RSV)));
             const ekv_h8 aV = {v_lo[0], v_lo[1], v_lo[2], v_lo[3], v_hi[0], v_hi[1], v_hi[2], v_hi[3]};
-            oacc[db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(aV, bP[kb][m], oacc[db], 0, 0, 0);
+            oacc[db] = EKV_MFMA_32x32x16(aV, bP[kb][m], oacc[db], 0, 0, 0);
           }
         }
         EKW_PRIO(0);
@@ -726,7 +730,7 @@ __global__ void __launch_bounds__(64 * NWQ * NWK, EKV_WIDE_MODE == 2 ? (EKV_WIDE
 #pragma unroll
               for (int m = 0; m < 2; ++m)
 #pragma unroll
-                for (int j = 0; j < 8; ++j) bP[kb][m][j] = (_Float16)s[kb][8 * m + j];
+                for (int j = 0; j < 8; ++j) bP[kb][m][j] = (ekv_e)s[kb][8 * m + j];
           } else {
           float mx = kWFloor;
 #pragma unroll
@@ -757,7 +761,7 @@ __global__ void __launch_bounds__(64 * NWQ * NWK, EKV_WIDE_MODE == 2 ? (EKV_WIDE
 #pragma unroll
               for (int m = 0; m < 2; ++m)
 #pragma unroll
-                for (int j = 0; j < 8; ++j) bP[kb][m][j] = (_Float16)s[kb][8 * m + j];
+                for (int j = 0; j < 8; ++j) bP[kb][m][j] = (ekv_e)s[kb][8 * m + j];
           }
           }
         }
@@ -956,8 +960,8 @@ __global__ void __launch_bounds__(64 * NWQ * NWK, EKV_WIDE_MODE == 2 ? (EKV_WIDE
         for (int db = 0; db < DB; ++db)
 #pragma unroll
           for (int q4 = 0; q4 < 4; ++q4) {
-            const __half2 lo = __floats2half2_rn(oacc[db][4 * q4] * inv, oacc[db][4 * q4 + 1] * inv);
-            const __half2 hh = __floats2half2_rn(oacc[db][4 * q4 + 2] * inv, oacc[db][4 * q4 + 3] * inv);
+            const __half2 lo = ekv_to_e2(oacc[db][4 * q4] * inv, oacc[db][4 * q4 + 1] * inv);
+            const __half2 hh = ekv_to_e2(oacc[db][4 * q4 + 2] * inv, oacc[db][4 * q4 + 3] * inv);
             uint2 pk;
             pk.x = __builtin_bit_cast(unsigned int, lo);
             pk.y = __builtin_bit_cast(unsigned int, hh);
@@ -1035,13 +1039,13 @@ hipError_t launch_wide_rep(const EkvAttnArgs& a, int layer_count, hipStream_t s,
 
 }  // namespace
 
-#define EKW_CAT3(a, b, c, d) a##b##c##d
-#define EKW_CAT4(a, b, c, d) EKW_CAT3(a, b, c, d)
+#define EKW_CAT3(a, b, c, d, t) a##b##c##d##t
+#define EKW_CAT4(a, b, c, d, t) EKW_CAT3(a, b, c, d, t)
 // nwq = query waves of 32 rows: 4 (65..128 rows) or 2 (33..64 rows); 256-thread workgroups
 #if EKV_WIDE_ROPE
-#define EKW_ENTRY(d, m) EKW_CAT4(ekv_launch_attn_wide_rope_d, d, _m, m)
+#define EKW_ENTRY(d, m) EKW_CAT4(ekv_launch_attn_wide_rope_d, d, _m, m, EKV_DT_TAG)
 #else
-#define EKW_ENTRY(d, m) EKW_CAT4(ekv_launch_attn_wide_d, d, _m, m)
+#define EKW_ENTRY(d, m) EKW_CAT4(ekv_launch_attn_wide_d, d, _m, m, EKV_DT_TAG)
 #endif
 hipError_t EKW_ENTRY(EKV_D, EKV_WIDE_MODE)(const EkvAttnArgs& a, int nwq, int layer_count, hipStream_t s, const EkvScoreArgs* tail) {
   switch (nwq) {

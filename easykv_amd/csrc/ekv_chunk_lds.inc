@@ -34,6 +34,9 @@
 // v_pk_fma_f32, one tile at a time in phase A, library expf, block-wide victim rounds) 260; this version 222-228.
 #include "ekv_common.h"
 #include "ekv_kernels.h"
+#if EKV_BF16   // (bf16 instances: the same kernel under a tagged name)
+#define ekv_chunk_lds_kernel ekv_chunk_lds_kernel_bf16
+#endif
 
 #ifndef EKV_LDS_ORDER
 #define EKV_LDS_ORDER 2   // 0: scorer then phase B, 1: phase B then scorer, 2: by the parity of the workgroup's wave slot
@@ -409,7 +412,7 @@ __global__ void __launch_bounds__(kLNT, 2) ekv_chunk_lds_kernel(const EkvAttnArg
   auto finish = [&](const ekv_h8 (&bk)[KB], int key0, unsigned dead_bits, int chunk_key0) __attribute__((always_inline)) {
     ekv_f4 sacc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int kb = 0; kb < KB; ++kb) sacc = __builtin_amdgcn_mfma_f32_16x16x32_f16(aq[kb], bk[kb], sacc, 0, 0, 0);
+    for (int kb = 0; kb < KB; ++kb) sacc = EKV_MFMA_16x16x32(aq[kb], bk[kb], sacc, 0, 0, 0);
     const bool dead = (dead_bits >> rr) & 1u;
     float x[4];
 #pragma unroll
@@ -829,7 +832,7 @@ __global__ void __launch_bounds__(kLNT, 2) ekv_chunk_lds_kernel(const EkvAttnArg
       for (int k = 0; k < 8; ++k) {
         float e = ep[k * NQ];
         if constexpr (RAW) e = __builtin_amdgcn_exp2f((e - mxq) * 1.4426950408889634f);
-        pa[k] = (_Float16)(c < NQ ? e : 0.f);
+        pa[k] = (ekv_e)(c < NQ ? e : 0.f);
       }
       uint32_t tb[8][4];
 #pragma unroll
@@ -845,7 +848,7 @@ __global__ void __launch_bounds__(kLNT, 2) ekv_chunk_lds_kernel(const EkvAttnArg
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
         const ekv_u4 t4 = {tb[i][0], tb[i][1], tb[i][2], tb[i][3]};
-        acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(pa, __builtin_bit_cast(ekv_h8, t4), acc[i], 0, 0, 0);
+        acc[i] = EKV_MFMA_16x16x32(pa, __builtin_bit_cast(ekv_h8, t4), acc[i], 0, 0, 0);
       }
     };
     const int n_batches = (E16 + RB - 1) / RB;
@@ -921,7 +924,7 @@ __global__ void __launch_bounds__(kLNT, 2) ekv_chunk_lds_kernel(const EkvAttnArg
     for (int idx = tid; idx < rows * D; idx += kLNT) {
       const int q = idx / D, d = idx % D;
       sc.out[(size_t)ll * a.n_q_heads * n * D + (size_t)(h * rep + q % rep) * a.o_hs + (size_t)(q / rep) * a.o_ts + d] =
-          __float2half((scr[(size_t)q * D + d] + scr[((size_t)NQ + q) * D + d]) * s_invL[q]);
+          ekv_to_e((scr[(size_t)q * D + d] + scr[((size_t)NQ + q) * D + d]) * s_invL[q]);
     }
   };
   auto phase_b_valu = [&]() __attribute__((always_inline)) {      // D = 64 / 32
@@ -1023,7 +1026,7 @@ __global__ void __launch_bounds__(kLNT, 2) ekv_chunk_lds_kernel(const EkvAttnArg
         float acc = 0.f;
   #pragma unroll
         for (int w = 0; w < kLNW; ++w) acc += scr[((size_t)w * NQ + q) * D + d];
-        sc.out[(size_t)ll * a.n_q_heads * n * D + (size_t)(h * rep + q % rep) * a.o_hs + (size_t)(q / rep) * a.o_ts + d] = __float2half(acc * s_invL[q]);
+        sc.out[(size_t)ll * a.n_q_heads * n * D + (size_t)(h * rep + q % rep) * a.o_hs + (size_t)(q / rep) * a.o_ts + d] = ekv_to_e(acc * s_invL[q]);
       }
     }
   }
@@ -1097,12 +1100,17 @@ hipError_t launch_lds(const EkvAttnArgs& a, const EkvScoreArgs& sc, int layer_co
 #define EKV_LCAT_(a, b) a##b
 #define EKV_LCAT(a, b) EKV_LCAT_(a, b)
 
+#define EKV_LCAT3_(a, b, t) a##b##t
+#define EKV_LCAT3(a, b, t) EKV_LCAT3_(a, b, t)
+
+#if !EKV_BF16   // (the LDS plan does not depend on the element type)
 size_t EKV_LCAT(ekv_chunk_lds_bytes_d, EKV_D)(int rows, int phys_extent, int n_slots) {
   const int e16 = (phys_extent + 15) & ~15;
   return rows <= 4 ? ekv_lds_plan<EKV_D, 4>(e16, n_slots).total : ekv_lds_plan<EKV_D, 8>(e16, n_slots).total;
 }
+#endif
 
-hipError_t EKV_LCAT(ekv_launch_chunk_lds_d, EKV_D)(const EkvAttnArgs& a, const EkvScoreArgs& sc, int layer_count, hipStream_t s) {
+hipError_t EKV_LCAT3(ekv_launch_chunk_lds_d, EKV_D, EKV_DT_TAG)(const EkvAttnArgs& a, const EkvScoreArgs& sc, int layer_count, hipStream_t s) {
   const int rows = (a.n_q_heads / a.n_kv_heads) * a.q_len;
   if (rows > 8 || a.n_slots > kLItems * kLNT) return hipErrorInvalidValue;
   return rows <= 4 ? launch_lds<4>(a, sc, layer_count, s) : launch_lds<8>(a, sc, layer_count, s);

@@ -8,8 +8,26 @@
 #define EKV_LOG2E 1.4426950408889634f
 #define EKV_NEG_INF (-__builtin_inff())
 
-typedef _Float16 ekv_h2 __attribute__((ext_vector_type(2)));
-typedef _Float16 ekv_h8 __attribute__((ext_vector_type(8)));
+// Element type of the 16-bit tensors (K/V rows, queries, outputs).  Every kernel instance is compiled for one of them: fp16, or
+// bf16 with EKV_BF16 = 1 (the *_bf16.hip instances, whose kernel and launcher names carry the tag _bf16).  Only what reads or
+// writes an element differs: the dot / MFMA builtins, the widening to f32 and the rounding of f32 to 16 bits.  The row pointers of
+// EkvAttnArgs / EkvScoreArgs stay __half*: rows are moved as bytes, and every element access goes through the helpers below.
+#ifndef EKV_BF16
+#define EKV_BF16 0
+#endif
+#if EKV_BF16
+typedef __bf16 ekv_e;
+#define EKV_DT_TAG _bf16
+#define EKV_MFMA_16x16x32 __builtin_amdgcn_mfma_f32_16x16x32_bf16
+#define EKV_MFMA_32x32x16 __builtin_amdgcn_mfma_f32_32x32x16_bf16
+#else
+typedef _Float16 ekv_e;
+#define EKV_DT_TAG
+#define EKV_MFMA_16x16x32 __builtin_amdgcn_mfma_f32_16x16x32_f16
+#define EKV_MFMA_32x32x16 __builtin_amdgcn_mfma_f32_32x32x16_f16
+#endif
+typedef ekv_e ekv_h2 __attribute__((ext_vector_type(2)));
+typedef ekv_e ekv_h8 __attribute__((ext_vector_type(8)));
 typedef unsigned int ekv_u4 __attribute__((ext_vector_type(4)));
 typedef float ekv_f2 __attribute__((ext_vector_type(2)));
 
@@ -29,11 +47,16 @@ __device__ __forceinline__ float ekv_group_sum(float x) {
   return x;
 }
 
+#if EKV_BF16
+#define EKV_FDOT2 __builtin_amdgcn_fdot2_f32_bf16
+#else
+#define EKV_FDOT2 __builtin_amdgcn_fdot2
+#endif
 __device__ __forceinline__ float ekv_dot8(const uint4& a, const uint4& b, float acc) {
-  acc = __builtin_amdgcn_fdot2(__builtin_bit_cast(ekv_h2, a.x), __builtin_bit_cast(ekv_h2, b.x), acc, false);
-  acc = __builtin_amdgcn_fdot2(__builtin_bit_cast(ekv_h2, a.y), __builtin_bit_cast(ekv_h2, b.y), acc, false);
-  acc = __builtin_amdgcn_fdot2(__builtin_bit_cast(ekv_h2, a.z), __builtin_bit_cast(ekv_h2, b.z), acc, false);
-  acc = __builtin_amdgcn_fdot2(__builtin_bit_cast(ekv_h2, a.w), __builtin_bit_cast(ekv_h2, b.w), acc, false);
+  acc = EKV_FDOT2(__builtin_bit_cast(ekv_h2, a.x), __builtin_bit_cast(ekv_h2, b.x), acc, false);
+  acc = EKV_FDOT2(__builtin_bit_cast(ekv_h2, a.y), __builtin_bit_cast(ekv_h2, b.y), acc, false);
+  acc = EKV_FDOT2(__builtin_bit_cast(ekv_h2, a.z), __builtin_bit_cast(ekv_h2, b.z), acc, false);
+  acc = EKV_FDOT2(__builtin_bit_cast(ekv_h2, a.w), __builtin_bit_cast(ekv_h2, b.w), acc, false);
   return acc;
 }
 
@@ -41,6 +64,22 @@ __device__ __forceinline__ void ekv_axpy8(float p, const uint4& v, float (&o)[8]
   const ekv_h8 h = __builtin_bit_cast(ekv_h8, v);
 #pragma unroll
   for (int i = 0; i < 8; ++i) o[i] = fmaf(p, (float)h[i], o[i]);
+}
+
+// f32 -> one 16-bit output element, rounded to nearest even (bf16: v_cvt_pk_bf16_f32, NaN kept), as the __half the row pointers hold
+__device__ __forceinline__ __half ekv_to_e(float x) {
+#if EKV_BF16
+  return __builtin_bit_cast(__half, (__bf16)x);
+#else
+  return __float2half(x);
+#endif
+}
+__device__ __forceinline__ __half2 ekv_to_e2(float x, float y) {
+#if EKV_BF16
+  return __builtin_bit_cast(__half2, ekv_h2{(__bf16)x, (__bf16)y});
+#else
+  return __floats2half2_rn(x, y);
+#endif
 }
 
 __device__ __forceinline__ float ekv_wave_max(float x) {

@@ -38,6 +38,7 @@ struct EkvStepPlan {
   int32_t fold_in_decode;   // split decode step whose last-arriving split of a head folds the partials (ekv_bank.arrive)
   int32_t flush_unsplit;    // deferred flush: the column-sum pass runs unsplit over the one pass's key-range statistics
   int32_t slot_rows, slot_tail_ok;   // fused decode step on the slot-indexed score rows (EKV_PHASE_SLOT_ROWS / _TAIL_OK)
+  int32_t bf16;             // 16-bit tensors are bf16: the launches run the EKV_BF16 kernel instances
   int32_t strides[6];       // q, kv, out row strides (token, head) in elements, the dense layout filled in
   // Workspace: byte offsets of this call's slices (a deferred call's layout spans every deferred layer), -1 = not in the layout
   int64_t logits;     // [layer_count][Hq][q_len][t_pad]   raw q.k/sm_div of every live position
@@ -53,8 +54,12 @@ struct EkvStepPlan {
   int32_t n_list;
   EkvLaunch list[6];
 };
-int ekv_plan_step(const ekv_bank* bank, const ekv_step* step, EkvStepPlan* plan);
+// dtype: EKV_DTYPE_F16 / EKV_DTYPE_BF16 (any other value: EKV_E_ARG).  A bf16 step plans exactly as the fp16 step (same tiling, launch
+// list and workspace) and runs the bf16 instances of the same kernels; RoPE-on-read has no bf16 build (EKV_E_UNSUPPORTED, no launches).
+int ekv_plan_step(const ekv_bank* bank, const ekv_step* step, int32_t dtype, EkvStepPlan* plan);
 
+// The __half* members below point at 16-bit rows: fp16, or bf16 for the EKV_BF16 kernel instances (ekv_common.h: rows move as
+// bytes, and every element access of a kernel goes through ekv_e / ekv_h8 / ekv_to_e).
 struct EkvAttnArgs {
   const __half* k;
   const __half* v;
@@ -125,19 +130,21 @@ struct EkvScoreArgs {
   int32_t slot_tail_ok;   // EKV_PHASE_SLOT_TAIL_OK: the newest `tail` entries are known to have consecutive births
 };
 
-hipError_t ekv_launch_attn_decode(const EkvAttnArgs& a, int head_dim, int layer_count, hipStream_t s);
+// bf16 (the launchers below that take it): run the EKV_BF16 instances — 16-bit rows of q, k_new, v_new, out and the bank read and
+// written as bf16 (ekv_common.h); the planner never sends a RoPE-on-read step there
+hipError_t ekv_launch_attn_decode(const EkvAttnArgs& a, int head_dim, int layer_count, hipStream_t s, bool bf16);
 // passes (wide-block kernel, two-pass scheme): bit 0 = the one pass (output + row statistics), bit 1 = the column-sum pass
 // tail_sc (wide-block kernel, two passes, passes & 2): the step's scorer runs as the tail of the column-sum pass (ekv_wide_tail.h)
 // wide: the wide-block kernel (ekv_chunk_wide, decided by the planner)
 hipError_t ekv_launch_attn_chunk(const EkvAttnArgs& a, int head_dim, int layer_count, bool wide, bool two_pass, hipStream_t s,
-                                 const EkvScoreArgs* fuse_sc, int passes, const EkvScoreArgs* tail_sc);
+                                 const EkvScoreArgs* fuse_sc, int passes, const EkvScoreArgs* tail_sc, bool bf16);
 // kernel launches ekv_launch_attn_chunk issues for these arguments (lives next to the launch code)
 int ekv_attn_chunk_launches(bool wide, bool rope, bool two_pass, int passes);
 // can the scorer of a two-pass wide step run as the tail of its column-sum pass: W score columns, n_wg workgroups per head
 bool ekv_wide_tail_supported(int W, int n_wg);
 // logits-resident scored chunk step (ekv_attn_resident.inc): the whole step of an unsplit head in ONE launch, K and V read once
 bool ekv_attn_resident_supported(int head_dim, int rep, int q_len, int n_slots, int W);
-hipError_t ekv_launch_attn_resident(const EkvAttnArgs& a, const EkvScoreArgs& sc, int layer_count, hipStream_t s);
+hipError_t ekv_launch_attn_resident(const EkvAttnArgs& a, const EkvScoreArgs& sc, int layer_count, hipStream_t s, bool bf16);
 size_t ekv_score_lds_bytes_nt256(const EkvScoreArgs& a);
 bool ekv_score_rows_exceed_lds(int W, int rows);   // generic scorer: S / Q / C + keys of W columns do not fit 160 KB of LDS
 bool ekv_chunk_two_pass(int head_dim, int rep, int q_len, int policy, bool scored, bool accumulate, bool rope, int mode);
@@ -145,19 +152,20 @@ bool ekv_chunk_two_pass(int head_dim, int rep, int q_len, int policy, bool score
 // plain or RoPE-on-read keys, head_dim 64 / 128, and either the two-pass scheme (rep in {1, 2, 4, 8, 16}) or a step that exports no logits
 bool ekv_chunk_wide(int head_dim, int rep, int q_len, bool rope, bool two_pass, bool wants_logits);
 hipError_t ekv_launch_tova_headmean(const EkvScoreArgs& a, int layer_count, hipStream_t s);
-hipError_t ekv_launch_score_select(const EkvScoreArgs& a, int layer_count, hipStream_t s);
+hipError_t ekv_launch_score_select(const EkvScoreArgs& a, int layer_count, hipStream_t s, bool bf16);
 bool ekv_attn_decode_supported(int head_dim, int rep);
 int ekv_decode_fused_nw(int n_heads_in_launch);
 bool ekv_decode_fused_supported(int head_dim, int rep, int n_slots, int t_pad, int l_pad, int n_evict, int cap, int nw);
-hipError_t ekv_launch_decode_fused(const EkvAttnArgs& a, const EkvScoreArgs& sc, int head_dim, int layer_count, int nw, hipStream_t s);
+hipError_t ekv_launch_decode_fused(const EkvAttnArgs& a, const EkvScoreArgs& sc, int head_dim, int layer_count, int nw, hipStream_t s,
+                                   bool bf16);
 bool ekv_attn_chunk_supported(int head_dim, int rep, int q_len);
 void ekv_chunk_blocks(int rep, int q_len, int* qb_rows, int* n_qblocks, int* qpw);
 int ekv_chunk_col_parts(int qpw, bool rope);
 size_t ekv_score_lds_bytes(const EkvScoreArgs& a);
 bool ekv_decode_score_supported(const EkvScoreArgs& sc);
-hipError_t ekv_launch_decode_score(const EkvScoreArgs& sc, int layer_count, hipStream_t s);
-hipError_t ekv_launch_fold(const EkvScoreArgs& sc, int layer_count, hipStream_t s);
+hipError_t ekv_launch_decode_score(const EkvScoreArgs& sc, int layer_count, hipStream_t s, bool bf16);
+hipError_t ekv_launch_fold(const EkvScoreArgs& sc, int layer_count, hipStream_t s, bool bf16);
 
 // Small-row chunk step with the logits in LDS (ekv_chunk_lds.inc): whole step in one launch, K and V read once.
 bool ekv_chunk_lds_supported(const ekv_bank* bank, const ekv_step* st, int phys_extent, bool scored);
-hipError_t ekv_launch_chunk_lds(const EkvAttnArgs& a, const EkvScoreArgs& sc, int head_dim, int layer_count, hipStream_t s);
+hipError_t ekv_launch_chunk_lds(const EkvAttnArgs& a, const EkvScoreArgs& sc, int head_dim, int layer_count, hipStream_t s, bool bf16);

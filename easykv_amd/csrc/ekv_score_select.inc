@@ -413,7 +413,7 @@ __device__ void ekv_score_select_body(const EkvScoreArgs& a, const int h, const 
     float mm, ls;
     const float o = ekv_fold_partials_auto<(EKV_SS_NT == 512 ? 16 : 8)>(a.partials + ((hq0 * n + row) * a.n_split) * PS, a.n_split, PS, d, mm, ls);
     if (!a.skip_fold)      // row = r * n + i (ekv_step.out_*_stride)
-      a.out[(size_t)ll * a.n_q_heads * n * D + (size_t)(h * rep + row / n) * a.o_hs + (size_t)(row % n) * a.o_ts + d] = __float2half(o);
+      a.out[(size_t)ll * a.n_q_heads * n * D + (size_t)(h * rep + row / n) * a.o_hs + (size_t)(row % n) * a.o_ts + d] = ekv_to_e(o);
     if (d == 0 && scored && a.colsum == nullptr) sRowM[row] = mm, sRowL[row] = 1.f / ls;
   }
 
@@ -690,12 +690,16 @@ __device__ void ekv_score_select_body(const EkvScoreArgs& a, const int h, const 
 }
 
 #ifndef EKV_SS_DEVICE_ONLY
+#if EKV_BF16   // (bf16 instances: the scorer under a tagged name; the head-mean row writes no 16-bit data and is built once)
+#define ekv_score_select_kernel ekv_score_select_kernel_bf16
+#endif
 template <bool BIG>
 __global__ void __launch_bounds__(kNT) ekv_score_select_kernel(const EkvScoreArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   ekv_score_select_body<BIG>(a, blockIdx.x, blockIdx.y, smem);
 }
 
+#if !EKV_BF16
 // 'tova' in encoding/ppl mode: one last-query row averaged over ALL kv heads (easykv/easykv.py:456, :847)
 __global__ void __launch_bounds__(kNT) ekv_tova_headmean_kernel(const EkvScoreArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -734,6 +738,7 @@ __global__ void __launch_bounds__(kNT) ekv_tova_headmean_kernel(const EkvScoreAr
     a.tova_row[(size_t)ll * a.t_pad + j] = acc / (float)H;
   }
 }
+#endif
 
 #endif  // EKV_SS_DEVICE_ONLY
 
@@ -742,15 +747,21 @@ __global__ void __launch_bounds__(kNT) ekv_tova_headmean_kernel(const EkvScoreAr
 #ifndef EKV_SS_DEVICE_ONLY
 #define EKV_SS_CAT_(a, b) a##b
 #define EKV_SS_CAT(a, b) EKV_SS_CAT_(a, b)
+#define EKV_SS_CAT3_(a, b, t) a##b##t
+#define EKV_SS_CAT3(a, b, t) EKV_SS_CAT3_(a, b, t)
 
+#if EKV_BF16
+size_t EKV_SS_CAT(ekv_score_lds_bytes_nt, EKV_SS_NT)(const EkvScoreArgs& a);
+#else
 size_t EKV_SS_CAT(ekv_score_lds_bytes_nt, EKV_SS_NT)(const EkvScoreArgs& a) {
   const bool scored = a.policy == EKV_POLICY_H2O_HEAD || a.policy == EKV_POLICY_ROCO || a.policy == EKV_POLICY_TOVA;
   const int W = a.n_slots - (scored ? a.score_off : 0);
   const int rows = a.colsum != nullptr ? 0 : (a.n_q_heads / a.n_kv_heads) * a.q_len;   // (lrows of the kernel body)
   return ekv_align((size_t)((a.big_rows != nullptr ? 1 : 4) * W + 2 * rows) * 4, 16) + 2 * kNWV * 8 * 4 + 264 * 4 + kNT * 8;   // .. + histogram + candidate list
 }
+#endif
 
-hipError_t EKV_SS_CAT(ekv_launch_score_select_nt, EKV_SS_NT)(const EkvScoreArgs& a, int layer_count, hipStream_t s) {
+hipError_t EKV_SS_CAT3(ekv_launch_score_select_nt, EKV_SS_NT, EKV_DT_TAG)(const EkvScoreArgs& a, int layer_count, hipStream_t s) {
   const size_t lds = EKV_SS_CAT(ekv_score_lds_bytes_nt, EKV_SS_NT)(a);
   if (lds > 160 * 1024) return hipErrorInvalidValue;
 #if EKV_SS_NT == 1024
@@ -769,9 +780,11 @@ hipError_t EKV_SS_CAT(ekv_launch_score_select_nt, EKV_SS_NT)(const EkvScoreArgs&
   return hipGetLastError();
 }
 
+#if !EKV_BF16
 hipError_t EKV_SS_CAT(ekv_launch_tova_headmean_nt, EKV_SS_NT)(const EkvScoreArgs& a, int layer_count, hipStream_t s) {
   const size_t lds = (size_t)a.n_q_heads * 2 * 4;
   hipLaunchKernelGGL(ekv_tova_headmean_kernel, dim3(layer_count), dim3(kNT), lds, s, a);
   return hipGetLastError();
 }
+#endif
 #endif  // EKV_SS_DEVICE_ONLY

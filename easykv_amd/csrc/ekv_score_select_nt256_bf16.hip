@@ -1,0 +1,4 @@
+// generic scorer, 256 threads per workgroup, bf16 outputs
+#define EKV_BF16 1
+#define EKV_SS_NT 256
+#include "ekv_score_select.inc"

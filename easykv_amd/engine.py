@@ -43,13 +43,14 @@ def _ptr(t: Optional[torch.Tensor]):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
-def _row_strides(t: torch.Tensor):
+def _row_strides(t: torch.Tensor, dtype=torch.float16):
     """(token_stride, head_stride) in elements when the rows of ``t`` ``[layers, heads, n, D]`` can be read in place by the kernels
-    (ekv_step.*_stride, ABI 8): fp16, D contiguous halfs per row, layers dense blocks apart, strides multiples of 8 — e.g. the
-    ``[1, heads, n, D]`` transposed views HF attention modules hand over.  (0, 0) = the dense layout; None = needs a copy."""
+    (ekv_step.*_stride, ABI 8): the bank's 16-bit ``dtype``, D contiguous elements per row, layers dense blocks apart, strides
+    multiples of 8 — e.g. the ``[1, heads, n, D]`` transposed views HF attention modules hand over.  (0, 0) = the dense layout;
+    None = needs a copy."""
     layers, heads, n, d = t.shape
     s0, s1, s2, s3 = t.stride()
-    if t.dtype != torch.float16 or s3 != 1 or (t.data_ptr() & 15):
+    if t.dtype != dtype or s3 != 1 or (t.data_ptr() & 15):
         return None
     if layers > 1 and s0 != heads * n * d:
         return None
@@ -64,10 +65,10 @@ def _row_strides(t: torch.Tensor):
     return ts, hs
 
 
-def _stride_rows(st, q, k_new, v_new, out):
-    """Fill the row strides of ``st`` from the tensors; tensors whose layout the kernels cannot read in place are copied dense (k_new
-    and v_new share one pair of strides).  Returns (q, k_new, v_new)."""
-    f16 = torch.float16
+def _stride_rows(st, q, k_new, v_new, out, dtype=torch.float16):
+    """Fill the row strides of ``st`` from the tensors; tensors whose layout the kernels cannot read in place, or whose dtype is not
+    the bank's ``dtype``, are converted / copied dense (k_new and v_new share one pair of strides).  Returns (q, k_new, v_new)."""
+    f16 = dtype
     if (q.dtype is f16 and k_new.dtype is f16 and v_new.dtype is f16 and q.is_contiguous() and k_new.is_contiguous() and v_new.is_contiguous()
             and (out is None or out.is_contiguous())):
         # dense tensors (the bank-level callers: tests, bench): a few C++ calls — this sits on the per-layer critical path of a decoder
@@ -75,25 +76,33 @@ def _stride_rows(st, q, k_new, v_new, out):
         if st.q_token_stride or st.q_head_stride or st.kv_token_stride or st.kv_head_stride or st.out_token_stride or st.out_head_stride:
             st.q_token_stride = st.q_head_stride = st.kv_token_stride = st.kv_head_stride = st.out_token_stride = st.out_head_stride = 0
         return q, k_new, v_new
-    sq = _row_strides(q)
+    sq = _row_strides(q, dtype)
     if sq is None:
-        q, sq = q.to(torch.float16).contiguous(), (0, 0)
-    sk, sv = _row_strides(k_new), _row_strides(v_new)
+        q, sq = q.to(dtype).contiguous(), (0, 0)
+    sk, sv = _row_strides(k_new, dtype), _row_strides(v_new, dtype)
     if sk is None or sv != sk:
-        k_new, v_new, sk = k_new.to(torch.float16).contiguous(), v_new.to(torch.float16).contiguous(), (0, 0)
-    so = (0, 0) if out is None else _row_strides(out)
+        k_new, v_new, sk = k_new.to(dtype).contiguous(), v_new.to(dtype).contiguous(), (0, 0)
+    so = (0, 0) if out is None else _row_strides(out, dtype)
     if so is None:
-        raise ValueError("`out` must be an fp16 tensor whose rows are head_dim contiguous halfs at strides that are multiples of 8")
+        raise ValueError(f"`out` must be a {dtype} tensor whose rows are head_dim contiguous elements at strides that are multiples of 8")
     (st.q_token_stride, st.q_head_stride), (st.kv_token_stride, st.kv_head_stride), (st.out_token_stride, st.out_head_stride) = sq, sk, so
     return q, k_new, v_new
 
 
 class KVBank:
-    """K/V rows + slot map + score rows of ``n_layers`` layers on one GPU."""
+    """K/V rows + slot map + score rows of ``n_layers`` layers on one GPU.
+
+    ``dtype`` (torch.float16 or torch.bfloat16) is the element type of the K/V rows, and of the queries, new rows and outputs of
+    every step: tensors of another dtype are converted to it, ``out`` is allocated in it.  bf16 banks run the bf16 builds of the
+    same kernels (include/easykv_hip.h, EKV_DTYPE_BF16); RoPE-on-read (``StepPlan.streaming``) has no bf16 build."""
 
     default_two_pass = 0    # StepPlan.two_pass used when a plan leaves it at 0 (tests force either chunk scheme with it)
+    dtype, _dt = torch.float16, _lib.DTYPE_F16      # (set per bank by __init__)
 
-    def __init__(self, n_layers, n_q_heads, n_kv_heads, head_dim, cap, device="cuda", scored=True):
+    def __init__(self, n_layers, n_q_heads, n_kv_heads, head_dim, cap, device="cuda", scored=True, dtype=torch.float16):
+        if dtype not in _lib.DTYPE_CODES:
+            raise ValueError(f"KVBank dtype must be torch.float16 or torch.bfloat16, not {dtype}")
+        self.dtype, self._dt = dtype, _lib.DTYPE_CODES[dtype]
         self.lib = _lib.load()
         dev = torch.device(device)
         if dev.type != "cuda":
@@ -102,7 +111,7 @@ class KVBank:
         self._dev_index = dev.index if dev.index is not None else torch.cuda.current_device()
         cap = (cap + 63) // 64 * 64     # rows of the slot map / score rows stay 16-byte aligned (fused kernel, LDS-DMA)
         self.n_layers, self.n_q_heads, self.n_kv_heads, self.head_dim, self.cap = n_layers, n_q_heads, n_kv_heads, head_dim, cap
-        self.k = torch.empty(n_layers, n_kv_heads, cap, head_dim, dtype=torch.float16, device=dev)
+        self.k = torch.empty(n_layers, n_kv_heads, cap, head_dim, dtype=dtype, device=dev)
         self.v = torch.empty_like(self.k)
         # (the state tensors are reached through properties: reading one converts slot-indexed layers back to the ordered layout)
         self._slot_of_pos = torch.empty(n_layers, n_kv_heads, cap, dtype=torch.int32, device=dev)
@@ -194,7 +203,7 @@ class KVBank:
         if ok is None:
             if len(self._slot_ok) > 4096:      # (a growing cache asks about a new shape every step)
                 self._slot_ok.clear()
-            ok = self._slot_ok[key] = self.lib.ekv_step_check(C.byref(self._bank), C.byref(st)) == 0
+            ok = self._slot_ok[key] = self.lib.ekv_step_check_typed(C.byref(self._bank), C.byref(st), self._dt) == 0
         st.phases = 0
         if not ok:
             return False
@@ -298,8 +307,8 @@ class KVBank:
         lc, n = k.shape[0], k.shape[2]
         self._ensure_ordered(layer_begin, lc)
         pos = self.n_slots[layer_begin] if pos_begin is None else pos_begin
-        k = k.to(self.device, torch.float16).contiguous()
-        v = v.to(self.device, torch.float16).contiguous()
+        k = k.to(self.device, self.dtype).contiguous()
+        v = v.to(self.device, self.dtype).contiguous()
         check(self.lib.ekv_scatter_rows(C.byref(self._bank), layer_begin, lc, pos, n, _ptr(k), _ptr(v), self._stream()), "ekv_scatter_rows")
         for l in range(layer_begin, layer_begin + lc):
             self.n_slots[l] = pos + n
@@ -310,7 +319,7 @@ class KVBank:
         lc = self.n_layers - layer_begin if layer_count is None else layer_count
         self._ensure_ordered(layer_begin, lc)
         t = self.n_slots[layer_begin]
-        k = torch.empty(lc, self.n_kv_heads, t, self.head_dim, dtype=torch.float16, device=self.device)
+        k = torch.empty(lc, self.n_kv_heads, t, self.head_dim, dtype=self.dtype, device=self.device)
         v = torch.empty_like(k)
         check(self.lib.ekv_gather_ordered(C.byref(self._bank), layer_begin, lc, t, _ptr(k), _ptr(v), self._stream()), "ekv_gather_ordered")
         return k, v
@@ -371,7 +380,7 @@ class KVBank:
         st = self.make_step(plan, q_len, layer_begin, self.n_layers - layer_begin if layer_count is None else layer_count)
         st.phases = phases
         info = (C.c_int32 * 9)()
-        check(self.lib.ekv_step_info(C.byref(self._bank), C.byref(st), info, 9), "ekv_step_info")
+        check(self.lib.ekv_step_info_typed(C.byref(self._bank), C.byref(st), self._dt, info, 9), "ekv_step_info")
         keys = ("n_split", "fused", "two_pass", "wide", "n_qblocks", "qb_rows", "n_col_parts", "fold_in_kernel", "n_launches")
         return dict(zip(keys, (int(x) for x in info)))
 
@@ -390,7 +399,7 @@ class KVBank:
         if self._side is None:
             self._side = [torch.cuda.Stream(self.device) for _ in range(4)]
         main = torch.cuda.current_stream(self.device)
-        need = self.lib.ekv_workspace_bytes(C.byref(self._bank), C.byref(st))
+        need = self.lib.ekv_workspace_bytes_typed(C.byref(self._bank), C.byref(st), self._dt)
         if not self._ws_ring or self._ws_ring[0].numel() < need:
             self._ws_ring = [torch.empty(int(need * 1.25) + 4096, dtype=torch.uint8, device=self.device) for _ in range(8)]
             self._ws_free = [None] * 8
@@ -403,13 +412,13 @@ class KVBank:
         args = (_ptr(q), _ptr(k_new), _ptr(v_new), _ptr(out), _ptr(evict_ids) if st.n_evict > 0 else None,
                 _ptr(self.rope_cos), _ptr(self.rope_sin), _ptr(ws), ws.numel())
         st.phases = 1 | 4
-        check(self.lib.ekv_step_attend(C.byref(self._bank), C.byref(st), *args, C.c_void_p(main.cuda_stream)), "ekv_step_attend")
+        check(self.lib.ekv_step_attend_typed(C.byref(self._bank), C.byref(st), self._dt, *args, C.c_void_p(main.cuda_stream)), "ekv_step_attend")
         ready = torch.cuda.Event()
         ready.record(main)
         side = self._side[slot % len(self._side)]
         side.wait_event(ready)
         st.phases = 8
-        check(self.lib.ekv_step_attend(C.byref(self._bank), C.byref(st), *args, C.c_void_p(side.cuda_stream)), "ekv_step_attend")
+        check(self.lib.ekv_step_attend_typed(C.byref(self._bank), C.byref(st), self._dt, *args, C.c_void_p(side.cuda_stream)), "ekv_step_attend")
         done = torch.cuda.Event()
         done.record(side)
         self._ws_free[slot] = done
@@ -440,24 +449,24 @@ class KVBank:
             # the scorer shape of the flush() call (phases = 8 over all layers) is validated NOW, before the first layer's
             # attention appends a row: a shape only the last call of the token would refuse must not leave the bank half-stepped
             st.layer_begin, st.layer_count, st.defer_index, st.phases = 0, self.n_layers, 0, 8
-            check(self.lib.ekv_step_check(C.byref(self._bank), C.byref(st)), "ekv_step_check (deferred scorer)")
-            need = self.lib.ekv_workspace_bytes(C.byref(self._bank), C.byref(st))
+            check(self.lib.ekv_step_check_typed(C.byref(self._bank), C.byref(st), self._dt), "ekv_step_check (deferred scorer)")
+            need = self.lib.ekv_workspace_bytes_typed(C.byref(self._bank), C.byref(st), self._dt)
             ids = torch.empty(self.n_layers, self.n_kv_heads, st.n_evict, dtype=torch.int32, device=self.device) if st.n_evict > 0 else None
             ws = self._workspace(need)
             # everything that is the same for all layers of the token step is resolved once: the per-layer call below is on the
             # critical path of the decoder stack (host cost per layer ~ GPU cost per layer in this regime)
             d = self._defer = dict(plan=plan, t=t, n=n, st=st, ws=ws, ids=ids, pending=0, rope=(_ptr(self.rope_cos), _ptr(self.rope_sin)),
                                    st_ref=C.byref(st), bank_ref=C.byref(self._bank), ws_ptr=ws.data_ptr(), ws_len=ws.numel(),
-                                   stream=self._stream(), call=self.lib.ekv_step_attend)
+                                   stream=self._stream(), call=self.lib.ekv_step_attend_typed, dt=self._dt)
         st = d["st"]
         st.layer_begin = st.defer_index = layer
         st.layer_count, st.phases = 1, 5
         ext = self.extent[layer]
         st.phys_extent = ext if ext > t else t
         if out is None:
-            out = torch.empty(1, self.n_q_heads, n, self.head_dim, dtype=torch.float16, device=self.device)
-        q, k_new, v_new = _stride_rows(st, q, k_new, v_new, out)
-        rc = d["call"](d["bank_ref"], d["st_ref"], q.data_ptr(), k_new.data_ptr(), v_new.data_ptr(), out.data_ptr(), None,
+            out = torch.empty(1, self.n_q_heads, n, self.head_dim, dtype=self.dtype, device=self.device)
+        q, k_new, v_new = _stride_rows(st, q, k_new, v_new, out, self.dtype)
+        rc = d["call"](d["bank_ref"], d["st_ref"], d["dt"], q.data_ptr(), k_new.data_ptr(), v_new.data_ptr(), out.data_ptr(), None,
                        d["rope"][0], d["rope"][1], d["ws_ptr"], d["ws_len"], d["stream"])
         if rc != 0:
             check(rc, "ekv_step_attend")
@@ -475,7 +484,7 @@ class KVBank:
             check(self.lib.ekv_step_plan(C.byref(self._bank), C.byref(st), C.byref(ns), C.byref(fu)), "ekv_step_plan")
             st.n_split = ns.value
         st.defer_layers, st.layer_begin, st.layer_count, st.defer_index, st.phases = self.n_layers, 0, self.n_layers, 0, 8
-        return int(self.lib.ekv_workspace_bytes(C.byref(self._bank), C.byref(st)))
+        return int(self.lib.ekv_workspace_bytes_typed(C.byref(self._bank), C.byref(st), self._dt))
 
     def flush(self):
         """Scorer of every layer of the token step opened by ``attend(..., defer=True)``: accumulate, select, compact — one
@@ -489,7 +498,7 @@ class KVBank:
         st.layer_begin, st.layer_count, st.defer_index, st.phases = 0, self.n_layers, 0, 8
         st.q_token_stride = st.q_head_stride = st.kv_token_stride = st.kv_head_stride = st.out_token_stride = st.out_head_stride = 0      # (no caller tensors in this call)
         st.phys_extent = max(max(self.extent), d["t"])
-        check(self.lib.ekv_step_attend(C.byref(self._bank), C.byref(st), ws.data_ptr(), ws.data_ptr(), ws.data_ptr(), ws.data_ptr(),
+        check(self.lib.ekv_step_attend_typed(C.byref(self._bank), C.byref(st), self._dt, ws.data_ptr(), ws.data_ptr(), ws.data_ptr(), ws.data_ptr(),
                                        _ptr(d["ids"]), d["rope"][0], d["rope"][1], ws.data_ptr(), ws.numel(), d["stream"]), "ekv_step_attend")
         for l in range(self.n_layers):
             self.n_slots[l] = d["t"] - st.n_evict
@@ -498,9 +507,9 @@ class KVBank:
         return d["ids"] if st.n_evict > 0 else None
 
     def attend(self, plan: StepPlan, q, k_new, v_new, layer_begin=0, out=None, evict_ids=None, phases=0, overlap_scorer=False, defer=False):
-        """q ``[layers, Hq, n, D]``, k_new/v_new ``[layers, H, n, D]`` (fp16, device; dense or strided views whose rows are read in
-        place — ekv_step.*_stride, see :func:`_row_strides`; anything else is copied dense first).
-        Returns (out ``[layers, Hq, n, D]`` fp16, evict_ids ``[layers, H, k]`` int32 or None).
+        """q ``[layers, Hq, n, D]``, k_new/v_new ``[layers, H, n, D]`` (the bank's dtype, device; dense or strided views whose rows are
+        read in place — ekv_step.*_stride, see :func:`_row_strides`; anything else is converted / copied dense first).
+        Returns (out ``[layers, Hq, n, D]`` in the bank's dtype, evict_ids ``[layers, H, k]`` int32 or None).
         ``defer=True`` (one layer per call): attention + fold only; the scorers of all layers run at :meth:`flush`.
         ``evict_ids=False``: the caller has no use for the evicted cache indices (none are returned; on the slot-indexed layout the
         step then skips ranking the victim's birth)."""
@@ -529,8 +538,8 @@ class KVBank:
             for l in range(layer_begin, layer_begin + lc):
                 self._slot_min_tail[l] = 0 if breaks_tail else min(self._slot_min_tail[l], tail)
         if out is None:
-            out = torch.empty(lc, self.n_q_heads, n, self.head_dim, dtype=torch.float16, device=self.device)
-        q, k_new, v_new = _stride_rows(st, q, k_new, v_new, out)
+            out = torch.empty(lc, self.n_q_heads, n, self.head_dim, dtype=self.dtype, device=self.device)
+        q, k_new, v_new = _stride_rows(st, q, k_new, v_new, out, self.dtype)
         want_ids = evict_ids is not False
         if evict_ids is False:      # the caller has no use for the evicted order indices (the slot-indexed layout then skips ranking the victim)
             evict_ids = None if slot else torch.empty(lc, self.n_kv_heads, max(st.n_evict, 1), dtype=torch.int32, device=self.device)
@@ -544,9 +553,9 @@ class KVBank:
             return out, (evict_ids if (st.n_evict > 0 and want_ids) else None)
         if any(ev is not None for ev in self._score_done[layer_begin:layer_begin + lc]):
             self.join()
-        need = self.lib.ekv_workspace_bytes(C.byref(self._bank), C.byref(st))
+        need = self.lib.ekv_workspace_bytes_typed(C.byref(self._bank), C.byref(st), self._dt)
         ws = self._workspace(need)
-        check(self.lib.ekv_step_attend(C.byref(self._bank), C.byref(st), _ptr(q), _ptr(k_new), _ptr(v_new), _ptr(out),
+        check(self.lib.ekv_step_attend_typed(C.byref(self._bank), C.byref(st), self._dt, _ptr(q), _ptr(k_new), _ptr(v_new), _ptr(out),
                                        _ptr(evict_ids) if (st.n_evict > 0 and evict_ids is not None) else None, _ptr(self.rope_cos), _ptr(self.rope_sin),
                                        _ptr(ws), ws.numel(), self._stream()), "ekv_step_attend")
         if phases != 1:     # phases == 1 launches the attention kernel only; the slot map is untouched

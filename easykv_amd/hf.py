@@ -7,9 +7,13 @@ here just hands the NEW rows back) and then the registered attention function, w
 :class:`~easykv_amd.api.BudgetedKVCache` of the forward in flight.  No attention mask is built (the implementation is
 not in the mask registry) and no probability matrix is ever returned.
 
-    model = AutoModelForCausalLM.from_pretrained(path, torch_dtype=torch.float16).cuda()
+    model = AutoModelForCausalLM.from_pretrained(path, torch_dtype=torch.bfloat16).cuda()
     easykv_amd.hf.patch_model(model)
     easykv_amd.enable_fixed_kv(model, tokenizer, mode='auto', stride=8)
+    model.easykv_generate(input_ids=ids, generation_config=dict(budget=2048, kv_policy='roco', kv_dtype='auto'))
+
+``kv_dtype='auto'`` keeps K/V in the model's own dtype (bf16 here): q / k / v reach the kernels as the module's own views and the
+output goes to ``o_proj`` without a conversion.  The default ``'float16'`` bank converts bf16 tensors on the way in and out.
 """
 from __future__ import annotations
 
@@ -38,8 +42,8 @@ def _easykv_attention(module, query, key, value, attention_mask=None, dropout=0.
         # rotates with the PURE tables at read time, so the model's s^2 on the logits is put back on the query alone
         s = float(cache.unrotate[2]) if len(cache.unrotate) > 2 else 1.0
         query, key = _unrotate(query, cos, sin, s), _unrotate(key, cos, sin, 1.0 / s)
-    out = cache.attend(module.layer_idx, query, key, value)        # [1, Hq, n, D] fp16
-    return out.transpose(1, 2).to(query.dtype), None
+    out = cache.attend(module.layer_idx, query, key, value)        # [1, Hq, n, D] in the bank's dtype
+    return out.transpose(1, 2).to(query.dtype), None      # (no conversion when the bank holds the model's dtype)
 
 
 def _unrotate(x, cos, sin, gain=1.0):

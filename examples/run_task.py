@@ -73,7 +73,7 @@ def load(args, dynamic_ntk=None, max_pos=None):
             rp.update(rope)
             config.rope_parameters = rp
             config.max_position_embeddings = max_pos or config.max_position_embeddings
-        model = AutoModelForCausalLM.from_pretrained(args.model, dtype=torch.float16, config=config).eval()
+        model = AutoModelForCausalLM.from_pretrained(args.model, dtype=getattr(torch, args.dtype), config=config).eval()
         tokenizer = AutoTokenizer.from_pretrained(args.model)
     else:
         hidden, inter, layers, heads, kv_heads, vocab = SHAPES[args.random_init]
@@ -83,7 +83,7 @@ def load(args, dynamic_ntk=None, max_pos=None):
             kw["rope_parameters"] = dict(rope, rope_theta=10000.0)
         torch.manual_seed(0)
         cls, ccls = (MistralForCausalLM, MistralConfig) if args.random_init.startswith("mistral") else (LlamaForCausalLM, LlamaConfig)
-        model = cls(ccls(**kw)).half().eval()
+        model = cls(ccls(**kw)).to(getattr(torch, args.dtype)).eval()
         tokenizer = SyntheticTokenizer(vocab)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world > 1:
@@ -124,6 +124,8 @@ def main():
     ap.add_argument("--max-new-tokens", type=int, default=None)
     ap.add_argument("--filler", type=int, default=400, help="passkey without --jsonl: filler sentences blocks in the synthetic prompt")
     ap.add_argument("--ntk-length", type=int, default=None, help="sequence length the DynamicNTK base is fixed for")
+    ap.add_argument("--dtype", choices=["float16", "bfloat16"], default="float16",
+                    help="model weights in this dtype; the K/V bank follows it (generation_config kv_dtype='auto')")
     args = ap.parse_args()
     import easykv_amd
     from easykv_amd import set_dynamicntk_rope_length
@@ -140,7 +142,7 @@ def main():
             for budget in args.budgets or [300, 150]:
                 gen = dict(temperature=1e-9, top_p=1.0, max_new_tokens=args.max_new_tokens or 2048, budget=int(budget), kv_policy=args.kv_policy or "roco")
                 ids = tok([prompt], return_tensors="pt").input_ids.cuda()
-                out = model.easykv_generate(input_ids=ids, generation_config=gen)
+                out = model.easykv_generate(input_ids=ids, generation_config=dict(gen, kv_dtype="auto"))
                 say(f"EasyKV-{gen['kv_policy']}(budget {gen['budget']}): {out}")
         elif args.task == "summarization":
             model, tok = load(args)
@@ -152,7 +154,7 @@ def main():
                 gen = dict(temperature=0.3, top_p=1.0, max_new_tokens=args.max_new_tokens or 256, budget=float(budget),
                            kv_policy=args.kv_policy or "roco", keep_attention=True)
                 ids = tok([prompt], return_tensors="pt").input_ids.cuda()
-                out = model.easykv_generate(input_ids=ids, generation_config=gen)
+                out = model.easykv_generate(input_ids=ids, generation_config=dict(gen, kv_dtype="auto"))
                 say(f"EasyKV-{gen['kv_policy']}({budget * 100:.2f}%): {out}")
         elif args.task in ("passkey", "passkey_ntk"):
             ntk = args.task == "passkey_ntk"
@@ -173,7 +175,7 @@ def main():
                 for budget in args.budgets or [0.5]:
                     gen = dict(temperature=1e-9, top_p=1.0, max_new_tokens=args.max_new_tokens or 6, budget=float(budget),
                                kv_policy=args.kv_policy or "roco", keep_attention=False)
-                    out = model.easykv_generate(input_ids=ids, generation_config=gen)
+                    out = model.easykv_generate(input_ids=ids, generation_config=dict(gen, kv_dtype="auto"))
                     hits += str(ex["target"]) in out
                     say((f"EasyKV-{gen['kv_policy']}({budget * 100:.2f}%):     [" + postfix + out + "]").replace("\n", "\\n"))
             say(f"retrieved {hits} of {len(examples) * len(args.budgets or [0.5])}")
@@ -185,7 +187,8 @@ def main():
             say("Input token length:", ids.shape[-1])
             for budget in args.budgets or [1.0, 0.5]:
                 for policy in ([args.kv_policy] if args.kv_policy else ["recency", "roco"]):
-                    ppl = model.easykv_ppl(input_ids=ids, generation_config=dict(budget=float(budget), kv_policy=policy, keep_attention=False))
+                    ppl = model.easykv_ppl(input_ids=ids, generation_config=dict(budget=float(budget), kv_policy=policy, keep_attention=False,
+                                                                                       kv_dtype="auto"))
                     say(f"EasyKV-{policy}-{budget * 100:.2f}% PPL: {float(ppl):.2f}")
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         from easykv_amd import dist as D

@@ -19,7 +19,7 @@
  *
  * Memory model ("bank" = the layers resident on this GPU, all device memory, caller-owned):
  *
- *   k, v          fp16  [n_layers][n_kv_heads][cap][head_dim]   physical rows ("slots")
+ *   k, v          16-bit [n_layers][n_kv_heads][cap][head_dim]  physical rows ("slots"): fp16, or bf16 through the _typed calls
  *   slot_of_pos   int32 [n_layers][n_kv_heads][cap]             permutation: logical position -> row.
  *                       positions [0, n_slots) are live, in the reference's birth order;
  *                       positions [n_slots, cap) hold the free rows.
@@ -62,6 +62,15 @@ enum {
   EKV_E_WORKSPACE = -3,    /* workspace too small                        */
   EKV_E_LAUNCH = -4        /* hipLaunch failure (hipGetLastError)        */
 };
+
+/* Element type of the 16-bit tensors of a step: the bank's k / v, q, k_new, v_new and out alike (ABI 8, additive).  The untyped
+ * calls are the EKV_DTYPE_F16 calls of the same code; any other value returns EKV_E_ARG.  A bf16 step is planned exactly as the
+ * fp16 step (tiling, launches, workspace) and runs the bf16 builds of the same kernels: logits, softmax statistics, scores and
+ * selection stay fp32, P is rounded to bf16 where it feeds a matrix-core product, and the output is rounded once from fp32.  Steps
+ * with rope_on_read have no bf16 build (EKV_E_UNSUPPORTED, no launches).  The row moves (ekv_gather_ordered, ekv_scatter_rows,
+ * ekv_compact_inplace) and the slot-map / score-row calls (ekv_rows_to_slots, ekv_rows_to_order, ekv_bank_reset, ekv_state_init)
+ * never read an element's value and serve bf16 banks as they are. */
+enum { EKV_DTYPE_F16 = 0, EKV_DTYPE_BF16 = 1 };
 
 typedef struct ekv_bank {
   void *k, *v;
@@ -139,6 +148,7 @@ const char *ekv_strerror(int code);
 
 /* bytes of scratch ekv_step_attend needs for (bank, step) */
 size_t ekv_workspace_bytes(const ekv_bank *bank, const ekv_step *step);
+size_t ekv_workspace_bytes_typed(const ekv_bank *bank, const ekv_step *step, int32_t dtype);
 
 /* How ekv_step_attend will run (bank, step): *n_split = key-range splits per head, *fused = 1 when the whole
  * step is ONE launch (the fused decode kernel, the logits-in-LDS chunk kernel, or a chunk step whose scorer runs as the tail
@@ -154,6 +164,7 @@ int ekv_step_plan(const ekv_bank *bank, const ekv_step *step, int32_t *n_split, 
  * one step or in query blocks. */
 #define EKV_STEP_INFO_N 9
 int ekv_step_info(const ekv_bank *bank, const ekv_step *step, int32_t *info, int32_t n_info);
+int ekv_step_info_typed(const ekv_bank *bank, const ekv_step *step, int32_t dtype, int32_t *info, int32_t n_info);
 
 /* slot_of_pos <- identity for the whole bank */
 int ekv_bank_reset(const ekv_bank *bank, void *stream);
@@ -168,10 +179,11 @@ int ekv_state_init(const ekv_bank *bank, int32_t layer_begin, int32_t layer_coun
 
 /* The fused step: append q_len new K/V rows, attention of the q_len queries over the n_slots live
  * positions, GQA fold, score accumulation, victim selection, slot-map + score-row compaction.
- *   q      fp16 [layer_count][n_q_heads][q_len][head_dim]    (dense, or rows at ekv_step.q_*_stride)
- *   k_new  fp16 [layer_count][n_kv_heads][q_len][head_dim]   (already rotated unless rope_on_read; ekv_step.kv_*_stride)
- *   v_new  fp16 [layer_count][n_kv_heads][q_len][head_dim]   (same strides as k_new)
- *   out    fp16 [layer_count][n_q_heads][q_len][head_dim]    (ekv_step.out_*_stride)
+ *   q      16-bit [layer_count][n_q_heads][q_len][head_dim]    (dense, or rows at ekv_step.q_*_stride)
+ *   k_new  16-bit [layer_count][n_kv_heads][q_len][head_dim]   (already rotated unless rope_on_read; ekv_step.kv_*_stride)
+ *   v_new  16-bit [layer_count][n_kv_heads][q_len][head_dim]   (same strides as k_new)
+ *   out    16-bit [layer_count][n_q_heads][q_len][head_dim]    (ekv_step.out_*_stride)
+ *          (16-bit: fp16, or bf16 through the _typed calls — the bank's k / v in the same type)
  *   evict_ids int32 [layer_count][n_kv_heads][n_evict] or NULL: evicted logical positions, ascending
  *   rope_cos/rope_sin fp32 [>= n_slots][head_dim] or NULL; layout cat(freqs, freqs) as in the reference (llama_patch.py:74-98):
  *                    the kernels read the first half of a row for both halves of the head.  The tables must be what RoPE tables are —
@@ -183,6 +195,9 @@ int ekv_state_init(const ekv_bank *bank, int32_t layer_begin, int32_t layer_coun
 int ekv_step_attend(const ekv_bank *bank, const ekv_step *step, const void *q, const void *k_new, const void *v_new,
                     void *out, int32_t *evict_ids, const float *rope_cos, const float *rope_sin, void *workspace,
                     size_t workspace_bytes, void *stream);
+int ekv_step_attend_typed(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const void *q, const void *k_new,
+                          const void *v_new, void *out, int32_t *evict_ids, const float *rope_cos, const float *rope_sin,
+                          void *workspace, size_t workspace_bytes, void *stream);
 
 /* Dry run of ekv_step_attend (ABI 4): every argument / shape / capability test of the real call for (bank, step), in the same
  * order, and nothing launched — no data pointer, workspace or stream is needed.  Returns what ekv_step_attend would return
@@ -190,6 +205,7 @@ int ekv_step_attend(const ekv_bank *bank, const ekv_step *step, const void *q, c
  * deferred scorer: per-layer phases = 1|4 calls append rows long before the phases = 8 call that scores them), so that a shape
  * the LAST call would refuse is refused before the FIRST one touches the bank. */
 int ekv_step_check(const ekv_bank *bank, const ekv_step *step);
+int ekv_step_check_typed(const ekv_bank *bank, const ekv_step *step, int32_t dtype);
 
 /* Slot-indexed score rows (ABI 6).  In the ordered layout an eviction shifts every entry of S / Q / C and of the slot map behind
  * the victim: a decode step rewrites all of them (28 KB per head at 2 k slots), and written bytes cost about twice what read
@@ -214,12 +230,12 @@ int ekv_step_check(const ekv_bank *bank, const ekv_step *step);
 int ekv_rows_to_slots(const ekv_bank *bank, int32_t layer_begin, int32_t layer_count, int32_t n_slots, void *stream);
 int ekv_rows_to_order(const ekv_bank *bank, int32_t layer_begin, int32_t layer_count, int32_t n_slots, void *stream);
 
-/* Ordered view: k_out/v_out fp16 [layer_count][n_kv_heads][n_slots][head_dim] <- rows in position order */
+/* Ordered view: k_out/v_out 16-bit (the bank's type) [layer_count][n_kv_heads][n_slots][head_dim] <- rows in position order */
 int ekv_gather_ordered(const ekv_bank *bank, int32_t layer_begin, int32_t layer_count, int32_t n_slots, void *k_out,
                        void *v_out, void *stream);
 
 /* Load ordered rows into the bank at positions [pos_begin, pos_begin+n) (prefix prefill / cache import):
- *   k_in/v_in fp16 [layer_count][n_kv_heads][n][head_dim] */
+ *   k_in/v_in 16-bit (the bank's type) [layer_count][n_kv_heads][n][head_dim] */
 int ekv_scatter_rows(const ekv_bank *bank, int32_t layer_begin, int32_t layer_count, int32_t pos_begin, int32_t n,
                      const void *k_in, const void *v_in, void *stream);
 
