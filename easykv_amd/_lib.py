@@ -27,6 +27,11 @@ EXPORTS = ("ekv_abi_version", "ekv_strerror", "ekv_workspace_bytes", "ekv_step_p
            "ekv_step_attend", "ekv_gather_ordered", "ekv_scatter_rows", "ekv_compact_inplace", "ekv_step_check", "ekv_step_info",
            "ekv_rows_to_slots", "ekv_rows_to_order", "ekv_workspace_bytes_typed", "ekv_step_check_typed", "ekv_step_info_typed",
            "ekv_step_attend_typed")
+# the FP8 K/V storage calls (include/easykv_hip.h, "kv8"), checked and typed by load() like EXPORTS.  A list of their own:
+# tests/test_host_cpu.py pins EXPORTS to the header's names as a digit-free pattern reads them, which a name with "kv8" in it is not.
+EXPORTS_KV8 = ("ekv_kv8_quantize", "ekv_kv8_dequantize", "ekv_kv8_step_check", "ekv_kv8_step_info", "ekv_kv8_workspace_bytes",
+               "ekv_kv8_step_attend")
+DTYPE_F32 = 2      # ekv_kv8_dequantize's out_dtype only
 
 
 class Bank(C.Structure):
@@ -34,6 +39,11 @@ class Bank(C.Structure):
                 ("score_sum", C.c_void_p), ("score_sq", C.c_void_p), ("score_cnt", C.c_void_p),
                 ("n_layers", C.c_int32), ("n_q_heads", C.c_int32), ("n_kv_heads", C.c_int32),
                 ("head_dim", C.c_int32), ("cap", C.c_int32), ("arrive", C.c_void_p), ("birth", C.c_void_p), ("slot_state", C.c_void_p)]
+
+
+class Kv8(C.Structure):
+    """ekv_kv8: the FP8 code planes and fp32 row scales that stand for a bank's K/V rows (include/easykv_hip.h, "kv8")."""
+    _fields_ = [("k_codes", C.c_void_p), ("v_codes", C.c_void_p), ("k_scale", C.c_void_p), ("v_scale", C.c_void_p)]
 
 
 class Step(C.Structure):
@@ -61,7 +71,7 @@ def load():
         raise EkvError(f"{LIB} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                        "(hipcc --offload-arch=gfx950).  There is no CPU fallback for the product path.")
     lib = C.CDLL(LIB)
-    for name in EXPORTS:
+    for name in EXPORTS + EXPORTS_KV8:
         if not hasattr(lib, name):
             raise EkvError(f"{LIB} does not export {name}")
     vp, i32 = C.c_void_p, C.c_int32
@@ -85,9 +95,16 @@ def load():
     lib.ekv_step_check_typed.argtypes = [C.POINTER(Bank), C.POINTER(Step), i32]
     lib.ekv_step_info_typed.argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, C.POINTER(C.c_int32), C.c_int32]
     lib.ekv_step_attend_typed.argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
-    for name in EXPORTS[3:]:
+    lib.ekv_kv8_quantize.argtypes = [C.POINTER(Bank), C.POINTER(Kv8), i32, i32, i32, i32, vp]
+    lib.ekv_kv8_dequantize.argtypes = [C.POINTER(Bank), C.POINTER(Kv8), i32, i32, i32, i32, vp, vp, vp]
+    lib.ekv_kv8_step_check.argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, C.POINTER(Kv8)]
+    lib.ekv_kv8_step_info.argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, C.POINTER(Kv8), C.POINTER(C.c_int32), C.c_int32]
+    lib.ekv_kv8_workspace_bytes.argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, C.POINTER(Kv8)]
+    lib.ekv_kv8_step_attend.argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, C.POINTER(Kv8), vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
+    for name in EXPORTS[3:] + EXPORTS_KV8:
         getattr(lib, name).restype = C.c_int
     lib.ekv_workspace_bytes_typed.restype = C.c_size_t
+    lib.ekv_kv8_workspace_bytes.restype = C.c_size_t
     if lib.ekv_abi_version() != 8:
         raise EkvError("ABI version mismatch")
     _lib = lib

@@ -117,6 +117,15 @@ class BudgetedKVCache:
         self._defer_this_forward = None
         self.defer_chunk_scorer = True     # scored chunk steps of a layer-per-call model: one scorer launch per forward (round 4)
 
+    @property
+    def kv_quant(self):
+        """None, or "fp8" once the bank's K/V rows are FP8 codes with per-row scales (KVBank.quantize_fp8)."""
+        return self.bank.kv_quant
+
+    def kv_bytes(self) -> int:
+        """Bytes the bank holds for K/V rows."""
+        return self.bank.kv_bytes()
+
     def owns(self, layer_idx: int) -> bool:
         return self.layer_begin <= layer_idx < self.layer_begin + self.layer_count
 
@@ -290,7 +299,22 @@ def generate(self, input_ids, generation_config, kv_mode="encoding", stride=1, r
     kv_dtype = _kv_dtype(self, cfg.get("kv_dtype", "float16"))
     if kv_dtype is torch.bfloat16 and streaming:
         raise ValueError("generation_config['kv_dtype'] = bfloat16 with streaming=True: RoPE-on-read has no bf16 build (use float16)")
+    # extension key: storage of the K/V rows during the decode phase — None (the 16-bit rows of kv_dtype) or "fp8": the prefill runs on
+    # the 16-bit bank as always and the bank is quantised once at the prefill -> decode boundary (KVBank.quantize_fp8: OCP e4m3fn codes
+    # + one fp32 scale per row, 2 * head_dim + 8 bytes per row pair).  kv_dtype keeps meaning the 16-bit type of q / k / v / out.
+    kv_quant = cfg.get("kv_quant", None)
+    if kv_quant not in (None, "fp8"):
+        raise ValueError(f"generation_config['kv_quant'] must be None or 'fp8', not {kv_quant!r}")
+    if kv_quant is not None:
+        if streaming:
+            raise ValueError("generation_config['kv_quant'] = 'fp8' with streaming=True: the FP8 decode kernels have no RoPE-on-read build")
+        if kv_mode == "ppl":
+            raise ValueError("generation_config['kv_quant'] = 'fp8' with kv_mode='ppl': there is no decode phase to quantise the bank for")
+        if getattr(self, "layer_shard", None) is not None and self.layer_shard.world > 1:
+            raise ValueError("generation_config['kv_quant'] = 'fp8' is not supported on a layer-sharded model (model.layer_shard)")
     n_layers, hq, h, d = _dims(self)
+    if kv_quant is not None and d not in (64, 128):
+        raise ValueError(f"generation_config['kv_quant'] = 'fp8' needs head_dim 64 or 128 (this model: {d})")
     dev = torch.device(self.device)
     if input_ids.dim() != 2 or input_ids.shape[0] != 1:
         raise ValueError(f"input_ids must be [1, S] (batch size 1, as the reference); got {tuple(input_ids.shape)}")
@@ -577,6 +601,8 @@ def generate(self, input_ids, generation_config, kv_mode="encoding", stride=1, r
         out = forward(cache, input_ids, list(range(length)), StepPlan(policy="full", phase="prefill", accumulate=False))
         if evicting and scored:
             cache.bank.state_init(budget + 1, 0)                   # :242-245
+        if kv_quant:      # prefill -> decode boundary: the decode steps run on FP8 rows
+            cache.bank.quantize_fp8()
         out_ids, fed = decode_loop(cache, out.logits[:, -1, :], length, length, budget, False)
         kept = min(fed, budget) if evicting else fed             # == cache length - prompt length when no forward ran past an EOS
         print(f"KV cache budget ratio: {kept / len(out_ids) * 100:.2f}%({kept}/{len(out_ids)})")
@@ -595,6 +621,8 @@ def generate(self, input_ids, generation_config, kv_mode="encoding", stride=1, r
             logits_last, _, _ = prefill(cache, budget_p, idx, r_idx, True)
         kept = cache.get_seq_length()
         print(f"KV cache budget ratio: {kept / length * 100:.2f}%({kept}/{length})")
+        if kv_quant:      # prefill -> decode boundary
+            cache.bank.quantize_fp8()
         log, cur_pos, t_first, n_fwd = TokenLog(), length, None, 0
         while log.n < max_new_tokens:                              # :508-526 plain decode, no eviction
             tok = sample(logits_last)
@@ -623,6 +651,8 @@ def generate(self, input_ids, generation_config, kv_mode="encoding", stride=1, r
         budget_p, idx, r_idx = geometry("auto", length, budget, stride)
         cache = new_cache(idx + stride + 1)
         logits_last, _, _ = prefill(cache, budget_p, idx, r_idx, False)
+        if kv_quant:      # prefill -> decode boundary
+            cache.bank.quantize_fp8()
         # the score rows keep their first idx+1 columns (:666-669); the decode rules then run over the whole cache
         out_ids, _ = decode_loop(cache, logits_last, length, 0, budget_p, True)
         size = cache.get_seq_length()

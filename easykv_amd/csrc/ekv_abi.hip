@@ -693,12 +693,34 @@ int ekv_plan_step(const ekv_bank* bank, const ekv_step* step, int32_t dtype, Ekv
   return rc;
 }
 
-// Body of ekv_step_attend: the plan, the pointers, then its launch sequence.
+// FP8 rows: the plan of the 16-bit step of the same shape (the scorers read logits and partials, never a K/V element, so splits,
+// launches and workspace carry over), run on the kv8 instances of the two decode attention kernels — which is all a kv8 bank has.
+int ekv_plan_step_kv8(const ekv_bank* bank, const ekv_step* step, int32_t dtype, EkvStepPlan* P) {
+  const int rc = ekv_plan_step(bank, step, dtype, P);
+  P->kv8 = 1;
+  if (rc != EKV_OK) return rc;
+  if (step->q_len != 1 || step->rope_on_read || (bank->head_dim != 64 && bank->head_dim != 128)) {
+    P->one_launch = P->n_launches = P->n_list = 0;
+    return EKV_E_UNSUPPORTED;
+  }
+  return EKV_OK;
+}
+
+// The bank a kv8 call plans and launches with: the code planes stand where the 16-bit rows were (bank->k / bank->v are not read)
+static bool kv8_bank(const ekv_bank* bank, const ekv_kv8* q8, ekv_bank* out) {
+  if (!bank || !q8 || !q8->k_codes || !q8->v_codes || !q8->k_scale || !q8->v_scale) return false;
+  *out = *bank;
+  out->k = q8->k_codes;
+  out->v = q8->v_codes;
+  return true;
+}
+
+// Body of ekv_step_attend: the plan, the pointers, then its launch sequence.  q8 != NULL: a step on FP8 rows (bank = kv8_bank()).
 static int step_attend_impl(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const void* q, const void* k_new,
                             const void* v_new, void* out, int32_t* evict_ids, const float* rope_cos, const float* rope_sin,
-                            void* workspace, size_t workspace_bytes, void* stream) {
+                            void* workspace, size_t workspace_bytes, void* stream, const ekv_kv8* q8 = nullptr) {
   EkvStepPlan P;
-  if (int e = ekv_plan_step(bank, st, dtype, &P)) return e;
+  if (int e = q8 ? ekv_plan_step_kv8(bank, st, dtype, &P) : ekv_plan_step(bank, st, dtype, &P)) return e;
   if (!q || !k_new || !v_new || !out || !workspace || (st->rope_on_read && (!rope_cos || !rope_sin))) return EKV_E_ARG;
   if (P.bytes > workspace_bytes) return EKV_E_WORKSPACE;
   hipStream_t s = static_cast<hipStream_t>(stream);
@@ -756,6 +778,8 @@ static int step_attend_impl(const ekv_bank* bank, const ekv_step* st, int32_t dt
   sa.tova_row = f32(P.tova_row);
   sa.colsum = aa.colsum;
   sa.row_stats = aa.row_stats;
+  // FP8 rows: the scale planes (they share the storage of stats / colsum, which a decode step — all a kv8 plan can be — never has)
+  if (q8) aa.k_scale = q8->k_scale, aa.v_scale = q8->v_scale;
   sa.out = static_cast<__half*>(out);
   sa.evict_ids = evict_ids;
   sa.big_rows = f32(P.big_rows);
@@ -766,17 +790,19 @@ static int step_attend_impl(const ekv_bank* bank, const ekv_step* st, int32_t dt
     sa.slot_tail_ok = P.slot_tail_ok;
   }
 
-  const bool bf16 = P.bf16 != 0;
+  const bool bf16 = P.bf16 != 0, kv8 = P.kv8 != 0;
   drop_stale_error();
   for (int i = 0; i < P.n_list; ++i) {
     const EkvLaunch& L = P.list[i];
     sa.skip_fold = L.skip_fold;
     hipError_t e = hipSuccess;
+    // (a kv8 plan is a decode plan: the decode attention launches and the scorers behind them, which read no K/V element)
+    if (kv8 && (L.kind == EKV_RUN_CHUNK_LDS || L.kind == EKV_RUN_RESIDENT || L.kind == EKV_RUN_CHUNK || L.kind == EKV_RUN_FLUSH)) return EKV_E_UNSUPPORTED;
     switch (L.kind) {
-      case EKV_RUN_FUSED_DECODE: e = ekv_launch_decode_fused(aa, sa, D, lc, P.fused_nw, s, bf16); break;
+      case EKV_RUN_FUSED_DECODE: e = ekv_launch_decode_fused(aa, sa, D, lc, P.fused_nw, s, bf16, kv8); break;
       case EKV_RUN_CHUNK_LDS: e = ekv_launch_chunk_lds(aa, sa, D, lc, s, bf16); break;
       case EKV_RUN_RESIDENT: e = ekv_launch_attn_resident(aa, sa, lc, s, bf16); break;
-      case EKV_RUN_DECODE: e = ekv_launch_attn_decode(aa, D, lc, s, bf16); break;
+      case EKV_RUN_DECODE: e = ekv_launch_attn_decode(aa, D, lc, s, bf16, kv8); break;
       case EKV_RUN_CHUNK:
         e = ekv_launch_attn_chunk(aa, D, lc, P.wide, P.two_pass, s, L.fuse ? &sa : nullptr, L.passes, L.tail ? &sa : nullptr, bf16);
         break;
@@ -830,6 +856,76 @@ int ekv_step_check_typed(const ekv_bank* bank, const ekv_step* st, int32_t dtype
 }
 
 int ekv_step_check(const ekv_bank* bank, const ekv_step* st) { return ekv_step_check_typed(bank, st, EKV_DTYPE_F16); }
+
+// ---- FP8 K/V storage (include/easykv_hip.h, "kv8")
+int ekv_kv8_step_check(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_kv8* q8) {
+  if (dtype != EKV_DTYPE_F16 && dtype != EKV_DTYPE_BF16) return EKV_E_ARG;
+  ekv_bank b;
+  if (!kv8_bank(bank, q8, &b)) return EKV_E_ARG;
+  EkvStepPlan P;
+  return ekv_plan_step_kv8(&b, st, dtype, &P);
+}
+
+int ekv_kv8_step_info(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_kv8* q8, int32_t* info, int32_t n_info) {
+  if (dtype != EKV_DTYPE_F16 && dtype != EKV_DTYPE_BF16) return EKV_E_ARG;
+  ekv_bank b;
+  if (!kv8_bank(bank, q8, &b)) return EKV_E_ARG;
+  if (int e = check_bank(&b)) return e;
+  if (!st || !info || n_info < 1) return EKV_E_ARG;
+  EkvStepPlan P;
+  const bool ok = ekv_plan_step_kv8(&b, st, dtype, &P) == EKV_OK;
+  const int32_t v[EKV_STEP_INFO_N] = {P.n_split, ok ? P.one_launch : 0, P.two_pass, P.wide, P.n_qblocks, P.qb_rows, P.n_col_parts,
+                                      P.fold_in_kernel, ok ? P.n_launches : 0};
+  for (int i = 0; i < n_info && i < EKV_STEP_INFO_N; ++i) info[i] = v[i];
+  for (int i = EKV_STEP_INFO_N; i < n_info; ++i) info[i] = 0;
+  return EKV_OK;
+}
+
+size_t ekv_kv8_workspace_bytes(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_kv8* q8) {
+  ekv_bank b;
+  if (!kv8_bank(bank, q8, &b)) return 0;
+  EkvStepPlan P;
+  (void)ekv_plan_step_kv8(&b, st, dtype, &P);
+  return P.bytes;
+}
+
+int ekv_kv8_step_attend(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_kv8* q8, const void* q, const void* k_new,
+                        const void* v_new, void* out, int32_t* evict_ids, const float* rope_cos, const float* rope_sin,
+                        void* workspace, size_t workspace_bytes, void* stream) {
+  if (dtype != EKV_DTYPE_F16 && dtype != EKV_DTYPE_BF16) return EKV_E_ARG;
+  ekv_bank b;
+  if (!kv8_bank(bank, q8, &b)) return EKV_E_ARG;
+  return step_attend_impl(&b, st, dtype, q, k_new, v_new, out, evict_ids, rope_cos, rope_sin, workspace, workspace_bytes, stream, q8);
+}
+
+static int kv8_convert_check(const ekv_bank* bank, const ekv_kv8* q8, int32_t layer_begin, int32_t layer_count, int32_t extent) {
+  if (!bank || !q8 || !q8->k_codes || !q8->v_codes || !q8->k_scale || !q8->v_scale) return EKV_E_ARG;
+  if (bank->n_layers <= 0 || bank->n_kv_heads <= 0 || bank->cap <= 0) return EKV_E_ARG;
+  if (int e = check_layers(bank, layer_begin, layer_count)) return e;
+  if (extent < 0 || extent > bank->cap) return EKV_E_ARG;
+  if (bank->head_dim != 64 && bank->head_dim != 128) return EKV_E_UNSUPPORTED;
+  return EKV_OK;
+}
+
+int ekv_kv8_quantize(const ekv_bank* bank, const ekv_kv8* q8, int32_t dtype, int32_t layer_begin, int32_t layer_count, int32_t extent,
+                     void* stream) {
+  if (dtype != EKV_DTYPE_F16 && dtype != EKV_DTYPE_BF16) return EKV_E_ARG;
+  if (int e = kv8_convert_check(bank, q8, layer_begin, layer_count, extent)) return e;
+  if (!bank->k || !bank->v) return EKV_E_ARG;
+  drop_stale_error();
+  return ekv_launch_kv8_quantize(bank, q8, dtype == EKV_DTYPE_BF16, layer_begin, layer_count, extent, static_cast<hipStream_t>(stream)) == hipSuccess
+             ? EKV_OK : EKV_E_LAUNCH;
+}
+
+int ekv_kv8_dequantize(const ekv_bank* bank, const ekv_kv8* q8, int32_t out_dtype, int32_t layer_begin, int32_t layer_count,
+                       int32_t extent, void* k_out, void* v_out, void* stream) {
+  if (out_dtype != EKV_DTYPE_F16 && out_dtype != EKV_DTYPE_BF16 && out_dtype != EKV_DTYPE_F32) return EKV_E_ARG;
+  if (int e = kv8_convert_check(bank, q8, layer_begin, layer_count, extent)) return e;
+  if (!k_out || !v_out) return EKV_E_ARG;
+  drop_stale_error();
+  return ekv_launch_kv8_dequantize(bank, q8, out_dtype, layer_begin, layer_count, extent, k_out, v_out, static_cast<hipStream_t>(stream)) == hipSuccess
+             ? EKV_OK : EKV_E_LAUNCH;
+}
 
 int ekv_gather_ordered(const ekv_bank* bank, int32_t layer_begin, int32_t layer_count, int32_t n_slots, void* k_out,
                        void* v_out, void* stream) {

@@ -18,21 +18,43 @@
 // Compiled once per (EKV_D, EKV_ROPE) by the ekv_attn_decode_d*.hip stubs so the objects build in parallel.
 #include "ekv_decode_stream.h"
 #include "ekv_decode_tail.h"
-#if EKV_BF16   // (bf16 instances: the same kernels under tagged names)
+// EKV_KV8 = 1 (the *_kv8.hip instances): the bank's rows are FP8 codes + fp32 row scales (ekv_decode_stream.h, "FP8 rows"); q, k_new,
+// v_new and out keep the 16-bit type of the build.  Only the stream and the per-lane width of the output accumulators differ.
+#ifndef EKV_KV8
+#define EKV_KV8 0
+#endif
+#if EKV_KV8
+#define EKV_KV_TAG _kv8
+#if EKV_BF16
+#define ekv_attn_decode_kernel ekv_attn_decode_kernel_kv8_bf16
+#define ekv_decode_fused_kernel ekv_decode_fused_kernel_kv8_bf16
+#else
+#define ekv_attn_decode_kernel ekv_attn_decode_kernel_kv8
+#define ekv_decode_fused_kernel ekv_decode_fused_kernel_kv8
+#endif
+#elif EKV_BF16   // (bf16 instances: the same kernels under tagged names)
+#define EKV_KV_TAG
 #define ekv_attn_decode_kernel ekv_attn_decode_kernel_bf16
 #define ekv_decode_fused_kernel ekv_decode_fused_kernel_bf16
+#else
+#define EKV_KV_TAG
 #endif
+// FP8 rows: 4 rows in flight per lane group.  A lane's output slice is 16 floats per query head instead of 8, the query fragment
+// doubles and a row's widened codes are live next to its bytes: with 8 rows the one-launch build of GQA factor 1 needs 149..214 spilled
+// registers under its four-workgroups-per-CU bound, with 4 rows 102..111 VGPRs and none (tools/kernel_regs.py).
 #ifndef EKV_SPLIT_KU
-#define EKV_SPLIT_KU 8
+#define EKV_SPLIT_KU (EKV_KV8 ? 4 : 8)
 #endif
 #ifndef EKV_FUSED_KU
-#define EKV_FUSED_KU 8
+#define EKV_FUSED_KU (EKV_KV8 ? 4 : 8)
 #endif
 #ifndef EKV_ROPE_KU
 #define EKV_ROPE_KU(rep) ((rep) == 4 ? 8 : 4)      // rows in flight per lane group of the RoPE-on-read builds (the largest count without spilled VGPRs; rep 8: 8 spilled at 4)
 #endif
 
 namespace {
+
+constexpr int kEPL = EKV_KV8 ? 16 : 8;      // elements of a lane's 16-byte piece of a K/V row
 
 // SLOT_LDS = false: slot-map entries are fetched per iteration (needs 16-byte aligned map rows, cap % 4 == 0); saves the
 // staging pass and its barrier, which matters when a workgroup only streams one or two iterations.
@@ -59,13 +81,13 @@ __global__ void __launch_bounds__(256) ekv_attn_decode_kernel(const EkvAttnArgs 
     __syncthreads();
   }
 
-  float m[REP], l[REP], o[REP][8];
+  float m[REP], l[REP], o[REP][kEPL];
   float* logits = a.logits ? a.logits + ((size_t)ll * a.n_q_heads + hq0) * a.t_pad : nullptr;
   // EKV_SPLIT_KU = 16 would make a 256-row key range (one layer of a decoder stack, split to fill the chip) ONE batch of
   // loads per wave instead of two dependent ones (191 VGPRs, one workgroup per CU anyway).  Measured on the Llama2-7B decode
   // stack, one layer per launch: 14.0 us per layer against 13.7 with 8 — the second round trip is not what bounds the launch
   // (docs/TUNING.md §8, round 3) — so 8 stays.
-  constexpr int KU = (!ROPE && !SLOT_LDS && REP <= 2) ? EKV_SPLIT_KU : 8;
+  constexpr int KU = (!ROPE && !SLOT_LDS && REP <= 2) ? EKV_SPLIT_KU : (EKV_KV8 ? 4 : 8);
   ekv_decode_stream<D, REP, ROPE, SLOT_LDS, 4, false, KU>(a, SLOT_LDS ? s_slot : a.slot_of_pos + head_row, logits, a.t_pad, t0, t1,
                                                           ll, h, head_row, m, l, o, nullptr, EkvNoop(), nrep, hq0);
 
@@ -212,7 +234,7 @@ __global__ void __launch_bounds__(64 * NW, (NW >= 8 ? (REP == 1 ? 2 : 1) : (SLOT
   // constants (ekv_decode_stream.h) — 124 VGPRs at 4 rows (46 spilled at 8), GQA x 2 144 (13 spilled at 8), GQA x 4 230 at 8 rows
   // without spills, GQA x 8 (per-row tables) 247
   constexpr int KUF = ROPE ? EKV_ROPE_KU(REP) : EKV_FUSED_KU;
-  float m[REP], l[REP], o[REP][8];
+  float m[REP], l[REP], o[REP][kEPL];
   if (PHYS)
     ekv_decode_stream<D, REP, ROPE, false, NW, PHYS, KUF>(a, slot_row, s_logit, l_pad, 0, T, ll, h, head_row, m, l, o,
                                                      reinterpret_cast<const uint8_t*>(s_deadw), mask_ready, nrep, h * nrep);
@@ -328,9 +350,9 @@ hipError_t launch_fused(const EkvAttnArgs& a, const EkvScoreArgs& sc, int layer_
 
 }  // namespace
 
-#define EKV_CAT_(a, b, c, t) a##b##_##c##t
-#define EKV_CAT(a, b, c, t) EKV_CAT_(a, b, c, t)
-#define EKV_SYM(name) EKV_CAT(name, EKV_D, EKV_ROPE_TAG, EKV_DT_TAG)
+#define EKV_CAT_(a, b, c, t, k) a##b##_##c##t##k
+#define EKV_CAT(a, b, c, t, k) EKV_CAT_(a, b, c, t, k)
+#define EKV_SYM(name) EKV_CAT(name, EKV_D, EKV_ROPE_TAG, EKV_DT_TAG, EKV_KV_TAG)
 
 hipError_t EKV_SYM(ekv_launch_attn_decode_d)(const EkvAttnArgs& a, int rep, int layer_count, hipStream_t s) {
   if (rep < 1) return hipErrorInvalidValue;
@@ -353,7 +375,7 @@ hipError_t EKV_SYM(ekv_launch_decode_fused_d)(const EkvAttnArgs& a, const EkvSco
   }
 }
 
-#if !EKV_BF16   // (the LDS layout does not depend on the element type)
+#if !EKV_BF16 && !EKV_KV8   // (the LDS layout does not depend on the element type)
 size_t EKV_SYM(ekv_fused_lds_d)(int rep, int t_pad, int l_pad, int nw) {
   switch (rep) {
     case 1: return nw == 8 ? fused_lds<1, 8>(t_pad, l_pad, 3) : fused_lds<1, 4>(t_pad, l_pad, 3);

@@ -1,0 +1,7 @@
+// FP8-row ("kv8") instance of ekv_attn_decode.inc: head_dim 64, plain keys, bf16 queries / outputs
+#define EKV_KV8 1
+#define EKV_BF16 1
+#define EKV_D 64
+#define EKV_ROPE false
+#define EKV_ROPE_TAG plain
+#include "ekv_attn_decode.inc"

@@ -36,6 +36,15 @@ hipError_t ekv_launch_attn_decode_d96_plain_bf16(const EkvAttnArgs&, int, int, h
 hipError_t ekv_launch_decode_fused_d96_plain_bf16(const EkvAttnArgs&, const EkvScoreArgs&, int, int, int, hipStream_t);
 hipError_t ekv_launch_attn_decode_d128_plain_bf16(const EkvAttnArgs&, int, int, hipStream_t);
 hipError_t ekv_launch_decode_fused_d128_plain_bf16(const EkvAttnArgs&, const EkvScoreArgs&, int, int, int, hipStream_t);
+// FP8-row ("kv8") instances: plain keys, head_dim 64 / 128, fp16 or bf16 queries / outputs
+hipError_t ekv_launch_attn_decode_d64_plain_kv8(const EkvAttnArgs&, int, int, hipStream_t);
+hipError_t ekv_launch_decode_fused_d64_plain_kv8(const EkvAttnArgs&, const EkvScoreArgs&, int, int, int, hipStream_t);
+hipError_t ekv_launch_attn_decode_d128_plain_kv8(const EkvAttnArgs&, int, int, hipStream_t);
+hipError_t ekv_launch_decode_fused_d128_plain_kv8(const EkvAttnArgs&, const EkvScoreArgs&, int, int, int, hipStream_t);
+hipError_t ekv_launch_attn_decode_d64_plain_bf16_kv8(const EkvAttnArgs&, int, int, hipStream_t);
+hipError_t ekv_launch_decode_fused_d64_plain_bf16_kv8(const EkvAttnArgs&, const EkvScoreArgs&, int, int, int, hipStream_t);
+hipError_t ekv_launch_attn_decode_d128_plain_bf16_kv8(const EkvAttnArgs&, int, int, hipStream_t);
+hipError_t ekv_launch_decode_fused_d128_plain_bf16_kv8(const EkvAttnArgs&, const EkvScoreArgs&, int, int, int, hipStream_t);
 
 // any GQA factor (repeat_kv, llama_patch.py:19-29): factors <= 8 on the build of the next power of two, wider ones in groups of 8
 bool ekv_attn_decode_supported(int head_dim, int rep) {
@@ -51,9 +60,21 @@ bool ekv_attn_decode_supported(int head_dim, int rep) {
     case 128: return bf16 ? fn##128_plain_bf16(__VA_ARGS__) : rope ? fn##128_rope(__VA_ARGS__) : fn##128_plain(__VA_ARGS__); \
   }
 
-hipError_t ekv_launch_attn_decode(const EkvAttnArgs& a, int head_dim, int layer_count, hipStream_t s, bool bf16) {
+// (kv8: plain keys, head_dim 64 / 128, rows + scales — the planner refuses everything else before a launch)
+#define EKV_DISPATCH_KV8(fn, ...)                                                                        \
+  if (kv8) {                                                                                             \
+    if (rope || a.k_scale == nullptr || a.v_scale == nullptr) return hipErrorInvalidValue;               \
+    switch (head_dim) {                                                                                  \
+      case 64: return bf16 ? fn##64_plain_bf16_kv8(__VA_ARGS__) : fn##64_plain_kv8(__VA_ARGS__);         \
+      case 128: return bf16 ? fn##128_plain_bf16_kv8(__VA_ARGS__) : fn##128_plain_kv8(__VA_ARGS__);      \
+    }                                                                                                    \
+    return hipErrorInvalidValue;                                                                         \
+  }
+
+hipError_t ekv_launch_attn_decode(const EkvAttnArgs& a, int head_dim, int layer_count, hipStream_t s, bool bf16, bool kv8) {
   const int rep = a.n_q_heads / a.n_kv_heads;
   const bool rope = a.rope_cos != nullptr;
+  EKV_DISPATCH_KV8(ekv_launch_attn_decode_d, a, rep, layer_count, s)
   if (bf16 && rope) return hipErrorInvalidValue;
   EKV_DISPATCH(ekv_launch_attn_decode_d, a, rep, layer_count, s)
   return hipErrorInvalidValue;
@@ -81,9 +102,10 @@ bool ekv_decode_fused_supported(int head_dim, int rep, int n_slots, int t_pad, i
 }
 
 hipError_t ekv_launch_decode_fused(const EkvAttnArgs& a, const EkvScoreArgs& sc, int head_dim, int layer_count, int nw,
-                                   hipStream_t s, bool bf16) {
+                                   hipStream_t s, bool bf16, bool kv8) {
   const int rep = a.n_q_heads / a.n_kv_heads;
   const bool rope = a.rope_cos != nullptr;
+  EKV_DISPATCH_KV8(ekv_launch_decode_fused_d, a, sc, rep, layer_count, nw, s)
   if (bf16 && rope) return hipErrorInvalidValue;
   EKV_DISPATCH(ekv_launch_decode_fused_d, a, sc, rep, layer_count, nw, s)
   return hipErrorInvalidValue;

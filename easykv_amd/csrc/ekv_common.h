@@ -66,6 +66,72 @@ __device__ __forceinline__ void ekv_axpy8(float p, const uint4& v, float (&o)[8]
   for (int i = 0; i < 8; ++i) o[i] = fmaf(p, (float)h[i], o[i]);
 }
 
+// ---- FP8 K/V rows ("kv8", include/easykv_hip.h): OCP e4m3fn codes, one fp32 scale per row, value = code * scale ----
+// A lane's 16-byte piece of a row is 16 codes.  Widening a code to f16 / bf16 / f32 is exact (3 mantissa bits, 2^-9 .. 448), so the
+// K side runs on the packed-pair dot product of the 16-bit builds (v_cvt_scalef32_pk_{f16,bf16}_fp8 with scale 1) and the V side on
+// v_cvt_pk_f32_fp8 + fma; the row scales are applied to the fp32 logit and to p.
+#define EKV_FP8_MAX 448.f
+template <bool HI>
+__device__ __forceinline__ ekv_h2 ekv_fp8_pk_e(uint32_t w) {
+#if EKV_BF16
+  return __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, HI);
+#else
+  return __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w, 1.0f, HI);
+#endif
+}
+// 16 query elements (q0: 0..7, q1: 8..15) . 16 codes
+__device__ __forceinline__ float ekv_dot16_fp8(const uint4& q0, const uint4& q1, const uint4& c, float acc) {
+  acc = EKV_FDOT2(__builtin_bit_cast(ekv_h2, q0.x), ekv_fp8_pk_e<false>(c.x), acc, false);
+  acc = EKV_FDOT2(__builtin_bit_cast(ekv_h2, q0.y), ekv_fp8_pk_e<true>(c.x), acc, false);
+  acc = EKV_FDOT2(__builtin_bit_cast(ekv_h2, q0.z), ekv_fp8_pk_e<false>(c.y), acc, false);
+  acc = EKV_FDOT2(__builtin_bit_cast(ekv_h2, q0.w), ekv_fp8_pk_e<true>(c.y), acc, false);
+  acc = EKV_FDOT2(__builtin_bit_cast(ekv_h2, q1.x), ekv_fp8_pk_e<false>(c.z), acc, false);
+  acc = EKV_FDOT2(__builtin_bit_cast(ekv_h2, q1.y), ekv_fp8_pk_e<true>(c.z), acc, false);
+  acc = EKV_FDOT2(__builtin_bit_cast(ekv_h2, q1.z), ekv_fp8_pk_e<false>(c.w), acc, false);
+  acc = EKV_FDOT2(__builtin_bit_cast(ekv_h2, q1.w), ekv_fp8_pk_e<true>(c.w), acc, false);
+  return acc;
+}
+__device__ __forceinline__ void ekv_fp8_widen4(uint32_t w, float* f) {
+  const ekv_f2 lo = __builtin_amdgcn_cvt_pk_f32_fp8(w, false), hi = __builtin_amdgcn_cvt_pk_f32_fp8(w, true);
+  f[0] = lo[0], f[1] = lo[1], f[2] = hi[0], f[3] = hi[1];
+}
+// o[0..16) += p * codes   (p already carries the row's V scale)
+__device__ __forceinline__ void ekv_axpy16_fp8(float p, const uint4& c, float (&o)[16]) {
+  float f[16];
+  ekv_fp8_widen4(c.x, f), ekv_fp8_widen4(c.y, f + 4), ekv_fp8_widen4(c.z, f + 8), ekv_fp8_widen4(c.w, f + 12);
+#pragma unroll
+  for (int i = 0; i < 16; ++i) o[i] = fmaf(p, f[i], o[i]);
+}
+// The quantisation rule of a row (include/easykv_hip.h): s = amax / 448 (1 for an all-zero row), code = RNE(x / s).  The division is
+// the correctly rounded fp32 one, so x / s is bit for bit what the rule's restatement in torch computes; |x / s| <= 448 * (1 + 2^-23)
+// rounds to a finite code, nothing saturates.
+__device__ __forceinline__ float ekv_fp8_row_scale(float amax) { return amax == 0.f ? 1.f : amax / EKV_FP8_MAX; }
+__device__ __forceinline__ uint32_t ekv_fp8_quant4(float a, float b, float c, float d, float s) {
+  int w = __builtin_amdgcn_cvt_pk_fp8_f32(a / s, b / s, 0, false);
+  w = __builtin_amdgcn_cvt_pk_fp8_f32(c / s, d / s, w, true);
+  return (uint32_t)w;
+}
+// max over aligned groups of LPR consecutive lanes (the lane pattern of ekv_group_sum)
+template <int LPR>
+__device__ __forceinline__ float ekv_group_max(float x) {
+  x = fmaxf(x, ekv_dpp<0xB1>(x));
+  x = fmaxf(x, ekv_dpp<0x4E>(x));
+  if (LPR >= 8) x = fmaxf(x, ekv_dpp<0x141>(x));
+  if (LPR >= 16) x = fmaxf(x, ekv_dpp<0x140>(x));
+  return x;
+}
+// |x| of the 8 16-bit elements of a 16-byte piece, widened to f32
+__device__ __forceinline__ float ekv_widen8_amax(const uint4& v, float* f) {
+  const ekv_h8 h = __builtin_bit_cast(ekv_h8, v);
+  float m = 0.f;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    f[i] = (float)h[i];
+    m = fmaxf(m, fabsf(f[i]));
+  }
+  return m;
+}
+
 // f32 -> one 16-bit output element, rounded to nearest even (bf16: v_cvt_pk_bf16_f32, NaN kept), as the __half the row pointers hold
 __device__ __forceinline__ __half ekv_to_e(float x) {
 #if EKV_BF16

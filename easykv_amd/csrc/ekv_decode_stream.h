@@ -13,9 +13,10 @@ constexpr int kU = 8;   // rows in flight per lane group (K and V each)
 
 // head_dim 96 (any head_dim that is a multiple of 16 but not a power of two): a row keeps a power-of-two lane group (LPR = 16) of
 // which only the first LIVE = D / 8 lanes hold a 16-byte piece; the idle lanes carry zeros through the dot products and reductions.
-template <int D, int NW = 4, int KU = kU>
+// EPL = elements per 16-byte piece: 8 (16-bit rows) or 16 (FP8 rows, "kv8": a head_dim-128 row is 8 lanes, head_dim 64 is 4).
+template <int D, int NW = 4, int KU = kU, int EPL = 8>
 struct EkvDecodeGeom {
-  static constexpr int LIVE = D / 8;  // lanes of a row's lane group that hold a 16-byte piece
+  static constexpr int LIVE = D / EPL;  // lanes of a row's lane group that hold a 16-byte piece
   static constexpr int LPR = LIVE <= 4 ? 4 : (LIVE <= 8 ? 8 : 16);   // lanes per row (power of two)
   static constexpr int G = 64 / LPR;  // rows per wave-load
   static constexpr int RW = G * KU;   // rows per wave per iteration
@@ -47,14 +48,24 @@ struct EkvNoop {
 #ifndef EKV_ROPE_MOCK
 #define EKV_ROPE_MOCK 0      // experiment builds of the RoPE-on-read decode stream: 1 = no table loads, 2 = no partner exchange
 #endif
-template <int D, int REP, bool ROPE, bool SLOT_LDS, int NW = 4, bool PHYS = false, int KU = kU, typename MaskReady = EkvNoop>
+//
+// FP8 rows (EPL = 16, deduced from `o`; plain keys, head_dim 64 / 128): a.k / a.v are the code planes, one byte per element, and
+// a.k_scale / a.v_scale the fp32 row scales at the same physical index.  A lane's piece is 16 codes against 16 query elements; the
+// codes are widened in registers (ekv_common.h), logit = (q . codes) * k_scale[row] / sm_div, and v_scale[row] is folded into p
+// before the axpy.  The scales of an iteration's KU rows are read as 16-byte vectors when the rows are consecutive (PHYS) and per row
+// through the slot map otherwise.  The appended row is quantised here (row maximum over the lane group, codes + scale stored) and
+// takes part in the step AS QUANTISED, so the bank's contents alone determine the step.
+template <int D, int REP, bool ROPE, bool SLOT_LDS, int NW = 4, bool PHYS = false, int KU = kU, typename MaskReady = EkvNoop, int EPL = 8>
 __device__ __forceinline__ void ekv_decode_stream(const EkvAttnArgs& a, const int32_t* s_slot, float* logit_out,
                                                   int logit_stride, int t0, int t1_in, int ll, int h, size_t head_row,
-                                                  float (&m)[REP], float (&l)[REP], float (&o)[REP][8],
+                                                  float (&m)[REP], float (&l)[REP], float (&o)[REP][EPL],
                                                   const uint8_t* s_dead = nullptr, MaskReady mask_ready = MaskReady(),
                                                   int n_rep_real = 0, int q_head0 = -1) {
-  using Gm = EkvDecodeGeom<D, NW, KU>;
+  using Gm = EkvDecodeGeom<D, NW, KU, EPL>;
   constexpr int LPR = Gm::LPR, RW = Gm::RW, LIVE = Gm::LIVE;
+  constexpr bool KV8 = EPL == 16;
+  static_assert(EPL == 8 || (KV8 && !ROPE && LIVE == LPR), "FP8 rows: plain keys, head_dim 64 / 128");
+  constexpr int ESZ = KV8 ? 1 : 2;      // bytes per stored K/V element
   constexpr bool PADDED = LIVE != LPR;      // head_dim 96: lanes sub >= LIVE of a lane group are idle (zero pieces, no loads / stores)
   constexpr int kNW = NW;
   static_assert(!(PHYS && (ROPE || SLOT_LDS)), "physical-order streaming: plain keys, global slot map");
@@ -70,12 +81,13 @@ __device__ __forceinline__ void ekv_decode_stream(const EkvAttnArgs& a, const in
   const int nrep = n_rep_real > 0 ? n_rep_real : REP;
   const int hq0 = q_head0 >= 0 ? q_head0 : h * REP;
 
-  uint4 qv[REP];
+  uint4 qv[REP], qv1[REP];      // (qv1: FP8 rows, query elements 8..15 of the lane's 16)
   float qf[REP][8];  // ROPE: rotated query q' (fp32)
 #pragma unroll
   for (int r = 0; r < REP; ++r) {
     const __half* qp = a.q + ((size_t)ll * a.n_q_heads + hq0 + min(r, nrep - 1)) * D;
-    qv[r] = live_lane ? reinterpret_cast<const uint4*>(qp)[sub] : uint4{0, 0, 0, 0};
+    qv[r] = live_lane ? reinterpret_cast<const uint4*>(qp)[sub * (EPL / 8)] : uint4{0, 0, 0, 0};
+    qv1[r] = KV8 ? reinterpret_cast<const uint4*>(qp)[sub * 2 + 1] : uint4{0, 0, 0, 0};
 #pragma unroll
     for (int i = 0; i < 8; ++i) qf[r][i] = 0.f;
     if (ROPE && live_lane) {
@@ -176,7 +188,7 @@ __device__ __forceinline__ void ekv_decode_stream(const EkvAttnArgs& a, const in
     m[r] = EKV_NEG_INF;
     l[r] = 0.f;
 #pragma unroll
-    for (int i = 0; i < 8; ++i) o[r][i] = 0.f;
+    for (int i = 0; i < EPL; ++i) o[r][i] = 0.f;
   }
 
   // The appended row is peeled off the loop: its K/V come from k_new / v_new and one lane group appends and scores it AFTER
@@ -190,7 +202,27 @@ __device__ __forceinline__ void ekv_decode_stream(const EkvAttnArgs& a, const in
     const int slot_new = s_slot[t_new - slot_base];
     uint4 kn = uint4{0, 0, 0, 0}, vn = uint4{0, 0, 0, 0};
     const size_t off = (head_row + slot_new) * D;          // append: the new row goes into the recycled slot
-    if (live_lane) {
+    float ksn = 1.f, vsn = 1.f;      // FP8 rows: the new row's scales
+    if constexpr (KV8) {
+      // quantise the new row (rule: include/easykv_hip.h): row maximum over the lane group, then 16 codes per lane + one scale
+      float kf[16], vf[16];
+      const uint4* kq = reinterpret_cast<const uint4*>(k_new_row) + sub * 2;
+      const uint4* vq = reinterpret_cast<const uint4*>(v_new_row) + sub * 2;
+      float ka = fmaxf(ekv_widen8_amax(kq[0], kf), ekv_widen8_amax(kq[1], kf + 8));
+      float va = fmaxf(ekv_widen8_amax(vq[0], vf), ekv_widen8_amax(vq[1], vf + 8));
+      ksn = ekv_fp8_row_scale(ekv_group_max<LPR>(ka));
+      vsn = ekv_fp8_row_scale(ekv_group_max<LPR>(va));
+      kn = uint4{ekv_fp8_quant4(kf[0], kf[1], kf[2], kf[3], ksn), ekv_fp8_quant4(kf[4], kf[5], kf[6], kf[7], ksn),
+                 ekv_fp8_quant4(kf[8], kf[9], kf[10], kf[11], ksn), ekv_fp8_quant4(kf[12], kf[13], kf[14], kf[15], ksn)};
+      vn = uint4{ekv_fp8_quant4(vf[0], vf[1], vf[2], vf[3], vsn), ekv_fp8_quant4(vf[4], vf[5], vf[6], vf[7], vsn),
+                 ekv_fp8_quant4(vf[8], vf[9], vf[10], vf[11], vsn), ekv_fp8_quant4(vf[12], vf[13], vf[14], vf[15], vsn)};
+      reinterpret_cast<uint4*>(reinterpret_cast<uint8_t*>(a.k_w) + off)[sub] = kn;
+      reinterpret_cast<uint4*>(reinterpret_cast<uint8_t*>(a.v_w) + off)[sub] = vn;
+      if (sub == 0) {
+        a.k_scale[head_row + slot_new] = ksn;
+        a.v_scale[head_row + slot_new] = vsn;
+      }
+    } else if (live_lane) {
       kn = reinterpret_cast<const uint4*>(k_new_row)[sub];
       vn = reinterpret_cast<const uint4*>(v_new_row)[sub];
       reinterpret_cast<uint4*>(a.k_w + off)[sub] = kn;
@@ -209,10 +241,12 @@ __device__ __forceinline__ void ekv_decode_stream(const EkvAttnArgs& a, const in
         acc = 0.f;
 #pragma unroll
         for (int i = 0; i < 8; ++i) acc = fmaf(kpn[i], qf[r][i], acc);
+      } else if constexpr (KV8) {
+        acc = ekv_dot16_fp8(qv[r], qv1[r], kn, 0.f);
       } else {
         acc = ekv_dot8(qv[r], kn, 0.f);
       }
-      acc = ekv_group_sum<LPR>(acc) / a.sm_div;
+      acc = KV8 ? ekv_group_sum<LPR>(acc) * ksn / a.sm_div : ekv_group_sum<LPR>(acc) / a.sm_div;
       if (logit_out != nullptr && sub == 0 && r < nrep) logit_out[(size_t)r * logit_stride + (PHYS ? slot_new : t_new)] = acc;
       // one more row for this lane group's online softmax
       const float mn = fmaxf(m[r], acc);
@@ -220,8 +254,9 @@ __device__ __forceinline__ void ekv_decode_stream(const EkvAttnArgs& a, const in
       const float p = exp2f((acc - mn) * EKV_LOG2E);
       l[r] = l[r] * alpha + p;
 #pragma unroll
-      for (int i = 0; i < 8; ++i) o[r][i] *= alpha;
-      ekv_axpy8(p, vn, o[r]);
+      for (int i = 0; i < EPL; ++i) o[r][i] *= alpha;
+      if constexpr (KV8) ekv_axpy16_fp8(p * vsn, vn, o[r]);
+      else ekv_axpy8(p, vn, o[r]);
       m[r] = mn;
     }
   };
@@ -243,7 +278,28 @@ __device__ __forceinline__ void ekv_decode_stream(const EkvAttnArgs& a, const in
   }
   auto iteration = [&](const int base, auto&& after_issue) {
     uint4 kr[KU], vr[KU];
+    float ksc[KV8 ? KU : 1], vsc[KV8 ? KU : 1];      // FP8 rows: the scales of the KU rows
     const int j0 = base + grp * KU;
+    if constexpr (KV8 && PHYS) {
+      // consecutive physical rows: KU / 4 16-byte loads per plane (fused step: cap % 4 == 0, so head_row + j0 is 16-byte aligned); a
+      // group whose rows would run past the head's scale row reads them one by one (clamped; those rows are dead anyway)
+      if (j0 + KU <= a.cap) {
+        const float4* k4 = reinterpret_cast<const float4*>(a.k_scale + head_row + j0);
+        const float4* v4 = reinterpret_cast<const float4*>(a.v_scale + head_row + j0);
+#pragma unroll
+        for (int i = 0; i < KU / 4; ++i) {
+          const float4 kk = k4[i], vv = v4[i];
+          ksc[4 * i] = kk.x, ksc[4 * i + 1] = kk.y, ksc[4 * i + 2] = kk.z, ksc[4 * i + 3] = kk.w;
+          vsc[4 * i] = vv.x, vsc[4 * i + 1] = vv.y, vsc[4 * i + 2] = vv.z, vsc[4 * i + 3] = vv.w;
+        }
+      } else {
+#pragma unroll
+        for (int u = 0; u < KU; ++u) {
+          ksc[u] = a.k_scale[head_row + min(j0 + u, a.cap - 1)];
+          vsc[u] = a.v_scale[head_row + min(j0 + u, a.cap - 1)];
+        }
+      }
+    }
     int cur[KU];
 #pragma unroll
     for (int i = 0; i < KU / 4; ++i) {
@@ -262,8 +318,12 @@ __device__ __forceinline__ void ekv_decode_stream(const EkvAttnArgs& a, const in
       const int j = j0 + u;
       const int jj = j < t1 ? j : t1 - 1;
       const int row = PHYS ? jj : (SLOT_LDS ? s_slot[jj - t0] : (j < t1 ? cur[u] : last_slot));
-      const __half* kp = a.k + (head_row + row) * D;
-      const __half* vp = a.v + (head_row + row) * D;
+      const char* kp = reinterpret_cast<const char*>(a.k) + (head_row + row) * (D * ESZ);
+      const char* vp = reinterpret_cast<const char*>(a.v) + (head_row + row) * (D * ESZ);
+      if constexpr (KV8 && !PHYS) {      // rows through the slot map: one scale per row (the lanes of a group read the same word)
+        ksc[u] = a.k_scale[head_row + row];
+        vsc[u] = a.v_scale[head_row + row];
+      }
       // K/V rows are read exactly once per step and the cache (>1 GB) never fits L2/MALL: non-temporal loads
       // (measured on MI355X: 5.5 -> 6.1 TB/s on the pure stream)
       if (live_lane) {
@@ -281,7 +341,10 @@ __device__ __forceinline__ void ekv_decode_stream(const EkvAttnArgs& a, const in
     if (PHYS && dead8 != 0u) {   // rare: a dead row may hold anything (0 * inf = NaN in the PV accumulation)
 #pragma unroll
       for (int u = 0; u < KU; ++u)
-        if ((dead8 >> u) & 1u) vr[u] = uint4{0, 0, 0, 0};
+        if ((dead8 >> u) & 1u) {
+          vr[u] = uint4{0, 0, 0, 0};
+          if constexpr (KV8) vsc[u] = 0.f;
+        }
     }
     float sall[ROPE ? REP : 1][KU];   // ROPE: every row is rotated once, then dotted with all REP queries
     if (ROPE) {
@@ -311,8 +374,9 @@ __device__ __forceinline__ void ekv_decode_stream(const EkvAttnArgs& a, const in
         if (ROPE) {
           s[u] = sall[r][u];
         } else {
-          float acc = ekv_dot8(qv[r], kr[u], 0.f);
+          float acc = KV8 ? ekv_dot16_fp8(qv[r], qv1[r], kr[u], 0.f) : ekv_dot8(qv[r], kr[u], 0.f);
           acc = ekv_group_sum<LPR>(acc);
+          if constexpr (KV8) acc *= ksc[u];
           s[u] = (PHYS ? !((dead8 >> u) & 1u) : (j0 + u < t1)) ? acc / a.sm_div : EKV_NEG_INF;
         }
       }
@@ -336,12 +400,13 @@ __device__ __forceinline__ void ekv_decode_stream(const EkvAttnArgs& a, const in
       const float alpha = exp2f((m[r] - mn) * EKV_LOG2E);
       l[r] *= alpha;
 #pragma unroll
-      for (int i = 0; i < 8; ++i) o[r][i] *= alpha;
+      for (int i = 0; i < EPL; ++i) o[r][i] *= alpha;
 #pragma unroll
       for (int u = 0; u < KU; ++u) {
         const float p = exp2f((s[u] - mn) * EKV_LOG2E);
         l[r] += p;
-        ekv_axpy8(p, vr[u], o[r]);
+        if constexpr (KV8) ekv_axpy16_fp8(p * vsc[u], vr[u], o[r]);
+        else ekv_axpy8(p, vr[u], o[r]);
       }
       m[r] = mn;
     }
@@ -361,9 +426,9 @@ __device__ __forceinline__ void ekv_decode_stream(const EkvAttnArgs& a, const in
 
 // Combine the G lane groups of a wave (flash-decoding merge over lanes LPR, 2*LPR, ... apart); afterwards every lane
 // holds the wave's (m, l, o) for its 8-wide slice of head_dim.
-template <int D, int REP>
-__device__ __forceinline__ void ekv_decode_wave_combine(float (&m)[REP], float (&l)[REP], float (&o)[REP][8]) {
-  using Gm = EkvDecodeGeom<D>;
+template <int D, int REP, int EPL = 8>
+__device__ __forceinline__ void ekv_decode_wave_combine(float (&m)[REP], float (&l)[REP], float (&o)[REP][EPL]) {
+  using Gm = EkvDecodeGeom<D, 4, kU, EPL>;
 #pragma unroll
   for (int off = Gm::LPR; off < 64; off <<= 1) {
 #pragma unroll
@@ -374,17 +439,17 @@ __device__ __forceinline__ void ekv_decode_wave_combine(float (&m)[REP], float (
       const float wb = (mo == EKV_NEG_INF) ? 0.f : exp2f((mo - mn) * EKV_LOG2E);
       l[r] = l[r] * wa + lo * wb;
 #pragma unroll
-      for (int i = 0; i < 8; ++i) o[r][i] = o[r][i] * wa + __shfl_xor(o[r][i], off, 64) * wb;
+      for (int i = 0; i < EPL; ++i) o[r][i] = o[r][i] * wa + __shfl_xor(o[r][i], off, 64) * wb;
       m[r] = mn;
     }
   }
 }
 
 // Wave partials -> LDS (call after ekv_decode_wave_combine, then __syncthreads(), then ekv_decode_reduce).
-template <int D, int REP, int NW = 4>
+template <int D, int REP, int NW = 4, int EPL = 8>
 __device__ __forceinline__ void ekv_decode_stash(float* s_part, const float (&m)[REP], const float (&l)[REP],
-                                                 const float (&o)[REP][8]) {
-  using Gm = EkvDecodeGeom<D, NW>;
+                                                 const float (&o)[REP][EPL]) {
+  using Gm = EkvDecodeGeom<D, NW, kU, EPL>;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int sub = lane % Gm::LPR, grp = lane / Gm::LPR;
   if (grp != 0 || sub >= Gm::LIVE) return;
@@ -396,7 +461,7 @@ __device__ __forceinline__ void ekv_decode_stash(float* s_part, const float (&m)
       p[1] = l[r];
     }
 #pragma unroll
-    for (int i = 0; i < 8; ++i) p[2 + sub * 8 + i] = o[r][i];
+    for (int i = 0; i < EPL; ++i) p[2 + sub * EPL + i] = o[r][i];
   }
 }
 

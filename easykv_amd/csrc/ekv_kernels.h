@@ -39,6 +39,7 @@ struct EkvStepPlan {
   int32_t flush_unsplit;    // deferred flush: the column-sum pass runs unsplit over the one pass's key-range statistics
   int32_t slot_rows, slot_tail_ok;   // fused decode step on the slot-indexed score rows (EKV_PHASE_SLOT_ROWS / _TAIL_OK)
   int32_t bf16;             // 16-bit tensors are bf16: the launches run the EKV_BF16 kernel instances
+  int32_t kv8;              // the bank's K/V rows are FP8 codes + row scales (ekv_plan_step_kv8): the decode launches run the kv8 instances
   int32_t strides[6];       // q, kv, out row strides (token, head) in elements, the dense layout filled in
   // Workspace: byte offsets of this call's slices (a deferred call's layout spans every deferred layer), -1 = not in the layout
   int64_t logits;     // [layer_count][Hq][q_len][t_pad]   raw q.k/sm_div of every live position
@@ -57,6 +58,9 @@ struct EkvStepPlan {
 // dtype: EKV_DTYPE_F16 / EKV_DTYPE_BF16 (any other value: EKV_E_ARG).  A bf16 step plans exactly as the fp16 step (same tiling, launch
 // list and workspace) and runs the bf16 instances of the same kernels; RoPE-on-read has no bf16 build (EKV_E_UNSUPPORTED, no launches).
 int ekv_plan_step(const ekv_bank* bank, const ekv_step* step, int32_t dtype, EkvStepPlan* plan);
+// The same plan for a step on FP8 rows (`bank` with k / v standing for the code planes): what the 16-bit step of that shape plans,
+// with plan->kv8 set — or EKV_E_UNSUPPORTED (nothing to launch) for q_len > 1, rope_on_read and head_dim other than 64 / 128.
+int ekv_plan_step_kv8(const ekv_bank* bank, const ekv_step* step, int32_t dtype, EkvStepPlan* plan);
 
 // The __half* members below point at 16-bit rows: fp16, or bf16 for the EKV_BF16 kernel instances (ekv_common.h: rows move as
 // bytes, and every element access of a kernel goes through ekv_e / ekv_h8 / ekv_to_e).
@@ -77,8 +81,17 @@ struct EkvAttnArgs {
   __half* q_rot_lo;
   float* row_stats;    // with out_direct, one-pass scored steps: [layer_count][Hq][q_len][2] final (max, sum exp) per query row
   __half* out_direct;  // chunk kernels, unsplit heads: fold the two key halves in the kernel and write the fp16 output here
-  float* stats;      // two-pass chunk steps: [layer_count][Hq][q_len][2*n_split][2] (max, sum exp) per key-range half split
-  float* colsum;     // two-pass chunk steps: [layer_count][H][n_col_parts][2][t_pad] column sums of pbar and pbar^2
+  // FP8 rows (ekv_kv8_step_attend; the decode kernels' kv8 instances only — decode steps have no use for `stats` / `colsum`, whose
+  // storage the two pointers share, so the struct and with it every 16-bit kernel instance stays as it was): k / v / k_w / v_w are the
+  // code planes, one byte per element, and k_scale / v_scale the fp32 row scales [n_layers][H][cap] at the rows' physical indices
+  union {
+    float* stats;      // two-pass chunk steps: [layer_count][Hq][q_len][2*n_split][2] (max, sum exp) per key-range half split
+    float* k_scale;
+  };
+  union {
+    float* colsum;     // two-pass chunk steps: [layer_count][H][n_col_parts][2][t_pad] column sums of pbar and pbar^2
+    float* v_scale;
+  };
   int32_t n_col_parts;   // = query-tile waves per workgroup (2 or 4) * n_qblocks
   int32_t n_q_heads, n_kv_heads, cap, n_slots, q_len, n_split, rows_per_split, t_pad, layer_begin, causal;
   int32_t qb_rows, n_qblocks;  // chunk kernels: queries per query block, number of query blocks
@@ -132,7 +145,7 @@ struct EkvScoreArgs {
 
 // bf16 (the launchers below that take it): run the EKV_BF16 instances — 16-bit rows of q, k_new, v_new, out and the bank read and
 // written as bf16 (ekv_common.h); the planner never sends a RoPE-on-read step there
-hipError_t ekv_launch_attn_decode(const EkvAttnArgs& a, int head_dim, int layer_count, hipStream_t s, bool bf16);
+hipError_t ekv_launch_attn_decode(const EkvAttnArgs& a, int head_dim, int layer_count, hipStream_t s, bool bf16, bool kv8 = false);
 // passes (wide-block kernel, two-pass scheme): bit 0 = the one pass (output + row statistics), bit 1 = the column-sum pass
 // tail_sc (wide-block kernel, two passes, passes & 2): the step's scorer runs as the tail of the column-sum pass (ekv_wide_tail.h)
 // wide: the wide-block kernel (ekv_chunk_wide, decided by the planner)
@@ -157,7 +170,12 @@ bool ekv_attn_decode_supported(int head_dim, int rep);
 int ekv_decode_fused_nw(int n_heads_in_launch);
 bool ekv_decode_fused_supported(int head_dim, int rep, int n_slots, int t_pad, int l_pad, int n_evict, int cap, int nw);
 hipError_t ekv_launch_decode_fused(const EkvAttnArgs& a, const EkvScoreArgs& sc, int head_dim, int layer_count, int nw, hipStream_t s,
-                                   bool bf16);
+                                   bool bf16, bool kv8 = false);
+// FP8 bank conversion (ekv_kv8.hip).  src_bf16: the 16-bit rows are bf16; out_kind: 0 fp16, 1 bf16, 2 fp32
+hipError_t ekv_launch_kv8_quantize(const ekv_bank* bank, const ekv_kv8* q8, bool src_bf16, int layer_begin, int layer_count, int extent,
+                                   hipStream_t s);
+hipError_t ekv_launch_kv8_dequantize(const ekv_bank* bank, const ekv_kv8* q8, int out_kind, int layer_begin, int layer_count, int extent,
+                                     void* k_out, void* v_out, hipStream_t s);
 bool ekv_attn_chunk_supported(int head_dim, int rep, int q_len);
 void ekv_chunk_blocks(int rep, int q_len, int* qb_rows, int* n_qblocks, int* qpw);
 int ekv_chunk_col_parts(int qpw, bool rope);

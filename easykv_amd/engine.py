@@ -98,6 +98,7 @@ class KVBank:
 
     default_two_pass = 0    # StepPlan.two_pass used when a plan leaves it at 0 (tests force either chunk scheme with it)
     dtype, _dt = torch.float16, _lib.DTYPE_F16      # (set per bank by __init__)
+    kv_quant, _kv8 = None, None      # quantize_fp8(): "fp8" and the ekv_kv8 descriptor of the code planes / row scales
 
     def __init__(self, n_layers, n_q_heads, n_kv_heads, head_dim, cap, device="cuda", scored=True, dtype=torch.float16):
         if dtype not in _lib.DTYPE_CODES:
@@ -203,7 +204,7 @@ class KVBank:
         if ok is None:
             if len(self._slot_ok) > 4096:      # (a growing cache asks about a new shape every step)
                 self._slot_ok.clear()
-            ok = self._slot_ok[key] = self.lib.ekv_step_check_typed(C.byref(self._bank), C.byref(st), self._dt) == 0
+            ok = self._slot_ok[key] = self._step_check(st) == 0
         st.phases = 0
         if not ok:
             return False
@@ -237,6 +238,79 @@ class KVBank:
     def score_cnt(self):
         self._ensure_ordered()
         return self._score_cnt
+
+    # -- FP8 K/V storage ("kv8", include/easykv_hip.h) ----------------------------------------------
+    def _kv8_refuse(self, cond, what):
+        if cond and self._kv8 is not None:
+            raise _lib.EkvError(f"{what} is not available on a bank quantised by quantize_fp8(): its K/V rows are FP8 codes with per-row "
+                                "scales, which only decode steps (q_len == 1, plain keys) read and append to")
+
+    def quantize_fp8(self):
+        """Convert the live bank in place to FP8 (OCP e4m3fn) K/V rows with one fp32 scale per row: codes and scales are written at the
+        rows' physical indices (slot map, free list and score rows carry over as they are, in either layout), the 16-bit K/V tensors
+        are released, and ``attend`` / ``step_info`` / ``step_plan`` go to the kv8 calls.  From here on the bank serves decode steps
+        only: chunk steps, ``load_rows``, ``set_rope`` and the row moves raise :class:`EkvError`."""
+        if self._kv8 is not None:
+            return self
+        if self.head_dim not in (64, 128):
+            raise _lib.EkvError(f"quantize_fp8(): FP8 rows are built for head_dim 64 and 128, not {self.head_dim}")
+        if self.rope_cos is not None:
+            raise _lib.EkvError("quantize_fp8(): a RoPE-on-read (streaming) bank keeps un-rotated keys, which the FP8 decode kernels do not rotate")
+        if self._defer is not None and self._defer["pending"]:
+            raise _lib.EkvError("quantize_fp8(): a deferred token step is open (flush() first)")
+        if torch.cuda.is_current_stream_capturing():
+            raise _lib.EkvError("quantize_fp8() cannot be captured in a graph: convert the bank before the capture")
+        self.join()
+        shape = (self.n_layers, self.n_kv_heads, self.cap)
+        # rows that were never written keep code 0 / scale 1: every scale of the bank is finite whatever the kernels prefetch
+        self.k8 = torch.zeros(*shape, self.head_dim, dtype=torch.uint8, device=self.device)
+        self.v8 = torch.zeros_like(self.k8)
+        self.k_scale = torch.ones(*shape, dtype=torch.float32, device=self.device)
+        self.v_scale = torch.ones_like(self.k_scale)
+        kv8 = _lib.Kv8(self.k8.data_ptr(), self.v8.data_ptr(), self.k_scale.data_ptr(), self.v_scale.data_ptr())
+        check(self.lib.ekv_kv8_quantize(C.byref(self._bank), C.byref(kv8), self._dt, 0, self.n_layers, max(self.extent), self._stream()),
+              "ekv_kv8_quantize")
+        cur = torch.cuda.current_stream(self.device)
+        self.k.record_stream(cur)
+        self.v.record_stream(cur)
+        self.k = self.v = None
+        # the descriptor's planes stand where the rows were: the planning calls that take the bank alone never dereference them
+        self._bank.k, self._bank.v = self.k8.data_ptr(), self.v8.data_ptr()
+        self._kv8, self.kv_quant = kv8, "fp8"
+        self._slot_ok.clear()
+        self._defer = None
+        return self
+
+    def kv_bytes(self) -> int:
+        """Bytes held for the K/V rows: 16-bit rows, or FP8 codes + row scales (``2 * head_dim + 8`` per row pair)."""
+        rows = self.n_layers * self.n_kv_heads * self.cap
+        return rows * (2 * self.head_dim + 8) if self._kv8 is not None else rows * 4 * self.head_dim
+
+    def dequantized_rows(self, layer):
+        """(K, V) ``[H, cap, head_dim]`` fp32 of the PHYSICAL rows of ``layer``: code * scale of a quantised bank (exact), the 16-bit rows
+        of any other widened.  Rows that were never written read as zeros on a quantised bank.  For tests and tools."""
+        if self._kv8 is None:
+            return self.k[layer].float(), self.v[layer].float()
+        k = torch.empty(self.n_kv_heads, self.cap, self.head_dim, dtype=torch.float32, device=self.device)
+        v = torch.empty_like(k)
+        check(self.lib.ekv_kv8_dequantize(C.byref(self._bank), C.byref(self._kv8), _lib.DTYPE_F32, layer, 1, self.cap, _ptr(k), _ptr(v),
+                                          self._stream()), "ekv_kv8_dequantize")
+        return k, v
+
+    def _step_check(self, st):
+        if self._kv8 is not None:
+            return self.lib.ekv_kv8_step_check(C.byref(self._bank), C.byref(st), self._dt, C.byref(self._kv8))
+        return self.lib.ekv_step_check_typed(C.byref(self._bank), C.byref(st), self._dt)
+
+    def _step_ws_bytes(self, st):
+        if self._kv8 is not None:
+            return self.lib.ekv_kv8_workspace_bytes(C.byref(self._bank), C.byref(st), self._dt, C.byref(self._kv8))
+        return self.lib.ekv_workspace_bytes_typed(C.byref(self._bank), C.byref(st), self._dt)
+
+    def _step_attend(self, st, *args):
+        if self._kv8 is not None:
+            return self.lib.ekv_kv8_step_attend(C.byref(self._bank), C.byref(st), self._dt, C.byref(self._kv8), *args)
+        return self.lib.ekv_step_attend_typed(C.byref(self._bank), C.byref(st), self._dt, *args)
 
     # -- plumbing -----------------------------------------------------------------------------
     def _stream(self):
@@ -283,6 +357,7 @@ class KVBank:
 
     def set_rope(self, cos, sin):
         """fp32 tables ``[>= cap, head_dim]`` for the streaming (rope-on-read) variant."""
+        self._kv8_refuse(True, "set_rope (RoPE-on-read)")
         self.rope_cos = cos.to(self.device, torch.float32).contiguous()
         self.rope_sin = sin.to(self.device, torch.float32).contiguous()
         half = self.head_dim // 2
@@ -305,6 +380,7 @@ class KVBank:
     def load_rows(self, k, v, pos_begin=None, layer_begin=0):
         """Append ordered rows ``[layers, H, n, D]`` at positions [pos_begin, pos_begin+n)."""
         lc, n = k.shape[0], k.shape[2]
+        self._kv8_refuse(True, "load_rows")
         self._ensure_ordered(layer_begin, lc)
         pos = self.n_slots[layer_begin] if pos_begin is None else pos_begin
         k = k.to(self.device, self.dtype).contiguous()
@@ -317,6 +393,7 @@ class KVBank:
     def ordered_kv(self, layer_begin=0, layer_count=None):
         """The ordered ``[layers, H, T, D]`` view the HF legacy tuple needs (birth order)."""
         lc = self.n_layers - layer_begin if layer_count is None else layer_count
+        self._kv8_refuse(True, "ordered_kv (a row move)")
         self._ensure_ordered(layer_begin, lc)
         t = self.n_slots[layer_begin]
         k = torch.empty(lc, self.n_kv_heads, t, self.head_dim, dtype=self.dtype, device=self.device)
@@ -327,6 +404,7 @@ class KVBank:
     def compact_inplace(self, evict_ids, layer_begin=0):
         """Reference-shaped physical compaction for a bank kept in identity layout."""
         lc, _, kk = evict_ids.shape
+        self._kv8_refuse(True, "compact_inplace (a row move)")
         self._ensure_ordered(layer_begin, lc)
         t = self.n_slots[layer_begin]
         ids = evict_ids.to(self.device, torch.int32).contiguous()
@@ -371,6 +449,9 @@ class KVBank:
         """(n_split, fused) the library will use for this step."""
         st = self.make_step(plan, q_len, layer_begin, self.n_layers - layer_begin if layer_count is None else layer_count)
         st.phases = phases
+        if self._kv8 is not None:      # (the kv8 dry run: a step the FP8 bank refuses plans as not fused)
+            info = self.step_info(plan, q_len, layer_begin, layer_count, phases)
+            return info["n_split"], bool(info["fused"])
         ns, fu = C.c_int32(0), C.c_int32(0)
         check(self.lib.ekv_step_plan(C.byref(self._bank), C.byref(st), C.byref(ns), C.byref(fu)), "ekv_step_plan")
         return ns.value, bool(fu.value)
@@ -380,7 +461,10 @@ class KVBank:
         st = self.make_step(plan, q_len, layer_begin, self.n_layers - layer_begin if layer_count is None else layer_count)
         st.phases = phases
         info = (C.c_int32 * 9)()
-        check(self.lib.ekv_step_info_typed(C.byref(self._bank), C.byref(st), self._dt, info, 9), "ekv_step_info")
+        if self._kv8 is not None:
+            check(self.lib.ekv_kv8_step_info(C.byref(self._bank), C.byref(st), self._dt, C.byref(self._kv8), info, 9), "ekv_kv8_step_info")
+        else:
+            check(self.lib.ekv_step_info_typed(C.byref(self._bank), C.byref(st), self._dt, info, 9), "ekv_step_info")
         keys = ("n_split", "fused", "two_pass", "wide", "n_qblocks", "qb_rows", "n_col_parts", "fold_in_kernel", "n_launches")
         return dict(zip(keys, (int(x) for x in info)))
 
@@ -399,7 +483,7 @@ class KVBank:
         if self._side is None:
             self._side = [torch.cuda.Stream(self.device) for _ in range(4)]
         main = torch.cuda.current_stream(self.device)
-        need = self.lib.ekv_workspace_bytes_typed(C.byref(self._bank), C.byref(st), self._dt)
+        need = self._step_ws_bytes(st)
         if not self._ws_ring or self._ws_ring[0].numel() < need:
             self._ws_ring = [torch.empty(int(need * 1.25) + 4096, dtype=torch.uint8, device=self.device) for _ in range(8)]
             self._ws_free = [None] * 8
@@ -412,13 +496,13 @@ class KVBank:
         args = (_ptr(q), _ptr(k_new), _ptr(v_new), _ptr(out), _ptr(evict_ids) if st.n_evict > 0 else None,
                 _ptr(self.rope_cos), _ptr(self.rope_sin), _ptr(ws), ws.numel())
         st.phases = 1 | 4
-        check(self.lib.ekv_step_attend_typed(C.byref(self._bank), C.byref(st), self._dt, *args, C.c_void_p(main.cuda_stream)), "ekv_step_attend")
+        check(self._step_attend(st, *args, C.c_void_p(main.cuda_stream)), "ekv_step_attend")
         ready = torch.cuda.Event()
         ready.record(main)
         side = self._side[slot % len(self._side)]
         side.wait_event(ready)
         st.phases = 8
-        check(self.lib.ekv_step_attend_typed(C.byref(self._bank), C.byref(st), self._dt, *args, C.c_void_p(side.cuda_stream)), "ekv_step_attend")
+        check(self._step_attend(st, *args, C.c_void_p(side.cuda_stream)), "ekv_step_attend")
         done = torch.cuda.Event()
         done.record(side)
         self._ws_free[slot] = done
@@ -433,6 +517,7 @@ class KVBank:
         96-row chunk step of the Llama2-7B shape: 66 us of a 124 us layer).  Decode steps and, since round 4, chunk steps."""
         d = self._defer
         n = q.shape[2]
+        self._kv8_refuse(n > 1, "a chunk step (q_len > 1)")
         t = self.n_slots[layer] + n
         if self._slot_rows[layer]:
             self._ensure_ordered()      # (all layers in one launch: the conversion ranks births by counting, ~0.2 ms per launch of <= 256 heads)
@@ -449,15 +534,20 @@ class KVBank:
             # the scorer shape of the flush() call (phases = 8 over all layers) is validated NOW, before the first layer's
             # attention appends a row: a shape only the last call of the token would refuse must not leave the bank half-stepped
             st.layer_begin, st.layer_count, st.defer_index, st.phases = 0, self.n_layers, 0, 8
-            check(self.lib.ekv_step_check_typed(C.byref(self._bank), C.byref(st), self._dt), "ekv_step_check (deferred scorer)")
-            need = self.lib.ekv_workspace_bytes_typed(C.byref(self._bank), C.byref(st), self._dt)
+            check(self._step_check(st), "ekv_step_check (deferred scorer)")
+            need = self._step_ws_bytes(st)
             ids = torch.empty(self.n_layers, self.n_kv_heads, st.n_evict, dtype=torch.int32, device=self.device) if st.n_evict > 0 else None
             ws = self._workspace(need)
             # everything that is the same for all layers of the token step is resolved once: the per-layer call below is on the
             # critical path of the decoder stack (host cost per layer ~ GPU cost per layer in this regime)
             d = self._defer = dict(plan=plan, t=t, n=n, st=st, ws=ws, ids=ids, pending=0, rope=(_ptr(self.rope_cos), _ptr(self.rope_sin)),
                                    st_ref=C.byref(st), bank_ref=C.byref(self._bank), ws_ptr=ws.data_ptr(), ws_len=ws.numel(),
-                                   stream=self._stream(), call=self.lib.ekv_step_attend_typed, dt=self._dt)
+                                   stream=self._stream())
+            # (the call and its leading arguments: the typed step, or the kv8 step with the descriptor behind the dtype)
+            if self._kv8 is not None:
+                d["call"], d["head"] = self.lib.ekv_kv8_step_attend, (d["bank_ref"], d["st_ref"], self._dt, C.byref(self._kv8))
+            else:
+                d["call"], d["head"] = self.lib.ekv_step_attend_typed, (d["bank_ref"], d["st_ref"], self._dt)
         st = d["st"]
         st.layer_begin = st.defer_index = layer
         st.layer_count, st.phases = 1, 5
@@ -466,7 +556,7 @@ class KVBank:
         if out is None:
             out = torch.empty(1, self.n_q_heads, n, self.head_dim, dtype=self.dtype, device=self.device)
         q, k_new, v_new = _stride_rows(st, q, k_new, v_new, out, self.dtype)
-        rc = d["call"](d["bank_ref"], d["st_ref"], d["dt"], q.data_ptr(), k_new.data_ptr(), v_new.data_ptr(), out.data_ptr(), None,
+        rc = d["call"](*d["head"], q.data_ptr(), k_new.data_ptr(), v_new.data_ptr(), out.data_ptr(), None,
                        d["rope"][0], d["rope"][1], d["ws_ptr"], d["ws_len"], d["stream"])
         if rc != 0:
             check(rc, "ekv_step_attend")
@@ -484,7 +574,7 @@ class KVBank:
             check(self.lib.ekv_step_plan(C.byref(self._bank), C.byref(st), C.byref(ns), C.byref(fu)), "ekv_step_plan")
             st.n_split = ns.value
         st.defer_layers, st.layer_begin, st.layer_count, st.defer_index, st.phases = self.n_layers, 0, self.n_layers, 0, 8
-        return int(self.lib.ekv_workspace_bytes_typed(C.byref(self._bank), C.byref(st), self._dt))
+        return int(self._step_ws_bytes(st))
 
     def flush(self):
         """Scorer of every layer of the token step opened by ``attend(..., defer=True)``: accumulate, select, compact — one
@@ -498,8 +588,8 @@ class KVBank:
         st.layer_begin, st.layer_count, st.defer_index, st.phases = 0, self.n_layers, 0, 8
         st.q_token_stride = st.q_head_stride = st.kv_token_stride = st.kv_head_stride = st.out_token_stride = st.out_head_stride = 0      # (no caller tensors in this call)
         st.phys_extent = max(max(self.extent), d["t"])
-        check(self.lib.ekv_step_attend_typed(C.byref(self._bank), C.byref(st), self._dt, ws.data_ptr(), ws.data_ptr(), ws.data_ptr(), ws.data_ptr(),
-                                       _ptr(d["ids"]), d["rope"][0], d["rope"][1], ws.data_ptr(), ws.numel(), d["stream"]), "ekv_step_attend")
+        check(self._step_attend(st, ws.data_ptr(), ws.data_ptr(), ws.data_ptr(), ws.data_ptr(),
+                                _ptr(d["ids"]), d["rope"][0], d["rope"][1], ws.data_ptr(), ws.numel(), d["stream"]), "ekv_step_attend")
         for l in range(self.n_layers):
             self.n_slots[l] = d["t"] - st.n_evict
         d["pending"] = 0
@@ -518,6 +608,7 @@ class KVBank:
                 raise ValueError("defer=True is for one-layer calls")
             return self._attend_deferred(plan, q, k_new, v_new, layer_begin, out), None
         lc, _, n, _ = q.shape
+        self._kv8_refuse(n > 1, "a chunk step (q_len > 1)")
         st = self.make_step(plan, n, layer_begin, lc)
         # one-launch decode steps run on the slot-indexed layout of the score rows (nothing moves on an eviction); everything else
         # on the ordered one
@@ -553,11 +644,11 @@ class KVBank:
             return out, (evict_ids if (st.n_evict > 0 and want_ids) else None)
         if any(ev is not None for ev in self._score_done[layer_begin:layer_begin + lc]):
             self.join()
-        need = self.lib.ekv_workspace_bytes_typed(C.byref(self._bank), C.byref(st), self._dt)
+        need = self._step_ws_bytes(st)
         ws = self._workspace(need)
-        check(self.lib.ekv_step_attend_typed(C.byref(self._bank), C.byref(st), self._dt, _ptr(q), _ptr(k_new), _ptr(v_new), _ptr(out),
-                                       _ptr(evict_ids) if (st.n_evict > 0 and evict_ids is not None) else None, _ptr(self.rope_cos), _ptr(self.rope_sin),
-                                       _ptr(ws), ws.numel(), self._stream()), "ekv_step_attend")
+        check(self._step_attend(st, _ptr(q), _ptr(k_new), _ptr(v_new), _ptr(out),
+                                _ptr(evict_ids) if (st.n_evict > 0 and evict_ids is not None) else None, _ptr(self.rope_cos), _ptr(self.rope_sin),
+                                _ptr(ws), ws.numel(), self._stream()), "ekv_step_attend")
         if phases != 1:     # phases == 1 launches the attention kernel only; the slot map is untouched
             for l in range(layer_begin, layer_begin + lc):
                 self.n_slots[l] = st.n_slots - st.n_evict

@@ -126,6 +126,8 @@ def main():
     ap.add_argument("--ntk-length", type=int, default=None, help="sequence length the DynamicNTK base is fixed for")
     ap.add_argument("--dtype", choices=["float16", "bfloat16"], default="float16",
                     help="model weights in this dtype; the K/V bank follows it (generation_config kv_dtype='auto')")
+    ap.add_argument("--kv-quant", choices=["fp8"], default=None,
+                    help="store the K/V rows of the decode phase as FP8 codes with per-row scales (generation_config kv_quant; not for the ppl task)")
     args = ap.parse_args()
     import easykv_amd
     from easykv_amd import set_dynamicntk_rope_length
@@ -142,7 +144,7 @@ def main():
             for budget in args.budgets or [300, 150]:
                 gen = dict(temperature=1e-9, top_p=1.0, max_new_tokens=args.max_new_tokens or 2048, budget=int(budget), kv_policy=args.kv_policy or "roco")
                 ids = tok([prompt], return_tensors="pt").input_ids.cuda()
-                out = model.easykv_generate(input_ids=ids, generation_config=dict(gen, kv_dtype="auto"))
+                out = model.easykv_generate(input_ids=ids, generation_config=dict(gen, kv_dtype="auto", kv_quant=args.kv_quant))
                 say(f"EasyKV-{gen['kv_policy']}(budget {gen['budget']}): {out}")
         elif args.task == "summarization":
             model, tok = load(args)
@@ -154,7 +156,7 @@ def main():
                 gen = dict(temperature=0.3, top_p=1.0, max_new_tokens=args.max_new_tokens or 256, budget=float(budget),
                            kv_policy=args.kv_policy or "roco", keep_attention=True)
                 ids = tok([prompt], return_tensors="pt").input_ids.cuda()
-                out = model.easykv_generate(input_ids=ids, generation_config=dict(gen, kv_dtype="auto"))
+                out = model.easykv_generate(input_ids=ids, generation_config=dict(gen, kv_dtype="auto", kv_quant=args.kv_quant))
                 say(f"EasyKV-{gen['kv_policy']}({budget * 100:.2f}%): {out}")
         elif args.task in ("passkey", "passkey_ntk"):
             ntk = args.task == "passkey_ntk"
@@ -175,7 +177,7 @@ def main():
                 for budget in args.budgets or [0.5]:
                     gen = dict(temperature=1e-9, top_p=1.0, max_new_tokens=args.max_new_tokens or 6, budget=float(budget),
                                kv_policy=args.kv_policy or "roco", keep_attention=False)
-                    out = model.easykv_generate(input_ids=ids, generation_config=dict(gen, kv_dtype="auto"))
+                    out = model.easykv_generate(input_ids=ids, generation_config=dict(gen, kv_dtype="auto", kv_quant=args.kv_quant))
                     hits += str(ex["target"]) in out
                     say((f"EasyKV-{gen['kv_policy']}({budget * 100:.2f}%):     [" + postfix + out + "]").replace("\n", "\\n"))
             say(f"retrieved {hits} of {len(examples) * len(args.budgets or [0.5])}")

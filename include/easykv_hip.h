@@ -245,6 +245,52 @@ int ekv_scatter_rows(const ekv_bank *bank, int32_t layer_begin, int32_t layer_co
 int ekv_compact_inplace(const ekv_bank *bank, int32_t layer_begin, int32_t layer_count, int32_t n_slots,
                         int32_t n_evict, const int32_t *evict_ids, void *stream);
 
+/* FP8 K/V storage with per-row scales ("kv8"; ABI 8, additive).  A bank's K/V rows may be held as
+ *
+ *   k_codes, v_codes   uint8 [n_layers][n_kv_heads][cap][head_dim]   OCP e4m3fn codes (not fnuz), one byte per element
+ *   k_scale, v_scale   fp32  [n_layers][n_kv_heads][cap]             one scale per (layer, KV head, PHYSICAL row);  value = code * scale
+ *
+ * — 2 * head_dim + 8 bytes per K+V row pair instead of 4 * head_dim (264 instead of 512 at head_dim 128).  Rows never move, so a
+ * row's scale lives at the row's physical index for the row's whole life, and the slot map, the free list and the score rows (either
+ * layout) are those of the 16-bit bank: selection reads logits, never a K/V element.
+ *
+ * Quantisation rule of a row x (normative):  amax = max |x| over the row, in fp32;  s = amax / 448  (s = 1 when amax == 0);
+ * code = round-to-nearest-even(x / s), x / s being the correctly rounded fp32 quotient.  Nothing saturates by construction.  Rows are
+ * assumed finite.  What is stored is what is attended: the row a decode step appends takes part in that step's attention AS
+ * QUANTISED, so the bank's contents alone determine the step.
+ *
+ * The descriptor carries the four planes; every other field of `bank` is used as it is, and bank->k / bank->v are NOT read by the
+ * kv8 step calls (they may be NULL once the 16-bit rows have been released). */
+typedef struct ekv_kv8 {
+  void *k_codes, *v_codes;
+  float *k_scale, *v_scale;
+} ekv_kv8;
+
+/* Bank conversion, one pass: rows [0, extent) of `layer_count` layers of the 16-bit bank (dtype: EKV_DTYPE_F16 / _BF16 = the type of
+ * bank->k / bank->v) -> codes and scales at the SAME physical indices.  Rows >= extent and the 16-bit rows are left untouched. */
+int ekv_kv8_quantize(const ekv_bank *bank, const ekv_kv8 *kv8, int32_t dtype, int32_t layer_begin, int32_t layer_count,
+                     int32_t extent, void *stream);
+/* The inverse, for tests and tooling: k_out / v_out [layer_count][n_kv_heads][extent][head_dim] <- code * scale of the physical rows
+ * [0, extent), as out_dtype: EKV_DTYPE_F16, EKV_DTYPE_BF16 (rounded to nearest even) or EKV_DTYPE_F32 (exact). */
+#define EKV_DTYPE_F32 2 /* ekv_kv8_dequantize's out_dtype only: no step takes fp32 tensors */
+int ekv_kv8_dequantize(const ekv_bank *bank, const ekv_kv8 *kv8, int32_t out_dtype, int32_t layer_begin, int32_t layer_count,
+                       int32_t extent, void *k_out, void *v_out, void *stream);
+
+/* Decode steps on a kv8 bank: the _typed calls with the descriptor; `dtype` is the type of q, k_new, v_new and out (EKV_DTYPE_F16 /
+ * _BF16, anything else EKV_E_ARG).  Accepted: q_len == 1 with plain keys at head_dim 64 / 128 — every policy, every GQA factor and
+ * every phase combination the 16-bit decode step takes (whole step incl. the one-launch kernel on either score-row layout, the split
+ * path, the deferred per-layer form), planned exactly as the 16-bit step of that shape (same splits, launches and workspace) and run
+ * on the kv8 builds of the decode attention kernels: codes are widened in registers, logit = (q . codes) * k_scale[row] / sm_div,
+ * v_scale[row] is folded into p, and the appended row is quantised by the kernel (codes + scale written to the recycled row).
+ * Everything else is EKV_E_UNSUPPORTED from the dry run, before anything is launched: q_len > 1 (chunk steps), rope_on_read,
+ * head_dim 32 / 96.  The row moves (ekv_gather_ordered, ekv_scatter_rows, ekv_compact_inplace) do not serve kv8 banks. */
+int ekv_kv8_step_check(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const ekv_kv8 *kv8);
+int ekv_kv8_step_info(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const ekv_kv8 *kv8, int32_t *info, int32_t n_info);
+size_t ekv_kv8_workspace_bytes(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const ekv_kv8 *kv8);
+int ekv_kv8_step_attend(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const ekv_kv8 *kv8, const void *q,
+                        const void *k_new, const void *v_new, void *out, int32_t *evict_ids, const float *rope_cos,
+                        const float *rope_sin, void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
