@@ -1,8 +1,8 @@
 """MI355X-native budgeted-KV-cache attention path (drop-in for DRSY/EasyKV's hot path).
 
 Public surface mirrors the reference (easykv/__init__.py:1-2)."""
-from .api import BudgetedKVCache, enable_fixed_kv, generate, geometry  # noqa: F401
-from .engine import KVBank, StepPlan  # noqa: F401
+from .api import BudgetedKVCache, BudgetedKVCacheBatch, enable_fixed_kv, generate, generate_batch, geometry  # noqa: F401
+from .engine import KVBank, KVBankBatch, StepPlan  # noqa: F401
 
 
 def set_dynamicntk_rope_length(model, max_length):

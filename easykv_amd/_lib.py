@@ -26,7 +26,8 @@ DTYPE_CODES = {torch.float16: DTYPE_F16, torch.bfloat16: DTYPE_BF16}
 EXPORTS = ("ekv_abi_version", "ekv_strerror", "ekv_workspace_bytes", "ekv_step_plan", "ekv_bank_reset", "ekv_state_init",
            "ekv_step_attend", "ekv_gather_ordered", "ekv_scatter_rows", "ekv_compact_inplace", "ekv_step_check", "ekv_step_info",
            "ekv_rows_to_slots", "ekv_rows_to_order", "ekv_workspace_bytes_typed", "ekv_step_check_typed", "ekv_step_info_typed",
-           "ekv_step_attend_typed")
+           "ekv_step_attend_typed", "ekv_batch_step_check", "ekv_batch_step_info", "ekv_batch_workspace_bytes", "ekv_batch_step_attend")
+MAX_SEQS = 64      # EKV_MAX_SEQS: entries of one batched decode step
 # the FP8 K/V storage calls (include/easykv_hip.h, "kv8"), checked and typed by load() like EXPORTS.  A list of their own:
 # tests/test_host_cpu.py pins EXPORTS to the header's names as a digit-free pattern reads them, which a name with "kv8" in it is not.
 EXPORTS_KV8 = ("ekv_kv8_quantize", "ekv_kv8_dequantize", "ekv_kv8_step_check", "ekv_kv8_step_info", "ekv_kv8_workspace_bytes",
@@ -53,6 +54,12 @@ class Step(C.Structure):
         "n_split", "phases")] + [(n, C.c_float) for n in ("count_add", "count_tail_step", "sm_div")] + [(n, C.c_int32) for n in (
         "two_pass", "phys_extent", "defer_layers", "defer_index",
         "q_token_stride", "q_head_stride", "kv_token_stride", "kv_head_stride", "out_token_stride", "out_head_stride")]
+
+
+class Seq(C.Structure):
+    """ekv_seq: one sequence of a batched decode step (include/easykv_hip.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("layer", "n_slots", "score_off", "n_evict", "win_lo", "win_tail", "roco_k1", "range_start",
+                                         "phys_extent")]
 
 
 class EkvError(RuntimeError):
@@ -101,10 +108,15 @@ def load():
     lib.ekv_kv8_step_info.argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, C.POINTER(Kv8), C.POINTER(C.c_int32), C.c_int32]
     lib.ekv_kv8_workspace_bytes.argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, C.POINTER(Kv8)]
     lib.ekv_kv8_step_attend.argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, C.POINTER(Kv8), vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
+    lib.ekv_batch_step_check.argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, C.POINTER(Seq), i32]
+    lib.ekv_batch_step_info.argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, C.POINTER(Seq), i32, C.POINTER(C.c_int32), C.c_int32]
+    lib.ekv_batch_workspace_bytes.argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, C.POINTER(Seq), i32]
+    lib.ekv_batch_step_attend.argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, C.POINTER(Seq), i32, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
     for name in EXPORTS[3:] + EXPORTS_KV8:
         getattr(lib, name).restype = C.c_int
     lib.ekv_workspace_bytes_typed.restype = C.c_size_t
     lib.ekv_kv8_workspace_bytes.restype = C.c_size_t
+    lib.ekv_batch_workspace_bytes.restype = C.c_size_t
     if lib.ekv_abi_version() != 8:
         raise EkvError("ABI version mismatch")
     _lib = lib

@@ -33,7 +33,7 @@ from typing import List, Optional
 
 import torch
 
-from .engine import KVBank, StepPlan
+from .engine import KVBank, KVBankBatch, StepPlan
 
 KNOWN_POLICIES = ("roco", "h2o_head", "tova", "recency", "random", "full")
 SCORED = ("roco", "h2o_head", "tova")
@@ -231,6 +231,58 @@ class BudgetedKVCache:
         return out
 
 
+class BudgetedKVCacheBatch:
+    """What the attention seam sees during the decode phase of :func:`generate_batch`: the caches of the live sequences of one
+    :class:`KVBankBatch`.  The driver sets one :class:`StepPlan` per live sequence before each forward; every attention layer then
+    calls :meth:`attend` ONCE with ``[B', Hq, 1, D]`` queries — row i belongs to ``live[i]`` — which is one batched step of the
+    library (one launch per kernel kind) for that layer."""
+
+    streaming, unrotate = False, None      # (a batch has no RoPE-on-read form)
+
+    def __init__(self, bat: KVBankBatch, record=False):
+        self.bat = bat
+        self.plans, self.live, self.positions = [], [], None
+        self.record = record
+        self.evictions = [[] for _ in range(bat.n_seq)]      # record=True, per sequence: per evicting forward, per layer, int32 [H, 1]
+        self._cur = {}
+        self.n_attend = 0
+
+    def get_seq_length(self, layer_idx: Optional[int] = None) -> int:
+        return max((self.bat.n_slots(s) for s in self.live), default=0)
+
+    def update(self, key_states, value_states, layer_idx, cache_kwargs=None):
+        return key_states, value_states
+
+    @contextlib.contextmanager
+    def active(self, plans, live, positions=None):
+        """Scope of ONE batched decode forward over the sequences ``live`` (one plan each)."""
+        self.plans, self.live, self.positions, self.n_attend = list(plans), list(live), positions, 0
+        self._cur = {}
+        if self.record:
+            for s, plan in zip(self.live, self.plans):
+                if plan.evict:
+                    self._cur[s] = []
+                    self.evictions[s].append(self._cur[s])
+        tok = _ACTIVE.set(self)
+        try:
+            yield self
+        finally:
+            _ACTIVE.reset(tok)
+
+    def attend(self, layer_idx: int, q, k, v):
+        n = len(self.live)
+        if q.shape[0] != n or k.shape[0] != n or v.shape[0] != n or q.shape[2] != 1:
+            raise ValueError(f"a batched decode forward hands over [{n}, heads, 1, head_dim] rows for its {n} live sequences; got q {tuple(q.shape)}")
+        self.n_attend += 1
+        dt = self.bat.dtype
+        q, k, v = (t if t.dtype == dt else t.to(dt) for t in (q, k, v))
+        out, ids = self.bat.attend(self.plans, q, k, v, layer_idx, active=self.live)
+        for row, s in enumerate(self.live):
+            if s in self._cur:
+                self._cur[s].append(ids[row])
+        return out
+
+
 def rope_tables(seq_len: int, dim: int, base: float = 10000.0):
     """fp32 cos/sin ``[seq_len, dim]`` with the HF layout ``cat(freqs, freqs)``."""
     inv_freq = 1.0 / (base ** (torch.arange(0, dim, 2, dtype=torch.float32) / dim))
@@ -279,7 +331,8 @@ def _kv_dtype(model, key):
 # ------------------------------------------------------------------------------------------------
 @torch.inference_mode()
 def generate(self, input_ids, generation_config, kv_mode="encoding", stride=1, report_decoding_latency: bool = False,
-             return_cache: bool = False):
+             return_cache: bool = False, _stop_before_decode: bool = False):
+    # (_stop_before_decode: generate_batch's hook — run the prefill, then hand back what the decode phase starts from)
     cfg = generation_config
     temperature = cfg.get("temperature", 1.0)
     top_p = cfg.get("top_p", 1.0)
@@ -601,6 +654,8 @@ def generate(self, input_ids, generation_config, kv_mode="encoding", stride=1, r
         out = forward(cache, input_ids, list(range(length)), StepPlan(policy="full", phase="prefill", accumulate=False))
         if evicting and scored:
             cache.bank.state_init(budget + 1, 0)                   # :242-245
+        if _stop_before_decode:
+            return dict(mode="decoding", cache=cache, logits=out.logits[:, -1, :], length=length, score_off=length, budget_d=budget, whole=False)
         if kv_quant:      # prefill -> decode boundary: the decode steps run on FP8 rows
             cache.bank.quantize_fp8()
         out_ids, fed = decode_loop(cache, out.logits[:, -1, :], length, length, budget, False)
@@ -621,6 +676,8 @@ def generate(self, input_ids, generation_config, kv_mode="encoding", stride=1, r
             logits_last, _, _ = prefill(cache, budget_p, idx, r_idx, True)
         kept = cache.get_seq_length()
         print(f"KV cache budget ratio: {kept / length * 100:.2f}%({kept}/{length})")
+        if _stop_before_decode:
+            return dict(mode="encoding", cache=cache, logits=logits_last, length=length, score_off=0, budget_d=0, whole=False)
         if kv_quant:      # prefill -> decode boundary
             cache.bank.quantize_fp8()
         log, cur_pos, t_first, n_fwd = TokenLog(), length, None, 0
@@ -651,6 +708,8 @@ def generate(self, input_ids, generation_config, kv_mode="encoding", stride=1, r
         budget_p, idx, r_idx = geometry("auto", length, budget, stride)
         cache = new_cache(idx + stride + 1)
         logits_last, _, _ = prefill(cache, budget_p, idx, r_idx, False)
+        if _stop_before_decode:
+            return dict(mode="auto", cache=cache, logits=logits_last, length=length, score_off=0, budget_d=budget_p, whole=True)
         if kv_quant:      # prefill -> decode boundary
             cache.bank.quantize_fp8()
         # the score rows keep their first idx+1 columns (:666-669); the decode rules then run over the whole cache
@@ -690,9 +749,123 @@ def generate(self, input_ids, generation_config, kv_mode="encoding", stride=1, r
     return (result, cache) if return_cache else result
 
 
+@torch.inference_mode()
+def generate_batch(self, input_ids_list, generation_config, kv_mode="encoding", stride=1, return_cache: bool = False):
+    """``generate`` for several prompts of different lengths: every prompt is prefilled ALONE through :func:`generate`'s own prefill
+    (all modes keep the reference's geometry), its bank becomes one sequence of a :class:`KVBankBatch`, and the decode phase then
+    runs ONE model forward per token for all live sequences — ``input_ids [B', 1]``, ``position_ids [B', 1]`` with each sequence's
+    own position, one batched library step per layer.  Each sequence's plan is built as ``generate`` builds it (it evicts when ITS
+    length exceeds ITS budget, ``score_off`` = ITS prompt length, recency / random ranges per sequence) and a sequence leaves the
+    batch when it samples an EOS or has been fed ``max_new_tokens`` tokens.  Returns the decoded strings, in prompt order, and
+    prints each sequence's budget line as ``generate`` prints it.
+
+    Sampling: ``torch.multinomial`` draws for all live sequences at once, so with ``temperature`` / ``top_p`` that leave more than
+    one candidate the global generator is consumed differently from B solo runs; ``kv_policy='random'`` draws once per sequence
+    and step, in batch order."""
+    cfg = generation_config
+    if cfg.get("streaming", False):
+        raise ValueError("generate_batch: streaming=True (RoPE-on-read) has no batched decode step")
+    if cfg.get("kv_quant", None) is not None:
+        raise ValueError("generate_batch: generation_config['kv_quant'] is not supported (a batch runs 16-bit rows)")
+    if kv_mode == "ppl":
+        raise ValueError("generate_batch: kv_mode='ppl' has no decode phase to batch")
+    if cfg.get("hipgraph", False):
+        raise ValueError("generate_batch: generation_config['hipgraph'] is not supported")
+    if getattr(self, "layer_shard", None) is not None and self.layer_shard.world > 1:
+        raise ValueError("generate_batch is not supported on a layer-sharded model (model.layer_shard)")
+    prompts = [p.view(1, -1) if p.dim() == 1 else p for p in input_ids_list]
+    from . import _lib
+    if not 1 <= len(prompts) <= _lib.MAX_SEQS or any(p.dim() != 2 or p.shape[0] != 1 for p in prompts):
+        raise ValueError(f"generate_batch takes 1..{_lib.MAX_SEQS} prompts of shape [S] or [1, S]")
+    temperature, top_p = cfg.get("temperature", 1.0), cfg.get("top_p", 1.0)
+    max_new_tokens = cfg.get("max_new_tokens", 1024)
+    policy, sink = cfg.get("kv_policy", "recency"), cfg.get("temp_length", 4)
+    eos = set(int(e) for e in cfg.get("eos_token_ids", [self.tokenizer.eos_token_id]))
+    record = cfg.get("_record_evictions", False)
+    scored = policy in SCORED
+    evicting = policy in KNOWN_POLICIES and policy != "full"
+    dev = torch.device(self.device)
+
+    # ---- every prompt alone, through the single-sequence prefill; its bank becomes one sequence of the batch
+    seqs = [generate(self, p, cfg, kv_mode=kv_mode, stride=stride, _stop_before_decode=True) for p in prompts]
+    first = seqs[0]["cache"].bank
+    bat = KVBankBatch(len(seqs), first.n_layers, first.n_q_heads, first.n_kv_heads, first.head_dim, max(s["cache"].bank.cap for s in seqs),
+                      device=dev, dtype=first.dtype)
+    cache = BudgetedKVCacheBatch(bat, record=record)
+    for i, s in enumerate(seqs):
+        bat.adopt(i, s["cache"].bank)
+        cache.evictions[i] = s["cache"].evictions      # (the prefill's own evictions come first)
+        s.update(cache=None, out_ids=[], positions=[], cur_pos=s["length"], by_eos=False)
+    cache.prefill_len = [s["length"] for s in seqs]
+
+    # ---- the decode phase: one forward per token for all live sequences
+    live = list(range(len(seqs))) if max_new_tokens > 0 else []
+    while live:
+        prob, _ = logits_adapter(torch.cat([seqs[i]["logits"] for i in live]).float(), temperature, top_p)
+        tok = torch.multinomial(prob, num_samples=1)                      # [B', 1]
+        fed, plans = [], []
+        for row, t in enumerate(tok.view(-1).tolist()):                   # (the one host sync of the step: the EOS test, easykv.py:257-263)
+            s = seqs[live[row]]
+            s["out_ids"].append(t)
+            if t in eos:
+                s["by_eos"] = True
+                continue
+            fed.append((row, live[row]))
+        for row, i in fed:      # the plan of each sequence, as decode_loop builds it for one
+            s = seqs[i]
+            if s["mode"] == "encoding":      # :508-526 plain decode, no eviction
+                plans.append(StepPlan(policy="full", phase="decode", accumulate=False))
+                continue
+            t_now = bat.n_slots(i) + 1
+            evict = evicting and (s["whole"] or (t_now - s["score_off"]) > s["budget_d"])
+            plan = StepPlan(policy=policy, phase="decode", accumulate=scored, evict=evict, score_off=s["score_off"], budget=s["budget_d"])
+            s["positions"].append(s["cur_pos"])
+            if evict and policy in ("recency", "random"):
+                if s["whole"]:
+                    if policy == "random":
+                        raise UnboundLocalError("auto mode + kv_policy='random' is broken in the reference (easykv/easykv.py:744)")
+                    plan.range_start = sink
+                else:
+                    e = 0 if policy == "recency" else int(torch.topk(torch.rand(len(s["positions"])), k=1, dim=-1)[1][0])
+                    s["positions"].pop(e)
+                    plan.range_start = s["score_off"] + e
+            plans.append(plan)
+        if not fed:
+            break
+        rows = torch.as_tensor([r for r, _ in fed], device=dev)
+        now = [i for _, i in fed]
+        pos = torch.as_tensor([seqs[i]["cur_pos"] for i in now], dtype=torch.long, device=dev).view(-1, 1)
+        with cache.active(plans, now, pos):
+            out = self(input_ids=tok[rows].view(-1, 1), past_key_values=cache, position_ids=pos, use_cache=True)
+        if cache.n_attend != bat.n_layers:
+            raise RuntimeError(f"model forward made {cache.n_attend} batched attend() calls for {bat.n_layers} layers: route every "
+                               "attention layer through past_key_values.attend (easykv_amd.hf.patch_model for HF models)")
+        live = []
+        for row, i in enumerate(now):
+            s = seqs[i]
+            s["logits"] = out.logits[row:row + 1, -1, :]
+            s["cur_pos"] += 1
+            if len(s["out_ids"]) < max_new_tokens:
+                live.append(i)
+
+    results = []
+    for i, s in enumerate(seqs):
+        n_out = len(s["out_ids"])
+        fed_n = n_out - 1 if s["by_eos"] else n_out
+        if s["mode"] == "decoding":
+            kept = min(fed_n, s["budget_d"]) if evicting else fed_n
+            print(f"KV cache budget ratio: {kept / n_out * 100:.2f}%({kept}/{n_out})")
+        elif s["mode"] == "auto":
+            size = bat.n_slots(i)
+            print(f"KV Cache Budget ratio {size / (s['length'] + n_out) * 100:.2f}%[{size}/({s['length']}+{n_out})]")
+        results.append(self.tokenizer.decode(s["out_ids"], skip_special_tokens=True).strip())
+    return (results, cache) if return_cache else results
+
+
 def enable_fixed_kv(model, tokenizer, mode, stride=1, verbose=False):
     """easykv/easykv.py:903-908."""
     model.tokenizer = tokenizer
     model.easykv_generate = functools.partial(generate, self=model, kv_mode=mode, stride=stride, report_decoding_latency=verbose)
     model.easykv_ppl = functools.partial(generate, self=model, kv_mode="ppl", stride=stride)
+    model.easykv_generate_batch = functools.partial(generate_batch, self=model, kv_mode=mode, stride=stride)
     print(f"Fixed KV Cache for {mode} enabled")

@@ -152,6 +152,37 @@ __global__ void __launch_bounds__(256) ekv_range_evict_kernel(int32_t* slot_of_p
   for (int i = tid; i < k; i += 256) map[T - k + i] = s_vict[i];
 }
 
+// The same for a batched decode step (ekv_batch_step_attend): workgroup (head, entry) takes T, the range and the victim count from
+// its entry of the table (scalar loads from the kernel arguments) and addresses the map by the entry's bank layer; an entry that
+// evicts nothing this step leaves its map alone.  evict_ids rows are k_max (the table's largest n_evict) apart.
+__global__ void __launch_bounds__(256) ekv_range_evict_batch_kernel(int32_t* slot_of_pos, int32_t* evict_ids, int n_kv_heads, int cap,
+                                                                    int k_max, const EkvSeqTable tb) {
+  extern __shared__ int32_t s_vict[];
+  const int h = blockIdx.x, ll = blockIdx.y, tid = threadIdx.x;
+  const int T = tb.e[ll].n_slots, start = tb.e[ll].range_start, k = tb.e[ll].n_evict;
+  if (k == 0) return;
+  int32_t* map = slot_of_pos + ((size_t)tb.e[ll].layer * n_kv_heads + h) * cap;
+  for (int i = tid; i < k; i += 256) {
+    s_vict[i] = map[start + i];
+    if (evict_ids != nullptr) evict_ids[((size_t)ll * n_kv_heads + h) * k_max + i] = start + i;
+  }
+  __syncthreads();
+  constexpr int CH = 8;
+  for (int d0 = start; d0 < T - k; d0 += 256 * CH) {
+    int32_t buf[CH];
+#pragma unroll
+    for (int c = 0; c < CH; ++c) buf[c] = map[min(d0 + c * 256 + tid + k, T - 1)];
+    __syncthreads();
+#pragma unroll
+    for (int c = 0; c < CH; ++c) {
+      const int d = d0 + c * 256 + tid;
+      if (d < T - k) map[d] = buf[c];
+    }
+    __syncthreads();
+  }
+  for (int i = tid; i < k; i += 256) map[T - k + i] = s_vict[i];
+}
+
 // ---- ordered <-> slot-indexed score rows (ekv_decode_tail.h, "slot-indexed score rows") ------------------------------------------
 // One workgroup per (head, layer); everything is read into LDS before anything is written (the conversions are in place).
 // to_slots: entry j of the ordered rows (row = slot_of_pos[j]) becomes S[row], Q[row], C0[row] = C[j] (g = 0), birth[row] = j; the
@@ -706,6 +737,71 @@ int ekv_plan_step_kv8(const ekv_bank* bank, const ekv_step* step, int32_t dtype,
   return EKV_OK;
 }
 
+// A batched decode step (include/easykv_hip.h, ekv_seq): the plan of the uniform step of the batch's ENVELOPE — the longest entry, the
+// widest extent, one "layer" per entry — with plan->batch set, exactly as a kv8 plan is the 16-bit plan plus a flag: same splits,
+// launches and workspace pitches, so a uniform table plans field for field as the multi-layer step it spells out.  The entries keep
+// their own bounds inside those pitches (the kernels' batch instances read them from the table).  `tb` receives the table the
+// kernels get: the entries with phys_extent resolved as ekv_plan_step resolves a step's.
+int ekv_plan_batch(const ekv_bank* bank, const ekv_step* step, int32_t dtype, const ekv_seq* seqs, int32_t n_seq, EkvStepPlan* P,
+                   ekv_step* env, EkvSeqTable* tb) {
+  *P = EkvStepPlan{};
+  if (dtype != EKV_DTYPE_F16 && dtype != EKV_DTYPE_BF16) return EKV_E_ARG;
+  if (!bank || !step || !seqs || n_seq < 1 || n_seq > EKV_MAX_SEQS) return EKV_E_ARG;
+  auto refuse = [&](int code) {
+    P->one_launch = P->n_launches = P->n_list = 0;
+    P->bytes = 0;      // (nothing will run: ekv_batch_workspace_bytes of a refused table is 0)
+    return code;
+  };
+  // ---- the envelope
+  *env = *step;
+  env->layer_begin = 0;
+  env->layer_count = n_seq;
+  env->n_slots = env->n_evict = env->phys_extent = 0;
+  env->score_off = seqs[0].score_off;
+  for (int i = 0; i < n_seq; ++i) {
+    const ekv_seq& e = seqs[i];
+    tb->e[i] = e;
+    tb->e[i].phys_extent = (e.phys_extent >= e.n_slots && e.phys_extent <= bank->cap) ? e.phys_extent : bank->cap;
+    env->n_slots = std::max(env->n_slots, e.n_slots);
+    env->n_evict = std::max(env->n_evict, e.n_evict);
+    env->phys_extent = std::max(env->phys_extent, tb->e[i].phys_extent);
+    env->score_off = std::min(env->score_off, e.score_off);
+  }
+  // (selection windows are bounds, not pitches: the envelope carries the widest candidate set an entry's checks can leave)
+  env->win_lo = env->win_tail = env->range_start = 0;
+  env->roco_k1 = env->n_evict;
+  // the table first: an entry the single-sequence step would refuse as an argument error is one here, whatever the envelope says
+  for (int i = 0; i < n_seq; ++i) {
+    const ekv_seq& e = seqs[i];
+    if (e.layer < 0 || e.layer >= bank->n_layers || e.n_slots < 1 || e.n_slots > bank->cap) return EKV_E_ARG;
+    for (int j = 0; j < i; ++j)
+      if (seqs[j].layer == e.layer) return EKV_E_ARG;
+  }
+  const int rc = ekv_plan_step(bank, env, dtype, P);
+  P->batch = 1;
+  if (int e = check_bank(bank)) return refuse(e);
+  // the forms a batch does not take, whatever else the step says: chunk steps, RoPE-on-read, phased / deferred / slot-indexed steps
+  if (step->q_len != 1 || step->rope_on_read || step->phases != 0 || step->defer_layers != 0 || step->tova_head_mean) return refuse(EKV_E_UNSUPPORTED);
+  if (rc != EKV_OK) return refuse(rc);
+  for (int i = 0; i < n_seq; ++i) {      // per entry: the checks of the single-sequence step of that entry's geometry
+    const ekv_seq& e = seqs[i];
+    ekv_step one = *step;
+    one.layer_begin = e.layer, one.layer_count = 1, one.n_split = P->n_split;
+    one.n_slots = e.n_slots, one.score_off = e.score_off, one.n_evict = e.n_evict, one.win_lo = e.win_lo, one.win_tail = e.win_tail;
+    one.roco_k1 = e.roco_k1, one.range_start = e.range_start, one.phys_extent = e.phys_extent;
+    EkvStepPlan P1;
+    if (ekv_plan_step(bank, &one, dtype, &P1) == EKV_E_ARG) return refuse(EKV_E_ARG);
+  }
+  // the kernels with a batch instance: the one-launch step, the split attention kernel (+ fold) and the fast scorer behind it, the
+  // range compaction.  What is left to the generic scorer (GQA factors > 8, rows beyond 6144 slots, cap % 4 != 0) has none.
+  for (int i = 0; i < P->n_list; ++i) {
+    const int kind = P->list[i].kind;
+    if (kind != EKV_RUN_FUSED_DECODE && kind != EKV_RUN_DECODE && kind != EKV_RUN_FOLD && kind != EKV_RUN_RANGE && kind != EKV_RUN_DECODE_SCORE)
+      return refuse(EKV_E_UNSUPPORTED);
+  }
+  return EKV_OK;
+}
+
 // The bank a kv8 call plans and launches with: the code planes stand where the 16-bit rows were (bank->k / bank->v are not read)
 static bool kv8_bank(const ekv_bank* bank, const ekv_kv8* q8, ekv_bank* out) {
   if (!bank || !q8 || !q8->k_codes || !q8->v_codes || !q8->k_scale || !q8->v_scale) return false;
@@ -718,9 +814,12 @@ static bool kv8_bank(const ekv_bank* bank, const ekv_kv8* q8, ekv_bank* out) {
 // Body of ekv_step_attend: the plan, the pointers, then its launch sequence.  q8 != NULL: a step on FP8 rows (bank = kv8_bank()).
 static int step_attend_impl(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const void* q, const void* k_new,
                             const void* v_new, void* out, int32_t* evict_ids, const float* rope_cos, const float* rope_sin,
-                            void* workspace, size_t workspace_bytes, void* stream, const ekv_kv8* q8 = nullptr) {
+                            void* workspace, size_t workspace_bytes, void* stream, const ekv_kv8* q8 = nullptr,
+                            const EkvSeqTable* tb = nullptr, const EkvStepPlan* batch_plan = nullptr) {
+  // (tb != NULL: a batched decode step that ekv_plan_batch has accepted; st = its envelope, batch_plan = the plan made there)
   EkvStepPlan P;
-  if (int e = q8 ? ekv_plan_step_kv8(bank, st, dtype, &P) : ekv_plan_step(bank, st, dtype, &P)) return e;
+  if (batch_plan) P = *batch_plan;
+  else if (int e = q8 ? ekv_plan_step_kv8(bank, st, dtype, &P) : ekv_plan_step(bank, st, dtype, &P)) return e;
   if (!q || !k_new || !v_new || !out || !workspace || (st->rope_on_read && (!rope_cos || !rope_sin))) return EKV_E_ARG;
   if (P.bytes > workspace_bytes) return EKV_E_WORKSPACE;
   hipStream_t s = static_cast<hipStream_t>(stream);
@@ -799,10 +898,12 @@ static int step_attend_impl(const ekv_bank* bank, const ekv_step* st, int32_t dt
     // (a kv8 plan is a decode plan: the decode attention launches and the scorers behind them, which read no K/V element)
     if (kv8 && (L.kind == EKV_RUN_CHUNK_LDS || L.kind == EKV_RUN_RESIDENT || L.kind == EKV_RUN_CHUNK || L.kind == EKV_RUN_FLUSH)) return EKV_E_UNSUPPORTED;
     switch (L.kind) {
-      case EKV_RUN_FUSED_DECODE: e = ekv_launch_decode_fused(aa, sa, D, lc, P.fused_nw, s, bf16, kv8); break;
+      case EKV_RUN_FUSED_DECODE:
+        e = tb ? ekv_launch_decode_fused_batch(aa, sa, *tb, D, lc, P.fused_nw, s, bf16) : ekv_launch_decode_fused(aa, sa, D, lc, P.fused_nw, s, bf16, kv8);
+        break;
       case EKV_RUN_CHUNK_LDS: e = ekv_launch_chunk_lds(aa, sa, D, lc, s, bf16); break;
       case EKV_RUN_RESIDENT: e = ekv_launch_attn_resident(aa, sa, lc, s, bf16); break;
-      case EKV_RUN_DECODE: e = ekv_launch_attn_decode(aa, D, lc, s, bf16, kv8); break;
+      case EKV_RUN_DECODE: e = tb ? ekv_launch_attn_decode_batch(aa, *tb, D, lc, s, bf16) : ekv_launch_attn_decode(aa, D, lc, s, bf16, kv8); break;
       case EKV_RUN_CHUNK:
         e = ekv_launch_attn_chunk(aa, D, lc, P.wide, P.two_pass, s, L.fuse ? &sa : nullptr, L.passes, L.tail ? &sa : nullptr, bf16);
         break;
@@ -822,11 +923,15 @@ static int step_attend_impl(const ekv_bank* bank, const ekv_step* st, int32_t dt
       }
       case EKV_RUN_FOLD: e = ekv_launch_fold(sa, lc, s, bf16); break;
       case EKV_RUN_RANGE:
-        hipLaunchKernelGGL(ekv_range_evict_kernel, dim3(bank->n_kv_heads, lc), dim3(256), (size_t)st->n_evict * 4, s, bank->slot_of_pos,
-                           evict_ids, bank->n_kv_heads, bank->cap, st->layer_begin, st->n_slots, st->range_start, st->n_evict);
+        if (tb)
+          hipLaunchKernelGGL(ekv_range_evict_batch_kernel, dim3(bank->n_kv_heads, lc), dim3(256), (size_t)st->n_evict * 4, s, bank->slot_of_pos,
+                             evict_ids, bank->n_kv_heads, bank->cap, st->n_evict, *tb);
+        else
+          hipLaunchKernelGGL(ekv_range_evict_kernel, dim3(bank->n_kv_heads, lc), dim3(256), (size_t)st->n_evict * 4, s, bank->slot_of_pos,
+                             evict_ids, bank->n_kv_heads, bank->cap, st->layer_begin, st->n_slots, st->range_start, st->n_evict);
         e = hipGetLastError();
         break;
-      case EKV_RUN_DECODE_SCORE: e = ekv_launch_decode_score(sa, lc, s, bf16); break;
+      case EKV_RUN_DECODE_SCORE: e = tb ? ekv_launch_decode_score_batch(sa, *tb, lc, s, bf16) : ekv_launch_decode_score(sa, lc, s, bf16); break;
       case EKV_RUN_TOVA_MEAN: e = ekv_launch_tova_headmean(sa, lc, s); break;
       case EKV_RUN_SCORE_SELECT: e = ekv_launch_score_select(sa, lc, s, bf16); break;
     }
@@ -896,6 +1001,48 @@ int ekv_kv8_step_attend(const ekv_bank* bank, const ekv_step* st, int32_t dtype,
   ekv_bank b;
   if (!kv8_bank(bank, q8, &b)) return EKV_E_ARG;
   return step_attend_impl(&b, st, dtype, q, k_new, v_new, out, evict_ids, rope_cos, rope_sin, workspace, workspace_bytes, stream, q8);
+}
+
+// ---- batched decode steps (include/easykv_hip.h, ekv_seq)
+int ekv_batch_step_check(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_seq* seqs, int32_t n_seq) {
+  EkvStepPlan P;
+  ekv_step env;
+  EkvSeqTable tb;
+  return ekv_plan_batch(bank, st, dtype, seqs, n_seq, &P, &env, &tb);
+}
+
+int ekv_batch_step_info(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_seq* seqs, int32_t n_seq, int32_t* info,
+                        int32_t n_info) {
+  if (dtype != EKV_DTYPE_F16 && dtype != EKV_DTYPE_BF16) return EKV_E_ARG;
+  if (int e = check_bank(bank)) return e;
+  if (!st || !seqs || !info || n_info < 1) return EKV_E_ARG;
+  EkvStepPlan P;
+  ekv_step env;
+  EkvSeqTable tb;
+  const bool ok = ekv_plan_batch(bank, st, dtype, seqs, n_seq, &P, &env, &tb) == EKV_OK;
+  const int32_t v[EKV_STEP_INFO_N] = {P.n_split, ok ? P.one_launch : 0, P.two_pass, P.wide, P.n_qblocks, P.qb_rows, P.n_col_parts,
+                                      P.fold_in_kernel, ok ? P.n_launches : 0};
+  for (int i = 0; i < n_info && i < EKV_STEP_INFO_N; ++i) info[i] = v[i];
+  for (int i = EKV_STEP_INFO_N; i < n_info; ++i) info[i] = 0;
+  return EKV_OK;
+}
+
+size_t ekv_batch_workspace_bytes(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_seq* seqs, int32_t n_seq) {
+  EkvStepPlan P;
+  ekv_step env;
+  EkvSeqTable tb;
+  (void)ekv_plan_batch(bank, st, dtype, seqs, n_seq, &P, &env, &tb);
+  return P.bytes;      // (the table travels in the kernel arguments: nothing is staged)
+}
+
+int ekv_batch_step_attend(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_seq* seqs, int32_t n_seq, const void* q,
+                          const void* k_new, const void* v_new, void* out, int32_t* evict_ids, void* workspace, size_t workspace_bytes,
+                          void* stream) {
+  EkvStepPlan P;
+  ekv_step env;
+  EkvSeqTable tb;
+  if (int e = ekv_plan_batch(bank, st, dtype, seqs, n_seq, &P, &env, &tb)) return e;
+  return step_attend_impl(bank, &env, dtype, q, k_new, v_new, out, evict_ids, nullptr, nullptr, workspace, workspace_bytes, stream, nullptr, &tb, &P);
 }
 
 static int kv8_convert_check(const ekv_bank* bank, const ekv_kv8* q8, int32_t layer_begin, int32_t layer_count, int32_t extent) {

@@ -23,7 +23,27 @@
 #ifndef EKV_KV8
 #define EKV_KV8 0
 #endif
+// EKV_BATCH = 1 (the *_batch.hip instances): batched decode steps (include/easykv_hip.h, ekv_seq).  The kernels take the table of the
+// batch behind their argument structs; workgroup (head, entry) copies the structs and overwrites the per-step fields with its entry's
+// (scalar loads from the kernel arguments), and from there on IS the uniform kernel: pitches (t_pad, l_pad, n_split, rows_per_split,
+// LDS sizes, ITEMS) stay the envelope's, bounds (T, extent, score_off, windows) become the entry's, the bank is addressed by the
+// entry's layer and the workspace / q / k_new / v_new / out / evict_ids by the entry's index.  Plain keys, ordered score rows.
+#ifndef EKV_BATCH
+#define EKV_BATCH 0
+#endif
+#if EKV_BATCH
 #if EKV_KV8
+#error "batch instances: 16-bit rows, plain keys"
+#endif
+#define EKV_KV_TAG _batch
+#if EKV_BF16
+#define ekv_attn_decode_kernel ekv_attn_decode_kernel_batch_bf16
+#define ekv_decode_fused_kernel ekv_decode_fused_kernel_batch_bf16
+#else
+#define ekv_attn_decode_kernel ekv_attn_decode_kernel_batch
+#define ekv_decode_fused_kernel ekv_decode_fused_kernel_batch
+#endif
+#elif EKV_KV8
 #define EKV_KV_TAG _kv8
 #if EKV_BF16
 #define ekv_attn_decode_kernel ekv_attn_decode_kernel_kv8_bf16
@@ -59,7 +79,8 @@ constexpr int kEPL = EKV_KV8 ? 16 : 8;      // elements of a lane's 16-byte piec
 // SLOT_LDS = false: slot-map entries are fetched per iteration (needs 16-byte aligned map rows, cap % 4 == 0); saves the
 // staging pass and its barrier, which matters when a workgroup only streams one or two iterations.
 template <int D, int REP, bool ROPE, bool SLOT_LDS>
-__global__ void __launch_bounds__(256) ekv_attn_decode_kernel(const EkvAttnArgs a) {
+__global__ void __launch_bounds__(256) ekv_attn_decode_kernel(const EkvAttnArgs EKV_ARG_A EKV_TB_PARAM) {
+  EKV_SHADOW_A(blockIdx.z)
   using Gm = EkvDecodeGeom<D>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   int32_t* s_slot = reinterpret_cast<int32_t*>(smem);
@@ -127,7 +148,7 @@ __global__ void __launch_bounds__(256) ekv_attn_decode_kernel(const EkvAttnArgs 
   __syncthreads();
   uint32_t* s_last = reinterpret_cast<uint32_t*>(s_part);      // (the wave partials have been consumed)
   if (tid == 0) {
-    uint32_t* word = a.arrive + (size_t)ll * a.n_kv_heads + h;
+    uint32_t* word = a.arrive + (size_t)EKV_ARRIVE_ROW(ll) * a.n_kv_heads + h;
     // This is the guide's write-through hand-off in its counter form (cdna_hip_programming.md §5 "in-launch split-K reduction":
     // sc1 slab stores -> EVERY wave asm vmcnt(0) -> __syncthreads -> lane 0 relaxed agent fetch_add; the reducer reads the slabs
     // with sc1 loads): the sc1 stores have left the XCD's L2 before the counter moves, and sc1 loads bypass the reader's L1, so
@@ -154,7 +175,9 @@ __global__ void __launch_bounds__(256) ekv_attn_decode_kernel(const EkvAttnArgs 
 // fused kernel
 // ------------------------------------------------------------------------------------------------------
 template <int D, int REP, bool ROPE, int ITEMS, int NW, bool SLOT>
-__global__ void __launch_bounds__(64 * NW, (NW >= 8 ? (REP == 1 ? 2 : 1) : (SLOT && ITEMS > 12 ? 2 : (REP == 1 ? 4 : (REP == 2 ? 3 : 2))))) ekv_decode_fused_kernel(const EkvAttnArgs a, const EkvScoreArgs sc) {
+__global__ void __launch_bounds__(64 * NW, (NW >= 8 ? (REP == 1 ? 2 : 1) : (SLOT && ITEMS > 12 ? 2 : (REP == 1 ? 4 : (REP == 2 ? 3 : 2))))) ekv_decode_fused_kernel(const EkvAttnArgs EKV_ARG_A, const EkvScoreArgs EKV_ARG_SC EKV_TB_PARAM) {
+  EKV_SHADOW_A(blockIdx.z)
+  EKV_SHADOW_SC(blockIdx.z)
   using Gm = EkvDecodeGeom<D, NW>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int h = blockIdx.y, ll = blockIdx.z, tid = threadIdx.x;
@@ -286,19 +309,19 @@ __global__ void __launch_bounds__(64 * NW, (NW >= 8 ? (REP == 1 ? 2 : 1) : (SLOT
 }
 
 template <int REP>
-hipError_t launch(const EkvAttnArgs& a, int layer_count, hipStream_t s) {
+hipError_t launch(const EkvAttnArgs& a EKV_TB_DECL, int layer_count, hipStream_t s) {
   using Gm = EkvDecodeGeom<EKV_D>;
   const size_t part = (size_t)Gm::NP * REP * Gm::PS * 4;
   const int rep_all = a.n_q_heads / a.n_kv_heads;
   const dim3 grid(a.n_split * ((rep_all + REP - 1) / REP), a.n_kv_heads, layer_count);
   if ((a.cap & 3) == 0 && a.cap >= 16) {
-    hipLaunchKernelGGL((ekv_attn_decode_kernel<EKV_D, REP, EKV_ROPE, false>), grid, dim3(256), part, s, a);
+    hipLaunchKernelGGL((ekv_attn_decode_kernel<EKV_D, REP, EKV_ROPE, false>), grid, dim3(256), part, s, a EKV_TB_PASS);
   } else {
     const size_t lds = ekv_align((size_t)a.rows_per_split * 4, 16) + part;
     if (lds > 48 * 1024)
       (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ekv_attn_decode_kernel<EKV_D, REP, EKV_ROPE, true>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL((ekv_attn_decode_kernel<EKV_D, REP, EKV_ROPE, true>), grid, dim3(256), lds, s, a);
+    hipLaunchKernelGGL((ekv_attn_decode_kernel<EKV_D, REP, EKV_ROPE, true>), grid, dim3(256), lds, s, a EKV_TB_PASS);
   }
   return hipGetLastError();
 }
@@ -312,7 +335,7 @@ size_t fused_lds(int t_pad, int l_pad, int n_state) {
 }
 
 template <int REP, int ITEMS, int NW, bool SLOT>
-hipError_t launch_fused_k(const EkvAttnArgs& a, const EkvScoreArgs& sc, int layer_count, hipStream_t s) {
+hipError_t launch_fused_k(const EkvAttnArgs& a, const EkvScoreArgs& sc EKV_TB_DECL, int layer_count, hipStream_t s) {
   // (slot-indexed rows: S / Q over the physical rows [0, E) in LDS, count base and birth in registers)
   const size_t lds = SLOT ? fused_lds<REP, NW>(a.phys_extent, a.l_pad, sc.policy == EKV_POLICY_ROCO ? 2 : 1)
                           : fused_lds<REP, NW>(a.t_pad, a.l_pad, sc.policy == EKV_POLICY_ROCO ? 3 : 1);
@@ -320,7 +343,7 @@ hipError_t launch_fused_k(const EkvAttnArgs& a, const EkvScoreArgs& sc, int laye
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ekv_decode_fused_kernel<EKV_D, REP, EKV_ROPE, ITEMS, NW, SLOT>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   hipLaunchKernelGGL((ekv_decode_fused_kernel<EKV_D, REP, EKV_ROPE, ITEMS, NW, SLOT>), dim3(1, a.n_kv_heads, layer_count),
-                     dim3(64 * NW), lds, s, a, sc);
+                     dim3(64 * NW), lds, s, a, sc EKV_TB_PASS);
   return hipGetLastError();
 }
 
@@ -329,23 +352,23 @@ hipError_t launch_fused_k(const EkvAttnArgs& a, const EkvScoreArgs& sc, int laye
 //   NW = 8: for launches with only 1-2 heads per CU (GQA: Mistral's 8 KV heads x 32 layers = 256 heads): the same number
 //           of waves per CU streams one head, instead of leaving the CU to a single 4-wave workgroup.
 template <int REP, int NW>
-hipError_t launch_fused_nw(const EkvAttnArgs& a, const EkvScoreArgs& sc, int layer_count, hipStream_t s) {
+hipError_t launch_fused_nw(const EkvAttnArgs& a, const EkvScoreArgs& sc EKV_TB_DECL, int layer_count, hipStream_t s) {
   constexpr int NT = 64 * NW, I0 = (2304 + NT - 1) / NT, I1 = (6144 + NT - 1) / NT;
   if (sc.birth != nullptr) {      // slot-indexed rows: the thread-owned columns are the physical rows [0, E) (ekv_decode_slot_rows_supported)
-    if constexpr (!EKV_ROPE && REP <= 4) {
-      if (a.phys_extent <= NT * I0) return launch_fused_k<REP, I0, NW, true>(a, sc, layer_count, s);
+    if constexpr (!EKV_ROPE && !EKV_BATCH && REP <= 4) {      // (a batch runs on the ordered layout)
+      if (a.phys_extent <= NT * I0) return launch_fused_k<REP, I0, NW, true>(a, sc EKV_TB_PASS, layer_count, s);
       // extents up to 6144 rows: 12 (8-wave) / 24 (4-wave) columns per thread in registers; the 4-wave build gives up the fourth
       // workgroup per CU for them (LDS would not have allowed it at these row counts anyway)
-      if (a.phys_extent <= NT * I1) return launch_fused_k<REP, I1, NW, true>(a, sc, layer_count, s);
+      if (a.phys_extent <= NT * I1) return launch_fused_k<REP, I1, NW, true>(a, sc EKV_TB_PASS, layer_count, s);
     }
     return hipErrorInvalidValue;
   }
-  if (a.n_slots <= NT * I0) return launch_fused_k<REP, I0, NW, false>(a, sc, layer_count, s);
-  return launch_fused_k<REP, I1, NW, false>(a, sc, layer_count, s);
+  if (a.n_slots <= NT * I0) return launch_fused_k<REP, I0, NW, false>(a, sc EKV_TB_PASS, layer_count, s);
+  return launch_fused_k<REP, I1, NW, false>(a, sc EKV_TB_PASS, layer_count, s);
 }
 template <int REP>
-hipError_t launch_fused(const EkvAttnArgs& a, const EkvScoreArgs& sc, int layer_count, int nw, hipStream_t s) {
-  return nw == 8 ? launch_fused_nw<REP, 8>(a, sc, layer_count, s) : launch_fused_nw<REP, 4>(a, sc, layer_count, s);
+hipError_t launch_fused(const EkvAttnArgs& a, const EkvScoreArgs& sc EKV_TB_DECL, int layer_count, int nw, hipStream_t s) {
+  return nw == 8 ? launch_fused_nw<REP, 8>(a, sc EKV_TB_PASS, layer_count, s) : launch_fused_nw<REP, 4>(a, sc EKV_TB_PASS, layer_count, s);
 }
 
 }  // namespace
@@ -354,28 +377,28 @@ hipError_t launch_fused(const EkvAttnArgs& a, const EkvScoreArgs& sc, int layer_
 #define EKV_CAT(a, b, c, t, k) EKV_CAT_(a, b, c, t, k)
 #define EKV_SYM(name) EKV_CAT(name, EKV_D, EKV_ROPE_TAG, EKV_DT_TAG, EKV_KV_TAG)
 
-hipError_t EKV_SYM(ekv_launch_attn_decode_d)(const EkvAttnArgs& a, int rep, int layer_count, hipStream_t s) {
+hipError_t EKV_SYM(ekv_launch_attn_decode_d)(const EkvAttnArgs& a EKV_TB_DECL, int rep, int layer_count, hipStream_t s) {
   if (rep < 1) return hipErrorInvalidValue;
   switch (rep) {
-    case 1: return launch<1>(a, layer_count, s);
-    case 2: return launch<2>(a, layer_count, s);
-    case 3: case 4: return launch<4>(a, layer_count, s);
-    default: return launch<8>(a, layer_count, s);      // 5..8: one group of 8; wider factors: ceil(rep / 8) groups per KV head
+    case 1: return launch<1>(a EKV_TB_PASS, layer_count, s);
+    case 2: return launch<2>(a EKV_TB_PASS, layer_count, s);
+    case 3: case 4: return launch<4>(a EKV_TB_PASS, layer_count, s);
+    default: return launch<8>(a EKV_TB_PASS, layer_count, s);      // 5..8: one group of 8; wider factors: ceil(rep / 8) groups per KV head
   }
 }
 
-hipError_t EKV_SYM(ekv_launch_decode_fused_d)(const EkvAttnArgs& a, const EkvScoreArgs& sc, int rep, int layer_count,
+hipError_t EKV_SYM(ekv_launch_decode_fused_d)(const EkvAttnArgs& a, const EkvScoreArgs& sc EKV_TB_DECL, int rep, int layer_count,
                                               int nw, hipStream_t s) {
   switch (rep) {
-    case 1: return launch_fused<1>(a, sc, layer_count, nw, s);
-    case 2: return launch_fused<2>(a, sc, layer_count, nw, s);
-    case 3: case 4: return launch_fused<4>(a, sc, layer_count, nw, s);
-    case 5: case 6: case 7: case 8: return launch_fused<8>(a, sc, layer_count, nw, s);
+    case 1: return launch_fused<1>(a, sc EKV_TB_PASS, layer_count, nw, s);
+    case 2: return launch_fused<2>(a, sc EKV_TB_PASS, layer_count, nw, s);
+    case 3: case 4: return launch_fused<4>(a, sc EKV_TB_PASS, layer_count, nw, s);
+    case 5: case 6: case 7: case 8: return launch_fused<8>(a, sc EKV_TB_PASS, layer_count, nw, s);
     default: return hipErrorInvalidValue;
   }
 }
 
-#if !EKV_BF16 && !EKV_KV8   // (the LDS layout does not depend on the element type)
+#if !EKV_BF16 && !EKV_KV8 && !EKV_BATCH   // (the LDS layout does not depend on the element type)
 size_t EKV_SYM(ekv_fused_lds_d)(int rep, int t_pad, int l_pad, int nw) {
   switch (rep) {
     case 1: return nw == 8 ? fused_lds<1, 8>(t_pad, l_pad, 3) : fused_lds<1, 4>(t_pad, l_pad, 3);

@@ -1,0 +1,6 @@
+// batch instance of ekv_attn_decode.inc (batched decode steps, ekv_seq): head_dim 96, plain keys, fp16
+#define EKV_BATCH 1
+#define EKV_D 96
+#define EKV_ROPE false
+#define EKV_ROPE_TAG plain
+#include "ekv_attn_decode.inc"

@@ -45,6 +45,23 @@ hipError_t ekv_launch_attn_decode_d64_plain_bf16_kv8(const EkvAttnArgs&, int, in
 hipError_t ekv_launch_decode_fused_d64_plain_bf16_kv8(const EkvAttnArgs&, const EkvScoreArgs&, int, int, int, hipStream_t);
 hipError_t ekv_launch_attn_decode_d128_plain_bf16_kv8(const EkvAttnArgs&, int, int, hipStream_t);
 hipError_t ekv_launch_decode_fused_d128_plain_bf16_kv8(const EkvAttnArgs&, const EkvScoreArgs&, int, int, int, hipStream_t);
+// batch instances (batched decode steps, ekv_seq): plain keys, every head_dim, fp16 or bf16
+hipError_t ekv_launch_attn_decode_d32_plain_batch(const EkvAttnArgs&, const EkvSeqTable&, int, int, hipStream_t);
+hipError_t ekv_launch_decode_fused_d32_plain_batch(const EkvAttnArgs&, const EkvScoreArgs&, const EkvSeqTable&, int, int, int, hipStream_t);
+hipError_t ekv_launch_attn_decode_d32_plain_bf16_batch(const EkvAttnArgs&, const EkvSeqTable&, int, int, hipStream_t);
+hipError_t ekv_launch_decode_fused_d32_plain_bf16_batch(const EkvAttnArgs&, const EkvScoreArgs&, const EkvSeqTable&, int, int, int, hipStream_t);
+hipError_t ekv_launch_attn_decode_d64_plain_batch(const EkvAttnArgs&, const EkvSeqTable&, int, int, hipStream_t);
+hipError_t ekv_launch_decode_fused_d64_plain_batch(const EkvAttnArgs&, const EkvScoreArgs&, const EkvSeqTable&, int, int, int, hipStream_t);
+hipError_t ekv_launch_attn_decode_d64_plain_bf16_batch(const EkvAttnArgs&, const EkvSeqTable&, int, int, hipStream_t);
+hipError_t ekv_launch_decode_fused_d64_plain_bf16_batch(const EkvAttnArgs&, const EkvScoreArgs&, const EkvSeqTable&, int, int, int, hipStream_t);
+hipError_t ekv_launch_attn_decode_d96_plain_batch(const EkvAttnArgs&, const EkvSeqTable&, int, int, hipStream_t);
+hipError_t ekv_launch_decode_fused_d96_plain_batch(const EkvAttnArgs&, const EkvScoreArgs&, const EkvSeqTable&, int, int, int, hipStream_t);
+hipError_t ekv_launch_attn_decode_d96_plain_bf16_batch(const EkvAttnArgs&, const EkvSeqTable&, int, int, hipStream_t);
+hipError_t ekv_launch_decode_fused_d96_plain_bf16_batch(const EkvAttnArgs&, const EkvScoreArgs&, const EkvSeqTable&, int, int, int, hipStream_t);
+hipError_t ekv_launch_attn_decode_d128_plain_batch(const EkvAttnArgs&, const EkvSeqTable&, int, int, hipStream_t);
+hipError_t ekv_launch_decode_fused_d128_plain_batch(const EkvAttnArgs&, const EkvScoreArgs&, const EkvSeqTable&, int, int, int, hipStream_t);
+hipError_t ekv_launch_attn_decode_d128_plain_bf16_batch(const EkvAttnArgs&, const EkvSeqTable&, int, int, hipStream_t);
+hipError_t ekv_launch_decode_fused_d128_plain_bf16_batch(const EkvAttnArgs&, const EkvScoreArgs&, const EkvSeqTable&, int, int, int, hipStream_t);
 
 // any GQA factor (repeat_kv, llama_patch.py:19-29): factors <= 8 on the build of the next power of two, wider ones in groups of 8
 bool ekv_attn_decode_supported(int head_dim, int rep) {
@@ -108,5 +125,29 @@ hipError_t ekv_launch_decode_fused(const EkvAttnArgs& a, const EkvScoreArgs& sc,
   EKV_DISPATCH_KV8(ekv_launch_decode_fused_d, a, sc, rep, layer_count, nw, s)
   if (bf16 && rope) return hipErrorInvalidValue;
   EKV_DISPATCH(ekv_launch_decode_fused_d, a, sc, rep, layer_count, nw, s)
+  return hipErrorInvalidValue;
+}
+
+// batched decode steps: the batch instances of the two kernels above (plain keys; the planner refuses everything else)
+#define EKV_DISPATCH_BATCH(fn, ...)                                                                      \
+  switch (head_dim) {                                                                                    \
+    case 32: return bf16 ? fn##32_plain_bf16_batch(__VA_ARGS__) : fn##32_plain_batch(__VA_ARGS__);       \
+    case 64: return bf16 ? fn##64_plain_bf16_batch(__VA_ARGS__) : fn##64_plain_batch(__VA_ARGS__);       \
+    case 96: return bf16 ? fn##96_plain_bf16_batch(__VA_ARGS__) : fn##96_plain_batch(__VA_ARGS__);       \
+    case 128: return bf16 ? fn##128_plain_bf16_batch(__VA_ARGS__) : fn##128_plain_batch(__VA_ARGS__);    \
+  }
+
+hipError_t ekv_launch_attn_decode_batch(const EkvAttnArgs& a, const EkvSeqTable& tb, int head_dim, int n_seq, hipStream_t s, bool bf16) {
+  const int rep = a.n_q_heads / a.n_kv_heads;
+  if (a.rope_cos != nullptr) return hipErrorInvalidValue;
+  EKV_DISPATCH_BATCH(ekv_launch_attn_decode_d, a, tb, rep, n_seq, s)
+  return hipErrorInvalidValue;
+}
+
+hipError_t ekv_launch_decode_fused_batch(const EkvAttnArgs& a, const EkvScoreArgs& sc, const EkvSeqTable& tb, int head_dim, int n_seq, int nw,
+                                         hipStream_t s, bool bf16) {
+  const int rep = a.n_q_heads / a.n_kv_heads;
+  if (a.rope_cos != nullptr || sc.birth != nullptr) return hipErrorInvalidValue;
+  EKV_DISPATCH_BATCH(ekv_launch_decode_fused_d, a, sc, tb, rep, n_seq, nw, s)
   return hipErrorInvalidValue;
 }

@@ -6,9 +6,23 @@
 #define EKV_STAMP(i) do { if (threadIdx.x == 0) stamps[i] = __builtin_readcyclecounter(); } while (0)
 #endif
 #include "ekv_decode_tail.h"
+// EKV_BATCH = 1 (ekv_decode_score_batch*.hip): the scorer of a batched decode step — workgroup (head, entry) shadows the per-step
+// fields of its arguments from the entry's row of the table (as in ekv_attn_decode.inc) and is the uniform scorer from there on.
+// The fold kernel reads no per-step field (partials, split count and output rows are the envelope's): a batch launches the uniform one.
+#ifndef EKV_BATCH
+#define EKV_BATCH 0
+#endif
+#if EKV_BATCH
+#if EKV_BF16
+#define ekv_decode_score_kernel ekv_decode_score_kernel_batch_bf16
+#else
+#define ekv_decode_score_kernel ekv_decode_score_kernel_batch
+#endif
+#else
 #if EKV_BF16   // (bf16 instance: the same kernels under tagged names)
 #define ekv_decode_score_kernel ekv_decode_score_kernel_bf16
 #define ekv_fold_kernel ekv_fold_kernel_bf16
+#endif
 #endif
 
 namespace {
@@ -19,7 +33,8 @@ namespace {
 constexpr int kSNW = EKV_SCORE_NW, kSNT = 64 * kSNW;   // waves / threads per scorer workgroup
 
 template <int REP, int ITEMS>
-__global__ void __launch_bounds__(kSNT) ekv_decode_score_kernel(const EkvScoreArgs sc) {
+__global__ void __launch_bounds__(kSNT) ekv_decode_score_kernel(const EkvScoreArgs EKV_ARG_SC EKV_TB_PARAM) {
+  EKV_SHADOW_SC(blockIdx.y)
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int h = blockIdx.x, ll = blockIdx.y, tid = threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6;
@@ -72,6 +87,7 @@ __global__ void __launch_bounds__(kSNT) ekv_decode_score_kernel(const EkvScoreAr
   ekv_decode_tail<REP, ITEMS, kSNW>(sc, ll, h, head_row, T, off, W, s_logit, t_pad, sS, sQ, sC, red, s_hist, s_list, kSNT, nullptr, 0, 0, nrep);
 }
 
+#if !EKV_BATCH
 // Partials of the key-range splits -> 16-bit attention output, nothing else (rows = q_len * n_q_heads per layer).
 __global__ void __launch_bounds__(128) ekv_fold_kernel(const EkvScoreArgs sc) {
   const int D = sc.head_dim, PS = D + 2;
@@ -82,46 +98,59 @@ __global__ void __launch_bounds__(128) ekv_fold_kernel(const EkvScoreArgs sc) {
   for (int d = threadIdx.x; d < D; d += 128) orow[d] = ekv_to_e(ekv_fold_partials_auto(p0, sc.n_split, PS, d));
 }
 
+#endif
+
 size_t score_lds(int rep, int t_pad, int policy) {
   const size_t n_state = policy == EKV_POLICY_ROCO ? 3 : 1;
   return ((size_t)rep * t_pad + n_state * ekv_align((size_t)t_pad, 256)) * 4 + 2 * kSNW * 8 * 8 + 264 * 4 + kSNT * 8;
 }
 
 template <int REP, int ITEMS>
-hipError_t launch_k(const EkvScoreArgs& sc, int layer_count, hipStream_t s) {
+hipError_t launch_k(const EkvScoreArgs& sc EKV_TB_DECL, int layer_count, hipStream_t s) {
   const size_t lds = score_lds(REP, sc.t_pad, sc.policy);
   if (lds > 48 * 1024)
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ekv_decode_score_kernel<REP, ITEMS>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL((ekv_decode_score_kernel<REP, ITEMS>), dim3(sc.n_kv_heads, layer_count), dim3(kSNT), lds, s, sc);
+  hipLaunchKernelGGL((ekv_decode_score_kernel<REP, ITEMS>), dim3(sc.n_kv_heads, layer_count), dim3(kSNT), lds, s, sc EKV_TB_PASS);
   return hipGetLastError();
 }
 
 template <int REP>
-hipError_t launch_rep(const EkvScoreArgs& sc, int layer_count, hipStream_t s) {
+hipError_t launch_rep(const EkvScoreArgs& sc EKV_TB_DECL, int layer_count, hipStream_t s) {
   // ITEMS = ceil(row width / threads) (a floor here sent T = 2049 to the 6144-wide build: 12 items per thread instead of 5)
   constexpr int I0 = (2304 + kSNT - 1) / kSNT, I1 = (6144 + kSNT - 1) / kSNT;
-  return sc.n_slots <= kSNT * I0 ? launch_k<REP, I0>(sc, layer_count, s) : launch_k<REP, I1>(sc, layer_count, s);
+  return sc.n_slots <= kSNT * I0 ? launch_k<REP, I0>(sc EKV_TB_PASS, layer_count, s) : launch_k<REP, I1>(sc EKV_TB_PASS, layer_count, s);
 }
 
+#if !EKV_BATCH
 hipError_t launch_fold(const EkvScoreArgs& sc, int layer_count, hipStream_t s) {
   hipLaunchKernelGGL(ekv_fold_kernel, dim3(sc.n_q_heads * sc.q_len, layer_count), dim3(128), 0, s, sc);
   return hipGetLastError();
 }
+#endif
 
-hipError_t launch_score(const EkvScoreArgs& sc, int layer_count, hipStream_t s) {
+hipError_t launch_score(const EkvScoreArgs& sc EKV_TB_DECL, int layer_count, hipStream_t s) {
   switch (sc.n_q_heads / sc.n_kv_heads) {
-    case 1: return launch_rep<1>(sc, layer_count, s);
-    case 2: return launch_rep<2>(sc, layer_count, s);
-    case 3: case 4: return launch_rep<4>(sc, layer_count, s);
-    case 5: case 6: case 7: case 8: return launch_rep<8>(sc, layer_count, s);
+    case 1: return launch_rep<1>(sc EKV_TB_PASS, layer_count, s);
+    case 2: return launch_rep<2>(sc EKV_TB_PASS, layer_count, s);
+    case 3: case 4: return launch_rep<4>(sc EKV_TB_PASS, layer_count, s);
+    case 5: case 6: case 7: case 8: return launch_rep<8>(sc EKV_TB_PASS, layer_count, s);
     default: return hipErrorInvalidValue;
   }
 }
 
 }  // namespace
 
+#if EKV_BATCH
 #if EKV_BF16
+hipError_t ekv_launch_decode_score_batch_bf16(const EkvScoreArgs& sc, const EkvSeqTable& tb, int n_seq, hipStream_t s) { return launch_score(sc, tb, n_seq, s); }
+#else
+hipError_t ekv_launch_decode_score_batch_bf16(const EkvScoreArgs& sc, const EkvSeqTable& tb, int n_seq, hipStream_t s);
+hipError_t ekv_launch_decode_score_batch(const EkvScoreArgs& sc, const EkvSeqTable& tb, int n_seq, hipStream_t s, bool bf16) {
+  return bf16 ? ekv_launch_decode_score_batch_bf16(sc, tb, n_seq, s) : launch_score(sc, tb, n_seq, s);
+}
+#endif
+#elif EKV_BF16
 hipError_t ekv_launch_fold_bf16(const EkvScoreArgs& sc, int layer_count, hipStream_t s) { return launch_fold(sc, layer_count, s); }
 hipError_t ekv_launch_decode_score_bf16(const EkvScoreArgs& sc, int layer_count, hipStream_t s) { return launch_score(sc, layer_count, s); }
 #else

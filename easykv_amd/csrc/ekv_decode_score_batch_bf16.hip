@@ -1,0 +1,4 @@
+// scorer of the split path of a batched decode step (ekv_decode_score.inc, EKV_BATCH), bf16 outputs
+#define EKV_BATCH 1
+#define EKV_BF16 1
+#include "ekv_decode_score.inc"

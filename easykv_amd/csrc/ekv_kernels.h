@@ -40,6 +40,7 @@ struct EkvStepPlan {
   int32_t slot_rows, slot_tail_ok;   // fused decode step on the slot-indexed score rows (EKV_PHASE_SLOT_ROWS / _TAIL_OK)
   int32_t bf16;             // 16-bit tensors are bf16: the launches run the EKV_BF16 kernel instances
   int32_t kv8;              // the bank's K/V rows are FP8 codes + row scales (ekv_plan_step_kv8): the decode launches run the kv8 instances
+  int32_t batch;            // a batched decode step (ekv_plan_batch): the plan of the envelope; the launches run the batch instances
   int32_t strides[6];       // q, kv, out row strides (token, head) in elements, the dense layout filled in
   // Workspace: byte offsets of this call's slices (a deferred call's layout spans every deferred layer), -1 = not in the layout
   int64_t logits;     // [layer_count][Hq][q_len][t_pad]   raw q.k/sm_div of every live position
@@ -61,6 +62,15 @@ int ekv_plan_step(const ekv_bank* bank, const ekv_step* step, int32_t dtype, Ekv
 // The same plan for a step on FP8 rows (`bank` with k / v standing for the code planes): what the 16-bit step of that shape plans,
 // with plan->kv8 set — or EKV_E_UNSUPPORTED (nothing to launch) for q_len > 1, rope_on_read and head_dim other than 64 / 128.
 int ekv_plan_step_kv8(const ekv_bank* bank, const ekv_step* step, int32_t dtype, EkvStepPlan* plan);
+
+// The table of a batched decode step as the kernels' batch instances receive it: BY VALUE, behind the argument structs of the uniform
+// kernel (2304 bytes of the 4 KB a launch may carry).  Workgroup (head, entry ll) shadows the per-step fields of its argument structs
+// from e[ll] with wave-uniform loads before anything else; nothing is staged in device memory and no copy precedes the launch.
+struct EkvSeqTable {
+  ekv_seq e[EKV_MAX_SEQS];      // phys_extent resolved (ekv_plan_batch)
+};
+int ekv_plan_batch(const ekv_bank* bank, const ekv_step* step, int32_t dtype, const ekv_seq* seqs, int32_t n_seq, EkvStepPlan* plan,
+                   ekv_step* envelope, EkvSeqTable* table);
 
 // The __half* members below point at 16-bit rows: fp16, or bf16 for the EKV_BF16 kernel instances (ekv_common.h: rows move as
 // bytes, and every element access of a kernel goes through ekv_e / ekv_h8 / ekv_to_e).
@@ -171,6 +181,56 @@ int ekv_decode_fused_nw(int n_heads_in_launch);
 bool ekv_decode_fused_supported(int head_dim, int rep, int n_slots, int t_pad, int l_pad, int n_evict, int cap, int nw);
 hipError_t ekv_launch_decode_fused(const EkvAttnArgs& a, const EkvScoreArgs& sc, int head_dim, int layer_count, int nw, hipStream_t s,
                                    bool bf16, bool kv8 = false);
+// batch instances (16-bit rows, plain keys, ordered score rows): `a` / `sc` are the envelope's arguments with layer_begin = 0 and
+// a.arrive = the bank's counters; n_seq workgroup rows, one per table entry
+hipError_t ekv_launch_attn_decode_batch(const EkvAttnArgs& a, const EkvSeqTable& tb, int head_dim, int n_seq, hipStream_t s, bool bf16);
+hipError_t ekv_launch_decode_fused_batch(const EkvAttnArgs& a, const EkvScoreArgs& sc, const EkvSeqTable& tb, int head_dim, int n_seq, int nw,
+                                         hipStream_t s, bool bf16);
+hipError_t ekv_launch_decode_score_batch(const EkvScoreArgs& sc, const EkvSeqTable& tb, int n_seq, hipStream_t s, bool bf16);
+// What workgroup (head, entry z) of a batch instance does first: its argument structs are the envelope's with the per-step fields
+// replaced by its entry's (scalar loads from the kernel arguments).  layer_begin = layer - z: every `layer_begin + ll` of the kernel
+// body then names the entry's bank layer, while the workspace and the call's tensors stay indexed by ll = z.
+__device__ __forceinline__ EkvAttnArgs ekv_batch_attn_args(const EkvAttnArgs& env, const ekv_seq& e, int z) {
+  EkvAttnArgs a = env;
+  a.n_slots = e.n_slots;
+  a.phys_extent = e.phys_extent;
+  a.layer_begin = e.layer - z;
+  return a;
+}
+__device__ __forceinline__ EkvScoreArgs ekv_batch_score_args(const EkvScoreArgs& env, const ekv_seq& e, int z) {
+  EkvScoreArgs sc = env;
+  sc.n_slots = e.n_slots;
+  sc.layer_begin = e.layer - z;
+  sc.score_off = e.score_off;
+  sc.n_evict = e.n_evict;
+  sc.win_lo = e.win_lo;
+  sc.win_tail = e.win_tail;
+  sc.roco_k1 = e.roco_k1;
+  sc.range_start = e.range_start;
+  return sc;
+}
+// How a kernel source spells its batch instance (EKV_BATCH = 1, set by the *_batch.hip stubs before anything is included; off, the
+// macros vanish and the source is the uniform kernel's, token for token): the argument structs arrive under the names a_env / sc_env
+// with the table behind them, and EKV_SHADOW_* declares `a` / `sc` as this workgroup's own copies.
+#if defined(EKV_BATCH) && EKV_BATCH
+#define EKV_ARG_A a_env
+#define EKV_ARG_SC sc_env
+#define EKV_TB_PARAM , const EkvSeqTable tb
+#define EKV_TB_DECL , const EkvSeqTable& tb
+#define EKV_TB_PASS , tb
+#define EKV_ARRIVE_ROW(ll) (a.layer_begin + (ll))      // the arrival counters are the bank's: indexed by the entry's layer
+#define EKV_SHADOW_A(z) const EkvAttnArgs a = ekv_batch_attn_args(a_env, tb.e[z], (int)(z));
+#define EKV_SHADOW_SC(z) const EkvScoreArgs sc = ekv_batch_score_args(sc_env, tb.e[z], (int)(z));
+#else
+#define EKV_ARG_A a
+#define EKV_ARG_SC sc
+#define EKV_TB_PARAM
+#define EKV_TB_DECL
+#define EKV_TB_PASS
+#define EKV_ARRIVE_ROW(ll) (ll)
+#define EKV_SHADOW_A(z)
+#define EKV_SHADOW_SC(z)
+#endif
 // FP8 bank conversion (ekv_kv8.hip).  src_bf16: the 16-bit rows are bf16; out_kind: 0 fp16, 1 bf16, 2 fp32
 hipError_t ekv_launch_kv8_quantize(const ekv_bank* bank, const ekv_kv8* q8, bool src_bf16, int layer_begin, int layer_count, int extent,
                                    hipStream_t s);

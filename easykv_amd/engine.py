@@ -655,3 +655,154 @@ class KVBank:
         for l in range(layer_begin, layer_begin + lc):      # the new rows are written by the attention kernel
             self.extent[l] = st.phys_extent
         return out, (evict_ids if (st.n_evict > 0 and want_ids) else None)
+
+
+class _BankSlice:
+    """Layers ``[begin, begin + n_layers)`` of a bank as a bank of their own: the single-sequence calls of :class:`KVBank` with the
+    layer arguments shifted.  It owns nothing: rows, slot maps, score rows, ``n_slots`` / ``extent`` and the layout bookkeeping
+    (which layers hold the slot-indexed score rows) are the parent's, so a step taken through a slice is seen by every other user
+    of the storage."""
+
+    def __init__(self, bank: KVBank, begin: int, n_layers: int):
+        self.bank, self.begin, self.n_layers = bank, begin, n_layers
+        for name in ("n_q_heads", "n_kv_heads", "head_dim", "cap", "device", "dtype"):
+            setattr(self, name, getattr(bank, name))
+
+    def _rows(self, t):
+        return t[self.begin:self.begin + self.n_layers]
+
+    # (read-only snapshots: the bookkeeping is the shared bank's, advanced by the calls below)
+    n_slots = property(lambda self: tuple(self._rows(self.bank.n_slots)))
+    extent = property(lambda self: tuple(self._rows(self.bank.extent)))
+    slot_of_pos = property(lambda self: self._rows(self.bank.slot_of_pos))
+    score_sum = property(lambda self: self._rows(self.bank.score_sum))
+    score_sq = property(lambda self: self._rows(self.bank.score_sq))
+    score_cnt = property(lambda self: self._rows(self.bank.score_cnt))
+
+    def _span(self, layer_begin, layer_count):
+        lc = self.n_layers - layer_begin if layer_count is None else layer_count
+        if layer_begin < 0 or lc < 1 or layer_begin + lc > self.n_layers:
+            raise ValueError(f"layers [{layer_begin}, {layer_begin + lc}) are outside this {self.n_layers}-layer sequence")
+        return self.begin + layer_begin, lc
+
+    def state_init(self, width, mode, stride=1, layer_begin=0, layer_count=None):
+        lb, lc = self._span(layer_begin, layer_count)
+        self.bank.state_init(width, mode, stride, lb, lc)
+
+    def load_rows(self, k, v, pos_begin=None, layer_begin=0):
+        lb, _ = self._span(layer_begin, k.shape[0])
+        self.bank.load_rows(k, v, pos_begin, lb)
+
+    def ordered_kv(self, layer_begin=0, layer_count=None):
+        return self.bank.ordered_kv(*self._span(layer_begin, layer_count))
+
+    def attend(self, plan, q, k_new, v_new, layer_begin=0, out=None, evict_ids=None, phases=0):
+        lb, _ = self._span(layer_begin, q.shape[0])
+        return self.bank.attend(plan, q, k_new, v_new, lb, out, evict_ids, phases)
+
+
+class KVBankBatch:
+    """One bank of ``n_seq * n_layers`` layers laid out ``[sequence][layer]`` for the ragged decode batch (include/easykv_hip.h,
+    ekv_seq): :meth:`sequence` hands out sequence ``i``'s contiguous ``n_layers`` as an ordinary bank for its prefill, and
+    :meth:`attend` serves model layer ``layer`` of any subset of the sequences — each with its own cache length, score offset and
+    eviction geometry — in ONE call: one launch per kernel kind over the layers ``{s * n_layers + layer}``."""
+
+    def __init__(self, n_seq, n_layers, n_q_heads, n_kv_heads, head_dim, cap, device="cuda", scored=True, dtype=torch.float16):
+        if not 1 <= n_seq <= _lib.MAX_SEQS:
+            raise ValueError(f"a decode batch holds 1..{_lib.MAX_SEQS} sequences, not {n_seq}")
+        self.n_seq, self.n_layers = n_seq, n_layers
+        self.bank = KVBank(n_seq * n_layers, n_q_heads, n_kv_heads, head_dim, cap, device, scored, dtype)
+        self.lib, self.dtype = self.bank.lib, dtype
+        self.n_q_heads, self.n_kv_heads, self.head_dim, self.cap, self.device = n_q_heads, n_kv_heads, head_dim, self.bank.cap, self.bank.device
+        self.n_calls = 0      # batched attend calls issued (one per layer and decode forward)
+
+    def sequence(self, i) -> _BankSlice:
+        if not 0 <= i < self.n_seq:
+            raise ValueError(f"sequence {i} of a batch of {self.n_seq}")
+        return _BankSlice(self.bank, i * self.n_layers, self.n_layers)
+
+    def n_slots(self, i, layer=0):
+        return self.bank.n_slots[i * self.n_layers + layer]
+
+    def adopt(self, i, src: KVBank):
+        """Sequence ``i`` takes over the state of ``src``, a bank of this batch's layer count and head shape that one sequence was
+        prefilled on alone: K/V rows at their physical indices, slot maps, score rows (ordered layout), lengths and extents.  The
+        rows behind ``src.cap`` keep this bank's own free list, so a shorter ``src.cap`` is fine."""
+        b = self.bank
+        if (src.n_layers, src.n_q_heads, src.n_kv_heads, src.head_dim, src.dtype) != (self.n_layers, b.n_q_heads, b.n_kv_heads, b.head_dim, b.dtype) \
+                or src.cap > b.cap or src.kv_quant is not None or not 0 <= i < self.n_seq:
+            raise ValueError("adopt(): the source bank must have this batch's layers, heads, head_dim and dtype, 16-bit rows and cap <= the batch's")
+        src.join()
+        l0, l1, c = i * self.n_layers, (i + 1) * self.n_layers, src.cap
+        b._ensure_ordered(l0, self.n_layers)
+        for name in ("k", "v", "slot_of_pos", "score_sum", "score_sq", "score_cnt"):      # (the properties hand out the ordered layout)
+            t = getattr(src, name)
+            if t is not None:
+                getattr(b, name)[l0:l1, :, :c].copy_(t)
+        b.n_slots[l0:l1] = src.n_slots
+        b.extent[l0:l1] = src.extent
+
+    def make_table(self, plans, layer, active=None, n_split=0):
+        """(shared ekv_step, ekv_seq table) of the batched call for model layer ``layer`` over the sequences ``active`` (default:
+        all), one :class:`StepPlan` each: every entry by the arithmetic :meth:`KVBank.make_step` applies to that sequence alone."""
+        b = self.bank
+        seqs = list(range(self.n_seq)) if active is None else list(active)
+        if len(seqs) != len(plans) or not seqs:
+            raise ValueError(f"{len(plans)} plans for {len(seqs)} sequences")
+        if not 0 <= layer < self.n_layers or any(not 0 <= s < self.n_seq for s in seqs):
+            raise ValueError("layer or sequence index outside the batch")
+        tb = (_lib.Seq * len(seqs))()
+        shared = None
+        for e, s, plan in zip(tb, seqs, plans):
+            if plan.phase != "decode" or plan.streaming:
+                raise ValueError("a batched step is a decode step with plain keys")
+            l = s * self.n_layers + layer
+            st = b.make_step(plan, 1, l, 1)
+            e.layer, e.n_slots, e.score_off, e.n_evict, e.phys_extent = l, st.n_slots, st.score_off, st.n_evict, st.phys_extent
+            e.win_lo, e.win_tail, e.roco_k1, e.range_start = st.win_lo, st.win_tail, st.roco_k1, st.range_start
+            if shared is None:
+                shared = st
+            elif (st.policy, st.accumulate, st.tova_head_mean) != (shared.policy, shared.accumulate, shared.tova_head_mean):
+                raise ValueError("the sequences of a batched step share the policy and whether scores accumulate")
+            if st.n_evict:      # (read only by entries that evict: the reference adds the count inside its eviction branch)
+                shared.count_add, shared.count_tail_step = st.count_add, st.count_tail_step
+        shared.n_split = n_split
+        return shared, tb, seqs
+
+    def step_info(self, plans, layer, active=None, n_split=0) -> dict:
+        st, tb, _ = self.make_table(plans, layer, active, n_split)
+        info = (C.c_int32 * 9)()
+        check(self.lib.ekv_batch_step_info(C.byref(self.bank._bank), C.byref(st), self.bank._dt, tb, len(tb), info, 9), "ekv_batch_step_info")
+        keys = ("n_split", "fused", "two_pass", "wide", "n_qblocks", "qb_rows", "n_col_parts", "fold_in_kernel", "n_launches")
+        return dict(zip(keys, (int(x) for x in info)))
+
+    def attend(self, plans, q, k_new, v_new, layer, active=None, out=None, evict_ids=None, n_split=0):
+        """q / out ``[B', Hq, 1, D]``, k_new / v_new ``[B', H, 1, D]``: row i belongs to ``active[i]`` (default: every sequence).
+        Returns (out, evict_ids ``[B', H, 1]`` int32 or None when no sequence evicts; rows of sequences that keep everything are
+        left as they are)."""
+        b = self.bank
+        b._kv8_refuse(True, "a batched decode step")
+        st, tb, seqs = self.make_table(plans, layer, active, n_split)
+        n = len(seqs)
+        if q.shape[0] != n or q.shape[2] != 1:
+            raise ValueError(f"q must be [{n}, Hq, 1, D] for {n} sequences, not {tuple(q.shape)}")
+        for e in tb:
+            if b._slot_rows[e.layer]:
+                b._ensure_ordered(e.layer, 1)
+        if any(b._score_done[e.layer] is not None for e in tb):
+            b.join()
+        if out is None:
+            out = torch.empty(n, self.n_q_heads, 1, self.head_dim, dtype=self.dtype, device=self.device)
+        q, k_new, v_new = _stride_rows(st, q, k_new, v_new, out, self.dtype)
+        k_max = max(e.n_evict for e in tb)
+        if k_max > 0 and evict_ids is None:
+            evict_ids = torch.empty(n, self.n_kv_heads, k_max, dtype=torch.int32, device=self.device)
+        bank_ref, st_ref = C.byref(b._bank), C.byref(st)
+        ws = b._workspace(self.lib.ekv_batch_workspace_bytes(bank_ref, st_ref, b._dt, tb, n))
+        check(self.lib.ekv_batch_step_attend(bank_ref, st_ref, b._dt, tb, n, _ptr(q), _ptr(k_new), _ptr(v_new), _ptr(out),
+                                             _ptr(evict_ids) if k_max > 0 else None, _ptr(ws), ws.numel(), b._stream()), "ekv_batch_step_attend")
+        for e in tb:
+            b.n_slots[e.layer] = e.n_slots - e.n_evict
+            b.extent[e.layer] = e.phys_extent
+        self.n_calls += 1
+        return out, (evict_ids if k_max > 0 else None)

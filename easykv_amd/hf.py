@@ -42,7 +42,9 @@ def _easykv_attention(module, query, key, value, attention_mask=None, dropout=0.
         # rotates with the PURE tables at read time, so the model's s^2 on the logits is put back on the query alone
         s = float(cache.unrotate[2]) if len(cache.unrotate) > 2 else 1.0
         query, key = _unrotate(query, cos, sin, s), _unrotate(key, cos, sin, 1.0 / s)
-    out = cache.attend(module.layer_idx, query, key, value)        # [1, Hq, n, D] in the bank's dtype
+    # (one sequence: [1, Hq, n, D]; the decode phase of generate_batch: [B', Hq, 1, D] views, one batched step for the layer — the
+    #  active cache is then a BudgetedKVCacheBatch and reads the rows in place, a batch row being Hq * D elements apart)
+    out = cache.attend(module.layer_idx, query, key, value)        # in the bank's dtype
     return out.transpose(1, 2).to(query.dtype), None      # (no conversion when the bank holds the model's dtype)
 
 

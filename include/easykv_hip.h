@@ -291,6 +291,50 @@ int ekv_kv8_step_attend(const ekv_bank *bank, const ekv_step *step, int32_t dtyp
                         const void *k_new, const void *v_new, void *out, int32_t *evict_ids, const float *rope_cos,
                         const float *rope_sin, void *workspace, size_t workspace_bytes, void *stream);
 
+/* Batched decode steps (ABI 8, additive): ONE call, and one launch per kernel kind, serves n_seq sequences whose caches have
+ * different lengths and different eviction geometry.  Each entry of the table names the bank layer it attends and carries what
+ * ekv_step holds per step; entry i owns row i of the call's tensors.  The layers of a table need not be contiguous or ordered, so
+ * one bank of B * L layers laid out [sequence][layer] gives every sequence an ordinary contiguous L-layer bank for its prefill (the
+ * single-sequence calls above) and lets the batched call for model layer l address the layers { s * L + l }.
+ *
+ *   step   what the batch shares: q_len (must be 1), policy, accumulate, roco_tail, count_add, count_tail_step, sm_div, n_split
+ *          (0 = choose) and the row strides.  Its layer_begin, layer_count, n_slots, score_off, n_evict, win_lo, win_tail, roco_k1,
+ *          range_start and phys_extent are IGNORED in favour of the table.
+ *   seqs   HOST memory, 1 <= n_seq <= EKV_MAX_SEQS entries, read during the call only.  The table travels to the kernels BY VALUE in
+ *          their arguments (36 bytes per entry): nothing is staged in device memory, no copy is enqueued and the call never
+ *          synchronises with the device.
+ *   q, out            16-bit [n_seq][n_q_heads][1][head_dim]
+ *   k_new, v_new      16-bit [n_seq][n_kv_heads][1][head_dim]
+ *   evict_ids         int32  [n_seq][n_kv_heads][max n_evict of the table] or NULL; rows of entries that evict nothing are not written
+ *
+ * The step is planned as the uniform step of the table's ENVELOPE (the largest n_slots, the largest phys_extent, layer_count =
+ * n_seq): same key-range splits, launches and workspace, so ekv_batch_step_info of a table whose entries are all alike equals
+ * ekv_step_info_typed of the multi-layer step it spells out, and ekv_batch_workspace_bytes equals ekv_workspace_bytes_typed of it.
+ * Inside those pitches every entry keeps its own bounds: a workgroup serves one (head, entry) as it serves one (head, layer) of a
+ * uniform step, with the entry's n_slots, score_off, extent and selection windows — per entry the arithmetic, and therefore every
+ * output bit and every eviction decision, is that of the single-sequence step of its geometry under the same n_split.  A key-range
+ * split that is empty for a short entry contributes (m, l, o) = (-inf, 0, 0) to the fold.
+ *
+ * Accepted: q_len == 1 with plain keys, fp16 and bf16, every head_dim, in the whole-step form (phases == 0, defer_layers == 0) on the
+ * ordered score-row layout; GQA factors <= 8, at most one victim per entry and step (entries with n_evict 0 and 1 mix freely), at
+ * most 6144 slots and cap % 4 == 0 for scored policies — the shapes the one-launch kernel and the split path's fast scorer take.
+ * EKV_E_UNSUPPORTED from the dry run, nothing launched: q_len > 1, rope_on_read, any `phases` bit (EKV_PHASE_SLOT_ROWS included),
+ * defer_layers, tova_head_mean, and scored shapes only the generic scorer serves.  EKV_E_ARG: n_seq out of range, a `layer` outside
+ * the bank or named twice, n_slots outside [1, cap], or entry values the single-sequence step of that geometry refuses as EKV_E_ARG. */
+#define EKV_MAX_SEQS 64
+typedef struct ekv_seq {      /* one sequence of a batched decode step */
+  int32_t layer;        /* bank layer this entry attends                                        */
+  int32_t n_slots;      /* T of this sequence, including the new token                          */
+  int32_t score_off, n_evict, win_lo, win_tail, roco_k1, range_start, phys_extent;   /* as in ekv_step, per sequence */
+} ekv_seq;
+int ekv_batch_step_check(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const ekv_seq *seqs, int32_t n_seq);
+int ekv_batch_step_info(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const ekv_seq *seqs, int32_t n_seq, int32_t *info,
+                        int32_t n_info);
+size_t ekv_batch_workspace_bytes(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const ekv_seq *seqs, int32_t n_seq);
+int ekv_batch_step_attend(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const ekv_seq *seqs, int32_t n_seq, const void *q,
+                          const void *k_new, const void *v_new, void *out, int32_t *evict_ids, void *workspace, size_t workspace_bytes,
+                          void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,263 @@
+"""The batched decode step (ekv_batch_step_attend, KVBankBatch) against the paths a caller had before it, in one process, legs
+interleaved (rep of leg a, rep of leg b, ...); writes profiles/batch_bench.json and prints it as one JSON line.
+
+Llama2-7B head shape (Hq = H = 32, D = 128), budget 2048 (T = 2049), roco, every step evicting (steady state: lengths stay put),
+scattered slot maps, warm score state, per-layer calls of a decoder stack: a "token" is one call per layer, and every leg reports
+µs per per-layer call for B sequences (median over reps of per-rep means, HIP events on the launch stream) and its run-to-run spread.
+
+Per B in {1, 2, 4, 8, 16, 32}:
+  batched          one ekv_batch_step_attend per layer over the B sequences (table prebuilt: it is the same every step) — the feature
+  batched_engine   the same through KVBankBatch.attend (builds the table in Python every call: what a Python caller pays today)
+  solo_whole       B KVBank.attend calls of one layer each, whole-step form (attention + fold + scorer launches per call)
+  solo_deferred    B attend(defer=True) calls per layer + one flush() per token (the form tools/bench_kv8.py times per layer)
+  uniform_ordered  the existing multi-layer ekv_step_attend, layer_count = B, on the ORDERED score-row layout — like against like:
+                   the batched instance does the same work plus a handful of scalar loads
+  batched_contig   the batched call on a bank laid out as uniform_ordered's ([layer][sequence]: the B layers of a call are adjacent,
+                   where KVBankBatch keeps them a whole sequence apart) — same addresses, same kernels but for the table: separates
+                   what the table costs from what the [sequence][layer] layout costs
+  uniform_slot     the same launch on the slot-indexed layout where the library takes it (recorded as what a follow-up that brings
+                   that layout to batches would gain, not as a yardstick)
+and the same B with lengths spread over [256, 2049] (fixed seed, recorded):
+  ragged           one batched call per layer; against `batched` at the envelope length and against live bytes / envelope bytes
+
+Usage: python tools/bench_batch.py [--reps 9] [--tokens 24] [--warm 20] [--batches 1,2,4,8,16,32] [--out profiles/batch_bench.json]"""
+from __future__ import annotations
+
+import argparse
+import ctypes as C
+import gc
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+from tools.bench_common import HBM_PEAK_GBS, algorithmic_bytes  # noqa: E402
+
+HQ = H = 32
+D = 128
+BUDGET = 2048
+
+
+def _time(fn, n):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for i in range(n):
+        fn(i)
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) * 1e3 / n
+
+
+def _interleave(fns, reps, tokens, warm):
+    for f in fns.values():
+        for i in range(warm):
+            f(i)
+    torch.cuda.synchronize()
+    got = {k: [] for k in fns}
+    for _ in range(reps):
+        for k, f in fns.items():
+            got[k].append(_time(f, tokens))
+    return {k: dict(us=statistics.median(v), spread=round((max(v) - min(v)) / statistics.median(v), 4)) for k, v in got.items()}
+
+
+def _fill(bank, layers, rows, g):
+    """Layers of `bank` at `rows[i]` live rows each: random K/V, scattered slot map, decoding score state of width rows + 1, warm."""
+    dev = bank.device
+    for l, n in zip(layers, rows):
+        bank.load_rows(torch.randn(1, H, n, D, generator=g, device=dev).half(), torch.randn(1, H, n, D, generator=g, device=dev).half(),
+                       pos_begin=0, layer_begin=l)
+        bank.slot_of_pos[l, :, :n] = torch.argsort(torch.rand(H, n, generator=g, device=dev), dim=-1).int()
+        bank.state_init(n + 1, 0, layer_begin=l, layer_count=1)
+        warm = torch.rand(H, n, generator=g, device=dev) * 1e-3
+        bank.score_sum[l, :, :n] += warm
+        bank.score_sq[l, :, :n] += warm ** 2
+
+
+def _plan(budget, **kw):
+    from easykv_amd import StepPlan
+    return StepPlan(policy="roco", phase="decode", evict=True, score_off=0, budget=budget, **kw)
+
+
+def _tokens(B, lps, g, dev, n=8):
+    return tuple(torch.randn(n, lps, B, hh, 1, D, generator=g, device=dev).half() for hh in (HQ, H, H))
+
+
+def batched_legs(B, lps, lens, g):
+    """-> {name: forward} of the batched call over B sequences at `lens` (rows before the token), through the C ABI and through the engine."""
+    from easykv_amd import KVBankBatch
+    bat = KVBankBatch(B, lps, HQ, H, D, cap=BUDGET + 1 + 63)
+    _fill(bat.bank, [s * lps + l for s in range(B) for l in range(lps)], [lens[s] for s in range(B) for _ in range(lps)], g)
+    plans = [_plan(n) for n in lens]
+    qs, ks, vs = _tokens(B, lps, g, bat.device)
+    out = torch.empty(B, HQ, 1, D, dtype=torch.float16, device=bat.device)
+    ids = torch.empty(B, H, 1, dtype=torch.int32, device=bat.device)
+    tables = [bat.make_table(plans, l)[:2] for l in range(lps)]      # steady state: every entry evicts, the table never changes
+    b = bat.bank
+    ws = b._workspace(max(bat.lib.ekv_batch_workspace_bytes(C.byref(b._bank), C.byref(st), b._dt, tb, B) for st, tb in tables))
+    info = bat.step_info(plans, 0)
+
+    def raw(i):
+        j = i % qs.shape[0]
+        for l, (st, tb) in enumerate(tables):
+            rc = bat.lib.ekv_batch_step_attend(C.byref(b._bank), C.byref(st), b._dt, tb, B, qs[j, l].data_ptr(), ks[j, l].data_ptr(), vs[j, l].data_ptr(),
+                                               out.data_ptr(), ids.data_ptr(), ws.data_ptr(), ws.numel(), b._stream())
+            assert rc == 0, rc
+
+    def engine(i):
+        j = i % qs.shape[0]
+        for l in range(lps):
+            bat.attend(plans, qs[j, l], ks[j, l], vs[j, l], l, out=out, evict_ids=ids)
+    return raw, engine, info
+
+
+def solo_legs(B, lps, g):
+    from easykv_amd import KVBank
+    n = BUDGET
+    plan = _plan(n)
+    whole = KVBank(B * lps, HQ, H, D, cap=n + 1 + 63)
+    _fill(whole, range(B * lps), [n] * (B * lps), g)
+    defer = KVBank(B * lps, HQ, H, D, cap=n + 1 + 63)
+    _fill(defer, range(B * lps), [n] * (B * lps), g)
+    qs, ks, vs = _tokens(B, lps, g, whole.device)
+    out = torch.empty(1, HQ, 1, D, dtype=torch.float16, device=whole.device)
+    ids = torch.empty(1, H, 1, dtype=torch.int32, device=whole.device)
+
+    def f_whole(i):
+        j = i % qs.shape[0]
+        for l in range(lps):
+            for s in range(B):
+                whole.attend(plan, qs[j, l, s:s + 1], ks[j, l, s:s + 1], vs[j, l, s:s + 1], layer_begin=s * lps + l, out=out, evict_ids=ids)
+
+    def f_defer(i):
+        j = i % qs.shape[0]
+        for l in range(lps):
+            for s in range(B):
+                defer.attend(plan, qs[j, l, s:s + 1], ks[j, l, s:s + 1], vs[j, l, s:s + 1], layer_begin=s * lps + l, defer=True, out=out)
+        defer.flush()
+    return f_whole, f_defer
+
+
+def uniform_legs(B, lps, g):
+    """The existing multi-layer step over B contiguous layers ([layer][sequence] layout), ordered and slot-indexed score rows."""
+    from easykv_amd import KVBank, _lib
+    n = BUDGET
+    plan = _plan(n)
+    legs = {}
+    for name, slot in (("uniform_ordered", False), ("uniform_slot", True)):
+        bank = KVBank(B * lps, HQ, H, D, cap=n + 1 + 63)
+        bank.use_slot_rows = slot
+        _fill(bank, range(B * lps), [n] * (B * lps), g)
+        if slot and not bank.step_plan(plan, 1, 0, B)[1]:
+            continue      # (the layout is the one-launch step's: launches the planner splits stay ordered)
+        qs, ks, vs = _tokens(B, lps, g, bank.device)
+        out = torch.empty(B, HQ, 1, D, dtype=torch.float16, device=bank.device)
+        ids = torch.empty(B, H, 1, dtype=torch.int32, device=bank.device)
+
+        def fwd(i, bank=bank, qs=qs, ks=ks, vs=vs, out=out, ids=ids):
+            j = i % qs.shape[0]
+            for l in range(lps):
+                bank.attend(plan, qs[j, l], ks[j, l], vs[j, l], layer_begin=l * B, out=out, evict_ids=ids)
+        legs[name] = fwd
+    # the batched call over the same [layer][sequence] layout (straight through the C ABI, table prebuilt)
+    bank = KVBank(B * lps, HQ, H, D, cap=n + 1 + 63)
+    _fill(bank, range(B * lps), [n] * (B * lps), g)
+    qs, ks, vs = _tokens(B, lps, g, bank.device)
+    out = torch.empty(B, HQ, 1, D, dtype=torch.float16, device=bank.device)
+    ids = torch.empty(B, H, 1, dtype=torch.int32, device=bank.device)
+    st = bank.make_step(plan, 1, 0, B)
+    tables = []
+    for l in range(lps):
+        tb = (_lib.Seq * B)()
+        for s, e in enumerate(tb):
+            e.layer, e.n_slots, e.score_off, e.n_evict, e.phys_extent = l * B + s, st.n_slots, st.score_off, st.n_evict, st.phys_extent
+            e.win_lo, e.win_tail, e.roco_k1, e.range_start = st.win_lo, st.win_tail, st.roco_k1, st.range_start
+        tables.append(tb)
+    ws = bank._workspace(bank.lib.ekv_batch_workspace_bytes(C.byref(bank._bank), C.byref(st), bank._dt, tables[0], B))
+
+    def contig(i):
+        j = i % qs.shape[0]
+        for l, tb in enumerate(tables):
+            rc = bank.lib.ekv_batch_step_attend(C.byref(bank._bank), C.byref(st), bank._dt, tb, B, qs[j, l].data_ptr(), ks[j, l].data_ptr(),
+                                                vs[j, l].data_ptr(), out.data_ptr(), ids.data_ptr(), ws.data_ptr(), ws.numel(), bank._stream())
+            assert rc == 0, rc
+    legs["batched_contig"] = contig
+    return legs
+
+
+def bytes_per_call(lens):
+    return sum(algorithmic_bytes(H, HQ, D, n + 1, 1, 3)["total"] for n in lens)
+
+
+def run_batch(B, args):
+    dev = torch.device("cuda")
+    g = torch.Generator(device=dev).manual_seed(1000 + B)
+    lps = 16 if B <= 2 else 8      # layers per sequence: every leg's working set stays far above the 256 MB of the memory-side cache
+    rs = torch.Generator().manual_seed(20261016 + B)
+    ragged = sorted(int(x) for x in torch.randint(255, BUDGET + 1, (B,), generator=rs))
+    ragged[-1] = BUDGET      # (the envelope is the uniform shape)
+    raw, engine, info = batched_legs(B, lps, [BUDGET] * B, g)
+    fns = {"batched": raw, "batched_engine": engine}
+    fns["solo_whole"], fns["solo_deferred"] = solo_legs(B, lps, g)
+    fns.update(uniform_legs(B, lps, g))
+    if B > 1:
+        fns["ragged"], _, rinfo = batched_legs(B, lps, ragged, g)
+        assert rinfo == info, (rinfo, info)      # a ragged table plans as its envelope
+    if args.legs:      # (a kernel trace of two legs: their launches alone)
+        fns = {k: f for k, f in fns.items() if k in args.legs.split(",")}
+    t = _interleave(fns, args.reps, args.tokens, args.warm)
+    del fns
+    gc.collect()
+    torch.cuda.empty_cache()
+    res = {"layers_per_sequence": lps, "plan": info}
+    ub = bytes_per_call([BUDGET] * B)
+    for k, v in t.items():
+        us = v["us"] / lps      # per per-layer call (solo legs: B calls; solo_deferred: + its share of the flush)
+        nb = bytes_per_call(ragged) if k == "ragged" else ub
+        res[k] = dict(us_per_layer_call=round(us, 2), run_to_run_spread=v["spread"], path_tokens_per_s=round(B / (us * 32 * 1e-6), 1),
+                      gb_per_s=round(nb / (us * 1e-6) / 1e9, 1), frac_of_hbm_peak=round(nb / (us * 1e-6) / 1e9 / HBM_PEAK_GBS, 4))
+    if args.legs:
+        return res
+    us = lambda k: res[k]["us_per_layer_call"]
+    res["ratio_batched_over_uniform_ordered"] = round(us("batched") / us("uniform_ordered"), 4)
+    res["ratio_batched_contig_over_uniform_ordered"] = round(us("batched_contig") / us("uniform_ordered"), 4)
+    res["ratio_batched_over_solo_whole"] = round(us("batched") / us("solo_whole"), 4)
+    res["ratio_batched_over_solo_deferred"] = round(us("batched") / us("solo_deferred"), 4)
+    if "uniform_slot" in res:
+        res["ratio_uniform_slot_over_uniform_ordered"] = round(us("uniform_slot") / us("uniform_ordered"), 4)
+    if "ragged" in res:
+        res["ragged_lengths"] = [n + 1 for n in ragged]
+        res["ratio_ragged_over_batched_at_envelope"] = round(us("ragged") / us("batched"), 4)
+        res["live_bytes_over_envelope_bytes"] = round(bytes_per_call(ragged) / ub, 4)
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=9)
+    ap.add_argument("--tokens", type=int, default=24)
+    ap.add_argument("--warm", type=int, default=20)
+    ap.add_argument("--batches", default="1,2,4,8,16,32")
+    ap.add_argument("--legs", default=None, help="comma-separated legs to run alone, e.g. batched,uniform_ordered (no ratios; for a kernel trace)")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "batch_bench.json"))
+    args = ap.parse_args()
+    torch.cuda.set_device(0)
+    res = {"device": torch.cuda.get_device_name(0), "reps": args.reps, "tokens_per_rep": args.tokens, "warm_tokens": args.warm,
+           "hbm_peak_gb_per_s": HBM_PEAK_GBS,
+           "shape": "Hq = H = 32, D = 128, budget 2048 (T = 2049), roco, every step evicting, scattered slot maps, warm score state; "
+                    "per-layer calls; path tokens/s = B / (32 layers x us per per-layer call)"}
+    for B in (int(x) for x in args.batches.split(",")):
+        res[f"B{B}"] = run_batch(B, args)
+        print(f"B{B}", json.dumps(res[f"B{B}"]), flush=True)
+    with open(args.out, "w") as f:
+        json.dump(res, f, indent=1)
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
