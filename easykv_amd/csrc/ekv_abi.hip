@@ -318,7 +318,7 @@ int ekv_step_info_typed(const ekv_bank* bank, const ekv_step* st, int32_t dtype,
   EkvStepPlan P;
   const bool ok = ekv_plan_step(bank, st, dtype, &P) == EKV_OK;
   const int32_t v[EKV_STEP_INFO_N] = {P.n_split, ok ? P.one_launch : 0, P.two_pass, P.wide, P.n_qblocks, P.qb_rows, P.n_col_parts,
-                                      P.fold_in_kernel, ok ? P.n_launches : 0};
+                                      P.fold_in_kernel, ok ? P.n_launches : 0, ok ? (P.fused_order & 3) : 0};
   for (int i = 0; i < n_info && i < EKV_STEP_INFO_N; ++i) info[i] = v[i];
   for (int i = EKV_STEP_INFO_N; i < n_info; ++i) info[i] = 0;
   return EKV_OK;
@@ -591,6 +591,7 @@ static int plan_step_impl(const ekv_bank* bank, const ekv_step* step, EkvStepPla
     P->slot_rows = slot_rows ? 1 : 0;
     P->slot_tail_ok = slot_rows && (step->phases & EKV_PHASE_SLOT_TAIL_OK) ? 1 : 0;
     P->one_launch = 1;
+    P->fused_order = ekv_decode_fused_order(D, rep, scored, slot_rows, P->fused_nw, st->layer_count * bank->n_kv_heads, P->phys_extent);
     run(EKV_RUN_FUSED_DECODE, 1);
     return EKV_OK;
   }
@@ -729,6 +730,7 @@ int ekv_plan_step(const ekv_bank* bank, const ekv_step* step, int32_t dtype, Ekv
 int ekv_plan_step_kv8(const ekv_bank* bank, const ekv_step* step, int32_t dtype, EkvStepPlan* P) {
   const int rc = ekv_plan_step(bank, step, dtype, P);
   P->kv8 = 1;
+  P->fused_order = 0;      // (the kv8 instances keep order F)
   if (rc != EKV_OK) return rc;
   if (step->q_len != 1 || step->rope_on_read || (bank->head_dim != 64 && bank->head_dim != 128)) {
     P->one_launch = P->n_launches = P->n_list = 0;
@@ -779,6 +781,7 @@ int ekv_plan_batch(const ekv_bank* bank, const ekv_step* step, int32_t dtype, co
   }
   const int rc = ekv_plan_step(bank, env, dtype, P);
   P->batch = 1;
+  P->fused_order = 0;      // (the batch instances keep order F)
   if (int e = check_bank(bank)) return refuse(e);
   // the forms a batch does not take, whatever else the step says: chunk steps, RoPE-on-read, phased / deferred / slot-indexed steps
   if (step->q_len != 1 || step->rope_on_read || step->phases != 0 || step->defer_layers != 0 || step->tova_head_mean) return refuse(EKV_E_UNSUPPORTED);
@@ -899,6 +902,7 @@ static int step_attend_impl(const ekv_bank* bank, const ekv_step* st, int32_t dt
     if (kv8 && (L.kind == EKV_RUN_CHUNK_LDS || L.kind == EKV_RUN_RESIDENT || L.kind == EKV_RUN_CHUNK || L.kind == EKV_RUN_FLUSH)) return EKV_E_UNSUPPORTED;
     switch (L.kind) {
       case EKV_RUN_FUSED_DECODE:
+        aa.fused_order = (tb || kv8) ? 0 : P.fused_order;      // (shares its storage with score_tail, which only chunk launches set)
         e = tb ? ekv_launch_decode_fused_batch(aa, sa, *tb, D, lc, P.fused_nw, s, bf16) : ekv_launch_decode_fused(aa, sa, D, lc, P.fused_nw, s, bf16, kv8);
         break;
       case EKV_RUN_CHUNK_LDS: e = ekv_launch_chunk_lds(aa, sa, D, lc, s, bf16); break;
@@ -980,7 +984,7 @@ int ekv_kv8_step_info(const ekv_bank* bank, const ekv_step* st, int32_t dtype, c
   EkvStepPlan P;
   const bool ok = ekv_plan_step_kv8(&b, st, dtype, &P) == EKV_OK;
   const int32_t v[EKV_STEP_INFO_N] = {P.n_split, ok ? P.one_launch : 0, P.two_pass, P.wide, P.n_qblocks, P.qb_rows, P.n_col_parts,
-                                      P.fold_in_kernel, ok ? P.n_launches : 0};
+                                      P.fold_in_kernel, ok ? P.n_launches : 0, ok ? (P.fused_order & 3) : 0};
   for (int i = 0; i < n_info && i < EKV_STEP_INFO_N; ++i) info[i] = v[i];
   for (int i = EKV_STEP_INFO_N; i < n_info; ++i) info[i] = 0;
   return EKV_OK;
@@ -1021,7 +1025,7 @@ int ekv_batch_step_info(const ekv_bank* bank, const ekv_step* st, int32_t dtype,
   EkvSeqTable tb;
   const bool ok = ekv_plan_batch(bank, st, dtype, seqs, n_seq, &P, &env, &tb) == EKV_OK;
   const int32_t v[EKV_STEP_INFO_N] = {P.n_split, ok ? P.one_launch : 0, P.two_pass, P.wide, P.n_qblocks, P.qb_rows, P.n_col_parts,
-                                      P.fold_in_kernel, ok ? P.n_launches : 0};
+                                      P.fold_in_kernel, ok ? P.n_launches : 0, ok ? (P.fused_order & 3) : 0};
   for (int i = 0; i < n_info && i < EKV_STEP_INFO_N; ++i) info[i] = v[i];
   for (int i = EKV_STEP_INFO_N; i < n_info; ++i) info[i] = 0;
   return EKV_OK;

@@ -215,6 +215,31 @@ __global__ void __launch_bounds__(64 * NW, (NW >= 8 ? (REP == 1 ? 2 : 1) : (SLOT
   unsigned long long* stamps = reinterpret_cast<unsigned long long*>(sc.tova_row) + ((size_t)ll * a.n_kv_heads + h) * 8;
 #endif
   EKV_STAMP(0);
+  // ---- phase order of this workgroup (kOrders instances; a.fused_order: ekv_kernels.h).  Order F, what every other instance does:
+  // stream K+V, then the tail.  Order K: stream K, run the tail on the logits, stream V and replay the online softmax from the logits
+  // in LDS.  The tail is a latency-bound chain of block barriers that leaves HBM idle; when the workgroups of a CU are in different
+  // orders, each order's tail falls under the other's stream.  Both orders produce the same bits (below), so WHICH workgroups take
+  // order K may depend on where the hardware placed them.
+  constexpr bool kOrders = D == 128 && REP == 1 && !ROPE && NW == 4 && SLOT && ITEMS <= 12 && !EKV_KV8 && !EKV_BATCH;
+  bool order_k = false;
+  if constexpr (kOrders) {
+    const int om = a.fused_order & 3;
+    if (om == 2) {
+      order_k = scored;
+    } else if (om == 1 && scored) {
+      // one number per workgroup, from wave 0 (uniform by construction: the other waves read it from LDS, not from their own registers)
+      uint32_t* s_flag = reinterpret_cast<uint32_t*>(red.buf);
+      if (tid == 0) {
+        const uint32_t hw = __builtin_amdgcn_s_getreg(63492);   // HW_REG_HW_ID: WAVE_ID [3:0], TG_ID [19:16]
+        const int src = (a.fused_order >> 4) & 3;
+        const uint32_t x = src == 0 ? (hw >> 16) & 15u : (src == 1 ? hw & 15u : (uint32_t)(ll * a.n_kv_heads + h));
+        const bool below = (x & ((a.fused_order >> 8) & 15u)) < ((a.fused_order >> 12) & 15u);
+        *s_flag = below != (((a.fused_order >> 6) & 1) != 0) ? 1u : 0u;
+      }
+      __syncthreads();
+      order_k = __builtin_amdgcn_readfirstlane((int)*s_flag) != 0;
+    }
+  }
   const int32_t* slot_row = a.slot_of_pos + head_row;
   uint32_t* s_deadw = reinterpret_cast<uint32_t*>(red.buf + 2 * NW * 8);
   // ---- score rows -> LDS by asynchronous LDS-DMA, hidden inside the K/V stream (the ragged end follows after the stream) ----
@@ -250,6 +275,133 @@ __global__ void __launch_bounds__(64 * NW, (NW >= 8 ? (REP == 1 ? 2 : 1) : (SLOT
     }
     ekv_lds_barrier();
   };
+
+  if constexpr (kOrders) {
+    if (order_k) {
+      constexpr int LPR = Gm::LPR;
+      const int sub = lane % LPR, grp = lane / LPR;
+      const int new_row = slot_row[T - 1];
+      const uint8_t* s_dead = reinterpret_cast<const uint8_t*>(s_deadw);
+      // ---- K phase: raw logits of the live rows -> LDS at the physical row index (a logit depends on its row alone), running maximum
+      const uint4 qv = reinterpret_cast<const uint4*>(a.q + ((size_t)ll * a.n_q_heads + h) * D)[sub];
+      float mk = EKV_NEG_INF;
+      ekv_decode_plane_loop<D, NW>(a.k, head_row, E, mask_ready, [&](uint4 (&kr)[8], const int j0) {
+        const unsigned dead8 = (unsigned)s_dead[j0 >> 3];
+        float s[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+          const float acc = ekv_group_sum<LPR>(ekv_dot8(qv, kr[u], 0.f));
+          s[u] = !((dead8 >> u) & 1u) ? acc / a.sm_div : EKV_NEG_INF;
+        }
+        float mine = s[0];
+#pragma unroll
+        for (int u = 1; u < 8; ++u) mine = (sub == u) ? s[u] : mine;
+        if (sub < 8 && !((dead8 >> sub) & 1u)) s_logit[j0 + sub] = mine;
+#pragma unroll
+        for (int u = 0; u < 8; ++u) mk = fmaxf(mk, s[u]);
+      });
+      // the appended row: written to the bank (K and V) and scored from k_new, as in ekv_decode_stream
+      const __half* v_new_row = a.v_new + ((size_t)ll * a.n_kv_heads + h) * D;
+      if (wave == 0 && grp == 0) {
+        const uint4 kn = reinterpret_cast<const uint4*>(a.k_new + ((size_t)ll * a.n_kv_heads + h) * D)[sub];
+        const uint4 vn = reinterpret_cast<const uint4*>(v_new_row)[sub];
+        const size_t off_new = (head_row + new_row) * D;
+        reinterpret_cast<uint4*>(a.k_w + off_new)[sub] = kn;
+        reinterpret_cast<uint4*>(a.v_w + off_new)[sub] = vn;
+        const float acc = ekv_group_sum<LPR>(ekv_dot8(qv, kn, 0.f)) / a.sm_div;
+        if (sub == 0) s_logit[new_row] = acc;
+        mk = fmaxf(mk, acc);
+      }
+      ekv_tail_prefetch_ragged<NW>(sc, head_row, W, roco, sS, sQ, sC, false);
+      float cC[ITEMS];
+      int32_t cB[ITEMS];
+#pragma unroll
+      for (int it = 0; it < ITEMS; ++it) {
+        const int j = min(tid + it * 64 * NW, a.cap - 1);
+        cC[it] = roco ? sc.score_cnt[head_row + j] : 0.f;
+        cB[it] = sc.birth[head_row + j];
+      }
+      EKV_STAMP(1);
+      // the wave maxima where the tail looks for them (the maximum is exact in any order); the rest of s_part is the tail's candidate list
+      mk = ekv_wave_max(mk);
+      if (lane == 0) s_part[(size_t)wave * Gm::PS] = mk;
+      __syncthreads();  // publishes the maxima, s_logit and (vmcnt(0) before the barrier) the DMA'd score rows
+      uint32_t* s_hist = s_deadw + ekv_align(ekv_align((size_t)l_pad, 128) / 32, 4);
+      ekv_decode_tail_slot<REP, ITEMS, NW, true>(sc, ll, h, head_row, T, E, s_logit, l_pad, sS, sQ, cC, cB, red, s_hist,
+                                                 reinterpret_cast<unsigned long long*>(s_part), Gm::NP * REP * Gm::PS / 2, s_part, Gm::NP,
+                                                 Gm::PS, s_deadw, new_row, g_old, c_new, nb, nrep);
+      EKV_STAMP(2);
+      // ---- V phase: the fused loop's rows, in its order, with its online softmax — s[u] read back instead of computed, so (m, l, o)
+      // go through the same floating-point operations as in order F and the output is bit-identical
+      float m[1] = {EKV_NEG_INF}, l[1] = {0.f}, o[1][8];
+#pragma unroll
+      for (int i = 0; i < 8; ++i) o[0][i] = 0.f;
+      ekv_decode_plane_loop<D, NW>(a.v, head_row, E, EkvNoop(), [&](uint4 (&vr)[8], const int j0) {
+        const unsigned dead8 = (unsigned)s_dead[j0 >> 3];
+        float s[8];
+        if (dead8 == 0xFFu) {      // (nothing live here; past the extent there are no logits to read either)
+#pragma unroll
+          for (int u = 0; u < 8; ++u) s[u] = EKV_NEG_INF;
+        } else {
+          const float4 s0 = *reinterpret_cast<const float4*>(s_logit + j0), s1 = *reinterpret_cast<const float4*>(s_logit + j0 + 4);
+          s[0] = s0.x, s[1] = s0.y, s[2] = s0.z, s[3] = s0.w, s[4] = s1.x, s[5] = s1.y, s[6] = s1.z, s[7] = s1.w;
+        }
+        if (dead8 != 0u) {
+#pragma unroll
+          for (int u = 0; u < 8; ++u)
+            if ((dead8 >> u) & 1u) {
+              vr[u] = uint4{0, 0, 0, 0};
+              s[u] = EKV_NEG_INF;
+            }
+        }
+        float mx = s[0];
+#pragma unroll
+        for (int u = 1; u < 8; ++u) mx = fmaxf(mx, s[u]);
+        const float mn = fmaxf(m[0], mx);
+        if (mn == EKV_NEG_INF) return;
+        const float alpha = exp2f((m[0] - mn) * EKV_LOG2E);
+        l[0] *= alpha;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) o[0][i] *= alpha;
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+          const float p = exp2f((s[u] - mn) * EKV_LOG2E);
+          l[0] += p;
+          ekv_axpy8(p, vr[u], o[0]);
+        }
+        m[0] = mn;
+      });
+      if (wave == 0 && grp == 0) {      // the appended row, last, as in ekv_decode_stream
+        const uint4 vn = reinterpret_cast<const uint4*>(v_new_row)[sub];
+        const float acc = s_logit[new_row];
+        const float mn = fmaxf(m[0], acc);
+        const float alpha = m[0] == EKV_NEG_INF ? 0.f : exp2f((m[0] - mn) * EKV_LOG2E);
+        const float p = exp2f((acc - mn) * EKV_LOG2E);
+        l[0] = l[0] * alpha + p;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) o[0][i] *= alpha;
+        ekv_axpy8(p, vn, o[0]);
+        m[0] = mn;
+      }
+      ekv_decode_wave_combine<D, 1>(m, l, o);
+      ekv_decode_stash<D, 1, NW>(s_part, m, l, o);
+      __syncthreads();
+      for (int d = tid; d < D; d += 64 * NW) {
+        float mm, ls, os;
+        ekv_decode_reduce<D, 1, NW>(s_part, 0, d, mm, ls, os);
+        sc.out[((size_t)ll * a.n_q_heads + h) * D + d] = ekv_to_e(os / ls);
+      }
+      EKV_STAMP(5);
+#ifdef EKV_TAIL_PROFILE
+      if (tid == 0) {
+        stamps[3] = 1;
+        stamps[6] = __builtin_amdgcn_s_getreg(63492);
+        stamps[7] = __builtin_amdgcn_s_getreg(63508);
+      }
+#endif
+      return;
+    }
+  }
 
   // rows in flight per lane group: 8 for plain keys (REP = 1: neutral against 4, round 3; REP = 8: 114 vs 117 us despite 3..6 spilled
   // registers).  RoPE-on-read builds (EKV_ROPE_KU): rounds 1-5 kept 16 table floats per row next to the K / V registers (8 rows in flight

@@ -482,3 +482,41 @@ __device__ __forceinline__ void ekv_decode_reduce(const float* s_part, int r, in
     os += p[2 + d] * w;
   }
 }
+
+// One plane (K or V) of the physical-order stream on its own, for the phase order that runs the scorer tail between the K rows and
+// the V rows (ekv_attn_decode.inc, "order K").  Same row -> (wave, lane group, iteration) mapping as ekv_decode_stream with KU = 8:
+// lane group `grp` of wave `wave` takes rows base + grp * 8 .. + 7 of every block of NW * 32 rows, 16 lanes x 16 B per row.  With
+// one plane there are 8 loads per lane and iteration, so the NEXT iteration's rows are requested before the current ones are
+// consumed (two register sets, the loop unrolled by two): 16 x 16 B in flight per lane, as in the fused loop.  Rows past t1 are
+// clamped to t1 - 1 (requested and dropped; the dead-row bits decide what counts), so every request is unconditional and the
+// waits the compiler places count requests, not paths.  `first` runs once per wave, behind the first requests (mask_ready).
+template <int D, int NW, typename First, typename Consume>
+__device__ __forceinline__ void ekv_decode_plane_loop(const __half* plane, size_t head_row, int t1, First&& first, Consume&& consume) {
+  using Gm = EkvDecodeGeom<D, NW, 8, 8>;
+  static_assert(Gm::LIVE == Gm::LPR, "whole lane groups");
+  constexpr int RW = Gm::RW, STEP = NW * RW;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int sub = lane % Gm::LPR, grp = lane / Gm::LPR;
+  auto request = [&](uint4 (&r)[8], int base) {
+    const int j0 = base + grp * 8;
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int row = j0 + u < t1 ? j0 + u : t1 - 1;
+      const char* p = reinterpret_cast<const char*>(plane) + (head_row + row) * (D * 2);
+      r[u] = __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const ekv_u4*>(p) + sub));
+    }
+  };
+  uint4 ra[8], rb[8];
+  int base = wave * RW;
+  request(ra, base);
+  first();
+  while (base < t1) {
+    request(rb, base + STEP);
+    consume(ra, base + grp * 8);
+    base += STEP;
+    if (base >= t1) break;
+    request(ra, base + STEP);
+    consume(rb, base + grp * 8);
+    base += STEP;
+  }
+}

@@ -500,7 +500,10 @@ __device__ __forceinline__ void ekv_decode_tail(const EkvScoreArgs& sc, int ll, 
 // S / Q are staged in LDS by LDS-DMA under the stream (like the ordered layout's rows); C0 and birth come straight into registers
 // (`cB`, `cC`: loads issued by the caller when its stream ends, consumed after the softmax passes) — a third and fourth LDS row
 // would cost the fourth workgroup per CU.
-template <int REP, int ITEMS, int NW>
+// KEEP (one query head per KV head): the raw logits in s_logit stay as they are — exp(x - max) and the mean keys, which otherwise
+// overwrite them at the thread's own columns, live in registers.  Same arithmetic, same results; for the phase order that streams V
+// after the tail and replays the softmax from the logits (ekv_attn_decode.inc, "order K").
+template <int REP, int ITEMS, int NW, bool KEEP = false>
 __device__ __forceinline__ void ekv_decode_tail_slot(const EkvScoreArgs& sc, int ll, int h, size_t head_row, int T, int E,
                                                      float* s_logit, int l_pad, float* sS, float* sQ, const float (&cC)[ITEMS],
                                                      const int32_t (&cB)[ITEMS], RedN<NW>& red, uint32_t* s_hist,
@@ -530,17 +533,21 @@ __device__ __forceinline__ void ekv_decode_tail_slot(const EkvScoreArgs& sc, int
     float mx[REP], sm[REP];
 #pragma unroll
     for (int r = 0; r < REP; ++r) mx[r] = EKV_NEG_INF, sm[r] = 0.f;
+    static_assert(!KEEP || REP == 1, "KEEP: one query head per KV head");
+    float ek[KEEP ? ITEMS : 1];      // KEEP: e of this thread's rows
 #pragma unroll
     for (int r = 0; r < REP; ++r)
       for (int i = 0; i < n_part; ++i) mx[r] = fmaxf(mx[r], part_max[(size_t)(i * REP + r) * part_stride]);
 #pragma unroll
     for (int it = 0; it < ITEMS; ++it) {
       const int j = tid + it * NT;
+      if constexpr (KEEP) ek[it] = 0.f;
       if (j < E) {
 #pragma unroll
         for (int r = 0; r < REP; ++r) {
           const float e = lives(it) ? expf(s_logit[(size_t)r * l_pad + j] - mx[r]) : 0.f;
-          s_logit[(size_t)r * l_pad + j] = e;
+          if constexpr (KEEP) ek[it] = e;
+          else s_logit[(size_t)r * l_pad + j] = e;
           sm[r] += e;
         }
       }
@@ -556,7 +563,7 @@ __device__ __forceinline__ void ekv_decode_tail_slot(const EkvScoreArgs& sc, int
         float pb = 0.f;
 #pragma unroll
         for (int r = 0; r < REP; ++r)
-          if (r < nrep) pb += s_logit[(size_t)r * l_pad + j] * inv_sm[r];
+          if (r < nrep) pb += (KEEP ? ek[it] : s_logit[(size_t)r * l_pad + j]) * inv_sm[r];
         if (REP > 1) pb = pb / (float)nrep;
         const bool fresh = j == new_row || sc.policy == EKV_POLICY_TOVA;
         const float s_new = fresh ? pb : sS[j] + pb;
@@ -612,6 +619,7 @@ __device__ __forceinline__ void ekv_decode_tail_slot(const EkvScoreArgs& sc, int
     const uint32_t kSent = ekv_fkey(1e9f);
     uint32_t kstd[ITEMS];                       // std keys; rows that are not live rank after everything (composite ~0)
     uint32_t* kmean = reinterpret_cast<uint32_t*>(s_logit);
+    uint32_t km[KEEP ? ITEMS : 1];              // KEEP: the mean keys of this thread's rows
     auto comp = [&](int it) { return lives(it) ? (((unsigned long long)kstd[it] << 32) | (uint32_t)rB[it]) : ~0ull; };
     uint32_t kmin = ~0u, nmax = ~0u;
 #pragma unroll
@@ -624,7 +632,8 @@ __device__ __forceinline__ void ekv_decode_tail_slot(const EkvScoreArgs& sc, int
         float sd = sqrtf(sQ[j] / c - mean * mean);   //  is bit-identical only while numerator * 2^-24 stays normal — sums of p^2 do not)
         if (rB[it] > b_prot) sd = 1e9f;
         key = ekv_fkey(sd);
-        kmean[j] = ekv_fkey(mean);               // for the arg-min over the feasible set below (own column of the dead e row)
+        if constexpr (KEEP) km[it] = ekv_fkey(mean);
+        else kmean[j] = ekv_fkey(mean);          // for the arg-min over the feasible set below (own column of the dead e row)
         if (key < kSent) {
           kmin = min(kmin, key);
           nmax = min(nmax, ~key);
@@ -783,7 +792,7 @@ __device__ __forceinline__ void ekv_decode_tail_slot(const EkvScoreArgs& sc, int
     for (int it = 0; it < ITEMS; ++it) {
       const int j = tid + it * NT;
       if (lives(it) && comp(it) < thr) {
-        const unsigned long long x = ((unsigned long long)kmean[j] << 32) | (uint32_t)rB[it];
+        const unsigned long long x = ((unsigned long long)(KEEP ? km[it] : kmean[j]) << 32) | (uint32_t)rB[it];
         best = x < best ? x : best;
       }
     }

@@ -30,6 +30,7 @@ struct EkvStepPlan {
   int32_t n_partials;   // partials per query row the scorer folds (chunk kernels emit 2 per split)
   int32_t qb_rows, n_qblocks, n_col_parts;
   int32_t fused_nw;     // waves per workgroup of the fused decode kernel for this launch (4 or 8)
+  int32_t fused_order;  // phase order of its workgroups (ekv_decode_fused_order)
   int32_t l_pad, phys_extent;   // see EkvAttnArgs
   int32_t two_pass;
   int32_t wide;             // chunk step on the wide-query-block kernel (ekv_attn_wide.inc): ONE partial per split, ONE column-sum row
@@ -117,7 +118,12 @@ struct EkvAttnArgs {
   int32_t new_in_cache;
   // column-sum pass of the wide-block kernel: 1 = the scorer of the step runs as the tail of this launch (ekv_wide_tail.h; the
   // EkvScoreArgs are the launch's second argument); set only for heads whose column sums ONE workgroup writes
-  int32_t score_tail;
+  // fused decode step: the phase order of its workgroups (ekv_decode_fused_order; 0 = every workgroup streams K+V and then runs its
+  // tail).  Decode steps have no use for score_tail, whose storage it shares, so the struct stays as it was.
+  union {
+    int32_t score_tail;
+    int32_t fused_order;
+  };
   // row strides in elements (ekv_step.*_stride, ABI 8; always filled in: the dense layout is q_ts = D, q_hs = q_len * D, ...): row
   // (layer ll, head hd, token i) of q sits at ((size_t)ll * n_q_heads * q_len) * D + hd * q_hs + i * q_ts, k_new / v_new and out alike
   int32_t q_ts, q_hs, kv_ts, kv_hs, o_ts, o_hs;
@@ -178,6 +184,11 @@ hipError_t ekv_launch_tova_headmean(const EkvScoreArgs& a, int layer_count, hipS
 hipError_t ekv_launch_score_select(const EkvScoreArgs& a, int layer_count, hipStream_t s, bool bf16);
 bool ekv_attn_decode_supported(int head_dim, int rep);
 int ekv_decode_fused_nw(int n_heads_in_launch);
+// Phase order of the fused decode step's workgroups (ekv_attn_decode.inc, "order K"; the kernel field EkvAttnArgs.fused_order).  Bits
+// 0-1: 0 = all F (K+V stream, then the tail), 1 = mixed per CU, 2 = all K (K stream, tail, V stream).  Mixed: bits 4-5 = the number x that
+// decides (0 HW_ID.TG_ID, 1 HW_ID.WAVE_ID of wave 0, 2 the workgroup's index in the launch), bits 8-11 a mask m, bits 12-15 a bound b,
+// bit 6 = invert: order K when ((x & m) < b) != invert.  Both orders produce the same bits, so a hardware-derived number is as good as any.
+int ekv_decode_fused_order(int head_dim, int rep, bool scored, bool slot_rows, int nw, int n_heads_in_launch, int phys_extent);
 bool ekv_decode_fused_supported(int head_dim, int rep, int n_slots, int t_pad, int l_pad, int n_evict, int cap, int nw);
 hipError_t ekv_launch_decode_fused(const EkvAttnArgs& a, const EkvScoreArgs& sc, int head_dim, int layer_count, int nw, hipStream_t s,
                                    bool bf16, bool kv8 = false);

@@ -460,12 +460,12 @@ class KVBank:
         """The library's dispatch decisions for this step (ekv_step_info): n_split, fused, two_pass, wide, n_qblocks, ..."""
         st = self.make_step(plan, q_len, layer_begin, self.n_layers - layer_begin if layer_count is None else layer_count)
         st.phases = phases
-        info = (C.c_int32 * 9)()
+        info = (C.c_int32 * 10)()
         if self._kv8 is not None:
-            check(self.lib.ekv_kv8_step_info(C.byref(self._bank), C.byref(st), self._dt, C.byref(self._kv8), info, 9), "ekv_kv8_step_info")
+            check(self.lib.ekv_kv8_step_info(C.byref(self._bank), C.byref(st), self._dt, C.byref(self._kv8), info, 10), "ekv_kv8_step_info")
         else:
-            check(self.lib.ekv_step_info_typed(C.byref(self._bank), C.byref(st), self._dt, info, 9), "ekv_step_info")
-        keys = ("n_split", "fused", "two_pass", "wide", "n_qblocks", "qb_rows", "n_col_parts", "fold_in_kernel", "n_launches")
+            check(self.lib.ekv_step_info_typed(C.byref(self._bank), C.byref(st), self._dt, info, 10), "ekv_step_info")
+        keys = ("n_split", "fused", "two_pass", "wide", "n_qblocks", "qb_rows", "n_col_parts", "fold_in_kernel", "n_launches", "fused_order")
         return dict(zip(keys, (int(x) for x in info)))
 
     def join(self):
@@ -771,9 +771,9 @@ class KVBankBatch:
 
     def step_info(self, plans, layer, active=None, n_split=0) -> dict:
         st, tb, _ = self.make_table(plans, layer, active, n_split)
-        info = (C.c_int32 * 9)()
-        check(self.lib.ekv_batch_step_info(C.byref(self.bank._bank), C.byref(st), self.bank._dt, tb, len(tb), info, 9), "ekv_batch_step_info")
-        keys = ("n_split", "fused", "two_pass", "wide", "n_qblocks", "qb_rows", "n_col_parts", "fold_in_kernel", "n_launches")
+        info = (C.c_int32 * 10)()
+        check(self.lib.ekv_batch_step_info(C.byref(self.bank._bank), C.byref(st), self.bank._dt, tb, len(tb), info, 10), "ekv_batch_step_info")
+        keys = ("n_split", "fused", "two_pass", "wide", "n_qblocks", "qb_rows", "n_col_parts", "fold_in_kernel", "n_launches", "fused_order")
         return dict(zip(keys, (int(x) for x in info)))
 
     def attend(self, plans, q, k_new, v_new, layer, active=None, out=None, evict_ids=None, n_split=0):

@@ -159,10 +159,12 @@ int ekv_step_plan(const ekv_bank *bank, const ekv_step *step, int32_t *n_split, 
  * (ABI 5): info[0 .. n_info) <- { n_split, fused, two_pass (1 = statistics + column-sum scheme, no logits in HBM), wide (1 = the
  * 32x32x16 wide-block kernel, which walks all query blocks of a head inside one launch), n_qblocks, qb_rows, n_col_parts,
  * fold_in_kernel, n_launches (ABI 7: kernel launches this call issues — a two-pass wide step is 2 since the scorer became the tail
- * of its column-sum pass, 3 before; 0 = the dispatch refuses the step) }; entries beyond EKV_STEP_INFO_N are zeroed.  The reference has no counterpart (its keep_attention prefix
+ * of its column-sum pass, 3 before; 0 = the dispatch refuses the step), fused_order (phase order of the one-launch decode step's
+ * workgroups: 0 = all stream K+V and then run the scorer tail, 1 = mixed per CU with workgroups that run the tail between the K and
+ * the V rows, 2 = all of those; same results either way; EKV_FUSED_ORDER=0|1|2 in the environment forces it) }; entries beyond EKV_STEP_INFO_N are zeroed.  The reference has no counterpart (its keep_attention prefix
  * materialises the r x r map, easykv/easykv.py:396-405); easykv_amd.api uses it to decide whether a scored prefix goes down as
  * one step or in query blocks. */
-#define EKV_STEP_INFO_N 9
+#define EKV_STEP_INFO_N 10
 int ekv_step_info(const ekv_bank *bank, const ekv_step *step, int32_t *info, int32_t n_info);
 int ekv_step_info_typed(const ekv_bank *bank, const ekv_step *step, int32_t dtype, int32_t *info, int32_t n_info);
 
