@@ -3,6 +3,7 @@ from __future__ import annotations
 
 import glob
 import os
+import re
 import subprocess
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -14,12 +15,59 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fP
 OBJ = os.path.join(CSRC, "obj")
 
 
+MANIFEST = os.path.join(CSRC, "ekv_instances.def")
+
+
+def _tags(*words):
+    """File-name tags of an instance's words, in the order the object names have always had: rope, batch / kv8, bf16."""
+    return "".join("_" + w for w in ("batch", "kv8", "bf16") if w in words)
+
+
+def _on(*words):
+    sw = {"bf16": "EKV_BF16", "kv8": "EKV_KV8", "batch": "EKV_BATCH"}
+    return [f"-D{sw[w]}=1" for w in ("kv8", "batch", "bf16") if w in words]
+
+
+# family of a manifest line -> (its kernel source, object name, -D switches), all from the line's words
+FAMILIES = {
+    "EKV_DECODE": lambda d, keys, elem, rows, batching: (
+        "ekv_attn_decode.inc", f"ekv_attn_decode_d{d}_{keys}" + _tags(elem, rows, batching),
+        _on(elem, rows, batching) + [f"-DEKV_D={d}", "-DEKV_ROPE=" + ("true" if keys == "rope" else "false")]),
+    "EKV_DECODE_SCORE": lambda elem, batching: (
+        "ekv_decode_score.inc", "ekv_decode_score" + _tags(elem, batching), _on(elem, batching)),
+    "EKV_CHUNK": lambda d, m, elem: (
+        "ekv_attn_chunk.inc", f"ekv_attn_chunk_d{d}_m{m}" + _tags(elem), _on(elem) + [f"-DEKV_D={d}", f"-DEKV_CHUNK_MODE={m}"]),
+    "EKV_WIDE": lambda d, m, keys, elem: (
+        "ekv_attn_wide.inc", "ekv_attn_wide" + ("_rope" if keys == "rope" else "") + f"_d{d}_m{m}" + _tags(elem),
+        _on(elem) + [f"-DEKV_D={d}", f"-DEKV_WIDE_MODE={m}"] + (["-DEKV_WIDE_ROPE=1"] if keys == "rope" else [])),
+    "EKV_CHUNK_LDS": lambda d, elem: ("ekv_chunk_lds.inc", f"ekv_chunk_lds_d{d}" + _tags(elem), _on(elem) + [f"-DEKV_D={d}"]),
+    "EKV_RESIDENT": lambda d, elem: ("ekv_attn_resident.inc", f"ekv_attn_resident_d{d}" + _tags(elem), _on(elem)),
+    "EKV_SCORE_SELECT": lambda nt, elem: ("ekv_score_select.inc", f"ekv_score_select_nt{nt}" + _tags(elem), _on(elem) + [f"-DEKV_SS_NT={nt}"]),
+}
+
+
+def instances():
+    """(family, words) of every line of the manifest, in order."""
+    with open(MANIFEST) as f:
+        found = re.findall(r"^(EKV_[A-Z_]+)\(([^)]*)\)", f.read(), re.M)
+    return [(fam, tuple(w.strip() for w in args.split(","))) for fam, args in found]
+
+
 def sources():
     return sorted(glob.glob(os.path.join(CSRC, "*.hip")))
 
 
+def objects():
+    """(object name, hipcc arguments that select its source) of everything in the library: the .hip files and the manifest's instances."""
+    objs = [(os.path.basename(src)[:-4], [src]) for src in sources()]
+    for fam, words in instances():
+        inc, name, defs = FAMILIES[fam](*words)
+        objs.append((name, defs + ["-x", "hip", os.path.join(CSRC, inc)]))
+    return objs
+
+
 def headers():
-    return (glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.inc")) +
+    return (glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.inc")) + [MANIFEST] +
             [os.path.join(HERE, "..", "include", "easykv_hip.h")])
 
 
@@ -32,7 +80,7 @@ def stale() -> bool:
 
 
 def build_lib(force: bool = False, verbose: bool = False, jobs: int = 0) -> str:
-    """Compile every .hip to an object (in parallel; unchanged objects are reused) and link the .so."""
+    """Compile every .hip and every instance of the manifest to an object (in parallel; unchanged objects are reused) and link the .so."""
     if not force and not stale():
         return LIB
     from concurrent.futures import ThreadPoolExecutor
@@ -40,11 +88,12 @@ def build_lib(force: bool = False, verbose: bool = False, jobs: int = 0) -> str:
     os.makedirs(OBJ, exist_ok=True)
     hdr_t = max(os.path.getmtime(h) for h in headers())
     todo, objs = [], []
-    for src in sources():
-        obj = os.path.join(OBJ, os.path.basename(src)[:-4] + ".o")
+    for name, args in objects():
+        obj = os.path.join(OBJ, name + ".o")
         objs.append(obj)
-        if force or not os.path.exists(obj) or os.path.getmtime(obj) < max(os.path.getmtime(src), hdr_t):
-            todo.append([hipcc] + FLAGS + ["-c", src, "-o", obj])
+        src_t = os.path.getmtime(args[-1])
+        if force or not os.path.exists(obj) or os.path.getmtime(obj) < max(src_t, hdr_t):
+            todo.append([hipcc] + FLAGS + ["-c"] + args + ["-o", obj])
 
     def run(cmd):
         if verbose:

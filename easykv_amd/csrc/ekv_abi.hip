@@ -291,43 +291,6 @@ const char* ekv_strerror(int code) {
   }
 }
 
-size_t ekv_workspace_bytes_typed(const ekv_bank* bank, const ekv_step* step, int32_t dtype) {
-  EkvStepPlan P;
-  (void)ekv_plan_step(bank, step, dtype, &P);
-  return P.bytes;
-}
-
-size_t ekv_workspace_bytes(const ekv_bank* bank, const ekv_step* step) { return ekv_workspace_bytes_typed(bank, step, EKV_DTYPE_F16); }
-
-int ekv_step_plan(const ekv_bank* bank, const ekv_step* st, int32_t* n_split, int32_t* fused) {
-  if (int e = check_bank(bank)) return e;
-  if (!st || !n_split || !fused) return EKV_E_ARG;
-  EkvStepPlan P;
-  const int rc = ekv_plan_step(bank, st, EKV_DTYPE_F16, &P);
-  *n_split = P.n_split;
-  // one launch for the whole step: the fused decode kernel, the logits-in-LDS or logits-resident chunk kernel, or a chunk step whose
-  // scorer runs as the tail of the attention kernel; a step the call would refuse plans as 0
-  *fused = rc == EKV_OK ? P.one_launch : 0;
-  return EKV_OK;
-}
-
-int ekv_step_info_typed(const ekv_bank* bank, const ekv_step* st, int32_t dtype, int32_t* info, int32_t n_info) {
-  if (dtype != EKV_DTYPE_F16 && dtype != EKV_DTYPE_BF16) return EKV_E_ARG;
-  if (int e = check_bank(bank)) return e;
-  if (!st || !info || n_info < 1) return EKV_E_ARG;
-  EkvStepPlan P;
-  const bool ok = ekv_plan_step(bank, st, dtype, &P) == EKV_OK;
-  const int32_t v[EKV_STEP_INFO_N] = {P.n_split, ok ? P.one_launch : 0, P.two_pass, P.wide, P.n_qblocks, P.qb_rows, P.n_col_parts,
-                                      P.fold_in_kernel, ok ? P.n_launches : 0, ok ? (P.fused_order & 3) : 0};
-  for (int i = 0; i < n_info && i < EKV_STEP_INFO_N; ++i) info[i] = v[i];
-  for (int i = EKV_STEP_INFO_N; i < n_info; ++i) info[i] = 0;
-  return EKV_OK;
-}
-
-int ekv_step_info(const ekv_bank* bank, const ekv_step* st, int32_t* info, int32_t n_info) {
-  return ekv_step_info_typed(bank, st, EKV_DTYPE_F16, info, n_info);
-}
-
 int ekv_bank_reset(const ekv_bank* bank, void* stream) {
   if (int e = check_bank(bank)) return e;
   drop_stale_error();
@@ -409,7 +372,7 @@ static EkvScoreArgs score_args(const ekv_bank* bank, const ekv_step* st, const E
 // The whole dispatch of ekv_step_attend for a step: argument / shape / capability checks (the return code of the call, in the
 // order the call reports them), the tiling, the workspace layout and the launch sequence.  The tiling and the layout are filled in
 // for every step that has something to tile, also when the step is refused (ekv_workspace_bytes and ekv_step_info report them).
-static int plan_step_impl(const ekv_bank* bank, const ekv_step* step, EkvStepPlan* P) {
+static int ekv_plan_step(const ekv_bank* bank, const ekv_step* step, EkvStepPlan* P) {
   *P = EkvStepPlan{};
   const int bank_rc = check_bank(bank);
   if (!bank || !step) return bank_rc ? bank_rc : EKV_E_ARG;
@@ -709,120 +672,174 @@ static int plan_step_impl(const ekv_bank* bank, const ekv_step* step, EkvStepPla
   return EKV_OK;
 }
 
+// ---- one call path --------------------------------------------------------------------------------------------------------------
+// A call of the step family as its entry points spell it: the untyped / _typed functions (a bank, a step, an element type), ekv_kv8_*
+// (+ the FP8 planes) and ekv_batch_* (+ the table of a batched decode step).  The axes are independent here; which combinations run
+// is the planner's business (resolve_call) and the manifest's (ekv_instances.def).
+struct EkvCall {
+  const ekv_bank* bank;
+  const ekv_step* step;
+  int32_t dtype;
+  bool kv8;                // an ekv_kv8_* call (q8 may still be NULL: an argument error)
+  const ekv_kv8* q8;
+  bool batch;              // an ekv_batch_* call
+  const ekv_seq* seqs;
+  int32_t n_seq;
+};
+static EkvCall step_call(const ekv_bank* bank, const ekv_step* st, int32_t dtype) { return {bank, st, dtype, false, nullptr, false, nullptr, 0}; }
+static EkvCall kv8_call(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_kv8* q8) { return {bank, st, dtype, true, q8, false, nullptr, 0}; }
+static EkvCall batch_call(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_seq* seqs, int32_t n_seq) {
+  return {bank, st, dtype, false, nullptr, true, seqs, n_seq};
+}
+
+// Everything a call needs, resolved once (resolve_call): check, info, workspace bytes and attend all read it.
+struct EkvResolved {
+  const ekv_bank* bank;      // the bank planned and launched with; NULL: a kv8 call without its planes
+  const ekv_step* step;      // the step actually planned: the caller's, or the envelope of a batch
+  const EkvSeqTable* tb;     // the table the batch instances receive; NULL for a uniform step
+  EkvStepPlan plan;          // kv8 / batch / fused_order final; zero launches (a batch: zero bytes too) when the call is refused
+  ekv_bank bank8;            // storage of the above, where the call needs its own
+  ekv_step env;
+  EkvSeqTable table;
+};
+
+// The return code of the call, in the order the call reports its errors.  Stages: element type -> the bank a kv8 call runs on ->
+// envelope and table of a batch -> the plan of the (16-bit, uniform) step -> what the variant does not take.
+//
 // The element type only picks the kernel instances: a bf16 step is planned as the fp16 step.  RoPE-on-read keeps hi / lo fp16 planes
 // of the rotated keys and queries (ekv_attn_wide.inc, ekv_rope_q_kernel) and has no bf16 build.
-int ekv_plan_step(const ekv_bank* bank, const ekv_step* step, int32_t dtype, EkvStepPlan* P) {
-  if (dtype != EKV_DTYPE_F16 && dtype != EKV_DTYPE_BF16) {
-    *P = EkvStepPlan{};
-    return EKV_E_ARG;
-  }
-  const int rc = plan_step_impl(bank, step, P);
-  P->bf16 = dtype == EKV_DTYPE_BF16;
-  if (rc == EKV_OK && P->bf16 && step->rope_on_read) {
-    P->one_launch = P->n_launches = P->n_list = 0;
-    return EKV_E_UNSUPPORTED;
-  }
-  return rc;
-}
-
-// FP8 rows: the plan of the 16-bit step of the same shape (the scorers read logits and partials, never a K/V element, so splits,
-// launches and workspace carry over), run on the kv8 instances of the two decode attention kernels — which is all a kv8 bank has.
-int ekv_plan_step_kv8(const ekv_bank* bank, const ekv_step* step, int32_t dtype, EkvStepPlan* P) {
-  const int rc = ekv_plan_step(bank, step, dtype, P);
-  P->kv8 = 1;
-  P->fused_order = 0;      // (the kv8 instances keep order F)
-  if (rc != EKV_OK) return rc;
-  if (step->q_len != 1 || step->rope_on_read || (bank->head_dim != 64 && bank->head_dim != 128)) {
-    P->one_launch = P->n_launches = P->n_list = 0;
-    return EKV_E_UNSUPPORTED;
-  }
-  return EKV_OK;
-}
-
+// FP8 rows: the code planes stand where the 16-bit rows were (bank->k / bank->v are not read), and the plan is that of the 16-bit step
+// of the same shape (the scorers read logits and partials, never a K/V element, so splits, launches and workspace carry over), run on
+// the kv8 instances of the two decode attention kernels — which is all a kv8 bank has: decode steps, plain keys, head_dim 64 / 128.
 // A batched decode step (include/easykv_hip.h, ekv_seq): the plan of the uniform step of the batch's ENVELOPE — the longest entry, the
-// widest extent, one "layer" per entry — with plan->batch set, exactly as a kv8 plan is the 16-bit plan plus a flag: same splits,
-// launches and workspace pitches, so a uniform table plans field for field as the multi-layer step it spells out.  The entries keep
-// their own bounds inside those pitches (the kernels' batch instances read them from the table).  `tb` receives the table the
-// kernels get: the entries with phys_extent resolved as ekv_plan_step resolves a step's.
-int ekv_plan_batch(const ekv_bank* bank, const ekv_step* step, int32_t dtype, const ekv_seq* seqs, int32_t n_seq, EkvStepPlan* P,
-                   ekv_step* env, EkvSeqTable* tb) {
+// widest extent, one "layer" per entry: same splits, launches and workspace pitches, so a uniform table plans field for field as the
+// multi-layer step it spells out.  The entries keep their own bounds inside those pitches (the kernels' batch instances read them
+// from the table, whose entries have phys_extent resolved as ekv_plan_step resolves a step's).
+static int resolve_call(const EkvCall& c, EkvResolved* r) {
+  EkvStepPlan* P = &r->plan;
   *P = EkvStepPlan{};
-  if (dtype != EKV_DTYPE_F16 && dtype != EKV_DTYPE_BF16) return EKV_E_ARG;
-  if (!bank || !step || !seqs || n_seq < 1 || n_seq > EKV_MAX_SEQS) return EKV_E_ARG;
+  r->bank = c.kv8 ? nullptr : c.bank;
+  r->step = c.step;
+  r->tb = nullptr;
+  if (c.dtype != EKV_DTYPE_F16 && c.dtype != EKV_DTYPE_BF16) return EKV_E_ARG;
+  if (c.kv8) {
+    const ekv_kv8* q8 = c.q8;
+    if (!c.bank || !q8 || !q8->k_codes || !q8->v_codes || !q8->k_scale || !q8->v_scale) return EKV_E_ARG;
+    r->bank8 = *c.bank;
+    r->bank8.k = q8->k_codes;
+    r->bank8.v = q8->v_codes;
+    r->bank = &r->bank8;
+  }
+  const ekv_bank* bank = r->bank;
+  if (c.batch) {
+    const ekv_seq* seqs = c.seqs;
+    if (!bank || !c.step || !seqs || c.n_seq < 1 || c.n_seq > EKV_MAX_SEQS) return EKV_E_ARG;
+    ekv_step* env = &r->env;
+    *env = *c.step;
+    env->layer_begin = 0;
+    env->layer_count = c.n_seq;
+    env->n_slots = env->n_evict = env->phys_extent = 0;
+    env->score_off = seqs[0].score_off;
+    for (int i = 0; i < c.n_seq; ++i) {
+      const ekv_seq& e = seqs[i];
+      ekv_seq& t = r->table.e[i];
+      t = e;
+      t.phys_extent = (e.phys_extent >= e.n_slots && e.phys_extent <= bank->cap) ? e.phys_extent : bank->cap;
+      env->n_slots = std::max(env->n_slots, e.n_slots);
+      env->n_evict = std::max(env->n_evict, e.n_evict);
+      env->phys_extent = std::max(env->phys_extent, t.phys_extent);
+      env->score_off = std::min(env->score_off, e.score_off);
+    }
+    // (selection windows are bounds, not pitches: the envelope carries the widest candidate set an entry's checks can leave)
+    env->win_lo = env->win_tail = env->range_start = 0;
+    env->roco_k1 = env->n_evict;
+    // the table first: an entry the single-sequence step would refuse as an argument error is one here, whatever the envelope says
+    for (int i = 0; i < c.n_seq; ++i) {
+      const ekv_seq& e = seqs[i];
+      if (e.layer < 0 || e.layer >= bank->n_layers || e.n_slots < 1 || e.n_slots > bank->cap) return EKV_E_ARG;
+      for (int j = 0; j < i; ++j)
+        if (seqs[j].layer == e.layer) return EKV_E_ARG;
+    }
+    r->step = env;
+    r->tb = &r->table;
+  }
+
+  const int rc = ekv_plan_step(bank, r->step, P);
+  P->bf16 = c.dtype == EKV_DTYPE_BF16;
+  P->kv8 = c.kv8;
+  P->batch = c.batch;
+  if (c.kv8 || c.batch) P->fused_order = 0;      // (the kv8 and the batch instances keep order F)
   auto refuse = [&](int code) {
     P->one_launch = P->n_launches = P->n_list = 0;
-    P->bytes = 0;      // (nothing will run: ekv_batch_workspace_bytes of a refused table is 0)
+    if (c.batch) P->bytes = 0;      // (nothing will run: ekv_batch_workspace_bytes of a refused table is 0)
     return code;
   };
-  // ---- the envelope
-  *env = *step;
-  env->layer_begin = 0;
-  env->layer_count = n_seq;
-  env->n_slots = env->n_evict = env->phys_extent = 0;
-  env->score_off = seqs[0].score_off;
-  for (int i = 0; i < n_seq; ++i) {
-    const ekv_seq& e = seqs[i];
-    tb->e[i] = e;
-    tb->e[i].phys_extent = (e.phys_extent >= e.n_slots && e.phys_extent <= bank->cap) ? e.phys_extent : bank->cap;
-    env->n_slots = std::max(env->n_slots, e.n_slots);
-    env->n_evict = std::max(env->n_evict, e.n_evict);
-    env->phys_extent = std::max(env->phys_extent, tb->e[i].phys_extent);
-    env->score_off = std::min(env->score_off, e.score_off);
+  const ekv_step* st = c.step;
+  if (c.batch) {
+    if (int e = check_bank(bank)) return refuse(e);
+    // the forms a batch does not take, whatever else the step says: chunk steps, RoPE-on-read, phased / deferred / slot-indexed steps
+    if (st->q_len != 1 || st->rope_on_read || st->phases != 0 || st->defer_layers != 0 || st->tova_head_mean) return refuse(EKV_E_UNSUPPORTED);
   }
-  // (selection windows are bounds, not pitches: the envelope carries the widest candidate set an entry's checks can leave)
-  env->win_lo = env->win_tail = env->range_start = 0;
-  env->roco_k1 = env->n_evict;
-  // the table first: an entry the single-sequence step would refuse as an argument error is one here, whatever the envelope says
-  for (int i = 0; i < n_seq; ++i) {
-    const ekv_seq& e = seqs[i];
-    if (e.layer < 0 || e.layer >= bank->n_layers || e.n_slots < 1 || e.n_slots > bank->cap) return EKV_E_ARG;
-    for (int j = 0; j < i; ++j)
-      if (seqs[j].layer == e.layer) return EKV_E_ARG;
-  }
-  const int rc = ekv_plan_step(bank, env, dtype, P);
-  P->batch = 1;
-  P->fused_order = 0;      // (the batch instances keep order F)
-  if (int e = check_bank(bank)) return refuse(e);
-  // the forms a batch does not take, whatever else the step says: chunk steps, RoPE-on-read, phased / deferred / slot-indexed steps
-  if (step->q_len != 1 || step->rope_on_read || step->phases != 0 || step->defer_layers != 0 || step->tova_head_mean) return refuse(EKV_E_UNSUPPORTED);
+  if (rc == EKV_OK && P->bf16 && st->rope_on_read) return refuse(EKV_E_UNSUPPORTED);
   if (rc != EKV_OK) return refuse(rc);
-  for (int i = 0; i < n_seq; ++i) {      // per entry: the checks of the single-sequence step of that entry's geometry
-    const ekv_seq& e = seqs[i];
-    ekv_step one = *step;
-    one.layer_begin = e.layer, one.layer_count = 1, one.n_split = P->n_split;
-    one.n_slots = e.n_slots, one.score_off = e.score_off, one.n_evict = e.n_evict, one.win_lo = e.win_lo, one.win_tail = e.win_tail;
-    one.roco_k1 = e.roco_k1, one.range_start = e.range_start, one.phys_extent = e.phys_extent;
-    EkvStepPlan P1;
-    if (ekv_plan_step(bank, &one, dtype, &P1) == EKV_E_ARG) return refuse(EKV_E_ARG);
-  }
-  // the kernels with a batch instance: the one-launch step, the split attention kernel (+ fold) and the fast scorer behind it, the
-  // range compaction.  What is left to the generic scorer (GQA factors > 8, rows beyond 6144 slots, cap % 4 != 0) has none.
-  for (int i = 0; i < P->n_list; ++i) {
-    const int kind = P->list[i].kind;
-    if (kind != EKV_RUN_FUSED_DECODE && kind != EKV_RUN_DECODE && kind != EKV_RUN_FOLD && kind != EKV_RUN_RANGE && kind != EKV_RUN_DECODE_SCORE)
-      return refuse(EKV_E_UNSUPPORTED);
+  if (c.kv8 && (st->q_len != 1 || st->rope_on_read || (bank->head_dim != 64 && bank->head_dim != 128))) return refuse(EKV_E_UNSUPPORTED);
+  if (c.batch) {
+    for (int i = 0; i < c.n_seq; ++i) {      // per entry: the checks of the single-sequence step of that entry's geometry
+      const ekv_seq& e = c.seqs[i];
+      ekv_step one = *st;
+      one.layer_begin = e.layer, one.layer_count = 1, one.n_split = P->n_split;
+      one.n_slots = e.n_slots, one.score_off = e.score_off, one.n_evict = e.n_evict, one.win_lo = e.win_lo, one.win_tail = e.win_tail;
+      one.roco_k1 = e.roco_k1, one.range_start = e.range_start, one.phys_extent = e.phys_extent;
+      EkvStepPlan P1;
+      if (ekv_plan_step(bank, &one, &P1) == EKV_E_ARG) return refuse(EKV_E_ARG);
+    }
+    // the kernels with a batch instance: the one-launch step, the split attention kernel (+ fold) and the fast scorer behind it, the
+    // range compaction.  What is left to the generic scorer (GQA factors > 8, rows beyond 6144 slots, cap % 4 != 0) has none.
+    for (int i = 0; i < P->n_list; ++i) {
+      const int kind = P->list[i].kind;
+      if (kind != EKV_RUN_FUSED_DECODE && kind != EKV_RUN_DECODE && kind != EKV_RUN_FOLD && kind != EKV_RUN_RANGE && kind != EKV_RUN_DECODE_SCORE)
+        return refuse(EKV_E_UNSUPPORTED);
+    }
   }
   return EKV_OK;
 }
 
-// The bank a kv8 call plans and launches with: the code planes stand where the 16-bit rows were (bank->k / bank->v are not read)
-static bool kv8_bank(const ekv_bank* bank, const ekv_kv8* q8, ekv_bank* out) {
-  if (!bank || !q8 || !q8->k_codes || !q8->v_codes || !q8->k_scale || !q8->v_scale) return false;
-  *out = *bank;
-  out->k = q8->k_codes;
-  out->v = q8->v_codes;
-  return true;
+static int call_check(const EkvCall& c) {
+  EkvResolved r;
+  return resolve_call(c, &r);
 }
 
-// Body of ekv_step_attend: the plan, the pointers, then its launch sequence.  q8 != NULL: a step on FP8 rows (bank = kv8_bank()).
-static int step_attend_impl(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const void* q, const void* k_new,
-                            const void* v_new, void* out, int32_t* evict_ids, const float* rope_cos, const float* rope_sin,
-                            void* workspace, size_t workspace_bytes, void* stream, const ekv_kv8* q8 = nullptr,
-                            const EkvSeqTable* tb = nullptr, const EkvStepPlan* batch_plan = nullptr) {
-  // (tb != NULL: a batched decode step that ekv_plan_batch has accepted; st = its envelope, batch_plan = the plan made there)
-  EkvStepPlan P;
-  if (batch_plan) P = *batch_plan;
-  else if (int e = q8 ? ekv_plan_step_kv8(bank, st, dtype, &P) : ekv_plan_step(bank, st, dtype, &P)) return e;
+static size_t call_workspace_bytes(const EkvCall& c) {
+  EkvResolved r;
+  (void)resolve_call(c, &r);
+  return r.plan.bytes;      // (a batch: the table travels in the kernel arguments, nothing is staged)
+}
+
+// ekv_step_info and its kin: the plan's answers also for a step the call would refuse (launch counts 0 then); argument errors first
+static int call_info(const EkvCall& c, int32_t* info, int32_t n_info) {
+  EkvResolved r;
+  const bool ok = resolve_call(c, &r) == EKV_OK;
+  if (c.dtype != EKV_DTYPE_F16 && c.dtype != EKV_DTYPE_BF16) return EKV_E_ARG;
+  if (c.kv8 && !r.bank) return EKV_E_ARG;
+  if (int e = check_bank(r.bank)) return e;
+  if (!c.step || (c.batch && !c.seqs) || !info || n_info < 1) return EKV_E_ARG;
+  const EkvStepPlan& P = r.plan;
+  const int32_t v[EKV_STEP_INFO_N] = {P.n_split, ok ? P.one_launch : 0, P.two_pass, P.wide, P.n_qblocks, P.qb_rows, P.n_col_parts,
+                                      P.fold_in_kernel, ok ? P.n_launches : 0, ok ? (P.fused_order & 3) : 0};
+  for (int i = 0; i < n_info && i < EKV_STEP_INFO_N; ++i) info[i] = v[i];
+  for (int i = EKV_STEP_INFO_N; i < n_info; ++i) info[i] = 0;
+  return EKV_OK;
+}
+
+// Body of ekv_step_attend and its kin: the resolved call, the pointers, then the plan's launch sequence.
+static int call_attend(const EkvCall& c, const void* q, const void* k_new, const void* v_new, void* out, int32_t* evict_ids,
+                       const float* rope_cos, const float* rope_sin, void* workspace, size_t workspace_bytes, void* stream) {
+  EkvResolved r;
+  if (int e = resolve_call(c, &r)) return e;
+  const ekv_bank* bank = r.bank;
+  const ekv_step* st = r.step;
+  const EkvSeqTable* tb = r.tb;
+  const EkvStepPlan& P = r.plan;
   if (!q || !k_new || !v_new || !out || !workspace || (st->rope_on_read && (!rope_cos || !rope_sin))) return EKV_E_ARG;
   if (P.bytes > workspace_bytes) return EKV_E_WORKSPACE;
   hipStream_t s = static_cast<hipStream_t>(stream);
@@ -881,7 +898,7 @@ static int step_attend_impl(const ekv_bank* bank, const ekv_step* st, int32_t dt
   sa.colsum = aa.colsum;
   sa.row_stats = aa.row_stats;
   // FP8 rows: the scale planes (they share the storage of stats / colsum, which a decode step — all a kv8 plan can be — never has)
-  if (q8) aa.k_scale = q8->k_scale, aa.v_scale = q8->v_scale;
+  if (c.kv8) aa.k_scale = c.q8->k_scale, aa.v_scale = c.q8->v_scale;
   sa.out = static_cast<__half*>(out);
   sa.evict_ids = evict_ids;
   sa.big_rows = f32(P.big_rows);
@@ -902,12 +919,12 @@ static int step_attend_impl(const ekv_bank* bank, const ekv_step* st, int32_t dt
     if (kv8 && (L.kind == EKV_RUN_CHUNK_LDS || L.kind == EKV_RUN_RESIDENT || L.kind == EKV_RUN_CHUNK || L.kind == EKV_RUN_FLUSH)) return EKV_E_UNSUPPORTED;
     switch (L.kind) {
       case EKV_RUN_FUSED_DECODE:
-        aa.fused_order = (tb || kv8) ? 0 : P.fused_order;      // (shares its storage with score_tail, which only chunk launches set)
-        e = tb ? ekv_launch_decode_fused_batch(aa, sa, *tb, D, lc, P.fused_nw, s, bf16) : ekv_launch_decode_fused(aa, sa, D, lc, P.fused_nw, s, bf16, kv8);
+        aa.fused_order = P.fused_order;      // (shares its storage with score_tail, which only chunk launches set)
+        e = ekv_launch_decode_fused(aa, sa, tb, D, lc, P.fused_nw, s, bf16, kv8);
         break;
       case EKV_RUN_CHUNK_LDS: e = ekv_launch_chunk_lds(aa, sa, D, lc, s, bf16); break;
       case EKV_RUN_RESIDENT: e = ekv_launch_attn_resident(aa, sa, lc, s, bf16); break;
-      case EKV_RUN_DECODE: e = tb ? ekv_launch_attn_decode_batch(aa, *tb, D, lc, s, bf16) : ekv_launch_attn_decode(aa, D, lc, s, bf16, kv8); break;
+      case EKV_RUN_DECODE: e = ekv_launch_attn_decode(aa, tb, D, lc, s, bf16, kv8); break;
       case EKV_RUN_CHUNK:
         e = ekv_launch_attn_chunk(aa, D, lc, P.wide, P.two_pass, s, L.fuse ? &sa : nullptr, L.passes, L.tail ? &sa : nullptr, bf16);
         break;
@@ -935,7 +952,7 @@ static int step_attend_impl(const ekv_bank* bank, const ekv_step* st, int32_t dt
                              evict_ids, bank->n_kv_heads, bank->cap, st->layer_begin, st->n_slots, st->range_start, st->n_evict);
         e = hipGetLastError();
         break;
-      case EKV_RUN_DECODE_SCORE: e = tb ? ekv_launch_decode_score_batch(sa, *tb, lc, s, bf16) : ekv_launch_decode_score(sa, lc, s, bf16); break;
+      case EKV_RUN_DECODE_SCORE: e = ekv_launch_decode_score(sa, tb, lc, s, bf16); break;
       case EKV_RUN_TOVA_MEAN: e = ekv_launch_tova_headmean(sa, lc, s); break;
       case EKV_RUN_SCORE_SELECT: e = ekv_launch_score_select(sa, lc, s, bf16); break;
     }
@@ -946,107 +963,72 @@ static int step_attend_impl(const ekv_bank* bank, const ekv_step* st, int32_t dt
 
 extern "C" {
 
+// ---- the entry points of the step family: one or two lines over the four internals above
+size_t ekv_workspace_bytes_typed(const ekv_bank* bank, const ekv_step* step, int32_t dtype) { return call_workspace_bytes(step_call(bank, step, dtype)); }
+size_t ekv_workspace_bytes(const ekv_bank* bank, const ekv_step* step) { return call_workspace_bytes(step_call(bank, step, EKV_DTYPE_F16)); }
+
+int ekv_step_plan(const ekv_bank* bank, const ekv_step* st, int32_t* n_split, int32_t* fused) {
+  if (int e = check_bank(bank)) return e;
+  if (!st || !n_split || !fused) return EKV_E_ARG;
+  EkvResolved r;
+  const int rc = resolve_call(step_call(bank, st, EKV_DTYPE_F16), &r);
+  *n_split = r.plan.n_split;
+  // one launch for the whole step: the fused decode kernel, the logits-in-LDS or logits-resident chunk kernel, or a chunk step whose
+  // scorer runs as the tail of the attention kernel; a step the call would refuse plans as 0
+  *fused = rc == EKV_OK ? r.plan.one_launch : 0;
+  return EKV_OK;
+}
+
+int ekv_step_info_typed(const ekv_bank* bank, const ekv_step* st, int32_t dtype, int32_t* info, int32_t n_info) {
+  return call_info(step_call(bank, st, dtype), info, n_info);
+}
+int ekv_step_info(const ekv_bank* bank, const ekv_step* st, int32_t* info, int32_t n_info) {
+  return call_info(step_call(bank, st, EKV_DTYPE_F16), info, n_info);
+}
+
+int ekv_step_check_typed(const ekv_bank* bank, const ekv_step* st, int32_t dtype) { return call_check(step_call(bank, st, dtype)); }
+int ekv_step_check(const ekv_bank* bank, const ekv_step* st) { return call_check(step_call(bank, st, EKV_DTYPE_F16)); }
+
 int ekv_step_attend(const ekv_bank* bank, const ekv_step* st, const void* q, const void* k_new, const void* v_new,
                     void* out, int32_t* evict_ids, const float* rope_cos, const float* rope_sin, void* workspace,
                     size_t workspace_bytes, void* stream) {
-  return step_attend_impl(bank, st, EKV_DTYPE_F16, q, k_new, v_new, out, evict_ids, rope_cos, rope_sin, workspace, workspace_bytes,
-                          stream);
+  return call_attend(step_call(bank, st, EKV_DTYPE_F16), q, k_new, v_new, out, evict_ids, rope_cos, rope_sin, workspace, workspace_bytes, stream);
 }
-
 int ekv_step_attend_typed(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const void* q, const void* k_new,
                           const void* v_new, void* out, int32_t* evict_ids, const float* rope_cos, const float* rope_sin,
                           void* workspace, size_t workspace_bytes, void* stream) {
-  return step_attend_impl(bank, st, dtype, q, k_new, v_new, out, evict_ids, rope_cos, rope_sin, workspace, workspace_bytes, stream);
+  return call_attend(step_call(bank, st, dtype), q, k_new, v_new, out, evict_ids, rope_cos, rope_sin, workspace, workspace_bytes, stream);
 }
 
-int ekv_step_check_typed(const ekv_bank* bank, const ekv_step* st, int32_t dtype) {
-  EkvStepPlan P;
-  return ekv_plan_step(bank, st, dtype, &P);
-}
-
-int ekv_step_check(const ekv_bank* bank, const ekv_step* st) { return ekv_step_check_typed(bank, st, EKV_DTYPE_F16); }
-
-// ---- FP8 K/V storage (include/easykv_hip.h, "kv8")
-int ekv_kv8_step_check(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_kv8* q8) {
-  if (dtype != EKV_DTYPE_F16 && dtype != EKV_DTYPE_BF16) return EKV_E_ARG;
-  ekv_bank b;
-  if (!kv8_bank(bank, q8, &b)) return EKV_E_ARG;
-  EkvStepPlan P;
-  return ekv_plan_step_kv8(&b, st, dtype, &P);
-}
-
+// FP8 K/V storage (include/easykv_hip.h, "kv8")
+int ekv_kv8_step_check(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_kv8* q8) { return call_check(kv8_call(bank, st, dtype, q8)); }
 int ekv_kv8_step_info(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_kv8* q8, int32_t* info, int32_t n_info) {
-  if (dtype != EKV_DTYPE_F16 && dtype != EKV_DTYPE_BF16) return EKV_E_ARG;
-  ekv_bank b;
-  if (!kv8_bank(bank, q8, &b)) return EKV_E_ARG;
-  if (int e = check_bank(&b)) return e;
-  if (!st || !info || n_info < 1) return EKV_E_ARG;
-  EkvStepPlan P;
-  const bool ok = ekv_plan_step_kv8(&b, st, dtype, &P) == EKV_OK;
-  const int32_t v[EKV_STEP_INFO_N] = {P.n_split, ok ? P.one_launch : 0, P.two_pass, P.wide, P.n_qblocks, P.qb_rows, P.n_col_parts,
-                                      P.fold_in_kernel, ok ? P.n_launches : 0, ok ? (P.fused_order & 3) : 0};
-  for (int i = 0; i < n_info && i < EKV_STEP_INFO_N; ++i) info[i] = v[i];
-  for (int i = EKV_STEP_INFO_N; i < n_info; ++i) info[i] = 0;
-  return EKV_OK;
+  return call_info(kv8_call(bank, st, dtype, q8), info, n_info);
 }
-
 size_t ekv_kv8_workspace_bytes(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_kv8* q8) {
-  ekv_bank b;
-  if (!kv8_bank(bank, q8, &b)) return 0;
-  EkvStepPlan P;
-  (void)ekv_plan_step_kv8(&b, st, dtype, &P);
-  return P.bytes;
+  return call_workspace_bytes(kv8_call(bank, st, dtype, q8));
 }
-
 int ekv_kv8_step_attend(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_kv8* q8, const void* q, const void* k_new,
                         const void* v_new, void* out, int32_t* evict_ids, const float* rope_cos, const float* rope_sin,
                         void* workspace, size_t workspace_bytes, void* stream) {
-  if (dtype != EKV_DTYPE_F16 && dtype != EKV_DTYPE_BF16) return EKV_E_ARG;
-  ekv_bank b;
-  if (!kv8_bank(bank, q8, &b)) return EKV_E_ARG;
-  return step_attend_impl(&b, st, dtype, q, k_new, v_new, out, evict_ids, rope_cos, rope_sin, workspace, workspace_bytes, stream, q8);
+  return call_attend(kv8_call(bank, st, dtype, q8), q, k_new, v_new, out, evict_ids, rope_cos, rope_sin, workspace, workspace_bytes, stream);
 }
 
-// ---- batched decode steps (include/easykv_hip.h, ekv_seq)
+// batched decode steps (include/easykv_hip.h, ekv_seq)
 int ekv_batch_step_check(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_seq* seqs, int32_t n_seq) {
-  EkvStepPlan P;
-  ekv_step env;
-  EkvSeqTable tb;
-  return ekv_plan_batch(bank, st, dtype, seqs, n_seq, &P, &env, &tb);
+  return call_check(batch_call(bank, st, dtype, seqs, n_seq));
 }
-
 int ekv_batch_step_info(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_seq* seqs, int32_t n_seq, int32_t* info,
                         int32_t n_info) {
-  if (dtype != EKV_DTYPE_F16 && dtype != EKV_DTYPE_BF16) return EKV_E_ARG;
-  if (int e = check_bank(bank)) return e;
-  if (!st || !seqs || !info || n_info < 1) return EKV_E_ARG;
-  EkvStepPlan P;
-  ekv_step env;
-  EkvSeqTable tb;
-  const bool ok = ekv_plan_batch(bank, st, dtype, seqs, n_seq, &P, &env, &tb) == EKV_OK;
-  const int32_t v[EKV_STEP_INFO_N] = {P.n_split, ok ? P.one_launch : 0, P.two_pass, P.wide, P.n_qblocks, P.qb_rows, P.n_col_parts,
-                                      P.fold_in_kernel, ok ? P.n_launches : 0, ok ? (P.fused_order & 3) : 0};
-  for (int i = 0; i < n_info && i < EKV_STEP_INFO_N; ++i) info[i] = v[i];
-  for (int i = EKV_STEP_INFO_N; i < n_info; ++i) info[i] = 0;
-  return EKV_OK;
+  return call_info(batch_call(bank, st, dtype, seqs, n_seq), info, n_info);
 }
-
 size_t ekv_batch_workspace_bytes(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_seq* seqs, int32_t n_seq) {
-  EkvStepPlan P;
-  ekv_step env;
-  EkvSeqTable tb;
-  (void)ekv_plan_batch(bank, st, dtype, seqs, n_seq, &P, &env, &tb);
-  return P.bytes;      // (the table travels in the kernel arguments: nothing is staged)
+  return call_workspace_bytes(batch_call(bank, st, dtype, seqs, n_seq));
 }
-
 int ekv_batch_step_attend(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_seq* seqs, int32_t n_seq, const void* q,
                           const void* k_new, const void* v_new, void* out, int32_t* evict_ids, void* workspace, size_t workspace_bytes,
                           void* stream) {
-  EkvStepPlan P;
-  ekv_step env;
-  EkvSeqTable tb;
-  if (int e = ekv_plan_batch(bank, st, dtype, seqs, n_seq, &P, &env, &tb)) return e;
-  return step_attend_impl(bank, &env, dtype, q, k_new, v_new, out, evict_ids, nullptr, nullptr, workspace, workspace_bytes, stream, nullptr, &tb, &P);
+  return call_attend(batch_call(bank, st, dtype, seqs, n_seq), q, k_new, v_new, out, evict_ids, nullptr, nullptr, workspace, workspace_bytes, stream);
 }
 
 static int kv8_convert_check(const ekv_bank* bank, const ekv_kv8* q8, int32_t layer_begin, int32_t layer_count, int32_t extent) {

@@ -4,25 +4,52 @@
 #include "ekv_common.h"
 #include "ekv_kernels.h"
 
-#define EKV_DECL(d, m) hipError_t ekv_launch_attn_chunk_d##d##_m##m(const EkvAttnArgs&, int, int, hipStream_t, const EkvScoreArgs*);
-EKV_DECL(32, 0) EKV_DECL(32, 1) EKV_DECL(32, 2) EKV_DECL(64, 0) EKV_DECL(64, 1) EKV_DECL(64, 2)
-EKV_DECL(96, 0) EKV_DECL(96, 1) EKV_DECL(96, 2) EKV_DECL(128, 0) EKV_DECL(128, 1) EKV_DECL(128, 2)
-#undef EKV_DECL
+// ---- the instances (ekv_instances.def): launcher declarations, then one table entry per line
+typedef hipError_t EkvChunkFn(const EkvAttnArgs&, int shape, int layer_count, hipStream_t, const EkvScoreArgs*);
+typedef hipError_t EkvStepFn(const EkvAttnArgs&, const EkvScoreArgs&, int layer_count, hipStream_t);
+typedef size_t EkvLdsBytesFn(int, int, int);
+#define EKV_CHUNK(d, m, elem) EkvChunkFn EKV_FN_CHUNK(d, m, elem);
+#define EKV_WIDE(d, m, keys, elem) EkvChunkFn EKV_FN_WIDE(d, m, keys, elem);
+#define EKV_CHUNK_LDS(d, elem) EkvStepFn EKV_FN_D_ELEM(ekv_launch_chunk_lds, d, elem); EkvLdsBytesFn ekv_chunk_lds_bytes_d##d;
+#define EKV_RESIDENT(d, elem) EkvStepFn EKV_FN_D_ELEM(ekv_launch_attn_resident, d, elem);
+#include "ekv_instances.def"
 
-#define EKW_DECL(d, m) hipError_t ekv_launch_attn_wide_d##d##_m##m(const EkvAttnArgs&, int, int, hipStream_t, const EkvScoreArgs*);
-EKW_DECL(64, 0) EKW_DECL(64, 2) EKW_DECL(128, 0) EKW_DECL(128, 2)
-#undef EKW_DECL
-#define EKW_DECL(d, m) hipError_t ekv_launch_attn_wide_rope_d##d##_m##m(const EkvAttnArgs&, int, int, hipStream_t, const EkvScoreArgs*);
-EKW_DECL(64, 0) EKW_DECL(64, 2) EKW_DECL(128, 0) EKW_DECL(128, 2)
-#undef EKW_DECL
-// bf16 instances (plain keys only)
-#define EKV_DECL(d, m) hipError_t ekv_launch_attn_chunk_d##d##_m##m##_bf16(const EkvAttnArgs&, int, int, hipStream_t, const EkvScoreArgs*);
-EKV_DECL(32, 0) EKV_DECL(32, 1) EKV_DECL(32, 2) EKV_DECL(64, 0) EKV_DECL(64, 1) EKV_DECL(64, 2)
-EKV_DECL(96, 0) EKV_DECL(96, 1) EKV_DECL(96, 2) EKV_DECL(128, 0) EKV_DECL(128, 1) EKV_DECL(128, 2)
-#undef EKV_DECL
-#define EKW_DECL(d, m) hipError_t ekv_launch_attn_wide_d##d##_m##m##_bf16(const EkvAttnArgs&, int, int, hipStream_t, const EkvScoreArgs*);
-EKW_DECL(64, 0) EKW_DECL(64, 2) EKW_DECL(128, 0) EKW_DECL(128, 2)
-#undef EKW_DECL
+namespace {
+struct ChunkInstance {      // 16x16 kernel (rope: the fp16 builds rotate on read themselves) and wide-block kernel
+  bool wide;
+  int head_dim, mode;
+  bool rope, bf16;
+  EkvChunkFn* fn;
+};
+const ChunkInstance kChunk[] = {
+#define EKV_CHUNK(d, m, elem) {false, d, m, false, EKV_IS_##elem, EKV_FN_CHUNK(d, m, elem)},
+#define EKV_WIDE(d, m, keys, elem) {true, d, m, EKV_IS_##keys, EKV_IS_##elem, EKV_FN_WIDE(d, m, keys, elem)},
+#include "ekv_instances.def"
+};
+struct StepInstance {      // whole-step kernels: logits in LDS (with its LDS plan), logits-resident
+  bool resident;
+  int head_dim;
+  bool bf16;
+  EkvStepFn* fn;
+  EkvLdsBytesFn* lds_bytes;
+};
+const StepInstance kStep[] = {
+#define EKV_CHUNK_LDS(d, elem) {false, d, EKV_IS_##elem, EKV_FN_D_ELEM(ekv_launch_chunk_lds, d, elem), ekv_chunk_lds_bytes_d##d},
+#define EKV_RESIDENT(d, elem) {true, d, EKV_IS_##elem, EKV_FN_D_ELEM(ekv_launch_attn_resident, d, elem), nullptr},
+#include "ekv_instances.def"
+};
+
+EkvChunkFn* chunk_instance(bool wide, int head_dim, int mode, bool rope, bool bf16) {
+  for (const ChunkInstance& in : kChunk)
+    if (in.wide == wide && in.head_dim == head_dim && in.mode == mode && in.rope == rope && in.bf16 == bf16) return in.fn;
+  return nullptr;
+}
+const StepInstance* step_instance(bool resident, int head_dim, bool bf16) {
+  for (const StepInstance& in : kStep)
+    if (in.resident == resident && in.head_dim == head_dim && in.bf16 == bf16) return &in;
+  return nullptr;
+}
+}  // namespace
 
 // Two-pass scheme (16x16 kernel: statistics pass + exact pass with in-kernel column sums, ekv_attn_chunk.inc; wide-block kernel: one
 // pass for output + row statistics, then a K-only column-sum pass, ekv_attn_wide.inc) for scored chunk
@@ -144,8 +171,9 @@ hipError_t ekv_launch_attn_chunk(const EkvAttnArgs& a, int head_dim, int layer_c
     const int nwq = qpw == 4 ? 4 : 2;
     // one pass over K and V (output, and for a scored step every row's softmax statistics), then — scored steps — the column-sum
     // pass over K
-#define EKW_GO(d, m, aa, shape, t) (bf16 ? ekv_launch_attn_wide_d##d##_m##m##_bf16(aa, shape, layer_count, s, t) :                  \
-                                   rope ? ekv_launch_attn_wide_rope_d##d##_m##m(aa, shape, layer_count, s, t) : ekv_launch_attn_wide_d##d##_m##m(aa, shape, layer_count, s, t))
+    EkvChunkFn* const one = chunk_instance(true, head_dim, 0, rope, bf16);
+    EkvChunkFn* const sums = chunk_instance(true, head_dim, 2, rope, bf16);
+    if (one == nullptr || sums == nullptr) return hipErrorInvalidValue;
     hipError_t e = hipSuccess;
     if (passes & 1) {
       // a launch of at most one workgroup per CU (a layer-per-call model) runs 65..128-row blocks on 128-key tiles, 8 waves
@@ -154,41 +182,26 @@ hipError_t ekv_launch_attn_chunk(const EkvAttnArgs& a, int head_dim, int layer_c
       //  per split 43.2 / 38.2 us; 64 rows x 272 keys 24.5 / 26.1; 32 layers x 8 KV heads x 1248 keys unsplit (configs[2]) 43.1 / 41.5)
       const bool small = (size_t)layer_count * a.n_kv_heads * a.n_split * a.n_qblocks <= 256 && a.rows_per_split >= 512;
       const int shape0 = (!rope && small && !no_big) ? (nwq == 4 ? 8 : 9) : nwq;      // workgroup-shape code of ekv_attn_wide.inc's entry (8 / 9: 128-key tiles)
-      e = head_dim == 128 ? EKW_GO(128, 0, a, shape0, nullptr) : EKW_GO(64, 0, a, shape0, nullptr);
+      e = one(a, shape0, layer_count, s, nullptr);
     }
     if (two_pass && (passes & 2) && e == hipSuccess) {
       EkvAttnArgs a2 = a;
       a2.score_tail = tail_sc != nullptr ? 1 : 0;
-      e = head_dim == 128 ? EKW_GO(128, 2, a2, nwq, tail_sc) : EKW_GO(64, 2, a2, nwq, tail_sc);
+      e = sums(a2, nwq, layer_count, s, tail_sc);
     }
-#undef EKW_GO
     return e;
   }
-#define EKV_GO(d, m) (bf16 ? ekv_launch_attn_chunk_d##d##_m##m##_bf16(a, kernel_code(qpw, rope, m), layer_count, s, fuse_sc)  \
-                          : ekv_launch_attn_chunk_d##d##_m##m(a, kernel_code(qpw, rope, m), layer_count, s, fuse_sc))
-  hipError_t e = hipSuccess;
-  switch (head_dim) {
-    case 32: e = two_pass ? EKV_GO(32, 1) : EKV_GO(32, 0); if (two_pass && e == hipSuccess) e = EKV_GO(32, 2); break;
-    case 64: e = two_pass ? EKV_GO(64, 1) : EKV_GO(64, 0); if (two_pass && e == hipSuccess) e = EKV_GO(64, 2); break;
-    case 96: e = two_pass ? EKV_GO(96, 1) : EKV_GO(96, 0); if (two_pass && e == hipSuccess) e = EKV_GO(96, 2); break;
-    case 128: e = two_pass ? EKV_GO(128, 1) : EKV_GO(128, 0); if (two_pass && e == hipSuccess) e = EKV_GO(128, 2); break;
-    default: e = hipErrorInvalidValue;
-  }
-#undef EKV_GO
+  // (the fp16 instances of the 16x16 kernel hold the RoPE-on-read builds: one line per (head_dim, mode, element))
+  auto go = [&](int m) {
+    EkvChunkFn* const fn = chunk_instance(false, head_dim, m, false, bf16);
+    return fn ? fn(a, kernel_code(qpw, rope, m), layer_count, s, fuse_sc) : hipErrorInvalidValue;
+  };
+  hipError_t e = go(two_pass ? 1 : 0);
+  if (two_pass && e == hipSuccess) e = go(2);
   return e;
 }
 
 // ---- small-row chunk step with the logits in LDS (ekv_chunk_lds.inc) -------------------------------------------------------
-size_t ekv_chunk_lds_bytes_d32(int, int, int);
-size_t ekv_chunk_lds_bytes_d64(int, int, int);
-size_t ekv_chunk_lds_bytes_d128(int, int, int);
-hipError_t ekv_launch_chunk_lds_d32(const EkvAttnArgs&, const EkvScoreArgs&, int, hipStream_t);
-hipError_t ekv_launch_chunk_lds_d64(const EkvAttnArgs&, const EkvScoreArgs&, int, hipStream_t);
-hipError_t ekv_launch_chunk_lds_d128(const EkvAttnArgs&, const EkvScoreArgs&, int, hipStream_t);
-hipError_t ekv_launch_chunk_lds_d32_bf16(const EkvAttnArgs&, const EkvScoreArgs&, int, hipStream_t);
-hipError_t ekv_launch_chunk_lds_d64_bf16(const EkvAttnArgs&, const EkvScoreArgs&, int, hipStream_t);
-hipError_t ekv_launch_chunk_lds_d128_bf16(const EkvAttnArgs&, const EkvScoreArgs&, int, hipStream_t);
-
 // Eligible: a scored, accumulating chunk step (plain keys, score rows over the whole cache) with at most 8 GQA-folded query
 // rows whose logits fit LDS next to a second workgroup of the CU (<= 80 KB), one victim set per head.
 bool ekv_chunk_lds_supported(const ekv_bank* bank, const ekv_step* st, int phys_extent, bool scored) {
@@ -197,20 +210,17 @@ bool ekv_chunk_lds_supported(const ekv_bank* bank, const ekv_step* st, int phys_
   if (st->phases != 0 || st->n_split == -1 || st->two_pass != 0 || !st->causal) return false;   // (two_pass = -1: "exported logits")
   if (st->policy == EKV_POLICY_TOVA && st->tova_head_mean) return false;   // needs every head of the layer first
   if (st->n_slots > 10 * 256 || st->n_evict >= st->n_slots || st->n_evict > 16) return false;
-  size_t lds = 1u << 30;
-  switch (bank->head_dim) {
-    case 32: lds = ekv_chunk_lds_bytes_d32(rep * st->q_len, phys_extent, st->n_slots); break;
-    case 64: lds = ekv_chunk_lds_bytes_d64(rep * st->q_len, phys_extent, st->n_slots); break;
-    case 128: lds = ekv_chunk_lds_bytes_d128(rep * st->q_len, phys_extent, st->n_slots); break;
-  }
-  return lds <= 80 * 1024;
+  const StepInstance* in = step_instance(false, bank->head_dim, false);
+  return in != nullptr && in->lds_bytes(rep * st->q_len, phys_extent, st->n_slots) <= 80 * 1024;
 }
 
 hipError_t ekv_launch_chunk_lds(const EkvAttnArgs& a, const EkvScoreArgs& sc, int head_dim, int layer_count, hipStream_t s, bool bf16) {
-  switch (head_dim) {
-    case 32: return (bf16 ? ekv_launch_chunk_lds_d32_bf16 : ekv_launch_chunk_lds_d32)(a, sc, layer_count, s);
-    case 64: return (bf16 ? ekv_launch_chunk_lds_d64_bf16 : ekv_launch_chunk_lds_d64)(a, sc, layer_count, s);
-    case 128: return (bf16 ? ekv_launch_chunk_lds_d128_bf16 : ekv_launch_chunk_lds_d128)(a, sc, layer_count, s);
-  }
-  return hipErrorInvalidValue;
+  const StepInstance* in = step_instance(false, head_dim, bf16);
+  return in ? in->fn(a, sc, layer_count, s) : hipErrorInvalidValue;
+}
+
+// ---- logits-resident scored chunk step (ekv_attn_resident.inc; ekv_attn_resident_supported lives next to the kernel's geometry)
+hipError_t ekv_launch_attn_resident(const EkvAttnArgs& a, const EkvScoreArgs& sc, int layer_count, hipStream_t s, bool bf16) {
+  const StepInstance* in = step_instance(true, sc.head_dim, bf16);
+  return in ? in->fn(a, sc, layer_count, s) : hipErrorInvalidValue;
 }

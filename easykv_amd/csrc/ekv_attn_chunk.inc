@@ -716,13 +716,8 @@ hipError_t launch_k(const EkvAttnArgs& a, int layer_count, hipStream_t s, const 
 
 }  // namespace
 
-#define EKV_CAT_(a, b) a##b
-#define EKV_CAT(a, b) EKV_CAT_(a, b)
-
 // rows per query block = rep * qb_rows <= 32 * qpw
-#define EKV_CAT3(a, b, c, d, t) a##b##c##d##t
-#define EKV_CAT4(a, b, c, d, t) EKV_CAT3(a, b, c, d, t)
-hipError_t EKV_CAT4(ekv_launch_attn_chunk_d, EKV_D, _m, EKV_CHUNK_MODE, EKV_DT_TAG)(const EkvAttnArgs& a, int qpw, int layer_count, hipStream_t s,
+hipError_t EKV_FN_CHUNK(EKV_D, EKV_CHUNK_MODE, EKV_ELEM)(const EkvAttnArgs& a, int qpw, int layer_count, hipStream_t s,
                                                                                     const EkvScoreArgs* fuse_sc) {
   const bool rope = a.rope_cos != nullptr;
   constexpr bool R = !EKV_BF16;   // (RoPE-on-read builds: fp16 only)

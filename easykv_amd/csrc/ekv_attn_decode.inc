@@ -15,15 +15,15 @@
 #ifdef EKV_TAIL_PROFILE
 #define EKV_STAMP(i) do { if (threadIdx.x == 0) stamps[i] = __builtin_readcyclecounter(); } while (0)
 #endif
-// Compiled once per (EKV_D, EKV_ROPE) by the ekv_attn_decode_d*.hip stubs so the objects build in parallel.
+// Compiled once per EKV_DECODE line of ekv_instances.def (EKV_D, EKV_ROPE, EKV_BF16, EKV_KV8, EKV_BATCH) so the objects build in parallel.
 #include "ekv_decode_stream.h"
 #include "ekv_decode_tail.h"
-// EKV_KV8 = 1 (the *_kv8.hip instances): the bank's rows are FP8 codes + fp32 row scales (ekv_decode_stream.h, "FP8 rows"); q, k_new,
+// EKV_KV8 = 1 (the kv8 instances): the bank's rows are FP8 codes + fp32 row scales (ekv_decode_stream.h, "FP8 rows"); q, k_new,
 // v_new and out keep the 16-bit type of the build.  Only the stream and the per-lane width of the output accumulators differ.
 #ifndef EKV_KV8
 #define EKV_KV8 0
 #endif
-// EKV_BATCH = 1 (the *_batch.hip instances): batched decode steps (include/easykv_hip.h, ekv_seq).  The kernels take the table of the
+// EKV_BATCH = 1 (the batch instances): batched decode steps (include/easykv_hip.h, ekv_seq).  The kernels take the table of the
 // batch behind their argument structs; workgroup (head, entry) copies the structs and overwrites the per-step fields with its entry's
 // (scalar loads from the kernel arguments), and from there on IS the uniform kernel: pitches (t_pad, l_pad, n_split, rows_per_split,
 // LDS sizes, ITEMS) stay the envelope's, bounds (T, extent, score_off, windows) become the entry's, the bank is addressed by the
@@ -31,34 +31,11 @@
 #ifndef EKV_BATCH
 #define EKV_BATCH 0
 #endif
-#if EKV_BATCH
-#if EKV_KV8
+#if EKV_BATCH && EKV_KV8
 #error "batch instances: 16-bit rows, plain keys"
 #endif
-#define EKV_KV_TAG _batch
-#if EKV_BF16
-#define ekv_attn_decode_kernel ekv_attn_decode_kernel_batch_bf16
-#define ekv_decode_fused_kernel ekv_decode_fused_kernel_batch_bf16
-#else
-#define ekv_attn_decode_kernel ekv_attn_decode_kernel_batch
-#define ekv_decode_fused_kernel ekv_decode_fused_kernel_batch
-#endif
-#elif EKV_KV8
-#define EKV_KV_TAG _kv8
-#if EKV_BF16
-#define ekv_attn_decode_kernel ekv_attn_decode_kernel_kv8_bf16
-#define ekv_decode_fused_kernel ekv_decode_fused_kernel_kv8_bf16
-#else
-#define ekv_attn_decode_kernel ekv_attn_decode_kernel_kv8
-#define ekv_decode_fused_kernel ekv_decode_fused_kernel_kv8
-#endif
-#elif EKV_BF16   // (bf16 instances: the same kernels under tagged names)
-#define EKV_KV_TAG
-#define ekv_attn_decode_kernel ekv_attn_decode_kernel_bf16
-#define ekv_decode_fused_kernel ekv_decode_fused_kernel_bf16
-#else
-#define EKV_KV_TAG
-#endif
+#define ekv_attn_decode_kernel EKV_KERNEL_NAME(ekv_attn_decode_kernel)
+#define ekv_decode_fused_kernel EKV_KERNEL_NAME(ekv_decode_fused_kernel)
 // FP8 rows: 4 rows in flight per lane group.  A lane's output slice is 16 floats per query head instead of 8, the query fragment
 // doubles and a row's widened codes are live next to its bytes: with 8 rows the one-launch build of GQA factor 1 needs 149..214 spilled
 // registers under its four-workgroups-per-CU bound, with 4 rows 102..111 VGPRs and none (tools/kernel_regs.py).
@@ -479,12 +456,7 @@ hipError_t launch(const EkvAttnArgs& a EKV_TB_DECL, int layer_count, hipStream_t
 }
 
 template <int REP, int NW = 8>
-size_t fused_lds(int t_pad, int l_pad, int n_state) {
-  using Gm = EkvDecodeGeom<EKV_D, NW>;
-  const size_t part = ekv_align((size_t)Gm::NP * REP * Gm::PS, 4);
-  return ((size_t)REP * l_pad + part + (size_t)n_state * ekv_align((size_t)t_pad, 256)) * 4 + 2 * NW * 8 * 8 +
-         ekv_align(ekv_align((size_t)l_pad, 128) / 8, 16) + 264 * 4;   // + one dead-row bit per physical row + select histogram
-}
+size_t fused_lds(int t_pad, int l_pad, int n_state) { return ekv_fused_lds<EKV_D, REP, NW>(t_pad, l_pad, n_state); }
 
 template <int REP, int ITEMS, int NW, bool SLOT>
 hipError_t launch_fused_k(const EkvAttnArgs& a, const EkvScoreArgs& sc EKV_TB_DECL, int layer_count, hipStream_t s) {
@@ -525,38 +497,31 @@ hipError_t launch_fused(const EkvAttnArgs& a, const EkvScoreArgs& sc EKV_TB_DECL
 
 }  // namespace
 
-#define EKV_CAT_(a, b, c, t, k) a##b##_##c##t##k
-#define EKV_CAT(a, b, c, t, k) EKV_CAT_(a, b, c, t, k)
-#define EKV_SYM(name) EKV_CAT(name, EKV_D, EKV_ROPE_TAG, EKV_DT_TAG, EKV_KV_TAG)
+#if EKV_ROPE
+#define EKV_KEYS rope
+#else
+#define EKV_KEYS plain
+#endif
+#define EKV_SYM(fn) EKV_FN_DECODE(fn, EKV_D, EKV_KEYS, EKV_ELEM, EKV_ROWS, EKV_BATCHING)
 
-hipError_t EKV_SYM(ekv_launch_attn_decode_d)(const EkvAttnArgs& a EKV_TB_DECL, int rep, int layer_count, hipStream_t s) {
+// tb: the table of a batched step for the batch instances, unused (NULL) otherwise
+hipError_t EKV_SYM(ekv_launch_attn_decode)(const EkvAttnArgs& a, const EkvSeqTable* tb, int rep, int layer_count, hipStream_t s) {
   if (rep < 1) return hipErrorInvalidValue;
   switch (rep) {
-    case 1: return launch<1>(a EKV_TB_PASS, layer_count, s);
-    case 2: return launch<2>(a EKV_TB_PASS, layer_count, s);
-    case 3: case 4: return launch<4>(a EKV_TB_PASS, layer_count, s);
-    default: return launch<8>(a EKV_TB_PASS, layer_count, s);      // 5..8: one group of 8; wider factors: ceil(rep / 8) groups per KV head
+    case 1: return launch<1>(a EKV_TB_DEREF, layer_count, s);
+    case 2: return launch<2>(a EKV_TB_DEREF, layer_count, s);
+    case 3: case 4: return launch<4>(a EKV_TB_DEREF, layer_count, s);
+    default: return launch<8>(a EKV_TB_DEREF, layer_count, s);      // 5..8: one group of 8; wider factors: ceil(rep / 8) groups per KV head
   }
 }
 
-hipError_t EKV_SYM(ekv_launch_decode_fused_d)(const EkvAttnArgs& a, const EkvScoreArgs& sc EKV_TB_DECL, int rep, int layer_count,
-                                              int nw, hipStream_t s) {
+hipError_t EKV_SYM(ekv_launch_decode_fused)(const EkvAttnArgs& a, const EkvScoreArgs& sc, const EkvSeqTable* tb, int rep, int layer_count,
+                                            int nw, hipStream_t s) {
   switch (rep) {
-    case 1: return launch_fused<1>(a, sc EKV_TB_PASS, layer_count, nw, s);
-    case 2: return launch_fused<2>(a, sc EKV_TB_PASS, layer_count, nw, s);
-    case 3: case 4: return launch_fused<4>(a, sc EKV_TB_PASS, layer_count, nw, s);
-    case 5: case 6: case 7: case 8: return launch_fused<8>(a, sc EKV_TB_PASS, layer_count, nw, s);
+    case 1: return launch_fused<1>(a, sc EKV_TB_DEREF, layer_count, nw, s);
+    case 2: return launch_fused<2>(a, sc EKV_TB_DEREF, layer_count, nw, s);
+    case 3: case 4: return launch_fused<4>(a, sc EKV_TB_DEREF, layer_count, nw, s);
+    case 5: case 6: case 7: case 8: return launch_fused<8>(a, sc EKV_TB_DEREF, layer_count, nw, s);
     default: return hipErrorInvalidValue;
   }
 }
-
-#if !EKV_BF16 && !EKV_KV8 && !EKV_BATCH   // (the LDS layout does not depend on the element type)
-size_t EKV_SYM(ekv_fused_lds_d)(int rep, int t_pad, int l_pad, int nw) {
-  switch (rep) {
-    case 1: return nw == 8 ? fused_lds<1, 8>(t_pad, l_pad, 3) : fused_lds<1, 4>(t_pad, l_pad, 3);
-    case 2: return nw == 8 ? fused_lds<2, 8>(t_pad, l_pad, 3) : fused_lds<2, 4>(t_pad, l_pad, 3);
-    case 3: case 4: return nw == 8 ? fused_lds<4, 8>(t_pad, l_pad, 3) : fused_lds<4, 4>(t_pad, l_pad, 3);
-    default: return nw == 8 ? fused_lds<8, 8>(t_pad, l_pad, 3) : fused_lds<8, 4>(t_pad, l_pad, 3);
-  }
-}
-#endif

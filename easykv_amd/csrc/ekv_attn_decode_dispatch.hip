@@ -1,9 +1,10 @@
-// head_dim / rope dispatch over the per-(D, rope) decode objects.
+// Dispatch over the decode instances of ekv_instances.def: head_dim, keys, element type, row format, batching.
 #include <cstdio>
 #include <cstdlib>
 
 #include "ekv_common.h"
 #include "ekv_kernels.h"
+#include "ekv_decode_stream.h"      // (EkvDecodeGeom: the LDS plan of the one-launch kernel)
 
 // Mixed phase orders of the fused decode step: the default mode and rule (ekv_decode_fused_order).  Rule: order K for the workgroups
 // whose hardware slot on the CU (HW_ID.TG_ID) has bit 1 set — slots 2 and 3 of the four a CU holds.  The four workgroups of a CU do
@@ -19,97 +20,62 @@
 #define EKV_FUSED_ORDER_BOUND 2
 #define EKV_FUSED_ORDER_INVERT 1
 
-hipError_t ekv_launch_attn_decode_d32_plain(const EkvAttnArgs&, int, int, hipStream_t);
-hipError_t ekv_launch_decode_fused_d32_plain(const EkvAttnArgs&, const EkvScoreArgs&, int, int, int, hipStream_t);
-size_t ekv_fused_lds_d32_plain(int, int, int, int);
-hipError_t ekv_launch_attn_decode_d32_rope(const EkvAttnArgs&, int, int, hipStream_t);
-hipError_t ekv_launch_decode_fused_d32_rope(const EkvAttnArgs&, const EkvScoreArgs&, int, int, int, hipStream_t);
-size_t ekv_fused_lds_d32_rope(int, int, int, int);
-hipError_t ekv_launch_attn_decode_d64_plain(const EkvAttnArgs&, int, int, hipStream_t);
-hipError_t ekv_launch_decode_fused_d64_plain(const EkvAttnArgs&, const EkvScoreArgs&, int, int, int, hipStream_t);
-size_t ekv_fused_lds_d64_plain(int, int, int, int);
-hipError_t ekv_launch_attn_decode_d64_rope(const EkvAttnArgs&, int, int, hipStream_t);
-hipError_t ekv_launch_decode_fused_d64_rope(const EkvAttnArgs&, const EkvScoreArgs&, int, int, int, hipStream_t);
-size_t ekv_fused_lds_d64_rope(int, int, int, int);
-hipError_t ekv_launch_attn_decode_d96_plain(const EkvAttnArgs&, int, int, hipStream_t);
-hipError_t ekv_launch_decode_fused_d96_plain(const EkvAttnArgs&, const EkvScoreArgs&, int, int, int, hipStream_t);
-size_t ekv_fused_lds_d96_plain(int, int, int, int);
-hipError_t ekv_launch_attn_decode_d96_rope(const EkvAttnArgs&, int, int, hipStream_t);
-hipError_t ekv_launch_decode_fused_d96_rope(const EkvAttnArgs&, const EkvScoreArgs&, int, int, int, hipStream_t);
-size_t ekv_fused_lds_d96_rope(int, int, int, int);
-hipError_t ekv_launch_attn_decode_d128_plain(const EkvAttnArgs&, int, int, hipStream_t);
-hipError_t ekv_launch_decode_fused_d128_plain(const EkvAttnArgs&, const EkvScoreArgs&, int, int, int, hipStream_t);
-size_t ekv_fused_lds_d128_plain(int, int, int, int);
-hipError_t ekv_launch_attn_decode_d128_rope(const EkvAttnArgs&, int, int, hipStream_t);
-hipError_t ekv_launch_decode_fused_d128_rope(const EkvAttnArgs&, const EkvScoreArgs&, int, int, int, hipStream_t);
-size_t ekv_fused_lds_d128_rope(int, int, int, int);
-hipError_t ekv_launch_attn_decode_d32_plain_bf16(const EkvAttnArgs&, int, int, hipStream_t);
-hipError_t ekv_launch_decode_fused_d32_plain_bf16(const EkvAttnArgs&, const EkvScoreArgs&, int, int, int, hipStream_t);
-hipError_t ekv_launch_attn_decode_d64_plain_bf16(const EkvAttnArgs&, int, int, hipStream_t);
-hipError_t ekv_launch_decode_fused_d64_plain_bf16(const EkvAttnArgs&, const EkvScoreArgs&, int, int, int, hipStream_t);
-hipError_t ekv_launch_attn_decode_d96_plain_bf16(const EkvAttnArgs&, int, int, hipStream_t);
-hipError_t ekv_launch_decode_fused_d96_plain_bf16(const EkvAttnArgs&, const EkvScoreArgs&, int, int, int, hipStream_t);
-hipError_t ekv_launch_attn_decode_d128_plain_bf16(const EkvAttnArgs&, int, int, hipStream_t);
-hipError_t ekv_launch_decode_fused_d128_plain_bf16(const EkvAttnArgs&, const EkvScoreArgs&, int, int, int, hipStream_t);
-// FP8-row ("kv8") instances: plain keys, head_dim 64 / 128, fp16 or bf16 queries / outputs
-hipError_t ekv_launch_attn_decode_d64_plain_kv8(const EkvAttnArgs&, int, int, hipStream_t);
-hipError_t ekv_launch_decode_fused_d64_plain_kv8(const EkvAttnArgs&, const EkvScoreArgs&, int, int, int, hipStream_t);
-hipError_t ekv_launch_attn_decode_d128_plain_kv8(const EkvAttnArgs&, int, int, hipStream_t);
-hipError_t ekv_launch_decode_fused_d128_plain_kv8(const EkvAttnArgs&, const EkvScoreArgs&, int, int, int, hipStream_t);
-hipError_t ekv_launch_attn_decode_d64_plain_bf16_kv8(const EkvAttnArgs&, int, int, hipStream_t);
-hipError_t ekv_launch_decode_fused_d64_plain_bf16_kv8(const EkvAttnArgs&, const EkvScoreArgs&, int, int, int, hipStream_t);
-hipError_t ekv_launch_attn_decode_d128_plain_bf16_kv8(const EkvAttnArgs&, int, int, hipStream_t);
-hipError_t ekv_launch_decode_fused_d128_plain_bf16_kv8(const EkvAttnArgs&, const EkvScoreArgs&, int, int, int, hipStream_t);
-// batch instances (batched decode steps, ekv_seq): plain keys, every head_dim, fp16 or bf16
-hipError_t ekv_launch_attn_decode_d32_plain_batch(const EkvAttnArgs&, const EkvSeqTable&, int, int, hipStream_t);
-hipError_t ekv_launch_decode_fused_d32_plain_batch(const EkvAttnArgs&, const EkvScoreArgs&, const EkvSeqTable&, int, int, int, hipStream_t);
-hipError_t ekv_launch_attn_decode_d32_plain_bf16_batch(const EkvAttnArgs&, const EkvSeqTable&, int, int, hipStream_t);
-hipError_t ekv_launch_decode_fused_d32_plain_bf16_batch(const EkvAttnArgs&, const EkvScoreArgs&, const EkvSeqTable&, int, int, int, hipStream_t);
-hipError_t ekv_launch_attn_decode_d64_plain_batch(const EkvAttnArgs&, const EkvSeqTable&, int, int, hipStream_t);
-hipError_t ekv_launch_decode_fused_d64_plain_batch(const EkvAttnArgs&, const EkvScoreArgs&, const EkvSeqTable&, int, int, int, hipStream_t);
-hipError_t ekv_launch_attn_decode_d64_plain_bf16_batch(const EkvAttnArgs&, const EkvSeqTable&, int, int, hipStream_t);
-hipError_t ekv_launch_decode_fused_d64_plain_bf16_batch(const EkvAttnArgs&, const EkvScoreArgs&, const EkvSeqTable&, int, int, int, hipStream_t);
-hipError_t ekv_launch_attn_decode_d96_plain_batch(const EkvAttnArgs&, const EkvSeqTable&, int, int, hipStream_t);
-hipError_t ekv_launch_decode_fused_d96_plain_batch(const EkvAttnArgs&, const EkvScoreArgs&, const EkvSeqTable&, int, int, int, hipStream_t);
-hipError_t ekv_launch_attn_decode_d96_plain_bf16_batch(const EkvAttnArgs&, const EkvSeqTable&, int, int, hipStream_t);
-hipError_t ekv_launch_decode_fused_d96_plain_bf16_batch(const EkvAttnArgs&, const EkvScoreArgs&, const EkvSeqTable&, int, int, int, hipStream_t);
-hipError_t ekv_launch_attn_decode_d128_plain_batch(const EkvAttnArgs&, const EkvSeqTable&, int, int, hipStream_t);
-hipError_t ekv_launch_decode_fused_d128_plain_batch(const EkvAttnArgs&, const EkvScoreArgs&, const EkvSeqTable&, int, int, int, hipStream_t);
-hipError_t ekv_launch_attn_decode_d128_plain_bf16_batch(const EkvAttnArgs&, const EkvSeqTable&, int, int, hipStream_t);
-hipError_t ekv_launch_decode_fused_d128_plain_bf16_batch(const EkvAttnArgs&, const EkvScoreArgs&, const EkvSeqTable&, int, int, int, hipStream_t);
+// ---- the instances (ekv_instances.def): launcher declarations, then one table entry per line
+typedef hipError_t EkvDecodeFn(const EkvAttnArgs&, const EkvSeqTable*, int rep, int count, hipStream_t);
+typedef hipError_t EkvFusedFn(const EkvAttnArgs&, const EkvScoreArgs&, const EkvSeqTable*, int rep, int count, int nw, hipStream_t);
+typedef hipError_t EkvScoreFn(const EkvScoreArgs&, const EkvSeqTable*, int count, hipStream_t);
+typedef hipError_t EkvFoldFn(const EkvScoreArgs&, int layer_count, hipStream_t);
+#define EKV_DECODE(d, keys, elem, rows, batching)                            \
+  EkvDecodeFn EKV_FN_DECODE(ekv_launch_attn_decode, d, keys, elem, rows, batching); \
+  EkvFusedFn EKV_FN_DECODE(ekv_launch_decode_fused, d, keys, elem, rows, batching);
+#define EKV_DECODE_SCORE(elem, batching) EkvScoreFn EKV_FN_DECODE_SCORE(ekv_launch_decode_score, elem, batching);
+#include "ekv_instances.def"
+EkvFoldFn ekv_launch_fold_f16, ekv_launch_fold_bf16;      // (exported by the `single` scorer instances: the fold reads no per-step field)
+
+namespace {
+struct DecodeInstance {
+  int head_dim;
+  bool rope, bf16, kv8, batch;
+  EkvDecodeFn* attn;
+  EkvFusedFn* fused;
+};
+const DecodeInstance kDecode[] = {
+#define EKV_DECODE(d, keys, elem, rows, batching)                                                                   \
+  {d, EKV_IS_##keys, EKV_IS_##elem, EKV_IS_##rows, EKV_IS_##batching, EKV_FN_DECODE(ekv_launch_attn_decode, d, keys, elem, rows, batching), \
+   EKV_FN_DECODE(ekv_launch_decode_fused, d, keys, elem, rows, batching)},
+#include "ekv_instances.def"
+};
+struct ScoreInstance {
+  bool bf16, batch;
+  EkvScoreFn* score;
+};
+const ScoreInstance kDecodeScore[] = {
+#define EKV_DECODE_SCORE(elem, batching) {EKV_IS_##elem, EKV_IS_##batching, EKV_FN_DECODE_SCORE(ekv_launch_decode_score, elem, batching)},
+#include "ekv_instances.def"
+};
+
+// The instance of a decode launch, or nullptr (hipErrorInvalidValue) for a combination the manifest does not hold or the arguments do
+// not fit: kv8 needs plain keys and the scale planes, bf16 and batches have no RoPE-on-read build, a batch runs on the ordered layout
+// (the planner refuses all of these before a launch).
+const DecodeInstance* decode_instance(const EkvAttnArgs& a, const EkvSeqTable* tb, int head_dim, bool bf16, bool kv8, bool fused_slot_rows) {
+  const bool rope = a.rope_cos != nullptr, batch = tb != nullptr;
+  if (kv8 && (rope || a.k_scale == nullptr || a.v_scale == nullptr)) return nullptr;
+  if (bf16 && rope) return nullptr;
+  if (batch && (rope || fused_slot_rows)) return nullptr;
+  for (const DecodeInstance& in : kDecode)
+    if (in.head_dim == head_dim && in.rope == rope && in.bf16 == bf16 && in.kv8 == kv8 && in.batch == batch) return &in;
+  return nullptr;
+}
+}  // namespace
 
 // any GQA factor (repeat_kv, llama_patch.py:19-29): factors <= 8 on the build of the next power of two, wider ones in groups of 8
 bool ekv_attn_decode_supported(int head_dim, int rep) {
   return (head_dim == 32 || head_dim == 64 || head_dim == 96 || head_dim == 128) && rep >= 1;
 }
 
-// (bf16: plain keys only — the planner refuses RoPE-on-read steps of a bf16 bank)
-#define EKV_DISPATCH(fn, ...)                                                                                      \
-  switch (head_dim) {                                                                                              \
-    case 32: return bf16 ? fn##32_plain_bf16(__VA_ARGS__) : rope ? fn##32_rope(__VA_ARGS__) : fn##32_plain(__VA_ARGS__);    \
-    case 64: return bf16 ? fn##64_plain_bf16(__VA_ARGS__) : rope ? fn##64_rope(__VA_ARGS__) : fn##64_plain(__VA_ARGS__);    \
-    case 96: return bf16 ? fn##96_plain_bf16(__VA_ARGS__) : rope ? fn##96_rope(__VA_ARGS__) : fn##96_plain(__VA_ARGS__);    \
-    case 128: return bf16 ? fn##128_plain_bf16(__VA_ARGS__) : rope ? fn##128_rope(__VA_ARGS__) : fn##128_plain(__VA_ARGS__); \
-  }
-
-// (kv8: plain keys, head_dim 64 / 128, rows + scales — the planner refuses everything else before a launch)
-#define EKV_DISPATCH_KV8(fn, ...)                                                                        \
-  if (kv8) {                                                                                             \
-    if (rope || a.k_scale == nullptr || a.v_scale == nullptr) return hipErrorInvalidValue;               \
-    switch (head_dim) {                                                                                  \
-      case 64: return bf16 ? fn##64_plain_bf16_kv8(__VA_ARGS__) : fn##64_plain_kv8(__VA_ARGS__);         \
-      case 128: return bf16 ? fn##128_plain_bf16_kv8(__VA_ARGS__) : fn##128_plain_kv8(__VA_ARGS__);      \
-    }                                                                                                    \
-    return hipErrorInvalidValue;                                                                         \
-  }
-
-hipError_t ekv_launch_attn_decode(const EkvAttnArgs& a, int head_dim, int layer_count, hipStream_t s, bool bf16, bool kv8) {
-  const int rep = a.n_q_heads / a.n_kv_heads;
-  const bool rope = a.rope_cos != nullptr;
-  EKV_DISPATCH_KV8(ekv_launch_attn_decode_d, a, rep, layer_count, s)
-  if (bf16 && rope) return hipErrorInvalidValue;
-  EKV_DISPATCH(ekv_launch_attn_decode_d, a, rep, layer_count, s)
-  return hipErrorInvalidValue;
+hipError_t ekv_launch_attn_decode(const EkvAttnArgs& a, const EkvSeqTable* tb, int head_dim, int count, hipStream_t s, bool bf16, bool kv8) {
+  const DecodeInstance* in = decode_instance(a, tb, head_dim, bf16, kv8, false);
+  return in ? in->attn(a, tb, a.n_q_heads / a.n_kv_heads, count, s) : hipErrorInvalidValue;
 }
 
 // The whole decode step in one launch: possible when a head is not split, at most one victim, and the row fits.
@@ -141,44 +107,27 @@ bool ekv_decode_fused_supported(int head_dim, int rep, int n_slots, int t_pad, i
   if (!ekv_attn_decode_supported(head_dim, rep) || rep > 8 || n_evict > 1 || n_slots > 256 * 24 || (cap & 3) != 0 || cap < 16) return false;
   size_t lds = 1 << 30;
   switch (head_dim) {
-    case 32: lds = ekv_fused_lds_d32_plain(rep, t_pad, l_pad, nw); break;
-    case 64: lds = ekv_fused_lds_d64_plain(rep, t_pad, l_pad, nw); break;
-    case 96: lds = ekv_fused_lds_d96_plain(rep, t_pad, l_pad, nw); break;
-    case 128: lds = ekv_fused_lds_d128_plain(rep, t_pad, l_pad, nw); break;
+    case 32: lds = ekv_fused_lds_max<32>(rep, t_pad, l_pad, nw); break;
+    case 64: lds = ekv_fused_lds_max<64>(rep, t_pad, l_pad, nw); break;
+    case 96: lds = ekv_fused_lds_max<96>(rep, t_pad, l_pad, nw); break;
+    case 128: lds = ekv_fused_lds_max<128>(rep, t_pad, l_pad, nw); break;
   }
   return lds <= (nw == 8 ? 150 : 80) * 1024;   // 80 KB still leaves two 4-wave workgroups per CU
 }
 
-hipError_t ekv_launch_decode_fused(const EkvAttnArgs& a, const EkvScoreArgs& sc, int head_dim, int layer_count, int nw,
+hipError_t ekv_launch_decode_fused(const EkvAttnArgs& a, const EkvScoreArgs& sc, const EkvSeqTable* tb, int head_dim, int count, int nw,
                                    hipStream_t s, bool bf16, bool kv8) {
-  const int rep = a.n_q_heads / a.n_kv_heads;
-  const bool rope = a.rope_cos != nullptr;
-  EKV_DISPATCH_KV8(ekv_launch_decode_fused_d, a, sc, rep, layer_count, nw, s)
-  if (bf16 && rope) return hipErrorInvalidValue;
-  EKV_DISPATCH(ekv_launch_decode_fused_d, a, sc, rep, layer_count, nw, s)
+  const DecodeInstance* in = decode_instance(a, tb, head_dim, bf16, kv8, sc.birth != nullptr);
+  return in ? in->fused(a, sc, tb, a.n_q_heads / a.n_kv_heads, count, nw, s) : hipErrorInvalidValue;
+}
+
+// ---- scorer and fold of the split path (ekv_decode_score.inc)
+hipError_t ekv_launch_decode_score(const EkvScoreArgs& sc, const EkvSeqTable* tb, int count, hipStream_t s, bool bf16) {
+  for (const ScoreInstance& in : kDecodeScore)
+    if (in.bf16 == bf16 && in.batch == (tb != nullptr)) return in.score(sc, tb, count, s);
   return hipErrorInvalidValue;
 }
 
-// batched decode steps: the batch instances of the two kernels above (plain keys; the planner refuses everything else)
-#define EKV_DISPATCH_BATCH(fn, ...)                                                                      \
-  switch (head_dim) {                                                                                    \
-    case 32: return bf16 ? fn##32_plain_bf16_batch(__VA_ARGS__) : fn##32_plain_batch(__VA_ARGS__);       \
-    case 64: return bf16 ? fn##64_plain_bf16_batch(__VA_ARGS__) : fn##64_plain_batch(__VA_ARGS__);       \
-    case 96: return bf16 ? fn##96_plain_bf16_batch(__VA_ARGS__) : fn##96_plain_batch(__VA_ARGS__);       \
-    case 128: return bf16 ? fn##128_plain_bf16_batch(__VA_ARGS__) : fn##128_plain_batch(__VA_ARGS__);    \
-  }
-
-hipError_t ekv_launch_attn_decode_batch(const EkvAttnArgs& a, const EkvSeqTable& tb, int head_dim, int n_seq, hipStream_t s, bool bf16) {
-  const int rep = a.n_q_heads / a.n_kv_heads;
-  if (a.rope_cos != nullptr) return hipErrorInvalidValue;
-  EKV_DISPATCH_BATCH(ekv_launch_attn_decode_d, a, tb, rep, n_seq, s)
-  return hipErrorInvalidValue;
-}
-
-hipError_t ekv_launch_decode_fused_batch(const EkvAttnArgs& a, const EkvScoreArgs& sc, const EkvSeqTable& tb, int head_dim, int n_seq, int nw,
-                                         hipStream_t s, bool bf16) {
-  const int rep = a.n_q_heads / a.n_kv_heads;
-  if (a.rope_cos != nullptr || sc.birth != nullptr) return hipErrorInvalidValue;
-  EKV_DISPATCH_BATCH(ekv_launch_decode_fused_d, a, sc, tb, rep, n_seq, nw, s)
-  return hipErrorInvalidValue;
+hipError_t ekv_launch_fold(const EkvScoreArgs& sc, int layer_count, hipStream_t s, bool bf16) {
+  return (bf16 ? ekv_launch_fold_bf16 : ekv_launch_fold_f16)(sc, layer_count, s);
 }

@@ -530,16 +530,14 @@ hipError_t launch_resident_any(const EkvAttnArgs& a, const EkvScoreArgs& sc, int
 
 }  // namespace
 
+hipError_t EKV_FN_D_ELEM(ekv_launch_attn_resident, 128, EKV_ELEM)(const EkvAttnArgs& a, const EkvScoreArgs& sc, int layer_count, hipStream_t s) {
+  return launch_resident_any(a, sc, layer_count, s);
+}
+
+#if !EKV_BF16   // (the eligibility rule does not depend on the element type)
 // Which steps: a whole scored chunk step (roco / h2o_head, accumulating) of an unsplit head on plain keys, head_dim 128, GQA factor
 // 1 / 2 / 4 / 8, 9..64 folded rows in one query block (fewer: the logits-in-LDS kernel) against at most 1280 keys, or at most 32 rows against
 // at most 2560 keys.
-#if EKV_BF16
-hipError_t ekv_launch_attn_resident_bf16(const EkvAttnArgs& a, const EkvScoreArgs& sc, int layer_count, hipStream_t s) {
-  return launch_resident_any(a, sc, layer_count, s);
-}
-#else
-hipError_t ekv_launch_attn_resident_bf16(const EkvAttnArgs& a, const EkvScoreArgs& sc, int layer_count, hipStream_t s);
-
 bool ekv_attn_resident_supported(int head_dim, int rep, int q_len, int n_slots, int W) {
   static const bool off = [] { const char* e = std::getenv("EKV_NO_RESIDENT"); return e != nullptr && e[0] == '1'; }();     // (A/B switch)
   static const int min_rows = [] { const char* e = std::getenv("EKV_RESIDENT_MIN_ROWS"); return e != nullptr ? std::atoi(e) : 9; }();      // (A/B switch; see the header)
@@ -547,9 +545,5 @@ bool ekv_attn_resident_supported(int head_dim, int rep, int q_len, int n_slots, 
   const bool shape = (rows <= 64 && n_slots <= RL<false>::TMAX) || (rows <= 32 && n_slots <= RL<true>::TMAX);      // (LONG = false / true)
   return !off && head_dim == R_D && (rep == 1 || rep == 2 || rep == 4 || rep == 8) && rows >= min_rows && shape && n_slots >= q_len && W >= 1 &&
          W <= n_slots && ekw_tail_lds_bytes(W) <= (size_t)RL<false>::OFF_P;
-}
-
-hipError_t ekv_launch_attn_resident(const EkvAttnArgs& a, const EkvScoreArgs& sc, int layer_count, hipStream_t s, bool bf16) {
-  return bf16 ? ekv_launch_attn_resident_bf16(a, sc, layer_count, s) : launch_resident_any(a, sc, layer_count, s);
 }
 #endif

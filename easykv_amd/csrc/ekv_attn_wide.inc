@@ -1039,15 +1039,13 @@ hipError_t launch_wide_rep(const EkvAttnArgs& a, int layer_count, hipStream_t s,
 
 }  // namespace
 
-#define EKW_CAT3(a, b, c, d, t) a##b##c##d##t
-#define EKW_CAT4(a, b, c, d, t) EKW_CAT3(a, b, c, d, t)
 // nwq = query waves of 32 rows: 4 (65..128 rows) or 2 (33..64 rows); 256-thread workgroups
 #if EKV_WIDE_ROPE
-#define EKW_ENTRY(d, m) EKW_CAT4(ekv_launch_attn_wide_rope_d, d, _m, m, EKV_DT_TAG)
+#define EKW_KEYS rope
 #else
-#define EKW_ENTRY(d, m) EKW_CAT4(ekv_launch_attn_wide_d, d, _m, m, EKV_DT_TAG)
+#define EKW_KEYS plain
 #endif
-hipError_t EKW_ENTRY(EKV_D, EKV_WIDE_MODE)(const EkvAttnArgs& a, int nwq, int layer_count, hipStream_t s, const EkvScoreArgs* tail) {
+hipError_t EKV_FN_WIDE(EKV_D, EKV_WIDE_MODE, EKW_KEYS, EKV_ELEM)(const EkvAttnArgs& a, int nwq, int layer_count, hipStream_t s, const EkvScoreArgs* tail) {
   switch (nwq) {
 #ifndef EKW_M2_KPW
 #define EKW_M2_KPW 2

@@ -1100,9 +1100,6 @@ hipError_t launch_lds(const EkvAttnArgs& a, const EkvScoreArgs& sc, int layer_co
 #define EKV_LCAT_(a, b) a##b
 #define EKV_LCAT(a, b) EKV_LCAT_(a, b)
 
-#define EKV_LCAT3_(a, b, t) a##b##t
-#define EKV_LCAT3(a, b, t) EKV_LCAT3_(a, b, t)
-
 #if !EKV_BF16   // (the LDS plan does not depend on the element type)
 size_t EKV_LCAT(ekv_chunk_lds_bytes_d, EKV_D)(int rows, int phys_extent, int n_slots) {
   const int e16 = (phys_extent + 15) & ~15;
@@ -1110,7 +1107,7 @@ size_t EKV_LCAT(ekv_chunk_lds_bytes_d, EKV_D)(int rows, int phys_extent, int n_s
 }
 #endif
 
-hipError_t EKV_LCAT3(ekv_launch_chunk_lds_d, EKV_D, EKV_DT_TAG)(const EkvAttnArgs& a, const EkvScoreArgs& sc, int layer_count, hipStream_t s) {
+hipError_t EKV_FN_D_ELEM(ekv_launch_chunk_lds, EKV_D, EKV_ELEM)(const EkvAttnArgs& a, const EkvScoreArgs& sc, int layer_count, hipStream_t s) {
   const int rows = (a.n_q_heads / a.n_kv_heads) * a.q_len;
   if (rows > 8 || a.n_slots > kLItems * kLNT) return hipErrorInvalidValue;
   return rows <= 4 ? launch_lds<4>(a, sc, layer_count, s) : launch_lds<8>(a, sc, layer_count, s);

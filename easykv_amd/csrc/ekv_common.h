@@ -9,7 +9,7 @@
 #define EKV_NEG_INF (-__builtin_inff())
 
 // Element type of the 16-bit tensors (K/V rows, queries, outputs).  Every kernel instance is compiled for one of them: fp16, or
-// bf16 with EKV_BF16 = 1 (the *_bf16.hip instances, whose kernel and launcher names carry the tag _bf16).  Only what reads or
+// bf16 with EKV_BF16 = 1 (the bf16 lines of ekv_instances.def, whose kernel names carry the tag _bf16).  Only what reads or
 // writes an element differs: the dot / MFMA builtins, the widening to f32 and the rounding of f32 to 16 bits.  The row pointers of
 // EkvAttnArgs / EkvScoreArgs stay __half*: rows are moved as bytes, and every element access goes through the helpers below.
 #ifndef EKV_BF16
@@ -18,11 +18,13 @@
 #if EKV_BF16
 typedef __bf16 ekv_e;
 #define EKV_DT_TAG _bf16
+#define EKV_ELEM bf16
 #define EKV_MFMA_16x16x32 __builtin_amdgcn_mfma_f32_16x16x32_bf16
 #define EKV_MFMA_32x32x16 __builtin_amdgcn_mfma_f32_32x32x16_bf16
 #else
 typedef _Float16 ekv_e;
 #define EKV_DT_TAG
+#define EKV_ELEM f16
 #define EKV_MFMA_16x16x32 __builtin_amdgcn_mfma_f32_16x16x32_f16
 #define EKV_MFMA_32x32x16 __builtin_amdgcn_mfma_f32_32x32x16_f16
 #endif

@@ -6,24 +6,14 @@
 #define EKV_STAMP(i) do { if (threadIdx.x == 0) stamps[i] = __builtin_readcyclecounter(); } while (0)
 #endif
 #include "ekv_decode_tail.h"
-// EKV_BATCH = 1 (ekv_decode_score_batch*.hip): the scorer of a batched decode step — workgroup (head, entry) shadows the per-step
+// EKV_BATCH = 1 (the batch instances): the scorer of a batched decode step — workgroup (head, entry) shadows the per-step
 // fields of its arguments from the entry's row of the table (as in ekv_attn_decode.inc) and is the uniform scorer from there on.
 // The fold kernel reads no per-step field (partials, split count and output rows are the envelope's): a batch launches the uniform one.
 #ifndef EKV_BATCH
 #define EKV_BATCH 0
 #endif
-#if EKV_BATCH
-#if EKV_BF16
-#define ekv_decode_score_kernel ekv_decode_score_kernel_batch_bf16
-#else
-#define ekv_decode_score_kernel ekv_decode_score_kernel_batch
-#endif
-#else
-#if EKV_BF16   // (bf16 instance: the same kernels under tagged names)
-#define ekv_decode_score_kernel ekv_decode_score_kernel_bf16
-#define ekv_fold_kernel ekv_fold_kernel_bf16
-#endif
-#endif
+#define ekv_decode_score_kernel EKV_KERNEL_NAME(ekv_decode_score_kernel)
+#define ekv_fold_kernel EKV_KERNEL_NAME(ekv_fold_kernel)
 
 namespace {
 
@@ -141,34 +131,20 @@ hipError_t launch_score(const EkvScoreArgs& sc EKV_TB_DECL, int layer_count, hip
 
 }  // namespace
 
-#if EKV_BATCH
-#if EKV_BF16
-hipError_t ekv_launch_decode_score_batch_bf16(const EkvScoreArgs& sc, const EkvSeqTable& tb, int n_seq, hipStream_t s) { return launch_score(sc, tb, n_seq, s); }
-#else
-hipError_t ekv_launch_decode_score_batch_bf16(const EkvScoreArgs& sc, const EkvSeqTable& tb, int n_seq, hipStream_t s);
-hipError_t ekv_launch_decode_score_batch(const EkvScoreArgs& sc, const EkvSeqTable& tb, int n_seq, hipStream_t s, bool bf16) {
-  return bf16 ? ekv_launch_decode_score_batch_bf16(sc, tb, n_seq, s) : launch_score(sc, tb, n_seq, s);
+// tb: the table of a batched step for the batch instances, unused (NULL) otherwise
+hipError_t EKV_FN_DECODE_SCORE(ekv_launch_decode_score, EKV_ELEM, EKV_BATCHING)(const EkvScoreArgs& sc, const EkvSeqTable* tb, int count, hipStream_t s) {
+  return launch_score(sc EKV_TB_DEREF, count, s);
 }
-#endif
-#elif EKV_BF16
-hipError_t ekv_launch_fold_bf16(const EkvScoreArgs& sc, int layer_count, hipStream_t s) { return launch_fold(sc, layer_count, s); }
-hipError_t ekv_launch_decode_score_bf16(const EkvScoreArgs& sc, int layer_count, hipStream_t s) { return launch_score(sc, layer_count, s); }
-#else
-hipError_t ekv_launch_fold_bf16(const EkvScoreArgs& sc, int layer_count, hipStream_t s);
-hipError_t ekv_launch_decode_score_bf16(const EkvScoreArgs& sc, int layer_count, hipStream_t s);
 
+#if !EKV_BATCH
+hipError_t EKV_FN_ELEM(ekv_launch_fold, EKV_ELEM)(const EkvScoreArgs& sc, int layer_count, hipStream_t s) { return launch_fold(sc, layer_count, s); }
+#endif
+
+#if !EKV_BATCH && !EKV_BF16   // (the LDS plan does not depend on the element type)
 bool ekv_decode_score_supported(const EkvScoreArgs& sc) {
   const int rep = sc.n_q_heads / sc.n_kv_heads;
   if (sc.q_len != 1 || sc.n_evict > 1 || (sc.cap & 3) != 0 || sc.n_slots > 256 * 24) return false;
   if (rep < 1 || rep > 8) return false;      // (wider GQA factors: the generic scorer)
   return score_lds(rep <= 2 ? rep : (rep <= 4 ? 4 : 8), sc.t_pad, sc.policy) <= 150 * 1024;
-}
-
-hipError_t ekv_launch_fold(const EkvScoreArgs& sc, int layer_count, hipStream_t s, bool bf16) {
-  return bf16 ? ekv_launch_fold_bf16(sc, layer_count, s) : launch_fold(sc, layer_count, s);
-}
-
-hipError_t ekv_launch_decode_score(const EkvScoreArgs& sc, int layer_count, hipStream_t s, bool bf16) {
-  return bf16 ? ekv_launch_decode_score_bf16(sc, layer_count, s) : launch_score(sc, layer_count, s);
 }
 #endif

@@ -24,6 +24,26 @@ struct EkvDecodeGeom {
   static constexpr int PS = D + 2;    // (m, l, o[D])
 };
 
+// LDS bytes of the one-launch decode kernel (ekv_decode_fused_kernel, ekv_attn_decode.inc): host arithmetic over the geometry, the same
+// for every element type, row format and batching.  n_state = score rows kept in LDS (3 with roco on the ordered layout).
+template <int D, int REP, int NW = 8>
+inline size_t ekv_fused_lds(int t_pad, int l_pad, int n_state) {
+  using Gm = EkvDecodeGeom<D, NW>;
+  const size_t part = ekv_align((size_t)Gm::NP * REP * Gm::PS, 4);
+  return ((size_t)REP * l_pad + part + (size_t)n_state * ekv_align((size_t)t_pad, 256)) * 4 + 2 * NW * 8 * 8 +
+         ekv_align(ekv_align((size_t)l_pad, 128) / 8, 16) + 264 * 4;   // + one dead-row bit per physical row + select histogram
+}
+// ... of the widest build a step of GQA factor `rep` on nw-wave workgroups can need (the planner: ekv_decode_fused_supported)
+template <int D>
+inline size_t ekv_fused_lds_max(int rep, int t_pad, int l_pad, int nw) {
+  switch (rep) {
+    case 1: return nw == 8 ? ekv_fused_lds<D, 1, 8>(t_pad, l_pad, 3) : ekv_fused_lds<D, 1, 4>(t_pad, l_pad, 3);
+    case 2: return nw == 8 ? ekv_fused_lds<D, 2, 8>(t_pad, l_pad, 3) : ekv_fused_lds<D, 2, 4>(t_pad, l_pad, 3);
+    case 3: case 4: return nw == 8 ? ekv_fused_lds<D, 4, 8>(t_pad, l_pad, 3) : ekv_fused_lds<D, 4, 4>(t_pad, l_pad, 3);
+    default: return nw == 8 ? ekv_fused_lds<D, 8, 8>(t_pad, l_pad, 3) : ekv_fused_lds<D, 8, 4>(t_pad, l_pad, 3);
+  }
+}
+
 // Streams positions [t0, t1) of KV head h.  SLOT_LDS: s_slot holds slot_of_pos[t0..t1) in LDS; otherwise s_slot is
 // the head's row of the global slot map (t0 must be a multiple of 8) and the 8 indices of a lane group are fetched
 // one iteration ahead.  Logits (q.k / sm_div) go to `logit_out` (+ `logit_stride` per query head): workspace or LDS.

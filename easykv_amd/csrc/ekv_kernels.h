@@ -23,8 +23,8 @@ struct EkvLaunch {
   int32_t fuse, tail;  // ... the scorer runs as the tail of the 16x16 one-pass kernel / of the wide column-sum pass
 };
 
-// Everything ekv_step_attend decides about a step, from the bank and step descriptors alone (ekv_plan_step): nothing is
-// dereferenced.  ekv_step_attend, ekv_step_check, ekv_step_plan, ekv_step_info and ekv_workspace_bytes all read it.
+// Everything ekv_step_attend decides about a step, from the bank and step descriptors alone (resolve_call, ekv_abi.hip): nothing is
+// dereferenced.  ekv_step_attend, ekv_step_check, ekv_step_plan, ekv_step_info and ekv_workspace_bytes — and their kv8 / batch kin — all read it.
 struct EkvStepPlan {
   int32_t t_pad, n_split, rows_per_split;
   int32_t n_partials;   // partials per query row the scorer folds (chunk kernels emit 2 per split)
@@ -40,8 +40,8 @@ struct EkvStepPlan {
   int32_t flush_unsplit;    // deferred flush: the column-sum pass runs unsplit over the one pass's key-range statistics
   int32_t slot_rows, slot_tail_ok;   // fused decode step on the slot-indexed score rows (EKV_PHASE_SLOT_ROWS / _TAIL_OK)
   int32_t bf16;             // 16-bit tensors are bf16: the launches run the EKV_BF16 kernel instances
-  int32_t kv8;              // the bank's K/V rows are FP8 codes + row scales (ekv_plan_step_kv8): the decode launches run the kv8 instances
-  int32_t batch;            // a batched decode step (ekv_plan_batch): the plan of the envelope; the launches run the batch instances
+  int32_t kv8;              // the bank's K/V rows are FP8 codes + row scales (an ekv_kv8 call): the decode launches run the kv8 instances
+  int32_t batch;            // a batched decode step (an ekv_seq call): the plan of the envelope; the launches run the batch instances
   int32_t strides[6];       // q, kv, out row strides (token, head) in elements, the dense layout filled in
   // Workspace: byte offsets of this call's slices (a deferred call's layout spans every deferred layer), -1 = not in the layout
   int64_t logits;     // [layer_count][Hq][q_len][t_pad]   raw q.k/sm_div of every live position
@@ -57,21 +57,12 @@ struct EkvStepPlan {
   int32_t n_list;
   EkvLaunch list[6];
 };
-// dtype: EKV_DTYPE_F16 / EKV_DTYPE_BF16 (any other value: EKV_E_ARG).  A bf16 step plans exactly as the fp16 step (same tiling, launch
-// list and workspace) and runs the bf16 instances of the same kernels; RoPE-on-read has no bf16 build (EKV_E_UNSUPPORTED, no launches).
-int ekv_plan_step(const ekv_bank* bank, const ekv_step* step, int32_t dtype, EkvStepPlan* plan);
-// The same plan for a step on FP8 rows (`bank` with k / v standing for the code planes): what the 16-bit step of that shape plans,
-// with plan->kv8 set — or EKV_E_UNSUPPORTED (nothing to launch) for q_len > 1, rope_on_read and head_dim other than 64 / 128.
-int ekv_plan_step_kv8(const ekv_bank* bank, const ekv_step* step, int32_t dtype, EkvStepPlan* plan);
-
 // The table of a batched decode step as the kernels' batch instances receive it: BY VALUE, behind the argument structs of the uniform
 // kernel (2304 bytes of the 4 KB a launch may carry).  Workgroup (head, entry ll) shadows the per-step fields of its argument structs
 // from e[ll] with wave-uniform loads before anything else; nothing is staged in device memory and no copy precedes the launch.
 struct EkvSeqTable {
-  ekv_seq e[EKV_MAX_SEQS];      // phys_extent resolved (ekv_plan_batch)
+  ekv_seq e[EKV_MAX_SEQS];      // phys_extent resolved (resolve_call)
 };
-int ekv_plan_batch(const ekv_bank* bank, const ekv_step* step, int32_t dtype, const ekv_seq* seqs, int32_t n_seq, EkvStepPlan* plan,
-                   ekv_step* envelope, EkvSeqTable* table);
 
 // The __half* members below point at 16-bit rows: fp16, or bf16 for the EKV_BF16 kernel instances (ekv_common.h: rows move as
 // bytes, and every element access of a kernel goes through ekv_e / ekv_h8 / ekv_to_e).
@@ -160,8 +151,11 @@ struct EkvScoreArgs {
 };
 
 // bf16 (the launchers below that take it): run the EKV_BF16 instances — 16-bit rows of q, k_new, v_new, out and the bank read and
-// written as bf16 (ekv_common.h); the planner never sends a RoPE-on-read step there
-hipError_t ekv_launch_attn_decode(const EkvAttnArgs& a, int head_dim, int layer_count, hipStream_t s, bool bf16, bool kv8 = false);
+// written as bf16 (ekv_common.h); the planner never sends a RoPE-on-read step there.
+// tb (the decode launchers): NULL = a uniform step of `count` layers; the table of a batched decode step = the batch instances (16-bit
+// rows, plain keys, ordered score rows): `a` / `sc` are the envelope's arguments with layer_begin = 0 and a.arrive = the bank's
+// counters, and `count` is the number of table entries, one workgroup row each.
+hipError_t ekv_launch_attn_decode(const EkvAttnArgs& a, const EkvSeqTable* tb, int head_dim, int count, hipStream_t s, bool bf16, bool kv8);
 // passes (wide-block kernel, two-pass scheme): bit 0 = the one pass (output + row statistics), bit 1 = the column-sum pass
 // tail_sc (wide-block kernel, two passes, passes & 2): the step's scorer runs as the tail of the column-sum pass (ekv_wide_tail.h)
 // wide: the wide-block kernel (ekv_chunk_wide, decided by the planner)
@@ -190,14 +184,8 @@ int ekv_decode_fused_nw(int n_heads_in_launch);
 // bit 6 = invert: order K when ((x & m) < b) != invert.  Both orders produce the same bits, so a hardware-derived number is as good as any.
 int ekv_decode_fused_order(int head_dim, int rep, bool scored, bool slot_rows, int nw, int n_heads_in_launch, int phys_extent);
 bool ekv_decode_fused_supported(int head_dim, int rep, int n_slots, int t_pad, int l_pad, int n_evict, int cap, int nw);
-hipError_t ekv_launch_decode_fused(const EkvAttnArgs& a, const EkvScoreArgs& sc, int head_dim, int layer_count, int nw, hipStream_t s,
-                                   bool bf16, bool kv8 = false);
-// batch instances (16-bit rows, plain keys, ordered score rows): `a` / `sc` are the envelope's arguments with layer_begin = 0 and
-// a.arrive = the bank's counters; n_seq workgroup rows, one per table entry
-hipError_t ekv_launch_attn_decode_batch(const EkvAttnArgs& a, const EkvSeqTable& tb, int head_dim, int n_seq, hipStream_t s, bool bf16);
-hipError_t ekv_launch_decode_fused_batch(const EkvAttnArgs& a, const EkvScoreArgs& sc, const EkvSeqTable& tb, int head_dim, int n_seq, int nw,
-                                         hipStream_t s, bool bf16);
-hipError_t ekv_launch_decode_score_batch(const EkvScoreArgs& sc, const EkvSeqTable& tb, int n_seq, hipStream_t s, bool bf16);
+hipError_t ekv_launch_decode_fused(const EkvAttnArgs& a, const EkvScoreArgs& sc, const EkvSeqTable* tb, int head_dim, int count, int nw,
+                                   hipStream_t s, bool bf16, bool kv8);
 // What workgroup (head, entry z) of a batch instance does first: its argument structs are the envelope's with the per-step fields
 // replaced by its entry's (scalar loads from the kernel arguments).  layer_begin = layer - z: every `layer_begin + ll` of the kernel
 // body then names the entry's bank layer, while the workspace and the call's tensors stay indexed by ll = z.
@@ -220,28 +208,75 @@ __device__ __forceinline__ EkvScoreArgs ekv_batch_score_args(const EkvScoreArgs&
   sc.range_start = e.range_start;
   return sc;
 }
-// How a kernel source spells its batch instance (EKV_BATCH = 1, set by the *_batch.hip stubs before anything is included; off, the
-// macros vanish and the source is the uniform kernel's, token for token): the argument structs arrive under the names a_env / sc_env
-// with the table behind them, and EKV_SHADOW_* declares `a` / `sc` as this workgroup's own copies.
+// How a kernel source spells its batch instance (EKV_BATCH = 1, set for the batch lines of ekv_instances.def before anything is
+// included; off, the macros vanish and the source is the uniform kernel's, token for token): the argument structs arrive under the
+// names a_env / sc_env with the table behind them, and EKV_SHADOW_* declares `a` / `sc` as this workgroup's own copies.
+// EKV_TB_DEREF: what a host launcher (which always takes the table's address) hands to the launch templates.
 #if defined(EKV_BATCH) && EKV_BATCH
+#define EKV_BATCHING batch
+#define EKV_BATCH_TAG _batch
 #define EKV_ARG_A a_env
 #define EKV_ARG_SC sc_env
 #define EKV_TB_PARAM , const EkvSeqTable tb
 #define EKV_TB_DECL , const EkvSeqTable& tb
 #define EKV_TB_PASS , tb
+#define EKV_TB_DEREF , *tb
 #define EKV_ARRIVE_ROW(ll) (a.layer_begin + (ll))      // the arrival counters are the bank's: indexed by the entry's layer
 #define EKV_SHADOW_A(z) const EkvAttnArgs a = ekv_batch_attn_args(a_env, tb.e[z], (int)(z));
 #define EKV_SHADOW_SC(z) const EkvScoreArgs sc = ekv_batch_score_args(sc_env, tb.e[z], (int)(z));
 #else
+#define EKV_BATCHING single
+#define EKV_BATCH_TAG
 #define EKV_ARG_A a
 #define EKV_ARG_SC sc
 #define EKV_TB_PARAM
 #define EKV_TB_DECL
 #define EKV_TB_PASS
+#define EKV_TB_DEREF
 #define EKV_ARRIVE_ROW(ll) (ll)
 #define EKV_SHADOW_A(z)
 #define EKV_SHADOW_SC(z)
 #endif
+#if defined(EKV_KV8) && EKV_KV8
+#define EKV_ROWS kv8
+#define EKV_ROWS_TAG _kv8
+#else
+#define EKV_ROWS kv16
+#define EKV_ROWS_TAG
+#endif
+
+// ---- kernel instances (ekv_instances.def; DESIGN.md "kernel instances")
+// Kernel symbol of an instance = the kernel's name + independent tags that default to empty: _batch, _kv8, _bf16 (ekv_common.h).  A
+// kernel source renames itself with  #define ekv_x_kernel EKV_KERNEL_NAME(ekv_x_kernel)  (profiles and traces know these names).
+#define EKV_KERNEL_NAME_(base, b, r, t) base##b##r##t
+#define EKV_KERNEL_NAME_X(base, b, r, t) EKV_KERNEL_NAME_(base, b, r, t)
+#define EKV_KERNEL_NAME(base) EKV_KERNEL_NAME_X(base, EKV_BATCH_TAG, EKV_ROWS_TAG, EKV_DT_TAG)
+// Launcher of an instance = the family's entry + every word of its manifest line, in the line's order.  The instance (which pastes
+// its own switches: EKV_D, EKV_KEYS, EKV_ELEM, EKV_ROWS, EKV_BATCHING, ...) and the dispatch tables (which paste the manifest's words)
+// both spell it through these macros.
+#define EKV_FN_DECODE_(fn, d, keys, elem, rows, batching) fn##_d##d##_##keys##_##elem##_##rows##_##batching
+#define EKV_FN_DECODE(fn, d, keys, elem, rows, batching) EKV_FN_DECODE_(fn, d, keys, elem, rows, batching)
+#define EKV_FN_DECODE_SCORE_(fn, elem, batching) fn##_##elem##_##batching
+#define EKV_FN_DECODE_SCORE(fn, elem, batching) EKV_FN_DECODE_SCORE_(fn, elem, batching)
+#define EKV_FN_ELEM_(fn, elem) fn##_##elem
+#define EKV_FN_ELEM(fn, elem) EKV_FN_ELEM_(fn, elem)
+#define EKV_FN_CHUNK_(d, m, elem) ekv_launch_attn_chunk_d##d##_m##m##_##elem
+#define EKV_FN_CHUNK(d, m, elem) EKV_FN_CHUNK_(d, m, elem)
+#define EKV_FN_WIDE_(d, m, keys, elem) ekv_launch_attn_wide_d##d##_m##m##_##keys##_##elem
+#define EKV_FN_WIDE(d, m, keys, elem) EKV_FN_WIDE_(d, m, keys, elem)
+#define EKV_FN_D_ELEM_(fn, d, elem) fn##_d##d##_##elem
+#define EKV_FN_D_ELEM(fn, d, elem) EKV_FN_D_ELEM_(fn, d, elem)      // (EKV_CHUNK_LDS, EKV_RESIDENT)
+#define EKV_FN_SCORE_SELECT_(nt, elem) ekv_launch_score_select_nt##nt##_##elem
+#define EKV_FN_SCORE_SELECT(nt, elem) EKV_FN_SCORE_SELECT_(nt, elem)
+// the manifest's words as the booleans of a table entry
+#define EKV_IS_plain false
+#define EKV_IS_rope true
+#define EKV_IS_f16 false
+#define EKV_IS_bf16 true
+#define EKV_IS_kv16 false
+#define EKV_IS_kv8 true
+#define EKV_IS_single false
+#define EKV_IS_batch true
 // FP8 bank conversion (ekv_kv8.hip).  src_bf16: the 16-bit rows are bf16; out_kind: 0 fp16, 1 bf16, 2 fp32
 hipError_t ekv_launch_kv8_quantize(const ekv_bank* bank, const ekv_kv8* q8, bool src_bf16, int layer_begin, int layer_count, int extent,
                                    hipStream_t s);
@@ -252,7 +287,7 @@ void ekv_chunk_blocks(int rep, int q_len, int* qb_rows, int* n_qblocks, int* qpw
 int ekv_chunk_col_parts(int qpw, bool rope);
 size_t ekv_score_lds_bytes(const EkvScoreArgs& a);
 bool ekv_decode_score_supported(const EkvScoreArgs& sc);
-hipError_t ekv_launch_decode_score(const EkvScoreArgs& sc, int layer_count, hipStream_t s, bool bf16);
+hipError_t ekv_launch_decode_score(const EkvScoreArgs& sc, const EkvSeqTable* tb, int count, hipStream_t s, bool bf16);
 hipError_t ekv_launch_fold(const EkvScoreArgs& sc, int layer_count, hipStream_t s, bool bf16);
 
 // Small-row chunk step with the logits in LDS (ekv_chunk_lds.inc): whole step in one launch, K and V read once.

@@ -747,8 +747,6 @@ __global__ void __launch_bounds__(kNT) ekv_tova_headmean_kernel(const EkvScoreAr
 #ifndef EKV_SS_DEVICE_ONLY
 #define EKV_SS_CAT_(a, b) a##b
 #define EKV_SS_CAT(a, b) EKV_SS_CAT_(a, b)
-#define EKV_SS_CAT3_(a, b, t) a##b##t
-#define EKV_SS_CAT3(a, b, t) EKV_SS_CAT3_(a, b, t)
 
 #if EKV_BF16
 size_t EKV_SS_CAT(ekv_score_lds_bytes_nt, EKV_SS_NT)(const EkvScoreArgs& a);
@@ -761,7 +759,7 @@ size_t EKV_SS_CAT(ekv_score_lds_bytes_nt, EKV_SS_NT)(const EkvScoreArgs& a) {
 }
 #endif
 
-hipError_t EKV_SS_CAT3(ekv_launch_score_select_nt, EKV_SS_NT, EKV_DT_TAG)(const EkvScoreArgs& a, int layer_count, hipStream_t s) {
+hipError_t EKV_FN_SCORE_SELECT(EKV_SS_NT, EKV_ELEM)(const EkvScoreArgs& a, int layer_count, hipStream_t s) {
   const size_t lds = EKV_SS_CAT(ekv_score_lds_bytes_nt, EKV_SS_NT)(a);
   if (lds > 160 * 1024) return hipErrorInvalidValue;
 #if EKV_SS_NT == 1024

@@ -4,16 +4,29 @@
 #include "ekv_common.h"
 #include "ekv_kernels.h"
 
-size_t ekv_score_lds_bytes_nt256(const EkvScoreArgs&);
-size_t ekv_score_lds_bytes_nt512(const EkvScoreArgs&);
-hipError_t ekv_launch_score_select_nt256(const EkvScoreArgs&, int, hipStream_t);
-hipError_t ekv_launch_score_select_nt512(const EkvScoreArgs&, int, hipStream_t);
-hipError_t ekv_launch_tova_headmean_nt512(const EkvScoreArgs&, int, hipStream_t);
-size_t ekv_score_lds_bytes_nt1024(const EkvScoreArgs&);
-hipError_t ekv_launch_score_select_nt1024(const EkvScoreArgs&, int, hipStream_t);
-hipError_t ekv_launch_score_select_nt256_bf16(const EkvScoreArgs&, int, hipStream_t);
-hipError_t ekv_launch_score_select_nt512_bf16(const EkvScoreArgs&, int, hipStream_t);
-hipError_t ekv_launch_score_select_nt1024_bf16(const EkvScoreArgs&, int, hipStream_t);
+// ---- the instances (ekv_instances.def).  The LDS plan and the head-mean row do not depend on the element type: the f16 instance of a
+// block size exports them.
+typedef hipError_t EkvSelectFn(const EkvScoreArgs&, int layer_count, hipStream_t);
+typedef size_t EkvSelectLdsFn(const EkvScoreArgs&);
+#define EKV_SCORE_SELECT(nt, elem) EkvSelectFn EKV_FN_SCORE_SELECT(nt, elem), ekv_launch_tova_headmean_nt##nt; EkvSelectLdsFn ekv_score_lds_bytes_nt##nt;
+#include "ekv_instances.def"
+
+namespace {
+struct SelectInstance {
+  int threads;
+  bool bf16;
+  EkvSelectFn* fn;
+};
+const SelectInstance kSelect[] = {
+#define EKV_SCORE_SELECT(nt, elem) {nt, EKV_IS_##elem, EKV_FN_SCORE_SELECT(nt, elem)},
+#include "ekv_instances.def"
+};
+hipError_t launch_select(int threads, const EkvScoreArgs& a, int layer_count, hipStream_t s, bool bf16) {
+  for (const SelectInstance& in : kSelect)
+    if (in.threads == threads && in.bf16 == bf16) return in.fn(a, layer_count, s);
+  return hipErrorInvalidValue;
+}
+}  // namespace
 
 size_t ekv_score_lds_bytes(const EkvScoreArgs& a) { return a.big_rows != nullptr ? ekv_score_lds_bytes_nt1024(a) : ekv_score_lds_bytes_nt512(a); }
 
@@ -24,9 +37,9 @@ bool ekv_score_rows_exceed_lds(int W, int rows) {
 
 hipError_t ekv_launch_score_select(const EkvScoreArgs& a, int layer_count, hipStream_t s, bool bf16) {
   // (the bf16 instances differ only in how the folded output is rounded and stored)
-  const auto nt256 = bf16 ? ekv_launch_score_select_nt256_bf16 : ekv_launch_score_select_nt256;
-  const auto nt512 = bf16 ? ekv_launch_score_select_nt512_bf16 : ekv_launch_score_select_nt512;
-  const auto nt1024 = bf16 ? ekv_launch_score_select_nt1024_bf16 : ekv_launch_score_select_nt1024;
+  auto nt256 = [&](const EkvScoreArgs& x, int lc, hipStream_t st) { return launch_select(256, x, lc, st, bf16); };
+  auto nt512 = [&](const EkvScoreArgs& x, int lc, hipStream_t st) { return launch_select(512, x, lc, st, bf16); };
+  auto nt1024 = [&](const EkvScoreArgs& x, int lc, hipStream_t st) { return launch_select(1024, x, lc, st, bf16); };
   // 256 threads only while at least three such workgroups fit a CU's LDS; wide score rows (C4: W = 5098 -> 82 KB) leave
   // room for one workgroup per CU, which must then bring 512 threads
   if (a.big_rows != nullptr) return nt1024(a, layer_count, s);   // rows in global scratch, keys in LDS

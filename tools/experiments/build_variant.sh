@@ -1,7 +1,8 @@
 #!/bin/bash
-# usage: tools/experiments/build_variant.sh NAME "-DFLAG=1 ..." file1.hip [file2.hip ...]   -> easykv_amd/csrc/variants/lib_NAME.so
+# usage: tools/experiments/build_variant.sh NAME "-DFLAG=1 ..." object1 [object2 ...]   -> easykv_amd/csrc/variants/lib_NAME.so
 # (A/B builds for the experiment drivers in this directory: select one with EASYKV_HIP_LIB=...; *.so is git-ignored but travels with gpurun;
-#  objects of the untouched sources are reused from csrc/obj)
+#  an object is named as the library's build names it: an instance of easykv_amd/csrc/ekv_instances.def, e.g. ekv_attn_decode_d128_plain,
+#  or a .hip file's base name; objects of the untouched sources are reused from csrc/obj)
 set -e
 ROOT=$(cd "$(dirname "$0")/../.." && pwd)
 cd $ROOT/easykv_amd/csrc
@@ -14,7 +15,10 @@ for o in obj/*.o; do
   OBJS="$OBJS $use"
 done
 for f in "$@"; do
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC -Wall -Wno-unused-function $FLAGS -c $f -o /tmp/ekv_var/obj_$NAME/$(basename $f .hip).o &
+  b=$(basename $f .hip)
+  # the source and switches of the object, as easykv_amd/_build.py derives them
+  SRC=$(cd $ROOT && python3 -c "import sys; from easykv_amd import _build; print(' '.join(dict(_build.objects())[sys.argv[1]]))" $b)
+  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC -Wall -Wno-unused-function $FLAGS -c $SRC -o /tmp/ekv_var/obj_$NAME/$b.o &
 done
 wait
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC $OBJS -o $ROOT/easykv_amd/csrc/variants/lib_$NAME.so

@@ -1,7 +1,7 @@
-"""Cycle stamps of the fused decode step (headline shape) from a -DEKV_TAIL_PROFILE build of ekv_attn_decode_d128_plain.hip:
+"""Cycle stamps of the fused decode step (headline shape) from a -DEKV_TAIL_PROFILE build of the ekv_attn_decode_d128_plain instance:
 per CU, how long no resident workgroup is streaming K/V while the launch is still running (the exposed scorer tails).
 
-    tools/experiments/build_variant.sh tailprof "-DEKV_TAIL_PROFILE" ekv_attn_decode_d128_plain.hip
+    tools/experiments/build_variant.sh tailprof "-DEKV_TAIL_PROFILE" ekv_attn_decode_d128_plain
     EASYKV_HIP_LIB=easykv_amd/csrc/variants/lib_tailprof.so python tools/experiments/exp_orderprof.py [out.json]
 
 Stamps per head (8 x u64 in the unused tova_row scratch): 0 start, 1 end of the first stream phase, 2 end of a mid-life tail (order K

@@ -1,12 +1,19 @@
 #!/usr/bin/env python3
-"""Register / spill report of one HIP source: python tools/kernel_regs.py easykv_amd/csrc/<file>.hip [substring ...] [-Dmacro ...]"""
+"""Register / spill report of one object of the library: python tools/kernel_regs.py <object name> [substring ...] [-Dmacro ...]
+(an instance of easykv_amd/csrc/ekv_instances.def by its object name, e.g. ekv_attn_decode_d128_plain_kv8, or a .hip file's base name)"""
 import re, subprocess, sys, os
-src = sys.argv[1]
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+from easykv_amd import _build
+name = os.path.basename(sys.argv[1])
+name = name[:-4] if name.endswith(".hip") else name
 defs = [a for a in sys.argv[2:] if a.startswith("-D")]
 filt = [a for a in sys.argv[2:] if not a.startswith("-D")]
-cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-c", os.path.basename(src), "-o", "/tmp/_regs.o",
-       "-Rpass-analysis=kernel-resource-usage"] + defs
-out = subprocess.run(cmd, cwd=os.path.dirname(os.path.abspath(src)), capture_output=True, text=True).stderr
+args = dict(_build.objects()).get(name)
+if args is None:
+    sys.exit(f"no object named {name}: see easykv_amd/csrc/ekv_instances.def")
+cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-c"] + defs + args + ["-o", "/tmp/_regs.o",
+       "-Rpass-analysis=kernel-resource-usage"]
+out = subprocess.run(cmd, cwd=_build.CSRC, capture_output=True, text=True).stderr
 cur = None
 rows = {}
 for line in out.splitlines():

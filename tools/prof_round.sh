@@ -35,7 +35,7 @@ run_pmc chunk_c5_write WRITE_SIZE python $R/tools/bench_chunk.py 10253 96 6
 unset MODE BUDGET STREAMING SHAPE
 timeout 600 bash $R/tools/sq_counters.sh > $OUT/sq_counters.txt 2>&1
 # cycle stamps of the scorer tail of the wide column-sum pass (a -DEKV_TAIL_PROFILE build of the m2 translation units, made in the build
-# container: tools/experiments/build_variant.sh tailprof "-DEKV_TAIL_PROFILE" ekv_attn_wide_d128_m2.hip)
+# container: tools/experiments/build_variant.sh tailprof "-DEKV_TAIL_PROFILE" ekv_attn_wide_d128_m2)
 if [ -f $R/easykv_amd/csrc/variants/lib_tailprof.so ]; then
   EASYKV_HIP_LIB=$R/easykv_amd/csrc/variants/lib_tailprof.so timeout 300 python $R/tools/experiments/exp_widetail_prof.py c3 s64 c2 > $OUT/wide_tail_stamps.txt 2>&1
 fi
