@@ -20,11 +20,17 @@ Model contract (what ``self`` must provide; the reference's is SURVEY.md §8b):
     rotated by their TRUE positions (un-rotated when ``generation_config['streaming']``: the kernel then rotates at
     read time by slot index, easykv/llama_patch.py:310-327).
   ``easykv_amd.hf`` adapts HF transformers >= 5 Llama/Mistral models to this contract.
+
+Shape of the driver: ``generate`` = :class:`_Run` (generation_config read once, with every refusal) -> :func:`_prefill` (one prompt up
+to the decode phase, as a :class:`Prefilled`) -> :func:`_decode` (one loop; each step's plan from the sequence's
+:class:`DecodePlanner`) -> :func:`_print_budget_line`.  ``generate_batch`` runs the same ``_Run`` and ``_prefill`` per prompt and steps one
+``DecodePlanner`` per sequence.  All of it runs without a GPU over stub caches: tests/test_driver_cpu.py.
 """
 from __future__ import annotations
 
 import contextlib
 import contextvars
+import dataclasses
 import functools
 import math
 import statistics
@@ -33,6 +39,7 @@ from typing import List, Optional
 
 import torch
 
+from . import _lib
 from .engine import KVBank, KVBankBatch, StepPlan
 
 KNOWN_POLICIES = ("roco", "h2o_head", "tova", "recency", "random", "full")
@@ -327,119 +334,119 @@ def _kv_dtype(model, key):
 
 
 # ------------------------------------------------------------------------------------------------
-# generate
+# the driver: what one call fixes (_Run), the token log, the captured forward, the per-token decode rule
 # ------------------------------------------------------------------------------------------------
-@torch.inference_mode()
-def generate(self, input_ids, generation_config, kv_mode="encoding", stride=1, report_decoding_latency: bool = False,
-             return_cache: bool = False, _stop_before_decode: bool = False):
-    # (_stop_before_decode: generate_batch's hook — run the prefill, then hand back what the decode phase starts from)
-    cfg = generation_config
-    temperature = cfg.get("temperature", 1.0)
-    top_p = cfg.get("top_p", 1.0)
-    max_new_tokens = cfg.get("max_new_tokens", 1024)
-    budget = cfg.get("budget", 0.5)
-    policy = cfg.get("kv_policy", "recency")
-    sink = cfg.get("temp_length", 4)
-    recent_ratio = cfg.get("recent_ratio", 0.1)
-    keep_attention = cfg.get("keep_attention", False)
-    eos_token_ids = cfg.get("eos_token_ids", [self.tokenizer.eos_token_id])
-    streaming = cfg.get("streaming", False)
-    record = cfg.get("_record_evictions", False)      # test hook: keep the evicted ids of every forward
-    # extension key: capture the steady-state forwards — the evicting decode step and, round 6, the evicting strided chunk of the
-    # prefill — in a hipGraph each (GraphedForward)
-    use_graph = cfg.get("hipgraph", False)
-    # extension key: element type of the K/V bank — "float16" (default), "bfloat16", or "auto" (bf16 when the model's parameters are)
-    kv_dtype = _kv_dtype(self, cfg.get("kv_dtype", "float16"))
-    if kv_dtype is torch.bfloat16 and streaming:
-        raise ValueError("generation_config['kv_dtype'] = bfloat16 with streaming=True: RoPE-on-read has no bf16 build (use float16)")
-    # extension key: storage of the K/V rows during the decode phase — None (the 16-bit rows of kv_dtype) or "fp8": the prefill runs on
-    # the 16-bit bank as always and the bank is quantised once at the prefill -> decode boundary (KVBank.quantize_fp8: OCP e4m3fn codes
-    # + one fp32 scale per row, 2 * head_dim + 8 bytes per row pair).  kv_dtype keeps meaning the 16-bit type of q / k / v / out.
-    kv_quant = cfg.get("kv_quant", None)
-    if kv_quant not in (None, "fp8"):
-        raise ValueError(f"generation_config['kv_quant'] must be None or 'fp8', not {kv_quant!r}")
-    if kv_quant is not None:
-        if streaming:
-            raise ValueError("generation_config['kv_quant'] = 'fp8' with streaming=True: the FP8 decode kernels have no RoPE-on-read build")
-        if kv_mode == "ppl":
-            raise ValueError("generation_config['kv_quant'] = 'fp8' with kv_mode='ppl': there is no decode phase to quantise the bank for")
-        if getattr(self, "layer_shard", None) is not None and self.layer_shard.world > 1:
-            raise ValueError("generation_config['kv_quant'] = 'fp8' is not supported on a layer-sharded model (model.layer_shard)")
-    n_layers, hq, h, d = _dims(self)
-    if kv_quant is not None and d not in (64, 128):
-        raise ValueError(f"generation_config['kv_quant'] = 'fp8' needs head_dim 64 or 128 (this model: {d})")
-    dev = torch.device(self.device)
-    if input_ids.dim() != 2 or input_ids.shape[0] != 1:
-        raise ValueError(f"input_ids must be [1, S] (batch size 1, as the reference); got {tuple(input_ids.shape)}")
-    length = input_ids.shape[-1]
-    input_ids = input_ids.to(dev)
-    scored = policy in SCORED
-    evicting = policy in KNOWN_POLICIES and policy != "full"   # unknown strings evict nothing
+def _dist():
+    """easykv_amd.dist, imported on first use: only a layer-sharded run pays for torch.distributed."""
+    from . import dist
+    return dist
 
-    # Layer sharding: a model that carries ``layer_shard`` (easykv_amd.dist.LayerShard) runs only its own
-    # block of layers in this process; every rank drives the same loop (the plans depend on lengths only), the bank of a
-    # rank holds its layers only, the model's forward moves the stage output to the next rank, and the sampled token comes
-    # from the last stage.
-    shard = getattr(self, "layer_shard", None)
-    if shard is not None and shard.world == 1:
-        shard = None
-    if shard is not None:
-        if shard.world > n_layers or shard.count < 1:
-            raise ValueError(f"layer sharding over {shard.world} ranks needs at least one of the model's {n_layers} layers per rank")
-        if use_graph:
-            # a captured forward would contain the stage hand-off (dist.send / dist.recv and, on gloo, host staging)
-            raise ValueError("generation_config['hipgraph'] is not supported on a layer-sharded model (model.layer_shard)")
-    l_begin, l_count = (shard.begin, shard.count) if shard is not None else (0, n_layers)
 
-    def policy_draw(n, mask_tail=0):
+class _Run:
+    """What one call of :func:`generate` / :func:`generate_batch` fixes for all of its forwards.  ``generation_config`` is read HERE and
+    nowhere else: the reference's keys and defaults (easykv/easykv.py:199-210), the extension keys, and every refusal."""
+
+    def __init__(self, model, cfg, kv_mode, stride, prompts):
+        self.model, self.cfg, self.stride = model, cfg, stride
+        self.temperature, self.top_p = cfg.get("temperature", 1.0), cfg.get("top_p", 1.0)
+        self.max_new_tokens, self.budget = cfg.get("max_new_tokens", 1024), cfg.get("budget", 0.5)
+        self.policy = policy = cfg.get("kv_policy", "recency")
+        self.sink, self.recent_ratio = cfg.get("temp_length", 4), cfg.get("recent_ratio", 0.1)
+        self.keep_attention = cfg.get("keep_attention", False)
+        self.eos_token_ids = cfg.get("eos_token_ids", [model.tokenizer.eos_token_id])
+        self.streaming = streaming = cfg.get("streaming", False)
+        self.record = cfg.get("_record_evictions", False)      # test hook: keep the evicted ids of every forward
+        # extension key: capture the steady-state forwards — the evicting decode step and, round 6, the evicting strided chunk of the
+        # prefill — in a hipGraph each (GraphedForward)
+        self.use_graph = cfg.get("hipgraph", False)
+        # extension key: the chunks of the prefill that only grow the cache join the dense prefix (see _strided_prefill)
+        self.dense_growth = cfg.get("dense_growth", False)
+        # extension key: the host looks at the sampled tokens every N tokens.  Default 1 = the reference's control flow (it tests
+        # every token before feeding it, easykv/easykv.py:257-263); N > 1 is opt-in, see TokenLog
+        self.eos_poll = max(1, int(cfg.get("eos_poll", 1)))
+        # extension key: element type of the K/V bank — "float16" (default), "bfloat16", or "auto" (bf16 when the model's parameters are)
+        self.kv_dtype = _kv_dtype(model, cfg.get("kv_dtype", "float16"))
+        if self.kv_dtype is torch.bfloat16 and streaming:
+            raise ValueError("generation_config['kv_dtype'] = bfloat16 with streaming=True: RoPE-on-read has no bf16 build (use float16)")
+        # extension key: storage of the K/V rows during the decode phase — None (the 16-bit rows of kv_dtype) or "fp8": the prefill runs on
+        # the 16-bit bank as always and the bank is quantised once at the prefill -> decode boundary (KVBank.quantize_fp8: OCP e4m3fn codes
+        # + one fp32 scale per row, 2 * head_dim + 8 bytes per row pair).  kv_dtype keeps meaning the 16-bit type of q / k / v / out.
+        self.kv_quant = kv_quant = cfg.get("kv_quant", None)
+        shard = getattr(model, "layer_shard", None)
+        if shard is not None and shard.world == 1:
+            shard = None
+        if kv_quant not in (None, "fp8"):
+            raise ValueError(f"generation_config['kv_quant'] must be None or 'fp8', not {kv_quant!r}")
+        if kv_quant is not None:
+            if streaming:
+                raise ValueError("generation_config['kv_quant'] = 'fp8' with streaming=True: the FP8 decode kernels have no RoPE-on-read build")
+            if kv_mode == "ppl":
+                raise ValueError("generation_config['kv_quant'] = 'fp8' with kv_mode='ppl': there is no decode phase to quantise the bank for")
+            if shard is not None:
+                raise ValueError("generation_config['kv_quant'] = 'fp8' is not supported on a layer-sharded model (model.layer_shard)")
+        self.dims = n_layers, _, _, d = _dims(model)
+        if kv_quant is not None and d not in (64, 128):
+            raise ValueError(f"generation_config['kv_quant'] = 'fp8' needs head_dim 64 or 128 (this model: {d})")
+        self.dev = torch.device(model.device)
+        for p in prompts:
+            if p.dim() != 2 or p.shape[0] != 1:
+                raise ValueError(f"input_ids must be [1, S] (batch size 1, as the reference); got {tuple(p.shape)}")
+        self.scored = policy in SCORED
+        self.evicting = policy in KNOWN_POLICIES and policy != "full"   # unknown strings evict nothing (SURVEY.md §0)
+        # Layer sharding (SURVEY.md §8e): a model that carries ``layer_shard`` (easykv_amd.dist.LayerShard) runs only its own
+        # block of layers in this process; every rank drives the same loop (the plans depend on lengths only), the bank of a
+        # rank holds its layers only, the model's forward moves the stage output to the next rank, and the sampled token comes
+        # from the last stage.
+        self.shard = shard
+        if shard is not None:
+            if shard.world > n_layers or shard.count < 1:
+                raise ValueError(f"layer sharding over {shard.world} ranks needs at least one of the model's {n_layers} layers per rank")
+            if self.use_graph:
+                # a captured forward would contain the stage hand-off (dist.send / dist.recv and, on gloo, host staging)
+                raise ValueError("generation_config['hipgraph'] is not supported on a layer-sharded model (model.layer_shard)")
+        self.layers = (shard.begin, shard.count) if shard is not None else (0, n_layers)
+        if kv_mode == "auto":                                      # easykv/easykv.py:220-227 (resolved per prompt by _prefill)
+            assert type(self.budget) == int
+        # HF seam + streaming: the stock attention module hands over q/k already rotated by the TRUE positions, while the
+        # streaming variant caches un-rotated keys and rotates by slot index on every read (llama_patch.py:310-327).  The
+        # model's own rotary module supplies both the tables for the read-time rotation and the ones to take its rotation off.
+        self.hf_stream = streaming and getattr(model.config, "_attn_implementation", None) == "easykv_amd"
+        rp = getattr(model.config, "rope_parameters", None) or {}
+        if streaming and not self.hf_stream:
+            # native contract: the rotation at read time uses theta = config.rope_theta (Llama-3: 5e5, Mistral: 1e6); scaled
+            # RoPE variants need the caller's own tables (generation_config['rope_tables'] = (cos, sin) fp32 [>= cap, D])
+            scaling = getattr(model.config, "rope_scaling", None) or (rp if rp.get("rope_type", "default") != "default" else None)
+            if scaling and cfg.get("rope_tables") is None:
+                raise ValueError("streaming=True on a model with scaled RoPE needs generation_config['rope_tables'] = (cos, sin)")
+        self.rope_base = float(getattr(model.config, "rope_theta", None) or rp.get("rope_theta", 10000.0))
+
+    def draw(self, n, mask_tail=0):
         """kv_policy='random': the reference's own draw — argmax of torch.rand on the global CPU generator over the row
-        (easykv/easykv.py:354-356; the chunk's own columns excluded in prefill, :494-497).  Layer-sharded: every rank draws
-        (generators seeded alike stay in step) and rank 0's value is the one all ranks evict, as the reference evicts one
-        range in all layers."""
+        (easykv/easykv.py:354-356; the chunk's own columns excluded in prefill, :494-497), so a run seeded like a reference run
+        evicts the same slots.  Layer-sharded: every rank draws (generators seeded alike stay in step) and rank 0's value is the
+        one all ranks evict, as the reference evicts one range in all layers."""
         draw = torch.rand(n)
         if mask_tail:
             draw[-mask_tail:] = -1e9
         e = int(torch.topk(draw, k=1, dim=-1)[1][0])
-        if shard is not None:
-            from . import dist as DS
-            e = int(DS.broadcast_object(e, 0))
-        return e
+        return e if self.shard is None else int(_dist().broadcast_object(e, 0))
 
-    if kv_mode == "auto":                                      # easykv/easykv.py:220-227
-        assert type(budget) == int
-        if budget > length:
-            kv_mode, budget = "decoding", budget - length
-        else:
-            kv_mode = "encoding_decoding"
-
-    # HF seam + streaming: the stock attention module hands over q/k already rotated by the TRUE positions, while the
-    # streaming variant caches un-rotated keys and rotates by slot index on every read (llama_patch.py:310-327).  The
-    # model's own rotary module supplies both the tables for the read-time rotation and the ones to take its rotation off.
-    hf_stream = streaming and getattr(self.config, "_attn_implementation", None) == "easykv_amd"
-    if streaming and not hf_stream:
-        # native contract: the rotation at read time uses theta = config.rope_theta (Llama-3: 5e5, Mistral: 1e6); scaled
-        # RoPE variants need the caller's own tables (generation_config['rope_tables'] = (cos, sin) fp32 [>= cap, D])
-        rp = getattr(self.config, "rope_parameters", None) or {}
-        scaling = getattr(self.config, "rope_scaling", None) or (rp if rp.get("rope_type", "default") != "default" else None)
-        if scaling and cfg.get("rope_tables") is None:
-            raise ValueError("streaming=True on a model with scaled RoPE needs generation_config['rope_tables'] = (cos, sin)")
-    rope_base = float(getattr(self.config, "rope_theta", None) or (getattr(self.config, "rope_parameters", None) or {}).get("rope_theta", 10000.0))
-
-    def new_cache(cap):
-        hf_rope = cfg.get("rope_tables")
-        if hf_stream:     # tables cover every slot index (< cap) and every true position (< length + max_new_tokens)
+    def new_cache(self, cap, length):
+        n_layers, hq, h, d = self.dims
+        hf_rope = self.cfg.get("rope_tables")
+        if self.hf_stream:     # tables cover every slot index (< cap) and every true position (< length + max_new_tokens)
             from . import hf
-            hf_rope = hf.rope_tables_from_model(self, max(cap + 8, length + max_new_tokens + 1) + 64, d, dev)
-        cache = BudgetedKVCache(n_layers, hq, h, d, cap + 8, dev, streaming=streaming, record=record, rope=hf_rope,
-                                layer_begin=l_begin, layer_count=l_count, rope_base=rope_base, dtype=kv_dtype)
-        cache.unrotate = hf_rope if hf_stream else None
+            hf_rope = hf.rope_tables_from_model(self.model, max(cap + 8, length + self.max_new_tokens + 1) + 64, d, self.dev)
+        cache = BudgetedKVCache(n_layers, hq, h, d, cap + 8, self.dev, streaming=self.streaming, record=self.record, rope=hf_rope,
+                                layer_begin=self.layers[0], layer_count=self.layers[1], rope_base=self.rope_base, dtype=self.kv_dtype)
+        cache.unrotate = hf_rope if self.hf_stream else None
         return cache
 
-    def forward(cache, ids, positions, plan):
-        plan.streaming = streaming
-        pos = torch.as_tensor(positions, dtype=torch.long, device=dev)
+    def forward(self, cache, ids, positions, plan):
+        plan.streaming = self.streaming
+        pos = torch.as_tensor(positions, dtype=torch.long, device=self.dev)
         with cache.active(plan, pos):
-            out = self(input_ids=ids, past_key_values=cache, position_ids=pos.view(1, -1), use_cache=True)
+            out = self.model(input_ids=ids, past_key_values=cache, position_ids=pos.view(1, -1), use_cache=True)
         # every owned layer must have gone through attend() exactly once: a model whose attention was not routed here
         # (an un-patched HF model) would otherwise silently run stock attention over the new rows only
         if cache.n_attend != cache.layer_count:
@@ -447,317 +454,343 @@ def generate(self, input_ids, generation_config, kv_mode="encoding", stride=1, r
                                "every attention layer through past_key_values.attend (easykv_amd.hf.patch_model for HF models)")
         return out
 
-    last_rank = shard.world - 1 if shard is not None else 0
-
-    def sample(logits_last):
-        """Next token [1, 1] on the device.  Sharded: only the last stage holds the logits; its draw is broadcast."""
-        if shard is None:
-            prob, raw = logits_adapter(logits_last.float(), temperature, top_p)
-            return torch.multinomial(prob, num_samples=1)
-        from . import dist as DS
-        if shard.rank == last_rank:
-            prob, raw = logits_adapter(logits_last.float(), temperature, top_p)
+    def sample(self, logits_last):
+        """Next token ``[rows, 1]`` on the device.  Sharded: only the last stage holds the logits; its draw is broadcast."""
+        last_rank = self.shard.world - 1 if self.shard is not None else 0
+        if self.shard is None or self.shard.rank == last_rank:
+            prob, raw = logits_adapter(logits_last.float(), self.temperature, self.top_p)
             tok = torch.multinomial(prob, num_samples=1)
         else:
-            tok = torch.zeros(1, 1, dtype=torch.long, device=dev)
-        return DS.broadcast(tok, last_rank)
+            tok = torch.zeros(1, 1, dtype=torch.long, device=self.dev)
+        return tok if self.shard is None else _dist().broadcast(tok, last_rank)
 
-    # extension key: the host looks at the sampled tokens every N tokens.  Default 1 = the reference's control flow (it tests
-    # every token before feeding it, easykv/easykv.py:257-263); N > 1 is opt-in, see TokenLog
-    eos_poll = max(1, int(cfg.get("eos_poll", 1)))
 
-    class TokenLog:
-        """Sampled tokens stay on the device.  The reference pulls every token to the host to test it for EOS
-        (`.cpu()` / `.item()`, ~5 syncs per token, easykv/easykv.py:257-283); here the host polls the device-side log once per
-        ``eos_poll`` tokens: ONE host sync per ``eos_poll`` tokens.  ``eos_poll=1`` (the default) is the reference's exact
-        control flow: nothing runs past an EOS.  With N > 1 (opt-in) up to N-1 forwards run past an EOS before it is seen:
-        the returned text and the printed budget line are still the reference's (cut at the first EOS; counts derived from
-        the EOS index, not from the cache), but those forwards have evicted from the cache handed back by
-        ``return_cache=True`` and have drawn from the sampler's / the 'random' policy's generators."""
+class TokenLog:
+    """Sampled tokens stay on the device.  The reference pulls every token to the host to test it for EOS
+    (`.cpu()` / `.item()`, ~5 syncs per token, easykv/easykv.py:257-283); here the host polls the device-side log once per
+    ``eos_poll`` tokens: ONE host sync per ``eos_poll`` tokens.  ``eos_poll=1`` (the default) is the reference's exact
+    control flow: nothing runs past an EOS.  With N > 1 (opt-in) up to N-1 forwards run past an EOS before it is seen:
+    the returned text and the printed budget line are still the reference's (cut at the first EOS; counts derived from
+    the EOS index, not from the cache), but those forwards have evicted from the cache handed back by
+    ``return_cache=True`` and have drawn from the sampler's / the 'random' policy's generators."""
 
-        def __init__(self):
-            self.buf = torch.empty(max(1, max_new_tokens), dtype=torch.long, device=dev)
-            self.eos = torch.as_tensor([int(e) for e in eos_token_ids], dtype=torch.long, device=dev)
-            self.n = self.checked = self.syncs = self.sampled = 0
-            self.stopped_by_eos = False
+    def __init__(self, max_new_tokens, eos_token_ids, eos_poll, dev):
+        self.max_new_tokens, self.eos_poll = max_new_tokens, eos_poll
+        self.buf = torch.empty(max(1, max_new_tokens), dtype=torch.long, device=dev)
+        self.eos = torch.as_tensor([int(e) for e in eos_token_ids], dtype=torch.long, device=dev)
+        self.n = self.checked = self.syncs = self.sampled = 0
+        self.stopped_by_eos = False
 
-        def push(self, tok):
-            self.buf[self.n:self.n + 1].copy_(tok.view(1))
-            self.n += 1
-            self.sampled += 1      # every token drawn, including those past an EOS a later poll cuts off
+    def push(self, tok):
+        self.buf[self.n:self.n + 1].copy_(tok.view(1))
+        self.n += 1
+        self.sampled += 1      # every token drawn, including those past an EOS a later poll cuts off
 
-        def poll(self):
-            """True when the loop must stop: an EOS was found among the tokens not looked at yet (``n`` is cut back to it)."""
-            if self.n - self.checked < eos_poll and self.n < max_new_tokens:
-                return False
-            hit = torch.isin(self.buf[self.checked:self.n], self.eos).cpu()     # the one host sync of this poll
-            self.syncs += 1
-            first = self.checked
-            self.checked = self.n
-            if bool(hit.any()):
-                self.n = first + int(torch.nonzero(hit)[0, 0]) + 1
-                self.stopped_by_eos = True
-                return True
+    def poll(self):
+        """True when the loop must stop: an EOS was found among the tokens not looked at yet (``n`` is cut back to it)."""
+        if self.n - self.checked < self.eos_poll and self.n < self.max_new_tokens:
             return False
+        hit = torch.isin(self.buf[self.checked:self.n], self.eos).cpu()     # the one host sync of this poll
+        self.syncs += 1
+        first = self.checked
+        self.checked = self.n
+        if bool(hit.any()):
+            self.n = first + int(torch.nonzero(hit)[0, 0]) + 1
+            self.stopped_by_eos = True
+            return True
+        return False
 
-        def ids(self):
-            return self.buf[:self.n].cpu().tolist()
+    def ids(self):
+        return self.buf[:self.n].cpu().tolist()
 
-        @property
-        def fed(self):   # tokens the reference would have fed back into the model (:257-264: the EOS token itself is not)
-            return self.n - 1 if self.stopped_by_eos else self.n
+    @property
+    def fed(self):   # tokens the reference would have fed back into the model (:257-264: the EOS token itself is not)
+        return self.n - 1 if self.stopped_by_eos else self.n
 
-    class GraphedForward:
-        """One forward of the WHOLE model captured in a hipGraph — a decode step (one token), or, since round 6, a
-        strided chunk of the prefill (`stride` tokens).  At a fixed budget every evicting forward has the same shapes, the same
-        StepPlan and the same cache length before and after (the cache oscillates idx <-> idx + stride, easykv/easykv.py:426-433), so
-        the host work of a forward (HF's per-layer Python, ~0.4 ms per layer: 12 ms of a 13 ms chunk forward of a 32-layer model) is
-        paid once at capture and a forward costs one graph launch.  Token ids and positions live in static device tensors; sampling, the
-        EOS test and the collection of logits / evicted ids stay outside the graph."""
 
-        def __init__(self, cache, plan, tok, positions):
-            n = len(positions)
-            self.tok = tok.view(1, n).clone()
-            self.pos = torch.as_tensor(positions, dtype=torch.long).to(dev)
-            self.graph = torch.cuda.CUDAGraph()
-            plan.streaming = streaming
-            self.cache = cache
-            n_recorded = len(cache.evictions)
-            tk = _ACTIVE.set(cache)
-            try:
-                with torch.cuda.graph(self.graph):      # capture launches nothing: the first replay runs this forward
-                    cache.begin_forward(plan, self.pos)
-                    self.logits = self_model(input_ids=self.tok, past_key_values=cache, position_ids=self.pos.view(1, -1),
-                                             use_cache=True).logits
-            finally:
-                _ACTIVE.reset(tk)
-            if cache.n_attend != cache.layer_count:
-                raise RuntimeError(f"model forward made {cache.n_attend} attend() calls for {cache.layer_count} owned layers")
-            # record=True: the captured forward left its (static) id tensors in the log; every replay appends a copy instead
-            self.static_ids = cache.evictions.pop() if len(cache.evictions) > n_recorded else None
-            self.layout = cache.bank.layout_signature()     # the captured kernels are those of THIS score-row layout
+class GraphedForward:
+    """One forward of the WHOLE model captured in a hipGraph — a decode step (one token), or, since round 6, a
+    strided chunk of the prefill (`stride` tokens).  At a fixed budget every evicting forward has the same shapes, the same
+    StepPlan and the same cache length before and after (the cache oscillates idx <-> idx + stride, easykv/easykv.py:426-433), so
+    the host work of a forward (HF's per-layer Python, ~0.4 ms per layer: 12 ms of a 13 ms chunk forward of a 32-layer model) is
+    paid once at capture and a forward costs one graph launch.  Token ids and positions live in static device tensors; sampling, the
+    EOS test and the collection of logits / evicted ids stay outside the graph."""
 
-        def __call__(self, tok, positions):
-            if self.cache.bank.layout_signature() != self.layout:
-                raise RuntimeError("the bank's score-row layout changed between capture and replay of the forward's graph "
-                                   "(an eager call on the bank in between): capture again")
-            self.tok.copy_(tok.view(self.tok.shape))
-            if len(positions) == 1:
-                self.pos.fill_(positions[0])
-            else:      # (consecutive positions, built on the device: no host-to-device copy on the replay path)
-                torch.arange(positions[0], positions[0] + len(positions), dtype=torch.long, device=dev, out=self.pos)
-            self.graph.replay()
-            if self.static_ids is not None:
-                self.cache.evictions.append([t.clone() for t in self.static_ids])
-            return self.logits
+    def __init__(self, model, cache, plan, tok, positions, streaming=False):
+        n = len(positions)
+        self.tok = tok.view(1, n).clone()
+        self.pos = torch.as_tensor(positions, dtype=torch.long).to(tok.device)
+        self.graph = torch.cuda.CUDAGraph()
+        plan.streaming = streaming
+        self.cache = cache
+        n_recorded = len(cache.evictions)
+        tk = _ACTIVE.set(cache)
+        try:
+            with torch.cuda.graph(self.graph):      # capture launches nothing: the first replay runs this forward
+                cache.begin_forward(plan, self.pos)
+                self.logits = model(input_ids=self.tok, past_key_values=cache, position_ids=self.pos.view(1, -1), use_cache=True).logits
+        finally:
+            _ACTIVE.reset(tk)
+        if cache.n_attend != cache.layer_count:
+            raise RuntimeError(f"model forward made {cache.n_attend} attend() calls for {cache.layer_count} owned layers")
+        # record=True: the captured forward left its (static) id tensors in the log; every replay appends a copy instead
+        self.static_ids = cache.evictions.pop() if len(cache.evictions) > n_recorded else None
+        self.layout = cache.bank.layout_signature()     # the captured kernels are those of THIS score-row layout
 
-    self_model = self
+    def __call__(self, tok, positions):
+        if self.cache.bank.layout_signature() != self.layout:
+            raise RuntimeError("the bank's score-row layout changed between capture and replay of the forward's graph "
+                               "(an eager call on the bank in between): capture again")
+        self.tok.copy_(tok.view(self.tok.shape))
+        if len(positions) == 1:
+            self.pos.fill_(positions[0])
+        else:      # (consecutive positions, built on the device: no host-to-device copy on the replay path)
+            torch.arange(positions[0], positions[0] + len(positions), dtype=torch.long, device=self.pos.device, out=self.pos)
+        self.graph.replay()
+        if self.static_ids is not None:
+            self.cache.evictions.append([t.clone() for t in self.static_ids])
+        return self.logits
 
-    # ---- single-token decode with eviction (decoding mode, and the tail of auto mode) ----------------------
-    def decode_loop(cache, logits_last, cur_pos, score_off, budget_d, whole_cache):
-        log = TokenLog()
-        positions: List[int] = []
-        graphed, prev_sig = None, None
-        while log.n < max_new_tokens:                           # :257 / :670
-            tok = sample(logits_last)
-            log.push(tok)
-            if log.poll():
-                break
-            t_now = cache.get_seq_length() + 1
-            evict = evicting and (whole_cache or (t_now - score_off) > budget_d)     # :303 / every step :708
-            plan = StepPlan(policy=policy, phase="decode", accumulate=scored, evict=evict, score_off=score_off, budget=budget_d)
-            positions.append(cur_pos)
-            if evict and policy in ("recency", "random"):
-                if whole_cache:                                 # :741-747
-                    if policy == "random":
-                        raise UnboundLocalError("auto mode + kv_policy='random' is broken in the reference (easykv/easykv.py:744)")
-                    plan.range_start = sink
-                else:                                           # :343-362: oldest / uniformly random generated slot
-                    # 'random': the reference's own draw — argmax of torch.rand over the generated slots, CPU generator
-                    # (easykv/easykv.py:354-356), so a run seeded like a reference run evicts the same slots
-                    e = 0 if policy == "recency" else policy_draw(len(positions))
-                    positions.pop(e)
-                    plan.range_start = score_off + e
-            # steady state (same plan, same cache length as the step before, one slot evicted per step): replay the graph
-            sig = (t_now, evict, plan.range_start)
-            if use_graph and evict and policy != "random" and sig == prev_sig:
-                if graphed is None:
-                    graphed = GraphedForward(cache, plan, tok, [cur_pos])
-                logits_last = graphed(tok, [cur_pos])[:, -1, :]
-            else:
-                logits_last = forward(cache, tok.view(1, 1), [cur_pos], plan).logits[:, -1, :]
-            prev_sig = sig
-            cur_pos += 1
-        cache.host_syncs, cache.tokens_sampled = log.syncs, log.sampled
-        return log.ids(), log.fed
 
-    # ---- dense prefix + strided chunks with eviction (encoding, auto, ppl) ---------------------------------
-    def prefill(cache, budget_p, idx, r_idx, tova_head_mean, keep_logits=False):
-        recent = int(budget_p * recent_ratio)                    # :394
-        cache.bank.state_init(idx + stride, 1 if keep_attention else 2, stride)       # :412-416
-        cache.score_prefix = keep_attention
-        # prefix [0, r_idx): dense causal; with keep_attention its probabilities seed S and Q (:396, :403-405)
-        plan = StepPlan(policy="roco" if keep_attention else "full", phase="prefill", accumulate=keep_attention,
-                        evict=False, stride=stride)
-        # extension key `dense_growth` (default off = the reference's forward sequence): the chunks that only GROW the cache —
-        # tokens [r_idx, idx): no eviction, and without keep_attention no accumulation either (easykv.py:443, :460) — attend
-        # causally to everything before them, which is what the dense prefix does: they join it as ONE forward of idx tokens.
-        # auto / ppl geometry takes the smallest r_idx (:551-552, :779-780), i.e. (idx - r_idx) / stride shape-changing forwards
-        # that no graph can replay (256 of the 511 forwards of a 4096-token prompt at stride 8).  Same K / V rows, same state, same
-        # evictions afterwards; with keep_attention the prefix' column sums are formed in one sweep instead of chunk by chunk
-        # (equal up to fp32 summation order).
-        r_dense = idx if cfg.get("dense_growth", False) else r_idx
-        out = forward(cache, input_ids[:, :r_dense], list(range(r_dense)), plan)
-        cache.score_prefix = False
-        logits_last = out.logits[:, -1, :]
-        all_logits, all_ids = [], []
-        if keep_logits and r_dense > r_idx:      # (ppl mode collects the logits of every token from r_idx on, :816-901)
-            all_logits.append(out.logits[0, r_idx:r_dense])
-            all_ids.append(input_ids[0, r_idx:r_dense])
-        r_idx = r_dense
-        cur_pos = r_idx
-        graphed, prev_sig = None, None
-        for tok_i in range(r_idx, length, stride):                # :426
-            t_now = cache.get_seq_length() + stride
-            plan = StepPlan(policy=policy, phase="prefill", accumulate=scored and (t_now > idx or keep_attention),
-                            evict=evicting and t_now > idx, budget=budget_p, recent=recent, sink=sink, stride=stride,
-                            tova_head_mean=tova_head_mean)
-            if plan.evict and policy == "recency":
-                plan.range_start = sink                          # :491-493
-            elif plan.evict and policy == "random":              # :494-499: argmax of torch.rand over the row, chunk excluded
-                plan.range_start = policy_draw(idx + stride, stride)
-            # steady state (generation_config['hipgraph']): from the second evicting chunk on every forward has the plan, the shapes and
-            # the cache length of the one before it — captured once, replayed for the rest of the prompt
-            sig = (t_now, plan.accumulate, plan.evict, plan.range_start)
-            chunk_ids, chunk_pos = input_ids[:, tok_i:tok_i + stride], list(range(cur_pos, cur_pos + stride))
-            if use_graph and plan.evict and policy != "random" and sig == prev_sig and chunk_ids.shape[1] == stride:
-                if graphed is None:
-                    graphed = GraphedForward(cache, plan, chunk_ids, chunk_pos)
-                logits = graphed(chunk_ids, chunk_pos)
-                if keep_logits:
-                    logits = logits.clone()      # (the graph's output buffer is overwritten by the next replay)
-            else:
-                logits = forward(cache, chunk_ids, chunk_pos, plan).logits
-            prev_sig = sig
-            logits_last = logits[:, -1, :]
+class DecodePlanner:
+    """The per-token decode rule of ONE sequence (easykv/easykv.py:287-362; the tail of auto mode, :708-747): whether a step evicts,
+    and for recency / random which slot.  ``score_off``: first position the score rows cover (decoding: the prompt length — only
+    generated slots are evicted); ``budget_d``: slots from there on the cache may hold; ``whole_cache``: auto mode, every step evicts
+    over the whole cache.  Plain decode without eviction (encoding mode, :508-526) is policy "full" with ``score_off = budget_d = 0``.
+    :func:`generate` drives one planner, :func:`generate_batch` one per sequence."""
+
+    def __init__(self, policy, sink, score_off, budget_d, whole_cache, cur_pos, draw):
+        self.policy, self.sink, self.score_off, self.budget_d, self.whole_cache = policy, sink, score_off, budget_d, whole_cache
+        self.scored = policy in SCORED
+        self.evicting = policy in KNOWN_POLICIES and policy != "full"
+        self.cur_pos = cur_pos                  # true position of the token the next step feeds
+        self.positions: List[int] = []          # true positions of the fed tokens still in the cache (recency / random)
+        self.draw = draw                        # n -> index of the 'random' victim among n generated slots (_Run.draw)
+
+    def step(self, t_before: int) -> StepPlan:
+        """The plan of the step that feeds the token at ``cur_pos`` to a cache of ``t_before`` slots; moves on to the next position."""
+        policy, score_off = self.policy, self.score_off
+        evict = self.evicting and (self.whole_cache or (t_before + 1 - score_off) > self.budget_d)     # :303 / every step :708
+        plan = StepPlan(policy=policy, phase="decode", accumulate=self.scored, evict=evict, score_off=score_off, budget=self.budget_d)
+        self.positions.append(self.cur_pos)
+        self.cur_pos += 1
+        if evict and policy in ("recency", "random"):
+            if self.whole_cache:                            # :741-747
+                if policy == "random":
+                    raise UnboundLocalError("auto mode + kv_policy='random' is broken in the reference (easykv/easykv.py:744)")
+                plan.range_start = self.sink
+            else:                                           # :343-362: oldest / uniformly random generated slot
+                e = 0 if policy == "recency" else self.draw(len(self.positions))
+                self.positions.pop(e)
+                plan.range_start = score_off + e
+        return plan
+
+
+@dataclasses.dataclass
+class Prefilled:
+    """What the decode phase of one sequence starts from (:func:`_prefill`)."""
+    cache: Optional[BudgetedKVCache]
+    logits: torch.Tensor         # [1, V]: the logits of the prompt's last token
+    planner: DecodePlanner
+    mode: str                    # "decoding" | "encoding" | "encoding_decoding" ('auto' resolved)
+    length: int                  # prompt length
+
+
+# ------------------------------------------------------------------------------------------------
+# prefill (easykv/easykv.py:228-245, :367-503, :530-669), decode, report; generate and generate_batch on top of them
+# ------------------------------------------------------------------------------------------------
+def _strided_prefill(run, cache, input_ids, budget_p, idx, r_idx, tova_head_mean, keep_logits=False):
+    """Dense prefix + strided chunks with eviction (encoding, auto, ppl).  -> (last logits, [logits per forward], [their token ids])"""
+    length, stride, policy, sink, keep_attention = input_ids.shape[-1], run.stride, run.policy, run.sink, run.keep_attention
+    recent = int(budget_p * run.recent_ratio)                # :394
+    cache.bank.state_init(idx + stride, 1 if keep_attention else 2, stride)       # :412-416
+    cache.score_prefix = keep_attention
+    # prefix [0, r_idx): dense causal; with keep_attention its probabilities seed S and Q (:396, :403-405)
+    plan = StepPlan(policy="roco" if keep_attention else "full", phase="prefill", accumulate=keep_attention,
+                    evict=False, stride=stride)
+    # extension key `dense_growth` (default off = the reference's forward sequence): the chunks that only GROW the cache —
+    # tokens [r_idx, idx): no eviction, and without keep_attention no accumulation either (easykv.py:443, :460) — attend
+    # causally to everything before them, which is what the dense prefix does: they join it as ONE forward of idx tokens.
+    # auto / ppl geometry takes the smallest r_idx (:551-552, :779-780), i.e. (idx - r_idx) / stride shape-changing forwards
+    # that no graph can replay (256 of the 511 forwards of a 4096-token prompt at stride 8).  Same K / V rows, same state, same
+    # evictions afterwards; with keep_attention the prefix' column sums are formed in one sweep instead of chunk by chunk
+    # (equal up to fp32 summation order).
+    r_dense = idx if run.dense_growth else r_idx
+    out = run.forward(cache, input_ids[:, :r_dense], list(range(r_dense)), plan)
+    cache.score_prefix = False
+    logits_last = out.logits[:, -1, :]
+    all_logits, all_ids = [], []
+    if keep_logits and r_dense > r_idx:      # (ppl mode collects the logits of every token from r_idx on, :816-901)
+        all_logits.append(out.logits[0, r_idx:r_dense])
+        all_ids.append(input_ids[0, r_idx:r_dense])
+    graphed, prev_sig = None, None
+    for tok_i in range(r_dense, length, stride):              # :426
+        t_now = cache.get_seq_length() + stride
+        plan = StepPlan(policy=policy, phase="prefill", accumulate=run.scored and (t_now > idx or keep_attention),
+                        evict=run.evicting and t_now > idx, budget=budget_p, recent=recent, sink=sink, stride=stride,
+                        tova_head_mean=tova_head_mean)
+        if plan.evict and policy == "recency":
+            plan.range_start = sink                          # :491-493
+        elif plan.evict and policy == "random":              # :494-499: argmax of torch.rand over the row, chunk excluded
+            plan.range_start = run.draw(idx + stride, stride)
+        # steady state (generation_config['hipgraph']): from the second evicting chunk on every forward has the plan, the shapes and
+        # the cache length of the one before it — captured once, replayed for the rest of the prompt
+        sig = (t_now, plan.accumulate, plan.evict, plan.range_start)
+        chunk_ids, chunk_pos = input_ids[:, tok_i:tok_i + stride], list(range(tok_i, tok_i + stride))
+        if run.use_graph and plan.evict and policy != "random" and sig == prev_sig and chunk_ids.shape[1] == stride:
+            if graphed is None:
+                graphed = GraphedForward(run.model, cache, plan, chunk_ids, chunk_pos, run.streaming)
+            logits = graphed(chunk_ids, chunk_pos)
             if keep_logits:
-                all_logits.append(logits[0])
-                all_ids.append(input_ids[0, tok_i:tok_i + stride])
-            cur_pos += stride
-        cache.bank.release_workspace(keep_bytes=64 << 20)      # (deferred chunk steps keep all layers' logits / column sums: not the decode phase's business)
-        return logits_last, all_logits, all_ids
+                logits = logits.clone()      # (the graph's output buffer is overwritten by the next replay)
+        else:
+            logits = run.forward(cache, chunk_ids, chunk_pos, plan).logits
+        prev_sig = sig
+        logits_last = logits[:, -1, :]
+        if keep_logits:
+            all_logits.append(logits[0])
+            all_ids.append(input_ids[0, tok_i:tok_i + stride])
+    cache.bank.release_workspace(keep_bytes=64 << 20)      # (deferred chunk steps keep all layers' logits / column sums: not the decode phase's business)
+    return logits_last, all_logits, all_ids
 
-    result = None
-    if kv_mode == "decoding":                                     # easykv/easykv.py:228-366
-        cap = length + (budget + 1 if evicting else max_new_tokens + 1)
-        cache = new_cache(cap)
-        out = forward(cache, input_ids, list(range(length)), StepPlan(policy="full", phase="prefill", accumulate=False))
-        if evicting and scored:
-            cache.bank.state_init(budget + 1, 0)                   # :242-245
-        if _stop_before_decode:
-            return dict(mode="decoding", cache=cache, logits=out.logits[:, -1, :], length=length, score_off=length, budget_d=budget, whole=False)
-        if kv_quant:      # prefill -> decode boundary: the decode steps run on FP8 rows
-            cache.bank.quantize_fp8()
-        out_ids, fed = decode_loop(cache, out.logits[:, -1, :], length, length, budget, False)
-        kept = min(fed, budget) if evicting else fed             # == cache length - prompt length when no forward ran past an EOS
-        print(f"KV cache budget ratio: {kept / len(out_ids) * 100:.2f}%({kept}/{len(out_ids)})")
-        result = self.tokenizer.decode(out_ids, skip_special_tokens=True).strip()
 
-    elif kv_mode == "encoding":                                   # :367-529
-        full = (type(budget) == float and budget >= 1.0) or (type(budget) == int and budget >= length)
-        if full:
-            cache = new_cache(length + max_new_tokens)
-            logits_last = forward(cache, input_ids, list(range(length)),
-                                  StepPlan(policy="full", phase="prefill", accumulate=False)).logits[:, -1, :]
+def _print_budget_line(mode, length, size, n_out=0, fed=0, budget_d=None):
+    """The reference's report, one function of the mode and the counts.  ``size``: live slots when the line is printed — encoding:
+    right after the prefill (:503); auto: after the last step (:751).  decoding (:364-365) reports the generated slots kept, derived
+    from the tokens ``fed`` (== cache length - prompt length when no forward ran past an EOS); ``budget_d`` None = nothing evicts."""
+    if mode == "encoding_decoding":
+        print(f"KV Cache Budget ratio {size / (length + n_out) * 100:.2f}%[{size}/({length}+{n_out})]")
+    else:
+        kept, of = (size, length) if mode == "encoding" else (fed if budget_d is None else min(fed, budget_d), n_out)
+        print(f"KV cache budget ratio: {kept / of * 100:.2f}%({kept}/{of})")
+
+
+def _prefill(run: _Run, input_ids, kv_mode) -> Prefilled:
+    """Everything before the decode phase of ONE prompt: 'auto' resolved, geometry, the cache, dense prefix, strided chunks, the
+    state of the decode rule.  Shared by :func:`generate` and, prompt by prompt, :func:`generate_batch`."""
+    length, budget, stride = input_ids.shape[-1], run.budget, run.stride
+    input_ids = input_ids.to(run.dev)
+    if kv_mode == "auto":                                        # easykv/easykv.py:220-227
+        kv_mode, budget = ("decoding", budget - length) if budget > length else ("encoding_decoding", budget)
+    dense = StepPlan(policy="full", phase="prefill", accumulate=False)
+    if kv_mode == "decoding":                                    # :228-366
+        cache = run.new_cache(length + (budget + 1 if run.evicting else run.max_new_tokens + 1), length)
+        logits = run.forward(cache, input_ids, list(range(length)), dense).logits[:, -1, :]
+        if run.evicting and run.scored:
+            cache.bank.state_init(budget + 1, 0)                 # :242-245
+        rule = dict(policy=run.policy, score_off=length, budget_d=budget, whole_cache=False)
+    elif kv_mode == "encoding":                                  # :367-529
+        if (type(budget) == float and budget >= 1.0) or (type(budget) == int and budget >= length):
+            cache = run.new_cache(length + run.max_new_tokens, length)
+            logits = run.forward(cache, input_ids, list(range(length)), dense).logits[:, -1, :]
         else:
             budget_p, idx, r_idx = geometry("encoding", length, budget, stride)
             # 'full' / unknown policy strings evict nothing (the reference's cache just grows): size for the whole prompt
-            cache = new_cache((idx + stride if evicting else length) + max_new_tokens)
-            logits_last, _, _ = prefill(cache, budget_p, idx, r_idx, True)
-        kept = cache.get_seq_length()
-        print(f"KV cache budget ratio: {kept / length * 100:.2f}%({kept}/{length})")
-        if _stop_before_decode:
-            return dict(mode="encoding", cache=cache, logits=logits_last, length=length, score_off=0, budget_d=0, whole=False)
-        if kv_quant:      # prefill -> decode boundary
-            cache.bank.quantize_fp8()
-        log, cur_pos, t_first, n_fwd = TokenLog(), length, None, 0
-        while log.n < max_new_tokens:                              # :508-526 plain decode, no eviction
-            tok = sample(logits_last)
-            log.push(tok)
-            if log.poll():
-                break
-            logits_last = forward(cache, tok.view(1, 1), [cur_pos],
-                                  StepPlan(policy="full", phase="decode", accumulate=False)).logits[:, -1, :]
-            n_fwd += 1
-            if report_decoding_latency and n_fwd == 1:             # the reference drops the first step from the mean (:527)
-                torch.cuda.synchronize(dev)
-                t_first = time.time()
-            cur_pos += 1
-        out_ids = log.ids()
-        cache.host_syncs, cache.tokens_sampled = log.syncs, log.sampled
-        result = self.tokenizer.decode(out_ids, skip_special_tokens=True).strip()
-        if report_decoding_latency and n_fwd > 1:
-            torch.cuda.synchronize(dev)
-            print(f"Per-step decoding latency: {(time.time() - t_first) / (n_fwd - 1):.3f}")
-
-    elif kv_mode == "encoding_decoding":                          # :530-753
+            cache = run.new_cache((idx + stride if run.evicting else length) + run.max_new_tokens, length)
+            logits = _strided_prefill(run, cache, input_ids, budget_p, idx, r_idx, True)[0]
+        _print_budget_line("encoding", length, cache.get_seq_length())
+        rule = dict(policy="full", score_off=0, budget_d=0, whole_cache=False)      # :508-526 plain decode, no eviction
+    elif kv_mode == "encoding_decoding":                         # :530-753
         assert type(budget) == int and budget <= length
         white_lst = ["random", "recency", "tova", "roco"]
-        assert policy in white_lst, f"mode must be within {white_lst}, get {policy} instead"
+        assert run.policy in white_lst, f"mode must be within {white_lst}, get {run.policy} instead"
         assert stride > 1, "auto mode needs stride > 1 (the reference asserts at easykv/easykv.py:666-669)"
         budget_p, idx, r_idx = geometry("auto", length, budget, stride)
-        cache = new_cache(idx + stride + 1)
-        logits_last, _, _ = prefill(cache, budget_p, idx, r_idx, False)
-        if _stop_before_decode:
-            return dict(mode="auto", cache=cache, logits=logits_last, length=length, score_off=0, budget_d=budget_p, whole=True)
-        if kv_quant:      # prefill -> decode boundary
-            cache.bank.quantize_fp8()
+        cache = run.new_cache(idx + stride + 1, length)
+        logits = _strided_prefill(run, cache, input_ids, budget_p, idx, r_idx, False)[0]
         # the score rows keep their first idx+1 columns (:666-669); the decode rules then run over the whole cache
-        out_ids, _ = decode_loop(cache, logits_last, length, 0, budget_p, True)
-        size = cache.get_seq_length()
-        print(f"KV Cache Budget ratio {size / (length + len(out_ids)) * 100:.2f}%[{size}/({length}+{len(out_ids)})]")
-        result = self.tokenizer.decode(out_ids, skip_special_tokens=True).strip()
-
-    elif kv_mode == "ppl":                                        # :754-901
-        ce = torch.nn.CrossEntropyLoss(reduction="none")
-        has_logits = shard is None or shard.rank == last_rank     # sharded: the logits exist on the last stage only
-        if budget >= 1.0:     # NB: like the reference, ANY int budget takes this branch (:759); pass a ratio to evict
-            cache = new_cache(length)
-            out = forward(cache, input_ids, list(range(length)), StepPlan(policy="full", phase="prefill", accumulate=False))
-            if has_logits:
-                lp = ce(out.logits[0, :-1].float(), input_ids[0, 1:]).cpu().numpy().tolist()
-                result = math.exp(statistics.mean(lp))
-        else:
-            budget_p, idx, r_idx = geometry("ppl", length, budget, stride)
-            cache = new_cache(idx + stride if evicting else length)
-            _, all_logits, all_ids = prefill(cache, budget_p, idx, r_idx, True, keep_logits=has_logits)
-            kept = cache.get_seq_length()
-            print(f"KV cache budget ratio: {kept / length * 100:.2f}%({kept}/{length})")
-            if has_logits:
-                ids_cat, log_cat = torch.cat(all_ids), torch.cat(all_logits, dim=0)
-                assert ids_cat.shape[0] == log_cat.shape[0]
-                lp = ce(log_cat[:-1].float(), ids_cat[1:]).cpu().numpy().tolist()
-                result = math.exp(statistics.mean(lp))
-        if shard is not None:
-            from . import dist as DS
-            result = DS.broadcast_object(result, last_rank)
+        rule = dict(policy=run.policy, score_off=0, budget_d=budget_p, whole_cache=True)
     else:
         raise ValueError(f"unknown kv_mode {kv_mode!r}")
-    if shard is not None:       # stage outputs still in flight (easykv_amd.dist.PipelineStage posts them without waiting)
-        from . import dist as DS
-        DS.drain_stages()
+    return Prefilled(cache, logits, DecodePlanner(sink=run.sink, cur_pos=length, draw=run.draw, **rule), kv_mode, length)
+
+
+def _decode(run: _Run, pre: Prefilled, report_latency=False):
+    """The decode phase of one sequence (:257-366, :508-526, :670-747): sample, test for EOS, plan, forward.  -> (token ids, tokens fed)"""
+    cache, planner, logits_last = pre.cache, pre.planner, pre.logits
+    log = TokenLog(run.max_new_tokens, run.eos_token_ids, run.eos_poll, run.dev)
+    graphed, prev_sig, n_fwd, t_first = None, None, 0, None
+    while log.n < run.max_new_tokens:                           # :257 / :670
+        tok = run.sample(logits_last)
+        log.push(tok)
+        if log.poll():
+            break
+        t_now, pos = cache.get_seq_length() + 1, [planner.cur_pos]
+        plan = planner.step(t_now - 1)
+        # steady state (same plan, same cache length as the step before, one slot evicted per step): replay the graph
+        sig = (t_now, plan.evict, plan.range_start)
+        if run.use_graph and plan.evict and planner.policy != "random" and sig == prev_sig:
+            if graphed is None:
+                graphed = GraphedForward(run.model, cache, plan, tok, pos, run.streaming)
+            logits_last = graphed(tok, pos)[:, -1, :]
+        else:
+            logits_last = run.forward(cache, tok.view(1, 1), pos, plan).logits[:, -1, :]
+        prev_sig = sig
+        n_fwd += 1
+        if report_latency and n_fwd == 1:                       # the reference drops the first step from the mean (:527)
+            torch.cuda.synchronize(run.dev)
+            t_first = time.time()
+    cache.host_syncs, cache.tokens_sampled = log.syncs, log.sampled
+    if report_latency and n_fwd > 1:
+        torch.cuda.synchronize(run.dev)
+        print(f"Per-step decoding latency: {(time.time() - t_first) / (n_fwd - 1):.3f}")
+    return log.ids(), log.fed
+
+
+def _perplexity(run: _Run, input_ids):
+    """kv_mode='ppl' (easykv/easykv.py:754-901): the strided prefill alone, keeping every token's logits.  -> (perplexity, cache)"""
+    length, budget, shard = input_ids.shape[-1], run.budget, run.shard
+    input_ids = input_ids.to(run.dev)
+    has_logits = shard is None or shard.rank == shard.world - 1     # sharded: the logits exist on the last stage only
+    if budget >= 1.0:     # NB: like the reference, ANY int budget takes this branch (:759); pass a ratio to evict
+        cache = run.new_cache(length, length)
+        out = run.forward(cache, input_ids, list(range(length)), StepPlan(policy="full", phase="prefill", accumulate=False))
+        all_logits, all_ids = ([out.logits[0]], [input_ids[0]]) if has_logits else ([], [])
+    else:
+        budget_p, idx, r_idx = geometry("ppl", length, budget, run.stride)
+        cache = run.new_cache(idx + run.stride if run.evicting else length, length)
+        _, all_logits, all_ids = _strided_prefill(run, cache, input_ids, budget_p, idx, r_idx, True, keep_logits=has_logits)
+        _print_budget_line("encoding", length, cache.get_seq_length())
+    result = None
+    if has_logits:
+        ids_cat, log_cat = torch.cat(all_ids), torch.cat(all_logits, dim=0)
+        assert ids_cat.shape[0] == log_cat.shape[0]
+        lp = torch.nn.CrossEntropyLoss(reduction="none")(log_cat[:-1].float(), ids_cat[1:]).cpu().numpy().tolist()
+        result = math.exp(statistics.mean(lp))
+    if shard is not None:
+        result = _dist().broadcast_object(result, shard.world - 1)
+    return result, cache
+
+
+@torch.inference_mode()
+def generate(self, input_ids, generation_config, kv_mode="encoding", stride=1, report_decoding_latency: bool = False,
+             return_cache: bool = False):
+    run = _Run(self, generation_config, kv_mode, stride, [input_ids])
+    if kv_mode == "ppl":
+        result, cache = _perplexity(run, input_ids)
+    else:
+        pre = _prefill(run, input_ids, kv_mode)
+        cache = pre.cache
+        if run.kv_quant:      # prefill -> decode boundary: the decode steps run on FP8 rows
+            cache.bank.quantize_fp8()
+        out_ids, fed = _decode(run, pre, report_decoding_latency and pre.mode == "encoding")
+        if pre.mode != "encoding":      # (encoding mode reports the cache the prefill left: printed there)
+            _print_budget_line(pre.mode, pre.length, cache.get_seq_length(), len(out_ids), fed, pre.planner.budget_d if run.evicting else None)
+        result = self.tokenizer.decode(out_ids, skip_special_tokens=True).strip()
+    if run.shard is not None:       # stage outputs still in flight (easykv_amd.dist.PipelineStage posts them without waiting)
+        _dist().drain_stages()
     return (result, cache) if return_cache else result
 
 
 @torch.inference_mode()
 def generate_batch(self, input_ids_list, generation_config, kv_mode="encoding", stride=1, return_cache: bool = False):
-    """``generate`` for several prompts of different lengths: every prompt is prefilled ALONE through :func:`generate`'s own prefill
-    (all modes keep the reference's geometry), its bank becomes one sequence of a :class:`KVBankBatch`, and the decode phase then
-    runs ONE model forward per token for all live sequences — ``input_ids [B', 1]``, ``position_ids [B', 1]`` with each sequence's
-    own position, one batched library step per layer.  Each sequence's plan is built as ``generate`` builds it (it evicts when ITS
-    length exceeds ITS budget, ``score_off`` = ITS prompt length, recency / random ranges per sequence) and a sequence leaves the
-    batch when it samples an EOS or has been fed ``max_new_tokens`` tokens.  Returns the decoded strings, in prompt order, and
-    prints each sequence's budget line as ``generate`` prints it.
+    """``generate`` for several prompts of different lengths: every prompt is prefilled ALONE through :func:`_prefill`, as
+    ``generate`` does it (all modes keep the reference's geometry), its bank becomes one sequence of a :class:`KVBankBatch`, and the
+    decode phase then runs ONE model forward per token for all live sequences — ``input_ids [B', 1]``, ``position_ids [B', 1]`` with
+    each sequence's own position, one batched library step per layer.  Each sequence's plan comes from its own
+    :class:`DecodePlanner` (it evicts when ITS length exceeds ITS budget, ``score_off`` = ITS prompt length, recency / random ranges
+    per sequence) and a sequence leaves the batch when it samples an EOS or has been fed ``max_new_tokens`` tokens.  Returns the
+    decoded strings, in prompt order, and prints each sequence's budget line as ``generate`` prints it.
 
     Sampling: ``torch.multinomial`` draws for all live sequences at once, so with ``temperature`` / ``top_p`` that leave more than
     one candidate the global generator is consumed differently from B solo runs; ``kv_policy='random'`` draws once per sequence
@@ -774,91 +807,56 @@ def generate_batch(self, input_ids_list, generation_config, kv_mode="encoding", 
     if getattr(self, "layer_shard", None) is not None and self.layer_shard.world > 1:
         raise ValueError("generate_batch is not supported on a layer-sharded model (model.layer_shard)")
     prompts = [p.view(1, -1) if p.dim() == 1 else p for p in input_ids_list]
-    from . import _lib
     if not 1 <= len(prompts) <= _lib.MAX_SEQS or any(p.dim() != 2 or p.shape[0] != 1 for p in prompts):
         raise ValueError(f"generate_batch takes 1..{_lib.MAX_SEQS} prompts of shape [S] or [1, S]")
-    temperature, top_p = cfg.get("temperature", 1.0), cfg.get("top_p", 1.0)
-    max_new_tokens = cfg.get("max_new_tokens", 1024)
-    policy, sink = cfg.get("kv_policy", "recency"), cfg.get("temp_length", 4)
-    eos = set(int(e) for e in cfg.get("eos_token_ids", [self.tokenizer.eos_token_id]))
-    record = cfg.get("_record_evictions", False)
-    scored = policy in SCORED
-    evicting = policy in KNOWN_POLICIES and policy != "full"
-    dev = torch.device(self.device)
+    run = _Run(self, cfg, kv_mode, stride, prompts)
+    eos, dev, max_new_tokens = set(int(e) for e in run.eos_token_ids), run.dev, run.max_new_tokens
 
     # ---- every prompt alone, through the single-sequence prefill; its bank becomes one sequence of the batch
-    seqs = [generate(self, p, cfg, kv_mode=kv_mode, stride=stride, _stop_before_decode=True) for p in prompts]
-    first = seqs[0]["cache"].bank
-    bat = KVBankBatch(len(seqs), first.n_layers, first.n_q_heads, first.n_kv_heads, first.head_dim, max(s["cache"].bank.cap for s in seqs),
+    seqs = [_prefill(run, p, kv_mode) for p in prompts]
+    first = seqs[0].cache.bank
+    bat = KVBankBatch(len(seqs), first.n_layers, first.n_q_heads, first.n_kv_heads, first.head_dim, max(s.cache.bank.cap for s in seqs),
                       device=dev, dtype=first.dtype)
-    cache = BudgetedKVCacheBatch(bat, record=record)
+    cache = BudgetedKVCacheBatch(bat, record=run.record)
     for i, s in enumerate(seqs):
-        bat.adopt(i, s["cache"].bank)
-        cache.evictions[i] = s["cache"].evictions      # (the prefill's own evictions come first)
-        s.update(cache=None, out_ids=[], positions=[], cur_pos=s["length"], by_eos=False)
-    cache.prefill_len = [s["length"] for s in seqs]
+        bat.adopt(i, s.cache.bank)
+        cache.evictions[i] = s.cache.evictions      # (the prefill's own evictions come first)
+        s.cache = None
+    out_ids, by_eos = [[] for _ in seqs], [False] * len(seqs)
 
     # ---- the decode phase: one forward per token for all live sequences
     live = list(range(len(seqs))) if max_new_tokens > 0 else []
     while live:
-        prob, _ = logits_adapter(torch.cat([seqs[i]["logits"] for i in live]).float(), temperature, top_p)
-        tok = torch.multinomial(prob, num_samples=1)                      # [B', 1]
-        fed, plans = [], []
+        tok = run.sample(torch.cat([seqs[i].logits for i in live]))       # [B', 1]
+        rows, now, plans, pos = [], [], [], []
         for row, t in enumerate(tok.view(-1).tolist()):                   # (the one host sync of the step: the EOS test, easykv.py:257-263)
-            s = seqs[live[row]]
-            s["out_ids"].append(t)
+            i = live[row]
+            out_ids[i].append(t)
             if t in eos:
-                s["by_eos"] = True
+                by_eos[i] = True
                 continue
-            fed.append((row, live[row]))
-        for row, i in fed:      # the plan of each sequence, as decode_loop builds it for one
-            s = seqs[i]
-            if s["mode"] == "encoding":      # :508-526 plain decode, no eviction
-                plans.append(StepPlan(policy="full", phase="decode", accumulate=False))
-                continue
-            t_now = bat.n_slots(i) + 1
-            evict = evicting and (s["whole"] or (t_now - s["score_off"]) > s["budget_d"])
-            plan = StepPlan(policy=policy, phase="decode", accumulate=scored, evict=evict, score_off=s["score_off"], budget=s["budget_d"])
-            s["positions"].append(s["cur_pos"])
-            if evict and policy in ("recency", "random"):
-                if s["whole"]:
-                    if policy == "random":
-                        raise UnboundLocalError("auto mode + kv_policy='random' is broken in the reference (easykv/easykv.py:744)")
-                    plan.range_start = sink
-                else:
-                    e = 0 if policy == "recency" else int(torch.topk(torch.rand(len(s["positions"])), k=1, dim=-1)[1][0])
-                    s["positions"].pop(e)
-                    plan.range_start = s["score_off"] + e
-            plans.append(plan)
-        if not fed:
+            rows.append(row)
+            now.append(i)
+            pos.append(seqs[i].planner.cur_pos)
+            plans.append(seqs[i].planner.step(bat.n_slots(i)))
+        if not now:
             break
-        rows = torch.as_tensor([r for r, _ in fed], device=dev)
-        now = [i for _, i in fed]
-        pos = torch.as_tensor([seqs[i]["cur_pos"] for i in now], dtype=torch.long, device=dev).view(-1, 1)
+        pos = torch.as_tensor(pos, dtype=torch.long, device=dev).view(-1, 1)
         with cache.active(plans, now, pos):
-            out = self(input_ids=tok[rows].view(-1, 1), past_key_values=cache, position_ids=pos, use_cache=True)
+            out = self(input_ids=tok[torch.as_tensor(rows, device=dev)].view(-1, 1), past_key_values=cache, position_ids=pos, use_cache=True)
         if cache.n_attend != bat.n_layers:
             raise RuntimeError(f"model forward made {cache.n_attend} batched attend() calls for {bat.n_layers} layers: route every "
                                "attention layer through past_key_values.attend (easykv_amd.hf.patch_model for HF models)")
-        live = []
         for row, i in enumerate(now):
-            s = seqs[i]
-            s["logits"] = out.logits[row:row + 1, -1, :]
-            s["cur_pos"] += 1
-            if len(s["out_ids"]) < max_new_tokens:
-                live.append(i)
+            seqs[i].logits = out.logits[row:row + 1, -1, :]
+        live = [i for i in now if len(out_ids[i]) < max_new_tokens]
 
     results = []
     for i, s in enumerate(seqs):
-        n_out = len(s["out_ids"])
-        fed_n = n_out - 1 if s["by_eos"] else n_out
-        if s["mode"] == "decoding":
-            kept = min(fed_n, s["budget_d"]) if evicting else fed_n
-            print(f"KV cache budget ratio: {kept / n_out * 100:.2f}%({kept}/{n_out})")
-        elif s["mode"] == "auto":
-            size = bat.n_slots(i)
-            print(f"KV Cache Budget ratio {size / (s['length'] + n_out) * 100:.2f}%[{size}/({s['length']}+{n_out})]")
-        results.append(self.tokenizer.decode(s["out_ids"], skip_special_tokens=True).strip())
+        n_out = len(out_ids[i])
+        if s.mode != "encoding":
+            _print_budget_line(s.mode, s.length, bat.n_slots(i), n_out, n_out - 1 if by_eos[i] else n_out, s.planner.budget_d if run.evicting else None)
+        results.append(self.tokenizer.decode(out_ids[i], skip_special_tokens=True).strip())
     return (results, cache) if return_cache else results
 
 
