@@ -54,12 +54,13 @@ def instances():
 
 
 def sources():
-    return sorted(glob.glob(os.path.join(CSRC, "*.hip")))
+    """The library's own translation units: the .hip files, and the host-only planner (plain C++: no -x hip, no device pass)."""
+    return sorted(glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.cpp")))
 
 
 def objects():
-    """(object name, hipcc arguments that select its source) of everything in the library: the .hip files and the manifest's instances."""
-    objs = [(os.path.basename(src)[:-4], [src]) for src in sources()]
+    """(object name, hipcc arguments that select its source) of everything in the library: its own files and the manifest's instances."""
+    objs = [(os.path.splitext(os.path.basename(src))[0], [src]) for src in sources()]
     for fam, words in instances():
         inc, name, defs = FAMILIES[fam](*words)
         objs.append((name, defs + ["-x", "hip", os.path.join(CSRC, inc)]))

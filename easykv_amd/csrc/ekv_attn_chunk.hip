@@ -1,4 +1,4 @@
-// head_dim dispatch and query-block planning of the chunk (q_len > 1) attention kernels.
+// head_dim dispatch of the chunk (q_len > 1) attention kernels (which kernel and scheme a step takes: ekv_plan.cpp).
 #include <cstdlib>
 
 #include "ekv_common.h"
@@ -7,10 +7,9 @@
 // ---- the instances (ekv_instances.def): launcher declarations, then one table entry per line
 typedef hipError_t EkvChunkFn(const EkvAttnArgs&, int shape, int layer_count, hipStream_t, const EkvScoreArgs*);
 typedef hipError_t EkvStepFn(const EkvAttnArgs&, const EkvScoreArgs&, int layer_count, hipStream_t);
-typedef size_t EkvLdsBytesFn(int, int, int);
 #define EKV_CHUNK(d, m, elem) EkvChunkFn EKV_FN_CHUNK(d, m, elem);
 #define EKV_WIDE(d, m, keys, elem) EkvChunkFn EKV_FN_WIDE(d, m, keys, elem);
-#define EKV_CHUNK_LDS(d, elem) EkvStepFn EKV_FN_D_ELEM(ekv_launch_chunk_lds, d, elem); EkvLdsBytesFn ekv_chunk_lds_bytes_d##d;
+#define EKV_CHUNK_LDS(d, elem) EkvStepFn EKV_FN_D_ELEM(ekv_launch_chunk_lds, d, elem);
 #define EKV_RESIDENT(d, elem) EkvStepFn EKV_FN_D_ELEM(ekv_launch_attn_resident, d, elem);
 #include "ekv_instances.def"
 
@@ -26,16 +25,15 @@ const ChunkInstance kChunk[] = {
 #define EKV_WIDE(d, m, keys, elem) {true, d, m, EKV_IS_##keys, EKV_IS_##elem, EKV_FN_WIDE(d, m, keys, elem)},
 #include "ekv_instances.def"
 };
-struct StepInstance {      // whole-step kernels: logits in LDS (with its LDS plan), logits-resident
+struct StepInstance {      // whole-step kernels: logits in LDS, logits-resident
   bool resident;
   int head_dim;
   bool bf16;
   EkvStepFn* fn;
-  EkvLdsBytesFn* lds_bytes;
 };
 const StepInstance kStep[] = {
-#define EKV_CHUNK_LDS(d, elem) {false, d, EKV_IS_##elem, EKV_FN_D_ELEM(ekv_launch_chunk_lds, d, elem), ekv_chunk_lds_bytes_d##d},
-#define EKV_RESIDENT(d, elem) {true, d, EKV_IS_##elem, EKV_FN_D_ELEM(ekv_launch_attn_resident, d, elem), nullptr},
+#define EKV_CHUNK_LDS(d, elem) {false, d, EKV_IS_##elem, EKV_FN_D_ELEM(ekv_launch_chunk_lds, d, elem)},
+#define EKV_RESIDENT(d, elem) {true, d, EKV_IS_##elem, EKV_FN_D_ELEM(ekv_launch_attn_resident, d, elem)},
 #include "ekv_instances.def"
 };
 
@@ -50,57 +48,6 @@ const StepInstance* step_instance(bool resident, int head_dim, bool bf16) {
   return nullptr;
 }
 }  // namespace
-
-// Two-pass scheme (16x16 kernel: statistics pass + exact pass with in-kernel column sums, ekv_attn_chunk.inc; wide-block kernel: one
-// pass for output + row statistics, then a K-only column-sum pass, ekv_attn_wide.inc) for scored chunk
-// steps.  It trades one extra read of K (and a third MFMA product) for the rep x n x T logits never touching HBM: at rep*n = 96
-// the logits are 384 B per key against 512 B of K + V, written once and read once.  Measured on MI355X (docs/TUNING.md §8): in
-// round 1 the one-pass path won at every BASELINE shape (C4 1.89 vs 2.31 ms); with the round-2 instruction diet of the MFMA
-// kernel the two passes win from ~40 query rows up (C4: 1.17 vs 1.48 ms per step, stride 64: 0.43 vs 0.49), so `auto` picks
-// them there.  Not with rope-on-read (every product is three MFMAs on the hi/lo pairs: C5 1.98 vs 2.59 ms).
-// ekv_step.two_pass = 1 / -1 selects a scheme explicitly (every golden case runs under both).  tova needs the last query row
-// itself, not column sums, and always uses the one-pass kernel.
-// Round 4: with rope-on-read the two passes run on the wide-block kernel's RoPE variants (head_dim 64 / 128: K rotated in LDS, no
-// logits in HBM) from the same 40 rows; head_dim 32 keeps the one-pass 16x16 kernel.
-bool ekv_chunk_two_pass(int head_dim, int rep, int q_len, int policy, bool scored, bool accumulate, bool rope, int mode) {
-  const bool rep_ok = rep == 1 || rep == 2 || rep == 4 || rep == 8 || rep == 16;   // rep query heads share a 16-lane row
-  const bool can = q_len > 1 && scored && accumulate && policy != EKV_POLICY_TOVA && rep_ok;
-  if (!can || mode < 0) return false;
-  // measured crossover: 32 rows 0.34 (one pass) vs 0.36 ms, 48 rows 0.42 vs 0.41 ms.  RoPE-on-read steps keep the two passes too (round 5,
-  // end): with the logits exported by the wide kernel's one pass and swept by the scorer, a configs[4] step is 2190 vs 2205 us
-  return mode > 0 || ((!rope || head_dim == 64 || head_dim == 128) && rep * q_len >= 40);
-}
-
-bool ekv_attn_chunk_supported(int head_dim, int rep, int q_len) {
-  return (head_dim == 32 || head_dim == 64 || head_dim == 96 || head_dim == 128) && rep >= 1 && rep <= 128 && q_len >= 1;
-}
-
-// A query block is <= 128 GQA-folded rows (rep x qb_rows).  qpw = 1 or 2: 16-row query tiles per wave of a 4-wave
-// workgroup (<= 32 / <= 64 rows); qpw = 4 selects the 8-wave workgroup (2 tiles per wave x 4 query-tile waves, <= 128 rows).
-void ekv_chunk_blocks(int rep, int q_len, int* qb_rows, int* n_qblocks, int* qpw) {
-  int rows = q_len;
-  if (rep * q_len > 128) rows = 128 / rep > 0 ? 128 / rep : 1;   // (64-row blocks on 4-wave workgroups: 324 vs 378 TFLOP/s on the dense prefix)
-  // (65..128 rows stay ONE block on the 8-wave workgroup: two 4-wave blocks of <= 64 rows, even XCD-local so that the second K/V
-  // read is an L2 hit, measured 1.55 vs 1.19 ms per C4 step)
-  *qb_rows = rows;
-  *n_qblocks = (q_len + rows - 1) / rows;
-  const int r = rep * rows;
-  *qpw = r <= 32 ? 1 : (r <= 64 ? 2 : 4);
-}
-
-// Wide query blocks (33..128 GQA-folded rows) run on the 32x32x16 kernel of ekv_attn_wide.inc: the dense prefix and every wide
-// strided chunk step are bound by the MFMA kernel itself, not by HBM (docs/TUNING.md §3.5).  EKV_NO_WIDE=1 in the environment keeps
-// the 16x16x32 kernel (A/B measurements on one box).
-bool ekv_chunk_wide(int head_dim, int rep, int q_len, bool rope, bool two_pass, bool wants_logits) {
-  static const bool off = [] { const char* e = std::getenv("EKV_NO_WIDE"); return e != nullptr && e[0] == '1'; }();
-  if (off || q_len < 2 || (head_dim != 64 && head_dim != 128)) return false;
-  int qb_rows, n_qblocks, qpw;
-  ekv_chunk_blocks(rep, q_len, &qb_rows, &n_qblocks, &qpw);
-  if (qpw < 2) return false;                                  // <= 32 rows: HBM-bound shapes, the small-tile kernels
-  if (two_pass) return rep == 1 || rep == 2 || rep == 4 || rep == 8 || rep == 16;   // the column-sum pass folds the rep query heads in registers
-  // only the RoPE builds export logits, and only for single-block steps (every key of the range is visited) of a power-of-two GQA factor
-  return !wants_logits || (rope && n_qblocks == 1 && (rep == 1 || rep == 2 || rep == 4 || rep == 8 || rep == 16));
-}
 
 // rope_on_read: q' = q*cos[pos] + rotate_half(q)*sin[pos] with pos = T - n + i (llama_patch.py:311, :326), once per step,
 // stored as an fp16 pair hi + lo (q' is an fp32 product; hi alone would cost ~5e-4 relative on the logits).
@@ -134,25 +81,8 @@ __global__ void __launch_bounds__(256) ekv_rope_q_kernel(const EkvAttnArgs a, in
 // column-sum partial rows, which costs the scorer more than the attention kernel gains (C4 step 1.16 -> 1.25 ms, measured).
 static int kernel_code(int qpw, bool rope, int mode) { return (qpw == 4 && !rope && mode == 0) ? 8 : qpw; }
 
-// partial column-sum rows the exact pass writes per (head, query block) = its query-tile waves
-int ekv_chunk_col_parts(int qpw, bool rope) { (void)rope; return qpw == 4 ? 4 : 2; }
-
 // fuse_sc != nullptr: one-pass step with unsplit heads whose scorer runs as the tail of the attention kernel (no second launch)
-// The scorer as the tail of the wide column-sum pass holds the score rows of a head in registers (24 columns per thread of a
-// 256-thread workgroup) and the selection keys in the pass's tile buffers; only heads whose column sums come from ONE workgroup
-// (a last-arriver election for split heads was built and measured slower than the stand-alone scorer: ekv_wide_tail.h)
-bool ekv_wide_tail_supported(int W, int n_wg) {
-  static const bool off = [] { const char* e = std::getenv("EKV_NO_WIDE_TAIL"); return e != nullptr && e[0] == '1'; }();     // (A/B switch)
-  return !off && W >= 1 && W <= 24 * 256 && n_wg == 1;
-}
-
-// Kernel launches of ekv_launch_attn_chunk below for the same arguments: the query rotation of the 16x16 RoPE path, one launch per
-// pass of the wide kernel (`passes` bits), two for the 16x16 two-pass scheme.  Keep next to the launch code.
-int ekv_attn_chunk_launches(bool wide, bool rope, bool two_pass, int passes) {
-  if (wide) return ((passes & 1) ? 1 : 0) + ((two_pass && (passes & 2)) ? 1 : 0);
-  return (rope ? 1 : 0) + (two_pass ? 2 : 1);
-}
-
+// (kernel launches per call: ekv_attn_chunk_launches, ekv_plan.cpp)
 hipError_t ekv_launch_attn_chunk(const EkvAttnArgs& a, int head_dim, int layer_count, bool wide, bool two_pass, hipStream_t s,
                                  const EkvScoreArgs* fuse_sc, int passes, const EkvScoreArgs* tail_sc, bool bf16) {
   if (two_pass && (fuse_sc != nullptr || a.stats == nullptr || a.colsum == nullptr)) return hipErrorInvalidValue;
@@ -202,24 +132,12 @@ hipError_t ekv_launch_attn_chunk(const EkvAttnArgs& a, int head_dim, int layer_c
 }
 
 // ---- small-row chunk step with the logits in LDS (ekv_chunk_lds.inc) -------------------------------------------------------
-// Eligible: a scored, accumulating chunk step (plain keys, score rows over the whole cache) with at most 8 GQA-folded query
-// rows whose logits fit LDS next to a second workgroup of the CU (<= 80 KB), one victim set per head.
-bool ekv_chunk_lds_supported(const ekv_bank* bank, const ekv_step* st, int phys_extent, bool scored) {
-  const int rep = bank->n_q_heads / bank->n_kv_heads;
-  if (st->q_len < 2 || rep * st->q_len > 8 || (rep & (rep - 1)) != 0 || !scored || !st->accumulate || st->rope_on_read || st->score_off != 0) return false;
-  if (st->phases != 0 || st->n_split == -1 || st->two_pass != 0 || !st->causal) return false;   // (two_pass = -1: "exported logits")
-  if (st->policy == EKV_POLICY_TOVA && st->tova_head_mean) return false;   // needs every head of the layer first
-  if (st->n_slots > 10 * 256 || st->n_evict >= st->n_slots || st->n_evict > 16) return false;
-  const StepInstance* in = step_instance(false, bank->head_dim, false);
-  return in != nullptr && in->lds_bytes(rep * st->q_len, phys_extent, st->n_slots) <= 80 * 1024;
-}
-
 hipError_t ekv_launch_chunk_lds(const EkvAttnArgs& a, const EkvScoreArgs& sc, int head_dim, int layer_count, hipStream_t s, bool bf16) {
   const StepInstance* in = step_instance(false, head_dim, bf16);
   return in ? in->fn(a, sc, layer_count, s) : hipErrorInvalidValue;
 }
 
-// ---- logits-resident scored chunk step (ekv_attn_resident.inc; ekv_attn_resident_supported lives next to the kernel's geometry)
+// ---- logits-resident scored chunk step (ekv_attn_resident.inc)
 hipError_t ekv_launch_attn_resident(const EkvAttnArgs& a, const EkvScoreArgs& sc, int layer_count, hipStream_t s, bool bf16) {
   const StepInstance* in = step_instance(true, sc.head_dim, bf16);
   return in ? in->fn(a, sc, layer_count, s) : hipErrorInvalidValue;

@@ -42,7 +42,6 @@
 #define EKV_SS_NT 256
 #define EKV_SS_DEVICE_ONLY
 #include "ekv_score_select.inc"
-size_t ekv_score_lds_bytes_nt256(const EkvScoreArgs&);
 #endif
 
 // P operand of the PV product: one fp16 per probability (what the reference's own GPU path multiplies with: softmax(...).to(fp16),
@@ -699,7 +698,7 @@ hipError_t launch_k(const EkvAttnArgs& a, int layer_count, hipStream_t s, const 
 #if EKV_CHUNK_MODE == 0
   if (fuse_sc != nullptr) {
     if (NW != 4 || a.n_split != 1 || a.n_qblocks != 1 || a.out_direct == nullptr) return hipErrorInvalidValue;
-    lds = std::max(lds, ekv_score_lds_bytes_nt256(*fuse_sc));
+    lds = std::max(lds, ekv_score_lds_bytes(256, *fuse_sc));
     if (lds > 48 * 1024)
       (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ekv_attn_chunk_kernel<QPW, ROPE, 4, true>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);

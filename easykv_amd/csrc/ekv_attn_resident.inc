@@ -57,28 +57,7 @@ typedef short ekr_s4 __attribute__((ext_vector_type(4)));
 typedef float ekr_f4 __attribute__((ext_vector_type(4)));
 typedef ekv_e ekr_h4 __attribute__((ext_vector_type(4)));
 
-constexpr int R_D = 128, R_NT = 512, R_TK = 128, R_NB = 3, R_MAXT = 10;      // R_MAXT: 32 x 32 logit blocks a wave keeps (160 registers)
-constexpr int R_RS = 2 * R_D;                         // bytes per K / V row in LDS (unpadded, XOR-swizzled 16-byte chunks)
-constexpr int R_TBUF = R_TK * R_RS;                   // 32 KB per ring slot
-// Two shapes of the same kernel (the 320 KB of accumulator registers hold either):
-//   LONG = false  up to 64 rows x 1280 keys: query-wave group wq owns rows wq*32 .. +32 of EVERY tile
-//   LONG = true   up to 32 rows x 2560 keys: both groups hold rows 0 .. 31, group wq owns the tiles t with (t & 1) == wq; the V pass
-//                 splits a tile's keys over the two groups and their O^T blocks are added once at the end
-template <bool LONG>
-struct RL {
-  static constexpr int TILES = LONG ? 2 * R_MAXT : R_MAXT, TMAX = TILES * R_TK;
-  static constexpr int PSTR = LONG ? 80 : 144;        // bytes per key row of a P^T tile: 32 / 64 queries x fp16 + 16 (an odd multiple of 16: conflict-free writes and transposing reads)
-  static constexpr int PBUF = R_TK * PSTR;
-  static constexpr int OFF_P = R_NB * R_TBUF;         // P^T tiles [2][128][PSTR]; LONG = false, behind the V pass: the query waves' column-sum exchange
-  static constexpr int OFF_SLOT = OFF_P + 2 * PBUF;   // slot-map entries of the head's cache rows [TMAX]
-  static constexpr int OFF_CS = OFF_SLOT + TMAX * 4;  // column sums [2][TMAX]
-  static constexpr int OFF_RED = OFF_CS + 2 * TMAX * 4;   // row maxima [rows][NSH], row sums [rows][NSH] (256 words each), 1 / L [64]
-  static constexpr int LDS = OFF_RED + (256 + 256 + 64) * 4;
-  static constexpr int NSH = LONG ? 8 : 4;            // shares of a row's statistics: the waves that hold keys of the row
-  static constexpr int TI = (TMAX + R_NT - 1) / R_NT; // score columns per thread of the scorer
-  static_assert(LDS <= 160 * 1024, "one workgroup per CU");
-  static_assert(2 * TMAX * 4 <= 2 * PBUF || LONG, "the column-sum exchange fits the P^T tile buffers");
-};
+// (R_* and the two LDS layouts RL<LONG> of the kernel: ekv_geometry.h)
 
 // 16 bytes per lane global -> LDS (global_load_lds_dwordx4): lds_dst = wave-uniform base of a 1 KB piece, lane i lands at + 16 * i.
 // By inline asm (cdna_hip_programming.md §5.7: M0 written in the statement that reads it), NOT the builtin: hipcc models the builtin
@@ -533,17 +512,3 @@ hipError_t launch_resident_any(const EkvAttnArgs& a, const EkvScoreArgs& sc, int
 hipError_t EKV_FN_D_ELEM(ekv_launch_attn_resident, 128, EKV_ELEM)(const EkvAttnArgs& a, const EkvScoreArgs& sc, int layer_count, hipStream_t s) {
   return launch_resident_any(a, sc, layer_count, s);
 }
-
-#if !EKV_BF16   // (the eligibility rule does not depend on the element type)
-// Which steps: a whole scored chunk step (roco / h2o_head, accumulating) of an unsplit head on plain keys, head_dim 128, GQA factor
-// 1 / 2 / 4 / 8, 9..64 folded rows in one query block (fewer: the logits-in-LDS kernel) against at most 1280 keys, or at most 32 rows against
-// at most 2560 keys.
-bool ekv_attn_resident_supported(int head_dim, int rep, int q_len, int n_slots, int W) {
-  static const bool off = [] { const char* e = std::getenv("EKV_NO_RESIDENT"); return e != nullptr && e[0] == '1'; }();     // (A/B switch)
-  static const int min_rows = [] { const char* e = std::getenv("EKV_RESIDENT_MIN_ROWS"); return e != nullptr ? std::atoi(e) : 9; }();      // (A/B switch; see the header)
-  const int rows = rep * q_len;
-  const bool shape = (rows <= 64 && n_slots <= RL<false>::TMAX) || (rows <= 32 && n_slots <= RL<true>::TMAX);      // (LONG = false / true)
-  return !off && head_dim == R_D && (rep == 1 || rep == 2 || rep == 4 || rep == 8) && rows >= min_rows && shape && n_slots >= q_len && W >= 1 &&
-         W <= n_slots && ekw_tail_lds_bytes(W) <= (size_t)RL<false>::OFF_P;
-}
-#endif

@@ -1008,7 +1008,7 @@ hipError_t launch_wide(const EkvAttnArgs& a, int layer_count, hipStream_t s, con
 #if EKW_HAS_TAIL
   if (a.score_tail) {
     if (tail == nullptr) return hipErrorInvalidValue;
-    lds = std::max(lds, ekw_tail_lds_bytes(tail->n_slots - tail->score_off));      // (the tail's keys + select scratch alias the tile buffers)
+    lds = std::max(lds, ekw_tail_lds_bytes(kNT, tail->n_slots - tail->score_off));      // (the tail's keys + select scratch alias the tile buffers)
   }
 #endif
   const EkvScoreArgs sc = (MODE == 2 && tail != nullptr) ? *tail : EkvScoreArgs{};

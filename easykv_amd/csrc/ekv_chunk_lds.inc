@@ -61,31 +61,8 @@ typedef float ekv_f2 __attribute__((ext_vector_type(2)));
 // loads + 32 accumulators (phase B) per lane in flight (a scratch reload inside a stream loop waits for every
 // load issued before it: vmcnt retires in order).  8-wave workgroups at 128 registers were tried: they need the query rows split
 // between wave groups in phase B (V fetched twice) and were slower in BOTH stream phases.
-constexpr int kLNW = 4, kLNT = 64 * kLNW;   // waves / threads per workgroup
-constexpr int kLItems = 10;                 // owned columns per thread: score rows up to 10 * 256 = 2560 positions
-constexpr int kListCap = 256;               // candidate list of the select (entries)
+constexpr int kLNT = 64 * kLNW;            // threads per workgroup (kLNW, kLItems, kListCap and the LDS plan ekv_lds_plan: ekv_geometry.h)
 constexpr unsigned kLdsResident = 512;      // workgroups resident at a time on an MI355X: 256 CUs x 2 (LDS)
-
-struct LdsPlan {
-  size_t e_bytes, key_off, stat_off, red_off, hist_off, dead_off, total;
-};
-// LDS: logits / probabilities [E16 + 16 keys][NQ] fp32 (the last 16 "keys" are the chunk's own) | keys of the fallback select |
-// row statistics + their reduction scratch | block-reduction scratch | select histogram + candidate list | dead-row bits
-template <int D, int NQ>
-__host__ __device__ inline LdsPlan ekv_lds_plan(int e16, int W) {
-  LdsPlan p;
-  const size_t logits = (size_t)(e16 + 16) * NQ * 4;
-  const size_t oscr = (size_t)kLNW * NQ * D * 4;   // cross-wave output reduction, aliases the (dead) logits at the very end
-  p.e_bytes = ekv_align(logits > oscr ? logits : oscr, 16);
-  p.key_off = p.e_bytes;
-  const size_t stage = (size_t)kLNW * (D >= 128 ? 8 : 64 / (D / 8)) * D * 2;   // phase A's per-wave staging tiles (8 or G rows) alias the fallback select's key array
-  p.stat_off = p.key_off + ekv_align((size_t)W * 4 > stage ? (size_t)W * 4 : stage, 16);
-  p.red_off = p.stat_off + (2 * 16 + 2 * kLNW * 8) * 4;
-  p.hist_off = p.red_off + 2 * kLNW * 8 * 2;
-  p.dead_off = p.hist_off + 264 * 4 + kListCap * 8;
-  p.total = p.dead_off + ekv_align((size_t)(e16 / 32 + 2) * 4, 16);
-  return p;
-}
 
 // Exclusive threshold `thr` on UNIQUE 64-bit composites ((order-preserving key) << 32 | position) such that exactly k of the
 // workgroup's composites lie below it — "the k smallest keys, ties to the lower position" — or 0 when the fast path does not
@@ -1096,16 +1073,6 @@ hipError_t launch_lds(const EkvAttnArgs& a, const EkvScoreArgs& sc, int layer_co
 }
 
 }  // namespace
-
-#define EKV_LCAT_(a, b) a##b
-#define EKV_LCAT(a, b) EKV_LCAT_(a, b)
-
-#if !EKV_BF16   // (the LDS plan does not depend on the element type)
-size_t EKV_LCAT(ekv_chunk_lds_bytes_d, EKV_D)(int rows, int phys_extent, int n_slots) {
-  const int e16 = (phys_extent + 15) & ~15;
-  return rows <= 4 ? ekv_lds_plan<EKV_D, 4>(e16, n_slots).total : ekv_lds_plan<EKV_D, 8>(e16, n_slots).total;
-}
-#endif
 
 hipError_t EKV_FN_D_ELEM(ekv_launch_chunk_lds, EKV_D, EKV_ELEM)(const EkvAttnArgs& a, const EkvScoreArgs& sc, int layer_count, hipStream_t s) {
   const int rows = (a.n_q_heads / a.n_kv_heads) * a.q_len;

@@ -4,6 +4,8 @@
 #include <hip/hip_fp16.h>
 #include <stdint.h>
 
+#include "ekv_geometry.h"      // (ekv_align and the families' LDS plans)
+
 #define EKV_WAVE 64
 #define EKV_LOG2E 1.4426950408889634f
 #define EKV_NEG_INF (-__builtin_inff())
@@ -292,5 +294,3 @@ __device__ __forceinline__ void ekv_lds_barrier() {
   __builtin_amdgcn_s_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
 }
-
-static inline __host__ __device__ size_t ekv_align(size_t x, size_t a) { return (x + a - 1) / a * a; }

@@ -17,11 +17,7 @@
 
 namespace {
 
-#ifndef EKV_SCORE_NW
-#define EKV_SCORE_NW 8
-#endif
-constexpr int kSNW = EKV_SCORE_NW, kSNT = 64 * kSNW;   // waves / threads per scorer workgroup
-
+// (kSNW waves / kSNT threads per scorer workgroup and the LDS plan ekv_decode_score_lds: ekv_geometry.h)
 template <int REP, int ITEMS>
 __global__ void __launch_bounds__(kSNT) ekv_decode_score_kernel(const EkvScoreArgs EKV_ARG_SC EKV_TB_PARAM) {
   EKV_SHADOW_SC(blockIdx.y)
@@ -90,14 +86,9 @@ __global__ void __launch_bounds__(128) ekv_fold_kernel(const EkvScoreArgs sc) {
 
 #endif
 
-size_t score_lds(int rep, int t_pad, int policy) {
-  const size_t n_state = policy == EKV_POLICY_ROCO ? 3 : 1;
-  return ((size_t)rep * t_pad + n_state * ekv_align((size_t)t_pad, 256)) * 4 + 2 * kSNW * 8 * 8 + 264 * 4 + kSNT * 8;
-}
-
 template <int REP, int ITEMS>
 hipError_t launch_k(const EkvScoreArgs& sc EKV_TB_DECL, int layer_count, hipStream_t s) {
-  const size_t lds = score_lds(REP, sc.t_pad, sc.policy);
+  const size_t lds = ekv_decode_score_lds(REP, sc.t_pad, sc.policy);
   if (lds > 48 * 1024)
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ekv_decode_score_kernel<REP, ITEMS>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -138,13 +129,4 @@ hipError_t EKV_FN_DECODE_SCORE(ekv_launch_decode_score, EKV_ELEM, EKV_BATCHING)(
 
 #if !EKV_BATCH
 hipError_t EKV_FN_ELEM(ekv_launch_fold, EKV_ELEM)(const EkvScoreArgs& sc, int layer_count, hipStream_t s) { return launch_fold(sc, layer_count, s); }
-#endif
-
-#if !EKV_BATCH && !EKV_BF16   // (the LDS plan does not depend on the element type)
-bool ekv_decode_score_supported(const EkvScoreArgs& sc) {
-  const int rep = sc.n_q_heads / sc.n_kv_heads;
-  if (sc.q_len != 1 || sc.n_evict > 1 || (sc.cap & 3) != 0 || sc.n_slots > 256 * 24) return false;
-  if (rep < 1 || rep > 8) return false;      // (wider GQA factors: the generic scorer)
-  return score_lds(rep <= 2 ? rep : (rep <= 4 ? 4 : 8), sc.t_pad, sc.policy) <= 150 * 1024;
-}
 #endif

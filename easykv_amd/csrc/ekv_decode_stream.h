@@ -9,40 +9,7 @@
 #include "ekv_common.h"
 #include "ekv_kernels.h"
 
-constexpr int kU = 8;   // rows in flight per lane group (K and V each)
-
-// head_dim 96 (any head_dim that is a multiple of 16 but not a power of two): a row keeps a power-of-two lane group (LPR = 16) of
-// which only the first LIVE = D / 8 lanes hold a 16-byte piece; the idle lanes carry zeros through the dot products and reductions.
-// EPL = elements per 16-byte piece: 8 (16-bit rows) or 16 (FP8 rows, "kv8": a head_dim-128 row is 8 lanes, head_dim 64 is 4).
-template <int D, int NW = 4, int KU = kU, int EPL = 8>
-struct EkvDecodeGeom {
-  static constexpr int LIVE = D / EPL;  // lanes of a row's lane group that hold a 16-byte piece
-  static constexpr int LPR = LIVE <= 4 ? 4 : (LIVE <= 8 ? 8 : 16);   // lanes per row (power of two)
-  static constexpr int G = 64 / LPR;  // rows per wave-load
-  static constexpr int RW = G * KU;   // rows per wave per iteration
-  static constexpr int NP = NW;       // partials per workgroup = waves (lane groups are combined in-wave)
-  static constexpr int PS = D + 2;    // (m, l, o[D])
-};
-
-// LDS bytes of the one-launch decode kernel (ekv_decode_fused_kernel, ekv_attn_decode.inc): host arithmetic over the geometry, the same
-// for every element type, row format and batching.  n_state = score rows kept in LDS (3 with roco on the ordered layout).
-template <int D, int REP, int NW = 8>
-inline size_t ekv_fused_lds(int t_pad, int l_pad, int n_state) {
-  using Gm = EkvDecodeGeom<D, NW>;
-  const size_t part = ekv_align((size_t)Gm::NP * REP * Gm::PS, 4);
-  return ((size_t)REP * l_pad + part + (size_t)n_state * ekv_align((size_t)t_pad, 256)) * 4 + 2 * NW * 8 * 8 +
-         ekv_align(ekv_align((size_t)l_pad, 128) / 8, 16) + 264 * 4;   // + one dead-row bit per physical row + select histogram
-}
-// ... of the widest build a step of GQA factor `rep` on nw-wave workgroups can need (the planner: ekv_decode_fused_supported)
-template <int D>
-inline size_t ekv_fused_lds_max(int rep, int t_pad, int l_pad, int nw) {
-  switch (rep) {
-    case 1: return nw == 8 ? ekv_fused_lds<D, 1, 8>(t_pad, l_pad, 3) : ekv_fused_lds<D, 1, 4>(t_pad, l_pad, 3);
-    case 2: return nw == 8 ? ekv_fused_lds<D, 2, 8>(t_pad, l_pad, 3) : ekv_fused_lds<D, 2, 4>(t_pad, l_pad, 3);
-    case 3: case 4: return nw == 8 ? ekv_fused_lds<D, 4, 8>(t_pad, l_pad, 3) : ekv_fused_lds<D, 4, 4>(t_pad, l_pad, 3);
-    default: return nw == 8 ? ekv_fused_lds<D, 8, 8>(t_pad, l_pad, 3) : ekv_fused_lds<D, 8, 4>(t_pad, l_pad, 3);
-  }
-}
+// EkvDecodeGeom, kU and the LDS bytes of the one-launch kernel (ekv_fused_lds): ekv_geometry.h
 
 // Streams positions [t0, t1) of KV head h.  SLOT_LDS: s_slot holds slot_of_pos[t0..t1) in LDS; otherwise s_slot is
 // the head's row of the global slot map (t0 must be a multiple of 8) and the 8 indices of a lane group are fetched

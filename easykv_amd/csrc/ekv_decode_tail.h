@@ -495,7 +495,7 @@ __device__ __forceinline__ void ekv_decode_tail(const EkvScoreArgs& sc, int ll, 
 // An eviction moves nothing: the victim's row goes to the front of the free list (slot_of_pos[T - 1], one word) and its S / Q / C0 /
 // birth die with it.  Ties go to the lower birth = the lower order index (same decisions as the ordered layout); windows that the
 // ordered layout states as index ranges — the newest `tail` entries — are birth thresholds, exact by a counting check with a
-// bisection fallback.  ekv_rows_to_slots / ekv_rows_to_order convert between the layouts (ekv_abi.hip).
+// bisection fallback.  ekv_rows_to_slots / ekv_rows_to_order convert between the layouts (ekv_bank_ops.hip).
 // Thread t owns rows t, t + NT, ...: every pass touches its own columns only, so the passes need no barrier between them.
 // S / Q are staged in LDS by LDS-DMA under the stream (like the ordered layout's rows); C0 and birth come straight into registers
 // (`cB`, `cC`: loads issued by the caller when its stream ends, consumed after the softmax passes) — a third and fourth LDS row

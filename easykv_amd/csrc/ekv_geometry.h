@@ -1,0 +1,159 @@
+// Geometry of the kernel families: the limits a family states and its LDS plan, in ONE place.  Plain C++17: the kernels and their
+// launchers include it for the layout they run on, the step planner (ekv_plan.cpp, host-only) for the byte counts and bounds it decides
+// on.  No intrinsics and no HIP type: includable from a translation unit that never sees hipcc.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#include "../../include/easykv_hip.h"
+
+#if defined(__HIP__)
+#define EKV_HD __host__ __device__
+#else
+#define EKV_HD
+#endif
+
+static inline EKV_HD size_t ekv_align(size_t x, size_t a) { return (x + a - 1) / a * a; }
+
+// ---- decode stream and the one-launch decode kernel (ekv_decode_stream.h, ekv_attn_decode.inc) -------------------------------------
+constexpr int kU = 8;   // rows in flight per lane group (K and V each)
+
+// head_dim 96 (any head_dim that is a multiple of 16 but not a power of two): a row keeps a power-of-two lane group (LPR = 16) of
+// which only the first LIVE = D / 8 lanes hold a 16-byte piece; the idle lanes carry zeros through the dot products and reductions.
+// EPL = elements per 16-byte piece: 8 (16-bit rows) or 16 (FP8 rows, "kv8": a head_dim-128 row is 8 lanes, head_dim 64 is 4).
+template <int D, int NW = 4, int KU = kU, int EPL = 8>
+struct EkvDecodeGeom {
+  static constexpr int LIVE = D / EPL;  // lanes of a row's lane group that hold a 16-byte piece
+  static constexpr int LPR = LIVE <= 4 ? 4 : (LIVE <= 8 ? 8 : 16);   // lanes per row (power of two)
+  static constexpr int G = 64 / LPR;  // rows per wave-load
+  static constexpr int RW = G * KU;   // rows per wave per iteration
+  static constexpr int NP = NW;       // partials per workgroup = waves (lane groups are combined in-wave)
+  static constexpr int PS = D + 2;    // (m, l, o[D])
+};
+
+// LDS bytes of the one-launch decode kernel (ekv_decode_fused_kernel, ekv_attn_decode.inc): host arithmetic over the geometry, the same
+// for every element type, row format and batching.  n_state = score rows kept in LDS (3 with roco on the ordered layout).
+template <int D, int REP, int NW = 8>
+inline size_t ekv_fused_lds(int t_pad, int l_pad, int n_state) {
+  using Gm = EkvDecodeGeom<D, NW>;
+  const size_t part = ekv_align((size_t)Gm::NP * REP * Gm::PS, 4);
+  return ((size_t)REP * l_pad + part + (size_t)n_state * ekv_align((size_t)t_pad, 256)) * 4 + 2 * NW * 8 * 8 +
+         ekv_align(ekv_align((size_t)l_pad, 128) / 8, 16) + 264 * 4;   // + one dead-row bit per physical row + select histogram
+}
+// ... of the widest build a step of GQA factor `rep` on nw-wave workgroups can need (the planner: ekv_decode_fused_supported)
+template <int D>
+inline size_t ekv_fused_lds_max(int rep, int t_pad, int l_pad, int nw) {
+  switch (rep) {
+    case 1: return nw == 8 ? ekv_fused_lds<D, 1, 8>(t_pad, l_pad, 3) : ekv_fused_lds<D, 1, 4>(t_pad, l_pad, 3);
+    case 2: return nw == 8 ? ekv_fused_lds<D, 2, 8>(t_pad, l_pad, 3) : ekv_fused_lds<D, 2, 4>(t_pad, l_pad, 3);
+    case 3: case 4: return nw == 8 ? ekv_fused_lds<D, 4, 8>(t_pad, l_pad, 3) : ekv_fused_lds<D, 4, 4>(t_pad, l_pad, 3);
+    default: return nw == 8 ? ekv_fused_lds<D, 8, 8>(t_pad, l_pad, 3) : ekv_fused_lds<D, 8, 4>(t_pad, l_pad, 3);
+  }
+}
+
+// ---- split-path decode scorer (ekv_decode_score.inc) ---------------------------------------------------------------------------------
+#ifndef EKV_SCORE_NW
+#define EKV_SCORE_NW 8
+#endif
+constexpr int kSNW = EKV_SCORE_NW, kSNT = 64 * kSNW;   // waves / threads per scorer workgroup
+
+// logits of the rep query heads | score rows | reduction scratch | histogram | candidate list
+inline size_t ekv_decode_score_lds(int rep, int t_pad, int policy) {
+  const size_t n_state = policy == EKV_POLICY_ROCO ? 3 : 1;
+  return ((size_t)rep * t_pad + n_state * ekv_align((size_t)t_pad, 256)) * 4 + 2 * kSNW * 8 * 8 + 264 * 4 + kSNT * 8;
+}
+
+// ---- generic scorer (ekv_score_select.inc), nt threads per workgroup -------------------------------------------------------------------
+// W score columns, `rows` logits rows swept per head (0 when column sums replace the logits); big: S / Q / C live in global scratch and
+// only the selection keys in LDS.  Keys (+ rows) | reduction scratch | histogram | candidate list.
+inline size_t ekv_score_lds_bytes(int nt, int64_t W, int64_t rows, bool big) {
+  return ekv_align(((size_t)(big ? 1 : 4) * (size_t)W + 2 * (size_t)rows) * 4, 16) + 2 * (nt / 64) * 8 * 4 + 264 * 4 + nt * 8;
+}
+// ... of a launch's arguments (EkvScoreArgs, ekv_kernels.h; a template only so that this header needs no HIP type)
+template <typename ScoreArgs>
+inline size_t ekv_score_lds_bytes(int nt, const ScoreArgs& a) {
+  const bool scored = a.policy == EKV_POLICY_H2O_HEAD || a.policy == EKV_POLICY_ROCO || a.policy == EKV_POLICY_TOVA;
+  const int64_t W = (int64_t)a.n_slots - (scored ? a.score_off : 0);
+  const int64_t rows = a.colsum != nullptr ? 0 : (int64_t)(a.n_q_heads / a.n_kv_heads) * a.q_len;   // (lrows of the kernel body)
+  return ekv_score_lds_bytes(nt, W, rows, a.big_rows != nullptr);
+}
+// generic scorer: S / Q / C + keys of W columns do not fit 160 KB of LDS (decided at workspace-planning time, before the arguments
+// exist: the 512-thread build with all four arrays in LDS)
+inline bool ekv_score_rows_exceed_lds(int W, int rows) { return ekv_score_lds_bytes(512, W, rows, false) > 160 * 1024; }
+
+// ---- scorer as the tail of the wide column-sum pass and of the logits-resident kernel (ekv_wide_tail.h), nt threads ------------------
+inline size_t ekw_tail_lds_bytes(int nt, int W) {      // keys | reduction scratch | histogram | candidate list
+  return ekv_align((size_t)W * 4, 16) + 2 * (nt / 64) * 8 * 4 + 264 * 4 + nt * 8;
+}
+
+// ---- small-row chunk step with the logits in LDS (ekv_chunk_lds.inc) --------------------------------------------------------------------
+constexpr int kLNW = 4;                     // waves per workgroup
+constexpr int kLItems = 10;                 // owned columns per thread: score rows up to 10 * 256 = 2560 positions
+constexpr int kListCap = 256;               // candidate list of the select (entries)
+
+struct LdsPlan {
+  size_t e_bytes, key_off, stat_off, red_off, hist_off, dead_off, total;
+};
+// LDS: logits / probabilities [E16 + 16 keys][NQ] fp32 (the last 16 "keys" are the chunk's own) | keys of the fallback select |
+// row statistics + their reduction scratch | block-reduction scratch | select histogram + candidate list | dead-row bits
+template <int D, int NQ>
+EKV_HD inline LdsPlan ekv_lds_plan(int e16, int W) {
+  LdsPlan p;
+  const size_t logits = (size_t)(e16 + 16) * NQ * 4;
+  const size_t oscr = (size_t)kLNW * NQ * D * 4;   // cross-wave output reduction, aliases the (dead) logits at the very end
+  p.e_bytes = ekv_align(logits > oscr ? logits : oscr, 16);
+  p.key_off = p.e_bytes;
+  const size_t stage = (size_t)kLNW * (D >= 128 ? 8 : 64 / (D / 8)) * D * 2;   // phase A's per-wave staging tiles (8 or G rows) alias the fallback select's key array
+  p.stat_off = p.key_off + ekv_align((size_t)W * 4 > stage ? (size_t)W * 4 : stage, 16);
+  p.red_off = p.stat_off + (2 * 16 + 2 * kLNW * 8) * 4;
+  p.hist_off = p.red_off + 2 * kLNW * 8 * 2;
+  p.dead_off = p.hist_off + 264 * 4 + kListCap * 8;
+  p.total = p.dead_off + ekv_align((size_t)(e16 / 32 + 2) * 4, 16);
+  return p;
+}
+// LDS bytes of a step of `rows` GQA-folded query rows (the 4-row or the 8-row build)
+template <int D>
+inline size_t ekv_chunk_lds_bytes(int rows, int phys_extent, int n_slots) {
+  const int e16 = (phys_extent + 15) & ~15;
+  return rows <= 4 ? ekv_lds_plan<D, 4>(e16, n_slots).total : ekv_lds_plan<D, 8>(e16, n_slots).total;
+}
+
+// ---- logits-resident scored chunk step (ekv_attn_resident.inc) --------------------------------------------------------------------------
+constexpr int R_D = 128, R_NT = 512, R_TK = 128, R_NB = 3, R_MAXT = 10;      // R_MAXT: 32 x 32 logit blocks a wave keeps (160 registers)
+constexpr int R_RS = 2 * R_D;                         // bytes per K / V row in LDS (unpadded, XOR-swizzled 16-byte chunks)
+constexpr int R_TBUF = R_TK * R_RS;                   // 32 KB per ring slot
+// Two shapes of the same kernel (the 320 KB of accumulator registers hold either):
+//   LONG = false  up to 64 rows x 1280 keys: query-wave group wq owns rows wq*32 .. +32 of EVERY tile
+//   LONG = true   up to 32 rows x 2560 keys: both groups hold rows 0 .. 31, group wq owns the tiles t with (t & 1) == wq; the V pass
+//                 splits a tile's keys over the two groups and their O^T blocks are added once at the end
+template <bool LONG>
+struct RL {
+  static constexpr int TILES = LONG ? 2 * R_MAXT : R_MAXT, TMAX = TILES * R_TK;
+  static constexpr int PSTR = LONG ? 80 : 144;        // bytes per key row of a P^T tile: 32 / 64 queries x fp16 + 16 (an odd multiple of 16: conflict-free writes and transposing reads)
+  static constexpr int PBUF = R_TK * PSTR;
+  static constexpr int OFF_P = R_NB * R_TBUF;         // P^T tiles [2][128][PSTR]; LONG = false, behind the V pass: the query waves' column-sum exchange
+  static constexpr int OFF_SLOT = OFF_P + 2 * PBUF;   // slot-map entries of the head's cache rows [TMAX]
+  static constexpr int OFF_CS = OFF_SLOT + TMAX * 4;  // column sums [2][TMAX]
+  static constexpr int OFF_RED = OFF_CS + 2 * TMAX * 4;   // row maxima [rows][NSH], row sums [rows][NSH] (256 words each), 1 / L [64]
+  static constexpr int LDS = OFF_RED + (256 + 256 + 64) * 4;
+  static constexpr int NSH = LONG ? 8 : 4;            // shares of a row's statistics: the waves that hold keys of the row
+  static constexpr int TI = (TMAX + R_NT - 1) / R_NT; // score columns per thread of the scorer
+  static_assert(LDS <= 160 * 1024, "one workgroup per CU");
+  static_assert(2 * TMAX * 4 <= 2 * PBUF || LONG, "the column-sum exchange fits the P^T tile buffers");
+};
+
+// ---- query blocks of the chunk attention kernels (ekv_attn_chunk.inc, ekv_attn_wide.inc) ------------------------------------------------
+// A query block is <= 128 GQA-folded rows (rep x qb_rows).  qpw = 1 or 2: 16-row query tiles per wave of a 4-wave
+// workgroup (<= 32 / <= 64 rows); qpw = 4 selects the 8-wave workgroup (2 tiles per wave x 4 query-tile waves, <= 128 rows).
+inline void ekv_chunk_blocks(int rep, int q_len, int* qb_rows, int* n_qblocks, int* qpw) {
+  int rows = q_len;
+  if ((int64_t)rep * q_len > 128) rows = 128 / rep > 0 ? 128 / rep : 1;   // (64-row blocks on 4-wave workgroups: 324 vs 378 TFLOP/s on the dense prefix)
+  // (65..128 rows stay ONE block on the 8-wave workgroup: two 4-wave blocks of <= 64 rows, even XCD-local so that the second K/V
+  // read is an L2 hit, measured 1.55 vs 1.19 ms per C4 step)
+  *qb_rows = rows;
+  *n_qblocks = (int)(((int64_t)q_len + rows - 1) / rows);
+  const int64_t r = (int64_t)rep * rows;
+  *qpw = r <= 32 ? 1 : (r <= 64 ? 2 : 4);
+}
+// partial column-sum rows the exact pass writes per (head, query block) = its query-tile waves
+inline int ekv_chunk_col_parts(int qpw, bool rope) { (void)rope; return qpw == 4 ? 4 : 2; }

@@ -1,10 +1,11 @@
-// Internal launch interface between the C ABI (ekv_abi.hip) and the kernels.
+// Internal launch interface between the C ABI (ekv_abi.hip) and the kernels; what the planner (ekv_plan.h) decides travels in EkvStepPlan.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 #include <stdint.h>
 
 #include "../../include/easykv_hip.h"
+#include "ekv_geometry.h"
 
 // One kernel launch sequence entry of a step (EkvStepPlan::list), in issue order.
 enum EkvLaunchKind : int32_t {
@@ -23,7 +24,7 @@ struct EkvLaunch {
   int32_t fuse, tail;  // ... the scorer runs as the tail of the 16x16 one-pass kernel / of the wide column-sum pass
 };
 
-// Everything ekv_step_attend decides about a step, from the bank and step descriptors alone (resolve_call, ekv_abi.hip): nothing is
+// Everything ekv_step_attend decides about a step, from the bank and step descriptors alone (resolve_call, ekv_plan.cpp): nothing is
 // dereferenced.  ekv_step_attend, ekv_step_check, ekv_step_plan, ekv_step_info and ekv_workspace_bytes — and their kv8 / batch kin — all read it.
 struct EkvStepPlan {
   int32_t t_pad, n_split, rows_per_split;
@@ -158,32 +159,12 @@ struct EkvScoreArgs {
 hipError_t ekv_launch_attn_decode(const EkvAttnArgs& a, const EkvSeqTable* tb, int head_dim, int count, hipStream_t s, bool bf16, bool kv8);
 // passes (wide-block kernel, two-pass scheme): bit 0 = the one pass (output + row statistics), bit 1 = the column-sum pass
 // tail_sc (wide-block kernel, two passes, passes & 2): the step's scorer runs as the tail of the column-sum pass (ekv_wide_tail.h)
-// wide: the wide-block kernel (ekv_chunk_wide, decided by the planner)
+// wide: the wide-block kernel (ekv_chunk_wide, ekv_plan.h)
 hipError_t ekv_launch_attn_chunk(const EkvAttnArgs& a, int head_dim, int layer_count, bool wide, bool two_pass, hipStream_t s,
                                  const EkvScoreArgs* fuse_sc, int passes, const EkvScoreArgs* tail_sc, bool bf16);
-// kernel launches ekv_launch_attn_chunk issues for these arguments (lives next to the launch code)
-int ekv_attn_chunk_launches(bool wide, bool rope, bool two_pass, int passes);
-// can the scorer of a two-pass wide step run as the tail of its column-sum pass: W score columns, n_wg workgroups per head
-bool ekv_wide_tail_supported(int W, int n_wg);
-// logits-resident scored chunk step (ekv_attn_resident.inc): the whole step of an unsplit head in ONE launch, K and V read once
-bool ekv_attn_resident_supported(int head_dim, int rep, int q_len, int n_slots, int W);
 hipError_t ekv_launch_attn_resident(const EkvAttnArgs& a, const EkvScoreArgs& sc, int layer_count, hipStream_t s, bool bf16);
-size_t ekv_score_lds_bytes_nt256(const EkvScoreArgs& a);
-bool ekv_score_rows_exceed_lds(int W, int rows);   // generic scorer: S / Q / C + keys of W columns do not fit 160 KB of LDS
-bool ekv_chunk_two_pass(int head_dim, int rep, int q_len, int policy, bool scored, bool accumulate, bool rope, int mode);
-// the launch runs on the wide-query-block kernel (32x32x16 MFMA, ekv_attn_wide.inc): 33..128 GQA-folded rows per query block,
-// plain or RoPE-on-read keys, head_dim 64 / 128, and either the two-pass scheme (rep in {1, 2, 4, 8, 16}) or a step that exports no logits
-bool ekv_chunk_wide(int head_dim, int rep, int q_len, bool rope, bool two_pass, bool wants_logits);
 hipError_t ekv_launch_tova_headmean(const EkvScoreArgs& a, int layer_count, hipStream_t s);
 hipError_t ekv_launch_score_select(const EkvScoreArgs& a, int layer_count, hipStream_t s, bool bf16);
-bool ekv_attn_decode_supported(int head_dim, int rep);
-int ekv_decode_fused_nw(int n_heads_in_launch);
-// Phase order of the fused decode step's workgroups (ekv_attn_decode.inc, "order K"; the kernel field EkvAttnArgs.fused_order).  Bits
-// 0-1: 0 = all F (K+V stream, then the tail), 1 = mixed per CU, 2 = all K (K stream, tail, V stream).  Mixed: bits 4-5 = the number x that
-// decides (0 HW_ID.TG_ID, 1 HW_ID.WAVE_ID of wave 0, 2 the workgroup's index in the launch), bits 8-11 a mask m, bits 12-15 a bound b,
-// bit 6 = invert: order K when ((x & m) < b) != invert.  Both orders produce the same bits, so a hardware-derived number is as good as any.
-int ekv_decode_fused_order(int head_dim, int rep, bool scored, bool slot_rows, int nw, int n_heads_in_launch, int phys_extent);
-bool ekv_decode_fused_supported(int head_dim, int rep, int n_slots, int t_pad, int l_pad, int n_evict, int cap, int nw);
 hipError_t ekv_launch_decode_fused(const EkvAttnArgs& a, const EkvScoreArgs& sc, const EkvSeqTable* tb, int head_dim, int count, int nw,
                                    hipStream_t s, bool bf16, bool kv8);
 // What workgroup (head, entry z) of a batch instance does first: its argument structs are the envelope's with the per-step fields
@@ -282,14 +263,25 @@ hipError_t ekv_launch_kv8_quantize(const ekv_bank* bank, const ekv_kv8* q8, bool
                                    hipStream_t s);
 hipError_t ekv_launch_kv8_dequantize(const ekv_bank* bank, const ekv_kv8* q8, int out_kind, int layer_begin, int layer_count, int extent,
                                      void* k_out, void* v_out, hipStream_t s);
-bool ekv_attn_chunk_supported(int head_dim, int rep, int q_len);
-void ekv_chunk_blocks(int rep, int q_len, int* qb_rows, int* n_qblocks, int* qpw);
-int ekv_chunk_col_parts(int qpw, bool rope);
-size_t ekv_score_lds_bytes(const EkvScoreArgs& a);
-bool ekv_decode_score_supported(const EkvScoreArgs& sc);
 hipError_t ekv_launch_decode_score(const EkvScoreArgs& sc, const EkvSeqTable* tb, int count, hipStream_t s, bool bf16);
 hipError_t ekv_launch_fold(const EkvScoreArgs& sc, int layer_count, hipStream_t s, bool bf16);
 
 // Small-row chunk step with the logits in LDS (ekv_chunk_lds.inc): whole step in one launch, K and V read once.
-bool ekv_chunk_lds_supported(const ekv_bank* bank, const ekv_step* st, int phys_extent, bool scored);
 hipError_t ekv_launch_chunk_lds(const EkvAttnArgs& a, const EkvScoreArgs& sc, int head_dim, int layer_count, hipStream_t s, bool bf16);
+
+// ---- bank utility kernels (ekv_bank_ops.hip); the entry points (ekv_abi.hip) have checked the arguments
+hipError_t ekv_launch_bank_reset(const ekv_bank* bank, hipStream_t s);
+hipError_t ekv_launch_state_init(const ekv_bank* bank, int layer_begin, int layer_count, int width, int mode, int stride, hipStream_t s);
+// gather: the first n slots of the layers, in order, to dense k_lin / v_lin; else scatter n dense rows to positions pos_begin ..
+hipError_t ekv_launch_rows_copy(const ekv_bank* bank, bool gather, int layer_begin, int layer_count, int pos_begin, int n, void* k_lin, void* v_lin,
+                                hipStream_t s);
+hipError_t ekv_launch_compact_inplace(const ekv_bank* bank, int layer_begin, int layer_count, int n_slots, int n_evict, const int32_t* evict_ids,
+                                      hipStream_t s);
+// EKV_POLICY_RANGE: tb != NULL = a batched decode step (the range of each entry from the table; `st` is its envelope)
+hipError_t ekv_launch_range_evict(const ekv_bank* bank, const ekv_step* st, const EkvSeqTable* tb, int32_t* evict_ids, hipStream_t s);
+hipError_t ekv_launch_rows_to_slots(const ekv_bank* bank, int layer_begin, int layer_count, int n_slots, size_t lds, hipStream_t s);
+hipError_t ekv_launch_rows_to_order(const ekv_bank* bank, int layer_begin, int layer_count, int n_slots, size_t lds, hipStream_t s);
+// second half of ekv_bank.birth: the parked tail of the ordered count row (float), same [layer][head][cap] indexing
+inline float* ekv_cnt_tail(const ekv_bank* bank) {
+  return reinterpret_cast<float*>(bank->birth + (size_t)bank->n_layers * bank->n_kv_heads * bank->cap);
+}

@@ -1,0 +1,73 @@
+// The step planner (ekv_plan.cpp): every decision about a call of the step family, from the caller's descriptors alone.  Host-only —
+// no kernel, no launch, no HIP call — over the families' geometry (ekv_geometry.h); ekv_abi.hip launches what it plans.
+#pragma once
+#include "ekv_kernels.h"
+
+int check_bank(const ekv_bank* b);
+int check_layers(const ekv_bank* b, int begin, int count);
+
+// ---- what a kernel family takes (each rule next to the measurements that set it: ekv_plan.cpp)
+bool ekv_attn_decode_supported(int head_dim, int rep);
+int ekv_decode_fused_nw(int64_t n_heads_in_launch);
+// Phase order of the fused decode step's workgroups (ekv_attn_decode.inc, "order K"; the kernel field EkvAttnArgs.fused_order).  Bits
+// 0-1: 0 = all F (K+V stream, then the tail), 1 = mixed per CU, 2 = all K (K stream, tail, V stream).  Mixed: bits 4-5 = the number x that
+// decides (0 HW_ID.TG_ID, 1 HW_ID.WAVE_ID of wave 0, 2 the workgroup's index in the launch), bits 8-11 a mask m, bits 12-15 a bound b,
+// bit 6 = invert: order K when ((x & m) < b) != invert.  Both orders produce the same bits, so a hardware-derived number is as good as any.
+int ekv_decode_fused_order(int head_dim, int rep, bool scored, bool slot_rows, int nw, int64_t n_heads_in_launch, int phys_extent);
+bool ekv_decode_fused_supported(int head_dim, int rep, int n_slots, int t_pad, int l_pad, int n_evict, int cap, int nw);
+bool ekv_decode_score_supported(const EkvScoreArgs& sc);
+bool ekv_attn_chunk_supported(int head_dim, int rep, int q_len);
+bool ekv_chunk_two_pass(int head_dim, int rep, int q_len, int policy, bool scored, bool accumulate, bool rope, int mode);
+// the launch runs on the wide-query-block kernel (32x32x16 MFMA, ekv_attn_wide.inc): 33..128 GQA-folded rows per query block,
+// plain or RoPE-on-read keys, head_dim 64 / 128, and either the two-pass scheme (rep in {1, 2, 4, 8, 16}) or a step that exports no logits
+bool ekv_chunk_wide(int head_dim, int rep, int q_len, bool rope, bool two_pass, bool wants_logits);
+// can the scorer of a two-pass wide step run as the tail of its column-sum pass: W score columns, n_wg workgroups per head
+bool ekv_wide_tail_supported(int64_t W, int64_t n_wg);
+// logits-resident scored chunk step (ekv_attn_resident.inc): the whole step of an unsplit head in ONE launch, K and V read once
+bool ekv_attn_resident_supported(int head_dim, int rep, int q_len, int n_slots, int64_t W);
+// small-row chunk step with the logits in LDS (ekv_chunk_lds.inc): whole step in one launch, K and V read once
+bool ekv_chunk_lds_supported(const ekv_bank* bank, const ekv_step* st, int phys_extent, bool scored);
+// kernel launches ekv_launch_attn_chunk issues for these arguments
+int ekv_attn_chunk_launches(bool wide, bool rope, bool two_pass, int passes);
+
+// The scalar (shape) fields of the scorer's arguments; call_attend adds the pointers.
+EkvScoreArgs score_args(const ekv_bank* bank, const ekv_step* st, const EkvStepPlan& P);
+int ekv_plan_step(const ekv_bank* bank, const ekv_step* step, EkvStepPlan* P);
+
+// ---- one call path --------------------------------------------------------------------------------------------------------------
+// A call of the step family as its entry points spell it: the untyped / _typed functions (a bank, a step, an element type), ekv_kv8_*
+// (+ the FP8 planes) and ekv_batch_* (+ the table of a batched decode step).  The axes are independent here; which combinations run
+// is the planner's business (resolve_call) and the manifest's (ekv_instances.def).
+struct EkvCall {
+  const ekv_bank* bank;
+  const ekv_step* step;
+  int32_t dtype;
+  bool kv8;                // an ekv_kv8_* call (q8 may still be NULL: an argument error)
+  const ekv_kv8* q8;
+  bool batch;              // an ekv_batch_* call
+  const ekv_seq* seqs;
+  int32_t n_seq;
+};
+inline EkvCall step_call(const ekv_bank* bank, const ekv_step* st, int32_t dtype) { return {bank, st, dtype, false, nullptr, false, nullptr, 0}; }
+inline EkvCall kv8_call(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_kv8* q8) { return {bank, st, dtype, true, q8, false, nullptr, 0}; }
+inline EkvCall batch_call(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_seq* seqs, int32_t n_seq) {
+  return {bank, st, dtype, false, nullptr, true, seqs, n_seq};
+}
+
+// Everything a call needs, resolved once (resolve_call): check, info, workspace bytes and attend all read it.
+struct EkvResolved {
+  const ekv_bank* bank;      // the bank planned and launched with; NULL: a kv8 call without its planes
+  const ekv_step* step;      // the step actually planned: the caller's, or the envelope of a batch
+  const EkvSeqTable* tb;     // the table the batch instances receive; NULL for a uniform step
+  EkvStepPlan plan;          // kv8 / batch / fused_order final; zero launches (a batch: zero bytes too) when the call is refused
+  ekv_bank bank8;            // storage of the above, where the call needs its own
+  ekv_step env;
+  EkvSeqTable table;
+};
+int resolve_call(const EkvCall& c, EkvResolved* r);
+int call_check(const EkvCall& c);
+size_t call_workspace_bytes(const EkvCall& c);
+// ekv_step_info and its kin: the plan's answers also for a step the call would refuse (launch counts 0 then); argument errors first
+int call_info(const EkvCall& c, int32_t* info, int32_t n_info);
+// ekv_step_plan: the split count, and whether the whole step is one launch (0 for a step the call would refuse)
+int call_plan(const ekv_bank* bank, const ekv_step* st, int32_t* n_split, int32_t* fused);

@@ -351,7 +351,7 @@ __device__ __forceinline__ void wide_sweep(const EkvScoreArgs& a, int tid, size_
 }
 
 // The scorer of one (KV head h, layer ll of the launch) by the kNT threads of a workgroup; `smem` = its dynamic LDS
-// (ekv_score_lds_bytes_nt*).  Body of ekv_score_select_kernel, and the tail of the chunk attention kernel when a head is not
+// (ekv_score_lds_bytes, ekv_geometry.h).  Body of ekv_score_select_kernel, and the tail of the chunk attention kernel when a head is not
 // split (ekv_attn_chunk.inc, FUSE): the scorer of one head then overlaps the K/V stream of the workgroups still streaming.
 // BIG: rows wider than one CU's LDS (W > ~10 000: 16 B of LDS per column).  The working copies of the score rows live in global
 // scratch (a.big_rows; L2-resident, the workgroup's own barriers order its accesses) and LDS holds the selection keys only, 4 B per
@@ -748,19 +748,8 @@ __global__ void __launch_bounds__(kNT) ekv_tova_headmean_kernel(const EkvScoreAr
 #define EKV_SS_CAT_(a, b) a##b
 #define EKV_SS_CAT(a, b) EKV_SS_CAT_(a, b)
 
-#if EKV_BF16
-size_t EKV_SS_CAT(ekv_score_lds_bytes_nt, EKV_SS_NT)(const EkvScoreArgs& a);
-#else
-size_t EKV_SS_CAT(ekv_score_lds_bytes_nt, EKV_SS_NT)(const EkvScoreArgs& a) {
-  const bool scored = a.policy == EKV_POLICY_H2O_HEAD || a.policy == EKV_POLICY_ROCO || a.policy == EKV_POLICY_TOVA;
-  const int W = a.n_slots - (scored ? a.score_off : 0);
-  const int rows = a.colsum != nullptr ? 0 : (a.n_q_heads / a.n_kv_heads) * a.q_len;   // (lrows of the kernel body)
-  return ekv_align((size_t)((a.big_rows != nullptr ? 1 : 4) * W + 2 * rows) * 4, 16) + 2 * kNWV * 8 * 4 + 264 * 4 + kNT * 8;   // .. + histogram + candidate list
-}
-#endif
-
 hipError_t EKV_FN_SCORE_SELECT(EKV_SS_NT, EKV_ELEM)(const EkvScoreArgs& a, int layer_count, hipStream_t s) {
-  const size_t lds = EKV_SS_CAT(ekv_score_lds_bytes_nt, EKV_SS_NT)(a);
+  const size_t lds = ekv_score_lds_bytes(kNT, a);
   if (lds > 160 * 1024) return hipErrorInvalidValue;
 #if EKV_SS_NT == 1024
   if (a.big_rows != nullptr) {

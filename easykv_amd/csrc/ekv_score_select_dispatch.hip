@@ -4,11 +4,10 @@
 #include "ekv_common.h"
 #include "ekv_kernels.h"
 
-// ---- the instances (ekv_instances.def).  The LDS plan and the head-mean row do not depend on the element type: the f16 instance of a
-// block size exports them.
+// ---- the instances (ekv_instances.def).  The head-mean row does not depend on the element type: the f16 instance of a block size
+// exports it.  (LDS bytes of a block size: ekv_score_lds_bytes, ekv_geometry.h)
 typedef hipError_t EkvSelectFn(const EkvScoreArgs&, int layer_count, hipStream_t);
-typedef size_t EkvSelectLdsFn(const EkvScoreArgs&);
-#define EKV_SCORE_SELECT(nt, elem) EkvSelectFn EKV_FN_SCORE_SELECT(nt, elem), ekv_launch_tova_headmean_nt##nt; EkvSelectLdsFn ekv_score_lds_bytes_nt##nt;
+#define EKV_SCORE_SELECT(nt, elem) EkvSelectFn EKV_FN_SCORE_SELECT(nt, elem), ekv_launch_tova_headmean_nt##nt;
 #include "ekv_instances.def"
 
 namespace {
@@ -28,13 +27,6 @@ hipError_t launch_select(int threads, const EkvScoreArgs& a, int layer_count, hi
 }
 }  // namespace
 
-size_t ekv_score_lds_bytes(const EkvScoreArgs& a) { return a.big_rows != nullptr ? ekv_score_lds_bytes_nt1024(a) : ekv_score_lds_bytes_nt512(a); }
-
-// (mirrors ekv_score_lds_bytes_nt512 with all four arrays in LDS; decided at workspace-planning time, before the arguments exist)
-bool ekv_score_rows_exceed_lds(int W, int rows) {
-  return ekv_align((size_t)(4 * (size_t)W + 2 * (size_t)rows) * 4, 16) + 2 * 8 * 8 * 4 + 264 * 4 + 512 * 8 > 160 * 1024;
-}
-
 hipError_t ekv_launch_score_select(const EkvScoreArgs& a, int layer_count, hipStream_t s, bool bf16) {
   // (the bf16 instances differ only in how the folded output is rounded and stored)
   auto nt256 = [&](const EkvScoreArgs& x, int lc, hipStream_t st) { return launch_select(256, x, lc, st, bf16); };
@@ -44,15 +36,15 @@ hipError_t ekv_launch_score_select(const EkvScoreArgs& a, int layer_count, hipSt
   // room for one workgroup per CU, which must then bring 512 threads
   if (a.big_rows != nullptr) return nt1024(a, layer_count, s);   // rows in global scratch, keys in LDS
   static const int force = [] { const char* e = std::getenv("EKV_SS_NT"); return e ? std::atoi(e) : 0; }();   // (A/B knob: 256 / 512 / 1024)
-  if (force == 256 && ekv_score_lds_bytes_nt256(a) <= 160 * 1024) return nt256(a, layer_count, s);
-  if (force == 512 && ekv_score_lds_bytes_nt512(a) <= 160 * 1024) return nt512(a, layer_count, s);
-  if (force == 1024 && ekv_score_lds_bytes_nt1024(a) <= 160 * 1024) return nt1024(a, layer_count, s);
-  const bool small_blocks = a.n_kv_heads * layer_count >= 768 && ekv_score_lds_bytes_nt256(a) <= 53 * 1024;
+  if (force == 256 && ekv_score_lds_bytes(256, a) <= 160 * 1024) return nt256(a, layer_count, s);
+  if (force == 512 && ekv_score_lds_bytes(512, a) <= 160 * 1024) return nt512(a, layer_count, s);
+  if (force == 1024 && ekv_score_lds_bytes(1024, a) <= 160 * 1024) return nt1024(a, layer_count, s);
+  const bool small_blocks = a.n_kv_heads * layer_count >= 768 && ekv_score_lds_bytes(256, a) <= 53 * 1024;
   if (small_blocks) return nt256(a, layer_count, s);
   // one workgroup per CU either way (at most one (head, layer) pair per CU, or LDS rows too wide for two): give it all 16
   // wave slots — the logits sweep is VALU-bound on exact expf / IEEE div and 2 waves per SIMD do not fill the pipeline
-  const bool one_per_cu = a.n_kv_heads * layer_count <= 256 || ekv_score_lds_bytes_nt512(a) > 80 * 1024;
-  if (one_per_cu && ekv_score_lds_bytes_nt1024(a) <= 160 * 1024) return nt1024(a, layer_count, s);
+  const bool one_per_cu = a.n_kv_heads * layer_count <= 256 || ekv_score_lds_bytes(512, a) > 80 * 1024;
+  if (one_per_cu && ekv_score_lds_bytes(1024, a) <= 160 * 1024) return nt1024(a, layer_count, s);
   return nt512(a, layer_count, s);
 }
 

@@ -38,9 +38,7 @@
 
 constexpr int kTailItems = 24;                       // owned columns per thread: score rows of up to 24 * 256 = 6144 positions
 
-__host__ __device__ inline size_t ekw_tail_lds_bytes(int W) {      // keys | reduction scratch | histogram | candidate list
-  return ekv_align((size_t)W * 4, 16) + 2 * kNWV * 8 * 4 + 264 * 4 + kNT * 8;
-}
+// (LDS of the tail: ekw_tail_lds_bytes(kNT, W), ekv_geometry.h)
 
 // The score rows of the thread's columns, requested ahead of the tail (ekv_attn_resident.inc issues them before its column-sum phase: the
 // round trip is over when the tail starts): the loads of step 1 below, same clamping.

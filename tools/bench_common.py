@@ -214,7 +214,7 @@ def live_pmc(extra_args, kernel_substr, timeout_s=150, script=None):
 
 def seqs_per_launch(n_layers_of_rank, n_kv_heads, want=0, min_heads=256):
     """In-flight sequences a pipeline stage serves per launch.  A stage that owns few layers launches few heads (N = 8: 4 layers x 32
-    = 128 heads, half a head per CU: the fused one-launch step needs >= 256, ekv_abi.hip) — but the pipeline holds >= N
+    = 128 heads, half a head per CU: the fused one-launch step needs >= 256, ekv_plan.cpp) — but the pipeline holds >= N
     sequences in
     flight anyway, and the bank is generic in its layer count: (sequence, layer) pairs are just more
     layers.  Default:
