@@ -31,7 +31,8 @@ MAX_SEQS = 64      # EKV_MAX_SEQS: entries of one batched decode step
 # the FP8 K/V storage calls (include/easykv_hip.h, "kv8"), checked and typed by load() like EXPORTS.  A list of their own:
 # tests/test_host_cpu.py pins EXPORTS to the header's names as a digit-free pattern reads them, which a name with "kv8" in it is not.
 EXPORTS_KV8 = ("ekv_kv8_quantize", "ekv_kv8_dequantize", "ekv_kv8_step_check", "ekv_kv8_step_info", "ekv_kv8_workspace_bytes",
-               "ekv_kv8_step_attend")
+               "ekv_kv8_step_attend", "ekv_kv8_batch_step_check", "ekv_kv8_batch_step_info", "ekv_kv8_batch_workspace_bytes",
+               "ekv_kv8_batch_step_attend")
 DTYPE_F32 = 2      # ekv_kv8_dequantize's out_dtype only
 
 
@@ -112,11 +113,16 @@ def load():
     lib.ekv_batch_step_info.argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, C.POINTER(Seq), i32, C.POINTER(C.c_int32), C.c_int32]
     lib.ekv_batch_workspace_bytes.argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, C.POINTER(Seq), i32]
     lib.ekv_batch_step_attend.argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, C.POINTER(Seq), i32, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
+    lib.ekv_kv8_batch_step_check.argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, C.POINTER(Kv8), C.POINTER(Seq), i32]
+    lib.ekv_kv8_batch_step_info.argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, C.POINTER(Kv8), C.POINTER(Seq), i32, C.POINTER(C.c_int32), C.c_int32]
+    lib.ekv_kv8_batch_workspace_bytes.argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, C.POINTER(Kv8), C.POINTER(Seq), i32]
+    lib.ekv_kv8_batch_step_attend.argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, C.POINTER(Kv8), C.POINTER(Seq), i32, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
     for name in EXPORTS[3:] + EXPORTS_KV8:
         getattr(lib, name).restype = C.c_int
     lib.ekv_workspace_bytes_typed.restype = C.c_size_t
     lib.ekv_kv8_workspace_bytes.restype = C.c_size_t
     lib.ekv_batch_workspace_bytes.restype = C.c_size_t
+    lib.ekv_kv8_batch_workspace_bytes.restype = C.c_size_t
     if lib.ekv_abi_version() != 8:
         raise EkvError("ABI version mismatch")
     _lib = lib

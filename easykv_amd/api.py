@@ -791,6 +791,8 @@ def generate_batch(self, input_ids_list, generation_config, kv_mode="encoding", 
     :class:`DecodePlanner` (it evicts when ITS length exceeds ITS budget, ``score_off`` = ITS prompt length, recency / random ranges
     per sequence) and a sequence leaves the batch when it samples an EOS or has been fed ``max_new_tokens`` tokens.  Returns the
     decoded strings, in prompt order, and prints each sequence's budget line as ``generate`` prints it.
+    ``generation_config['kv_quant'] = 'fp8'``: every prompt's bank is quantised right after its own 16-bit prefill (as ``generate``
+    does at the prefill -> decode boundary) and the decode phase runs one FP8 batched step per layer and token.
 
     Sampling: ``torch.multinomial`` draws for all live sequences at once, so with ``temperature`` / ``top_p`` that leave more than
     one candidate the global generator is consumed differently from B solo runs; ``kv_policy='random'`` draws once per sequence
@@ -798,8 +800,6 @@ def generate_batch(self, input_ids_list, generation_config, kv_mode="encoding", 
     cfg = generation_config
     if cfg.get("streaming", False):
         raise ValueError("generate_batch: streaming=True (RoPE-on-read) has no batched decode step")
-    if cfg.get("kv_quant", None) is not None:
-        raise ValueError("generate_batch: generation_config['kv_quant'] is not supported (a batch runs 16-bit rows)")
     if kv_mode == "ppl":
         raise ValueError("generate_batch: kv_mode='ppl' has no decode phase to batch")
     if cfg.get("hipgraph", False):
@@ -813,10 +813,17 @@ def generate_batch(self, input_ids_list, generation_config, kv_mode="encoding", 
     eos, dev, max_new_tokens = set(int(e) for e in run.eos_token_ids), run.dev, run.max_new_tokens
 
     # ---- every prompt alone, through the single-sequence prefill; its bank becomes one sequence of the batch
-    seqs = [_prefill(run, p, kv_mode) for p in prompts]
+    # (kv_quant='fp8': a prompt's bank is quantised right after its own prefill, so at most one 16-bit bank is alive at a time, and the
+    # batch bank is created holding FP8 planes only)
+    seqs = []
+    for p in prompts:
+        seqs.append(_prefill(run, p, kv_mode))
+        if run.kv_quant:
+            seqs[-1].cache.bank.quantize_fp8()
     first = seqs[0].cache.bank
+    rows = dict(kv_quant=run.kv_quant) if run.kv_quant else {}      # (FP8 planes only: the 16-bit rows of the batch are never allocated)
     bat = KVBankBatch(len(seqs), first.n_layers, first.n_q_heads, first.n_kv_heads, first.head_dim, max(s.cache.bank.cap for s in seqs),
-                      device=dev, dtype=first.dtype)
+                      device=dev, dtype=first.dtype, **rows)
     cache = BudgetedKVCacheBatch(bat, record=run.record)
     for i, s in enumerate(seqs):
         bat.adopt(i, s.cache.bank)

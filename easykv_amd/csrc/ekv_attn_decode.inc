@@ -31,9 +31,7 @@
 #ifndef EKV_BATCH
 #define EKV_BATCH 0
 #endif
-#if EKV_BATCH && EKV_KV8
-#error "batch instances: 16-bit rows, plain keys"
-#endif
+// Both switches at once (the batch kv8 instances) are independent: DESIGN.md §3.9, "Batches".
 #define ekv_attn_decode_kernel EKV_KERNEL_NAME(ekv_attn_decode_kernel)
 #define ekv_decode_fused_kernel EKV_KERNEL_NAME(ekv_decode_fused_kernel)
 // FP8 rows: 4 rows in flight per lane group.  A lane's output slice is 16 floats per query head instead of 8, the query fragment

@@ -38,7 +38,8 @@ const ScoreInstance kDecodeScore[] = {
 
 // The instance of a decode launch, or nullptr (hipErrorInvalidValue) for a combination the manifest does not hold or the arguments do
 // not fit: kv8 needs plain keys and the scale planes, bf16 and batches have no RoPE-on-read build, a batch runs on the ordered layout
-// (the planner refuses all of these before a launch).
+// (the planner refuses all of these before a launch).  kv8 and batch are independent: a batched step on FP8 rows looks up its own
+// instance (head_dim 64 / 128, plain keys), which takes the table and the scale planes together.
 const DecodeInstance* decode_instance(const EkvAttnArgs& a, const EkvSeqTable* tb, int head_dim, bool bf16, bool kv8, bool fused_slot_rows) {
   const bool rope = a.rope_cos != nullptr, batch = tb != nullptr;
   if (kv8 && (rope || a.k_scale == nullptr || a.v_scale == nullptr)) return nullptr;

@@ -154,7 +154,7 @@ struct EkvScoreArgs {
 // bf16 (the launchers below that take it): run the EKV_BF16 instances — 16-bit rows of q, k_new, v_new, out and the bank read and
 // written as bf16 (ekv_common.h); the planner never sends a RoPE-on-read step there.
 // tb (the decode launchers): NULL = a uniform step of `count` layers; the table of a batched decode step = the batch instances (16-bit
-// rows, plain keys, ordered score rows): `a` / `sc` are the envelope's arguments with layer_begin = 0 and a.arrive = the bank's
+// or FP8 rows, plain keys, ordered score rows): `a` / `sc` are the envelope's arguments with layer_begin = 0 and a.arrive = the bank's
 // counters, and `count` is the number of table entries, one workgroup row each.
 hipError_t ekv_launch_attn_decode(const EkvAttnArgs& a, const EkvSeqTable* tb, int head_dim, int count, hipStream_t s, bool bf16, bool kv8);
 // passes (wide-block kernel, two-pass scheme): bit 0 = the one pass (output + row statistics), bit 1 = the column-sum pass

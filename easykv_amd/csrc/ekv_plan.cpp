@@ -631,6 +631,9 @@ int ekv_plan_step(const ekv_bank* bank, const ekv_step* step, EkvStepPlan* P) {
 // widest extent, one "layer" per entry: same splits, launches and workspace pitches, so a uniform table plans field for field as the
 // multi-layer step it spells out.  The entries keep their own bounds inside those pitches (the kernels' batch instances read them
 // from the table, whose entries have phys_extent resolved as ekv_plan_step resolves a step's).
+// Both at once (an ekv_kv8_batch_* call): the stages apply independently — a missing plane is an argument error before the table is
+// read, the table is checked against the bank the code planes stand in, and the refusals of either variant hold unchanged (head_dim
+// 32 / 96 in a table: EKV_E_UNSUPPORTED with zero launches and zero bytes).  The plan is the 16-bit batched call's of the same table.
 int resolve_call(const EkvCall& c, EkvResolved* r) {
   EkvStepPlan* P = &r->plan;
   *P = EkvStepPlan{};

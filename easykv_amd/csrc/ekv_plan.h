@@ -44,7 +44,7 @@ struct EkvCall {
   int32_t dtype;
   bool kv8;                // an ekv_kv8_* call (q8 may still be NULL: an argument error)
   const ekv_kv8* q8;
-  bool batch;              // an ekv_batch_* call
+  bool batch;              // an ekv_batch_* call (with kv8: an ekv_kv8_batch_* call)
   const ekv_seq* seqs;
   int32_t n_seq;
 };
@@ -52,6 +52,10 @@ inline EkvCall step_call(const ekv_bank* bank, const ekv_step* st, int32_t dtype
 inline EkvCall kv8_call(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_kv8* q8) { return {bank, st, dtype, true, q8, false, nullptr, 0}; }
 inline EkvCall batch_call(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_seq* seqs, int32_t n_seq) {
   return {bank, st, dtype, false, nullptr, true, seqs, n_seq};
+}
+// an ekv_kv8_batch_* call: both variants at once (resolve_call applies them independently)
+inline EkvCall kv8_batch_call(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_kv8* q8, const ekv_seq* seqs, int32_t n_seq) {
+  return {bank, st, dtype, true, q8, true, seqs, n_seq};
 }
 
 // Everything a call needs, resolved once (resolve_call): check, info, workspace bytes and attend all read it.

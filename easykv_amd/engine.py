@@ -100,9 +100,15 @@ class KVBank:
     dtype, _dt = torch.float16, _lib.DTYPE_F16      # (set per bank by __init__)
     kv_quant, _kv8 = None, None      # quantize_fp8(): "fp8" and the ekv_kv8 descriptor of the code planes / row scales
 
-    def __init__(self, n_layers, n_q_heads, n_kv_heads, head_dim, cap, device="cuda", scored=True, dtype=torch.float16):
+    def __init__(self, n_layers, n_q_heads, n_kv_heads, head_dim, cap, device="cuda", scored=True, dtype=torch.float16, kv_quant=None):
+        """``kv_quant='fp8'``: the bank is created holding FP8 planes only (see :meth:`quantize_fp8`); the 16-bit K/V rows are never
+        allocated.  Such a bank is filled by decode steps or, as one sequence of a :class:`KVBankBatch`, by ``adopt()``."""
         if dtype not in _lib.DTYPE_CODES:
             raise ValueError(f"KVBank dtype must be torch.float16 or torch.bfloat16, not {dtype}")
+        if kv_quant not in (None, "fp8"):
+            raise ValueError(f"KVBank kv_quant must be None or 'fp8', not {kv_quant!r}")
+        if kv_quant is not None and head_dim not in (64, 128):
+            raise _lib.EkvError(f"kv_quant='fp8': FP8 rows are built for head_dim 64 and 128, not {head_dim}")
         self.dtype, self._dt = dtype, _lib.DTYPE_CODES[dtype]
         self.lib = _lib.load()
         dev = torch.device(device)
@@ -112,8 +118,8 @@ class KVBank:
         self._dev_index = dev.index if dev.index is not None else torch.cuda.current_device()
         cap = (cap + 63) // 64 * 64     # rows of the slot map / score rows stay 16-byte aligned (fused kernel, LDS-DMA)
         self.n_layers, self.n_q_heads, self.n_kv_heads, self.head_dim, self.cap = n_layers, n_q_heads, n_kv_heads, head_dim, cap
-        self.k = torch.empty(n_layers, n_kv_heads, cap, head_dim, dtype=dtype, device=dev)
-        self.v = torch.empty_like(self.k)
+        self.k = torch.empty(n_layers, n_kv_heads, cap, head_dim, dtype=dtype, device=dev) if kv_quant is None else None
+        self.v = torch.empty_like(self.k) if kv_quant is None else None
         # (the state tensors are reached through properties: reading one converts slot-indexed layers back to the ordered layout)
         self._slot_of_pos = torch.empty(n_layers, n_kv_heads, cap, dtype=torch.int32, device=dev)
         self._score_sum = torch.zeros(n_layers, n_kv_heads, cap, dtype=torch.float32, device=dev) if scored else None
@@ -143,12 +149,14 @@ class KVBank:
         self._score_done = [None] * n_layers
         self._defer = None      # deferred-scorer state of the token step in flight (attend(..., defer=True) ... flush())
         self.arrive = torch.zeros(n_layers, n_kv_heads, dtype=torch.int32, device=dev)     # arrival counters of the in-kernel fold
-        self._bank = Bank(self.k.data_ptr(), self.v.data_ptr(), self._slot_of_pos.data_ptr(),
+        self._bank = Bank(_ptr(self.k), _ptr(self.v), self._slot_of_pos.data_ptr(),
                           self._score_sum.data_ptr() if scored else None, self._score_sq.data_ptr() if scored else None,
                           self._score_cnt.data_ptr() if scored else None, n_layers, n_q_heads, n_kv_heads, head_dim, cap,
                           self.arrive.data_ptr(), self.birth.data_ptr() if scored else None,
                           self.slot_state.data_ptr() if scored else None)
         self.rope_cos = self.rope_sin = None
+        if kv_quant is not None:
+            self._attach_fp8()
         self.reset()
 
     # -- layout of the score rows -------------------------------------------------------------------
@@ -261,25 +269,33 @@ class KVBank:
         if torch.cuda.is_current_stream_capturing():
             raise _lib.EkvError("quantize_fp8() cannot be captured in a graph: convert the bank before the capture")
         self.join()
-        shape = (self.n_layers, self.n_kv_heads, self.cap)
-        # rows that were never written keep code 0 / scale 1: every scale of the bank is finite whatever the kernels prefetch
-        self.k8 = torch.zeros(*shape, self.head_dim, dtype=torch.uint8, device=self.device)
-        self.v8 = torch.zeros_like(self.k8)
-        self.k_scale = torch.ones(*shape, dtype=torch.float32, device=self.device)
-        self.v_scale = torch.ones_like(self.k_scale)
-        kv8 = _lib.Kv8(self.k8.data_ptr(), self.v8.data_ptr(), self.k_scale.data_ptr(), self.v_scale.data_ptr())
+        kv8 = self._fp8_planes()
         check(self.lib.ekv_kv8_quantize(C.byref(self._bank), C.byref(kv8), self._dt, 0, self.n_layers, max(self.extent), self._stream()),
               "ekv_kv8_quantize")
         cur = torch.cuda.current_stream(self.device)
         self.k.record_stream(cur)
         self.v.record_stream(cur)
         self.k = self.v = None
+        self._attach_fp8(kv8)
+        return self
+
+    def _fp8_planes(self):
+        shape = (self.n_layers, self.n_kv_heads, self.cap)
+        # rows that were never written keep code 0 / scale 1: every scale of the bank is finite whatever the kernels prefetch
+        self.k8 = torch.zeros(*shape, self.head_dim, dtype=torch.uint8, device=self.device)
+        self.v8 = torch.zeros_like(self.k8)
+        self.k_scale = torch.ones(*shape, dtype=torch.float32, device=self.device)
+        self.v_scale = torch.ones_like(self.k_scale)
+        return _lib.Kv8(self.k8.data_ptr(), self.v8.data_ptr(), self.k_scale.data_ptr(), self.v_scale.data_ptr())
+
+    def _attach_fp8(self, kv8=None):
+        """The bank's rows are the FP8 planes from here on (``kv8=None``: a bank created without 16-bit rows allocates them now)."""
+        kv8 = self._fp8_planes() if kv8 is None else kv8
         # the descriptor's planes stand where the rows were: the planning calls that take the bank alone never dereference them
         self._bank.k, self._bank.v = self.k8.data_ptr(), self.v8.data_ptr()
         self._kv8, self.kv_quant = kv8, "fp8"
         self._slot_ok.clear()
         self._defer = None
-        return self
 
     def kv_bytes(self) -> int:
         """Bytes held for the K/V rows: 16-bit rows, or FP8 codes + row scales (``2 * head_dim + 8`` per row pair)."""
@@ -707,11 +723,13 @@ class KVBankBatch:
     :meth:`attend` serves model layer ``layer`` of any subset of the sequences — each with its own cache length, score offset and
     eviction geometry — in ONE call: one launch per kernel kind over the layers ``{s * n_layers + layer}``."""
 
-    def __init__(self, n_seq, n_layers, n_q_heads, n_kv_heads, head_dim, cap, device="cuda", scored=True, dtype=torch.float16):
+    def __init__(self, n_seq, n_layers, n_q_heads, n_kv_heads, head_dim, cap, device="cuda", scored=True, dtype=torch.float16, kv_quant=None):
+        """``kv_quant='fp8'``: the shared bank holds FP8 planes only from the start (the 16-bit rows of ``n_seq`` sequences are never
+        allocated); its sequences are filled by :meth:`adopt` from banks quantised by :meth:`KVBank.quantize_fp8`."""
         if not 1 <= n_seq <= _lib.MAX_SEQS:
             raise ValueError(f"a decode batch holds 1..{_lib.MAX_SEQS} sequences, not {n_seq}")
         self.n_seq, self.n_layers = n_seq, n_layers
-        self.bank = KVBank(n_seq * n_layers, n_q_heads, n_kv_heads, head_dim, cap, device, scored, dtype)
+        self.bank = KVBank(n_seq * n_layers, n_q_heads, n_kv_heads, head_dim, cap, device, scored, dtype, kv_quant)
         self.lib, self.dtype = self.bank.lib, dtype
         self.n_q_heads, self.n_kv_heads, self.head_dim, self.cap, self.device = n_q_heads, n_kv_heads, head_dim, self.bank.cap, self.bank.device
         self.n_calls = 0      # batched attend calls issued (one per layer and decode forward)
@@ -724,18 +742,37 @@ class KVBankBatch:
     def n_slots(self, i, layer=0):
         return self.bank.n_slots[i * self.n_layers + layer]
 
+    kv_quant = property(lambda self: self.bank.kv_quant)
+
+    def quantize_fp8(self):
+        """:meth:`KVBank.quantize_fp8` of the shared bank: the rows ``[0, max extent)`` of every layer become FP8 codes + row scales at
+        their physical indices (slot maps, score rows, lengths and extents of every sequence carry over), the 16-bit tensors are
+        released and :meth:`attend` / :meth:`step_info` go to the kv8 batch calls.  ``sequence(i)`` then behaves as a quantised
+        :class:`KVBank`: decode steps only."""
+        self.bank.quantize_fp8()
+        return self
+
+    def kv_bytes(self) -> int:
+        """Bytes held for the K/V rows of all sequences (:meth:`KVBank.kv_bytes` of the shared bank)."""
+        return self.bank.kv_bytes()
+
     def adopt(self, i, src: KVBank):
         """Sequence ``i`` takes over the state of ``src``, a bank of this batch's layer count and head shape that one sequence was
         prefilled on alone: K/V rows at their physical indices, slot maps, score rows (ordered layout), lengths and extents.  The
-        rows behind ``src.cap`` keep this bank's own free list, so a shorter ``src.cap`` is fine."""
+        rows behind ``src.cap`` keep this bank's own free list, so a shorter ``src.cap`` is fine.  A quantised batch takes a quantised
+        source (codes and row scales are copied as they are); 16-bit and FP8 rows do not mix."""
         b = self.bank
         if (src.n_layers, src.n_q_heads, src.n_kv_heads, src.head_dim, src.dtype) != (self.n_layers, b.n_q_heads, b.n_kv_heads, b.head_dim, b.dtype) \
-                or src.cap > b.cap or src.kv_quant is not None or not 0 <= i < self.n_seq:
-            raise ValueError("adopt(): the source bank must have this batch's layers, heads, head_dim and dtype, 16-bit rows and cap <= the batch's")
+                or src.cap > b.cap or not 0 <= i < self.n_seq:
+            raise ValueError("adopt(): the source bank must have this batch's layers, heads, head_dim and dtype, and cap <= the batch's")
+        if src.kv_quant != b.kv_quant:
+            raise ValueError(f"adopt(): the source bank's rows (kv_quant={src.kv_quant!r}) are not this batch's (kv_quant={b.kv_quant!r}): "
+                             "quantize_fp8() both or neither")
         src.join()
         l0, l1, c = i * self.n_layers, (i + 1) * self.n_layers, src.cap
         b._ensure_ordered(l0, self.n_layers)
-        for name in ("k", "v", "slot_of_pos", "score_sum", "score_sq", "score_cnt"):      # (the properties hand out the ordered layout)
+        rows = ("k", "v") if b.kv_quant is None else ("k8", "v8", "k_scale", "v_scale")
+        for name in rows + ("slot_of_pos", "score_sum", "score_sq", "score_cnt"):      # (the properties hand out the ordered layout)
             t = getattr(src, name)
             if t is not None:
                 getattr(b, name)[l0:l1, :, :c].copy_(t)
@@ -772,16 +809,26 @@ class KVBankBatch:
     def step_info(self, plans, layer, active=None, n_split=0) -> dict:
         st, tb, _ = self.make_table(plans, layer, active, n_split)
         info = (C.c_int32 * 10)()
-        check(self.lib.ekv_batch_step_info(C.byref(self.bank._bank), C.byref(st), self.bank._dt, tb, len(tb), info, 10), "ekv_batch_step_info")
+        b = self.bank
+        if b._kv8 is not None:
+            check(self.lib.ekv_kv8_batch_step_info(C.byref(b._bank), C.byref(st), b._dt, C.byref(b._kv8), tb, len(tb), info, 10), "ekv_kv8_batch_step_info")
+        else:
+            check(self.lib.ekv_batch_step_info(C.byref(b._bank), C.byref(st), b._dt, tb, len(tb), info, 10), "ekv_batch_step_info")
         keys = ("n_split", "fused", "two_pass", "wide", "n_qblocks", "qb_rows", "n_col_parts", "fold_in_kernel", "n_launches", "fused_order")
         return dict(zip(keys, (int(x) for x in info)))
+
+    def workspace_bytes(self, st, tb) -> int:
+        """Workspace of the batched call of (shared step, table) as :meth:`make_table` returns them."""
+        b = self.bank
+        if b._kv8 is not None:
+            return self.lib.ekv_kv8_batch_workspace_bytes(C.byref(b._bank), C.byref(st), b._dt, C.byref(b._kv8), tb, len(tb))
+        return self.lib.ekv_batch_workspace_bytes(C.byref(b._bank), C.byref(st), b._dt, tb, len(tb))
 
     def attend(self, plans, q, k_new, v_new, layer, active=None, out=None, evict_ids=None, n_split=0):
         """q / out ``[B', Hq, 1, D]``, k_new / v_new ``[B', H, 1, D]``: row i belongs to ``active[i]`` (default: every sequence).
         Returns (out, evict_ids ``[B', H, 1]`` int32 or None when no sequence evicts; rows of sequences that keep everything are
         left as they are)."""
         b = self.bank
-        b._kv8_refuse(True, "a batched decode step")
         st, tb, seqs = self.make_table(plans, layer, active, n_split)
         n = len(seqs)
         if q.shape[0] != n or q.shape[2] != 1:
@@ -798,9 +845,12 @@ class KVBankBatch:
         if k_max > 0 and evict_ids is None:
             evict_ids = torch.empty(n, self.n_kv_heads, k_max, dtype=torch.int32, device=self.device)
         bank_ref, st_ref = C.byref(b._bank), C.byref(st)
-        ws = b._workspace(self.lib.ekv_batch_workspace_bytes(bank_ref, st_ref, b._dt, tb, n))
-        check(self.lib.ekv_batch_step_attend(bank_ref, st_ref, b._dt, tb, n, _ptr(q), _ptr(k_new), _ptr(v_new), _ptr(out),
-                                             _ptr(evict_ids) if k_max > 0 else None, _ptr(ws), ws.numel(), b._stream()), "ekv_batch_step_attend")
+        ws = b._workspace(self.workspace_bytes(st, tb))
+        tensors = (_ptr(q), _ptr(k_new), _ptr(v_new), _ptr(out), _ptr(evict_ids) if k_max > 0 else None, _ptr(ws), ws.numel(), b._stream())
+        if b._kv8 is not None:      # FP8 rows: the kv8 batch call, the descriptor behind the dtype
+            check(self.lib.ekv_kv8_batch_step_attend(bank_ref, st_ref, b._dt, C.byref(b._kv8), tb, n, *tensors), "ekv_kv8_batch_step_attend")
+        else:
+            check(self.lib.ekv_batch_step_attend(bank_ref, st_ref, b._dt, tb, n, *tensors), "ekv_batch_step_attend")
         for e in tb:
             b.n_slots[e.layer] = e.n_slots - e.n_evict
             b.extent[e.layer] = e.phys_extent

@@ -337,6 +337,29 @@ int ekv_batch_step_attend(const ekv_bank *bank, const ekv_step *step, int32_t dt
                           const void *k_new, const void *v_new, void *out, int32_t *evict_ids, void *workspace, size_t workspace_bytes,
                           void *stream);
 
+/* Batched decode steps on a kv8 bank ("kv8 batches"; ABI 8, additive): the ekv_batch_* calls with the descriptor after `dtype`.  The
+ * table, the shared step and the call's tensors are those of ekv_batch_step_attend; the bank's rows are the code and scale planes of
+ * `kv8` (bank->k / bank->v are not read), and `dtype` is the type of q, k_new, v_new and out.
+ *
+ * Accepted: the intersection of what a kv8 step and a batched step accept — q_len == 1 with plain keys at head_dim 64 / 128, fp16 and
+ * bf16, in the whole-step form (phases == 0, defer_layers == 0) on the ordered score-row layout; GQA factors <= 8, at most one victim
+ * per entry and step, at most 6144 slots and cap % 4 == 0 for scored policies.  Planned exactly as ekv_batch_step_attend of the same
+ * table (same key-range splits, launches, workspace and info fields) and run on the kv8 builds of the batch instances: per entry the
+ * arithmetic is that of ekv_kv8_step_attend of the entry's geometry under the same n_split, the row an entry appends is quantised by
+ * the kernel into the row its free list names (codes + scale), and it takes part in the step as quantised.
+ * The refusals of both families apply unchanged.  EKV_E_UNSUPPORTED from the dry run, nothing launched and 0 workspace bytes: head_dim
+ * 32 / 96, q_len > 1, rope_on_read, any `phases` bit, defer_layers, tova_head_mean, scored shapes only the generic scorer serves.
+ * EKV_E_ARG: a NULL descriptor or plane, a dtype other than EKV_DTYPE_F16 / _BF16, and everything ekv_batch_step_check calls a bad table. */
+int ekv_kv8_batch_step_check(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const ekv_kv8 *kv8, const ekv_seq *seqs,
+                             int32_t n_seq);
+int ekv_kv8_batch_step_info(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const ekv_kv8 *kv8, const ekv_seq *seqs,
+                            int32_t n_seq, int32_t *info, int32_t n_info);
+size_t ekv_kv8_batch_workspace_bytes(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const ekv_kv8 *kv8, const ekv_seq *seqs,
+                                     int32_t n_seq);
+int ekv_kv8_batch_step_attend(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const ekv_kv8 *kv8, const ekv_seq *seqs,
+                              int32_t n_seq, const void *q, const void *k_new, const void *v_new, void *out, int32_t *evict_ids,
+                              void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,8 +19,14 @@ Per B in {1, 2, 4, 8, 16, 32}:
                    that layout to batches would gain, not as a yardstick)
 and the same B with lengths spread over [256, 2049] (fixed seed, recorded):
   ragged           one batched call per layer; against `batched` at the envelope length and against live bytes / envelope bytes
+and with --kv8 (output: profiles/batch_kv8_bench.json), interleaved with the legs above on copies of the SAME rows, slot maps and
+score state, quantised (KVBankBatch.quantize_fp8 / KVBank.quantize_fp8):
+  batched_kv8        one ekv_kv8_batch_step_attend per layer over the B sequences (table prebuilt) — against `batched`
+  solo_kv8_deferred  B FP8 attend(defer=True) calls per layer + one flush() per token — what a caller of FP8 banks had before
+  ragged_kv8         the FP8 batched call at the ragged lengths — against `ragged`
+Every leg also reports its algorithmic bytes per per-layer call (FP8 rows: 2 * D + 8 bytes per K+V row pair instead of 4 * D).
 
-Usage: python tools/bench_batch.py [--reps 9] [--tokens 24] [--warm 20] [--batches 1,2,4,8,16,32] [--out profiles/batch_bench.json]"""
+Usage: python tools/bench_batch.py [--reps 9] [--tokens 24] [--warm 20] [--batches 1,2,4,8,16,32] [--kv8] [--out profiles/batch_bench.json]"""
 from __future__ import annotations
 
 import argparse
@@ -88,7 +94,39 @@ def _tokens(B, lps, g, dev, n=8):
     return tuple(torch.randn(n, lps, B, hh, 1, D, generator=g, device=dev).half() for hh in (HQ, H, H))
 
 
-def batched_legs(B, lps, lens, g):
+def _quantised_copy(src, make):
+    """A bank from `make()` holding the state of `src` (rows, slot maps, score rows, lengths, extents), quantised to FP8 rows."""
+    dst = make()
+    for name in ("k", "v", "slot_of_pos", "score_sum", "score_sq", "score_cnt"):
+        getattr(dst, name).copy_(getattr(src, name))
+    dst.n_slots, dst.extent = list(src.n_slots), list(src.extent)
+    return dst.quantize_fp8()
+
+
+def batched_kv8_leg(bat, lps, plans, toks):
+    """The FP8 twin of a batched leg: the same bank contents quantised, the same tables and tokens, straight through the C ABI."""
+    from easykv_amd import KVBankBatch
+    B = bat.n_seq
+    bat8 = KVBankBatch(B, lps, HQ, H, D, cap=BUDGET + 1 + 63)
+    _quantised_copy(bat.bank, lambda: bat8.bank)
+    qs, ks, vs = toks
+    out = torch.empty(B, HQ, 1, D, dtype=torch.float16, device=bat8.device)
+    ids = torch.empty(B, H, 1, dtype=torch.int32, device=bat8.device)
+    tables = [bat8.make_table(plans, l)[:2] for l in range(lps)]
+    b = bat8.bank
+    ws = b._workspace(max(bat8.workspace_bytes(st, tb) for st, tb in tables))
+    assert bat8.step_info(plans, 0) == bat.step_info(plans, 0)      # planned as the 16-bit batched call of the same table
+
+    def raw8(i):
+        j = i % qs.shape[0]
+        for l, (st, tb) in enumerate(tables):
+            rc = bat8.lib.ekv_kv8_batch_step_attend(C.byref(b._bank), C.byref(st), b._dt, C.byref(b._kv8), tb, B, qs[j, l].data_ptr(), ks[j, l].data_ptr(),
+                                                    vs[j, l].data_ptr(), out.data_ptr(), ids.data_ptr(), ws.data_ptr(), ws.numel(), b._stream())
+            assert rc == 0, rc
+    return raw8
+
+
+def batched_legs(B, lps, lens, g, kv8=False):
     """-> {name: forward} of the batched call over B sequences at `lens` (rows before the token), through the C ABI and through the engine."""
     from easykv_amd import KVBankBatch
     bat = KVBankBatch(B, lps, HQ, H, D, cap=BUDGET + 1 + 63)
@@ -113,10 +151,12 @@ def batched_legs(B, lps, lens, g):
         j = i % qs.shape[0]
         for l in range(lps):
             bat.attend(plans, qs[j, l], ks[j, l], vs[j, l], l, out=out, evict_ids=ids)
+    if kv8:      # (the twin is built before any leg has stepped the 16-bit bank)
+        return raw, engine, info, batched_kv8_leg(bat, lps, plans, (qs, ks, vs))
     return raw, engine, info
 
 
-def solo_legs(B, lps, g):
+def solo_legs(B, lps, g, kv8=False):
     from easykv_amd import KVBank
     n = BUDGET
     plan = _plan(n)
@@ -140,7 +180,17 @@ def solo_legs(B, lps, g):
             for s in range(B):
                 defer.attend(plan, qs[j, l, s:s + 1], ks[j, l, s:s + 1], vs[j, l, s:s + 1], layer_begin=s * lps + l, defer=True, out=out)
         defer.flush()
-    return f_whole, f_defer
+    if not kv8:
+        return f_whole, f_defer
+    defer8 = _quantised_copy(defer, lambda: KVBank(B * lps, HQ, H, D, cap=n + 1 + 63))
+
+    def f_defer8(i):
+        j = i % qs.shape[0]
+        for l in range(lps):
+            for s in range(B):
+                defer8.attend(plan, qs[j, l, s:s + 1], ks[j, l, s:s + 1], vs[j, l, s:s + 1], layer_begin=s * lps + l, defer=True, out=out)
+        defer8.flush()
+    return f_whole, f_defer, f_defer8
 
 
 def uniform_legs(B, lps, g):
@@ -190,8 +240,14 @@ def uniform_legs(B, lps, g):
     return legs
 
 
-def bytes_per_call(lens):
-    return sum(algorithmic_bytes(H, HQ, D, n + 1, 1, 3)["total"] for n in lens)
+def bytes_per_call(lens, kv8=False):
+    """Algorithmic bytes of one per-layer call over sequences of `lens` rows; kv8: K/V rows as FP8 codes + two fp32 scales per row pair."""
+    total = 0
+    for n in lens:
+        b = algorithmic_bytes(H, HQ, D, n + 1, 1, 3)
+        kv16 = 2 * H * (n + 1) * D * 2
+        total += b["total"] - kv16 + H * (n + 1) * (2 * D + 8) if kv8 else b["total"]
+    return total
 
 
 def run_batch(B, args):
@@ -201,13 +257,17 @@ def run_batch(B, args):
     rs = torch.Generator().manual_seed(20261016 + B)
     ragged = sorted(int(x) for x in torch.randint(255, BUDGET + 1, (B,), generator=rs))
     ragged[-1] = BUDGET      # (the envelope is the uniform shape)
-    raw, engine, info = batched_legs(B, lps, [BUDGET] * B, g)
+    raw, engine, info, *raw8 = batched_legs(B, lps, [BUDGET] * B, g, args.kv8)
     fns = {"batched": raw, "batched_engine": engine}
-    fns["solo_whole"], fns["solo_deferred"] = solo_legs(B, lps, g)
+    fns["solo_whole"], fns["solo_deferred"], *defer8 = solo_legs(B, lps, g, args.kv8)
     fns.update(uniform_legs(B, lps, g))
+    if args.kv8:
+        fns["batched_kv8"], fns["solo_kv8_deferred"] = raw8[0], defer8[0]
     if B > 1:
-        fns["ragged"], _, rinfo = batched_legs(B, lps, ragged, g)
+        fns["ragged"], _, rinfo, *ragged8 = batched_legs(B, lps, ragged, g, args.kv8)
         assert rinfo == info, (rinfo, info)      # a ragged table plans as its envelope
+        if args.kv8:
+            fns["ragged_kv8"] = ragged8[0]
     if args.legs:      # (a kernel trace of two legs: their launches alone)
         fns = {k: f for k, f in fns.items() if k in args.legs.split(",")}
     t = _interleave(fns, args.reps, args.tokens, args.warm)
@@ -218,9 +278,9 @@ def run_batch(B, args):
     ub = bytes_per_call([BUDGET] * B)
     for k, v in t.items():
         us = v["us"] / lps      # per per-layer call (solo legs: B calls; solo_deferred: + its share of the flush)
-        nb = bytes_per_call(ragged) if k == "ragged" else ub
+        nb = bytes_per_call(ragged if k.startswith("ragged") else [BUDGET] * B, "kv8" in k)
         res[k] = dict(us_per_layer_call=round(us, 2), run_to_run_spread=v["spread"], path_tokens_per_s=round(B / (us * 32 * 1e-6), 1),
-                      gb_per_s=round(nb / (us * 1e-6) / 1e9, 1), frac_of_hbm_peak=round(nb / (us * 1e-6) / 1e9 / HBM_PEAK_GBS, 4))
+                      bytes_per_layer_call=nb, gb_per_s=round(nb / (us * 1e-6) / 1e9, 1), frac_of_hbm_peak=round(nb / (us * 1e-6) / 1e9 / HBM_PEAK_GBS, 4))
     if args.legs:
         return res
     us = lambda k: res[k]["us_per_layer_call"]
@@ -230,6 +290,13 @@ def run_batch(B, args):
     res["ratio_batched_over_solo_deferred"] = round(us("batched") / us("solo_deferred"), 4)
     if "uniform_slot" in res:
         res["ratio_uniform_slot_over_uniform_ordered"] = round(us("uniform_slot") / us("uniform_ordered"), 4)
+    if "batched_kv8" in res:
+        res["ratio_batched_kv8_over_batched"] = round(us("batched_kv8") / us("batched"), 4)
+        res["ratio_batched_kv8_over_solo_kv8_deferred"] = round(us("batched_kv8") / us("solo_kv8_deferred"), 4)
+        res["byte_ratio_batched_kv8_over_batched"] = round(res["batched_kv8"]["bytes_per_layer_call"] / res["batched"]["bytes_per_layer_call"], 4)
+    if "ragged_kv8" in res:
+        res["ratio_ragged_kv8_over_ragged"] = round(us("ragged_kv8") / us("ragged"), 4)
+        res["ratio_ragged_kv8_over_batched_kv8_at_envelope"] = round(us("ragged_kv8") / us("batched_kv8"), 4)
     if "ragged" in res:
         res["ragged_lengths"] = [n + 1 for n in ragged]
         res["ratio_ragged_over_batched_at_envelope"] = round(us("ragged") / us("batched"), 4)
@@ -244,8 +311,10 @@ def main():
     ap.add_argument("--warm", type=int, default=20)
     ap.add_argument("--batches", default="1,2,4,8,16,32")
     ap.add_argument("--legs", default=None, help="comma-separated legs to run alone, e.g. batched,uniform_ordered (no ratios; for a kernel trace)")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "batch_bench.json"))
+    ap.add_argument("--kv8", action="store_true", help="add the FP8 legs batched_kv8, solo_kv8_deferred, ragged_kv8 (default --out: profiles/batch_kv8_bench.json)")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    args.out = args.out or os.path.join(ROOT, "profiles", "batch_kv8_bench.json" if args.kv8 else "batch_bench.json")
     torch.cuda.set_device(0)
     res = {"device": torch.cuda.get_device_name(0), "reps": args.reps, "tokens_per_rep": args.tokens, "warm_tokens": args.warm,
            "hbm_peak_gb_per_s": HBM_PEAK_GBS,
