@@ -16,6 +16,10 @@ OBJ = os.path.join(CSRC, "obj")
 
 
 MANIFEST = os.path.join(CSRC, "ekv_instances.def")
+# What the library holds beside the recorded set (objects() / all_objects() below are fixtures of the tests): the MXFP4 ("kv4") family,
+# whose lines the manifest includes from a file of its own, and the translation unit of its bank conversion.
+MANIFEST_KV4 = os.path.join(CSRC, "ekv_instances_kv4.def")
+EXTRA_SOURCES = ("ekv_kv4.hip",)
 
 
 def _tags(*words):
@@ -42,6 +46,9 @@ FAMILIES = {
         _on(elem) + [f"-DEKV_D={d}", f"-DEKV_WIDE_MODE={m}"] + (["-DEKV_WIDE_ROPE=1"] if keys == "rope" else [])),
     "EKV_CHUNK_LDS": lambda d, elem: ("ekv_chunk_lds.inc", f"ekv_chunk_lds_d{d}" + _tags(elem), _on(elem) + [f"-DEKV_D={d}"]),
     "EKV_RESIDENT": lambda d, elem: ("ekv_attn_resident.inc", f"ekv_attn_resident_d{d}" + _tags(elem), _on(elem)),
+    "EKV_DECODE_KV4": lambda d, elem: (
+        "ekv_attn_decode.inc", f"ekv_attn_decode_d{d}_plain_kv4" + _tags(elem),
+        _on(elem) + ["-DEKV_KV4=1", f"-DEKV_D={d}", "-DEKV_ROPE=false"]),
     "EKV_SCORE_SELECT": lambda nt, elem: ("ekv_score_select.inc", f"ekv_score_select_nt{nt}" + _tags(elem), _on(elem) + [f"-DEKV_SS_NT={nt}"]),
 }
 
@@ -55,7 +62,24 @@ def instances():
 
 def sources():
     """The library's own translation units: the .hip files, and the host-only planner (plain C++: no -x hip, no device pass)."""
-    return sorted(glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.cpp")))
+    return sorted(p for p in glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.cpp"))
+                  if os.path.basename(p) not in EXTRA_SOURCES)
+
+
+def extra_instances():
+    """(family, words) of the lines of ekv_instances_kv4.def."""
+    with open(MANIFEST_KV4) as f:
+        found = re.findall(r"^(EKV_[A-Z0-9_]+)\(([^)]*)\)", f.read(), re.M)
+    return [(fam, tuple(w.strip() for w in args.split(","))) for fam, args in found]
+
+
+def extra_objects():
+    """The objects built and linked beside all_objects(): EXTRA_SOURCES and the instances of ekv_instances_kv4.def."""
+    objs = [(os.path.splitext(name)[0], [os.path.join(CSRC, name)]) for name in EXTRA_SOURCES]
+    for fam, words in extra_instances():
+        inc, name, defs = FAMILIES[fam](*words)
+        objs.append((name, defs + ["-x", "hip", os.path.join(CSRC, inc)]))
+    return objs
 
 
 def _instance_objects(combined):
@@ -81,7 +105,7 @@ def all_objects():
 
 
 def headers():
-    return (glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.inc")) + [MANIFEST] +
+    return (glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.inc")) + [MANIFEST, MANIFEST_KV4] +
             [os.path.join(HERE, "..", "include", "easykv_hip.h")])
 
 
@@ -89,7 +113,7 @@ def stale() -> bool:
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    deps = sources() + headers()
+    deps = sources() + [os.path.join(CSRC, name) for name in EXTRA_SOURCES] + headers()
     return any(os.path.getmtime(d) > t for d in deps)
 
 
@@ -102,7 +126,7 @@ def build_lib(force: bool = False, verbose: bool = False, jobs: int = 0) -> str:
     os.makedirs(OBJ, exist_ok=True)
     hdr_t = max(os.path.getmtime(h) for h in headers())
     todo, objs = [], []
-    for name, args in all_objects():
+    for name, args in all_objects() + extra_objects():
         obj = os.path.join(OBJ, name + ".o")
         objs.append(obj)
         src_t = os.path.getmtime(args[-1])

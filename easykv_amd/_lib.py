@@ -33,7 +33,10 @@ MAX_SEQS = 64      # EKV_MAX_SEQS: entries of one batched decode step
 EXPORTS_KV8 = ("ekv_kv8_quantize", "ekv_kv8_dequantize", "ekv_kv8_step_check", "ekv_kv8_step_info", "ekv_kv8_workspace_bytes",
                "ekv_kv8_step_attend", "ekv_kv8_batch_step_check", "ekv_kv8_batch_step_info", "ekv_kv8_batch_workspace_bytes",
                "ekv_kv8_batch_step_attend")
-DTYPE_F32 = 2      # ekv_kv8_dequantize's out_dtype only
+DTYPE_F32 = 2      # ekv_kv8_dequantize's / ekv_kv4_dequantize's out_dtype only
+# the MXFP4 K/V storage calls (include/easykv_hip.h, "kv4"): a list of their own for the same reason
+EXPORTS_KV4 = ("ekv_kv4_quantize", "ekv_kv4_dequantize", "ekv_kv4_step_check", "ekv_kv4_step_info", "ekv_kv4_workspace_bytes",
+               "ekv_kv4_step_attend")
 
 
 class Bank(C.Structure):
@@ -46,6 +49,11 @@ class Bank(C.Structure):
 class Kv8(C.Structure):
     """ekv_kv8: the FP8 code planes and fp32 row scales that stand for a bank's K/V rows (include/easykv_hip.h, "kv8")."""
     _fields_ = [("k_codes", C.c_void_p), ("v_codes", C.c_void_p), ("k_scale", C.c_void_p), ("v_scale", C.c_void_p)]
+
+
+class Kv4(C.Structure):
+    """ekv_kv4: the MXFP4 code planes and E8M0 block exponents that stand for a bank's K/V rows (include/easykv_hip.h, "kv4")."""
+    _fields_ = [("k_codes", C.c_void_p), ("v_codes", C.c_void_p), ("k_exp", C.c_void_p), ("v_exp", C.c_void_p)]
 
 
 class Step(C.Structure):
@@ -79,7 +87,7 @@ def load():
         raise EkvError(f"{LIB} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                        "(hipcc --offload-arch=gfx950).  There is no CPU fallback for the product path.")
     lib = C.CDLL(LIB)
-    for name in EXPORTS + EXPORTS_KV8:
+    for name in EXPORTS + EXPORTS_KV8 + EXPORTS_KV4:
         if not hasattr(lib, name):
             raise EkvError(f"{LIB} does not export {name}")
     vp, i32 = C.c_void_p, C.c_int32
@@ -109,6 +117,12 @@ def load():
     lib.ekv_kv8_step_info.argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, C.POINTER(Kv8), C.POINTER(C.c_int32), C.c_int32]
     lib.ekv_kv8_workspace_bytes.argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, C.POINTER(Kv8)]
     lib.ekv_kv8_step_attend.argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, C.POINTER(Kv8), vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
+    lib.ekv_kv4_quantize.argtypes = [C.POINTER(Bank), C.POINTER(Kv4), i32, i32, i32, i32, vp]
+    lib.ekv_kv4_dequantize.argtypes = [C.POINTER(Bank), C.POINTER(Kv4), i32, i32, i32, i32, vp, vp, vp]
+    lib.ekv_kv4_step_check.argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, C.POINTER(Kv4)]
+    lib.ekv_kv4_step_info.argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, C.POINTER(Kv4), C.POINTER(C.c_int32), C.c_int32]
+    lib.ekv_kv4_workspace_bytes.argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, C.POINTER(Kv4)]
+    lib.ekv_kv4_step_attend.argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, C.POINTER(Kv4), vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
     lib.ekv_batch_step_check.argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, C.POINTER(Seq), i32]
     lib.ekv_batch_step_info.argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, C.POINTER(Seq), i32, C.POINTER(C.c_int32), C.c_int32]
     lib.ekv_batch_workspace_bytes.argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, C.POINTER(Seq), i32]
@@ -117,10 +131,11 @@ def load():
     lib.ekv_kv8_batch_step_info.argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, C.POINTER(Kv8), C.POINTER(Seq), i32, C.POINTER(C.c_int32), C.c_int32]
     lib.ekv_kv8_batch_workspace_bytes.argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, C.POINTER(Kv8), C.POINTER(Seq), i32]
     lib.ekv_kv8_batch_step_attend.argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, C.POINTER(Kv8), C.POINTER(Seq), i32, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
-    for name in EXPORTS[3:] + EXPORTS_KV8:
+    for name in EXPORTS[3:] + EXPORTS_KV8 + EXPORTS_KV4:
         getattr(lib, name).restype = C.c_int
     lib.ekv_workspace_bytes_typed.restype = C.c_size_t
     lib.ekv_kv8_workspace_bytes.restype = C.c_size_t
+    lib.ekv_kv4_workspace_bytes.restype = C.c_size_t
     lib.ekv_batch_workspace_bytes.restype = C.c_size_t
     lib.ekv_kv8_batch_workspace_bytes.restype = C.c_size_t
     if lib.ekv_abi_version() != 8:

@@ -126,7 +126,8 @@ class BudgetedKVCache:
 
     @property
     def kv_quant(self):
-        """None, or "fp8" once the bank's K/V rows are FP8 codes with per-row scales (KVBank.quantize_fp8)."""
+        """None, "fp8" once the bank's K/V rows are FP8 codes with per-row scales (KVBank.quantize_fp8), or "mxfp4" once they are
+        MXFP4 codes with block exponents (KVBank.quantize_mxfp4)."""
         return self.bank.kv_quant
 
     def kv_bytes(self) -> int:
@@ -370,23 +371,29 @@ class _Run:
             raise ValueError("generation_config['kv_dtype'] = bfloat16 with streaming=True: RoPE-on-read has no bf16 build (use float16)")
         # extension key: storage of the K/V rows during the decode phase — None (the 16-bit rows of kv_dtype) or "fp8": the prefill runs on
         # the 16-bit bank as always and the bank is quantised once at the prefill -> decode boundary (KVBank.quantize_fp8: OCP e4m3fn codes
-        # + one fp32 scale per row, 2 * head_dim + 8 bytes per row pair).  kv_dtype keeps meaning the 16-bit type of q / k / v / out.
+        # + one fp32 scale per row, 2 * head_dim + 8 bytes per row pair), or "mxfp4" (KVBank.quantize_mxfp4: e2m1 codes + one E8M0 exponent
+        # per 32 elements, 136 bytes per row pair; head_dim 128, GQA factors up to 4, no batched form).  kv_dtype keeps meaning the 16-bit
+        # type of q / k / v / out.
         self.kv_quant = kv_quant = cfg.get("kv_quant", None)
         shard = getattr(model, "layer_shard", None)
         if shard is not None and shard.world == 1:
             shard = None
-        if kv_quant not in (None, "fp8"):
-            raise ValueError(f"generation_config['kv_quant'] must be None or 'fp8', not {kv_quant!r}")
+        if kv_quant not in (None, "fp8", "mxfp4"):
+            raise ValueError(f"generation_config['kv_quant'] must be None or 'fp8' / 'mxfp4', not {kv_quant!r}")
         if kv_quant is not None:
             if streaming:
-                raise ValueError("generation_config['kv_quant'] = 'fp8' with streaming=True: the FP8 decode kernels have no RoPE-on-read build")
+                raise ValueError(f"generation_config['kv_quant'] = {kv_quant!r} with streaming=True: the quantised decode kernels have no RoPE-on-read build")
             if kv_mode == "ppl":
-                raise ValueError("generation_config['kv_quant'] = 'fp8' with kv_mode='ppl': there is no decode phase to quantise the bank for")
+                raise ValueError(f"generation_config['kv_quant'] = {kv_quant!r} with kv_mode='ppl': there is no decode phase to quantise the bank for")
             if shard is not None:
-                raise ValueError("generation_config['kv_quant'] = 'fp8' is not supported on a layer-sharded model (model.layer_shard)")
-        self.dims = n_layers, _, _, d = _dims(model)
-        if kv_quant is not None and d not in (64, 128):
+                raise ValueError(f"generation_config['kv_quant'] = {kv_quant!r} is not supported on a layer-sharded model (model.layer_shard)")
+        self.dims = n_layers, hq, hkv, d = _dims(model)
+        if kv_quant == "fp8" and d not in (64, 128):
             raise ValueError(f"generation_config['kv_quant'] = 'fp8' needs head_dim 64 or 128 (this model: {d})")
+        if kv_quant == "mxfp4" and d != 128:
+            raise ValueError(f"generation_config['kv_quant'] = 'mxfp4' needs head_dim 128 (this model: {d})")
+        if kv_quant == "mxfp4" and hq // hkv > 4:
+            raise ValueError(f"generation_config['kv_quant'] = 'mxfp4' needs a GQA factor of at most 4 (this model: {hq // hkv})")
         self.dev = torch.device(model.device)
         for p in prompts:
             if p.dim() != 2 or p.shape[0] != 1:
@@ -771,7 +778,9 @@ def generate(self, input_ids, generation_config, kv_mode="encoding", stride=1, r
     else:
         pre = _prefill(run, input_ids, kv_mode)
         cache = pre.cache
-        if run.kv_quant:      # prefill -> decode boundary: the decode steps run on FP8 rows
+        if run.kv_quant == "mxfp4":      # prefill -> decode boundary: the decode steps run on quantised rows
+            cache.bank.quantize_mxfp4()
+        elif run.kv_quant:
             cache.bank.quantize_fp8()
         out_ids, fed = _decode(run, pre, report_decoding_latency and pre.mode == "encoding")
         if pre.mode != "encoding":      # (encoding mode reports the cache the prefill left: printed there)
@@ -806,6 +815,8 @@ def generate_batch(self, input_ids_list, generation_config, kv_mode="encoding", 
         raise ValueError("generate_batch: generation_config['hipgraph'] is not supported")
     if getattr(self, "layer_shard", None) is not None and self.layer_shard.world > 1:
         raise ValueError("generate_batch is not supported on a layer-sharded model (model.layer_shard)")
+    if cfg.get("kv_quant", None) == "mxfp4":
+        raise ValueError("generate_batch: generation_config['kv_quant'] = 'mxfp4' has no batched decode step (use 'fp8' or None)")
     prompts = [p.view(1, -1) if p.dim() == 1 else p for p in input_ids_list]
     if not 1 <= len(prompts) <= _lib.MAX_SEQS or any(p.dim() != 2 or p.shape[0] != 1 for p in prompts):
         raise ValueError(f"generate_batch takes 1..{_lib.MAX_SEQS} prompts of shape [S] or [1, S]")

@@ -77,6 +77,7 @@ static int call_attend(const EkvCall& c, const void* q, const void* k_new, const
   sa.row_stats = aa.row_stats;
   // FP8 rows: the scale planes (they share the storage of stats / colsum, which a decode step — all a kv8 plan can be — never has)
   if (c.kv8) aa.k_scale = c.q8->k_scale, aa.v_scale = c.q8->v_scale;
+  if (c.kv4) aa.k_exp = c.q4->k_exp, aa.v_exp = c.q4->v_exp;      // MXFP4 rows: the exponent planes, in the same storage
   sa.out = static_cast<__half*>(out);
   sa.evict_ids = evict_ids;
   sa.big_rows = f32(P.big_rows);
@@ -87,22 +88,22 @@ static int call_attend(const EkvCall& c, const void* q, const void* k_new, const
     sa.slot_tail_ok = P.slot_tail_ok;
   }
 
-  const bool bf16 = P.bf16 != 0, kv8 = P.kv8 != 0;
+  const bool bf16 = P.bf16 != 0, kv8 = P.kv8 != 0, kv4 = P.kv4 != 0;
   drop_stale_error();
   for (int i = 0; i < P.n_list; ++i) {
     const EkvLaunch& L = P.list[i];
     sa.skip_fold = L.skip_fold;
     hipError_t e = hipSuccess;
     // (a kv8 plan is a decode plan: the decode attention launches and the scorers behind them, which read no K/V element)
-    if (kv8 && (L.kind == EKV_RUN_CHUNK_LDS || L.kind == EKV_RUN_RESIDENT || L.kind == EKV_RUN_CHUNK || L.kind == EKV_RUN_FLUSH)) return EKV_E_UNSUPPORTED;
+    if ((kv8 || kv4) && (L.kind == EKV_RUN_CHUNK_LDS || L.kind == EKV_RUN_RESIDENT || L.kind == EKV_RUN_CHUNK || L.kind == EKV_RUN_FLUSH)) return EKV_E_UNSUPPORTED;
     switch (L.kind) {
       case EKV_RUN_FUSED_DECODE:
         aa.fused_order = P.fused_order;      // (shares its storage with score_tail, which only chunk launches set)
-        e = ekv_launch_decode_fused(aa, sa, tb, D, lc, P.fused_nw, s, bf16, kv8);
+        e = ekv_launch_decode_fused(aa, sa, tb, D, lc, P.fused_nw, s, bf16, kv8, kv4);
         break;
       case EKV_RUN_CHUNK_LDS: e = ekv_launch_chunk_lds(aa, sa, D, lc, s, bf16); break;
       case EKV_RUN_RESIDENT: e = ekv_launch_attn_resident(aa, sa, lc, s, bf16); break;
-      case EKV_RUN_DECODE: e = ekv_launch_attn_decode(aa, tb, D, lc, s, bf16, kv8); break;
+      case EKV_RUN_DECODE: e = ekv_launch_attn_decode(aa, tb, D, lc, s, bf16, kv8, kv4); break;
       case EKV_RUN_CHUNK:
         e = ekv_launch_attn_chunk(aa, D, lc, P.wide, P.two_pass, s, L.fuse ? &sa : nullptr, L.passes, L.tail ? &sa : nullptr, bf16);
         break;
@@ -237,6 +238,47 @@ int ekv_kv8_dequantize(const ekv_bank* bank, const ekv_kv8* q8, int32_t out_dtyp
   drop_stale_error();
   return ekv_launch_kv8_dequantize(bank, q8, out_dtype, layer_begin, layer_count, extent, k_out, v_out, static_cast<hipStream_t>(stream)) == hipSuccess
              ? EKV_OK : EKV_E_LAUNCH;
+}
+
+// MXFP4 K/V storage (include/easykv_hip.h, "kv4")
+int ekv_kv4_step_check(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_kv4* q4) { return call_check(kv4_call(bank, st, dtype, q4)); }
+int ekv_kv4_step_info(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_kv4* q4, int32_t* info, int32_t n_info) {
+  return call_info(kv4_call(bank, st, dtype, q4), info, n_info);
+}
+size_t ekv_kv4_workspace_bytes(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_kv4* q4) {
+  return call_workspace_bytes(kv4_call(bank, st, dtype, q4));
+}
+int ekv_kv4_step_attend(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_kv4* q4, const void* q, const void* k_new,
+                        const void* v_new, void* out, int32_t* evict_ids, const float* rope_cos, const float* rope_sin,
+                        void* workspace, size_t workspace_bytes, void* stream) {
+  return call_attend(kv4_call(bank, st, dtype, q4), q, k_new, v_new, out, evict_ids, rope_cos, rope_sin, workspace, workspace_bytes, stream);
+}
+
+static int kv4_convert_check(const ekv_bank* bank, const ekv_kv4* q4, int32_t layer_begin, int32_t layer_count, int32_t extent) {
+  if (!bank || !q4 || !q4->k_codes || !q4->v_codes || !q4->k_exp || !q4->v_exp) return EKV_E_ARG;
+  if (bank->n_layers <= 0 || bank->n_kv_heads <= 0 || bank->cap <= 0) return EKV_E_ARG;
+  if (int e = check_layers(bank, layer_begin, layer_count)) return e;
+  if (extent < 0 || extent > bank->cap) return EKV_E_ARG;
+  if (bank->head_dim != 128) return EKV_E_UNSUPPORTED;
+  return EKV_OK;
+}
+
+int ekv_kv4_quantize(const ekv_bank* bank, const ekv_kv4* q4, int32_t dtype, int32_t layer_begin, int32_t layer_count, int32_t extent,
+                     void* stream) {
+  if (dtype != EKV_DTYPE_F16 && dtype != EKV_DTYPE_BF16) return EKV_E_ARG;
+  if (int e = kv4_convert_check(bank, q4, layer_begin, layer_count, extent)) return e;
+  if (!bank->k || !bank->v) return EKV_E_ARG;
+  drop_stale_error();
+  return launch_code(ekv_launch_kv4_quantize(bank, q4, dtype == EKV_DTYPE_BF16, layer_begin, layer_count, extent, static_cast<hipStream_t>(stream)));
+}
+
+int ekv_kv4_dequantize(const ekv_bank* bank, const ekv_kv4* q4, int32_t out_dtype, int32_t layer_begin, int32_t layer_count,
+                       int32_t extent, void* k_out, void* v_out, void* stream) {
+  if (out_dtype != EKV_DTYPE_F16 && out_dtype != EKV_DTYPE_BF16 && out_dtype != EKV_DTYPE_F32) return EKV_E_ARG;
+  if (int e = kv4_convert_check(bank, q4, layer_begin, layer_count, extent)) return e;
+  if (!k_out || !v_out) return EKV_E_ARG;
+  drop_stale_error();
+  return launch_code(ekv_launch_kv4_dequantize(bank, q4, out_dtype, layer_begin, layer_count, extent, k_out, v_out, static_cast<hipStream_t>(stream)));
 }
 
 // ---- bank utilities: argument checks here, kernels and launch code in ekv_bank_ops.hip

@@ -136,6 +136,78 @@ __device__ __forceinline__ float ekv_widen8_amax(const uint4& v, float* f) {
   return m;
 }
 
+// ---- MXFP4 K/V rows ("kv4", include/easykv_hip.h): e2m1 codes, two per byte, one E8M0 exponent per 32-element block ----
+// A lane's 16-byte piece of a row is the 32 codes of ONE block.  Widening a code is exact in every target type (one mantissa bit), so
+// the K side runs on the packed-pair dot product of the 16-bit builds (v_cvt_scalef32_pk_{f16,bf16}_fp4 with scale 1, the block's 2^e
+// applied to the lane's partial sum) and the V side on v_cvt_scalef32_pk_f32_fp4 with the block's scale + fma.
+// Exponent byte of a block from its maximum: the smallest e with amax <= 6 * 2^e = 1.5 * 2^(e + 2), i.e. the float's own exponent
+// minus 2, plus one when its mantissa exceeds 1.5 (the carry of the addition below); clamped to [-126, 127], 0 for an all-zero block.
+__device__ __forceinline__ uint32_t ekv_fp4_block_exp(float amax) {
+  if (amax == 0.f) return 127u;
+  const int b = (int)((__float_as_uint(amax) + 0x3FFFFFu) >> 23) - 2;
+  return (uint32_t)min(max(b, 1), 254);
+}
+// 2^(byte - 127) as the fp32 the conversions read their scale from (byte in [1, 254]: a normal number)
+__device__ __forceinline__ float ekv_fp4_exp_scale(uint32_t byte) { return __uint_as_float(byte << 23); }
+// 8 values -> 8 codes (one 32-bit word): RNE(x / scale), element 2i in the low nibble of byte i
+__device__ __forceinline__ uint32_t ekv_fp4_quant8(const float* f, float scale) {
+  uint32_t w = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(0u, f[0], f[1], scale, 0);
+  w = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(w, f[2], f[3], scale, 1);
+  w = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(w, f[4], f[5], scale, 2);
+  w = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(w, f[6], f[7], scale, 3);
+  return w;
+}
+template <int SEL>
+__device__ __forceinline__ ekv_h2 ekv_fp4_pk_e(uint32_t w) {
+#if EKV_BF16
+  return __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, 1.0f, SEL);
+#else
+  return __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, 1.0f, SEL);
+#endif
+}
+// 8 query elements . the 8 codes of one word
+__device__ __forceinline__ float ekv_dot8_fp4(const uint4& q, uint32_t c, float acc) {
+  acc = EKV_FDOT2(__builtin_bit_cast(ekv_h2, q.x), ekv_fp4_pk_e<0>(c), acc, false);
+  acc = EKV_FDOT2(__builtin_bit_cast(ekv_h2, q.y), ekv_fp4_pk_e<1>(c), acc, false);
+  acc = EKV_FDOT2(__builtin_bit_cast(ekv_h2, q.z), ekv_fp4_pk_e<2>(c), acc, false);
+  acc = EKV_FDOT2(__builtin_bit_cast(ekv_h2, q.w), ekv_fp4_pk_e<3>(c), acc, false);
+  return acc;
+}
+// 32 query elements . the 32 codes of a block (the block's scale is the caller's business)
+__device__ __forceinline__ float ekv_dot32_fp4(const uint4 (&q)[4], const uint4& c, float acc) {
+  acc = ekv_dot8_fp4(q[0], c.x, acc);
+  acc = ekv_dot8_fp4(q[1], c.y, acc);
+  acc = ekv_dot8_fp4(q[2], c.z, acc);
+  return ekv_dot8_fp4(q[3], c.w, acc);
+}
+// the 8 codes of one word times the block's scale, as fp32 (exact)
+__device__ __forceinline__ void ekv_fp4_widen8(uint32_t w, float scale, float* f) {
+  const ekv_f2 a = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, scale, 0), b = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, scale, 1);
+  const ekv_f2 c = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, scale, 2), d = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, scale, 3);
+  f[0] = a[0], f[1] = a[1], f[2] = b[0], f[3] = b[1], f[4] = c[0], f[5] = c[1], f[6] = d[0], f[7] = d[1];
+}
+// o[0..32) += p * (codes * scale)
+__device__ __forceinline__ void ekv_axpy32_fp4(float p, float scale, const uint4& c, float (&o)[32]) {
+  const uint32_t w[4] = {c.x, c.y, c.z, c.w};
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    float f[8];
+    ekv_fp4_widen8(w[i], scale, f);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) o[8 * i + j] = fmaf(p, f[j], o[8 * i + j]);
+  }
+}
+// 32 source elements (four 16-byte pieces) -> their block: 16 bytes of codes, the exponent byte in `e`
+__device__ __forceinline__ uint4 ekv_fp4_quant_block(const uint4* src, uint32_t& e) {
+  float f[32];
+  float amax = 0.f;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) amax = fmaxf(amax, ekv_widen8_amax(src[i], f + 8 * i));
+  e = ekv_fp4_block_exp(amax);
+  const float s = ekv_fp4_exp_scale(e);
+  return uint4{ekv_fp4_quant8(f, s), ekv_fp4_quant8(f + 8, s), ekv_fp4_quant8(f + 16, s), ekv_fp4_quant8(f + 24, s)};
+}
+
 // f32 -> one 16-bit output element, rounded to nearest even (bf16: v_cvt_pk_bf16_f32, NaN kept), as the __half the row pointers hold
 __device__ __forceinline__ __half ekv_to_e(float x) {
 #if EKV_BF16

@@ -42,6 +42,13 @@ struct EkvNoop {
 // before the axpy.  The scales of an iteration's KU rows are read as 16-byte vectors when the rows are consecutive (PHYS) and per row
 // through the slot map otherwise.  The appended row is quantised here (row maximum over the lane group, codes + scale stored) and
 // takes part in the step AS QUANTISED, so the bank's contents alone determine the step.
+//
+// MXFP4 rows (EPL = 32; plain keys, head_dim 128): a.k / a.v are the code planes, two e2m1 codes per byte, and a.k_exp / a.v_exp the
+// E8M0 bytes, four per row at the same physical index.  A row is a 4-lane group and a lane's piece is exactly ONE block: 32 codes
+// against 32 query elements, so the block's 2^e multiplies the lane's partial dot product BEFORE the lane-group sum, and on the V
+// side goes into the conversion of the lane's codes to fp32.  The exponent words of an iteration's KU rows are read as 16-byte
+// vectors when the rows are consecutive (PHYS) and per row through the slot map otherwise.  The appended row is quantised here, one
+// block per lane, and takes part in the step as quantised.
 template <int D, int REP, bool ROPE, bool SLOT_LDS, int NW = 4, bool PHYS = false, int KU = kU, typename MaskReady = EkvNoop, int EPL = 8>
 __device__ __forceinline__ void ekv_decode_stream(const EkvAttnArgs& a, const int32_t* s_slot, float* logit_out,
                                                   int logit_stride, int t0, int t1_in, int ll, int h, size_t head_row,
@@ -50,9 +57,11 @@ __device__ __forceinline__ void ekv_decode_stream(const EkvAttnArgs& a, const in
                                                   int n_rep_real = 0, int q_head0 = -1) {
   using Gm = EkvDecodeGeom<D, NW, KU, EPL>;
   constexpr int LPR = Gm::LPR, RW = Gm::RW, LIVE = Gm::LIVE;
-  constexpr bool KV8 = EPL == 16;
-  static_assert(EPL == 8 || (KV8 && !ROPE && LIVE == LPR), "FP8 rows: plain keys, head_dim 64 / 128");
+  constexpr bool KV8 = EPL == 16, KV4 = EPL == 32;
+  static_assert(EPL == 8 || (KV8 && !ROPE && LIVE == LPR) || KV4, "FP8 rows: plain keys, head_dim 64 / 128");
+  static_assert(!KV4 || (!ROPE && D == 128 && LPR == 4), "MXFP4 rows: plain keys, head_dim 128 (a lane = one 32-element block)");
   constexpr int ESZ = KV8 ? 1 : 2;      // bytes per stored K/V element
+  constexpr int ROWB = KV4 ? D / 2 : D * ESZ;      // bytes per stored K/V row
   constexpr bool PADDED = LIVE != LPR;      // head_dim 96: lanes sub >= LIVE of a lane group are idle (zero pieces, no loads / stores)
   constexpr int kNW = NW;
   static_assert(!(PHYS && (ROPE || SLOT_LDS)), "physical-order streaming: plain keys, global slot map");
@@ -69,12 +78,17 @@ __device__ __forceinline__ void ekv_decode_stream(const EkvAttnArgs& a, const in
   const int hq0 = q_head0 >= 0 ? q_head0 : h * REP;
 
   uint4 qv[REP], qv1[REP];      // (qv1: FP8 rows, query elements 8..15 of the lane's 16)
+  uint4 qx[KV4 ? REP : 1][4];      // (MXFP4 rows: the lane's 32 query elements)
   float qf[REP][8];  // ROPE: rotated query q' (fp32)
 #pragma unroll
   for (int r = 0; r < REP; ++r) {
     const __half* qp = a.q + ((size_t)ll * a.n_q_heads + hq0 + min(r, nrep - 1)) * D;
     qv[r] = live_lane ? reinterpret_cast<const uint4*>(qp)[sub * (EPL / 8)] : uint4{0, 0, 0, 0};
     qv1[r] = KV8 ? reinterpret_cast<const uint4*>(qp)[sub * 2 + 1] : uint4{0, 0, 0, 0};
+    if constexpr (KV4) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) qx[r][i] = reinterpret_cast<const uint4*>(qp)[sub * 4 + i];
+    }
 #pragma unroll
     for (int i = 0; i < 8; ++i) qf[r][i] = 0.f;
     if (ROPE && live_lane) {
@@ -209,6 +223,16 @@ __device__ __forceinline__ void ekv_decode_stream(const EkvAttnArgs& a, const in
         a.k_scale[head_row + slot_new] = ksn;
         a.v_scale[head_row + slot_new] = vsn;
       }
+    } else if constexpr (KV4) {
+      // quantise the new row (rule: include/easykv_hip.h): each lane's 32 elements are one block — 16 bytes of codes + one exponent byte
+      uint32_t ke, ve;
+      kn = ekv_fp4_quant_block(reinterpret_cast<const uint4*>(k_new_row) + sub * 4, ke);
+      vn = ekv_fp4_quant_block(reinterpret_cast<const uint4*>(v_new_row) + sub * 4, ve);
+      ksn = ekv_fp4_exp_scale(ke), vsn = ekv_fp4_exp_scale(ve);
+      reinterpret_cast<uint4*>(reinterpret_cast<uint8_t*>(a.k_w) + off / 2)[sub] = kn;
+      reinterpret_cast<uint4*>(reinterpret_cast<uint8_t*>(a.v_w) + off / 2)[sub] = vn;
+      a.k_exp[(head_row + slot_new) * 4 + sub] = (uint8_t)ke;
+      a.v_exp[(head_row + slot_new) * 4 + sub] = (uint8_t)ve;
     } else if (live_lane) {
       kn = reinterpret_cast<const uint4*>(k_new_row)[sub];
       vn = reinterpret_cast<const uint4*>(v_new_row)[sub];
@@ -230,6 +254,8 @@ __device__ __forceinline__ void ekv_decode_stream(const EkvAttnArgs& a, const in
         for (int i = 0; i < 8; ++i) acc = fmaf(kpn[i], qf[r][i], acc);
       } else if constexpr (KV8) {
         acc = ekv_dot16_fp8(qv[r], qv1[r], kn, 0.f);
+      } else if constexpr (KV4) {
+        acc = ekv_dot32_fp4(qx[r], kn, 0.f) * ksn;      // (this lane's block scale, before the group sum)
       } else {
         acc = ekv_dot8(qv[r], kn, 0.f);
       }
@@ -243,6 +269,7 @@ __device__ __forceinline__ void ekv_decode_stream(const EkvAttnArgs& a, const in
 #pragma unroll
       for (int i = 0; i < EPL; ++i) o[r][i] *= alpha;
       if constexpr (KV8) ekv_axpy16_fp8(p * vsn, vn, o[r]);
+      else if constexpr (KV4) ekv_axpy32_fp4(p, vsn, vn, o[r]);
       else ekv_axpy8(p, vn, o[r]);
       m[r] = mn;
     }
@@ -265,7 +292,7 @@ __device__ __forceinline__ void ekv_decode_stream(const EkvAttnArgs& a, const in
   }
   auto iteration = [&](const int base, auto&& after_issue) {
     uint4 kr[KU], vr[KU];
-    float ksc[KV8 ? KU : 1], vsc[KV8 ? KU : 1];      // FP8 rows: the scales of the KU rows
+    float ksc[KV8 || KV4 ? KU : 1], vsc[KV8 || KV4 ? KU : 1];      // FP8 rows: the scales of the KU rows; MXFP4 rows: of this lane's block of each
     const int j0 = base + grp * KU;
     if constexpr (KV8 && PHYS) {
       // consecutive physical rows: KU / 4 16-byte loads per plane (fused step: cap % 4 == 0, so head_row + j0 is 16-byte aligned); a
@@ -287,6 +314,32 @@ __device__ __forceinline__ void ekv_decode_stream(const EkvAttnArgs& a, const in
         }
       }
     }
+    if constexpr (KV4 && PHYS) {
+      // consecutive physical rows: their exponent words (4 bytes per row) as KU / 4 16-byte loads per plane, under the bound of the FP8
+      // scales above; lane `sub` of a row's group keeps byte `sub`, its own block's
+      uint32_t kw[KU], vw[KU];
+      if (j0 + KU <= a.cap) {
+        const uint4* k4 = reinterpret_cast<const uint4*>(a.k_exp + (head_row + j0) * 4);
+        const uint4* v4 = reinterpret_cast<const uint4*>(a.v_exp + (head_row + j0) * 4);
+#pragma unroll
+        for (int i = 0; i < KU / 4; ++i) {
+          const uint4 kk = k4[i], vv = v4[i];
+          kw[4 * i] = kk.x, kw[4 * i + 1] = kk.y, kw[4 * i + 2] = kk.z, kw[4 * i + 3] = kk.w;
+          vw[4 * i] = vv.x, vw[4 * i + 1] = vv.y, vw[4 * i + 2] = vv.z, vw[4 * i + 3] = vv.w;
+        }
+      } else {
+#pragma unroll
+        for (int u = 0; u < KU; ++u) {
+          kw[u] = reinterpret_cast<const uint32_t*>(a.k_exp)[head_row + min(j0 + u, a.cap - 1)];
+          vw[u] = reinterpret_cast<const uint32_t*>(a.v_exp)[head_row + min(j0 + u, a.cap - 1)];
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < KU; ++u) {
+        ksc[u] = ekv_fp4_exp_scale((kw[u] >> (8 * sub)) & 0xFFu);
+        vsc[u] = ekv_fp4_exp_scale((vw[u] >> (8 * sub)) & 0xFFu);
+      }
+    }
     int cur[KU];
 #pragma unroll
     for (int i = 0; i < KU / 4; ++i) {
@@ -305,11 +358,15 @@ __device__ __forceinline__ void ekv_decode_stream(const EkvAttnArgs& a, const in
       const int j = j0 + u;
       const int jj = j < t1 ? j : t1 - 1;
       const int row = PHYS ? jj : (SLOT_LDS ? s_slot[jj - t0] : (j < t1 ? cur[u] : last_slot));
-      const char* kp = reinterpret_cast<const char*>(a.k) + (head_row + row) * (D * ESZ);
-      const char* vp = reinterpret_cast<const char*>(a.v) + (head_row + row) * (D * ESZ);
+      const char* kp = reinterpret_cast<const char*>(a.k) + (head_row + row) * ROWB;
+      const char* vp = reinterpret_cast<const char*>(a.v) + (head_row + row) * ROWB;
       if constexpr (KV8 && !PHYS) {      // rows through the slot map: one scale per row (the lanes of a group read the same word)
         ksc[u] = a.k_scale[head_row + row];
         vsc[u] = a.v_scale[head_row + row];
+      }
+      if constexpr (KV4 && !PHYS) {      // rows through the slot map: this lane's exponent byte of each row
+        ksc[u] = ekv_fp4_exp_scale(a.k_exp[(head_row + row) * 4 + sub]);
+        vsc[u] = ekv_fp4_exp_scale(a.v_exp[(head_row + row) * 4 + sub]);
       }
       // K/V rows are read exactly once per step and the cache (>1 GB) never fits L2/MALL: non-temporal loads
       // (measured on MI355X: 5.5 -> 6.1 TB/s on the pure stream)
@@ -331,6 +388,7 @@ __device__ __forceinline__ void ekv_decode_stream(const EkvAttnArgs& a, const in
         if ((dead8 >> u) & 1u) {
           vr[u] = uint4{0, 0, 0, 0};
           if constexpr (KV8) vsc[u] = 0.f;
+          if constexpr (KV4) vsc[u] = 1.f;      // (zero codes under a finite scale)
         }
     }
     float sall[ROPE ? REP : 1][KU];   // ROPE: every row is rotated once, then dotted with all REP queries
@@ -361,7 +419,9 @@ __device__ __forceinline__ void ekv_decode_stream(const EkvAttnArgs& a, const in
         if (ROPE) {
           s[u] = sall[r][u];
         } else {
-          float acc = KV8 ? ekv_dot16_fp8(qv[r], qv1[r], kr[u], 0.f) : ekv_dot8(qv[r], kr[u], 0.f);
+          float acc;
+          if constexpr (KV4) acc = ekv_dot32_fp4(qx[r], kr[u], 0.f) * ksc[u];      // (the lane's block scale, before the group sum)
+          else acc = KV8 ? ekv_dot16_fp8(qv[r], qv1[r], kr[u], 0.f) : ekv_dot8(qv[r], kr[u], 0.f);
           acc = ekv_group_sum<LPR>(acc);
           if constexpr (KV8) acc *= ksc[u];
           s[u] = (PHYS ? !((dead8 >> u) & 1u) : (j0 + u < t1)) ? acc / a.sm_div : EKV_NEG_INF;
@@ -393,6 +453,7 @@ __device__ __forceinline__ void ekv_decode_stream(const EkvAttnArgs& a, const in
         const float p = exp2f((s[u] - mn) * EKV_LOG2E);
         l[r] += p;
         if constexpr (KV8) ekv_axpy16_fp8(p * vsc[u], vr[u], o[r]);
+        else if constexpr (KV4) ekv_axpy32_fp4(p, vsc[u], vr[u], o[r]);
         else ekv_axpy8(p, vr[u], o[r]);
       }
       m[r] = mn;

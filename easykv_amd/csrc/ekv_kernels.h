@@ -42,6 +42,7 @@ struct EkvStepPlan {
   int32_t slot_rows, slot_tail_ok;   // fused decode step on the slot-indexed score rows (EKV_PHASE_SLOT_ROWS / _TAIL_OK)
   int32_t bf16;             // 16-bit tensors are bf16: the launches run the EKV_BF16 kernel instances
   int32_t kv8;              // the bank's K/V rows are FP8 codes + row scales (an ekv_kv8 call): the decode launches run the kv8 instances
+  int32_t kv4;              // the bank's K/V rows are MXFP4 codes + block exponents (an ekv_kv4 call): the decode launches run the kv4 instances
   int32_t batch;            // a batched decode step (an ekv_seq call): the plan of the envelope; the launches run the batch instances
   int32_t strides[6];       // q, kv, out row strides (token, head) in elements, the dense layout filled in
   // Workspace: byte offsets of this call's slices (a deferred call's layout spans every deferred layer), -1 = not in the layout
@@ -87,13 +88,17 @@ struct EkvAttnArgs {
   // FP8 rows (ekv_kv8_step_attend; the decode kernels' kv8 instances only — decode steps have no use for `stats` / `colsum`, whose
   // storage the two pointers share, so the struct and with it every 16-bit kernel instance stays as it was): k / v / k_w / v_w are the
   // code planes, one byte per element, and k_scale / v_scale the fp32 row scales [n_layers][H][cap] at the rows' physical indices
+  // MXFP4 rows (ekv_kv4_step_attend; the kv4 instances only), likewise: k / v / k_w / v_w are the code planes, two codes per byte, and
+  // k_exp / v_exp the E8M0 bytes [n_layers][H][cap][head_dim / 32]
   union {
     float* stats;      // two-pass chunk steps: [layer_count][Hq][q_len][2*n_split][2] (max, sum exp) per key-range half split
     float* k_scale;
+    uint8_t* k_exp;
   };
   union {
     float* colsum;     // two-pass chunk steps: [layer_count][H][n_col_parts][2][t_pad] column sums of pbar and pbar^2
     float* v_scale;
+    uint8_t* v_exp;
   };
   int32_t n_col_parts;   // = query-tile waves per workgroup (2 or 4) * n_qblocks
   int32_t n_q_heads, n_kv_heads, cap, n_slots, q_len, n_split, rows_per_split, t_pad, layer_begin, causal;
@@ -156,7 +161,9 @@ struct EkvScoreArgs {
 // tb (the decode launchers): NULL = a uniform step of `count` layers; the table of a batched decode step = the batch instances (16-bit
 // or FP8 rows, plain keys, ordered score rows): `a` / `sc` are the envelope's arguments with layer_begin = 0 and a.arrive = the bank's
 // counters, and `count` is the number of table entries, one workgroup row each.
-hipError_t ekv_launch_attn_decode(const EkvAttnArgs& a, const EkvSeqTable* tb, int head_dim, int count, hipStream_t s, bool bf16, bool kv8);
+// kv4: the MXFP4 instances (EKV_DECODE_KV4 lines of the manifest; never together with kv8 or a table)
+hipError_t ekv_launch_attn_decode(const EkvAttnArgs& a, const EkvSeqTable* tb, int head_dim, int count, hipStream_t s, bool bf16, bool kv8,
+                                  bool kv4 = false);
 // passes (wide-block kernel, two-pass scheme): bit 0 = the one pass (output + row statistics), bit 1 = the column-sum pass
 // tail_sc (wide-block kernel, two passes, passes & 2): the step's scorer runs as the tail of the column-sum pass (ekv_wide_tail.h)
 // wide: the wide-block kernel (ekv_chunk_wide, ekv_plan.h)
@@ -166,7 +173,7 @@ hipError_t ekv_launch_attn_resident(const EkvAttnArgs& a, const EkvScoreArgs& sc
 hipError_t ekv_launch_tova_headmean(const EkvScoreArgs& a, int layer_count, hipStream_t s);
 hipError_t ekv_launch_score_select(const EkvScoreArgs& a, int layer_count, hipStream_t s, bool bf16);
 hipError_t ekv_launch_decode_fused(const EkvAttnArgs& a, const EkvScoreArgs& sc, const EkvSeqTable* tb, int head_dim, int count, int nw,
-                                   hipStream_t s, bool bf16, bool kv8);
+                                   hipStream_t s, bool bf16, bool kv8, bool kv4 = false);
 // What workgroup (head, entry z) of a batch instance does first: its argument structs are the envelope's with the per-step fields
 // replaced by its entry's (scalar loads from the kernel arguments).  layer_begin = layer - z: every `layer_begin + ll` of the kernel
 // body then names the entry's bank layer, while the workspace and the call's tensors stay indexed by ll = z.
@@ -221,6 +228,9 @@ __device__ __forceinline__ EkvScoreArgs ekv_batch_score_args(const EkvScoreArgs&
 #if defined(EKV_KV8) && EKV_KV8
 #define EKV_ROWS kv8
 #define EKV_ROWS_TAG _kv8
+#elif defined(EKV_KV4) && EKV_KV4
+#define EKV_ROWS kv4
+#define EKV_ROWS_TAG _kv4
 #else
 #define EKV_ROWS kv16
 #define EKV_ROWS_TAG
@@ -262,6 +272,11 @@ __device__ __forceinline__ EkvScoreArgs ekv_batch_score_args(const EkvScoreArgs&
 hipError_t ekv_launch_kv8_quantize(const ekv_bank* bank, const ekv_kv8* q8, bool src_bf16, int layer_begin, int layer_count, int extent,
                                    hipStream_t s);
 hipError_t ekv_launch_kv8_dequantize(const ekv_bank* bank, const ekv_kv8* q8, int out_kind, int layer_begin, int layer_count, int extent,
+                                     void* k_out, void* v_out, hipStream_t s);
+// MXFP4 bank conversion (ekv_kv4.hip), same arguments
+hipError_t ekv_launch_kv4_quantize(const ekv_bank* bank, const ekv_kv4* q4, bool src_bf16, int layer_begin, int layer_count, int extent,
+                                   hipStream_t s);
+hipError_t ekv_launch_kv4_dequantize(const ekv_bank* bank, const ekv_kv4* q4, int out_kind, int layer_begin, int layer_count, int extent,
                                      void* k_out, void* v_out, hipStream_t s);
 hipError_t ekv_launch_decode_score(const EkvScoreArgs& sc, const EkvSeqTable* tb, int count, hipStream_t s, bool bf16);
 hipError_t ekv_launch_fold(const EkvScoreArgs& sc, int layer_count, hipStream_t s, bool bf16);

@@ -1,0 +1,133 @@
+// MXFP4 K/V storage ("kv4", include/easykv_hip.h; head_dim 128): conversion of a 16-bit bank to e2m1 codes + E8M0 block exponents at the
+// same physical rows, and the inverse.  One pass, 16-byte loads, one lane per 32-element block (four lanes per row): a lane reads its
+// block's 64 source bytes, takes the exponent from the bits of the block maximum and packs the codes with v_cvt_scalef32_pk_fp4_f32.
+#include "ekv_common.h"
+#include "ekv_kernels.h"
+
+namespace {
+
+constexpr int kBlocks = 4;      // blocks (lanes) per row at head_dim 128
+
+// block b of the launch -> index of physical row (layer_begin + r / (H * extent), head, row) in a [layers][H][cap] array; r = b / 4
+__device__ __forceinline__ size_t kv4_row(long long r, int n_kv_heads, int cap, int layer_begin, int extent) {
+  const long long lh = r / extent;
+  return ((size_t)layer_begin * n_kv_heads + (size_t)lh) * cap + (size_t)(r % extent);
+}
+
+// BF: the source elements are bf16.  (Both element types in one unit: the widening is spelled out instead of going through ekv_e.)
+template <bool BF>
+__global__ void __launch_bounds__(256) ekv_kv4_quantize_kernel(const uint4* __restrict__ k, const uint4* __restrict__ v, uint4* __restrict__ kc,
+                                                               uint4* __restrict__ vc, uint8_t* __restrict__ ke, uint8_t* __restrict__ ve,
+                                                               int n_kv_heads, int cap, int layer_begin, int extent, long long n_rows) {
+  const int sub = threadIdx.x % kBlocks;
+  const long long r = (long long)blockIdx.x * (256 / kBlocks) + threadIdx.x / kBlocks;
+  if (r >= n_rows) return;
+  const size_t row = kv4_row(r, n_kv_heads, cap, layer_begin, extent);
+  auto one = [&](const uint4* src, uint4* codes, uint8_t* exps) {
+    float f[32];
+    float amax = 0.f;
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      const uint4 x = __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const ekv_u4*>(src + row * 16) + sub * 4 + p));
+      const uint32_t w[4] = {x.x, x.y, x.z, x.w};
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        float a, b;
+        if (BF) {
+          a = __uint_as_float(w[i] << 16);
+          b = __uint_as_float(w[i] & 0xFFFF0000u);
+        } else {
+          typedef _Float16 h2 __attribute__((ext_vector_type(2)));
+          const h2 h = __builtin_bit_cast(h2, w[i]);
+          a = (float)h[0];
+          b = (float)h[1];
+        }
+        f[8 * p + 2 * i] = a;
+        f[8 * p + 2 * i + 1] = b;
+        amax = fmaxf(amax, fmaxf(fabsf(a), fabsf(b)));
+      }
+    }
+    const uint32_t e = ekv_fp4_block_exp(amax);
+    const float s = ekv_fp4_exp_scale(e);
+    codes[row * kBlocks + sub] = uint4{ekv_fp4_quant8(f, s), ekv_fp4_quant8(f + 8, s), ekv_fp4_quant8(f + 16, s), ekv_fp4_quant8(f + 24, s)};
+    exps[row * kBlocks + sub] = (uint8_t)e;
+  };
+  one(k, kc, ke);
+  one(v, vc, ve);
+}
+
+// OUT: 0 fp16, 1 bf16, 2 fp32.  One thread per block; out is dense [rows][128].
+template <int OUT>
+__global__ void __launch_bounds__(256) ekv_kv4_dequantize_kernel(const uint4* __restrict__ kc, const uint4* __restrict__ vc, const uint8_t* __restrict__ ke,
+                                                                 const uint8_t* __restrict__ ve, void* __restrict__ k_out, void* __restrict__ v_out,
+                                                                 int n_kv_heads, int cap, int layer_begin, int extent, long long n_rows) {
+  const int sub = threadIdx.x % kBlocks;
+  const long long r = (long long)blockIdx.x * (256 / kBlocks) + threadIdx.x / kBlocks;
+  if (r >= n_rows) return;
+  const size_t row = kv4_row(r, n_kv_heads, cap, layer_begin, extent);
+  auto one = [&](const uint4* codes, const uint8_t* exps, void* out) {
+    const uint4 c = codes[row * kBlocks + sub];
+    const float s = ekv_fp4_exp_scale(exps[row * kBlocks + sub]);
+    float f[32];
+    ekv_fp4_widen8(c.x, s, f), ekv_fp4_widen8(c.y, s, f + 8), ekv_fp4_widen8(c.z, s, f + 16), ekv_fp4_widen8(c.w, s, f + 24);
+    const size_t o = ((size_t)r * kBlocks + sub) * 32;
+    if (OUT == 2) {
+      float4* p = reinterpret_cast<float4*>(static_cast<float*>(out) + o);
+#pragma unroll
+      for (int i = 0; i < 8; ++i) p[i] = float4{f[4 * i], f[4 * i + 1], f[4 * i + 2], f[4 * i + 3]};
+    } else {
+      uint32_t w[16];
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        if (OUT == 1) {
+          typedef __bf16 b2 __attribute__((ext_vector_type(2)));
+          w[i] = __builtin_bit_cast(uint32_t, b2{(__bf16)f[2 * i], (__bf16)f[2 * i + 1]});
+        } else {
+          w[i] = __builtin_bit_cast(uint32_t, __floats2half2_rn(f[2 * i], f[2 * i + 1]));
+        }
+      }
+      uint4* p = reinterpret_cast<uint4*>(static_cast<uint16_t*>(out) + o);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) p[i] = uint4{w[4 * i], w[4 * i + 1], w[4 * i + 2], w[4 * i + 3]};
+    }
+  };
+  one(kc, ke, k_out);
+  one(vc, ve, v_out);
+}
+
+inline dim3 kv4_grid(long long n_rows) { return dim3((unsigned)((n_rows + 256 / kBlocks - 1) / (256 / kBlocks))); }
+
+}  // namespace
+
+hipError_t ekv_launch_kv4_quantize(const ekv_bank* bank, const ekv_kv4* q4, bool src_bf16, int layer_begin, int layer_count, int extent,
+                                   hipStream_t s) {
+  if (bank->head_dim != 128) return hipErrorInvalidValue;
+  const long long n_rows = (long long)layer_count * bank->n_kv_heads * extent;
+  if (n_rows == 0) return hipSuccess;
+#define EKV_KV4_Q(BF)                                                                                                           \
+  hipLaunchKernelGGL((ekv_kv4_quantize_kernel<BF>), kv4_grid(n_rows), dim3(256), 0, s, static_cast<const uint4*>(bank->k),     \
+                     static_cast<const uint4*>(bank->v), static_cast<uint4*>(q4->k_codes), static_cast<uint4*>(q4->v_codes),   \
+                     q4->k_exp, q4->v_exp, bank->n_kv_heads, bank->cap, layer_begin, extent, n_rows)
+  if (src_bf16) EKV_KV4_Q(true); else EKV_KV4_Q(false);
+#undef EKV_KV4_Q
+  return hipGetLastError();
+}
+
+hipError_t ekv_launch_kv4_dequantize(const ekv_bank* bank, const ekv_kv4* q4, int out_kind, int layer_begin, int layer_count, int extent,
+                                     void* k_out, void* v_out, hipStream_t s) {
+  if (bank->head_dim != 128) return hipErrorInvalidValue;
+  const long long n_rows = (long long)layer_count * bank->n_kv_heads * extent;
+  if (n_rows == 0) return hipSuccess;
+#define EKV_KV4_DQ(OUT)                                                                                                         \
+  hipLaunchKernelGGL((ekv_kv4_dequantize_kernel<OUT>), kv4_grid(n_rows), dim3(256), 0, s, static_cast<const uint4*>(q4->k_codes), \
+                     static_cast<const uint4*>(q4->v_codes), q4->k_exp, q4->v_exp, k_out, v_out, bank->n_kv_heads, bank->cap,   \
+                     layer_begin, extent, n_rows)
+  switch (out_kind) {
+    case 0: EKV_KV4_DQ(0); break;
+    case 1: EKV_KV4_DQ(1); break;
+    case 2: EKV_KV4_DQ(2); break;
+    default: return hipErrorInvalidValue;
+  }
+#undef EKV_KV4_DQ
+  return hipGetLastError();
+}

@@ -627,6 +627,7 @@ int ekv_plan_step(const ekv_bank* bank, const ekv_step* step, EkvStepPlan* P) {
 // FP8 rows: the code planes stand where the 16-bit rows were (bank->k / bank->v are not read), and the plan is that of the 16-bit step
 // of the same shape (the scorers read logits and partials, never a K/V element, so splits, launches and workspace carry over), run on
 // the kv8 instances of the two decode attention kernels — which is all a kv8 bank has: decode steps, plain keys, head_dim 64 / 128.
+// MXFP4 rows (an ekv_kv4_* call): the same stage with the kv4 planes and instances — decode steps, plain keys, head_dim 128, GQA <= 4.
 // A batched decode step (include/easykv_hip.h, ekv_seq): the plan of the uniform step of the batch's ENVELOPE — the longest entry, the
 // widest extent, one "layer" per entry: same splits, launches and workspace pitches, so a uniform table plans field for field as the
 // multi-layer step it spells out.  The entries keep their own bounds inside those pitches (the kernels' batch instances read them
@@ -637,7 +638,7 @@ int ekv_plan_step(const ekv_bank* bank, const ekv_step* step, EkvStepPlan* P) {
 int resolve_call(const EkvCall& c, EkvResolved* r) {
   EkvStepPlan* P = &r->plan;
   *P = EkvStepPlan{};
-  r->bank = c.kv8 ? nullptr : c.bank;
+  r->bank = (c.kv8 || c.kv4) ? nullptr : c.bank;
   r->step = c.step;
   r->tb = nullptr;
   if (c.dtype != EKV_DTYPE_F16 && c.dtype != EKV_DTYPE_BF16) return EKV_E_ARG;
@@ -647,6 +648,14 @@ int resolve_call(const EkvCall& c, EkvResolved* r) {
     r->bank8 = *c.bank;
     r->bank8.k = q8->k_codes;
     r->bank8.v = q8->v_codes;
+    r->bank = &r->bank8;
+  }
+  if (c.kv4) {      // MXFP4 rows: one more variant stage, as the FP8 one (the code planes stand where the 16-bit rows were)
+    const ekv_kv4* q4 = c.q4;
+    if (c.kv8 || c.batch || !c.bank || !q4 || !q4->k_codes || !q4->v_codes || !q4->k_exp || !q4->v_exp) return EKV_E_ARG;
+    r->bank8 = *c.bank;
+    r->bank8.k = q4->k_codes;
+    r->bank8.v = q4->v_codes;
     r->bank = &r->bank8;
   }
   const ekv_bank* bank = r->bank;
@@ -686,8 +695,9 @@ int resolve_call(const EkvCall& c, EkvResolved* r) {
   const int rc = ekv_plan_step(bank, r->step, P);
   P->bf16 = c.dtype == EKV_DTYPE_BF16;
   P->kv8 = c.kv8;
+  P->kv4 = c.kv4;
   P->batch = c.batch;
-  if (c.kv8 || c.batch) P->fused_order = 0;      // (the kv8 and the batch instances keep order F)
+  if (c.kv8 || c.kv4 || c.batch) P->fused_order = 0;      // (the kv8, kv4 and batch instances keep order F)
   auto refuse = [&](int code) {
     P->one_launch = P->n_launches = P->n_list = 0;
     if (c.batch) P->bytes = 0;      // (nothing will run: ekv_batch_workspace_bytes of a refused table is 0)
@@ -702,6 +712,8 @@ int resolve_call(const EkvCall& c, EkvResolved* r) {
   if (rc == EKV_OK && P->bf16 && st->rope_on_read) return refuse(EKV_E_UNSUPPORTED);
   if (rc != EKV_OK) return refuse(rc);
   if (c.kv8 && (st->q_len != 1 || st->rope_on_read || (bank->head_dim != 64 && bank->head_dim != 128))) return refuse(EKV_E_UNSUPPORTED);
+  // MXFP4 rows: head_dim 128 (a lane's 16-byte piece = one 32-element block), GQA factors up to 4 (32 output floats per lane and head)
+  if (c.kv4 && (st->q_len != 1 || st->rope_on_read || bank->head_dim != 128 || bank->n_q_heads / bank->n_kv_heads > 4)) return refuse(EKV_E_UNSUPPORTED);
   if (c.batch) {
     for (int i = 0; i < c.n_seq; ++i) {      // per entry: the checks of the single-sequence step of that entry's geometry
       const ekv_seq& e = c.seqs[i];
@@ -738,7 +750,7 @@ int call_info(const EkvCall& c, int32_t* info, int32_t n_info) {
   EkvResolved r;
   const bool ok = resolve_call(c, &r) == EKV_OK;
   if (c.dtype != EKV_DTYPE_F16 && c.dtype != EKV_DTYPE_BF16) return EKV_E_ARG;
-  if (c.kv8 && !r.bank) return EKV_E_ARG;
+  if ((c.kv8 || c.kv4) && !r.bank) return EKV_E_ARG;
   if (int e = check_bank(r.bank)) return e;
   if (!c.step || (c.batch && !c.seqs) || !info || n_info < 1) return EKV_E_ARG;
   const EkvStepPlan& P = r.plan;

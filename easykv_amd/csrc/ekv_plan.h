@@ -36,7 +36,7 @@ int ekv_plan_step(const ekv_bank* bank, const ekv_step* step, EkvStepPlan* P);
 
 // ---- one call path --------------------------------------------------------------------------------------------------------------
 // A call of the step family as its entry points spell it: the untyped / _typed functions (a bank, a step, an element type), ekv_kv8_*
-// (+ the FP8 planes) and ekv_batch_* (+ the table of a batched decode step).  The axes are independent here; which combinations run
+// (+ the FP8 planes), ekv_kv4_* (+ the MXFP4 planes) and ekv_batch_* (+ the table of a batched decode step).  The axes are independent here; which combinations run
 // is the planner's business (resolve_call) and the manifest's (ekv_instances.def).
 struct EkvCall {
   const ekv_bank* bank;
@@ -47,11 +47,16 @@ struct EkvCall {
   bool batch;              // an ekv_batch_* call (with kv8: an ekv_kv8_batch_* call)
   const ekv_seq* seqs;
   int32_t n_seq;
+  bool kv4;                // an ekv_kv4_* call (q4 may still be NULL: an argument error)
+  const ekv_kv4* q4;
 };
 inline EkvCall step_call(const ekv_bank* bank, const ekv_step* st, int32_t dtype) { return {bank, st, dtype, false, nullptr, false, nullptr, 0}; }
 inline EkvCall kv8_call(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_kv8* q8) { return {bank, st, dtype, true, q8, false, nullptr, 0}; }
 inline EkvCall batch_call(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_seq* seqs, int32_t n_seq) {
   return {bank, st, dtype, false, nullptr, true, seqs, n_seq};
+}
+inline EkvCall kv4_call(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_kv4* q4) {
+  return {bank, st, dtype, false, nullptr, false, nullptr, 0, true, q4};
 }
 // an ekv_kv8_batch_* call: both variants at once (resolve_call applies them independently)
 inline EkvCall kv8_batch_call(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_kv8* q8, const ekv_seq* seqs, int32_t n_seq) {
@@ -60,7 +65,7 @@ inline EkvCall kv8_batch_call(const ekv_bank* bank, const ekv_step* st, int32_t 
 
 // Everything a call needs, resolved once (resolve_call): check, info, workspace bytes and attend all read it.
 struct EkvResolved {
-  const ekv_bank* bank;      // the bank planned and launched with; NULL: a kv8 call without its planes
+  const ekv_bank* bank;      // the bank planned and launched with; NULL: a kv8 / kv4 call without its planes
   const ekv_step* step;      // the step actually planned: the caller's, or the envelope of a batch
   const EkvSeqTable* tb;     // the table the batch instances receive; NULL for a uniform step
   EkvStepPlan plan;          // kv8 / batch / fused_order final; zero launches (a batch: zero bytes too) when the call is refused

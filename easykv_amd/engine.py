@@ -99,6 +99,7 @@ class KVBank:
     default_two_pass = 0    # StepPlan.two_pass used when a plan leaves it at 0 (tests force either chunk scheme with it)
     dtype, _dt = torch.float16, _lib.DTYPE_F16      # (set per bank by __init__)
     kv_quant, _kv8 = None, None      # quantize_fp8(): "fp8" and the ekv_kv8 descriptor of the code planes / row scales
+    _kv4 = None                      # quantize_mxfp4(): kv_quant "mxfp4" and the ekv_kv4 descriptor of the code planes / block exponents
 
     def __init__(self, n_layers, n_q_heads, n_kv_heads, head_dim, cap, device="cuda", scored=True, dtype=torch.float16, kv_quant=None):
         """``kv_quant='fp8'``: the bank is created holding FP8 planes only (see :meth:`quantize_fp8`); the 16-bit K/V rows are never
@@ -252,12 +253,26 @@ class KVBank:
         if cond and self._kv8 is not None:
             raise _lib.EkvError(f"{what} is not available on a bank quantised by quantize_fp8(): its K/V rows are FP8 codes with per-row "
                                 "scales, which only decode steps (q_len == 1, plain keys) read and append to")
+        if cond and self._kv4 is not None:
+            raise _lib.EkvError(f"{what} is not available on a bank quantised by quantize_mxfp4(): its K/V rows are MXFP4 codes with "
+                                "block exponents, which only decode steps (q_len == 1, plain keys) read and append to")
+
+    @property
+    def _quant(self):
+        """(call prefix, descriptor) of a quantised bank's step calls — ("ekv_kv8", ekv_kv8) / ("ekv_kv4", ekv_kv4) — or None."""
+        if self._kv8 is not None:
+            return "ekv_kv8", self._kv8
+        if self._kv4 is not None:
+            return "ekv_kv4", self._kv4
+        return None
 
     def quantize_fp8(self):
         """Convert the live bank in place to FP8 (OCP e4m3fn) K/V rows with one fp32 scale per row: codes and scales are written at the
         rows' physical indices (slot map, free list and score rows carry over as they are, in either layout), the 16-bit K/V tensors
         are released, and ``attend`` / ``step_info`` / ``step_plan`` go to the kv8 calls.  From here on the bank serves decode steps
         only: chunk steps, ``load_rows``, ``set_rope`` and the row moves raise :class:`EkvError`."""
+        if self._kv4 is not None:
+            raise _lib.EkvError("quantize_fp8(): the bank's rows are MXFP4 already (quantize_mxfp4())")
         if self._kv8 is not None:
             return self
         if self.head_dim not in (64, 128):
@@ -297,35 +312,84 @@ class KVBank:
         self._slot_ok.clear()
         self._defer = None
 
+    # -- MXFP4 K/V storage ("kv4", include/easykv_hip.h) --------------------------------------------
+    def quantize_mxfp4(self):
+        """Convert the live bank in place to MXFP4 K/V rows: e2m1 codes, two per byte, with one E8M0 exponent per 32-element block,
+        written at the rows' physical indices (``k4`` / ``v4`` / ``k_exp`` / ``v_exp``; slot map, free list and score rows carry over
+        as they are, in either layout).  The 16-bit K/V tensors are released, ``kv_quant`` is ``'mxfp4'`` and ``attend`` /
+        ``step_info`` / ``step_plan`` go to the kv4 calls.  head_dim 128 and GQA factors up to 4; from here on the bank serves decode
+        steps only, as after :meth:`quantize_fp8`.  A bank is quantised once: a second conversion of either kind raises."""
+        if self._kv8 is not None or self._kv4 is not None:
+            raise _lib.EkvError(f"quantize_mxfp4(): the bank's rows are quantised already (kv_quant={self.kv_quant!r})")
+        if self.head_dim != 128:
+            raise _lib.EkvError(f"quantize_mxfp4(): MXFP4 rows are built for head_dim 128, not {self.head_dim}")
+        if self.n_q_heads // self.n_kv_heads > 4:
+            raise _lib.EkvError(f"quantize_mxfp4(): MXFP4 rows are built for GQA factors up to 4, not {self.n_q_heads // self.n_kv_heads}")
+        if self.rope_cos is not None:
+            raise _lib.EkvError("quantize_mxfp4(): a RoPE-on-read (streaming) bank keeps un-rotated keys, which the MXFP4 decode kernels do not rotate")
+        if self._defer is not None and self._defer["pending"]:
+            raise _lib.EkvError("quantize_mxfp4(): a deferred token step is open (flush() first)")
+        if torch.cuda.is_current_stream_capturing():
+            raise _lib.EkvError("quantize_mxfp4() cannot be captured in a graph: convert the bank before the capture")
+        self.join()
+        shape = (self.n_layers, self.n_kv_heads, self.cap)
+        # rows that were never written keep code 0 / exponent byte 127 (scale 1): finite whatever the kernels prefetch
+        self.k4 = torch.zeros(*shape, self.head_dim // 2, dtype=torch.uint8, device=self.device)
+        self.v4 = torch.zeros_like(self.k4)
+        self.k_exp = torch.full((*shape, self.head_dim // 32), 127, dtype=torch.uint8, device=self.device)
+        self.v_exp = torch.full_like(self.k_exp, 127)
+        kv4 = _lib.Kv4(self.k4.data_ptr(), self.v4.data_ptr(), self.k_exp.data_ptr(), self.v_exp.data_ptr())
+        check(self.lib.ekv_kv4_quantize(C.byref(self._bank), C.byref(kv4), self._dt, 0, self.n_layers, max(self.extent), self._stream()),
+              "ekv_kv4_quantize")
+        cur = torch.cuda.current_stream(self.device)
+        self.k.record_stream(cur)
+        self.v.record_stream(cur)
+        self.k = self.v = None
+        self._bank.k, self._bank.v = self.k4.data_ptr(), self.v4.data_ptr()
+        self._kv4, self.kv_quant = kv4, "mxfp4"
+        self._slot_ok.clear()
+        self._defer = None
+        return self
+
     def kv_bytes(self) -> int:
-        """Bytes held for the K/V rows: 16-bit rows, or FP8 codes + row scales (``2 * head_dim + 8`` per row pair)."""
+        """Bytes held for the K/V rows: 16-bit rows, FP8 codes + row scales (``2 * head_dim + 8`` per row pair), or MXFP4 codes +
+        block exponents (``head_dim + head_dim / 16``: 136 at head_dim 128)."""
         rows = self.n_layers * self.n_kv_heads * self.cap
+        if self._kv4 is not None:
+            return rows * (self.head_dim + self.head_dim // 16)
         return rows * (2 * self.head_dim + 8) if self._kv8 is not None else rows * 4 * self.head_dim
 
     def dequantized_rows(self, layer):
         """(K, V) ``[H, cap, head_dim]`` fp32 of the PHYSICAL rows of ``layer``: code * scale of a quantised bank (exact), the 16-bit rows
         of any other widened.  Rows that were never written read as zeros on a quantised bank.  For tests and tools."""
-        if self._kv8 is None:
+        if self._quant is None:
             return self.k[layer].float(), self.v[layer].float()
         k = torch.empty(self.n_kv_heads, self.cap, self.head_dim, dtype=torch.float32, device=self.device)
         v = torch.empty_like(k)
+        if self._kv4 is not None:
+            check(self.lib.ekv_kv4_dequantize(C.byref(self._bank), C.byref(self._kv4), _lib.DTYPE_F32, layer, 1, self.cap, _ptr(k), _ptr(v),
+                                              self._stream()), "ekv_kv4_dequantize")
+            return k, v
         check(self.lib.ekv_kv8_dequantize(C.byref(self._bank), C.byref(self._kv8), _lib.DTYPE_F32, layer, 1, self.cap, _ptr(k), _ptr(v),
                                           self._stream()), "ekv_kv8_dequantize")
         return k, v
 
     def _step_check(self, st):
-        if self._kv8 is not None:
-            return self.lib.ekv_kv8_step_check(C.byref(self._bank), C.byref(st), self._dt, C.byref(self._kv8))
+        if self._quant is not None:
+            name, desc = self._quant
+            return getattr(self.lib, name + "_step_check")(C.byref(self._bank), C.byref(st), self._dt, C.byref(desc))
         return self.lib.ekv_step_check_typed(C.byref(self._bank), C.byref(st), self._dt)
 
     def _step_ws_bytes(self, st):
-        if self._kv8 is not None:
-            return self.lib.ekv_kv8_workspace_bytes(C.byref(self._bank), C.byref(st), self._dt, C.byref(self._kv8))
+        if self._quant is not None:
+            name, desc = self._quant
+            return getattr(self.lib, name + "_workspace_bytes")(C.byref(self._bank), C.byref(st), self._dt, C.byref(desc))
         return self.lib.ekv_workspace_bytes_typed(C.byref(self._bank), C.byref(st), self._dt)
 
     def _step_attend(self, st, *args):
-        if self._kv8 is not None:
-            return self.lib.ekv_kv8_step_attend(C.byref(self._bank), C.byref(st), self._dt, C.byref(self._kv8), *args)
+        if self._quant is not None:
+            name, desc = self._quant
+            return getattr(self.lib, name + "_step_attend")(C.byref(self._bank), C.byref(st), self._dt, C.byref(desc), *args)
         return self.lib.ekv_step_attend_typed(C.byref(self._bank), C.byref(st), self._dt, *args)
 
     # -- plumbing -----------------------------------------------------------------------------
@@ -465,7 +529,7 @@ class KVBank:
         """(n_split, fused) the library will use for this step."""
         st = self.make_step(plan, q_len, layer_begin, self.n_layers - layer_begin if layer_count is None else layer_count)
         st.phases = phases
-        if self._kv8 is not None:      # (the kv8 dry run: a step the FP8 bank refuses plans as not fused)
+        if self._quant is not None:      # (the kv8 / kv4 dry run: a step the quantised bank refuses plans as not fused)
             info = self.step_info(plan, q_len, layer_begin, layer_count, phases)
             return info["n_split"], bool(info["fused"])
         ns, fu = C.c_int32(0), C.c_int32(0)
@@ -477,8 +541,9 @@ class KVBank:
         st = self.make_step(plan, q_len, layer_begin, self.n_layers - layer_begin if layer_count is None else layer_count)
         st.phases = phases
         info = (C.c_int32 * 10)()
-        if self._kv8 is not None:
-            check(self.lib.ekv_kv8_step_info(C.byref(self._bank), C.byref(st), self._dt, C.byref(self._kv8), info, 10), "ekv_kv8_step_info")
+        if self._quant is not None:
+            name, desc = self._quant
+            check(getattr(self.lib, name + "_step_info")(C.byref(self._bank), C.byref(st), self._dt, C.byref(desc), info, 10), name + "_step_info")
         else:
             check(self.lib.ekv_step_info_typed(C.byref(self._bank), C.byref(st), self._dt, info, 10), "ekv_step_info")
         keys = ("n_split", "fused", "two_pass", "wide", "n_qblocks", "qb_rows", "n_col_parts", "fold_in_kernel", "n_launches", "fused_order")
@@ -560,8 +625,9 @@ class KVBank:
                                    st_ref=C.byref(st), bank_ref=C.byref(self._bank), ws_ptr=ws.data_ptr(), ws_len=ws.numel(),
                                    stream=self._stream())
             # (the call and its leading arguments: the typed step, or the kv8 step with the descriptor behind the dtype)
-            if self._kv8 is not None:
-                d["call"], d["head"] = self.lib.ekv_kv8_step_attend, (d["bank_ref"], d["st_ref"], self._dt, C.byref(self._kv8))
+            if self._quant is not None:
+                name, desc = self._quant
+                d["call"], d["head"] = getattr(self.lib, name + "_step_attend"), (d["bank_ref"], d["st_ref"], self._dt, C.byref(desc))
             else:
                 d["call"], d["head"] = self.lib.ekv_step_attend_typed, (d["bank_ref"], d["st_ref"], self._dt)
         st = d["st"]

@@ -293,6 +293,56 @@ int ekv_kv8_step_attend(const ekv_bank *bank, const ekv_step *step, int32_t dtyp
                         const void *k_new, const void *v_new, void *out, int32_t *evict_ids, const float *rope_cos,
                         const float *rope_sin, void *workspace, size_t workspace_bytes, void *stream);
 
+/* MXFP4 K/V storage with block scales ("kv4"; ABI 8, additive; head_dim 128).  A bank's K/V rows may be held as
+ *
+ *   k_codes, v_codes   uint8 [n_layers][n_kv_heads][cap][head_dim / 2]    two e2m1 codes per byte: element 2i in the low nibble
+ *                                                                         (bits 3:0), element 2i + 1 in the high nibble (bits 7:4) —
+ *                                                                         the order the gfx950 pack conversions read and write
+ *   k_exp,   v_exp     uint8 [n_layers][n_kv_heads][cap][head_dim / 32]   E8M0: one biased exponent per 32-element block of the
+ *                                                                         PHYSICAL row;  value = code * 2^(byte - 127)
+ *
+ * — head_dim + head_dim / 16 bytes per K+V row pair: 136 at head_dim 128, against 264 (kv8) and 512 (16-bit rows).  A code is sign
+ * (bit 3) and magnitude index into {0, 0.5, 1, 1.5, 2, 3, 4, 6}.  As for kv8, rows never move: a row's exponents live at its physical
+ * index, and the slot map, the free list and the score rows (either layout) are those of the 16-bit bank.
+ *
+ * Quantisation rule of a block x[0..32) (normative), in fp32:  amax = max |x|;  e = the smallest integer with amax <= 6 * 2^e, clamped
+ * to [-126, 127], and e = 0 for an all-zero block;  the stored byte is e + 127 (255 never occurs);  code = round-to-nearest(x / 2^e)
+ * onto the eight magnitudes with the sign of x, ties to the even code (1.25 -> 1, 2.5 -> 2, 5 -> 4).  The quotient is exact, |x / 2^e|
+ * <= 6, so nothing saturates by construction and the rule has no rounding of its own: an implementation is bit-identical to another
+ * up to the sign of zero — codes 0 and 8 (+0 / -0) are equivalent.  Rows are assumed finite.  What is stored is what is attended:
+ * the row a decode step appends is quantised by the kernel and takes part in that step AS QUANTISED.
+ *
+ * The descriptor carries the four planes; every other field of `bank` is used as it is, and bank->k / bank->v are NOT read by the
+ * kv4 step calls. */
+typedef struct ekv_kv4 {
+  void *k_codes, *v_codes;
+  uint8_t *k_exp, *v_exp;
+} ekv_kv4;
+
+/* Bank conversion and its inverse: the arguments and contracts of ekv_kv8_quantize / ekv_kv8_dequantize (rows [0, extent) at the same
+ * physical indices, rows >= extent and the 16-bit rows untouched; out_dtype EKV_DTYPE_F32 is exact: code * 2^e).  head_dim != 128 is
+ * EKV_E_UNSUPPORTED. */
+int ekv_kv4_quantize(const ekv_bank *bank, const ekv_kv4 *kv4, int32_t dtype, int32_t layer_begin, int32_t layer_count,
+                     int32_t extent, void *stream);
+int ekv_kv4_dequantize(const ekv_bank *bank, const ekv_kv4 *kv4, int32_t out_dtype, int32_t layer_begin, int32_t layer_count,
+                       int32_t extent, void *k_out, void *v_out, void *stream);
+
+/* Decode steps on a kv4 bank: the ekv_kv8_step_* signatures with the kv4 descriptor.  Accepted: q_len == 1 with plain keys at
+ * head_dim 128 and a GQA factor <= 4 (factor 3 on the padded build), fp16 / bf16 q, k_new, v_new and out — every policy and every
+ * phase combination the 16-bit decode step takes (the whole step incl. the one-launch kernel on either score-row layout, the split
+ * path, the deferred per-layer form), planned exactly as the 16-bit step of that shape: same splits, launches, workspace and info
+ * fields, fused_order 0.  The kv4 builds of the decode attention kernels read a row as a 4-lane group, one block per lane: the lane's
+ * partial q . codes is multiplied by its block's 2^e before the group sum, V codes are converted to fp32 with the block's scale, and
+ * the appended row is quantised by its lane group (codes + exponents written to the recycled row).  Everything behind the logits is
+ * the 16-bit step's.  EKV_E_UNSUPPORTED from the dry run, before anything is launched: q_len > 1, rope_on_read, head_dim != 128, a
+ * GQA factor > 4.  A missing plane is EKV_E_ARG.  There is no batch form, and the row moves do not serve kv4 banks. */
+int ekv_kv4_step_check(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const ekv_kv4 *kv4);
+int ekv_kv4_step_info(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const ekv_kv4 *kv4, int32_t *info, int32_t n_info);
+size_t ekv_kv4_workspace_bytes(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const ekv_kv4 *kv4);
+int ekv_kv4_step_attend(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const ekv_kv4 *kv4, const void *q,
+                        const void *k_new, const void *v_new, void *out, int32_t *evict_ids, const float *rope_cos,
+                        const float *rope_sin, void *workspace, size_t workspace_bytes, void *stream);
+
 /* Batched decode steps (ABI 8, additive): ONE call, and one launch per kernel kind, serves n_seq sequences whose caches have
  * different lengths and different eviction geometry.  Each entry of the table names the bank layer it attends and carries what
  * ekv_step holds per step; entry i owns row i of the call's tensors.  The layers of a table need not be contiguous or ordered, so

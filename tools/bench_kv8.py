@@ -10,7 +10,11 @@ Per leg: µs per launch (median of per-rep means, HIP events on the launch strea
 bytes per launch computed from the shapes (K/V rows read once — 2 * D * 2 bytes per row pair, or 2 * D + 8 with FP8 codes and two
 scales — + the appended row, q / out, and the score rows once in and once out), GB/s and the fraction of the 8 TB/s HBM peak.
 
-Usage: python tools/bench_kv8.py [--reps 15] [--steps 20] [--warm 1000] [--out profiles/kv8_bench.json]"""
+--mxfp4 adds a third leg on MXFP4 rows (KVBank.quantize_mxfp4: head_dim + head_dim / 16 bytes per row pair) to the head_dim-128 runs,
+interleaved with the other two in the same process on a third copy of the same rows, slot map and score state (fp16 rep, fp8 rep,
+mxfp4 rep, ...), and writes profiles/kv4_bench.json instead: per leg the median, the run-to-run spread and the algorithmic bytes.
+
+Usage: python tools/bench_kv8.py [--reps 15] [--steps 20] [--warm 1000] [--mxfp4] [--out profiles/kv8_bench.json]"""
 from __future__ import annotations
 
 import argparse
@@ -35,6 +39,10 @@ def step_bytes(kind, L, H, Hq, D, T, n_state=3):
     if kind == "fp8":
         kv = H * T * (2 * D + 8)                  # codes of K and V + the two row scales, read once
         new = H * (2 * D + 8)                     # the appended row, as stored
+        b = dict(total=kv + new + 2 * Hq * D * 2 + 2 * n_state * H * T * 4, kv=kv)
+    elif kind == "mxfp4":
+        kv = H * T * (D + D // 16)                # codes of K and V (half a byte per element) + one exponent byte per 32 elements
+        new = H * (D + D // 16)
         b = dict(total=kv + new + 2 * Hq * D * 2 + 2 * n_state * H * T * 4, kv=kv)
     else:
         b = dict(total=b["total"], kv=2 * H * T * D * 2)
@@ -79,6 +87,8 @@ def make_bank(kind, L, H, D, budget):
     bank.score_sq[:, :, :budget] += warm ** 2
     if kind == "fp8":
         bank.quantize_fp8()
+    elif kind == "mxfp4":
+        bank.quantize_mxfp4()
     return bank, g
 
 
@@ -111,15 +121,15 @@ def deferred_step(kind, L=32, H=32, D=128, budget=2048):
     return forward
 
 
-def leg(name, maker, shape, reps, steps, warm, per=1):
-    fns = {kind: maker(kind, **shape) for kind in ("fp16", "fp8")}
+def leg(name, maker, shape, reps, steps, warm, per=1, kinds=("fp16", "fp8")):
+    fns = {kind: maker(kind, **shape) for kind in kinds}
     t = _interleave(fns, reps, steps, warm)
     del fns
     gc.collect()
     torch.cuda.empty_cache()
     L, H, D, T = shape["L"], shape["H"], shape["D"], shape["budget"] + 1
     res = {}
-    for kind in ("fp16", "fp8"):
+    for kind in kinds:
         b = step_bytes(kind, L, H, H, D, T)
         us = t[kind]["us"] / per
         gbs = b["total"] / per / (us * 1e-6) / 1e9
@@ -128,6 +138,10 @@ def leg(name, maker, shape, reps, steps, warm, per=1):
     res["time_ratio_fp8_over_fp16"] = round(res["fp8"]["us_per_launch"] / res["fp16"]["us_per_launch"], 4)
     res["byte_ratio_fp8_over_fp16"] = round(res["fp8"]["bytes_per_launch"] / res["fp16"]["bytes_per_launch"], 4)
     res["faster_by_more_than_the_fp16_spread"] = bool(1.0 - res["time_ratio_fp8_over_fp16"] > res["fp16"]["run_to_run_spread"])
+    if "mxfp4" in kinds:
+        for other in ("fp16", "fp8"):
+            res[f"time_ratio_mxfp4_over_{other}"] = round(res["mxfp4"]["us_per_launch"] / res[other]["us_per_launch"], 4)
+            res[f"byte_ratio_mxfp4_over_{other}"] = round(res["mxfp4"]["bytes_per_launch"] / res[other]["bytes_per_launch"], 4)
     return res
 
 
@@ -136,22 +150,27 @@ def main():
     ap.add_argument("--reps", type=int, default=15)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warm", type=int, default=1000)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "kv8_bench.json"))
+    ap.add_argument("--mxfp4", action="store_true", help="add the MXFP4 leg to the head_dim-128 runs; the default --out becomes profiles/kv4_bench.json")
+    ap.add_argument("--out", default=None)
     ap.add_argument("--only", default=None, help="run one leg: fused_d128, fused_d64 or deferred_d128 (nothing is written)")
     args = ap.parse_args()
+    out = args.out or os.path.join(ROOT, "profiles", "kv4_bench.json" if args.mxfp4 else "kv8_bench.json")
+    kinds = ("fp16", "fp8", "mxfp4") if args.mxfp4 else ("fp16", "fp8")
     torch.cuda.set_device(0)
     res = {"device": torch.cuda.get_device_name(0), "reps": args.reps, "steps": args.steps, "warm": args.warm, "hbm_peak_gb_per_s": HBM_PEAK_GBS,
            "shape": "32 layers x 32 heads, budget 2048 (T = 2049), roco, scattered slot map, warm score state"}
     shape = dict(L=32, H=32, D=128, budget=2048)
-    legs = {"fused_d128": lambda: leg("fused_d128", fused_step, shape, args.reps, args.steps, args.warm),
+    legs = {"fused_d128": lambda: leg("fused_d128", fused_step, shape, args.reps, args.steps, args.warm, kinds=kinds),
             "fused_d64": lambda: leg("fused_d64", fused_step, dict(shape, D=64), args.reps, args.steps, args.warm),
             # (per layer: one forward is 32 attention launches + the flush; bytes per layer likewise)
-            "deferred_d128": lambda: leg("deferred_d128", deferred_step, shape, args.reps, max(4, args.steps // 4), max(20, args.warm // 32), per=32)}
+            "deferred_d128": lambda: leg("deferred_d128", deferred_step, shape, args.reps, max(4, args.steps // 4), max(20, args.warm // 32), per=32, kinds=kinds)}
+    if args.mxfp4:
+        del legs["fused_d64"]      # (MXFP4 rows are head_dim 128's)
     for name, run in legs.items():
         if args.only in (None, name):
             res[name] = run()
     if args.only is None:
-        with open(args.out, "w") as f:
+        with open(out, "w") as f:
             json.dump(res, f, indent=1)
     print(json.dumps(res))
 
