@@ -20,6 +20,8 @@ MANIFEST = os.path.join(CSRC, "ekv_instances.def")
 # whose lines the manifest includes from a file of its own, and the translation unit of its bank conversion.
 MANIFEST_KV4 = os.path.join(CSRC, "ekv_instances_kv4.def")
 EXTRA_SOURCES = ("ekv_kv4.hip",)
+# ... and beside those (extra_objects() is a fixture too): the batched MXFP4 family, from a manifest file of its own again
+MANIFEST_KV4_BATCH = os.path.join(CSRC, "ekv_instances_kv4_batch.def")
 
 
 def _tags(*words):
@@ -49,6 +51,9 @@ FAMILIES = {
     "EKV_DECODE_KV4": lambda d, elem: (
         "ekv_attn_decode.inc", f"ekv_attn_decode_d{d}_plain_kv4" + _tags(elem),
         _on(elem) + ["-DEKV_KV4=1", f"-DEKV_D={d}", "-DEKV_ROPE=false"]),
+    "EKV_DECODE_KV4_BATCH": lambda d, elem: (
+        "ekv_attn_decode.inc", f"ekv_attn_decode_d{d}_plain_batch_kv4" + _tags(elem),
+        _on(elem) + ["-DEKV_KV4=1", "-DEKV_BATCH=1", f"-DEKV_D={d}", "-DEKV_ROPE=false"]),
     "EKV_SCORE_SELECT": lambda nt, elem: ("ekv_score_select.inc", f"ekv_score_select_nt{nt}" + _tags(elem), _on(elem) + [f"-DEKV_SS_NT={nt}"]),
 }
 
@@ -66,11 +71,34 @@ def sources():
                   if os.path.basename(p) not in EXTRA_SOURCES)
 
 
-def extra_instances():
-    """(family, words) of the lines of ekv_instances_kv4.def."""
-    with open(MANIFEST_KV4) as f:
+def _file_instances(path):
+    with open(path) as f:
         found = re.findall(r"^(EKV_[A-Z0-9_]+)\(([^)]*)\)", f.read(), re.M)
     return [(fam, tuple(w.strip() for w in args.split(","))) for fam, args in found]
+
+
+def extra_instances():
+    """(family, words) of the lines of ekv_instances_kv4.def."""
+    return _file_instances(MANIFEST_KV4)
+
+
+def batch_kv4_instances():
+    """(family, words) of the lines of ekv_instances_kv4_batch.def."""
+    return _file_instances(MANIFEST_KV4_BATCH)
+
+
+def batch_kv4_objects():
+    """The objects built and linked beside all_objects() and extra_objects(): the instances of ekv_instances_kv4_batch.def."""
+    objs = []
+    for fam, words in batch_kv4_instances():
+        inc, name, defs = FAMILIES[fam](*words)
+        objs.append((name, defs + ["-x", "hip", os.path.join(CSRC, inc)]))
+    return objs
+
+
+def linked_objects():
+    """Everything build_lib compiles and links, in link order (tools/kernel_regs.py and tools/isa_identity.py read it too)."""
+    return all_objects() + extra_objects() + batch_kv4_objects()
 
 
 def extra_objects():
@@ -105,7 +133,7 @@ def all_objects():
 
 
 def headers():
-    return (glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.inc")) + [MANIFEST, MANIFEST_KV4] +
+    return (glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.inc")) + [MANIFEST, MANIFEST_KV4, MANIFEST_KV4_BATCH] +
             [os.path.join(HERE, "..", "include", "easykv_hip.h")])
 
 
@@ -126,7 +154,7 @@ def build_lib(force: bool = False, verbose: bool = False, jobs: int = 0) -> str:
     os.makedirs(OBJ, exist_ok=True)
     hdr_t = max(os.path.getmtime(h) for h in headers())
     todo, objs = [], []
-    for name, args in all_objects() + extra_objects():
+    for name, args in linked_objects():
         obj = os.path.join(OBJ, name + ".o")
         objs.append(obj)
         src_t = os.path.getmtime(args[-1])

@@ -37,6 +37,8 @@ DTYPE_F32 = 2      # ekv_kv8_dequantize's / ekv_kv4_dequantize's out_dtype only
 # the MXFP4 K/V storage calls (include/easykv_hip.h, "kv4"): a list of their own for the same reason
 EXPORTS_KV4 = ("ekv_kv4_quantize", "ekv_kv4_dequantize", "ekv_kv4_step_check", "ekv_kv4_step_info", "ekv_kv4_workspace_bytes",
                "ekv_kv4_step_attend")
+# the batched decode step on MXFP4 rows ("kv4 batches"): a list of its own once more — tests/test_kv4_cpu.py pins EXPORTS_KV4 to the six above
+EXPORTS_KV4_BATCH = ("ekv_kv4_batch_step_check", "ekv_kv4_batch_step_info", "ekv_kv4_batch_workspace_bytes", "ekv_kv4_batch_step_attend")
 
 
 class Bank(C.Structure):
@@ -87,7 +89,7 @@ def load():
         raise EkvError(f"{LIB} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                        "(hipcc --offload-arch=gfx950).  There is no CPU fallback for the product path.")
     lib = C.CDLL(LIB)
-    for name in EXPORTS + EXPORTS_KV8 + EXPORTS_KV4:
+    for name in EXPORTS + EXPORTS_KV8 + EXPORTS_KV4 + EXPORTS_KV4_BATCH:
         if not hasattr(lib, name):
             raise EkvError(f"{LIB} does not export {name}")
     vp, i32 = C.c_void_p, C.c_int32
@@ -131,13 +133,18 @@ def load():
     lib.ekv_kv8_batch_step_info.argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, C.POINTER(Kv8), C.POINTER(Seq), i32, C.POINTER(C.c_int32), C.c_int32]
     lib.ekv_kv8_batch_workspace_bytes.argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, C.POINTER(Kv8), C.POINTER(Seq), i32]
     lib.ekv_kv8_batch_step_attend.argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, C.POINTER(Kv8), C.POINTER(Seq), i32, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
-    for name in EXPORTS[3:] + EXPORTS_KV8 + EXPORTS_KV4:
+    lib.ekv_kv4_batch_step_check.argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, C.POINTER(Kv4), C.POINTER(Seq), i32]
+    lib.ekv_kv4_batch_step_info.argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, C.POINTER(Kv4), C.POINTER(Seq), i32, C.POINTER(C.c_int32), C.c_int32]
+    lib.ekv_kv4_batch_workspace_bytes.argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, C.POINTER(Kv4), C.POINTER(Seq), i32]
+    lib.ekv_kv4_batch_step_attend.argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, C.POINTER(Kv4), C.POINTER(Seq), i32, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
+    for name in EXPORTS[3:] + EXPORTS_KV8 + EXPORTS_KV4 + EXPORTS_KV4_BATCH:
         getattr(lib, name).restype = C.c_int
     lib.ekv_workspace_bytes_typed.restype = C.c_size_t
     lib.ekv_kv8_workspace_bytes.restype = C.c_size_t
     lib.ekv_kv4_workspace_bytes.restype = C.c_size_t
     lib.ekv_batch_workspace_bytes.restype = C.c_size_t
     lib.ekv_kv8_batch_workspace_bytes.restype = C.c_size_t
+    lib.ekv_kv4_batch_workspace_bytes.restype = C.c_size_t
     if lib.ekv_abi_version() != 8:
         raise EkvError("ABI version mismatch")
     _lib = lib

@@ -254,6 +254,23 @@ int ekv_kv4_step_attend(const ekv_bank* bank, const ekv_step* st, int32_t dtype,
   return call_attend(kv4_call(bank, st, dtype, q4), q, k_new, v_new, out, evict_ids, rope_cos, rope_sin, workspace, workspace_bytes, stream);
 }
 
+// batched decode steps on a kv4 bank (include/easykv_hip.h, "kv4 batches")
+int ekv_kv4_batch_step_check(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_kv4* q4, const ekv_seq* seqs, int32_t n_seq) {
+  return call_check(kv4_batch_call(bank, st, dtype, q4, seqs, n_seq));
+}
+int ekv_kv4_batch_step_info(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_kv4* q4, const ekv_seq* seqs, int32_t n_seq,
+                            int32_t* info, int32_t n_info) {
+  return call_info(kv4_batch_call(bank, st, dtype, q4, seqs, n_seq), info, n_info);
+}
+size_t ekv_kv4_batch_workspace_bytes(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_kv4* q4, const ekv_seq* seqs, int32_t n_seq) {
+  return call_workspace_bytes(kv4_batch_call(bank, st, dtype, q4, seqs, n_seq));
+}
+int ekv_kv4_batch_step_attend(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_kv4* q4, const ekv_seq* seqs, int32_t n_seq,
+                              const void* q, const void* k_new, const void* v_new, void* out, int32_t* evict_ids, void* workspace,
+                              size_t workspace_bytes, void* stream) {
+  return call_attend(kv4_batch_call(bank, st, dtype, q4, seqs, n_seq), q, k_new, v_new, out, evict_ids, nullptr, nullptr, workspace, workspace_bytes, stream);
+}
+
 static int kv4_convert_check(const ekv_bank* bank, const ekv_kv4* q4, int32_t layer_begin, int32_t layer_count, int32_t extent) {
   if (!bank || !q4 || !q4->k_codes || !q4->v_codes || !q4->k_exp || !q4->v_exp) return EKV_E_ARG;
   if (bank->n_layers <= 0 || bank->n_kv_heads <= 0 || bank->cap <= 0) return EKV_E_ARG;

@@ -13,6 +13,9 @@ typedef hipError_t EkvFoldFn(const EkvScoreArgs&, int layer_count, hipStream_t);
 #define EKV_DECODE_KV4(d, elem)                                            \
   EkvDecodeFn EKV_FN_DECODE(ekv_launch_attn_decode, d, plain, elem, kv4, single); \
   EkvFusedFn EKV_FN_DECODE(ekv_launch_decode_fused, d, plain, elem, kv4, single);
+#define EKV_DECODE_KV4_BATCH(d, elem)                                     \
+  EkvDecodeFn EKV_FN_DECODE(ekv_launch_attn_decode, d, plain, elem, kv4, batch); \
+  EkvFusedFn EKV_FN_DECODE(ekv_launch_decode_fused, d, plain, elem, kv4, batch);
 #define EKV_DECODE_SCORE(elem, batching) EkvScoreFn EKV_FN_DECODE_SCORE(ekv_launch_decode_score, elem, batching);
 #include "ekv_instances.def"
 EkvFoldFn ekv_launch_fold_f16, ekv_launch_fold_bf16;      // (exported by the `single` scorer instances: the fold reads no per-step field)
@@ -23,7 +26,7 @@ struct DecodeInstance {
   bool rope, bf16, kv8, batch;
   EkvDecodeFn* attn;
   EkvFusedFn* fused;
-  bool kv4;      // an EKV_DECODE_KV4 line (plain keys, single steps)
+  bool kv4;      // an EKV_DECODE_KV4 / EKV_DECODE_KV4_BATCH line (plain keys; `batch` says which)
 };
 const DecodeInstance kDecode[] = {
 #define EKV_DECODE(d, keys, elem, rows, batching)                                                                   \
@@ -32,6 +35,9 @@ const DecodeInstance kDecode[] = {
 #define EKV_DECODE_KV4(d, elem)                                                                                     \
   {d, false, EKV_IS_##elem, false, false, EKV_FN_DECODE(ekv_launch_attn_decode, d, plain, elem, kv4, single),      \
    EKV_FN_DECODE(ekv_launch_decode_fused, d, plain, elem, kv4, single), true},
+#define EKV_DECODE_KV4_BATCH(d, elem)                                                                               \
+  {d, false, EKV_IS_##elem, false, true, EKV_FN_DECODE(ekv_launch_attn_decode, d, plain, elem, kv4, batch),        \
+   EKV_FN_DECODE(ekv_launch_decode_fused, d, plain, elem, kv4, batch), true},
 #include "ekv_instances.def"
 };
 struct ScoreInstance {
@@ -47,7 +53,8 @@ const ScoreInstance kDecodeScore[] = {
 // not fit: kv8 needs plain keys and the scale planes, bf16 and batches have no RoPE-on-read build, a batch runs on the ordered layout
 // (the planner refuses all of these before a launch).  kv8 and batch are independent: a batched step on FP8 rows looks up its own
 // instance (head_dim 64 / 128, plain keys), which takes the table and the scale planes together.  kv4 is one more independent field:
-// plain keys, the exponent planes, no table, never with kv8 — a combination without a line of the manifest finds nothing.
+// plain keys, the exponent planes, GQA factors up to 4, never with kv8; with a table it finds the EKV_DECODE_KV4_BATCH instances, as a
+// kv8 batch finds its own — a combination without a line of the manifest finds nothing.
 const DecodeInstance* decode_instance(const EkvAttnArgs& a, const EkvSeqTable* tb, int head_dim, bool bf16, bool kv8, bool kv4, bool fused_slot_rows) {
   const bool rope = a.rope_cos != nullptr, batch = tb != nullptr;
   if (kv8 && (rope || a.k_scale == nullptr || a.v_scale == nullptr)) return nullptr;

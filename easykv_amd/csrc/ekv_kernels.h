@@ -161,7 +161,7 @@ struct EkvScoreArgs {
 // tb (the decode launchers): NULL = a uniform step of `count` layers; the table of a batched decode step = the batch instances (16-bit
 // or FP8 rows, plain keys, ordered score rows): `a` / `sc` are the envelope's arguments with layer_begin = 0 and a.arrive = the bank's
 // counters, and `count` is the number of table entries, one workgroup row each.
-// kv4: the MXFP4 instances (EKV_DECODE_KV4 lines of the manifest; never together with kv8 or a table)
+// kv4: the MXFP4 instances (EKV_DECODE_KV4 lines of the manifest, EKV_DECODE_KV4_BATCH lines with a table; never together with kv8)
 hipError_t ekv_launch_attn_decode(const EkvAttnArgs& a, const EkvSeqTable* tb, int head_dim, int count, hipStream_t s, bool bf16, bool kv8,
                                   bool kv4 = false);
 // passes (wide-block kernel, two-pass scheme): bit 0 = the one pass (output + row statistics), bit 1 = the column-sum pass

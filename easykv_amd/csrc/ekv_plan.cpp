@@ -635,6 +635,8 @@ int ekv_plan_step(const ekv_bank* bank, const ekv_step* step, EkvStepPlan* P) {
 // Both at once (an ekv_kv8_batch_* call): the stages apply independently — a missing plane is an argument error before the table is
 // read, the table is checked against the bank the code planes stand in, and the refusals of either variant hold unchanged (head_dim
 // 32 / 96 in a table: EKV_E_UNSUPPORTED with zero launches and zero bytes).  The plan is the 16-bit batched call's of the same table.
+// An ekv_kv4_batch_* call is the same pair of stages with the kv4 planes: head_dim != 128 or a GQA factor > 4 in a table is refused as
+// the kv4 step refuses it.  kv4 with kv8 is an argument error.
 int resolve_call(const EkvCall& c, EkvResolved* r) {
   EkvStepPlan* P = &r->plan;
   *P = EkvStepPlan{};
@@ -652,7 +654,7 @@ int resolve_call(const EkvCall& c, EkvResolved* r) {
   }
   if (c.kv4) {      // MXFP4 rows: one more variant stage, as the FP8 one (the code planes stand where the 16-bit rows were)
     const ekv_kv4* q4 = c.q4;
-    if (c.kv8 || c.batch || !c.bank || !q4 || !q4->k_codes || !q4->v_codes || !q4->k_exp || !q4->v_exp) return EKV_E_ARG;
+    if (c.kv8 || !c.bank || !q4 || !q4->k_codes || !q4->v_codes || !q4->k_exp || !q4->v_exp) return EKV_E_ARG;
     r->bank8 = *c.bank;
     r->bank8.k = q4->k_codes;
     r->bank8.v = q4->v_codes;

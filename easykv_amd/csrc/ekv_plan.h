@@ -44,7 +44,7 @@ struct EkvCall {
   int32_t dtype;
   bool kv8;                // an ekv_kv8_* call (q8 may still be NULL: an argument error)
   const ekv_kv8* q8;
-  bool batch;              // an ekv_batch_* call (with kv8: an ekv_kv8_batch_* call)
+  bool batch;              // an ekv_batch_* call (with kv8: an ekv_kv8_batch_* call, with kv4: an ekv_kv4_batch_* call)
   const ekv_seq* seqs;
   int32_t n_seq;
   bool kv4;                // an ekv_kv4_* call (q4 may still be NULL: an argument error)
@@ -61,6 +61,10 @@ inline EkvCall kv4_call(const ekv_bank* bank, const ekv_step* st, int32_t dtype,
 // an ekv_kv8_batch_* call: both variants at once (resolve_call applies them independently)
 inline EkvCall kv8_batch_call(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_kv8* q8, const ekv_seq* seqs, int32_t n_seq) {
   return {bank, st, dtype, true, q8, true, seqs, n_seq};
+}
+// an ekv_kv4_batch_* call, likewise
+inline EkvCall kv4_batch_call(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_kv4* q4, const ekv_seq* seqs, int32_t n_seq) {
+  return {bank, st, dtype, false, nullptr, true, seqs, n_seq, true, q4};
 }
 
 // Everything a call needs, resolved once (resolve_call): check, info, workspace bytes and attend all read it.

@@ -103,13 +103,16 @@ class KVBank:
 
     def __init__(self, n_layers, n_q_heads, n_kv_heads, head_dim, cap, device="cuda", scored=True, dtype=torch.float16, kv_quant=None):
         """``kv_quant='fp8'``: the bank is created holding FP8 planes only (see :meth:`quantize_fp8`); the 16-bit K/V rows are never
-        allocated.  Such a bank is filled by decode steps or, as one sequence of a :class:`KVBankBatch`, by ``adopt()``."""
+        allocated.  Such a bank is filled by decode steps or, as one sequence of a :class:`KVBankBatch`, by ``adopt()``.
+        ``kv_quant='mxfp4'``: likewise with MXFP4 planes only (see :meth:`quantize_mxfp4`; head_dim 128, GQA factors up to 4)."""
         if dtype not in _lib.DTYPE_CODES:
             raise ValueError(f"KVBank dtype must be torch.float16 or torch.bfloat16, not {dtype}")
-        if kv_quant not in (None, "fp8"):
-            raise ValueError(f"KVBank kv_quant must be None or 'fp8', not {kv_quant!r}")
-        if kv_quant is not None and head_dim not in (64, 128):
+        if kv_quant not in (None, "fp8", "mxfp4"):
+            raise ValueError(f"KVBank kv_quant must be None or 'fp8' / 'mxfp4', not {kv_quant!r}")
+        if kv_quant == "fp8" and head_dim not in (64, 128):
             raise _lib.EkvError(f"kv_quant='fp8': FP8 rows are built for head_dim 64 and 128, not {head_dim}")
+        if kv_quant == "mxfp4":
+            self._mxfp4_shape_check(head_dim, n_q_heads // max(1, n_kv_heads))
         self.dtype, self._dt = dtype, _lib.DTYPE_CODES[dtype]
         self.lib = _lib.load()
         dev = torch.device(device)
@@ -156,8 +159,10 @@ class KVBank:
                           self.arrive.data_ptr(), self.birth.data_ptr() if scored else None,
                           self.slot_state.data_ptr() if scored else None)
         self.rope_cos = self.rope_sin = None
-        if kv_quant is not None:
+        if kv_quant == "fp8":
             self._attach_fp8()
+        elif kv_quant == "mxfp4":
+            self._attach_mxfp4()
         self.reset()
 
     # -- layout of the score rows -------------------------------------------------------------------
@@ -321,10 +326,7 @@ class KVBank:
         steps only, as after :meth:`quantize_fp8`.  A bank is quantised once: a second conversion of either kind raises."""
         if self._kv8 is not None or self._kv4 is not None:
             raise _lib.EkvError(f"quantize_mxfp4(): the bank's rows are quantised already (kv_quant={self.kv_quant!r})")
-        if self.head_dim != 128:
-            raise _lib.EkvError(f"quantize_mxfp4(): MXFP4 rows are built for head_dim 128, not {self.head_dim}")
-        if self.n_q_heads // self.n_kv_heads > 4:
-            raise _lib.EkvError(f"quantize_mxfp4(): MXFP4 rows are built for GQA factors up to 4, not {self.n_q_heads // self.n_kv_heads}")
+        self._mxfp4_shape_check(self.head_dim, self.n_q_heads // self.n_kv_heads)
         if self.rope_cos is not None:
             raise _lib.EkvError("quantize_mxfp4(): a RoPE-on-read (streaming) bank keeps un-rotated keys, which the MXFP4 decode kernels do not rotate")
         if self._defer is not None and self._defer["pending"]:
@@ -332,24 +334,39 @@ class KVBank:
         if torch.cuda.is_current_stream_capturing():
             raise _lib.EkvError("quantize_mxfp4() cannot be captured in a graph: convert the bank before the capture")
         self.join()
-        shape = (self.n_layers, self.n_kv_heads, self.cap)
-        # rows that were never written keep code 0 / exponent byte 127 (scale 1): finite whatever the kernels prefetch
-        self.k4 = torch.zeros(*shape, self.head_dim // 2, dtype=torch.uint8, device=self.device)
-        self.v4 = torch.zeros_like(self.k4)
-        self.k_exp = torch.full((*shape, self.head_dim // 32), 127, dtype=torch.uint8, device=self.device)
-        self.v_exp = torch.full_like(self.k_exp, 127)
-        kv4 = _lib.Kv4(self.k4.data_ptr(), self.v4.data_ptr(), self.k_exp.data_ptr(), self.v_exp.data_ptr())
+        kv4 = self._mxfp4_planes()
         check(self.lib.ekv_kv4_quantize(C.byref(self._bank), C.byref(kv4), self._dt, 0, self.n_layers, max(self.extent), self._stream()),
               "ekv_kv4_quantize")
         cur = torch.cuda.current_stream(self.device)
         self.k.record_stream(cur)
         self.v.record_stream(cur)
         self.k = self.v = None
+        self._attach_mxfp4(kv4)
+        return self
+
+    @staticmethod
+    def _mxfp4_shape_check(head_dim, rep):
+        if head_dim != 128:
+            raise _lib.EkvError(f"quantize_mxfp4(): MXFP4 rows are built for head_dim 128, not {head_dim}")
+        if rep > 4:
+            raise _lib.EkvError(f"quantize_mxfp4(): MXFP4 rows are built for GQA factors up to 4, not {rep}")
+
+    def _mxfp4_planes(self):
+        shape = (self.n_layers, self.n_kv_heads, self.cap)
+        # rows that were never written keep code 0 / exponent byte 127 (scale 1): finite whatever the kernels prefetch
+        self.k4 = torch.zeros(*shape, self.head_dim // 2, dtype=torch.uint8, device=self.device)
+        self.v4 = torch.zeros_like(self.k4)
+        self.k_exp = torch.full((*shape, self.head_dim // 32), 127, dtype=torch.uint8, device=self.device)
+        self.v_exp = torch.full_like(self.k_exp, 127)
+        return _lib.Kv4(self.k4.data_ptr(), self.v4.data_ptr(), self.k_exp.data_ptr(), self.v_exp.data_ptr())
+
+    def _attach_mxfp4(self, kv4=None):
+        """The bank's rows are the MXFP4 planes from here on (``kv4=None``: a bank created without 16-bit rows allocates them now)."""
+        kv4 = self._mxfp4_planes() if kv4 is None else kv4
         self._bank.k, self._bank.v = self.k4.data_ptr(), self.v4.data_ptr()
         self._kv4, self.kv_quant = kv4, "mxfp4"
         self._slot_ok.clear()
         self._defer = None
-        return self
 
     def kv_bytes(self) -> int:
         """Bytes held for the K/V rows: 16-bit rows, FP8 codes + row scales (``2 * head_dim + 8`` per row pair), or MXFP4 codes +
@@ -791,7 +808,8 @@ class KVBankBatch:
 
     def __init__(self, n_seq, n_layers, n_q_heads, n_kv_heads, head_dim, cap, device="cuda", scored=True, dtype=torch.float16, kv_quant=None):
         """``kv_quant='fp8'``: the shared bank holds FP8 planes only from the start (the 16-bit rows of ``n_seq`` sequences are never
-        allocated); its sequences are filled by :meth:`adopt` from banks quantised by :meth:`KVBank.quantize_fp8`."""
+        allocated); its sequences are filled by :meth:`adopt` from banks quantised by :meth:`KVBank.quantize_fp8`.
+        ``kv_quant='mxfp4'``: likewise with MXFP4 planes, filled from banks quantised by :meth:`KVBank.quantize_mxfp4`."""
         if not 1 <= n_seq <= _lib.MAX_SEQS:
             raise ValueError(f"a decode batch holds 1..{_lib.MAX_SEQS} sequences, not {n_seq}")
         self.n_seq, self.n_layers = n_seq, n_layers
@@ -818,6 +836,22 @@ class KVBankBatch:
         self.bank.quantize_fp8()
         return self
 
+    def quantize_mxfp4(self):
+        """:meth:`KVBank.quantize_mxfp4` of the shared bank: the rows ``[0, max extent)`` of every layer become MXFP4 codes + block
+        exponents at their physical indices (slot maps, score rows, lengths and extents of every sequence carry over), the 16-bit
+        tensors are released and :meth:`attend` / :meth:`step_info` go to the kv4 batch calls.  ``sequence(i)`` then behaves as a
+        quantised :class:`KVBank`: decode steps only.  head_dim 128, GQA factors up to 4."""
+        self.bank.quantize_mxfp4()
+        return self
+
+    def _quant_call(self, what):
+        """(the batched call `what` of this bank's row kind, its leading descriptor arguments)."""
+        quant = self.bank._quant
+        if quant is None:
+            return getattr(self.lib, "ekv_batch_" + what), ()
+        name, desc = quant
+        return getattr(self.lib, f"{name}_batch_{what}"), (C.byref(desc),)
+
     def kv_bytes(self) -> int:
         """Bytes held for the K/V rows of all sequences (:meth:`KVBank.kv_bytes` of the shared bank)."""
         return self.bank.kv_bytes()
@@ -826,18 +860,18 @@ class KVBankBatch:
         """Sequence ``i`` takes over the state of ``src``, a bank of this batch's layer count and head shape that one sequence was
         prefilled on alone: K/V rows at their physical indices, slot maps, score rows (ordered layout), lengths and extents.  The
         rows behind ``src.cap`` keep this bank's own free list, so a shorter ``src.cap`` is fine.  A quantised batch takes a quantised
-        source (codes and row scales are copied as they are); 16-bit and FP8 rows do not mix."""
+        source of the same kind (codes and row scales / block exponents are copied as they are); 16-bit, FP8 and MXFP4 rows do not mix."""
         b = self.bank
         if (src.n_layers, src.n_q_heads, src.n_kv_heads, src.head_dim, src.dtype) != (self.n_layers, b.n_q_heads, b.n_kv_heads, b.head_dim, b.dtype) \
                 or src.cap > b.cap or not 0 <= i < self.n_seq:
             raise ValueError("adopt(): the source bank must have this batch's layers, heads, head_dim and dtype, and cap <= the batch's")
         if src.kv_quant != b.kv_quant:
             raise ValueError(f"adopt(): the source bank's rows (kv_quant={src.kv_quant!r}) are not this batch's (kv_quant={b.kv_quant!r}): "
-                             "quantize_fp8() both or neither")
+                             "quantize_fp8() both or neither, or quantize_mxfp4() both")
         src.join()
         l0, l1, c = i * self.n_layers, (i + 1) * self.n_layers, src.cap
         b._ensure_ordered(l0, self.n_layers)
-        rows = ("k", "v") if b.kv_quant is None else ("k8", "v8", "k_scale", "v_scale")
+        rows = {None: ("k", "v"), "fp8": ("k8", "v8", "k_scale", "v_scale"), "mxfp4": ("k4", "v4", "k_exp", "v_exp")}[b.kv_quant]
         for name in rows + ("slot_of_pos", "score_sum", "score_sq", "score_cnt"):      # (the properties hand out the ordered layout)
             t = getattr(src, name)
             if t is not None:
@@ -876,19 +910,16 @@ class KVBankBatch:
         st, tb, _ = self.make_table(plans, layer, active, n_split)
         info = (C.c_int32 * 10)()
         b = self.bank
-        if b._kv8 is not None:
-            check(self.lib.ekv_kv8_batch_step_info(C.byref(b._bank), C.byref(st), b._dt, C.byref(b._kv8), tb, len(tb), info, 10), "ekv_kv8_batch_step_info")
-        else:
-            check(self.lib.ekv_batch_step_info(C.byref(b._bank), C.byref(st), b._dt, tb, len(tb), info, 10), "ekv_batch_step_info")
+        fn, desc = self._quant_call("step_info")      # (FP8 / MXFP4 rows: the kv8 / kv4 batch call, the descriptor behind the dtype)
+        check(fn(C.byref(b._bank), C.byref(st), b._dt, *desc, tb, len(tb), info, 10), fn.__name__)
         keys = ("n_split", "fused", "two_pass", "wide", "n_qblocks", "qb_rows", "n_col_parts", "fold_in_kernel", "n_launches", "fused_order")
         return dict(zip(keys, (int(x) for x in info)))
 
     def workspace_bytes(self, st, tb) -> int:
         """Workspace of the batched call of (shared step, table) as :meth:`make_table` returns them."""
         b = self.bank
-        if b._kv8 is not None:
-            return self.lib.ekv_kv8_batch_workspace_bytes(C.byref(b._bank), C.byref(st), b._dt, C.byref(b._kv8), tb, len(tb))
-        return self.lib.ekv_batch_workspace_bytes(C.byref(b._bank), C.byref(st), b._dt, tb, len(tb))
+        fn, desc = self._quant_call("workspace_bytes")
+        return fn(C.byref(b._bank), C.byref(st), b._dt, *desc, tb, len(tb))
 
     def attend(self, plans, q, k_new, v_new, layer, active=None, out=None, evict_ids=None, n_split=0):
         """q / out ``[B', Hq, 1, D]``, k_new / v_new ``[B', H, 1, D]``: row i belongs to ``active[i]`` (default: every sequence).
@@ -913,10 +944,8 @@ class KVBankBatch:
         bank_ref, st_ref = C.byref(b._bank), C.byref(st)
         ws = b._workspace(self.workspace_bytes(st, tb))
         tensors = (_ptr(q), _ptr(k_new), _ptr(v_new), _ptr(out), _ptr(evict_ids) if k_max > 0 else None, _ptr(ws), ws.numel(), b._stream())
-        if b._kv8 is not None:      # FP8 rows: the kv8 batch call, the descriptor behind the dtype
-            check(self.lib.ekv_kv8_batch_step_attend(bank_ref, st_ref, b._dt, C.byref(b._kv8), tb, n, *tensors), "ekv_kv8_batch_step_attend")
-        else:
-            check(self.lib.ekv_batch_step_attend(bank_ref, st_ref, b._dt, tb, n, *tensors), "ekv_batch_step_attend")
+        fn, desc = self._quant_call("step_attend")
+        check(fn(bank_ref, st_ref, b._dt, *desc, tb, n, *tensors), fn.__name__)
         for e in tb:
             b.n_slots[e.layer] = e.n_slots - e.n_evict
             b.extent[e.layer] = e.phys_extent

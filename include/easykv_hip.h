@@ -335,7 +335,7 @@ int ekv_kv4_dequantize(const ekv_bank *bank, const ekv_kv4 *kv4, int32_t out_dty
  * partial q . codes is multiplied by its block's 2^e before the group sum, V codes are converted to fp32 with the block's scale, and
  * the appended row is quantised by its lane group (codes + exponents written to the recycled row).  Everything behind the logits is
  * the 16-bit step's.  EKV_E_UNSUPPORTED from the dry run, before anything is launched: q_len > 1, rope_on_read, head_dim != 128, a
- * GQA factor > 4.  A missing plane is EKV_E_ARG.  There is no batch form, and the row moves do not serve kv4 banks. */
+ * GQA factor > 4.  A missing plane is EKV_E_ARG.  The row moves do not serve kv4 banks; the batch form is ekv_kv4_batch_* below. */
 int ekv_kv4_step_check(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const ekv_kv4 *kv4);
 int ekv_kv4_step_info(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const ekv_kv4 *kv4, int32_t *info, int32_t n_info);
 size_t ekv_kv4_workspace_bytes(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const ekv_kv4 *kv4);
@@ -407,6 +407,32 @@ int ekv_kv8_batch_step_info(const ekv_bank *bank, const ekv_step *step, int32_t 
 size_t ekv_kv8_batch_workspace_bytes(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const ekv_kv8 *kv8, const ekv_seq *seqs,
                                      int32_t n_seq);
 int ekv_kv8_batch_step_attend(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const ekv_kv8 *kv8, const ekv_seq *seqs,
+                              int32_t n_seq, const void *q, const void *k_new, const void *v_new, void *out, int32_t *evict_ids,
+                              void *workspace, size_t workspace_bytes, void *stream);
+
+/* Batched decode steps on a kv4 bank ("kv4 batches"; ABI 8, additive): the ekv_kv8_batch_* signatures with the kv4 descriptor.  The
+ * table, the shared step and the call's tensors are those of ekv_batch_step_attend; the bank's rows are the code and exponent planes
+ * of `kv4` (bank->k / bank->v are not read), and `dtype` is the type of q, k_new, v_new and out.
+ *
+ * Accepted: the intersection of what a kv4 step and a batched step accept — q_len == 1 with plain keys at head_dim 128, a GQA factor
+ * <= 4 (factor 3 on the padded build), fp16 and bf16, in the whole-step form (phases == 0, defer_layers == 0) on the ordered score-row
+ * layout; at most EKV_MAX_SEQS entries, at most one victim per entry and step, at most 6144 slots and cap % 4 == 0 for scored
+ * policies.  Planned exactly as ekv_batch_step_attend of the same table (same key-range splits, launches, workspace and info fields,
+ * fused_order 0) and run on the kv4 builds of the batch instances: per entry the arithmetic is that of ekv_kv4_step_attend of the
+ * entry's geometry under the same n_split, the row an entry appends is quantised by its lane group into the row the entry's free list
+ * names (codes + block exponents), and it is attended as quantised.  The scorer, the fold and the range compaction behind the
+ * attention kernels are the 16-bit batch's: they read logits and partials, never a row.
+ * The refusals of both families apply unchanged.  EKV_E_UNSUPPORTED from the dry run, nothing launched and 0 workspace bytes: head_dim
+ * != 128, a GQA factor > 4, q_len > 1, rope_on_read, any `phases` bit, defer_layers, tova_head_mean, scored shapes only the generic
+ * scorer serves.  EKV_E_ARG: a NULL descriptor or plane, a dtype other than EKV_DTYPE_F16 / _BF16, and everything
+ * ekv_batch_step_check calls a bad table. */
+int ekv_kv4_batch_step_check(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const ekv_kv4 *kv4, const ekv_seq *seqs,
+                             int32_t n_seq);
+int ekv_kv4_batch_step_info(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const ekv_kv4 *kv4, const ekv_seq *seqs,
+                            int32_t n_seq, int32_t *info, int32_t n_info);
+size_t ekv_kv4_batch_workspace_bytes(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const ekv_kv4 *kv4, const ekv_seq *seqs,
+                                     int32_t n_seq);
+int ekv_kv4_batch_step_attend(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const ekv_kv4 *kv4, const ekv_seq *seqs,
                               int32_t n_seq, const void *q, const void *k_new, const void *v_new, void *out, int32_t *evict_ids,
                               void *workspace, size_t workspace_bytes, void *stream);
 

@@ -24,9 +24,19 @@ score state, quantised (KVBankBatch.quantize_fp8 / KVBank.quantize_fp8):
   batched_kv8        one ekv_kv8_batch_step_attend per layer over the B sequences (table prebuilt) — against `batched`
   solo_kv8_deferred  B FP8 attend(defer=True) calls per layer + one flush() per token — what a caller of FP8 banks had before
   ragged_kv8         the FP8 batched call at the ragged lengths — against `ragged`
-Every leg also reports its algorithmic bytes per per-layer call (FP8 rows: 2 * D + 8 bytes per K+V row pair instead of 4 * D).
+and with --mxfp4 (output: profiles/batch_kv4_bench.json), interleaved in the same way with `batched`, `batched_kv8`, `ragged` and
+`ragged_kv8` — the yardsticks of the same run; the other 16-bit legs are left to the two files above — on MXFP4 copies of the same
+state (KVBankBatch.quantize_mxfp4 / KVBank.quantize_mxfp4):
+  batched_kv4        one ekv_kv4_batch_step_attend per layer over the B sequences (table prebuilt)
+  solo_kv4_deferred  B MXFP4 attend(defer=True) calls per layer + one flush() per token — what a caller of MXFP4 banks had before
+  ragged_kv4         the MXFP4 batched call at the ragged lengths
+plus one GQA x 4 table (Hq 32 over H 8, B = 8 and 32; key "gqa4"): `batched` and `batched_kv4` as planned, with a forced key-range split
+(n_split = 8: the split kernel's GQA builds do not spill) and forced into one launch (n_split = 1: the one-launch GQA x 4 kv4 build
+spills, profiles/batch_kv4_registers.txt).
+Every leg also reports its algorithmic bytes per per-layer call (K+V row pair: 4 * D bytes in 16 bits, 2 * D + 8 as FP8 codes + row
+scales, D + D / 16 as MXFP4 codes + block exponents).
 
-Usage: python tools/bench_batch.py [--reps 9] [--tokens 24] [--warm 20] [--batches 1,2,4,8,16,32] [--kv8] [--out profiles/batch_bench.json]"""
+Usage: python tools/bench_batch.py [--reps 9] [--tokens 24] [--warm 20] [--batches 1,2,4,8,16,32] [--kv8 | --mxfp4] [--out profiles/batch_bench.json]"""
 from __future__ import annotations
 
 import argparse
@@ -94,40 +104,42 @@ def _tokens(B, lps, g, dev, n=8):
     return tuple(torch.randn(n, lps, B, hh, 1, D, generator=g, device=dev).half() for hh in (HQ, H, H))
 
 
-def _quantised_copy(src, make):
-    """A bank from `make()` holding the state of `src` (rows, slot maps, score rows, lengths, extents), quantised to FP8 rows."""
+def _quantised_copy(src, make, rows="kv8"):
+    """A bank from `make()` holding the state of `src` (rows, slot maps, score rows, lengths, extents), quantised to FP8 / MXFP4 rows."""
     dst = make()
     for name in ("k", "v", "slot_of_pos", "score_sum", "score_sq", "score_cnt"):
         getattr(dst, name).copy_(getattr(src, name))
     dst.n_slots, dst.extent = list(src.n_slots), list(src.extent)
-    return dst.quantize_fp8()
+    return dst.quantize_mxfp4() if rows == "kv4" else dst.quantize_fp8()
 
 
-def batched_kv8_leg(bat, lps, plans, toks):
-    """The FP8 twin of a batched leg: the same bank contents quantised, the same tables and tokens, straight through the C ABI."""
+def batched_quant_leg(bat, lps, plans, toks, rows="kv8", n_split=0):
+    """The FP8 / MXFP4 twin of a batched leg: the same bank contents quantised, the same tables and tokens, straight through the C ABI."""
     from easykv_amd import KVBankBatch
     B = bat.n_seq
-    bat8 = KVBankBatch(B, lps, HQ, H, D, cap=BUDGET + 1 + 63)
-    _quantised_copy(bat.bank, lambda: bat8.bank)
+    batq = KVBankBatch(B, lps, HQ, H, D, cap=BUDGET + 1 + 63)
+    _quantised_copy(bat.bank, lambda: batq.bank, rows)
     qs, ks, vs = toks
-    out = torch.empty(B, HQ, 1, D, dtype=torch.float16, device=bat8.device)
-    ids = torch.empty(B, H, 1, dtype=torch.int32, device=bat8.device)
-    tables = [bat8.make_table(plans, l)[:2] for l in range(lps)]
-    b = bat8.bank
-    ws = b._workspace(max(bat8.workspace_bytes(st, tb) for st, tb in tables))
-    assert bat8.step_info(plans, 0) == bat.step_info(plans, 0)      # planned as the 16-bit batched call of the same table
+    out = torch.empty(B, HQ, 1, D, dtype=torch.float16, device=batq.device)
+    ids = torch.empty(B, H, 1, dtype=torch.int32, device=batq.device)
+    tables = [batq.make_table(plans, l, n_split=n_split)[:2] for l in range(lps)]
+    b = batq.bank
+    ws = b._workspace(max(batq.workspace_bytes(st, tb) for st, tb in tables))
+    assert batq.step_info(plans, 0, n_split=n_split) == bat.step_info(plans, 0, n_split=n_split)      # planned as the 16-bit batched call of the same table
+    call, desc = (batq.lib.ekv_kv4_batch_step_attend, b._kv4) if rows == "kv4" else (batq.lib.ekv_kv8_batch_step_attend, b._kv8)
 
-    def raw8(i):
+    def rawq(i):
         j = i % qs.shape[0]
         for l, (st, tb) in enumerate(tables):
-            rc = bat8.lib.ekv_kv8_batch_step_attend(C.byref(b._bank), C.byref(st), b._dt, C.byref(b._kv8), tb, B, qs[j, l].data_ptr(), ks[j, l].data_ptr(),
-                                                    vs[j, l].data_ptr(), out.data_ptr(), ids.data_ptr(), ws.data_ptr(), ws.numel(), b._stream())
+            rc = call(C.byref(b._bank), C.byref(st), b._dt, C.byref(desc), tb, B, qs[j, l].data_ptr(), ks[j, l].data_ptr(),
+                      vs[j, l].data_ptr(), out.data_ptr(), ids.data_ptr(), ws.data_ptr(), ws.numel(), b._stream())
             assert rc == 0, rc
-    return raw8
+    return rawq
 
 
-def batched_legs(B, lps, lens, g, kv8=False):
-    """-> {name: forward} of the batched call over B sequences at `lens` (rows before the token), through the C ABI and through the engine."""
+def batched_legs(B, lps, lens, g, quant=(), n_split=0):
+    """-> (forward through the C ABI, forward through the engine, plan info, one twin per row kind in `quant`) of the batched call over B
+    sequences at `lens` (rows before the token)."""
     from easykv_amd import KVBankBatch
     bat = KVBankBatch(B, lps, HQ, H, D, cap=BUDGET + 1 + 63)
     _fill(bat.bank, [s * lps + l for s in range(B) for l in range(lps)], [lens[s] for s in range(B) for _ in range(lps)], g)
@@ -135,10 +147,10 @@ def batched_legs(B, lps, lens, g, kv8=False):
     qs, ks, vs = _tokens(B, lps, g, bat.device)
     out = torch.empty(B, HQ, 1, D, dtype=torch.float16, device=bat.device)
     ids = torch.empty(B, H, 1, dtype=torch.int32, device=bat.device)
-    tables = [bat.make_table(plans, l)[:2] for l in range(lps)]      # steady state: every entry evicts, the table never changes
+    tables = [bat.make_table(plans, l, n_split=n_split)[:2] for l in range(lps)]      # steady state: every entry evicts, the table never changes
     b = bat.bank
     ws = b._workspace(max(bat.lib.ekv_batch_workspace_bytes(C.byref(b._bank), C.byref(st), b._dt, tb, B) for st, tb in tables))
-    info = bat.step_info(plans, 0)
+    info = bat.step_info(plans, 0, n_split=n_split)
 
     def raw(i):
         j = i % qs.shape[0]
@@ -151,22 +163,22 @@ def batched_legs(B, lps, lens, g, kv8=False):
         j = i % qs.shape[0]
         for l in range(lps):
             bat.attend(plans, qs[j, l], ks[j, l], vs[j, l], l, out=out, evict_ids=ids)
-    if kv8:      # (the twin is built before any leg has stepped the 16-bit bank)
-        return raw, engine, info, batched_kv8_leg(bat, lps, plans, (qs, ks, vs))
-    return raw, engine, info
+    # (the twins are built before any leg has stepped the 16-bit bank)
+    return (raw, engine, info) + tuple(batched_quant_leg(bat, lps, plans, (qs, ks, vs), rows, n_split) for rows in quant)
 
 
-def solo_legs(B, lps, g, kv8=False):
+def solo_legs(B, lps, g, quant=(), only_quant=False):
     from easykv_amd import KVBank
     n = BUDGET
     plan = _plan(n)
-    whole = KVBank(B * lps, HQ, H, D, cap=n + 1 + 63)
-    _fill(whole, range(B * lps), [n] * (B * lps), g)
+    whole = None if only_quant else KVBank(B * lps, HQ, H, D, cap=n + 1 + 63)      # (only_quant: the 16-bit solo legs are not run)
+    if not only_quant:
+        _fill(whole, range(B * lps), [n] * (B * lps), g)
     defer = KVBank(B * lps, HQ, H, D, cap=n + 1 + 63)
     _fill(defer, range(B * lps), [n] * (B * lps), g)
-    qs, ks, vs = _tokens(B, lps, g, whole.device)
-    out = torch.empty(1, HQ, 1, D, dtype=torch.float16, device=whole.device)
-    ids = torch.empty(1, H, 1, dtype=torch.int32, device=whole.device)
+    qs, ks, vs = _tokens(B, lps, g, defer.device)
+    out = torch.empty(1, HQ, 1, D, dtype=torch.float16, device=defer.device)
+    ids = torch.empty(1, H, 1, dtype=torch.int32, device=defer.device)
 
     def f_whole(i):
         j = i % qs.shape[0]
@@ -180,17 +192,17 @@ def solo_legs(B, lps, g, kv8=False):
             for s in range(B):
                 defer.attend(plan, qs[j, l, s:s + 1], ks[j, l, s:s + 1], vs[j, l, s:s + 1], layer_begin=s * lps + l, defer=True, out=out)
         defer.flush()
-    if not kv8:
-        return f_whole, f_defer
-    defer8 = _quantised_copy(defer, lambda: KVBank(B * lps, HQ, H, D, cap=n + 1 + 63))
+    def deferred_twin(rows):
+        bank = _quantised_copy(defer, lambda: KVBank(B * lps, HQ, H, D, cap=n + 1 + 63), rows)
 
-    def f_defer8(i):
-        j = i % qs.shape[0]
-        for l in range(lps):
-            for s in range(B):
-                defer8.attend(plan, qs[j, l, s:s + 1], ks[j, l, s:s + 1], vs[j, l, s:s + 1], layer_begin=s * lps + l, defer=True, out=out)
-        defer8.flush()
-    return f_whole, f_defer, f_defer8
+        def f_deferq(i):
+            j = i % qs.shape[0]
+            for l in range(lps):
+                for s in range(B):
+                    bank.attend(plan, qs[j, l, s:s + 1], ks[j, l, s:s + 1], vs[j, l, s:s + 1], layer_begin=s * lps + l, defer=True, out=out)
+            bank.flush()
+        return f_deferq
+    return (f_whole, f_defer) + tuple(deferred_twin(rows) for rows in quant)
 
 
 def uniform_legs(B, lps, g):
@@ -240,13 +252,19 @@ def uniform_legs(B, lps, g):
     return legs
 
 
-def bytes_per_call(lens, kv8=False):
-    """Algorithmic bytes of one per-layer call over sequences of `lens` rows; kv8: K/V rows as FP8 codes + two fp32 scales per row pair."""
+PAIR_BYTES = {"kv16": 4 * D, "kv8": 2 * D + 8, "kv4": D + D // 16}      # one K+V row pair: 16-bit / FP8 codes + two fp32 scales / MXFP4 codes + exponents
+
+
+def _rows_of(leg):
+    return "kv8" if "kv8" in leg else ("kv4" if "kv4" in leg else "kv16")
+
+
+def bytes_per_call(lens, rows="kv16"):
+    """Algorithmic bytes of one per-layer call over sequences of `lens` rows, their K/V rows held as `rows`."""
     total = 0
     for n in lens:
         b = algorithmic_bytes(H, HQ, D, n + 1, 1, 3)
-        kv16 = 2 * H * (n + 1) * D * 2
-        total += b["total"] - kv16 + H * (n + 1) * (2 * D + 8) if kv8 else b["total"]
+        total += b["total"] - H * (n + 1) * PAIR_BYTES["kv16"] + H * (n + 1) * PAIR_BYTES[rows]
     return total
 
 
@@ -257,17 +275,23 @@ def run_batch(B, args):
     rs = torch.Generator().manual_seed(20261016 + B)
     ragged = sorted(int(x) for x in torch.randint(255, BUDGET + 1, (B,), generator=rs))
     ragged[-1] = BUDGET      # (the envelope is the uniform shape)
-    raw, engine, info, *raw8 = batched_legs(B, lps, [BUDGET] * B, g, args.kv8)
+    quant = ("kv8", "kv4") if args.mxfp4 else (("kv8",) if args.kv8 else ())
+    raw, engine, info, *rawq = batched_legs(B, lps, [BUDGET] * B, g, quant)
     fns = {"batched": raw, "batched_engine": engine}
-    fns["solo_whole"], fns["solo_deferred"], *defer8 = solo_legs(B, lps, g, args.kv8)
-    fns.update(uniform_legs(B, lps, g))
-    if args.kv8:
-        fns["batched_kv8"], fns["solo_kv8_deferred"] = raw8[0], defer8[0]
+    solo_quant = ("kv4",) if args.mxfp4 else quant
+    fns["solo_whole"], fns["solo_deferred"], *deferq = solo_legs(B, lps, g, solo_quant, only_quant=args.mxfp4)
+    if not args.mxfp4:
+        fns.update(uniform_legs(B, lps, g))
+    fns.update({f"batched_{rows}": f for rows, f in zip(quant, rawq)})
+    fns.update({f"solo_{rows}_deferred": f for rows, f in zip(solo_quant, deferq)})
     if B > 1:
-        fns["ragged"], _, rinfo, *ragged8 = batched_legs(B, lps, ragged, g, args.kv8)
+        fns["ragged"], _, rinfo, *raggedq = batched_legs(B, lps, ragged, g, quant)
         assert rinfo == info, (rinfo, info)      # a ragged table plans as its envelope
-        if args.kv8:
-            fns["ragged_kv8"] = ragged8[0]
+        for rows, f in zip(quant, raggedq):
+            fns[f"ragged_{rows}"] = f
+    if args.mxfp4:      # the yardsticks of the same run and the three new legs; the other legs: profiles/batch_bench.json, batch_kv8_bench.json
+        keep = ("batched", "batched_kv8", "batched_kv4", "solo_kv4_deferred", "ragged", "ragged_kv8", "ragged_kv4")
+        fns = {k: f for k, f in fns.items() if k in keep}
     if args.legs:      # (a kernel trace of two legs: their launches alone)
         fns = {k: f for k, f in fns.items() if k in args.legs.split(",")}
     t = _interleave(fns, args.reps, args.tokens, args.warm)
@@ -278,22 +302,34 @@ def run_batch(B, args):
     ub = bytes_per_call([BUDGET] * B)
     for k, v in t.items():
         us = v["us"] / lps      # per per-layer call (solo legs: B calls; solo_deferred: + its share of the flush)
-        nb = bytes_per_call(ragged if k.startswith("ragged") else [BUDGET] * B, "kv8" in k)
+        nb = bytes_per_call(ragged if k.startswith("ragged") else [BUDGET] * B, _rows_of(k))
         res[k] = dict(us_per_layer_call=round(us, 2), run_to_run_spread=v["spread"], path_tokens_per_s=round(B / (us * 32 * 1e-6), 1),
                       bytes_per_layer_call=nb, gb_per_s=round(nb / (us * 1e-6) / 1e9, 1), frac_of_hbm_peak=round(nb / (us * 1e-6) / 1e9 / HBM_PEAK_GBS, 4))
     if args.legs:
         return res
     us = lambda k: res[k]["us_per_layer_call"]
-    res["ratio_batched_over_uniform_ordered"] = round(us("batched") / us("uniform_ordered"), 4)
-    res["ratio_batched_contig_over_uniform_ordered"] = round(us("batched_contig") / us("uniform_ordered"), 4)
-    res["ratio_batched_over_solo_whole"] = round(us("batched") / us("solo_whole"), 4)
-    res["ratio_batched_over_solo_deferred"] = round(us("batched") / us("solo_deferred"), 4)
+    if "uniform_ordered" in res:
+        res["ratio_batched_over_uniform_ordered"] = round(us("batched") / us("uniform_ordered"), 4)
+        res["ratio_batched_contig_over_uniform_ordered"] = round(us("batched_contig") / us("uniform_ordered"), 4)
+        res["ratio_batched_over_solo_whole"] = round(us("batched") / us("solo_whole"), 4)
+        res["ratio_batched_over_solo_deferred"] = round(us("batched") / us("solo_deferred"), 4)
     if "uniform_slot" in res:
         res["ratio_uniform_slot_over_uniform_ordered"] = round(us("uniform_slot") / us("uniform_ordered"), 4)
     if "batched_kv8" in res:
         res["ratio_batched_kv8_over_batched"] = round(us("batched_kv8") / us("batched"), 4)
-        res["ratio_batched_kv8_over_solo_kv8_deferred"] = round(us("batched_kv8") / us("solo_kv8_deferred"), 4)
+        if "solo_kv8_deferred" in res:
+            res["ratio_batched_kv8_over_solo_kv8_deferred"] = round(us("batched_kv8") / us("solo_kv8_deferred"), 4)
         res["byte_ratio_batched_kv8_over_batched"] = round(res["batched_kv8"]["bytes_per_layer_call"] / res["batched"]["bytes_per_layer_call"], 4)
+    if "batched_kv4" in res:
+        res["ratio_batched_kv4_over_batched"] = round(us("batched_kv4") / us("batched"), 4)
+        res["ratio_batched_kv4_over_batched_kv8"] = round(us("batched_kv4") / us("batched_kv8"), 4)
+        res["ratio_batched_kv4_over_solo_kv4_deferred"] = round(us("batched_kv4") / us("solo_kv4_deferred"), 4)
+        res["byte_ratio_batched_kv4_over_batched"] = round(res["batched_kv4"]["bytes_per_layer_call"] / res["batched"]["bytes_per_layer_call"], 4)
+        res["byte_ratio_batched_kv4_over_batched_kv8"] = round(res["batched_kv4"]["bytes_per_layer_call"] / res["batched_kv8"]["bytes_per_layer_call"], 4)
+    if "ragged_kv4" in res:
+        res["ratio_ragged_kv4_over_ragged"] = round(us("ragged_kv4") / us("ragged"), 4)
+        res["ratio_ragged_kv4_over_ragged_kv8"] = round(us("ragged_kv4") / us("ragged_kv8"), 4)
+        res["ratio_ragged_kv4_over_batched_kv4_at_envelope"] = round(us("ragged_kv4") / us("batched_kv4"), 4)
     if "ragged_kv8" in res:
         res["ratio_ragged_kv8_over_ragged"] = round(us("ragged_kv8") / us("ragged"), 4)
         res["ratio_ragged_kv8_over_batched_kv8_at_envelope"] = round(us("ragged_kv8") / us("batched_kv8"), 4)
@@ -304,6 +340,37 @@ def run_batch(B, args):
     return res
 
 
+def run_gqa4(B, args):
+    """The GQA x 4 table (Hq 32 over H 8): `batched` and `batched_kv4` at the uniform length, as planned, with a forced key-range split
+    and forced into one launch — the one-launch GQA x 4 kv4 build spills registers, the split kernel's does not."""
+    global HQ, H
+    dev = torch.device("cuda")
+    keep = (HQ, H)
+    HQ, H = 32, 8
+    try:
+        lps = 16
+        fns, plans = {}, {}
+        for name, n_split in (("planned", 0), ("split8", 8), ("one_launch", 1)):
+            g = torch.Generator(device=dev).manual_seed(3000 + B)      # (the same rows, maps and tokens under every plan)
+            raw, _, info, raw4 = batched_legs(B, lps, [BUDGET] * B, g, ("kv4",), n_split)
+            fns[f"batched_{name}"], fns[f"batched_kv4_{name}"], plans[name] = raw, raw4, info
+        t = _interleave(fns, args.reps, args.tokens, args.warm)
+        del fns
+        gc.collect()
+        torch.cuda.empty_cache()
+        res = {"layers_per_sequence": lps, "plans": plans}
+        for k, v in t.items():
+            us = v["us"] / lps
+            nb = bytes_per_call([BUDGET] * B, _rows_of(k))
+            res[k] = dict(us_per_layer_call=round(us, 2), run_to_run_spread=v["spread"], bytes_per_layer_call=nb, gb_per_s=round(nb / (us * 1e-6) / 1e9, 1))
+        for name in plans:
+            res[f"ratio_batched_kv4_over_batched_{name}"] = round(res[f"batched_kv4_{name}"]["us_per_layer_call"] / res[f"batched_{name}"]["us_per_layer_call"], 4)
+        res["byte_ratio_batched_kv4_over_batched"] = round(res["batched_kv4_planned"]["bytes_per_layer_call"] / res["batched_planned"]["bytes_per_layer_call"], 4)
+        return res
+    finally:
+        HQ, H = keep
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=9)
@@ -312,9 +379,12 @@ def main():
     ap.add_argument("--batches", default="1,2,4,8,16,32")
     ap.add_argument("--legs", default=None, help="comma-separated legs to run alone, e.g. batched,uniform_ordered (no ratios; for a kernel trace)")
     ap.add_argument("--kv8", action="store_true", help="add the FP8 legs batched_kv8, solo_kv8_deferred, ragged_kv8 (default --out: profiles/batch_kv8_bench.json)")
+    ap.add_argument("--mxfp4", action="store_true", help="the MXFP4 legs batched_kv4, solo_kv4_deferred, ragged_kv4 next to batched, batched_kv8, ragged, "
+                    "ragged_kv8, and the GQA x 4 table (default --out: profiles/batch_kv4_bench.json)")
+    ap.add_argument("--gqa4-batches", default="8,32", help="--mxfp4: batch sizes of the GQA x 4 table ('' = none)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    args.out = args.out or os.path.join(ROOT, "profiles", "batch_kv8_bench.json" if args.kv8 else "batch_bench.json")
+    args.out = args.out or os.path.join(ROOT, "profiles", "batch_kv4_bench.json" if args.mxfp4 else ("batch_kv8_bench.json" if args.kv8 else "batch_bench.json"))
     torch.cuda.set_device(0)
     res = {"device": torch.cuda.get_device_name(0), "reps": args.reps, "tokens_per_rep": args.tokens, "warm_tokens": args.warm,
            "hbm_peak_gb_per_s": HBM_PEAK_GBS,
@@ -323,6 +393,11 @@ def main():
     for B in (int(x) for x in args.batches.split(",")):
         res[f"B{B}"] = run_batch(B, args)
         print(f"B{B}", json.dumps(res[f"B{B}"]), flush=True)
+    if args.mxfp4 and not args.legs and args.gqa4_batches:
+        res["gqa4"] = {"shape": "Hq = 32 over H = 8 (GQA x 4), D = 128, otherwise as above; planned / split8 (n_split = 8) / one_launch (n_split = 1)"}
+        for B in (int(x) for x in args.gqa4_batches.split(",")):
+            res["gqa4"][f"B{B}"] = run_gqa4(B, args)
+            print(f"gqa4 B{B}", json.dumps(res["gqa4"][f"B{B}"]), flush=True)
     with open(args.out, "w") as f:
         json.dump(res, f, indent=1)
     print(json.dumps(res))
