@@ -13,25 +13,17 @@ LIB = os.environ.get("EASYKV_HIP_LIB") or os.path.join(CSRC, "libeasykv_hip.so")
 # (q/c - (s/c)**2); FMAs that are wanted are written as fmaf()/dot2/MFMA explicitly.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-Wall", "-Wno-unused-function"]
 OBJ = os.path.join(CSRC, "obj")
-
-
 MANIFEST = os.path.join(CSRC, "ekv_instances.def")
-# What the library holds beside the recorded set (objects() / all_objects() below are fixtures of the tests): the MXFP4 ("kv4") family,
-# whose lines the manifest includes from a file of its own, and the translation unit of its bank conversion.
-MANIFEST_KV4 = os.path.join(CSRC, "ekv_instances_kv4.def")
-EXTRA_SOURCES = ("ekv_kv4.hip",)
-# ... and beside those (extra_objects() is a fixture too): the batched MXFP4 family, from a manifest file of its own again
-MANIFEST_KV4_BATCH = os.path.join(CSRC, "ekv_instances_kv4_batch.def")
 
 
 def _tags(*words):
-    """File-name tags of an instance's words, in the order the object names have always had: rope, batch / kv8, bf16."""
-    return "".join("_" + w for w in ("batch", "kv8", "bf16") if w in words)
+    """File-name tags of an instance's words, in the order the object names have always had: batch, kv8 / kv4, bf16."""
+    return "".join("_" + w for w in ("batch", "kv8", "kv4", "bf16") if w in words)
 
 
 def _on(*words):
-    sw = {"bf16": "EKV_BF16", "kv8": "EKV_KV8", "batch": "EKV_BATCH"}
-    return [f"-D{sw[w]}=1" for w in ("kv8", "batch", "bf16") if w in words]
+    sw = {"bf16": "EKV_BF16", "kv8": "EKV_KV8", "kv4": "EKV_KV4", "batch": "EKV_BATCH"}
+    return [f"-D{sw[w]}=1" for w in ("kv8", "kv4", "batch", "bf16") if w in words]
 
 
 # family of a manifest line -> (its kernel source, object name, -D switches), all from the line's words
@@ -48,12 +40,6 @@ FAMILIES = {
         _on(elem) + [f"-DEKV_D={d}", f"-DEKV_WIDE_MODE={m}"] + (["-DEKV_WIDE_ROPE=1"] if keys == "rope" else [])),
     "EKV_CHUNK_LDS": lambda d, elem: ("ekv_chunk_lds.inc", f"ekv_chunk_lds_d{d}" + _tags(elem), _on(elem) + [f"-DEKV_D={d}"]),
     "EKV_RESIDENT": lambda d, elem: ("ekv_attn_resident.inc", f"ekv_attn_resident_d{d}" + _tags(elem), _on(elem)),
-    "EKV_DECODE_KV4": lambda d, elem: (
-        "ekv_attn_decode.inc", f"ekv_attn_decode_d{d}_plain_kv4" + _tags(elem),
-        _on(elem) + ["-DEKV_KV4=1", f"-DEKV_D={d}", "-DEKV_ROPE=false"]),
-    "EKV_DECODE_KV4_BATCH": lambda d, elem: (
-        "ekv_attn_decode.inc", f"ekv_attn_decode_d{d}_plain_batch_kv4" + _tags(elem),
-        _on(elem) + ["-DEKV_KV4=1", "-DEKV_BATCH=1", f"-DEKV_D={d}", "-DEKV_ROPE=false"]),
     "EKV_SCORE_SELECT": lambda nt, elem: ("ekv_score_select.inc", f"ekv_score_select_nt{nt}" + _tags(elem), _on(elem) + [f"-DEKV_SS_NT={nt}"]),
 }
 
@@ -67,73 +53,21 @@ def instances():
 
 def sources():
     """The library's own translation units: the .hip files, and the host-only planner (plain C++: no -x hip, no device pass)."""
-    return sorted(p for p in glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.cpp"))
-                  if os.path.basename(p) not in EXTRA_SOURCES)
-
-
-def _file_instances(path):
-    with open(path) as f:
-        found = re.findall(r"^(EKV_[A-Z0-9_]+)\(([^)]*)\)", f.read(), re.M)
-    return [(fam, tuple(w.strip() for w in args.split(","))) for fam, args in found]
-
-
-def extra_instances():
-    """(family, words) of the lines of ekv_instances_kv4.def."""
-    return _file_instances(MANIFEST_KV4)
-
-
-def batch_kv4_instances():
-    """(family, words) of the lines of ekv_instances_kv4_batch.def."""
-    return _file_instances(MANIFEST_KV4_BATCH)
-
-
-def batch_kv4_objects():
-    """The objects built and linked beside all_objects() and extra_objects(): the instances of ekv_instances_kv4_batch.def."""
-    objs = []
-    for fam, words in batch_kv4_instances():
-        inc, name, defs = FAMILIES[fam](*words)
-        objs.append((name, defs + ["-x", "hip", os.path.join(CSRC, inc)]))
-    return objs
-
-
-def linked_objects():
-    """Everything build_lib compiles and links, in link order (tools/kernel_regs.py and tools/isa_identity.py read it too)."""
-    return all_objects() + extra_objects() + batch_kv4_objects()
-
-
-def extra_objects():
-    """The objects built and linked beside all_objects(): EXTRA_SOURCES and the instances of ekv_instances_kv4.def."""
-    objs = [(os.path.splitext(name)[0], [os.path.join(CSRC, name)]) for name in EXTRA_SOURCES]
-    for fam, words in extra_instances():
-        inc, name, defs = FAMILIES[fam](*words)
-        objs.append((name, defs + ["-x", "hip", os.path.join(CSRC, inc)]))
-    return objs
-
-
-def _instance_objects(combined):
-    """Manifest lines that switch on kv8 AND batch (`combined`: an orthogonal combination of two instances that exist), or the others."""
-    objs = []
-    for fam, words in instances():
-        if ("kv8" in words and "batch" in words) == combined:
-            inc, name, defs = FAMILIES[fam](*words)
-            objs.append((name, defs + ["-x", "hip", os.path.join(CSRC, inc)]))
-    return objs
+    return sorted(glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.cpp")))
 
 
 def objects():
-    """(object name, hipcc arguments that select its source) of the library's own files and of the manifest's instances, the kv8 + batch
-    combinations left out: the set tests/golden/dispatch/instances.txt records (a fixture a change that adds instances may not edit)."""
-    return [(os.path.splitext(os.path.basename(src))[0], [src]) for src in sources()] + _instance_objects(False)
-
-
-def all_objects():
-    """Everything that is compiled and linked into the library: objects() and the kv8 + batch combination instances, whose names
-    tests/test_batch_kv8_cpu.py holds to the manifest."""
-    return objects() + _instance_objects(True)
+    """(object name, hipcc arguments that select its source) of everything that is compiled and linked, in link order: the library's
+    own files, then one object per line of the manifest (tests/golden/dispatch/instances.txt records the names)."""
+    objs = [(os.path.splitext(os.path.basename(src))[0], [src]) for src in sources()]
+    for fam, words in instances():
+        inc, name, defs = FAMILIES[fam](*words)
+        objs.append((name, defs + ["-x", "hip", os.path.join(CSRC, inc)]))
+    return objs
 
 
 def headers():
-    return (glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.inc")) + [MANIFEST, MANIFEST_KV4, MANIFEST_KV4_BATCH] +
+    return (glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.inc")) + [MANIFEST] +
             [os.path.join(HERE, "..", "include", "easykv_hip.h")])
 
 
@@ -141,8 +75,7 @@ def stale() -> bool:
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    deps = sources() + [os.path.join(CSRC, name) for name in EXTRA_SOURCES] + headers()
-    return any(os.path.getmtime(d) > t for d in deps)
+    return any(os.path.getmtime(d) > t for d in sources() + headers())
 
 
 def build_lib(force: bool = False, verbose: bool = False, jobs: int = 0) -> str:
@@ -154,7 +87,7 @@ def build_lib(force: bool = False, verbose: bool = False, jobs: int = 0) -> str:
     os.makedirs(OBJ, exist_ok=True)
     hdr_t = max(os.path.getmtime(h) for h in headers())
     todo, objs = [], []
-    for name, args in linked_objects():
+    for name, args in objects():
         obj = os.path.join(OBJ, name + ".o")
         objs.append(obj)
         src_t = os.path.getmtime(args[-1])

@@ -23,22 +23,24 @@ POLICY_CODES = {"full": POLICY_NONE, "h2o_head": POLICY_H2O_HEAD, "roco": POLICY
 DTYPE_F16, DTYPE_BF16 = 0, 1
 DTYPE_CODES = {torch.float16: DTYPE_F16, torch.bfloat16: DTYPE_BF16}
 
+MAX_SEQS = 64      # EKV_MAX_SEQS: entries of one batched decode step
+DTYPE_F32 = 2      # ekv_kv8_dequantize's / ekv_kv4_dequantize's out_dtype only
+STEP_CALLS = ("step_check", "step_info", "workspace_bytes", "step_attend")
+
+
+def step_call_name(rows, batch, what):
+    """Name of the call `what` (one of STEP_CALLS) of the step family for a bank's row format — None (16-bit rows: the _typed calls),
+    "kv8" or "kv4" — and a uniform step or a batched one (include/easykv_hip.h)."""
+    if rows is None and not batch:
+        return "ekv_" + what + "_typed"
+    return "ekv_" + (rows + "_" if rows else "") + ("batch_" if batch else "") + what
+
+
+# every function of include/easykv_hip.h (tests/test_host_cpu.py holds the tuple to the header's declarations)
 EXPORTS = ("ekv_abi_version", "ekv_strerror", "ekv_workspace_bytes", "ekv_step_plan", "ekv_bank_reset", "ekv_state_init",
            "ekv_step_attend", "ekv_gather_ordered", "ekv_scatter_rows", "ekv_compact_inplace", "ekv_step_check", "ekv_step_info",
-           "ekv_rows_to_slots", "ekv_rows_to_order", "ekv_workspace_bytes_typed", "ekv_step_check_typed", "ekv_step_info_typed",
-           "ekv_step_attend_typed", "ekv_batch_step_check", "ekv_batch_step_info", "ekv_batch_workspace_bytes", "ekv_batch_step_attend")
-MAX_SEQS = 64      # EKV_MAX_SEQS: entries of one batched decode step
-# the FP8 K/V storage calls (include/easykv_hip.h, "kv8"), checked and typed by load() like EXPORTS.  A list of their own:
-# tests/test_host_cpu.py pins EXPORTS to the header's names as a digit-free pattern reads them, which a name with "kv8" in it is not.
-EXPORTS_KV8 = ("ekv_kv8_quantize", "ekv_kv8_dequantize", "ekv_kv8_step_check", "ekv_kv8_step_info", "ekv_kv8_workspace_bytes",
-               "ekv_kv8_step_attend", "ekv_kv8_batch_step_check", "ekv_kv8_batch_step_info", "ekv_kv8_batch_workspace_bytes",
-               "ekv_kv8_batch_step_attend")
-DTYPE_F32 = 2      # ekv_kv8_dequantize's / ekv_kv4_dequantize's out_dtype only
-# the MXFP4 K/V storage calls (include/easykv_hip.h, "kv4"): a list of their own for the same reason
-EXPORTS_KV4 = ("ekv_kv4_quantize", "ekv_kv4_dequantize", "ekv_kv4_step_check", "ekv_kv4_step_info", "ekv_kv4_workspace_bytes",
-               "ekv_kv4_step_attend")
-# the batched decode step on MXFP4 rows ("kv4 batches"): a list of its own once more — tests/test_kv4_cpu.py pins EXPORTS_KV4 to the six above
-EXPORTS_KV4_BATCH = ("ekv_kv4_batch_step_check", "ekv_kv4_batch_step_info", "ekv_kv4_batch_workspace_bytes", "ekv_kv4_batch_step_attend")
+           "ekv_rows_to_slots", "ekv_rows_to_order", "ekv_kv8_quantize", "ekv_kv8_dequantize", "ekv_kv4_quantize", "ekv_kv4_dequantize") + tuple(
+               step_call_name(rows, batch, what) for rows in (None, "kv8", "kv4") for batch in (False, True) for what in STEP_CALLS)
 
 
 class Bank(C.Structure):
@@ -89,7 +91,7 @@ def load():
         raise EkvError(f"{LIB} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                        "(hipcc --offload-arch=gfx950).  There is no CPU fallback for the product path.")
     lib = C.CDLL(LIB)
-    for name in EXPORTS + EXPORTS_KV8 + EXPORTS_KV4 + EXPORTS_KV4_BATCH:
+    for name in EXPORTS:
         if not hasattr(lib, name):
             raise EkvError(f"{LIB} does not export {name}")
     vp, i32 = C.c_void_p, C.c_int32
@@ -109,42 +111,20 @@ def load():
     lib.ekv_step_info.argtypes = [C.POINTER(Bank), C.POINTER(Step), C.POINTER(C.c_int32), C.c_int32]
     lib.ekv_rows_to_slots.argtypes = [C.POINTER(Bank), i32, i32, i32, vp]
     lib.ekv_rows_to_order.argtypes = [C.POINTER(Bank), i32, i32, i32, vp]
-    lib.ekv_workspace_bytes_typed.argtypes = [C.POINTER(Bank), C.POINTER(Step), i32]
-    lib.ekv_step_check_typed.argtypes = [C.POINTER(Bank), C.POINTER(Step), i32]
-    lib.ekv_step_info_typed.argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, C.POINTER(C.c_int32), C.c_int32]
-    lib.ekv_step_attend_typed.argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
-    lib.ekv_kv8_quantize.argtypes = [C.POINTER(Bank), C.POINTER(Kv8), i32, i32, i32, i32, vp]
-    lib.ekv_kv8_dequantize.argtypes = [C.POINTER(Bank), C.POINTER(Kv8), i32, i32, i32, i32, vp, vp, vp]
-    lib.ekv_kv8_step_check.argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, C.POINTER(Kv8)]
-    lib.ekv_kv8_step_info.argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, C.POINTER(Kv8), C.POINTER(C.c_int32), C.c_int32]
-    lib.ekv_kv8_workspace_bytes.argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, C.POINTER(Kv8)]
-    lib.ekv_kv8_step_attend.argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, C.POINTER(Kv8), vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
-    lib.ekv_kv4_quantize.argtypes = [C.POINTER(Bank), C.POINTER(Kv4), i32, i32, i32, i32, vp]
-    lib.ekv_kv4_dequantize.argtypes = [C.POINTER(Bank), C.POINTER(Kv4), i32, i32, i32, i32, vp, vp, vp]
-    lib.ekv_kv4_step_check.argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, C.POINTER(Kv4)]
-    lib.ekv_kv4_step_info.argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, C.POINTER(Kv4), C.POINTER(C.c_int32), C.c_int32]
-    lib.ekv_kv4_workspace_bytes.argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, C.POINTER(Kv4)]
-    lib.ekv_kv4_step_attend.argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, C.POINTER(Kv4), vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
-    lib.ekv_batch_step_check.argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, C.POINTER(Seq), i32]
-    lib.ekv_batch_step_info.argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, C.POINTER(Seq), i32, C.POINTER(C.c_int32), C.c_int32]
-    lib.ekv_batch_workspace_bytes.argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, C.POINTER(Seq), i32]
-    lib.ekv_batch_step_attend.argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, C.POINTER(Seq), i32, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
-    lib.ekv_kv8_batch_step_check.argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, C.POINTER(Kv8), C.POINTER(Seq), i32]
-    lib.ekv_kv8_batch_step_info.argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, C.POINTER(Kv8), C.POINTER(Seq), i32, C.POINTER(C.c_int32), C.c_int32]
-    lib.ekv_kv8_batch_workspace_bytes.argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, C.POINTER(Kv8), C.POINTER(Seq), i32]
-    lib.ekv_kv8_batch_step_attend.argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, C.POINTER(Kv8), C.POINTER(Seq), i32, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
-    lib.ekv_kv4_batch_step_check.argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, C.POINTER(Kv4), C.POINTER(Seq), i32]
-    lib.ekv_kv4_batch_step_info.argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, C.POINTER(Kv4), C.POINTER(Seq), i32, C.POINTER(C.c_int32), C.c_int32]
-    lib.ekv_kv4_batch_workspace_bytes.argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, C.POINTER(Kv4), C.POINTER(Seq), i32]
-    lib.ekv_kv4_batch_step_attend.argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, C.POINTER(Kv4), C.POINTER(Seq), i32, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
-    for name in EXPORTS[3:] + EXPORTS_KV8 + EXPORTS_KV4 + EXPORTS_KV4_BATCH:
-        getattr(lib, name).restype = C.c_int
-    lib.ekv_workspace_bytes_typed.restype = C.c_size_t
-    lib.ekv_kv8_workspace_bytes.restype = C.c_size_t
-    lib.ekv_kv4_workspace_bytes.restype = C.c_size_t
-    lib.ekv_batch_workspace_bytes.restype = C.c_size_t
-    lib.ekv_kv8_batch_workspace_bytes.restype = C.c_size_t
-    lib.ekv_kv4_batch_workspace_bytes.restype = C.c_size_t
+    # the step family: (bank, step, dtype[, descriptor][, table, entries]) + what the call itself takes
+    tails = {"step_check": [], "workspace_bytes": [], "step_info": [C.POINTER(C.c_int32), C.c_int32]}
+    for rows, desc in ((None, None), ("kv8", Kv8), ("kv4", Kv4)):
+        for batch in (False, True):
+            head = [C.POINTER(Bank), C.POINTER(Step), i32] + ([C.POINTER(desc)] if desc else []) + ([C.POINTER(Seq), i32] if batch else [])
+            tails["step_attend"] = [vp] * (6 if batch else 8) + [C.c_size_t, vp]      # (a batch has no rope tables)
+            for what in STEP_CALLS:
+                getattr(lib, step_call_name(rows, batch, what)).argtypes = head + tails[what]
+        if desc:
+            getattr(lib, f"ekv_{rows}_quantize").argtypes = [C.POINTER(Bank), C.POINTER(desc), i32, i32, i32, i32, vp]
+            getattr(lib, f"ekv_{rows}_dequantize").argtypes = [C.POINTER(Bank), C.POINTER(desc), i32, i32, i32, i32, vp, vp, vp]
+    for name in EXPORTS:
+        if name != "ekv_strerror":
+            getattr(lib, name).restype = C.c_size_t if "workspace_bytes" in name else C.c_int
     if lib.ekv_abi_version() != 8:
         raise EkvError("ABI version mismatch")
     _lib = lib

@@ -40,7 +40,7 @@ from typing import List, Optional
 import torch
 
 from . import _lib
-from .engine import KVBank, KVBankBatch, StepPlan
+from .engine import KVBank, KVBankBatch, StepPlan, row_format
 
 KNOWN_POLICIES = ("roco", "h2o_head", "tova", "recency", "random", "full")
 SCORED = ("roco", "h2o_head", "tova")
@@ -370,16 +370,15 @@ class _Run:
         if self.kv_dtype is torch.bfloat16 and streaming:
             raise ValueError("generation_config['kv_dtype'] = bfloat16 with streaming=True: RoPE-on-read has no bf16 build (use float16)")
         # extension key: storage of the K/V rows during the decode phase — None (the 16-bit rows of kv_dtype) or "fp8": the prefill runs on
-        # the 16-bit bank as always and the bank is quantised once at the prefill -> decode boundary (KVBank.quantize_fp8: OCP e4m3fn codes
-        # + one fp32 scale per row, 2 * head_dim + 8 bytes per row pair), or "mxfp4" (KVBank.quantize_mxfp4: e2m1 codes + one E8M0 exponent
-        # per 32 elements, 136 bytes per row pair; head_dim 128, GQA factors up to 4, no batched form).  kv_dtype keeps meaning the 16-bit
+        # the 16-bit bank as always and the bank is quantised once at the prefill -> decode boundary (KVBank.quantize(kv_quant): OCP e4m3fn
+        # codes + one fp32 scale per row, 2 * head_dim + 8 bytes per row pair), or "mxfp4" (e2m1 codes + one E8M0 exponent per 32 elements,
+        # 136 bytes per row pair; no batched form).  The shapes each takes are engine.ROW_FORMATS'.  kv_dtype keeps meaning the 16-bit
         # type of q / k / v / out.
         self.kv_quant = kv_quant = cfg.get("kv_quant", None)
         shard = getattr(model, "layer_shard", None)
         if shard is not None and shard.world == 1:
             shard = None
-        if kv_quant not in (None, "fp8", "mxfp4"):
-            raise ValueError(f"generation_config['kv_quant'] must be None or 'fp8' / 'mxfp4', not {kv_quant!r}")
+        fmt = row_format(kv_quant, "generation_config['kv_quant']")
         if kv_quant is not None:
             if streaming:
                 raise ValueError(f"generation_config['kv_quant'] = {kv_quant!r} with streaming=True: the quantised decode kernels have no RoPE-on-read build")
@@ -388,12 +387,10 @@ class _Run:
             if shard is not None:
                 raise ValueError(f"generation_config['kv_quant'] = {kv_quant!r} is not supported on a layer-sharded model (model.layer_shard)")
         self.dims = n_layers, hq, hkv, d = _dims(model)
-        if kv_quant == "fp8" and d not in (64, 128):
-            raise ValueError(f"generation_config['kv_quant'] = 'fp8' needs head_dim 64 or 128 (this model: {d})")
-        if kv_quant == "mxfp4" and d != 128:
-            raise ValueError(f"generation_config['kv_quant'] = 'mxfp4' needs head_dim 128 (this model: {d})")
-        if kv_quant == "mxfp4" and hq // hkv > 4:
-            raise ValueError(f"generation_config['kv_quant'] = 'mxfp4' needs a GQA factor of at most 4 (this model: {hq // hkv})")
+        if fmt is not None and d not in fmt["head_dims"]:
+            raise ValueError(f"generation_config['kv_quant'] = {kv_quant!r} needs head_dim {' or '.join(map(str, fmt['head_dims']))} (this model: {d})")
+        if fmt is not None and fmt["max_rep"] is not None and hq // hkv > fmt["max_rep"]:
+            raise ValueError(f"generation_config['kv_quant'] = {kv_quant!r} needs a GQA factor of at most {fmt['max_rep']} (this model: {hq // hkv})")
         self.dev = torch.device(model.device)
         for p in prompts:
             if p.dim() != 2 or p.shape[0] != 1:
@@ -778,10 +775,8 @@ def generate(self, input_ids, generation_config, kv_mode="encoding", stride=1, r
     else:
         pre = _prefill(run, input_ids, kv_mode)
         cache = pre.cache
-        if run.kv_quant == "mxfp4":      # prefill -> decode boundary: the decode steps run on quantised rows
-            cache.bank.quantize_mxfp4()
-        elif run.kv_quant:
-            cache.bank.quantize_fp8()
+        if run.kv_quant:      # prefill -> decode boundary: the decode steps run on quantised rows
+            cache.bank.quantize(run.kv_quant)
         out_ids, fed = _decode(run, pre, report_decoding_latency and pre.mode == "encoding")
         if pre.mode != "encoding":      # (encoding mode reports the cache the prefill left: printed there)
             _print_budget_line(pre.mode, pre.length, cache.get_seq_length(), len(out_ids), fed, pre.planner.budget_d if run.evicting else None)
@@ -830,7 +825,7 @@ def generate_batch(self, input_ids_list, generation_config, kv_mode="encoding", 
     for p in prompts:
         seqs.append(_prefill(run, p, kv_mode))
         if run.kv_quant:
-            seqs[-1].cache.bank.quantize_fp8()
+            seqs[-1].cache.bank.quantize(run.kv_quant)
     first = seqs[0].cache.bank
     rows = dict(kv_quant=run.kv_quant) if run.kv_quant else {}      # (FP8 planes only: the 16-bit rows of the batch are never allocated)
     bat = KVBankBatch(len(seqs), first.n_layers, first.n_q_heads, first.n_kv_heads, first.head_dim, max(s.cache.bank.cap for s in seqs),

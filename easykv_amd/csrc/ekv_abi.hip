@@ -75,9 +75,10 @@ static int call_attend(const EkvCall& c, const void* q, const void* k_new, const
   sa.tova_row = f32(P.tova_row);
   sa.colsum = aa.colsum;
   sa.row_stats = aa.row_stats;
-  // FP8 rows: the scale planes (they share the storage of stats / colsum, which a decode step — all a kv8 plan can be — never has)
-  if (c.kv8) aa.k_scale = c.q8->k_scale, aa.v_scale = c.q8->v_scale;
-  if (c.kv4) aa.k_exp = c.q4->k_exp, aa.v_exp = c.q4->v_exp;      // MXFP4 rows: the exponent planes, in the same storage
+  // quantised rows: the row scales / block exponents (they share the storage of stats / colsum, which a decode step — all a quantised
+  // plan can be — never has)
+  if (c.rows == EKV_ROWS_kv8) aa.k_scale = static_cast<float*>(c.planes.k_aux), aa.v_scale = static_cast<float*>(c.planes.v_aux);
+  if (c.rows == EKV_ROWS_kv4) aa.k_exp = static_cast<uint8_t*>(c.planes.k_aux), aa.v_exp = static_cast<uint8_t*>(c.planes.v_aux);
   sa.out = static_cast<__half*>(out);
   sa.evict_ids = evict_ids;
   sa.big_rows = f32(P.big_rows);
@@ -88,22 +89,23 @@ static int call_attend(const EkvCall& c, const void* q, const void* k_new, const
     sa.slot_tail_ok = P.slot_tail_ok;
   }
 
-  const bool bf16 = P.bf16 != 0, kv8 = P.kv8 != 0, kv4 = P.kv4 != 0;
+  const bool bf16 = P.bf16 != 0;
+  const EkvRows rows = static_cast<EkvRows>(P.rows);
   drop_stale_error();
   for (int i = 0; i < P.n_list; ++i) {
     const EkvLaunch& L = P.list[i];
     sa.skip_fold = L.skip_fold;
     hipError_t e = hipSuccess;
-    // (a kv8 plan is a decode plan: the decode attention launches and the scorers behind them, which read no K/V element)
-    if ((kv8 || kv4) && (L.kind == EKV_RUN_CHUNK_LDS || L.kind == EKV_RUN_RESIDENT || L.kind == EKV_RUN_CHUNK || L.kind == EKV_RUN_FLUSH)) return EKV_E_UNSUPPORTED;
+    // (a quantised plan is a decode plan: the decode attention launches and the scorers behind them, which read no K/V element)
+    if (rows != EKV_ROWS_kv16 && (L.kind == EKV_RUN_CHUNK_LDS || L.kind == EKV_RUN_RESIDENT || L.kind == EKV_RUN_CHUNK || L.kind == EKV_RUN_FLUSH)) return EKV_E_UNSUPPORTED;
     switch (L.kind) {
       case EKV_RUN_FUSED_DECODE:
         aa.fused_order = P.fused_order;      // (shares its storage with score_tail, which only chunk launches set)
-        e = ekv_launch_decode_fused(aa, sa, tb, D, lc, P.fused_nw, s, bf16, kv8, kv4);
+        e = ekv_launch_decode_fused(aa, sa, tb, D, lc, P.fused_nw, s, bf16, rows);
         break;
       case EKV_RUN_CHUNK_LDS: e = ekv_launch_chunk_lds(aa, sa, D, lc, s, bf16); break;
       case EKV_RUN_RESIDENT: e = ekv_launch_attn_resident(aa, sa, lc, s, bf16); break;
-      case EKV_RUN_DECODE: e = ekv_launch_attn_decode(aa, tb, D, lc, s, bf16, kv8, kv4); break;
+      case EKV_RUN_DECODE: e = ekv_launch_attn_decode(aa, tb, D, lc, s, bf16, rows); break;
       case EKV_RUN_CHUNK:
         e = ekv_launch_attn_chunk(aa, D, lc, P.wide, P.two_pass, s, L.fuse ? &sa : nullptr, L.passes, L.tail ? &sa : nullptr, bf16);
         break;
@@ -211,35 +213,6 @@ int ekv_kv8_batch_step_attend(const ekv_bank* bank, const ekv_step* st, int32_t 
   return call_attend(kv8_batch_call(bank, st, dtype, q8, seqs, n_seq), q, k_new, v_new, out, evict_ids, nullptr, nullptr, workspace, workspace_bytes, stream);
 }
 
-static int kv8_convert_check(const ekv_bank* bank, const ekv_kv8* q8, int32_t layer_begin, int32_t layer_count, int32_t extent) {
-  if (!bank || !q8 || !q8->k_codes || !q8->v_codes || !q8->k_scale || !q8->v_scale) return EKV_E_ARG;
-  if (bank->n_layers <= 0 || bank->n_kv_heads <= 0 || bank->cap <= 0) return EKV_E_ARG;
-  if (int e = check_layers(bank, layer_begin, layer_count)) return e;
-  if (extent < 0 || extent > bank->cap) return EKV_E_ARG;
-  if (bank->head_dim != 64 && bank->head_dim != 128) return EKV_E_UNSUPPORTED;
-  return EKV_OK;
-}
-
-int ekv_kv8_quantize(const ekv_bank* bank, const ekv_kv8* q8, int32_t dtype, int32_t layer_begin, int32_t layer_count, int32_t extent,
-                     void* stream) {
-  if (dtype != EKV_DTYPE_F16 && dtype != EKV_DTYPE_BF16) return EKV_E_ARG;
-  if (int e = kv8_convert_check(bank, q8, layer_begin, layer_count, extent)) return e;
-  if (!bank->k || !bank->v) return EKV_E_ARG;
-  drop_stale_error();
-  return ekv_launch_kv8_quantize(bank, q8, dtype == EKV_DTYPE_BF16, layer_begin, layer_count, extent, static_cast<hipStream_t>(stream)) == hipSuccess
-             ? EKV_OK : EKV_E_LAUNCH;
-}
-
-int ekv_kv8_dequantize(const ekv_bank* bank, const ekv_kv8* q8, int32_t out_dtype, int32_t layer_begin, int32_t layer_count,
-                       int32_t extent, void* k_out, void* v_out, void* stream) {
-  if (out_dtype != EKV_DTYPE_F16 && out_dtype != EKV_DTYPE_BF16 && out_dtype != EKV_DTYPE_F32) return EKV_E_ARG;
-  if (int e = kv8_convert_check(bank, q8, layer_begin, layer_count, extent)) return e;
-  if (!k_out || !v_out) return EKV_E_ARG;
-  drop_stale_error();
-  return ekv_launch_kv8_dequantize(bank, q8, out_dtype, layer_begin, layer_count, extent, k_out, v_out, static_cast<hipStream_t>(stream)) == hipSuccess
-             ? EKV_OK : EKV_E_LAUNCH;
-}
-
 // MXFP4 K/V storage (include/easykv_hip.h, "kv4")
 int ekv_kv4_step_check(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_kv4* q4) { return call_check(kv4_call(bank, st, dtype, q4)); }
 int ekv_kv4_step_info(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_kv4* q4, int32_t* info, int32_t n_info) {
@@ -271,29 +244,51 @@ int ekv_kv4_batch_step_attend(const ekv_bank* bank, const ekv_step* st, int32_t 
   return call_attend(kv4_batch_call(bank, st, dtype, q4, seqs, n_seq), q, k_new, v_new, out, evict_ids, nullptr, nullptr, workspace, workspace_bytes, stream);
 }
 
-static int kv4_convert_check(const ekv_bank* bank, const ekv_kv4* q4, int32_t layer_begin, int32_t layer_count, int32_t extent) {
-  if (!bank || !q4 || !q4->k_codes || !q4->v_codes || !q4->k_exp || !q4->v_exp) return EKV_E_ARG;
+// ---- bank conversions (ekv_kv8.hip, ekv_kv4.hip): one argument check for both row formats
+static int convert_check(const ekv_bank* bank, EkvRows rows, const EkvPlanes& planes, int32_t layer_begin, int32_t layer_count, int32_t extent) {
+  if (!bank || !ekv_planes_complete(planes)) return EKV_E_ARG;
   if (bank->n_layers <= 0 || bank->n_kv_heads <= 0 || bank->cap <= 0) return EKV_E_ARG;
   if (int e = check_layers(bank, layer_begin, layer_count)) return e;
   if (extent < 0 || extent > bank->cap) return EKV_E_ARG;
-  if (bank->head_dim != 128) return EKV_E_UNSUPPORTED;
-  return EKV_OK;
+  return ekv_rows_head_dim(rows, bank->head_dim) ? EKV_OK : EKV_E_UNSUPPORTED;
+}
+static int quantize_check(const ekv_bank* bank, EkvRows rows, const EkvPlanes& planes, int32_t dtype, int32_t layer_begin, int32_t layer_count,
+                          int32_t extent) {
+  if (dtype != EKV_DTYPE_F16 && dtype != EKV_DTYPE_BF16) return EKV_E_ARG;
+  if (int e = convert_check(bank, rows, planes, layer_begin, layer_count, extent)) return e;
+  return bank->k && bank->v ? EKV_OK : EKV_E_ARG;
+}
+static int dequantize_check(const ekv_bank* bank, EkvRows rows, const EkvPlanes& planes, int32_t out_dtype, int32_t layer_begin,
+                            int32_t layer_count, int32_t extent, const void* k_out, const void* v_out) {
+  if (out_dtype != EKV_DTYPE_F16 && out_dtype != EKV_DTYPE_BF16 && out_dtype != EKV_DTYPE_F32) return EKV_E_ARG;
+  if (int e = convert_check(bank, rows, planes, layer_begin, layer_count, extent)) return e;
+  return k_out && v_out ? EKV_OK : EKV_E_ARG;
+}
+
+int ekv_kv8_quantize(const ekv_bank* bank, const ekv_kv8* q8, int32_t dtype, int32_t layer_begin, int32_t layer_count, int32_t extent,
+                     void* stream) {
+  if (int e = quantize_check(bank, EKV_ROWS_kv8, ekv_planes(q8), dtype, layer_begin, layer_count, extent)) return e;
+  drop_stale_error();
+  return launch_code(ekv_launch_kv8_quantize(bank, q8, dtype == EKV_DTYPE_BF16, layer_begin, layer_count, extent, static_cast<hipStream_t>(stream)));
+}
+
+int ekv_kv8_dequantize(const ekv_bank* bank, const ekv_kv8* q8, int32_t out_dtype, int32_t layer_begin, int32_t layer_count,
+                       int32_t extent, void* k_out, void* v_out, void* stream) {
+  if (int e = dequantize_check(bank, EKV_ROWS_kv8, ekv_planes(q8), out_dtype, layer_begin, layer_count, extent, k_out, v_out)) return e;
+  drop_stale_error();
+  return launch_code(ekv_launch_kv8_dequantize(bank, q8, out_dtype, layer_begin, layer_count, extent, k_out, v_out, static_cast<hipStream_t>(stream)));
 }
 
 int ekv_kv4_quantize(const ekv_bank* bank, const ekv_kv4* q4, int32_t dtype, int32_t layer_begin, int32_t layer_count, int32_t extent,
                      void* stream) {
-  if (dtype != EKV_DTYPE_F16 && dtype != EKV_DTYPE_BF16) return EKV_E_ARG;
-  if (int e = kv4_convert_check(bank, q4, layer_begin, layer_count, extent)) return e;
-  if (!bank->k || !bank->v) return EKV_E_ARG;
+  if (int e = quantize_check(bank, EKV_ROWS_kv4, ekv_planes(q4), dtype, layer_begin, layer_count, extent)) return e;
   drop_stale_error();
   return launch_code(ekv_launch_kv4_quantize(bank, q4, dtype == EKV_DTYPE_BF16, layer_begin, layer_count, extent, static_cast<hipStream_t>(stream)));
 }
 
 int ekv_kv4_dequantize(const ekv_bank* bank, const ekv_kv4* q4, int32_t out_dtype, int32_t layer_begin, int32_t layer_count,
                        int32_t extent, void* k_out, void* v_out, void* stream) {
-  if (out_dtype != EKV_DTYPE_F16 && out_dtype != EKV_DTYPE_BF16 && out_dtype != EKV_DTYPE_F32) return EKV_E_ARG;
-  if (int e = kv4_convert_check(bank, q4, layer_begin, layer_count, extent)) return e;
-  if (!k_out || !v_out) return EKV_E_ARG;
+  if (int e = dequantize_check(bank, EKV_ROWS_kv4, ekv_planes(q4), out_dtype, layer_begin, layer_count, extent, k_out, v_out)) return e;
   drop_stale_error();
   return launch_code(ekv_launch_kv4_dequantize(bank, q4, out_dtype, layer_begin, layer_count, extent, k_out, v_out, static_cast<hipStream_t>(stream)));
 }

@@ -31,7 +31,7 @@
 #ifndef EKV_BATCH
 #define EKV_BATCH 0
 #endif
-// EKV_KV4 = 1 (the kv4 instances, EKV_DECODE_KV4 lines): the bank's rows are MXFP4 codes + E8M0 block exponents (ekv_decode_stream.h,
+// EKV_KV4 = 1 (the kv4 instances, the manifest's kv4 lines): the bank's rows are MXFP4 codes + E8M0 block exponents (ekv_decode_stream.h,
 // "MXFP4 rows"); head_dim 128, plain keys, GQA factors up to 4 (a lane's output slice is 32 floats per query head: no REP = 8 build).
 #ifndef EKV_KV4
 #define EKV_KV4 0

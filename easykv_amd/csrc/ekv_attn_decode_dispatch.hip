@@ -10,12 +10,6 @@ typedef hipError_t EkvFoldFn(const EkvScoreArgs&, int layer_count, hipStream_t);
 #define EKV_DECODE(d, keys, elem, rows, batching)                            \
   EkvDecodeFn EKV_FN_DECODE(ekv_launch_attn_decode, d, keys, elem, rows, batching); \
   EkvFusedFn EKV_FN_DECODE(ekv_launch_decode_fused, d, keys, elem, rows, batching);
-#define EKV_DECODE_KV4(d, elem)                                            \
-  EkvDecodeFn EKV_FN_DECODE(ekv_launch_attn_decode, d, plain, elem, kv4, single); \
-  EkvFusedFn EKV_FN_DECODE(ekv_launch_decode_fused, d, plain, elem, kv4, single);
-#define EKV_DECODE_KV4_BATCH(d, elem)                                     \
-  EkvDecodeFn EKV_FN_DECODE(ekv_launch_attn_decode, d, plain, elem, kv4, batch); \
-  EkvFusedFn EKV_FN_DECODE(ekv_launch_decode_fused, d, plain, elem, kv4, batch);
 #define EKV_DECODE_SCORE(elem, batching) EkvScoreFn EKV_FN_DECODE_SCORE(ekv_launch_decode_score, elem, batching);
 #include "ekv_instances.def"
 EkvFoldFn ekv_launch_fold_f16, ekv_launch_fold_bf16;      // (exported by the `single` scorer instances: the fold reads no per-step field)
@@ -23,21 +17,16 @@ EkvFoldFn ekv_launch_fold_f16, ekv_launch_fold_bf16;      // (exported by the `s
 namespace {
 struct DecodeInstance {
   int head_dim;
-  bool rope, bf16, kv8, batch;
+  bool rope, bf16;
+  EkvRows rows;
+  bool batch;
   EkvDecodeFn* attn;
   EkvFusedFn* fused;
-  bool kv4;      // an EKV_DECODE_KV4 / EKV_DECODE_KV4_BATCH line (plain keys; `batch` says which)
 };
 const DecodeInstance kDecode[] = {
 #define EKV_DECODE(d, keys, elem, rows, batching)                                                                   \
-  {d, EKV_IS_##keys, EKV_IS_##elem, EKV_IS_##rows, EKV_IS_##batching, EKV_FN_DECODE(ekv_launch_attn_decode, d, keys, elem, rows, batching), \
-   EKV_FN_DECODE(ekv_launch_decode_fused, d, keys, elem, rows, batching), false},
-#define EKV_DECODE_KV4(d, elem)                                                                                     \
-  {d, false, EKV_IS_##elem, false, false, EKV_FN_DECODE(ekv_launch_attn_decode, d, plain, elem, kv4, single),      \
-   EKV_FN_DECODE(ekv_launch_decode_fused, d, plain, elem, kv4, single), true},
-#define EKV_DECODE_KV4_BATCH(d, elem)                                                                               \
-  {d, false, EKV_IS_##elem, false, true, EKV_FN_DECODE(ekv_launch_attn_decode, d, plain, elem, kv4, batch),        \
-   EKV_FN_DECODE(ekv_launch_decode_fused, d, plain, elem, kv4, batch), true},
+  {d, EKV_IS_##keys, EKV_IS_##elem, EKV_ROWS_##rows, EKV_IS_##batching, EKV_FN_DECODE(ekv_launch_attn_decode, d, keys, elem, rows, batching), \
+   EKV_FN_DECODE(ekv_launch_decode_fused, d, keys, elem, rows, batching)},
 #include "ekv_instances.def"
 };
 struct ScoreInstance {
@@ -50,33 +39,31 @@ const ScoreInstance kDecodeScore[] = {
 };
 
 // The instance of a decode launch, or nullptr (hipErrorInvalidValue) for a combination the manifest does not hold or the arguments do
-// not fit: kv8 needs plain keys and the scale planes, bf16 and batches have no RoPE-on-read build, a batch runs on the ordered layout
-// (the planner refuses all of these before a launch).  kv8 and batch are independent: a batched step on FP8 rows looks up its own
-// instance (head_dim 64 / 128, plain keys), which takes the table and the scale planes together.  kv4 is one more independent field:
-// plain keys, the exponent planes, GQA factors up to 4, never with kv8; with a table it finds the EKV_DECODE_KV4_BATCH instances, as a
-// kv8 batch finds its own — a combination without a line of the manifest finds nothing.
-const DecodeInstance* decode_instance(const EkvAttnArgs& a, const EkvSeqTable* tb, int head_dim, bool bf16, bool kv8, bool kv4, bool fused_slot_rows) {
+// not fit: quantised rows need plain keys and their auxiliary planes (kv8: the row scales; kv4: the block exponents, and a GQA factor of
+// at most 4), bf16 and batches have no RoPE-on-read build, a batch runs on the ordered layout (the planner refuses all of these before
+// a launch).  The row format and the batching are independent fields: a batched step on quantised rows looks up its own instance,
+// which takes the table and the planes together, and a combination without a line of the manifest finds nothing.
+const DecodeInstance* decode_instance(const EkvAttnArgs& a, const EkvSeqTable* tb, int head_dim, bool bf16, EkvRows rows, bool fused_slot_rows) {
   const bool rope = a.rope_cos != nullptr, batch = tb != nullptr;
-  if (kv8 && (rope || a.k_scale == nullptr || a.v_scale == nullptr)) return nullptr;
-  if (kv4 && (rope || a.k_exp == nullptr || a.v_exp == nullptr || a.n_q_heads > 4 * a.n_kv_heads)) return nullptr;
+  if (rows == EKV_ROWS_kv8 && (rope || a.k_scale == nullptr || a.v_scale == nullptr)) return nullptr;
+  if (rows == EKV_ROWS_kv4 && (rope || a.k_exp == nullptr || a.v_exp == nullptr || a.n_q_heads > 4 * a.n_kv_heads)) return nullptr;
   if (bf16 && rope) return nullptr;
   if (batch && (rope || fused_slot_rows)) return nullptr;
   for (const DecodeInstance& in : kDecode)
-    if (in.head_dim == head_dim && in.rope == rope && in.bf16 == bf16 && in.kv8 == kv8 && in.batch == batch && in.kv4 == kv4) return &in;
+    if (in.head_dim == head_dim && in.rope == rope && in.bf16 == bf16 && in.rows == rows && in.batch == batch) return &in;
   return nullptr;
 }
 }  // namespace
 
-hipError_t ekv_launch_attn_decode(const EkvAttnArgs& a, const EkvSeqTable* tb, int head_dim, int count, hipStream_t s, bool bf16, bool kv8,
-                                  bool kv4) {
-  const DecodeInstance* in = decode_instance(a, tb, head_dim, bf16, kv8, kv4, false);
+hipError_t ekv_launch_attn_decode(const EkvAttnArgs& a, const EkvSeqTable* tb, int head_dim, int count, hipStream_t s, bool bf16, EkvRows rows) {
+  const DecodeInstance* in = decode_instance(a, tb, head_dim, bf16, rows, false);
   return in ? in->attn(a, tb, a.n_q_heads / a.n_kv_heads, count, s) : hipErrorInvalidValue;
 }
 
 // The whole decode step in one launch (which steps, how many waves, which phase order: ekv_plan.cpp)
 hipError_t ekv_launch_decode_fused(const EkvAttnArgs& a, const EkvScoreArgs& sc, const EkvSeqTable* tb, int head_dim, int count, int nw,
-                                   hipStream_t s, bool bf16, bool kv8, bool kv4) {
-  const DecodeInstance* in = decode_instance(a, tb, head_dim, bf16, kv8, kv4, sc.birth != nullptr);
+                                   hipStream_t s, bool bf16, EkvRows rows) {
+  const DecodeInstance* in = decode_instance(a, tb, head_dim, bf16, rows, sc.birth != nullptr);
   return in ? in->fused(a, sc, tb, a.n_q_heads / a.n_kv_heads, count, nw, s) : hipErrorInvalidValue;
 }
 

@@ -7,6 +7,10 @@
 #include "../../include/easykv_hip.h"
 #include "ekv_geometry.h"
 
+// The row format of a bank's K/V rows: the `rows` word of a manifest line (ekv_instances.def), and what a call of the step family says
+// about its bank.  kv16: 16-bit rows.  kv8: FP8 codes + fp32 row scales (ekv_kv8).  kv4: MXFP4 codes + E8M0 block exponents (ekv_kv4).
+enum EkvRows : int32_t { EKV_ROWS_kv16, EKV_ROWS_kv8, EKV_ROWS_kv4 };
+
 // One kernel launch sequence entry of a step (EkvStepPlan::list), in issue order.
 enum EkvLaunchKind : int32_t {
   EKV_RUN_FUSED_DECODE,   // ekv_launch_decode_fused: the whole decode step
@@ -41,8 +45,7 @@ struct EkvStepPlan {
   int32_t flush_unsplit;    // deferred flush: the column-sum pass runs unsplit over the one pass's key-range statistics
   int32_t slot_rows, slot_tail_ok;   // fused decode step on the slot-indexed score rows (EKV_PHASE_SLOT_ROWS / _TAIL_OK)
   int32_t bf16;             // 16-bit tensors are bf16: the launches run the EKV_BF16 kernel instances
-  int32_t kv8;              // the bank's K/V rows are FP8 codes + row scales (an ekv_kv8 call): the decode launches run the kv8 instances
-  int32_t kv4;              // the bank's K/V rows are MXFP4 codes + block exponents (an ekv_kv4 call): the decode launches run the kv4 instances
+  int32_t rows;             // EkvRows of the bank's K/V rows: the decode launches run the instances of that row format
   int32_t batch;            // a batched decode step (an ekv_seq call): the plan of the envelope; the launches run the batch instances
   int32_t strides[6];       // q, kv, out row strides (token, head) in elements, the dense layout filled in
   // Workspace: byte offsets of this call's slices (a deferred call's layout spans every deferred layer), -1 = not in the layout
@@ -161,9 +164,8 @@ struct EkvScoreArgs {
 // tb (the decode launchers): NULL = a uniform step of `count` layers; the table of a batched decode step = the batch instances (16-bit
 // or FP8 rows, plain keys, ordered score rows): `a` / `sc` are the envelope's arguments with layer_begin = 0 and a.arrive = the bank's
 // counters, and `count` is the number of table entries, one workgroup row each.
-// kv4: the MXFP4 instances (EKV_DECODE_KV4 lines of the manifest, EKV_DECODE_KV4_BATCH lines with a table; never together with kv8)
-hipError_t ekv_launch_attn_decode(const EkvAttnArgs& a, const EkvSeqTable* tb, int head_dim, int count, hipStream_t s, bool bf16, bool kv8,
-                                  bool kv4 = false);
+// rows: the instances of that row format (kv8: a.k_scale / a.v_scale set, kv4: a.k_exp / a.v_exp; plain keys either way)
+hipError_t ekv_launch_attn_decode(const EkvAttnArgs& a, const EkvSeqTable* tb, int head_dim, int count, hipStream_t s, bool bf16, EkvRows rows);
 // passes (wide-block kernel, two-pass scheme): bit 0 = the one pass (output + row statistics), bit 1 = the column-sum pass
 // tail_sc (wide-block kernel, two passes, passes & 2): the step's scorer runs as the tail of the column-sum pass (ekv_wide_tail.h)
 // wide: the wide-block kernel (ekv_chunk_wide, ekv_plan.h)
@@ -173,7 +175,7 @@ hipError_t ekv_launch_attn_resident(const EkvAttnArgs& a, const EkvScoreArgs& sc
 hipError_t ekv_launch_tova_headmean(const EkvScoreArgs& a, int layer_count, hipStream_t s);
 hipError_t ekv_launch_score_select(const EkvScoreArgs& a, int layer_count, hipStream_t s, bool bf16);
 hipError_t ekv_launch_decode_fused(const EkvAttnArgs& a, const EkvScoreArgs& sc, const EkvSeqTable* tb, int head_dim, int count, int nw,
-                                   hipStream_t s, bool bf16, bool kv8, bool kv4 = false);
+                                   hipStream_t s, bool bf16, EkvRows rows);
 // What workgroup (head, entry z) of a batch instance does first: its argument structs are the envelope's with the per-step fields
 // replaced by its entry's (scalar loads from the kernel arguments).  layer_begin = layer - z: every `layer_begin + ll` of the kernel
 // body then names the entry's bank layer, while the workspace and the call's tensors stay indexed by ll = z.
@@ -259,13 +261,11 @@ __device__ __forceinline__ EkvScoreArgs ekv_batch_score_args(const EkvScoreArgs&
 #define EKV_FN_D_ELEM(fn, d, elem) EKV_FN_D_ELEM_(fn, d, elem)      // (EKV_CHUNK_LDS, EKV_RESIDENT)
 #define EKV_FN_SCORE_SELECT_(nt, elem) ekv_launch_score_select_nt##nt##_##elem
 #define EKV_FN_SCORE_SELECT(nt, elem) EKV_FN_SCORE_SELECT_(nt, elem)
-// the manifest's words as the booleans of a table entry
+// the manifest's words as the fields of a table entry: booleans, and EKV_ROWS_<rows> above
 #define EKV_IS_plain false
 #define EKV_IS_rope true
 #define EKV_IS_f16 false
 #define EKV_IS_bf16 true
-#define EKV_IS_kv16 false
-#define EKV_IS_kv8 true
 #define EKV_IS_single false
 #define EKV_IS_batch true
 // FP8 bank conversion (ekv_kv8.hip).  src_bf16: the 16-bit rows are bf16; out_kind: 0 fp16, 1 bf16, 2 fp32

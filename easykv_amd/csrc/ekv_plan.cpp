@@ -619,46 +619,50 @@ int ekv_plan_step(const ekv_bank* bank, const ekv_step* step, EkvStepPlan* P) {
 }
 
 // ---- one call ----------------------------------------------------------------------------------------------------------------------
-// The return code of the call, in the order the call reports its errors.  Stages: element type -> the bank a kv8 call runs on ->
-// envelope and table of a batch -> the plan of the (16-bit, uniform) step -> what the variant does not take.
+// What each row format takes, beyond decode steps (q_len == 1) on plain keys — all a quantised bank serves: its head_dims (0: none) and
+// the largest GQA factor.  kv8: head_dim 64 / 128.  kv4: head_dim 128 (a lane's 16-byte piece = one 32-element block), GQA factors up
+// to 4 (32 output floats per lane and head).  resolve_call refuses by it, and the bank conversions (ekv_abi.hip) ask for the head_dim.
+namespace {
+struct RowsRule {
+  int32_t head_dims[2], max_rep;
+};
+const RowsRule kRowsRules[] = {/* kv16 */ {{0, 0}, 1 << 30}, /* kv8 */ {{64, 128}, 1 << 30}, /* kv4 */ {{128, 0}, 4}};
+}  // namespace
+bool ekv_rows_head_dim(EkvRows rows, int head_dim) {
+  const RowsRule& rule = kRowsRules[rows];
+  return head_dim > 0 && (head_dim == rule.head_dims[0] || head_dim == rule.head_dims[1]);
+}
+
+// The return code of the call, in the order the call reports its errors.  Stages: element type -> the bank a quantised call runs on ->
+// envelope and table of a batch -> the plan of the (16-bit, uniform) step -> what the row format and the batching do not take.
 //
 // The element type only picks the kernel instances: a bf16 step is planned as the fp16 step.  RoPE-on-read keeps hi / lo fp16 planes
 // of the rotated keys and queries (ekv_attn_wide.inc, ekv_rope_q_kernel) and has no bf16 build.
-// FP8 rows: the code planes stand where the 16-bit rows were (bank->k / bank->v are not read), and the plan is that of the 16-bit step
-// of the same shape (the scorers read logits and partials, never a K/V element, so splits, launches and workspace carry over), run on
-// the kv8 instances of the two decode attention kernels — which is all a kv8 bank has: decode steps, plain keys, head_dim 64 / 128.
-// MXFP4 rows (an ekv_kv4_* call): the same stage with the kv4 planes and instances — decode steps, plain keys, head_dim 128, GQA <= 4.
+// Quantised rows (kv8, kv4): the code planes stand where the 16-bit rows were (bank->k / bank->v are not read; a missing plane is an
+// argument error before anything else of the call is read), and the plan is that of the 16-bit step of the same shape (the scorers
+// read logits and partials, never a K/V element, so splits, launches and workspace carry over), run on that format's instances of the
+// two decode attention kernels — which is all a quantised bank has: decode steps, plain keys, and the shapes of kRowsRules.
 // A batched decode step (include/easykv_hip.h, ekv_seq): the plan of the uniform step of the batch's ENVELOPE — the longest entry, the
 // widest extent, one "layer" per entry: same splits, launches and workspace pitches, so a uniform table plans field for field as the
 // multi-layer step it spells out.  The entries keep their own bounds inside those pitches (the kernels' batch instances read them
 // from the table, whose entries have phys_extent resolved as ekv_plan_step resolves a step's).
-// Both at once (an ekv_kv8_batch_* call): the stages apply independently — a missing plane is an argument error before the table is
-// read, the table is checked against the bank the code planes stand in, and the refusals of either variant hold unchanged (head_dim
-// 32 / 96 in a table: EKV_E_UNSUPPORTED with zero launches and zero bytes).  The plan is the 16-bit batched call's of the same table.
-// An ekv_kv4_batch_* call is the same pair of stages with the kv4 planes: head_dim != 128 or a GQA factor > 4 in a table is refused as
-// the kv4 step refuses it.  kv4 with kv8 is an argument error.
+// The two axes apply independently: the table of a quantised batch is checked against the bank the code planes stand in, and the
+// refusals of either axis hold unchanged (a head_dim the row format does not take, in a table: EKV_E_UNSUPPORTED with zero launches
+// and zero bytes).  The plan is the 16-bit batched call's of the same table.
 int resolve_call(const EkvCall& c, EkvResolved* r) {
   EkvStepPlan* P = &r->plan;
   *P = EkvStepPlan{};
-  r->bank = (c.kv8 || c.kv4) ? nullptr : c.bank;
+  const bool quant = c.rows != EKV_ROWS_kv16;
+  r->bank = quant ? nullptr : c.bank;
   r->step = c.step;
   r->tb = nullptr;
   if (c.dtype != EKV_DTYPE_F16 && c.dtype != EKV_DTYPE_BF16) return EKV_E_ARG;
-  if (c.kv8) {
-    const ekv_kv8* q8 = c.q8;
-    if (!c.bank || !q8 || !q8->k_codes || !q8->v_codes || !q8->k_scale || !q8->v_scale) return EKV_E_ARG;
-    r->bank8 = *c.bank;
-    r->bank8.k = q8->k_codes;
-    r->bank8.v = q8->v_codes;
-    r->bank = &r->bank8;
-  }
-  if (c.kv4) {      // MXFP4 rows: one more variant stage, as the FP8 one (the code planes stand where the 16-bit rows were)
-    const ekv_kv4* q4 = c.q4;
-    if (c.kv8 || !c.bank || !q4 || !q4->k_codes || !q4->v_codes || !q4->k_exp || !q4->v_exp) return EKV_E_ARG;
-    r->bank8 = *c.bank;
-    r->bank8.k = q4->k_codes;
-    r->bank8.v = q4->v_codes;
-    r->bank = &r->bank8;
+  if (quant) {
+    if (!c.bank || !ekv_planes_complete(c.planes)) return EKV_E_ARG;
+    r->bank_q = *c.bank;
+    r->bank_q.k = c.planes.k_codes;
+    r->bank_q.v = c.planes.v_codes;
+    r->bank = &r->bank_q;
   }
   const ekv_bank* bank = r->bank;
   if (c.batch) {
@@ -696,10 +700,9 @@ int resolve_call(const EkvCall& c, EkvResolved* r) {
 
   const int rc = ekv_plan_step(bank, r->step, P);
   P->bf16 = c.dtype == EKV_DTYPE_BF16;
-  P->kv8 = c.kv8;
-  P->kv4 = c.kv4;
+  P->rows = c.rows;
   P->batch = c.batch;
-  if (c.kv8 || c.kv4 || c.batch) P->fused_order = 0;      // (the kv8, kv4 and batch instances keep order F)
+  if (quant || c.batch) P->fused_order = 0;      // (the quantised and the batch instances keep order F)
   auto refuse = [&](int code) {
     P->one_launch = P->n_launches = P->n_list = 0;
     if (c.batch) P->bytes = 0;      // (nothing will run: ekv_batch_workspace_bytes of a refused table is 0)
@@ -713,9 +716,9 @@ int resolve_call(const EkvCall& c, EkvResolved* r) {
   }
   if (rc == EKV_OK && P->bf16 && st->rope_on_read) return refuse(EKV_E_UNSUPPORTED);
   if (rc != EKV_OK) return refuse(rc);
-  if (c.kv8 && (st->q_len != 1 || st->rope_on_read || (bank->head_dim != 64 && bank->head_dim != 128))) return refuse(EKV_E_UNSUPPORTED);
-  // MXFP4 rows: head_dim 128 (a lane's 16-byte piece = one 32-element block), GQA factors up to 4 (32 output floats per lane and head)
-  if (c.kv4 && (st->q_len != 1 || st->rope_on_read || bank->head_dim != 128 || bank->n_q_heads / bank->n_kv_heads > 4)) return refuse(EKV_E_UNSUPPORTED);
+  if (quant && (st->q_len != 1 || st->rope_on_read || !ekv_rows_head_dim(c.rows, bank->head_dim) ||
+                bank->n_q_heads / bank->n_kv_heads > kRowsRules[c.rows].max_rep))
+    return refuse(EKV_E_UNSUPPORTED);
   if (c.batch) {
     for (int i = 0; i < c.n_seq; ++i) {      // per entry: the checks of the single-sequence step of that entry's geometry
       const ekv_seq& e = c.seqs[i];
@@ -752,7 +755,7 @@ int call_info(const EkvCall& c, int32_t* info, int32_t n_info) {
   EkvResolved r;
   const bool ok = resolve_call(c, &r) == EKV_OK;
   if (c.dtype != EKV_DTYPE_F16 && c.dtype != EKV_DTYPE_BF16) return EKV_E_ARG;
-  if ((c.kv8 || c.kv4) && !r.bank) return EKV_E_ARG;
+  if (c.rows != EKV_ROWS_kv16 && !r.bank) return EKV_E_ARG;
   if (int e = check_bank(r.bank)) return e;
   if (!c.step || (c.batch && !c.seqs) || !info || n_info < 1) return EKV_E_ARG;
   const EkvStepPlan& P = r.plan;

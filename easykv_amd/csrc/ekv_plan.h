@@ -35,45 +35,53 @@ EkvScoreArgs score_args(const ekv_bank* bank, const ekv_step* st, const EkvStepP
 int ekv_plan_step(const ekv_bank* bank, const ekv_step* step, EkvStepPlan* P);
 
 // ---- one call path --------------------------------------------------------------------------------------------------------------
-// A call of the step family as its entry points spell it: the untyped / _typed functions (a bank, a step, an element type), ekv_kv8_*
-// (+ the FP8 planes), ekv_kv4_* (+ the MXFP4 planes) and ekv_batch_* (+ the table of a batched decode step).  The axes are independent here; which combinations run
-// is the planner's business (resolve_call) and the manifest's (ekv_instances.def).
+// A call of the step family as its entry points spell it, along two independent axes: the row format of the bank (the untyped / _typed
+// functions: kv16; ekv_kv8_*: kv8; ekv_kv4_*: kv4 — a quantised call brings the four planes of its descriptor) and the batching
+// (ekv_*batch_*: the table of a batched decode step).  Which combinations run is the planner's business (resolve_call, over
+// kRowsRules) and the manifest's (ekv_instances.def).
+struct EkvPlanes {      // what stands for the K/V rows of a quantised bank: the code planes, and the row scales (kv8) / block exponents (kv4)
+  void *k_codes, *v_codes, *k_aux, *v_aux;
+};
+inline EkvPlanes ekv_planes(const ekv_kv8* q) { return q ? EkvPlanes{q->k_codes, q->v_codes, q->k_scale, q->v_scale} : EkvPlanes{}; }
+inline EkvPlanes ekv_planes(const ekv_kv4* q) { return q ? EkvPlanes{q->k_codes, q->v_codes, q->k_exp, q->v_exp} : EkvPlanes{}; }
+inline bool ekv_planes_complete(const EkvPlanes& p) { return p.k_codes && p.v_codes && p.k_aux && p.v_aux; }
 struct EkvCall {
   const ekv_bank* bank;
   const ekv_step* step;
   int32_t dtype;
-  bool kv8;                // an ekv_kv8_* call (q8 may still be NULL: an argument error)
-  const ekv_kv8* q8;
-  bool batch;              // an ekv_batch_* call (with kv8: an ekv_kv8_batch_* call, with kv4: an ekv_kv4_batch_* call)
+  EkvRows rows;
+  EkvPlanes planes;        // rows != kv16: the descriptor's pointers (all NULL for a NULL descriptor; any NULL is an argument error)
+  bool batch;              // an ekv_*batch_* call
   const ekv_seq* seqs;
   int32_t n_seq;
-  bool kv4;                // an ekv_kv4_* call (q4 may still be NULL: an argument error)
-  const ekv_kv4* q4;
 };
-inline EkvCall step_call(const ekv_bank* bank, const ekv_step* st, int32_t dtype) { return {bank, st, dtype, false, nullptr, false, nullptr, 0}; }
-inline EkvCall kv8_call(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_kv8* q8) { return {bank, st, dtype, true, q8, false, nullptr, 0}; }
+inline EkvCall step_call(const ekv_bank* bank, const ekv_step* st, int32_t dtype) { return {bank, st, dtype, EKV_ROWS_kv16, {}, false, nullptr, 0}; }
 inline EkvCall batch_call(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_seq* seqs, int32_t n_seq) {
-  return {bank, st, dtype, false, nullptr, true, seqs, n_seq};
+  return {bank, st, dtype, EKV_ROWS_kv16, {}, true, seqs, n_seq};
+}
+// the quantised calls: the same two with a row format and its planes
+inline EkvCall kv8_call(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_kv8* q8) {
+  return {bank, st, dtype, EKV_ROWS_kv8, ekv_planes(q8), false, nullptr, 0};
 }
 inline EkvCall kv4_call(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_kv4* q4) {
-  return {bank, st, dtype, false, nullptr, false, nullptr, 0, true, q4};
+  return {bank, st, dtype, EKV_ROWS_kv4, ekv_planes(q4), false, nullptr, 0};
 }
-// an ekv_kv8_batch_* call: both variants at once (resolve_call applies them independently)
 inline EkvCall kv8_batch_call(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_kv8* q8, const ekv_seq* seqs, int32_t n_seq) {
-  return {bank, st, dtype, true, q8, true, seqs, n_seq};
+  return {bank, st, dtype, EKV_ROWS_kv8, ekv_planes(q8), true, seqs, n_seq};
 }
-// an ekv_kv4_batch_* call, likewise
 inline EkvCall kv4_batch_call(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_kv4* q4, const ekv_seq* seqs, int32_t n_seq) {
-  return {bank, st, dtype, false, nullptr, true, seqs, n_seq, true, q4};
+  return {bank, st, dtype, EKV_ROWS_kv4, ekv_planes(q4), true, seqs, n_seq};
 }
+// is `head_dim` one the row format is built for (the table of what each format takes: ekv_plan.cpp, kRowsRules; the conversions ask too)
+bool ekv_rows_head_dim(EkvRows rows, int head_dim);
 
 // Everything a call needs, resolved once (resolve_call): check, info, workspace bytes and attend all read it.
 struct EkvResolved {
-  const ekv_bank* bank;      // the bank planned and launched with; NULL: a kv8 / kv4 call without its planes
+  const ekv_bank* bank;      // the bank planned and launched with; NULL: a quantised call without its planes
   const ekv_step* step;      // the step actually planned: the caller's, or the envelope of a batch
   const EkvSeqTable* tb;     // the table the batch instances receive; NULL for a uniform step
-  EkvStepPlan plan;          // kv8 / batch / fused_order final; zero launches (a batch: zero bytes too) when the call is refused
-  ekv_bank bank8;            // storage of the above, where the call needs its own
+  EkvStepPlan plan;          // rows / batch / fused_order final; zero launches (a batch: zero bytes too) when the call is refused
+  ekv_bank bank_q;           // storage of the above, where the call needs its own
   ekv_step env;
   EkvSeqTable table;
 };

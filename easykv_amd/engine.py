@@ -39,6 +39,38 @@ class StepPlan:
     two_pass: int = 0           # scored chunk steps: 0 auto, 1 force the two-pass kernels, -1 force one pass
 
 
+# The row formats of a quantised bank, by ``kv_quant`` (include/easykv_hip.h, "kv8" / "kv4"): everything the bank, the batch and the
+# driver (api.py) need to know about one.  rows: the calls' prefix (ekv_<rows>_*); desc: the descriptor of the four planes; planes:
+# (attribute, trailing shape at head_dim d, dtype, fill) in the descriptor's order — rows that were never written keep code 0 and
+# scale 1 (exponent byte 127), so every scale of the bank is finite whatever the kernels prefetch; head_dims / max_rep: the shapes the
+# decode kernels of the format are built for; pair_bytes: bytes of one K + V row pair.
+ROW_FORMATS = {
+    "fp8": dict(kind="fp8", rows="kv8", desc=_lib.Kv8, label="FP8", method="quantize_fp8", stored="FP8 codes with per-row scales",
+                planes=(("k8", lambda d: (d,), torch.uint8, 0), ("v8", lambda d: (d,), torch.uint8, 0),
+                        ("k_scale", lambda d: (), torch.float32, 1), ("v_scale", lambda d: (), torch.float32, 1)),
+                head_dims=(64, 128), max_rep=None, pair_bytes=lambda d: 2 * d + 8),
+    "mxfp4": dict(kind="mxfp4", rows="kv4", desc=_lib.Kv4, label="MXFP4", method="quantize_mxfp4", stored="MXFP4 codes with block exponents",
+                  planes=(("k4", lambda d: (d // 2,), torch.uint8, 0), ("v4", lambda d: (d // 2,), torch.uint8, 0),
+                          ("k_exp", lambda d: (d // 32,), torch.uint8, 127), ("v_exp", lambda d: (d // 32,), torch.uint8, 127)),
+                  head_dims=(128,), max_rep=4, pair_bytes=lambda d: d + d // 16),
+}
+
+
+def row_format(kind, what="kv_quant"):
+    """The entry of ROW_FORMATS for ``kind``, or None for None (16-bit rows); anything else is a ValueError naming ``what``."""
+    if kind is not None and kind not in ROW_FORMATS:
+        raise ValueError(f"{what} must be None or 'fp8' / 'mxfp4', not {kind!r}")
+    return ROW_FORMATS.get(kind)
+
+
+def _check_row_shape(fmt, head_dim, rep):
+    """EkvError unless the decode kernels of ``fmt`` are built for this head_dim and GQA factor."""
+    if head_dim not in fmt["head_dims"]:
+        raise _lib.EkvError(f"{fmt['method']}(): {fmt['label']} rows are built for head_dim {' and '.join(map(str, fmt['head_dims']))}, not {head_dim}")
+    if fmt["max_rep"] is not None and rep > fmt["max_rep"]:
+        raise _lib.EkvError(f"{fmt['method']}(): {fmt['label']} rows are built for GQA factors up to {fmt['max_rep']}, not {rep}")
+
+
 def _ptr(t: Optional[torch.Tensor]):
     return None if t is None else C.c_void_p(t.data_ptr())
 
@@ -98,8 +130,7 @@ class KVBank:
 
     default_two_pass = 0    # StepPlan.two_pass used when a plan leaves it at 0 (tests force either chunk scheme with it)
     dtype, _dt = torch.float16, _lib.DTYPE_F16      # (set per bank by __init__)
-    kv_quant, _kv8 = None, None      # quantize_fp8(): "fp8" and the ekv_kv8 descriptor of the code planes / row scales
-    _kv4 = None                      # quantize_mxfp4(): kv_quant "mxfp4" and the ekv_kv4 descriptor of the code planes / block exponents
+    kv_quant = None      # quantize(): "fp8" / "mxfp4" (ROW_FORMATS; _fmt is the entry, _desc the descriptor of the four planes)
 
     def __init__(self, n_layers, n_q_heads, n_kv_heads, head_dim, cap, device="cuda", scored=True, dtype=torch.float16, kv_quant=None):
         """``kv_quant='fp8'``: the bank is created holding FP8 planes only (see :meth:`quantize_fp8`); the 16-bit K/V rows are never
@@ -107,12 +138,9 @@ class KVBank:
         ``kv_quant='mxfp4'``: likewise with MXFP4 planes only (see :meth:`quantize_mxfp4`; head_dim 128, GQA factors up to 4)."""
         if dtype not in _lib.DTYPE_CODES:
             raise ValueError(f"KVBank dtype must be torch.float16 or torch.bfloat16, not {dtype}")
-        if kv_quant not in (None, "fp8", "mxfp4"):
-            raise ValueError(f"KVBank kv_quant must be None or 'fp8' / 'mxfp4', not {kv_quant!r}")
-        if kv_quant == "fp8" and head_dim not in (64, 128):
-            raise _lib.EkvError(f"kv_quant='fp8': FP8 rows are built for head_dim 64 and 128, not {head_dim}")
-        if kv_quant == "mxfp4":
-            self._mxfp4_shape_check(head_dim, n_q_heads // max(1, n_kv_heads))
+        fmt = row_format(kv_quant, "KVBank kv_quant")
+        if fmt is not None:
+            _check_row_shape(fmt, head_dim, n_q_heads // max(1, n_kv_heads))
         self.dtype, self._dt = dtype, _lib.DTYPE_CODES[dtype]
         self.lib = _lib.load()
         dev = torch.device(device)
@@ -159,10 +187,7 @@ class KVBank:
                           self.arrive.data_ptr(), self.birth.data_ptr() if scored else None,
                           self.slot_state.data_ptr() if scored else None)
         self.rope_cos = self.rope_sin = None
-        if kv_quant == "fp8":
-            self._attach_fp8()
-        elif kv_quant == "mxfp4":
-            self._attach_mxfp4()
+        self._attach(fmt)
         self.reset()
 
     # -- layout of the score rows -------------------------------------------------------------------
@@ -253,161 +278,101 @@ class KVBank:
         self._ensure_ordered()
         return self._score_cnt
 
-    # -- FP8 K/V storage ("kv8", include/easykv_hip.h) ----------------------------------------------
-    def _kv8_refuse(self, cond, what):
-        if cond and self._kv8 is not None:
-            raise _lib.EkvError(f"{what} is not available on a bank quantised by quantize_fp8(): its K/V rows are FP8 codes with per-row "
-                                "scales, which only decode steps (q_len == 1, plain keys) read and append to")
-        if cond and self._kv4 is not None:
-            raise _lib.EkvError(f"{what} is not available on a bank quantised by quantize_mxfp4(): its K/V rows are MXFP4 codes with "
-                                "block exponents, which only decode steps (q_len == 1, plain keys) read and append to")
+    # -- quantised K/V storage ("kv8" / "kv4", include/easykv_hip.h; ROW_FORMATS) ----------------------
+    def _quant_refuse(self, cond, what):
+        if cond and self._fmt is not None:
+            raise _lib.EkvError(f"{what} is not available on a bank quantised by {self._fmt['method']}(): its K/V rows are "
+                                f"{self._fmt['stored']}, which only decode steps (q_len == 1, plain keys) read and append to")
 
-    @property
-    def _quant(self):
-        """(call prefix, descriptor) of a quantised bank's step calls — ("ekv_kv8", ekv_kv8) / ("ekv_kv4", ekv_kv4) — or None."""
-        if self._kv8 is not None:
-            return "ekv_kv8", self._kv8
-        if self._kv4 is not None:
-            return "ekv_kv4", self._kv4
-        return None
+    def quantize(self, kind):
+        """Convert the live bank in place to the row format ``kind`` ('fp8' / 'mxfp4'): codes and scales / exponents are written at the
+        rows' physical indices (slot map, free list and score rows carry over as they are, in either layout), the 16-bit K/V tensors
+        are released, ``kv_quant`` is ``kind`` and ``attend`` / ``step_info`` / ``step_plan`` go to that format's calls.  From here on
+        the bank serves decode steps only: chunk steps, ``load_rows``, ``set_rope`` and the row moves raise :class:`EkvError`.  A bank
+        is quantised once: a second conversion raises."""
+        fmt = row_format(kind, "quantize(kind)")
+        if fmt is None:
+            raise ValueError("quantize(kind): kind must be 'fp8' or 'mxfp4'")
+        m = fmt["method"] + "()"
+        if self._fmt is not None:
+            raise _lib.EkvError(f"{m}: the bank's rows are quantised already ({self._fmt['label']} already: kv_quant={self.kv_quant!r})")
+        _check_row_shape(fmt, self.head_dim, self.n_q_heads // self.n_kv_heads)
+        if self.rope_cos is not None:
+            raise _lib.EkvError(f"{m}: a RoPE-on-read (streaming) bank keeps un-rotated keys, which the {fmt['label']} decode kernels do not rotate")
+        if self._defer is not None and self._defer["pending"]:
+            raise _lib.EkvError(f"{m}: a deferred token step is open (flush() first)")
+        if torch.cuda.is_current_stream_capturing():
+            raise _lib.EkvError(f"{m} cannot be captured in a graph: convert the bank before the capture")
+        self.join()
+        desc = self._planes(fmt)
+        call = f"ekv_{fmt['rows']}_quantize"
+        check(getattr(self.lib, call)(C.byref(self._bank), C.byref(desc), self._dt, 0, self.n_layers, max(self.extent), self._stream()), call)
+        cur = torch.cuda.current_stream(self.device)
+        self.k.record_stream(cur)
+        self.v.record_stream(cur)
+        self.k = self.v = None
+        self._attach(fmt, desc)
+        return self
 
     def quantize_fp8(self):
-        """Convert the live bank in place to FP8 (OCP e4m3fn) K/V rows with one fp32 scale per row: codes and scales are written at the
-        rows' physical indices (slot map, free list and score rows carry over as they are, in either layout), the 16-bit K/V tensors
-        are released, and ``attend`` / ``step_info`` / ``step_plan`` go to the kv8 calls.  From here on the bank serves decode steps
-        only: chunk steps, ``load_rows``, ``set_rope`` and the row moves raise :class:`EkvError`."""
-        if self._kv4 is not None:
-            raise _lib.EkvError("quantize_fp8(): the bank's rows are MXFP4 already (quantize_mxfp4())")
-        if self._kv8 is not None:
-            return self
-        if self.head_dim not in (64, 128):
-            raise _lib.EkvError(f"quantize_fp8(): FP8 rows are built for head_dim 64 and 128, not {self.head_dim}")
-        if self.rope_cos is not None:
-            raise _lib.EkvError("quantize_fp8(): a RoPE-on-read (streaming) bank keeps un-rotated keys, which the FP8 decode kernels do not rotate")
-        if self._defer is not None and self._defer["pending"]:
-            raise _lib.EkvError("quantize_fp8(): a deferred token step is open (flush() first)")
-        if torch.cuda.is_current_stream_capturing():
-            raise _lib.EkvError("quantize_fp8() cannot be captured in a graph: convert the bank before the capture")
-        self.join()
-        kv8 = self._fp8_planes()
-        check(self.lib.ekv_kv8_quantize(C.byref(self._bank), C.byref(kv8), self._dt, 0, self.n_layers, max(self.extent), self._stream()),
-              "ekv_kv8_quantize")
-        cur = torch.cuda.current_stream(self.device)
-        self.k.record_stream(cur)
-        self.v.record_stream(cur)
-        self.k = self.v = None
-        self._attach_fp8(kv8)
-        return self
+        """:meth:`quantize` to FP8 (OCP e4m3fn) K/V rows with one fp32 scale per row (``k8`` / ``v8`` / ``k_scale`` / ``v_scale``),
+        head_dim 64 and 128.  On a bank that holds FP8 rows already it does nothing."""
+        return self if self.kv_quant == "fp8" else self.quantize("fp8")
 
-    def _fp8_planes(self):
-        shape = (self.n_layers, self.n_kv_heads, self.cap)
-        # rows that were never written keep code 0 / scale 1: every scale of the bank is finite whatever the kernels prefetch
-        self.k8 = torch.zeros(*shape, self.head_dim, dtype=torch.uint8, device=self.device)
-        self.v8 = torch.zeros_like(self.k8)
-        self.k_scale = torch.ones(*shape, dtype=torch.float32, device=self.device)
-        self.v_scale = torch.ones_like(self.k_scale)
-        return _lib.Kv8(self.k8.data_ptr(), self.v8.data_ptr(), self.k_scale.data_ptr(), self.v_scale.data_ptr())
-
-    def _attach_fp8(self, kv8=None):
-        """The bank's rows are the FP8 planes from here on (``kv8=None``: a bank created without 16-bit rows allocates them now)."""
-        kv8 = self._fp8_planes() if kv8 is None else kv8
-        # the descriptor's planes stand where the rows were: the planning calls that take the bank alone never dereference them
-        self._bank.k, self._bank.v = self.k8.data_ptr(), self.v8.data_ptr()
-        self._kv8, self.kv_quant = kv8, "fp8"
-        self._slot_ok.clear()
-        self._defer = None
-
-    # -- MXFP4 K/V storage ("kv4", include/easykv_hip.h) --------------------------------------------
     def quantize_mxfp4(self):
-        """Convert the live bank in place to MXFP4 K/V rows: e2m1 codes, two per byte, with one E8M0 exponent per 32-element block,
-        written at the rows' physical indices (``k4`` / ``v4`` / ``k_exp`` / ``v_exp``; slot map, free list and score rows carry over
-        as they are, in either layout).  The 16-bit K/V tensors are released, ``kv_quant`` is ``'mxfp4'`` and ``attend`` /
-        ``step_info`` / ``step_plan`` go to the kv4 calls.  head_dim 128 and GQA factors up to 4; from here on the bank serves decode
-        steps only, as after :meth:`quantize_fp8`.  A bank is quantised once: a second conversion of either kind raises."""
-        if self._kv8 is not None or self._kv4 is not None:
-            raise _lib.EkvError(f"quantize_mxfp4(): the bank's rows are quantised already (kv_quant={self.kv_quant!r})")
-        self._mxfp4_shape_check(self.head_dim, self.n_q_heads // self.n_kv_heads)
-        if self.rope_cos is not None:
-            raise _lib.EkvError("quantize_mxfp4(): a RoPE-on-read (streaming) bank keeps un-rotated keys, which the MXFP4 decode kernels do not rotate")
-        if self._defer is not None and self._defer["pending"]:
-            raise _lib.EkvError("quantize_mxfp4(): a deferred token step is open (flush() first)")
-        if torch.cuda.is_current_stream_capturing():
-            raise _lib.EkvError("quantize_mxfp4() cannot be captured in a graph: convert the bank before the capture")
-        self.join()
-        kv4 = self._mxfp4_planes()
-        check(self.lib.ekv_kv4_quantize(C.byref(self._bank), C.byref(kv4), self._dt, 0, self.n_layers, max(self.extent), self._stream()),
-              "ekv_kv4_quantize")
-        cur = torch.cuda.current_stream(self.device)
-        self.k.record_stream(cur)
-        self.v.record_stream(cur)
-        self.k = self.v = None
-        self._attach_mxfp4(kv4)
-        return self
+        """:meth:`quantize` to MXFP4 K/V rows: e2m1 codes, two per byte, with one E8M0 exponent per 32-element block (``k4`` / ``v4``
+        / ``k_exp`` / ``v_exp``), head_dim 128 and GQA factors up to 4."""
+        return self.quantize("mxfp4")
 
-    @staticmethod
-    def _mxfp4_shape_check(head_dim, rep):
-        if head_dim != 128:
-            raise _lib.EkvError(f"quantize_mxfp4(): MXFP4 rows are built for head_dim 128, not {head_dim}")
-        if rep > 4:
-            raise _lib.EkvError(f"quantize_mxfp4(): MXFP4 rows are built for GQA factors up to 4, not {rep}")
-
-    def _mxfp4_planes(self):
+    def _planes(self, fmt):
+        """Allocate the planes of ``fmt`` as the bank's attributes; returns their descriptor."""
         shape = (self.n_layers, self.n_kv_heads, self.cap)
-        # rows that were never written keep code 0 / exponent byte 127 (scale 1): finite whatever the kernels prefetch
-        self.k4 = torch.zeros(*shape, self.head_dim // 2, dtype=torch.uint8, device=self.device)
-        self.v4 = torch.zeros_like(self.k4)
-        self.k_exp = torch.full((*shape, self.head_dim // 32), 127, dtype=torch.uint8, device=self.device)
-        self.v_exp = torch.full_like(self.k_exp, 127)
-        return _lib.Kv4(self.k4.data_ptr(), self.v4.data_ptr(), self.k_exp.data_ptr(), self.v_exp.data_ptr())
+        for name, tail, dtype, fill in fmt["planes"]:
+            setattr(self, name, torch.full(shape + tail(self.head_dim), fill, dtype=dtype, device=self.device))
+        return fmt["desc"](*(getattr(self, name).data_ptr() for name, *_ in fmt["planes"]))
 
-    def _attach_mxfp4(self, kv4=None):
-        """The bank's rows are the MXFP4 planes from here on (``kv4=None``: a bank created without 16-bit rows allocates them now)."""
-        kv4 = self._mxfp4_planes() if kv4 is None else kv4
-        self._bank.k, self._bank.v = self.k4.data_ptr(), self.v4.data_ptr()
-        self._kv4, self.kv_quant = kv4, "mxfp4"
-        self._slot_ok.clear()
-        self._defer = None
+    def _attach(self, fmt, desc=None):
+        """The bank's rows are in the format ``fmt`` from here on (None: 16-bit rows; ``desc=None``: a bank created without 16-bit rows
+        allocates its planes now).  The library calls of the format and the descriptor reference are resolved here, once: the
+        per-layer callers below are host-bound and look nothing up."""
+        if fmt is not None:
+            self._desc = self._planes(fmt) if desc is None else desc
+            # the descriptor's planes stand where the rows were: the planning calls that take the bank alone never dereference them
+            self._bank.k, self._bank.v = self._desc.k_codes, self._desc.v_codes
+            self.kv_quant = fmt["kind"]
+            self._slot_ok.clear()
+            self._defer = None
+        rows = fmt["rows"] if fmt is not None else None
+        self._fmt, self._desc_ref = fmt, () if fmt is None else (C.byref(self._desc),)
+        self._calls = {(batch, what): getattr(self.lib, _lib.step_call_name(rows, batch, what))
+                       for batch in (False, True) for what in _lib.STEP_CALLS}
+        self._check_fn, self._info_fn, self._ws_fn, self._attend_fn = (self._calls[False, what] for what in _lib.STEP_CALLS)
 
     def kv_bytes(self) -> int:
         """Bytes held for the K/V rows: 16-bit rows, FP8 codes + row scales (``2 * head_dim + 8`` per row pair), or MXFP4 codes +
         block exponents (``head_dim + head_dim / 16``: 136 at head_dim 128)."""
-        rows = self.n_layers * self.n_kv_heads * self.cap
-        if self._kv4 is not None:
-            return rows * (self.head_dim + self.head_dim // 16)
-        return rows * (2 * self.head_dim + 8) if self._kv8 is not None else rows * 4 * self.head_dim
+        pair = 4 * self.head_dim if self._fmt is None else self._fmt["pair_bytes"](self.head_dim)
+        return self.n_layers * self.n_kv_heads * self.cap * pair
 
     def dequantized_rows(self, layer):
         """(K, V) ``[H, cap, head_dim]`` fp32 of the PHYSICAL rows of ``layer``: code * scale of a quantised bank (exact), the 16-bit rows
         of any other widened.  Rows that were never written read as zeros on a quantised bank.  For tests and tools."""
-        if self._quant is None:
+        if self._fmt is None:
             return self.k[layer].float(), self.v[layer].float()
         k = torch.empty(self.n_kv_heads, self.cap, self.head_dim, dtype=torch.float32, device=self.device)
         v = torch.empty_like(k)
-        if self._kv4 is not None:
-            check(self.lib.ekv_kv4_dequantize(C.byref(self._bank), C.byref(self._kv4), _lib.DTYPE_F32, layer, 1, self.cap, _ptr(k), _ptr(v),
-                                              self._stream()), "ekv_kv4_dequantize")
-            return k, v
-        check(self.lib.ekv_kv8_dequantize(C.byref(self._bank), C.byref(self._kv8), _lib.DTYPE_F32, layer, 1, self.cap, _ptr(k), _ptr(v),
-                                          self._stream()), "ekv_kv8_dequantize")
+        call = f"ekv_{self._fmt['rows']}_dequantize"
+        check(getattr(self.lib, call)(C.byref(self._bank), *self._desc_ref, _lib.DTYPE_F32, layer, 1, self.cap, _ptr(k), _ptr(v), self._stream()), call)
         return k, v
 
     def _step_check(self, st):
-        if self._quant is not None:
-            name, desc = self._quant
-            return getattr(self.lib, name + "_step_check")(C.byref(self._bank), C.byref(st), self._dt, C.byref(desc))
-        return self.lib.ekv_step_check_typed(C.byref(self._bank), C.byref(st), self._dt)
+        return self._check_fn(C.byref(self._bank), C.byref(st), self._dt, *self._desc_ref)
 
     def _step_ws_bytes(self, st):
-        if self._quant is not None:
-            name, desc = self._quant
-            return getattr(self.lib, name + "_workspace_bytes")(C.byref(self._bank), C.byref(st), self._dt, C.byref(desc))
-        return self.lib.ekv_workspace_bytes_typed(C.byref(self._bank), C.byref(st), self._dt)
+        return self._ws_fn(C.byref(self._bank), C.byref(st), self._dt, *self._desc_ref)
 
     def _step_attend(self, st, *args):
-        if self._quant is not None:
-            name, desc = self._quant
-            return getattr(self.lib, name + "_step_attend")(C.byref(self._bank), C.byref(st), self._dt, C.byref(desc), *args)
-        return self.lib.ekv_step_attend_typed(C.byref(self._bank), C.byref(st), self._dt, *args)
+        return self._attend_fn(C.byref(self._bank), C.byref(st), self._dt, *self._desc_ref, *args)
 
     # -- plumbing -----------------------------------------------------------------------------
     def _stream(self):
@@ -454,7 +419,7 @@ class KVBank:
 
     def set_rope(self, cos, sin):
         """fp32 tables ``[>= cap, head_dim]`` for the streaming (rope-on-read) variant."""
-        self._kv8_refuse(True, "set_rope (RoPE-on-read)")
+        self._quant_refuse(True, "set_rope (RoPE-on-read)")
         self.rope_cos = cos.to(self.device, torch.float32).contiguous()
         self.rope_sin = sin.to(self.device, torch.float32).contiguous()
         half = self.head_dim // 2
@@ -477,7 +442,7 @@ class KVBank:
     def load_rows(self, k, v, pos_begin=None, layer_begin=0):
         """Append ordered rows ``[layers, H, n, D]`` at positions [pos_begin, pos_begin+n)."""
         lc, n = k.shape[0], k.shape[2]
-        self._kv8_refuse(True, "load_rows")
+        self._quant_refuse(True, "load_rows")
         self._ensure_ordered(layer_begin, lc)
         pos = self.n_slots[layer_begin] if pos_begin is None else pos_begin
         k = k.to(self.device, self.dtype).contiguous()
@@ -490,7 +455,7 @@ class KVBank:
     def ordered_kv(self, layer_begin=0, layer_count=None):
         """The ordered ``[layers, H, T, D]`` view the HF legacy tuple needs (birth order)."""
         lc = self.n_layers - layer_begin if layer_count is None else layer_count
-        self._kv8_refuse(True, "ordered_kv (a row move)")
+        self._quant_refuse(True, "ordered_kv (a row move)")
         self._ensure_ordered(layer_begin, lc)
         t = self.n_slots[layer_begin]
         k = torch.empty(lc, self.n_kv_heads, t, self.head_dim, dtype=self.dtype, device=self.device)
@@ -501,7 +466,7 @@ class KVBank:
     def compact_inplace(self, evict_ids, layer_begin=0):
         """Reference-shaped physical compaction for a bank kept in identity layout."""
         lc, _, kk = evict_ids.shape
-        self._kv8_refuse(True, "compact_inplace (a row move)")
+        self._quant_refuse(True, "compact_inplace (a row move)")
         self._ensure_ordered(layer_begin, lc)
         t = self.n_slots[layer_begin]
         ids = evict_ids.to(self.device, torch.int32).contiguous()
@@ -546,7 +511,7 @@ class KVBank:
         """(n_split, fused) the library will use for this step."""
         st = self.make_step(plan, q_len, layer_begin, self.n_layers - layer_begin if layer_count is None else layer_count)
         st.phases = phases
-        if self._quant is not None:      # (the kv8 / kv4 dry run: a step the quantised bank refuses plans as not fused)
+        if self._fmt is not None:      # (the quantised dry run: a step the bank refuses plans as not fused)
             info = self.step_info(plan, q_len, layer_begin, layer_count, phases)
             return info["n_split"], bool(info["fused"])
         ns, fu = C.c_int32(0), C.c_int32(0)
@@ -558,11 +523,7 @@ class KVBank:
         st = self.make_step(plan, q_len, layer_begin, self.n_layers - layer_begin if layer_count is None else layer_count)
         st.phases = phases
         info = (C.c_int32 * 10)()
-        if self._quant is not None:
-            name, desc = self._quant
-            check(getattr(self.lib, name + "_step_info")(C.byref(self._bank), C.byref(st), self._dt, C.byref(desc), info, 10), name + "_step_info")
-        else:
-            check(self.lib.ekv_step_info_typed(C.byref(self._bank), C.byref(st), self._dt, info, 10), "ekv_step_info")
+        check(self._info_fn(C.byref(self._bank), C.byref(st), self._dt, *self._desc_ref, info, 10), self._info_fn.__name__)
         keys = ("n_split", "fused", "two_pass", "wide", "n_qblocks", "qb_rows", "n_col_parts", "fold_in_kernel", "n_launches", "fused_order")
         return dict(zip(keys, (int(x) for x in info)))
 
@@ -615,7 +576,7 @@ class KVBank:
         96-row chunk step of the Llama2-7B shape: 66 us of a 124 us layer).  Decode steps and, since round 4, chunk steps."""
         d = self._defer
         n = q.shape[2]
-        self._kv8_refuse(n > 1, "a chunk step (q_len > 1)")
+        self._quant_refuse(n > 1, "a chunk step (q_len > 1)")
         t = self.n_slots[layer] + n
         if self._slot_rows[layer]:
             self._ensure_ordered()      # (all layers in one launch: the conversion ranks births by counting, ~0.2 ms per launch of <= 256 heads)
@@ -641,12 +602,8 @@ class KVBank:
             d = self._defer = dict(plan=plan, t=t, n=n, st=st, ws=ws, ids=ids, pending=0, rope=(_ptr(self.rope_cos), _ptr(self.rope_sin)),
                                    st_ref=C.byref(st), bank_ref=C.byref(self._bank), ws_ptr=ws.data_ptr(), ws_len=ws.numel(),
                                    stream=self._stream())
-            # (the call and its leading arguments: the typed step, or the kv8 step with the descriptor behind the dtype)
-            if self._quant is not None:
-                name, desc = self._quant
-                d["call"], d["head"] = getattr(self.lib, name + "_step_attend"), (d["bank_ref"], d["st_ref"], self._dt, C.byref(desc))
-            else:
-                d["call"], d["head"] = self.lib.ekv_step_attend_typed, (d["bank_ref"], d["st_ref"], self._dt)
+            # (the call and its leading arguments: the step of the bank's row format, a quantised one with the descriptor behind the dtype)
+            d["call"], d["head"] = self._attend_fn, (d["bank_ref"], d["st_ref"], self._dt, *self._desc_ref)
         st = d["st"]
         st.layer_begin = st.defer_index = layer
         st.layer_count, st.phases = 1, 5
@@ -707,7 +664,7 @@ class KVBank:
                 raise ValueError("defer=True is for one-layer calls")
             return self._attend_deferred(plan, q, k_new, v_new, layer_begin, out), None
         lc, _, n, _ = q.shape
-        self._kv8_refuse(n > 1, "a chunk step (q_len > 1)")
+        self._quant_refuse(n > 1, "a chunk step (q_len > 1)")
         st = self.make_step(plan, n, layer_begin, lc)
         # one-launch decode steps run on the slot-indexed layout of the score rows (nothing moves on an eviction); everything else
         # on the ordered one
@@ -828,29 +785,26 @@ class KVBankBatch:
 
     kv_quant = property(lambda self: self.bank.kv_quant)
 
-    def quantize_fp8(self):
-        """:meth:`KVBank.quantize_fp8` of the shared bank: the rows ``[0, max extent)`` of every layer become FP8 codes + row scales at
+    def quantize(self, kind):
+        """:meth:`KVBank.quantize` of the shared bank: the rows ``[0, max extent)`` of every layer become codes + scales / exponents at
         their physical indices (slot maps, score rows, lengths and extents of every sequence carry over), the 16-bit tensors are
-        released and :meth:`attend` / :meth:`step_info` go to the kv8 batch calls.  ``sequence(i)`` then behaves as a quantised
+        released and :meth:`attend` / :meth:`step_info` go to that format's batch calls.  ``sequence(i)`` then behaves as a quantised
         :class:`KVBank`: decode steps only."""
+        self.bank.quantize(kind)
+        return self
+
+    def quantize_fp8(self):
+        """:meth:`quantize` to FP8 rows (:meth:`KVBank.quantize_fp8`)."""
         self.bank.quantize_fp8()
         return self
 
     def quantize_mxfp4(self):
-        """:meth:`KVBank.quantize_mxfp4` of the shared bank: the rows ``[0, max extent)`` of every layer become MXFP4 codes + block
-        exponents at their physical indices (slot maps, score rows, lengths and extents of every sequence carry over), the 16-bit
-        tensors are released and :meth:`attend` / :meth:`step_info` go to the kv4 batch calls.  ``sequence(i)`` then behaves as a
-        quantised :class:`KVBank`: decode steps only.  head_dim 128, GQA factors up to 4."""
-        self.bank.quantize_mxfp4()
-        return self
+        """:meth:`quantize` to MXFP4 rows (:meth:`KVBank.quantize_mxfp4`: head_dim 128, GQA factors up to 4)."""
+        return self.quantize("mxfp4")
 
     def _quant_call(self, what):
-        """(the batched call `what` of this bank's row kind, its leading descriptor arguments)."""
-        quant = self.bank._quant
-        if quant is None:
-            return getattr(self.lib, "ekv_batch_" + what), ()
-        name, desc = quant
-        return getattr(self.lib, f"{name}_batch_{what}"), (C.byref(desc),)
+        """(the batched call `what` of this bank's row format, its leading descriptor arguments), as the bank resolved them."""
+        return self.bank._calls[True, what], self.bank._desc_ref
 
     def kv_bytes(self) -> int:
         """Bytes held for the K/V rows of all sequences (:meth:`KVBank.kv_bytes` of the shared bank)."""
@@ -871,7 +825,7 @@ class KVBankBatch:
         src.join()
         l0, l1, c = i * self.n_layers, (i + 1) * self.n_layers, src.cap
         b._ensure_ordered(l0, self.n_layers)
-        rows = {None: ("k", "v"), "fp8": ("k8", "v8", "k_scale", "v_scale"), "mxfp4": ("k4", "v4", "k_exp", "v_exp")}[b.kv_quant]
+        rows = ("k", "v") if b._fmt is None else tuple(name for name, *_ in b._fmt["planes"])
         for name in rows + ("slot_of_pos", "score_sum", "score_sq", "score_cnt"):      # (the properties hand out the ordered layout)
             t = getattr(src, name)
             if t is not None:

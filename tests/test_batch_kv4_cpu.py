@@ -78,10 +78,9 @@ def test_kv4_batch_calls_are_exported_and_declared():
     declared = set(re.findall(r"\b(ekv_[a-z0-9_]+)\s*\(", header))
     raw = ctypes.CDLL(L.LIB)
     for name in CALLS:
-        assert name in declared and name in L.EXPORTS_KV4_BATCH and hasattr(raw, name) and hasattr(lib, name), name
-        assert name not in L.EXPORTS and name not in L.EXPORTS_KV4 and name not in L.EXPORTS_KV8, name
+        assert name in declared and name in L.EXPORTS and hasattr(raw, name) and hasattr(lib, name), name
         assert getattr(lib, name).argtypes is not None, name      # typed by load()
-    assert tuple(L.EXPORTS_KV4_BATCH) == CALLS and lib.ekv_abi_version() == 8
+    assert lib.ekv_abi_version() == 8
     assert lib.ekv_kv4_batch_workspace_bytes.restype is ctypes.c_size_t and lib.ekv_kv4_batch_step_check.restype is ctypes.c_int
     assert "There is no batch form" not in header and '"kv4 batches"' in header
     # argument checks come before any device access
@@ -199,24 +198,21 @@ def test_kv4_batch_refusals_come_before_any_launch():
 # ---- 4. build -----------------------------------------------------------------------------------------------------------------------
 def test_batch_kv4_objects_are_built_beside_the_recorded_lists():
     from easykv_amd import _build
-    new = [n for n, _ in _build.batch_kv4_objects()]
-    base, extra = [n for n, _ in _build.all_objects()], [n for n, _ in _build.extra_objects()]
-    assert new == OBJECTS and not set(new) & set(base) and not set(new) & set(extra)
-    assert [n for n, _ in _build.linked_objects()] == base + extra + new
-    # the existing lists are what their own tests record
-    assert extra == ["ekv_kv4", "ekv_attn_decode_d128_plain_kv4", "ekv_attn_decode_d128_plain_kv4_bf16"]
-    assert base == [n for n, _ in _build.objects()] + [f"ekv_attn_decode_d{d}_plain_batch_kv8{t}" for d in (64, 128) for t in ("", "_bf16")]
-    assert len(base) == len(_build.sources()) + len(_build.instances())
-    assert _build.batch_kv4_instances() == [("EKV_DECODE_KV4_BATCH", ("128", "f16")), ("EKV_DECODE_KV4_BATCH", ("128", "bf16"))]
-    main = open(_build.MANIFEST).read()
-    assert '#include "ekv_instances_kv4_batch.def"' in main and "#define EKV_DECODE_KV4_BATCH(head_dim, element)" in main
-    args = dict(_build.batch_kv4_objects())
+    every = [n for n, _ in _build.objects()]
+    assert [n for n in every if "batch_kv4" in n] == OBJECTS and len(set(every)) == len(every)
+    # the other quantised objects are there under the names their own tests hold them to
+    for n in ["ekv_kv4", "ekv_attn_decode_d128_plain_kv4", "ekv_attn_decode_d128_plain_kv4_bf16"] + \
+            [f"ekv_attn_decode_d{d}_plain_batch_kv8{t}" for d in (64, 128) for t in ("", "_bf16")]:
+        assert n in every, n
+    assert len(every) == len(_build.sources()) + len(_build.instances())      # one object per source + one per manifest line
+    lines = [(fam, w) for fam, w in _build.instances() if "kv4" in w and "batch" in w]
+    assert lines == [("EKV_DECODE", ("128", "plain", "f16", "kv4", "batch")), ("EKV_DECODE", ("128", "plain", "bf16", "kv4", "batch"))]
+    args = dict(_build.objects())
     for n in OBJECTS:
         assert "-DEKV_KV4=1" in args[n] and "-DEKV_BATCH=1" in args[n] and "-DEKV_D=128" in args[n] and args[n][-1].endswith("ekv_attn_decode.inc")
     assert "-DEKV_BF16=1" in args[OBJECTS[1]] and "-DEKV_BF16=1" not in args[OBJECTS[0]]
-    assert _build.MANIFEST_KV4_BATCH in _build.headers()
     _build.build_lib()
-    t = os.path.getmtime(_build.MANIFEST_KV4_BATCH)
+    t = os.path.getmtime(_build.MANIFEST)
     for n in OBJECTS:
         obj = os.path.join(_build.OBJ, n + ".o")
         assert os.path.exists(obj) and os.path.getmtime(obj) >= t, n

@@ -38,8 +38,8 @@ class StubBank:
     def release_workspace(self, **k):
         pass
 
-    def quantize_fp8(self):
-        self.kv_quant = "fp8"
+    def quantize(self, kind):
+        self.kv_quant = kind
 
     def layout_signature(self):
         return 0

@@ -18,9 +18,11 @@ What is compared is what the existing tests of each variant compare against, wit
   * kv8: the oracle on the bank's own dequantised contents and the appended row checked against the rule's torch restatement
     (tests/kv8_ref.py), as tests/test_hip_kv8.py does: out_close, victims identical wherever tests.test_hip_fullsize.Probe calls
     the decision well defined;
+  * kv4: the same scheme with the MXFP4 rule (tests/kv4_ref.py) and the helpers of tests/test_hip_kv4.py;
   * batch: every entry against the uniform step of a twin bank that holds the entry's rows alone (tests/test_hip_batch.py's _fill /
     _copy_layer): identical victims, outputs under out_close — the bar tests/test_hip_decode_parity.py holds two kernels of one step to
-    (the twin of a short entry runs the one-launch kernel where the batch runs the envelope's split).
+    (the twin of a short entry runs the one-launch kernel where the batch runs the envelope's split).  A batch line on quantised rows
+    quantises the batch bank and the twins alike (quantize(kind)) once they are filled, so the call launches the line's own instance.
 bf16 cases draw V at 1/4 scale for the reason tests/test_hip_kv8.py gives: the flat 1e-3 bar then applies to a bf16 output too.
 
 A table entry wired to another head_dim or element type misses these bars by orders of magnitude or fails to launch."""
@@ -36,6 +38,7 @@ L, CAP = 2, 192
 # (n_slots of the step, requested n_split, the dry run's answer: one launch?)
 PATHS = [(100, 1, True), (100, 2, True), (164, 2, False)]
 SHORT = 37      # the second entry of a batch
+KIND = {"kv16": None, "kv8": "fp8", "kv4": "mxfp4"}      # the manifest's `rows` word -> KVBank.quantize(kind)
 # Instances the planner cannot reach at these shapes, by object name, with the reason.  (None: RoPE-on-read decode steps get their
 # tables from the oracle's rope_tables.)
 EXCLUDED = {}
@@ -129,7 +132,35 @@ def _check_kv8(tag, bank, plan, oplan, dtype, g):
         O.SELECT_HOOK = None
 
 
-def _check_batch(tag, hq, h, D, dtype, T, n_split, one_launch, g):
+def _check_kv4(tag, bank, plan, oplan, dtype, g):
+    from oracle import easykv_oracle as O
+    from tests.test_hip_fullsize import Probe
+    from tests.test_hip_kv4 import _appended_rows_are_the_rules, _oracle_states
+    hq, h, D = bank.n_q_heads, bank.n_kv_heads, bank.head_dim
+    states = _oracle_states(bank, plan.budget + 1, range(L))
+    q, k, v = _tokens(L, hq, h, D, dtype, g)
+    rows = torch.arange(h)
+    new_row = torch.stack([bank._slot_of_pos[l, :, bank.n_slots[l]] for l in range(L)]).cpu().long()
+    out, ids = bank.attend(plan, q.cuda(), k.cuda(), v.cuda())
+    assert out.dtype == dtype
+    probe = Probe()
+    O.SELECT_HOOK = probe
+    try:
+        for l in range(L):
+            _appended_rows_are_the_rules(bank, l, rows, new_row[l], k[l, :, 0], v[l, :, 0], (tag, l))
+            kd, vd = bank.dequantized_rows(l)
+            kq, vq = kd[rows, new_row[l]].cpu().view(1, h, 1, D), vd[rows, new_row[l]].cpu().view(1, h, 1, D)
+            o_ref, ids_ref = O.layer_step(states[l], q[l:l + 1].float(), kq, vq, oplan)
+            err = float((out[l].float().cpu() - o_ref[0]).abs().max())
+            print(f"[instances] {tag} layer {l}: max |o - ref| = {err:.3e}")
+            assert out_close(out[l].float().cpu(), o_ref[0]), (tag, l, err)
+            same = ids[l, :, 0].cpu().long() == ids_ref[:, 0]
+            assert bool(same[~probe.last_unstable].all()), (tag, l)
+    finally:
+        O.SELECT_HOOK = None
+
+
+def _check_batch(tag, hq, h, D, dtype, rows, T, n_split, one_launch, g):
     """Entries of T and SHORT slots in one call, each against the uniform step of a twin bank that holds its rows alone."""
     from easykv_amd import KVBank, KVBankBatch, StepPlan
     from tests.test_hip_batch import _copy_layer, _fill
@@ -146,6 +177,10 @@ def _check_batch(tag, hq, h, D, dtype, T, n_split, one_launch, g):
         _copy_layer(bat.bank, i, twin, 0)
         twins.append(twin)
         plans.append(StepPlan(policy="roco", phase="decode", evict=True, score_off=0, budget=t - 1, n_split=n_split))
+    if KIND[rows] is not None:      # the line's own row format: the same conversion of the same rows on both sides
+        for b in [bat] + twins:
+            b.quantize(KIND[rows])
+        assert bat.kv_quant == KIND[rows]
     info = bat.step_info(plans, 0, None, n_split)
     assert bool(info["fused"]) == one_launch and (info["n_split"] > 1) == (not one_launch), (tag, info)
     q, k, v = (x.cuda() for x in _tokens(len(lens), hq, h, D, dtype, g))
@@ -171,17 +206,19 @@ def test_instance_runs_its_own_variant(head_dim, keys, element, rows, batching, 
     for T, n_split, one_launch in PATHS:
         tag = (f"d{D} {keys} {element} {rows} {batching} hq={hq}", T, n_split)
         if batching == "batch":
-            _check_batch(tag, hq, h, D, dtype, T, n_split, one_launch, g)
+            _check_batch(tag, hq, h, D, dtype, rows, T, n_split, one_launch, g)
             continue
         bank = _bank(hq, h, D, dtype, T - 1, g, rope)
-        if rows == "kv8":
-            bank.quantize_fp8()
+        if KIND[rows] is not None:
+            bank.quantize(KIND[rows])
         kw = dict(policy="roco", phase="decode", evict=True, score_off=0, budget=T - 1, streaming=keys == "rope")
         plan = StepPlan(n_split=n_split, **kw)
         info = bank.step_info(plan, 1)
         assert bool(info["fused"]) == one_launch and (info["n_split"] > 1) == (not one_launch), (tag, info)
         if rows == "kv8":
             _check_kv8(tag, bank, plan, O.StepPlan(**kw), dtype, g)
+        elif rows == "kv4":
+            _check_kv4(tag, bank, plan, O.StepPlan(**kw), dtype, g)
         else:
             _check_16bit(tag, bank, plan, O.StepPlan(**kw), dtype, rope, g)
 

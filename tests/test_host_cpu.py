@@ -32,7 +32,7 @@ def test_geometry_matches_oracle_and_readme():
 def test_abi_exports_every_declared_symbol():
     from easykv_amd import _build, _lib
     header = open(os.path.join(ROOT, "include", "easykv_hip.h")).read()
-    declared = set(re.findall(r"\b(ekv_[a-z_]+)\s*\(", header))
+    declared = set(re.findall(r"\b(ekv_[a-z0-9_]+)\s*\(", header))
     assert declared == set(_lib.EXPORTS), declared ^ set(_lib.EXPORTS)
     if not os.path.exists(_build.LIB):
         _build.build_lib()
@@ -248,6 +248,7 @@ def test_step_info_launch_counts_of_the_baseline_shapes():
     def bank(L, Hq, H, D, cap, n):
         b = KVBank.__new__(KVBank)
         b.lib = _lib.load()
+        b._attach(None)      # (16-bit rows: the _typed calls)
         cap = (cap + 63) // 64 * 64
         b.n_layers, b.n_q_heads, b.n_kv_heads, b.head_dim, b.cap = L, Hq, H, D, cap
         b._bank = Bank(256, 256, 256, 256, 256, 256, L, Hq, H, D, cap, 256, 256, 256)       # (dummy non-null pointers: nothing is dereferenced)

@@ -33,8 +33,7 @@ def test_kv4_calls_are_exported_and_declared():
     declared = set(re.findall(r"\b(ekv_[a-z0-9_]+)\s*\(", header))
     raw = ctypes.CDLL(L.LIB)
     for name in CALLS:
-        assert name in declared and name in L.EXPORTS_KV4 and name not in L.EXPORTS and hasattr(raw, name) and hasattr(lib, name), name
-    assert tuple(L.EXPORTS_KV4) == CALLS
+        assert name in declared and name in L.EXPORTS and hasattr(raw, name) and hasattr(lib, name), name
     assert lib.ekv_abi_version() == 8
     assert "typedef struct ekv_kv4 {" in header and "e2m1" in header and "E8M0" in header and "low nibble" in header
     assert ctypes.sizeof(L.Kv4) == 4 * 8
@@ -112,23 +111,20 @@ def test_kv4_dry_runs_over_the_dispatch_grid():
 
 
 def test_new_objects_are_built_beside_the_recorded_ones():
-    """objects() and all_objects() are what the fixtures of tests/test_instances_cpu.py and tests/test_batch_kv8_cpu.py record; the
-    kv4 family and its conversion unit are built and linked beside them (extra_objects), from manifest lines of their own."""
+    """The kv4 family and its conversion unit among easykv_amd._build.objects() (which tests/test_instances_cpu.py holds to the recorded
+    set): the conversion unit is an ordinary source, the instances come from ordinary lines of the manifest."""
     from easykv_amd import _build
     want = ["ekv_kv4", "ekv_attn_decode_d128_plain_kv4", "ekv_attn_decode_d128_plain_kv4_bf16"]
-    base = [n for n, _ in _build.all_objects()]
-    extra = [n for n, _ in _build.extra_objects()]
-    assert extra == want and not set(extra) & set(base)
-    assert base == [n for n, _ in _build.objects()] + [f"ekv_attn_decode_d{d}_plain_batch_kv8{t}" for d in (64, 128) for t in ("", "_bf16")]
-    assert _build.extra_instances() == [("EKV_DECODE_KV4", ("128", "f16")), ("EKV_DECODE_KV4", ("128", "bf16"))]
-    assert all(fam in _build.FAMILIES for fam, _ in _build.extra_instances())
-    assert "ekv_kv4" not in [n for n, _ in _build.objects()]
-    main = open(_build.MANIFEST).read()
-    assert '#include "ekv_instances_kv4.def"' in main and "#define EKV_DECODE_KV4(head_dim, element)" in main
-    args = dict(_build.extra_objects())
+    every = [n for n, _ in _build.objects()]
+    assert [n for n in every if n == "ekv_kv4" or n.startswith("ekv_attn_decode_d128_plain_kv4")] == want and len(set(every)) == len(every)
+    assert len(every) == len(_build.sources()) + len(_build.instances())      # one object per source + one per manifest line
+    lines = [(fam, w) for fam, w in _build.instances() if "kv4" in w and "single" in w]
+    assert lines == [("EKV_DECODE", ("128", "plain", "f16", "kv4", "single")), ("EKV_DECODE", ("128", "plain", "bf16", "kv4", "single"))]
+    assert all(fam in _build.FAMILIES for fam, _ in lines)
+    args = dict(_build.objects())
     assert "-DEKV_KV4=1" in args["ekv_attn_decode_d128_plain_kv4"] and "-DEKV_BF16=1" in args["ekv_attn_decode_d128_plain_kv4_bf16"]
     _build.build_lib()
-    t = os.path.getmtime(_build.MANIFEST_KV4)
+    t = os.path.getmtime(_build.MANIFEST)
     for n in want:
         obj = os.path.join(_build.OBJ, n + ".o")
         assert os.path.exists(obj) and os.path.getmtime(obj) >= t, n
@@ -205,13 +201,9 @@ def test_generate_quantises_once_at_the_boundary_and_refuses_before_a_cache(api,
     events = []
 
     class Bank(T.StubBank):
-        def quantize_mxfp4(self):
-            events.append(("mxfp4", self.n_slots[0]))
-            self.kv_quant = "mxfp4"
-
-        def quantize_fp8(self):
-            events.append(("fp8", self.n_slots[0]))
-            self.kv_quant = "fp8"
+        def quantize(self, kind):
+            events.append((kind, self.n_slots[0]))
+            self.kv_quant = kind
     monkeypatch.setattr(T, "StubBank", Bank)
     attend = T.StubCache.attend
 

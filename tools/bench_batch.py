@@ -110,7 +110,7 @@ def _quantised_copy(src, make, rows="kv8"):
     for name in ("k", "v", "slot_of_pos", "score_sum", "score_sq", "score_cnt"):
         getattr(dst, name).copy_(getattr(src, name))
     dst.n_slots, dst.extent = list(src.n_slots), list(src.extent)
-    return dst.quantize_mxfp4() if rows == "kv4" else dst.quantize_fp8()
+    return dst.quantize("mxfp4" if rows == "kv4" else "fp8")
 
 
 def batched_quant_leg(bat, lps, plans, toks, rows="kv8", n_split=0):
@@ -126,7 +126,7 @@ def batched_quant_leg(bat, lps, plans, toks, rows="kv8", n_split=0):
     b = batq.bank
     ws = b._workspace(max(batq.workspace_bytes(st, tb) for st, tb in tables))
     assert batq.step_info(plans, 0, n_split=n_split) == bat.step_info(plans, 0, n_split=n_split)      # planned as the 16-bit batched call of the same table
-    call, desc = (batq.lib.ekv_kv4_batch_step_attend, b._kv4) if rows == "kv4" else (batq.lib.ekv_kv8_batch_step_attend, b._kv8)
+    call, desc = getattr(batq.lib, f"ekv_{rows}_batch_step_attend"), b._desc
 
     def rawq(i):
         j = i % qs.shape[0]

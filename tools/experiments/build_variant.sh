@@ -17,7 +17,7 @@ done
 for f in "$@"; do
   b=$(basename $f .hip)
   # the source and switches of the object, as easykv_amd/_build.py derives them
-  SRC=$(cd $ROOT && python3 -c "import sys; from easykv_amd import _build; print(' '.join(dict(_build.all_objects())[sys.argv[1]]))" $b)
+  SRC=$(cd $ROOT && python3 -c "import sys; from easykv_amd import _build; print(' '.join(dict(_build.objects())[sys.argv[1]]))" $b)
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC -Wall -Wno-unused-function $FLAGS -c $SRC -o /tmp/ekv_var/obj_$NAME/$b.o &
 done
 wait
