@@ -127,7 +127,7 @@ class BudgetedKVCache:
     @property
     def kv_quant(self):
         """None, "fp8" once the bank's K/V rows are FP8 codes with per-row scales (KVBank.quantize_fp8), or "mxfp4" once they are
-        MXFP4 codes with block exponents (KVBank.quantize_mxfp4)."""
+        MXFP4 codes with block exponents (KVBank.quantize_mxfp4), or "mxfp6" (MXFP6 codes, KVBank.quantize_mxfp6)."""
         return self.bank.kv_quant
 
     def kv_bytes(self) -> int:
@@ -372,7 +372,8 @@ class _Run:
         # extension key: storage of the K/V rows during the decode phase — None (the 16-bit rows of kv_dtype) or "fp8": the prefill runs on
         # the 16-bit bank as always and the bank is quantised once at the prefill -> decode boundary (KVBank.quantize(kv_quant): OCP e4m3fn
         # codes + one fp32 scale per row, 2 * head_dim + 8 bytes per row pair), or "mxfp4" (e2m1 codes + one E8M0 exponent per 32 elements,
-        # 136 bytes per row pair; no batched form).  The shapes each takes are engine.ROW_FORMATS'.  kv_dtype keeps meaning the 16-bit
+        # 136 bytes per row pair; no batched form in generate_batch), or "mxfp6" (e2m3 codes, 32 per 24-byte block, + the same exponents: 200 bytes
+        # per row pair; batched as well).  The shapes each takes are engine.ROW_FORMATS'.  kv_dtype keeps meaning the 16-bit
         # type of q / k / v / out.
         self.kv_quant = kv_quant = cfg.get("kv_quant", None)
         shard = getattr(model, "layer_shard", None)
@@ -796,7 +797,8 @@ def generate_batch(self, input_ids_list, generation_config, kv_mode="encoding", 
     per sequence) and a sequence leaves the batch when it samples an EOS or has been fed ``max_new_tokens`` tokens.  Returns the
     decoded strings, in prompt order, and prints each sequence's budget line as ``generate`` prints it.
     ``generation_config['kv_quant'] = 'fp8'``: every prompt's bank is quantised right after its own 16-bit prefill (as ``generate``
-    does at the prefill -> decode boundary) and the decode phase runs one FP8 batched step per layer and token.
+    does at the prefill -> decode boundary) and the decode phase runs one FP8 batched step per layer and token.  ``'mxfp6'``: the same
+    on MXFP6 rows (head_dim 128, GQA factors up to 4).  ``'mxfp4'`` is refused here.
 
     Sampling: ``torch.multinomial`` draws for all live sequences at once, so with ``temperature`` / ``top_p`` that leave more than
     one candidate the global generator is consumed differently from B solo runs; ``kv_policy='random'`` draws once per sequence
@@ -819,15 +821,15 @@ def generate_batch(self, input_ids_list, generation_config, kv_mode="encoding", 
     eos, dev, max_new_tokens = set(int(e) for e in run.eos_token_ids), run.dev, run.max_new_tokens
 
     # ---- every prompt alone, through the single-sequence prefill; its bank becomes one sequence of the batch
-    # (kv_quant='fp8': a prompt's bank is quantised right after its own prefill, so at most one 16-bit bank is alive at a time, and the
-    # batch bank is created holding FP8 planes only)
+    # (kv_quant='fp8' / 'mxfp6': a prompt's bank is quantised right after its own prefill, so at most one 16-bit bank is alive at a time, and the
+    # batch bank is created holding that format's planes only)
     seqs = []
     for p in prompts:
         seqs.append(_prefill(run, p, kv_mode))
         if run.kv_quant:
             seqs[-1].cache.bank.quantize(run.kv_quant)
     first = seqs[0].cache.bank
-    rows = dict(kv_quant=run.kv_quant) if run.kv_quant else {}      # (FP8 planes only: the 16-bit rows of the batch are never allocated)
+    rows = dict(kv_quant=run.kv_quant) if run.kv_quant else {}      # (the format's planes only: the 16-bit rows of the batch are never allocated)
     bat = KVBankBatch(len(seqs), first.n_layers, first.n_q_heads, first.n_kv_heads, first.head_dim, max(s.cache.bank.cap for s in seqs),
                       device=dev, dtype=first.dtype, **rows)
     cache = BudgetedKVCacheBatch(bat, record=run.record)

@@ -36,6 +36,16 @@
 #ifndef EKV_KV4
 #define EKV_KV4 0
 #endif
+// EKV_KV6 = 1 (the kv6 instances): MXFP6 codes + E8M0 block exponents (ekv_decode_stream.h, "MXFP6 rows").  The geometry, the rows in
+// flight, the occupancy bounds and the GQA limit are the MXFP4 builds' (EKV_MX below); only the stream's piece differs, by its format tag.
+#ifndef EKV_KV6
+#define EKV_KV6 0
+#endif
+#if EKV_KV4 || EKV_KV6
+#define EKV_MX 1      // one 32-element block per lane
+#else
+#define EKV_MX 0
+#endif
 // Both switches at once (the batch kv8 instances) are independent: DESIGN.md §3.9, "Batches".
 #define ekv_attn_decode_kernel EKV_KERNEL_NAME(ekv_attn_decode_kernel)
 #define ekv_decode_fused_kernel EKV_KERNEL_NAME(ekv_decode_fused_kernel)
@@ -47,10 +57,10 @@
 // two workgroups per CU instead of four (under the four-workgroup bound: 77..235 spilled registers; scheduling barriers between the
 // rows' conversions made it 85..277).  GQA x 2 / x 4 spill (profiles/kv4_registers.txt).
 #ifndef EKV_SPLIT_KU
-#define EKV_SPLIT_KU (EKV_KV8 || EKV_KV4 ? 4 : 8)
+#define EKV_SPLIT_KU (EKV_KV8 || EKV_MX ? 4 : 8)
 #endif
 #ifndef EKV_FUSED_KU
-#define EKV_FUSED_KU (EKV_KV8 || EKV_KV4 ? 4 : 8)
+#define EKV_FUSED_KU (EKV_KV8 || EKV_MX ? 4 : 8)
 #endif
 #ifndef EKV_ROPE_KU
 #define EKV_ROPE_KU(rep) ((rep) == 4 ? 8 : 4)      // rows in flight per lane group of the RoPE-on-read builds (the largest count without spilled VGPRs; rep 8: 8 spilled at 4)
@@ -58,7 +68,8 @@
 
 namespace {
 
-constexpr int kEPL = EKV_KV4 ? 32 : (EKV_KV8 ? 16 : 8);      // elements of a lane's 16-byte piece of a K/V row
+constexpr int kEPL = EKV_MX ? 32 : (EKV_KV8 ? 16 : 8);      // elements of a lane's piece of a K/V row (16 bytes; MXFP6: 24)
+constexpr int kFMT = EKV_KV6 ? 6 : 0;      // the stream's format tag: what EPL alone does not tell
 
 // SLOT_LDS = false: slot-map entries are fetched per iteration (needs 16-byte aligned map rows, cap % 4 == 0); saves the
 // staging pass and its barrier, which matters when a workgroup only streams one or two iterations.
@@ -92,9 +103,9 @@ __global__ void __launch_bounds__(256) ekv_attn_decode_kernel(const EkvAttnArgs 
   // loads per wave instead of two dependent ones (191 VGPRs, one workgroup per CU anyway).  Measured on the Llama2-7B decode
   // stack, one layer per launch: 14.0 us per layer against 13.7 with 8 — the second round trip is not what bounds the launch
   // (docs/TUNING.md §8, round 3) — so 8 stays.
-  constexpr int KU = (!ROPE && !SLOT_LDS && REP <= 2) ? EKV_SPLIT_KU : (EKV_KV8 || EKV_KV4 ? 4 : 8);
-  ekv_decode_stream<D, REP, ROPE, SLOT_LDS, 4, false, KU>(a, SLOT_LDS ? s_slot : a.slot_of_pos + head_row, logits, a.t_pad, t0, t1,
-                                                          ll, h, head_row, m, l, o, nullptr, EkvNoop(), nrep, hq0);
+  constexpr int KU = (!ROPE && !SLOT_LDS && REP <= 2) ? EKV_SPLIT_KU : (EKV_KV8 || EKV_MX ? 4 : 8);
+  ekv_decode_stream<D, REP, ROPE, SLOT_LDS, 4, false, KU, EkvNoop, kEPL, kFMT>(a, SLOT_LDS ? s_slot : a.slot_of_pos + head_row, logits, a.t_pad,
+                                                                               t0, t1, ll, h, head_row, m, l, o, nullptr, EkvNoop(), nrep, hq0);
 
   ekv_decode_wave_combine<D, REP>(m, l, o);
   ekv_decode_stash<D, REP>(s_part, m, l, o);
@@ -159,7 +170,7 @@ __global__ void __launch_bounds__(256) ekv_attn_decode_kernel(const EkvAttnArgs 
 // fused kernel
 // ------------------------------------------------------------------------------------------------------
 template <int D, int REP, bool ROPE, int ITEMS, int NW, bool SLOT>
-__global__ void __launch_bounds__(64 * NW, (NW >= 8 ? (REP == 1 ? 2 : 1) : (SLOT && ITEMS > 12 ? 2 : (REP == 1 ? (EKV_KV4 ? 2 : 4) : (REP == 2 ? 3 : 2))))) ekv_decode_fused_kernel(const EkvAttnArgs EKV_ARG_A, const EkvScoreArgs EKV_ARG_SC EKV_TB_PARAM) {
+__global__ void __launch_bounds__(64 * NW, (NW >= 8 ? (REP == 1 ? 2 : 1) : (SLOT && ITEMS > 12 ? 2 : (REP == 1 ? (EKV_MX ? 2 : 4) : (REP == 2 ? 3 : 2))))) ekv_decode_fused_kernel(const EkvAttnArgs EKV_ARG_A, const EkvScoreArgs EKV_ARG_SC EKV_TB_PARAM) {
   EKV_SHADOW_A(blockIdx.z)
   EKV_SHADOW_SC(blockIdx.z)
   using Gm = EkvDecodeGeom<D, NW>;
@@ -204,7 +215,7 @@ __global__ void __launch_bounds__(64 * NW, (NW >= 8 ? (REP == 1 ? 2 : 1) : (SLOT
   // in LDS.  The tail is a latency-bound chain of block barriers that leaves HBM idle; when the workgroups of a CU are in different
   // orders, each order's tail falls under the other's stream.  Both orders produce the same bits (below), so WHICH workgroups take
   // order K may depend on where the hardware placed them.
-  constexpr bool kOrders = D == 128 && REP == 1 && !ROPE && NW == 4 && SLOT && ITEMS <= 12 && !EKV_KV8 && !EKV_KV4 && !EKV_BATCH;
+  constexpr bool kOrders = D == 128 && REP == 1 && !ROPE && NW == 4 && SLOT && ITEMS <= 12 && !EKV_KV8 && !EKV_MX && !EKV_BATCH;
   bool order_k = false;
   if constexpr (kOrders) {
     const int om = a.fused_order & 3;
@@ -395,11 +406,11 @@ __global__ void __launch_bounds__(64 * NW, (NW >= 8 ? (REP == 1 ? 2 : 1) : (SLOT
   constexpr int KUF = ROPE ? EKV_ROPE_KU(REP) : EKV_FUSED_KU;
   float m[REP], l[REP], o[REP][kEPL];
   if (PHYS)
-    ekv_decode_stream<D, REP, ROPE, false, NW, PHYS, KUF>(a, slot_row, s_logit, l_pad, 0, T, ll, h, head_row, m, l, o,
+    ekv_decode_stream<D, REP, ROPE, false, NW, PHYS, KUF, decltype(mask_ready), kEPL, kFMT>(a, slot_row, s_logit, l_pad, 0, T, ll, h, head_row, m, l, o,
                                                      reinterpret_cast<const uint8_t*>(s_deadw), mask_ready, nrep, h * nrep);
   else
-    ekv_decode_stream<D, REP, ROPE, false, NW, false, KUF>(a, slot_row, s_logit, l_pad, 0, T, ll, h, head_row, m, l, o, nullptr, EkvNoop(),
-                                                      nrep, h * nrep);
+    ekv_decode_stream<D, REP, ROPE, false, NW, false, KUF, EkvNoop, kEPL, kFMT>(a, slot_row, s_logit, l_pad, 0, T, ll, h, head_row, m, l, o, nullptr,
+                                                      EkvNoop(), nrep, h * nrep);
   if (scored) ekv_tail_prefetch_ragged<NW>(sc, head_row, W, roco, sS, sQ, sC, !SLOT);   // published by the barrier below
   // SLOT: count base and birth of this thread's rows, straight into registers (consumed after the softmax passes of the tail)
   float cC[SLOT ? ITEMS : 1];
@@ -518,7 +529,7 @@ hipError_t EKV_SYM(ekv_launch_attn_decode)(const EkvAttnArgs& a, const EkvSeqTab
     case 1: return launch<1>(a EKV_TB_DEREF, layer_count, s);
     case 2: return launch<2>(a EKV_TB_DEREF, layer_count, s);
     case 3: case 4: return launch<4>(a EKV_TB_DEREF, layer_count, s);
-#if EKV_KV4
+#if EKV_MX
     default: return hipErrorInvalidValue;      // (no REP = 8 build: 256 output registers per lane)
 #else
     default: return launch<8>(a EKV_TB_DEREF, layer_count, s);      // 5..8: one group of 8; wider factors: ceil(rep / 8) groups per KV head
@@ -532,7 +543,7 @@ hipError_t EKV_SYM(ekv_launch_decode_fused)(const EkvAttnArgs& a, const EkvScore
     case 1: return launch_fused<1>(a, sc EKV_TB_DEREF, layer_count, nw, s);
     case 2: return launch_fused<2>(a, sc EKV_TB_DEREF, layer_count, nw, s);
     case 3: case 4: return launch_fused<4>(a, sc EKV_TB_DEREF, layer_count, nw, s);
-#if !EKV_KV4
+#if !EKV_MX
     case 5: case 6: case 7: case 8: return launch_fused<8>(a, sc EKV_TB_DEREF, layer_count, nw, s);
 #endif
     default: return hipErrorInvalidValue;

@@ -208,6 +208,85 @@ __device__ __forceinline__ uint4 ekv_fp4_quant_block(const uint4* src, uint32_t&
   return uint4{ekv_fp4_quant8(f, s), ekv_fp4_quant8(f + 8, s), ekv_fp4_quant8(f + 16, s), ekv_fp4_quant8(f + 24, s)};
 }
 
+// ---- MXFP6 K/V rows ("kv6", include/easykv_hip.h): e2m3 codes, 32 per 24-byte block, one E8M0 exponent per 32-element block ----
+// A lane's piece of a row is the 24 bytes of ONE block, 8-byte aligned (byte 24 * sub of a 96-byte row): three 8-byte loads into six
+// registers.  Widening a code is exact in every target type (four significant bits), so the K side converts the block to 32 packed
+// f16 / bf16 with scale 1 (v_cvt_scalef32_pk32_{f16,bf16}_fp6) and runs the packed-pair dot product of the 16-bit builds, the block's
+// 2^e applied to the lane's partial sum; the V side converts with the block's scale (v_cvt_scalef32_pk32_f32_fp6) + fma.  The
+// exponent plane and the fp32 form of a scale are kv4's (ekv_fp4_exp_scale).
+typedef unsigned int ekv_u2 __attribute__((ext_vector_type(2)));
+typedef unsigned int ekv_u6 __attribute__((ext_vector_type(6)));
+typedef float ekv_f16x __attribute__((ext_vector_type(16)));
+typedef float ekv_f32x __attribute__((ext_vector_type(32)));
+typedef ekv_e ekv_h32 __attribute__((ext_vector_type(32)));
+// Exponent byte of a block from its maximum: the smallest e with amax <= 7.5 * 2^e = 1.875 * 2^(e + 2), i.e. the float's own exponent
+// minus 2, plus one when its mantissa exceeds 1.875 (the carry of the addition below); clamped to [-126, 127], 0 for an all-zero block.
+__device__ __forceinline__ uint32_t ekv_fp6_block_exp(float amax) {
+  if (amax == 0.f) return 127u;
+  const int b = (int)((__float_as_uint(amax) + 0x0FFFFFu) >> 23) - 2;
+  return (uint32_t)min(max(b, 1), 254);
+}
+// the lane's block of the row at `row_ptr` (96 bytes), non-temporal like every K/V row
+__device__ __forceinline__ ekv_u6 ekv_fp6_load_block(const char* row_ptr, int sub) {
+  const ekv_u2* p = reinterpret_cast<const ekv_u2*>(row_ptr) + sub * 3;
+  const ekv_u2 a = __builtin_nontemporal_load(p), b = __builtin_nontemporal_load(p + 1), c = __builtin_nontemporal_load(p + 2);
+  return ekv_u6{a[0], a[1], b[0], b[1], c[0], c[1]};
+}
+__device__ __forceinline__ void ekv_fp6_store_block(char* row_ptr, int sub, const ekv_u6& c) {
+  ekv_u2* p = reinterpret_cast<ekv_u2*>(row_ptr) + sub * 3;
+  p[0] = ekv_u2{c[0], c[1]}, p[1] = ekv_u2{c[2], c[3]}, p[2] = ekv_u2{c[4], c[5]};
+}
+// 32 query elements . the 32 codes of a block (the block's scale is the caller's business)
+__device__ __forceinline__ float ekv_dot32_fp6(const uint4 (&q)[4], const ekv_u6& c, float acc) {
+#if EKV_BF16
+  const ekv_h32 k = __builtin_amdgcn_cvt_scalef32_pk32_bf16_fp6(c, 1.0f);
+#else
+  const ekv_h32 k = __builtin_amdgcn_cvt_scalef32_pk32_f16_fp6(c, 1.0f);
+#endif
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const uint32_t w[4] = {q[i].x, q[i].y, q[i].z, q[i].w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc = EKV_FDOT2(__builtin_bit_cast(ekv_h2, w[j]), ekv_h2{k[8 * i + 2 * j], k[8 * i + 2 * j + 1]}, acc, false);
+  }
+  return acc;
+}
+// o[0..32) += p * (codes * scale)
+__device__ __forceinline__ void ekv_axpy32_fp6(float p, float scale, const ekv_u6& c, float (&o)[32]) {
+  const ekv_f32x f = __builtin_amdgcn_cvt_scalef32_pk32_f32_fp6(c, scale);
+#pragma unroll
+  for (int i = 0; i < 32; ++i) o[i] = fmaf(p, f[i], o[i]);
+}
+// 32 values -> their block under `scale` (a power of two): RNE(x / scale).  v_cvt_scalef32_2xpk16_fp6_f32 interleaves its operands —
+// element i of the first lands at position 2i, of the second at 2i + 1 (measured on MI355X) — so they are the even and the odd elements.
+// The instruction writes its six result registers while it still reads its 32 sources, and the compiler does not know: left alone it
+// places the result inside a source tuple that dies here (v[34:39] over v[28:43] in the split kernel), or over the scale register
+// (v[34:39] with the scale in v34 in the conversion kernel): wrong codes, both seen on the part.  The empty asm below keeps the two
+// sources and the scale live across the conversion, so the result gets registers of its own.
+// What this does and does not guarantee: sources, scale and result are all live right behind the instruction, hence pairwise
+// disjoint THERE; nothing stops the compiler from copying a source just before the conversion and converting from the copy, which
+// could again die at the instruction.  It does not do that today (every conversion of the kv6 objects and of ekv_kv4 was read in the
+// assembly: disjoint operands), and check_rows on every appended and converted row (tests/test_hip_kv6.py) is what would notice.
+// The pk32 conversions above need no guard: in this compiler their destination is early-clobber (the machine IR behind instruction
+// selection says `early-clobber %dst = V_CVT_SCALEF32_PK32_{F32,F16,BF16}_FP6_e64`), the 2xpk16 one's is not.
+__device__ __forceinline__ ekv_u6 ekv_fp6_quant32(const float* f, float scale) {
+  ekv_f16x even, odd;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) even[i] = f[2 * i], odd[i] = f[2 * i + 1];
+  const ekv_u6 c = __builtin_amdgcn_cvt_scalef32_2xpk16_fp6_f32(even, odd, scale);
+  asm volatile("" : : "v"(even), "v"(odd), "v"(scale), "v"(c));
+  return c;
+}
+// 32 source elements (four 16-byte pieces) -> their block: 24 bytes of codes, the exponent byte in `e`
+__device__ __forceinline__ ekv_u6 ekv_fp6_quant_block(const uint4* src, uint32_t& e) {
+  float f[32];
+  float amax = 0.f;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) amax = fmaxf(amax, ekv_widen8_amax(src[i], f + 8 * i));
+  e = ekv_fp6_block_exp(amax);
+  return ekv_fp6_quant32(f, ekv_fp4_exp_scale(e));
+}
+
 // f32 -> one 16-bit output element, rounded to nearest even (bf16: v_cvt_pk_bf16_f32, NaN kept), as the __half the row pointers hold
 __device__ __forceinline__ __half ekv_to_e(float x) {
 #if EKV_BF16

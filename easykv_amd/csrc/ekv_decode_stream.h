@@ -49,7 +49,12 @@ struct EkvNoop {
 // side goes into the conversion of the lane's codes to fp32.  The exponent words of an iteration's KU rows are read as 16-byte
 // vectors when the rows are consecutive (PHYS) and per row through the slot map otherwise.  The appended row is quantised here, one
 // block per lane, and takes part in the step as quantised.
-template <int D, int REP, bool ROPE, bool SLOT_LDS, int NW = 4, bool PHYS = false, int KU = kU, typename MaskReady = EkvNoop, int EPL = 8>
+//
+// MXFP6 rows (EPL = 32 like MXFP4, told apart by the format tag FMT = 6; plain keys, head_dim 128): the geometry, the exponent planes
+// and everything around the piece are MXFP4's.  The piece is the block's 24 bytes at byte 24 * sub of a 96-byte row (8-byte aligned:
+// three 8-byte loads, six registers per row in flight); K: the 32 codes widened to packed 16-bit pairs, V: to fp32 under the block's
+// scale (ekv_common.h).
+template <int D, int REP, bool ROPE, bool SLOT_LDS, int NW = 4, bool PHYS = false, int KU = kU, typename MaskReady = EkvNoop, int EPL = 8, int FMT = 0>
 __device__ __forceinline__ void ekv_decode_stream(const EkvAttnArgs& a, const int32_t* s_slot, float* logit_out,
                                                   int logit_stride, int t0, int t1_in, int ll, int h, size_t head_row,
                                                   float (&m)[REP], float (&l)[REP], float (&o)[REP][EPL],
@@ -57,11 +62,13 @@ __device__ __forceinline__ void ekv_decode_stream(const EkvAttnArgs& a, const in
                                                   int n_rep_real = 0, int q_head0 = -1) {
   using Gm = EkvDecodeGeom<D, NW, KU, EPL>;
   constexpr int LPR = Gm::LPR, RW = Gm::RW, LIVE = Gm::LIVE;
-  constexpr bool KV8 = EPL == 16, KV4 = EPL == 32;
+  constexpr bool KV8 = EPL == 16, KV4 = EPL == 32;      // (KV4: the MX geometry, one block per lane — MXFP4 and MXFP6 rows)
+  constexpr bool KV6 = KV4 && FMT == 6;
+  static_assert(FMT == 0 || KV6, "format tag: 6 = MXFP6 rows (EPL = 32)");
   static_assert(EPL == 8 || (KV8 && !ROPE && LIVE == LPR) || KV4, "FP8 rows: plain keys, head_dim 64 / 128");
   static_assert(!KV4 || (!ROPE && D == 128 && LPR == 4), "MXFP4 rows: plain keys, head_dim 128 (a lane = one 32-element block)");
   constexpr int ESZ = KV8 ? 1 : 2;      // bytes per stored K/V element
-  constexpr int ROWB = KV4 ? D / 2 : D * ESZ;      // bytes per stored K/V row
+  constexpr int ROWB = KV6 ? 3 * D / 4 : (KV4 ? D / 2 : D * ESZ);      // bytes per stored K/V row
   constexpr bool PADDED = LIVE != LPR;      // head_dim 96: lanes sub >= LIVE of a lane group are idle (zero pieces, no loads / stores)
   constexpr int kNW = NW;
   static_assert(!(PHYS && (ROPE || SLOT_LDS)), "physical-order streaming: plain keys, global slot map");
@@ -204,7 +211,18 @@ __device__ __forceinline__ void ekv_decode_stream(const EkvAttnArgs& a, const in
     uint4 kn = uint4{0, 0, 0, 0}, vn = uint4{0, 0, 0, 0};
     const size_t off = (head_row + slot_new) * D;          // append: the new row goes into the recycled slot
     float ksn = 1.f, vsn = 1.f;      // FP8 rows: the new row's scales
-    if constexpr (KV8) {
+    ekv_u6 kn6 = {0, 0, 0, 0, 0, 0}, vn6 = {0, 0, 0, 0, 0, 0};      // MXFP6 rows: the new row's blocks
+    if constexpr (KV6) {
+      // quantise the new row (rule: include/easykv_hip.h): each lane's 32 elements are one block — 24 bytes of codes + one exponent byte
+      uint32_t ke, ve;
+      kn6 = ekv_fp6_quant_block(reinterpret_cast<const uint4*>(k_new_row) + sub * 4, ke);
+      vn6 = ekv_fp6_quant_block(reinterpret_cast<const uint4*>(v_new_row) + sub * 4, ve);
+      ksn = ekv_fp4_exp_scale(ke), vsn = ekv_fp4_exp_scale(ve);
+      ekv_fp6_store_block(reinterpret_cast<char*>(a.k_w) + (head_row + slot_new) * ROWB, sub, kn6);
+      ekv_fp6_store_block(reinterpret_cast<char*>(a.v_w) + (head_row + slot_new) * ROWB, sub, vn6);
+      a.k_exp[(head_row + slot_new) * 4 + sub] = (uint8_t)ke;
+      a.v_exp[(head_row + slot_new) * 4 + sub] = (uint8_t)ve;
+    } else if constexpr (KV8) {
       // quantise the new row (rule: include/easykv_hip.h): row maximum over the lane group, then 16 codes per lane + one scale
       float kf[16], vf[16];
       const uint4* kq = reinterpret_cast<const uint4*>(k_new_row) + sub * 2;
@@ -254,6 +272,8 @@ __device__ __forceinline__ void ekv_decode_stream(const EkvAttnArgs& a, const in
         for (int i = 0; i < 8; ++i) acc = fmaf(kpn[i], qf[r][i], acc);
       } else if constexpr (KV8) {
         acc = ekv_dot16_fp8(qv[r], qv1[r], kn, 0.f);
+      } else if constexpr (KV6) {
+        acc = ekv_dot32_fp6(qx[r], kn6, 0.f) * ksn;      // (this lane's block scale, before the group sum)
       } else if constexpr (KV4) {
         acc = ekv_dot32_fp4(qx[r], kn, 0.f) * ksn;      // (this lane's block scale, before the group sum)
       } else {
@@ -269,6 +289,7 @@ __device__ __forceinline__ void ekv_decode_stream(const EkvAttnArgs& a, const in
 #pragma unroll
       for (int i = 0; i < EPL; ++i) o[r][i] *= alpha;
       if constexpr (KV8) ekv_axpy16_fp8(p * vsn, vn, o[r]);
+      else if constexpr (KV6) ekv_axpy32_fp6(p, vsn, vn6, o[r]);
       else if constexpr (KV4) ekv_axpy32_fp4(p, vsn, vn, o[r]);
       else ekv_axpy8(p, vn, o[r]);
       m[r] = mn;
@@ -292,6 +313,7 @@ __device__ __forceinline__ void ekv_decode_stream(const EkvAttnArgs& a, const in
   }
   auto iteration = [&](const int base, auto&& after_issue) {
     uint4 kr[KU], vr[KU];
+    ekv_u6 kr6[KV6 ? KU : 1], vr6[KV6 ? KU : 1];      // MXFP6 rows: the lane's block of each row (kr / vr stay unused)
     float ksc[KV8 || KV4 ? KU : 1], vsc[KV8 || KV4 ? KU : 1];      // FP8 rows: the scales of the KU rows; MXFP4 rows: of this lane's block of each
     const int j0 = base + grp * KU;
     if constexpr (KV8 && PHYS) {
@@ -370,7 +392,10 @@ __device__ __forceinline__ void ekv_decode_stream(const EkvAttnArgs& a, const in
       }
       // K/V rows are read exactly once per step and the cache (>1 GB) never fits L2/MALL: non-temporal loads
       // (measured on MI355X: 5.5 -> 6.1 TB/s on the pure stream)
-      if (live_lane) {
+      if constexpr (KV6) {
+        kr6[u] = ekv_fp6_load_block(kp, sub);
+        vr6[u] = ekv_fp6_load_block(vp, sub);
+      } else if (live_lane) {
         kr[u] = __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const ekv_u4*>(kp) + sub));
         vr[u] = __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const ekv_u4*>(vp) + sub));
       } else {
@@ -387,6 +412,7 @@ __device__ __forceinline__ void ekv_decode_stream(const EkvAttnArgs& a, const in
       for (int u = 0; u < KU; ++u)
         if ((dead8 >> u) & 1u) {
           vr[u] = uint4{0, 0, 0, 0};
+          if constexpr (KV6) vr6[u] = ekv_u6{0, 0, 0, 0, 0, 0};
           if constexpr (KV8) vsc[u] = 0.f;
           if constexpr (KV4) vsc[u] = 1.f;      // (zero codes under a finite scale)
         }
@@ -420,7 +446,8 @@ __device__ __forceinline__ void ekv_decode_stream(const EkvAttnArgs& a, const in
           s[u] = sall[r][u];
         } else {
           float acc;
-          if constexpr (KV4) acc = ekv_dot32_fp4(qx[r], kr[u], 0.f) * ksc[u];      // (the lane's block scale, before the group sum)
+          if constexpr (KV6) acc = ekv_dot32_fp6(qx[r], kr6[u], 0.f) * ksc[u];
+          else if constexpr (KV4) acc = ekv_dot32_fp4(qx[r], kr[u], 0.f) * ksc[u];      // (the lane's block scale, before the group sum)
           else acc = KV8 ? ekv_dot16_fp8(qv[r], qv1[r], kr[u], 0.f) : ekv_dot8(qv[r], kr[u], 0.f);
           acc = ekv_group_sum<LPR>(acc);
           if constexpr (KV8) acc *= ksc[u];
@@ -453,6 +480,7 @@ __device__ __forceinline__ void ekv_decode_stream(const EkvAttnArgs& a, const in
         const float p = exp2f((s[u] - mn) * EKV_LOG2E);
         l[r] += p;
         if constexpr (KV8) ekv_axpy16_fp8(p * vsc[u], vr[u], o[r]);
+        else if constexpr (KV6) ekv_axpy32_fp6(p, vsc[u], vr6[u], o[r]);
         else if constexpr (KV4) ekv_axpy32_fp4(p, vsc[u], vr[u], o[r]);
         else ekv_axpy8(p, vr[u], o[r]);
       }

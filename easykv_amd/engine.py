@@ -39,7 +39,7 @@ class StepPlan:
     two_pass: int = 0           # scored chunk steps: 0 auto, 1 force the two-pass kernels, -1 force one pass
 
 
-# The row formats of a quantised bank, by ``kv_quant`` (include/easykv_hip.h, "kv8" / "kv4"): everything the bank, the batch and the
+# The row formats of a quantised bank, by ``kv_quant`` (include/easykv_hip.h, "kv8" / "kv4" / "kv6"): everything the bank, the batch and the
 # driver (api.py) need to know about one.  rows: the calls' prefix (ekv_<rows>_*); desc: the descriptor of the four planes; planes:
 # (attribute, trailing shape at head_dim d, dtype, fill) in the descriptor's order — rows that were never written keep code 0 and
 # scale 1 (exponent byte 127), so every scale of the bank is finite whatever the kernels prefetch; head_dims / max_rep: the shapes the
@@ -53,13 +53,17 @@ ROW_FORMATS = {
                   planes=(("k4", lambda d: (d // 2,), torch.uint8, 0), ("v4", lambda d: (d // 2,), torch.uint8, 0),
                           ("k_exp", lambda d: (d // 32,), torch.uint8, 127), ("v_exp", lambda d: (d // 32,), torch.uint8, 127)),
                   head_dims=(128,), max_rep=4, pair_bytes=lambda d: d + d // 16),
+    "mxfp6": dict(kind="mxfp6", rows="kv6", desc=_lib.Kv6, label="MXFP6", method="quantize_mxfp6", stored="MXFP6 codes with block exponents",
+                  planes=(("k6", lambda d: (3 * d // 4,), torch.uint8, 0), ("v6", lambda d: (3 * d // 4,), torch.uint8, 0),
+                          ("k_exp", lambda d: (d // 32,), torch.uint8, 127), ("v_exp", lambda d: (d // 32,), torch.uint8, 127)),
+                  head_dims=(128,), max_rep=4, pair_bytes=lambda d: 3 * d // 2 + d // 16),
 }
 
 
 def row_format(kind, what="kv_quant"):
     """The entry of ROW_FORMATS for ``kind``, or None for None (16-bit rows); anything else is a ValueError naming ``what``."""
     if kind is not None and kind not in ROW_FORMATS:
-        raise ValueError(f"{what} must be None or 'fp8' / 'mxfp4', not {kind!r}")
+        raise ValueError(f"{what} must be None or 'fp8' / 'mxfp4', not {kind!r}; 'mxfp6' is accepted as well")
     return ROW_FORMATS.get(kind)
 
 
@@ -130,12 +134,13 @@ class KVBank:
 
     default_two_pass = 0    # StepPlan.two_pass used when a plan leaves it at 0 (tests force either chunk scheme with it)
     dtype, _dt = torch.float16, _lib.DTYPE_F16      # (set per bank by __init__)
-    kv_quant = None      # quantize(): "fp8" / "mxfp4" (ROW_FORMATS; _fmt is the entry, _desc the descriptor of the four planes)
+    kv_quant = None      # quantize(): "fp8" / "mxfp4" / "mxfp6" (ROW_FORMATS; _fmt is the entry, _desc the descriptor of the four planes)
 
     def __init__(self, n_layers, n_q_heads, n_kv_heads, head_dim, cap, device="cuda", scored=True, dtype=torch.float16, kv_quant=None):
         """``kv_quant='fp8'``: the bank is created holding FP8 planes only (see :meth:`quantize_fp8`); the 16-bit K/V rows are never
         allocated.  Such a bank is filled by decode steps or, as one sequence of a :class:`KVBankBatch`, by ``adopt()``.
-        ``kv_quant='mxfp4'``: likewise with MXFP4 planes only (see :meth:`quantize_mxfp4`; head_dim 128, GQA factors up to 4)."""
+        ``kv_quant='mxfp4'``: likewise with MXFP4 planes only (see :meth:`quantize_mxfp4`; head_dim 128, GQA factors up to 4).
+        ``kv_quant='mxfp6'``: likewise with MXFP6 planes only (see :meth:`quantize_mxfp6`; the same shapes)."""
         if dtype not in _lib.DTYPE_CODES:
             raise ValueError(f"KVBank dtype must be torch.float16 or torch.bfloat16, not {dtype}")
         fmt = row_format(kv_quant, "KVBank kv_quant")
@@ -285,7 +290,7 @@ class KVBank:
                                 f"{self._fmt['stored']}, which only decode steps (q_len == 1, plain keys) read and append to")
 
     def quantize(self, kind):
-        """Convert the live bank in place to the row format ``kind`` ('fp8' / 'mxfp4'): codes and scales / exponents are written at the
+        """Convert the live bank in place to the row format ``kind`` ('fp8' / 'mxfp4' / 'mxfp6'): codes and scales / exponents are written at the
         rows' physical indices (slot map, free list and score rows carry over as they are, in either layout), the 16-bit K/V tensors
         are released, ``kv_quant`` is ``kind`` and ``attend`` / ``step_info`` / ``step_plan`` go to that format's calls.  From here on
         the bank serves decode steps only: chunk steps, ``load_rows``, ``set_rope`` and the row moves raise :class:`EkvError`.  A bank
@@ -324,6 +329,11 @@ class KVBank:
         / ``k_exp`` / ``v_exp``), head_dim 128 and GQA factors up to 4."""
         return self.quantize("mxfp4")
 
+    def quantize_mxfp6(self):
+        """:meth:`quantize` to MXFP6 K/V rows: e2m3 codes, 32 per 24-byte block, with one E8M0 exponent per 32-element block (``k6`` /
+        ``v6`` / ``k_exp`` / ``v_exp``; 200 bytes per row pair), head_dim 128 and GQA factors up to 4."""
+        return self.quantize("mxfp6")
+
     def _planes(self, fmt):
         """Allocate the planes of ``fmt`` as the bank's attributes; returns their descriptor."""
         shape = (self.n_layers, self.n_kv_heads, self.cap)
@@ -350,7 +360,7 @@ class KVBank:
 
     def kv_bytes(self) -> int:
         """Bytes held for the K/V rows: 16-bit rows, FP8 codes + row scales (``2 * head_dim + 8`` per row pair), or MXFP4 codes +
-        block exponents (``head_dim + head_dim / 16``: 136 at head_dim 128)."""
+        block exponents (``head_dim + head_dim / 16``: 136 at head_dim 128; MXFP6: ``3 * head_dim / 2 + head_dim / 16``, 200)."""
         pair = 4 * self.head_dim if self._fmt is None else self._fmt["pair_bytes"](self.head_dim)
         return self.n_layers * self.n_kv_heads * self.cap * pair
 
@@ -766,7 +776,8 @@ class KVBankBatch:
     def __init__(self, n_seq, n_layers, n_q_heads, n_kv_heads, head_dim, cap, device="cuda", scored=True, dtype=torch.float16, kv_quant=None):
         """``kv_quant='fp8'``: the shared bank holds FP8 planes only from the start (the 16-bit rows of ``n_seq`` sequences are never
         allocated); its sequences are filled by :meth:`adopt` from banks quantised by :meth:`KVBank.quantize_fp8`.
-        ``kv_quant='mxfp4'``: likewise with MXFP4 planes, filled from banks quantised by :meth:`KVBank.quantize_mxfp4`."""
+        ``kv_quant='mxfp4'``: likewise with MXFP4 planes, filled from banks quantised by :meth:`KVBank.quantize_mxfp4`.
+        ``kv_quant='mxfp6'``: likewise with MXFP6 planes (:meth:`KVBank.quantize_mxfp6`)."""
         if not 1 <= n_seq <= _lib.MAX_SEQS:
             raise ValueError(f"a decode batch holds 1..{_lib.MAX_SEQS} sequences, not {n_seq}")
         self.n_seq, self.n_layers = n_seq, n_layers
@@ -802,6 +813,10 @@ class KVBankBatch:
         """:meth:`quantize` to MXFP4 rows (:meth:`KVBank.quantize_mxfp4`: head_dim 128, GQA factors up to 4)."""
         return self.quantize("mxfp4")
 
+    def quantize_mxfp6(self):
+        """:meth:`quantize` to MXFP6 rows (:meth:`KVBank.quantize_mxfp6`: head_dim 128, GQA factors up to 4)."""
+        return self.quantize("mxfp6")
+
     def _quant_call(self, what):
         """(the batched call `what` of this bank's row format, its leading descriptor arguments), as the bank resolved them."""
         return self.bank._calls[True, what], self.bank._desc_ref
@@ -814,7 +829,7 @@ class KVBankBatch:
         """Sequence ``i`` takes over the state of ``src``, a bank of this batch's layer count and head shape that one sequence was
         prefilled on alone: K/V rows at their physical indices, slot maps, score rows (ordered layout), lengths and extents.  The
         rows behind ``src.cap`` keep this bank's own free list, so a shorter ``src.cap`` is fine.  A quantised batch takes a quantised
-        source of the same kind (codes and row scales / block exponents are copied as they are); 16-bit, FP8 and MXFP4 rows do not mix."""
+        source of the same kind (codes and row scales / block exponents are copied as they are); 16-bit, FP8, MXFP4 and MXFP6 rows do not mix."""
         b = self.bank
         if (src.n_layers, src.n_q_heads, src.n_kv_heads, src.head_dim, src.dtype) != (self.n_layers, b.n_q_heads, b.n_kv_heads, b.head_dim, b.dtype) \
                 or src.cap > b.cap or not 0 <= i < self.n_seq:
@@ -864,7 +879,7 @@ class KVBankBatch:
         st, tb, _ = self.make_table(plans, layer, active, n_split)
         info = (C.c_int32 * 10)()
         b = self.bank
-        fn, desc = self._quant_call("step_info")      # (FP8 / MXFP4 rows: the kv8 / kv4 batch call, the descriptor behind the dtype)
+        fn, desc = self._quant_call("step_info")      # (FP8 / MXFP4 / MXFP6 rows: the kv8 / kv4 / kv6 batch call, the descriptor behind the dtype)
         check(fn(C.byref(b._bank), C.byref(st), b._dt, *desc, tb, len(tb), info, 10), fn.__name__)
         keys = ("n_split", "fused", "two_pass", "wide", "n_qblocks", "qb_rows", "n_col_parts", "fold_in_kernel", "n_launches", "fused_order")
         return dict(zip(keys, (int(x) for x in info)))

@@ -343,6 +343,54 @@ int ekv_kv4_step_attend(const ekv_bank *bank, const ekv_step *step, int32_t dtyp
                         const void *k_new, const void *v_new, void *out, int32_t *evict_ids, const float *rope_cos,
                         const float *rope_sin, void *workspace, size_t workspace_bytes, void *stream);
 
+/* MXFP6 K/V storage with block scales ("kv6"; ABI 8, additive; head_dim 128).  A bank's K/V rows may be held as
+ *
+ *   k_codes, v_codes   uint8 [n_layers][n_kv_heads][cap][3 * head_dim / 4]   32 six-bit e2m3 codes per 24-byte block, 4 blocks per row
+ *                                                                            (head_dim 128: 96 bytes)
+ *   k_exp,   v_exp     uint8 [n_layers][n_kv_heads][cap][head_dim / 32]      E8M0, exactly kv4's plane: value = code * 2^(byte - 127)
+ *
+ * — 3 * head_dim / 2 + head_dim / 16 bytes per K+V row pair: 200 at head_dim 128, against 136 (kv4), 264 (kv8) and 512 (16-bit rows).
+ * A code is sign (bit 5) and a magnitude index i (bits 4:0): the value is i / 8 for i < 8 and (1 + (i & 7) / 8) * 2^((i >> 3) - 1)
+ * otherwise — the grid 0 .. 0.875 and 1 .. 1.875 in steps of 0.125, 2 .. 3.75 in steps of 0.25, 4 .. 7.5 in steps of 0.5.
+ * Packing: element j of a block sits at bits [6j, 6j + 6) of the block's 24 bytes read as one little-endian 192-bit integer — the
+ * order v_cvt_scalef32_pk32_{f32,f16,bf16}_fp6 read (measured on MI355X).  v_cvt_scalef32_2xpk16_fp6_f32 writes that order with its
+ * operands INTERLEAVED: element i of the first operand lands at position 2i, of the second at 2i + 1 (measured likewise), so a block
+ * is packed from its even and its odd elements.  Rows never move, as for kv8 / kv4.
+ *
+ * Quantisation rule of a block x[0..32) (normative), in fp32:  amax = max |x|;  e = the smallest integer with amax <= 7.5 * 2^e, clamped
+ * to [-126, 127], and e = 0 for an all-zero block;  the stored byte is e + 127 (255 never occurs);  code = round-to-nearest(x / 2^e)
+ * onto the 32 magnitudes with the sign of x, ties to the even code (1.9375 -> 2, 3.875 -> 4, 0.0625 -> 0).  The quotient is exact,
+ * |x / 2^e| <= 7.5, so nothing saturates by construction and the rule has no rounding of its own: an implementation is bit-identical
+ * to another up to the sign of zero — codes 0 and 32 (+0 / -0) are equivalent.  Rows are assumed finite.  What is stored is what is
+ * attended: the row a decode step appends is quantised by the kernel and takes part in that step AS QUANTISED.
+ *
+ * The descriptor carries the four planes; bank->k / bank->v are NOT read by the kv6 step calls. */
+typedef struct ekv_kv6 {
+  void *k_codes, *v_codes;
+  uint8_t *k_exp, *v_exp;
+} ekv_kv6;
+
+/* Bank conversion and its inverse: the arguments and contracts of ekv_kv4_quantize / ekv_kv4_dequantize (out_dtype EKV_DTYPE_F32 is
+ * exact: code * 2^e).  head_dim != 128 is EKV_E_UNSUPPORTED. */
+int ekv_kv6_quantize(const ekv_bank *bank, const ekv_kv6 *kv6, int32_t dtype, int32_t layer_begin, int32_t layer_count,
+                     int32_t extent, void *stream);
+int ekv_kv6_dequantize(const ekv_bank *bank, const ekv_kv6 *kv6, int32_t out_dtype, int32_t layer_begin, int32_t layer_count,
+                       int32_t extent, void *k_out, void *v_out, void *stream);
+
+/* Decode steps on a kv6 bank: the ekv_kv4_step_* signatures with the kv6 descriptor, and exactly what a kv4 step accepts — q_len == 1
+ * with plain keys at head_dim 128 and a GQA factor <= 4 (factor 3 on the padded build), fp16 / bf16 q, k_new, v_new and out, every
+ * policy and phase combination of the 16-bit decode step — planned exactly as the 16-bit step of that shape, fused_order 0.  The kv6
+ * builds read a row as a 4-lane group, one 24-byte block per lane: the lane's partial q . codes is multiplied by its block's 2^e
+ * before the group sum, V codes are converted to fp32 with the block's scale, and the appended row is quantised by its lane group.
+ * EKV_E_UNSUPPORTED from the dry run, before anything is launched: q_len > 1, rope_on_read, head_dim != 128, a GQA factor > 4.  A
+ * missing plane is EKV_E_ARG.  The row moves do not serve kv6 banks; the batch form is ekv_kv6_batch_* below. */
+int ekv_kv6_step_check(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const ekv_kv6 *kv6);
+int ekv_kv6_step_info(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const ekv_kv6 *kv6, int32_t *info, int32_t n_info);
+size_t ekv_kv6_workspace_bytes(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const ekv_kv6 *kv6);
+int ekv_kv6_step_attend(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const ekv_kv6 *kv6, const void *q,
+                        const void *k_new, const void *v_new, void *out, int32_t *evict_ids, const float *rope_cos,
+                        const float *rope_sin, void *workspace, size_t workspace_bytes, void *stream);
+
 /* Batched decode steps (ABI 8, additive): ONE call, and one launch per kernel kind, serves n_seq sequences whose caches have
  * different lengths and different eviction geometry.  Each entry of the table names the bank layer it attends and carries what
  * ekv_step holds per step; entry i owns row i of the call's tensors.  The layers of a table need not be contiguous or ordered, so
@@ -433,6 +481,21 @@ int ekv_kv4_batch_step_info(const ekv_bank *bank, const ekv_step *step, int32_t 
 size_t ekv_kv4_batch_workspace_bytes(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const ekv_kv4 *kv4, const ekv_seq *seqs,
                                      int32_t n_seq);
 int ekv_kv4_batch_step_attend(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const ekv_kv4 *kv4, const ekv_seq *seqs,
+                              int32_t n_seq, const void *q, const void *k_new, const void *v_new, void *out, int32_t *evict_ids,
+                              void *workspace, size_t workspace_bytes, void *stream);
+
+/* Batched decode steps on a kv6 bank ("kv6 batches"; ABI 8, additive): the ekv_kv4_batch_* signatures with the kv6 descriptor, with
+ * the acceptance, the planning (the 16-bit batched call of the same table, fused_order 0) and the refusals of the kv4 batch calls:
+ * EKV_E_UNSUPPORTED from the dry run with nothing launched and 0 workspace bytes, EKV_E_ARG for a NULL descriptor or plane, a dtype
+ * other than EKV_DTYPE_F16 / _BF16 and a bad table.  Per entry the arithmetic is that of ekv_kv6_step_attend of the entry's geometry
+ * under the same n_split. */
+int ekv_kv6_batch_step_check(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const ekv_kv6 *kv6, const ekv_seq *seqs,
+                             int32_t n_seq);
+int ekv_kv6_batch_step_info(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const ekv_kv6 *kv6, const ekv_seq *seqs,
+                            int32_t n_seq, int32_t *info, int32_t n_info);
+size_t ekv_kv6_batch_workspace_bytes(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const ekv_kv6 *kv6, const ekv_seq *seqs,
+                                     int32_t n_seq);
+int ekv_kv6_batch_step_attend(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const ekv_kv6 *kv6, const ekv_seq *seqs,
                               int32_t n_seq, const void *q, const void *k_new, const void *v_new, void *out, int32_t *evict_ids,
                               void *workspace, size_t workspace_bytes, void *stream);
 

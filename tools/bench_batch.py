@@ -34,9 +34,12 @@ plus one GQA x 4 table (Hq 32 over H 8, B = 8 and 32; key "gqa4"): `batched` and
 (n_split = 8: the split kernel's GQA builds do not spill) and forced into one launch (n_split = 1: the one-launch GQA x 4 kv4 build
 spills, profiles/batch_kv4_registers.txt).
 Every leg also reports its algorithmic bytes per per-layer call (K+V row pair: 4 * D bytes in 16 bits, 2 * D + 8 as FP8 codes + row
-scales, D + D / 16 as MXFP4 codes + block exponents).
+scales, D + D / 16 as MXFP4 codes + block exponents, 3 D / 2 + D / 16 as MXFP6 codes + block exponents).
+--mxfp6 (output: profiles/batch_kv6_bench.json) does what --mxfp4 does for MXFP6 rows — batched_kv6, solo_kv6_deferred, ragged_kv6 —
+with `batched`, `batched_kv8`, `batched_kv4`, `ragged`, `ragged_kv8` and `ragged_kv4` as the yardsticks of the same interleaved run
+(no GQA x 4 table).
 
-Usage: python tools/bench_batch.py [--reps 9] [--tokens 24] [--warm 20] [--batches 1,2,4,8,16,32] [--kv8 | --mxfp4] [--out profiles/batch_bench.json]"""
+Usage: python tools/bench_batch.py [--reps 9] [--tokens 24] [--warm 20] [--batches 1,2,4,8,16,32] [--kv8 | --mxfp4 | --mxfp6] [--out profiles/batch_bench.json]"""
 from __future__ import annotations
 
 import argparse
@@ -110,7 +113,7 @@ def _quantised_copy(src, make, rows="kv8"):
     for name in ("k", "v", "slot_of_pos", "score_sum", "score_sq", "score_cnt"):
         getattr(dst, name).copy_(getattr(src, name))
     dst.n_slots, dst.extent = list(src.n_slots), list(src.extent)
-    return dst.quantize("mxfp4" if rows == "kv4" else "fp8")
+    return dst.quantize({"kv4": "mxfp4", "kv6": "mxfp6"}.get(rows, "fp8"))
 
 
 def batched_quant_leg(bat, lps, plans, toks, rows="kv8", n_split=0):
@@ -252,11 +255,11 @@ def uniform_legs(B, lps, g):
     return legs
 
 
-PAIR_BYTES = {"kv16": 4 * D, "kv8": 2 * D + 8, "kv4": D + D // 16}      # one K+V row pair: 16-bit / FP8 codes + two fp32 scales / MXFP4 codes + exponents
+PAIR_BYTES = {"kv16": 4 * D, "kv8": 2 * D + 8, "kv4": D + D // 16, "kv6": 3 * D // 2 + D // 16}      # one K+V row pair: 16-bit / FP8 codes + two fp32 scales / MXFP4 codes + exponents
 
 
 def _rows_of(leg):
-    return "kv8" if "kv8" in leg else ("kv4" if "kv4" in leg else "kv16")
+    return next((r for r in ("kv8", "kv4", "kv6") if r in leg), "kv16")
 
 
 def bytes_per_call(lens, rows="kv16"):
@@ -275,12 +278,13 @@ def run_batch(B, args):
     rs = torch.Generator().manual_seed(20261016 + B)
     ragged = sorted(int(x) for x in torch.randint(255, BUDGET + 1, (B,), generator=rs))
     ragged[-1] = BUDGET      # (the envelope is the uniform shape)
-    quant = ("kv8", "kv4") if args.mxfp4 else (("kv8",) if args.kv8 else ())
+    mx = "kv6" if args.mxfp6 else ("kv4" if args.mxfp4 else None)      # the MX format under test: its legs + the yardsticks of the same run
+    quant = ("kv8", "kv4", "kv6") if args.mxfp6 else (("kv8", "kv4") if args.mxfp4 else (("kv8",) if args.kv8 else ()))
     raw, engine, info, *rawq = batched_legs(B, lps, [BUDGET] * B, g, quant)
     fns = {"batched": raw, "batched_engine": engine}
-    solo_quant = ("kv4",) if args.mxfp4 else quant
-    fns["solo_whole"], fns["solo_deferred"], *deferq = solo_legs(B, lps, g, solo_quant, only_quant=args.mxfp4)
-    if not args.mxfp4:
+    solo_quant = (mx,) if mx else quant
+    fns["solo_whole"], fns["solo_deferred"], *deferq = solo_legs(B, lps, g, solo_quant, only_quant=mx is not None)
+    if not mx:
         fns.update(uniform_legs(B, lps, g))
     fns.update({f"batched_{rows}": f for rows, f in zip(quant, rawq)})
     fns.update({f"solo_{rows}_deferred": f for rows, f in zip(solo_quant, deferq)})
@@ -289,8 +293,8 @@ def run_batch(B, args):
         assert rinfo == info, (rinfo, info)      # a ragged table plans as its envelope
         for rows, f in zip(quant, raggedq):
             fns[f"ragged_{rows}"] = f
-    if args.mxfp4:      # the yardsticks of the same run and the three new legs; the other legs: profiles/batch_bench.json, batch_kv8_bench.json
-        keep = ("batched", "batched_kv8", "batched_kv4", "solo_kv4_deferred", "ragged", "ragged_kv8", "ragged_kv4")
+    if mx:      # the yardsticks of the same run and the three new legs; the other legs: profiles/batch_bench.json, batch_kv8_bench.json
+        keep = ("batched", "batched_kv8", "batched_kv4", "batched_kv6", f"solo_{mx}_deferred", "ragged", "ragged_kv8", "ragged_kv4", "ragged_kv6")
         fns = {k: f for k, f in fns.items() if k in keep}
     if args.legs:      # (a kernel trace of two legs: their launches alone)
         fns = {k: f for k, f in fns.items() if k in args.legs.split(",")}
@@ -323,13 +327,23 @@ def run_batch(B, args):
     if "batched_kv4" in res:
         res["ratio_batched_kv4_over_batched"] = round(us("batched_kv4") / us("batched"), 4)
         res["ratio_batched_kv4_over_batched_kv8"] = round(us("batched_kv4") / us("batched_kv8"), 4)
-        res["ratio_batched_kv4_over_solo_kv4_deferred"] = round(us("batched_kv4") / us("solo_kv4_deferred"), 4)
+        if "solo_kv4_deferred" in res:
+            res["ratio_batched_kv4_over_solo_kv4_deferred"] = round(us("batched_kv4") / us("solo_kv4_deferred"), 4)
         res["byte_ratio_batched_kv4_over_batched"] = round(res["batched_kv4"]["bytes_per_layer_call"] / res["batched"]["bytes_per_layer_call"], 4)
         res["byte_ratio_batched_kv4_over_batched_kv8"] = round(res["batched_kv4"]["bytes_per_layer_call"] / res["batched_kv8"]["bytes_per_layer_call"], 4)
     if "ragged_kv4" in res:
         res["ratio_ragged_kv4_over_ragged"] = round(us("ragged_kv4") / us("ragged"), 4)
         res["ratio_ragged_kv4_over_ragged_kv8"] = round(us("ragged_kv4") / us("ragged_kv8"), 4)
         res["ratio_ragged_kv4_over_batched_kv4_at_envelope"] = round(us("ragged_kv4") / us("batched_kv4"), 4)
+    if "batched_kv6" in res:
+        for other in ("batched", "batched_kv8", "batched_kv4", "solo_kv6_deferred"):
+            res[f"ratio_batched_kv6_over_{other}"] = round(us("batched_kv6") / us(other), 4)
+        for other in ("batched", "batched_kv8"):
+            res[f"byte_ratio_batched_kv6_over_{other}"] = round(res["batched_kv6"]["bytes_per_layer_call"] / res[other]["bytes_per_layer_call"], 4)
+    if "ragged_kv6" in res:
+        for other in ("ragged", "ragged_kv8", "ragged_kv4"):
+            res[f"ratio_ragged_kv6_over_{other}"] = round(us("ragged_kv6") / us(other), 4)
+        res["ratio_ragged_kv6_over_batched_kv6_at_envelope"] = round(us("ragged_kv6") / us("batched_kv6"), 4)
     if "ragged_kv8" in res:
         res["ratio_ragged_kv8_over_ragged"] = round(us("ragged_kv8") / us("ragged"), 4)
         res["ratio_ragged_kv8_over_batched_kv8_at_envelope"] = round(us("ragged_kv8") / us("batched_kv8"), 4)
@@ -381,10 +395,12 @@ def main():
     ap.add_argument("--kv8", action="store_true", help="add the FP8 legs batched_kv8, solo_kv8_deferred, ragged_kv8 (default --out: profiles/batch_kv8_bench.json)")
     ap.add_argument("--mxfp4", action="store_true", help="the MXFP4 legs batched_kv4, solo_kv4_deferred, ragged_kv4 next to batched, batched_kv8, ragged, "
                     "ragged_kv8, and the GQA x 4 table (default --out: profiles/batch_kv4_bench.json)")
+    ap.add_argument("--mxfp6", action="store_true", help="the MXFP6 legs batched_kv6, solo_kv6_deferred, ragged_kv6 next to the 16-bit, FP8 and MXFP4 "
+                    "batched / ragged legs of the same run (default --out: profiles/batch_kv6_bench.json)")
     ap.add_argument("--gqa4-batches", default="8,32", help="--mxfp4: batch sizes of the GQA x 4 table ('' = none)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    args.out = args.out or os.path.join(ROOT, "profiles", "batch_kv4_bench.json" if args.mxfp4 else ("batch_kv8_bench.json" if args.kv8 else "batch_bench.json"))
+    args.out = args.out or os.path.join(ROOT, "profiles", "batch_kv6_bench.json" if args.mxfp6 else "batch_kv4_bench.json" if args.mxfp4 else ("batch_kv8_bench.json" if args.kv8 else "batch_bench.json"))
     torch.cuda.set_device(0)
     res = {"device": torch.cuda.get_device_name(0), "reps": args.reps, "tokens_per_rep": args.tokens, "warm_tokens": args.warm,
            "hbm_peak_gb_per_s": HBM_PEAK_GBS,

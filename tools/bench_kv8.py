@@ -14,7 +14,10 @@ scales — + the appended row, q / out, and the score rows once in and once out)
 interleaved with the other two in the same process on a third copy of the same rows, slot map and score state (fp16 rep, fp8 rep,
 mxfp4 rep, ...), and writes profiles/kv4_bench.json instead: per leg the median, the run-to-run spread and the algorithmic bytes.
 
-Usage: python tools/bench_kv8.py [--reps 15] [--steps 20] [--warm 1000] [--mxfp4] [--out profiles/kv8_bench.json]"""
+--mxfp6 adds the MXFP4 leg and a fourth leg on MXFP6 rows (KVBank.quantize_mxfp6: 3 * head_dim / 2 + head_dim / 16 bytes per row pair)
+in the same way — fp16, fp8, mxfp4 and mxfp6 interleaved on copies of the same rows — and writes profiles/kv6_bench.json.
+
+Usage: python tools/bench_kv8.py [--reps 15] [--steps 20] [--warm 1000] [--mxfp4 | --mxfp6] [--out profiles/kv8_bench.json]"""
 from __future__ import annotations
 
 import argparse
@@ -43,6 +46,10 @@ def step_bytes(kind, L, H, Hq, D, T, n_state=3):
     elif kind == "mxfp4":
         kv = H * T * (D + D // 16)                # codes of K and V (half a byte per element) + one exponent byte per 32 elements
         new = H * (D + D // 16)
+        b = dict(total=kv + new + 2 * Hq * D * 2 + 2 * n_state * H * T * 4, kv=kv)
+    elif kind == "mxfp6":
+        kv = H * T * (3 * D // 2 + D // 16)       # codes of K and V (six bits per element) + one exponent byte per 32 elements
+        new = H * (3 * D // 2 + D // 16)
         b = dict(total=kv + new + 2 * Hq * D * 2 + 2 * n_state * H * T * 4, kv=kv)
     else:
         b = dict(total=b["total"], kv=2 * H * T * D * 2)
@@ -87,8 +94,8 @@ def make_bank(kind, L, H, D, budget):
     bank.score_sq[:, :, :budget] += warm ** 2
     if kind == "fp8":
         bank.quantize_fp8()
-    elif kind == "mxfp4":
-        bank.quantize_mxfp4()
+    elif kind in ("mxfp4", "mxfp6"):
+        bank.quantize(kind)
     return bank, g
 
 
@@ -138,10 +145,11 @@ def leg(name, maker, shape, reps, steps, warm, per=1, kinds=("fp16", "fp8")):
     res["time_ratio_fp8_over_fp16"] = round(res["fp8"]["us_per_launch"] / res["fp16"]["us_per_launch"], 4)
     res["byte_ratio_fp8_over_fp16"] = round(res["fp8"]["bytes_per_launch"] / res["fp16"]["bytes_per_launch"], 4)
     res["faster_by_more_than_the_fp16_spread"] = bool(1.0 - res["time_ratio_fp8_over_fp16"] > res["fp16"]["run_to_run_spread"])
-    if "mxfp4" in kinds:
-        for other in ("fp16", "fp8"):
-            res[f"time_ratio_mxfp4_over_{other}"] = round(res["mxfp4"]["us_per_launch"] / res[other]["us_per_launch"], 4)
-            res[f"byte_ratio_mxfp4_over_{other}"] = round(res["mxfp4"]["bytes_per_launch"] / res[other]["bytes_per_launch"], 4)
+    for mx in ("mxfp4", "mxfp6"):
+        if mx in kinds:
+            for other in kinds[:kinds.index(mx)]:
+                res[f"time_ratio_{mx}_over_{other}"] = round(res[mx]["us_per_launch"] / res[other]["us_per_launch"], 4)
+                res[f"byte_ratio_{mx}_over_{other}"] = round(res[mx]["bytes_per_launch"] / res[other]["bytes_per_launch"], 4)
     return res
 
 
@@ -151,11 +159,12 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warm", type=int, default=1000)
     ap.add_argument("--mxfp4", action="store_true", help="add the MXFP4 leg to the head_dim-128 runs; the default --out becomes profiles/kv4_bench.json")
+    ap.add_argument("--mxfp6", action="store_true", help="add the MXFP4 and MXFP6 legs to the head_dim-128 runs; the default --out becomes profiles/kv6_bench.json")
     ap.add_argument("--out", default=None)
     ap.add_argument("--only", default=None, help="run one leg: fused_d128, fused_d64 or deferred_d128 (nothing is written)")
     args = ap.parse_args()
-    out = args.out or os.path.join(ROOT, "profiles", "kv4_bench.json" if args.mxfp4 else "kv8_bench.json")
-    kinds = ("fp16", "fp8", "mxfp4") if args.mxfp4 else ("fp16", "fp8")
+    out = args.out or os.path.join(ROOT, "profiles", "kv6_bench.json" if args.mxfp6 else ("kv4_bench.json" if args.mxfp4 else "kv8_bench.json"))
+    kinds = ("fp16", "fp8", "mxfp4", "mxfp6") if args.mxfp6 else (("fp16", "fp8", "mxfp4") if args.mxfp4 else ("fp16", "fp8"))
     torch.cuda.set_device(0)
     res = {"device": torch.cuda.get_device_name(0), "reps": args.reps, "steps": args.steps, "warm": args.warm, "hbm_peak_gb_per_s": HBM_PEAK_GBS,
            "shape": "32 layers x 32 heads, budget 2048 (T = 2049), roco, scattered slot map, warm score state"}
@@ -164,8 +173,8 @@ def main():
             "fused_d64": lambda: leg("fused_d64", fused_step, dict(shape, D=64), args.reps, args.steps, args.warm),
             # (per layer: one forward is 32 attention launches + the flush; bytes per layer likewise)
             "deferred_d128": lambda: leg("deferred_d128", deferred_step, shape, args.reps, max(4, args.steps // 4), max(20, args.warm // 32), per=32, kinds=kinds)}
-    if args.mxfp4:
-        del legs["fused_d64"]      # (MXFP4 rows are head_dim 128's)
+    if args.mxfp4 or args.mxfp6:
+        del legs["fused_d64"]      # (MXFP4 / MXFP6 rows are head_dim 128's)
     for name, run in legs.items():
         if args.only in (None, name):
             res[name] = run()
