@@ -40,7 +40,7 @@ def step_call_name(rows, batch, what):
 EXPORTS = ("ekv_abi_version", "ekv_strerror", "ekv_workspace_bytes", "ekv_step_plan", "ekv_bank_reset", "ekv_state_init",
            "ekv_step_attend", "ekv_gather_ordered", "ekv_scatter_rows", "ekv_compact_inplace", "ekv_step_check", "ekv_step_info",
            "ekv_rows_to_slots", "ekv_rows_to_order", "ekv_kv8_quantize", "ekv_kv8_dequantize", "ekv_kv4_quantize", "ekv_kv4_dequantize",
-           "ekv_kv6_quantize", "ekv_kv6_dequantize") + tuple(
+           "ekv_kv6_quantize", "ekv_kv6_dequantize", "ekv_set_resident_bytes", "ekv_step_resident_rows") + tuple(
                step_call_name(rows, batch, what) for rows in (None, "kv8", "kv4", "kv6") for batch in (False, True) for what in STEP_CALLS)
 
 
@@ -117,6 +117,8 @@ def load():
     lib.ekv_step_info.argtypes = [C.POINTER(Bank), C.POINTER(Step), C.POINTER(C.c_int32), C.c_int32]
     lib.ekv_rows_to_slots.argtypes = [C.POINTER(Bank), i32, i32, i32, vp]
     lib.ekv_rows_to_order.argtypes = [C.POINTER(Bank), i32, i32, i32, vp]
+    lib.ekv_set_resident_bytes.argtypes = [C.c_int64]
+    lib.ekv_step_resident_rows.argtypes = [C.POINTER(Bank), C.POINTER(Step), i32]
     # the step family: (bank, step, dtype[, descriptor][, table, entries]) + what the call itself takes
     tails = {"step_check": [], "workspace_bytes": [], "step_info": [C.POINTER(C.c_int32), C.c_int32]}
     for rows, desc in ((None, None), ("kv8", Kv8), ("kv4", Kv4), ("kv6", Kv6)):
@@ -135,6 +137,13 @@ def load():
         raise EkvError("ABI version mismatch")
     _lib = lib
     return lib
+
+
+def set_resident_bytes(nbytes):
+    """Byte budget of the resident rows of one-launch decode steps (include/easykv_hip.h, "resident rows") for this process; None or
+    a negative value: the library's default (EKV_RESIDENT_MB in the environment, else the compile-time value).  Always handed to the
+    library (the value is a process global there: whoever calls the C setter directly is overruled by the next step of a bank)."""
+    load().ekv_set_resident_bytes(-1 if nbytes is None or nbytes < 0 else int(nbytes))
 
 
 def check(code: int, what: str):

@@ -109,6 +109,9 @@ class BudgetedKVCache:
         if dtype is torch.bfloat16 and streaming:
             raise ValueError("a bf16 K/V bank has no RoPE-on-read build: streaming=True needs kv_dtype='float16'")
         self.bank = KVBank(self.layer_count, n_q_heads, n_kv_heads, head_dim, cap, device=device, dtype=dtype)
+        # no resident rows behind a model: its weights (gigabytes) stream through the Infinity Cache between two attention launches
+        # of a layer, and plain loads that miss cost more than non-temporal ones ("resident rows": the harm run)
+        self.bank.resident_bytes = 0
         self.plan = StepPlan(policy="full", phase="prefill", accumulate=False)
         self.streaming = streaming
         self.positions = None    # true position ids of the forward in flight (set by the driver)

@@ -151,6 +151,13 @@ int ekv_step_info(const ekv_bank* bank, const ekv_step* st, int32_t* info, int32
   return call_info(step_call(bank, st, EKV_DTYPE_F16), info, n_info);
 }
 
+// resident rows of the one-launch decode step (include/easykv_hip.h, "resident rows")
+int ekv_set_resident_bytes(int64_t bytes) {
+  ekv_resident_set_budget_bytes(bytes);
+  return EKV_OK;
+}
+int ekv_step_resident_rows(const ekv_bank* bank, const ekv_step* st, int32_t dtype) { return call_resident_rows(step_call(bank, st, dtype)); }
+
 int ekv_step_check_typed(const ekv_bank* bank, const ekv_step* st, int32_t dtype) { return call_check(step_call(bank, st, dtype)); }
 int ekv_step_check(const ekv_bank* bank, const ekv_step* st) { return call_check(step_call(bank, st, EKV_DTYPE_F16)); }
 

@@ -194,6 +194,10 @@ __global__ void __launch_bounds__(64 * NW, (NW >= 8 ? (REP == 1 ? 2 : 1) : (SLOT
   constexpr bool PHYS = !ROPE;
 #endif
   const int l_pad = a.l_pad;   // pitch of a logits row: physical rows [0, E) (PHYS) or positions [0, T)
+  // Resident rows (ekv_decode_stream.h, "load policy"): the 16-bit instances of the flagship geometry — head_dim 128, one query head
+  // per KV head, slot-indexed score rows, both phase orders, 4 and 8 waves, every column count.  Every other instance keeps its code.
+  constexpr bool kResident = D == 128 && REP == 1 && PHYS && SLOT && !EKV_KV8 && !EKV_MX && !EKV_BATCH;
+  const int res_rows = kResident ? EKV_RESIDENT_ROWS(a.fused_order) : 0;
   // LDS: logits [REP][l_pad] | wave partials [4][REP][PS] | score rows S (Q C) [w_pad] | reduction scratch | dead-row bits
   float* s_logit = reinterpret_cast<float*>(smem);
   float* s_part = s_logit + (size_t)REP * l_pad;
@@ -280,7 +284,7 @@ __global__ void __launch_bounds__(64 * NW, (NW >= 8 ? (REP == 1 ? 2 : 1) : (SLOT
       // ---- K phase: raw logits of the live rows -> LDS at the physical row index (a logit depends on its row alone), running maximum
       const uint4 qv = reinterpret_cast<const uint4*>(a.q + ((size_t)ll * a.n_q_heads + h) * D)[sub];
       float mk = EKV_NEG_INF;
-      ekv_decode_plane_loop<D, NW>(a.k, head_row, E, mask_ready, [&](uint4 (&kr)[8], const int j0) {
+      ekv_decode_plane_loop<D, NW, kResident>(a.k, head_row, E, mask_ready, [&](uint4 (&kr)[8], const int j0) {
         const unsigned dead8 = (unsigned)s_dead[j0 >> 3];
         float s[8];
 #pragma unroll
@@ -294,7 +298,7 @@ __global__ void __launch_bounds__(64 * NW, (NW >= 8 ? (REP == 1 ? 2 : 1) : (SLOT
         if (sub < 8 && !((dead8 >> sub) & 1u)) s_logit[j0 + sub] = mine;
 #pragma unroll
         for (int u = 0; u < 8; ++u) mk = fmaxf(mk, s[u]);
-      });
+      }, res_rows);
       // the appended row: written to the bank (K and V) and scored from k_new, as in ekv_decode_stream
       const __half* v_new_row = a.v_new + ((size_t)ll * a.n_kv_heads + h) * D;
       if (wave == 0 && grp == 0) {
@@ -331,7 +335,7 @@ __global__ void __launch_bounds__(64 * NW, (NW >= 8 ? (REP == 1 ? 2 : 1) : (SLOT
       float m[1] = {EKV_NEG_INF}, l[1] = {0.f}, o[1][8];
 #pragma unroll
       for (int i = 0; i < 8; ++i) o[0][i] = 0.f;
-      ekv_decode_plane_loop<D, NW>(a.v, head_row, E, EkvNoop(), [&](uint4 (&vr)[8], const int j0) {
+      ekv_decode_plane_loop<D, NW, kResident>(a.v, head_row, E, EkvNoop(), [&](uint4 (&vr)[8], const int j0) {
         const unsigned dead8 = (unsigned)s_dead[j0 >> 3];
         float s[8];
         if (dead8 == 0xFFu) {      // (nothing live here; past the extent there are no logits to read either)
@@ -365,7 +369,7 @@ __global__ void __launch_bounds__(64 * NW, (NW >= 8 ? (REP == 1 ? 2 : 1) : (SLOT
           ekv_axpy8(p, vr[u], o[0]);
         }
         m[0] = mn;
-      });
+      }, res_rows);
       if (wave == 0 && grp == 0) {      // the appended row, last, as in ekv_decode_stream
         const uint4 vn = reinterpret_cast<const uint4*>(v_new_row)[sub];
         const float acc = s_logit[new_row];
@@ -406,8 +410,8 @@ __global__ void __launch_bounds__(64 * NW, (NW >= 8 ? (REP == 1 ? 2 : 1) : (SLOT
   constexpr int KUF = ROPE ? EKV_ROPE_KU(REP) : EKV_FUSED_KU;
   float m[REP], l[REP], o[REP][kEPL];
   if (PHYS)
-    ekv_decode_stream<D, REP, ROPE, false, NW, PHYS, KUF, decltype(mask_ready), kEPL, kFMT>(a, slot_row, s_logit, l_pad, 0, T, ll, h, head_row, m, l, o,
-                                                     reinterpret_cast<const uint8_t*>(s_deadw), mask_ready, nrep, h * nrep);
+    ekv_decode_stream<D, REP, ROPE, false, NW, PHYS, KUF, decltype(mask_ready), kEPL, kFMT, kResident>(a, slot_row, s_logit, l_pad, 0, T, ll, h, head_row, m, l, o,
+                                                     reinterpret_cast<const uint8_t*>(s_deadw), mask_ready, nrep, h * nrep, res_rows);
   else
     ekv_decode_stream<D, REP, ROPE, false, NW, false, KUF, EkvNoop, kEPL, kFMT>(a, slot_row, s_logit, l_pad, 0, T, ll, h, head_row, m, l, o, nullptr,
                                                       EkvNoop(), nrep, h * nrep);

@@ -54,12 +54,32 @@ struct EkvNoop {
 // and everything around the piece are MXFP4's.  The piece is the block's 24 bytes at byte 24 * sub of a 96-byte row (8-byte aligned:
 // three 8-byte loads, six registers per row in flight); K: the 32 codes widened to packed 16-bit pairs, V: to fp32 under the block's
 // scale (ekv_common.h).
-template <int D, int REP, bool ROPE, bool SLOT_LDS, int NW = 4, bool PHYS = false, int KU = kU, typename MaskReady = EkvNoop, int EPL = 8, int FMT = 0>
+//
+// Load policy of the 16-bit K/V rows.  A row is read exactly once per step and the bank (> 1 GB at the flagship shape) never fits L2 or
+// the 256 MiB Infinity Cache: non-temporal loads (measured on MI355X: 5.5 -> 6.1 TB/s on the pure stream).  But step i + 1 reads the
+// rows of step i except one per head, so a fixed SHARE of the bank can stay in the Infinity Cache from step to step.  RES (the
+// instances named in ekv_attn_decode.inc, kResident; PHYS only): the wave iterations over the physical rows [0, res_rows) — a multiple
+// of RW, planned per launch (ekv_decode_resident_rows, ekv_plan.h) — issue default-policy loads, all others non-temporal ones.  The
+// policy is an instruction modifier, so an iteration's requests exist twice, under a wave-uniform branch (base is per wave); the row ->
+// (wave, lane group, iteration) mapping, the request order, the clamping and everything behind the loads are shared and unchanged.
+template <bool RESIDENT>
+__device__ __forceinline__ uint4 ekv_load_row_piece(const char* row, int sub) {
+  const ekv_u4* p = reinterpret_cast<const ekv_u4*>(row) + sub;
+  if constexpr (RESIDENT) return __builtin_bit_cast(uint4, *p);
+  else return __builtin_bit_cast(uint4, __builtin_nontemporal_load(p));
+}
+template <bool B>
+struct EkvBool {
+  static constexpr bool value = B;
+};
+
+template <int D, int REP, bool ROPE, bool SLOT_LDS, int NW = 4, bool PHYS = false, int KU = kU, typename MaskReady = EkvNoop, int EPL = 8, int FMT = 0, bool RES = false>
 __device__ __forceinline__ void ekv_decode_stream(const EkvAttnArgs& a, const int32_t* s_slot, float* logit_out,
                                                   int logit_stride, int t0, int t1_in, int ll, int h, size_t head_row,
                                                   float (&m)[REP], float (&l)[REP], float (&o)[REP][EPL],
                                                   const uint8_t* s_dead = nullptr, MaskReady mask_ready = MaskReady(),
-                                                  int n_rep_real = 0, int q_head0 = -1) {
+                                                  int n_rep_real = 0, int q_head0 = -1, int res_rows = 0) {
+  static_assert(!RES || (PHYS && EPL == 8 && D == 128), "resident rows: 16-bit rows of head_dim 128 (whole lane groups) in physical order");
   using Gm = EkvDecodeGeom<D, NW, KU, EPL>;
   constexpr int LPR = Gm::LPR, RW = Gm::RW, LIVE = Gm::LIVE;
   constexpr bool KV8 = EPL == 16, KV4 = EPL == 32;      // (KV4: the MX geometry, one block per lane — MXFP4 and MXFP6 rows)
@@ -375,6 +395,23 @@ __device__ __forceinline__ void ekv_decode_stream(const EkvAttnArgs& a, const in
 #pragma unroll
       for (int i = 0; i < KU / 4; ++i) iv[i] = ip[i];
     }
+    if constexpr (RES) {
+      // the iteration's K/V requests under one load policy, twice (see the head of this function).  The row index is opaque inside each
+      // copy, so that every address is formed next to its load as in the single-policy code: hoisted above the branch, the 2 * KU
+      // addresses are live at once and cost the occupancy the kernel is built for
+      auto request = [&](auto resident) {
+        int jr = j0;
+        asm volatile("" : "+v"(jr));
+#pragma unroll
+        for (int u = 0; u < KU; ++u) {
+          const int row = jr + u < t1 ? jr + u : t1 - 1;
+          kr[u] = ekv_load_row_piece<decltype(resident)::value>(reinterpret_cast<const char*>(a.k) + (head_row + row) * ROWB, sub);
+          vr[u] = ekv_load_row_piece<decltype(resident)::value>(reinterpret_cast<const char*>(a.v) + (head_row + row) * ROWB, sub);
+        }
+      };
+      if (base < res_rows) request(EkvBool<true>());
+      else request(EkvBool<false>());
+    } else {
 #pragma unroll
     for (int u = 0; u < KU; ++u) {
       const int j = j0 + u;
@@ -390,8 +427,7 @@ __device__ __forceinline__ void ekv_decode_stream(const EkvAttnArgs& a, const in
         ksc[u] = ekv_fp4_exp_scale(a.k_exp[(head_row + row) * 4 + sub]);
         vsc[u] = ekv_fp4_exp_scale(a.v_exp[(head_row + row) * 4 + sub]);
       }
-      // K/V rows are read exactly once per step and the cache (>1 GB) never fits L2/MALL: non-temporal loads
-      // (measured on MI355X: 5.5 -> 6.1 TB/s on the pure stream)
+      // a row is read once per step: non-temporal loads (the load policy: the head of this function)
       if constexpr (KV6) {
         kr6[u] = ekv_fp6_load_block(kp, sub);
         vr6[u] = ekv_fp6_load_block(vp, sub);
@@ -401,6 +437,7 @@ __device__ __forceinline__ void ekv_decode_stream(const EkvAttnArgs& a, const in
       } else {
         kr[u] = vr[u] = uint4{0, 0, 0, 0};
       }
+    }
     }
     ekv_f2 rc[4], rs[4];      // ROPE: (cos, signed sin) of row j0 for this lane's 8 frequencies — the seed, read with the K / V rows
     if (ROPE) rope_seed(min(j0, t1 - 1), rc, rs);
@@ -566,20 +603,31 @@ __device__ __forceinline__ void ekv_decode_reduce(const float* s_part, int r, in
 // consumed (two register sets, the loop unrolled by two): 16 x 16 B in flight per lane, as in the fused loop.  Rows past t1 are
 // clamped to t1 - 1 (requested and dropped; the dead-row bits decide what counts), so every request is unconditional and the
 // waits the compiler places count requests, not paths.  `first` runs once per wave, behind the first requests (mask_ready).
-template <int D, int NW, typename First, typename Consume>
-__device__ __forceinline__ void ekv_decode_plane_loop(const __half* plane, size_t head_row, int t1, First&& first, Consume&& consume) {
+// RES / res_rows: the load policy per block of RW rows, as in ekv_decode_stream; a block wholly past t1 (a request ahead of the loop's
+// end: every row clamped to t1 - 1) takes the policy of that row's block.
+template <int D, int NW, bool RES = false, typename First, typename Consume>
+__device__ __forceinline__ void ekv_decode_plane_loop(const __half* plane, size_t head_row, int t1, First&& first, Consume&& consume, int res_rows = 0) {
   using Gm = EkvDecodeGeom<D, NW, 8, 8>;
   static_assert(Gm::LIVE == Gm::LPR, "whole lane groups");
   constexpr int RW = Gm::RW, STEP = NW * RW;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int sub = lane % Gm::LPR, grp = lane / Gm::LPR;
-  auto request = [&](uint4 (&r)[8], int base) {
-    const int j0 = base + grp * 8;
+  auto request_as = [&](auto resident, uint4 (&r)[8], int base) {
+    int j0 = base + grp * 8;
+    if constexpr (RES) asm volatile("" : "+v"(j0));      // (opaque per copy: addresses formed next to their loads, see ekv_decode_stream)
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
       const int row = j0 + u < t1 ? j0 + u : t1 - 1;
       const char* p = reinterpret_cast<const char*>(plane) + (head_row + row) * (D * 2);
-      r[u] = __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const ekv_u4*>(p) + sub));
+      r[u] = ekv_load_row_piece<decltype(resident)::value>(p, sub);
+    }
+  };
+  auto request = [&](uint4 (&r)[8], int base) {
+    if constexpr (RES) {
+      if (min(base, t1 - 1) < res_rows) request_as(EkvBool<true>(), r, base);
+      else request_as(EkvBool<false>(), r, base);
+    } else {
+      request_as(EkvBool<false>(), r, base);
     }
   };
   uint4 ra[8], rb[8];

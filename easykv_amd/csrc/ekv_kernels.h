@@ -12,6 +12,11 @@
 // kv6: MXFP6 (e2m3) codes + E8M0 block exponents (ekv_kv6).
 enum EkvRows : int32_t { EKV_ROWS_kv16, EKV_ROWS_kv8, EKV_ROWS_kv4, EKV_ROWS_kv6 };
 
+// The resident rows of a one-launch decode step as they travel in EkvAttnArgs.fused_order / EkvStepPlan.fused_order (bits 16-23)
+#define EKV_RESIDENT_UNIT 32      // rows of one wave iteration of the stream (EkvDecodeGeom::RW at head_dim 128)
+#define EKV_RESIDENT_BITS(rows) ((((rows) / EKV_RESIDENT_UNIT) > 255 ? 255 : ((rows) / EKV_RESIDENT_UNIT)) << 16)
+#define EKV_RESIDENT_ROWS(order) ((((order) >> 16) & 255) * EKV_RESIDENT_UNIT)
+
 // One kernel launch sequence entry of a step (EkvStepPlan::list), in issue order.
 enum EkvLaunchKind : int32_t {
   EKV_RUN_FUSED_DECODE,   // ekv_launch_decode_fused: the whole decode step
@@ -121,6 +126,9 @@ struct EkvAttnArgs {
   // EkvScoreArgs are the launch's second argument); set only for heads whose column sums ONE workgroup writes
   // fused decode step: the phase order of its workgroups (ekv_decode_fused_order; 0 = every workgroup streams K+V and then runs its
   // tail).  Decode steps have no use for score_tail, whose storage it shares, so the struct stays as it was.
+  // Bits 16-23 of fused_order: the planned resident rows of the launch in units of 32 rows (EKV_RESIDENT_ROWS; ekv_decode_resident_rows,
+  // ekv_plan.h) — physical rows below it are read with default-policy loads, the rest non-temporally.  Only the 16-bit slot-indexed
+  // head_dim 128 instances of GQA factor 1 read the bits.
   union {
     int32_t score_tail;
     int32_t fused_order;

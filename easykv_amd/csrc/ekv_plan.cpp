@@ -75,6 +75,36 @@ int ekv_decode_fused_order(int head_dim, int rep, bool scored, bool slot_rows, i
   return n_heads_in_launch >= 512 ? (1 | rule) : 0;
 }
 
+// Resident rows of the one-launch decode step (ekv_plan.h).  Step i + 1 reads the rows of step i except one per head, and the chip has a
+// 256 MiB Infinity Cache: a fixed share of the bank read with default-policy loads can be served from it, while the rest is streamed
+// non-temporally as before.  The default budget is what the sweep of tools/experiments/exp_resident.py measured best
+// (profiles/resident_sweep.json); 0 = every K/V load non-temporal, the code before the resident rows.
+#ifndef EKV_RESIDENT_MB_DEFAULT
+#define EKV_RESIDENT_MB_DEFAULT 224
+#endif
+namespace {
+i64 g_resident_bytes = -1;      // ekv_set_resident_bytes; < 0: the environment / compile-time default
+}
+i64 ekv_resident_budget_bytes() {
+  static const i64 dflt = (i64)std::max(0, std::min(env_int("EKV_RESIDENT_MB", EKV_RESIDENT_MB_DEFAULT), 1 << 20)) << 20;
+  return g_resident_bytes < 0 ? dflt : g_resident_bytes;
+}
+void ekv_resident_set_budget_bytes(i64 bytes) { g_resident_bytes = bytes; }
+
+int ekv_decode_resident_rows(i64 n_heads_in_launch, i64 row_bytes, int phys_extent, int cap, int score_rows, i64 budget_bytes) {
+  static const int force = env_int("EKV_RESIDENT_ROWS", -1);   // (A/B and test knob)
+  if (n_heads_in_launch <= 0 || row_bytes <= 0 || phys_extent <= 0 || cap <= 0 || score_rows < 0) return 0;
+  const i64 unit = EKV_RESIDENT_UNIT;
+  const i64 ext = std::min<i64>(((i64)phys_extent + unit - 1) / unit * unit, 255 * unit);      // (what the kernel field holds)
+  if (budget_bytes <= 0) return 0;      // (a caller that switched the resident rows off keeps them off, whatever the knob says)
+  if (force >= 0) return (int)std::min<i64>(force / unit * unit, ext);
+  const i64 heads = std::min<i64>(n_heads_in_launch, 1 << 20);
+  const i64 score = heads * 4 * cap * (score_rows + 2);      // score rows + slot map + birth, `cap` words each
+  const i64 per_unit = heads * 2 * unit * std::min<i64>(row_bytes, 1 << 16);      // K + V of 32 rows of every head
+  if (budget_bytes < score) return 0;
+  return (int)(std::min<i64>((budget_bytes - score) / per_unit, ext / unit) * unit);
+}
+
 bool ekv_decode_fused_supported(int head_dim, int rep, int n_slots, int t_pad, int l_pad, int n_evict, int cap, int nw) {
   // (the slot map and the score rows are fetched 16 bytes at a time: rows must be 16-byte aligned)
   if (!ekv_attn_decode_supported(head_dim, rep) || rep > 8 || n_evict > 1 || n_slots > 256 * 24 || (cap & 3) != 0 || cap < 16) return false;
@@ -437,6 +467,11 @@ bool plan_whole_step(const StepShape& s, EkvStepPlan* P, int* rc) {
     P->slot_tail_ok = s.slot_rows && s.slot_tail_ok ? 1 : 0;
     P->one_launch = 1;
     P->fused_order = ekv_decode_fused_order(s.D, s.rep, s.scored, s.slot_rows, P->fused_nw, heads_now, P->phys_extent);
+    // resident rows: the instances that read them (ekv_attn_decode.inc, kResident) — 16-bit rows (resolve_call clears the field for the
+    // quantised and the batch calls), head_dim 128, one query head per KV head, slot-indexed score rows (so plain keys, physical order)
+    if (s.D == 128 && s.rep == 1 && s.slot_rows && !st->rope_on_read)
+      P->fused_order |= EKV_RESIDENT_BITS(ekv_decode_resident_rows(heads_now, 2 * s.D, P->phys_extent, bank->cap,
+                                                                   st->policy == EKV_POLICY_ROCO ? 3 : 1, ekv_resident_budget_bytes()));
     run(P, EKV_RUN_FUSED_DECODE, 1);
     return true;
   }
@@ -764,6 +799,16 @@ int call_info(const EkvCall& c, int32_t* info, int32_t n_info) {
   for (int i = 0; i < n_info && i < EKV_STEP_INFO_N; ++i) info[i] = v[i];
   for (int i = EKV_STEP_INFO_N; i < n_info; ++i) info[i] = 0;
   return EKV_OK;
+}
+
+int call_resident_rows(const EkvCall& c) {
+  EkvResolved r;
+  const bool ok = resolve_call(c, &r) == EKV_OK;
+  if (c.dtype != EKV_DTYPE_F16 && c.dtype != EKV_DTYPE_BF16) return EKV_E_ARG;
+  if (c.rows != EKV_ROWS_kv16 && !r.bank) return EKV_E_ARG;
+  if (int e = check_bank(r.bank)) return e;
+  if (!c.step || (c.batch && !c.seqs)) return EKV_E_ARG;
+  return ok && r.plan.one_launch ? EKV_RESIDENT_ROWS(r.plan.fused_order) : 0;
 }
 
 int call_plan(const ekv_bank* bank, const ekv_step* st, int32_t* n_split, int32_t* fused) {

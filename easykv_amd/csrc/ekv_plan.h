@@ -14,6 +14,17 @@ int ekv_decode_fused_nw(int64_t n_heads_in_launch);
 // decides (0 HW_ID.TG_ID, 1 HW_ID.WAVE_ID of wave 0, 2 the workgroup's index in the launch), bits 8-11 a mask m, bits 12-15 a bound b,
 // bit 6 = invert: order K when ((x & m) < b) != invert.  Both orders produce the same bits, so a hardware-derived number is as good as any.
 int ekv_decode_fused_order(int head_dim, int rep, bool scored, bool slot_rows, int nw, int64_t n_heads_in_launch, int phys_extent);
+// Resident rows of a one-launch decode step (the kernel field: bits 16-23 of EkvAttnArgs.fused_order, EKV_RESIDENT_ROWS): the physical
+// rows [0, result) of every head are read with default-policy loads, so that they stay in the Infinity Cache from one step to the next;
+// the rest are streamed non-temporally.  The largest multiple of 32 rows such that heads * (2 * rows * row_bytes + the score bytes a
+// head re-reads every step: `score_rows` float rows, the slot map and the birth row, `cap` words each) fits `budget_bytes`, at most
+// phys_extent rounded up to 32; 0 when not even the score bytes fit.  EKV_RESIDENT_ROWS in the environment (an A/B and test knob, read
+// once) replaces the byte rule by a row count, capped the same way, under any budget but 0 (0 stays 0).
+int ekv_decode_resident_rows(int64_t n_heads_in_launch, int64_t row_bytes, int phys_extent, int cap, int score_rows, int64_t budget_bytes);
+// The byte budget of the above: EKV_RESIDENT_MB in the environment (MiB, read once) or the compile-time default, until
+// ekv_set_resident_bytes sets one (a negative value returns to the former).
+int64_t ekv_resident_budget_bytes();
+void ekv_resident_set_budget_bytes(int64_t bytes);
 bool ekv_decode_fused_supported(int head_dim, int rep, int n_slots, int t_pad, int l_pad, int n_evict, int cap, int nw);
 bool ekv_decode_score_supported(const EkvScoreArgs& sc);
 bool ekv_attn_chunk_supported(int head_dim, int rep, int q_len);
@@ -97,5 +108,8 @@ int call_check(const EkvCall& c);
 size_t call_workspace_bytes(const EkvCall& c);
 // ekv_step_info and its kin: the plan's answers also for a step the call would refuse (launch counts 0 then); argument errors first
 int call_info(const EkvCall& c, int32_t* info, int32_t n_info);
+// ekv_step_resident_rows: the resident rows the call's launch is planned with (0 for every call but a one-launch decode step of the
+// instances that have them, and for a step the call would refuse); argument errors as negative codes
+int call_resident_rows(const EkvCall& c);
 // ekv_step_plan: the split count, and whether the whole step is one launch (0 for a step the call would refuse)
 int call_plan(const ekv_bank* bank, const ekv_step* st, int32_t* n_split, int32_t* fused);

@@ -134,6 +134,10 @@ class KVBank:
 
     default_two_pass = 0    # StepPlan.two_pass used when a plan leaves it at 0 (tests force either chunk scheme with it)
     dtype, _dt = torch.float16, _lib.DTYPE_F16      # (set per bank by __init__)
+    # byte budget of the resident rows of this bank's one-launch decode steps (include/easykv_hip.h, "resident rows"): None = the
+    # library's default, 0 = every K/V load non-temporal — what a caller sets whose process streams more than the Infinity Cache holds
+    # between two steps (easykv_amd.api: a model's weights)
+    resident_bytes = None
     kv_quant = None      # quantize(): "fp8" / "mxfp4" / "mxfp6" (ROW_FORMATS; _fmt is the entry, _desc the descriptor of the four planes)
 
     def __init__(self, n_layers, n_q_heads, n_kv_heads, head_dim, cap, device="cuda", scored=True, dtype=torch.float16, kv_quant=None):
@@ -382,6 +386,7 @@ class KVBank:
         return self._ws_fn(C.byref(self._bank), C.byref(st), self._dt, *self._desc_ref)
 
     def _step_attend(self, st, *args):
+        _lib.set_resident_bytes(self.resident_bytes)
         return self._attend_fn(C.byref(self._bank), C.byref(st), self._dt, *self._desc_ref, *args)
 
     # -- plumbing -----------------------------------------------------------------------------
@@ -536,6 +541,19 @@ class KVBank:
         check(self._info_fn(C.byref(self._bank), C.byref(st), self._dt, *self._desc_ref, info, 10), self._info_fn.__name__)
         keys = ("n_split", "fused", "two_pass", "wide", "n_qblocks", "qb_rows", "n_col_parts", "fold_in_kernel", "n_launches", "fused_order")
         return dict(zip(keys, (int(x) for x in info)))
+
+    def resident_rows(self, plan: StepPlan, q_len=1, layer_begin=0, layer_count=None, phases=0) -> int:
+        """Resident rows the library plans this step's launch with (ekv_step_resident_rows) under this bank's ``resident_bytes``;
+        0 for a quantised bank."""
+        if self._fmt is not None:
+            return 0
+        st = self.make_step(plan, q_len, layer_begin, self.n_layers - layer_begin if layer_count is None else layer_count)
+        st.phases = phases
+        _lib.set_resident_bytes(self.resident_bytes)
+        rows = self.lib.ekv_step_resident_rows(C.byref(self._bank), C.byref(st), self._dt)
+        if rows < 0:
+            check(rows, "ekv_step_resident_rows")
+        return rows
 
     def join(self):
         """Make the current stream wait for every scorer still running on a side stream."""

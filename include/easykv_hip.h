@@ -168,6 +168,21 @@ int ekv_step_plan(const ekv_bank *bank, const ekv_step *step, int32_t *n_split, 
 int ekv_step_info(const ekv_bank *bank, const ekv_step *step, int32_t *info, int32_t n_info);
 int ekv_step_info_typed(const ekv_bank *bank, const ekv_step *step, int32_t dtype, int32_t *info, int32_t n_info);
 
+/* Resident rows of the one-launch decode step.  Step i + 1 reads the K/V rows of step i except one per head, so a fixed share of the
+ * bank can stay in the 256 MiB Infinity Cache between two steps: the physical rows [0, R) of every head of a launch are read with
+ * default-policy loads, the rest non-temporally as before (results are bit-identical for every R).  R is planned per launch from a
+ * byte budget: the largest multiple of 32 rows whose K + V bytes, plus the score rows, slot map and birth rows the step re-reads
+ * anyway, fit it; at most the physical extent rounded up to 32, so a launch that fits entirely is read with plain loads.  R is 0
+ * for RoPE-on-read, quantised rows, batched and split steps, and for shapes other than head_dim 128 with one query head per KV head
+ * on the slot-indexed score rows.  The budget: EKV_RESIDENT_MB in the environment (MiB, read once per process; 0 = every K/V load
+ * non-temporal) over the library's default, until ekv_set_resident_bytes sets a value for the process (negative: back to the
+ * former).  A caller whose process streams more than the cache holds between two decode steps of a layer (a model's weights) should
+ * set 0: plain loads that miss are slower than non-temporal ones.  ekv_step_resident_rows is the dry run: R of (bank, step), or a
+ * negative error code.  EKV_RESIDENT_ROWS in the environment forces R (capped at the rounded extent) under any budget but 0, for A/B
+ * runs and tests: a caller that set the budget to 0 keeps every load non-temporal. */
+int ekv_set_resident_bytes(int64_t bytes);
+int ekv_step_resident_rows(const ekv_bank *bank, const ekv_step *step, int32_t dtype);
+
 /* slot_of_pos <- identity for the whole bank */
 int ekv_bank_reset(const ekv_bank *bank, void *stream);
 
