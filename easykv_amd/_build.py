@@ -15,16 +15,17 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fP
 OBJ = os.path.join(CSRC, "obj")
 MANIFEST = os.path.join(CSRC, "ekv_instances.def")
 ADDED_MANIFEST = os.path.join(CSRC, "ekv_instances_added.def")      # (see added_objects())
+LATER_MANIFEST = os.path.join(CSRC, "ekv_instances_later.def")      # (see later_objects())
 
 
 def _tags(*words):
-    """File-name tags of an instance's words, in the order the object names have always had: batch, kv8 / kv4 / kv6, bf16."""
-    return "".join("_" + w for w in ("batch", "kv8", "kv4", "kv6", "bf16") if w in words)
+    """File-name tags of an instance's words, in the order the object names have always had: batch, kv8 / kv4 / kv6 / kv84, bf16."""
+    return "".join("_" + w for w in ("batch", "kv8", "kv4", "kv6", "kv84", "bf16") if w in words)
 
 
 def _on(*words):
-    sw = {"bf16": "EKV_BF16", "kv8": "EKV_KV8", "kv4": "EKV_KV4", "kv6": "EKV_KV6", "batch": "EKV_BATCH"}
-    return [f"-D{sw[w]}=1" for w in ("kv8", "kv4", "kv6", "batch", "bf16") if w in words]
+    sw = {"bf16": "EKV_BF16", "kv8": "EKV_KV8", "kv4": "EKV_KV4", "kv6": "EKV_KV6", "kv84": "EKV_KV84", "batch": "EKV_BATCH"}
+    return [f"-D{sw[w]}=1" for w in ("kv8", "kv4", "kv6", "kv84", "batch", "bf16") if w in words]
 
 
 # family of a manifest line -> (its kernel source, object name, -D switches), all from the line's words
@@ -87,8 +88,20 @@ def added_objects():
     return _instance_objects(added_instances())
 
 
+# added_objects() in turn is held by its tests to exactly the four kv6 lines, so the instances added after those are the lines of a third
+# file, included by the manifest next to the second.  This one is open: a feature appends its lines, and tests ask only that their own
+# objects are among later_objects(), apart from the other two lists, and built and linked.
+def later_instances():
+    return instances(LATER_MANIFEST)
+
+
+def later_objects():
+    """(object name, hipcc arguments) of the instances of ekv_instances_later.def (the kv84 decode instances first)."""
+    return _instance_objects(later_instances())
+
+
 def headers():
-    return (glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.inc")) + [MANIFEST, ADDED_MANIFEST] +
+    return (glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.inc")) + [MANIFEST, ADDED_MANIFEST, LATER_MANIFEST] +
             [os.path.join(HERE, "..", "include", "easykv_hip.h")])
 
 
@@ -108,7 +121,7 @@ def build_lib(force: bool = False, verbose: bool = False, jobs: int = 0) -> str:
     os.makedirs(OBJ, exist_ok=True)
     hdr_t = max(os.path.getmtime(h) for h in headers())
     todo, objs = [], []
-    for name, args in objects() + added_objects():
+    for name, args in objects() + added_objects() + later_objects():
         obj = os.path.join(OBJ, name + ".o")
         objs.append(obj)
         src_t = os.path.getmtime(args[-1])

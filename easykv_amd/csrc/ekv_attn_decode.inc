@@ -46,6 +46,16 @@
 #else
 #define EKV_MX 0
 #endif
+// EKV_KV84 = 1 (the kv84 instances): FP8 keys with MXFP4 values (ekv_decode_stream.h, "FP8-key / MXFP4-value rows").  Geometry, rows in
+// flight, occupancy bounds and GQA builds are the FP8 builds' (EKV_G8 below); the stream's V side differs, by its format tag.
+#ifndef EKV_KV84
+#define EKV_KV84 0
+#endif
+#if EKV_KV8 || EKV_KV84
+#define EKV_G8 1      // the FP8 geometry: 16 elements per lane
+#else
+#define EKV_G8 0
+#endif
 // Both switches at once (the batch kv8 instances) are independent: DESIGN.md §3.9, "Batches".
 #define ekv_attn_decode_kernel EKV_KERNEL_NAME(ekv_attn_decode_kernel)
 #define ekv_decode_fused_kernel EKV_KERNEL_NAME(ekv_decode_fused_kernel)
@@ -57,10 +67,10 @@
 // two workgroups per CU instead of four (under the four-workgroup bound: 77..235 spilled registers; scheduling barriers between the
 // rows' conversions made it 85..277).  GQA x 2 / x 4 spill (profiles/kv4_registers.txt).
 #ifndef EKV_SPLIT_KU
-#define EKV_SPLIT_KU (EKV_KV8 || EKV_MX ? 4 : 8)
+#define EKV_SPLIT_KU (EKV_G8 || EKV_MX ? 4 : 8)
 #endif
 #ifndef EKV_FUSED_KU
-#define EKV_FUSED_KU (EKV_KV8 || EKV_MX ? 4 : 8)
+#define EKV_FUSED_KU (EKV_G8 || EKV_MX ? 4 : 8)
 #endif
 #ifndef EKV_ROPE_KU
 #define EKV_ROPE_KU(rep) ((rep) == 4 ? 8 : 4)      // rows in flight per lane group of the RoPE-on-read builds (the largest count without spilled VGPRs; rep 8: 8 spilled at 4)
@@ -68,8 +78,8 @@
 
 namespace {
 
-constexpr int kEPL = EKV_MX ? 32 : (EKV_KV8 ? 16 : 8);      // elements of a lane's piece of a K/V row (16 bytes; MXFP6: 24)
-constexpr int kFMT = EKV_KV6 ? 6 : 0;      // the stream's format tag: what EPL alone does not tell
+constexpr int kEPL = EKV_MX ? 32 : (EKV_G8 ? 16 : 8);      // elements of a lane's piece of a K/V row (16 bytes; MXFP6: 24)
+constexpr int kFMT = EKV_KV6 ? 6 : (EKV_KV84 ? 84 : 0);      // the stream's format tag: what EPL alone does not tell
 
 // SLOT_LDS = false: slot-map entries are fetched per iteration (needs 16-byte aligned map rows, cap % 4 == 0); saves the
 // staging pass and its barrier, which matters when a workgroup only streams one or two iterations.
@@ -103,7 +113,7 @@ __global__ void __launch_bounds__(256) ekv_attn_decode_kernel(const EkvAttnArgs 
   // loads per wave instead of two dependent ones (191 VGPRs, one workgroup per CU anyway).  Measured on the Llama2-7B decode
   // stack, one layer per launch: 14.0 us per layer against 13.7 with 8 — the second round trip is not what bounds the launch
   // (docs/TUNING.md §8, round 3) — so 8 stays.
-  constexpr int KU = (!ROPE && !SLOT_LDS && REP <= 2) ? EKV_SPLIT_KU : (EKV_KV8 || EKV_MX ? 4 : 8);
+  constexpr int KU = (!ROPE && !SLOT_LDS && REP <= 2) ? EKV_SPLIT_KU : (EKV_G8 || EKV_MX ? 4 : 8);
   ekv_decode_stream<D, REP, ROPE, SLOT_LDS, 4, false, KU, EkvNoop, kEPL, kFMT>(a, SLOT_LDS ? s_slot : a.slot_of_pos + head_row, logits, a.t_pad,
                                                                                t0, t1, ll, h, head_row, m, l, o, nullptr, EkvNoop(), nrep, hq0);
 
@@ -196,7 +206,7 @@ __global__ void __launch_bounds__(64 * NW, (NW >= 8 ? (REP == 1 ? 2 : 1) : (SLOT
   const int l_pad = a.l_pad;   // pitch of a logits row: physical rows [0, E) (PHYS) or positions [0, T)
   // Resident rows (ekv_decode_stream.h, "load policy"): the 16-bit instances of the flagship geometry — head_dim 128, one query head
   // per KV head, slot-indexed score rows, both phase orders, 4 and 8 waves, every column count.  Every other instance keeps its code.
-  constexpr bool kResident = D == 128 && REP == 1 && PHYS && SLOT && !EKV_KV8 && !EKV_MX && !EKV_BATCH;
+  constexpr bool kResident = D == 128 && REP == 1 && PHYS && SLOT && !EKV_G8 && !EKV_MX && !EKV_BATCH;
   const int res_rows = kResident ? EKV_RESIDENT_ROWS(a.fused_order) : 0;
   // LDS: logits [REP][l_pad] | wave partials [4][REP][PS] | score rows S (Q C) [w_pad] | reduction scratch | dead-row bits
   float* s_logit = reinterpret_cast<float*>(smem);
@@ -219,7 +229,7 @@ __global__ void __launch_bounds__(64 * NW, (NW >= 8 ? (REP == 1 ? 2 : 1) : (SLOT
   // in LDS.  The tail is a latency-bound chain of block barriers that leaves HBM idle; when the workgroups of a CU are in different
   // orders, each order's tail falls under the other's stream.  Both orders produce the same bits (below), so WHICH workgroups take
   // order K may depend on where the hardware placed them.
-  constexpr bool kOrders = D == 128 && REP == 1 && !ROPE && NW == 4 && SLOT && ITEMS <= 12 && !EKV_KV8 && !EKV_MX && !EKV_BATCH;
+  constexpr bool kOrders = D == 128 && REP == 1 && !ROPE && NW == 4 && SLOT && ITEMS <= 12 && !EKV_G8 && !EKV_MX && !EKV_BATCH;
   bool order_k = false;
   if constexpr (kOrders) {
     const int om = a.fused_order & 3;

@@ -197,6 +197,17 @@ __device__ __forceinline__ void ekv_axpy32_fp4(float p, float scale, const uint4
     for (int j = 0; j < 8; ++j) o[8 * i + j] = fmaf(p, f[j], o[8 * i + j]);
   }
 }
+// o[0..16) += p * (codes * scale): half a block, the 16 codes of two words (FP8-key / MXFP4-value rows, "kv84": a lane pair per block)
+__device__ __forceinline__ void ekv_axpy16_fp4(float p, float scale, const uint2& c, float (&o)[16]) {
+  const uint32_t w[2] = {c.x, c.y};
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    float f[8];
+    ekv_fp4_widen8(w[i], scale, f);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) o[8 * i + j] = fmaf(p, f[j], o[8 * i + j]);
+  }
+}
 // 32 source elements (four 16-byte pieces) -> their block: 16 bytes of codes, the exponent byte in `e`
 __device__ __forceinline__ uint4 ekv_fp4_quant_block(const uint4* src, uint32_t& e) {
   float f[32];

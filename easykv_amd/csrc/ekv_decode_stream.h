@@ -55,6 +55,13 @@ struct EkvNoop {
 // three 8-byte loads, six registers per row in flight); K: the 32 codes widened to packed 16-bit pairs, V: to fp32 under the block's
 // scale (ekv_common.h).
 //
+// FP8-key / MXFP4-value rows (EPL = 16 like FP8, told apart by the format tag FMT = 84; plain keys, head_dim 128): the K side IS the FP8
+// rows' — codes, row scales, dot product, group sum, the appended row's K quantisation — so logits and (m, l) partials are bit for bit
+// those of an FP8 step on the same K codes.  The V plane is MXFP4's (64-byte rows, a.v_exp: four E8M0 bytes per row) read on the FP8
+// geometry: a lane's piece is 8 bytes, 16 e2m1 codes = half a block, at byte 8 * sub of the row, and lane `sub` takes exponent byte
+// sub >> 1.  The exponent words are read as MXFP4 reads them.  The appended V row: block maximum over the lane pair, 16 codes per lane,
+// the even lane stores the exponent byte.
+//
 // Load policy of the 16-bit K/V rows.  A row is read exactly once per step and the bank (> 1 GB at the flagship shape) never fits L2 or
 // the 256 MiB Infinity Cache: non-temporal loads (measured on MI355X: 5.5 -> 6.1 TB/s on the pure stream).  But step i + 1 reads the
 // rows of step i except one per head, so a fixed SHARE of the bank can stay in the Infinity Cache from step to step.  RES (the
@@ -84,11 +91,14 @@ __device__ __forceinline__ void ekv_decode_stream(const EkvAttnArgs& a, const in
   constexpr int LPR = Gm::LPR, RW = Gm::RW, LIVE = Gm::LIVE;
   constexpr bool KV8 = EPL == 16, KV4 = EPL == 32;      // (KV4: the MX geometry, one block per lane — MXFP4 and MXFP6 rows)
   constexpr bool KV6 = KV4 && FMT == 6;
-  static_assert(FMT == 0 || KV6, "format tag: 6 = MXFP6 rows (EPL = 32)");
+  constexpr bool KV84 = KV8 && FMT == 84;      // FP8 keys (everything KV8 says about K holds), MXFP4 values
+  static_assert(FMT == 0 || KV6 || KV84, "format tag: 6 = MXFP6 rows (EPL = 32), 84 = FP8 keys with MXFP4 values (EPL = 16)");
+  static_assert(!KV84 || (D == 128 && LPR == 8), "FP8-key / MXFP4-value rows: head_dim 128 (a lane pair = one 32-element V block)");
   static_assert(EPL == 8 || (KV8 && !ROPE && LIVE == LPR) || KV4, "FP8 rows: plain keys, head_dim 64 / 128");
   static_assert(!KV4 || (!ROPE && D == 128 && LPR == 4), "MXFP4 rows: plain keys, head_dim 128 (a lane = one 32-element block)");
   constexpr int ESZ = KV8 ? 1 : 2;      // bytes per stored K/V element
   constexpr int ROWB = KV6 ? 3 * D / 4 : (KV4 ? D / 2 : D * ESZ);      // bytes per stored K/V row
+  constexpr int VROWB = KV84 ? D / 2 : ROWB;      // ... of a V row where the planes differ
   constexpr bool PADDED = LIVE != LPR;      // head_dim 96: lanes sub >= LIVE of a lane group are idle (zero pieces, no loads / stores)
   constexpr int kNW = NW;
   static_assert(!(PHYS && (ROPE || SLOT_LDS)), "physical-order streaming: plain keys, global slot map");
@@ -250,16 +260,26 @@ __device__ __forceinline__ void ekv_decode_stream(const EkvAttnArgs& a, const in
       float ka = fmaxf(ekv_widen8_amax(kq[0], kf), ekv_widen8_amax(kq[1], kf + 8));
       float va = fmaxf(ekv_widen8_amax(vq[0], vf), ekv_widen8_amax(vq[1], vf + 8));
       ksn = ekv_fp8_row_scale(ekv_group_max<LPR>(ka));
-      vsn = ekv_fp8_row_scale(ekv_group_max<LPR>(va));
+      uint32_t ve = 127u;      // KV84: the exponent byte of the lane pair's V block (the MXFP4 rule over the pair's maximum)
+      if constexpr (KV84) ve = ekv_fp4_block_exp(fmaxf(va, ekv_dpp<0xB1>(va))), vsn = ekv_fp4_exp_scale(ve);
+      else vsn = ekv_fp8_row_scale(ekv_group_max<LPR>(va));
       kn = uint4{ekv_fp8_quant4(kf[0], kf[1], kf[2], kf[3], ksn), ekv_fp8_quant4(kf[4], kf[5], kf[6], kf[7], ksn),
                  ekv_fp8_quant4(kf[8], kf[9], kf[10], kf[11], ksn), ekv_fp8_quant4(kf[12], kf[13], kf[14], kf[15], ksn)};
-      vn = uint4{ekv_fp8_quant4(vf[0], vf[1], vf[2], vf[3], vsn), ekv_fp8_quant4(vf[4], vf[5], vf[6], vf[7], vsn),
-                 ekv_fp8_quant4(vf[8], vf[9], vf[10], vf[11], vsn), ekv_fp8_quant4(vf[12], vf[13], vf[14], vf[15], vsn)};
+      if constexpr (KV84)
+        vn = uint4{ekv_fp4_quant8(vf, vsn), ekv_fp4_quant8(vf + 8, vsn), 0, 0};      // (the lane's 16 codes: half a block)
+      else
+        vn = uint4{ekv_fp8_quant4(vf[0], vf[1], vf[2], vf[3], vsn), ekv_fp8_quant4(vf[4], vf[5], vf[6], vf[7], vsn),
+                   ekv_fp8_quant4(vf[8], vf[9], vf[10], vf[11], vsn), ekv_fp8_quant4(vf[12], vf[13], vf[14], vf[15], vsn)};
       reinterpret_cast<uint4*>(reinterpret_cast<uint8_t*>(a.k_w) + off)[sub] = kn;
-      reinterpret_cast<uint4*>(reinterpret_cast<uint8_t*>(a.v_w) + off)[sub] = vn;
+      if constexpr (KV84) {
+        reinterpret_cast<uint2*>(reinterpret_cast<uint8_t*>(a.v_w) + off / 2)[sub] = uint2{vn.x, vn.y};
+        if (!(sub & 1)) a.v_exp[(head_row + slot_new) * 4 + (sub >> 1)] = (uint8_t)ve;
+      } else {
+        reinterpret_cast<uint4*>(reinterpret_cast<uint8_t*>(a.v_w) + off)[sub] = vn;
+      }
       if (sub == 0) {
         a.k_scale[head_row + slot_new] = ksn;
-        a.v_scale[head_row + slot_new] = vsn;
+        if constexpr (!KV84) a.v_scale[head_row + slot_new] = vsn;
       }
     } else if constexpr (KV4) {
       // quantise the new row (rule: include/easykv_hip.h): each lane's 32 elements are one block — 16 bytes of codes + one exponent byte
@@ -308,7 +328,8 @@ __device__ __forceinline__ void ekv_decode_stream(const EkvAttnArgs& a, const in
       l[r] = l[r] * alpha + p;
 #pragma unroll
       for (int i = 0; i < EPL; ++i) o[r][i] *= alpha;
-      if constexpr (KV8) ekv_axpy16_fp8(p * vsn, vn, o[r]);
+      if constexpr (KV84) ekv_axpy16_fp4(p, vsn, uint2{vn.x, vn.y}, o[r]);
+      else if constexpr (KV8) ekv_axpy16_fp8(p * vsn, vn, o[r]);
       else if constexpr (KV6) ekv_axpy32_fp6(p, vsn, vn6, o[r]);
       else if constexpr (KV4) ekv_axpy32_fp4(p, vsn, vn, o[r]);
       else ekv_axpy8(p, vn, o[r]);
@@ -344,7 +365,7 @@ __device__ __forceinline__ void ekv_decode_stream(const EkvAttnArgs& a, const in
         const float4* v4 = reinterpret_cast<const float4*>(a.v_scale + head_row + j0);
 #pragma unroll
         for (int i = 0; i < KU / 4; ++i) {
-          const float4 kk = k4[i], vv = v4[i];
+          const float4 kk = k4[i], vv = KV84 ? float4{1.f, 1.f, 1.f, 1.f} : v4[i];      // (KV84: a.v_scale is a.v_exp — below)
           ksc[4 * i] = kk.x, ksc[4 * i + 1] = kk.y, ksc[4 * i + 2] = kk.z, ksc[4 * i + 3] = kk.w;
           vsc[4 * i] = vv.x, vsc[4 * i + 1] = vv.y, vsc[4 * i + 2] = vv.z, vsc[4 * i + 3] = vv.w;
         }
@@ -352,9 +373,27 @@ __device__ __forceinline__ void ekv_decode_stream(const EkvAttnArgs& a, const in
 #pragma unroll
         for (int u = 0; u < KU; ++u) {
           ksc[u] = a.k_scale[head_row + min(j0 + u, a.cap - 1)];
-          vsc[u] = a.v_scale[head_row + min(j0 + u, a.cap - 1)];
+          vsc[u] = KV84 ? 1.f : a.v_scale[head_row + min(j0 + u, a.cap - 1)];
         }
       }
+    }
+    if constexpr (KV84 && PHYS) {
+      // the V exponent words of the KU consecutive rows, as the MXFP4 stream reads them (same bound); lane `sub` holds half of block
+      // sub >> 1
+      uint32_t vw[KU];
+      if (j0 + KU <= a.cap) {
+        const uint4* v4 = reinterpret_cast<const uint4*>(a.v_exp + (head_row + j0) * 4);
+#pragma unroll
+        for (int i = 0; i < KU / 4; ++i) {
+          const uint4 vv = v4[i];
+          vw[4 * i] = vv.x, vw[4 * i + 1] = vv.y, vw[4 * i + 2] = vv.z, vw[4 * i + 3] = vv.w;
+        }
+      } else {
+#pragma unroll
+        for (int u = 0; u < KU; ++u) vw[u] = reinterpret_cast<const uint32_t*>(a.v_exp)[head_row + min(j0 + u, a.cap - 1)];
+      }
+#pragma unroll
+      for (int u = 0; u < KU; ++u) vsc[u] = ekv_fp4_exp_scale((vw[u] >> (8 * (sub >> 1))) & 0xFFu);
     }
     if constexpr (KV4 && PHYS) {
       // consecutive physical rows: their exponent words (4 bytes per row) as KU / 4 16-byte loads per plane, under the bound of the FP8
@@ -418,10 +457,11 @@ __device__ __forceinline__ void ekv_decode_stream(const EkvAttnArgs& a, const in
       const int jj = j < t1 ? j : t1 - 1;
       const int row = PHYS ? jj : (SLOT_LDS ? s_slot[jj - t0] : (j < t1 ? cur[u] : last_slot));
       const char* kp = reinterpret_cast<const char*>(a.k) + (head_row + row) * ROWB;
-      const char* vp = reinterpret_cast<const char*>(a.v) + (head_row + row) * ROWB;
+      const char* vp = reinterpret_cast<const char*>(a.v) + (head_row + row) * VROWB;
       if constexpr (KV8 && !PHYS) {      // rows through the slot map: one scale per row (the lanes of a group read the same word)
         ksc[u] = a.k_scale[head_row + row];
-        vsc[u] = a.v_scale[head_row + row];
+        if constexpr (KV84) vsc[u] = ekv_fp4_exp_scale(a.v_exp[(head_row + row) * 4 + (sub >> 1)]);
+        else vsc[u] = a.v_scale[head_row + row];
       }
       if constexpr (KV4 && !PHYS) {      // rows through the slot map: this lane's exponent byte of each row
         ksc[u] = ekv_fp4_exp_scale(a.k_exp[(head_row + row) * 4 + sub]);
@@ -431,6 +471,10 @@ __device__ __forceinline__ void ekv_decode_stream(const EkvAttnArgs& a, const in
       if constexpr (KV6) {
         kr6[u] = ekv_fp6_load_block(kp, sub);
         vr6[u] = ekv_fp6_load_block(vp, sub);
+      } else if constexpr (KV84) {      // 16 K codes, and the 8 bytes (16 codes) of the V row at byte 8 * sub
+        kr[u] = __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const ekv_u4*>(kp) + sub));
+        const ekv_u2 w = __builtin_nontemporal_load(reinterpret_cast<const ekv_u2*>(vp) + sub);
+        vr[u] = uint4{w[0], w[1], 0, 0};
       } else if (live_lane) {
         kr[u] = __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const ekv_u4*>(kp) + sub));
         vr[u] = __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const ekv_u4*>(vp) + sub));
@@ -450,7 +494,7 @@ __device__ __forceinline__ void ekv_decode_stream(const EkvAttnArgs& a, const in
         if ((dead8 >> u) & 1u) {
           vr[u] = uint4{0, 0, 0, 0};
           if constexpr (KV6) vr6[u] = ekv_u6{0, 0, 0, 0, 0, 0};
-          if constexpr (KV8) vsc[u] = 0.f;
+          if constexpr (KV8) vsc[u] = KV84 ? 1.f : 0.f;      // (KV84: zero codes under scale 1, as MXFP4)
           if constexpr (KV4) vsc[u] = 1.f;      // (zero codes under a finite scale)
         }
     }
@@ -516,7 +560,8 @@ __device__ __forceinline__ void ekv_decode_stream(const EkvAttnArgs& a, const in
       for (int u = 0; u < KU; ++u) {
         const float p = exp2f((s[u] - mn) * EKV_LOG2E);
         l[r] += p;
-        if constexpr (KV8) ekv_axpy16_fp8(p * vsc[u], vr[u], o[r]);
+        if constexpr (KV84) ekv_axpy16_fp4(p, vsc[u], uint2{vr[u].x, vr[u].y}, o[r]);
+        else if constexpr (KV8) ekv_axpy16_fp8(p * vsc[u], vr[u], o[r]);
         else if constexpr (KV6) ekv_axpy32_fp6(p, vsc[u], vr6[u], o[r]);
         else if constexpr (KV4) ekv_axpy32_fp4(p, vsc[u], vr[u], o[r]);
         else ekv_axpy8(p, vr[u], o[r]);

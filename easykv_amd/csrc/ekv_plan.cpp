@@ -656,12 +656,12 @@ int ekv_plan_step(const ekv_bank* bank, const ekv_step* step, EkvStepPlan* P) {
 // ---- one call ----------------------------------------------------------------------------------------------------------------------
 // What each row format takes, beyond decode steps (q_len == 1) on plain keys — all a quantised bank serves: its head_dims (0: none) and
 // the largest GQA factor.  kv8: head_dim 64 / 128.  kv4: head_dim 128 (a lane's 16-byte piece = one 32-element block), GQA factors up
-// to 4 (32 output floats per lane and head).  kv6: the geometry of kv4, so its shapes.  resolve_call refuses by it, and the bank conversions (ekv_abi.hip) ask for the head_dim.
+// to 4 (32 output floats per lane and head).  kv6: the geometry of kv4, so its shapes.  kv84: head_dim 128 (its V blocks), GQA factors as kv8 takes them (its geometry).  resolve_call refuses by it, and the bank conversions (ekv_abi.hip) ask for the head_dim.
 namespace {
 struct RowsRule {
   int32_t head_dims[2], max_rep;
 };
-const RowsRule kRowsRules[] = {/* kv16 */ {{0, 0}, 1 << 30}, /* kv8 */ {{64, 128}, 1 << 30}, /* kv4 */ {{128, 0}, 4}, /* kv6 */ {{128, 0}, 4}};
+const RowsRule kRowsRules[] = {/* kv16 */ {{0, 0}, 1 << 30}, /* kv8 */ {{64, 128}, 1 << 30}, /* kv4 */ {{128, 0}, 4}, /* kv6 */ {{128, 0}, 4}, /* kv84 */ {{128, 0}, 1 << 30}};
 }  // namespace
 bool ekv_rows_head_dim(EkvRows rows, int head_dim) {
   const RowsRule& rule = kRowsRules[rows];
@@ -673,7 +673,7 @@ bool ekv_rows_head_dim(EkvRows rows, int head_dim) {
 //
 // The element type only picks the kernel instances: a bf16 step is planned as the fp16 step.  RoPE-on-read keeps hi / lo fp16 planes
 // of the rotated keys and queries (ekv_attn_wide.inc, ekv_rope_q_kernel) and has no bf16 build.
-// Quantised rows (kv8, kv4, kv6): the code planes stand where the 16-bit rows were (bank->k / bank->v are not read; a missing plane is an
+// Quantised rows (kv8, kv4, kv6, kv84): the code planes stand where the 16-bit rows were (bank->k / bank->v are not read; a missing plane is an
 // argument error before anything else of the call is read), and the plan is that of the 16-bit step of the same shape (the scorers
 // read logits and partials, never a K/V element, so splits, launches and workspace carry over), run on that format's instances of the
 // two decode attention kernels — which is all a quantised bank has: decode steps, plain keys, and the shapes of kRowsRules.

@@ -39,7 +39,7 @@ class StepPlan:
     two_pass: int = 0           # scored chunk steps: 0 auto, 1 force the two-pass kernels, -1 force one pass
 
 
-# The row formats of a quantised bank, by ``kv_quant`` (include/easykv_hip.h, "kv8" / "kv4" / "kv6"): everything the bank, the batch and the
+# The row formats of a quantised bank, by ``kv_quant`` (include/easykv_hip.h, "kv8" / "kv4" / "kv6" / "kv84"): everything the bank, the batch and the
 # driver (api.py) need to know about one.  rows: the calls' prefix (ekv_<rows>_*); desc: the descriptor of the four planes; planes:
 # (attribute, trailing shape at head_dim d, dtype, fill) in the descriptor's order — rows that were never written keep code 0 and
 # scale 1 (exponent byte 127), so every scale of the bank is finite whatever the kernels prefetch; head_dims / max_rep: the shapes the
@@ -57,13 +57,19 @@ ROW_FORMATS = {
                   planes=(("k6", lambda d: (3 * d // 4,), torch.uint8, 0), ("v6", lambda d: (3 * d // 4,), torch.uint8, 0),
                           ("k_exp", lambda d: (d // 32,), torch.uint8, 127), ("v_exp", lambda d: (d // 32,), torch.uint8, 127)),
                   head_dims=(128,), max_rep=4, pair_bytes=lambda d: 3 * d // 2 + d // 16),
+    # FP8 keys (the "fp8" K planes) with MXFP4 values (the "mxfp4" V planes): the eviction decisions of FP8 rows at MXFP6's bytes
+    "fp8_mxfp4": dict(kind="fp8_mxfp4", rows="kv84", desc=_lib.Kv84, label="FP8-key / MXFP4-value", method="quantize_fp8_mxfp4",
+                      stored="FP8 key codes with per-row scales and MXFP4 value codes with block exponents",
+                      planes=(("k8", lambda d: (d,), torch.uint8, 0), ("v4", lambda d: (d // 2,), torch.uint8, 0),
+                              ("k_scale", lambda d: (), torch.float32, 1), ("v_exp", lambda d: (d // 32,), torch.uint8, 127)),
+                      head_dims=(128,), max_rep=None, pair_bytes=lambda d: 3 * d // 2 + 4 + d // 32),
 }
 
 
 def row_format(kind, what="kv_quant"):
     """The entry of ROW_FORMATS for ``kind``, or None for None (16-bit rows); anything else is a ValueError naming ``what``."""
     if kind is not None and kind not in ROW_FORMATS:
-        raise ValueError(f"{what} must be None or 'fp8' / 'mxfp4', not {kind!r}; 'mxfp6' is accepted as well")
+        raise ValueError(f"{what} must be None or 'fp8' / 'mxfp4', not {kind!r}; 'mxfp6' is accepted as well, and 'fp8_mxfp4'")
     return ROW_FORMATS.get(kind)
 
 
@@ -138,13 +144,14 @@ class KVBank:
     # library's default, 0 = every K/V load non-temporal — what a caller sets whose process streams more than the Infinity Cache holds
     # between two steps (easykv_amd.api: a model's weights)
     resident_bytes = None
-    kv_quant = None      # quantize(): "fp8" / "mxfp4" / "mxfp6" (ROW_FORMATS; _fmt is the entry, _desc the descriptor of the four planes)
+    kv_quant = None      # quantize(): "fp8" / "mxfp4" / "mxfp6" / "fp8_mxfp4" (ROW_FORMATS; _fmt is the entry, _desc the descriptor of the four planes)
 
     def __init__(self, n_layers, n_q_heads, n_kv_heads, head_dim, cap, device="cuda", scored=True, dtype=torch.float16, kv_quant=None):
         """``kv_quant='fp8'``: the bank is created holding FP8 planes only (see :meth:`quantize_fp8`); the 16-bit K/V rows are never
         allocated.  Such a bank is filled by decode steps or, as one sequence of a :class:`KVBankBatch`, by ``adopt()``.
         ``kv_quant='mxfp4'``: likewise with MXFP4 planes only (see :meth:`quantize_mxfp4`; head_dim 128, GQA factors up to 4).
-        ``kv_quant='mxfp6'``: likewise with MXFP6 planes only (see :meth:`quantize_mxfp6`; the same shapes)."""
+        ``kv_quant='mxfp6'``: likewise with MXFP6 planes only (see :meth:`quantize_mxfp6`; the same shapes).
+        ``kv_quant='fp8_mxfp4'``: likewise with FP8 key planes and MXFP4 value planes (see :meth:`quantize_fp8_mxfp4`; head_dim 128)."""
         if dtype not in _lib.DTYPE_CODES:
             raise ValueError(f"KVBank dtype must be torch.float16 or torch.bfloat16, not {dtype}")
         fmt = row_format(kv_quant, "KVBank kv_quant")
@@ -294,7 +301,7 @@ class KVBank:
                                 f"{self._fmt['stored']}, which only decode steps (q_len == 1, plain keys) read and append to")
 
     def quantize(self, kind):
-        """Convert the live bank in place to the row format ``kind`` ('fp8' / 'mxfp4' / 'mxfp6'): codes and scales / exponents are written at the
+        """Convert the live bank in place to the row format ``kind`` ('fp8' / 'mxfp4' / 'mxfp6' / 'fp8_mxfp4'): codes and scales / exponents are written at the
         rows' physical indices (slot map, free list and score rows carry over as they are, in either layout), the 16-bit K/V tensors
         are released, ``kv_quant`` is ``kind`` and ``attend`` / ``step_info`` / ``step_plan`` go to that format's calls.  From here on
         the bank serves decode steps only: chunk steps, ``load_rows``, ``set_rope`` and the row moves raise :class:`EkvError`.  A bank
@@ -338,6 +345,12 @@ class KVBank:
         ``v6`` / ``k_exp`` / ``v_exp``; 200 bytes per row pair), head_dim 128 and GQA factors up to 4."""
         return self.quantize("mxfp6")
 
+    def quantize_fp8_mxfp4(self):
+        """:meth:`quantize` to FP8 keys with MXFP4 values: the K planes of :meth:`quantize_fp8` (``k8`` / ``k_scale``) and the V planes of
+        :meth:`quantize_mxfp4` (``v4`` / ``v_exp``), 200 bytes per row pair at head_dim 128, the only head_dim; every GQA factor FP8
+        rows take.  Eviction reads logits only, so the bank evicts exactly what its FP8 twin evicts."""
+        return self.quantize("fp8_mxfp4")
+
     def _planes(self, fmt):
         """Allocate the planes of ``fmt`` as the bank's attributes; returns their descriptor."""
         shape = (self.n_layers, self.n_kv_heads, self.cap)
@@ -364,7 +377,8 @@ class KVBank:
 
     def kv_bytes(self) -> int:
         """Bytes held for the K/V rows: 16-bit rows, FP8 codes + row scales (``2 * head_dim + 8`` per row pair), or MXFP4 codes +
-        block exponents (``head_dim + head_dim / 16``: 136 at head_dim 128; MXFP6: ``3 * head_dim / 2 + head_dim / 16``, 200)."""
+        block exponents (``head_dim + head_dim / 16``: 136 at head_dim 128; MXFP6: ``3 * head_dim / 2 + head_dim / 16``, 200; FP8 keys with MXFP4
+        values: ``3 * head_dim / 2 + 4 + head_dim / 32``, 200)."""
         pair = 4 * self.head_dim if self._fmt is None else self._fmt["pair_bytes"](self.head_dim)
         return self.n_layers * self.n_kv_heads * self.cap * pair
 
@@ -795,7 +809,8 @@ class KVBankBatch:
         """``kv_quant='fp8'``: the shared bank holds FP8 planes only from the start (the 16-bit rows of ``n_seq`` sequences are never
         allocated); its sequences are filled by :meth:`adopt` from banks quantised by :meth:`KVBank.quantize_fp8`.
         ``kv_quant='mxfp4'``: likewise with MXFP4 planes, filled from banks quantised by :meth:`KVBank.quantize_mxfp4`.
-        ``kv_quant='mxfp6'``: likewise with MXFP6 planes (:meth:`KVBank.quantize_mxfp6`)."""
+        ``kv_quant='mxfp6'``: likewise with MXFP6 planes (:meth:`KVBank.quantize_mxfp6`).
+        ``kv_quant='fp8_mxfp4'``: likewise with FP8 key and MXFP4 value planes (:meth:`KVBank.quantize_fp8_mxfp4`)."""
         if not 1 <= n_seq <= _lib.MAX_SEQS:
             raise ValueError(f"a decode batch holds 1..{_lib.MAX_SEQS} sequences, not {n_seq}")
         self.n_seq, self.n_layers = n_seq, n_layers
@@ -835,6 +850,10 @@ class KVBankBatch:
         """:meth:`quantize` to MXFP6 rows (:meth:`KVBank.quantize_mxfp6`: head_dim 128, GQA factors up to 4)."""
         return self.quantize("mxfp6")
 
+    def quantize_fp8_mxfp4(self):
+        """:meth:`quantize` to FP8 keys with MXFP4 values (:meth:`KVBank.quantize_fp8_mxfp4`: head_dim 128)."""
+        return self.quantize("fp8_mxfp4")
+
     def _quant_call(self, what):
         """(the batched call `what` of this bank's row format, its leading descriptor arguments), as the bank resolved them."""
         return self.bank._calls[True, what], self.bank._desc_ref
@@ -847,7 +866,7 @@ class KVBankBatch:
         """Sequence ``i`` takes over the state of ``src``, a bank of this batch's layer count and head shape that one sequence was
         prefilled on alone: K/V rows at their physical indices, slot maps, score rows (ordered layout), lengths and extents.  The
         rows behind ``src.cap`` keep this bank's own free list, so a shorter ``src.cap`` is fine.  A quantised batch takes a quantised
-        source of the same kind (codes and row scales / block exponents are copied as they are); 16-bit, FP8, MXFP4 and MXFP6 rows do not mix."""
+        source of the same kind (codes and row scales / block exponents are copied as they are); 16-bit, FP8, MXFP4, MXFP6 and FP8-key / MXFP4-value rows do not mix."""
         b = self.bank
         if (src.n_layers, src.n_q_heads, src.n_kv_heads, src.head_dim, src.dtype) != (self.n_layers, b.n_q_heads, b.n_kv_heads, b.head_dim, b.dtype) \
                 or src.cap > b.cap or not 0 <= i < self.n_seq:

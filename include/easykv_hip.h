@@ -406,6 +406,47 @@ int ekv_kv6_step_attend(const ekv_bank *bank, const ekv_step *step, int32_t dtyp
                         const void *k_new, const void *v_new, void *out, int32_t *evict_ids, const float *rope_cos,
                         const float *rope_sin, void *workspace, size_t workspace_bytes, void *stream);
 
+/* FP8 keys with MXFP4 values ("kv84"; ABI 8, additive; head_dim 128).  A bank's K/V rows may be held as
+ *
+ *   k_codes   uint8 [n_layers][n_kv_heads][cap][head_dim]        and   k_scale   fp32  [n_layers][n_kv_heads][cap]
+ *   v_codes   uint8 [n_layers][n_kv_heads][cap][head_dim / 2]    and   v_exp     uint8 [n_layers][n_kv_heads][cap][head_dim / 32]
+ *
+ * — head_dim + 4 bytes of K and head_dim / 2 + head_dim / 32 bytes of V per row: 200 per K+V row pair at head_dim 128, what kv6 takes,
+ * against 264 (kv8) and 136 (kv4).  The K planes follow the quantisation rule of kv8 ("FP8 K/V storage" above: layout, rule and scale
+ * of ekv_kv8's k_codes / k_scale), the V planes the rule of kv4 ("MXFP4 K/V storage": layout, packing, rule and exponent of ekv_kv4's
+ * v_codes / v_exp); neither is restated here.  The eviction scores of a step are computed from its logits alone, so a kv84 bank takes
+ * the eviction decisions of the kv8 bank with the same K planes, exactly; the V format touches the output only.  What is stored is
+ * what is attended, for both planes.  Rows never move, as for kv8 / kv4.
+ *
+ * The descriptor carries the four planes; bank->k / bank->v are NOT read by the kv84 step calls (they may be NULL). */
+typedef struct ekv_kv84 {
+  void *k_codes, *v_codes;
+  float *k_scale;
+  uint8_t *v_exp;
+} ekv_kv84;
+
+/* Bank conversion and its inverse: the arguments and contracts of ekv_kv8_quantize / ekv_kv8_dequantize and of the kv4 pair
+ * (out_dtype EKV_DTYPE_F32 is exact: code * scale for K, code * 2^e for V).  head_dim != 128 is EKV_E_UNSUPPORTED. */
+int ekv_kv84_quantize(const ekv_bank *bank, const ekv_kv84 *kv84, int32_t dtype, int32_t layer_begin, int32_t layer_count,
+                      int32_t extent, void *stream);
+int ekv_kv84_dequantize(const ekv_bank *bank, const ekv_kv84 *kv84, int32_t out_dtype, int32_t layer_begin, int32_t layer_count,
+                        int32_t extent, void *k_out, void *v_out, void *stream);
+
+/* Decode steps on a kv84 bank: the ekv_kv8_step_* signatures with the kv84 descriptor — q_len == 1 with plain keys at head_dim 128,
+ * the GQA factors a kv8 step takes, fp16 / bf16 q, k_new, v_new and out, every policy and phase combination of the 16-bit decode
+ * step — planned exactly as the 16-bit step of that shape, fused_order 0.  The kv84 builds run on the geometry of the kv8 builds (a row
+ * is an 8-lane group, 16 elements per lane) and their K side is the kv8 builds' arithmetic: logits, softmax partials, scores and
+ * victims are bit for bit those of a kv8 step on the same K planes.  A lane's V piece is half a block (16 codes) under the block's
+ * exponent; the appended row's K is quantised by the kv8 rule, its V by the kv4 rule (block maximum over the lane pair).
+ * EKV_E_UNSUPPORTED from the dry run, before anything is launched: q_len > 1, rope_on_read, head_dim != 128.  A missing plane is
+ * EKV_E_ARG.  The row moves do not serve kv84 banks; the batch form is ekv_kv84_batch_* below. */
+int ekv_kv84_step_check(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const ekv_kv84 *kv84);
+int ekv_kv84_step_info(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const ekv_kv84 *kv84, int32_t *info, int32_t n_info);
+size_t ekv_kv84_workspace_bytes(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const ekv_kv84 *kv84);
+int ekv_kv84_step_attend(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const ekv_kv84 *kv84, const void *q,
+                         const void *k_new, const void *v_new, void *out, int32_t *evict_ids, const float *rope_cos,
+                         const float *rope_sin, void *workspace, size_t workspace_bytes, void *stream);
+
 /* Batched decode steps (ABI 8, additive): ONE call, and one launch per kernel kind, serves n_seq sequences whose caches have
  * different lengths and different eviction geometry.  Each entry of the table names the bank layer it attends and carries what
  * ekv_step holds per step; entry i owns row i of the call's tensors.  The layers of a table need not be contiguous or ordered, so
@@ -513,6 +554,21 @@ size_t ekv_kv6_batch_workspace_bytes(const ekv_bank *bank, const ekv_step *step,
 int ekv_kv6_batch_step_attend(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const ekv_kv6 *kv6, const ekv_seq *seqs,
                               int32_t n_seq, const void *q, const void *k_new, const void *v_new, void *out, int32_t *evict_ids,
                               void *workspace, size_t workspace_bytes, void *stream);
+
+/* Batched decode steps on a kv84 bank ("kv84 batches"; ABI 8, additive): the ekv_kv8_batch_* signatures with the kv84 descriptor, with
+ * the acceptance (head_dim 128 only), the planning (the 16-bit batched call of the same table, fused_order 0) and the refusals of the
+ * kv8 batch calls: EKV_E_UNSUPPORTED from the dry run with nothing launched and 0 workspace bytes, EKV_E_ARG for a NULL descriptor or
+ * plane, a dtype other than EKV_DTYPE_F16 / _BF16 and a bad table.  Per entry the arithmetic is that of ekv_kv84_step_attend of the
+ * entry's geometry under the same n_split. */
+int ekv_kv84_batch_step_check(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const ekv_kv84 *kv84, const ekv_seq *seqs,
+                              int32_t n_seq);
+int ekv_kv84_batch_step_info(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const ekv_kv84 *kv84, const ekv_seq *seqs,
+                             int32_t n_seq, int32_t *info, int32_t n_info);
+size_t ekv_kv84_batch_workspace_bytes(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const ekv_kv84 *kv84,
+                                      const ekv_seq *seqs, int32_t n_seq);
+int ekv_kv84_batch_step_attend(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const ekv_kv84 *kv84, const ekv_seq *seqs,
+                               int32_t n_seq, const void *q, const void *k_new, const void *v_new, void *out, int32_t *evict_ids,
+                               void *workspace, size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }

@@ -2,7 +2,7 @@
 """Device-assembly identity of two source trees:  tools/isa_identity.py PARENT_TREE NEW_TREE [--work DIR] [--jobs N] [--reuse]
 
 For every object of each tree's easykv_amd/_build.objects() — plus, in an older tree that still splits what it links over several
-lists, its all_objects() / extra_objects() / batch_kv4_objects(), and this tree's added_objects() — the device side is compiled to assembly (hipcc <the build's flags>
+lists, its all_objects() / extra_objects() / batch_kv4_objects(), and this tree's added_objects() / later_objects() — the device side is compiled to assembly (hipcc <the build's flags>
 --offload-device-only -S), the compilation-unit id (__hip_cuid_<hex>) is replaced by a constant, and the texts are compared: per
 object, and per kernel symbol where an object has no partner of its name or differs (a file that was split: its kernels are looked up
 in whichever object of the other tree holds them; local label numbers, which count the functions of a file, are dropped for that).
@@ -33,7 +33,7 @@ def assemble(tree, work, jobs, reuse):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     os.makedirs(work, exist_ok=True)
     todo, out = [], {}
-    for name, args in getattr(b, "all_objects", b.objects)() + getattr(b, "extra_objects", list)() + getattr(b, "batch_kv4_objects", list)() + getattr(b, "added_objects", list)():      # (objects() + added_objects() in this tree)
+    for name, args in getattr(b, "all_objects", b.objects)() + getattr(b, "extra_objects", list)() + getattr(b, "batch_kv4_objects", list)() + getattr(b, "added_objects", list)() + getattr(b, "later_objects", list)():      # (objects() + added_objects() + later_objects() in this tree)
         if args[-1].endswith(".cpp"):
             out[name] = None
             continue

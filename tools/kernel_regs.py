@@ -8,7 +8,7 @@ name = os.path.basename(sys.argv[1])
 name = name[:-4] if name.endswith(".hip") else name
 defs = [a for a in sys.argv[2:] if a.startswith("-D")]
 filt = [a for a in sys.argv[2:] if not a.startswith("-D")]
-args = dict(_build.objects() + _build.added_objects()).get(name)
+args = dict(_build.objects() + _build.added_objects() + _build.later_objects()).get(name)
 if args is None:
     sys.exit(f"no object named {name}: see easykv_amd/csrc/ekv_instances.def")
 cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-c"] + defs + args + ["-o", "/tmp/_regs.o",
