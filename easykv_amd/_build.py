@@ -19,13 +19,13 @@ LATER_MANIFEST = os.path.join(CSRC, "ekv_instances_later.def")      # (see later
 
 
 def _tags(*words):
-    """File-name tags of an instance's words, in the order the object names have always had: batch, kv8 / kv4 / kv6 / kv84, bf16."""
-    return "".join("_" + w for w in ("batch", "kv8", "kv4", "kv6", "kv84", "bf16") if w in words)
+    """File-name tags of an instance's words, in the order the object names have always had: batch, kv8 / kv4 / kv6 / kv84 / kv164, bf16."""
+    return "".join("_" + w for w in ("batch", "kv8", "kv4", "kv6", "kv84", "kv164", "bf16") if w in words)
 
 
 def _on(*words):
-    sw = {"bf16": "EKV_BF16", "kv8": "EKV_KV8", "kv4": "EKV_KV4", "kv6": "EKV_KV6", "kv84": "EKV_KV84", "batch": "EKV_BATCH"}
-    return [f"-D{sw[w]}=1" for w in ("kv8", "kv4", "kv6", "kv84", "batch", "bf16") if w in words]
+    sw = {"bf16": "EKV_BF16", "kv8": "EKV_KV8", "kv4": "EKV_KV4", "kv6": "EKV_KV6", "kv84": "EKV_KV84", "kv164": "EKV_KV164", "batch": "EKV_BATCH"}
+    return [f"-D{sw[w]}=1" for w in ("kv8", "kv4", "kv6", "kv84", "kv164", "batch", "bf16") if w in words]
 
 
 # family of a manifest line -> (its kernel source, object name, -D switches), all from the line's words
@@ -96,7 +96,7 @@ def later_instances():
 
 
 def later_objects():
-    """(object name, hipcc arguments) of the instances of ekv_instances_later.def (the kv84 decode instances first)."""
+    """(object name, hipcc arguments) of the instances of ekv_instances_later.def (the kv84 decode instances, then the kv164 ones)."""
     return _instance_objects(later_instances())
 
 

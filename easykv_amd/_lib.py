@@ -30,7 +30,7 @@ STEP_CALLS = ("step_check", "step_info", "workspace_bytes", "step_attend")
 
 def step_call_name(rows, batch, what):
     """Name of the call `what` (one of STEP_CALLS) of the step family for a bank's row format — None (16-bit rows: the _typed calls),
-    "kv8", "kv4", "kv6" or "kv84" — and a uniform step or a batched one (include/easykv_hip.h)."""
+    "kv8", "kv4", "kv6", "kv84" or "kv164" — and a uniform step or a batched one (include/easykv_hip.h)."""
     if rows is None and not batch:
         return "ekv_" + what + "_typed"
     return "ekv_" + (rows + "_" if rows else "") + ("batch_" if batch else "") + what
@@ -40,8 +40,9 @@ def step_call_name(rows, batch, what):
 EXPORTS = ("ekv_abi_version", "ekv_strerror", "ekv_workspace_bytes", "ekv_step_plan", "ekv_bank_reset", "ekv_state_init",
            "ekv_step_attend", "ekv_gather_ordered", "ekv_scatter_rows", "ekv_compact_inplace", "ekv_step_check", "ekv_step_info",
            "ekv_rows_to_slots", "ekv_rows_to_order", "ekv_kv8_quantize", "ekv_kv8_dequantize", "ekv_kv4_quantize", "ekv_kv4_dequantize",
-           "ekv_kv6_quantize", "ekv_kv6_dequantize", "ekv_set_resident_bytes", "ekv_step_resident_rows", "ekv_kv84_quantize", "ekv_kv84_dequantize") + tuple(
-               step_call_name(rows, batch, what) for rows in (None, "kv8", "kv4", "kv6", "kv84") for batch in (False, True) for what in STEP_CALLS)
+           "ekv_kv6_quantize", "ekv_kv6_dequantize", "ekv_set_resident_bytes", "ekv_step_resident_rows", "ekv_kv84_quantize", "ekv_kv84_dequantize",
+           "ekv_kv164_quantize", "ekv_kv164_dequantize") + tuple(
+               step_call_name(rows, batch, what) for rows in (None, "kv8", "kv4", "kv6", "kv84", "kv164") for batch in (False, True) for what in STEP_CALLS)
 
 
 class Bank(C.Structure):
@@ -69,6 +70,11 @@ class Kv6(C.Structure):
 class Kv84(C.Structure):
     """ekv_kv84: FP8 key codes with fp32 row scales and MXFP4 value codes with E8M0 block exponents (include/easykv_hip.h, "kv84")."""
     _fields_ = [("k_codes", C.c_void_p), ("v_codes", C.c_void_p), ("k_scale", C.c_void_p), ("v_exp", C.c_void_p)]
+
+
+class Kv164(C.Structure):
+    """ekv_kv164: MXFP4 value codes with E8M0 block exponents; the keys are the bank's 16-bit rows (include/easykv_hip.h, "kv164")."""
+    _fields_ = [("v_codes", C.c_void_p), ("v_exp", C.c_void_p)]
 
 
 class Step(C.Structure):
@@ -126,7 +132,7 @@ def load():
     lib.ekv_step_resident_rows.argtypes = [C.POINTER(Bank), C.POINTER(Step), i32]
     # the step family: (bank, step, dtype[, descriptor][, table, entries]) + what the call itself takes
     tails = {"step_check": [], "workspace_bytes": [], "step_info": [C.POINTER(C.c_int32), C.c_int32]}
-    for rows, desc in ((None, None), ("kv8", Kv8), ("kv4", Kv4), ("kv6", Kv6), ("kv84", Kv84)):
+    for rows, desc in ((None, None), ("kv8", Kv8), ("kv4", Kv4), ("kv6", Kv6), ("kv84", Kv84), ("kv164", Kv164)):
         for batch in (False, True):
             head = [C.POINTER(Bank), C.POINTER(Step), i32] + ([C.POINTER(desc)] if desc else []) + ([C.POINTER(Seq), i32] if batch else [])
             tails["step_attend"] = [vp] * (6 if batch else 8) + [C.c_size_t, vp]      # (a batch has no rope tables)
@@ -135,6 +141,7 @@ def load():
         if desc:
             getattr(lib, f"ekv_{rows}_quantize").argtypes = [C.POINTER(Bank), C.POINTER(desc), i32, i32, i32, i32, vp]
             getattr(lib, f"ekv_{rows}_dequantize").argtypes = [C.POINTER(Bank), C.POINTER(desc), i32, i32, i32, i32, vp, vp, vp]
+    lib.ekv_kv164_dequantize.argtypes = [C.POINTER(Bank), C.POINTER(Kv164), i32, i32, i32, i32, vp, vp]      # (V only: one output)
     for name in EXPORTS:
         if name != "ekv_strerror":
             getattr(lib, name).restype = C.c_size_t if "workspace_bytes" in name else C.c_int

@@ -131,7 +131,8 @@ class BudgetedKVCache:
     def kv_quant(self):
         """None, "fp8" once the bank's K/V rows are FP8 codes with per-row scales (KVBank.quantize_fp8), or "mxfp4" once they are
         MXFP4 codes with block exponents (KVBank.quantize_mxfp4), or "mxfp6" (MXFP6 codes, KVBank.quantize_mxfp6), or "fp8_mxfp4"
-        (FP8 keys with MXFP4 values, KVBank.quantize_fp8_mxfp4)."""
+        (FP8 keys with MXFP4 values, KVBank.quantize_fp8_mxfp4), or "k16_mxfp4" (the 16-bit keys with MXFP4 values,
+        KVBank.quantize_k16_mxfp4)."""
         return self.bank.kv_quant
 
     def kv_bytes(self) -> int:
@@ -378,7 +379,8 @@ class _Run:
         # codes + one fp32 scale per row, 2 * head_dim + 8 bytes per row pair), or "mxfp4" (e2m1 codes + one E8M0 exponent per 32 elements,
         # 136 bytes per row pair; no batched form in generate_batch), or "mxfp6" (e2m3 codes, 32 per 24-byte block, + the same exponents: 200 bytes
         # per row pair; batched as well), or "fp8_mxfp4" (the FP8 keys with the MXFP4 values: 200 bytes per row pair and FP8's eviction
-        # decisions; head_dim 128, batched as well).  The shapes each takes are engine.ROW_FORMATS'.  kv_dtype keeps meaning the 16-bit
+        # decisions; head_dim 128, batched as well), or "k16_mxfp4" (the 16-bit keys, untouched, with the MXFP4 values: 324 bytes per row pair
+        # and exactly the eviction decisions of the unquantised run; head_dim 128, every GQA factor, batched as well).  The shapes each takes are engine.ROW_FORMATS'.  kv_dtype keeps meaning the 16-bit
         # type of q / k / v / out.
         self.kv_quant = kv_quant = cfg.get("kv_quant", None)
         shard = getattr(model, "layer_shard", None)
@@ -803,7 +805,8 @@ def generate_batch(self, input_ids_list, generation_config, kv_mode="encoding", 
     decoded strings, in prompt order, and prints each sequence's budget line as ``generate`` prints it.
     ``generation_config['kv_quant'] = 'fp8'``: every prompt's bank is quantised right after its own 16-bit prefill (as ``generate``
     does at the prefill -> decode boundary) and the decode phase runs one FP8 batched step per layer and token.  ``'mxfp6'``: the same
-    on MXFP6 rows (head_dim 128, GQA factors up to 4); ``'fp8_mxfp4'``: the same on FP8 keys with MXFP4 values (head_dim 128).
+    on MXFP6 rows (head_dim 128, GQA factors up to 4); ``'fp8_mxfp4'``: the same on FP8 keys with MXFP4 values (head_dim 128);
+    ``'k16_mxfp4'``: the same on 16-bit keys with MXFP4 values (head_dim 128; the evictions of the unquantised run).
     ``'mxfp4'`` is refused here.
 
     Sampling: ``torch.multinomial`` draws for all live sequences at once, so with ``temperature`` / ``top_p`` that leave more than
@@ -827,7 +830,7 @@ def generate_batch(self, input_ids_list, generation_config, kv_mode="encoding", 
     eos, dev, max_new_tokens = set(int(e) for e in run.eos_token_ids), run.dev, run.max_new_tokens
 
     # ---- every prompt alone, through the single-sequence prefill; its bank becomes one sequence of the batch
-    # (kv_quant='fp8' / 'mxfp6' / 'fp8_mxfp4': a prompt's bank is quantised right after its own prefill, so at most one 16-bit bank is alive at a time, and the
+    # (kv_quant='fp8' / 'mxfp6' / 'fp8_mxfp4' / 'k16_mxfp4': a prompt's bank is quantised right after its own prefill, so at most one 16-bit bank is alive at a time, and the
     # batch bank is created holding that format's planes only)
     seqs = []
     for p in prompts:

@@ -80,6 +80,7 @@ static int call_attend(const EkvCall& c, const void* q, const void* k_new, const
   if (c.rows == EKV_ROWS_kv8) aa.k_scale = static_cast<float*>(c.planes.k_aux), aa.v_scale = static_cast<float*>(c.planes.v_aux);
   if (c.rows == EKV_ROWS_kv4 || c.rows == EKV_ROWS_kv6) aa.k_exp = static_cast<uint8_t*>(c.planes.k_aux), aa.v_exp = static_cast<uint8_t*>(c.planes.v_aux);
   if (c.rows == EKV_ROWS_kv84) aa.k_scale = static_cast<float*>(c.planes.k_aux), aa.v_exp = static_cast<uint8_t*>(c.planes.v_aux);
+  if (c.rows == EKV_ROWS_kv164) aa.v_exp = static_cast<uint8_t*>(c.planes.v_aux);      // (the keys: bank->k, as resolve_call left it)
   sa.out = static_cast<__half*>(out);
   sa.evict_ids = evict_ids;
   sa.big_rows = f32(P.big_rows);
@@ -310,9 +311,38 @@ int ekv_kv84_batch_step_attend(const ekv_bank* bank, const ekv_step* st, int32_t
   return call_attend(kv84_batch_call(bank, st, dtype, q84, seqs, n_seq), q, k_new, v_new, out, evict_ids, nullptr, nullptr, workspace, workspace_bytes, stream);
 }
 
+// 16-bit-key / MXFP4-value K/V storage (include/easykv_hip.h, "kv164"), uniform and batched steps
+int ekv_kv164_step_check(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_kv164* q164) { return call_check(kv164_call(bank, st, dtype, q164)); }
+int ekv_kv164_step_info(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_kv164* q164, int32_t* info, int32_t n_info) {
+  return call_info(kv164_call(bank, st, dtype, q164), info, n_info);
+}
+size_t ekv_kv164_workspace_bytes(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_kv164* q164) {
+  return call_workspace_bytes(kv164_call(bank, st, dtype, q164));
+}
+int ekv_kv164_step_attend(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_kv164* q164, const void* q, const void* k_new,
+                          const void* v_new, void* out, int32_t* evict_ids, const float* rope_cos, const float* rope_sin,
+                          void* workspace, size_t workspace_bytes, void* stream) {
+  return call_attend(kv164_call(bank, st, dtype, q164), q, k_new, v_new, out, evict_ids, rope_cos, rope_sin, workspace, workspace_bytes, stream);
+}
+int ekv_kv164_batch_step_check(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_kv164* q164, const ekv_seq* seqs, int32_t n_seq) {
+  return call_check(kv164_batch_call(bank, st, dtype, q164, seqs, n_seq));
+}
+int ekv_kv164_batch_step_info(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_kv164* q164, const ekv_seq* seqs, int32_t n_seq,
+                              int32_t* info, int32_t n_info) {
+  return call_info(kv164_batch_call(bank, st, dtype, q164, seqs, n_seq), info, n_info);
+}
+size_t ekv_kv164_batch_workspace_bytes(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_kv164* q164, const ekv_seq* seqs, int32_t n_seq) {
+  return call_workspace_bytes(kv164_batch_call(bank, st, dtype, q164, seqs, n_seq));
+}
+int ekv_kv164_batch_step_attend(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_kv164* q164, const ekv_seq* seqs, int32_t n_seq,
+                                const void* q, const void* k_new, const void* v_new, void* out, int32_t* evict_ids, void* workspace,
+                                size_t workspace_bytes, void* stream) {
+  return call_attend(kv164_batch_call(bank, st, dtype, q164, seqs, n_seq), q, k_new, v_new, out, evict_ids, nullptr, nullptr, workspace, workspace_bytes, stream);
+}
+
 // ---- bank conversions (ekv_kv8.hip, ekv_kv4.hip): one argument check for every row format
 static int convert_check(const ekv_bank* bank, EkvRows rows, const EkvPlanes& planes, int32_t layer_begin, int32_t layer_count, int32_t extent) {
-  if (!bank || !ekv_planes_complete(planes)) return EKV_E_ARG;
+  if (!bank || !ekv_planes_complete(rows, planes)) return EKV_E_ARG;
   if (bank->n_layers <= 0 || bank->n_kv_heads <= 0 || bank->cap <= 0) return EKV_E_ARG;
   if (int e = check_layers(bank, layer_begin, layer_count)) return e;
   if (extent < 0 || extent > bank->cap) return EKV_E_ARG;
@@ -322,7 +352,7 @@ static int quantize_check(const ekv_bank* bank, EkvRows rows, const EkvPlanes& p
                           int32_t extent) {
   if (dtype != EKV_DTYPE_F16 && dtype != EKV_DTYPE_BF16) return EKV_E_ARG;
   if (int e = convert_check(bank, rows, planes, layer_begin, layer_count, extent)) return e;
-  return bank->k && bank->v ? EKV_OK : EKV_E_ARG;
+  return (bank->k || rows == EKV_ROWS_kv164) && bank->v ? EKV_OK : EKV_E_ARG;      // (kv164 converts V alone)
 }
 static int dequantize_check(const ekv_bank* bank, EkvRows rows, const EkvPlanes& planes, int32_t out_dtype, int32_t layer_begin,
                             int32_t layer_count, int32_t extent, const void* k_out, const void* v_out) {
@@ -385,6 +415,20 @@ int ekv_kv84_dequantize(const ekv_bank* bank, const ekv_kv84* q84, int32_t out_d
   if (int e = dequantize_check(bank, EKV_ROWS_kv84, ekv_planes(q84), out_dtype, layer_begin, layer_count, extent, k_out, v_out)) return e;
   drop_stale_error();
   return launch_code(ekv_launch_kv84_dequantize(bank, q84, out_dtype, layer_begin, layer_count, extent, k_out, v_out, static_cast<hipStream_t>(stream)));
+}
+
+int ekv_kv164_quantize(const ekv_bank* bank, const ekv_kv164* q164, int32_t dtype, int32_t layer_begin, int32_t layer_count, int32_t extent,
+                       void* stream) {
+  if (int e = quantize_check(bank, EKV_ROWS_kv164, ekv_planes(q164), dtype, layer_begin, layer_count, extent)) return e;
+  drop_stale_error();
+  return launch_code(ekv_launch_kv164_quantize(bank, q164, dtype == EKV_DTYPE_BF16, layer_begin, layer_count, extent, static_cast<hipStream_t>(stream)));
+}
+
+int ekv_kv164_dequantize(const ekv_bank* bank, const ekv_kv164* q164, int32_t out_dtype, int32_t layer_begin, int32_t layer_count,
+                         int32_t extent, void* v_out, void* stream) {
+  if (int e = dequantize_check(bank, EKV_ROWS_kv164, ekv_planes(q164), out_dtype, layer_begin, layer_count, extent, v_out, v_out)) return e;
+  drop_stale_error();
+  return launch_code(ekv_launch_kv164_dequantize(bank, q164, out_dtype, layer_begin, layer_count, extent, v_out, static_cast<hipStream_t>(stream)));
 }
 
 // ---- bank utilities: argument checks here, kernels and launch code in ekv_bank_ops.hip

@@ -56,6 +56,20 @@
 #else
 #define EKV_G8 0
 #endif
+// EKV_KV164 = 1 (the kv164 instances): 16-bit keys with MXFP4 values (ekv_decode_stream.h, "16-bit-key / MXFP4-value rows").  Geometry, rows
+// in flight, occupancy bounds and GQA builds are the 16-bit builds'; the stream's V side differs, by its format tag, and the resident rows
+// and the phase order K of the 16-bit flagship instances are compiled out (kResident, kOrders below).  One exception to "the 16-bit
+// builds' rows in flight": the GQA x 1 one-launch builds run 4 rows per lane group, not 8 (EKV_KV164_FUSED_KU1).  With 8 the slot-indexed
+// 4-wave build spills 2 VGPRs under its four-workgroup bound and the 8-wave build needs 133 (3 waves per SIMD, the 16-bit build: 128 / 4
+// — the exponent words, their scales and the widened codes of 8 rows are live next to the 16-byte K pieces); with 4: 70 .. 103 VGPRs, no
+// spill, 4 .. 7 waves per SIMD (profiles/kv164_registers.txt).  The tail takes only the maxima from the stream's partials and the split
+// kernel keeps 8 rows, so logits, scores and victims stay the 16-bit step's bit for bit.
+#ifndef EKV_KV164
+#define EKV_KV164 0
+#endif
+#ifndef EKV_KV164_FUSED_KU1
+#define EKV_KV164_FUSED_KU1 4
+#endif
 // Both switches at once (the batch kv8 instances) are independent: DESIGN.md §3.9, "Batches".
 #define ekv_attn_decode_kernel EKV_KERNEL_NAME(ekv_attn_decode_kernel)
 #define ekv_decode_fused_kernel EKV_KERNEL_NAME(ekv_decode_fused_kernel)
@@ -79,7 +93,7 @@
 namespace {
 
 constexpr int kEPL = EKV_MX ? 32 : (EKV_G8 ? 16 : 8);      // elements of a lane's piece of a K/V row (16 bytes; MXFP6: 24)
-constexpr int kFMT = EKV_KV6 ? 6 : (EKV_KV84 ? 84 : 0);      // the stream's format tag: what EPL alone does not tell
+constexpr int kFMT = EKV_KV6 ? 6 : (EKV_KV84 ? 84 : (EKV_KV164 ? 164 : 0));      // the stream's format tag: what EPL alone does not tell
 
 // SLOT_LDS = false: slot-map entries are fetched per iteration (needs 16-byte aligned map rows, cap % 4 == 0); saves the
 // staging pass and its barrier, which matters when a workgroup only streams one or two iterations.
@@ -206,7 +220,7 @@ __global__ void __launch_bounds__(64 * NW, (NW >= 8 ? (REP == 1 ? 2 : 1) : (SLOT
   const int l_pad = a.l_pad;   // pitch of a logits row: physical rows [0, E) (PHYS) or positions [0, T)
   // Resident rows (ekv_decode_stream.h, "load policy"): the 16-bit instances of the flagship geometry — head_dim 128, one query head
   // per KV head, slot-indexed score rows, both phase orders, 4 and 8 waves, every column count.  Every other instance keeps its code.
-  constexpr bool kResident = D == 128 && REP == 1 && PHYS && SLOT && !EKV_G8 && !EKV_MX && !EKV_BATCH;
+  constexpr bool kResident = D == 128 && REP == 1 && PHYS && SLOT && !EKV_G8 && !EKV_MX && !EKV_KV164 && !EKV_BATCH;
   const int res_rows = kResident ? EKV_RESIDENT_ROWS(a.fused_order) : 0;
   // LDS: logits [REP][l_pad] | wave partials [4][REP][PS] | score rows S (Q C) [w_pad] | reduction scratch | dead-row bits
   float* s_logit = reinterpret_cast<float*>(smem);
@@ -229,7 +243,7 @@ __global__ void __launch_bounds__(64 * NW, (NW >= 8 ? (REP == 1 ? 2 : 1) : (SLOT
   // in LDS.  The tail is a latency-bound chain of block barriers that leaves HBM idle; when the workgroups of a CU are in different
   // orders, each order's tail falls under the other's stream.  Both orders produce the same bits (below), so WHICH workgroups take
   // order K may depend on where the hardware placed them.
-  constexpr bool kOrders = D == 128 && REP == 1 && !ROPE && NW == 4 && SLOT && ITEMS <= 12 && !EKV_G8 && !EKV_MX && !EKV_BATCH;
+  constexpr bool kOrders = D == 128 && REP == 1 && !ROPE && NW == 4 && SLOT && ITEMS <= 12 && !EKV_G8 && !EKV_MX && !EKV_KV164 && !EKV_BATCH;
   bool order_k = false;
   if constexpr (kOrders) {
     const int om = a.fused_order & 3;
@@ -417,7 +431,7 @@ __global__ void __launch_bounds__(64 * NW, (NW >= 8 ? (REP == 1 ? 2 : 1) : (SLOT
   // spilled 19 registers in the Llama-shape build: 284 us; 4 rows 221 us); since round 6 one (cos, sin) seed per iteration + 16 step
   // constants (ekv_decode_stream.h) — 124 VGPRs at 4 rows (46 spilled at 8), GQA x 2 144 (13 spilled at 8), GQA x 4 230 at 8 rows
   // without spills, GQA x 8 (per-row tables) 247
-  constexpr int KUF = ROPE ? EKV_ROPE_KU(REP) : EKV_FUSED_KU;
+  constexpr int KUF = ROPE ? EKV_ROPE_KU(REP) : (EKV_KV164 && REP == 1 ? EKV_KV164_FUSED_KU1 : EKV_FUSED_KU);
   float m[REP], l[REP], o[REP][kEPL];
   if (PHYS)
     ekv_decode_stream<D, REP, ROPE, false, NW, PHYS, KUF, decltype(mask_ready), kEPL, kFMT, kResident>(a, slot_row, s_logit, l_pad, 0, T, ll, h, head_row, m, l, o,

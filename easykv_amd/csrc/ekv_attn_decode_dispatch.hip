@@ -40,7 +40,7 @@ const ScoreInstance kDecodeScore[] = {
 
 // The instance of a decode launch, or nullptr (hipErrorInvalidValue) for a combination the manifest does not hold or the arguments do
 // not fit: quantised rows need plain keys and their auxiliary planes (kv8: the row scales; kv4 / kv6: the block exponents, and a GQA factor of
-// at most 4; kv84: the K row scales and the V block exponents), bf16 and batches have no RoPE-on-read build, a batch runs on the ordered layout (the planner refuses all of these before
+// at most 4; kv84: the K row scales and the V block exponents; kv164: the V block exponents), bf16 and batches have no RoPE-on-read build, a batch runs on the ordered layout (the planner refuses all of these before
 // a launch).  The row format and the batching are independent fields: a batched step on quantised rows looks up its own instance,
 // which takes the table and the planes together, and a combination without a line of the manifest finds nothing.
 const DecodeInstance* decode_instance(const EkvAttnArgs& a, const EkvSeqTable* tb, int head_dim, bool bf16, EkvRows rows, bool fused_slot_rows) {
@@ -48,6 +48,7 @@ const DecodeInstance* decode_instance(const EkvAttnArgs& a, const EkvSeqTable* t
   if (rows == EKV_ROWS_kv8 && (rope || a.k_scale == nullptr || a.v_scale == nullptr)) return nullptr;
   if ((rows == EKV_ROWS_kv4 || rows == EKV_ROWS_kv6) && (rope || a.k_exp == nullptr || a.v_exp == nullptr || a.n_q_heads > 4 * a.n_kv_heads)) return nullptr;
   if (rows == EKV_ROWS_kv84 && (rope || a.k_scale == nullptr || a.v_exp == nullptr)) return nullptr;
+  if (rows == EKV_ROWS_kv164 && (rope || a.v_exp == nullptr)) return nullptr;
   if (bf16 && rope) return nullptr;
   if (batch && (rope || fused_slot_rows)) return nullptr;
   for (const DecodeInstance& in : kDecode)

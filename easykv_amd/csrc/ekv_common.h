@@ -208,6 +208,13 @@ __device__ __forceinline__ void ekv_axpy16_fp4(float p, float scale, const uint2
     for (int j = 0; j < 8; ++j) o[8 * i + j] = fmaf(p, f[j], o[8 * i + j]);
   }
 }
+// o[0..8) += p * (codes * scale): a quarter of a block, the 8 codes of one word (16-bit-key / MXFP4-value rows, "kv164": a lane quad per block)
+__device__ __forceinline__ void ekv_axpy8_fp4(float p, float scale, uint32_t c, float (&o)[8]) {
+  float f[8];
+  ekv_fp4_widen8(c, scale, f);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) o[j] = fmaf(p, f[j], o[j]);
+}
 // 32 source elements (four 16-byte pieces) -> their block: 16 bytes of codes, the exponent byte in `e`
 __device__ __forceinline__ uint4 ekv_fp4_quant_block(const uint4* src, uint32_t& e) {
   float f[32];

@@ -62,6 +62,14 @@ struct EkvNoop {
 // sub >> 1.  The exponent words are read as MXFP4 reads them.  The appended V row: block maximum over the lane pair, 16 codes per lane,
 // the even lane stores the exponent byte.
 //
+// 16-bit-key / MXFP4-value rows (EPL = 8 like 16-bit rows, told apart by the format tag FMT = 164; plain keys, head_dim 128): the K side
+// IS the 16-bit rows' — the 16-byte non-temporal load, ekv_dot8, the group sum over 16 lanes, / sm_div, the appended K row stored as it
+// comes — so logits and (m, l) partials are bit for bit those of a 16-bit step on the same K rows.  The V plane is MXFP4's (64-byte rows,
+// a.v_exp: four E8M0 bytes per row) read on the 16-bit geometry: a lane's piece is 4 bytes, 8 e2m1 codes = a quarter of a block — its
+// own 8 output elements — at byte 4 * sub of the row, and lane `sub` takes exponent byte sub >> 2.  The exponent words are read as MXFP4
+// reads them.  The appended V row: block maximum over the lane quad, 8 codes per lane, lane sub % 4 == 0 stores the exponent byte, and
+// the row is attended as quantised.  No resident rows and no phase order K (ekv_attn_decode.inc).
+//
 // Load policy of the 16-bit K/V rows.  A row is read exactly once per step and the bank (> 1 GB at the flagship shape) never fits L2 or
 // the 256 MiB Infinity Cache: non-temporal loads (measured on MI355X: 5.5 -> 6.1 TB/s on the pure stream).  But step i + 1 reads the
 // rows of step i except one per head, so a fixed SHARE of the bank can stay in the Infinity Cache from step to step.  RES (the
@@ -92,13 +100,18 @@ __device__ __forceinline__ void ekv_decode_stream(const EkvAttnArgs& a, const in
   constexpr bool KV8 = EPL == 16, KV4 = EPL == 32;      // (KV4: the MX geometry, one block per lane — MXFP4 and MXFP6 rows)
   constexpr bool KV6 = KV4 && FMT == 6;
   constexpr bool KV84 = KV8 && FMT == 84;      // FP8 keys (everything KV8 says about K holds), MXFP4 values
-  static_assert(FMT == 0 || KV6 || KV84, "format tag: 6 = MXFP6 rows (EPL = 32), 84 = FP8 keys with MXFP4 values (EPL = 16)");
+  constexpr bool KV164 = EPL == 8 && FMT == 164;      // 16-bit keys (the K side is the 16-bit code itself), MXFP4 values
+  constexpr bool V4 = KV84 || KV164;      // the V plane is MXFP4's: 64-byte rows under a.v_exp, LPR / 4 lanes per block
+  constexpr int VSH = KV164 ? 2 : 1;      // ... lane `sub` holds a piece of block sub >> VSH
+  static_assert(FMT == 0 || KV6 || KV84 || KV164,
+                "format tag: 6 = MXFP6 rows (EPL = 32), 84 = FP8 keys with MXFP4 values (EPL = 16), 164 = 16-bit keys with MXFP4 values (EPL = 8)");
   static_assert(!KV84 || (D == 128 && LPR == 8), "FP8-key / MXFP4-value rows: head_dim 128 (a lane pair = one 32-element V block)");
+  static_assert(!KV164 || (D == 128 && LPR == 16 && !ROPE && !RES), "16-bit-key / MXFP4-value rows: plain keys, head_dim 128 (a lane quad = one 32-element V block), no resident rows");
   static_assert(EPL == 8 || (KV8 && !ROPE && LIVE == LPR) || KV4, "FP8 rows: plain keys, head_dim 64 / 128");
   static_assert(!KV4 || (!ROPE && D == 128 && LPR == 4), "MXFP4 rows: plain keys, head_dim 128 (a lane = one 32-element block)");
   constexpr int ESZ = KV8 ? 1 : 2;      // bytes per stored K/V element
   constexpr int ROWB = KV6 ? 3 * D / 4 : (KV4 ? D / 2 : D * ESZ);      // bytes per stored K/V row
-  constexpr int VROWB = KV84 ? D / 2 : ROWB;      // ... of a V row where the planes differ
+  constexpr int VROWB = V4 ? D / 2 : ROWB;     // ... of a V row where the planes differ
   constexpr bool PADDED = LIVE != LPR;      // head_dim 96: lanes sub >= LIVE of a lane group are idle (zero pieces, no loads / stores)
   constexpr int kNW = NW;
   static_assert(!(PHYS && (ROPE || SLOT_LDS)), "physical-order streaming: plain keys, global slot map");
@@ -291,6 +304,20 @@ __device__ __forceinline__ void ekv_decode_stream(const EkvAttnArgs& a, const in
       reinterpret_cast<uint4*>(reinterpret_cast<uint8_t*>(a.v_w) + off / 2)[sub] = vn;
       a.k_exp[(head_row + slot_new) * 4 + sub] = (uint8_t)ke;
       a.v_exp[(head_row + slot_new) * 4 + sub] = (uint8_t)ve;
+    } else if constexpr (KV164) {
+      // K: stored as the 16-bit step stores it.  V: quantised by the MXFP4 rule (include/easykv_hip.h) — the block maximum over the lane
+      // quad (two DPP quad_perms), 8 codes per lane (4 bytes at byte 4 * sub of the 64-byte row), one exponent byte per quad
+      kn = reinterpret_cast<const uint4*>(k_new_row)[sub];
+      reinterpret_cast<uint4*>(a.k_w + off)[sub] = kn;
+      float vf[8];
+      float va = ekv_widen8_amax(reinterpret_cast<const uint4*>(v_new_row)[sub], vf);
+      va = fmaxf(va, ekv_dpp<0xB1>(va));
+      va = fmaxf(va, ekv_dpp<0x4E>(va));
+      const uint32_t ve = ekv_fp4_block_exp(va);
+      vsn = ekv_fp4_exp_scale(ve);
+      vn.x = ekv_fp4_quant8(vf, vsn);
+      reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(a.v_w) + off / 2)[sub] = vn.x;
+      if (!(sub & 3)) a.v_exp[(head_row + slot_new) * 4 + (sub >> 2)] = (uint8_t)ve;
     } else if (live_lane) {
       kn = reinterpret_cast<const uint4*>(k_new_row)[sub];
       vn = reinterpret_cast<const uint4*>(v_new_row)[sub];
@@ -332,6 +359,7 @@ __device__ __forceinline__ void ekv_decode_stream(const EkvAttnArgs& a, const in
       else if constexpr (KV8) ekv_axpy16_fp8(p * vsn, vn, o[r]);
       else if constexpr (KV6) ekv_axpy32_fp6(p, vsn, vn6, o[r]);
       else if constexpr (KV4) ekv_axpy32_fp4(p, vsn, vn, o[r]);
+      else if constexpr (KV164) ekv_axpy8_fp4(p, vsn, vn.x, o[r]);
       else ekv_axpy8(p, vn, o[r]);
       m[r] = mn;
     }
@@ -355,7 +383,7 @@ __device__ __forceinline__ void ekv_decode_stream(const EkvAttnArgs& a, const in
   auto iteration = [&](const int base, auto&& after_issue) {
     uint4 kr[KU], vr[KU];
     ekv_u6 kr6[KV6 ? KU : 1], vr6[KV6 ? KU : 1];      // MXFP6 rows: the lane's block of each row (kr / vr stay unused)
-    float ksc[KV8 || KV4 ? KU : 1], vsc[KV8 || KV4 ? KU : 1];      // FP8 rows: the scales of the KU rows; MXFP4 rows: of this lane's block of each
+    float ksc[KV8 || KV4 ? KU : 1], vsc[KV8 || KV4 || KV164 ? KU : 1];     // FP8 rows: the scales of the KU rows; MXFP4 rows: of this lane's block of each
     const int j0 = base + grp * KU;
     if constexpr (KV8 && PHYS) {
       // consecutive physical rows: KU / 4 16-byte loads per plane (fused step: cap % 4 == 0, so head_row + j0 is 16-byte aligned); a
@@ -377,9 +405,9 @@ __device__ __forceinline__ void ekv_decode_stream(const EkvAttnArgs& a, const in
         }
       }
     }
-    if constexpr (KV84 && PHYS) {
+    if constexpr (V4 && PHYS) {
       // the V exponent words of the KU consecutive rows, as the MXFP4 stream reads them (same bound); lane `sub` holds half of block
-      // sub >> 1
+      // sub >> 1 (16-bit keys: a quarter of block sub >> 2)
       uint32_t vw[KU];
       if (j0 + KU <= a.cap) {
         const uint4* v4 = reinterpret_cast<const uint4*>(a.v_exp + (head_row + j0) * 4);
@@ -393,7 +421,7 @@ __device__ __forceinline__ void ekv_decode_stream(const EkvAttnArgs& a, const in
         for (int u = 0; u < KU; ++u) vw[u] = reinterpret_cast<const uint32_t*>(a.v_exp)[head_row + min(j0 + u, a.cap - 1)];
       }
 #pragma unroll
-      for (int u = 0; u < KU; ++u) vsc[u] = ekv_fp4_exp_scale((vw[u] >> (8 * (sub >> 1))) & 0xFFu);
+      for (int u = 0; u < KU; ++u) vsc[u] = ekv_fp4_exp_scale((vw[u] >> (8 * (sub >> VSH))) & 0xFFu);
     }
     if constexpr (KV4 && PHYS) {
       // consecutive physical rows: their exponent words (4 bytes per row) as KU / 4 16-byte loads per plane, under the bound of the FP8
@@ -475,6 +503,10 @@ __device__ __forceinline__ void ekv_decode_stream(const EkvAttnArgs& a, const in
         kr[u] = __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const ekv_u4*>(kp) + sub));
         const ekv_u2 w = __builtin_nontemporal_load(reinterpret_cast<const ekv_u2*>(vp) + sub);
         vr[u] = uint4{w[0], w[1], 0, 0};
+      } else if constexpr (KV164) {      // the 16-bit K piece as always, and the 4 bytes (8 codes) of the V row at byte 4 * sub
+        if constexpr (!PHYS) vsc[u] = ekv_fp4_exp_scale(a.v_exp[(head_row + row) * 4 + (sub >> 2)]);      // (through the slot map: one byte per row)
+        kr[u] = __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const ekv_u4*>(kp) + sub));
+        vr[u] = uint4{__builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(vp) + sub), 0, 0, 0};
       } else if (live_lane) {
         kr[u] = __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const ekv_u4*>(kp) + sub));
         vr[u] = __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const ekv_u4*>(vp) + sub));
@@ -495,7 +527,7 @@ __device__ __forceinline__ void ekv_decode_stream(const EkvAttnArgs& a, const in
           vr[u] = uint4{0, 0, 0, 0};
           if constexpr (KV6) vr6[u] = ekv_u6{0, 0, 0, 0, 0, 0};
           if constexpr (KV8) vsc[u] = KV84 ? 1.f : 0.f;      // (KV84: zero codes under scale 1, as MXFP4)
-          if constexpr (KV4) vsc[u] = 1.f;      // (zero codes under a finite scale)
+          if constexpr (KV4 || KV164) vsc[u] = 1.f;      // (zero codes under a finite scale)
         }
     }
     float sall[ROPE ? REP : 1][KU];   // ROPE: every row is rotated once, then dotted with all REP queries
@@ -564,6 +596,7 @@ __device__ __forceinline__ void ekv_decode_stream(const EkvAttnArgs& a, const in
         else if constexpr (KV8) ekv_axpy16_fp8(p * vsc[u], vr[u], o[r]);
         else if constexpr (KV6) ekv_axpy32_fp6(p, vsc[u], vr6[u], o[r]);
         else if constexpr (KV4) ekv_axpy32_fp4(p, vsc[u], vr[u], o[r]);
+        else if constexpr (KV164) ekv_axpy8_fp4(p, vsc[u], vr[u].x, o[r]);
         else ekv_axpy8(p, vr[u], o[r]);
       }
       m[r] = mn;

@@ -10,7 +10,8 @@
 // The row format of a bank's K/V rows: the `rows` word of a manifest line (ekv_instances.def), and what a call of the step family says
 // about its bank.  kv16: 16-bit rows.  kv8: FP8 codes + fp32 row scales (ekv_kv8).  kv4: MXFP4 codes + E8M0 block exponents (ekv_kv4).
 // kv6: MXFP6 (e2m3) codes + E8M0 block exponents (ekv_kv6).  kv84: FP8 K codes + fp32 row scales, MXFP4 V codes + E8M0 block exponents (ekv_kv84).
-enum EkvRows : int32_t { EKV_ROWS_kv16, EKV_ROWS_kv8, EKV_ROWS_kv4, EKV_ROWS_kv6, EKV_ROWS_kv84 };
+// kv164: the bank's 16-bit K rows, MXFP4 V codes + E8M0 block exponents (ekv_kv164).
+enum EkvRows : int32_t { EKV_ROWS_kv16, EKV_ROWS_kv8, EKV_ROWS_kv4, EKV_ROWS_kv6, EKV_ROWS_kv84, EKV_ROWS_kv164 };
 
 // The resident rows of a one-launch decode step as they travel in EkvAttnArgs.fused_order / EkvStepPlan.fused_order (bits 16-23)
 #define EKV_RESIDENT_UNIT 32      // rows of one wave iteration of the stream (EkvDecodeGeom::RW at head_dim 128)
@@ -100,6 +101,7 @@ struct EkvAttnArgs {
   // MXFP4 rows (ekv_kv4_step_attend; the kv4 instances only), likewise: k / v / k_w / v_w are the code planes, two codes per byte, and
   // k_exp / v_exp the E8M0 bytes [n_layers][H][cap][head_dim / 32].  MXFP6 rows (the kv6 instances): the same with 24-byte blocks of 32 codes
   // FP8 keys with MXFP4 values (the kv84 instances): k / k_w / k_scale as for FP8 rows, v / v_w / v_exp as for MXFP4 rows
+  // 16-bit keys with MXFP4 values (the kv164 instances): k / k_w are the bank's 16-bit K rows, v / v_w / v_exp as for MXFP4 rows
   union {
     float* stats;      // two-pass chunk steps: [layer_count][Hq][q_len][2*n_split][2] (max, sum exp) per key-range half split
     float* k_scale;
@@ -174,7 +176,7 @@ struct EkvScoreArgs {
 // tb (the decode launchers): NULL = a uniform step of `count` layers; the table of a batched decode step = the batch instances (16-bit
 // or FP8 rows, plain keys, ordered score rows): `a` / `sc` are the envelope's arguments with layer_begin = 0 and a.arrive = the bank's
 // counters, and `count` is the number of table entries, one workgroup row each.
-// rows: the instances of that row format (kv8: a.k_scale / a.v_scale set, kv4 / kv6: a.k_exp / a.v_exp, kv84: a.k_scale / a.v_exp; plain keys either way)
+// rows: the instances of that row format (kv8: a.k_scale / a.v_scale set, kv4 / kv6: a.k_exp / a.v_exp, kv84: a.k_scale / a.v_exp, kv164: a.v_exp; plain keys either way)
 hipError_t ekv_launch_attn_decode(const EkvAttnArgs& a, const EkvSeqTable* tb, int head_dim, int count, hipStream_t s, bool bf16, EkvRows rows);
 // passes (wide-block kernel, two-pass scheme): bit 0 = the one pass (output + row statistics), bit 1 = the column-sum pass
 // tail_sc (wide-block kernel, two passes, passes & 2): the step's scorer runs as the tail of the column-sum pass (ekv_wide_tail.h)
@@ -249,6 +251,9 @@ __device__ __forceinline__ EkvScoreArgs ekv_batch_score_args(const EkvScoreArgs&
 #elif defined(EKV_KV84) && EKV_KV84
 #define EKV_ROWS kv84
 #define EKV_ROWS_TAG _kv84
+#elif defined(EKV_KV164) && EKV_KV164
+#define EKV_ROWS kv164
+#define EKV_ROWS_TAG _kv164
 #else
 #define EKV_ROWS kv16
 #define EKV_ROWS_TAG
@@ -304,6 +309,11 @@ hipError_t ekv_launch_kv84_quantize(const ekv_bank* bank, const ekv_kv84* q84, b
                                     hipStream_t s);
 hipError_t ekv_launch_kv84_dequantize(const ekv_bank* bank, const ekv_kv84* q84, int out_kind, int layer_begin, int layer_count, int extent,
                                       void* k_out, void* v_out, hipStream_t s);
+// 16-bit-key / MXFP4-value bank conversion (ekv_kv4.hip): the V planes only, K is neither read nor written
+hipError_t ekv_launch_kv164_quantize(const ekv_bank* bank, const ekv_kv164* q164, bool src_bf16, int layer_begin, int layer_count, int extent,
+                                     hipStream_t s);
+hipError_t ekv_launch_kv164_dequantize(const ekv_bank* bank, const ekv_kv164* q164, int out_kind, int layer_begin, int layer_count, int extent,
+                                       void* v_out, hipStream_t s);
 hipError_t ekv_launch_decode_score(const EkvScoreArgs& sc, const EkvSeqTable* tb, int count, hipStream_t s, bool bf16);
 hipError_t ekv_launch_fold(const EkvScoreArgs& sc, int layer_count, hipStream_t s, bool bf16);
 

@@ -656,12 +656,12 @@ int ekv_plan_step(const ekv_bank* bank, const ekv_step* step, EkvStepPlan* P) {
 // ---- one call ----------------------------------------------------------------------------------------------------------------------
 // What each row format takes, beyond decode steps (q_len == 1) on plain keys — all a quantised bank serves: its head_dims (0: none) and
 // the largest GQA factor.  kv8: head_dim 64 / 128.  kv4: head_dim 128 (a lane's 16-byte piece = one 32-element block), GQA factors up
-// to 4 (32 output floats per lane and head).  kv6: the geometry of kv4, so its shapes.  kv84: head_dim 128 (its V blocks), GQA factors as kv8 takes them (its geometry).  resolve_call refuses by it, and the bank conversions (ekv_abi.hip) ask for the head_dim.
+// to 4 (32 output floats per lane and head).  kv6: the geometry of kv4, so its shapes.  kv84: head_dim 128 (its V blocks), GQA factors as kv8 takes them (its geometry).  kv164: head_dim 128 (its V blocks), every GQA factor (the 16-bit geometry and plan).  resolve_call refuses by it, and the bank conversions (ekv_abi.hip) ask for the head_dim.
 namespace {
 struct RowsRule {
   int32_t head_dims[2], max_rep;
 };
-const RowsRule kRowsRules[] = {/* kv16 */ {{0, 0}, 1 << 30}, /* kv8 */ {{64, 128}, 1 << 30}, /* kv4 */ {{128, 0}, 4}, /* kv6 */ {{128, 0}, 4}, /* kv84 */ {{128, 0}, 1 << 30}};
+const RowsRule kRowsRules[] = {/* kv16 */ {{0, 0}, 1 << 30}, /* kv8 */ {{64, 128}, 1 << 30}, /* kv4 */ {{128, 0}, 4}, /* kv6 */ {{128, 0}, 4}, /* kv84 */ {{128, 0}, 1 << 30}, /* kv164 */ {{128, 0}, 1 << 30}};
 }  // namespace
 bool ekv_rows_head_dim(EkvRows rows, int head_dim) {
   const RowsRule& rule = kRowsRules[rows];
@@ -677,6 +677,8 @@ bool ekv_rows_head_dim(EkvRows rows, int head_dim) {
 // argument error before anything else of the call is read), and the plan is that of the 16-bit step of the same shape (the scorers
 // read logits and partials, never a K/V element, so splits, launches and workspace carry over), run on that format's instances of the
 // two decode attention kernels — which is all a quantised bank has: decode steps, plain keys, and the shapes of kRowsRules.
+// kv164 keeps its keys in the bank's 16-bit K rows: the call reads bank->k (NULL is an argument error like a missing plane) and only
+// bank->v is replaced by a plane.
 // A batched decode step (include/easykv_hip.h, ekv_seq): the plan of the uniform step of the batch's ENVELOPE — the longest entry, the
 // widest extent, one "layer" per entry: same splits, launches and workspace pitches, so a uniform table plans field for field as the
 // multi-layer step it spells out.  The entries keep their own bounds inside those pitches (the kernels' batch instances read them
@@ -693,9 +695,10 @@ int resolve_call(const EkvCall& c, EkvResolved* r) {
   r->tb = nullptr;
   if (c.dtype != EKV_DTYPE_F16 && c.dtype != EKV_DTYPE_BF16) return EKV_E_ARG;
   if (quant) {
-    if (!c.bank || !ekv_planes_complete(c.planes)) return EKV_E_ARG;
+    const bool own_k = c.rows == EKV_ROWS_kv164;      // (the keys are the bank's own rows)
+    if (!c.bank || !ekv_planes_complete(c.rows, c.planes) || (own_k && !c.bank->k)) return EKV_E_ARG;
     r->bank_q = *c.bank;
-    r->bank_q.k = c.planes.k_codes;
+    r->bank_q.k = own_k ? c.bank->k : c.planes.k_codes;
     r->bank_q.v = c.planes.v_codes;
     r->bank = &r->bank_q;
   }

@@ -47,17 +47,20 @@ int ekv_plan_step(const ekv_bank* bank, const ekv_step* step, EkvStepPlan* P);
 
 // ---- one call path --------------------------------------------------------------------------------------------------------------
 // A call of the step family as its entry points spell it, along two independent axes: the row format of the bank (the untyped / _typed
-// functions: kv16; ekv_kv8_*: kv8; ekv_kv4_*: kv4; ekv_kv6_*: kv6; ekv_kv84_*: kv84 — a quantised call brings the four planes of its descriptor) and the batching
+// functions: kv16; ekv_kv8_*: kv8; ekv_kv4_*: kv4; ekv_kv6_*: kv6; ekv_kv84_*: kv84; ekv_kv164_*: kv164 — a quantised call brings the planes of its descriptor) and the batching
 // (ekv_*batch_*: the table of a batched decode step).  Which combinations run is the planner's business (resolve_call, over
 // kRowsRules) and the manifest's (ekv_instances.def).
-struct EkvPlanes {      // what stands for the K/V rows of a quantised bank: the code planes, and the row scales (kv8) / block exponents (kv4, kv6); kv84: K row scales, V block exponents
+struct EkvPlanes {      // what stands for the K/V rows of a quantised bank: the code planes, and the row scales (kv8) / block exponents (kv4, kv6); kv84: K row scales, V block exponents; kv164: the V planes alone (K stays bank->k)
   void *k_codes, *v_codes, *k_aux, *v_aux;
 };
 inline EkvPlanes ekv_planes(const ekv_kv8* q) { return q ? EkvPlanes{q->k_codes, q->v_codes, q->k_scale, q->v_scale} : EkvPlanes{}; }
 inline EkvPlanes ekv_planes(const ekv_kv4* q) { return q ? EkvPlanes{q->k_codes, q->v_codes, q->k_exp, q->v_exp} : EkvPlanes{}; }
 inline EkvPlanes ekv_planes(const ekv_kv6* q) { return q ? EkvPlanes{q->k_codes, q->v_codes, q->k_exp, q->v_exp} : EkvPlanes{}; }
 inline EkvPlanes ekv_planes(const ekv_kv84* q) { return q ? EkvPlanes{q->k_codes, q->v_codes, q->k_scale, q->v_exp} : EkvPlanes{}; }
+inline EkvPlanes ekv_planes(const ekv_kv164* q) { return q ? EkvPlanes{nullptr, q->v_codes, nullptr, q->v_exp} : EkvPlanes{}; }
 inline bool ekv_planes_complete(const EkvPlanes& p) { return p.k_codes && p.v_codes && p.k_aux && p.v_aux; }
+// ... of a call on `rows`: kv164 has no K planes (its keys are the bank's 16-bit rows, which resolve_call asks for)
+inline bool ekv_planes_complete(EkvRows rows, const EkvPlanes& p) { return rows == EKV_ROWS_kv164 ? p.v_codes && p.v_aux : ekv_planes_complete(p); }
 struct EkvCall {
   const ekv_bank* bank;
   const ekv_step* step;
@@ -96,6 +99,12 @@ inline EkvCall kv84_call(const ekv_bank* bank, const ekv_step* st, int32_t dtype
 }
 inline EkvCall kv84_batch_call(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_kv84* q84, const ekv_seq* seqs, int32_t n_seq) {
   return {bank, st, dtype, EKV_ROWS_kv84, ekv_planes(q84), true, seqs, n_seq};
+}
+inline EkvCall kv164_call(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_kv164* q164) {
+  return {bank, st, dtype, EKV_ROWS_kv164, ekv_planes(q164), false, nullptr, 0};
+}
+inline EkvCall kv164_batch_call(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_kv164* q164, const ekv_seq* seqs, int32_t n_seq) {
+  return {bank, st, dtype, EKV_ROWS_kv164, ekv_planes(q164), true, seqs, n_seq};
 }
 // is `head_dim` one the row format is built for (the table of what each format takes: ekv_plan.cpp, kRowsRules; the conversions ask too)
 bool ekv_rows_head_dim(EkvRows rows, int head_dim);

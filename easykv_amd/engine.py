@@ -39,11 +39,12 @@ class StepPlan:
     two_pass: int = 0           # scored chunk steps: 0 auto, 1 force the two-pass kernels, -1 force one pass
 
 
-# The row formats of a quantised bank, by ``kv_quant`` (include/easykv_hip.h, "kv8" / "kv4" / "kv6" / "kv84"): everything the bank, the batch and the
+# The row formats of a quantised bank, by ``kv_quant`` (include/easykv_hip.h, "kv8" / "kv4" / "kv6" / "kv84" / "kv164"): everything the bank, the batch and the
 # driver (api.py) need to know about one.  rows: the calls' prefix (ekv_<rows>_*); desc: the descriptor of the four planes; planes:
 # (attribute, trailing shape at head_dim d, dtype, fill) in the descriptor's order — rows that were never written keep code 0 and
 # scale 1 (exponent byte 127), so every scale of the bank is finite whatever the kernels prefetch; head_dims / max_rep: the shapes the
-# decode kernels of the format are built for; pair_bytes: bytes of one K + V row pair.
+# decode kernels of the format are built for; pair_bytes: bytes of one K + V row pair; keeps (optional): the 16-bit tensors the format
+# keeps next to its planes ("k16_mxfp4": the K rows), which its descriptor does not carry.
 ROW_FORMATS = {
     "fp8": dict(kind="fp8", rows="kv8", desc=_lib.Kv8, label="FP8", method="quantize_fp8", stored="FP8 codes with per-row scales",
                 planes=(("k8", lambda d: (d,), torch.uint8, 0), ("v8", lambda d: (d,), torch.uint8, 0),
@@ -63,11 +64,17 @@ ROW_FORMATS = {
                       planes=(("k8", lambda d: (d,), torch.uint8, 0), ("v4", lambda d: (d // 2,), torch.uint8, 0),
                               ("k_scale", lambda d: (), torch.float32, 1), ("v_exp", lambda d: (d // 32,), torch.uint8, 127)),
                       head_dims=(128,), max_rep=None, pair_bytes=lambda d: 3 * d // 2 + 4 + d // 32),
+    # the bank's own 16-bit keys, untouched, with MXFP4 values (the "mxfp4" V planes): the eviction decisions of the 16-bit bank, exactly
+    "k16_mxfp4": dict(kind="k16_mxfp4", rows="kv164", desc=_lib.Kv164, label="16-bit-key / MXFP4-value", method="quantize_k16_mxfp4",
+                      stored="16-bit keys and MXFP4 value codes with block exponents", keeps=("k",),
+                      planes=(("v4", lambda d: (d // 2,), torch.uint8, 0), ("v_exp", lambda d: (d // 32,), torch.uint8, 127)),
+                      head_dims=(128,), max_rep=None, pair_bytes=lambda d: 2 * d + d // 2 + d // 32),
 }
 
 
 def row_format(kind, what="kv_quant"):
-    """The entry of ROW_FORMATS for ``kind``, or None for None (16-bit rows); anything else is a ValueError naming ``what``."""
+    """The entry of ROW_FORMATS for ``kind`` ('fp8', 'mxfp4', 'mxfp6', 'fp8_mxfp4' or 'k16_mxfp4'), or None for None (16-bit rows);
+    anything else is a ValueError naming ``what``."""
     if kind is not None and kind not in ROW_FORMATS:
         raise ValueError(f"{what} must be None or 'fp8' / 'mxfp4', not {kind!r}; 'mxfp6' is accepted as well, and 'fp8_mxfp4'")
     return ROW_FORMATS.get(kind)
@@ -144,14 +151,16 @@ class KVBank:
     # library's default, 0 = every K/V load non-temporal — what a caller sets whose process streams more than the Infinity Cache holds
     # between two steps (easykv_amd.api: a model's weights)
     resident_bytes = None
-    kv_quant = None      # quantize(): "fp8" / "mxfp4" / "mxfp6" / "fp8_mxfp4" (ROW_FORMATS; _fmt is the entry, _desc the descriptor of the four planes)
+    kv_quant = None      # quantize(): "fp8" / "mxfp4" / "mxfp6" / "fp8_mxfp4" / "k16_mxfp4" (ROW_FORMATS; _fmt is the entry, _desc the descriptor of its planes)
 
     def __init__(self, n_layers, n_q_heads, n_kv_heads, head_dim, cap, device="cuda", scored=True, dtype=torch.float16, kv_quant=None):
         """``kv_quant='fp8'``: the bank is created holding FP8 planes only (see :meth:`quantize_fp8`); the 16-bit K/V rows are never
         allocated.  Such a bank is filled by decode steps or, as one sequence of a :class:`KVBankBatch`, by ``adopt()``.
         ``kv_quant='mxfp4'``: likewise with MXFP4 planes only (see :meth:`quantize_mxfp4`; head_dim 128, GQA factors up to 4).
         ``kv_quant='mxfp6'``: likewise with MXFP6 planes only (see :meth:`quantize_mxfp6`; the same shapes).
-        ``kv_quant='fp8_mxfp4'``: likewise with FP8 key planes and MXFP4 value planes (see :meth:`quantize_fp8_mxfp4`; head_dim 128)."""
+        ``kv_quant='fp8_mxfp4'``: likewise with FP8 key planes and MXFP4 value planes (see :meth:`quantize_fp8_mxfp4`; head_dim 128).
+        ``kv_quant='k16_mxfp4'``: the 16-bit K rows and MXFP4 value planes (see :meth:`quantize_k16_mxfp4`; head_dim 128); a 16-bit V is
+        never allocated."""
         if dtype not in _lib.DTYPE_CODES:
             raise ValueError(f"KVBank dtype must be torch.float16 or torch.bfloat16, not {dtype}")
         fmt = row_format(kv_quant, "KVBank kv_quant")
@@ -166,8 +175,8 @@ class KVBank:
         self._dev_index = dev.index if dev.index is not None else torch.cuda.current_device()
         cap = (cap + 63) // 64 * 64     # rows of the slot map / score rows stay 16-byte aligned (fused kernel, LDS-DMA)
         self.n_layers, self.n_q_heads, self.n_kv_heads, self.head_dim, self.cap = n_layers, n_q_heads, n_kv_heads, head_dim, cap
-        self.k = torch.empty(n_layers, n_kv_heads, cap, head_dim, dtype=dtype, device=dev) if kv_quant is None else None
-        self.v = torch.empty_like(self.k) if kv_quant is None else None
+        keeps = ("k", "v") if fmt is None else fmt.get("keeps", ())      # the 16-bit tensors this bank holds
+        self.k, self.v = (torch.empty(n_layers, n_kv_heads, cap, head_dim, dtype=dtype, device=dev) if name in keeps else None for name in ("k", "v"))
         # (the state tensors are reached through properties: reading one converts slot-indexed layers back to the ordered layout)
         self._slot_of_pos = torch.empty(n_layers, n_kv_heads, cap, dtype=torch.int32, device=dev)
         self._score_sum = torch.zeros(n_layers, n_kv_heads, cap, dtype=torch.float32, device=dev) if scored else None
@@ -301,9 +310,9 @@ class KVBank:
                                 f"{self._fmt['stored']}, which only decode steps (q_len == 1, plain keys) read and append to")
 
     def quantize(self, kind):
-        """Convert the live bank in place to the row format ``kind`` ('fp8' / 'mxfp4' / 'mxfp6' / 'fp8_mxfp4'): codes and scales / exponents are written at the
+        """Convert the live bank in place to the row format ``kind`` ('fp8' / 'mxfp4' / 'mxfp6' / 'fp8_mxfp4' / 'k16_mxfp4'): codes and scales / exponents are written at the
         rows' physical indices (slot map, free list and score rows carry over as they are, in either layout), the 16-bit K/V tensors
-        are released, ``kv_quant`` is ``kind`` and ``attend`` / ``step_info`` / ``step_plan`` go to that format's calls.  From here on
+        are released (``'k16_mxfp4'`` keeps ``k``, untouched, and releases ``v`` only), ``kv_quant`` is ``kind`` and ``attend`` / ``step_info`` / ``step_plan`` go to that format's calls.  From here on
         the bank serves decode steps only: chunk steps, ``load_rows``, ``set_rope`` and the row moves raise :class:`EkvError`.  A bank
         is quantised once: a second conversion raises."""
         fmt = row_format(kind, "quantize(kind)")
@@ -324,9 +333,10 @@ class KVBank:
         call = f"ekv_{fmt['rows']}_quantize"
         check(getattr(self.lib, call)(C.byref(self._bank), C.byref(desc), self._dt, 0, self.n_layers, max(self.extent), self._stream()), call)
         cur = torch.cuda.current_stream(self.device)
-        self.k.record_stream(cur)
-        self.v.record_stream(cur)
-        self.k = self.v = None
+        for name in ("k", "v"):      # (the 16-bit tensors the format does not keep)
+            if name not in fmt.get("keeps", ()):
+                getattr(self, name).record_stream(cur)
+                setattr(self, name, None)
         self._attach(fmt, desc)
         return self
 
@@ -351,6 +361,13 @@ class KVBank:
         rows take.  Eviction reads logits only, so the bank evicts exactly what its FP8 twin evicts."""
         return self.quantize("fp8_mxfp4")
 
+    def quantize_k16_mxfp4(self):
+        """:meth:`quantize` to 16-bit keys with MXFP4 values: ``k`` stays as it is and only V becomes the V planes of
+        :meth:`quantize_mxfp4` (``v4`` / ``v_exp``), 324 bytes per row pair at head_dim 128, the only head_dim; every GQA factor the
+        16-bit decode step takes.  Eviction reads logits only and the keys are not quantised, so the bank evicts exactly what the
+        16-bit bank evicts."""
+        return self.quantize("k16_mxfp4")
+
     def _planes(self, fmt):
         """Allocate the planes of ``fmt`` as the bank's attributes; returns their descriptor."""
         shape = (self.n_layers, self.n_kv_heads, self.cap)
@@ -365,7 +382,9 @@ class KVBank:
         if fmt is not None:
             self._desc = self._planes(fmt) if desc is None else desc
             # the descriptor's planes stand where the rows were: the planning calls that take the bank alone never dereference them
-            self._bank.k, self._bank.v = self._desc.k_codes, self._desc.v_codes
+            # (a format that keeps the 16-bit keys has no K plane: bank.k stays the rows')
+            self._bank.k = _ptr(self.k) if "k" in fmt.get("keeps", ()) else self._desc.k_codes
+            self._bank.v = self._desc.v_codes
             self.kv_quant = fmt["kind"]
             self._slot_ok.clear()
             self._defer = None
@@ -378,7 +397,7 @@ class KVBank:
     def kv_bytes(self) -> int:
         """Bytes held for the K/V rows: 16-bit rows, FP8 codes + row scales (``2 * head_dim + 8`` per row pair), or MXFP4 codes +
         block exponents (``head_dim + head_dim / 16``: 136 at head_dim 128; MXFP6: ``3 * head_dim / 2 + head_dim / 16``, 200; FP8 keys with MXFP4
-        values: ``3 * head_dim / 2 + 4 + head_dim / 32``, 200)."""
+        values: ``3 * head_dim / 2 + 4 + head_dim / 32``, 200; 16-bit keys with MXFP4 values: ``2 * head_dim + head_dim / 2 + head_dim / 32``, 324)."""
         pair = 4 * self.head_dim if self._fmt is None else self._fmt["pair_bytes"](self.head_dim)
         return self.n_layers * self.n_kv_heads * self.cap * pair
 
@@ -390,6 +409,9 @@ class KVBank:
         k = torch.empty(self.n_kv_heads, self.cap, self.head_dim, dtype=torch.float32, device=self.device)
         v = torch.empty_like(k)
         call = f"ekv_{self._fmt['rows']}_dequantize"
+        if "k" in self._fmt.get("keeps", ()):      # (the keys are 16-bit rows: the conversion is V's alone)
+            check(getattr(self.lib, call)(C.byref(self._bank), *self._desc_ref, _lib.DTYPE_F32, layer, 1, self.cap, _ptr(v), self._stream()), call)
+            return self.k[layer].float(), v
         check(getattr(self.lib, call)(C.byref(self._bank), *self._desc_ref, _lib.DTYPE_F32, layer, 1, self.cap, _ptr(k), _ptr(v), self._stream()), call)
         return k, v
 
@@ -810,7 +832,8 @@ class KVBankBatch:
         allocated); its sequences are filled by :meth:`adopt` from banks quantised by :meth:`KVBank.quantize_fp8`.
         ``kv_quant='mxfp4'``: likewise with MXFP4 planes, filled from banks quantised by :meth:`KVBank.quantize_mxfp4`.
         ``kv_quant='mxfp6'``: likewise with MXFP6 planes (:meth:`KVBank.quantize_mxfp6`).
-        ``kv_quant='fp8_mxfp4'``: likewise with FP8 key and MXFP4 value planes (:meth:`KVBank.quantize_fp8_mxfp4`)."""
+        ``kv_quant='fp8_mxfp4'``: likewise with FP8 key and MXFP4 value planes (:meth:`KVBank.quantize_fp8_mxfp4`).
+        ``kv_quant='k16_mxfp4'``: the 16-bit K rows with MXFP4 value planes (:meth:`KVBank.quantize_k16_mxfp4`); no 16-bit V."""
         if not 1 <= n_seq <= _lib.MAX_SEQS:
             raise ValueError(f"a decode batch holds 1..{_lib.MAX_SEQS} sequences, not {n_seq}")
         self.n_seq, self.n_layers = n_seq, n_layers
@@ -854,6 +877,10 @@ class KVBankBatch:
         """:meth:`quantize` to FP8 keys with MXFP4 values (:meth:`KVBank.quantize_fp8_mxfp4`: head_dim 128)."""
         return self.quantize("fp8_mxfp4")
 
+    def quantize_k16_mxfp4(self):
+        """:meth:`quantize` to 16-bit keys with MXFP4 values (:meth:`KVBank.quantize_k16_mxfp4`: head_dim 128)."""
+        return self.quantize("k16_mxfp4")
+
     def _quant_call(self, what):
         """(the batched call `what` of this bank's row format, its leading descriptor arguments), as the bank resolved them."""
         return self.bank._calls[True, what], self.bank._desc_ref
@@ -866,7 +893,8 @@ class KVBankBatch:
         """Sequence ``i`` takes over the state of ``src``, a bank of this batch's layer count and head shape that one sequence was
         prefilled on alone: K/V rows at their physical indices, slot maps, score rows (ordered layout), lengths and extents.  The
         rows behind ``src.cap`` keep this bank's own free list, so a shorter ``src.cap`` is fine.  A quantised batch takes a quantised
-        source of the same kind (codes and row scales / block exponents are copied as they are); 16-bit, FP8, MXFP4, MXFP6 and FP8-key / MXFP4-value rows do not mix."""
+        source of the same kind (codes and row scales / block exponents are copied as they are); 16-bit, FP8, MXFP4, MXFP6, FP8-key / MXFP4-value
+        and 16-bit-key / MXFP4-value rows do not mix (the last: ``k``, ``v4`` and ``v_exp`` are copied)."""
         b = self.bank
         if (src.n_layers, src.n_q_heads, src.n_kv_heads, src.head_dim, src.dtype) != (self.n_layers, b.n_q_heads, b.n_kv_heads, b.head_dim, b.dtype) \
                 or src.cap > b.cap or not 0 <= i < self.n_seq:
@@ -877,7 +905,7 @@ class KVBankBatch:
         src.join()
         l0, l1, c = i * self.n_layers, (i + 1) * self.n_layers, src.cap
         b._ensure_ordered(l0, self.n_layers)
-        rows = ("k", "v") if b._fmt is None else tuple(name for name, *_ in b._fmt["planes"])
+        rows = ("k", "v") if b._fmt is None else tuple(b._fmt.get("keeps", ())) + tuple(name for name, *_ in b._fmt["planes"])
         for name in rows + ("slot_of_pos", "score_sum", "score_sq", "score_cnt"):      # (the properties hand out the ordered layout)
             t = getattr(src, name)
             if t is not None:

@@ -126,10 +126,11 @@ def main():
     ap.add_argument("--ntk-length", type=int, default=None, help="sequence length the DynamicNTK base is fixed for")
     ap.add_argument("--dtype", choices=["float16", "bfloat16"], default="float16",
                     help="model weights in this dtype; the K/V bank follows it (generation_config kv_dtype='auto')")
-    ap.add_argument("--kv-quant", choices=["fp8", "mxfp4", "mxfp6", "fp8_mxfp4"], default=None,
+    ap.add_argument("--kv-quant", choices=["fp8", "mxfp4", "mxfp6", "fp8_mxfp4", "k16_mxfp4"], default=None,
                     help="store the K/V rows of the decode phase as FP8 codes with per-row scales, or as MXFP4 / MXFP6 codes with block exponents "
                          "(both: head_dim 128, GQA <= 4; MXFP6 keeps FP8's three mantissa bits at 200 bytes per row pair), or as FP8 keys "
-                         "with MXFP4 values (fp8_mxfp4: head_dim 128, 200 bytes per row pair, FP8's eviction decisions) "
+                         "with MXFP4 values (fp8_mxfp4: head_dim 128, 200 bytes per row pair, FP8's eviction decisions), or as "
+                         "16-bit keys with MXFP4 values (k16_mxfp4: head_dim 128, 324 bytes per row pair, the unquantised run's eviction decisions) "
                          "(generation_config kv_quant; not for the ppl task)")
     args = ap.parse_args()
     import easykv_amd

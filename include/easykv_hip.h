@@ -447,6 +447,51 @@ int ekv_kv84_step_attend(const ekv_bank *bank, const ekv_step *step, int32_t dty
                          const void *k_new, const void *v_new, void *out, int32_t *evict_ids, const float *rope_cos,
                          const float *rope_sin, void *workspace, size_t workspace_bytes, void *stream);
 
+/* 16-bit keys with MXFP4 values ("kv164"; ABI 8, additive; head_dim 128).  A bank may keep its K rows as they are — bank->k, the
+ * 16-bit rows [n_layers][n_kv_heads][cap][head_dim], untouched — and hold only its V rows as
+ *
+ *   v_codes   uint8 [n_layers][n_kv_heads][cap][head_dim / 2]    and   v_exp     uint8 [n_layers][n_kv_heads][cap][head_dim / 32]
+ *
+ * at the rows' physical indices: 2 * head_dim bytes of K and head_dim / 2 + head_dim / 32 bytes of V per row, 324 per K+V row pair at
+ * head_dim 128 against 512 for 16-bit rows.  The V planes follow the rule of kv4 ("MXFP4 K/V storage" above: layout, packing, rule and
+ * exponent of ekv_kv4's v_codes / v_exp), which is not restated here; they are exactly the V planes ekv_kv4_quantize and
+ * ekv_kv84_quantize write for the same rows.  The eviction scores of a step are computed from its logits alone and the keys are not
+ * quantised, so a kv164 bank takes the eviction decisions of the 16-bit bank with the same rows, exactly, on every path; the V format
+ * touches the output only.  What is stored is what is attended.  Rows never move, as for kv8 / kv4.
+ *
+ * The descriptor carries the two V planes; K is bank->k, which the kv164 step calls READ and append to (NULL is EKV_E_ARG).  bank->v is
+ * not read by them (it may be NULL). */
+typedef struct ekv_kv164 {
+  void *v_codes;
+  uint8_t *v_exp;
+} ekv_kv164;
+
+/* Bank conversion and its inverse, V only.  ekv_kv164_quantize writes the two planes from bank->v (fp16 / bf16 by `dtype`) for the
+ * physical rows [0, extent) of the layers [layer_begin, layer_begin + layer_count); it reads and writes nothing of K (bank->k may be
+ * NULL here).  ekv_kv164_dequantize writes those rows of V densely, [layer_count][n_kv_heads][extent][head_dim], to v_out (out_dtype
+ * EKV_DTYPE_F32 is exact: code * 2^e).  The argument checks and contracts are those of the kv4 pair; head_dim != 128 is
+ * EKV_E_UNSUPPORTED; every check precedes any device access. */
+int ekv_kv164_quantize(const ekv_bank *bank, const ekv_kv164 *kv164, int32_t dtype, int32_t layer_begin, int32_t layer_count,
+                       int32_t extent, void *stream);
+int ekv_kv164_dequantize(const ekv_bank *bank, const ekv_kv164 *kv164, int32_t out_dtype, int32_t layer_begin, int32_t layer_count,
+                         int32_t extent, void *v_out, void *stream);
+
+/* Decode steps on a kv164 bank: the ekv_kv8_step_* signatures with the kv164 descriptor — q_len == 1 with plain keys at head_dim 128,
+ * every GQA factor the 16-bit decode step takes, fp16 / bf16 banks, q, k_new, v_new and out, every policy and phase combination of
+ * the 16-bit decode step — planned exactly as the 16-bit step of that shape, fused_order 0 (no resident rows, no phase order K).  The
+ * kv164 builds run on the geometry of the 16-bit builds (a row is a 16-lane group, 8 elements per lane) and their K side is the
+ * 16-bit builds' code: logits, softmax partials, scores and victims are bit for bit those of a 16-bit step on the same K rows.  A
+ * lane's V piece is a quarter of a block (8 codes, its own 8 output elements) under the block's exponent; the appended row's K is
+ * stored as it comes, its V is quantised by the kv4 rule (block maximum over the lane quad) and attended as quantised.
+ * EKV_E_UNSUPPORTED from the dry run, before anything is launched: q_len > 1, rope_on_read, head_dim != 128.  A missing plane or a
+ * NULL bank->k is EKV_E_ARG.  The row moves do not serve kv164 banks; the batch form is ekv_kv164_batch_* below. */
+int ekv_kv164_step_check(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const ekv_kv164 *kv164);
+int ekv_kv164_step_info(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const ekv_kv164 *kv164, int32_t *info, int32_t n_info);
+size_t ekv_kv164_workspace_bytes(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const ekv_kv164 *kv164);
+int ekv_kv164_step_attend(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const ekv_kv164 *kv164, const void *q,
+                          const void *k_new, const void *v_new, void *out, int32_t *evict_ids, const float *rope_cos,
+                          const float *rope_sin, void *workspace, size_t workspace_bytes, void *stream);
+
 /* Batched decode steps (ABI 8, additive): ONE call, and one launch per kernel kind, serves n_seq sequences whose caches have
  * different lengths and different eviction geometry.  Each entry of the table names the bank layer it attends and carries what
  * ekv_step holds per step; entry i owns row i of the call's tensors.  The layers of a table need not be contiguous or ordered, so
@@ -569,6 +614,21 @@ size_t ekv_kv84_batch_workspace_bytes(const ekv_bank *bank, const ekv_step *step
 int ekv_kv84_batch_step_attend(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const ekv_kv84 *kv84, const ekv_seq *seqs,
                                int32_t n_seq, const void *q, const void *k_new, const void *v_new, void *out, int32_t *evict_ids,
                                void *workspace, size_t workspace_bytes, void *stream);
+
+/* Batched decode steps on a kv164 bank ("kv164 batches"; ABI 8, additive): the ekv_kv8_batch_* signatures with the kv164 descriptor,
+ * with the acceptance (head_dim 128 only, every GQA factor of the 16-bit batched call), the planning (the 16-bit batched call of the
+ * same table, fused_order 0) and the refusals of the kv84 batch calls: EKV_E_UNSUPPORTED from the dry run with nothing launched and 0
+ * workspace bytes, EKV_E_ARG for a NULL descriptor or plane, a NULL bank->k, a dtype other than EKV_DTYPE_F16 / _BF16 and a bad table.
+ * Per entry the arithmetic is that of ekv_kv164_step_attend of the entry's geometry under the same n_split. */
+int ekv_kv164_batch_step_check(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const ekv_kv164 *kv164, const ekv_seq *seqs,
+                               int32_t n_seq);
+int ekv_kv164_batch_step_info(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const ekv_kv164 *kv164, const ekv_seq *seqs,
+                              int32_t n_seq, int32_t *info, int32_t n_info);
+size_t ekv_kv164_batch_workspace_bytes(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const ekv_kv164 *kv164,
+                                       const ekv_seq *seqs, int32_t n_seq);
+int ekv_kv164_batch_step_attend(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const ekv_kv164 *kv164, const ekv_seq *seqs,
+                                int32_t n_seq, const void *q, const void *k_new, const void *v_new, void *out, int32_t *evict_ids,
+                                void *workspace, size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }

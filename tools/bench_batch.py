@@ -43,7 +43,11 @@ with `batched`, `batched_kv8`, `batched_kv4`, `ragged`, `ragged_kv8` and `ragged
 pair) — batched_kv84, solo_kv84_deferred, ragged_kv84 — with the 16-bit, FP8, MXFP4 and MXFP6 batched / ragged legs as the yardsticks
 of the same interleaved run.
 
-Usage: python tools/bench_batch.py [--reps 9] [--tokens 24] [--warm 20] [--batches 1,2,4,8,16,32] [--kv8 | --mxfp4 | --mxfp6 | --fp8-mxfp4] [--out profiles/batch_bench.json]"""
+--k16-mxfp4 (output: profiles/batch_kv164_bench.json) does the same for 16-bit keys with MXFP4 values (2 D + D / 2 + D / 32 bytes per row
+pair) — batched_kv164, solo_kv164_deferred, ragged_kv164 — with the 16-bit, FP8 and FP8-key / MXFP4-value batched / ragged legs as the
+yardsticks of the same interleaved run.
+
+Usage: python tools/bench_batch.py [--reps 9] [--tokens 24] [--warm 20] [--batches 1,2,4,8,16,32] [--kv8 | --mxfp4 | --mxfp6 | --fp8-mxfp4 | --k16-mxfp4] [--out profiles/batch_bench.json]"""
 from __future__ import annotations
 
 import argparse
@@ -117,7 +121,7 @@ def _quantised_copy(src, make, rows="kv8"):
     for name in ("k", "v", "slot_of_pos", "score_sum", "score_sq", "score_cnt"):
         getattr(dst, name).copy_(getattr(src, name))
     dst.n_slots, dst.extent = list(src.n_slots), list(src.extent)
-    return dst.quantize({"kv4": "mxfp4", "kv6": "mxfp6", "kv84": "fp8_mxfp4"}.get(rows, "fp8"))
+    return dst.quantize({"kv4": "mxfp4", "kv6": "mxfp6", "kv84": "fp8_mxfp4", "kv164": "k16_mxfp4"}.get(rows, "fp8"))
 
 
 def batched_quant_leg(bat, lps, plans, toks, rows="kv8", n_split=0):
@@ -260,11 +264,11 @@ def uniform_legs(B, lps, g):
 
 
 PAIR_BYTES = {"kv16": 4 * D, "kv8": 2 * D + 8, "kv4": D + D // 16, "kv6": 3 * D // 2 + D // 16,
-              "kv84": 3 * D // 2 + 4 + D // 32}      # one K+V row pair: 16-bit / FP8 codes + two fp32 scales / MXFP4 codes + exponents
+              "kv84": 3 * D // 2 + 4 + D // 32, "kv164": 2 * D + D // 2 + D // 32}      # one K+V row pair: 16-bit / FP8 codes + two fp32 scales / MXFP4 codes + exponents
 
 
 def _rows_of(leg):
-    return next((r for r in ("kv84", "kv8", "kv4", "kv6") if r in leg.split("_")), "kv16")
+    return next((r for r in ("kv164", "kv84", "kv8", "kv4", "kv6") if r in leg.split("_")), "kv16")
 
 
 def bytes_per_call(lens, rows="kv16"):
@@ -283,8 +287,8 @@ def run_batch(B, args):
     rs = torch.Generator().manual_seed(20261016 + B)
     ragged = sorted(int(x) for x in torch.randint(255, BUDGET + 1, (B,), generator=rs))
     ragged[-1] = BUDGET      # (the envelope is the uniform shape)
-    mx = "kv84" if args.fp8_mxfp4 else "kv6" if args.mxfp6 else ("kv4" if args.mxfp4 else None)      # the MX format under test: its legs + the yardsticks of the same run
-    quant = ("kv8", "kv4", "kv6", "kv84") if args.fp8_mxfp4 else ("kv8", "kv4", "kv6") if args.mxfp6 else (("kv8", "kv4") if args.mxfp4 else (("kv8",) if args.kv8 else ()))
+    mx = "kv164" if args.k16_mxfp4 else "kv84" if args.fp8_mxfp4 else "kv6" if args.mxfp6 else ("kv4" if args.mxfp4 else None)      # the MX format under test: its legs + the yardsticks of the same run
+    quant = ("kv8", "kv84", "kv164") if args.k16_mxfp4 else ("kv8", "kv4", "kv6", "kv84") if args.fp8_mxfp4 else ("kv8", "kv4", "kv6") if args.mxfp6 else (("kv8", "kv4") if args.mxfp4 else (("kv8",) if args.kv8 else ()))
     raw, engine, info, *rawq = batched_legs(B, lps, [BUDGET] * B, g, quant)
     fns = {"batched": raw, "batched_engine": engine}
     solo_quant = (mx,) if mx else quant
@@ -299,8 +303,8 @@ def run_batch(B, args):
         for rows, f in zip(quant, raggedq):
             fns[f"ragged_{rows}"] = f
     if mx:      # the yardsticks of the same run and the three new legs; the other legs: profiles/batch_bench.json, batch_kv8_bench.json
-        keep = ("batched", "batched_kv8", "batched_kv4", "batched_kv6", "batched_kv84", f"solo_{mx}_deferred", "ragged", "ragged_kv8", "ragged_kv4", "ragged_kv6",
-                "ragged_kv84")
+        keep = ("batched", "batched_kv8", "batched_kv4", "batched_kv6", "batched_kv84", "batched_kv164", f"solo_{mx}_deferred", "ragged", "ragged_kv8", "ragged_kv4",
+                "ragged_kv6", "ragged_kv84", "ragged_kv164")
         fns = {k: f for k, f in fns.items() if k in keep}
     if args.legs:      # (a kernel trace of two legs: their launches alone)
         fns = {k: f for k, f in fns.items() if k in args.legs.split(",")}
@@ -351,13 +355,23 @@ def run_batch(B, args):
         for other in ("ragged", "ragged_kv8", "ragged_kv4"):
             res[f"ratio_ragged_kv6_over_{other}"] = round(us("ragged_kv6") / us(other), 4)
         res["ratio_ragged_kv6_over_batched_kv6_at_envelope"] = round(us("ragged_kv6") / us("batched_kv6"), 4)
+    if "batched_kv164" in res:
+        for other in ("batched", "batched_kv8", "batched_kv84", "solo_kv164_deferred"):
+            res[f"ratio_batched_kv164_over_{other}"] = round(us("batched_kv164") / us(other), 4)
+        for other in ("batched", "batched_kv8"):
+            res[f"byte_ratio_batched_kv164_over_{other}"] = round(res["batched_kv164"]["bytes_per_layer_call"] / res[other]["bytes_per_layer_call"], 4)
+    if "ragged_kv164" in res:
+        for other in ("ragged", "ragged_kv8", "ragged_kv84"):
+            res[f"ratio_ragged_kv164_over_{other}"] = round(us("ragged_kv164") / us(other), 4)
+        res["ratio_ragged_kv164_over_batched_kv164_at_envelope"] = round(us("ragged_kv164") / us("batched_kv164"), 4)
     if "batched_kv84" in res:
         for other in ("batched", "batched_kv8", "batched_kv4", "batched_kv6", "solo_kv84_deferred"):
-            res[f"ratio_batched_kv84_over_{other}"] = round(us("batched_kv84") / us(other), 4)
+            if other in res:      # (the legs of the run: --k16-mxfp4 has no MXFP4 / MXFP6 leg and no kv84 solo leg)
+                res[f"ratio_batched_kv84_over_{other}"] = round(us("batched_kv84") / us(other), 4)
         for other in ("batched", "batched_kv8"):
             res[f"byte_ratio_batched_kv84_over_{other}"] = round(res["batched_kv84"]["bytes_per_layer_call"] / res[other]["bytes_per_layer_call"], 4)
     if "ragged_kv84" in res:
-        for other in ("ragged", "ragged_kv8", "ragged_kv4", "ragged_kv6"):
+        for other in (o for o in ("ragged", "ragged_kv8", "ragged_kv4", "ragged_kv6") if o in res):
             res[f"ratio_ragged_kv84_over_{other}"] = round(us("ragged_kv84") / us(other), 4)
         res["ratio_ragged_kv84_over_batched_kv84_at_envelope"] = round(us("ragged_kv84") / us("batched_kv84"), 4)
     if "ragged_kv8" in res:
@@ -415,10 +429,12 @@ def main():
                     "batched / ragged legs of the same run (default --out: profiles/batch_kv6_bench.json)")
     ap.add_argument("--fp8-mxfp4", action="store_true", help="the FP8-key / MXFP4-value legs batched_kv84, solo_kv84_deferred, ragged_kv84 next to the 16-bit, "
                     "FP8, MXFP4 and MXFP6 batched / ragged legs of the same run (default --out: profiles/batch_kv84_bench.json)")
+    ap.add_argument("--k16-mxfp4", action="store_true", help="the 16-bit-key / MXFP4-value legs batched_kv164, solo_kv164_deferred, ragged_kv164 next to the "
+                    "16-bit, FP8 and FP8-key / MXFP4-value batched / ragged legs of the same run (default --out: profiles/batch_kv164_bench.json)")
     ap.add_argument("--gqa4-batches", default="8,32", help="--mxfp4: batch sizes of the GQA x 4 table ('' = none)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    args.out = args.out or os.path.join(ROOT, "profiles", "batch_kv84_bench.json" if args.fp8_mxfp4 else "batch_kv6_bench.json" if args.mxfp6 else "batch_kv4_bench.json" if args.mxfp4 else ("batch_kv8_bench.json" if args.kv8 else "batch_bench.json"))
+    args.out = args.out or os.path.join(ROOT, "profiles", "batch_kv164_bench.json" if args.k16_mxfp4 else "batch_kv84_bench.json" if args.fp8_mxfp4 else "batch_kv6_bench.json" if args.mxfp6 else "batch_kv4_bench.json" if args.mxfp4 else ("batch_kv8_bench.json" if args.kv8 else "batch_bench.json"))
     torch.cuda.set_device(0)
     res = {"device": torch.cuda.get_device_name(0), "reps": args.reps, "tokens_per_rep": args.tokens, "warm_tokens": args.warm,
            "hbm_peak_gb_per_s": HBM_PEAK_GBS,

@@ -21,7 +21,10 @@ in the same way — fp16, fp8, mxfp4 and mxfp6 interleaved on copies of the same
 head_dim / 32 bytes per row pair, MXFP6's 200 at head_dim 128) — fp16, fp8, mxfp4, mxfp6 and fp8_mxfp4 interleaved on copies of the same
 rows — and writes profiles/kv84_bench.json.
 
-Usage: python tools/bench_kv8.py [--reps 15] [--steps 20] [--warm 1000] [--mxfp4 | --mxfp6 | --fp8-mxfp4] [--out profiles/kv8_bench.json]"""
+--k16-mxfp4 runs four legs — fp16, fp8, fp8_mxfp4 and 16-bit keys with MXFP4 values (KVBank.quantize_k16_mxfp4: 2 * head_dim + head_dim / 2
++ head_dim / 32 bytes per row pair, 324 at head_dim 128) — interleaved on copies of the same rows, and writes profiles/kv164_bench.json.
+
+Usage: python tools/bench_kv8.py [--reps 15] [--steps 20] [--warm 1000] [--mxfp4 | --mxfp6 | --fp8-mxfp4 | --k16-mxfp4] [--out profiles/kv8_bench.json]"""
 from __future__ import annotations
 
 import argparse
@@ -57,6 +60,10 @@ def step_bytes(kind, L, H, Hq, D, T, n_state=3):
         b = dict(total=kv + new + 2 * Hq * D * 2 + 2 * n_state * H * T * 4, kv=kv)
     elif kind == "fp8_mxfp4":
         pair = 3 * D // 2 + 4 + D // 32           # K: one byte per element + the row scale; V: half a byte per element + one exponent byte per 32
+        kv = H * T * pair
+        b = dict(total=kv + H * pair + 2 * Hq * D * 2 + 2 * n_state * H * T * 4, kv=kv)
+    elif kind == "k16_mxfp4":
+        pair = 2 * D + D // 2 + D // 32           # K: the 16-bit row; V: half a byte per element + one exponent byte per 32
         kv = H * T * pair
         b = dict(total=kv + H * pair + 2 * Hq * D * 2 + 2 * n_state * H * T * 4, kv=kv)
     else:
@@ -102,7 +109,7 @@ def make_bank(kind, L, H, D, budget):
     bank.score_sq[:, :, :budget] += warm ** 2
     if kind == "fp8":
         bank.quantize_fp8()
-    elif kind in ("mxfp4", "mxfp6", "fp8_mxfp4"):
+    elif kind in ("mxfp4", "mxfp6", "fp8_mxfp4", "k16_mxfp4"):
         bank.quantize(kind)
     return bank, g
 
@@ -153,7 +160,7 @@ def leg(name, maker, shape, reps, steps, warm, per=1, kinds=("fp16", "fp8")):
     res["time_ratio_fp8_over_fp16"] = round(res["fp8"]["us_per_launch"] / res["fp16"]["us_per_launch"], 4)
     res["byte_ratio_fp8_over_fp16"] = round(res["fp8"]["bytes_per_launch"] / res["fp16"]["bytes_per_launch"], 4)
     res["faster_by_more_than_the_fp16_spread"] = bool(1.0 - res["time_ratio_fp8_over_fp16"] > res["fp16"]["run_to_run_spread"])
-    for mx in ("mxfp4", "mxfp6", "fp8_mxfp4"):
+    for mx in ("mxfp4", "mxfp6", "fp8_mxfp4", "k16_mxfp4"):
         if mx in kinds:
             for other in kinds[:kinds.index(mx)]:
                 res[f"time_ratio_{mx}_over_{other}"] = round(res[mx]["us_per_launch"] / res[other]["us_per_launch"], 4)
@@ -170,14 +177,18 @@ def main():
     ap.add_argument("--mxfp6", action="store_true", help="add the MXFP4 and MXFP6 legs to the head_dim-128 runs; the default --out becomes profiles/kv6_bench.json")
     ap.add_argument("--fp8-mxfp4", action="store_true", help="add the MXFP4, MXFP6 and FP8-key / MXFP4-value legs to the head_dim-128 runs; the default "
                     "--out becomes profiles/kv84_bench.json")
+    ap.add_argument("--k16-mxfp4", action="store_true", help="the fp16, FP8, FP8-key / MXFP4-value and 16-bit-key / MXFP4-value legs of the head_dim-128 "
+                    "runs; the default --out becomes profiles/kv164_bench.json")
     ap.add_argument("--out", default=None)
     ap.add_argument("--only", default=None, help="run one leg: fused_d128, fused_d64 or deferred_d128 (nothing is written)")
     args = ap.parse_args()
-    name = "kv84_bench.json" if args.fp8_mxfp4 else ("kv6_bench.json" if args.mxfp6 else ("kv4_bench.json" if args.mxfp4 else "kv8_bench.json"))
+    name = "kv164_bench.json" if args.k16_mxfp4 else "kv84_bench.json" if args.fp8_mxfp4 else ("kv6_bench.json" if args.mxfp6 else ("kv4_bench.json" if args.mxfp4 else "kv8_bench.json"))
     out = args.out or os.path.join(ROOT, "profiles", name)
     kinds = ("fp16", "fp8", "mxfp4", "mxfp6") if args.mxfp6 else (("fp16", "fp8", "mxfp4") if args.mxfp4 else ("fp16", "fp8"))
     if args.fp8_mxfp4:
         kinds = ("fp16", "fp8", "mxfp4", "mxfp6", "fp8_mxfp4")
+    if args.k16_mxfp4:
+        kinds = ("fp16", "fp8", "fp8_mxfp4", "k16_mxfp4")
     torch.cuda.set_device(0)
     res = {"device": torch.cuda.get_device_name(0), "reps": args.reps, "steps": args.steps, "warm": args.warm, "hbm_peak_gb_per_s": HBM_PEAK_GBS,
            "shape": "32 layers x 32 heads, budget 2048 (T = 2049), roco, scattered slot map, warm score state"}
@@ -186,7 +197,7 @@ def main():
             "fused_d64": lambda: leg("fused_d64", fused_step, dict(shape, D=64), args.reps, args.steps, args.warm),
             # (per layer: one forward is 32 attention launches + the flush; bytes per layer likewise)
             "deferred_d128": lambda: leg("deferred_d128", deferred_step, shape, args.reps, max(4, args.steps // 4), max(20, args.warm // 32), per=32, kinds=kinds)}
-    if args.mxfp4 or args.mxfp6 or args.fp8_mxfp4:
+    if args.mxfp4 or args.mxfp6 or args.fp8_mxfp4 or args.k16_mxfp4:
         del legs["fused_d64"]      # (MXFP4 / MXFP6 / FP8-key MXFP4-value rows are head_dim 128's)
     for name, run in legs.items():
         if args.only in (None, name):
