@@ -43,6 +43,7 @@ FAMILIES = {
     "EKV_CHUNK_LDS": lambda d, elem: ("ekv_chunk_lds.inc", f"ekv_chunk_lds_d{d}" + _tags(elem), _on(elem) + [f"-DEKV_D={d}"]),
     "EKV_RESIDENT": lambda d, elem: ("ekv_attn_resident.inc", f"ekv_attn_resident_d{d}" + _tags(elem), _on(elem)),
     "EKV_SCORE_SELECT": lambda nt, elem: ("ekv_score_select.inc", f"ekv_score_select_nt{nt}" + _tags(elem), _on(elem) + [f"-DEKV_SS_NT={nt}"]),
+    "EKV_SCORE_LONG": lambda nt: ("ekv_score_long.inc", "ekv_score_long", [f"-DEKV_LONG_NT={nt}"]),
 }
 
 
@@ -96,7 +97,7 @@ def later_instances():
 
 
 def later_objects():
-    """(object name, hipcc arguments) of the instances of ekv_instances_later.def (the kv84 decode instances, then the kv164 ones)."""
+    """(object name, hipcc arguments) of the instances of ekv_instances_later.def (the kv84 decode instances, the kv164 ones, the long-row scorer)."""
     return _instance_objects(later_instances())
 
 

@@ -43,6 +43,10 @@ EXPORTS = ("ekv_abi_version", "ekv_strerror", "ekv_workspace_bytes", "ekv_step_p
            "ekv_kv6_quantize", "ekv_kv6_dequantize", "ekv_set_resident_bytes", "ekv_step_resident_rows", "ekv_kv84_quantize", "ekv_kv84_dequantize",
            "ekv_kv164_quantize", "ekv_kv164_dequantize") + tuple(
                step_call_name(rows, batch, what) for rows in (None, "kv8", "kv4", "kv6", "kv84", "kv164") for batch in (False, True) for what in STEP_CALLS)
+# the long-row family (include/easykv_hip.h, "long score rows"): the signatures of the _typed calls; 16-bit rows, one sequence
+LONG_CALLS = {what: "ekv_long_" + what for what in STEP_CALLS}
+EXPORTS += tuple(LONG_CALLS[what] for what in STEP_CALLS)
+LONG_INFO_N = 12      # EKV_LONG_INFO_N: [10] the step ends in the long-row scorer, [11] column tiles per head of its sweep
 
 
 class Bank(C.Structure):
@@ -138,6 +142,10 @@ def load():
             tails["step_attend"] = [vp] * (6 if batch else 8) + [C.c_size_t, vp]      # (a batch has no rope tables)
             for what in STEP_CALLS:
                 getattr(lib, step_call_name(rows, batch, what)).argtypes = head + tails[what]
+        if rows is None:      # (the long family: the uniform 16-bit signatures)
+            tails["step_attend"] = [vp] * 8 + [C.c_size_t, vp]
+            for what in STEP_CALLS:
+                getattr(lib, LONG_CALLS[what]).argtypes = [C.POINTER(Bank), C.POINTER(Step), i32] + tails[what]
         if desc:
             getattr(lib, f"ekv_{rows}_quantize").argtypes = [C.POINTER(Bank), C.POINTER(desc), i32, i32, i32, i32, vp]
             getattr(lib, f"ekv_{rows}_dequantize").argtypes = [C.POINTER(Bank), C.POINTER(desc), i32, i32, i32, i32, vp, vp, vp]

@@ -99,7 +99,7 @@ class BudgetedKVCache:
     converted to it and the attention output comes back in it.  A bf16 bank has no RoPE-on-read build (``streaming``)."""
 
     def __init__(self, n_layers, n_q_heads, n_kv_heads, head_dim, cap, device, streaming=False, rope=None,
-                 record=False, layer_begin=0, layer_count=None, rope_base=10000.0, dtype=None):
+                 record=False, layer_begin=0, layer_count=None, rope_base=10000.0, dtype=None, long_rows=False):
         self.layer_begin = layer_begin
         self.layer_count = n_layers - layer_begin if layer_count is None else layer_count
         if not (0 <= self.layer_begin and self.layer_count >= 1 and self.layer_begin + self.layer_count <= n_layers):
@@ -108,7 +108,8 @@ class BudgetedKVCache:
         dtype = torch.float16 if dtype is None else dtype
         if dtype is torch.bfloat16 and streaming:
             raise ValueError("a bf16 K/V bank has no RoPE-on-read build: streaming=True needs kv_dtype='float16'")
-        self.bank = KVBank(self.layer_count, n_q_heads, n_kv_heads, head_dim, cap, device=device, dtype=dtype)
+        # long_rows: the bank's steps go to the long-row call family (KVBank(long_rows=True): score rows of any width up to cap)
+        self.bank = KVBank(self.layer_count, n_q_heads, n_kv_heads, head_dim, cap, device=device, dtype=dtype, long_rows=long_rows)
         # no resident rows behind a model: its weights (gigabytes) stream through the Infinity Cache between two attention launches
         # of a layer, and plain loads that miss cost more than non-temporal ones ("resident rows": the harm run)
         self.bank.resident_bytes = 0
@@ -394,6 +395,15 @@ class _Run:
                 raise ValueError(f"generation_config['kv_quant'] = {kv_quant!r} with kv_mode='ppl': there is no decode phase to quantise the bank for")
             if shard is not None:
                 raise ValueError(f"generation_config['kv_quant'] = {kv_quant!r} is not supported on a layer-sharded model (model.layer_shard)")
+        # extension key: False (default) or True — the steps of the run's bank go to the long-row call family (KVBank(long_rows=True)):
+        # scored steps of any width up to the cache's capacity, where the plain family refuses beyond about 38 400 score columns; same
+        # tokens and evictions wherever both run.  16-bit rows and single sequences only (generate_batch refuses it).
+        self.long_rows = cfg.get("long_rows", False)
+        if self.long_rows not in (False, True):
+            raise ValueError(f"generation_config['long_rows'] must be False or True, not {self.long_rows!r}")
+        if self.long_rows and kv_quant is not None:
+            raise ValueError(f"generation_config['long_rows'] = True with kv_quant = {kv_quant!r}: the long-row scorer is built for 16-bit rows, "
+                             "and the quantised decode calls have no long form")
         self.dims = n_layers, hq, hkv, d = _dims(model)
         if fmt is not None and d not in fmt["head_dims"]:
             raise ValueError(f"generation_config['kv_quant'] = {kv_quant!r} needs head_dim {' or '.join(map(str, fmt['head_dims']))} (this model: {d})")
@@ -450,7 +460,8 @@ class _Run:
             from . import hf
             hf_rope = hf.rope_tables_from_model(self.model, max(cap + 8, length + self.max_new_tokens + 1) + 64, d, self.dev)
         cache = BudgetedKVCache(n_layers, hq, h, d, cap + 8, self.dev, streaming=self.streaming, record=self.record, rope=hf_rope,
-                                layer_begin=self.layers[0], layer_count=self.layers[1], rope_base=self.rope_base, dtype=self.kv_dtype)
+                                layer_begin=self.layers[0], layer_count=self.layers[1], rope_base=self.rope_base, dtype=self.kv_dtype,
+                                **(dict(long_rows=True) if self.long_rows else {}))      # (opt-in: named only when asked for)
         cache.unrotate = hf_rope if self.hf_stream else None
         return cache
 
@@ -821,6 +832,8 @@ def generate_batch(self, input_ids_list, generation_config, kv_mode="encoding", 
         raise ValueError("generate_batch: generation_config['hipgraph'] is not supported")
     if getattr(self, "layer_shard", None) is not None and self.layer_shard.world > 1:
         raise ValueError("generate_batch is not supported on a layer-sharded model (model.layer_shard)")
+    if cfg.get("long_rows", False):
+        raise ValueError("generate_batch: generation_config['long_rows'] has no batched decode step (the long-row scorer serves single sequences)")
     if cfg.get("kv_quant", None) == "mxfp4":
         raise ValueError("generate_batch: generation_config['kv_quant'] = 'mxfp4' has no batched decode step (use 'fp8' or None)")
     prompts = [p.view(1, -1) if p.dim() == 1 else p for p in input_ids_list]

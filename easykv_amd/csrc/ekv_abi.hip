@@ -132,6 +132,11 @@ static int call_attend(const EkvCall& c, const void* q, const void* k_new, const
       case EKV_RUN_DECODE_SCORE: e = ekv_launch_decode_score(sa, tb, lc, s, bf16); break;
       case EKV_RUN_TOVA_MEAN: e = ekv_launch_tova_headmean(sa, lc, s); break;
       case EKV_RUN_SCORE_SELECT: e = ekv_launch_score_select(sa, lc, s, bf16); break;
+      // long calls (L.passes: the plain plan keeps its rows in scratch)
+      case EKV_RUN_LONG_FOLD: e = ekv_launch_long_fold(sa, L.passes != 0, lc, s, bf16); break;
+      case EKV_RUN_LONG_SCORE:
+        e = ekv_launch_score_long(sa, P.key_rows < 0 ? nullptr : reinterpret_cast<uint32_t*>(ws + P.key_rows), L.passes != 0, lc, s);
+        break;
     }
     if (e != hipSuccess) return EKV_E_LAUNCH;
   }
@@ -172,6 +177,18 @@ int ekv_step_attend_typed(const ekv_bank* bank, const ekv_step* st, int32_t dtyp
                           const void* v_new, void* out, int32_t* evict_ids, const float* rope_cos, const float* rope_sin,
                           void* workspace, size_t workspace_bytes, void* stream) {
   return call_attend(step_call(bank, st, dtype), q, k_new, v_new, out, evict_ids, rope_cos, rope_sin, workspace, workspace_bytes, stream);
+}
+
+// long score rows (include/easykv_hip.h, "long score rows"): the _typed calls with the long-row scorer where the plan would end in the generic one
+int ekv_long_step_check(const ekv_bank* bank, const ekv_step* st, int32_t dtype) { return call_check(long_call(bank, st, dtype)); }
+int ekv_long_step_info(const ekv_bank* bank, const ekv_step* st, int32_t dtype, int32_t* info, int32_t n_info) {
+  return call_info(long_call(bank, st, dtype), info, n_info);
+}
+size_t ekv_long_workspace_bytes(const ekv_bank* bank, const ekv_step* st, int32_t dtype) { return call_workspace_bytes(long_call(bank, st, dtype)); }
+int ekv_long_step_attend(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const void* q, const void* k_new, const void* v_new,
+                         void* out, int32_t* evict_ids, const float* rope_cos, const float* rope_sin, void* workspace,
+                         size_t workspace_bytes, void* stream) {
+  return call_attend(long_call(bank, st, dtype), q, k_new, v_new, out, evict_ids, rope_cos, rope_sin, workspace, workspace_bytes, stream);
 }
 
 // FP8 K/V storage (include/easykv_hip.h, "kv8")

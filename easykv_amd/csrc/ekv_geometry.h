@@ -80,6 +80,27 @@ inline size_t ekv_score_lds_bytes(int nt, const ScoreArgs& a) {
 // generic scorer: S / Q / C + keys of W columns do not fit 160 KB of LDS (decided at workspace-planning time, before the arguments
 // exist: the 512-thread build with all four arrays in LDS)
 inline bool ekv_score_rows_exceed_lds(int W, int rows) { return ekv_score_lds_bytes(512, W, rows, false) > 160 * 1024; }
+// Threads per workgroup the generic scorer's dispatch picks for a launch of `pairs` (head, layer) pairs (ekv_score_select_dispatch.hip;
+// its reasons are there).  The 512-thread build folds key-range partials in batches of 16, the other two in batches of 8 (a 1024-thread
+// launch bound leaves 64 VGPRs): the long-row scorer folds in the batches of the build the plain call would have run, so that the
+// row statistics and the folded output keep their bits.
+inline int ekv_score_select_threads(int64_t pairs, int64_t W, int64_t rows, bool big) {
+  if (big) return 1024;
+  if (pairs >= 768 && ekv_score_lds_bytes(256, W, rows, false) <= 53 * 1024) return 256;
+  const bool one_per_cu = pairs <= 256 || ekv_score_lds_bytes(512, W, rows, false) > 80 * 1024;
+  if (one_per_cu && ekv_score_lds_bytes(1024, W, rows, false) <= 160 * 1024) return 1024;
+  return 512;
+}
+
+// ---- long-row scorer (ekv_score_long.inc): sweep over column tiles, then one select workgroup per head -------------------------------
+constexpr int kLongSweepNT = 256;      // threads of a sweep workgroup, four consecutive columns each
+constexpr int kLongTile = 4 * kLongSweepNT;      // columns per sweep workgroup
+constexpr int kLongSelectNT = 1024;    // threads of the select workgroup
+inline int64_t ekv_long_tiles(int64_t W) { return W <= 0 ? 0 : (W + kLongTile - 1) / kLongTile; }
+// sweep: (M, 1 / L) of the `rows` logits rows (0 when column sums replace the logits) — its only LDS, whatever the width
+inline size_t ekv_long_sweep_lds(int64_t rows) { return (size_t)2 * (size_t)rows * 4; }
+// select: reduction scratch | histogram | candidate list (the keys are in global scratch)
+constexpr size_t ekv_long_select_lds() { return 2 * (kLongSelectNT / 64) * 8 * 4 + 264 * 4 + kLongSelectNT * 8; }
 
 // ---- scorer as the tail of the wide column-sum pass and of the logits-resident kernel (ekv_wide_tail.h), nt threads ------------------
 inline size_t ekw_tail_lds_bytes(int nt, int W) {      // keys | reduction scratch | histogram | candidate list

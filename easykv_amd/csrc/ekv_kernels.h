@@ -26,7 +26,9 @@ enum EkvLaunchKind : int32_t {
   EKV_RUN_DECODE,         // ekv_launch_attn_decode: split decode attention
   EKV_RUN_CHUNK,          // ekv_launch_attn_chunk
   EKV_RUN_FLUSH,          // ekv_launch_attn_chunk: the deferred column-sum pass of all layers, from the kept queries
-  EKV_RUN_FOLD, EKV_RUN_RANGE, EKV_RUN_DECODE_SCORE, EKV_RUN_TOVA_MEAN, EKV_RUN_SCORE_SELECT
+  EKV_RUN_FOLD, EKV_RUN_RANGE, EKV_RUN_DECODE_SCORE, EKV_RUN_TOVA_MEAN, EKV_RUN_SCORE_SELECT,
+  EKV_RUN_LONG_FOLD,      // ekv_launch_long_fold: the fold of a long call whose generic scorer would have folded the output itself
+  EKV_RUN_LONG_SCORE      // ekv_launch_score_long: sweep + select of the long-row scorer (two kernels) where the plain plan has EKV_RUN_SCORE_SELECT
 };
 struct EkvLaunch {
   int32_t kind, kernel_count;
@@ -68,6 +70,10 @@ struct EkvStepPlan {
   int32_t n_launches;   // kernel launches of the call: the sum of list[].kernel_count
   int32_t n_list;
   EkvLaunch list[6];
+  // long calls (ekv_long_*, ekv_plan.cpp "long rows"): the step ends in the long-row scorer; column tiles per head of its sweep; byte
+  // offset of its selection keys [layer_count][H][t_pad] uint32 (-1 = not in the layout)
+  int32_t long_rows, long_tiles;
+  int64_t key_rows;
 };
 // The table of a batched decode step as the kernels' batch instances receive it: BY VALUE, behind the argument structs of the uniform
 // kernel (2304 bytes of the 4 KB a launch may carry).  Workgroup (head, entry ll) shadows the per-step fields of its argument structs
@@ -188,6 +194,11 @@ hipError_t ekv_launch_tova_headmean(const EkvScoreArgs& a, int layer_count, hipS
 hipError_t ekv_launch_score_select(const EkvScoreArgs& a, int layer_count, hipStream_t s, bool bf16);
 hipError_t ekv_launch_decode_fused(const EkvAttnArgs& a, const EkvScoreArgs& sc, const EkvSeqTable* tb, int head_dim, int count, int nw,
                                    hipStream_t s, bool bf16, EkvRows rows);
+// Long-row scorer (ekv_score_long.inc; one build for fp16 and bf16 banks).  a.big_rows and key_rows ([layer_count][H][a.big_stride]
+// uint32) must be set.  plain_big: the plain call's plan of this step keeps its rows in scratch (it decides which build of the generic
+// scorer the plain call runs, and with it the batch width of the partials fold: ekv_score_select_threads).
+hipError_t ekv_launch_score_long(const EkvScoreArgs& a, uint32_t* key_rows, bool plain_big, int layer_count, hipStream_t s);
+hipError_t ekv_launch_long_fold(const EkvScoreArgs& a, bool plain_big, int layer_count, hipStream_t s, bool bf16);
 // What workgroup (head, entry z) of a batch instance does first: its argument structs are the envelope's with the per-step fields
 // replaced by its entry's (scalar loads from the kernel arguments).  layer_begin = layer - z: every `layer_begin + ll` of the kernel
 // body then names the entry's bank layer, while the workspace and the call's tensors stay indexed by ll = z.

@@ -272,6 +272,7 @@ struct StepShape {
   i64 W;                  // score columns
   int LC;                 // layers the workspace is laid out for: all deferred layers (ekv_step.defer_layers), whatever this call launches
   int max_rows;           // rows an unsplit chunk workgroup may walk (its slot entries live in LDS): 6144 with RoPE-on-read, 16384 plain
+  bool long_rows;         // a long call (ekv_plan_step): the long-row scorer where the plan would end in the generic one
 };
 
 // ---- stage 1: tiling
@@ -548,9 +549,12 @@ int plan_ending(const StepShape& s, EkvStepPlan* P, StepEnding* end) {
   const bool fold_only = (!scored && st->n_evict == 0) || !wants_scorer;
   const bool range_only = wants_scorer && st->policy == EKV_POLICY_RANGE;
   const bool fast_scorer = wants_scorer && !fold_only && !range_only && !fuse_chunk && ekv_decode_score_supported(shape);
-  if (wants_scorer && !fold_only && !range_only && !fuse_chunk && !fast_scorer &&
-      ekv_score_lds_bytes(shape.big_rows != nullptr ? 1024 : 512, shape) > 160 * 1024)
+  const bool generic_scorer = wants_scorer && !fold_only && !range_only && !fuse_chunk && !fast_scorer;
+  if (generic_scorer && !s.long_rows && ekv_score_lds_bytes(shape.big_rows != nullptr ? 1024 : 512, shape) > 160 * 1024)
     return EKV_E_UNSUPPORTED;   // even the selection keys alone exceed one CU's LDS (W > ~39 000): see DESIGN.md "size limits"
+  // (a long call: the keys are in scratch, so no width bound; what its sweep keeps in LDS is the (M, 1 / L) pair of every logits row —
+  //  the term the bound above also carries, and the same 160 KB)
+  if (generic_scorer && s.long_rows && ekv_long_sweep_lds(shape.colsum != nullptr ? 0 : (i64)rep * n) > 160 * 1024) return EKV_E_UNSUPPORTED;
   if (n == 1 ? !ekv_attn_decode_supported(D, rep) : !ekv_attn_chunk_supported(D, rep, n)) return EKV_E_UNSUPPORTED;
 
   // decode split path whose partials are folded right behind the attention kernel (attention + fold phases, or a step that has
@@ -615,9 +619,35 @@ int plan_launches(const StepShape& s, EkvStepPlan* P) {
     run(P, EKV_RUN_DECODE_SCORE, 1, skip_fold);
     return EKV_OK;
   }
+  // a long call, exactly here: a fold launch of its own where the generic scorer would have folded the output, then sweep + select in
+  // place of the generic scorer's launch.  `passes` of the two entries: 1 = the plain plan keeps its score rows in scratch (which build
+  // of the generic scorer the plain call runs, and with it the batches its fold takes the partials in: ekv_score_select_threads)
+  const int plain_big = P->big_rows >= 0 ? 1 : 0;
+  if (s.long_rows && !skip_fold) run(P, EKV_RUN_LONG_FOLD, 1, 0, plain_big);
   if (st->policy == EKV_POLICY_TOVA && st->tova_head_mean && st->accumulate) run(P, EKV_RUN_TOVA_MEAN, 1, skip_fold);
+  if (s.long_rows) {
+    run(P, EKV_RUN_LONG_SCORE, 2, 1, plain_big);
+    P->long_rows = 1;
+    P->long_tiles = (int32_t)ekv_long_tiles(s.W);
+    return EKV_OK;
+  }
   run(P, EKV_RUN_SCORE_SELECT, 1, skip_fold);
   return EKV_OK;
+}
+
+// ---- stage 5, long calls only: the scratch of the long-row scorer, BEHIND everything the plain layout holds (every other offset, and
+// with it every other kernel's view of the workspace, is the plain call's): the working copies of the score rows unless the plain
+// layout has them already, then the selection keys, one row of t_pad words per (layer, head); a deferred call's slices as in plan_checks
+void plan_long_layout(const StepShape& s, EkvStepPlan* P) {
+  const size_t LC = (size_t)s.LC, H = (size_t)s.bank->n_kv_heads, li = s.st.defer_layers != 0 ? (size_t)s.st.defer_index : 0;
+  size_t off = P->bytes;
+  if (P->big_rows < 0) {
+    P->big_rows = (int64_t)(off + li * H * 3 * P->t_pad * 4);
+    off += ekv_align(LC * H * 3 * P->t_pad * 4, 256);
+  }
+  P->key_rows = (int64_t)(off + li * H * P->t_pad * 4);
+  off += ekv_align(LC * H * P->t_pad * 4, 256);
+  P->bytes = off;
 }
 
 }  // namespace
@@ -625,8 +655,16 @@ int plan_launches(const StepShape& s, EkvStepPlan* P) {
 // The whole dispatch of ekv_step_attend for a step, in four stages: the tiling, the workspace layout, the argument / shape / capability
 // checks (the return code of the call, in the order the call reports them) and the launch sequence (whole-step kernels, else ending + launches).  The tiling and the layout are
 // filled in for every step that has something to tile, also when the step is refused (ekv_workspace_bytes and ekv_step_info report them).
-int ekv_plan_step(const ekv_bank* bank, const ekv_step* step, EkvStepPlan* P) {
+//
+// Long rows (the ekv_long_* calls), the rule of the family stated once: a long call plans exactly as the plain call of the same (bank,
+// step, dtype) — tiling, layout, checks, whole-step kernels, ending — except that wherever that plan would end in EKV_RUN_SCORE_SELECT
+// (whole steps, phases & 2, phases & 8, the deferred flush over all layers) it ends in the long-row scorer (ekv_score_long.inc:
+// EKV_RUN_LONG_SCORE, two kernels; a preceding EKV_RUN_TOVA_MEAN stays; EKV_RUN_LONG_FOLD in front where the generic scorer would have
+// folded the output itself), the width refusal of plan_ending does not apply, and the workspace grows by that scorer's scratch
+// (plan_long_layout).  A step that ends anywhere else plans field for field as the plain call.
+int ekv_plan_step(const ekv_bank* bank, const ekv_step* step, EkvStepPlan* P, bool long_rows) {
   *P = EkvStepPlan{};
+  P->key_rows = -1;
   const int bank_rc = check_bank(bank);
   if (!bank || !step) return bank_rc ? bank_rc : EKV_E_ARG;
   StepShape s{};
@@ -644,13 +682,16 @@ int ekv_plan_step(const ekv_bank* bank, const ekv_step* step, EkvStepPlan* P) {
   s.W = (i64)s.T - (s.scored ? step->score_off : 0);
   s.LC = step->defer_layers > 0 ? step->defer_layers : step->layer_count;
   s.max_rows = step->rope_on_read ? 6144 : 16384;
+  s.long_rows = long_rows;
 
   plan_tiling(s, P);
   plan_layout(s, P);
   if (int e = plan_checks(s, bank_rc, P)) return e;
   int rc;
   if (plan_whole_step(s, P, &rc)) return rc;
-  return plan_launches(s, P);
+  rc = plan_launches(s, P);
+  if (rc == EKV_OK && P->long_rows) plan_long_layout(s, P);
+  return rc;
 }
 
 // ---- one call ----------------------------------------------------------------------------------------------------------------------
@@ -736,13 +777,19 @@ int resolve_call(const EkvCall& c, EkvResolved* r) {
     r->tb = &r->table;
   }
 
-  const int rc = ekv_plan_step(bank, r->step, P);
+  // (a long call is a 16-bit, single-sequence call: its entry points spell nothing else, and no other combination has an instance)
+  const int rc = (c.long_rows && (quant || c.batch)) ? EKV_E_UNSUPPORTED : ekv_plan_step(bank, r->step, P, c.long_rows);
   P->bf16 = c.dtype == EKV_DTYPE_BF16;
   P->rows = c.rows;
   P->batch = c.batch;
   if (quant || c.batch) P->fused_order = 0;      // (the quantised and the batch instances keep order F)
   auto refuse = [&](int code) {
-    P->one_launch = P->n_launches = P->n_list = 0;
+    if (P->long_rows) {      // (a long plan that is refused after all reports the layout of the plain call: nothing of the long scorer remains)
+      EkvStepPlan plain;
+      (void)ekv_plan_step(bank, r->step, &plain);
+      P->bytes = plain.bytes, P->big_rows = plain.big_rows, P->key_rows = -1;
+    }
+    P->one_launch = P->n_launches = P->n_list = P->long_rows = P->long_tiles = 0;
     if (c.batch) P->bytes = 0;      // (nothing will run: ekv_batch_workspace_bytes of a refused table is 0)
     return code;
   };
@@ -801,6 +848,10 @@ int call_info(const EkvCall& c, int32_t* info, int32_t n_info) {
                                       P.fold_in_kernel, ok ? P.n_launches : 0, ok ? (P.fused_order & 3) : 0};
   for (int i = 0; i < n_info && i < EKV_STEP_INFO_N; ++i) info[i] = v[i];
   for (int i = EKV_STEP_INFO_N; i < n_info; ++i) info[i] = 0;
+  if (c.long_rows) {      // ekv_long_step_info: does the step end in the long-row scorer, and the column tiles per head of its sweep
+    if (n_info > 10) info[10] = ok ? P.long_rows : 0;
+    if (n_info > 11) info[11] = ok ? P.long_tiles : 0;
+  }
   return EKV_OK;
 }
 

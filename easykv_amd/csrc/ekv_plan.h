@@ -43,7 +43,8 @@ int ekv_attn_chunk_launches(bool wide, bool rope, bool two_pass, int passes);
 
 // The scalar (shape) fields of the scorer's arguments; call_attend adds the pointers.
 EkvScoreArgs score_args(const ekv_bank* bank, const ekv_step* st, const EkvStepPlan& P);
-int ekv_plan_step(const ekv_bank* bank, const ekv_step* step, EkvStepPlan* P);
+// long_rows: the plan of a long call (ekv_long_*; the rule is stated once, at ekv_plan_step in ekv_plan.cpp)
+int ekv_plan_step(const ekv_bank* bank, const ekv_step* step, EkvStepPlan* P, bool long_rows = false);
 
 // ---- one call path --------------------------------------------------------------------------------------------------------------
 // A call of the step family as its entry points spell it, along two independent axes: the row format of the bank (the untyped / _typed
@@ -70,11 +71,13 @@ struct EkvCall {
   bool batch;              // an ekv_*batch_* call
   const ekv_seq* seqs;
   int32_t n_seq;
+  bool long_rows;          // an ekv_long_* call: the long-row scorer where the plan would end in the generic one (16-bit rows, one sequence)
 };
 inline EkvCall step_call(const ekv_bank* bank, const ekv_step* st, int32_t dtype) { return {bank, st, dtype, EKV_ROWS_kv16, {}, false, nullptr, 0}; }
 inline EkvCall batch_call(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_seq* seqs, int32_t n_seq) {
   return {bank, st, dtype, EKV_ROWS_kv16, {}, true, seqs, n_seq};
 }
+inline EkvCall long_call(const ekv_bank* bank, const ekv_step* st, int32_t dtype) { return {bank, st, dtype, EKV_ROWS_kv16, {}, false, nullptr, 0, true}; }
 // the quantised calls: the same two with a row format and its planes
 inline EkvCall kv8_call(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_kv8* q8) {
   return {bank, st, dtype, EKV_ROWS_kv8, ekv_planes(q8), false, nullptr, 0};
@@ -123,6 +126,7 @@ int resolve_call(const EkvCall& c, EkvResolved* r);
 int call_check(const EkvCall& c);
 size_t call_workspace_bytes(const EkvCall& c);
 // ekv_step_info and its kin: the plan's answers also for a step the call would refuse (launch counts 0 then); argument errors first
+// (a long call: entries [10], [11] of EKV_LONG_INFO_N behind the ten of every call)
 int call_info(const EkvCall& c, int32_t* info, int32_t n_info);
 // ekv_step_resident_rows: the resident rows the call's launch is planned with (0 for every call but a one-launch decode step of the
 // instances that have them, and for a step the call would refuse); argument errors as negative codes

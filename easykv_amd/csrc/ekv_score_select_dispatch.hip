@@ -39,13 +39,18 @@ hipError_t ekv_launch_score_select(const EkvScoreArgs& a, int layer_count, hipSt
   if (force == 256 && ekv_score_lds_bytes(256, a) <= 160 * 1024) return nt256(a, layer_count, s);
   if (force == 512 && ekv_score_lds_bytes(512, a) <= 160 * 1024) return nt512(a, layer_count, s);
   if (force == 1024 && ekv_score_lds_bytes(1024, a) <= 160 * 1024) return nt1024(a, layer_count, s);
-  const bool small_blocks = a.n_kv_heads * layer_count >= 768 && ekv_score_lds_bytes(256, a) <= 53 * 1024;
-  if (small_blocks) return nt256(a, layer_count, s);
+  // (the rule itself is ekv_score_select_threads, ekv_geometry.h: the long-row scorer asks it which build the plain call would run)
+  // 256 threads where the grid alone fills the chip and three workgroups fit a CU's LDS.
   // one workgroup per CU either way (at most one (head, layer) pair per CU, or LDS rows too wide for two): give it all 16
   // wave slots — the logits sweep is VALU-bound on exact expf / IEEE div and 2 waves per SIMD do not fill the pipeline
-  const bool one_per_cu = a.n_kv_heads * layer_count <= 256 || ekv_score_lds_bytes(512, a) > 80 * 1024;
-  if (one_per_cu && ekv_score_lds_bytes(1024, a) <= 160 * 1024) return nt1024(a, layer_count, s);
-  return nt512(a, layer_count, s);
+  const bool scored = a.policy == EKV_POLICY_H2O_HEAD || a.policy == EKV_POLICY_ROCO || a.policy == EKV_POLICY_TOVA;
+  const int64_t W = (int64_t)a.n_slots - (scored ? a.score_off : 0);
+  const int64_t rows = a.colsum != nullptr ? 0 : (int64_t)(a.n_q_heads / a.n_kv_heads) * a.q_len;
+  switch (ekv_score_select_threads((int64_t)a.n_kv_heads * layer_count, W, rows, false)) {
+    case 256: return nt256(a, layer_count, s);
+    case 1024: return nt1024(a, layer_count, s);
+    default: return nt512(a, layer_count, s);
+  }
 }
 
 hipError_t ekv_launch_tova_headmean(const EkvScoreArgs& a, int layer_count, hipStream_t s) {

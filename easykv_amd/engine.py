@@ -153,8 +153,15 @@ class KVBank:
     resident_bytes = None
     kv_quant = None      # quantize(): "fp8" / "mxfp4" / "mxfp6" / "fp8_mxfp4" / "k16_mxfp4" (ROW_FORMATS; _fmt is the entry, _desc the descriptor of its planes)
 
-    def __init__(self, n_layers, n_q_heads, n_kv_heads, head_dim, cap, device="cuda", scored=True, dtype=torch.float16, kv_quant=None):
-        """``kv_quant='fp8'``: the bank is created holding FP8 planes only (see :meth:`quantize_fp8`); the 16-bit K/V rows are never
+    long_rows = False    # KVBank(..., long_rows=True): the steps go to the long-row family (ekv_long_*), set per bank by __init__
+
+    def __init__(self, n_layers, n_q_heads, n_kv_heads, head_dim, cap, device="cuda", scored=True, dtype=torch.float16, kv_quant=None, long_rows=False):
+        """``long_rows=True``: a 16-bit bank whose steps go to the long-row call family (include/easykv_hip.h, "long score rows"):
+        planned and run exactly as the plain calls, except that a scored step which would end in the generic scorer ends in the
+        long-row scorer instead, whose width is bounded by ``cap`` and the workspace, not by one CU's LDS (the plain family refuses
+        such a step beyond about 38 400 score columns).  Same bits wherever both run.  Not with ``kv_quant``, and :meth:`quantize`
+        refuses such a bank.
+        ``kv_quant='fp8'``: the bank is created holding FP8 planes only (see :meth:`quantize_fp8`); the 16-bit K/V rows are never
         allocated.  Such a bank is filled by decode steps or, as one sequence of a :class:`KVBankBatch`, by ``adopt()``.
         ``kv_quant='mxfp4'``: likewise with MXFP4 planes only (see :meth:`quantize_mxfp4`; head_dim 128, GQA factors up to 4).
         ``kv_quant='mxfp6'``: likewise with MXFP6 planes only (see :meth:`quantize_mxfp6`; the same shapes).
@@ -164,6 +171,10 @@ class KVBank:
         if dtype not in _lib.DTYPE_CODES:
             raise ValueError(f"KVBank dtype must be torch.float16 or torch.bfloat16, not {dtype}")
         fmt = row_format(kv_quant, "KVBank kv_quant")
+        if long_rows and fmt is not None:
+            raise _lib.EkvError(f"KVBank(long_rows=True): the long-row scorer is built for 16-bit rows, not for {fmt['label']} rows "
+                                f"(kv_quant={kv_quant!r}): a quantised bank serves decode steps through its own calls, which have no long form")
+        self.long_rows = bool(long_rows)
         if fmt is not None:
             _check_row_shape(fmt, head_dim, n_q_heads // max(1, n_kv_heads))
         self.dtype, self._dt = dtype, _lib.DTYPE_CODES[dtype]
@@ -319,6 +330,9 @@ class KVBank:
         if fmt is None:
             raise ValueError("quantize(kind): kind must be 'fp8' or 'mxfp4'")
         m = fmt["method"] + "()"
+        if self.long_rows:
+            raise _lib.EkvError(f"{m}: the bank was created with long_rows=True, and the long-row scorer is built for 16-bit rows, not "
+                                f"for {fmt['label']} rows: {fmt['label']} rows have no long form")
         if self._fmt is not None:
             raise _lib.EkvError(f"{m}: the bank's rows are quantised already ({self._fmt['label']} already: kv_quant={self.kv_quant!r})")
         _check_row_shape(fmt, self.head_dim, self.n_q_heads // self.n_kv_heads)
@@ -393,6 +407,8 @@ class KVBank:
         self._calls = {(batch, what): getattr(self.lib, _lib.step_call_name(rows, batch, what))
                        for batch in (False, True) for what in _lib.STEP_CALLS}
         self._check_fn, self._info_fn, self._ws_fn, self._attend_fn = (self._calls[False, what] for what in _lib.STEP_CALLS)
+        if self.long_rows:      # (16-bit rows: __init__ and quantize() refuse every other format) the long family, same signatures
+            self._check_fn, self._info_fn, self._ws_fn, self._attend_fn = (getattr(self.lib, _lib.LONG_CALLS[what]) for what in _lib.STEP_CALLS)
 
     def kv_bytes(self) -> int:
         """Bytes held for the K/V rows: 16-bit rows, FP8 codes + row scales (``2 * head_dim + 8`` per row pair), or MXFP4 codes +
@@ -562,7 +578,7 @@ class KVBank:
         """(n_split, fused) the library will use for this step."""
         st = self.make_step(plan, q_len, layer_begin, self.n_layers - layer_begin if layer_count is None else layer_count)
         st.phases = phases
-        if self._fmt is not None:      # (the quantised dry run: a step the bank refuses plans as not fused)
+        if self._fmt is not None or self.long_rows:      # (the dry run of the bank's own family: a step the bank refuses plans as not fused)
             info = self.step_info(plan, q_len, layer_begin, layer_count, phases)
             return info["n_split"], bool(info["fused"])
         ns, fu = C.c_int32(0), C.c_int32(0)
@@ -573,9 +589,11 @@ class KVBank:
         """The library's dispatch decisions for this step (ekv_step_info): n_split, fused, two_pass, wide, n_qblocks, ..."""
         st = self.make_step(plan, q_len, layer_begin, self.n_layers - layer_begin if layer_count is None else layer_count)
         st.phases = phases
-        info = (C.c_int32 * 10)()
-        check(self._info_fn(C.byref(self._bank), C.byref(st), self._dt, *self._desc_ref, info, 10), self._info_fn.__name__)
-        keys = ("n_split", "fused", "two_pass", "wide", "n_qblocks", "qb_rows", "n_col_parts", "fold_in_kernel", "n_launches", "fused_order")
+        n_info = _lib.LONG_INFO_N if self.long_rows else 10
+        info = (C.c_int32 * n_info)()
+        check(self._info_fn(C.byref(self._bank), C.byref(st), self._dt, *self._desc_ref, info, n_info), self._info_fn.__name__)
+        keys = ("n_split", "fused", "two_pass", "wide", "n_qblocks", "qb_rows", "n_col_parts", "fold_in_kernel", "n_launches", "fused_order",
+                "long_scorer", "long_tiles")      # (the last two: a long_rows bank only)
         return dict(zip(keys, (int(x) for x in info)))
 
     def resident_rows(self, plan: StepPlan, q_len=1, layer_begin=0, layer_count=None, phases=0) -> int:
@@ -827,13 +845,16 @@ class KVBankBatch:
     :meth:`attend` serves model layer ``layer`` of any subset of the sequences — each with its own cache length, score offset and
     eviction geometry — in ONE call: one launch per kernel kind over the layers ``{s * n_layers + layer}``."""
 
-    def __init__(self, n_seq, n_layers, n_q_heads, n_kv_heads, head_dim, cap, device="cuda", scored=True, dtype=torch.float16, kv_quant=None):
+    def __init__(self, n_seq, n_layers, n_q_heads, n_kv_heads, head_dim, cap, device="cuda", scored=True, dtype=torch.float16, kv_quant=None, long_rows=False):
         """``kv_quant='fp8'``: the shared bank holds FP8 planes only from the start (the 16-bit rows of ``n_seq`` sequences are never
         allocated); its sequences are filled by :meth:`adopt` from banks quantised by :meth:`KVBank.quantize_fp8`.
         ``kv_quant='mxfp4'``: likewise with MXFP4 planes, filled from banks quantised by :meth:`KVBank.quantize_mxfp4`.
         ``kv_quant='mxfp6'``: likewise with MXFP6 planes (:meth:`KVBank.quantize_mxfp6`).
         ``kv_quant='fp8_mxfp4'``: likewise with FP8 key and MXFP4 value planes (:meth:`KVBank.quantize_fp8_mxfp4`).
         ``kv_quant='k16_mxfp4'``: the 16-bit K rows with MXFP4 value planes (:meth:`KVBank.quantize_k16_mxfp4`); no 16-bit V."""
+        if long_rows:
+            raise _lib.EkvError("KVBankBatch(long_rows=True): the long-row scorer is built for single sequences, not for decode batches: "
+                                "the batched calls have no long form (what a batch leaves to the generic scorer it refuses)")
         if not 1 <= n_seq <= _lib.MAX_SEQS:
             raise ValueError(f"a decode batch holds 1..{_lib.MAX_SEQS} sequences, not {n_seq}")
         self.n_seq, self.n_layers = n_seq, n_layers

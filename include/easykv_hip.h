@@ -492,6 +492,30 @@ int ekv_kv164_step_attend(const ekv_bank *bank, const ekv_step *step, int32_t dt
                           const void *k_new, const void *v_new, void *out, int32_t *evict_ids, const float *rope_cos,
                           const float *rope_sin, void *workspace, size_t workspace_bytes, void *stream);
 
+/* Long score rows (ABI 8, additive): the *_typed calls of a 16-bit bank with a scorer whose row width is bounded by memory, not by one
+ * CU's LDS.  The plain calls refuse a scored step with EKV_E_UNSUPPORTED once a head's score row has more than about 38 400 columns (the
+ * generic scorer keeps its selection keys in LDS); the attention kernels have no such bound.  A long call plans exactly as the plain call
+ * of the same (bank, step, dtype) — same tiling, same attention launches, same return codes for argument errors and for what an attention
+ * kernel refuses — except where that plan would end in the generic scorer launch (whole steps, phases & 2, phases & 8, the deferred
+ * flush over all layers).  There the long scorer runs instead, in two launches: a sweep over (column tile, head, layer) that builds the
+ * working copies of the score rows and the selection keys in workspace scratch, and one 1024-thread workgroup per (head, layer) that
+ * selects and compacts with its keys in that scratch.  Where the generic scorer would have folded the key-range partials into `out`
+ * itself, a fold launch of the long family precedes the sweep.  The width refusal does not apply: n_slots is bounded by cap and the
+ * workspace alone.  The arithmetic, its order and the selection rule (the k smallest (key, index) pairs, ties to the lowest index, NaN
+ * largest) are the generic scorer's: wherever both families run, out, evict_ids, the slot map and the score rows are equal bit for bit.
+ * Steps that end in another scorer (the one-launch kernels, the fast decode scorer, a kernel tail, the range compaction) plan and run
+ * field for field as the plain call.  16-bit rows and single sequences only: the quantised and the batched calls have no long form.
+ * ekv_long_step_info fills the EKV_STEP_INFO_N fields of the plain info call, then [10] = 1 when the step ends in the long scorer (0
+ * otherwise, and for a step the call refuses) and [11] = the column tiles per head of its sweep (0 likewise); entries beyond
+ * EKV_LONG_INFO_N are zeroed. */
+#define EKV_LONG_INFO_N 12
+int ekv_long_step_check(const ekv_bank *bank, const ekv_step *step, int32_t dtype);
+int ekv_long_step_info(const ekv_bank *bank, const ekv_step *step, int32_t dtype, int32_t *info, int32_t n_info);
+size_t ekv_long_workspace_bytes(const ekv_bank *bank, const ekv_step *step, int32_t dtype);
+int ekv_long_step_attend(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const void *q, const void *k_new,
+                         const void *v_new, void *out, int32_t *evict_ids, const float *rope_cos, const float *rope_sin,
+                         void *workspace, size_t workspace_bytes, void *stream);
+
 /* Batched decode steps (ABI 8, additive): ONE call, and one launch per kernel kind, serves n_seq sequences whose caches have
  * different lengths and different eviction geometry.  Each entry of the table names the bank layer it attends and carries what
  * ekv_step holds per step; entry i owns row i of the call's tensors.  The layers of a table need not be contiguous or ordered, so
