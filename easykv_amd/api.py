@@ -40,7 +40,7 @@ from typing import List, Optional
 import torch
 
 from . import _lib
-from .engine import KVBank, KVBankBatch, StepPlan, row_format
+from .engine import PLAIN_KEYS_HEAD_DIMS, KVBank, KVBankBatch, StepPlan, row_format
 
 KNOWN_POLICIES = ("roco", "h2o_head", "tova", "recency", "random", "full")
 SCORED = ("roco", "h2o_head", "tova")
@@ -405,6 +405,8 @@ class _Run:
             raise ValueError(f"generation_config['long_rows'] = True with kv_quant = {kv_quant!r}: the long-row scorer is built for 16-bit rows, "
                              "and the quantised decode calls have no long form")
         self.dims = n_layers, hq, hkv, d = _dims(model)
+        if streaming and d in PLAIN_KEYS_HEAD_DIMS:
+            raise ValueError(f"streaming=True: RoPE-on-read has no build for head_dim {d} (plain keys only)")
         if fmt is not None and d not in fmt["head_dims"]:
             raise ValueError(f"generation_config['kv_quant'] = {kv_quant!r} needs head_dim {' or '.join(map(str, fmt['head_dims']))} (this model: {d})")
         if fmt is not None and fmt["max_rep"] is not None and hq // hkv > fmt["max_rep"]:

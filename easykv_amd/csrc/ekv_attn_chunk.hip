@@ -88,7 +88,7 @@ hipError_t ekv_launch_attn_chunk(const EkvAttnArgs& a, int head_dim, int layer_c
   if (two_pass && (fuse_sc != nullptr || a.stats == nullptr || a.colsum == nullptr)) return hipErrorInvalidValue;
   if (tail_sc != nullptr && !(wide && two_pass && (passes & 2))) return hipErrorInvalidValue;
   int qb_rows, n_qblocks, qpw;
-  ekv_chunk_blocks(a.n_q_heads / a.n_kv_heads, a.q_len, &qb_rows, &n_qblocks, &qpw);
+  ekv_chunk_blocks(a.n_q_heads / a.n_kv_heads, a.q_len, &qb_rows, &n_qblocks, &qpw, head_dim);
   const bool rope = a.rope_cos != nullptr;
   if (bf16 && rope) return hipErrorInvalidValue;   // (no bf16 RoPE-on-read build)
   if (rope && !wide) {      // (the wide-block kernel rotates its query rows itself, in the lane that holds them)

@@ -690,10 +690,10 @@ __global__ void __launch_bounds__(64 * NW, (NW == 16 || (NW == 8 && EKV_CHUNK_MO
 
 template <int QPW, bool ROPE, int NW>
 hipError_t launch_k(const EkvAttnArgs& a, int layer_count, hipStream_t s, const EkvScoreArgs* fuse_sc) {
-  size_t lds = ekv_align((size_t)a.rows_per_split * 4, 16) + (size_t)((ROPE ? 3 : 2) - (EKV_CHUNK_MODE == 1 ? 1 : 0)) * kKT * (EKV_D + kPadH) * 2 +
-               (EKV_Q_LDS(QPW, ROPE, NW) ? (size_t)(ROPE ? 2 : 1) * 16 * QPW * (NW / 2) * (EKV_D + kPadH) * 2 : 0);   // + the query block
-  if (NW == 16 && a.out_direct != nullptr)   // the in-kernel fold of the two key halves exchanges NWQ x 64 x (D + 2) floats through LDS
-    lds = std::max(lds, ekv_align((size_t)a.rows_per_split * 4, 16) + (size_t)(NW / 2) * 64 * ((EKV_D / 16) * 4 + 2) * 4);
+  // slot entries | tiles | the query block; the 16-wave in-kernel fold exchanges NWQ x 64 x (D + 2) floats (ekv_geometry.h, where the planner reads it too)
+  static_assert(kKT == kChunkKT && kPadH == kChunkPadH && EKV_Q_LDS(QPW, ROPE, NW) == ekv_chunk_q_in_lds(EKV_CHUNK_MODE, QPW, ROPE, NW),
+                "the LDS plan of ekv_geometry.h is this kernel's");
+  size_t lds = ekv_chunk_kernel_lds(EKV_D, EKV_CHUNK_MODE, QPW, ROPE, NW, a.rows_per_split, a.out_direct != nullptr);
   const dim3 grid(a.n_kv_heads, a.n_split * a.n_qblocks, layer_count);
 #if EKV_CHUNK_MODE == 0
   if (fuse_sc != nullptr) {
@@ -719,8 +719,15 @@ hipError_t launch_k(const EkvAttnArgs& a, int layer_count, hipStream_t s, const 
 hipError_t EKV_FN_CHUNK(EKV_D, EKV_CHUNK_MODE, EKV_ELEM)(const EkvAttnArgs& a, int qpw, int layer_count, hipStream_t s,
                                                                                     const EkvScoreArgs* fuse_sc) {
   const bool rope = a.rope_cos != nullptr;
-  constexpr bool R = !EKV_BF16;   // (RoPE-on-read builds: fp16 only)
+  constexpr bool R = !EKV_BF16 && EKV_D < kChunkNarrowD;   // (RoPE-on-read builds: fp16 only, head_dim <= 128)
   if (rope && !R) return hipErrorInvalidValue;
+#if EKV_D >= 256
+  // head_dim 256: the one-tile build alone (ekv_chunk_blocks plans blocks of <= 32 rows).  Its 16 output blocks, 16 staged pieces and 8
+  // query operands per lane are 254-255 VGPRs without scratch; the two-tile builds spill (448+ bytes of scratch per lane) and are not built.
+  static_assert(EKV_D == kChunkNarrowD && EKV_D % 32 == 0, "head_dim 256 is the narrow-block head_dim of ekv_geometry.h");
+  if (qpw != 1) return hipErrorInvalidValue;
+  return launch_k<1, false, 4>(a, layer_count, s, fuse_sc);
+#else
   switch (qpw) {
     case 1: return rope ? launch_k<1, R, 4>(a, layer_count, s, fuse_sc) : launch_k<1, false, 4>(a, layer_count, s, fuse_sc);
     case 2: return rope ? launch_k<2, R, 4>(a, layer_count, s, fuse_sc) : launch_k<2, false, 4>(a, layer_count, s, fuse_sc);
@@ -732,4 +739,5 @@ hipError_t EKV_FN_CHUNK(EKV_D, EKV_CHUNK_MODE, EKV_ELEM)(const EkvAttnArgs& a, i
 #endif
     default: return hipErrorInvalidValue;
   }
+#endif
 }

@@ -40,14 +40,23 @@ __device__ __forceinline__ float ekv_dpp(float x) {
   return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), CTRL, 0xf, 0xf, true));
 }
 
-// All-reduce (sum) over aligned groups of LPR consecutive lanes, LPR in {4,8,16}; every lane gets the total.
-// quad_perm[1,0,3,2], quad_perm[2,3,0,1], row_half_mirror, row_mirror: one fused v_add_f32_dpp each.
+// The value of lane ^ 16: the partner across the DPP row boundary, inside each half of the wave (ds_swizzle, bit mode: and 0x1F, xor 0x10
+// — no address register, no LDS memory touched).
+__device__ __forceinline__ float ekv_swap_x16(float x) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_ds_swizzle(__builtin_bit_cast(int, x), 0x401F));
+}
+
+// All-reduce (sum) over aligned groups of LPR consecutive lanes, LPR in {4,8,16,32}; every lane gets the total.
+// quad_perm[1,0,3,2], quad_perm[2,3,0,1], row_half_mirror, row_mirror: one fused v_add_f32_dpp each; 32 lanes (head_dim 256: a row is
+// half a wave) take one more step across the DPP row boundary.
 template <int LPR>
 __device__ __forceinline__ float ekv_group_sum(float x) {
+  static_assert(LPR == 4 || LPR == 8 || LPR == 16 || LPR == 32, "lane groups of 4, 8, 16 or 32 lanes");
   x += ekv_dpp<0xB1>(x);
   x += ekv_dpp<0x4E>(x);
   if (LPR >= 8) x += ekv_dpp<0x141>(x);
   if (LPR >= 16) x += ekv_dpp<0x140>(x);
+  if constexpr (LPR >= 32) x += ekv_swap_x16(x);
   return x;
 }
 
@@ -118,10 +127,12 @@ __device__ __forceinline__ uint32_t ekv_fp8_quant4(float a, float b, float c, fl
 // max over aligned groups of LPR consecutive lanes (the lane pattern of ekv_group_sum)
 template <int LPR>
 __device__ __forceinline__ float ekv_group_max(float x) {
+  static_assert(LPR == 4 || LPR == 8 || LPR == 16 || LPR == 32, "lane groups of 4, 8, 16 or 32 lanes");
   x = fmaxf(x, ekv_dpp<0xB1>(x));
   x = fmaxf(x, ekv_dpp<0x4E>(x));
   if (LPR >= 8) x = fmaxf(x, ekv_dpp<0x141>(x));
   if (LPR >= 16) x = fmaxf(x, ekv_dpp<0x140>(x));
+  if constexpr (LPR >= 32) x = fmaxf(x, ekv_swap_x16(x));
   return x;
 }
 // |x| of the 8 16-bit elements of a 16-byte piece, widened to f32

@@ -116,6 +116,9 @@ __device__ __forceinline__ void ekv_decode_stream(const EkvAttnArgs& a, const in
   constexpr int kNW = NW;
   static_assert(!(PHYS && (ROPE || SLOT_LDS)), "physical-order streaming: plain keys, global slot map");
   static_assert((KU == 4 || KU == 8 || KU == 16) && (!PHYS || KU <= 8), "4, 8 or 16 rows per lane group; the dead-row mask is one byte per 8 rows");
+  // head_dim 256 (LPR = 32: two rows per wave-load, the group sums cross the DPP row boundary): 16-bit rows with plain keys only
+  static_assert(LPR <= 16 || (EPL == 8 && FMT == 0 && !ROPE && !RES), "lane groups of 32: 16-bit rows, plain keys");
+  static_assert(LIVE <= LPR && LPR * Gm::G == 64, "one 16-byte piece per lane, whole rows per wave-load");
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int sub = lane % LPR, grp = lane / LPR;
   const int t_new = a.n_slots - 1;  // the appended position

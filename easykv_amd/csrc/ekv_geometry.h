@@ -21,14 +21,21 @@ constexpr int kU = 8;   // rows in flight per lane group (K and V each)
 // head_dim 96 (any head_dim that is a multiple of 16 but not a power of two): a row keeps a power-of-two lane group (LPR = 16) of
 // which only the first LIVE = D / 8 lanes hold a 16-byte piece; the idle lanes carry zeros through the dot products and reductions.
 // EPL = elements per 16-byte piece: 8 (16-bit rows) or 16 (FP8 rows, "kv8": a head_dim-128 row is 8 lanes, head_dim 64 is 4).
+// head_dim 256 (16-bit rows): a row is 32 pieces, so the lane group is half a wave (LPR = 32) and a wave-load covers two rows.  Every
+// lane still holds ONE piece of a row and 8 output floats per query head — the per-lane state is head_dim 128's — and the sums and
+// maxima over a lane group take one step across the DPP row boundary (ekv_group_sum / ekv_group_max, ekv_common.h).
 template <int D, int NW = 4, int KU = kU, int EPL = 8>
 struct EkvDecodeGeom {
   static constexpr int LIVE = D / EPL;  // lanes of a row's lane group that hold a 16-byte piece
-  static constexpr int LPR = LIVE <= 4 ? 4 : (LIVE <= 8 ? 8 : 16);   // lanes per row (power of two)
+  static constexpr int LPR = LIVE <= 4 ? 4 : (LIVE <= 8 ? 8 : (LIVE <= 16 ? 16 : 32));   // lanes per row (power of two)
   static constexpr int G = 64 / LPR;  // rows per wave-load
   static constexpr int RW = G * KU;   // rows per wave per iteration
   static constexpr int NP = NW;       // partials per workgroup = waves (lane groups are combined in-wave)
   static constexpr int PS = D + 2;    // (m, l, o[D])
+  // what the stream handles: one piece per lane, whole rows inside a wave, group reductions of at most half a wave
+  static_assert(D % EPL == 0 && LIVE >= 1, "a row is a whole number of 16-byte pieces");
+  static_assert(LIVE <= LPR, "a lane holds one piece of a row: a wider row needs a wider lane group, or the stream drops its end");
+  static_assert(LPR <= 32 && G * LPR == 64, "a lane group is at most half a wave (ekv_group_sum / ekv_group_max stop at 32 lanes)");
 };
 
 // LDS bytes of the one-launch decode kernel (ekv_decode_fused_kernel, ekv_attn_decode.inc): host arithmetic over the geometry, the same
@@ -166,7 +173,19 @@ struct RL {
 // ---- query blocks of the chunk attention kernels (ekv_attn_chunk.inc, ekv_attn_wide.inc) ------------------------------------------------
 // A query block is <= 128 GQA-folded rows (rep x qb_rows).  qpw = 1 or 2: 16-row query tiles per wave of a 4-wave
 // workgroup (<= 32 / <= 64 rows); qpw = 4 selects the 8-wave workgroup (2 tiles per wave x 4 query-tile waves, <= 128 rows).
-inline void ekv_chunk_blocks(int rep, int q_len, int* qb_rows, int* n_qblocks, int* qpw) {
+// head_dim 256 (kChunkNarrowD): blocks of <= 32 folded rows, ONE query tile per wave of the 4-wave workgroup (qpw = 1) — the only build
+// of the 16x16x32 kernel whose 16 output blocks per tile, staged K/V pieces and query operands fit 256 VGPRs without scratch; the
+// two-tile builds are not instantiated at that head_dim (ekv_attn_chunk.inc), so GQA factors above 32 are refused (ekv_plan.cpp).
+constexpr int kChunkNarrowD = 256;
+constexpr int kChunkNarrowRows = 32;
+inline void ekv_chunk_blocks(int rep, int q_len, int* qb_rows, int* n_qblocks, int* qpw, int head_dim = 0) {
+  if (head_dim >= kChunkNarrowD) {
+    const int rows = (int64_t)rep * q_len > kChunkNarrowRows ? (kChunkNarrowRows / rep > 0 ? kChunkNarrowRows / rep : 1) : q_len;
+    *qb_rows = rows;
+    *n_qblocks = (int)(((int64_t)q_len + rows - 1) / rows);
+    *qpw = 1;
+    return;
+  }
   int rows = q_len;
   if ((int64_t)rep * q_len > 128) rows = 128 / rep > 0 ? 128 / rep : 1;   // (64-row blocks on 4-wave workgroups: 324 vs 378 TFLOP/s on the dense prefix)
   // (65..128 rows stay ONE block on the 8-wave workgroup: two 4-wave blocks of <= 64 rows, even XCD-local so that the second K/V
@@ -178,3 +197,33 @@ inline void ekv_chunk_blocks(int rep, int q_len, int* qb_rows, int* n_qblocks, i
 }
 // partial column-sum rows the exact pass writes per (head, query block) = its query-tile waves
 inline int ekv_chunk_col_parts(int qpw, bool rope) { (void)rope; return qpw == 4 ? 4 : 2; }
+
+// ---- LDS of the 16x16x32 chunk kernel (ekv_attn_chunk.inc): its launcher sizes the launch with it, the planner holds it to one CU ------
+constexpr int kChunkKT = 64;     // positions per K/V super-tile
+constexpr int kChunkPadH = 16;   // LDS row padding in halfs
+// mode 0 / 1 / 2 = one pass / statistics pass / exact pass; tiles = 16-row query tiles per wave (1 or 2), nw = waves per workgroup
+// (4, 8 or 16).  Slot entries of the key range | K tile (+ V tile, + the low plane of rotated keys) | the query block where it lives in
+// LDS; the 16-wave build's in-kernel fold of the two key halves exchanges (m, l, o[D]) of nw / 2 x 64 lanes over the tile buffers.
+constexpr bool ekv_chunk_q_in_lds(int mode, int tiles, bool rope, int nw) {
+  return mode == 1 ? (rope && tiles >= 2) : (nw == 8 || (tiles >= 2 && rope));
+}
+inline size_t ekv_chunk_kernel_lds(int head_dim, int mode, int tiles, bool rope, int nw, int rows_per_split, bool fold) {
+  const size_t row = (size_t)(head_dim + kChunkPadH) * 2, slots = ekv_align((size_t)rows_per_split * 4, 16);
+  size_t lds = slots + (size_t)((rope ? 3 : 2) - (mode == 1 ? 1 : 0)) * kChunkKT * row +
+               (ekv_chunk_q_in_lds(mode, tiles, rope, nw) ? (size_t)(rope ? 2 : 1) * 16 * tiles * (nw / 2) * row : 0);
+  const size_t xch = slots + (size_t)(nw / 2) * 64 * ((size_t)(head_dim / 16) * 4 + 2) * 4;
+  if (nw == 16 && fold && xch > lds) lds = xch;
+  return lds;
+}
+// ... of the largest launch a step on this kernel makes: qpw as ekv_chunk_blocks answers it (4: the 8-wave workgroup with two tiles
+// per wave, or the 16-wave one-pass build without RoPE-on-read)
+inline size_t ekv_chunk_step_lds(int head_dim, int qpw, bool rope, bool two_pass, int rows_per_split, bool fold) {
+  const int tiles = qpw == 4 ? 2 : qpw, nw = qpw == 4 ? 8 : 4;
+  if (two_pass) {
+    const size_t a = ekv_chunk_kernel_lds(head_dim, 1, tiles, rope, nw, rows_per_split, false);
+    const size_t b = ekv_chunk_kernel_lds(head_dim, 2, tiles, rope, nw, rows_per_split, fold);
+    return a > b ? a : b;
+  }
+  if (qpw == 4 && !rope) return ekv_chunk_kernel_lds(head_dim, 0, 1, false, 16, rows_per_split, fold);
+  return ekv_chunk_kernel_lds(head_dim, 0, tiles, rope, nw, rows_per_split, fold);
+}

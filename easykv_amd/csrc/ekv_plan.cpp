@@ -23,7 +23,7 @@ bool pow2_to_16(int rep) { return rep == 1 || rep == 2 || rep == 4 || rep == 8 |
 int check_bank(const ekv_bank* b) {
   if (!b || !b->k || !b->v || !b->slot_of_pos) return EKV_E_ARG;
   if (b->n_layers <= 0 || b->n_kv_heads <= 0 || b->n_q_heads % b->n_kv_heads || b->cap <= 0) return EKV_E_ARG;
-  if (b->head_dim != 32 && b->head_dim != 64 && b->head_dim != 96 && b->head_dim != 128) return EKV_E_UNSUPPORTED;
+  if (b->head_dim != 32 && b->head_dim != 64 && b->head_dim != 96 && b->head_dim != 128 && b->head_dim != 256) return EKV_E_UNSUPPORTED;
   return EKV_OK;
 }
 
@@ -34,7 +34,7 @@ int check_layers(const ekv_bank* b, int begin, int count) {
 // ---- decode steps ------------------------------------------------------------------------------------------------------------------
 // any GQA factor (repeat_kv, llama_patch.py:19-29): factors <= 8 on the build of the next power of two, wider ones in groups of 8
 bool ekv_attn_decode_supported(int head_dim, int rep) {
-  return (head_dim == 32 || head_dim == 64 || head_dim == 96 || head_dim == 128) && rep >= 1;
+  return (head_dim == 32 || head_dim == 64 || head_dim == 96 || head_dim == 128 || head_dim == 256) && rep >= 1;
 }
 
 // The whole decode step in one launch: possible when a head is not split, at most one victim, and the row fits.
@@ -114,6 +114,7 @@ bool ekv_decode_fused_supported(int head_dim, int rep, int n_slots, int t_pad, i
     case 64: lds = ekv_fused_lds_max<64>(rep, t_pad, l_pad, nw); break;
     case 96: lds = ekv_fused_lds_max<96>(rep, t_pad, l_pad, nw); break;
     case 128: lds = ekv_fused_lds_max<128>(rep, t_pad, l_pad, nw); break;
+    case 256: lds = ekv_fused_lds_max<256>(rep, t_pad, l_pad, nw); break;
   }
   return lds <= (size_t)(nw == 8 ? 150 : 80) * 1024;   // 80 KB still leaves two 4-wave workgroups per CU
 }
@@ -162,7 +163,10 @@ bool ekv_chunk_two_pass(int head_dim, int rep, int q_len, int policy, bool score
   return mode > 0 || ((!rope || head_dim == 64 || head_dim == 128) && (i64)rep * q_len >= 40);
 }
 
+// head_dim 256 runs the one-tile-per-wave build of the 16x16x32 kernel alone (ekv_chunk_blocks, ekv_geometry.h): a query's rep folded
+// rows must fit one block of 32
 bool ekv_attn_chunk_supported(int head_dim, int rep, int q_len) {
+  if (head_dim == kChunkNarrowD) return rep >= 1 && rep <= kChunkNarrowRows && q_len >= 1;
   return (head_dim == 32 || head_dim == 64 || head_dim == 96 || head_dim == 128) && rep >= 1 && rep <= 128 && q_len >= 1;
 }
 
@@ -285,7 +289,7 @@ void plan_tiling(const StepShape& s, EkvStepPlan* P) {
   P->t_pad = (int)ekv_align((size_t)T, 64);
   P->qb_rows = P->n_qblocks = 1;
   int qpw = 1;
-  if (n > 1) ekv_chunk_blocks(rep, n, &P->qb_rows, &P->n_qblocks, &qpw);
+  if (n > 1) ekv_chunk_blocks(rep, n, &P->qb_rows, &P->n_qblocks, &qpw, D);
   // physical extent E of the step (every live row has a physical index < E): the caller's value when it is consistent, else cap
   P->phys_extent = (st->phys_extent >= T && st->phys_extent <= bank->cap) ? st->phys_extent : bank->cap;
   // pitch of a logits row in the fused decode kernel's LDS: logical positions (RoPE-on-read streams in position order, the rotation
@@ -443,6 +447,8 @@ int plan_checks(const StepShape& s, int bank_rc, EkvStepPlan* P) {
     slice(P->row_stats, rows0 * 2 * 4);
     slice(P->q_keep, rows0 * D * 2);
   }
+  // head_dim 256: plain keys only — no RoPE-on-read build of the decode stream or of the chunk kernel exists at that head_dim
+  if (D == kChunkNarrowD && st->rope_on_read) return EKV_E_UNSUPPORTED;
   return EKV_OK;
 }
 
@@ -556,6 +562,15 @@ int plan_ending(const StepShape& s, EkvStepPlan* P, StepEnding* end) {
   //  the term the bound above also carries, and the same 160 KB)
   if (generic_scorer && s.long_rows && ekv_long_sweep_lds(shape.colsum != nullptr ? 0 : (i64)rep * n) > 160 * 1024) return EKV_E_UNSUPPORTED;
   if (n == 1 ? !ekv_attn_decode_supported(D, rep) : !ekv_attn_chunk_supported(D, rep, n)) return EKV_E_UNSUPPORTED;
+  // the 16x16x32 chunk kernel keeps the slot entries of its key range, its K/V tiles and (some builds) the query block in LDS: one CU's
+  // 160 KB bound every launch of the step (ekv_chunk_step_lds, ekv_geometry.h — the arithmetic its launcher sizes the launch with).  The
+  // row bound of the tiling (max_rows) keeps every head_dim up to 256 inside it; a step beyond it is refused here, not at the launch.
+  if (n > 1 && !P->wide && !P->resident) {
+    int qb_rows, n_qblocks, qpw;
+    ekv_chunk_blocks(rep, n, &qb_rows, &n_qblocks, &qpw, D);
+    if (ekv_chunk_step_lds(D, qpw, st->rope_on_read != 0, P->two_pass != 0, P->rows_per_split, P->fold_in_kernel != 0) > 160 * 1024)
+      return EKV_E_UNSUPPORTED;
+  }
 
   // decode split path whose partials are folded right behind the attention kernel (attention + fold phases, or a step that has
   // nothing to score): the last-arriving split of a head folds them inside the attention kernel — no fold launch

@@ -72,6 +72,10 @@ ROW_FORMATS = {
 }
 
 
+# head_dims served with plain keys and 16-bit rows only: no RoPE-on-read build (set_rope, streaming) and no quantised row format
+PLAIN_KEYS_HEAD_DIMS = (256,)
+
+
 def row_format(kind, what="kv_quant"):
     """The entry of ROW_FORMATS for ``kind`` ('fp8', 'mxfp4', 'mxfp6', 'fp8_mxfp4' or 'k16_mxfp4'), or None for None (16-bit rows);
     anything else is a ValueError naming ``what``."""
@@ -487,6 +491,8 @@ class KVBank:
     def set_rope(self, cos, sin):
         """fp32 tables ``[>= cap, head_dim]`` for the streaming (rope-on-read) variant."""
         self._quant_refuse(True, "set_rope (RoPE-on-read)")
+        if self.head_dim in PLAIN_KEYS_HEAD_DIMS:
+            raise _lib.EkvError(f"set_rope(): RoPE-on-read has no build for head_dim {self.head_dim} (plain keys only)")
         self.rope_cos = cos.to(self.device, torch.float32).contiguous()
         self.rope_sin = sin.to(self.device, torch.float32).contiguous()
         half = self.head_dim // 2

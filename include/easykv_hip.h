@@ -59,6 +59,9 @@ enum {
   EKV_OK = 0,
   EKV_E_ARG = -1,          /* inconsistent sizes / null pointer          */
   EKV_E_UNSUPPORTED = -2,  /* head_dim / group size / width not built    */
+  /* head_dim: 32 / 64 / 96 / 128 / 256.  head_dim 256 (16-bit rows, fp16 or bf16): every step with plain keys — decode steps of any GQA
+   * factor, single and batched, chunk steps of GQA factors up to 32, the long family; rope_on_read and every quantised row format
+   * (ekv_kv8_* ... ekv_kv164_*) answer EKV_E_UNSUPPORTED at that head_dim, before anything is launched. */
   EKV_E_WORKSPACE = -3,    /* workspace too small                        */
   EKV_E_LAUNCH = -4        /* hipLaunch failure (hipGetLastError)        */
 };
