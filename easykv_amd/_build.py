@@ -33,10 +33,16 @@ FAMILIES = {
     "EKV_DECODE": lambda d, keys, elem, rows, batching: (
         "ekv_attn_decode.inc", f"ekv_attn_decode_d{d}_{keys}" + _tags(elem, rows, batching),
         _on(elem, rows, batching) + [f"-DEKV_D={d}", "-DEKV_ROPE=" + ("true" if keys == "rope" else "false")]),
+    "EKV_DECODE_CAP": lambda elem, d: (      # the decode kernels with plain keys and soft-capped logits
+        "ekv_attn_decode.inc", f"ekv_attn_decode_d{d}_cap" + _tags(elem), _on(elem) + [f"-DEKV_D={d}", "-DEKV_ROPE=false", "-DEKV_SOFTCAP=1"]),
     "EKV_DECODE_SCORE": lambda elem, batching: (
         "ekv_decode_score.inc", "ekv_decode_score" + _tags(elem, batching), _on(elem, batching)),
     "EKV_CHUNK": lambda d, m, elem: (
         "ekv_attn_chunk.inc", f"ekv_attn_chunk_d{d}_m{m}" + _tags(elem), _on(elem) + [f"-DEKV_D={d}", f"-DEKV_CHUNK_MODE={m}"]),
+    "EKV_CHUNK_CAP": lambda elem, d, m: (      # the 16x16x32 chunk kernel with soft-capped logits
+        "ekv_attn_chunk.inc", f"ekv_attn_chunk_cap_d{d}_m{m}" + _tags(elem),
+        _on(elem) + [f"-DEKV_D={d}", f"-DEKV_CHUNK_MODE={m}", "-DEKV_SOFTCAP=1"]),
+    "EKV_SOFTCAP_EVAL": lambda elem, nt: ("ekv_softcap_eval.inc", "ekv_softcap_eval", [f"-DEKV_EVAL_NT={nt}"]),
     "EKV_WIDE": lambda d, m, keys, elem: (
         "ekv_attn_wide.inc", "ekv_attn_wide" + ("_rope" if keys == "rope" else "") + f"_d{d}_m{m}" + _tags(elem),
         _on(elem) + [f"-DEKV_D={d}", f"-DEKV_WIDE_MODE={m}"] + (["-DEKV_WIDE_ROPE=1"] if keys == "rope" else [])),
@@ -97,7 +103,7 @@ def later_instances():
 
 
 def later_objects():
-    """(object name, hipcc arguments) of the instances of ekv_instances_later.def (the kv84 decode instances, the kv164 ones, the long-row scorer)."""
+    """(object name, hipcc arguments) of the instances of ekv_instances_later.def (the kv84 decode instances, the kv164 ones, the long-row scorer, head_dim 256, the soft-capped instances)."""
     return _instance_objects(later_instances())
 
 

@@ -47,6 +47,9 @@ EXPORTS = ("ekv_abi_version", "ekv_strerror", "ekv_workspace_bytes", "ekv_step_p
 LONG_CALLS = {what: "ekv_long_" + what for what in STEP_CALLS}
 EXPORTS += tuple(LONG_CALLS[what] for what in STEP_CALLS)
 LONG_INFO_N = 12      # EKV_LONG_INFO_N: [10] the step ends in the long-row scorer, [11] column tiles per head of its sweep
+# the soft-capped family (include/easykv_hip.h, "soft-capped logits"): the _typed calls with a float cap behind the dtype; 16-bit rows, one sequence
+CAP_CALLS = {what: "ekv_cap_" + what for what in STEP_CALLS}
+EXPORTS += tuple(CAP_CALLS[what] for what in STEP_CALLS) + ("ekv_softcap_eval",)
 
 
 class Bank(C.Structure):
@@ -146,9 +149,11 @@ def load():
             tails["step_attend"] = [vp] * 8 + [C.c_size_t, vp]
             for what in STEP_CALLS:
                 getattr(lib, LONG_CALLS[what]).argtypes = [C.POINTER(Bank), C.POINTER(Step), i32] + tails[what]
+                getattr(lib, CAP_CALLS[what]).argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, C.c_float] + tails[what]
         if desc:
             getattr(lib, f"ekv_{rows}_quantize").argtypes = [C.POINTER(Bank), C.POINTER(desc), i32, i32, i32, i32, vp]
             getattr(lib, f"ekv_{rows}_dequantize").argtypes = [C.POINTER(Bank), C.POINTER(desc), i32, i32, i32, i32, vp, vp, vp]
+    lib.ekv_softcap_eval.argtypes = [vp, C.c_int64, C.c_float, C.c_float, vp, vp]
     lib.ekv_kv164_dequantize.argtypes = [C.POINTER(Bank), C.POINTER(Kv164), i32, i32, i32, i32, vp, vp]      # (V only: one output)
     for name in EXPORTS:
         if name != "ekv_strerror":

@@ -40,7 +40,7 @@ from typing import List, Optional
 import torch
 
 from . import _lib
-from .engine import PLAIN_KEYS_HEAD_DIMS, KVBank, KVBankBatch, StepPlan, row_format
+from .engine import CAPPED_HEAD_DIMS, PLAIN_KEYS_HEAD_DIMS, KVBank, KVBankBatch, StepPlan, row_format
 
 KNOWN_POLICIES = ("roco", "h2o_head", "tova", "recency", "random", "full")
 SCORED = ("roco", "h2o_head", "tova")
@@ -96,10 +96,14 @@ class BudgetedKVCache:
     per GPU owns a block, easykv_amd/dist.py).  The bank holds only those layers; :meth:`attend` takes GLOBAL layer indices.
 
     ``dtype``: element type of the K/V bank, torch.float16 (None = the default) or torch.bfloat16; q / k / v of another dtype are
-    converted to it and the attention output comes back in it.  A bf16 bank has no RoPE-on-read build (``streaming``)."""
+    converted to it and the attention output comes back in it.  A bf16 bank has no RoPE-on-read build (``streaming``).
+
+    ``sm_scale``: the softmax scale (None: ``1 / sqrt(head_dim)``); ``logit_cap``: attention-logit soft-capping (None: off).  Both are
+    the bank's (:class:`~easykv_amd.engine.KVBank`) and are kept as attributes: the HF seam holds the attention module's own
+    ``scaling`` / ``softcap`` against them."""
 
     def __init__(self, n_layers, n_q_heads, n_kv_heads, head_dim, cap, device, streaming=False, rope=None,
-                 record=False, layer_begin=0, layer_count=None, rope_base=10000.0, dtype=None, long_rows=False):
+                 record=False, layer_begin=0, layer_count=None, rope_base=10000.0, dtype=None, long_rows=False, logit_cap=None, sm_scale=None):
         self.layer_begin = layer_begin
         self.layer_count = n_layers - layer_begin if layer_count is None else layer_count
         if not (0 <= self.layer_begin and self.layer_count >= 1 and self.layer_begin + self.layer_count <= n_layers):
@@ -109,7 +113,11 @@ class BudgetedKVCache:
         if dtype is torch.bfloat16 and streaming:
             raise ValueError("a bf16 K/V bank has no RoPE-on-read build: streaming=True needs kv_dtype='float16'")
         # long_rows: the bank's steps go to the long-row call family (KVBank(long_rows=True): score rows of any width up to cap)
-        self.bank = KVBank(self.layer_count, n_q_heads, n_kv_heads, head_dim, cap, device=device, dtype=dtype, long_rows=long_rows)
+        if logit_cap is not None and streaming:
+            raise ValueError("a soft-capped cache (logit_cap) has no RoPE-on-read build: streaming=True needs logit_cap=None")
+        self.logit_cap, self.sm_scale = logit_cap, sm_scale
+        extra = {k: v for k, v in (("logit_cap", logit_cap), ("sm_scale", sm_scale)) if v is not None}      # (opt-in: named only when set)
+        self.bank = KVBank(self.layer_count, n_q_heads, n_kv_heads, head_dim, cap, device=device, dtype=dtype, long_rows=long_rows, **extra)
         # no resident rows behind a model: its weights (gigabytes) stream through the Infinity Cache between two attention launches
         # of a layer, and plain loads that miss cost more than non-temporal ones ("resident rows": the harm run)
         self.bank.resident_bytes = 0
@@ -252,9 +260,11 @@ class BudgetedKVCacheBatch:
     library (one launch per kernel kind) for that layer."""
 
     streaming, unrotate = False, None      # (a batch has no RoPE-on-read form)
+    logit_cap = None                        # (... and no soft-capped one; the softmax scale is the shared bank's)
 
     def __init__(self, bat: KVBankBatch, record=False):
         self.bat = bat
+        self.sm_scale = bat.bank.sm_scale
         self.plans, self.live, self.positions = [], [], None
         self.record = record
         self.evictions = [[] for _ in range(bat.n_seq)]      # record=True, per sequence: per evicting forward, per layer, int32 [H, 1]
@@ -411,6 +421,24 @@ class _Run:
             raise ValueError(f"generation_config['kv_quant'] = {kv_quant!r} needs head_dim {' or '.join(map(str, fmt['head_dims']))} (this model: {d})")
         if fmt is not None and fmt["max_rep"] is not None and hq // hkv > fmt["max_rep"]:
             raise ValueError(f"generation_config['kv_quant'] = {kv_quant!r} needs a GQA factor of at most {fmt['max_rep']} (this model: {hq // hkv})")
+        # the model's own attention arithmetic, read where head_dim is: attn_logit_softcapping (Gemma 2; absent or None = off) becomes the
+        # cache's logit_cap, query_pre_attn_scalar (Gemma 2 / 3; absent = head_dim) its softmax scale qpas ** -0.5 (None = 1 / sqrt(head_dim))
+        cap_ = getattr(model.config, "attn_logit_softcapping", None)
+        self.logit_cap = None if cap_ is None else float(cap_)
+        qpas = getattr(model.config, "query_pre_attn_scalar", None)
+        self.sm_scale = None if qpas is None or float(qpas) == float(d) else float(qpas) ** -0.5
+        if self.logit_cap is not None:      # (before any bank exists)
+            what = f"a model with attn_logit_softcapping = {self.logit_cap:g}"
+            if not (0.0 < self.logit_cap < float("inf")):
+                raise ValueError(f"{what}: the cap must be finite and > 0")
+            if streaming:
+                raise ValueError(f"{what} with streaming=True: RoPE-on-read has no soft-capped build")
+            if kv_quant is not None:
+                raise ValueError(f"{what} with generation_config['kv_quant'] = {kv_quant!r}: there is no capped quantised decode step")
+            if self.long_rows:
+                raise ValueError(f"{what} with generation_config['long_rows'] = True: there is no capped long call")
+            if d not in CAPPED_HEAD_DIMS:
+                raise ValueError(f"{what}: soft-capped logits are built for head_dim {' and '.join(map(str, CAPPED_HEAD_DIMS))} (this model: {d})")
         self.dev = torch.device(model.device)
         for p in prompts:
             if p.dim() != 2 or p.shape[0] != 1:
@@ -463,7 +491,8 @@ class _Run:
             hf_rope = hf.rope_tables_from_model(self.model, max(cap + 8, length + self.max_new_tokens + 1) + 64, d, self.dev)
         cache = BudgetedKVCache(n_layers, hq, h, d, cap + 8, self.dev, streaming=self.streaming, record=self.record, rope=hf_rope,
                                 layer_begin=self.layers[0], layer_count=self.layers[1], rope_base=self.rope_base, dtype=self.kv_dtype,
-                                **(dict(long_rows=True) if self.long_rows else {}))      # (opt-in: named only when asked for)
+                                **(dict(long_rows=True) if self.long_rows else {}),      # (opt-in: named only when asked for)
+                                **{k: v for k, v in (("logit_cap", self.logit_cap), ("sm_scale", self.sm_scale)) if v is not None})
         cache.unrotate = hf_rope if self.hf_stream else None
         return cache
 
@@ -838,6 +867,8 @@ def generate_batch(self, input_ids_list, generation_config, kv_mode="encoding", 
         raise ValueError("generate_batch: generation_config['long_rows'] has no batched decode step (the long-row scorer serves single sequences)")
     if cfg.get("kv_quant", None) == "mxfp4":
         raise ValueError("generate_batch: generation_config['kv_quant'] = 'mxfp4' has no batched decode step (use 'fp8' or None)")
+    if getattr(self.config, "attn_logit_softcapping", None) is not None:
+        raise ValueError("generate_batch: a model with attn_logit_softcapping has no batched decode step (soft-capped logits serve single sequences)")
     prompts = [p.view(1, -1) if p.dim() == 1 else p for p in input_ids_list]
     if not 1 <= len(prompts) <= _lib.MAX_SEQS or any(p.dim() != 2 or p.shape[0] != 1 for p in prompts):
         raise ValueError(f"generate_batch takes 1..{_lib.MAX_SEQS} prompts of shape [S] or [1, S]")
@@ -855,7 +886,7 @@ def generate_batch(self, input_ids_list, generation_config, kv_mode="encoding", 
     first = seqs[0].cache.bank
     rows = dict(kv_quant=run.kv_quant) if run.kv_quant else {}      # (the format's planes only: the 16-bit rows of the batch are never allocated)
     bat = KVBankBatch(len(seqs), first.n_layers, first.n_q_heads, first.n_kv_heads, first.head_dim, max(s.cache.bank.cap for s in seqs),
-                      device=dev, dtype=first.dtype, **rows)
+                      device=dev, dtype=first.dtype, **rows, **(dict(sm_scale=run.sm_scale) if run.sm_scale is not None else {}))
     cache = BudgetedKVCacheBatch(bat, record=run.record)
     for i, s in enumerate(seqs):
         bat.adopt(i, s.cache.bank)

@@ -60,6 +60,7 @@ static int call_attend(const EkvCall& c, const void* q, const void* k_new, const
   aa.qb_rows = P.qb_rows;
   aa.n_qblocks = P.n_qblocks;
   aa.sm_div = st->sm_div;
+  aa.softcap = c.capped ? c.softcap : 0.f;
   aa.q_keep = f16(P.q_keep);
   aa.phys_extent = P.phys_extent;
   aa.l_pad = P.l_pad;
@@ -93,6 +94,7 @@ static int call_attend(const EkvCall& c, const void* q, const void* k_new, const
 
   const bool bf16 = P.bf16 != 0;
   const EkvRows rows = static_cast<EkvRows>(P.rows);
+  const bool capped = P.capped != 0;
   drop_stale_error();
   for (int i = 0; i < P.n_list; ++i) {
     const EkvLaunch& L = P.list[i];
@@ -100,16 +102,18 @@ static int call_attend(const EkvCall& c, const void* q, const void* k_new, const
     hipError_t e = hipSuccess;
     // (a quantised plan is a decode plan: the decode attention launches and the scorers behind them, which read no K/V element)
     if (rows != EKV_ROWS_kv16 && (L.kind == EKV_RUN_CHUNK_LDS || L.kind == EKV_RUN_RESIDENT || L.kind == EKV_RUN_CHUNK || L.kind == EKV_RUN_FLUSH)) return EKV_E_UNSUPPORTED;
+    // (a capped plan: the decode launches and the 16x16x32 chunk kernel, the only kernels with capped instances)
+    if (capped && (L.kind == EKV_RUN_CHUNK_LDS || L.kind == EKV_RUN_RESIDENT || L.kind == EKV_RUN_FLUSH || (L.kind == EKV_RUN_CHUNK && P.wide))) return EKV_E_UNSUPPORTED;
     switch (L.kind) {
       case EKV_RUN_FUSED_DECODE:
         aa.fused_order = P.fused_order;      // (shares its storage with score_tail, which only chunk launches set)
-        e = ekv_launch_decode_fused(aa, sa, tb, D, lc, P.fused_nw, s, bf16, rows);
+        e = ekv_launch_decode_fused(aa, sa, tb, D, lc, P.fused_nw, s, bf16, rows, capped);
         break;
       case EKV_RUN_CHUNK_LDS: e = ekv_launch_chunk_lds(aa, sa, D, lc, s, bf16); break;
       case EKV_RUN_RESIDENT: e = ekv_launch_attn_resident(aa, sa, lc, s, bf16); break;
-      case EKV_RUN_DECODE: e = ekv_launch_attn_decode(aa, tb, D, lc, s, bf16, rows); break;
+      case EKV_RUN_DECODE: e = ekv_launch_attn_decode(aa, tb, D, lc, s, bf16, rows, capped); break;
       case EKV_RUN_CHUNK:
-        e = ekv_launch_attn_chunk(aa, D, lc, P.wide, P.two_pass, s, L.fuse ? &sa : nullptr, L.passes, L.tail ? &sa : nullptr, bf16);
+        e = ekv_launch_attn_chunk(aa, D, lc, P.wide, P.two_pass, s, L.fuse ? &sa : nullptr, L.passes, L.tail ? &sa : nullptr, bf16, capped);
         break;
       case EKV_RUN_FLUSH: {
         EkvAttnArgs a2 = aa;
@@ -189,6 +193,25 @@ int ekv_long_step_attend(const ekv_bank* bank, const ekv_step* st, int32_t dtype
                          void* out, int32_t* evict_ids, const float* rope_cos, const float* rope_sin, void* workspace,
                          size_t workspace_bytes, void* stream) {
   return call_attend(long_call(bank, st, dtype), q, k_new, v_new, out, evict_ids, rope_cos, rope_sin, workspace, workspace_bytes, stream);
+}
+
+// soft-capped attention logits (include/easykv_hip.h, "soft-capped logits"): the _typed calls with a cap
+int ekv_cap_step_check(const ekv_bank* bank, const ekv_step* st, int32_t dtype, float softcap) { return call_check(cap_call(bank, st, dtype, softcap)); }
+int ekv_cap_step_info(const ekv_bank* bank, const ekv_step* st, int32_t dtype, float softcap, int32_t* info, int32_t n_info) {
+  return call_info(cap_call(bank, st, dtype, softcap), info, n_info);
+}
+size_t ekv_cap_workspace_bytes(const ekv_bank* bank, const ekv_step* st, int32_t dtype, float softcap) {
+  return call_workspace_bytes(cap_call(bank, st, dtype, softcap));
+}
+int ekv_cap_step_attend(const ekv_bank* bank, const ekv_step* st, int32_t dtype, float softcap, const void* q, const void* k_new, const void* v_new,
+                        void* out, int32_t* evict_ids, const float* rope_cos, const float* rope_sin, void* workspace,
+                        size_t workspace_bytes, void* stream) {
+  return call_attend(cap_call(bank, st, dtype, softcap), q, k_new, v_new, out, evict_ids, rope_cos, rope_sin, workspace, workspace_bytes, stream);
+}
+int ekv_softcap_eval(const float* x, int64_t n, float sm_div, float cap, float* out, void* stream) {
+  if (n < 0 || (n > 0 && (!x || !out)) || !(cap > 0.f && cap <= 3.0e38f) || !(sm_div > 0.f)) return EKV_E_ARG;
+  drop_stale_error();
+  return launch_code(ekv_launch_softcap_eval(x, n, sm_div, cap, out, static_cast<hipStream_t>(stream)));
 }
 
 // FP8 K/V storage (include/easykv_hip.h, "kv8")

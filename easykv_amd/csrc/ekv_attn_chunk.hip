@@ -8,6 +8,7 @@
 typedef hipError_t EkvChunkFn(const EkvAttnArgs&, int shape, int layer_count, hipStream_t, const EkvScoreArgs*);
 typedef hipError_t EkvStepFn(const EkvAttnArgs&, const EkvScoreArgs&, int layer_count, hipStream_t);
 #define EKV_CHUNK(d, m, elem) EkvChunkFn EKV_FN_CHUNK(d, m, elem);
+#define EKV_CHUNK_CAP(elem, d, m) EkvChunkFn EKV_FN_CHUNK_CAP(d, m, elem);
 #define EKV_WIDE(d, m, keys, elem) EkvChunkFn EKV_FN_WIDE(d, m, keys, elem);
 #define EKV_CHUNK_LDS(d, elem) EkvStepFn EKV_FN_D_ELEM(ekv_launch_chunk_lds, d, elem);
 #define EKV_RESIDENT(d, elem) EkvStepFn EKV_FN_D_ELEM(ekv_launch_attn_resident, d, elem);
@@ -17,12 +18,13 @@ namespace {
 struct ChunkInstance {      // 16x16 kernel (rope: the fp16 builds rotate on read themselves) and wide-block kernel
   bool wide;
   int head_dim, mode;
-  bool rope, bf16;
+  bool rope, bf16, capped;      // capped: the soft-capped builds of the 16x16 kernel (EKV_CHUNK_CAP)
   EkvChunkFn* fn;
 };
 const ChunkInstance kChunk[] = {
-#define EKV_CHUNK(d, m, elem) {false, d, m, false, EKV_IS_##elem, EKV_FN_CHUNK(d, m, elem)},
-#define EKV_WIDE(d, m, keys, elem) {true, d, m, EKV_IS_##keys, EKV_IS_##elem, EKV_FN_WIDE(d, m, keys, elem)},
+#define EKV_CHUNK(d, m, elem) {false, d, m, false, EKV_IS_##elem, false, EKV_FN_CHUNK(d, m, elem)},
+#define EKV_CHUNK_CAP(elem, d, m) {false, d, m, false, EKV_IS_##elem, true, EKV_FN_CHUNK_CAP(d, m, elem)},
+#define EKV_WIDE(d, m, keys, elem) {true, d, m, EKV_IS_##keys, EKV_IS_##elem, false, EKV_FN_WIDE(d, m, keys, elem)},
 #include "ekv_instances.def"
 };
 struct StepInstance {      // whole-step kernels: logits in LDS, logits-resident
@@ -37,9 +39,9 @@ const StepInstance kStep[] = {
 #include "ekv_instances.def"
 };
 
-EkvChunkFn* chunk_instance(bool wide, int head_dim, int mode, bool rope, bool bf16) {
+EkvChunkFn* chunk_instance(bool wide, int head_dim, int mode, bool rope, bool bf16, bool capped = false) {
   for (const ChunkInstance& in : kChunk)
-    if (in.wide == wide && in.head_dim == head_dim && in.mode == mode && in.rope == rope && in.bf16 == bf16) return in.fn;
+    if (in.wide == wide && in.head_dim == head_dim && in.mode == mode && in.rope == rope && in.bf16 == bf16 && in.capped == capped) return in.fn;
   return nullptr;
 }
 const StepInstance* step_instance(bool resident, int head_dim, bool bf16) {
@@ -84,12 +86,14 @@ static int kernel_code(int qpw, bool rope, int mode) { return (qpw == 4 && !rope
 // fuse_sc != nullptr: one-pass step with unsplit heads whose scorer runs as the tail of the attention kernel (no second launch)
 // (kernel launches per call: ekv_attn_chunk_launches, ekv_plan.cpp)
 hipError_t ekv_launch_attn_chunk(const EkvAttnArgs& a, int head_dim, int layer_count, bool wide, bool two_pass, hipStream_t s,
-                                 const EkvScoreArgs* fuse_sc, int passes, const EkvScoreArgs* tail_sc, bool bf16) {
+                                 const EkvScoreArgs* fuse_sc, int passes, const EkvScoreArgs* tail_sc, bool bf16, bool capped) {
   if (two_pass && (fuse_sc != nullptr || a.stats == nullptr || a.colsum == nullptr)) return hipErrorInvalidValue;
   if (tail_sc != nullptr && !(wide && two_pass && (passes & 2))) return hipErrorInvalidValue;
   int qb_rows, n_qblocks, qpw;
-  ekv_chunk_blocks(a.n_q_heads / a.n_kv_heads, a.q_len, &qb_rows, &n_qblocks, &qpw, head_dim);
+  // (a capped step is blocked as head_dim 256's, at either head_dim: the one-tile build is the only capped one)
+  ekv_chunk_blocks(a.n_q_heads / a.n_kv_heads, a.q_len, &qb_rows, &n_qblocks, &qpw, capped ? kChunkNarrowD : head_dim);
   const bool rope = a.rope_cos != nullptr;
+  if (capped && (wide || rope || !(a.softcap > 0.f) || a.softcap > 3.0e38f)) return hipErrorInvalidValue;      // (no capped wide or RoPE-on-read build)
   if (bf16 && rope) return hipErrorInvalidValue;   // (no bf16 RoPE-on-read build)
   if (rope && !wide) {      // (the wide-block kernel rotates its query rows itself, in the lane that holds them)
     if (a.q_rot_hi == nullptr || a.q_rot_lo == nullptr) return hipErrorInvalidValue;
@@ -123,7 +127,7 @@ hipError_t ekv_launch_attn_chunk(const EkvAttnArgs& a, int head_dim, int layer_c
   }
   // (the fp16 instances of the 16x16 kernel hold the RoPE-on-read builds: one line per (head_dim, mode, element))
   auto go = [&](int m) {
-    EkvChunkFn* const fn = chunk_instance(false, head_dim, m, false, bf16);
+    EkvChunkFn* const fn = chunk_instance(false, head_dim, m, false, bf16, capped);
     return fn ? fn(a, kernel_code(qpw, rope, m), layer_count, s, fuse_sc) : hipErrorInvalidValue;
   };
   hipError_t e = go(two_pass ? 1 : 0);

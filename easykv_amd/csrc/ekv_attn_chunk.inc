@@ -32,8 +32,23 @@
 
 #include "ekv_common.h"
 #include "ekv_kernels.h"
+// EKV_SOFTCAP = 1 (the EKV_CHUNK_CAP lines of the manifest): soft-capped logits (ekv_softcap, ekv_common.h).  Every accumulator element
+// of S^T becomes s = cap * tanh((q.k / sm_div) / cap) before the causal mask, the running maximum and the exponent, in all three modes and
+// by the same operations: the quotient (the reference's, as the exported logits have it), then ekv_softcap.  So the capped builds never
+// fold 1 / sm_div into the exponent (need_div below is always on), the statistics pass and the exact pass see the same s from the same
+// accumulators, and what leaves the kernel — logits, (m, l, o) partials, row statistics, column sums — is in capped units.  Plain keys, the
+// one-tile build alone (blocks of <= 32 folded rows, as head_dim 256 plans them: ekv_chunk_blocks), at head_dim 128 and 256.
+#ifndef EKV_SOFTCAP
+#define EKV_SOFTCAP 0
+#endif
 #if EKV_BF16   // (bf16 instances: the same kernel under a tagged name)
+#if EKV_SOFTCAP
+#define ekv_attn_chunk_kernel ekv_attn_chunk_kernel_cap_bf16
+#else
 #define ekv_attn_chunk_kernel ekv_attn_chunk_kernel_bf16
+#endif
+#elif EKV_SOFTCAP
+#define ekv_attn_chunk_kernel ekv_attn_chunk_kernel_cap
 #endif
 
 #if EKV_CHUNK_MODE == 0
@@ -152,7 +167,7 @@ __global__ void __launch_bounds__(64 * NW, (NW == 16 || (NW == 8 && EKV_CHUNK_MO
   // The exported logits, the row statistics the scorer reads and the probabilities of the exact pass are built on the reference's
   // quotients s / sqrt(D).  A launch that only produces the attention output, and the statistics pass (whose row maximum is
   // converted exactly at the end: the quotient of the maximum IS the maximum of the quotients), work on the raw accumulators.
-  const bool need_div = MODE == 2 || a.logits != nullptr || a.row_stats != nullptr;
+  const bool need_div = EKV_SOFTCAP || MODE == 2 || a.logits != nullptr || a.row_stats != nullptr;      // (capped builds: always — the cap takes the quotient)
   const float cexp = need_div ? EKV_LOG2E : EKV_LOG2E * inv_sm_div;
   constexpr float kMFloor = -1.0e30f;
 
@@ -413,6 +428,9 @@ __global__ void __launch_bounds__(64 * NW, (NW == 16 || (NW == 8 && EKV_CHUNK_MO
             // correctly rounded quotient for every normal operand, 3 instructions instead of the 11 of v_div_scale/fmas/fixup
             const float q0 = sv[e] * inv_sm_div;
             sv[e] = fmaf(fmaf(-a.sm_div, q0, sv[e]), inv_sm_div, q0);
+#if EKV_SOFTCAP
+            sv[e] = ekv_softcap(sv[e], a.softcap);
+#endif
           }
         }
         // masking is needed only where the 32 keys of this wave reach the chunk's own positions or the end of the range: a
@@ -716,6 +734,15 @@ hipError_t launch_k(const EkvAttnArgs& a, int layer_count, hipStream_t s, const 
 }  // namespace
 
 // rows per query block = rep * qb_rows <= 32 * qpw
+#if EKV_SOFTCAP
+// the capped instances: plain keys, the one-tile build alone, at either head_dim (the planner blocks their steps as head_dim 256's)
+hipError_t EKV_FN_CHUNK_CAP(EKV_D, EKV_CHUNK_MODE, EKV_ELEM)(const EkvAttnArgs& a, int qpw, int layer_count, hipStream_t s,
+                                                             const EkvScoreArgs* fuse_sc) {
+  static_assert(EKV_D == 128 || EKV_D == kChunkNarrowD, "capped chunk instances: head_dim 128 and 256");
+  if (a.rope_cos != nullptr || qpw != 1 || !(a.softcap > 0.f)) return hipErrorInvalidValue;
+  return launch_k<1, false, 4>(a, layer_count, s, fuse_sc);
+}
+#else
 hipError_t EKV_FN_CHUNK(EKV_D, EKV_CHUNK_MODE, EKV_ELEM)(const EkvAttnArgs& a, int qpw, int layer_count, hipStream_t s,
                                                                                     const EkvScoreArgs* fuse_sc) {
   const bool rope = a.rope_cos != nullptr;
@@ -741,3 +768,4 @@ hipError_t EKV_FN_CHUNK(EKV_D, EKV_CHUNK_MODE, EKV_ELEM)(const EkvAttnArgs& a, i
   }
 #endif
 }
+#endif

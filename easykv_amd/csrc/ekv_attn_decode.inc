@@ -70,6 +70,13 @@
 #ifndef EKV_KV164_FUSED_KU1
 #define EKV_KV164_FUSED_KU1 4
 #endif
+// EKV_SOFTCAP = 1 (the EKV_DECODE_CAP lines of the manifest: 16-bit rows, plain keys, one sequence): every logit is the soft-capped one
+// (ekv_softcap, ekv_common.h; EKV_LOGIT at every site that forms q.k / sm_div — the stream, its appended row and the K phase of order K).
+// One capped logit per (row, query head) against a 256- or 512-byte row; geometry, rows in flight, phase orders and resident rows are
+// the 16-bit builds'.
+#if EKV_SOFTCAP && (EKV_ROPE || EKV_KV8 || EKV_KV4 || EKV_KV6 || EKV_KV84 || EKV_KV164 || EKV_BATCH)
+#error "soft-capped decode instances: 16-bit rows, plain keys, one sequence"
+#endif
 // Both switches at once (the batch kv8 instances) are independent: DESIGN.md §3.9, "Batches".
 #define ekv_attn_decode_kernel EKV_KERNEL_NAME(ekv_attn_decode_kernel)
 #define ekv_decode_fused_kernel EKV_KERNEL_NAME(ekv_decode_fused_kernel)
@@ -314,7 +321,7 @@ __global__ void __launch_bounds__(64 * NW, (NW >= 8 ? (REP == 1 ? 2 : 1) : (SLOT
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
           const float acc = ekv_group_sum<LPR>(ekv_dot8(qv, kr[u], 0.f));
-          s[u] = !((dead8 >> u) & 1u) ? acc / a.sm_div : EKV_NEG_INF;
+          s[u] = !((dead8 >> u) & 1u) ? EKV_LOGIT(acc, a) : EKV_NEG_INF;
         }
         float mine = s[0];
 #pragma unroll
@@ -331,7 +338,7 @@ __global__ void __launch_bounds__(64 * NW, (NW >= 8 ? (REP == 1 ? 2 : 1) : (SLOT
         const size_t off_new = (head_row + new_row) * D;
         reinterpret_cast<uint4*>(a.k_w + off_new)[sub] = kn;
         reinterpret_cast<uint4*>(a.v_w + off_new)[sub] = vn;
-        const float acc = ekv_group_sum<LPR>(ekv_dot8(qv, kn, 0.f)) / a.sm_div;
+        const float acc = EKV_LOGIT(ekv_group_sum<LPR>(ekv_dot8(qv, kn, 0.f)), a);
         if (sub == 0) s_logit[new_row] = acc;
         mk = fmaxf(mk, acc);
       }
@@ -543,7 +550,9 @@ hipError_t launch_fused(const EkvAttnArgs& a, const EkvScoreArgs& sc EKV_TB_DECL
 
 }  // namespace
 
-#if EKV_ROPE
+#if EKV_SOFTCAP
+#define EKV_KEYS cap      // (plain keys, soft-capped logits)
+#elif EKV_ROPE
 #define EKV_KEYS rope
 #else
 #define EKV_KEYS plain

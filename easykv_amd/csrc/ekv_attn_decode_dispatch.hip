@@ -10,6 +10,8 @@ typedef hipError_t EkvFoldFn(const EkvScoreArgs&, int layer_count, hipStream_t);
 #define EKV_DECODE(d, keys, elem, rows, batching)                            \
   EkvDecodeFn EKV_FN_DECODE(ekv_launch_attn_decode, d, keys, elem, rows, batching); \
   EkvFusedFn EKV_FN_DECODE(ekv_launch_decode_fused, d, keys, elem, rows, batching);
+// (the soft-capped decode instances: plain keys, 16-bit rows, one sequence; their launchers carry `cap` where the others name their keys)
+#define EKV_DECODE_CAP(elem, d) EKV_DECODE(d, cap, elem, kv16, single)
 #define EKV_DECODE_SCORE(elem, batching) EkvScoreFn EKV_FN_DECODE_SCORE(ekv_launch_decode_score, elem, batching);
 #include "ekv_instances.def"
 EkvFoldFn ekv_launch_fold_f16, ekv_launch_fold_bf16;      // (exported by the `single` scorer instances: the fold reads no per-step field)
@@ -17,7 +19,7 @@ EkvFoldFn ekv_launch_fold_f16, ekv_launch_fold_bf16;      // (exported by the `s
 namespace {
 struct DecodeInstance {
   int head_dim;
-  bool rope, bf16;
+  bool rope, capped, bf16;      // (keys: plain | rope | cap)
   EkvRows rows;
   bool batch;
   EkvDecodeFn* attn;
@@ -25,8 +27,9 @@ struct DecodeInstance {
 };
 const DecodeInstance kDecode[] = {
 #define EKV_DECODE(d, keys, elem, rows, batching)                                                                   \
-  {d, EKV_IS_##keys, EKV_IS_##elem, EKV_ROWS_##rows, EKV_IS_##batching, EKV_FN_DECODE(ekv_launch_attn_decode, d, keys, elem, rows, batching), \
+  {d, EKV_IS_##keys, EKV_CAPPED_##keys, EKV_IS_##elem, EKV_ROWS_##rows, EKV_IS_##batching, EKV_FN_DECODE(ekv_launch_attn_decode, d, keys, elem, rows, batching), \
    EKV_FN_DECODE(ekv_launch_decode_fused, d, keys, elem, rows, batching)},
+#define EKV_DECODE_CAP(elem, d) EKV_DECODE(d, cap, elem, kv16, single)
 #include "ekv_instances.def"
 };
 struct ScoreInstance {
@@ -43,8 +46,11 @@ const ScoreInstance kDecodeScore[] = {
 // at most 4; kv84: the K row scales and the V block exponents; kv164: the V block exponents), bf16 and batches have no RoPE-on-read build, a batch runs on the ordered layout (the planner refuses all of these before
 // a launch).  The row format and the batching are independent fields: a batched step on quantised rows looks up its own instance,
 // which takes the table and the planes together, and a combination without a line of the manifest finds nothing.
-const DecodeInstance* decode_instance(const EkvAttnArgs& a, const EkvSeqTable* tb, int head_dim, bool bf16, EkvRows rows, bool fused_slot_rows) {
+// A capped launch (ekv_cap_*): 16-bit rows, plain keys, one sequence, a cap that is finite and > 0 — its own instances, never another's.
+const DecodeInstance* decode_instance(const EkvAttnArgs& a, const EkvSeqTable* tb, int head_dim, bool bf16, EkvRows rows, bool fused_slot_rows,
+                                      bool capped) {
   const bool rope = a.rope_cos != nullptr, batch = tb != nullptr;
+  if (capped && (rope || batch || rows != EKV_ROWS_kv16 || !(a.softcap > 0.f) || a.softcap > 3.0e38f)) return nullptr;
   if (rows == EKV_ROWS_kv8 && (rope || a.k_scale == nullptr || a.v_scale == nullptr)) return nullptr;
   if ((rows == EKV_ROWS_kv4 || rows == EKV_ROWS_kv6) && (rope || a.k_exp == nullptr || a.v_exp == nullptr || a.n_q_heads > 4 * a.n_kv_heads)) return nullptr;
   if (rows == EKV_ROWS_kv84 && (rope || a.k_scale == nullptr || a.v_exp == nullptr)) return nullptr;
@@ -52,20 +58,21 @@ const DecodeInstance* decode_instance(const EkvAttnArgs& a, const EkvSeqTable* t
   if (bf16 && rope) return nullptr;
   if (batch && (rope || fused_slot_rows)) return nullptr;
   for (const DecodeInstance& in : kDecode)
-    if (in.head_dim == head_dim && in.rope == rope && in.bf16 == bf16 && in.rows == rows && in.batch == batch) return &in;
+    if (in.head_dim == head_dim && in.rope == rope && in.capped == capped && in.bf16 == bf16 && in.rows == rows && in.batch == batch) return &in;
   return nullptr;
 }
 }  // namespace
 
-hipError_t ekv_launch_attn_decode(const EkvAttnArgs& a, const EkvSeqTable* tb, int head_dim, int count, hipStream_t s, bool bf16, EkvRows rows) {
-  const DecodeInstance* in = decode_instance(a, tb, head_dim, bf16, rows, false);
+hipError_t ekv_launch_attn_decode(const EkvAttnArgs& a, const EkvSeqTable* tb, int head_dim, int count, hipStream_t s, bool bf16, EkvRows rows,
+                                  bool capped) {
+  const DecodeInstance* in = decode_instance(a, tb, head_dim, bf16, rows, false, capped);
   return in ? in->attn(a, tb, a.n_q_heads / a.n_kv_heads, count, s) : hipErrorInvalidValue;
 }
 
 // The whole decode step in one launch (which steps, how many waves, which phase order: ekv_plan.cpp)
 hipError_t ekv_launch_decode_fused(const EkvAttnArgs& a, const EkvScoreArgs& sc, const EkvSeqTable* tb, int head_dim, int count, int nw,
-                                   hipStream_t s, bool bf16, EkvRows rows) {
-  const DecodeInstance* in = decode_instance(a, tb, head_dim, bf16, rows, sc.birth != nullptr);
+                                   hipStream_t s, bool bf16, EkvRows rows, bool capped) {
+  const DecodeInstance* in = decode_instance(a, tb, head_dim, bf16, rows, sc.birth != nullptr, capped);
   return in ? in->fused(a, sc, tb, a.n_q_heads / a.n_kv_heads, count, nw, s) : hipErrorInvalidValue;
 }
 

@@ -316,6 +316,67 @@ __device__ __forceinline__ ekv_u6 ekv_fp6_quant_block(const uint4* src, uint32_t
   return ekv_fp6_quant32(f, ekv_fp4_exp_scale(e));
 }
 
+// ---- attention-logit soft-capping (include/easykv_hip.h, "soft-capped logits"): s = cap * tanh(x / cap), x = q.k / sm_div ----------
+// The one place the capped logit is computed: every kernel of an EKV_SOFTCAP = 1 build calls ekv_softcap on the fp32 quotient it would
+// otherwise have used as the logit, before the mask, the running maximum and the exponent, and everything downstream (softmax, exported
+// logits, (m, l, o) partials, row statistics, column sums, scorers and tails) sees only the result.  y = x / cap is the correctly
+// rounded quotient.  Three ranges of |y|, each free of the cancellation of 1 - 2 / (1 + e^2y) near 0 (one ulp of 1.0 there is
+// cap * 6e-8 on the logit, ten times what torch's own fp32 tanh leaves):
+//   |y| < 0.6         tanh y = y + y * w(y), w(y) = y^2 * P(y^2) (degree 5, |error| 3.4e-10 relative); the result is fma(x, w, x), so the
+//                     leading term is x itself and no rounding of y or of cap * ... reaches it
+//   0.6 <= |y| < 1.6  tanh(a + u) = A + (1 - A^2) * tau / (1 + A * tau) around the nearest of four centres a (|u| <= 0.125), tau = tanh u by
+//                     the same polynomial, A = tanh a as an fp32 pair: the correction stays below 0.08, so its roundings stay below half an
+//                     ulp of the result
+//   |y| >= 1.6        1 - 2 / (1 + e^(2|y|)), the exponent's argument carried as an fp32 pair (2 / (1 + e) < 0.08: v_exp_f32's own ulp is
+//                     far below the result's); |y| is clamped to 44 (e^88 is finite), so +-inf gives +-cap
+// NaN takes the last branch and propagates; the result is odd in x by construction (|y| and a sign copy) and within 0.75 ulp of
+// cap * tanh(x / cap) for a power-of-two cap, within 2 ulp for any other (the rounding of y, as in torch's three ops).  Measured against
+// float64 per decade of |y|: profiles/softcap_accuracy.json, tests/test_hip_softcap.py.
+#ifndef EKV_SOFTCAP
+#define EKV_SOFTCAP 0
+#endif
+__device__ __forceinline__ float ekv_tanh_w(float u) {      // tanh(u) / u - 1 for |u| <= 0.6
+  const float z = u * u;
+  float p = 0x1.3719fcp-9f;
+  p = fmaf(p, z, -0x1.13a9a0p-7f);
+  p = fmaf(p, z, 0x1.64fe24p-6f);
+  p = fmaf(p, z, -0x1.ba0dcap-5f);
+  p = fmaf(p, z, 0x1.1110f6p-3f);
+  p = fmaf(p, z, -0x1.555556p-2f);
+  return z * p;
+}
+__device__ __forceinline__ float ekv_softcap(float x, float cap) {
+  const float y = x / cap, ay = fabsf(y);
+  if (ay < 0.6f) return fmaf(x, ekv_tanh_w(y), x);
+  float t;
+  if (ay < 1.6f) {
+    // centre a, tanh a = ah + al, 1 - tanh^2 a
+    const bool c1 = ay >= 0.85f, c2 = ay >= 1.1f, c3 = ay >= 1.35f;
+    const float a = c3 ? 1.475f : (c2 ? 1.225f : (c1 ? 0.975f : 0.725f));
+    const float ah = c3 ? 0x1.cd11e0p-1f : (c2 ? 0x1.aea7aap-1f : (c1 ? 0x1.807516p-1f : 0x1.3d703cp-1f));
+    const float al = c3 ? -0x1.470dbcp-26f : (c2 ? -0x1.1e7b62p-26f : (c1 ? -0x1.b0c960p-31f : -0x1.85a524p-26f));
+    const float b = c3 ? 0x1.832d40p-3f : (c2 ? 0x1.2b8854p-2f : (c1 ? 0x1.bea088p-2f : 0x1.3b306ep-1f));
+    const float u = ay - a;      // (exact: both in [0.6, 1.6))
+    const float tau = fmaf(u, ekv_tanh_w(u), u);
+    t = ah + (al + (tau * b) / fmaf(ah, tau, 1.f));
+  } else {
+    const float ac = ay > 44.f ? 44.f : ay;      // (NaN stays NaN)
+    const float k = 2.f * EKV_LOG2E, kl = (float)(2.0 * 1.4426950408889634 - (double)(2.f * EKV_LOG2E));
+    const float eh = ac * k;
+    const float el = fmaf(ac, kl, fmaf(ac, k, -eh));      // the argument's low part: 2 |y| log2 e = eh + el
+    const float e0 = exp2f(eh);
+    const float e = fmaf(e0, el * 0.6931471805599453f, e0);
+    t = 1.f - 2.f / (1.f + e);
+  }
+  return cap * copysignf(t, y);
+}
+// The logit of a (row, query head) from its dot product: the quotient, capped in the EKV_SOFTCAP builds (decode kernels)
+#if EKV_SOFTCAP
+#define EKV_LOGIT(acc, a) ekv_softcap((acc) / (a).sm_div, (a).softcap)
+#else
+#define EKV_LOGIT(acc, a) ((acc) / (a).sm_div)
+#endif
+
 // f32 -> one 16-bit output element, rounded to nearest even (bf16: v_cvt_pk_bf16_f32, NaN kept), as the __half the row pointers hold
 __device__ __forceinline__ __half ekv_to_e(float x) {
 #if EKV_BF16

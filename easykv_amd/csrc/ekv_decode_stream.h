@@ -349,7 +349,7 @@ __device__ __forceinline__ void ekv_decode_stream(const EkvAttnArgs& a, const in
       } else {
         acc = ekv_dot8(qv[r], kn, 0.f);
       }
-      acc = KV8 ? ekv_group_sum<LPR>(acc) * ksn / a.sm_div : ekv_group_sum<LPR>(acc) / a.sm_div;
+      acc = KV8 ? ekv_group_sum<LPR>(acc) * ksn / a.sm_div : EKV_LOGIT(ekv_group_sum<LPR>(acc), a);
       if (logit_out != nullptr && sub == 0 && r < nrep) logit_out[(size_t)r * logit_stride + (PHYS ? slot_new : t_new)] = acc;
       // one more row for this lane group's online softmax
       const float mn = fmaxf(m[r], acc);
@@ -567,7 +567,7 @@ __device__ __forceinline__ void ekv_decode_stream(const EkvAttnArgs& a, const in
           else acc = KV8 ? ekv_dot16_fp8(qv[r], qv1[r], kr[u], 0.f) : ekv_dot8(qv[r], kr[u], 0.f);
           acc = ekv_group_sum<LPR>(acc);
           if constexpr (KV8) acc *= ksc[u];
-          s[u] = (PHYS ? !((dead8 >> u) & 1u) : (j0 + u < t1)) ? acc / a.sm_div : EKV_NEG_INF;
+          s[u] = (PHYS ? !((dead8 >> u) & 1u) : (j0 + u < t1)) ? EKV_LOGIT(acc, a) : EKV_NEG_INF;
         }
       }
       // export the raw logits: lane `sub` of the group owns row j0+sub -> 8 consecutive floats per group

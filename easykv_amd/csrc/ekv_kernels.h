@@ -74,6 +74,7 @@ struct EkvStepPlan {
   // offset of its selection keys [layer_count][H][t_pad] uint32 (-1 = not in the layout)
   int32_t long_rows, long_tiles;
   int64_t key_rows;
+  int32_t capped;       // an ekv_cap_* call: the launches run the EKV_SOFTCAP instances (chunk steps: the one-tile 16x16x32 build alone)
 };
 // The table of a batched decode step as the kernels' batch instances receive it: BY VALUE, behind the argument structs of the uniform
 // kernel (2304 bytes of the 4 KB a launch may carry).  Workgroup (head, entry ll) shadows the per-step fields of its argument structs
@@ -126,6 +127,9 @@ struct EkvAttnArgs {
   uint32_t* arrive;            // split decode kernel: non-null = fold the key-range partials in the kernel (last-arriving split of a
                                //   head) and write the fp16 output to out_direct; the bank's counters [n_layers][H], 0 when idle
   float sm_div;
+  // soft-capped logits (the ekv_cap_* calls; read by the EKV_SOFTCAP instances only): the cap, finite and > 0.  It fills the padding
+  // behind sm_div, so the struct, its offsets and with them every other instance stay as they were.
+  float softcap;
   // deferred column-sum pass of the wide-block kernel (ekv_step.defer_layers, chunk steps): the one pass of a layer keeps its raw
   // queries in q_keep ([layers][Hq][q_len][D], this call's slice); the column-sum pass at the flush reads them as `q` and takes the
   // chunk's own K rows from the cache slots (new_in_cache) instead of k_new
@@ -183,17 +187,21 @@ struct EkvScoreArgs {
 // or FP8 rows, plain keys, ordered score rows): `a` / `sc` are the envelope's arguments with layer_begin = 0 and a.arrive = the bank's
 // counters, and `count` is the number of table entries, one workgroup row each.
 // rows: the instances of that row format (kv8: a.k_scale / a.v_scale set, kv4 / kv6: a.k_exp / a.v_exp, kv84: a.k_scale / a.v_exp, kv164: a.v_exp; plain keys either way)
-hipError_t ekv_launch_attn_decode(const EkvAttnArgs& a, const EkvSeqTable* tb, int head_dim, int count, hipStream_t s, bool bf16, EkvRows rows);
+// capped (every launcher below that takes it): the EKV_SOFTCAP instances, a.softcap set (ekv_cap_* calls)
+hipError_t ekv_launch_attn_decode(const EkvAttnArgs& a, const EkvSeqTable* tb, int head_dim, int count, hipStream_t s, bool bf16, EkvRows rows,
+                                  bool capped = false);
 // passes (wide-block kernel, two-pass scheme): bit 0 = the one pass (output + row statistics), bit 1 = the column-sum pass
 // tail_sc (wide-block kernel, two passes, passes & 2): the step's scorer runs as the tail of the column-sum pass (ekv_wide_tail.h)
 // wide: the wide-block kernel (ekv_chunk_wide, ekv_plan.h)
 hipError_t ekv_launch_attn_chunk(const EkvAttnArgs& a, int head_dim, int layer_count, bool wide, bool two_pass, hipStream_t s,
-                                 const EkvScoreArgs* fuse_sc, int passes, const EkvScoreArgs* tail_sc, bool bf16);
+                                 const EkvScoreArgs* fuse_sc, int passes, const EkvScoreArgs* tail_sc, bool bf16, bool capped = false);
 hipError_t ekv_launch_attn_resident(const EkvAttnArgs& a, const EkvScoreArgs& sc, int layer_count, hipStream_t s, bool bf16);
 hipError_t ekv_launch_tova_headmean(const EkvScoreArgs& a, int layer_count, hipStream_t s);
 hipError_t ekv_launch_score_select(const EkvScoreArgs& a, int layer_count, hipStream_t s, bool bf16);
 hipError_t ekv_launch_decode_fused(const EkvAttnArgs& a, const EkvScoreArgs& sc, const EkvSeqTable* tb, int head_dim, int count, int nw,
-                                   hipStream_t s, bool bf16, EkvRows rows);
+                                   hipStream_t s, bool bf16, EkvRows rows, bool capped = false);
+// ekv_softcap_eval: out[i] = ekv_softcap(x[i] / sm_div, cap) (ekv_attn_decode_dispatch.hip)
+hipError_t ekv_launch_softcap_eval(const float* x, int64_t n, float sm_div, float cap, float* out, hipStream_t s);
 // Long-row scorer (ekv_score_long.inc; one build for fp16 and bf16 banks).  a.big_rows and key_rows ([layer_count][H][a.big_stride]
 // uint32) must be set.  plain_big: the plain call's plan of this step keeps its rows in scratch (it decides which build of the generic
 // scorer the plain call runs, and with it the batch width of the partials fold: ekv_score_select_threads).
@@ -270,12 +278,19 @@ __device__ __forceinline__ EkvScoreArgs ekv_batch_score_args(const EkvScoreArgs&
 #define EKV_ROWS_TAG
 #endif
 
+// soft-capped logits (EKV_SOFTCAP = 1: the EKV_DECODE_CAP and EKV_CHUNK_CAP lines of the manifest; ekv_common.h)
+#if defined(EKV_SOFTCAP) && EKV_SOFTCAP
+#define EKV_CAP_TAG _cap
+#else
+#define EKV_CAP_TAG
+#endif
+
 // ---- kernel instances (ekv_instances.def; DESIGN.md "kernel instances")
-// Kernel symbol of an instance = the kernel's name + independent tags that default to empty: _batch, _kv8, _bf16 (ekv_common.h).  A
+// Kernel symbol of an instance = the kernel's name + independent tags that default to empty: _batch, _kv8, _cap, _bf16 (ekv_common.h).  A
 // kernel source renames itself with  #define ekv_x_kernel EKV_KERNEL_NAME(ekv_x_kernel)  (profiles and traces know these names).
-#define EKV_KERNEL_NAME_(base, b, r, t) base##b##r##t
-#define EKV_KERNEL_NAME_X(base, b, r, t) EKV_KERNEL_NAME_(base, b, r, t)
-#define EKV_KERNEL_NAME(base) EKV_KERNEL_NAME_X(base, EKV_BATCH_TAG, EKV_ROWS_TAG, EKV_DT_TAG)
+#define EKV_KERNEL_NAME_(base, b, r, c, t) base##b##r##c##t
+#define EKV_KERNEL_NAME_X(base, b, r, c, t) EKV_KERNEL_NAME_(base, b, r, c, t)
+#define EKV_KERNEL_NAME(base) EKV_KERNEL_NAME_X(base, EKV_BATCH_TAG, EKV_ROWS_TAG, EKV_CAP_TAG, EKV_DT_TAG)
 // Launcher of an instance = the family's entry + every word of its manifest line, in the line's order.  The instance (which pastes
 // its own switches: EKV_D, EKV_KEYS, EKV_ELEM, EKV_ROWS, EKV_BATCHING, ...) and the dispatch tables (which paste the manifest's words)
 // both spell it through these macros.
@@ -287,6 +302,8 @@ __device__ __forceinline__ EkvScoreArgs ekv_batch_score_args(const EkvScoreArgs&
 #define EKV_FN_ELEM(fn, elem) EKV_FN_ELEM_(fn, elem)
 #define EKV_FN_CHUNK_(d, m, elem) ekv_launch_attn_chunk_d##d##_m##m##_##elem
 #define EKV_FN_CHUNK(d, m, elem) EKV_FN_CHUNK_(d, m, elem)
+#define EKV_FN_CHUNK_CAP_(d, m, elem) ekv_launch_attn_chunk_cap_d##d##_m##m##_##elem
+#define EKV_FN_CHUNK_CAP(d, m, elem) EKV_FN_CHUNK_CAP_(d, m, elem)
 #define EKV_FN_WIDE_(d, m, keys, elem) ekv_launch_attn_wide_d##d##_m##m##_##keys##_##elem
 #define EKV_FN_WIDE(d, m, keys, elem) EKV_FN_WIDE_(d, m, keys, elem)
 #define EKV_FN_D_ELEM_(fn, d, elem) fn##_d##d##_##elem
@@ -296,6 +313,10 @@ __device__ __forceinline__ EkvScoreArgs ekv_batch_score_args(const EkvScoreArgs&
 // the manifest's words as the fields of a table entry: booleans, and EKV_ROWS_<rows> above
 #define EKV_IS_plain false
 #define EKV_IS_rope true
+#define EKV_IS_cap false      // (`cap`, the keys word in the launcher names of the soft-capped decode instances: plain keys ...
+#define EKV_CAPPED_plain false
+#define EKV_CAPPED_rope false
+#define EKV_CAPPED_cap true   //  ... and capped logits)
 #define EKV_IS_f16 false
 #define EKV_IS_bf16 true
 #define EKV_IS_single false

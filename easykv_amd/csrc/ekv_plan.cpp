@@ -277,6 +277,8 @@ struct StepShape {
   int LC;                 // layers the workspace is laid out for: all deferred layers (ekv_step.defer_layers), whatever this call launches
   int max_rows;           // rows an unsplit chunk workgroup may walk (its slot entries live in LDS): 6144 with RoPE-on-read, 16384 plain
   bool long_rows;         // a long call (ekv_plan_step): the long-row scorer where the plan would end in the generic one
+  bool capped;            // a capped call (ekv_plan_step): chunk steps on the one-tile build of the 16x16x32 kernel alone
+  int Dblk;               // the head_dim a chunk step's query blocks are cut for: D, or kChunkNarrowD for a capped call (blocks of <= 32 rows)
 };
 
 // ---- stage 1: tiling
@@ -289,7 +291,7 @@ void plan_tiling(const StepShape& s, EkvStepPlan* P) {
   P->t_pad = (int)ekv_align((size_t)T, 64);
   P->qb_rows = P->n_qblocks = 1;
   int qpw = 1;
-  if (n > 1) ekv_chunk_blocks(rep, n, &P->qb_rows, &P->n_qblocks, &qpw, D);
+  if (n > 1) ekv_chunk_blocks(rep, n, &P->qb_rows, &P->n_qblocks, &qpw, s.Dblk);
   // physical extent E of the step (every live row has a physical index < E): the caller's value when it is consistent, else cap
   P->phys_extent = (st->phys_extent >= T && st->phys_extent <= bank->cap) ? st->phys_extent : bank->cap;
   // pitch of a logits row in the fused decode kernel's LDS: logical positions (RoPE-on-read streams in position order, the rotation
@@ -310,13 +312,13 @@ void plan_tiling(const StepShape& s, EkvStepPlan* P) {
   // model: those launches hold 8..32 heads, and their column-sum pass + scorer run once over all layers).  The kernel's scorer is the
   // wide column-sum pass's tail (ekv_wide_tail.h): where that tail is off (EKV_NO_WIDE_TAIL) the step is planned as any other.  It is
   // laid out as an unsplit two-pass step of the wide-block kernel (the workspace of one is never touched).
-  P->resident = (n > 1 && st->phases == 0 && !s.slot_rows && st->defer_layers == 0 && st->two_pass == 0 && n_split <= 1 &&
+  P->resident = (n > 1 && !s.capped && st->phases == 0 && !s.slot_rows && st->defer_layers == 0 && st->two_pass == 0 && n_split <= 1 &&
                  (st->policy == EKV_POLICY_H2O_HEAD || st->policy == EKV_POLICY_ROCO) && st->accumulate && !st->rope_on_read &&
                  P->n_qblocks == 1 && st->score_off >= 0 && st->score_off < T && ekv_attn_resident_supported(D, rep, n, T, s.W) &&
                  ekv_wide_tail_supported(s.W, 1)) ? 1 : 0;
   if (P->resident) n_split = 1;
   P->two_pass = (P->resident || (n > 1 && ekv_chunk_two_pass(D, rep, n, st->policy, s.scored, st->accumulate != 0, st->rope_on_read != 0, st->two_pass))) ? 1 : 0;
-  P->wide = (P->resident || (n > 1 && ekv_chunk_wide(D, rep, n, st->rope_on_read != 0, P->two_pass, !P->two_pass && s.scored && st->accumulate != 0))) ? 1 : 0;
+  P->wide = (P->resident || (n > 1 && !s.capped && ekv_chunk_wide(D, rep, n, st->rope_on_read != 0, P->two_pass, !P->two_pass && s.scored && st->accumulate != 0))) ? 1 : 0;
   if (n_split <= 0 && n > 1) {
     // Chunk steps (two or three workgroups per CU): a split costs a partial per query row and split, a fold in the scorer and a
     // shorter stream per workgroup, so the grid is filled to the 256..512 workgroups that are resident at a time — not to 1024:
@@ -487,7 +489,7 @@ bool plan_whole_step(const StepShape& s, EkvStepPlan* P, int* rc) {
     return true;
   }
   // small-row chunk step (configs[1]: stride 8): one launch, logits in LDS, K and V read once
-  if (s.n > 1 && ekv_chunk_lds_supported(bank, st, P->phys_extent, s.scored) && (heads_now >= 256 || s.T <= 1024)) {
+  if (s.n > 1 && !s.capped && ekv_chunk_lds_supported(bank, st, P->phys_extent, s.scored) && (heads_now >= 256 || s.T <= 1024)) {
     P->one_launch = 1;
     run(P, EKV_RUN_CHUNK_LDS, 1);
     return true;
@@ -561,13 +563,13 @@ int plan_ending(const StepShape& s, EkvStepPlan* P, StepEnding* end) {
   // (a long call: the keys are in scratch, so no width bound; what its sweep keeps in LDS is the (M, 1 / L) pair of every logits row —
   //  the term the bound above also carries, and the same 160 KB)
   if (generic_scorer && s.long_rows && ekv_long_sweep_lds(shape.colsum != nullptr ? 0 : (i64)rep * n) > 160 * 1024) return EKV_E_UNSUPPORTED;
-  if (n == 1 ? !ekv_attn_decode_supported(D, rep) : !ekv_attn_chunk_supported(D, rep, n)) return EKV_E_UNSUPPORTED;
+  if (n == 1 ? !ekv_attn_decode_supported(D, rep) : !ekv_attn_chunk_supported(s.Dblk, rep, n)) return EKV_E_UNSUPPORTED;
   // the 16x16x32 chunk kernel keeps the slot entries of its key range, its K/V tiles and (some builds) the query block in LDS: one CU's
   // 160 KB bound every launch of the step (ekv_chunk_step_lds, ekv_geometry.h — the arithmetic its launcher sizes the launch with).  The
   // row bound of the tiling (max_rows) keeps every head_dim up to 256 inside it; a step beyond it is refused here, not at the launch.
   if (n > 1 && !P->wide && !P->resident) {
     int qb_rows, n_qblocks, qpw;
-    ekv_chunk_blocks(rep, n, &qb_rows, &n_qblocks, &qpw, D);
+    ekv_chunk_blocks(rep, n, &qb_rows, &n_qblocks, &qpw, s.Dblk);
     if (ekv_chunk_step_lds(D, qpw, st->rope_on_read != 0, P->two_pass != 0, P->rows_per_split, P->fold_in_kernel != 0) > 160 * 1024)
       return EKV_E_UNSUPPORTED;
   }
@@ -677,7 +679,7 @@ void plan_long_layout(const StepShape& s, EkvStepPlan* P) {
 // EKV_RUN_LONG_SCORE, two kernels; a preceding EKV_RUN_TOVA_MEAN stays; EKV_RUN_LONG_FOLD in front where the generic scorer would have
 // folded the output itself), the width refusal of plan_ending does not apply, and the workspace grows by that scorer's scratch
 // (plan_long_layout).  A step that ends anywhere else plans field for field as the plain call.
-int ekv_plan_step(const ekv_bank* bank, const ekv_step* step, EkvStepPlan* P, bool long_rows) {
+int ekv_plan_step(const ekv_bank* bank, const ekv_step* step, EkvStepPlan* P, bool long_rows, bool capped) {
   *P = EkvStepPlan{};
   P->key_rows = -1;
   const int bank_rc = check_bank(bank);
@@ -698,6 +700,8 @@ int ekv_plan_step(const ekv_bank* bank, const ekv_step* step, EkvStepPlan* P, bo
   s.LC = step->defer_layers > 0 ? step->defer_layers : step->layer_count;
   s.max_rows = step->rope_on_read ? 6144 : 16384;
   s.long_rows = long_rows;
+  s.capped = capped;
+  s.Dblk = capped ? kChunkNarrowD : s.D;
 
   plan_tiling(s, P);
   plan_layout(s, P);
@@ -793,7 +797,19 @@ int resolve_call(const EkvCall& c, EkvResolved* r) {
   }
 
   // (a long call is a 16-bit, single-sequence call: its entry points spell nothing else, and no other combination has an instance)
-  const int rc = (c.long_rows && (quant || c.batch)) ? EKV_E_UNSUPPORTED : ekv_plan_step(bank, r->step, P, c.long_rows);
+  // Capped calls (ekv_cap_*), the rule of the family stated once.  "Capped" is one more independent variant of a call; its entry points
+  // spell 16-bit rows and one sequence only, and no other combination has an instance.  The cap must be finite and > 0 (argument error,
+  // behind the element type, before anything is planned).  A decode step plans field for field as the uncapped call of the same (bank,
+  // step, dtype) — splits, launches, workspace, phase order and resident rows — and runs the `cap` decode instances.  A chunk step or
+  // dense prefix plans onto the 16x16x32 kernel alone, in its one-tile build, at head_dim 128 as head_dim 256 always does (blocks of at
+  // most 32 folded rows; one pass or statistics + exact pass by the existing rules): never the wide, the logits-in-LDS or the
+  // logits-resident kernel.  Refused with zero launches and zero bytes: RoPE-on-read, head_dim 32 / 64 / 96, a chunk step whose GQA
+  // factor exceeds a block (EKV_E_UNSUPPORTED).
+  if (c.capped && !(c.softcap > 0.f && c.softcap <= 3.0e38f)) return EKV_E_ARG;
+  const int rc = ((c.long_rows || c.capped) && (quant || c.batch || (c.long_rows && c.capped)))
+                     ? EKV_E_UNSUPPORTED
+                     : ekv_plan_step(bank, r->step, P, c.long_rows, c.capped);
+  P->capped = c.capped ? 1 : 0;
   P->bf16 = c.dtype == EKV_DTYPE_BF16;
   P->rows = c.rows;
   P->batch = c.batch;
@@ -805,7 +821,7 @@ int resolve_call(const EkvCall& c, EkvResolved* r) {
       P->bytes = plain.bytes, P->big_rows = plain.big_rows, P->key_rows = -1;
     }
     P->one_launch = P->n_launches = P->n_list = P->long_rows = P->long_tiles = 0;
-    if (c.batch) P->bytes = 0;      // (nothing will run: ekv_batch_workspace_bytes of a refused table is 0)
+    if (c.batch || c.capped) P->bytes = 0;      // (nothing will run: ekv_batch_workspace_bytes of a refused table, ekv_cap_workspace_bytes of a refused step, is 0)
     return code;
   };
   const ekv_step* st = c.step;
@@ -816,6 +832,7 @@ int resolve_call(const EkvCall& c, EkvResolved* r) {
   }
   if (rc == EKV_OK && P->bf16 && st->rope_on_read) return refuse(EKV_E_UNSUPPORTED);
   if (rc != EKV_OK) return refuse(rc);
+  if (c.capped && (st->rope_on_read || (bank->head_dim != 128 && bank->head_dim != kChunkNarrowD))) return refuse(EKV_E_UNSUPPORTED);
   if (quant && (st->q_len != 1 || st->rope_on_read || !ekv_rows_head_dim(c.rows, bank->head_dim) ||
                 bank->n_q_heads / bank->n_kv_heads > kRowsRules[c.rows].max_rep))
     return refuse(EKV_E_UNSUPPORTED);
@@ -855,6 +872,7 @@ int call_info(const EkvCall& c, int32_t* info, int32_t n_info) {
   EkvResolved r;
   const bool ok = resolve_call(c, &r) == EKV_OK;
   if (c.dtype != EKV_DTYPE_F16 && c.dtype != EKV_DTYPE_BF16) return EKV_E_ARG;
+  if (c.capped && !(c.softcap > 0.f && c.softcap <= 3.0e38f)) return EKV_E_ARG;      // (a cap no step can be planned with)
   if (c.rows != EKV_ROWS_kv16 && !r.bank) return EKV_E_ARG;
   if (int e = check_bank(r.bank)) return e;
   if (!c.step || (c.batch && !c.seqs) || !info || n_info < 1) return EKV_E_ARG;

@@ -72,6 +72,8 @@ ROW_FORMATS = {
 }
 
 
+# head_dims the soft-capped kernels (KVBank(logit_cap=...)) are built for
+CAPPED_HEAD_DIMS = (128, 256)
 # head_dims served with plain keys and 16-bit rows only: no RoPE-on-read build (set_rope, streaming) and no quantised row format
 PLAIN_KEYS_HEAD_DIMS = (256,)
 
@@ -158,9 +160,19 @@ class KVBank:
     kv_quant = None      # quantize(): "fp8" / "mxfp4" / "mxfp6" / "fp8_mxfp4" / "k16_mxfp4" (ROW_FORMATS; _fmt is the entry, _desc the descriptor of its planes)
 
     long_rows = False    # KVBank(..., long_rows=True): the steps go to the long-row family (ekv_long_*), set per bank by __init__
+    logit_cap = None     # KVBank(..., logit_cap=c): soft-capped logits, the steps go to the capped family (ekv_cap_*), set per bank by __init__
+    sm_scale = None      # KVBank(..., sm_scale=s): logits are q.k * s (None: 1 / sqrt(head_dim)), in every call family
 
-    def __init__(self, n_layers, n_q_heads, n_kv_heads, head_dim, cap, device="cuda", scored=True, dtype=torch.float16, kv_quant=None, long_rows=False):
-        """``long_rows=True``: a 16-bit bank whose steps go to the long-row call family (include/easykv_hip.h, "long score rows"):
+    def __init__(self, n_layers, n_q_heads, n_kv_heads, head_dim, cap, device="cuda", scored=True, dtype=torch.float16, kv_quant=None, long_rows=False,
+                 logit_cap=None, sm_scale=None):
+        """``sm_scale``: the softmax scale, logits are ``q.k * sm_scale`` (None: ``1 / sqrt(head_dim)``; e.g. ``query_pre_attn_scalar ** -0.5``
+        of a Gemma 2 / Gemma 3 model).  Every call family reads it (``ekv_step.sm_div = 1 / sm_scale``).
+        ``logit_cap=c`` (finite, > 0): attention-logit soft-capping, ``s = c * tanh(q.k * sm_scale / c)`` before the mask and the
+        softmax (Gemma 2: ``attn_logit_softcapping``; include/easykv_hip.h, "soft-capped logits").  The bank's steps go to the capped
+        call family: decode steps plan as the uncapped ones, chunk steps and the dense prefix run on the 16x16 chunk kernel in blocks of
+        at most 32 folded rows.  head_dim 128 and 256, 16-bit rows, plain keys: not with ``kv_quant`` or ``long_rows``, and
+        :meth:`quantize` / :meth:`set_rope` refuse such a bank.
+        ``long_rows=True``: a 16-bit bank whose steps go to the long-row call family (include/easykv_hip.h, "long score rows"):
         planned and run exactly as the plain calls, except that a scored step which would end in the generic scorer ends in the
         long-row scorer instead, whose width is bounded by ``cap`` and the workspace, not by one CU's LDS (the plain family refuses
         such a step beyond about 38 400 score columns).  Same bits wherever both run.  Not with ``kv_quant``, and :meth:`quantize`
@@ -179,6 +191,20 @@ class KVBank:
             raise _lib.EkvError(f"KVBank(long_rows=True): the long-row scorer is built for 16-bit rows, not for {fmt['label']} rows "
                                 f"(kv_quant={kv_quant!r}): a quantised bank serves decode steps through its own calls, which have no long form")
         self.long_rows = bool(long_rows)
+        if sm_scale is not None and not (isinstance(sm_scale, (int, float)) and 0.0 < float(sm_scale) < math.inf):
+            raise ValueError(f"KVBank sm_scale must be None (1 / sqrt(head_dim)) or a finite number > 0, not {sm_scale!r}")
+        self.sm_scale = None if sm_scale is None else float(sm_scale)
+        if logit_cap is not None:      # (before anything is allocated)
+            if not (isinstance(logit_cap, (int, float)) and 0.0 < float(logit_cap) < math.inf):
+                raise ValueError(f"KVBank logit_cap must be None or a finite number > 0, not {logit_cap!r}")
+            if fmt is not None:
+                raise _lib.EkvError(f"KVBank(logit_cap=...): soft-capped logits are built for 16-bit rows, not for {fmt['label']} rows "
+                                    f"(kv_quant={kv_quant!r}): there is no capped quantised call")
+            if long_rows:
+                raise _lib.EkvError("KVBank(logit_cap=..., long_rows=True): there is no capped long call (the long-row family has no soft-capped form)")
+            if head_dim not in CAPPED_HEAD_DIMS:
+                raise _lib.EkvError(f"KVBank(logit_cap=...): soft-capped logits are built for head_dim {' and '.join(map(str, CAPPED_HEAD_DIMS))}, not {head_dim}")
+            self.logit_cap = float(logit_cap)
         if fmt is not None:
             _check_row_shape(fmt, head_dim, n_q_heads // max(1, n_kv_heads))
         self.dtype, self._dt = dtype, _lib.DTYPE_CODES[dtype]
@@ -334,6 +360,9 @@ class KVBank:
         if fmt is None:
             raise ValueError("quantize(kind): kind must be 'fp8' or 'mxfp4'")
         m = fmt["method"] + "()"
+        if self.logit_cap is not None:
+            raise _lib.EkvError(f"{m}: the bank was created with logit_cap={self.logit_cap:g}, and soft-capped logits are built for 16-bit "
+                                f"rows, not for {fmt['label']} rows: there is no capped quantised call")
         if self.long_rows:
             raise _lib.EkvError(f"{m}: the bank was created with long_rows=True, and the long-row scorer is built for 16-bit rows, not "
                                 f"for {fmt['label']} rows: {fmt['label']} rows have no long form")
@@ -413,6 +442,9 @@ class KVBank:
         self._check_fn, self._info_fn, self._ws_fn, self._attend_fn = (self._calls[False, what] for what in _lib.STEP_CALLS)
         if self.long_rows:      # (16-bit rows: __init__ and quantize() refuse every other format) the long family, same signatures
             self._check_fn, self._info_fn, self._ws_fn, self._attend_fn = (getattr(self.lib, _lib.LONG_CALLS[what]) for what in _lib.STEP_CALLS)
+        if self.logit_cap is not None:      # (16-bit rows likewise) the capped family: the cap stands behind the dtype, where a quantised call has its descriptor
+            self._check_fn, self._info_fn, self._ws_fn, self._attend_fn = (getattr(self.lib, _lib.CAP_CALLS[what]) for what in _lib.STEP_CALLS)
+            self._desc_ref = (C.c_float(self.logit_cap),)
 
     def kv_bytes(self) -> int:
         """Bytes held for the K/V rows: 16-bit rows, FP8 codes + row scales (``2 * head_dim + 8`` per row pair), or MXFP4 codes +
@@ -491,6 +523,8 @@ class KVBank:
     def set_rope(self, cos, sin):
         """fp32 tables ``[>= cap, head_dim]`` for the streaming (rope-on-read) variant."""
         self._quant_refuse(True, "set_rope (RoPE-on-read)")
+        if self.logit_cap is not None:
+            raise _lib.EkvError("set_rope(): RoPE-on-read has no soft-capped build (a bank created with logit_cap serves plain keys only)")
         if self.head_dim in PLAIN_KEYS_HEAD_DIMS:
             raise _lib.EkvError(f"set_rope(): RoPE-on-read has no build for head_dim {self.head_dim} (plain keys only)")
         self.rope_cos = cos.to(self.device, torch.float32).contiguous()
@@ -559,7 +593,7 @@ class KVBank:
         st.rope_on_read = int(plan.streaming)
         st.n_split = plan.n_split
         st.two_pass = plan.two_pass or KVBank.default_two_pass
-        st.sm_div = math.sqrt(self.head_dim)
+        st.sm_div = math.sqrt(self.head_dim) if self.sm_scale is None else 1.0 / self.sm_scale
         st.tova_head_mean = int(plan.tova_head_mean)
         st.roco_tail = ROCO_TAIL
         st.range_start = -1
@@ -584,7 +618,7 @@ class KVBank:
         """(n_split, fused) the library will use for this step."""
         st = self.make_step(plan, q_len, layer_begin, self.n_layers - layer_begin if layer_count is None else layer_count)
         st.phases = phases
-        if self._fmt is not None or self.long_rows:      # (the dry run of the bank's own family: a step the bank refuses plans as not fused)
+        if self._fmt is not None or self.long_rows or self.logit_cap is not None:      # (the dry run of the bank's own family: a step the bank refuses plans as not fused)
             info = self.step_info(plan, q_len, layer_begin, layer_count, phases)
             return info["n_split"], bool(info["fused"])
         ns, fu = C.c_int32(0), C.c_int32(0)
@@ -674,9 +708,7 @@ class KVBank:
             st = self.make_step(plan, n, 0, 1)
             if plan.n_split <= 0:      # the split count of a one-layer launch, fixed for both halves of the step
                 st.phases = 1
-                ns, fu = C.c_int32(0), C.c_int32(0)
-                check(self.lib.ekv_step_plan(C.byref(self._bank), C.byref(st), C.byref(ns), C.byref(fu)), "ekv_step_plan")
-                st.n_split = ns.value
+                st.n_split = self._planned_split(st)
             st.defer_layers = self.n_layers
             # the scorer shape of the flush() call (phases = 8 over all layers) is validated NOW, before the first layer's
             # attention appends a row: a shape only the last call of the token would refuse must not leave the bank half-stepped
@@ -708,15 +740,24 @@ class KVBank:
         d["pending"] += 1
         return out
 
+    def _planned_split(self, st) -> int:
+        """The split count the library plans for ``st`` (a capped bank: by its own family — a capped chunk step is tiled in narrower
+        blocks than the plain call's)."""
+        if self.logit_cap is not None:
+            info = (C.c_int32 * 10)()
+            check(self._info_fn(C.byref(self._bank), C.byref(st), self._dt, *self._desc_ref, info, 10), self._info_fn.__name__)
+            return int(info[0])
+        ns, fu = C.c_int32(0), C.c_int32(0)
+        check(self.lib.ekv_step_plan(C.byref(self._bank), C.byref(st), C.byref(ns), C.byref(fu)), "ekv_step_plan")
+        return ns.value
+
     def deferred_workspace_bytes(self, plan: StepPlan, q_len: int) -> int:
         """Scratch a step of ``q_len`` queries needs when the scorers of all layers are deferred to :meth:`flush` (the logits / column
         sums of every layer stay alive until then)."""
         st = self.make_step(plan, q_len, 0, 1)
         if plan.n_split <= 0:
             st.phases = 1
-            ns, fu = C.c_int32(0), C.c_int32(0)
-            check(self.lib.ekv_step_plan(C.byref(self._bank), C.byref(st), C.byref(ns), C.byref(fu)), "ekv_step_plan")
-            st.n_split = ns.value
+            st.n_split = self._planned_split(st)
         st.defer_layers, st.layer_begin, st.layer_count, st.defer_index, st.phases = self.n_layers, 0, self.n_layers, 0, 8
         return int(self._step_ws_bytes(st))
 
@@ -851,8 +892,11 @@ class KVBankBatch:
     :meth:`attend` serves model layer ``layer`` of any subset of the sequences — each with its own cache length, score offset and
     eviction geometry — in ONE call: one launch per kernel kind over the layers ``{s * n_layers + layer}``."""
 
-    def __init__(self, n_seq, n_layers, n_q_heads, n_kv_heads, head_dim, cap, device="cuda", scored=True, dtype=torch.float16, kv_quant=None, long_rows=False):
-        """``kv_quant='fp8'``: the shared bank holds FP8 planes only from the start (the 16-bit rows of ``n_seq`` sequences are never
+    def __init__(self, n_seq, n_layers, n_q_heads, n_kv_heads, head_dim, cap, device="cuda", scored=True, dtype=torch.float16, kv_quant=None, long_rows=False,
+                 logit_cap=None, sm_scale=None):
+        """``sm_scale``: the softmax scale of every sequence (:class:`KVBank`; None: ``1 / sqrt(head_dim)``).  ``logit_cap`` raises: there is
+        no capped batch call.
+        ``kv_quant='fp8'``: the shared bank holds FP8 planes only from the start (the 16-bit rows of ``n_seq`` sequences are never
         allocated); its sequences are filled by :meth:`adopt` from banks quantised by :meth:`KVBank.quantize_fp8`.
         ``kv_quant='mxfp4'``: likewise with MXFP4 planes, filled from banks quantised by :meth:`KVBank.quantize_mxfp4`.
         ``kv_quant='mxfp6'``: likewise with MXFP6 planes (:meth:`KVBank.quantize_mxfp6`).
@@ -861,10 +905,13 @@ class KVBankBatch:
         if long_rows:
             raise _lib.EkvError("KVBankBatch(long_rows=True): the long-row scorer is built for single sequences, not for decode batches: "
                                 "the batched calls have no long form (what a batch leaves to the generic scorer it refuses)")
+        if logit_cap is not None:
+            raise _lib.EkvError("KVBankBatch(logit_cap=...): soft-capped logits are built for single sequences, not for decode batches: "
+                                "there is no capped batch call")
         if not 1 <= n_seq <= _lib.MAX_SEQS:
             raise ValueError(f"a decode batch holds 1..{_lib.MAX_SEQS} sequences, not {n_seq}")
         self.n_seq, self.n_layers = n_seq, n_layers
-        self.bank = KVBank(n_seq * n_layers, n_q_heads, n_kv_heads, head_dim, cap, device, scored, dtype, kv_quant)
+        self.bank = KVBank(n_seq * n_layers, n_q_heads, n_kv_heads, head_dim, cap, device, scored, dtype, kv_quant, sm_scale=sm_scale)
         self.lib, self.dtype = self.bank.lib, dtype
         self.n_q_heads, self.n_kv_heads, self.head_dim, self.cap, self.device = n_q_heads, n_kv_heads, head_dim, self.bank.cap, self.bank.device
         self.n_calls = 0      # batched attend calls issued (one per layer and decode forward)

@@ -25,13 +25,26 @@ IMPL = "easykv_amd"
 _registered = False
 
 
-def _easykv_attention(module, query, key, value, attention_mask=None, dropout=0.0, scaling=None, **kwargs):
+def _easykv_attention(module, query, key, value, attention_mask=None, dropout=0.0, scaling=None, softcap=None, **kwargs):
+    """The attention function of the seam.  ``scaling`` and ``softcap`` (Gemma 2 passes ``attn_logit_softcapping`` under that name) are what
+    the MODULE would compute with; the kernels compute with the active cache's ``sm_scale`` / ``logit_cap`` (set by the driver from the
+    model's config).  They are held against each other (relative tolerance 1e-3) and a mismatch raises rather than compute another model.
+    ``sliding_window`` (in ``kwargs``) is ignored: the retained cache is attended whole, on Gemma 2's local layers too, as the reference
+    does for Mistral."""
     cache = api.active_cache()
     if cache is None:
         raise RuntimeError("easykv_amd attention called outside easykv_generate(): no BudgetedKVCache is active")
     d = query.shape[-1]
-    if scaling is not None and abs(scaling * (d ** 0.5) - 1.0) > 1e-3:
-        raise ValueError("easykv_amd attention supports the standard 1/sqrt(head_dim) scaling only")
+    sm_scale, logit_cap = getattr(cache, "sm_scale", None), getattr(cache, "logit_cap", None)
+    if sm_scale is None:
+        if scaling is not None and abs(scaling * (d ** 0.5) - 1.0) > 1e-3:
+            raise ValueError("easykv_amd attention supports the standard 1/sqrt(head_dim) scaling only")
+    elif abs((d ** -0.5 if scaling is None else scaling) / sm_scale - 1.0) > 1e-3:
+        raise ValueError(f"easykv_amd attention: the module scales its logits by {d ** -0.5 if scaling is None else scaling:g}, the active cache by {sm_scale:g}")
+    if softcap is not None and softcap is not False and logit_cap is None:
+        raise ValueError(f"easykv_amd attention: the module soft-caps its logits at {softcap:g}, the active cache has no logit_cap")
+    if logit_cap is not None and (softcap is None or abs(softcap / logit_cap - 1.0) > 1e-3):
+        raise ValueError(f"easykv_amd attention: the active cache soft-caps its logits at {logit_cap:g}, the module at {softcap}")
     if cache.streaming:
         # streaming=True (llama_patch.py:310-327) caches UN-rotated keys; the stock module has already applied RoPE at the
         # true positions, so take it off again (rotation by -theta: x = x'*cos - rotate_half(x')*sin, fp32)

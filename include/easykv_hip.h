@@ -519,6 +519,36 @@ int ekv_long_step_attend(const ekv_bank *bank, const ekv_step *step, int32_t dty
                          const void *v_new, void *out, int32_t *evict_ids, const float *rope_cos, const float *rope_sin,
                          void *workspace, size_t workspace_bytes, void *stream);
 
+/* Soft-capped logits (ABI 8, additive): the *_typed calls of a 16-bit bank with attention-logit soft-capping (Gemma 2:
+ * attn_logit_softcapping).  NORMATIVE.  For a real (not masked, not dead) key the logit of a capped call is
+ *
+ *     s = cap * tanh((q.k / sm_div) / cap)          in fp32, cap finite and > 0
+ *
+ * Masked and dead entries become -inf AFTER the cap (the mask is added to the capped logit); NaN propagates; +-inf gives +-cap.
+ * Everything downstream sees s and nothing else: the online and the exact softmax, the exported logits rows, the (m, l, o) partials and
+ * their fold, the row statistics and column sums of the two-pass chunk scheme, the decode tails and every scorer (eviction scores are
+ * sums of the probabilities of s).  The uncapped calls compute the same with s = q.k / sm_div.  One device function evaluates s for
+ * every capped kernel (ekv_softcap, csrc/ekv_common.h: a form without the cancellation of 1 - 2 / (1 + e^2y) near 0; within 0.75 ulp of
+ * the float64 value for a power-of-two cap, within 2 ulp otherwise), and ekv_softcap_eval below applies it to a vector for tests and tools.
+ * ekv_step.sm_div is free in every call family, capped or not: the logits are q.k / sm_div whatever head_dim is.
+ *
+ * A capped DECODE step plans field for field as the uncapped call of the same (bank, step, dtype): same n_split, launches, workspace,
+ * phase order and resident rows (info [9] and ekv_step_resident_rows of the plain call say which).  A capped CHUNK step or dense prefix
+ * runs on the 16x16x32 kernel alone, in blocks of at most 32 GQA-folded rows at head_dim 128 as at head_dim 256, one pass or statistics +
+ * exact pass by the rules of the plain call; it never resolves to the wide, the logits-in-LDS or the logits-resident kernel, so info [3]
+ * (wide) is always 0.  Refused before any launch, with ekv_cap_workspace_bytes = 0: rope_on_read, head_dim 32 / 64 / 96, chunk steps
+ * whose GQA factor exceeds 32 (EKV_E_UNSUPPORTED); a cap that is <= 0, NaN or infinite (EKV_E_ARG, behind the element type and before
+ * anything else is read).  16-bit rows and single sequences only: there is no capped quantised, batched or long call. */
+int ekv_cap_step_check(const ekv_bank *bank, const ekv_step *step, int32_t dtype, float softcap);
+int ekv_cap_step_info(const ekv_bank *bank, const ekv_step *step, int32_t dtype, float softcap, int32_t *info, int32_t n_info);
+size_t ekv_cap_workspace_bytes(const ekv_bank *bank, const ekv_step *step, int32_t dtype, float softcap);
+int ekv_cap_step_attend(const ekv_bank *bank, const ekv_step *step, int32_t dtype, float softcap, const void *q, const void *k_new,
+                        const void *v_new, void *out, int32_t *evict_ids, const float *rope_cos, const float *rope_sin,
+                        void *workspace, size_t workspace_bytes, void *stream);
+/* out[i] = cap * tanh((x[i] / sm_div) / cap) by the kernels' own function; x and out are DEVICE pointers to n floats (n = 0: nothing
+ * runs).  EKV_E_ARG: n < 0, a NULL pointer with n > 0, sm_div <= 0 or NaN, a cap that is <= 0, NaN or infinite. */
+int ekv_softcap_eval(const float *x, int64_t n, float sm_div, float cap, float *out, void *stream);
+
 /* Batched decode steps (ABI 8, additive): ONE call, and one launch per kernel kind, serves n_seq sequences whose caches have
  * different lengths and different eviction geometry.  Each entry of the table names the bank layer it attends and carries what
  * ekv_step holds per step; entry i owns row i of the call's tensors.  The layers of a table need not be contiguous or ordered, so
