@@ -42,6 +42,14 @@ FAMILIES = {
     "EKV_CHUNK_CAP": lambda elem, d, m: (      # the 16x16x32 chunk kernel with soft-capped logits
         "ekv_attn_chunk.inc", f"ekv_attn_chunk_cap_d{d}_m{m}" + _tags(elem),
         _on(elem) + [f"-DEKV_D={d}", f"-DEKV_CHUNK_MODE={m}", "-DEKV_SOFTCAP=1"]),
+    # attention sinks (-DEKV_SINK=1): the decode kernels, the split path's scorer and the 16x16x32 chunk kernel, plain keys, 16-bit rows
+    "EKV_DECODE_SINK": lambda elem, d: (
+        "ekv_attn_decode.inc", f"ekv_attn_decode_d{d}_sink" + _tags(elem), _on(elem) + [f"-DEKV_D={d}", "-DEKV_ROPE=false", "-DEKV_SINK=1"]),
+    "EKV_DECODE_SCORE_SINK": lambda elem: ("ekv_decode_score.inc", "ekv_decode_score_sink" + _tags(elem), _on(elem) + ["-DEKV_SINK=1"]),
+    "EKV_TOVA_MEAN_SINK": lambda elem, nt: ("ekv_score_select.inc", "ekv_tova_headmean_sink", [f"-DEKV_SS_NT={nt}", "-DEKV_SINK=1"]),
+    "EKV_CHUNK_SINK": lambda elem, d, m: (
+        "ekv_attn_chunk.inc", f"ekv_attn_chunk_sink_d{d}_m{m}" + _tags(elem),
+        _on(elem) + [f"-DEKV_D={d}", f"-DEKV_CHUNK_MODE={m}", "-DEKV_SINK=1"]),
     "EKV_SOFTCAP_EVAL": lambda elem, nt: ("ekv_softcap_eval.inc", "ekv_softcap_eval", [f"-DEKV_EVAL_NT={nt}"]),
     "EKV_WIDE": lambda d, m, keys, elem: (
         "ekv_attn_wide.inc", "ekv_attn_wide" + ("_rope" if keys == "rope" else "") + f"_d{d}_m{m}" + _tags(elem),
@@ -103,7 +111,7 @@ def later_instances():
 
 
 def later_objects():
-    """(object name, hipcc arguments) of the instances of ekv_instances_later.def (the kv84 decode instances, the kv164 ones, the long-row scorer, head_dim 256, the soft-capped instances)."""
+    """(object name, hipcc arguments) of the instances of ekv_instances_later.def (the kv84 decode instances, the kv164 ones, the long-row scorer, head_dim 256, the soft-capped instances, the sink instances)."""
     return _instance_objects(later_instances())
 
 

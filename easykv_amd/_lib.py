@@ -50,6 +50,9 @@ LONG_INFO_N = 12      # EKV_LONG_INFO_N: [10] the step ends in the long-row scor
 # the soft-capped family (include/easykv_hip.h, "soft-capped logits"): the _typed calls with a float cap behind the dtype; 16-bit rows, one sequence
 CAP_CALLS = {what: "ekv_cap_" + what for what in STEP_CALLS}
 EXPORTS += tuple(CAP_CALLS[what] for what in STEP_CALLS) + ("ekv_softcap_eval",)
+# the sink family (include/easykv_hip.h, "attention sinks"): the _typed calls with the device pointer of the sinks behind the dtype; 16-bit rows, one sequence
+SINK_CALLS = {what: "ekv_sink_" + what for what in STEP_CALLS}
+EXPORTS += tuple(SINK_CALLS[what] for what in STEP_CALLS)
 
 
 class Bank(C.Structure):
@@ -150,6 +153,7 @@ def load():
             for what in STEP_CALLS:
                 getattr(lib, LONG_CALLS[what]).argtypes = [C.POINTER(Bank), C.POINTER(Step), i32] + tails[what]
                 getattr(lib, CAP_CALLS[what]).argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, C.c_float] + tails[what]
+                getattr(lib, SINK_CALLS[what]).argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, vp] + tails[what]
         if desc:
             getattr(lib, f"ekv_{rows}_quantize").argtypes = [C.POINTER(Bank), C.POINTER(desc), i32, i32, i32, i32, vp]
             getattr(lib, f"ekv_{rows}_dequantize").argtypes = [C.POINTER(Bank), C.POINTER(desc), i32, i32, i32, i32, vp, vp, vp]

@@ -40,7 +40,7 @@ from typing import List, Optional
 import torch
 
 from . import _lib
-from .engine import CAPPED_HEAD_DIMS, PLAIN_KEYS_HEAD_DIMS, KVBank, KVBankBatch, StepPlan, row_format
+from .engine import CAPPED_HEAD_DIMS, PLAIN_KEYS_HEAD_DIMS, SINK_HEAD_DIMS, KVBank, KVBankBatch, StepPlan, row_format
 
 KNOWN_POLICIES = ("roco", "h2o_head", "tova", "recency", "random", "full")
 SCORED = ("roco", "h2o_head", "tova")
@@ -100,10 +100,14 @@ class BudgetedKVCache:
 
     ``sm_scale``: the softmax scale (None: ``1 / sqrt(head_dim)``); ``logit_cap``: attention-logit soft-capping (None: off).  Both are
     the bank's (:class:`~easykv_amd.engine.KVBank`) and are kept as attributes: the HF seam holds the attention module's own
-    ``scaling`` / ``softcap`` against them."""
+    ``scaling`` / ``softcap`` against them.
+
+    ``sinks``: learned attention sinks ``[n_layers, n_q_heads]`` of the layers this cache owns (None: off; gpt-oss), the bank's likewise
+    and kept as an attribute (fp32, on the device): the seam holds the module's ``s_aux`` against the row of its layer."""
 
     def __init__(self, n_layers, n_q_heads, n_kv_heads, head_dim, cap, device, streaming=False, rope=None,
-                 record=False, layer_begin=0, layer_count=None, rope_base=10000.0, dtype=None, long_rows=False, logit_cap=None, sm_scale=None):
+                 record=False, layer_begin=0, layer_count=None, rope_base=10000.0, dtype=None, long_rows=False, logit_cap=None, sm_scale=None,
+                 sinks=None):
         self.layer_begin = layer_begin
         self.layer_count = n_layers - layer_begin if layer_count is None else layer_count
         if not (0 <= self.layer_begin and self.layer_count >= 1 and self.layer_begin + self.layer_count <= n_layers):
@@ -115,9 +119,13 @@ class BudgetedKVCache:
         # long_rows: the bank's steps go to the long-row call family (KVBank(long_rows=True): score rows of any width up to cap)
         if logit_cap is not None and streaming:
             raise ValueError("a soft-capped cache (logit_cap) has no RoPE-on-read build: streaming=True needs logit_cap=None")
+        if sinks is not None and streaming:
+            raise ValueError("a cache with attention sinks has no RoPE-on-read build: streaming=True needs sinks=None")
         self.logit_cap, self.sm_scale = logit_cap, sm_scale
-        extra = {k: v for k, v in (("logit_cap", logit_cap), ("sm_scale", sm_scale)) if v is not None}      # (opt-in: named only when set)
+        extra = {k: v for k, v in (("logit_cap", logit_cap), ("sm_scale", sm_scale), ("sinks", sinks)) if v is not None}      # (opt-in: named only when set)
         self.bank = KVBank(self.layer_count, n_q_heads, n_kv_heads, head_dim, cap, device=device, dtype=dtype, long_rows=long_rows, **extra)
+        self.sinks = self.bank.sinks      # (fp32 on the device, or None)
+        self._sinks_checked = set()       # layers whose module's s_aux the seam has held against the row (hf._easykv_attention)
         # no resident rows behind a model: its weights (gigabytes) stream through the Infinity Cache between two attention launches
         # of a layer, and plain loads that miss cost more than non-temporal ones ("resident rows": the harm run)
         self.bank.resident_bytes = 0
@@ -261,6 +269,7 @@ class BudgetedKVCacheBatch:
 
     streaming, unrotate = False, None      # (a batch has no RoPE-on-read form)
     logit_cap = None                        # (... and no soft-capped one; the softmax scale is the shared bank's)
+    sinks = None                            # (... and no sink one)
 
     def __init__(self, bat: KVBankBatch, record=False):
         self.bat = bat
@@ -335,6 +344,33 @@ def _dims(self):
     h = getattr(cfg, "num_key_value_heads", None) or hq
     d = getattr(cfg, "head_dim", None) or (cfg.hidden_size // hq)
     return n_layers, hq, h, d
+
+
+def _collect_sinks(model, cfg, n_layers, hq):
+    """The attention sinks of a model as one fp32 tensor ``[n_layers, n_q_heads]``, or None for a model without them.  Either
+    ``generation_config['attention_sinks']`` (anything ``torch.as_tensor`` takes, of that shape), or — what a stock gpt-oss has — every
+    module of the model that carries a ``sinks`` tensor of ``num_attention_heads`` elements and an integer ``layer_idx``: each layer must
+    then have exactly one."""
+    given = cfg.get("attention_sinks", None)
+    if given is not None:
+        t = torch.as_tensor(given).detach().float().cpu()
+        if tuple(t.shape) != (n_layers, hq):
+            raise ValueError(f"generation_config['attention_sinks'] must have shape [num_hidden_layers, num_attention_heads] = "
+                             f"[{n_layers}, {hq}], not {tuple(t.shape)}")
+        return t
+    modules = getattr(model, "modules", None)
+    rows = {}
+    for m in (modules() if callable(modules) else ()):
+        s, li = getattr(m, "sinks", None), getattr(m, "layer_idx", None)
+        if torch.is_tensor(s) and s.numel() == hq and isinstance(li, int) and not isinstance(li, bool):
+            if li in rows or not 0 <= li < n_layers:
+                raise ValueError(f"attention sinks: layer_idx {li} occurs twice among the model's modules or lies outside its {n_layers} layers")
+            rows[li] = s.detach().float().reshape(hq).cpu()
+    if not rows:
+        return None
+    if len(rows) != n_layers:
+        raise ValueError(f"attention sinks: {len(rows)} of the model's {n_layers} layers carry a `sinks` parameter; all or none must")
+    return torch.stack([rows[i] for i in range(n_layers)])
 
 
 def _kv_dtype(model, key):
@@ -439,6 +475,23 @@ class _Run:
                 raise ValueError(f"{what} with generation_config['long_rows'] = True: there is no capped long call")
             if d not in CAPPED_HEAD_DIMS:
                 raise ValueError(f"{what}: soft-capped logits are built for head_dim {' and '.join(map(str, CAPPED_HEAD_DIMS))} (this model: {d})")
+        # attention sinks (gpt-oss): one learned logit per layer and query head — generation_config['attention_sinks'] ([L, Hq]) or the
+        # model's own `sinks` parameters (_collect_sinks) — become the cache's sinks
+        self.sinks = _collect_sinks(model, cfg, n_layers, hq)
+        if self.sinks is not None:      # (before any bank exists)
+            what = "a model with attention sinks"
+            if streaming:
+                raise ValueError(f"{what} with streaming=True: RoPE-on-read has no sink build")
+            if kv_quant is not None:
+                raise ValueError(f"{what} with generation_config['kv_quant'] = {kv_quant!r}: there is no quantised sink decode step")
+            if self.long_rows:
+                raise ValueError(f"{what} with generation_config['long_rows'] = True: there is no long sink call")
+            if self.logit_cap is not None:
+                raise ValueError(f"{what} and attn_logit_softcapping = {self.logit_cap:g}: there is no capped sink call")
+            if shard is not None:
+                raise ValueError(f"{what} is not supported on a layer-sharded model (model.layer_shard)")
+            if d not in SINK_HEAD_DIMS:
+                raise ValueError(f"{what}: the sink kernels are built for head_dim {' and '.join(map(str, SINK_HEAD_DIMS))} (this model: {d})")
         self.dev = torch.device(model.device)
         for p in prompts:
             if p.dim() != 2 or p.shape[0] != 1:
@@ -492,7 +545,7 @@ class _Run:
         cache = BudgetedKVCache(n_layers, hq, h, d, cap + 8, self.dev, streaming=self.streaming, record=self.record, rope=hf_rope,
                                 layer_begin=self.layers[0], layer_count=self.layers[1], rope_base=self.rope_base, dtype=self.kv_dtype,
                                 **(dict(long_rows=True) if self.long_rows else {}),      # (opt-in: named only when asked for)
-                                **{k: v for k, v in (("logit_cap", self.logit_cap), ("sm_scale", self.sm_scale)) if v is not None})
+                                **{k: v for k, v in (("logit_cap", self.logit_cap), ("sm_scale", self.sm_scale), ("sinks", self.sinks)) if v is not None})
         cache.unrotate = hf_rope if self.hf_stream else None
         return cache
 
@@ -869,6 +922,8 @@ def generate_batch(self, input_ids_list, generation_config, kv_mode="encoding", 
         raise ValueError("generate_batch: generation_config['kv_quant'] = 'mxfp4' has no batched decode step (use 'fp8' or None)")
     if getattr(self.config, "attn_logit_softcapping", None) is not None:
         raise ValueError("generate_batch: a model with attn_logit_softcapping has no batched decode step (soft-capped logits serve single sequences)")
+    if _collect_sinks(self, cfg, *_dims(self)[:2]) is not None:
+        raise ValueError("generate_batch: a model with attention sinks has no batched decode step (the sink kernels serve single sequences)")
     prompts = [p.view(1, -1) if p.dim() == 1 else p for p in input_ids_list]
     if not 1 <= len(prompts) <= _lib.MAX_SEQS or any(p.dim() != 2 or p.shape[0] != 1 for p in prompts):
         raise ValueError(f"generate_batch takes 1..{_lib.MAX_SEQS} prompts of shape [S] or [1, S]")

@@ -95,6 +95,7 @@ static int call_attend(const EkvCall& c, const void* q, const void* k_new, const
   const bool bf16 = P.bf16 != 0;
   const EkvRows rows = static_cast<EkvRows>(P.rows);
   const bool capped = P.capped != 0;
+  const float* const sinks = P.sink ? c.sinks : nullptr;      // (a sink plan: every attention launch and the split path's scorer run the sink instances)
   drop_stale_error();
   for (int i = 0; i < P.n_list; ++i) {
     const EkvLaunch& L = P.list[i];
@@ -103,17 +104,23 @@ static int call_attend(const EkvCall& c, const void* q, const void* k_new, const
     // (a quantised plan is a decode plan: the decode attention launches and the scorers behind them, which read no K/V element)
     if (rows != EKV_ROWS_kv16 && (L.kind == EKV_RUN_CHUNK_LDS || L.kind == EKV_RUN_RESIDENT || L.kind == EKV_RUN_CHUNK || L.kind == EKV_RUN_FLUSH)) return EKV_E_UNSUPPORTED;
     // (a capped plan: the decode launches and the 16x16x32 chunk kernel, the only kernels with capped instances)
+    // (a sink plan likewise)
+    if (sinks && (L.kind == EKV_RUN_CHUNK_LDS || L.kind == EKV_RUN_RESIDENT || L.kind == EKV_RUN_FLUSH || (L.kind == EKV_RUN_CHUNK && P.wide))) return EKV_E_UNSUPPORTED;
     if (capped && (L.kind == EKV_RUN_CHUNK_LDS || L.kind == EKV_RUN_RESIDENT || L.kind == EKV_RUN_FLUSH || (L.kind == EKV_RUN_CHUNK && P.wide))) return EKV_E_UNSUPPORTED;
     switch (L.kind) {
       case EKV_RUN_FUSED_DECODE:
         aa.fused_order = P.fused_order;      // (shares its storage with score_tail, which only chunk launches set)
-        e = ekv_launch_decode_fused(aa, sa, tb, D, lc, P.fused_nw, s, bf16, rows, capped);
+        e = sinks ? ekv_launch_decode_fused_sink(aa, sa, sinks, D, lc, P.fused_nw, s, bf16)
+                  : ekv_launch_decode_fused(aa, sa, tb, D, lc, P.fused_nw, s, bf16, rows, capped);
         break;
       case EKV_RUN_CHUNK_LDS: e = ekv_launch_chunk_lds(aa, sa, D, lc, s, bf16); break;
       case EKV_RUN_RESIDENT: e = ekv_launch_attn_resident(aa, sa, lc, s, bf16); break;
-      case EKV_RUN_DECODE: e = ekv_launch_attn_decode(aa, tb, D, lc, s, bf16, rows, capped); break;
+      case EKV_RUN_DECODE:
+        e = sinks ? ekv_launch_attn_decode_sink(aa, sinks, D, lc, s, bf16) : ekv_launch_attn_decode(aa, tb, D, lc, s, bf16, rows, capped);
+        break;
       case EKV_RUN_CHUNK:
-        e = ekv_launch_attn_chunk(aa, D, lc, P.wide, P.two_pass, s, L.fuse ? &sa : nullptr, L.passes, L.tail ? &sa : nullptr, bf16, capped);
+        e = sinks ? ekv_launch_attn_chunk_sink(aa, sinks, D, lc, P.two_pass, s, L.fuse ? &sa : nullptr, bf16)
+                  : ekv_launch_attn_chunk(aa, D, lc, P.wide, P.two_pass, s, L.fuse ? &sa : nullptr, L.passes, L.tail ? &sa : nullptr, bf16, capped);
         break;
       case EKV_RUN_FLUSH: {
         EkvAttnArgs a2 = aa;
@@ -133,8 +140,8 @@ static int call_attend(const EkvCall& c, const void* q, const void* k_new, const
       case EKV_RUN_RANGE:
         e = ekv_launch_range_evict(bank, st, tb, evict_ids, s);
         break;
-      case EKV_RUN_DECODE_SCORE: e = ekv_launch_decode_score(sa, tb, lc, s, bf16); break;
-      case EKV_RUN_TOVA_MEAN: e = ekv_launch_tova_headmean(sa, lc, s); break;
+      case EKV_RUN_DECODE_SCORE: e = sinks ? ekv_launch_decode_score_sink(sa, sinks, lc, s, bf16) : ekv_launch_decode_score(sa, tb, lc, s, bf16); break;
+      case EKV_RUN_TOVA_MEAN: e = sinks ? ekv_launch_tova_headmean_sink(sa, sinks, lc, s) : ekv_launch_tova_headmean(sa, lc, s); break;
       case EKV_RUN_SCORE_SELECT: e = ekv_launch_score_select(sa, lc, s, bf16); break;
       // long calls (L.passes: the plain plan keeps its rows in scratch)
       case EKV_RUN_LONG_FOLD: e = ekv_launch_long_fold(sa, L.passes != 0, lc, s, bf16); break;
@@ -212,6 +219,20 @@ int ekv_softcap_eval(const float* x, int64_t n, float sm_div, float cap, float* 
   if (n < 0 || (n > 0 && (!x || !out)) || !(cap > 0.f && cap <= 3.0e38f) || !(sm_div > 0.f)) return EKV_E_ARG;
   drop_stale_error();
   return launch_code(ekv_launch_softcap_eval(x, n, sm_div, cap, out, static_cast<hipStream_t>(stream)));
+}
+
+// attention sinks (include/easykv_hip.h, "attention sinks"): the _typed calls with the sinks behind the element type
+int ekv_sink_step_check(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const float* sinks) { return call_check(sink_call(bank, st, dtype, sinks)); }
+int ekv_sink_step_info(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const float* sinks, int32_t* info, int32_t n_info) {
+  return call_info(sink_call(bank, st, dtype, sinks), info, n_info);
+}
+size_t ekv_sink_workspace_bytes(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const float* sinks) {
+  return call_workspace_bytes(sink_call(bank, st, dtype, sinks));
+}
+int ekv_sink_step_attend(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const float* sinks, const void* q, const void* k_new,
+                         const void* v_new, void* out, int32_t* evict_ids, const float* rope_cos, const float* rope_sin, void* workspace,
+                         size_t workspace_bytes, void* stream) {
+  return call_attend(sink_call(bank, st, dtype, sinks), q, k_new, v_new, out, evict_ids, rope_cos, rope_sin, workspace, workspace_bytes, stream);
 }
 
 // FP8 K/V storage (include/easykv_hip.h, "kv8")

@@ -10,6 +10,9 @@ typedef hipError_t EkvStepFn(const EkvAttnArgs&, const EkvScoreArgs&, int layer_
 #define EKV_CHUNK(d, m, elem) EkvChunkFn EKV_FN_CHUNK(d, m, elem);
 #define EKV_CHUNK_CAP(elem, d, m) EkvChunkFn EKV_FN_CHUNK_CAP(d, m, elem);
 #define EKV_WIDE(d, m, keys, elem) EkvChunkFn EKV_FN_WIDE(d, m, keys, elem);
+// (the sink instances of the 16x16 kernel: their launchers take the sinks behind the arguments)
+typedef hipError_t EkvSinkChunkFn(const EkvAttnArgs&, const float* sinks, int shape, int layer_count, hipStream_t, const EkvScoreArgs*);
+#define EKV_CHUNK_SINK(elem, d, m) EkvSinkChunkFn EKV_FN_CHUNK_SINK(d, m, elem);
 #define EKV_CHUNK_LDS(d, elem) EkvStepFn EKV_FN_D_ELEM(ekv_launch_chunk_lds, d, elem);
 #define EKV_RESIDENT(d, elem) EkvStepFn EKV_FN_D_ELEM(ekv_launch_attn_resident, d, elem);
 #include "ekv_instances.def"
@@ -25,6 +28,15 @@ const ChunkInstance kChunk[] = {
 #define EKV_CHUNK(d, m, elem) {false, d, m, false, EKV_IS_##elem, false, EKV_FN_CHUNK(d, m, elem)},
 #define EKV_CHUNK_CAP(elem, d, m) {false, d, m, false, EKV_IS_##elem, true, EKV_FN_CHUNK_CAP(d, m, elem)},
 #define EKV_WIDE(d, m, keys, elem) {true, d, m, EKV_IS_##keys, EKV_IS_##elem, false, EKV_FN_WIDE(d, m, keys, elem)},
+#include "ekv_instances.def"
+};
+struct SinkChunkInstance {
+  int head_dim, mode;
+  bool bf16;
+  EkvSinkChunkFn* fn;
+};
+const SinkChunkInstance kSinkChunk[] = {
+#define EKV_CHUNK_SINK(elem, d, m) {d, m, EKV_IS_##elem, EKV_FN_CHUNK_SINK(d, m, elem)},
 #include "ekv_instances.def"
 };
 struct StepInstance {      // whole-step kernels: logits in LDS, logits-resident
@@ -129,6 +141,24 @@ hipError_t ekv_launch_attn_chunk(const EkvAttnArgs& a, int head_dim, int layer_c
   auto go = [&](int m) {
     EkvChunkFn* const fn = chunk_instance(false, head_dim, m, false, bf16, capped);
     return fn ? fn(a, kernel_code(qpw, rope, m), layer_count, s, fuse_sc) : hipErrorInvalidValue;
+  };
+  hipError_t e = go(two_pass ? 1 : 0);
+  if (two_pass && e == hipSuccess) e = go(2);
+  return e;
+}
+
+// ---- attention sinks (the ekv_sink_* calls): the 16x16 kernel's sink instances, one pass (fuse_sc: with the scorer as its tail) or
+// statistics pass + exact pass.  Blocked as head_dim 256's at either head_dim: the one-tile build is the only sink one.
+hipError_t ekv_launch_attn_chunk_sink(const EkvAttnArgs& a, const float* sinks, int head_dim, int layer_count, bool two_pass, hipStream_t s,
+                                      const EkvScoreArgs* fuse_sc, bool bf16) {
+  if (sinks == nullptr || a.rope_cos != nullptr) return hipErrorInvalidValue;
+  if (two_pass && (fuse_sc != nullptr || a.stats == nullptr || a.colsum == nullptr)) return hipErrorInvalidValue;
+  int qb_rows, n_qblocks, qpw;
+  ekv_chunk_blocks(a.n_q_heads / a.n_kv_heads, a.q_len, &qb_rows, &n_qblocks, &qpw, kChunkNarrowD);
+  auto go = [&](int m) {
+    for (const SinkChunkInstance& in : kSinkChunk)
+      if (in.head_dim == head_dim && in.mode == m && in.bf16 == bf16) return in.fn(a, sinks, qpw, layer_count, s, fuse_sc);
+    return hipErrorInvalidValue;
   };
   hipError_t e = go(two_pass ? 1 : 0);
   if (two_pass && e == hipSuccess) e = go(2);

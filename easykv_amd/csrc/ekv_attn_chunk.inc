@@ -41,14 +41,27 @@
 #ifndef EKV_SOFTCAP
 #define EKV_SOFTCAP 0
 #endif
+// EKV_SINK = 1 (the EKV_CHUNK_SINK lines of the manifest): attention sinks (ekv_common.h).  The kernel takes the sinks as its last argument;
+// the wave that owns the first key half of the first split (split 0, wk 0: ONE of the 2 * n_split partials of a query row) starts the row's
+// running (m, l) at (a, 1) in lane group 0 instead of (-inf, 0), in the one pass and in the statistics pass alike, so partials, the
+// in-kernel fold, the row statistics, the statistics the exact pass folds and with them its probabilities and column sums all carry the
+// virtual key.  The exact pass, whose partials are sums of normalised probabilities, adds the virtual key's own probability to the same
+// lane's sum (its value is 0: the output gains nothing).  Plain keys, the one-tile build alone (as the capped instances), head_dim 64 / 128.
+#if EKV_SINK && EKV_SOFTCAP
+#error "sink chunk instances: uncapped logits"
+#endif
 #if EKV_BF16   // (bf16 instances: the same kernel under a tagged name)
 #if EKV_SOFTCAP
 #define ekv_attn_chunk_kernel ekv_attn_chunk_kernel_cap_bf16
+#elif EKV_SINK
+#define ekv_attn_chunk_kernel ekv_attn_chunk_kernel_sink_bf16
 #else
 #define ekv_attn_chunk_kernel ekv_attn_chunk_kernel_bf16
 #endif
 #elif EKV_SOFTCAP
 #define ekv_attn_chunk_kernel ekv_attn_chunk_kernel_cap
+#elif EKV_SINK
+#define ekv_attn_chunk_kernel ekv_attn_chunk_kernel_sink
 #endif
 
 #if EKV_CHUNK_MODE == 0
@@ -115,7 +128,7 @@ constexpr int kPadH = 16;  // LDS row padding in halfs (32 B): conflict-free ds_
 template <int QPW, bool ROPE, int NW, bool FUSE = false>
 // (the statistics pass has no output accumulators: <= 128 VGPRs, so two 8-wave workgroups per CU — two workgroups drift out of
 // phase and their VALU / LDS / MFMA phases overlap, which the lock-stepped waves of ONE workgroup never do)
-__global__ void __launch_bounds__(64 * NW, (NW == 16 || (NW == 8 && EKV_CHUNK_MODE != 1)) ? 1 : 2) ekv_attn_chunk_kernel(const EkvAttnArgs a, const EkvScoreArgs sc) {
+__global__ void __launch_bounds__(64 * NW, (NW == 16 || (NW == 8 && EKV_CHUNK_MODE != 1)) ? 1 : 2) ekv_attn_chunk_kernel(const EkvAttnArgs a, const EkvScoreArgs sc EKV_SINK_ONLY(, const float* const sinks)) {
   constexpr int D = EKV_D;
   constexpr int MODE = EKV_CHUNK_MODE;
   constexpr int NT = 64 * NW;               // threads
@@ -219,6 +232,26 @@ __global__ void __launch_bounds__(64 * NW, (NW == 16 || (NW == 8 && EKV_CHUNK_MO
       inv_l[t] = row_ok[t] ? 1.f / ls : 0.f;
     }
   }
+
+#if EKV_SINK
+  // attention sinks: the virtual key of this lane's query row, counted once per row — in lane group 0 of the wave that owns the first key
+  // half of the first split.  m_run is in the units of this launch's logits (raw accumulators unless need_div).  In raw units the seed is
+  // fl(a * sm_div), which the conversion at the end takes back to fl(fl(a * sm_div) / sm_div): where the sink is the row's maximum the
+  // exported M may differ from a by an ulp, while the exact pass forms the sink's own probability from a itself — a relative 1e-7 on that
+  // one term, not bit-for-bit agreement between the two passes on it (the real keys' terms do agree: both passes use the exported M).
+  if (split == 0 && wk == 0) {
+#pragma unroll
+    for (int t = 0; t < QPW; ++t) {
+      const float sink_a = sinks[(size_t)(a.layer_begin + ll) * a.n_q_heads + h * rep + row_r[t]];
+      if (MODE == 2) {      // (m_run = M and inv_l = 1 / L have the virtual key: the statistics pass seeded it)
+        if (row_ok[t] && g == 0) l_run[t] = exp2f((sink_a - m_run[t]) * EKV_LOG2E) * inv_l[t];
+      } else {
+        m_run[t] = need_div ? sink_a : sink_a * a.sm_div;
+        l_run[t] = g == 0 ? 1.f : 0.f;
+      }
+    }
+  }
+#endif
 
   // append: the (split, query block) that owns the new positions [t_new+i0, t_new+i0+nb) within its key range copies their
   // K/V rows into the cache slots.  Done here, not inside the tile loads: predicated stores in the load sequence made the
@@ -707,7 +740,7 @@ __global__ void __launch_bounds__(64 * NW, (NW == 16 || (NW == 8 && EKV_CHUNK_MO
 }
 
 template <int QPW, bool ROPE, int NW>
-hipError_t launch_k(const EkvAttnArgs& a, int layer_count, hipStream_t s, const EkvScoreArgs* fuse_sc) {
+hipError_t launch_k(const EkvAttnArgs& a, int layer_count, hipStream_t s, const EkvScoreArgs* fuse_sc EKV_SINK_ONLY(, const float* sinks)) {
   // slot entries | tiles | the query block; the 16-wave in-kernel fold exchanges NWQ x 64 x (D + 2) floats (ekv_geometry.h, where the planner reads it too)
   static_assert(kKT == kChunkKT && kPadH == kChunkPadH && EKV_Q_LDS(QPW, ROPE, NW) == ekv_chunk_q_in_lds(EKV_CHUNK_MODE, QPW, ROPE, NW),
                 "the LDS plan of ekv_geometry.h is this kernel's");
@@ -720,14 +753,14 @@ hipError_t launch_k(const EkvAttnArgs& a, int layer_count, hipStream_t s, const 
     if (lds > 48 * 1024)
       (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ekv_attn_chunk_kernel<QPW, ROPE, 4, true>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL((ekv_attn_chunk_kernel<QPW, ROPE, 4, true>), grid, dim3(256), lds, s, a, *fuse_sc);
+    hipLaunchKernelGGL((ekv_attn_chunk_kernel<QPW, ROPE, 4, true>), grid, dim3(256), lds, s, a, *fuse_sc EKV_SINK_ONLY(, sinks));
     return hipGetLastError();
   }
 #endif
   if (lds > 48 * 1024)
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ekv_attn_chunk_kernel<QPW, ROPE, NW>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL((ekv_attn_chunk_kernel<QPW, ROPE, NW>), grid, dim3(64 * NW), lds, s, a, EkvScoreArgs{});
+  hipLaunchKernelGGL((ekv_attn_chunk_kernel<QPW, ROPE, NW>), grid, dim3(64 * NW), lds, s, a, EkvScoreArgs{} EKV_SINK_ONLY(, sinks));
   return hipGetLastError();
 }
 
@@ -741,6 +774,14 @@ hipError_t EKV_FN_CHUNK_CAP(EKV_D, EKV_CHUNK_MODE, EKV_ELEM)(const EkvAttnArgs& 
   static_assert(EKV_D == 128 || EKV_D == kChunkNarrowD, "capped chunk instances: head_dim 128 and 256");
   if (a.rope_cos != nullptr || qpw != 1 || !(a.softcap > 0.f)) return hipErrorInvalidValue;
   return launch_k<1, false, 4>(a, layer_count, s, fuse_sc);
+}
+#elif EKV_SINK
+// the sink instances: plain keys, the one-tile build alone (the planner blocks their steps as head_dim 256's), head_dim 64 and 128
+hipError_t EKV_FN_CHUNK_SINK(EKV_D, EKV_CHUNK_MODE, EKV_ELEM)(const EkvAttnArgs& a, const float* sinks, int qpw, int layer_count, hipStream_t s,
+                                                              const EkvScoreArgs* fuse_sc) {
+  static_assert(EKV_D == 64 || EKV_D == 128, "sink chunk instances: head_dim 64 and 128");
+  if (a.rope_cos != nullptr || qpw != 1 || sinks == nullptr) return hipErrorInvalidValue;
+  return launch_k<1, false, 4>(a, layer_count, s, fuse_sc, sinks);
 }
 #else
 hipError_t EKV_FN_CHUNK(EKV_D, EKV_CHUNK_MODE, EKV_ELEM)(const EkvAttnArgs& a, int qpw, int layer_count, hipStream_t s,

@@ -77,6 +77,15 @@
 #if EKV_SOFTCAP && (EKV_ROPE || EKV_KV8 || EKV_KV4 || EKV_KV6 || EKV_KV84 || EKV_KV164 || EKV_BATCH)
 #error "soft-capped decode instances: 16-bit rows, plain keys, one sequence"
 #endif
+// EKV_SINK = 1 (the EKV_DECODE_SINK lines of the manifest: 16-bit rows, plain keys, one sequence, head_dim 64 / 128): attention sinks
+// (ekv_common.h).  Both kernels take the sinks as their last argument.  The stream folds the virtual key of every query head into the
+// online (m, l, o) of the lane group that scores the appended row, so the partials of the split kernel, both of its folds, the output of
+// the one-launch kernel and the maxima its tail takes from the wave partials have it; the tail adds exp(a - M) to the sum it rebuilds from
+// the logits (ekv_decode_tail.h).  The phase order K and the resident rows of the 16-bit flagship instances are compiled out, as for
+// kv164 (kResident, kOrders below: order K would replay the softmax from the logits in LDS, where the virtual key has no column).
+#if EKV_SINK && (EKV_ROPE || EKV_KV8 || EKV_KV4 || EKV_KV6 || EKV_KV84 || EKV_KV164 || EKV_BATCH || EKV_SOFTCAP)
+#error "sink decode instances: 16-bit rows, plain keys, one sequence, uncapped logits"
+#endif
 // Both switches at once (the batch kv8 instances) are independent: DESIGN.md §3.9, "Batches".
 #define ekv_attn_decode_kernel EKV_KERNEL_NAME(ekv_attn_decode_kernel)
 #define ekv_decode_fused_kernel EKV_KERNEL_NAME(ekv_decode_fused_kernel)
@@ -105,7 +114,7 @@ constexpr int kFMT = EKV_KV6 ? 6 : (EKV_KV84 ? 84 : (EKV_KV164 ? 164 : 0));     
 // SLOT_LDS = false: slot-map entries are fetched per iteration (needs 16-byte aligned map rows, cap % 4 == 0); saves the
 // staging pass and its barrier, which matters when a workgroup only streams one or two iterations.
 template <int D, int REP, bool ROPE, bool SLOT_LDS>
-__global__ void __launch_bounds__(256) ekv_attn_decode_kernel(const EkvAttnArgs EKV_ARG_A EKV_TB_PARAM) {
+__global__ void __launch_bounds__(256) ekv_attn_decode_kernel(const EkvAttnArgs EKV_ARG_A EKV_TB_PARAM EKV_SINK_ONLY(, const float* const sinks)) {
   EKV_SHADOW_A(blockIdx.z)
   using Gm = EkvDecodeGeom<D>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -136,7 +145,8 @@ __global__ void __launch_bounds__(256) ekv_attn_decode_kernel(const EkvAttnArgs 
   // (docs/TUNING.md §8, round 3) — so 8 stays.
   constexpr int KU = (!ROPE && !SLOT_LDS && REP <= 2) ? EKV_SPLIT_KU : (EKV_G8 || EKV_MX ? 4 : 8);
   ekv_decode_stream<D, REP, ROPE, SLOT_LDS, 4, false, KU, EkvNoop, kEPL, kFMT>(a, SLOT_LDS ? s_slot : a.slot_of_pos + head_row, logits, a.t_pad,
-                                                                               t0, t1, ll, h, head_row, m, l, o, nullptr, EkvNoop(), nrep, hq0);
+                                                                               t0, t1, ll, h, head_row, m, l, o, nullptr, EkvNoop(), nrep, hq0
+                                                                               EKV_SINK_ONLY(, 0, sinks + (size_t)(a.layer_begin + ll) * a.n_q_heads));
 
   ekv_decode_wave_combine<D, REP>(m, l, o);
   ekv_decode_stash<D, REP>(s_part, m, l, o);
@@ -201,7 +211,7 @@ __global__ void __launch_bounds__(256) ekv_attn_decode_kernel(const EkvAttnArgs 
 // fused kernel
 // ------------------------------------------------------------------------------------------------------
 template <int D, int REP, bool ROPE, int ITEMS, int NW, bool SLOT>
-__global__ void __launch_bounds__(64 * NW, (NW >= 8 ? (REP == 1 ? 2 : 1) : (SLOT && ITEMS > 12 ? 2 : (REP == 1 ? (EKV_MX ? 2 : 4) : (REP == 2 ? 3 : 2))))) ekv_decode_fused_kernel(const EkvAttnArgs EKV_ARG_A, const EkvScoreArgs EKV_ARG_SC EKV_TB_PARAM) {
+__global__ void __launch_bounds__(64 * NW, (NW >= 8 ? (REP == 1 ? 2 : 1) : (SLOT && ITEMS > 12 ? 2 : (REP == 1 ? (EKV_MX ? 2 : 4) : (REP == 2 ? 3 : 2))))) ekv_decode_fused_kernel(const EkvAttnArgs EKV_ARG_A, const EkvScoreArgs EKV_ARG_SC EKV_TB_PARAM EKV_SINK_ONLY(, const float* const sinks)) {
   EKV_SHADOW_A(blockIdx.z)
   EKV_SHADOW_SC(blockIdx.z)
   using Gm = EkvDecodeGeom<D, NW>;
@@ -227,7 +237,7 @@ __global__ void __launch_bounds__(64 * NW, (NW >= 8 ? (REP == 1 ? 2 : 1) : (SLOT
   const int l_pad = a.l_pad;   // pitch of a logits row: physical rows [0, E) (PHYS) or positions [0, T)
   // Resident rows (ekv_decode_stream.h, "load policy"): the 16-bit instances of the flagship geometry — head_dim 128, one query head
   // per KV head, slot-indexed score rows, both phase orders, 4 and 8 waves, every column count.  Every other instance keeps its code.
-  constexpr bool kResident = D == 128 && REP == 1 && PHYS && SLOT && !EKV_G8 && !EKV_MX && !EKV_KV164 && !EKV_BATCH;
+  constexpr bool kResident = D == 128 && REP == 1 && PHYS && SLOT && !EKV_G8 && !EKV_MX && !EKV_KV164 && !EKV_BATCH && !EKV_SINK;
   const int res_rows = kResident ? EKV_RESIDENT_ROWS(a.fused_order) : 0;
   // LDS: logits [REP][l_pad] | wave partials [4][REP][PS] | score rows S (Q C) [w_pad] | reduction scratch | dead-row bits
   float* s_logit = reinterpret_cast<float*>(smem);
@@ -250,7 +260,7 @@ __global__ void __launch_bounds__(64 * NW, (NW >= 8 ? (REP == 1 ? 2 : 1) : (SLOT
   // in LDS.  The tail is a latency-bound chain of block barriers that leaves HBM idle; when the workgroups of a CU are in different
   // orders, each order's tail falls under the other's stream.  Both orders produce the same bits (below), so WHICH workgroups take
   // order K may depend on where the hardware placed them.
-  constexpr bool kOrders = D == 128 && REP == 1 && !ROPE && NW == 4 && SLOT && ITEMS <= 12 && !EKV_G8 && !EKV_MX && !EKV_KV164 && !EKV_BATCH;
+  constexpr bool kOrders = D == 128 && REP == 1 && !ROPE && NW == 4 && SLOT && ITEMS <= 12 && !EKV_G8 && !EKV_MX && !EKV_KV164 && !EKV_BATCH && !EKV_SINK;
   bool order_k = false;
   if constexpr (kOrders) {
     const int om = a.fused_order & 3;
@@ -440,12 +450,13 @@ __global__ void __launch_bounds__(64 * NW, (NW >= 8 ? (REP == 1 ? 2 : 1) : (SLOT
   // without spills, GQA x 8 (per-row tables) 247
   constexpr int KUF = ROPE ? EKV_ROPE_KU(REP) : (EKV_KV164 && REP == 1 ? EKV_KV164_FUSED_KU1 : EKV_FUSED_KU);
   float m[REP], l[REP], o[REP][kEPL];
+  EKV_SINK_ONLY(const float* const sink_row = sinks + (size_t)(a.layer_begin + ll) * a.n_q_heads;)      // (the sinks of this bank layer)
   if (PHYS)
     ekv_decode_stream<D, REP, ROPE, false, NW, PHYS, KUF, decltype(mask_ready), kEPL, kFMT, kResident>(a, slot_row, s_logit, l_pad, 0, T, ll, h, head_row, m, l, o,
-                                                     reinterpret_cast<const uint8_t*>(s_deadw), mask_ready, nrep, h * nrep, res_rows);
+                                                     reinterpret_cast<const uint8_t*>(s_deadw), mask_ready, nrep, h * nrep, res_rows EKV_SINK_ONLY(, sink_row));
   else
     ekv_decode_stream<D, REP, ROPE, false, NW, false, KUF, EkvNoop, kEPL, kFMT>(a, slot_row, s_logit, l_pad, 0, T, ll, h, head_row, m, l, o, nullptr,
-                                                      EkvNoop(), nrep, h * nrep);
+                                                      EkvNoop(), nrep, h * nrep EKV_SINK_ONLY(, 0, sink_row));
   if (scored) ekv_tail_prefetch_ragged<NW>(sc, head_row, W, roco, sS, sQ, sC, !SLOT);   // published by the barrier below
   // SLOT: count base and birth of this thread's rows, straight into registers (consumed after the softmax passes of the tail)
   float cC[SLOT ? ITEMS : 1];
@@ -476,10 +487,11 @@ __global__ void __launch_bounds__(64 * NW, (NW >= 8 ? (REP == 1 ? 2 : 1) : (SLOT
   if constexpr (SLOT) {
     ekv_decode_tail_slot<REP, ITEMS, NW>(sc, ll, h, head_row, T, E, s_logit, l_pad, sS, sQ, cC, cB, red, s_hist,
                                          reinterpret_cast<unsigned long long*>(s_part), Gm::NP * REP * Gm::PS / 2, s_part, Gm::NP, Gm::PS,
-                                         s_deadw, slot_row[T - 1], g_old, c_new, nb, nrep);
+                                         s_deadw, slot_row[T - 1], g_old, c_new, nb, nrep EKV_SINK_ONLY(, sink_row + h * nrep));
   } else {
     ekv_decode_tail<REP, ITEMS, NW, PHYS>(sc, ll, h, head_row, T, off, W, s_logit, l_pad, sS, sQ, sC, red, s_hist,
-                                          reinterpret_cast<unsigned long long*>(s_part), Gm::NP * REP * Gm::PS / 2, s_part, Gm::NP, Gm::PS, nrep);
+                                          reinterpret_cast<unsigned long long*>(s_part), Gm::NP * REP * Gm::PS / 2, s_part, Gm::NP, Gm::PS, nrep
+                                          EKV_SINK_ONLY(, sink_row + h * nrep));
   }
   EKV_STAMP(5);
 #ifdef EKV_TAIL_PROFILE
@@ -491,19 +503,19 @@ __global__ void __launch_bounds__(64 * NW, (NW >= 8 ? (REP == 1 ? 2 : 1) : (SLOT
 }
 
 template <int REP>
-hipError_t launch(const EkvAttnArgs& a EKV_TB_DECL, int layer_count, hipStream_t s) {
+hipError_t launch(const EkvAttnArgs& a EKV_TB_DECL EKV_SINK_ONLY(, const float* sinks), int layer_count, hipStream_t s) {
   using Gm = EkvDecodeGeom<EKV_D>;
   const size_t part = (size_t)Gm::NP * REP * Gm::PS * 4;
   const int rep_all = a.n_q_heads / a.n_kv_heads;
   const dim3 grid(a.n_split * ((rep_all + REP - 1) / REP), a.n_kv_heads, layer_count);
   if ((a.cap & 3) == 0 && a.cap >= 16) {
-    hipLaunchKernelGGL((ekv_attn_decode_kernel<EKV_D, REP, EKV_ROPE, false>), grid, dim3(256), part, s, a EKV_TB_PASS);
+    hipLaunchKernelGGL((ekv_attn_decode_kernel<EKV_D, REP, EKV_ROPE, false>), grid, dim3(256), part, s, a EKV_TB_PASS EKV_SINK_ONLY(, sinks));
   } else {
     const size_t lds = ekv_align((size_t)a.rows_per_split * 4, 16) + part;
     if (lds > 48 * 1024)
       (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ekv_attn_decode_kernel<EKV_D, REP, EKV_ROPE, true>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL((ekv_attn_decode_kernel<EKV_D, REP, EKV_ROPE, true>), grid, dim3(256), lds, s, a EKV_TB_PASS);
+    hipLaunchKernelGGL((ekv_attn_decode_kernel<EKV_D, REP, EKV_ROPE, true>), grid, dim3(256), lds, s, a EKV_TB_PASS EKV_SINK_ONLY(, sinks));
   }
   return hipGetLastError();
 }
@@ -512,7 +524,7 @@ template <int REP, int NW = 8>
 size_t fused_lds(int t_pad, int l_pad, int n_state) { return ekv_fused_lds<EKV_D, REP, NW>(t_pad, l_pad, n_state); }
 
 template <int REP, int ITEMS, int NW, bool SLOT>
-hipError_t launch_fused_k(const EkvAttnArgs& a, const EkvScoreArgs& sc EKV_TB_DECL, int layer_count, hipStream_t s) {
+hipError_t launch_fused_k(const EkvAttnArgs& a, const EkvScoreArgs& sc EKV_TB_DECL EKV_SINK_ONLY(, const float* sinks), int layer_count, hipStream_t s) {
   // (slot-indexed rows: S / Q over the physical rows [0, E) in LDS, count base and birth in registers)
   const size_t lds = SLOT ? fused_lds<REP, NW>(a.phys_extent, a.l_pad, sc.policy == EKV_POLICY_ROCO ? 2 : 1)
                           : fused_lds<REP, NW>(a.t_pad, a.l_pad, sc.policy == EKV_POLICY_ROCO ? 3 : 1);
@@ -520,7 +532,7 @@ hipError_t launch_fused_k(const EkvAttnArgs& a, const EkvScoreArgs& sc EKV_TB_DE
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ekv_decode_fused_kernel<EKV_D, REP, EKV_ROPE, ITEMS, NW, SLOT>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   hipLaunchKernelGGL((ekv_decode_fused_kernel<EKV_D, REP, EKV_ROPE, ITEMS, NW, SLOT>), dim3(1, a.n_kv_heads, layer_count),
-                     dim3(64 * NW), lds, s, a, sc EKV_TB_PASS);
+                     dim3(64 * NW), lds, s, a, sc EKV_TB_PASS EKV_SINK_ONLY(, sinks));
   return hipGetLastError();
 }
 
@@ -529,27 +541,51 @@ hipError_t launch_fused_k(const EkvAttnArgs& a, const EkvScoreArgs& sc EKV_TB_DE
 //   NW = 8: for launches with only 1-2 heads per CU (GQA: Mistral's 8 KV heads x 32 layers = 256 heads): the same number
 //           of waves per CU streams one head, instead of leaving the CU to a single 4-wave workgroup.
 template <int REP, int NW>
-hipError_t launch_fused_nw(const EkvAttnArgs& a, const EkvScoreArgs& sc EKV_TB_DECL, int layer_count, hipStream_t s) {
+hipError_t launch_fused_nw(const EkvAttnArgs& a, const EkvScoreArgs& sc EKV_TB_DECL EKV_SINK_ONLY(, const float* sinks), int layer_count, hipStream_t s) {
   constexpr int NT = 64 * NW, I0 = (2304 + NT - 1) / NT, I1 = (6144 + NT - 1) / NT;
   if (sc.birth != nullptr) {      // slot-indexed rows: the thread-owned columns are the physical rows [0, E) (ekv_decode_slot_rows_supported)
     if constexpr (!EKV_ROPE && !EKV_BATCH && REP <= 4) {      // (a batch runs on the ordered layout)
-      if (a.phys_extent <= NT * I0) return launch_fused_k<REP, I0, NW, true>(a, sc EKV_TB_PASS, layer_count, s);
+      if (a.phys_extent <= NT * I0) return launch_fused_k<REP, I0, NW, true>(a, sc EKV_TB_PASS EKV_SINK_ONLY(, sinks), layer_count, s);
       // extents up to 6144 rows: 12 (8-wave) / 24 (4-wave) columns per thread in registers; the 4-wave build gives up the fourth
       // workgroup per CU for them (LDS would not have allowed it at these row counts anyway)
-      if (a.phys_extent <= NT * I1) return launch_fused_k<REP, I1, NW, true>(a, sc EKV_TB_PASS, layer_count, s);
+      if (a.phys_extent <= NT * I1) return launch_fused_k<REP, I1, NW, true>(a, sc EKV_TB_PASS EKV_SINK_ONLY(, sinks), layer_count, s);
     }
     return hipErrorInvalidValue;
   }
-  if (a.n_slots <= NT * I0) return launch_fused_k<REP, I0, NW, false>(a, sc EKV_TB_PASS, layer_count, s);
-  return launch_fused_k<REP, I1, NW, false>(a, sc EKV_TB_PASS, layer_count, s);
+  if (a.n_slots <= NT * I0) return launch_fused_k<REP, I0, NW, false>(a, sc EKV_TB_PASS EKV_SINK_ONLY(, sinks), layer_count, s);
+  return launch_fused_k<REP, I1, NW, false>(a, sc EKV_TB_PASS EKV_SINK_ONLY(, sinks), layer_count, s);
 }
 template <int REP>
-hipError_t launch_fused(const EkvAttnArgs& a, const EkvScoreArgs& sc EKV_TB_DECL, int layer_count, int nw, hipStream_t s) {
-  return nw == 8 ? launch_fused_nw<REP, 8>(a, sc EKV_TB_PASS, layer_count, s) : launch_fused_nw<REP, 4>(a, sc EKV_TB_PASS, layer_count, s);
+hipError_t launch_fused(const EkvAttnArgs& a, const EkvScoreArgs& sc EKV_TB_DECL EKV_SINK_ONLY(, const float* sinks), int layer_count, int nw, hipStream_t s) {
+  return nw == 8 ? launch_fused_nw<REP, 8>(a, sc EKV_TB_PASS EKV_SINK_ONLY(, sinks), layer_count, s) : launch_fused_nw<REP, 4>(a, sc EKV_TB_PASS EKV_SINK_ONLY(, sinks), layer_count, s);
 }
 
 }  // namespace
 
+#if EKV_SINK
+// the sink instances: their launchers take the sinks where the others take the table of a batch (EKV_FN_SINK: element type, head_dim)
+hipError_t EKV_FN_SINK(ekv_launch_attn_decode, EKV_ELEM, EKV_D)(const EkvAttnArgs& a, const float* sinks, int rep, int layer_count, hipStream_t s) {
+  if (rep < 1 || sinks == nullptr) return hipErrorInvalidValue;
+  switch (rep) {
+    case 1: return launch<1>(a, sinks, layer_count, s);
+    case 2: return launch<2>(a, sinks, layer_count, s);
+    case 3: case 4: return launch<4>(a, sinks, layer_count, s);
+    default: return launch<8>(a, sinks, layer_count, s);
+  }
+}
+
+hipError_t EKV_FN_SINK(ekv_launch_decode_fused, EKV_ELEM, EKV_D)(const EkvAttnArgs& a, const EkvScoreArgs& sc, const float* sinks, int rep,
+                                                                 int layer_count, int nw, hipStream_t s) {
+  if (sinks == nullptr) return hipErrorInvalidValue;
+  switch (rep) {
+    case 1: return launch_fused<1>(a, sc, sinks, layer_count, nw, s);
+    case 2: return launch_fused<2>(a, sc, sinks, layer_count, nw, s);
+    case 3: case 4: return launch_fused<4>(a, sc, sinks, layer_count, nw, s);
+    case 5: case 6: case 7: case 8: return launch_fused<8>(a, sc, sinks, layer_count, nw, s);
+    default: return hipErrorInvalidValue;
+  }
+}
+#else
 #if EKV_SOFTCAP
 #define EKV_KEYS cap      // (plain keys, soft-capped logits)
 #elif EKV_ROPE
@@ -586,3 +622,4 @@ hipError_t EKV_SYM(ekv_launch_decode_fused)(const EkvAttnArgs& a, const EkvScore
     default: return hipErrorInvalidValue;
   }
 }
+#endif

@@ -13,6 +13,14 @@ typedef hipError_t EkvFoldFn(const EkvScoreArgs&, int layer_count, hipStream_t);
 // (the soft-capped decode instances: plain keys, 16-bit rows, one sequence; their launchers carry `cap` where the others name their keys)
 #define EKV_DECODE_CAP(elem, d) EKV_DECODE(d, cap, elem, kv16, single)
 #define EKV_DECODE_SCORE(elem, batching) EkvScoreFn EKV_FN_DECODE_SCORE(ekv_launch_decode_score, elem, batching);
+// (the sink instances: 16-bit rows, plain keys, one sequence; their launchers take the sinks where the others take the table of a batch)
+typedef hipError_t EkvSinkDecodeFn(const EkvAttnArgs&, const float* sinks, int rep, int count, hipStream_t);
+typedef hipError_t EkvSinkFusedFn(const EkvAttnArgs&, const EkvScoreArgs&, const float* sinks, int rep, int count, int nw, hipStream_t);
+typedef hipError_t EkvSinkScoreFn(const EkvScoreArgs&, const float* sinks, int count, hipStream_t);
+#define EKV_DECODE_SINK(elem, d)                                   \
+  EkvSinkDecodeFn EKV_FN_SINK(ekv_launch_attn_decode, elem, d);    \
+  EkvSinkFusedFn EKV_FN_SINK(ekv_launch_decode_fused, elem, d);
+#define EKV_DECODE_SCORE_SINK(elem) EkvSinkScoreFn EKV_FN_ELEM(ekv_launch_decode_score_sink, elem);
 #include "ekv_instances.def"
 EkvFoldFn ekv_launch_fold_f16, ekv_launch_fold_bf16;      // (exported by the `single` scorer instances: the fold reads no per-step field)
 
@@ -32,6 +40,31 @@ const DecodeInstance kDecode[] = {
 #define EKV_DECODE_CAP(elem, d) EKV_DECODE(d, cap, elem, kv16, single)
 #include "ekv_instances.def"
 };
+struct SinkInstance {
+  int head_dim;
+  bool bf16;
+  EkvSinkDecodeFn* attn;
+  EkvSinkFusedFn* fused;
+};
+const SinkInstance kSinkDecode[] = {
+#define EKV_DECODE_SINK(elem, d) {d, EKV_IS_##elem, EKV_FN_SINK(ekv_launch_attn_decode, elem, d), EKV_FN_SINK(ekv_launch_decode_fused, elem, d)},
+#include "ekv_instances.def"
+};
+struct SinkScoreInstance {
+  bool bf16;
+  EkvSinkScoreFn* score;
+};
+const SinkScoreInstance kSinkScore[] = {
+#define EKV_DECODE_SCORE_SINK(elem) {EKV_IS_##elem, EKV_FN_ELEM(ekv_launch_decode_score_sink, elem)},
+#include "ekv_instances.def"
+};
+// A sink launch (ekv_sink_*): 16-bit rows, plain keys, one sequence — its own instances, never another's
+const SinkInstance* sink_instance(const EkvAttnArgs& a, const float* sinks, int head_dim, bool bf16) {
+  if (sinks == nullptr || a.rope_cos != nullptr) return nullptr;
+  for (const SinkInstance& in : kSinkDecode)
+    if (in.head_dim == head_dim && in.bf16 == bf16) return &in;
+  return nullptr;
+}
 struct ScoreInstance {
   bool bf16, batch;
   EkvScoreFn* score;
@@ -85,4 +118,22 @@ hipError_t ekv_launch_decode_score(const EkvScoreArgs& sc, const EkvSeqTable* tb
 
 hipError_t ekv_launch_fold(const EkvScoreArgs& sc, int layer_count, hipStream_t s, bool bf16) {
   return (bf16 ? ekv_launch_fold_bf16 : ekv_launch_fold_f16)(sc, layer_count, s);
+}
+
+// ---- attention sinks (the ekv_sink_* calls): the split kernel, the one-launch kernel and the split path's scorer
+hipError_t ekv_launch_attn_decode_sink(const EkvAttnArgs& a, const float* sinks, int head_dim, int count, hipStream_t s, bool bf16) {
+  const SinkInstance* in = sink_instance(a, sinks, head_dim, bf16);
+  return in ? in->attn(a, sinks, a.n_q_heads / a.n_kv_heads, count, s) : hipErrorInvalidValue;
+}
+
+hipError_t ekv_launch_decode_fused_sink(const EkvAttnArgs& a, const EkvScoreArgs& sc, const float* sinks, int head_dim, int count, int nw,
+                                        hipStream_t s, bool bf16) {
+  const SinkInstance* in = sink_instance(a, sinks, head_dim, bf16);
+  return in ? in->fused(a, sc, sinks, a.n_q_heads / a.n_kv_heads, count, nw, s) : hipErrorInvalidValue;
+}
+
+hipError_t ekv_launch_decode_score_sink(const EkvScoreArgs& sc, const float* sinks, int count, hipStream_t s, bool bf16) {
+  for (const SinkScoreInstance& in : kSinkScore)
+    if (in.bf16 == bf16) return in.score(sc, sinks, count, s);
+  return hipErrorInvalidValue;
 }

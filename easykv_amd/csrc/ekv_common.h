@@ -377,6 +377,34 @@ __device__ __forceinline__ float ekv_softcap(float x, float cap) {
 #define EKV_LOGIT(acc, a) ((acc) / (a).sm_div)
 #endif
 
+// ---- attention sinks (include/easykv_hip.h, "attention sinks"): one learned logit a per query head joins every softmax as a virtual key
+// with value 0 ------------------------------------------------------------------------------------------------------------------------
+// EKV_SINK = 1 (the EKV_*_SINK lines of the manifest) builds the kernels that take the sinks [n_layers][n_q_heads] (fp32, indexed by bank
+// layer) as their LAST kernel argument; EKV_SINK_ONLY(...) spells what exists only in those builds — a parameter, an argument — and
+// vanishes everywhere else, so every other instance keeps its tokens.  Every (m, l) that leaves a sink kernel carries the virtual key:
+// the decode stream folds it into the online state of the lane group that scores the appended row (ekv_sink_fold: once per query head),
+// the chunk kernel seeds the running (m, l) of the first key half of the first split with (a, 1).  Partials, folds, row statistics and
+// the statistics pass then have it, and only the places that rebuild the sum of exponentials from a logits row (the decode tails) add
+// exp(a - M) themselves.
+#ifndef EKV_SINK
+#define EKV_SINK 0
+#endif
+#if EKV_SINK
+#define EKV_SINK_ONLY(...) __VA_ARGS__
+#else
+#define EKV_SINK_ONLY(...)
+#endif
+// one more key, of logit a and value 0, for an online-softmax state (m may still be -inf; a is finite)
+template <int N>
+__device__ __forceinline__ void ekv_sink_fold(float a, float& m, float& l, float (&o)[N]) {
+  const float mn = fmaxf(m, a);
+  const float alpha = m == EKV_NEG_INF ? 0.f : exp2f((m - mn) * EKV_LOG2E);
+  l = l * alpha + exp2f((a - mn) * EKV_LOG2E);
+#pragma unroll
+  for (int i = 0; i < N; ++i) o[i] *= alpha;
+  m = mn;
+}
+
 // f32 -> one 16-bit output element, rounded to nearest even (bf16: v_cvt_pk_bf16_f32, NaN kept), as the __half the row pointers hold
 __device__ __forceinline__ __half ekv_to_e(float x) {
 #if EKV_BF16

@@ -12,6 +12,12 @@
 #ifndef EKV_BATCH
 #define EKV_BATCH 0
 #endif
+// EKV_SINK = 1 (the EKV_DECODE_SCORE_SINK lines of the manifest): the scorer behind the split decode kernel's sink instances.  The partials
+// it folds carry the virtual key already; the tail, which rebuilds the softmax of the exported logits, takes the sinks (ekv_decode_tail.h).
+// The fold kernel is the uniform one (it only folds partials), so these objects export the scorer alone.
+#if EKV_SINK && EKV_BATCH
+#error "sink scorer instances: one sequence"
+#endif
 #define ekv_decode_score_kernel EKV_KERNEL_NAME(ekv_decode_score_kernel)
 #define ekv_fold_kernel EKV_KERNEL_NAME(ekv_fold_kernel)
 
@@ -19,7 +25,7 @@ namespace {
 
 // (kSNW waves / kSNT threads per scorer workgroup and the LDS plan ekv_decode_score_lds: ekv_geometry.h)
 template <int REP, int ITEMS>
-__global__ void __launch_bounds__(kSNT) ekv_decode_score_kernel(const EkvScoreArgs EKV_ARG_SC EKV_TB_PARAM) {
+__global__ void __launch_bounds__(kSNT) ekv_decode_score_kernel(const EkvScoreArgs EKV_ARG_SC EKV_TB_PARAM EKV_SINK_ONLY(, const float* const sinks)) {
   EKV_SHADOW_SC(blockIdx.y)
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int h = blockIdx.x, ll = blockIdx.y, tid = threadIdx.x;
@@ -70,10 +76,11 @@ __global__ void __launch_bounds__(kSNT) ekv_decode_score_kernel(const EkvScoreAr
   EKV_STAMP(1);
   uint32_t* s_hist = reinterpret_cast<uint32_t*>(red.buf + 2 * kSNW * 8);     // roco select scratch: histogram, candidate list
   unsigned long long* s_list = reinterpret_cast<unsigned long long*>(s_hist + 264);
-  ekv_decode_tail<REP, ITEMS, kSNW>(sc, ll, h, head_row, T, off, W, s_logit, t_pad, sS, sQ, sC, red, s_hist, s_list, kSNT, nullptr, 0, 0, nrep);
+  ekv_decode_tail<REP, ITEMS, kSNW>(sc, ll, h, head_row, T, off, W, s_logit, t_pad, sS, sQ, sC, red, s_hist, s_list, kSNT, nullptr, 0, 0, nrep
+                                    EKV_SINK_ONLY(, sinks + (size_t)(sc.layer_begin + ll) * sc.n_q_heads + (size_t)h * nrep));
 }
 
-#if !EKV_BATCH
+#if !EKV_BATCH && !EKV_SINK
 // Partials of the key-range splits -> 16-bit attention output, nothing else (rows = q_len * n_q_heads per layer).
 __global__ void __launch_bounds__(128) ekv_fold_kernel(const EkvScoreArgs sc) {
   const int D = sc.head_dim, PS = D + 2;
@@ -87,46 +94,52 @@ __global__ void __launch_bounds__(128) ekv_fold_kernel(const EkvScoreArgs sc) {
 #endif
 
 template <int REP, int ITEMS>
-hipError_t launch_k(const EkvScoreArgs& sc EKV_TB_DECL, int layer_count, hipStream_t s) {
+hipError_t launch_k(const EkvScoreArgs& sc EKV_TB_DECL EKV_SINK_ONLY(, const float* sinks), int layer_count, hipStream_t s) {
   const size_t lds = ekv_decode_score_lds(REP, sc.t_pad, sc.policy);
   if (lds > 48 * 1024)
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ekv_decode_score_kernel<REP, ITEMS>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL((ekv_decode_score_kernel<REP, ITEMS>), dim3(sc.n_kv_heads, layer_count), dim3(kSNT), lds, s, sc EKV_TB_PASS);
+  hipLaunchKernelGGL((ekv_decode_score_kernel<REP, ITEMS>), dim3(sc.n_kv_heads, layer_count), dim3(kSNT), lds, s, sc EKV_TB_PASS EKV_SINK_ONLY(, sinks));
   return hipGetLastError();
 }
 
 template <int REP>
-hipError_t launch_rep(const EkvScoreArgs& sc EKV_TB_DECL, int layer_count, hipStream_t s) {
+hipError_t launch_rep(const EkvScoreArgs& sc EKV_TB_DECL EKV_SINK_ONLY(, const float* sinks), int layer_count, hipStream_t s) {
   // ITEMS = ceil(row width / threads) (a floor here sent T = 2049 to the 6144-wide build: 12 items per thread instead of 5)
   constexpr int I0 = (2304 + kSNT - 1) / kSNT, I1 = (6144 + kSNT - 1) / kSNT;
-  return sc.n_slots <= kSNT * I0 ? launch_k<REP, I0>(sc EKV_TB_PASS, layer_count, s) : launch_k<REP, I1>(sc EKV_TB_PASS, layer_count, s);
+  return sc.n_slots <= kSNT * I0 ? launch_k<REP, I0>(sc EKV_TB_PASS EKV_SINK_ONLY(, sinks), layer_count, s) : launch_k<REP, I1>(sc EKV_TB_PASS EKV_SINK_ONLY(, sinks), layer_count, s);
 }
 
-#if !EKV_BATCH
+#if !EKV_BATCH && !EKV_SINK
 hipError_t launch_fold(const EkvScoreArgs& sc, int layer_count, hipStream_t s) {
   hipLaunchKernelGGL(ekv_fold_kernel, dim3(sc.n_q_heads * sc.q_len, layer_count), dim3(128), 0, s, sc);
   return hipGetLastError();
 }
 #endif
 
-hipError_t launch_score(const EkvScoreArgs& sc EKV_TB_DECL, int layer_count, hipStream_t s) {
+hipError_t launch_score(const EkvScoreArgs& sc EKV_TB_DECL EKV_SINK_ONLY(, const float* sinks), int layer_count, hipStream_t s) {
   switch (sc.n_q_heads / sc.n_kv_heads) {
-    case 1: return launch_rep<1>(sc EKV_TB_PASS, layer_count, s);
-    case 2: return launch_rep<2>(sc EKV_TB_PASS, layer_count, s);
-    case 3: case 4: return launch_rep<4>(sc EKV_TB_PASS, layer_count, s);
-    case 5: case 6: case 7: case 8: return launch_rep<8>(sc EKV_TB_PASS, layer_count, s);
+    case 1: return launch_rep<1>(sc EKV_TB_PASS EKV_SINK_ONLY(, sinks), layer_count, s);
+    case 2: return launch_rep<2>(sc EKV_TB_PASS EKV_SINK_ONLY(, sinks), layer_count, s);
+    case 3: case 4: return launch_rep<4>(sc EKV_TB_PASS EKV_SINK_ONLY(, sinks), layer_count, s);
+    case 5: case 6: case 7: case 8: return launch_rep<8>(sc EKV_TB_PASS EKV_SINK_ONLY(, sinks), layer_count, s);
     default: return hipErrorInvalidValue;
   }
 }
 
 }  // namespace
 
+#if EKV_SINK
+hipError_t EKV_FN_ELEM(ekv_launch_decode_score_sink, EKV_ELEM)(const EkvScoreArgs& sc, const float* sinks, int count, hipStream_t s) {
+  return sinks != nullptr ? launch_score(sc, sinks, count, s) : hipErrorInvalidValue;
+}
+#else
 // tb: the table of a batched step for the batch instances, unused (NULL) otherwise
 hipError_t EKV_FN_DECODE_SCORE(ekv_launch_decode_score, EKV_ELEM, EKV_BATCHING)(const EkvScoreArgs& sc, const EkvSeqTable* tb, int count, hipStream_t s) {
   return launch_score(sc EKV_TB_DEREF, count, s);
 }
+#endif
 
-#if !EKV_BATCH
+#if !EKV_BATCH && !EKV_SINK
 hipError_t EKV_FN_ELEM(ekv_launch_fold, EKV_ELEM)(const EkvScoreArgs& sc, int layer_count, hipStream_t s) { return launch_fold(sc, layer_count, s); }
 #endif

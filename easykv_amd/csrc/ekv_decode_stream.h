@@ -93,7 +93,8 @@ __device__ __forceinline__ void ekv_decode_stream(const EkvAttnArgs& a, const in
                                                   int logit_stride, int t0, int t1_in, int ll, int h, size_t head_row,
                                                   float (&m)[REP], float (&l)[REP], float (&o)[REP][EPL],
                                                   const uint8_t* s_dead = nullptr, MaskReady mask_ready = MaskReady(),
-                                                  int n_rep_real = 0, int q_head0 = -1, int res_rows = 0) {
+                                                  int n_rep_real = 0, int q_head0 = -1, int res_rows = 0
+                                                  EKV_SINK_ONLY(, const float* sink_row = nullptr)) {      // (the sinks of this bank layer's query heads)
   static_assert(!RES || (PHYS && EPL == 8 && D == 128), "resident rows: 16-bit rows of head_dim 128 (whole lane groups) in physical order");
   using Gm = EkvDecodeGeom<D, NW, KU, EPL>;
   constexpr int LPR = Gm::LPR, RW = Gm::RW, LIVE = Gm::LIVE;
@@ -365,6 +366,11 @@ __device__ __forceinline__ void ekv_decode_stream(const EkvAttnArgs& a, const in
       else if constexpr (KV164) ekv_axpy8_fp4(p, vsn, vn.x, o[r]);
       else ekv_axpy8(p, vn, o[r]);
       m[r] = mn;
+#if EKV_SINK
+      // the sink of query head r: a virtual key with value 0, counted here and nowhere else in the launch — this lane group of the one
+      // workgroup whose key range holds the appended row
+      ekv_sink_fold(sink_row[hq0 + min(r, nrep - 1)], m[r], l[r], o[r]);
+#endif
     }
   };
   if (!PHYS && t1 <= t0) {   // the split held only the appended row

@@ -133,7 +133,8 @@ template <int REP, int ITEMS, int NW = 4, bool PHYS = false>
 __device__ __forceinline__ void ekv_decode_tail(const EkvScoreArgs& sc, int ll, int h, size_t head_row, int T, int off, int W,
                                                 float* s_logit, int t_pad, float* sS, float* sQ, float* sC, RedN<NW>& red,
                                                 uint32_t* s_hist, unsigned long long* s_list, int list_cap,
-                                                const float* part_max = nullptr, int n_part = 0, int part_stride = 0, int nrep_in = 0) {
+                                                const float* part_max = nullptr, int n_part = 0, int part_stride = 0, int nrep_in = 0
+                                                EKV_SINK_ONLY(, const float* sink_h = nullptr)) {      // (the sinks of this KV head's query heads)
   const int tid = threadIdx.x;
   constexpr int NT = 64 * NW;
   // GQA factors 3 / 5 / 6 / 7 run the REP = 4 / 8 build: the logit rows r >= nrep are copies of the last real head and stay out of
@@ -195,6 +196,16 @@ __device__ __forceinline__ void ekv_decode_tail(const EkvScoreArgs& sc, int ll, 
       }
       red.template max_n<REP>(mx);
     }
+#if EKV_SINK
+    // attention sinks: M = max(the row's maximum, a) — the stream's partials already have it, a maximum taken from the logits does not —
+    // and the sum of exponentials below gains the virtual key's exp(a - M) (<= 1); it has no column, no score and is never a victim
+    float sink_a[REP];
+#pragma unroll
+    for (int r = 0; r < REP; ++r) {
+      sink_a[r] = sink_h[min(r, nrep - 1)];
+      mx[r] = fmaxf(mx[r], sink_a[r]);
+    }
+#endif
     if (PHYS) {
 #pragma unroll
       for (int it = 0; it < ITEMS; ++it) {
@@ -219,6 +230,10 @@ __device__ __forceinline__ void ekv_decode_tail(const EkvScoreArgs& sc, int ll, 
       }
     }
     red.template sum_n<REP>(sm);
+#if EKV_SINK
+#pragma unroll
+    for (int r = 0; r < REP; ++r) sm[r] += expf(sink_a[r] - mx[r]);
+#endif
     float inv_sm[REP];     // p = e * (1 / sum): see ekv_score_select.inc on why not a division per element
 #pragma unroll
     for (int r = 0; r < REP; ++r) inv_sm[r] = 1.f / sm[r];
@@ -509,7 +524,7 @@ __device__ __forceinline__ void ekv_decode_tail_slot(const EkvScoreArgs& sc, int
                                                      const int32_t (&cB)[ITEMS], RedN<NW>& red, uint32_t* s_hist,
                                                      unsigned long long* s_list, int list_cap, const float* part_max, int n_part,
                                                      int part_stride, const uint32_t* s_deadw, int new_row, float g_old, float c_new,
-                                                     int nb, int nrep_in = 0) {
+                                                     int nb, int nrep_in = 0 EKV_SINK_ONLY(, const float* sink_h = nullptr)) {
   const int tid = threadIdx.x;
   constexpr int NT = 64 * NW;
   const int nrep = (REP == 1 || REP == 2 || nrep_in <= 0) ? REP : nrep_in;      // (GQA factor 3 on the REP = 4 build: see ekv_decode_tail)
@@ -538,6 +553,14 @@ __device__ __forceinline__ void ekv_decode_tail_slot(const EkvScoreArgs& sc, int
 #pragma unroll
     for (int r = 0; r < REP; ++r)
       for (int i = 0; i < n_part; ++i) mx[r] = fmaxf(mx[r], part_max[(size_t)(i * REP + r) * part_stride]);
+#if EKV_SINK
+    float sink_a[REP];      // attention sinks, as in ekv_decode_tail: M includes a (the partials' maxima have it), the sum gains exp(a - M)
+#pragma unroll
+    for (int r = 0; r < REP; ++r) {
+      sink_a[r] = sink_h[min(r, nrep - 1)];
+      mx[r] = fmaxf(mx[r], sink_a[r]);
+    }
+#endif
 #pragma unroll
     for (int it = 0; it < ITEMS; ++it) {
       const int j = tid + it * NT;
@@ -553,6 +576,10 @@ __device__ __forceinline__ void ekv_decode_tail_slot(const EkvScoreArgs& sc, int
       }
     }
     red.template sum_n<REP>(sm);
+#if EKV_SINK
+#pragma unroll
+    for (int r = 0; r < REP; ++r) sm[r] += expf(sink_a[r] - mx[r]);
+#endif
     float inv_sm[REP];
 #pragma unroll
     for (int r = 0; r < REP; ++r) inv_sm[r] = 1.f / sm[r];

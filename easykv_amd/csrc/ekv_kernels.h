@@ -75,6 +75,7 @@ struct EkvStepPlan {
   int32_t long_rows, long_tiles;
   int64_t key_rows;
   int32_t capped;       // an ekv_cap_* call: the launches run the EKV_SOFTCAP instances (chunk steps: the one-tile 16x16x32 build alone)
+  int32_t sink;         // an ekv_sink_* call: the launches run the EKV_SINK instances (chunk steps likewise; decode steps in phase order F, no resident rows)
 };
 // The table of a batched decode step as the kernels' batch instances receive it: BY VALUE, behind the argument structs of the uniform
 // kernel (2304 bytes of the 4 KB a launch may carry).  Workgroup (head, entry ll) shadows the per-step fields of its argument structs
@@ -200,6 +201,16 @@ hipError_t ekv_launch_tova_headmean(const EkvScoreArgs& a, int layer_count, hipS
 hipError_t ekv_launch_score_select(const EkvScoreArgs& a, int layer_count, hipStream_t s, bool bf16);
 hipError_t ekv_launch_decode_fused(const EkvAttnArgs& a, const EkvScoreArgs& sc, const EkvSeqTable* tb, int head_dim, int count, int nw,
                                    hipStream_t s, bool bf16, EkvRows rows, bool capped = false);
+// Attention sinks (the ekv_sink_* calls; EKV_SINK instances, ekv_common.h): the launchers of a sink step.  sinks: device fp32
+// [bank->n_layers][n_q_heads], indexed by bank layer.  16-bit rows, plain keys, one sequence; head_dim 64 / 128.  The chunk launcher runs
+// the 16x16x32 kernel in its one-tile build (pass: 0 one pass, 1 statistics pass, 2 exact pass; fuse_sc: the scorer as the one pass's tail).
+hipError_t ekv_launch_attn_decode_sink(const EkvAttnArgs& a, const float* sinks, int head_dim, int count, hipStream_t s, bool bf16);
+hipError_t ekv_launch_decode_fused_sink(const EkvAttnArgs& a, const EkvScoreArgs& sc, const float* sinks, int head_dim, int count, int nw,
+                                        hipStream_t s, bool bf16);
+hipError_t ekv_launch_decode_score_sink(const EkvScoreArgs& sc, const float* sinks, int count, hipStream_t s, bool bf16);
+hipError_t ekv_launch_tova_headmean_sink(const EkvScoreArgs& a, const float* sinks, int layer_count, hipStream_t s);      // (ekv_score_select.inc, EKV_SINK build)
+hipError_t ekv_launch_attn_chunk_sink(const EkvAttnArgs& a, const float* sinks, int head_dim, int layer_count, bool two_pass, hipStream_t s,
+                                      const EkvScoreArgs* fuse_sc, bool bf16);
 // ekv_softcap_eval: out[i] = ekv_softcap(x[i] / sm_div, cap) (ekv_attn_decode_dispatch.hip)
 hipError_t ekv_launch_softcap_eval(const float* x, int64_t n, float sm_div, float cap, float* out, hipStream_t s);
 // Long-row scorer (ekv_score_long.inc; one build for fp16 and bf16 banks).  a.big_rows and key_rows ([layer_count][H][a.big_stride]
@@ -285,12 +296,19 @@ __device__ __forceinline__ EkvScoreArgs ekv_batch_score_args(const EkvScoreArgs&
 #define EKV_CAP_TAG
 #endif
 
+// attention sinks (EKV_SINK = 1: the EKV_*_SINK lines of the manifest; ekv_common.h)
+#if defined(EKV_SINK) && EKV_SINK
+#define EKV_SINK_TAG _sink
+#else
+#define EKV_SINK_TAG
+#endif
+
 // ---- kernel instances (ekv_instances.def; DESIGN.md "kernel instances")
-// Kernel symbol of an instance = the kernel's name + independent tags that default to empty: _batch, _kv8, _cap, _bf16 (ekv_common.h).  A
+// Kernel symbol of an instance = the kernel's name + independent tags that default to empty: _batch, _kv8, _cap, _sink, _bf16 (ekv_common.h).  A
 // kernel source renames itself with  #define ekv_x_kernel EKV_KERNEL_NAME(ekv_x_kernel)  (profiles and traces know these names).
-#define EKV_KERNEL_NAME_(base, b, r, c, t) base##b##r##c##t
-#define EKV_KERNEL_NAME_X(base, b, r, c, t) EKV_KERNEL_NAME_(base, b, r, c, t)
-#define EKV_KERNEL_NAME(base) EKV_KERNEL_NAME_X(base, EKV_BATCH_TAG, EKV_ROWS_TAG, EKV_CAP_TAG, EKV_DT_TAG)
+#define EKV_KERNEL_NAME_(base, b, r, c, k, t) base##b##r##c##k##t
+#define EKV_KERNEL_NAME_X(base, b, r, c, k, t) EKV_KERNEL_NAME_(base, b, r, c, k, t)
+#define EKV_KERNEL_NAME(base) EKV_KERNEL_NAME_X(base, EKV_BATCH_TAG, EKV_ROWS_TAG, EKV_CAP_TAG, EKV_SINK_TAG, EKV_DT_TAG)
 // Launcher of an instance = the family's entry + every word of its manifest line, in the line's order.  The instance (which pastes
 // its own switches: EKV_D, EKV_KEYS, EKV_ELEM, EKV_ROWS, EKV_BATCHING, ...) and the dispatch tables (which paste the manifest's words)
 // both spell it through these macros.
@@ -304,6 +322,10 @@ __device__ __forceinline__ EkvScoreArgs ekv_batch_score_args(const EkvScoreArgs&
 #define EKV_FN_CHUNK(d, m, elem) EKV_FN_CHUNK_(d, m, elem)
 #define EKV_FN_CHUNK_CAP_(d, m, elem) ekv_launch_attn_chunk_cap_d##d##_m##m##_##elem
 #define EKV_FN_CHUNK_CAP(d, m, elem) EKV_FN_CHUNK_CAP_(d, m, elem)
+#define EKV_FN_SINK_(fn, elem, d) fn##_sink_d##d##_##elem
+#define EKV_FN_SINK(fn, elem, d) EKV_FN_SINK_(fn, elem, d)      // (EKV_DECODE_SINK; EKV_DECODE_SCORE_SINK names no head_dim)
+#define EKV_FN_CHUNK_SINK_(d, m, elem) ekv_launch_attn_chunk_sink_d##d##_m##m##_##elem
+#define EKV_FN_CHUNK_SINK(d, m, elem) EKV_FN_CHUNK_SINK_(d, m, elem)
 #define EKV_FN_WIDE_(d, m, keys, elem) ekv_launch_attn_wide_d##d##_m##m##_##keys##_##elem
 #define EKV_FN_WIDE(d, m, keys, elem) EKV_FN_WIDE_(d, m, keys, elem)
 #define EKV_FN_D_ELEM_(fn, d, elem) fn##_d##d##_##elem

@@ -806,14 +806,26 @@ int resolve_call(const EkvCall& c, EkvResolved* r) {
   // logits-resident kernel.  Refused with zero launches and zero bytes: RoPE-on-read, head_dim 32 / 64 / 96, a chunk step whose GQA
   // factor exceeds a block (EKV_E_UNSUPPORTED).
   if (c.capped && !(c.softcap > 0.f && c.softcap <= 3.0e38f)) return EKV_E_ARG;
-  const int rc = ((c.long_rows || c.capped) && (quant || c.batch || (c.long_rows && c.capped)))
+  // Sink calls (ekv_sink_*), likewise stated once.  "Sink" is one more independent variant of a call; its entry points spell 16-bit rows,
+  // one sequence and uncapped logits only, and no other combination has an instance.  NULL sinks are an argument error, behind the element
+  // type and before anything is planned; the pointer is never dereferenced here.  A decode step plans as the plain call of the same (bank,
+  // step, dtype) — splits, launches, workspace — and runs the sink decode instances, in which the phase order K and the resident rows are
+  // compiled out (as in the kv164 ones): the plan says order F and no resident rows (info [9] = 0, ekv_step_resident_rows' rule gives 0).
+  // A chunk step or dense prefix plans by the capped call's rule: the 16x16x32 kernel alone, one-tile build, blocks of at most 32 folded
+  // rows, one pass (the scorer as its tail where the step is one unsplit block) or statistics + exact pass + generic scorer.  Refused with
+  // zero launches and zero bytes (EKV_E_UNSUPPORTED): RoPE-on-read, a head_dim other than 64 / 128, a chunk step whose GQA factor
+  // exceeds a block.  The head-mean TOVA row (tova_head_mean) runs the sink build of its kernel.
+  if (c.sink && c.sinks == nullptr) return EKV_E_ARG;
+  const int variants = (c.long_rows ? 1 : 0) + (c.capped ? 1 : 0) + (c.sink ? 1 : 0);
+  const int rc = (variants && (quant || c.batch || variants > 1))
                      ? EKV_E_UNSUPPORTED
-                     : ekv_plan_step(bank, r->step, P, c.long_rows, c.capped);
+                     : ekv_plan_step(bank, r->step, P, c.long_rows, c.capped || c.sink);
   P->capped = c.capped ? 1 : 0;
+  P->sink = c.sink ? 1 : 0;
   P->bf16 = c.dtype == EKV_DTYPE_BF16;
   P->rows = c.rows;
   P->batch = c.batch;
-  if (quant || c.batch) P->fused_order = 0;      // (the quantised and the batch instances keep order F)
+  if (quant || c.batch || c.sink) P->fused_order = 0;      // (the quantised, the batch and the sink instances keep order F, without resident rows)
   auto refuse = [&](int code) {
     if (P->long_rows) {      // (a long plan that is refused after all reports the layout of the plain call: nothing of the long scorer remains)
       EkvStepPlan plain;
@@ -821,7 +833,7 @@ int resolve_call(const EkvCall& c, EkvResolved* r) {
       P->bytes = plain.bytes, P->big_rows = plain.big_rows, P->key_rows = -1;
     }
     P->one_launch = P->n_launches = P->n_list = P->long_rows = P->long_tiles = 0;
-    if (c.batch || c.capped) P->bytes = 0;      // (nothing will run: ekv_batch_workspace_bytes of a refused table, ekv_cap_workspace_bytes of a refused step, is 0)
+    if (c.batch || c.capped || c.sink) P->bytes = 0;      // (nothing will run: ekv_batch_workspace_bytes of a refused table, ekv_cap_ / ekv_sink_workspace_bytes of a refused step, is 0)
     return code;
   };
   const ekv_step* st = c.step;
@@ -833,6 +845,7 @@ int resolve_call(const EkvCall& c, EkvResolved* r) {
   if (rc == EKV_OK && P->bf16 && st->rope_on_read) return refuse(EKV_E_UNSUPPORTED);
   if (rc != EKV_OK) return refuse(rc);
   if (c.capped && (st->rope_on_read || (bank->head_dim != 128 && bank->head_dim != kChunkNarrowD))) return refuse(EKV_E_UNSUPPORTED);
+  if (c.sink && (st->rope_on_read || (bank->head_dim != 64 && bank->head_dim != 128))) return refuse(EKV_E_UNSUPPORTED);
   if (quant && (st->q_len != 1 || st->rope_on_read || !ekv_rows_head_dim(c.rows, bank->head_dim) ||
                 bank->n_q_heads / bank->n_kv_heads > kRowsRules[c.rows].max_rep))
     return refuse(EKV_E_UNSUPPORTED);
@@ -873,6 +886,7 @@ int call_info(const EkvCall& c, int32_t* info, int32_t n_info) {
   const bool ok = resolve_call(c, &r) == EKV_OK;
   if (c.dtype != EKV_DTYPE_F16 && c.dtype != EKV_DTYPE_BF16) return EKV_E_ARG;
   if (c.capped && !(c.softcap > 0.f && c.softcap <= 3.0e38f)) return EKV_E_ARG;      // (a cap no step can be planned with)
+  if (c.sink && c.sinks == nullptr) return EKV_E_ARG;
   if (c.rows != EKV_ROWS_kv16 && !r.bank) return EKV_E_ARG;
   if (int e = check_bank(r.bank)) return e;
   if (!c.step || (c.batch && !c.seqs) || !info || n_info < 1) return EKV_E_ARG;

@@ -44,7 +44,8 @@ int ekv_attn_chunk_launches(bool wide, bool rope, bool two_pass, int passes);
 // The scalar (shape) fields of the scorer's arguments; call_attend adds the pointers.
 EkvScoreArgs score_args(const ekv_bank* bank, const ekv_step* st, const EkvStepPlan& P);
 // long_rows: the plan of a long call (ekv_long_*; the rule is stated once, at ekv_plan_step in ekv_plan.cpp)
-// capped: the plan of a capped call (ekv_cap_*; the rule is stated once, at resolve_call in ekv_plan.cpp)
+// capped: the plan of a capped call (ekv_cap_*; the rule is stated once, at resolve_call in ekv_plan.cpp); a sink call (ekv_sink_*) tiles
+// its chunk steps by the same rule and passes true as well
 int ekv_plan_step(const ekv_bank* bank, const ekv_step* step, EkvStepPlan* P, bool long_rows = false, bool capped = false);
 
 // ---- one call path --------------------------------------------------------------------------------------------------------------
@@ -75,6 +76,8 @@ struct EkvCall {
   bool long_rows;          // an ekv_long_* call: the long-row scorer where the plan would end in the generic one (16-bit rows, one sequence)
   bool capped;             // an ekv_cap_* call: soft-capped logits (16-bit rows, one sequence, plain keys, head_dim 128 / 256)
   float softcap;           // ... its cap: finite and > 0, or the call is an argument error
+  bool sink;               // an ekv_sink_* call: attention sinks (16-bit rows, one sequence, plain keys, head_dim 64 / 128)
+  const float* sinks;      // ... the sinks, device fp32 [bank->n_layers][n_q_heads]: only tested for NULL here (an argument error)
 };
 inline EkvCall step_call(const ekv_bank* bank, const ekv_step* st, int32_t dtype) { return {bank, st, dtype, EKV_ROWS_kv16, {}, false, nullptr, 0}; }
 inline EkvCall batch_call(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_seq* seqs, int32_t n_seq) {
@@ -83,6 +86,9 @@ inline EkvCall batch_call(const ekv_bank* bank, const ekv_step* st, int32_t dtyp
 inline EkvCall long_call(const ekv_bank* bank, const ekv_step* st, int32_t dtype) { return {bank, st, dtype, EKV_ROWS_kv16, {}, false, nullptr, 0, true}; }
 inline EkvCall cap_call(const ekv_bank* bank, const ekv_step* st, int32_t dtype, float softcap) {
   return {bank, st, dtype, EKV_ROWS_kv16, {}, false, nullptr, 0, false, true, softcap};
+}
+inline EkvCall sink_call(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const float* sinks) {
+  return {bank, st, dtype, EKV_ROWS_kv16, {}, false, nullptr, 0, false, false, 0.f, true, sinks};
 }
 // the quantised calls: the same two with a row format and its planes
 inline EkvCall kv8_call(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_kv8* q8) {

@@ -457,15 +457,23 @@ __device__ void ekv_score_select_body(const EkvScoreArgs& a, const int h, const 
 #if EKV_BF16   // (bf16 instances: the scorer under a tagged name; the head-mean row writes no 16-bit data and is built once)
 #define ekv_score_select_kernel ekv_score_select_kernel_bf16
 #endif
+// EKV_SINK = 1 (the EKV_TOVA_MEAN_SINK line of the manifest): the head-mean TOVA row of a sink call (ekv_common.h, "attention sinks"), the
+// one kernel of this file that rebuilds a softmax from exported logits alone: M = max(row maximum, a) and the sum gains exp(a - M).  The
+// object holds that kernel only — the scorer itself takes (M, 1 / L) of every row from partials or row statistics that carry the sink.
+#if EKV_SINK
+#define ekv_tova_headmean_kernel ekv_tova_headmean_kernel_sink
+#else
 template <bool BIG>
 __global__ void __launch_bounds__(kNT) ekv_score_select_kernel(const EkvScoreArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   ekv_score_select_body<BIG>(a, blockIdx.x, blockIdx.y, smem);
 }
 
+#endif  // !EKV_SINK
+
 #if !EKV_BF16
 // 'tova' in encoding/ppl mode: one last-query row averaged over ALL kv heads (easykv/easykv.py:456, :847)
-__global__ void __launch_bounds__(kNT) ekv_tova_headmean_kernel(const EkvScoreArgs a) {
+__global__ void __launch_bounds__(kNT) ekv_tova_headmean_kernel(const EkvScoreArgs a EKV_SINK_ONLY(, const float* const sinks)) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int ll = blockIdx.x;
   const int T = a.n_slots, n = a.q_len, H = a.n_kv_heads;
@@ -478,9 +486,16 @@ __global__ void __launch_bounds__(kNT) ekv_tova_headmean_kernel(const EkvScoreAr
     float mx = EKV_NEG_INF;
     for (int j = lane; j < T; j += 64) mx = fmaxf(mx, lg[j]);
     mx = ekv_wave_max(mx);
+#if EKV_SINK
+    const float sink_a = sinks[(size_t)(a.layer_begin + ll) * a.n_q_heads + hr];
+    mx = fmaxf(mx, sink_a);
+#endif
     float sm = 0.f;
     for (int j = lane; j < T; j += 64) sm += expf(lg[j] - mx);
     sm = ekv_wave_sum(sm);
+#if EKV_SINK
+    sm += expf(sink_a - mx);      // the virtual key: no column, its share of the row's mass
+#endif
     if (lane == 0) {
       sM[hr] = mx;
       sL[hr] = 1.f / sm;
@@ -512,6 +527,14 @@ __global__ void __launch_bounds__(kNT) ekv_tova_headmean_kernel(const EkvScoreAr
 #define EKV_SS_CAT_(a, b) a##b
 #define EKV_SS_CAT(a, b) EKV_SS_CAT_(a, b)
 
+#if EKV_SINK
+hipError_t ekv_launch_tova_headmean_sink(const EkvScoreArgs& a, const float* sinks, int layer_count, hipStream_t s) {
+  if (sinks == nullptr) return hipErrorInvalidValue;
+  const size_t lds = (size_t)a.n_q_heads * 2 * 4;
+  hipLaunchKernelGGL(ekv_tova_headmean_kernel, dim3(layer_count), dim3(kNT), lds, s, a, sinks);
+  return hipGetLastError();
+}
+#else
 hipError_t EKV_FN_SCORE_SELECT(EKV_SS_NT, EKV_ELEM)(const EkvScoreArgs& a, int layer_count, hipStream_t s) {
   const size_t lds = ekv_score_lds_bytes(kNT, a);
   if (lds > 160 * 1024) return hipErrorInvalidValue;
@@ -538,4 +561,5 @@ hipError_t EKV_SS_CAT(ekv_launch_tova_headmean_nt, EKV_SS_NT)(const EkvScoreArgs
   return hipGetLastError();
 }
 #endif
+#endif  // !EKV_SINK
 #endif  // EKV_SS_DEVICE_ONLY

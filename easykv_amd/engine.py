@@ -74,6 +74,8 @@ ROW_FORMATS = {
 
 # head_dims the soft-capped kernels (KVBank(logit_cap=...)) are built for
 CAPPED_HEAD_DIMS = (128, 256)
+# head_dims the sink kernels (KVBank(sinks=...)) are built for
+SINK_HEAD_DIMS = (64, 128)
 # head_dims served with plain keys and 16-bit rows only: no RoPE-on-read build (set_rope, streaming) and no quantised row format
 PLAIN_KEYS_HEAD_DIMS = (256,)
 
@@ -162,10 +164,18 @@ class KVBank:
     long_rows = False    # KVBank(..., long_rows=True): the steps go to the long-row family (ekv_long_*), set per bank by __init__
     logit_cap = None     # KVBank(..., logit_cap=c): soft-capped logits, the steps go to the capped family (ekv_cap_*), set per bank by __init__
     sm_scale = None      # KVBank(..., sm_scale=s): logits are q.k * s (None: 1 / sqrt(head_dim)), in every call family
+    sinks = None         # KVBank(..., sinks=t): attention sinks, the steps go to the sink family (ekv_sink_*), set per bank by __init__
 
     def __init__(self, n_layers, n_q_heads, n_kv_heads, head_dim, cap, device="cuda", scored=True, dtype=torch.float16, kv_quant=None, long_rows=False,
-                 logit_cap=None, sm_scale=None):
-        """``sm_scale``: the softmax scale, logits are ``q.k * sm_scale`` (None: ``1 / sqrt(head_dim)``; e.g. ``query_pre_attn_scalar ** -0.5``
+                 logit_cap=None, sm_scale=None, sinks=None):
+        """``sinks``: a tensor ``[n_layers, n_q_heads]`` of finite values, kept as fp32 on the device: learned attention sinks (gpt-oss:
+        ``s_aux``; include/easykv_hip.h, "attention sinks").  The logit of layer ``l`` and query head ``h`` joins every softmax of that
+        head as a virtual key with value 0: it takes its share of the probability mass and has no column, no score and is never a
+        victim.  The bank's steps go to the sink call family: decode steps plan as the plain ones (phase order F, no resident rows),
+        chunk steps and the dense prefix run on the 16x16 chunk kernel in blocks of at most 32 folded rows.  head_dim 64 and 128, 16-bit
+        rows, plain keys: not with ``logit_cap``, ``kv_quant`` or ``long_rows``, and :meth:`quantize` / :meth:`set_rope` refuse such a
+        bank.  A wrong shape or a non-finite value raises ``ValueError``.
+        ``sm_scale``: the softmax scale, logits are ``q.k * sm_scale`` (None: ``1 / sqrt(head_dim)``; e.g. ``query_pre_attn_scalar ** -0.5``
         of a Gemma 2 / Gemma 3 model).  Every call family reads it (``ekv_step.sm_div = 1 / sm_scale``).
         ``logit_cap=c`` (finite, > 0): attention-logit soft-capping, ``s = c * tanh(q.k * sm_scale / c)`` before the mask and the
         softmax (Gemma 2: ``attn_logit_softcapping``; include/easykv_hip.h, "soft-capped logits").  The bank's steps go to the capped
@@ -205,6 +215,21 @@ class KVBank:
             if head_dim not in CAPPED_HEAD_DIMS:
                 raise _lib.EkvError(f"KVBank(logit_cap=...): soft-capped logits are built for head_dim {' and '.join(map(str, CAPPED_HEAD_DIMS))}, not {head_dim}")
             self.logit_cap = float(logit_cap)
+        if sinks is not None:      # (before anything is allocated or loaded)
+            if not (torch.is_tensor(sinks) and tuple(sinks.shape) == (n_layers, n_q_heads)):
+                got = tuple(sinks.shape) if torch.is_tensor(sinks) else type(sinks).__name__
+                raise ValueError(f"KVBank sinks must be a tensor of shape [n_layers, n_q_heads] = [{n_layers}, {n_q_heads}], not {got}")
+            if not bool(torch.isfinite(sinks.detach().float()).all()):
+                raise ValueError("KVBank sinks must be finite (a sink is a logit: -inf would be 'no sink', which is sinks=None)")
+            if logit_cap is not None:
+                raise _lib.EkvError("KVBank(sinks=..., logit_cap=...): there is no capped sink call (the sink family has no soft-capped form)")
+            if fmt is not None:
+                raise _lib.EkvError(f"KVBank(sinks=...): attention sinks are built for 16-bit rows, not for {fmt['label']} rows "
+                                    f"(kv_quant={kv_quant!r}): there is no quantised sink call")
+            if long_rows:
+                raise _lib.EkvError("KVBank(sinks=..., long_rows=True): there is no long sink call (the long-row family has no sink form)")
+            if head_dim not in SINK_HEAD_DIMS:
+                raise _lib.EkvError(f"KVBank(sinks=...): attention sinks are built for head_dim {' and '.join(map(str, SINK_HEAD_DIMS))}, not {head_dim}")
         if fmt is not None:
             _check_row_shape(fmt, head_dim, n_q_heads // max(1, n_kv_heads))
         self.dtype, self._dt = dtype, _lib.DTYPE_CODES[dtype]
@@ -253,6 +278,8 @@ class KVBank:
                           self.arrive.data_ptr(), self.birth.data_ptr() if scored else None,
                           self.slot_state.data_ptr() if scored else None)
         self.rope_cos = self.rope_sin = None
+        if sinks is not None:      # (a constant of the bank: the pointer every sink call carries, hipGraph capture included)
+            self.sinks = sinks.detach().to(dev, torch.float32).contiguous().clone()
         self._attach(fmt)
         self.reset()
 
@@ -363,6 +390,9 @@ class KVBank:
         if self.logit_cap is not None:
             raise _lib.EkvError(f"{m}: the bank was created with logit_cap={self.logit_cap:g}, and soft-capped logits are built for 16-bit "
                                 f"rows, not for {fmt['label']} rows: there is no capped quantised call")
+        if self.sinks is not None:
+            raise _lib.EkvError(f"{m}: the bank was created with sinks, and attention sinks are built for 16-bit rows, not for "
+                                f"{fmt['label']} rows: there is no quantised sink call")
         if self.long_rows:
             raise _lib.EkvError(f"{m}: the bank was created with long_rows=True, and the long-row scorer is built for 16-bit rows, not "
                                 f"for {fmt['label']} rows: {fmt['label']} rows have no long form")
@@ -445,6 +475,9 @@ class KVBank:
         if self.logit_cap is not None:      # (16-bit rows likewise) the capped family: the cap stands behind the dtype, where a quantised call has its descriptor
             self._check_fn, self._info_fn, self._ws_fn, self._attend_fn = (getattr(self.lib, _lib.CAP_CALLS[what]) for what in _lib.STEP_CALLS)
             self._desc_ref = (C.c_float(self.logit_cap),)
+        if self.sinks is not None:      # (16-bit rows likewise) the sink family: the sinks' device pointer stands behind the dtype
+            self._check_fn, self._info_fn, self._ws_fn, self._attend_fn = (getattr(self.lib, _lib.SINK_CALLS[what]) for what in _lib.STEP_CALLS)
+            self._desc_ref = (C.c_void_p(self.sinks.data_ptr()),)
 
     def kv_bytes(self) -> int:
         """Bytes held for the K/V rows: 16-bit rows, FP8 codes + row scales (``2 * head_dim + 8`` per row pair), or MXFP4 codes +
@@ -525,6 +558,8 @@ class KVBank:
         self._quant_refuse(True, "set_rope (RoPE-on-read)")
         if self.logit_cap is not None:
             raise _lib.EkvError("set_rope(): RoPE-on-read has no soft-capped build (a bank created with logit_cap serves plain keys only)")
+        if self.sinks is not None:
+            raise _lib.EkvError("set_rope(): RoPE-on-read has no sink build (a bank created with sinks serves plain keys only)")
         if self.head_dim in PLAIN_KEYS_HEAD_DIMS:
             raise _lib.EkvError(f"set_rope(): RoPE-on-read has no build for head_dim {self.head_dim} (plain keys only)")
         self.rope_cos = cos.to(self.device, torch.float32).contiguous()
@@ -618,7 +653,7 @@ class KVBank:
         """(n_split, fused) the library will use for this step."""
         st = self.make_step(plan, q_len, layer_begin, self.n_layers - layer_begin if layer_count is None else layer_count)
         st.phases = phases
-        if self._fmt is not None or self.long_rows or self.logit_cap is not None:      # (the dry run of the bank's own family: a step the bank refuses plans as not fused)
+        if self._fmt is not None or self.long_rows or self.logit_cap is not None or self.sinks is not None:      # (the dry run of the bank's own family: a step the bank refuses plans as not fused)
             info = self.step_info(plan, q_len, layer_begin, layer_count, phases)
             return info["n_split"], bool(info["fused"])
         ns, fu = C.c_int32(0), C.c_int32(0)
@@ -639,7 +674,7 @@ class KVBank:
     def resident_rows(self, plan: StepPlan, q_len=1, layer_begin=0, layer_count=None, phases=0) -> int:
         """Resident rows the library plans this step's launch with (ekv_step_resident_rows) under this bank's ``resident_bytes``;
         0 for a quantised bank."""
-        if self._fmt is not None:
+        if self._fmt is not None or self.sinks is not None:      # (the sink instances are built without resident rows, as the kv164 ones)
             return 0
         st = self.make_step(plan, q_len, layer_begin, self.n_layers - layer_begin if layer_count is None else layer_count)
         st.phases = phases
@@ -743,7 +778,7 @@ class KVBank:
     def _planned_split(self, st) -> int:
         """The split count the library plans for ``st`` (a capped bank: by its own family — a capped chunk step is tiled in narrower
         blocks than the plain call's)."""
-        if self.logit_cap is not None:
+        if self.logit_cap is not None or self.sinks is not None:
             info = (C.c_int32 * 10)()
             check(self._info_fn(C.byref(self._bank), C.byref(st), self._dt, *self._desc_ref, info, 10), self._info_fn.__name__)
             return int(info[0])
@@ -893,9 +928,9 @@ class KVBankBatch:
     eviction geometry — in ONE call: one launch per kernel kind over the layers ``{s * n_layers + layer}``."""
 
     def __init__(self, n_seq, n_layers, n_q_heads, n_kv_heads, head_dim, cap, device="cuda", scored=True, dtype=torch.float16, kv_quant=None, long_rows=False,
-                 logit_cap=None, sm_scale=None):
+                 logit_cap=None, sm_scale=None, sinks=None):
         """``sm_scale``: the softmax scale of every sequence (:class:`KVBank`; None: ``1 / sqrt(head_dim)``).  ``logit_cap`` raises: there is
-        no capped batch call.
+        no capped batch call.  ``sinks`` raises: there is no sink batch call.
         ``kv_quant='fp8'``: the shared bank holds FP8 planes only from the start (the 16-bit rows of ``n_seq`` sequences are never
         allocated); its sequences are filled by :meth:`adopt` from banks quantised by :meth:`KVBank.quantize_fp8`.
         ``kv_quant='mxfp4'``: likewise with MXFP4 planes, filled from banks quantised by :meth:`KVBank.quantize_mxfp4`.
@@ -908,6 +943,9 @@ class KVBankBatch:
         if logit_cap is not None:
             raise _lib.EkvError("KVBankBatch(logit_cap=...): soft-capped logits are built for single sequences, not for decode batches: "
                                 "there is no capped batch call")
+        if sinks is not None:
+            raise _lib.EkvError("KVBankBatch(sinks=...): attention sinks are built for single sequences, not for decode batches: "
+                                "there is no sink batch call")
         if not 1 <= n_seq <= _lib.MAX_SEQS:
             raise ValueError(f"a decode batch holds 1..{_lib.MAX_SEQS} sequences, not {n_seq}")
         self.n_seq, self.n_layers = n_seq, n_layers

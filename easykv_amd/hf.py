@@ -25,12 +25,15 @@ IMPL = "easykv_amd"
 _registered = False
 
 
-def _easykv_attention(module, query, key, value, attention_mask=None, dropout=0.0, scaling=None, softcap=None, **kwargs):
+def _easykv_attention(module, query, key, value, attention_mask=None, dropout=0.0, scaling=None, softcap=None, s_aux=None, **kwargs):
     """The attention function of the seam.  ``scaling`` and ``softcap`` (Gemma 2 passes ``attn_logit_softcapping`` under that name) are what
     the MODULE would compute with; the kernels compute with the active cache's ``sm_scale`` / ``logit_cap`` (set by the driver from the
     model's config).  They are held against each other (relative tolerance 1e-3) and a mismatch raises rather than compute another model.
-    ``sliding_window`` (in ``kwargs``) is ignored: the retained cache is attended whole, on Gemma 2's local layers too, as the reference
-    does for Mistral."""
+    ``s_aux`` (gpt-oss passes its learned attention sinks, one logit per query head, under that name) is held against the active cache's
+    ``sinks`` row of ``module.layer_idx`` likewise — once per (cache, layer), so the decode loop gains no host sync; a module with sinks on
+    a cache without them, or the reverse, raises.
+    ``sliding_window`` (in ``kwargs``) is ignored: the retained cache is attended whole, on Gemma 2's and gpt-oss's local layers too, as
+    the reference does for Mistral."""
     cache = api.active_cache()
     if cache is None:
         raise RuntimeError("easykv_amd attention called outside easykv_generate(): no BudgetedKVCache is active")
@@ -45,6 +48,9 @@ def _easykv_attention(module, query, key, value, attention_mask=None, dropout=0.
         raise ValueError(f"easykv_amd attention: the module soft-caps its logits at {softcap:g}, the active cache has no logit_cap")
     if logit_cap is not None and (softcap is None or abs(softcap / logit_cap - 1.0) > 1e-3):
         raise ValueError(f"easykv_amd attention: the active cache soft-caps its logits at {logit_cap:g}, the module at {softcap}")
+    sinks = getattr(cache, "sinks", None)
+    if s_aux is not None or sinks is not None:
+        _check_sinks(cache, sinks, module, s_aux)
     if cache.streaming:
         # streaming=True (llama_patch.py:310-327) caches UN-rotated keys; the stock module has already applied RoPE at the
         # true positions, so take it off again (rotation by -theta: x = x'*cos - rotate_half(x')*sin, fp32)
@@ -59,6 +65,27 @@ def _easykv_attention(module, query, key, value, attention_mask=None, dropout=0.
     #  active cache is then a BudgetedKVCacheBatch and reads the rows in place, a batch row being Hq * D elements apart)
     out = cache.attend(module.layer_idx, query, key, value)        # in the bank's dtype
     return out.transpose(1, 2).to(query.dtype), None      # (no conversion when the bank holds the model's dtype)
+
+
+def _check_sinks(cache, sinks, module, s_aux):
+    """The module's attention sinks against the active cache's row of its layer (relative tolerance 1e-3), once per (cache, layer)."""
+    layer = module.layer_idx
+    if s_aux is None:
+        raise ValueError(f"easykv_amd attention: the active cache has attention sinks, the module of layer {layer} passes none (s_aux)")
+    if sinks is None:
+        raise ValueError(f"easykv_amd attention: the module of layer {layer} passes attention sinks (s_aux), the active cache has none: "
+                         "it would compute another model")
+    checked = cache._sinks_checked
+    if layer in checked:
+        return
+    row = layer - getattr(cache, "layer_begin", 0)
+    if not 0 <= row < sinks.shape[0] or s_aux.numel() != sinks.shape[1]:
+        raise ValueError(f"easykv_amd attention: the module of layer {layer} passes {s_aux.numel()} attention sinks, the active cache holds "
+                         f"{sinks.shape[1]} per layer for {sinks.shape[0]} layers")
+    mine, theirs = sinks[row].float(), s_aux.detach().reshape(-1).to(sinks.device, torch.float32)
+    if not bool(((mine - theirs).abs() <= 1e-3 * torch.maximum(mine.abs(), theirs.abs())).all()):
+        raise ValueError(f"easykv_amd attention: the attention sinks of the module of layer {layer} differ from the active cache's row {row}")
+    checked.add(layer)
 
 
 def _unrotate(x, cos, sin, gain=1.0):

@@ -549,6 +549,40 @@ int ekv_cap_step_attend(const ekv_bank *bank, const ekv_step *step, int32_t dtyp
  * runs).  EKV_E_ARG: n < 0, a NULL pointer with n > 0, sm_div <= 0 or NaN, a cap that is <= 0, NaN or infinite. */
 int ekv_softcap_eval(const float *x, int64_t n, float sm_div, float cap, float *out, void *stream);
 
+/* Attention sinks (ABI 8, additive): the *_typed calls of a 16-bit bank whose model adds one learned logit per query head to every
+ * softmax (gpt-oss: `sinks`, handed to the attention function as s_aux).  NORMATIVE.  Take a query row of query head hq in bank layer l.
+ * Its real-key logits are s_j = q.k_j / sm_div, formed exactly as the plain call forms them, with the mask and the dead rows already
+ * applied as -inf.  The sink is a = sinks[l][hq], fp32 and finite.  Then
+ *
+ *     M   = max(max_j s_j, a)
+ *     p_j = exp(s_j - M) / (sum_i exp(s_i - M) + exp(a - M))
+ *     out = sum_j p_j v_j
+ *
+ * The sink is a virtual key with value 0.  It has no score column and no slot, and it is never a victim.  Everything downstream sees
+ * p_j and nothing else: the outputs, the column sums, sum p / sum p^2 / counts, the tova row, the GQA mean over the group and every
+ * select.  Selection rules, windows and tie rules are untouched.  Where M already includes a, the extra term is <= 1.  A sink far below
+ * every logit (exp(a - M) rounds to 0) gives the plain call's results bit for bit.
+ *
+ * sinks: DEVICE pointer, fp32 [bank->n_layers][n_q_heads], indexed by BANK layer (step->layer_begin + the launch's layer); the dry-run
+ * calls (check, info, workspace_bytes) only test it for NULL, and it must stay valid until the step has run (a captured graph keeps
+ * the pointer).  No public struct changes.
+ *
+ * A sink DECODE step plans as the plain call of the same (bank, step, dtype): same n_split, launches and workspace.  The sink instances
+ * are built without the mixed phase orders and without resident rows (as the kv164 ones): info [9] is 0, every workgroup runs order F.
+ * A sink CHUNK step or dense prefix runs on the 16x16x32 kernel alone, by the rules of the capped call: blocks of at most 32 GQA-folded
+ * rows; one pass, with the scorer as the kernel's tail where the step is one unsplit block, else statistics pass + exact pass + generic
+ * scorer; never the wide, the logits-in-LDS or the logits-resident kernel, so info [3] (wide) is always 0.  Refused before any launch,
+ * with ekv_sink_workspace_bytes = 0: rope_on_read, a head_dim other than 64 / 128, chunk steps whose GQA factor exceeds 32
+ * (EKV_E_UNSUPPORTED); NULL sinks (EKV_E_ARG, behind the element type and before anything else is read).  The head-averaged TOVA row
+ * (tova_head_mean) is rebuilt from the exported logits by a sink build of its kernel: M and the sum include the sink.  16-bit rows and single sequences only: there is no sink
+ * batched, quantised, long or capped call. */
+int ekv_sink_step_check(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const float *sinks);
+int ekv_sink_step_info(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const float *sinks, int32_t *info, int32_t n_info);
+size_t ekv_sink_workspace_bytes(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const float *sinks);
+int ekv_sink_step_attend(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const float *sinks, const void *q, const void *k_new,
+                         const void *v_new, void *out, int32_t *evict_ids, const float *rope_cos, const float *rope_sin,
+                         void *workspace, size_t workspace_bytes, void *stream);
+
 /* Batched decode steps (ABI 8, additive): ONE call, and one launch per kernel kind, serves n_seq sequences whose caches have
  * different lengths and different eviction geometry.  Each entry of the table names the bank layer it attends and carries what
  * ekv_step holds per step; entry i owns row i of the call's tensors.  The layers of a table need not be contiguous or ordered, so
