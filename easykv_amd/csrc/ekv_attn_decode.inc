@@ -210,8 +210,14 @@ __global__ void __launch_bounds__(256) ekv_attn_decode_kernel(const EkvAttnArgs 
 // ------------------------------------------------------------------------------------------------------
 // fused kernel
 // ------------------------------------------------------------------------------------------------------
+// The 8-wave 5-column flagship build (16-bit rows, head_dim 128, GQA x 1, slot-indexed rows: the one with both phase orders that a
+// launch of more than 512 heads runs in two rounds) must fit TWO workgroups on a CU: four waves per SIMD, 128 VGPRs.  The second
+// launch bound counts waves per SIMD; every other 8-wave build of GQA factor 1 keeps 2 (the soft-capped one too: under 128 VGPRs it
+// spills six, so it keeps order F alone and its code).
+#define EKV_FUSED_TWO_PER_CU(D, ROPE, ITEMS, SLOT) \
+  ((D) == 128 && !(ROPE) && (SLOT) && (ITEMS) <= 5 && !EKV_G8 && !EKV_MX && !EKV_KV164 && !EKV_BATCH && !EKV_SINK && !EKV_SOFTCAP)
 template <int D, int REP, bool ROPE, int ITEMS, int NW, bool SLOT>
-__global__ void __launch_bounds__(64 * NW, (NW >= 8 ? (REP == 1 ? 2 : 1) : (SLOT && ITEMS > 12 ? 2 : (REP == 1 ? (EKV_MX ? 2 : 4) : (REP == 2 ? 3 : 2))))) ekv_decode_fused_kernel(const EkvAttnArgs EKV_ARG_A, const EkvScoreArgs EKV_ARG_SC EKV_TB_PARAM EKV_SINK_ONLY(, const float* const sinks)) {
+__global__ void __launch_bounds__(64 * NW, (NW >= 8 ? (REP == 1 ? (EKV_FUSED_TWO_PER_CU(D, ROPE, ITEMS, SLOT) ? 4 : 2) : 1) : (SLOT && ITEMS > 12 ? 2 : (REP == 1 ? (EKV_MX ? 2 : 4) : (REP == 2 ? 3 : 2))))) ekv_decode_fused_kernel(const EkvAttnArgs EKV_ARG_A, const EkvScoreArgs EKV_ARG_SC EKV_TB_PARAM EKV_SINK_ONLY(, const float* const sinks)) {
   EKV_SHADOW_A(blockIdx.z)
   EKV_SHADOW_SC(blockIdx.z)
   using Gm = EkvDecodeGeom<D, NW>;
@@ -260,7 +266,12 @@ __global__ void __launch_bounds__(64 * NW, (NW >= 8 ? (REP == 1 ? 2 : 1) : (SLOT
   // in LDS.  The tail is a latency-bound chain of block barriers that leaves HBM idle; when the workgroups of a CU are in different
   // orders, each order's tail falls under the other's stream.  Both orders produce the same bits (below), so WHICH workgroups take
   // order K may depend on where the hardware placed them.
-  constexpr bool kOrders = D == 128 && REP == 1 && !ROPE && NW == 4 && SLOT && ITEMS <= 12 && !EKV_G8 && !EKV_MX && !EKV_KV164 && !EKV_BATCH && !EKV_SINK;
+  // 8-wave workgroups (not the soft-capped builds) have both orders too: the plane loop, the KEEP tail and the V replay are written
+  // over NW, and a launch of more than two of them per CU runs in dispatch rounds (rule source 3 below).  ITEMS 5: extents up to 2304
+  // rows.  Extents up to 6144 rows: the 12-column build keeps order F alone and its code — with both orders in it, its order F ran 4 %
+  // slower (118.9 -> 124.0 us at 512 heads x 2561 rows: 78 scalar registers spilled, 36 bytes of scratch) — and a launch that asks
+  // for order K there runs a build of its own, ITEMS 13 (launch_fused_nw).
+  constexpr bool kOrders = D == 128 && REP == 1 && !ROPE && ((NW == 4 && ITEMS <= 12) || (NW == 8 && !EKV_SOFTCAP && (ITEMS <= 5 || ITEMS == 13))) && SLOT && !EKV_G8 && !EKV_MX && !EKV_KV164 && !EKV_BATCH && !EKV_SINK;
   bool order_k = false;
   if constexpr (kOrders) {
     const int om = a.fused_order & 3;
@@ -273,7 +284,12 @@ __global__ void __launch_bounds__(64 * NW, (NW >= 8 ? (REP == 1 ? 2 : 1) : (SLOT
         const uint32_t hw = __builtin_amdgcn_s_getreg(63492);   // HW_REG_HW_ID: WAVE_ID [3:0], TG_ID [19:16]
         const int src = (a.fused_order >> 4) & 3;
         const uint32_t x = src == 0 ? (hw >> 16) & 15u : (src == 1 ? hw & 15u : (uint32_t)(ll * a.n_kv_heads + h));
-        const bool below = (x & ((a.fused_order >> 8) & 15u)) < ((a.fused_order >> 12) & 15u);
+        bool below = (x & ((a.fused_order >> 8) & 15u)) < ((a.fused_order >> 12) & 15u);
+        // Source 3 (the 8-wave instances; the 4-wave ones keep their code and read it as source 2), the rule by dispatch round:
+        // workgroups are dispatched in grid order, so on a launch that runs in rounds the position in the grid, not the hardware
+        // slot, says who ends last.  The two nibbles are one threshold, (mask << 4 | bound) * EKV_ORDER_ROUND_UNIT workgroups.
+        if constexpr (NW == 8)
+          if (src == 3) below = x < (uint32_t)EKV_ORDER_ROUND_THRESHOLD(a.fused_order);
         *s_flag = below != (((a.fused_order >> 6) & 1) != 0) ? 1u : 0u;
       }
       __syncthreads();
@@ -286,10 +302,21 @@ __global__ void __launch_bounds__(64 * NW, (NW >= 8 ? (REP == 1 ? 2 : 1) : (SLOT
   if (scored) ekv_tail_prefetch_rows<NW, false>(sc, head_row, W, w_pad, roco, sS, sQ, sC, !SLOT);
   float g_old = 0.f, c_new = 0.f;
   int nb = 0;
-  if (SLOT) {
+  // The 8-wave instances with both orders have 128 VGPRs for two workgroups per CU and none to carry the three numbers across the
+  // stream: they are requested behind it, with the count bases and births (the tail reads all of them after its softmax passes).
+  // Every other instance keeps the statements where they were (and its device code).
+  constexpr bool kLateHeadState = kOrders && NW == 8;
+  // (the appended entry starts from the count the ordered row holds behind its live entries — 0 after decode steps — minus the
+  //  running offset: count = base + g)
+#define EKV_HEAD_STATE()                                                                  \
+  do {                                                                                    \
+    const size_t head = (size_t)(a.layer_begin + ll) * a.n_kv_heads + h;                  \
+    g_old = sc.slot_state[4 * head];                                                      \
+    nb = reinterpret_cast<const int32_t*>(sc.slot_state)[4 * head + 1];                   \
+    c_new = sc.cnt_tail[head_row + T - 1] - g_old;                                        \
+  } while (0)
+  if (SLOT && !kLateHeadState) {
     const size_t head = (size_t)(a.layer_begin + ll) * a.n_kv_heads + h;
-    // (the appended entry starts from the count the ordered row holds behind its live entries — 0 after decode steps — minus the
-    //  running offset: count = base + g)
     g_old = sc.slot_state[4 * head];
     nb = reinterpret_cast<const int32_t*>(sc.slot_state)[4 * head + 1];
     c_new = sc.cnt_tail[head_row + T - 1] - g_old;
@@ -353,6 +380,7 @@ __global__ void __launch_bounds__(64 * NW, (NW >= 8 ? (REP == 1 ? 2 : 1) : (SLOT
         mk = fmaxf(mk, acc);
       }
       ekv_tail_prefetch_ragged<NW>(sc, head_row, W, roco, sS, sQ, sC, false);
+      if constexpr (kLateHeadState) EKV_HEAD_STATE();
       float cC[ITEMS];
       int32_t cB[ITEMS];
 #pragma unroll
@@ -462,6 +490,7 @@ __global__ void __launch_bounds__(64 * NW, (NW >= 8 ? (REP == 1 ? 2 : 1) : (SLOT
   float cC[SLOT ? ITEMS : 1];
   int32_t cB[SLOT ? ITEMS : 1];
   if (SLOT) {
+    if constexpr (kLateHeadState) EKV_HEAD_STATE();
 #pragma unroll
     for (int it = 0; it < (SLOT ? ITEMS : 1); ++it) {
       const int j = min(tid + it * 64 * NW, a.cap - 1);
@@ -501,6 +530,8 @@ __global__ void __launch_bounds__(64 * NW, (NW >= 8 ? (REP == 1 ? 2 : 1) : (SLOT
   }
 #endif
 }
+
+#undef EKV_HEAD_STATE
 
 template <int REP>
 hipError_t launch(const EkvAttnArgs& a EKV_TB_DECL EKV_SINK_ONLY(, const float* sinks), int layer_count, hipStream_t s) {
@@ -548,6 +579,10 @@ hipError_t launch_fused_nw(const EkvAttnArgs& a, const EkvScoreArgs& sc EKV_TB_D
       if (a.phys_extent <= NT * I0) return launch_fused_k<REP, I0, NW, true>(a, sc EKV_TB_PASS EKV_SINK_ONLY(, sinks), layer_count, s);
       // extents up to 6144 rows: 12 (8-wave) / 24 (4-wave) columns per thread in registers; the 4-wave build gives up the fourth
       // workgroup per CU for them (LDS would not have allowed it at these row counts anyway)
+      // (8 waves, 16-bit rows, head_dim 128, one query head per KV head: a launch that asks for order K at these extents runs the
+      //  13-column build, the one that has both orders there; the 12-column build stays what it was)
+      if constexpr (NW == 8 && REP == 1 && EKV_D == 128 && !EKV_G8 && !EKV_MX && !EKV_KV164 && !EKV_SINK && !EKV_SOFTCAP)
+        if ((a.fused_order & 3) != 0 && a.phys_extent <= NT * I1) return launch_fused_k<REP, I1 + 1, NW, true>(a, sc EKV_TB_PASS EKV_SINK_ONLY(, sinks), layer_count, s);
       if (a.phys_extent <= NT * I1) return launch_fused_k<REP, I1, NW, true>(a, sc EKV_TB_PASS EKV_SINK_ONLY(, sinks), layer_count, s);
     }
     return hipErrorInvalidValue;

@@ -17,6 +17,13 @@ enum EkvRows : int32_t { EKV_ROWS_kv16, EKV_ROWS_kv8, EKV_ROWS_kv4, EKV_ROWS_kv6
 #define EKV_RESIDENT_UNIT 32      // rows of one wave iteration of the stream (EkvDecodeGeom::RW at head_dim 128)
 #define EKV_RESIDENT_BITS(rows) ((((rows) / EKV_RESIDENT_UNIT) > 255 ? 255 : ((rows) / EKV_RESIDENT_UNIT)) << 16)
 #define EKV_RESIDENT_ROWS(order) ((((order) >> 16) & 255) * EKV_RESIDENT_UNIT)
+// Rule source 3 of the mixed phase order (bits 4-5 of fused_order = 3; the 8-wave flagship instances): order K for the workgroups at or
+// past a threshold in the grid's dispatch order (layer-major, head-minor).  The threshold travels in the rule's mask (bits 8-11, high
+// nibble) and bound (bits 12-15, low nibble) fields, in units of 8 workgroups: 0 .. 2040.
+#define EKV_ORDER_ROUND_UNIT 8
+#define EKV_ORDER_ROUND_BITS(wgs) \
+  (((((wgs) / EKV_ORDER_ROUND_UNIT > 255 ? 255 : (wgs) / EKV_ORDER_ROUND_UNIT) >> 4) << 8) | ((((wgs) / EKV_ORDER_ROUND_UNIT > 255 ? 255 : (wgs) / EKV_ORDER_ROUND_UNIT) & 15) << 12))
+#define EKV_ORDER_ROUND_THRESHOLD(order) ((((((order) >> 8) & 15) << 4) | (((order) >> 12) & 15)) * EKV_ORDER_ROUND_UNIT)
 
 // One kernel launch sequence entry of a step (EkvStepPlan::list), in issue order.
 enum EkvLaunchKind : int32_t {

@@ -39,10 +39,39 @@ bool ekv_attn_decode_supported(int head_dim, int rep) {
 
 // The whole decode step in one launch: possible when a head is not split, at most one victim, and the row fits.
 // nw = 4: up to four workgroups per CU (LDS <= 80 KB keeps >= 2); nw = 8: one or two workgroups per CU.
-int ekv_decode_fused_nw(i64 n_heads_in_launch) {
+// Two rounds (rounds_shape: the step runs the 8-wave instance that has both phase orders — head_dim 128, one query head per KV head,
+// 16-bit rows, plain keys, slot-indexed rows, a scored policy, an extent of at most 2304 rows, the 5-column build): a launch of 1024 heads or more runs
+// as 8-wave workgroups, two resident per CU, the rest dispatched as the first ones end, every workgroup in order K (the rule by
+// dispatch round with threshold 0, ekv_decode_fused_order).  EKV_FUSED_ROUNDS = 0 / 1 (A/B knob, read once) over the compile-time
+// default, which is what the headline comparison of DESIGN.md §8 "two rounds" decided: 170.4 -> 165.4 us at 1024 heads (roco; h2o_head
+// and tova measured there too), 287.0 -> 282.0 us at the 1600 heads of the 13B shape.
+#ifndef EKV_FUSED_ROUNDS_DEFAULT
+#define EKV_FUSED_ROUNDS_DEFAULT 1
+#endif
+// First workgroup, in dispatch order, that runs order K on such a launch.  Measured on the flagship launch (1024 heads, us per launch,
+// DESIGN.md §8 "two rounds"): 0 -> 164.2 .. 164.8, 64 -> 164.8 .. 165.2, 128 -> 165.7 .. 166.4, 256 -> 168.2 .. 168.5, 512 (the second
+// round alone) 168.3 .. 170.1, 768 -> 168.2 .. 169.3; order K in the FIRST round alone 170.6 .. 171.2; all F 171.6 .. 173.4; the 4-wave
+// launch with its slot rule 168.4 .. 169.4.  With two 8-wave workgroups per CU the K stream of one falls under the V stream or the tail
+// of the other from the first round on, so every workgroup takes order K: threshold 0.
+#ifndef EKV_FUSED_ROUNDS_THRESHOLD
+#define EKV_FUSED_ROUNDS_THRESHOLD 0
+#endif
+// Fewest heads of a launch the planner runs this way by itself: two full rounds on 256 CUs.  At 576 heads (18 layers: one round and an
+// eighth) the 8-wave launch is level with the 4-wave one, 110.1 against 110.2 us, so those launches keep four waves.
+#ifndef EKV_FUSED_ROUNDS_MIN_HEADS
+#define EKV_FUSED_ROUNDS_MIN_HEADS 1024
+#endif
+namespace {
+int fused_nw_forced() {
   static const int force = env_int("EKV_FUSED_NW", 0);   // (A/B knob)
-  if (force == 4 || force == 8) return force;
-  return (n_heads_in_launch >= 256 && n_heads_in_launch <= 512) ? 8 : 4;
+  return force == 4 || force == 8 ? force : 0;
+}
+}  // namespace
+int ekv_decode_fused_nw(i64 n_heads_in_launch, bool rounds_shape) {
+  static const int rounds = env_int("EKV_FUSED_ROUNDS", EKV_FUSED_ROUNDS_DEFAULT);
+  if (fused_nw_forced()) return fused_nw_forced();
+  if (n_heads_in_launch >= 256 && n_heads_in_launch <= 512) return 8;
+  return (rounds > 0 && rounds_shape && n_heads_in_launch >= EKV_FUSED_ROUNDS_MIN_HEADS) ? 8 : 4;
 }
 
 // Mixed phase orders of the fused decode step: the default mode and rule (ekv_decode_fused_order).  Rule: order K for the workgroups
@@ -59,20 +88,39 @@ int ekv_decode_fused_nw(i64 n_heads_in_launch) {
 #define EKV_FUSED_ORDER_BOUND 2
 #define EKV_FUSED_ORDER_INVERT 1
 
-// Which phase order the workgroups of a one-launch decode step run in (ekv_plan.h).  Order K exists in the instance that serves the
-// flagship shape: head_dim 128, one query head per KV head, 4-wave workgroups, slot-indexed rows of at most 2304 physical rows, and only
+// Which phase order the workgroups of a one-launch decode step run in (ekv_plan.h).  Order K exists in the instances that serve the
+// flagship shape: head_dim 128, one query head per KV head, slot-indexed rows, 4-wave workgroups of at most 2304 physical rows (the
+// rule by hardware slot, below) or 8-wave workgroups of at most 6144 (the rule by dispatch round, in the function), and only
 // a scored policy has a tail to move.  Mixed needs at least two workgroups on a CU (256 CUs): per-layer and short stage launches keep
 // order F.  EKV_FUSED_ORDER = 0 all F / 1 mixed / 2 all K and EKV_FUSED_ORDER_RULE = source, mask, bound, invert as "s,m,b,i" (A/B knobs, read once).
 int ekv_decode_fused_order(int head_dim, int rep, bool scored, bool slot_rows, int nw, i64 n_heads_in_launch, int phys_extent) {
   static const int knob = env_int("EKV_FUSED_ORDER", EKV_FUSED_ORDER_DEFAULT);
-  static const int rule = [] {
+  static const bool rule_given = std::getenv("EKV_FUSED_ORDER_RULE") != nullptr;
+  auto pack = [](int s, int m, int b, int inv) { return ((s & 3) << 4) | ((inv & 1) << 6) | ((m & 15) << 8) | ((b & 15) << 12); };
+  static const int rule = [&] {
     int s = EKV_FUSED_ORDER_SRC, m = EKV_FUSED_ORDER_MASK, b = EKV_FUSED_ORDER_BOUND, inv = EKV_FUSED_ORDER_INVERT;
     if (const char* e = std::getenv("EKV_FUSED_ORDER_RULE")) std::sscanf(e, "%d,%d,%d,%d", &s, &m, &b, &inv);
-    return ((s & 3) << 4) | ((inv & 1) << 6) | ((m & 15) << 8) | ((b & 15) << 12);
+    return pack(s, m, b, inv);
   }();
-  if (knob <= 0 || knob > 2 || head_dim != 128 || rep != 1 || !scored || !slot_rows || nw != 4 || phys_extent > 2304) return 0;
+  if (knob <= 0 || knob > 2 || head_dim != 128 || rep != 1 || !scored || !slot_rows) return 0;
+  if (nw == 8) {
+    // The 8-wave instances (extents up to 6144 rows).  Launches of 256 .. 512 heads are one round of one or two workgroups per CU and
+    // keep order F in every mode.  More heads run in rounds: on such a launch the hardware slot says nothing about who ends last, the
+    // position in the dispatch order does — rule source 3 (ekv_kernels.h, EKV_ORDER_ROUND_*) with the invert bit set: order K from
+    // workgroup EKV_FUSED_ROUNDS_THRESHOLD on.  That threshold is 0, so every workgroup of the launch decides by the rule and takes order K
+    // (512, the first workgroup that has to wait for a slot on 256 CUs, measured slower: see the macro).  Fewer than 256 heads on 8 waves only exist under EKV_FUSED_NW = 8: all K
+    // on request, mixed under an explicit EKV_FUSED_ORDER_RULE (tests and A/B runs).
+    if (phys_extent > 6144 || (n_heads_in_launch >= 256 && n_heads_in_launch <= 512)) return 0;
+    if (knob == 2) return 2;
+    if (rule_given) return 1 | rule;
+    return n_heads_in_launch > 512 ? (1 | (3 << 4) | (1 << 6) | EKV_ORDER_ROUND_BITS(EKV_FUSED_ROUNDS_THRESHOLD)) : 0;
+  }
+  if (nw != 4 || phys_extent > 2304) return 0;
   if (knob == 2) return 2;
-  return n_heads_in_launch >= 512 ? (1 | rule) : 0;
+  // (rule source 3 is compiled into the 8-wave instances alone: a 4-wave launch ignores an EKV_FUSED_ORDER_RULE that names it and keeps
+  //  its slot rule, instead of reading the nibbles as the mask and bound of another source)
+  const int rule4 = ((rule >> 4) & 3) == 3 ? pack(EKV_FUSED_ORDER_SRC, EKV_FUSED_ORDER_MASK, EKV_FUSED_ORDER_BOUND, EKV_FUSED_ORDER_INVERT) : rule;
+  return n_heads_in_launch >= 512 ? (1 | rule4) : 0;
 }
 
 // Resident rows of the one-launch decode step (ekv_plan.h).  Step i + 1 reads the rows of step i except one per head, and the chip has a
@@ -278,6 +326,7 @@ struct StepShape {
   int max_rows;           // rows an unsplit chunk workgroup may walk (its slot entries live in LDS): 6144 with RoPE-on-read, 16384 plain
   bool long_rows;         // a long call (ekv_plan_step): the long-row scorer where the plan would end in the generic one
   bool capped;            // a capped call (ekv_plan_step): chunk steps on the one-tile build of the 16x16x32 kernel alone
+  bool no_orders;         // the call runs instances without the phase order K (quantised rows, a batch, sinks): no two-round launch
   int Dblk;               // the head_dim a chunk step's query blocks are cut for: D, or kChunkNarrowD for a capped call (blocks of <= 32 rows)
 };
 
@@ -299,7 +348,9 @@ void plan_tiling(const StepShape& s, EkvStepPlan* P) {
   P->l_pad = st->rope_on_read ? P->t_pad : (int)ekv_align((size_t)P->phys_extent, 64);
   const int wg_unit = n == 1 ? 128 : 64;
   i64 n_split = st->n_split;
-  P->fused_nw = ekv_decode_fused_nw(heads);
+  // (the 5-column 8-wave instance with both phase orders, two workgroups per CU: what a launch of 1024 heads or more runs in two rounds)
+  const bool rounds_shape = n == 1 && D == 128 && rep == 1 && !st->rope_on_read && s.slot_rows && s.scored && !s.no_orders && P->phys_extent <= 2304;
+  P->fused_nw = ekv_decode_fused_nw(heads, rounds_shape);
   if (n_split <= 0 && n == 1 && heads >= 256 && P->fused_nw == 8 &&
       ekv_decode_fused_supported(D, rep, T, P->t_pad, P->l_pad, st->n_evict, bank->cap, 8)) {
     n_split = 1;   // >= 1 head per CU: one 8-wave workgroup per head beats key-range splits + a second kernel (GQA shapes)
@@ -679,7 +730,7 @@ void plan_long_layout(const StepShape& s, EkvStepPlan* P) {
 // EKV_RUN_LONG_SCORE, two kernels; a preceding EKV_RUN_TOVA_MEAN stays; EKV_RUN_LONG_FOLD in front where the generic scorer would have
 // folded the output itself), the width refusal of plan_ending does not apply, and the workspace grows by that scorer's scratch
 // (plan_long_layout).  A step that ends anywhere else plans field for field as the plain call.
-int ekv_plan_step(const ekv_bank* bank, const ekv_step* step, EkvStepPlan* P, bool long_rows, bool capped) {
+int ekv_plan_step(const ekv_bank* bank, const ekv_step* step, EkvStepPlan* P, bool long_rows, bool capped, bool no_orders) {
   *P = EkvStepPlan{};
   P->key_rows = -1;
   const int bank_rc = check_bank(bank);
@@ -700,6 +751,7 @@ int ekv_plan_step(const ekv_bank* bank, const ekv_step* step, EkvStepPlan* P, bo
   s.LC = step->defer_layers > 0 ? step->defer_layers : step->layer_count;
   s.max_rows = step->rope_on_read ? 6144 : 16384;
   s.long_rows = long_rows;
+  s.no_orders = no_orders;
   s.capped = capped;
   s.Dblk = capped ? kChunkNarrowD : s.D;
 
@@ -819,13 +871,14 @@ int resolve_call(const EkvCall& c, EkvResolved* r) {
   const int variants = (c.long_rows ? 1 : 0) + (c.capped ? 1 : 0) + (c.sink ? 1 : 0);
   const int rc = (variants && (quant || c.batch || variants > 1))
                      ? EKV_E_UNSUPPORTED
-                     : ekv_plan_step(bank, r->step, P, c.long_rows, c.capped || c.sink);
+                     : ekv_plan_step(bank, r->step, P, c.long_rows, c.capped || c.sink, quant || c.batch || c.sink || c.capped);
   P->capped = c.capped ? 1 : 0;
   P->sink = c.sink ? 1 : 0;
   P->bf16 = c.dtype == EKV_DTYPE_BF16;
   P->rows = c.rows;
   P->batch = c.batch;
   if (quant || c.batch || c.sink) P->fused_order = 0;      // (the quantised, the batch and the sink instances keep order F, without resident rows)
+  if (c.capped && P->fused_nw == 8) P->fused_order &= ~0xFFFF;      // (the soft-capped 8-wave instances keep order F; their resident rows stay)
   auto refuse = [&](int code) {
     if (P->long_rows) {      // (a long plan that is refused after all reports the layout of the plain call: nothing of the long scorer remains)
       EkvStepPlan plain;

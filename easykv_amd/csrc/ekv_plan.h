@@ -8,11 +8,18 @@ int check_layers(const ekv_bank* b, int begin, int count);
 
 // ---- what a kernel family takes (each rule next to the measurements that set it: ekv_plan.cpp)
 bool ekv_attn_decode_supported(int head_dim, int rep);
-int ekv_decode_fused_nw(int64_t n_heads_in_launch);
+// Waves per workgroup of the one-launch decode step: 8 for launches of 256 .. 512 heads; 8 as well for more heads when the step runs
+// the 8-wave instance with both phase orders (rounds_shape) and the two-round default is on (ekv_plan.cpp); else 4.  EKV_FUSED_NW = 4 | 8
+// in the environment overrides.
+int ekv_decode_fused_nw(int64_t n_heads_in_launch, bool rounds_shape = false);
 // Phase order of the fused decode step's workgroups (ekv_attn_decode.inc, "order K"; the kernel field EkvAttnArgs.fused_order).  Bits
 // 0-1: 0 = all F (K+V stream, then the tail), 1 = mixed per CU, 2 = all K (K stream, tail, V stream).  Mixed: bits 4-5 = the number x that
 // decides (0 HW_ID.TG_ID, 1 HW_ID.WAVE_ID of wave 0, 2 the workgroup's index in the launch), bits 8-11 a mask m, bits 12-15 a bound b,
 // bit 6 = invert: order K when ((x & m) < b) != invert.  Both orders produce the same bits, so a hardware-derived number is as good as any.
+// Source 3 (8-wave workgroups): x = the workgroup's index in the launch, which is its place in the dispatch order, and the two nibbles
+// are one threshold t in units of 8 workgroups (EKV_ORDER_ROUND_THRESHOLD): order K when (x < t) != invert.  The planner always sets
+// invert with this source — order K at or past t — and plans t = 0: every workgroup in order K.  A 4-wave launch never gets source 3:
+// an EKV_FUSED_ORDER_RULE that names it is ignored there (the slot rule stays).
 int ekv_decode_fused_order(int head_dim, int rep, bool scored, bool slot_rows, int nw, int64_t n_heads_in_launch, int phys_extent);
 // Resident rows of a one-launch decode step (the kernel field: bits 16-23 of EkvAttnArgs.fused_order, EKV_RESIDENT_ROWS): the physical
 // rows [0, result) of every head are read with default-policy loads, so that they stay in the Infinity Cache from one step to the next;
@@ -46,7 +53,7 @@ EkvScoreArgs score_args(const ekv_bank* bank, const ekv_step* st, const EkvStepP
 // long_rows: the plan of a long call (ekv_long_*; the rule is stated once, at ekv_plan_step in ekv_plan.cpp)
 // capped: the plan of a capped call (ekv_cap_*; the rule is stated once, at resolve_call in ekv_plan.cpp); a sink call (ekv_sink_*) tiles
 // its chunk steps by the same rule and passes true as well
-int ekv_plan_step(const ekv_bank* bank, const ekv_step* step, EkvStepPlan* P, bool long_rows = false, bool capped = false);
+int ekv_plan_step(const ekv_bank* bank, const ekv_step* step, EkvStepPlan* P, bool long_rows = false, bool capped = false, bool no_orders = false);
 
 // ---- one call path --------------------------------------------------------------------------------------------------------------
 // A call of the step family as its entry points spell it, along two independent axes: the row format of the bank (the untyped / _typed

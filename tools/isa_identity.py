@@ -5,7 +5,8 @@ For every object of each tree's easykv_amd/_build.objects() — plus, in an olde
 lists, its all_objects() / extra_objects() / batch_kv4_objects(), and this tree's added_objects() / later_objects() — the device side is compiled to assembly (hipcc <the build's flags>
 --offload-device-only -S), the compilation-unit id (__hip_cuid_<hex>) is replaced by a constant, and the texts are compared: per
 object, and per kernel symbol where an object has no partner of its name or differs (a file that was split: its kernels are looked up
-in whichever object of the other tree holds them; local label numbers, which count the functions of a file, are dropped for that).
+in whichever object of the other tree holds them; local label numbers, which count the functions of a file, are dropped for that, in
+labels and in the comments that name them).
 One line per object / kernel:  name sha256(parent) sha256(new) lines verdict;  differing texts are shown line by line below their entry.
 The tool only compiles and diffs text.  Host-only objects (.cpp) have no device side and are listed as such."""
 import argparse
@@ -62,7 +63,9 @@ def kernels(text):
         start = next(j for j, l in enumerate(lines) if l.startswith(name + ":"))
         end = next(j for j in range(i, len(lines)) if lines[j].strip() == ".end_amdhsa_kernel")
         body = "\n".join(lines[start:end + 1])
-        found[name] = re.sub(r"\.L(BB|func_begin|func_end|tmp)\d+", r".L\1", body)
+        body = re.sub(r"\.L(BB|func_begin|func_end|tmp)\d+", r".L\1", body)
+        body = re.sub(r"\bBB\d+_", "BB_", body)      # (the same index inside comments: "; in Loop: Header=BB35_4")
+        found[name] = re.sub(r"[ \t]+;", " ;", body)      # (... and the padding in front of a comment, which follows the label's width)
     return found
 
 
