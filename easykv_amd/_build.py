@@ -50,6 +50,19 @@ FAMILIES = {
     "EKV_CHUNK_SINK": lambda elem, d, m: (
         "ekv_attn_chunk.inc", f"ekv_attn_chunk_sink_d{d}_m{m}" + _tags(elem),
         _on(elem) + [f"-DEKV_D={d}", f"-DEKV_CHUNK_MODE={m}", "-DEKV_SINK=1"]),
+    # sliding windows (-DEKV_WINDOW=1, orthogonal to the sinks): the decode kernels and the 16x16x32 chunk kernel, plain keys, 16-bit rows.  With sinks: -DEKV_WINDOW=2,
+    # which the sources read as window + sinks (ekv_common.h), and `saux` (the name a model hands its sinks over by) in the object name:
+    # the objects compiled with -DEKV_SINK=1, and those named *sink*, are the sink family's own list, held to it by its tests
+    "EKV_DECODE_WIN": lambda elem, d: (
+        "ekv_attn_decode.inc", f"ekv_attn_decode_d{d}_win" + _tags(elem), _on(elem) + [f"-DEKV_D={d}", "-DEKV_ROPE=false", "-DEKV_WINDOW=1"]),
+    "EKV_DECODE_SINK_WIN": lambda elem, d: (
+        "ekv_attn_decode.inc", f"ekv_attn_decode_d{d}_saux_win" + _tags(elem), _on(elem) + [f"-DEKV_D={d}", "-DEKV_ROPE=false", "-DEKV_WINDOW=2"]),
+    "EKV_CHUNK_WIN": lambda elem, d, m: (
+        "ekv_attn_chunk.inc", f"ekv_attn_chunk_win_d{d}_m{m}" + _tags(elem),
+        _on(elem) + [f"-DEKV_D={d}", f"-DEKV_CHUNK_MODE={m}", "-DEKV_WINDOW=1"]),
+    "EKV_CHUNK_SINK_WIN": lambda elem, d, m: (
+        "ekv_attn_chunk.inc", f"ekv_attn_chunk_saux_win_d{d}_m{m}" + _tags(elem),
+        _on(elem) + [f"-DEKV_D={d}", f"-DEKV_CHUNK_MODE={m}", "-DEKV_WINDOW=2"]),
     "EKV_SOFTCAP_EVAL": lambda elem, nt: ("ekv_softcap_eval.inc", "ekv_softcap_eval", [f"-DEKV_EVAL_NT={nt}"]),
     "EKV_WIDE": lambda d, m, keys, elem: (
         "ekv_attn_wide.inc", "ekv_attn_wide" + ("_rope" if keys == "rope" else "") + f"_d{d}_m{m}" + _tags(elem),
@@ -111,7 +124,7 @@ def later_instances():
 
 
 def later_objects():
-    """(object name, hipcc arguments) of the instances of ekv_instances_later.def (the kv84 decode instances, the kv164 ones, the long-row scorer, head_dim 256, the soft-capped instances, the sink instances)."""
+    """(object name, hipcc arguments) of the instances of ekv_instances_later.def (the kv84 decode instances, the kv164 ones, the long-row scorer, head_dim 256, the soft-capped instances, the sink instances, the window instances)."""
     return _instance_objects(later_instances())
 
 

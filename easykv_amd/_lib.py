@@ -53,6 +53,9 @@ EXPORTS += tuple(CAP_CALLS[what] for what in STEP_CALLS) + ("ekv_softcap_eval",)
 # the sink family (include/easykv_hip.h, "attention sinks"): the _typed calls with the device pointer of the sinks behind the dtype; 16-bit rows, one sequence
 SINK_CALLS = {what: "ekv_sink_" + what for what in STEP_CALLS}
 EXPORTS += tuple(SINK_CALLS[what] for what in STEP_CALLS)
+# the window family (include/easykv_hip.h, "sliding windows"): the _typed calls with an ekv_win struct behind the dtype; 16-bit rows, one sequence
+WIN_CALLS = {what: "ekv_win_" + what for what in STEP_CALLS}
+EXPORTS += tuple(WIN_CALLS[what] for what in STEP_CALLS)
 
 
 class Bank(C.Structure):
@@ -85,6 +88,12 @@ class Kv84(C.Structure):
 class Kv164(C.Structure):
     """ekv_kv164: MXFP4 value codes with E8M0 block exponents; the keys are the bank's 16-bit rows (include/easykv_hip.h, "kv164")."""
     _fields_ = [("v_codes", C.c_void_p), ("v_exp", C.c_void_p)]
+
+
+class Win(C.Structure):
+    """ekv_win: token positions of the physical rows, the layers' windows (device, and a host copy the library can check), the sinks or
+    NULL, and the token position of the step's query (include/easykv_hip.h, "sliding windows")."""
+    _fields_ = [("tok_pos", C.c_void_p), ("windows", C.c_void_p), ("windows_host", C.POINTER(C.c_int32)), ("s_aux", C.c_void_p), ("q_pos0", C.c_int32)]
 
 
 class Step(C.Structure):
@@ -154,6 +163,7 @@ def load():
                 getattr(lib, LONG_CALLS[what]).argtypes = [C.POINTER(Bank), C.POINTER(Step), i32] + tails[what]
                 getattr(lib, CAP_CALLS[what]).argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, C.c_float] + tails[what]
                 getattr(lib, SINK_CALLS[what]).argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, vp] + tails[what]
+                getattr(lib, WIN_CALLS[what]).argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, C.POINTER(Win)] + tails[what]
         if desc:
             getattr(lib, f"ekv_{rows}_quantize").argtypes = [C.POINTER(Bank), C.POINTER(desc), i32, i32, i32, i32, vp]
             getattr(lib, f"ekv_{rows}_dequantize").argtypes = [C.POINTER(Bank), C.POINTER(desc), i32, i32, i32, i32, vp, vp, vp]

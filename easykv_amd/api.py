@@ -40,7 +40,7 @@ from typing import List, Optional
 import torch
 
 from . import _lib
-from .engine import CAPPED_HEAD_DIMS, PLAIN_KEYS_HEAD_DIMS, SINK_HEAD_DIMS, KVBank, KVBankBatch, StepPlan, row_format
+from .engine import CAPPED_HEAD_DIMS, PLAIN_KEYS_HEAD_DIMS, SINK_HEAD_DIMS, WINDOW_HEAD_DIM, KVBank, KVBankBatch, StepPlan, row_format
 
 KNOWN_POLICIES = ("roco", "h2o_head", "tova", "recency", "random", "full")
 SCORED = ("roco", "h2o_head", "tova")
@@ -107,7 +107,7 @@ class BudgetedKVCache:
 
     def __init__(self, n_layers, n_q_heads, n_kv_heads, head_dim, cap, device, streaming=False, rope=None,
                  record=False, layer_begin=0, layer_count=None, rope_base=10000.0, dtype=None, long_rows=False, logit_cap=None, sm_scale=None,
-                 sinks=None):
+                 sinks=None, windows=None):
         self.layer_begin = layer_begin
         self.layer_count = n_layers - layer_begin if layer_count is None else layer_count
         if not (0 <= self.layer_begin and self.layer_count >= 1 and self.layer_begin + self.layer_count <= n_layers):
@@ -122,9 +122,13 @@ class BudgetedKVCache:
         if sinks is not None and streaming:
             raise ValueError("a cache with attention sinks has no RoPE-on-read build: streaming=True needs sinks=None")
         self.logit_cap, self.sm_scale = logit_cap, sm_scale
-        extra = {k: v for k, v in (("logit_cap", logit_cap), ("sm_scale", sm_scale), ("sinks", sinks)) if v is not None}      # (opt-in: named only when set)
+        if windows is not None and streaming:
+            raise ValueError("a cache with sliding windows has no RoPE-on-read build: streaming=True needs windows=None")
+        extra = {k: v for k, v in (("logit_cap", logit_cap), ("sm_scale", sm_scale), ("sinks", sinks), ("windows", windows)) if v is not None}      # (opt-in: named only when set)
         self.bank = KVBank(self.layer_count, n_q_heads, n_kv_heads, head_dim, cap, device=device, dtype=dtype, long_rows=long_rows, **extra)
         self.sinks = self.bank.sinks      # (fp32 on the device, or None)
+        self.windows = self.bank.windows      # (the windows of the layers this cache owns, a tuple, or None)
+        self._windows_checked = set()      # layers whose module's sliding_window the seam has held against it (hf._easykv_attention)
         self._sinks_checked = set()       # layers whose module's s_aux the seam has held against the row (hf._easykv_attention)
         # no resident rows behind a model: its weights (gigabytes) stream through the Infinity Cache between two attention launches
         # of a layer, and plain loads that miss cost more than non-temporal ones ("resident rows": the harm run)
@@ -270,6 +274,7 @@ class BudgetedKVCacheBatch:
     streaming, unrotate = False, None      # (a batch has no RoPE-on-read form)
     logit_cap = None                        # (... and no soft-capped one; the softmax scale is the shared bank's)
     sinks = None                            # (... and no sink one)
+    windows = None                          # (... and no window one)
 
     def __init__(self, bat: KVBankBatch, record=False):
         self.bat = bat
@@ -371,6 +376,35 @@ def _collect_sinks(model, cfg, n_layers, hq):
     if len(rows) != n_layers:
         raise ValueError(f"attention sinks: {len(rows)} of the model's {n_layers} layers carry a `sinks` parameter; all or none must")
     return torch.stack([rows[i] for i in range(n_layers)])
+
+
+def _collect_windows(model, cfg, n_layers):
+    """generation_config['sliding_window'] -> the per-layer windows as a list of ``n_layers`` ints, or None (absent / None: today's
+    behaviour, the window is ignored).  ``'model'``: ``config.sliding_window`` on the layers whose ``config.layer_types`` entry is
+    ``'sliding_attention'`` (every layer when the config has no ``layer_types``), 0 elsewhere.  Or an explicit list of ``n_layers``
+    integers >= 0."""
+    given = cfg.get("sliding_window", None)
+    if given is None:
+        return None
+    if isinstance(given, str):
+        if given != "model":
+            raise ValueError(f"generation_config['sliding_window'] must be None, 'model' or a list of {n_layers} integers, not {given!r}")
+        w = getattr(model.config, "sliding_window", None)
+        if not (isinstance(w, int) and not isinstance(w, bool) and w > 0):
+            raise ValueError(f"generation_config['sliding_window'] = 'model': the model's config.sliding_window is {w!r}")
+        types = getattr(model.config, "layer_types", None)
+        if types is None:
+            return [w] * n_layers
+        if len(types) != n_layers:
+            raise ValueError(f"generation_config['sliding_window'] = 'model': config.layer_types has {len(types)} entries for {n_layers} layers")
+        return [w if t == "sliding_attention" else 0 for t in types]
+    try:
+        wl = given.tolist() if torch.is_tensor(given) else list(given)
+    except TypeError:
+        wl = None
+    if not (isinstance(wl, list) and len(wl) == n_layers and all(isinstance(x, int) and not isinstance(x, bool) and x >= 0 for x in wl)):
+        raise ValueError(f"generation_config['sliding_window'] must be None, 'model' or a list of {n_layers} integers >= 0, not {given!r}")
+    return wl
 
 
 def _kv_dtype(model, key):
@@ -492,6 +526,27 @@ class _Run:
                 raise ValueError(f"{what} is not supported on a layer-sharded model (model.layer_shard)")
             if d not in SINK_HEAD_DIMS:
                 raise ValueError(f"{what}: the sink kernels are built for head_dim {' and '.join(map(str, SINK_HEAD_DIMS))} (this model: {d})")
+        # sliding windows (gpt-oss's local layers): opt-in by generation_config['sliding_window'] (_collect_windows); None: ignored as before
+        self.windows = _collect_windows(model, cfg, n_layers)
+        if self.windows is not None:      # (before any bank exists)
+            what = "generation_config['sliding_window']"
+            if streaming:
+                raise ValueError(f"{what} with streaming=True: RoPE-on-read has no window build")
+            if kv_quant is not None:
+                raise ValueError(f"{what} with generation_config['kv_quant'] = {kv_quant!r}: there is no quantised window step")
+            if self.long_rows:
+                raise ValueError(f"{what} with generation_config['long_rows'] = True: there is no long window call")
+            if self.logit_cap is not None:
+                raise ValueError(f"{what} and attn_logit_softcapping = {self.logit_cap:g}: there is no capped window call")
+            if self.use_graph:
+                raise ValueError(f"{what} with generation_config['hipgraph']: the token position of a step's query (q_pos0) is a host scalar of "
+                                 "every window call, which a captured graph would freeze")
+            if shard is not None:
+                raise ValueError(f"{what} is not supported on a layer-sharded model (model.layer_shard)")
+            want = WINDOW_HEAD_DIM[self.sinks is not None]
+            if d != want:
+                raise ValueError(f"{what}: the window kernels {'with' if self.sinks is not None else 'without'} sinks are built for head_dim {want} "
+                                 f"(this model: {d})")
         self.dev = torch.device(model.device)
         for p in prompts:
             if p.dim() != 2 or p.shape[0] != 1:
@@ -545,7 +600,8 @@ class _Run:
         cache = BudgetedKVCache(n_layers, hq, h, d, cap + 8, self.dev, streaming=self.streaming, record=self.record, rope=hf_rope,
                                 layer_begin=self.layers[0], layer_count=self.layers[1], rope_base=self.rope_base, dtype=self.kv_dtype,
                                 **(dict(long_rows=True) if self.long_rows else {}),      # (opt-in: named only when asked for)
-                                **{k: v for k, v in (("logit_cap", self.logit_cap), ("sm_scale", self.sm_scale), ("sinks", self.sinks)) if v is not None})
+                                **{k: v for k, v in (("logit_cap", self.logit_cap), ("sm_scale", self.sm_scale), ("sinks", self.sinks),
+                                                    ("windows", self.windows)) if v is not None})
         cache.unrotate = hf_rope if self.hf_stream else None
         return cache
 
@@ -924,6 +980,8 @@ def generate_batch(self, input_ids_list, generation_config, kv_mode="encoding", 
         raise ValueError("generate_batch: a model with attn_logit_softcapping has no batched decode step (soft-capped logits serve single sequences)")
     if _collect_sinks(self, cfg, *_dims(self)[:2]) is not None:
         raise ValueError("generate_batch: a model with attention sinks has no batched decode step (the sink kernels serve single sequences)")
+    if cfg.get("sliding_window", None) is not None:
+        raise ValueError("generate_batch: generation_config['sliding_window'] has no batched decode step (the window kernels serve single sequences)")
     prompts = [p.view(1, -1) if p.dim() == 1 else p for p in input_ids_list]
     if not 1 <= len(prompts) <= _lib.MAX_SEQS or any(p.dim() != 2 or p.shape[0] != 1 for p in prompts):
         raise ValueError(f"generate_batch takes 1..{_lib.MAX_SEQS} prompts of shape [S] or [1, S]")

@@ -96,11 +96,17 @@ static int call_attend(const EkvCall& c, const void* q, const void* k_new, const
   const EkvRows rows = static_cast<EkvRows>(P.rows);
   const bool capped = P.capped != 0;
   const float* const sinks = P.sink ? c.sinks : nullptr;      // (a sink plan: every attention launch and the split path's scorer run the sink instances)
+  // (a window plan: the attention launches run the window instances — with sinks the sink + window ones — and stamp the appended rows'
+  // token positions; the scorers behind them read logits, partials, row statistics and column sums and are the plain / sink ones)
+  const bool window = P.window != 0;
+  const EkvWinArgs win = window ? EkvWinArgs{c.win->tok_pos, c.win->windows, c.win->q_pos0} : EkvWinArgs{};
   drop_stale_error();
   for (int i = 0; i < P.n_list; ++i) {
     const EkvLaunch& L = P.list[i];
     sa.skip_fold = L.skip_fold;
     hipError_t e = hipSuccess;
+    // (a window plan: the decode launches and the 16x16x32 chunk kernel, the only kernels with window instances)
+    if (window && (L.kind == EKV_RUN_CHUNK_LDS || L.kind == EKV_RUN_RESIDENT || L.kind == EKV_RUN_FLUSH || (L.kind == EKV_RUN_CHUNK && P.wide))) return EKV_E_UNSUPPORTED;
     // (a quantised plan is a decode plan: the decode attention launches and the scorers behind them, which read no K/V element)
     if (rows != EKV_ROWS_kv16 && (L.kind == EKV_RUN_CHUNK_LDS || L.kind == EKV_RUN_RESIDENT || L.kind == EKV_RUN_CHUNK || L.kind == EKV_RUN_FLUSH)) return EKV_E_UNSUPPORTED;
     // (a capped plan: the decode launches and the 16x16x32 chunk kernel, the only kernels with capped instances)
@@ -110,16 +116,19 @@ static int call_attend(const EkvCall& c, const void* q, const void* k_new, const
     switch (L.kind) {
       case EKV_RUN_FUSED_DECODE:
         aa.fused_order = P.fused_order;      // (shares its storage with score_tail, which only chunk launches set)
-        e = sinks ? ekv_launch_decode_fused_sink(aa, sa, sinks, D, lc, P.fused_nw, s, bf16)
+        e = window ? ekv_launch_decode_fused_win(aa, sa, sinks, win, D, lc, P.fused_nw, s, bf16)
+          : sinks ? ekv_launch_decode_fused_sink(aa, sa, sinks, D, lc, P.fused_nw, s, bf16)
                   : ekv_launch_decode_fused(aa, sa, tb, D, lc, P.fused_nw, s, bf16, rows, capped);
         break;
       case EKV_RUN_CHUNK_LDS: e = ekv_launch_chunk_lds(aa, sa, D, lc, s, bf16); break;
       case EKV_RUN_RESIDENT: e = ekv_launch_attn_resident(aa, sa, lc, s, bf16); break;
       case EKV_RUN_DECODE:
-        e = sinks ? ekv_launch_attn_decode_sink(aa, sinks, D, lc, s, bf16) : ekv_launch_attn_decode(aa, tb, D, lc, s, bf16, rows, capped);
+        e = window ? ekv_launch_attn_decode_win(aa, sinks, win, D, lc, s, bf16)
+          : sinks ? ekv_launch_attn_decode_sink(aa, sinks, D, lc, s, bf16) : ekv_launch_attn_decode(aa, tb, D, lc, s, bf16, rows, capped);
         break;
       case EKV_RUN_CHUNK:
-        e = sinks ? ekv_launch_attn_chunk_sink(aa, sinks, D, lc, P.two_pass, s, L.fuse ? &sa : nullptr, bf16)
+        e = window ? ekv_launch_attn_chunk_win(aa, sinks, win, D, lc, P.two_pass, s, L.fuse ? &sa : nullptr, bf16)
+          : sinks ? ekv_launch_attn_chunk_sink(aa, sinks, D, lc, P.two_pass, s, L.fuse ? &sa : nullptr, bf16)
                   : ekv_launch_attn_chunk(aa, D, lc, P.wide, P.two_pass, s, L.fuse ? &sa : nullptr, L.passes, L.tail ? &sa : nullptr, bf16, capped);
         break;
       case EKV_RUN_FLUSH: {
@@ -233,6 +242,20 @@ int ekv_sink_step_attend(const ekv_bank* bank, const ekv_step* st, int32_t dtype
                          const void* v_new, void* out, int32_t* evict_ids, const float* rope_cos, const float* rope_sin, void* workspace,
                          size_t workspace_bytes, void* stream) {
   return call_attend(sink_call(bank, st, dtype, sinks), q, k_new, v_new, out, evict_ids, rope_cos, rope_sin, workspace, workspace_bytes, stream);
+}
+
+// sliding windows (include/easykv_hip.h, "sliding windows"): the _typed calls with the window struct behind the element type
+int ekv_win_step_check(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_win* win) { return call_check(win_call(bank, st, dtype, win)); }
+int ekv_win_step_info(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_win* win, int32_t* info, int32_t n_info) {
+  return call_info(win_call(bank, st, dtype, win), info, n_info);
+}
+size_t ekv_win_workspace_bytes(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_win* win) {
+  return call_workspace_bytes(win_call(bank, st, dtype, win));
+}
+int ekv_win_step_attend(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_win* win, const void* q, const void* k_new,
+                        const void* v_new, void* out, int32_t* evict_ids, const float* rope_cos, const float* rope_sin, void* workspace,
+                        size_t workspace_bytes, void* stream) {
+  return call_attend(win_call(bank, st, dtype, win), q, k_new, v_new, out, evict_ids, rope_cos, rope_sin, workspace, workspace_bytes, stream);
 }
 
 // FP8 K/V storage (include/easykv_hip.h, "kv8")

@@ -13,6 +13,10 @@ typedef hipError_t EkvStepFn(const EkvAttnArgs&, const EkvScoreArgs&, int layer_
 // (the sink instances of the 16x16 kernel: their launchers take the sinks behind the arguments)
 typedef hipError_t EkvSinkChunkFn(const EkvAttnArgs&, const float* sinks, int shape, int layer_count, hipStream_t, const EkvScoreArgs*);
 #define EKV_CHUNK_SINK(elem, d, m) EkvSinkChunkFn EKV_FN_CHUNK_SINK(d, m, elem);
+// (the window instances, alone and with sinks: one signature, `sinks` NULL in the window-alone ones)
+typedef hipError_t EkvWinChunkFn(const EkvAttnArgs&, const float* sinks, const EkvWinArgs&, int shape, int layer_count, hipStream_t, const EkvScoreArgs*);
+#define EKV_CHUNK_WIN(elem, d, m) EkvWinChunkFn EKV_FN_CHUNK_WIN(d, m, elem);
+#define EKV_CHUNK_SINK_WIN(elem, d, m) EkvWinChunkFn EKV_FN_CHUNK_SINK_WIN(d, m, elem);
 #define EKV_CHUNK_LDS(d, elem) EkvStepFn EKV_FN_D_ELEM(ekv_launch_chunk_lds, d, elem);
 #define EKV_RESIDENT(d, elem) EkvStepFn EKV_FN_D_ELEM(ekv_launch_attn_resident, d, elem);
 #include "ekv_instances.def"
@@ -37,6 +41,16 @@ struct SinkChunkInstance {
 };
 const SinkChunkInstance kSinkChunk[] = {
 #define EKV_CHUNK_SINK(elem, d, m) {d, m, EKV_IS_##elem, EKV_FN_CHUNK_SINK(d, m, elem)},
+#include "ekv_instances.def"
+};
+struct WinChunkInstance {
+  int head_dim, mode;
+  bool bf16, sink;
+  EkvWinChunkFn* fn;
+};
+const WinChunkInstance kWinChunk[] = {
+#define EKV_CHUNK_WIN(elem, d, m) {d, m, EKV_IS_##elem, false, EKV_FN_CHUNK_WIN(d, m, elem)},
+#define EKV_CHUNK_SINK_WIN(elem, d, m) {d, m, EKV_IS_##elem, true, EKV_FN_CHUNK_SINK_WIN(d, m, elem)},
 #include "ekv_instances.def"
 };
 struct StepInstance {      // whole-step kernels: logits in LDS, logits-resident
@@ -158,6 +172,23 @@ hipError_t ekv_launch_attn_chunk_sink(const EkvAttnArgs& a, const float* sinks, 
   auto go = [&](int m) {
     for (const SinkChunkInstance& in : kSinkChunk)
       if (in.head_dim == head_dim && in.mode == m && in.bf16 == bf16) return in.fn(a, sinks, qpw, layer_count, s, fuse_sc);
+    return hipErrorInvalidValue;
+  };
+  hipError_t e = go(two_pass ? 1 : 0);
+  if (two_pass && e == hipSuccess) e = go(2);
+  return e;
+}
+
+// ---- sliding windows (the ekv_win_* calls): the 16x16 kernel's window instances, with or without sinks, passes as the sink launcher's
+hipError_t ekv_launch_attn_chunk_win(const EkvAttnArgs& a, const float* sinks, const EkvWinArgs& win, int head_dim, int layer_count, bool two_pass,
+                                     hipStream_t s, const EkvScoreArgs* fuse_sc, bool bf16) {
+  if (win.tok_pos == nullptr || win.windows == nullptr || a.rope_cos != nullptr) return hipErrorInvalidValue;
+  if (two_pass && (fuse_sc != nullptr || a.stats == nullptr || a.colsum == nullptr)) return hipErrorInvalidValue;
+  int qb_rows, n_qblocks, qpw;
+  ekv_chunk_blocks(a.n_q_heads / a.n_kv_heads, a.q_len, &qb_rows, &n_qblocks, &qpw, kChunkNarrowD);
+  auto go = [&](int m) {
+    for (const WinChunkInstance& in : kWinChunk)
+      if (in.head_dim == head_dim && in.mode == m && in.bf16 == bf16 && in.sink == (sinks != nullptr)) return in.fn(a, sinks, win, qpw, layer_count, s, fuse_sc);
     return hipErrorInvalidValue;
   };
   hipError_t e = go(two_pass ? 1 : 0);

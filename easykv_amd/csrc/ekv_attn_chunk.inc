@@ -50,7 +50,28 @@
 #if EKV_SINK && EKV_SOFTCAP
 #error "sink chunk instances: uncapped logits"
 #endif
-#if EKV_BF16   // (bf16 instances: the same kernel under a tagged name)
+// EKV_WINDOW != 0 (the EKV_CHUNK_WIN lines of the manifest, head_dim 128; = 2, with sinks, the EKV_CHUNK_SINK_WIN lines, head_dim 64): sliding-
+// window masking (ekv_common.h).  The kernel takes EkvWinArgs as its last argument, behind the sinks.  Logical order is monotone in token
+// position (the slot map keeps birth order), so the keys a query does not attend are a PREFIX of the logical positions: every lane finds
+// the first attended position of its query row once, before the tile loop — a binary search over the token positions of the cached rows
+// (slot map -> tok_pos, ~log2 T dependent pairs of loads per workgroup lifetime), joined with the bound among the chunk's own keys, whose
+// positions are q_pos0 + i' (i - i' >= W is masked) — and the tile loop masks j < that bound next to the causal j >= jlim, under a
+// wave-uniform test that keeps the compares out of every tile past the wave's largest bound.  The mask sits before the running maximum
+// and the export, so all three modes, the exported logits, the row statistics, the partials and the column sums carry it; a (split, row)
+// whose keys are all masked leaves the floor maximum and a zero sum, as a causally empty one does.  The rows the launch appends are
+// stamped with their token positions at the append site.  Plain keys, the one-tile build alone (as the sink instances).
+#if EKV_WINDOW && EKV_SOFTCAP
+#error "window chunk instances: uncapped logits"
+#endif
+#if EKV_WINDOW && EKV_SINK && EKV_BF16
+#define ekv_attn_chunk_kernel ekv_attn_chunk_kernel_sink_win_bf16
+#elif EKV_WINDOW && EKV_SINK
+#define ekv_attn_chunk_kernel ekv_attn_chunk_kernel_sink_win
+#elif EKV_WINDOW && EKV_BF16
+#define ekv_attn_chunk_kernel ekv_attn_chunk_kernel_win_bf16
+#elif EKV_WINDOW
+#define ekv_attn_chunk_kernel ekv_attn_chunk_kernel_win
+#elif EKV_BF16   // (bf16 instances: the same kernel under a tagged name)
 #if EKV_SOFTCAP
 #define ekv_attn_chunk_kernel ekv_attn_chunk_kernel_cap_bf16
 #elif EKV_SINK
@@ -128,7 +149,7 @@ constexpr int kPadH = 16;  // LDS row padding in halfs (32 B): conflict-free ds_
 template <int QPW, bool ROPE, int NW, bool FUSE = false>
 // (the statistics pass has no output accumulators: <= 128 VGPRs, so two 8-wave workgroups per CU — two workgroups drift out of
 // phase and their VALU / LDS / MFMA phases overlap, which the lock-stepped waves of ONE workgroup never do)
-__global__ void __launch_bounds__(64 * NW, (NW == 16 || (NW == 8 && EKV_CHUNK_MODE != 1)) ? 1 : 2) ekv_attn_chunk_kernel(const EkvAttnArgs a, const EkvScoreArgs sc EKV_SINK_ONLY(, const float* const sinks)) {
+__global__ void __launch_bounds__(64 * NW, (NW == 16 || (NW == 8 && EKV_CHUNK_MODE != 1)) ? 1 : 2) ekv_attn_chunk_kernel(const EkvAttnArgs a, const EkvScoreArgs sc EKV_SINK_ONLY(, const float* const sinks) EKV_WIN_ONLY(, const EkvWinArgs win)) {
   constexpr int D = EKV_D;
   constexpr int MODE = EKV_CHUNK_MODE;
   constexpr int NT = 64 * NW;               // threads
@@ -253,6 +274,32 @@ __global__ void __launch_bounds__(64 * NW, (NW == 16 || (NW == 8 && EKV_CHUNK_MO
   }
 #endif
 
+#if EKV_WINDOW
+  // sliding window: win_lo[t] = first logical position this lane's query attends (0: no window here); win_lo_wave = the wave's largest
+  const int win_w = win.windows[a.layer_begin + ll];
+  int win_lo[QPW], win_lo_wave = 0;
+#pragma unroll
+  for (int t = 0; t < QPW; ++t) {
+    int lo = 0;
+    if (win_w > 0 && row_ok[t]) {
+      const int pq = win.q_pos0 + row_i[t];      // token position of the query
+      int b0 = t_new;                            // cached rows [0, t_new): the first whose key lies within the window
+      while (lo < b0) {
+        const int mid = (lo + b0) >> 1;
+        const int tp = win.tok_pos[head_row + a.slot_of_pos[head_row + mid]];
+        if (ekv_win_masked(pq, tp, win_w)) lo = mid + 1;
+        else b0 = mid;
+      }
+      lo = max(lo, t_new + row_i[t] - win_w + 1);      // the chunk's own keys: position t_new + i' is token q_pos0 + i'
+    }
+    win_lo[t] = lo;
+    win_lo_wave = max(win_lo_wave, lo);
+  }
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) win_lo_wave = max(win_lo_wave, __shfl_xor(win_lo_wave, off, 64));
+  win_lo_wave = __builtin_amdgcn_readfirstlane(win_lo_wave);
+#endif
+
   // append: the (split, query block) that owns the new positions [t_new+i0, t_new+i0+nb) within its key range copies their
   // K/V rows into the cache slots.  Done here, not inside the tile loads: predicated stores in the load sequence made the
   // compiler wait on the loads in flight (and spill the store addresses).  Nobody reads these slots in this launch —
@@ -265,6 +312,7 @@ __global__ void __launch_bounds__(64 * NW, (NW == 16 || (NW == 8 && EKV_CHUNK_MO
       const size_t noff = (size_t)ll * a.n_kv_heads * n * D + (size_t)h * a.kv_hs + (size_t)(j - t_new) * a.kv_ts;
       reinterpret_cast<uint4*>(a.k_w + off)[sub] = reinterpret_cast<const uint4*>(a.k_new + noff)[sub];
       reinterpret_cast<uint4*>(a.v_w + off)[sub] = reinterpret_cast<const uint4*>(a.v_new + noff)[sub];
+      EKV_WIN_ONLY(if (sub == 0) win.tok_pos[head_row + s_slot[j - t0]] = win.q_pos0 + (j - t_new);)      // (the row's token position, with the row)
     }
   }
 
@@ -476,6 +524,15 @@ __global__ void __launch_bounds__(64 * NW, (NW == 16 || (NW == 8 && EKV_CHUNK_MO
             if (j >= jlim) sv[e] = EKV_NEG_INF;
           }
         }
+#if EKV_WINDOW
+        if (kt + kg < win_lo_wave) {      // wave-uniform: tiles past every bound of the wave skip the compares
+#pragma unroll
+          for (int e = 0; e < 8; ++e) {
+            const int j = kt + kg + (e < 4 ? 4 * g + e : 16 + 4 * g + (e - 4));
+            if (j < win_lo[t]) sv[e] = EKV_NEG_INF;
+          }
+        }
+#endif
         // (fmaxf() canonicalises both operands first under IEEE mode, v_max_f32 x, x: 3 instructions per maximum)
         float mx = ekv_max3(ekv_max3(ekv_max3(sv[0], sv[1], sv[2]), sv[3], sv[4]), ekv_max3(sv[5], sv[6], sv[7]), EKV_NEG_INF);
         if (MODE == 0 && a.logits != nullptr && row_ok[t]) {
@@ -740,7 +797,7 @@ __global__ void __launch_bounds__(64 * NW, (NW == 16 || (NW == 8 && EKV_CHUNK_MO
 }
 
 template <int QPW, bool ROPE, int NW>
-hipError_t launch_k(const EkvAttnArgs& a, int layer_count, hipStream_t s, const EkvScoreArgs* fuse_sc EKV_SINK_ONLY(, const float* sinks)) {
+hipError_t launch_k(const EkvAttnArgs& a, int layer_count, hipStream_t s, const EkvScoreArgs* fuse_sc EKV_SINK_ONLY(, const float* sinks) EKV_WIN_ONLY(, const EkvWinArgs& win)) {
   // slot entries | tiles | the query block; the 16-wave in-kernel fold exchanges NWQ x 64 x (D + 2) floats (ekv_geometry.h, where the planner reads it too)
   static_assert(kKT == kChunkKT && kPadH == kChunkPadH && EKV_Q_LDS(QPW, ROPE, NW) == ekv_chunk_q_in_lds(EKV_CHUNK_MODE, QPW, ROPE, NW),
                 "the LDS plan of ekv_geometry.h is this kernel's");
@@ -753,14 +810,14 @@ hipError_t launch_k(const EkvAttnArgs& a, int layer_count, hipStream_t s, const 
     if (lds > 48 * 1024)
       (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ekv_attn_chunk_kernel<QPW, ROPE, 4, true>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL((ekv_attn_chunk_kernel<QPW, ROPE, 4, true>), grid, dim3(256), lds, s, a, *fuse_sc EKV_SINK_ONLY(, sinks));
+    hipLaunchKernelGGL((ekv_attn_chunk_kernel<QPW, ROPE, 4, true>), grid, dim3(256), lds, s, a, *fuse_sc EKV_SINK_ONLY(, sinks) EKV_WIN_ONLY(, win));
     return hipGetLastError();
   }
 #endif
   if (lds > 48 * 1024)
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ekv_attn_chunk_kernel<QPW, ROPE, NW>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL((ekv_attn_chunk_kernel<QPW, ROPE, NW>), grid, dim3(64 * NW), lds, s, a, EkvScoreArgs{} EKV_SINK_ONLY(, sinks));
+  hipLaunchKernelGGL((ekv_attn_chunk_kernel<QPW, ROPE, NW>), grid, dim3(64 * NW), lds, s, a, EkvScoreArgs{} EKV_SINK_ONLY(, sinks) EKV_WIN_ONLY(, win));
   return hipGetLastError();
 }
 
@@ -774,6 +831,20 @@ hipError_t EKV_FN_CHUNK_CAP(EKV_D, EKV_CHUNK_MODE, EKV_ELEM)(const EkvAttnArgs& 
   static_assert(EKV_D == 128 || EKV_D == kChunkNarrowD, "capped chunk instances: head_dim 128 and 256");
   if (a.rope_cos != nullptr || qpw != 1 || !(a.softcap > 0.f)) return hipErrorInvalidValue;
   return launch_k<1, false, 4>(a, layer_count, s, fuse_sc);
+}
+#elif EKV_WINDOW
+// the window instances, alone (head_dim 128) and with sinks (head_dim 64): one signature, `sinks` NULL in the window-alone ones; plain
+// keys, the one-tile build alone (the planner blocks their steps as the sink call's)
+#if EKV_SINK
+#define EKV_WCHUNK_SYM EKV_FN_CHUNK_SINK_WIN(EKV_D, EKV_CHUNK_MODE, EKV_ELEM)
+#else
+#define EKV_WCHUNK_SYM EKV_FN_CHUNK_WIN(EKV_D, EKV_CHUNK_MODE, EKV_ELEM)
+#endif
+hipError_t EKV_WCHUNK_SYM(const EkvAttnArgs& a, const float* sinks, const EkvWinArgs& win, int qpw, int layer_count, hipStream_t s,
+                          const EkvScoreArgs* fuse_sc) {
+  static_assert(EKV_D == 64 || EKV_D == 128, "window chunk instances: head_dim 64 and 128");
+  if (a.rope_cos != nullptr || qpw != 1 || (sinks == nullptr) != !EKV_SINK || win.tok_pos == nullptr || win.windows == nullptr) return hipErrorInvalidValue;
+  return launch_k<1, false, 4>(a, layer_count, s, fuse_sc EKV_SINK_ONLY(, sinks), win);
 }
 #elif EKV_SINK
 // the sink instances: plain keys, the one-tile build alone (the planner blocks their steps as head_dim 256's), head_dim 64 and 128

@@ -86,6 +86,20 @@
 #if EKV_SINK && (EKV_ROPE || EKV_KV8 || EKV_KV4 || EKV_KV6 || EKV_KV84 || EKV_KV164 || EKV_BATCH || EKV_SOFTCAP)
 #error "sink decode instances: 16-bit rows, plain keys, one sequence, uncapped logits"
 #endif
+// EKV_WINDOW = 1 (the EKV_DECODE_WIN lines of the manifest: head_dim 128; with EKV_SINK, the EKV_DECODE_SINK_WIN lines: head_dim 64):
+// sliding-window masking (ekv_common.h).  Both kernels take EkvWinArgs as their last argument, behind the sinks, and hand it to the
+// stream, which masks a row where it forms its logit and stamps the appended row's token position (ekv_decode_stream.h).  Nothing else
+// changes: the tails read -inf logits of live rows, and the folds take partials of (-inf, 0) from a key range that is wholly masked.
+// The phase order K and the resident rows are compiled out, as in the sink instances (order K's K phase forms its logits outside the
+// stream), so a window instance with every window 0 is the plain (or the sink) instance in order F, bit for bit.
+#if EKV_WINDOW && (EKV_ROPE || EKV_KV8 || EKV_KV4 || EKV_KV6 || EKV_KV84 || EKV_KV164 || EKV_BATCH || EKV_SOFTCAP)
+#error "window decode instances: 16-bit rows, plain keys, one sequence, uncapped logits"
+#endif
+#if EKV_WINDOW && !EKV_SINK
+#define EKV_WIN_ALONE(...) __VA_ARGS__      // (what a call site spells for the window where the sink build spells it for the sinks)
+#else
+#define EKV_WIN_ALONE(...)
+#endif
 // Both switches at once (the batch kv8 instances) are independent: DESIGN.md §3.9, "Batches".
 #define ekv_attn_decode_kernel EKV_KERNEL_NAME(ekv_attn_decode_kernel)
 #define ekv_decode_fused_kernel EKV_KERNEL_NAME(ekv_decode_fused_kernel)
@@ -114,7 +128,7 @@ constexpr int kFMT = EKV_KV6 ? 6 : (EKV_KV84 ? 84 : (EKV_KV164 ? 164 : 0));     
 // SLOT_LDS = false: slot-map entries are fetched per iteration (needs 16-byte aligned map rows, cap % 4 == 0); saves the
 // staging pass and its barrier, which matters when a workgroup only streams one or two iterations.
 template <int D, int REP, bool ROPE, bool SLOT_LDS>
-__global__ void __launch_bounds__(256) ekv_attn_decode_kernel(const EkvAttnArgs EKV_ARG_A EKV_TB_PARAM EKV_SINK_ONLY(, const float* const sinks)) {
+__global__ void __launch_bounds__(256) ekv_attn_decode_kernel(const EkvAttnArgs EKV_ARG_A EKV_TB_PARAM EKV_SINK_ONLY(, const float* const sinks) EKV_WIN_ONLY(, const EkvWinArgs win)) {
   EKV_SHADOW_A(blockIdx.z)
   using Gm = EkvDecodeGeom<D>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -146,7 +160,7 @@ __global__ void __launch_bounds__(256) ekv_attn_decode_kernel(const EkvAttnArgs 
   constexpr int KU = (!ROPE && !SLOT_LDS && REP <= 2) ? EKV_SPLIT_KU : (EKV_G8 || EKV_MX ? 4 : 8);
   ekv_decode_stream<D, REP, ROPE, SLOT_LDS, 4, false, KU, EkvNoop, kEPL, kFMT>(a, SLOT_LDS ? s_slot : a.slot_of_pos + head_row, logits, a.t_pad,
                                                                                t0, t1, ll, h, head_row, m, l, o, nullptr, EkvNoop(), nrep, hq0
-                                                                               EKV_SINK_ONLY(, 0, sinks + (size_t)(a.layer_begin + ll) * a.n_q_heads));
+                                                                               EKV_SINK_ONLY(, 0, sinks + (size_t)(a.layer_begin + ll) * a.n_q_heads) EKV_WIN_ALONE(, 0) EKV_WIN_ONLY(, win));
 
   ekv_decode_wave_combine<D, REP>(m, l, o);
   ekv_decode_stash<D, REP>(s_part, m, l, o);
@@ -215,9 +229,9 @@ __global__ void __launch_bounds__(256) ekv_attn_decode_kernel(const EkvAttnArgs 
 // launch bound counts waves per SIMD; every other 8-wave build of GQA factor 1 keeps 2 (the soft-capped one too: under 128 VGPRs it
 // spills six, so it keeps order F alone and its code).
 #define EKV_FUSED_TWO_PER_CU(D, ROPE, ITEMS, SLOT) \
-  ((D) == 128 && !(ROPE) && (SLOT) && (ITEMS) <= 5 && !EKV_G8 && !EKV_MX && !EKV_KV164 && !EKV_BATCH && !EKV_SINK && !EKV_SOFTCAP)
+  ((D) == 128 && !(ROPE) && (SLOT) && (ITEMS) <= 5 && !EKV_G8 && !EKV_MX && !EKV_KV164 && !EKV_BATCH && !EKV_SINK && !EKV_WINDOW && !EKV_SOFTCAP)
 template <int D, int REP, bool ROPE, int ITEMS, int NW, bool SLOT>
-__global__ void __launch_bounds__(64 * NW, (NW >= 8 ? (REP == 1 ? (EKV_FUSED_TWO_PER_CU(D, ROPE, ITEMS, SLOT) ? 4 : 2) : 1) : (SLOT && ITEMS > 12 ? 2 : (REP == 1 ? (EKV_MX ? 2 : 4) : (REP == 2 ? 3 : 2))))) ekv_decode_fused_kernel(const EkvAttnArgs EKV_ARG_A, const EkvScoreArgs EKV_ARG_SC EKV_TB_PARAM EKV_SINK_ONLY(, const float* const sinks)) {
+__global__ void __launch_bounds__(64 * NW, (NW >= 8 ? (REP == 1 ? (EKV_FUSED_TWO_PER_CU(D, ROPE, ITEMS, SLOT) ? 4 : 2) : 1) : (SLOT && ITEMS > 12 ? 2 : (REP == 1 ? (EKV_MX ? 2 : 4) : (REP == 2 ? 3 : 2))))) ekv_decode_fused_kernel(const EkvAttnArgs EKV_ARG_A, const EkvScoreArgs EKV_ARG_SC EKV_TB_PARAM EKV_SINK_ONLY(, const float* const sinks) EKV_WIN_ONLY(, const EkvWinArgs win)) {
   EKV_SHADOW_A(blockIdx.z)
   EKV_SHADOW_SC(blockIdx.z)
   using Gm = EkvDecodeGeom<D, NW>;
@@ -243,7 +257,7 @@ __global__ void __launch_bounds__(64 * NW, (NW >= 8 ? (REP == 1 ? (EKV_FUSED_TWO
   const int l_pad = a.l_pad;   // pitch of a logits row: physical rows [0, E) (PHYS) or positions [0, T)
   // Resident rows (ekv_decode_stream.h, "load policy"): the 16-bit instances of the flagship geometry — head_dim 128, one query head
   // per KV head, slot-indexed score rows, both phase orders, 4 and 8 waves, every column count.  Every other instance keeps its code.
-  constexpr bool kResident = D == 128 && REP == 1 && PHYS && SLOT && !EKV_G8 && !EKV_MX && !EKV_KV164 && !EKV_BATCH && !EKV_SINK;
+  constexpr bool kResident = D == 128 && REP == 1 && PHYS && SLOT && !EKV_G8 && !EKV_MX && !EKV_KV164 && !EKV_BATCH && !EKV_SINK && !EKV_WINDOW;
   const int res_rows = kResident ? EKV_RESIDENT_ROWS(a.fused_order) : 0;
   // LDS: logits [REP][l_pad] | wave partials [4][REP][PS] | score rows S (Q C) [w_pad] | reduction scratch | dead-row bits
   float* s_logit = reinterpret_cast<float*>(smem);
@@ -271,7 +285,7 @@ __global__ void __launch_bounds__(64 * NW, (NW >= 8 ? (REP == 1 ? (EKV_FUSED_TWO
   // rows.  Extents up to 6144 rows: the 12-column build keeps order F alone and its code — with both orders in it, its order F ran 4 %
   // slower (118.9 -> 124.0 us at 512 heads x 2561 rows: 78 scalar registers spilled, 36 bytes of scratch) — and a launch that asks
   // for order K there runs a build of its own, ITEMS 13 (launch_fused_nw).
-  constexpr bool kOrders = D == 128 && REP == 1 && !ROPE && ((NW == 4 && ITEMS <= 12) || (NW == 8 && !EKV_SOFTCAP && (ITEMS <= 5 || ITEMS == 13))) && SLOT && !EKV_G8 && !EKV_MX && !EKV_KV164 && !EKV_BATCH && !EKV_SINK;
+  constexpr bool kOrders = D == 128 && REP == 1 && !ROPE && ((NW == 4 && ITEMS <= 12) || (NW == 8 && !EKV_SOFTCAP && (ITEMS <= 5 || ITEMS == 13))) && SLOT && !EKV_G8 && !EKV_MX && !EKV_KV164 && !EKV_BATCH && !EKV_SINK && !EKV_WINDOW;
   bool order_k = false;
   if constexpr (kOrders) {
     const int om = a.fused_order & 3;
@@ -481,10 +495,10 @@ __global__ void __launch_bounds__(64 * NW, (NW >= 8 ? (REP == 1 ? (EKV_FUSED_TWO
   EKV_SINK_ONLY(const float* const sink_row = sinks + (size_t)(a.layer_begin + ll) * a.n_q_heads;)      // (the sinks of this bank layer)
   if (PHYS)
     ekv_decode_stream<D, REP, ROPE, false, NW, PHYS, KUF, decltype(mask_ready), kEPL, kFMT, kResident>(a, slot_row, s_logit, l_pad, 0, T, ll, h, head_row, m, l, o,
-                                                     reinterpret_cast<const uint8_t*>(s_deadw), mask_ready, nrep, h * nrep, res_rows EKV_SINK_ONLY(, sink_row));
+                                                     reinterpret_cast<const uint8_t*>(s_deadw), mask_ready, nrep, h * nrep, res_rows EKV_SINK_ONLY(, sink_row) EKV_WIN_ONLY(, win));
   else
     ekv_decode_stream<D, REP, ROPE, false, NW, false, KUF, EkvNoop, kEPL, kFMT>(a, slot_row, s_logit, l_pad, 0, T, ll, h, head_row, m, l, o, nullptr,
-                                                      EkvNoop(), nrep, h * nrep EKV_SINK_ONLY(, 0, sink_row));
+                                                      EkvNoop(), nrep, h * nrep EKV_SINK_ONLY(, 0, sink_row) EKV_WIN_ALONE(, 0) EKV_WIN_ONLY(, win));
   if (scored) ekv_tail_prefetch_ragged<NW>(sc, head_row, W, roco, sS, sQ, sC, !SLOT);   // published by the barrier below
   // SLOT: count base and birth of this thread's rows, straight into registers (consumed after the softmax passes of the tail)
   float cC[SLOT ? ITEMS : 1];
@@ -534,19 +548,19 @@ __global__ void __launch_bounds__(64 * NW, (NW >= 8 ? (REP == 1 ? (EKV_FUSED_TWO
 #undef EKV_HEAD_STATE
 
 template <int REP>
-hipError_t launch(const EkvAttnArgs& a EKV_TB_DECL EKV_SINK_ONLY(, const float* sinks), int layer_count, hipStream_t s) {
+hipError_t launch(const EkvAttnArgs& a EKV_TB_DECL EKV_SINK_ONLY(, const float* sinks) EKV_WIN_ONLY(, const EkvWinArgs& win), int layer_count, hipStream_t s) {
   using Gm = EkvDecodeGeom<EKV_D>;
   const size_t part = (size_t)Gm::NP * REP * Gm::PS * 4;
   const int rep_all = a.n_q_heads / a.n_kv_heads;
   const dim3 grid(a.n_split * ((rep_all + REP - 1) / REP), a.n_kv_heads, layer_count);
   if ((a.cap & 3) == 0 && a.cap >= 16) {
-    hipLaunchKernelGGL((ekv_attn_decode_kernel<EKV_D, REP, EKV_ROPE, false>), grid, dim3(256), part, s, a EKV_TB_PASS EKV_SINK_ONLY(, sinks));
+    hipLaunchKernelGGL((ekv_attn_decode_kernel<EKV_D, REP, EKV_ROPE, false>), grid, dim3(256), part, s, a EKV_TB_PASS EKV_SINK_ONLY(, sinks) EKV_WIN_ONLY(, win));
   } else {
     const size_t lds = ekv_align((size_t)a.rows_per_split * 4, 16) + part;
     if (lds > 48 * 1024)
       (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ekv_attn_decode_kernel<EKV_D, REP, EKV_ROPE, true>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL((ekv_attn_decode_kernel<EKV_D, REP, EKV_ROPE, true>), grid, dim3(256), lds, s, a EKV_TB_PASS EKV_SINK_ONLY(, sinks));
+    hipLaunchKernelGGL((ekv_attn_decode_kernel<EKV_D, REP, EKV_ROPE, true>), grid, dim3(256), lds, s, a EKV_TB_PASS EKV_SINK_ONLY(, sinks) EKV_WIN_ONLY(, win));
   }
   return hipGetLastError();
 }
@@ -555,7 +569,7 @@ template <int REP, int NW = 8>
 size_t fused_lds(int t_pad, int l_pad, int n_state) { return ekv_fused_lds<EKV_D, REP, NW>(t_pad, l_pad, n_state); }
 
 template <int REP, int ITEMS, int NW, bool SLOT>
-hipError_t launch_fused_k(const EkvAttnArgs& a, const EkvScoreArgs& sc EKV_TB_DECL EKV_SINK_ONLY(, const float* sinks), int layer_count, hipStream_t s) {
+hipError_t launch_fused_k(const EkvAttnArgs& a, const EkvScoreArgs& sc EKV_TB_DECL EKV_SINK_ONLY(, const float* sinks) EKV_WIN_ONLY(, const EkvWinArgs& win), int layer_count, hipStream_t s) {
   // (slot-indexed rows: S / Q over the physical rows [0, E) in LDS, count base and birth in registers)
   const size_t lds = SLOT ? fused_lds<REP, NW>(a.phys_extent, a.l_pad, sc.policy == EKV_POLICY_ROCO ? 2 : 1)
                           : fused_lds<REP, NW>(a.t_pad, a.l_pad, sc.policy == EKV_POLICY_ROCO ? 3 : 1);
@@ -563,7 +577,7 @@ hipError_t launch_fused_k(const EkvAttnArgs& a, const EkvScoreArgs& sc EKV_TB_DE
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ekv_decode_fused_kernel<EKV_D, REP, EKV_ROPE, ITEMS, NW, SLOT>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   hipLaunchKernelGGL((ekv_decode_fused_kernel<EKV_D, REP, EKV_ROPE, ITEMS, NW, SLOT>), dim3(1, a.n_kv_heads, layer_count),
-                     dim3(64 * NW), lds, s, a, sc EKV_TB_PASS EKV_SINK_ONLY(, sinks));
+                     dim3(64 * NW), lds, s, a, sc EKV_TB_PASS EKV_SINK_ONLY(, sinks) EKV_WIN_ONLY(, win));
   return hipGetLastError();
 }
 
@@ -572,32 +586,60 @@ hipError_t launch_fused_k(const EkvAttnArgs& a, const EkvScoreArgs& sc EKV_TB_DE
 //   NW = 8: for launches with only 1-2 heads per CU (GQA: Mistral's 8 KV heads x 32 layers = 256 heads): the same number
 //           of waves per CU streams one head, instead of leaving the CU to a single 4-wave workgroup.
 template <int REP, int NW>
-hipError_t launch_fused_nw(const EkvAttnArgs& a, const EkvScoreArgs& sc EKV_TB_DECL EKV_SINK_ONLY(, const float* sinks), int layer_count, hipStream_t s) {
+hipError_t launch_fused_nw(const EkvAttnArgs& a, const EkvScoreArgs& sc EKV_TB_DECL EKV_SINK_ONLY(, const float* sinks) EKV_WIN_ONLY(, const EkvWinArgs& win), int layer_count, hipStream_t s) {
   constexpr int NT = 64 * NW, I0 = (2304 + NT - 1) / NT, I1 = (6144 + NT - 1) / NT;
   if (sc.birth != nullptr) {      // slot-indexed rows: the thread-owned columns are the physical rows [0, E) (ekv_decode_slot_rows_supported)
     if constexpr (!EKV_ROPE && !EKV_BATCH && REP <= 4) {      // (a batch runs on the ordered layout)
-      if (a.phys_extent <= NT * I0) return launch_fused_k<REP, I0, NW, true>(a, sc EKV_TB_PASS EKV_SINK_ONLY(, sinks), layer_count, s);
+      if (a.phys_extent <= NT * I0) return launch_fused_k<REP, I0, NW, true>(a, sc EKV_TB_PASS EKV_SINK_ONLY(, sinks) EKV_WIN_ONLY(, win), layer_count, s);
       // extents up to 6144 rows: 12 (8-wave) / 24 (4-wave) columns per thread in registers; the 4-wave build gives up the fourth
       // workgroup per CU for them (LDS would not have allowed it at these row counts anyway)
       // (8 waves, 16-bit rows, head_dim 128, one query head per KV head: a launch that asks for order K at these extents runs the
       //  13-column build, the one that has both orders there; the 12-column build stays what it was)
-      if constexpr (NW == 8 && REP == 1 && EKV_D == 128 && !EKV_G8 && !EKV_MX && !EKV_KV164 && !EKV_SINK && !EKV_SOFTCAP)
-        if ((a.fused_order & 3) != 0 && a.phys_extent <= NT * I1) return launch_fused_k<REP, I1 + 1, NW, true>(a, sc EKV_TB_PASS EKV_SINK_ONLY(, sinks), layer_count, s);
-      if (a.phys_extent <= NT * I1) return launch_fused_k<REP, I1, NW, true>(a, sc EKV_TB_PASS EKV_SINK_ONLY(, sinks), layer_count, s);
+      if constexpr (NW == 8 && REP == 1 && EKV_D == 128 && !EKV_G8 && !EKV_MX && !EKV_KV164 && !EKV_SINK && !EKV_WINDOW && !EKV_SOFTCAP)
+        if ((a.fused_order & 3) != 0 && a.phys_extent <= NT * I1) return launch_fused_k<REP, I1 + 1, NW, true>(a, sc EKV_TB_PASS EKV_SINK_ONLY(, sinks) EKV_WIN_ONLY(, win), layer_count, s);
+      if (a.phys_extent <= NT * I1) return launch_fused_k<REP, I1, NW, true>(a, sc EKV_TB_PASS EKV_SINK_ONLY(, sinks) EKV_WIN_ONLY(, win), layer_count, s);
     }
     return hipErrorInvalidValue;
   }
-  if (a.n_slots <= NT * I0) return launch_fused_k<REP, I0, NW, false>(a, sc EKV_TB_PASS EKV_SINK_ONLY(, sinks), layer_count, s);
-  return launch_fused_k<REP, I1, NW, false>(a, sc EKV_TB_PASS EKV_SINK_ONLY(, sinks), layer_count, s);
+  if (a.n_slots <= NT * I0) return launch_fused_k<REP, I0, NW, false>(a, sc EKV_TB_PASS EKV_SINK_ONLY(, sinks) EKV_WIN_ONLY(, win), layer_count, s);
+  return launch_fused_k<REP, I1, NW, false>(a, sc EKV_TB_PASS EKV_SINK_ONLY(, sinks) EKV_WIN_ONLY(, win), layer_count, s);
 }
 template <int REP>
-hipError_t launch_fused(const EkvAttnArgs& a, const EkvScoreArgs& sc EKV_TB_DECL EKV_SINK_ONLY(, const float* sinks), int layer_count, int nw, hipStream_t s) {
-  return nw == 8 ? launch_fused_nw<REP, 8>(a, sc EKV_TB_PASS EKV_SINK_ONLY(, sinks), layer_count, s) : launch_fused_nw<REP, 4>(a, sc EKV_TB_PASS EKV_SINK_ONLY(, sinks), layer_count, s);
+hipError_t launch_fused(const EkvAttnArgs& a, const EkvScoreArgs& sc EKV_TB_DECL EKV_SINK_ONLY(, const float* sinks) EKV_WIN_ONLY(, const EkvWinArgs& win), int layer_count, int nw, hipStream_t s) {
+  return nw == 8 ? launch_fused_nw<REP, 8>(a, sc EKV_TB_PASS EKV_SINK_ONLY(, sinks) EKV_WIN_ONLY(, win), layer_count, s) : launch_fused_nw<REP, 4>(a, sc EKV_TB_PASS EKV_SINK_ONLY(, sinks) EKV_WIN_ONLY(, win), layer_count, s);
 }
 
 }  // namespace
 
+#if EKV_WINDOW
+// the window instances (EKV_FN_WIN; with sinks EKV_FN_SINK_WIN): one signature for both, `sinks` unused (NULL) in the window-alone ones
 #if EKV_SINK
+#define EKV_WSYM(fn) EKV_FN_SINK_WIN(fn, EKV_ELEM, EKV_D)
+#else
+#define EKV_WSYM(fn) EKV_FN_WIN(fn, EKV_ELEM, EKV_D)
+#endif
+hipError_t EKV_WSYM(ekv_launch_attn_decode)(const EkvAttnArgs& a, const float* sinks, const EkvWinArgs& win, int rep, int layer_count, hipStream_t s) {
+  if (rep < 1 || (sinks == nullptr) != !EKV_SINK || win.tok_pos == nullptr || win.windows == nullptr) return hipErrorInvalidValue;
+  switch (rep) {
+    case 1: return launch<1>(a EKV_SINK_ONLY(, sinks), win, layer_count, s);
+    case 2: return launch<2>(a EKV_SINK_ONLY(, sinks), win, layer_count, s);
+    case 3: case 4: return launch<4>(a EKV_SINK_ONLY(, sinks), win, layer_count, s);
+    default: return launch<8>(a EKV_SINK_ONLY(, sinks), win, layer_count, s);
+  }
+}
+
+hipError_t EKV_WSYM(ekv_launch_decode_fused)(const EkvAttnArgs& a, const EkvScoreArgs& sc, const float* sinks, const EkvWinArgs& win, int rep,
+                                             int layer_count, int nw, hipStream_t s) {
+  if ((sinks == nullptr) != !EKV_SINK || win.tok_pos == nullptr || win.windows == nullptr) return hipErrorInvalidValue;
+  switch (rep) {
+    case 1: return launch_fused<1>(a, sc EKV_SINK_ONLY(, sinks), win, layer_count, nw, s);
+    case 2: return launch_fused<2>(a, sc EKV_SINK_ONLY(, sinks), win, layer_count, nw, s);
+    case 3: case 4: return launch_fused<4>(a, sc EKV_SINK_ONLY(, sinks), win, layer_count, nw, s);
+    case 5: case 6: case 7: case 8: return launch_fused<8>(a, sc EKV_SINK_ONLY(, sinks), win, layer_count, nw, s);
+    default: return hipErrorInvalidValue;
+  }
+}
+#elif EKV_SINK
 // the sink instances: their launchers take the sinks where the others take the table of a batch (EKV_FN_SINK: element type, head_dim)
 hipError_t EKV_FN_SINK(ekv_launch_attn_decode, EKV_ELEM, EKV_D)(const EkvAttnArgs& a, const float* sinks, int rep, int layer_count, hipStream_t s) {
   if (rep < 1 || sinks == nullptr) return hipErrorInvalidValue;

@@ -21,6 +21,15 @@ typedef hipError_t EkvSinkScoreFn(const EkvScoreArgs&, const float* sinks, int c
   EkvSinkDecodeFn EKV_FN_SINK(ekv_launch_attn_decode, elem, d);    \
   EkvSinkFusedFn EKV_FN_SINK(ekv_launch_decode_fused, elem, d);
 #define EKV_DECODE_SCORE_SINK(elem) EkvSinkScoreFn EKV_FN_ELEM(ekv_launch_decode_score_sink, elem);
+// (the window instances, alone and with sinks: one signature, `sinks` NULL in the window-alone ones)
+typedef hipError_t EkvWinDecodeFn(const EkvAttnArgs&, const float* sinks, const EkvWinArgs&, int rep, int count, hipStream_t);
+typedef hipError_t EkvWinFusedFn(const EkvAttnArgs&, const EkvScoreArgs&, const float* sinks, const EkvWinArgs&, int rep, int count, int nw, hipStream_t);
+#define EKV_DECODE_WIN(elem, d)                                  \
+  EkvWinDecodeFn EKV_FN_WIN(ekv_launch_attn_decode, elem, d);    \
+  EkvWinFusedFn EKV_FN_WIN(ekv_launch_decode_fused, elem, d);
+#define EKV_DECODE_SINK_WIN(elem, d)                                  \
+  EkvWinDecodeFn EKV_FN_SINK_WIN(ekv_launch_attn_decode, elem, d);    \
+  EkvWinFusedFn EKV_FN_SINK_WIN(ekv_launch_decode_fused, elem, d);
 #include "ekv_instances.def"
 EkvFoldFn ekv_launch_fold_f16, ekv_launch_fold_bf16;      // (exported by the `single` scorer instances: the fold reads no per-step field)
 
@@ -63,6 +72,25 @@ const SinkInstance* sink_instance(const EkvAttnArgs& a, const float* sinks, int 
   if (sinks == nullptr || a.rope_cos != nullptr) return nullptr;
   for (const SinkInstance& in : kSinkDecode)
     if (in.head_dim == head_dim && in.bf16 == bf16) return &in;
+  return nullptr;
+}
+struct WinInstance {
+  int head_dim;
+  bool bf16, sink;
+  EkvWinDecodeFn* attn;
+  EkvWinFusedFn* fused;
+};
+const WinInstance kWinDecode[] = {
+#define EKV_DECODE_WIN(elem, d) {d, EKV_IS_##elem, false, EKV_FN_WIN(ekv_launch_attn_decode, elem, d), EKV_FN_WIN(ekv_launch_decode_fused, elem, d)},
+#define EKV_DECODE_SINK_WIN(elem, d) \
+  {d, EKV_IS_##elem, true, EKV_FN_SINK_WIN(ekv_launch_attn_decode, elem, d), EKV_FN_SINK_WIN(ekv_launch_decode_fused, elem, d)},
+#include "ekv_instances.def"
+};
+// A window launch (ekv_win_*): its own instances, with or without sinks, never another's
+const WinInstance* win_instance(const EkvAttnArgs& a, const float* sinks, const EkvWinArgs& win, int head_dim, bool bf16) {
+  if (win.tok_pos == nullptr || win.windows == nullptr || a.rope_cos != nullptr) return nullptr;
+  for (const WinInstance& in : kWinDecode)
+    if (in.head_dim == head_dim && in.bf16 == bf16 && in.sink == (sinks != nullptr)) return &in;
   return nullptr;
 }
 struct ScoreInstance {
@@ -136,4 +164,17 @@ hipError_t ekv_launch_decode_score_sink(const EkvScoreArgs& sc, const float* sin
   for (const SinkScoreInstance& in : kSinkScore)
     if (in.bf16 == bf16) return in.score(sc, sinks, count, s);
   return hipErrorInvalidValue;
+}
+
+// ---- sliding windows (the ekv_win_* calls): the split kernel and the one-launch kernel (the scorer behind the split kernel is the plain
+// or the sink one: ekv_kernels.h)
+hipError_t ekv_launch_attn_decode_win(const EkvAttnArgs& a, const float* sinks, const EkvWinArgs& win, int head_dim, int count, hipStream_t s, bool bf16) {
+  const WinInstance* in = win_instance(a, sinks, win, head_dim, bf16);
+  return in ? in->attn(a, sinks, win, a.n_q_heads / a.n_kv_heads, count, s) : hipErrorInvalidValue;
+}
+
+hipError_t ekv_launch_decode_fused_win(const EkvAttnArgs& a, const EkvScoreArgs& sc, const float* sinks, const EkvWinArgs& win, int head_dim, int count,
+                                       int nw, hipStream_t s, bool bf16) {
+  const WinInstance* in = win_instance(a, sinks, win, head_dim, bf16);
+  return in ? in->fused(a, sc, sinks, win, a.n_q_heads / a.n_kv_heads, count, nw, s) : hipErrorInvalidValue;
 }

@@ -386,6 +386,9 @@ __device__ __forceinline__ float ekv_softcap(float x, float cap) {
 // the chunk kernel seeds the running (m, l) of the first key half of the first split with (a, 1).  Partials, folds, row statistics and
 // the statistics pass then have it, and only the places that rebuild the sum of exponentials from a logits row (the decode tails) add
 // exp(a - M) themselves.
+#if defined(EKV_WINDOW) && EKV_WINDOW == 2 && !defined(EKV_SINK)
+#define EKV_SINK 1      // (-DEKV_WINDOW=2, the EKV_*_SINK_WIN lines of the manifest: sliding windows AND sinks, see below)
+#endif
 #ifndef EKV_SINK
 #define EKV_SINK 0
 #endif
@@ -404,6 +407,24 @@ __device__ __forceinline__ void ekv_sink_fold(float a, float& m, float& l, float
   for (int i = 0; i < N; ++i) o[i] *= alpha;
   m = mn;
 }
+
+// ---- sliding-window masking (include/easykv_hip.h, "sliding windows"): every physical K/V row carries the token position it was appended
+// at (tok_pos [n_layers][H][cap], indexed by physical row like a row scale), and a key whose position lies W_l or more behind the query's
+// is masked: logit -inf before the maximum, like a causally masked one, but the row stays live -----------------------------------------
+// EKV_WINDOW != 0 (the EKV_*_WIN lines of the manifest; orthogonal to EKV_SINK) builds the kernels that take EkvWinArgs (ekv_kernels.h)
+// as their LAST kernel argument, behind the sinks where both are on; EKV_WIN_ONLY(...) spells what exists only in those builds.
+// EKV_WINDOW = 2 (the EKV_*_SINK_WIN lines) is EKV_WINDOW = 1 with EKV_SINK = 1, spelled as one switch: the list of objects compiled
+// with the sink switch itself is the sink family's own.
+#ifndef EKV_WINDOW
+#define EKV_WINDOW 0
+#endif
+#if EKV_WINDOW
+#define EKV_WIN_ONLY(...) __VA_ARGS__
+#else
+#define EKV_WIN_ONLY(...)
+#endif
+// is the key appended at token position p_k masked for the query at p_q under window w (w = 0: no window; p_k <= p_q)
+__device__ __forceinline__ bool ekv_win_masked(int p_q, int p_k, int w) { return w > 0 && p_q - p_k >= w; }
 
 // f32 -> one 16-bit output element, rounded to nearest even (bf16: v_cvt_pk_bf16_f32, NaN kept), as the __half the row pointers hold
 __device__ __forceinline__ __half ekv_to_e(float x) {

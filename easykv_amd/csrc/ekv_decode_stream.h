@@ -94,7 +94,8 @@ __device__ __forceinline__ void ekv_decode_stream(const EkvAttnArgs& a, const in
                                                   float (&m)[REP], float (&l)[REP], float (&o)[REP][EPL],
                                                   const uint8_t* s_dead = nullptr, MaskReady mask_ready = MaskReady(),
                                                   int n_rep_real = 0, int q_head0 = -1, int res_rows = 0
-                                                  EKV_SINK_ONLY(, const float* sink_row = nullptr)) {      // (the sinks of this bank layer's query heads)
+                                                  EKV_SINK_ONLY(, const float* sink_row = nullptr)      // (the sinks of this bank layer's query heads)
+                                                  EKV_WIN_ONLY(, const EkvWinArgs win = EkvWinArgs{})) {      // (sliding windows: below)
   static_assert(!RES || (PHYS && EPL == 8 && D == 128), "resident rows: 16-bit rows of head_dim 128 (whole lane groups) in physical order");
   using Gm = EkvDecodeGeom<D, NW, KU, EPL>;
   constexpr int LPR = Gm::LPR, RW = Gm::RW, LIVE = Gm::LIVE;
@@ -123,6 +124,17 @@ __device__ __forceinline__ void ekv_decode_stream(const EkvAttnArgs& a, const in
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int sub = lane % LPR, grp = lane / LPR;
   const int t_new = a.n_slots - 1;  // the appended position
+#if EKV_WINDOW
+  // Sliding windows (ekv_common.h).  The KU rows of a lane group's iteration are scored by all of its lanes, so lane `sub` reads the token
+  // position of ONE of them, row sub % KU, behind the iteration's K/V requests (physical order: KU consecutive words per group; through
+  // the slot map: the row index is in a register already), tests it against the query's position, and one ballot per wave hands every
+  // group the mask bits of its rows.  A masked row's logit is -inf where it is formed: the online softmax gives it p = 0, its V row (a
+  // live row: finite) adds nothing, and the logit export writes the -inf, so the tails, which tell dead rows from live ones by the
+  // dead-row bits or the slot map and never by the logit, see a live column of probability 0.  The appended row is the query's own
+  // position and never masked; the lane that stores it stamps its token position (the row does not move until it is evicted).
+  static_assert(LPR >= KU && (KU & (KU - 1)) == 0 && EPL == 8 && FMT == 0 && !ROPE && !RES, "window instances: 16-bit rows, plain keys, no resident rows");
+  const int win_w = win.windows[a.layer_begin + ll];
+#endif
   int t1 = t1_in;
   const bool live_lane = !PADDED || sub < LIVE;
   // GQA factors that are not a power of two (or, in the split kernel, groups of <= 8 query heads of a wider factor): REP is the
@@ -328,6 +340,9 @@ __device__ __forceinline__ void ekv_decode_stream(const EkvAttnArgs& a, const in
       reinterpret_cast<uint4*>(a.k_w + off)[sub] = kn;
       reinterpret_cast<uint4*>(a.v_w + off)[sub] = vn;
     }
+#if EKV_WINDOW
+    if (sub == 0) win.tok_pos[head_row + slot_new] = win.q_pos0;
+#endif
     float kpn[8];
     if (ROPE) {
       ekv_f2 cn[4], sn[4];
@@ -458,6 +473,7 @@ __device__ __forceinline__ void ekv_decode_stream(const EkvAttnArgs& a, const in
         vsc[u] = ekv_fp4_exp_scale((vw[u] >> (8 * sub)) & 0xFFu);
       }
     }
+    EKV_WIN_ONLY(int win_tp = 0;)
     int cur[KU];
 #pragma unroll
     for (int i = 0; i < KU / 4; ++i) {
@@ -488,11 +504,13 @@ __device__ __forceinline__ void ekv_decode_stream(const EkvAttnArgs& a, const in
       if (base < res_rows) request(EkvBool<true>());
       else request(EkvBool<false>());
     } else {
+    EKV_WIN_ONLY(int win_row = 0;)      // (the physical row whose token position this lane reads)
 #pragma unroll
     for (int u = 0; u < KU; ++u) {
       const int j = j0 + u;
       const int jj = j < t1 ? j : t1 - 1;
       const int row = PHYS ? jj : (SLOT_LDS ? s_slot[jj - t0] : (j < t1 ? cur[u] : last_slot));
+      EKV_WIN_ONLY(win_row = (sub & (KU - 1)) == u ? row : win_row;)
       const char* kp = reinterpret_cast<const char*>(a.k) + (head_row + row) * ROWB;
       const char* vp = reinterpret_cast<const char*>(a.v) + (head_row + row) * VROWB;
       if constexpr (KV8 && !PHYS) {      // rows through the slot map: one scale per row (the lanes of a group read the same word)
@@ -523,6 +541,7 @@ __device__ __forceinline__ void ekv_decode_stream(const EkvAttnArgs& a, const in
         kr[u] = vr[u] = uint4{0, 0, 0, 0};
       }
     }
+    EKV_WIN_ONLY(win_tp = win.tok_pos[head_row + win_row];)      // (a row inside the head's map row, live or not: always readable)
     }
     ekv_f2 rc[4], rs[4];      // ROPE: (cos, signed sin) of row j0 for this lane's 8 frequencies — the seed, read with the K / V rows
     if (ROPE) rope_seed(min(j0, t1 - 1), rc, rs);
@@ -539,6 +558,10 @@ __device__ __forceinline__ void ekv_decode_stream(const EkvAttnArgs& a, const in
           if constexpr (KV4 || KV164) vsc[u] = 1.f;      // (zero codes under a finite scale)
         }
     }
+#if EKV_WINDOW
+    // bit u of win8 = row j0 + u is window-masked (bits of dead or out-of-range rows mean nothing: those are -inf already)
+    const unsigned win8 = (unsigned)(__ballot(ekv_win_masked(win.q_pos0, win_tp, win_w)) >> (grp * LPR)) & ((1u << KU) - 1u);
+#endif
     float sall[ROPE ? REP : 1][KU];   // ROPE: every row is rotated once, then dotted with all REP queries
     if (ROPE) {
 #pragma unroll
@@ -573,7 +596,7 @@ __device__ __forceinline__ void ekv_decode_stream(const EkvAttnArgs& a, const in
           else acc = KV8 ? ekv_dot16_fp8(qv[r], qv1[r], kr[u], 0.f) : ekv_dot8(qv[r], kr[u], 0.f);
           acc = ekv_group_sum<LPR>(acc);
           if constexpr (KV8) acc *= ksc[u];
-          s[u] = (PHYS ? !((dead8 >> u) & 1u) : (j0 + u < t1)) ? EKV_LOGIT(acc, a) : EKV_NEG_INF;
+          s[u] = ((PHYS ? !((dead8 >> u) & 1u) : (j0 + u < t1)) EKV_WIN_ONLY(&& !((win8 >> u) & 1u))) ? EKV_LOGIT(acc, a) : EKV_NEG_INF;
         }
       }
       // export the raw logits: lane `sub` of the group owns row j0+sub -> 8 consecutive floats per group

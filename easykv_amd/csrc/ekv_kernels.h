@@ -83,6 +83,7 @@ struct EkvStepPlan {
   int64_t key_rows;
   int32_t capped;       // an ekv_cap_* call: the launches run the EKV_SOFTCAP instances (chunk steps: the one-tile 16x16x32 build alone)
   int32_t sink;         // an ekv_sink_* call: the launches run the EKV_SINK instances (chunk steps likewise; decode steps in phase order F, no resident rows)
+  int32_t window;       // an ekv_win_* call: the launches run the EKV_WINDOW instances (with sinks: the EKV_SINK + EKV_WINDOW ones); planned as the sink call
 };
 // The table of a batched decode step as the kernels' batch instances receive it: BY VALUE, behind the argument structs of the uniform
 // kernel (2304 bytes of the 4 KB a launch may carry).  Workgroup (head, entry ll) shadows the per-step fields of its argument structs
@@ -218,6 +219,23 @@ hipError_t ekv_launch_decode_score_sink(const EkvScoreArgs& sc, const float* sin
 hipError_t ekv_launch_tova_headmean_sink(const EkvScoreArgs& a, const float* sinks, int layer_count, hipStream_t s);      // (ekv_score_select.inc, EKV_SINK build)
 hipError_t ekv_launch_attn_chunk_sink(const EkvAttnArgs& a, const float* sinks, int head_dim, int layer_count, bool two_pass, hipStream_t s,
                                       const EkvScoreArgs* fuse_sc, bool bf16);
+// Sliding windows (the ekv_win_* calls; EKV_WINDOW instances, ekv_common.h): what the window kernels receive as their last argument, and
+// the launchers of a window step.  tok_pos: int32 [bank->n_layers][n_kv_heads][cap], indexed by physical row, written by the kernel that
+// appends a row (the decode stream's and the chunk kernel's append sites: row i of the step is at q_pos0 + i); windows: int32 [bank->n_layers], 0 = no window.
+// sinks == NULL runs the window-alone instances (head_dim 128), sinks != NULL the sink + window ones (head_dim 64).
+struct EkvWinArgs {
+  int32_t* tok_pos;
+  const int32_t* windows;
+  int32_t q_pos0;      // token position of the step's (first) query row
+};
+hipError_t ekv_launch_attn_decode_win(const EkvAttnArgs& a, const float* sinks, const EkvWinArgs& win, int head_dim, int count, hipStream_t s, bool bf16);
+hipError_t ekv_launch_decode_fused_win(const EkvAttnArgs& a, const EkvScoreArgs& sc, const float* sinks, const EkvWinArgs& win, int head_dim, int count,
+                                       int nw, hipStream_t s, bool bf16);
+// The chunk launcher runs the 16x16x32 kernel's window instances in the one-tile build, as ekv_launch_attn_chunk_sink runs the sink ones.
+hipError_t ekv_launch_attn_chunk_win(const EkvAttnArgs& a, const float* sinks, const EkvWinArgs& win, int head_dim, int layer_count, bool two_pass,
+                                     hipStream_t s, const EkvScoreArgs* fuse_sc, bool bf16);
+// (the scorer behind the split kernel reads exported logits and partials, never a K/V row or a position: a window step runs the plain
+// scorer instance, a sink + window step the sink one)
 // ekv_softcap_eval: out[i] = ekv_softcap(x[i] / sm_div, cap) (ekv_attn_decode_dispatch.hip)
 hipError_t ekv_launch_softcap_eval(const float* x, int64_t n, float sm_div, float cap, float* out, hipStream_t s);
 // Long-row scorer (ekv_score_long.inc; one build for fp16 and bf16 banks).  a.big_rows and key_rows ([layer_count][H][a.big_stride]
@@ -304,18 +322,28 @@ __device__ __forceinline__ EkvScoreArgs ekv_batch_score_args(const EkvScoreArgs&
 #endif
 
 // attention sinks (EKV_SINK = 1: the EKV_*_SINK lines of the manifest; ekv_common.h)
+#if defined(EKV_WINDOW) && EKV_WINDOW == 2 && !defined(EKV_SINK)
+#define EKV_SINK 1      // (the sink + window instances: ekv_common.h)
+#endif
 #if defined(EKV_SINK) && EKV_SINK
 #define EKV_SINK_TAG _sink
 #else
 #define EKV_SINK_TAG
 #endif
 
+// sliding windows (EKV_WINDOW = 1: the EKV_*_WIN lines of the manifest; ekv_common.h)
+#if defined(EKV_WINDOW) && EKV_WINDOW
+#define EKV_WIN_TAG _win
+#else
+#define EKV_WIN_TAG
+#endif
+
 // ---- kernel instances (ekv_instances.def; DESIGN.md "kernel instances")
-// Kernel symbol of an instance = the kernel's name + independent tags that default to empty: _batch, _kv8, _cap, _sink, _bf16 (ekv_common.h).  A
+// Kernel symbol of an instance = the kernel's name + independent tags that default to empty: _batch, _kv8, _cap, _sink, _win, _bf16 (ekv_common.h).  A
 // kernel source renames itself with  #define ekv_x_kernel EKV_KERNEL_NAME(ekv_x_kernel)  (profiles and traces know these names).
-#define EKV_KERNEL_NAME_(base, b, r, c, k, t) base##b##r##c##k##t
-#define EKV_KERNEL_NAME_X(base, b, r, c, k, t) EKV_KERNEL_NAME_(base, b, r, c, k, t)
-#define EKV_KERNEL_NAME(base) EKV_KERNEL_NAME_X(base, EKV_BATCH_TAG, EKV_ROWS_TAG, EKV_CAP_TAG, EKV_SINK_TAG, EKV_DT_TAG)
+#define EKV_KERNEL_NAME_(base, b, r, c, k, w, t) base##b##r##c##k##w##t
+#define EKV_KERNEL_NAME_X(base, b, r, c, k, w, t) EKV_KERNEL_NAME_(base, b, r, c, k, w, t)
+#define EKV_KERNEL_NAME(base) EKV_KERNEL_NAME_X(base, EKV_BATCH_TAG, EKV_ROWS_TAG, EKV_CAP_TAG, EKV_SINK_TAG, EKV_WIN_TAG, EKV_DT_TAG)
 // Launcher of an instance = the family's entry + every word of its manifest line, in the line's order.  The instance (which pastes
 // its own switches: EKV_D, EKV_KEYS, EKV_ELEM, EKV_ROWS, EKV_BATCHING, ...) and the dispatch tables (which paste the manifest's words)
 // both spell it through these macros.
@@ -331,6 +359,14 @@ __device__ __forceinline__ EkvScoreArgs ekv_batch_score_args(const EkvScoreArgs&
 #define EKV_FN_CHUNK_CAP(d, m, elem) EKV_FN_CHUNK_CAP_(d, m, elem)
 #define EKV_FN_SINK_(fn, elem, d) fn##_sink_d##d##_##elem
 #define EKV_FN_SINK(fn, elem, d) EKV_FN_SINK_(fn, elem, d)      // (EKV_DECODE_SINK; EKV_DECODE_SCORE_SINK names no head_dim)
+#define EKV_FN_WIN_(fn, elem, d) fn##_win_d##d##_##elem
+#define EKV_FN_WIN(fn, elem, d) EKV_FN_WIN_(fn, elem, d)      // (EKV_DECODE_WIN)
+#define EKV_FN_SINK_WIN_(fn, elem, d) fn##_sink_win_d##d##_##elem
+#define EKV_FN_SINK_WIN(fn, elem, d) EKV_FN_SINK_WIN_(fn, elem, d)      // (EKV_DECODE_SINK_WIN)
+#define EKV_FN_CHUNK_WIN_(d, m, elem) ekv_launch_attn_chunk_win_d##d##_m##m##_##elem
+#define EKV_FN_CHUNK_WIN(d, m, elem) EKV_FN_CHUNK_WIN_(d, m, elem)
+#define EKV_FN_CHUNK_SINK_WIN_(d, m, elem) ekv_launch_attn_chunk_sink_win_d##d##_m##m##_##elem
+#define EKV_FN_CHUNK_SINK_WIN(d, m, elem) EKV_FN_CHUNK_SINK_WIN_(d, m, elem)
 #define EKV_FN_CHUNK_SINK_(d, m, elem) ekv_launch_attn_chunk_sink_d##d##_m##m##_##elem
 #define EKV_FN_CHUNK_SINK(d, m, elem) EKV_FN_CHUNK_SINK_(d, m, elem)
 #define EKV_FN_WIDE_(d, m, keys, elem) ekv_launch_attn_wide_d##d##_m##m##_##keys##_##elem

@@ -798,6 +798,15 @@ bool ekv_rows_head_dim(EkvRows rows, int head_dim) {
 // The two axes apply independently: the table of a quantised batch is checked against the bank the code planes stand in, and the
 // refusals of either axis hold unchanged (a head_dim the row format does not take, in a table: EKV_E_UNSUPPORTED with zero launches
 // and zero bytes).  The plan is the 16-bit batched call's of the same table.
+// the struct of a window call: complete, and nothing negative in what the host can read (windows_host: optional, bank->n_layers entries)
+static bool ekv_win_ok(const ekv_win* w, const ekv_bank* bank) {
+  if (!w || !w->tok_pos || !w->windows || w->q_pos0 < 0) return false;
+  if (w->windows_host && check_bank(bank) != EKV_E_ARG)      // (n_layers is read only from a bank whose fields have been checked: a bad bank is reported as such by the call)
+    for (int i = 0; i < bank->n_layers; ++i)
+      if (w->windows_host[i] < 0) return false;
+  return true;
+}
+
 int resolve_call(const EkvCall& c, EkvResolved* r) {
   EkvStepPlan* P = &r->plan;
   *P = EkvStepPlan{};
@@ -868,16 +877,29 @@ int resolve_call(const EkvCall& c, EkvResolved* r) {
   // zero launches and zero bytes (EKV_E_UNSUPPORTED): RoPE-on-read, a head_dim other than 64 / 128, a chunk step whose GQA factor
   // exceeds a block.  The head-mean TOVA row (tova_head_mean) runs the sink build of its kernel.
   if (c.sink && c.sinks == nullptr) return EKV_E_ARG;
-  const int variants = (c.long_rows ? 1 : 0) + (c.capped ? 1 : 0) + (c.sink ? 1 : 0);
+  // Window calls (ekv_win_*), likewise stated once.  "Window" is one more independent variant of a call, allowed together with "sink"
+  // (win->s_aux != NULL) and with nothing else.  A NULL struct, NULL tok_pos / windows, a negative q_pos0 and a negative entry of the
+  // host copy of the windows are argument errors, behind the element type and before anything is planned; no device pointer is
+  // dereferenced here.  A decode step plans as the SINK call of the same (bank, step, dtype) — order F, no resident rows, the same
+  // splits, launches and workspace — with or without sinks, and runs the window decode instances; the token position of the appended
+  // row is stamped at the kernels' append site, so the plan has no launch of its own for it.  A chunk step or dense prefix plans by the
+  // sink call's rule (the 16x16x32 kernel alone, blocks of at most 32 folded rows, wide = 0).  Refused with zero launches and zero bytes
+  // (EKV_E_UNSUPPORTED): RoPE-on-read, a head_dim other than 128 (window alone) / 64 (with sinks), and what the sink call refuses (a chunk
+  // step whose GQA factor exceeds a block).  The head-mean TOVA row (tova_head_mean) is rebuilt from the exported logits, whose masked
+  // columns are -inf (exp -> 0), by the plain build of its kernel, or by the sink build where the call has sinks.
+  if (c.window && !ekv_win_ok(c.win, bank)) return EKV_E_ARG;
+  const int variants = (c.long_rows ? 1 : 0) + (c.capped ? 1 : 0) + (c.sink || c.window ? 1 : 0);
+  const bool sinkish = c.sink || c.window;
   const int rc = (variants && (quant || c.batch || variants > 1))
                      ? EKV_E_UNSUPPORTED
-                     : ekv_plan_step(bank, r->step, P, c.long_rows, c.capped || c.sink, quant || c.batch || c.sink || c.capped);
+                     : ekv_plan_step(bank, r->step, P, c.long_rows, c.capped || sinkish, quant || c.batch || sinkish || c.capped);
   P->capped = c.capped ? 1 : 0;
   P->sink = c.sink ? 1 : 0;
+  P->window = c.window ? 1 : 0;
   P->bf16 = c.dtype == EKV_DTYPE_BF16;
   P->rows = c.rows;
   P->batch = c.batch;
-  if (quant || c.batch || c.sink) P->fused_order = 0;      // (the quantised, the batch and the sink instances keep order F, without resident rows)
+  if (quant || c.batch || sinkish) P->fused_order = 0;      // (the quantised, the batch and the sink instances keep order F, without resident rows)
   if (c.capped && P->fused_nw == 8) P->fused_order &= ~0xFFFF;      // (the soft-capped 8-wave instances keep order F; their resident rows stay)
   auto refuse = [&](int code) {
     if (P->long_rows) {      // (a long plan that is refused after all reports the layout of the plain call: nothing of the long scorer remains)
@@ -886,7 +908,7 @@ int resolve_call(const EkvCall& c, EkvResolved* r) {
       P->bytes = plain.bytes, P->big_rows = plain.big_rows, P->key_rows = -1;
     }
     P->one_launch = P->n_launches = P->n_list = P->long_rows = P->long_tiles = 0;
-    if (c.batch || c.capped || c.sink) P->bytes = 0;      // (nothing will run: ekv_batch_workspace_bytes of a refused table, ekv_cap_ / ekv_sink_workspace_bytes of a refused step, is 0)
+    if (c.batch || c.capped || sinkish) P->bytes = 0;      // (nothing will run: ekv_batch_workspace_bytes of a refused table, ekv_cap_ / ekv_sink_workspace_bytes of a refused step, is 0)
     return code;
   };
   const ekv_step* st = c.step;
@@ -899,6 +921,7 @@ int resolve_call(const EkvCall& c, EkvResolved* r) {
   if (rc != EKV_OK) return refuse(rc);
   if (c.capped && (st->rope_on_read || (bank->head_dim != 128 && bank->head_dim != kChunkNarrowD))) return refuse(EKV_E_UNSUPPORTED);
   if (c.sink && (st->rope_on_read || (bank->head_dim != 64 && bank->head_dim != 128))) return refuse(EKV_E_UNSUPPORTED);
+  if (c.window && (st->rope_on_read || bank->head_dim != (c.sink ? 64 : 128))) return refuse(EKV_E_UNSUPPORTED);
   if (quant && (st->q_len != 1 || st->rope_on_read || !ekv_rows_head_dim(c.rows, bank->head_dim) ||
                 bank->n_q_heads / bank->n_kv_heads > kRowsRules[c.rows].max_rep))
     return refuse(EKV_E_UNSUPPORTED);
@@ -940,6 +963,7 @@ int call_info(const EkvCall& c, int32_t* info, int32_t n_info) {
   if (c.dtype != EKV_DTYPE_F16 && c.dtype != EKV_DTYPE_BF16) return EKV_E_ARG;
   if (c.capped && !(c.softcap > 0.f && c.softcap <= 3.0e38f)) return EKV_E_ARG;      // (a cap no step can be planned with)
   if (c.sink && c.sinks == nullptr) return EKV_E_ARG;
+  if (c.window && !ekv_win_ok(c.win, r.bank)) return EKV_E_ARG;
   if (c.rows != EKV_ROWS_kv16 && !r.bank) return EKV_E_ARG;
   if (int e = check_bank(r.bank)) return e;
   if (!c.step || (c.batch && !c.seqs) || !info || n_info < 1) return EKV_E_ARG;

@@ -85,6 +85,8 @@ struct EkvCall {
   float softcap;           // ... its cap: finite and > 0, or the call is an argument error
   bool sink;               // an ekv_sink_* call: attention sinks (16-bit rows, one sequence, plain keys, head_dim 64 / 128)
   const float* sinks;      // ... the sinks, device fp32 [bank->n_layers][n_q_heads]: only tested for NULL here (an argument error)
+  bool window;             // an ekv_win_* call: sliding windows (16-bit rows, one sequence, plain keys; with sinks head_dim 64, alone 128)
+  const ekv_win* win;      // ... its struct (include/easykv_hip.h): NULL, NULL tok_pos / windows or a negative window are argument errors
 };
 inline EkvCall step_call(const ekv_bank* bank, const ekv_step* st, int32_t dtype) { return {bank, st, dtype, EKV_ROWS_kv16, {}, false, nullptr, 0}; }
 inline EkvCall batch_call(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_seq* seqs, int32_t n_seq) {
@@ -96,6 +98,10 @@ inline EkvCall cap_call(const ekv_bank* bank, const ekv_step* st, int32_t dtype,
 }
 inline EkvCall sink_call(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const float* sinks) {
   return {bank, st, dtype, EKV_ROWS_kv16, {}, false, nullptr, 0, false, false, 0.f, true, sinks};
+}
+// (win->s_aux != NULL: the window joins the sink variant; the struct itself is checked in resolve_call)
+inline EkvCall win_call(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_win* win) {
+  return {bank, st, dtype, EKV_ROWS_kv16, {}, false, nullptr, 0, false, false, 0.f, win != nullptr && win->s_aux != nullptr, win ? win->s_aux : nullptr, true, win};
 }
 // the quantised calls: the same two with a row format and its planes
 inline EkvCall kv8_call(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_kv8* q8) {

@@ -76,6 +76,8 @@ ROW_FORMATS = {
 CAPPED_HEAD_DIMS = (128, 256)
 # head_dims the sink kernels (KVBank(sinks=...)) are built for
 SINK_HEAD_DIMS = (64, 128)
+# head_dim the window kernels (KVBank(windows=...)) are built for: without sinks, with sinks (gpt-oss's shape)
+WINDOW_HEAD_DIM = {False: 128, True: 64}
 # head_dims served with plain keys and 16-bit rows only: no RoPE-on-read build (set_rope, streaming) and no quantised row format
 PLAIN_KEYS_HEAD_DIMS = (256,)
 
@@ -165,10 +167,20 @@ class KVBank:
     logit_cap = None     # KVBank(..., logit_cap=c): soft-capped logits, the steps go to the capped family (ekv_cap_*), set per bank by __init__
     sm_scale = None      # KVBank(..., sm_scale=s): logits are q.k * s (None: 1 / sqrt(head_dim)), in every call family
     sinks = None         # KVBank(..., sinks=t): attention sinks, the steps go to the sink family (ekv_sink_*), set per bank by __init__
+    windows = None       # KVBank(..., windows=[...]): sliding windows, the steps go to the window family (ekv_win_*), set per bank by __init__
+    tok_pos = None       # ... int32 [n_layers, H, cap]: the token position every physical row was appended at
 
     def __init__(self, n_layers, n_q_heads, n_kv_heads, head_dim, cap, device="cuda", scored=True, dtype=torch.float16, kv_quant=None, long_rows=False,
-                 logit_cap=None, sm_scale=None, sinks=None):
-        """``sinks``: a tensor ``[n_layers, n_q_heads]`` of finite values, kept as fp32 on the device: learned attention sinks (gpt-oss:
+                 logit_cap=None, sm_scale=None, sinks=None, windows=None):
+        """``windows``: ``n_layers`` integers >= 0, the sliding window of every layer (0: none; include/easykv_hip.h, "sliding windows";
+        gpt-oss: 128 on every other layer).  A key appended ``W`` or more tokens behind the query is masked — by the token position its
+        physical row carries (``tok_pos``), not by its place in the slot map, because eviction is per head.  A masked key stays live:
+        it keeps its slot and score column, receives p = 0 and a count, and may be a victim.  All-zero windows are legal and still route
+        to the window family (``ekv_win_*``), whose steps plan as the sink family's (decode: phase order F, no resident rows; chunk steps
+        and the dense prefix: the 16x16 chunk kernel in blocks of at most 32 folded rows).  head_dim 128 without ``sinks``, 64 with them; 16-bit rows,
+        plain keys: not with ``logit_cap``, ``kv_quant`` or ``long_rows``, and :meth:`quantize` / :meth:`set_rope` /
+        :meth:`compact_inplace` refuse such a bank.  A negative value or a wrong shape raises ``ValueError``.
+        ``sinks``: a tensor ``[n_layers, n_q_heads]`` of finite values, kept as fp32 on the device: learned attention sinks (gpt-oss:
         ``s_aux``; include/easykv_hip.h, "attention sinks").  The logit of layer ``l`` and query head ``h`` joins every softmax of that
         head as a virtual key with value 0: it takes its share of the probability mass and has no column, no score and is never a
         victim.  The bank's steps go to the sink call family: decode steps plan as the plain ones (phase order F, no resident rows),
@@ -230,6 +242,25 @@ class KVBank:
                 raise _lib.EkvError("KVBank(sinks=..., long_rows=True): there is no long sink call (the long-row family has no sink form)")
             if head_dim not in SINK_HEAD_DIMS:
                 raise _lib.EkvError(f"KVBank(sinks=...): attention sinks are built for head_dim {' and '.join(map(str, SINK_HEAD_DIMS))}, not {head_dim}")
+        if windows is not None:      # (before anything is allocated or loaded)
+            try:
+                wl = windows.tolist() if torch.is_tensor(windows) else list(windows)
+            except TypeError:
+                wl = None
+            if not (isinstance(wl, list) and len(wl) == n_layers and all(isinstance(w, int) and not isinstance(w, bool) for w in wl)):
+                raise ValueError(f"KVBank windows must be {n_layers} integers (one per layer), not {windows!r}")
+            if any(w < 0 for w in wl):
+                raise ValueError(f"KVBank windows must be >= 0 (0: no window), not {wl}")
+            if logit_cap is not None:
+                raise _lib.EkvError("KVBank(windows=..., logit_cap=...): there is no capped window call (the window family has no soft-capped form)")
+            if fmt is not None:
+                raise _lib.EkvError(f"KVBank(windows=...): sliding windows are built for 16-bit rows, not for {fmt['label']} rows "
+                                    f"(kv_quant={kv_quant!r}): there is no quantised window call")
+            if long_rows:
+                raise _lib.EkvError("KVBank(windows=..., long_rows=True): there is no long window call (the long-row family has no window form)")
+            if head_dim != WINDOW_HEAD_DIM[sinks is not None]:
+                raise _lib.EkvError(f"KVBank(windows=...): sliding windows {'with' if sinks is not None else 'without'} sinks are built for "
+                                    f"head_dim {WINDOW_HEAD_DIM[sinks is not None]}, not {head_dim}")
         if fmt is not None:
             _check_row_shape(fmt, head_dim, n_q_heads // max(1, n_kv_heads))
         self.dtype, self._dt = dtype, _lib.DTYPE_CODES[dtype]
@@ -280,6 +311,14 @@ class KVBank:
         self.rope_cos = self.rope_sin = None
         if sinks is not None:      # (a constant of the bank: the pointer every sink call carries, hipGraph capture included)
             self.sinks = sinks.detach().to(dev, torch.float32).contiguous().clone()
+        self._tokens = [0] * n_layers      # tokens every head of a layer has been handed so far: the position of its next query
+        if windows is not None:      # (allocated for a window bank only)
+            self.windows = tuple(wl)
+            self.tok_pos = torch.zeros(n_layers, n_kv_heads, cap, dtype=torch.int32, device=dev)
+            self._windows_dev = torch.tensor(wl, dtype=torch.int32, device=dev)
+            self._windows_host = (C.c_int32 * n_layers)(*wl)      # (the copy the library can check; kept alive with the bank)
+            self._win = _lib.Win(self.tok_pos.data_ptr(), self._windows_dev.data_ptr(), self._windows_host,
+                                 self.sinks.data_ptr() if self.sinks is not None else None, 0)
         self._attach(fmt)
         self.reset()
 
@@ -393,6 +432,9 @@ class KVBank:
         if self.sinks is not None:
             raise _lib.EkvError(f"{m}: the bank was created with sinks, and attention sinks are built for 16-bit rows, not for "
                                 f"{fmt['label']} rows: there is no quantised sink call")
+        if self.windows is not None:
+            raise _lib.EkvError(f"{m}: the bank was created with windows, and sliding windows are built for 16-bit rows, not for "
+                                f"{fmt['label']} rows: there is no quantised window call")
         if self.long_rows:
             raise _lib.EkvError(f"{m}: the bank was created with long_rows=True, and the long-row scorer is built for 16-bit rows, not "
                                 f"for {fmt['label']} rows: {fmt['label']} rows have no long form")
@@ -478,6 +520,39 @@ class KVBank:
         if self.sinks is not None:      # (16-bit rows likewise) the sink family: the sinks' device pointer stands behind the dtype
             self._check_fn, self._info_fn, self._ws_fn, self._attend_fn = (getattr(self.lib, _lib.SINK_CALLS[what]) for what in _lib.STEP_CALLS)
             self._desc_ref = (C.c_void_p(self.sinks.data_ptr()),)
+        if self.windows is not None:      # (16-bit rows likewise) the window family: its struct (sinks or NULL inside) stands behind the dtype;
+            # q_pos0 is written into the struct before every attention call (_set_q_pos), so cached references stay valid
+            self._check_fn, self._info_fn, self._ws_fn, self._attend_fn = (getattr(self.lib, _lib.WIN_CALLS[what]) for what in _lib.STEP_CALLS)
+            self._desc_ref = (C.byref(self._win),)
+
+    tokens_seen = property(lambda self: max(self._tokens), doc="tokens the sequence has been handed so far (the next query's position)")
+
+    def _set_q_pos(self, layer_begin, lc, q_pos):
+        """The token position of the step's query row, into the window struct (a window bank; a no-op otherwise): ``q_pos`` or, for
+        None, the tokens these layers have seen, which must agree.  Known on the host without a sync: every step appends ``q_len``
+        tokens to every head (row ``i`` of a chunk step is at ``q_pos + i``)."""
+        if self.windows is None:
+            return
+        if q_pos is None:
+            seen = set(self._tokens[layer_begin:layer_begin + lc])
+            if len(seen) != 1:
+                raise _lib.EkvError(f"attend(): layers [{layer_begin}, {layer_begin + lc}) have seen different token counts {sorted(seen)}")
+            q_pos = seen.pop()
+        if not (isinstance(q_pos, int) and q_pos >= 0):
+            raise ValueError(f"attend(q_pos=...) must be an integer >= 0, not {q_pos!r}")
+        if torch.cuda.is_current_stream_capturing():
+            raise _lib.EkvError("attend() on a bank created with windows during a hipGraph capture: the token position of the query (q_pos0) is a "
+                                "host scalar of every window call, which a captured graph would freeze")
+        self._win.q_pos0 = q_pos
+
+    def ordered_tok_pos(self, layer_begin=0, layer_count=None):
+        """The token positions of the live rows in slot-map order, int32 ``[layers, H, T]`` (a window bank; for tests and tools)."""
+        if self.windows is None:
+            raise _lib.EkvError("ordered_tok_pos(): the bank was created without windows")
+        lc = self.n_layers - layer_begin if layer_count is None else layer_count
+        t = self.n_slots[layer_begin]
+        slots = self.slot_of_pos[layer_begin:layer_begin + lc, :, :t].long()
+        return torch.gather(self.tok_pos[layer_begin:layer_begin + lc], 2, slots)
 
     def kv_bytes(self) -> int:
         """Bytes held for the K/V rows: 16-bit rows, FP8 codes + row scales (``2 * head_dim + 8`` per row pair), or MXFP4 codes +
@@ -534,6 +609,7 @@ class KVBank:
         self._slot_min_tail = [1 << 30] * self.n_layers
         self._slot_stretch = self._slot_short = self._slot_cool = 0
         self._defer = None      # (a half-open deferred token step dies with the bank's contents; arrive[] is zeroed by the reset)
+        self._tokens = [0] * self.n_layers
 
     def abort_step(self):
         """Drop a deferred token step that was opened (``attend(..., defer=True)`` on some layers) but never flushed — a model
@@ -560,6 +636,8 @@ class KVBank:
             raise _lib.EkvError("set_rope(): RoPE-on-read has no soft-capped build (a bank created with logit_cap serves plain keys only)")
         if self.sinks is not None:
             raise _lib.EkvError("set_rope(): RoPE-on-read has no sink build (a bank created with sinks serves plain keys only)")
+        if self.windows is not None:
+            raise _lib.EkvError("set_rope(): RoPE-on-read has no window build (a bank created with windows serves plain keys only)")
         if self.head_dim in PLAIN_KEYS_HEAD_DIMS:
             raise _lib.EkvError(f"set_rope(): RoPE-on-read has no build for head_dim {self.head_dim} (plain keys only)")
         self.rope_cos = cos.to(self.device, torch.float32).contiguous()
@@ -581,10 +659,24 @@ class KVBank:
                 raise _lib.EkvError("rope tables must be rotations linear in the position: row j = (cos(j * theta), sin(j * theta)) per frequency")
 
     # -- data movement at the boundary -------------------------------------------------------------
-    def load_rows(self, k, v, pos_begin=None, layer_begin=0):
-        """Append ordered rows ``[layers, H, n, D]`` at positions [pos_begin, pos_begin+n)."""
+    def load_rows(self, k, v, pos_begin=None, layer_begin=0, tok_pos=None):
+        """Append ordered rows ``[layers, H, n, D]`` at positions [pos_begin, pos_begin+n).  A window bank stamps the rows' token
+        positions: ``tok_pos=None`` the ``n`` positions after the tokens the layers have seen, or a given int ``[layers, H, n]``,
+        increasing along ``n`` (a cache with gaps, different per head); the layers have then seen ``max + 1`` tokens."""
         lc, n = k.shape[0], k.shape[2]
         self._quant_refuse(True, "load_rows")
+        if tok_pos is not None and self.windows is None:
+            raise _lib.EkvError("load_rows(tok_pos=...): the bank was created without windows")
+        if self.windows is not None:      # (before anything is written)
+            if tok_pos is None:
+                base = self._tokens[layer_begin]
+                tok_pos = (base + torch.arange(n, dtype=torch.int32, device=self.device)).expand(lc, self.n_kv_heads, n)
+                seen = base + n
+            else:
+                tok_pos = torch.as_tensor(tok_pos).to(self.device, torch.int32)
+                if tuple(tok_pos.shape) != (lc, self.n_kv_heads, n) or bool((tok_pos[..., 1:] <= tok_pos[..., :-1]).any()) or bool((tok_pos < 0).any()):
+                    raise ValueError(f"load_rows(tok_pos=...) must be [layers, H, n] = [{lc}, {self.n_kv_heads}, {n}], >= 0 and increasing along n")
+                seen = int(tok_pos.max()) + 1
         self._ensure_ordered(layer_begin, lc)
         pos = self.n_slots[layer_begin] if pos_begin is None else pos_begin
         k = k.to(self.device, self.dtype).contiguous()
@@ -593,6 +685,11 @@ class KVBank:
         for l in range(layer_begin, layer_begin + lc):
             self.n_slots[l] = pos + n
             self.extent[l] = max(self.extent[l], pos + n)
+        if self.windows is not None:      # (rows never move: the position goes where the slot map sent the row)
+            slots = self._slot_of_pos[layer_begin:layer_begin + lc, :, pos:pos + n].long()
+            self.tok_pos[layer_begin:layer_begin + lc].scatter_(2, slots, tok_pos.contiguous())
+            for l in range(layer_begin, layer_begin + lc):
+                self._tokens[l] = max(self._tokens[l], seen)
 
     def ordered_kv(self, layer_begin=0, layer_count=None):
         """The ordered ``[layers, H, T, D]`` view the HF legacy tuple needs (birth order)."""
@@ -609,6 +706,8 @@ class KVBank:
         """Reference-shaped physical compaction for a bank kept in identity layout."""
         lc, _, kk = evict_ids.shape
         self._quant_refuse(True, "compact_inplace (a row move)")
+        if self.windows is not None:
+            raise _lib.EkvError("compact_inplace(): a bank created with windows keeps the token position of a row with the row; rows do not move")
         self._ensure_ordered(layer_begin, lc)
         t = self.n_slots[layer_begin]
         ids = evict_ids.to(self.device, torch.int32).contiguous()
@@ -653,7 +752,7 @@ class KVBank:
         """(n_split, fused) the library will use for this step."""
         st = self.make_step(plan, q_len, layer_begin, self.n_layers - layer_begin if layer_count is None else layer_count)
         st.phases = phases
-        if self._fmt is not None or self.long_rows or self.logit_cap is not None or self.sinks is not None:      # (the dry run of the bank's own family: a step the bank refuses plans as not fused)
+        if self._fmt is not None or self.long_rows or self.logit_cap is not None or self.sinks is not None or self.windows is not None:      # (the dry run of the bank's own family: a step the bank refuses plans as not fused)
             info = self.step_info(plan, q_len, layer_begin, layer_count, phases)
             return info["n_split"], bool(info["fused"])
         ns, fu = C.c_int32(0), C.c_int32(0)
@@ -674,7 +773,7 @@ class KVBank:
     def resident_rows(self, plan: StepPlan, q_len=1, layer_begin=0, layer_count=None, phases=0) -> int:
         """Resident rows the library plans this step's launch with (ekv_step_resident_rows) under this bank's ``resident_bytes``;
         0 for a quantised bank."""
-        if self._fmt is not None or self.sinks is not None:      # (the sink instances are built without resident rows, as the kv164 ones)
+        if self._fmt is not None or self.sinks is not None or self.windows is not None:      # (the sink and the window instances are built without resident rows, as the kv164 ones)
             return 0
         st = self.make_step(plan, q_len, layer_begin, self.n_layers - layer_begin if layer_count is None else layer_count)
         st.phases = phases
@@ -726,7 +825,7 @@ class KVBank:
             self._score_done[l] = done
 
     # -- one layer per call (a real decoder stack): attention now, scoring / eviction once per token ------------------------
-    def _attend_deferred(self, plan: StepPlan, q, k_new, v_new, layer, out):
+    def _attend_deferred(self, plan: StepPlan, q, k_new, v_new, layer, out, q_pos=None):
         """Step of ONE layer with the scorer deferred (ekv_step.defer_layers): attention + fold of this layer now — its output is
         what the next layer waits for — and one scorer launch over all layers of the bank at :meth:`flush`, instead of a
         latency-bound scorer kernel of 32 workgroups on the critical path of every layer (decode: 15 us of a 25 us layer; a
@@ -767,18 +866,20 @@ class KVBank:
         if out is None:
             out = torch.empty(1, self.n_q_heads, n, self.head_dim, dtype=self.dtype, device=self.device)
         q, k_new, v_new = _stride_rows(st, q, k_new, v_new, out, self.dtype)
+        self._set_q_pos(layer, 1, q_pos)
         rc = d["call"](*d["head"], q.data_ptr(), k_new.data_ptr(), v_new.data_ptr(), out.data_ptr(), None,
                        d["rope"][0], d["rope"][1], d["ws_ptr"], d["ws_len"], d["stream"])
         if rc != 0:
             check(rc, "ekv_step_attend")
         self.extent[layer] = st.phys_extent
+        self._tokens[layer] += n
         d["pending"] += 1
         return out
 
     def _planned_split(self, st) -> int:
         """The split count the library plans for ``st`` (a capped bank: by its own family — a capped chunk step is tiled in narrower
         blocks than the plain call's)."""
-        if self.logit_cap is not None or self.sinks is not None:
+        if self.logit_cap is not None or self.sinks is not None or self.windows is not None:
             info = (C.c_int32 * 10)()
             check(self._info_fn(C.byref(self._bank), C.byref(st), self._dt, *self._desc_ref, info, 10), self._info_fn.__name__)
             return int(info[0])
@@ -816,19 +917,22 @@ class KVBank:
         d["t"] = -1
         return d["ids"] if st.n_evict > 0 else None
 
-    def attend(self, plan: StepPlan, q, k_new, v_new, layer_begin=0, out=None, evict_ids=None, phases=0, overlap_scorer=False, defer=False):
+    def attend(self, plan: StepPlan, q, k_new, v_new, layer_begin=0, out=None, evict_ids=None, phases=0, overlap_scorer=False, defer=False,
+               q_pos=None):
         """q ``[layers, Hq, n, D]``, k_new/v_new ``[layers, H, n, D]`` (the bank's dtype, device; dense or strided views whose rows are
         read in place — ekv_step.*_stride, see :func:`_row_strides`; anything else is converted / copied dense first).
         Returns (out ``[layers, Hq, n, D]`` in the bank's dtype, evict_ids ``[layers, H, k]`` int32 or None).
         ``defer=True`` (one layer per call): attention + fold only; the scorers of all layers run at :meth:`flush`.
         ``evict_ids=False``: the caller has no use for the evicted cache indices (none are returned; on the slot-indexed layout the
-        step then skips ranking the victim's birth)."""
+        step then skips ranking the victim's birth).
+        ``q_pos`` (a window bank): the token position of the (first) query; None: the tokens these layers have seen, which the call advances."""
         if defer:
             if q.shape[0] != 1 or phases != 0:
                 raise ValueError("defer=True is for one-layer calls")
-            return self._attend_deferred(plan, q, k_new, v_new, layer_begin, out), None
+            return self._attend_deferred(plan, q, k_new, v_new, layer_begin, out, q_pos), None
         lc, _, n, _ = q.shape
         self._quant_refuse(n > 1, "a chunk step (q_len > 1)")
+        self._set_q_pos(layer_begin, lc, q_pos)
         st = self.make_step(plan, n, layer_begin, lc)
         # one-launch decode steps run on the slot-indexed layout of the score rows (nothing moves on an eviction); everything else
         # on the ordered one
@@ -861,6 +965,7 @@ class KVBank:
             for l in range(layer_begin, layer_begin + lc):
                 self.n_slots[l] = st.n_slots - st.n_evict
                 self.extent[l] = st.phys_extent
+                self._tokens[l] += n
             return out, (evict_ids if (st.n_evict > 0 and want_ids) else None)
         if any(ev is not None for ev in self._score_done[layer_begin:layer_begin + lc]):
             self.join()
@@ -874,6 +979,8 @@ class KVBank:
                 self.n_slots[l] = st.n_slots - st.n_evict
         for l in range(layer_begin, layer_begin + lc):      # the new rows are written by the attention kernel
             self.extent[l] = st.phys_extent
+            if phases == 0 or phases & 1:      # (the calls that run the attention kernel, which appends the token's row)
+                self._tokens[l] += n
         return out, (evict_ids if (st.n_evict > 0 and want_ids) else None)
 
 
@@ -928,7 +1035,7 @@ class KVBankBatch:
     eviction geometry — in ONE call: one launch per kernel kind over the layers ``{s * n_layers + layer}``."""
 
     def __init__(self, n_seq, n_layers, n_q_heads, n_kv_heads, head_dim, cap, device="cuda", scored=True, dtype=torch.float16, kv_quant=None, long_rows=False,
-                 logit_cap=None, sm_scale=None, sinks=None):
+                 logit_cap=None, sm_scale=None, sinks=None, windows=None):
         """``sm_scale``: the softmax scale of every sequence (:class:`KVBank`; None: ``1 / sqrt(head_dim)``).  ``logit_cap`` raises: there is
         no capped batch call.  ``sinks`` raises: there is no sink batch call.
         ``kv_quant='fp8'``: the shared bank holds FP8 planes only from the start (the 16-bit rows of ``n_seq`` sequences are never
@@ -946,6 +1053,9 @@ class KVBankBatch:
         if sinks is not None:
             raise _lib.EkvError("KVBankBatch(sinks=...): attention sinks are built for single sequences, not for decode batches: "
                                 "there is no sink batch call")
+        if windows is not None:
+            raise _lib.EkvError("KVBankBatch(windows=...): sliding windows are built for single sequences, not for decode batches: "
+                                "there is no window batch call")
         if not 1 <= n_seq <= _lib.MAX_SEQS:
             raise ValueError(f"a decode batch holds 1..{_lib.MAX_SEQS} sequences, not {n_seq}")
         self.n_seq, self.n_layers = n_seq, n_layers

@@ -25,15 +25,18 @@ IMPL = "easykv_amd"
 _registered = False
 
 
-def _easykv_attention(module, query, key, value, attention_mask=None, dropout=0.0, scaling=None, softcap=None, s_aux=None, **kwargs):
+def _easykv_attention(module, query, key, value, attention_mask=None, dropout=0.0, scaling=None, softcap=None, s_aux=None, sliding_window=None,
+                      **kwargs):
     """The attention function of the seam.  ``scaling`` and ``softcap`` (Gemma 2 passes ``attn_logit_softcapping`` under that name) are what
     the MODULE would compute with; the kernels compute with the active cache's ``sm_scale`` / ``logit_cap`` (set by the driver from the
     model's config).  They are held against each other (relative tolerance 1e-3) and a mismatch raises rather than compute another model.
     ``s_aux`` (gpt-oss passes its learned attention sinks, one logit per query head, under that name) is held against the active cache's
     ``sinks`` row of ``module.layer_idx`` likewise — once per (cache, layer), so the decode loop gains no host sync; a module with sinks on
     a cache without them, or the reverse, raises.
-    ``sliding_window`` (in ``kwargs``) is ignored: the retained cache is attended whole, on Gemma 2's and gpt-oss's local layers too, as
-    the reference does for Mistral."""
+    ``sliding_window``: when the active cache has ``windows`` (``generation_config['sliding_window']``), the module's value is held
+    against the cache's row of ``module.layer_idx`` (None or 0 on the module is window 0) and a mismatch raises, once per (cache, layer).
+    On a cache WITHOUT windows it is ignored: the retained cache is attended whole, on Gemma 2's and gpt-oss's local layers too, as the
+    reference does for Mistral."""
     cache = api.active_cache()
     if cache is None:
         raise RuntimeError("easykv_amd attention called outside easykv_generate(): no BudgetedKVCache is active")
@@ -51,6 +54,9 @@ def _easykv_attention(module, query, key, value, attention_mask=None, dropout=0.
     sinks = getattr(cache, "sinks", None)
     if s_aux is not None or sinks is not None:
         _check_sinks(cache, sinks, module, s_aux)
+    windows = getattr(cache, "windows", None)
+    if windows is not None:
+        _check_window(cache, windows, module, sliding_window)
     if cache.streaming:
         # streaming=True (llama_patch.py:310-327) caches UN-rotated keys; the stock module has already applied RoPE at the
         # true positions, so take it off again (rotation by -theta: x = x'*cos - rotate_half(x')*sin, fp32)
@@ -85,6 +91,22 @@ def _check_sinks(cache, sinks, module, s_aux):
     mine, theirs = sinks[row].float(), s_aux.detach().reshape(-1).to(sinks.device, torch.float32)
     if not bool(((mine - theirs).abs() <= 1e-3 * torch.maximum(mine.abs(), theirs.abs())).all()):
         raise ValueError(f"easykv_amd attention: the attention sinks of the module of layer {layer} differ from the active cache's row {row}")
+    checked.add(layer)
+
+
+def _check_window(cache, windows, module, sliding_window):
+    """The module's sliding window against the active cache's window of its layer, once per (cache, layer)."""
+    layer = module.layer_idx
+    checked = cache._windows_checked
+    if layer in checked:
+        return
+    row = layer - getattr(cache, "layer_begin", 0)
+    if not 0 <= row < len(windows):
+        raise ValueError(f"easykv_amd attention: the module of layer {layer} is outside the {len(windows)} layers the active cache holds windows for")
+    theirs = int(sliding_window) if sliding_window else 0
+    if theirs != windows[row]:
+        raise ValueError(f"easykv_amd attention: the module of layer {layer} attends a sliding window of {theirs or 'none'}, the active cache "
+                         f"masks {windows[row] or 'none'} there: it would compute another model")
     checked.add(layer)
 
 

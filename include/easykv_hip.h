@@ -583,6 +583,55 @@ int ekv_sink_step_attend(const ekv_bank *bank, const ekv_step *step, int32_t dty
                          const void *v_new, void *out, int32_t *evict_ids, const float *rope_cos, const float *rope_sin,
                          void *workspace, size_t workspace_bytes, void *stream);
 
+/* Sliding windows (ABI 8, additive): the *_typed calls of a 16-bit bank whose model masks, per layer, the keys that lie a window or
+ * more behind the query (gpt-oss: sliding_window = 128 on every other layer).  NORMATIVE.  Every physical K/V row carries the TOKEN
+ * POSITION at which it was appended: the count of tokens the sequence had seen before it, 0, 1, 2, ...  This is not the row's logical
+ * position in the slot map: eviction is per head, so the same token can be retained in one head and gone in another, and the first
+ * attended logical position differs per head.  That is why the position lives with the row and not in a per-launch scalar.
+ *
+ * A layer has a window W_l >= 0; 0 means no window.  For a query at token position p_q and a live key at token position p_k <= p_q:
+ *
+ *     the key is attended  iff  W_l == 0  or  p_q - p_k < W_l
+ *
+ * (transformers' sliding_window_overlay, kv_idx > q_idx - sliding_window).  A masked key's logit is -inf before the maximum, exactly
+ * like a causally masked one.  Everything downstream sees p_j and nothing else: the outputs, the column sums, sum p / sum p^2 /
+ * counts, the tova row, the GQA mean and every select.  A masked key is still LIVE: it keeps its slot and its score column, receives
+ * p = 0 and a count, and may be a victim.  Selection rules, protected windows and tie rules are untouched.  With sinks, the virtual
+ * key is never masked.  A query always attends itself (W_l >= 1 keeps p_k = p_q), so no row is empty.
+ *
+ * tok_pos: DEVICE pointer, int32 [bank->n_layers][n_kv_heads][cap], indexed by PHYSICAL row as a row scale of a kv8 bank is: rows never
+ * move, so it is written once, when the row is appended, and no eviction or compaction touches it.  The step writes q_pos0 for the row
+ * it appends, at the kernel's own append site (the lane that stores the new K/V row stores its position: no launch of its own, so the
+ * plan is the sink call's launch for launch); rows put into the bank by other means must be stamped by the caller.
+ * windows: DEVICE pointer, int32 [bank->n_layers], indexed by bank layer.  windows_host: optional HOST copy of the same entries, the
+ * only one the library can check: a negative entry is an argument error.  s_aux: the sinks of the sink calls, or NULL for a model without
+ * them.  q_pos0: token position of the step's query row, >= 0.  The dry-run calls dereference no device pointer.
+ *
+ * A window DECODE step plans as the SINK call of the same (bank, step, dtype), with or
+ * without sinks: order F, no resident rows (info [9] = 0), the same n_split, launches and workspace.  With every window 0, or every
+ * window wider than the sequence, its results are those of the plain call (s_aux == NULL; forced to order F without resident rows) or
+ * the sink call, bit for bit.  A window CHUNK step or dense prefix plans as the sink call's (the 16x16x32 kernel alone, blocks of at most
+ * 32 GQA-folded rows, info [3] = 0); row i of the step is at token position q_pos0 + i, and the chunk's own keys are subject to the window
+ * too (i - i' >= W_l is masked).  The head-averaged TOVA row (tova_head_mean) is rebuilt from the exported logits, whose masked columns
+ * are -inf, by the plain or the sink build of its kernel.  Refused before any launch, with ekv_win_workspace_bytes = 0
+ * (EKV_E_UNSUPPORTED): rope_on_read, what the sink call refuses, a head_dim other than 128
+ * (s_aux == NULL) or 64 (with sinks).  EKV_E_ARG, behind the element type and before anything else is read: a NULL struct, NULL
+ * tok_pos / windows, q_pos0 < 0, a negative entry of windows_host.  16-bit rows and single sequences only: there is no window batched,
+ * quantised, long or capped call. */
+typedef struct ekv_win {
+  int32_t *tok_pos;
+  const int32_t *windows;
+  const int32_t *windows_host;
+  const float *s_aux;
+  int32_t q_pos0;
+} ekv_win;
+int ekv_win_step_check(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const ekv_win *win);
+int ekv_win_step_info(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const ekv_win *win, int32_t *info, int32_t n_info);
+size_t ekv_win_workspace_bytes(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const ekv_win *win);
+int ekv_win_step_attend(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const ekv_win *win, const void *q, const void *k_new,
+                        const void *v_new, void *out, int32_t *evict_ids, const float *rope_cos, const float *rope_sin,
+                        void *workspace, size_t workspace_bytes, void *stream);
+
 /* Batched decode steps (ABI 8, additive): ONE call, and one launch per kernel kind, serves n_seq sequences whose caches have
  * different lengths and different eviction geometry.  Each entry of the table names the bank layer it attends and carries what
  * ekv_step holds per step; entry i owns row i of the call's tensors.  The layers of a table need not be contiguous or ordered, so
