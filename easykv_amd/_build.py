@@ -71,6 +71,9 @@ FAMILIES = {
     "EKV_RESIDENT": lambda d, elem: ("ekv_attn_resident.inc", f"ekv_attn_resident_d{d}" + _tags(elem), _on(elem)),
     "EKV_SCORE_SELECT": lambda nt, elem: ("ekv_score_select.inc", f"ekv_score_select_nt{nt}" + _tags(elem), _on(elem) + [f"-DEKV_SS_NT={nt}"]),
     "EKV_SCORE_LONG": lambda nt: ("ekv_score_long.inc", "ekv_score_long", [f"-DEKV_LONG_NT={nt}"]),
+    # pooled selection (-DEKV_POOL=1): the generic scorer with the pooling stencil in front of its select
+    "EKV_SCORE_SELECT_POOL": lambda nt, elem: (
+        "ekv_score_select.inc", f"ekv_score_select_pool_nt{nt}" + _tags(elem), _on(elem) + [f"-DEKV_SS_NT={nt}", "-DEKV_POOL=1"]),
 }
 
 
@@ -124,7 +127,7 @@ def later_instances():
 
 
 def later_objects():
-    """(object name, hipcc arguments) of the instances of ekv_instances_later.def (the kv84 decode instances, the kv164 ones, the long-row scorer, head_dim 256, the soft-capped instances, the sink instances, the window instances)."""
+    """(object name, hipcc arguments) of the instances of ekv_instances_later.def (the kv84 decode instances, the kv164 ones, the long-row scorer, head_dim 256, the soft-capped instances, the sink instances, the window instances, the pooled scorer)."""
     return _instance_objects(later_instances())
 
 

@@ -56,6 +56,10 @@ EXPORTS += tuple(SINK_CALLS[what] for what in STEP_CALLS)
 # the window family (include/easykv_hip.h, "sliding windows"): the _typed calls with an ekv_win struct behind the dtype; 16-bit rows, one sequence
 WIN_CALLS = {what: "ekv_win_" + what for what in STEP_CALLS}
 EXPORTS += tuple(WIN_CALLS[what] for what in STEP_CALLS)
+# the pooled family (include/easykv_hip.h, "pooled selection"): the _typed calls with an ekv_pool struct behind the dtype; 16-bit rows, one sequence
+POOL_CALLS = {what: "ekv_pool_" + what for what in STEP_CALLS}
+EXPORTS += tuple(POOL_CALLS[what] for what in STEP_CALLS)
+POOL_OPS = {"max": 0, "avg": 1}      # EKV_POOL_MAX, EKV_POOL_AVG
 
 
 class Bank(C.Structure):
@@ -94,6 +98,11 @@ class Win(C.Structure):
     """ekv_win: token positions of the physical rows, the layers' windows (device, and a host copy the library can check), the sinks or
     NULL, and the token position of the step's query (include/easykv_hip.h, "sliding windows")."""
     _fields_ = [("tok_pos", C.c_void_p), ("windows", C.c_void_p), ("windows_host", C.POINTER(C.c_int32)), ("s_aux", C.c_void_p), ("q_pos0", C.c_int32)]
+
+
+class Pool(C.Structure):
+    """ekv_pool: radius (kernel size 2 * radius + 1) and op (POOL_OPS) of a pooled selection (include/easykv_hip.h, "pooled selection")."""
+    _fields_ = [("radius", C.c_int32), ("op", C.c_int32)]
 
 
 class Step(C.Structure):
@@ -164,6 +173,7 @@ def load():
                 getattr(lib, CAP_CALLS[what]).argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, C.c_float] + tails[what]
                 getattr(lib, SINK_CALLS[what]).argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, vp] + tails[what]
                 getattr(lib, WIN_CALLS[what]).argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, C.POINTER(Win)] + tails[what]
+                getattr(lib, POOL_CALLS[what]).argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, C.POINTER(Pool)] + tails[what]
         if desc:
             getattr(lib, f"ekv_{rows}_quantize").argtypes = [C.POINTER(Bank), C.POINTER(desc), i32, i32, i32, i32, vp]
             getattr(lib, f"ekv_{rows}_dequantize").argtypes = [C.POINTER(Bank), C.POINTER(desc), i32, i32, i32, i32, vp, vp, vp]

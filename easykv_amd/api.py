@@ -547,6 +547,52 @@ class _Run:
             if d != want:
                 raise ValueError(f"{what}: the window kernels {'with' if self.sinks is not None else 'without'} sinks are built for head_dim {want} "
                                  f"(this model: {d})")
+        # extension key: 'prefill' — None (default: the reference's strided prefill, byte for byte) or 'one_shot': one-shot prompt
+        # compression with pooled observation-window scores (include/easykv_hip.h, "one-shot prefill"; _one_shot_prefill): the prompt is
+        # prefilled densely, the keys are scored by the last `obs_window` queries alone, the ranking values are smoothed by a 1-D pooling of
+        # kernel size `score_pool` (odd; 1 = off) and op `score_pool_op` ('max' / 'avg'), and the cache is cut to the budget in ONE step.
+        self.prefill = cfg.get("prefill", None)
+        if self.prefill not in (None, "one_shot"):
+            raise ValueError(f"generation_config['prefill'] must be None or 'one_shot', not {self.prefill!r}")
+        self.one_shot = self.prefill == "one_shot"
+        if self.one_shot:      # (before any bank exists)
+            what = "generation_config['prefill'] = 'one_shot'"
+            self.obs_window, self.score_pool, self.score_pool_op = cfg.get("obs_window", 32), cfg.get("score_pool", 7), cfg.get("score_pool_op", "max")
+            isint = lambda x: isinstance(x, int) and not isinstance(x, bool)
+            if not (isint(self.obs_window) and self.obs_window >= 1):
+                raise ValueError(f"generation_config['obs_window'] must be an integer >= 1, not {self.obs_window!r}")
+            if not (isint(self.score_pool) and self.score_pool >= 1 and self.score_pool % 2 == 1):
+                raise ValueError(f"generation_config['score_pool'] is the kernel size of the pooling: an odd integer >= 1 (1 = off), not {self.score_pool!r}")
+            if self.score_pool_op not in ("max", "avg"):
+                raise ValueError(f"generation_config['score_pool_op'] must be 'max' or 'avg', not {self.score_pool_op!r}")
+            if kv_mode not in ("encoding", "auto"):
+                raise ValueError(f"{what} serves the modes 'encoding' and 'auto', not {kv_mode!r} (there is no prompt to compress in 'decoding', and 'ppl' "
+                                 "needs the logits of every strided forward)")
+            if streaming:
+                raise ValueError(f"{what} with streaming=True: the observation step would need RoPE-on-read over the whole prompt, which has no pooled form")
+            if policy not in SCORED:
+                raise ValueError(f"{what} needs a scored policy ('roco', 'h2o_head', 'tova'), not {policy!r}: recency / random score nothing to select by")
+            pooled = self.score_pool > 1
+            if pooled and policy == "roco":
+                raise ValueError(f"{what} with kv_policy='roco' and score_pool = {self.score_pool}: roco's two-stage rule has no single row to pool "
+                                 "(score_pool = 1 runs it unpooled)")
+            if pooled and policy == "tova" and kv_mode == "encoding":
+                raise ValueError(f"{what} with kv_policy='tova' in mode 'encoding' and score_pool = {self.score_pool}: encoding mode ranks one "
+                                 "head-averaged row, which has no pooled form (score_pool = 1, or mode 'auto')")
+            for name, on in (("attention sinks", self.sinks is not None), ("generation_config['sliding_window']", self.windows is not None),
+                             (f"attn_logit_softcapping = {self.logit_cap}", self.logit_cap is not None),
+                             ("generation_config['long_rows'] = True", bool(self.long_rows))):
+                if pooled and on:
+                    raise ValueError(f"{what} with score_pool = {self.score_pool} on a model with {name}: there is no pooled sink, window, capped or "
+                                     "long call (score_pool = 1 runs the observation step through the model's own call family)")
+            # The observation step is one chunk step of obs_window queries: its GQA-folded rows are cut into query blocks of at most 128
+            # rows (32 at head_dim 256 and on capped / sink / window models), so the GQA factor must fit a block; and the generic scorer keeps
+            # (max, 1 / sum) of every folded row in LDS next to its score rows: 4096 rows (32 KB) leave the key row its full width.
+            rep, block = hq // hkv, 32 if (d in PLAIN_KEYS_HEAD_DIMS or self.logit_cap is not None or self.sinks is not None or self.windows is not None) else 128
+            self.obs_max = 0 if rep > block else 4096 // rep
+            if self.obs_window > self.obs_max:
+                raise ValueError(f"{what}: obs_window = {self.obs_window} is more than one chunk step takes at this model's GQA factor {rep}; the largest "
+                                 f"that works is {self.obs_max}")
         self.dev = torch.device(model.device)
         for p in prompts:
             if p.dim() != 2 or p.shape[0] != 1:
@@ -817,6 +863,28 @@ def _strided_prefill(run, cache, input_ids, budget_p, idx, r_idx, tova_head_mean
     return logits_last, all_logits, all_ids
 
 
+def _one_shot_prefill(run, input_ids, budget, cap_decode, tova_head_mean):
+    """One-shot prompt compression (include/easykv_hip.h, "one-shot prefill"): two forwards and a hand-over.  ``budget``: the resolved
+    integer budget B < n; ``cap_decode``: the capacity the same mode's strided prefill would have given the cache.  -> (cache, last logits)"""
+    n, obs, sink = input_ids.shape[-1], run.obs_window, run.sink
+    if obs >= n or budget < obs + sink:
+        raise ValueError(f"generation_config['prefill'] = 'one_shot': obs_window = {obs} does not fit a prompt of {n} tokens cut to {budget} "
+                         f"(the {sink} sink tokens and the observation window are always kept); the largest that works is {max(0, min(n - 1, budget - sink))}")
+    # the prefill's peak memory is the whole prompt's K/V: a bank of n rows, released at the hand-over
+    cache = run.new_cache(n, n)
+    dense = StepPlan(policy="full", phase="prefill", accumulate=False)
+    run.forward(cache, input_ids[:, :n - obs], list(range(n - obs)), dense)                      # forward A
+    cache.bank.state_init(n, 2, obs)
+    plan = StepPlan(policy=run.policy, phase="prefill", accumulate=True, evict=True, budget=n, recent=obs, sink=sink, stride=obs,
+                    tova_head_mean=tova_head_mean and run.policy == "tova",      # (the head-averaged row is tova's alone; a pooled step refuses the flag)
+                    n_evict=n - budget, pool=run.score_pool, pool_op=run.score_pool_op)
+    logits = run.forward(cache, input_ids[:, n - obs:], list(range(n - obs, n)), plan).logits[:, -1, :]      # forward B: score, pool, select once
+    # hand-over: the decode steps stream the physical rows [0, extent) of every head; without it that is the prompt's n rows for the rest
+    # of the generation
+    cache.bank = cache.bank.hand_over(cap_decode + 8)
+    return cache, logits
+
+
 def _print_budget_line(mode, length, size, n_out=0, fed=0, budget_d=None):
     """The reference's report, one function of the mode and the counts.  ``size``: live slots when the line is printed — encoding:
     right after the prefill (:503); auto: after the last step (:751).  decoding (:364-365) reports the generated slots kept, derived
@@ -848,9 +916,13 @@ def _prefill(run: _Run, input_ids, kv_mode) -> Prefilled:
             logits = run.forward(cache, input_ids, list(range(length)), dense).logits[:, -1, :]
         else:
             budget_p, idx, r_idx = geometry("encoding", length, budget, stride)
-            # 'full' / unknown policy strings evict nothing (the reference's cache just grows): size for the whole prompt
-            cache = run.new_cache((idx + stride if run.evicting else length) + run.max_new_tokens, length)
-            logits = _strided_prefill(run, cache, input_ids, budget_p, idx, r_idx, True)[0]
+            if run.one_shot:      # (the resolved integer budget: B < length here)
+                cache, logits = _one_shot_prefill(run, input_ids, int(length * budget) if type(budget) == float else budget,
+                                                  idx + stride + run.max_new_tokens, True)
+            else:
+                # 'full' / unknown policy strings evict nothing (the reference's cache just grows): size for the whole prompt
+                cache = run.new_cache((idx + stride if run.evicting else length) + run.max_new_tokens, length)
+                logits = _strided_prefill(run, cache, input_ids, budget_p, idx, r_idx, True)[0]
         _print_budget_line("encoding", length, cache.get_seq_length())
         rule = dict(policy="full", score_off=0, budget_d=0, whole_cache=False)      # :508-526 plain decode, no eviction
     elif kv_mode == "encoding_decoding":                         # :530-753
@@ -859,10 +931,15 @@ def _prefill(run: _Run, input_ids, kv_mode) -> Prefilled:
         assert run.policy in white_lst, f"mode must be within {white_lst}, get {run.policy} instead"
         assert stride > 1, "auto mode needs stride > 1 (the reference asserts at easykv/easykv.py:666-669)"
         budget_p, idx, r_idx = geometry("auto", length, budget, stride)
-        cache = run.new_cache(idx + stride + 1, length)
-        logits = _strided_prefill(run, cache, input_ids, budget_p, idx, r_idx, False)[0]
-        # the score rows keep their first idx+1 columns (:666-669); the decode rules then run over the whole cache
-        rule = dict(policy=run.policy, score_off=0, budget_d=budget_p, whole_cache=True)
+        if run.one_shot and budget < length:
+            cache, logits = _one_shot_prefill(run, input_ids, budget, idx + stride + 1, False)
+            # the decode policy runs over the whole cache with budget B, on the score rows the observation step left
+            rule = dict(policy=run.policy, score_off=0, budget_d=budget, whole_cache=True)
+        else:
+            cache = run.new_cache(idx + stride + 1, length)
+            logits = _strided_prefill(run, cache, input_ids, budget_p, idx, r_idx, False)[0]
+            # the score rows keep their first idx+1 columns (:666-669); the decode rules then run over the whole cache
+            rule = dict(policy=run.policy, score_off=0, budget_d=budget_p, whole_cache=True)
     else:
         raise ValueError(f"unknown kv_mode {kv_mode!r}")
     return Prefilled(cache, logits, DecodePlanner(sink=run.sink, cur_pos=length, draw=run.draw, **rule), kv_mode, length)

@@ -151,7 +151,10 @@ static int call_attend(const EkvCall& c, const void* q, const void* k_new, const
         break;
       case EKV_RUN_DECODE_SCORE: e = sinks ? ekv_launch_decode_score_sink(sa, sinks, lc, s, bf16) : ekv_launch_decode_score(sa, tb, lc, s, bf16); break;
       case EKV_RUN_TOVA_MEAN: e = sinks ? ekv_launch_tova_headmean_sink(sa, sinks, lc, s) : ekv_launch_tova_headmean(sa, lc, s); break;
-      case EKV_RUN_SCORE_SELECT: e = ekv_launch_score_select(sa, lc, s, bf16); break;
+      // (a pooled plan: the EKV_POOL instances of the generic scorer, the struct's two words as the kernel's last argument)
+      case EKV_RUN_SCORE_SELECT:
+        e = P.pooled ? ekv_launch_score_select_pool(sa, EkvPoolArgs{c.pool->radius, c.pool->op}, lc, s, bf16) : ekv_launch_score_select(sa, lc, s, bf16);
+        break;
       // long calls (L.passes: the plain plan keeps its rows in scratch)
       case EKV_RUN_LONG_FOLD: e = ekv_launch_long_fold(sa, L.passes != 0, lc, s, bf16); break;
       case EKV_RUN_LONG_SCORE:
@@ -256,6 +259,20 @@ int ekv_win_step_attend(const ekv_bank* bank, const ekv_step* st, int32_t dtype,
                         const void* v_new, void* out, int32_t* evict_ids, const float* rope_cos, const float* rope_sin, void* workspace,
                         size_t workspace_bytes, void* stream) {
   return call_attend(win_call(bank, st, dtype, win), q, k_new, v_new, out, evict_ids, rope_cos, rope_sin, workspace, workspace_bytes, stream);
+}
+
+// pooled selection (include/easykv_hip.h, "pooled selection"): the _typed calls with the pooling struct behind the element type
+int ekv_pool_step_check(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_pool* pool) { return call_check(pool_call(bank, st, dtype, pool)); }
+int ekv_pool_step_info(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_pool* pool, int32_t* info, int32_t n_info) {
+  return call_info(pool_call(bank, st, dtype, pool), info, n_info);
+}
+size_t ekv_pool_workspace_bytes(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_pool* pool) {
+  return call_workspace_bytes(pool_call(bank, st, dtype, pool));
+}
+int ekv_pool_step_attend(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_pool* pool, const void* q, const void* k_new,
+                         const void* v_new, void* out, int32_t* evict_ids, const float* rope_cos, const float* rope_sin, void* workspace,
+                         size_t workspace_bytes, void* stream) {
+  return call_attend(pool_call(bank, st, dtype, pool), q, k_new, v_new, out, evict_ids, rope_cos, rope_sin, workspace, workspace_bytes, stream);
 }
 
 // FP8 K/V storage (include/easykv_hip.h, "kv8")

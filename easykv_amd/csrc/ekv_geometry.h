@@ -99,6 +99,19 @@ inline int ekv_score_select_threads(int64_t pairs, int64_t W, int64_t rows, bool
   return 512;
 }
 
+// ---- pooled generic scorer (ekv_score_select.inc, EKV_POOL build; the ekv_pool_* calls), 512 or 1024 threads ----------------------------
+// LDS plan: the unpooled scorer's, byte for byte (ekv_score_lds_bytes above).  The pooling stencil runs between accumulation and key
+// formation: it READS the score row S where it already sits (LDS; global scratch when `big`) and WRITES the selection keys, which have a
+// row of their own in LDS in either layout — the second row an out-of-place stencil needs is that key row, so nothing is added and no
+// halo is kept per thread.  Access pattern: thread t owns columns t, t + nt, ...; at tap d the lanes of a wave read 64 consecutive
+// words S[base + lane + d]: one LDS bank per lane, conflict-free, 2r + 1 reads per column.  Widest pooled row = the widest unpooled row:
+// ~10 000 columns with S in LDS, ~38 400 with S in scratch; beyond that the planner refuses the step (EKV_E_UNSUPPORTED, no launch).
+inline size_t ekv_score_pool_lds_bytes(int nt, int64_t W, int64_t rows, bool big) { return ekv_score_lds_bytes(nt, W, rows, big); }
+// the dispatch's block size (ekv_score_select_dispatch.hip): there is no 256-thread pooled build
+inline int ekv_score_pool_threads(int64_t pairs, int64_t W, int64_t rows, bool big) {
+  return ekv_score_select_threads(pairs, W, rows, big) == 1024 ? 1024 : 512;
+}
+
 // ---- long-row scorer (ekv_score_long.inc): sweep over column tiles, then one select workgroup per head -------------------------------
 constexpr int kLongSweepNT = 256;      // threads of a sweep workgroup, four consecutive columns each
 constexpr int kLongTile = 4 * kLongSweepNT;      // columns per sweep workgroup

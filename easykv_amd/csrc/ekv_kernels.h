@@ -84,6 +84,7 @@ struct EkvStepPlan {
   int32_t capped;       // an ekv_cap_* call: the launches run the EKV_SOFTCAP instances (chunk steps: the one-tile 16x16x32 build alone)
   int32_t sink;         // an ekv_sink_* call: the launches run the EKV_SINK instances (chunk steps likewise; decode steps in phase order F, no resident rows)
   int32_t window;       // an ekv_win_* call: the launches run the EKV_WINDOW instances (with sinks: the EKV_SINK + EKV_WINDOW ones); planned as the sink call
+  int32_t pooled;       // an ekv_pool_* call: EKV_RUN_SCORE_SELECT runs the EKV_POOL instances of the generic scorer; every in-kernel scorer tail is off
 };
 // The table of a batched decode step as the kernels' batch instances receive it: BY VALUE, behind the argument structs of the uniform
 // kernel (2304 bytes of the 4 KB a launch may carry).  Workgroup (head, entry ll) shadows the per-step fields of its argument structs
@@ -209,6 +210,13 @@ hipError_t ekv_launch_tova_headmean(const EkvScoreArgs& a, int layer_count, hipS
 hipError_t ekv_launch_score_select(const EkvScoreArgs& a, int layer_count, hipStream_t s, bool bf16);
 hipError_t ekv_launch_decode_fused(const EkvAttnArgs& a, const EkvScoreArgs& sc, const EkvSeqTable* tb, int head_dim, int count, int nw,
                                    hipStream_t s, bool bf16, EkvRows rows, bool capped = false);
+// Pooled selection (the ekv_pool_* calls; the EKV_POOL instances of ekv_score_select.inc): what the pooled scorer receives as its last
+// argument — the radius r >= 1 (kernel size 2r + 1) and the op (EKV_POOL_MAX / EKV_POOL_AVG) — and its launcher: the 512-thread build, or
+// the 1024-thread one where the unpooled dispatch would pick it (rows in scratch, one workgroup per CU).
+struct EkvPoolArgs {
+  int32_t radius, op;
+};
+hipError_t ekv_launch_score_select_pool(const EkvScoreArgs& a, const EkvPoolArgs& pool, int layer_count, hipStream_t s, bool bf16);
 // Attention sinks (the ekv_sink_* calls; EKV_SINK instances, ekv_common.h): the launchers of a sink step.  sinks: device fp32
 // [bank->n_layers][n_q_heads], indexed by bank layer.  16-bit rows, plain keys, one sequence; head_dim 64 / 128.  The chunk launcher runs
 // the 16x16x32 kernel in its one-tile build (pass: 0 one pass, 1 statistics pass, 2 exact pass; fuse_sc: the scorer as the one pass's tail).
@@ -375,6 +383,8 @@ __device__ __forceinline__ EkvScoreArgs ekv_batch_score_args(const EkvScoreArgs&
 #define EKV_FN_D_ELEM(fn, d, elem) EKV_FN_D_ELEM_(fn, d, elem)      // (EKV_CHUNK_LDS, EKV_RESIDENT)
 #define EKV_FN_SCORE_SELECT_(nt, elem) ekv_launch_score_select_nt##nt##_##elem
 #define EKV_FN_SCORE_SELECT(nt, elem) EKV_FN_SCORE_SELECT_(nt, elem)
+#define EKV_FN_SCORE_SELECT_POOL_(nt, elem) ekv_launch_score_select_pool_nt##nt##_##elem
+#define EKV_FN_SCORE_SELECT_POOL(nt, elem) EKV_FN_SCORE_SELECT_POOL_(nt, elem)
 // the manifest's words as the fields of a table entry: booleans, and EKV_ROWS_<rows> above
 #define EKV_IS_plain false
 #define EKV_IS_rope true

@@ -328,6 +328,7 @@ struct StepShape {
   bool capped;            // a capped call (ekv_plan_step): chunk steps on the one-tile build of the 16x16x32 kernel alone
   bool no_orders;         // the call runs instances without the phase order K (quantised rows, a batch, sinks): no two-round launch
   int Dblk;               // the head_dim a chunk step's query blocks are cut for: D, or kChunkNarrowD for a capped call (blocks of <= 32 rows)
+  bool pooled;            // a pooled call (resolve_call): the step ends in the generic scorer — no one-launch kernel, no in-kernel scorer tail
 };
 
 // ---- stage 1: tiling
@@ -351,7 +352,7 @@ void plan_tiling(const StepShape& s, EkvStepPlan* P) {
   // (the 5-column 8-wave instance with both phase orders, two workgroups per CU: what a launch of 1024 heads or more runs in two rounds)
   const bool rounds_shape = n == 1 && D == 128 && rep == 1 && !st->rope_on_read && s.slot_rows && s.scored && !s.no_orders && P->phys_extent <= 2304;
   P->fused_nw = ekv_decode_fused_nw(heads, rounds_shape);
-  if (n_split <= 0 && n == 1 && heads >= 256 && P->fused_nw == 8 &&
+  if (n_split <= 0 && n == 1 && heads >= 256 && P->fused_nw == 8 && !s.pooled &&
       ekv_decode_fused_supported(D, rep, T, P->t_pad, P->l_pad, st->n_evict, bank->cap, 8)) {
     n_split = 1;   // >= 1 head per CU: one 8-wave workgroup per head beats key-range splits + a second kernel (GQA shapes)
   }
@@ -363,7 +364,7 @@ void plan_tiling(const StepShape& s, EkvStepPlan* P) {
   // model: those launches hold 8..32 heads, and their column-sum pass + scorer run once over all layers).  The kernel's scorer is the
   // wide column-sum pass's tail (ekv_wide_tail.h): where that tail is off (EKV_NO_WIDE_TAIL) the step is planned as any other.  It is
   // laid out as an unsplit two-pass step of the wide-block kernel (the workspace of one is never touched).
-  P->resident = (n > 1 && !s.capped && st->phases == 0 && !s.slot_rows && st->defer_layers == 0 && st->two_pass == 0 && n_split <= 1 &&
+  P->resident = (n > 1 && !s.capped && !s.pooled && st->phases == 0 && !s.slot_rows && st->defer_layers == 0 && st->two_pass == 0 && n_split <= 1 &&
                  (st->policy == EKV_POLICY_H2O_HEAD || st->policy == EKV_POLICY_ROCO) && st->accumulate && !st->rope_on_read &&
                  P->n_qblocks == 1 && st->score_off >= 0 && st->score_off < T && ekv_attn_resident_supported(D, rep, n, T, s.W) &&
                  ekv_wide_tail_supported(s.W, 1)) ? 1 : 0;
@@ -517,7 +518,7 @@ bool plan_whole_step(const StepShape& s, EkvStepPlan* P, int* rc) {
   const i64 heads_now = (i64)st->layer_count * bank->n_kv_heads;
   *rc = EKV_OK;
   // whole decode step in one launch when no head has to be split
-  if (s.n == 1 && st->phases == 0 && P->n_split == 1 &&
+  if (s.n == 1 && st->phases == 0 && P->n_split == 1 && !s.pooled &&
       ekv_decode_fused_supported(s.D, s.rep, s.T, P->t_pad, P->l_pad, st->n_evict, bank->cap, P->fused_nw)) {
     if (s.slot_rows && !ekv_slot_rows_supported(bank, st, P->phys_extent, P->t_pad)) {
       *rc = EKV_E_UNSUPPORTED;
@@ -540,7 +541,7 @@ bool plan_whole_step(const StepShape& s, EkvStepPlan* P, int* rc) {
     return true;
   }
   // small-row chunk step (configs[1]: stride 8): one launch, logits in LDS, K and V read once
-  if (s.n > 1 && !s.capped && ekv_chunk_lds_supported(bank, st, P->phys_extent, s.scored) && (heads_now >= 256 || s.T <= 1024)) {
+  if (s.n > 1 && !s.capped && !s.pooled && ekv_chunk_lds_supported(bank, st, P->phys_extent, s.scored) && (heads_now >= 256 || s.T <= 1024)) {
     P->one_launch = 1;
     run(P, EKV_RUN_CHUNK_LDS, 1);
     return true;
@@ -580,7 +581,7 @@ int plan_ending(const StepShape& s, EkvStepPlan* P, StepEnding* end) {
   // streamed it and overlaps the K/V stream of the workgroups still running (tova_head_mean needs all heads of a layer first).
   // (not on the wide-block kernel: it has no scorer tail — an unsplit scored step of 33..64 rows that exports no logits, i.e. the
   //  first strided chunk of an encoding-mode prefill, runs as wide attention + scorer launch)
-  const bool fuse_chunk = n > 1 && ph == 0 && P->fold_in_kernel && !P->two_pass && !P->wide && scored && P->n_qblocks == 1 &&
+  const bool fuse_chunk = n > 1 && ph == 0 && !s.pooled && P->fold_in_kernel && !P->two_pass && !P->wide && scored && P->n_qblocks == 1 &&
                           (i64)rep * n <= 64 && !(st->policy == EKV_POLICY_TOVA && st->tova_head_mean && st->accumulate) &&
                           ekv_score_lds_bytes(256, shape) <= 64 * 1024 && st->n_split != -1;
   // Two-pass step on the wide-block kernel (whole step, or the flush of a layer-per-call step whose column-sum pass was deferred):
@@ -602,12 +603,12 @@ int plan_ending(const StepShape& s, EkvStepPlan* P, StepEnding* end) {
   P->flush_unsplit = flush_colsum && P->wide && P->two_pass && T <= s.max_rows &&
                      (size_t)st->layer_count * bank->n_kv_heads * P->n_col_parts >= 512;
   const i64 tail_wgs = (i64)(P->flush_unsplit ? 1 : P->n_split) * P->n_col_parts;
-  const bool tail_step = tail_shape && (ph == 0 || flush_colsum) && ekv_wide_tail_supported(W, tail_wgs);
+  const bool tail_step = tail_shape && !s.pooled && (ph == 0 || flush_colsum) && ekv_wide_tail_supported(W, tail_wgs);
 
   const bool wants_scorer = ph == 0 || (ph & (2 | 8));
   const bool fold_only = (!scored && st->n_evict == 0) || !wants_scorer;
   const bool range_only = wants_scorer && st->policy == EKV_POLICY_RANGE;
-  const bool fast_scorer = wants_scorer && !fold_only && !range_only && !fuse_chunk && ekv_decode_score_supported(shape);
+  const bool fast_scorer = wants_scorer && !fold_only && !range_only && !fuse_chunk && !s.pooled && ekv_decode_score_supported(shape);
   const bool generic_scorer = wants_scorer && !fold_only && !range_only && !fuse_chunk && !fast_scorer;
   if (generic_scorer && !s.long_rows && ekv_score_lds_bytes(shape.big_rows != nullptr ? 1024 : 512, shape) > 160 * 1024)
     return EKV_E_UNSUPPORTED;   // even the selection keys alone exceed one CU's LDS (W > ~39 000): see DESIGN.md "size limits"
@@ -730,7 +731,7 @@ void plan_long_layout(const StepShape& s, EkvStepPlan* P) {
 // EKV_RUN_LONG_SCORE, two kernels; a preceding EKV_RUN_TOVA_MEAN stays; EKV_RUN_LONG_FOLD in front where the generic scorer would have
 // folded the output itself), the width refusal of plan_ending does not apply, and the workspace grows by that scorer's scratch
 // (plan_long_layout).  A step that ends anywhere else plans field for field as the plain call.
-int ekv_plan_step(const ekv_bank* bank, const ekv_step* step, EkvStepPlan* P, bool long_rows, bool capped, bool no_orders) {
+int ekv_plan_step(const ekv_bank* bank, const ekv_step* step, EkvStepPlan* P, bool long_rows, bool capped, bool no_orders, bool pooled) {
   *P = EkvStepPlan{};
   P->key_rows = -1;
   const int bank_rc = check_bank(bank);
@@ -753,6 +754,7 @@ int ekv_plan_step(const ekv_bank* bank, const ekv_step* step, EkvStepPlan* P, bo
   s.long_rows = long_rows;
   s.no_orders = no_orders;
   s.capped = capped;
+  s.pooled = pooled;
   s.Dblk = capped ? kChunkNarrowD : s.D;
 
   plan_tiling(s, P);
@@ -888,14 +890,28 @@ int resolve_call(const EkvCall& c, EkvResolved* r) {
   // step whose GQA factor exceeds a block).  The head-mean TOVA row (tova_head_mean) is rebuilt from the exported logits, whose masked
   // columns are -inf (exp -> 0), by the plain build of its kernel, or by the sink build where the call has sinks.
   if (c.window && !ekv_win_ok(c.win, bank)) return EKV_E_ARG;
-  const int variants = (c.long_rows ? 1 : 0) + (c.capped ? 1 : 0) + (c.sink || c.window ? 1 : 0);
+  // Pooled calls (ekv_pool_*), likewise stated once.  "Pooled" is one more independent variant of a call, combined with nothing else: its
+  // entry points spell 16-bit rows and one sequence, and there is no pooled long, capped, sink or window call.  A NULL struct, a radius
+  // < 1 and an unknown op are argument errors, behind the element type and before anything is planned.  The ONE rule: a pooled step plans
+  // as the plain call of the same (bank, step, dtype) with every in-kernel scorer tail switched off — no one-launch decode step, no
+  // fast scorer behind the split kernel, no logits-in-LDS kernel, no scorer as the tail of the 16x16 one-pass kernel or of the wide
+  // column-sum pass, no logits-resident kernel — so that wherever the step scores it ends in EKV_RUN_SCORE_SELECT (whole steps, phases
+  // & 2, phases & 8, the deferred flush over all layers), which call_attend runs on the EKV_POOL instances of the generic scorer.  The
+  // tiling, the scheme (two passes, or one pass with exported logits), the workspace layout and the width bound are the plain call's
+  // rules: the stencil reads the score row where it sits and writes the key row, so the pooled LDS plan is the unpooled one and the widest
+  // pooled row is the generic scorer's (ekv_geometry.h).  Refused with zero launches and zero bytes (EKV_E_UNSUPPORTED): a policy other
+  // than h2o_head / tova (roco's two-stage rule has no single row to pool; EKV_POLICY_RANGE and EKV_POLICY_NONE have no row at all),
+  // RoPE-on-read, tova_head_mean, slot-indexed score rows, a row beyond the generic scorer's width.
+  if (c.pooled && !(c.pool != nullptr && c.pool->radius >= 1 && (c.pool->op == EKV_POOL_MAX || c.pool->op == EKV_POOL_AVG))) return EKV_E_ARG;
+  const int variants = (c.long_rows ? 1 : 0) + (c.capped ? 1 : 0) + (c.sink || c.window ? 1 : 0) + (c.pooled ? 1 : 0);
   const bool sinkish = c.sink || c.window;
   const int rc = (variants && (quant || c.batch || variants > 1))
                      ? EKV_E_UNSUPPORTED
-                     : ekv_plan_step(bank, r->step, P, c.long_rows, c.capped || sinkish, quant || c.batch || sinkish || c.capped);
+                     : ekv_plan_step(bank, r->step, P, c.long_rows, c.capped || sinkish, quant || c.batch || sinkish || c.capped, c.pooled);
   P->capped = c.capped ? 1 : 0;
   P->sink = c.sink ? 1 : 0;
   P->window = c.window ? 1 : 0;
+  P->pooled = c.pooled ? 1 : 0;
   P->bf16 = c.dtype == EKV_DTYPE_BF16;
   P->rows = c.rows;
   P->batch = c.batch;
@@ -908,7 +924,7 @@ int resolve_call(const EkvCall& c, EkvResolved* r) {
       P->bytes = plain.bytes, P->big_rows = plain.big_rows, P->key_rows = -1;
     }
     P->one_launch = P->n_launches = P->n_list = P->long_rows = P->long_tiles = 0;
-    if (c.batch || c.capped || sinkish) P->bytes = 0;      // (nothing will run: ekv_batch_workspace_bytes of a refused table, ekv_cap_ / ekv_sink_workspace_bytes of a refused step, is 0)
+    if (c.batch || c.capped || sinkish || c.pooled) P->bytes = 0;      // (nothing will run: ekv_batch_workspace_bytes of a refused table, ekv_cap_ / ekv_sink_ / ekv_pool_workspace_bytes of a refused step, is 0)
     return code;
   };
   const ekv_step* st = c.step;
@@ -922,6 +938,8 @@ int resolve_call(const EkvCall& c, EkvResolved* r) {
   if (c.capped && (st->rope_on_read || (bank->head_dim != 128 && bank->head_dim != kChunkNarrowD))) return refuse(EKV_E_UNSUPPORTED);
   if (c.sink && (st->rope_on_read || (bank->head_dim != 64 && bank->head_dim != 128))) return refuse(EKV_E_UNSUPPORTED);
   if (c.window && (st->rope_on_read || bank->head_dim != (c.sink ? 64 : 128))) return refuse(EKV_E_UNSUPPORTED);
+  if (c.pooled && (st->rope_on_read || st->tova_head_mean || (st->policy != EKV_POLICY_H2O_HEAD && st->policy != EKV_POLICY_TOVA)))
+    return refuse(EKV_E_UNSUPPORTED);
   if (quant && (st->q_len != 1 || st->rope_on_read || !ekv_rows_head_dim(c.rows, bank->head_dim) ||
                 bank->n_q_heads / bank->n_kv_heads > kRowsRules[c.rows].max_rep))
     return refuse(EKV_E_UNSUPPORTED);
@@ -964,6 +982,7 @@ int call_info(const EkvCall& c, int32_t* info, int32_t n_info) {
   if (c.capped && !(c.softcap > 0.f && c.softcap <= 3.0e38f)) return EKV_E_ARG;      // (a cap no step can be planned with)
   if (c.sink && c.sinks == nullptr) return EKV_E_ARG;
   if (c.window && !ekv_win_ok(c.win, r.bank)) return EKV_E_ARG;
+  if (c.pooled && !(c.pool != nullptr && c.pool->radius >= 1 && (c.pool->op == EKV_POOL_MAX || c.pool->op == EKV_POOL_AVG))) return EKV_E_ARG;
   if (c.rows != EKV_ROWS_kv16 && !r.bank) return EKV_E_ARG;
   if (int e = check_bank(r.bank)) return e;
   if (!c.step || (c.batch && !c.seqs) || !info || n_info < 1) return EKV_E_ARG;

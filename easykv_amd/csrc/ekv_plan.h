@@ -53,7 +53,9 @@ EkvScoreArgs score_args(const ekv_bank* bank, const ekv_step* st, const EkvStepP
 // long_rows: the plan of a long call (ekv_long_*; the rule is stated once, at ekv_plan_step in ekv_plan.cpp)
 // capped: the plan of a capped call (ekv_cap_*; the rule is stated once, at resolve_call in ekv_plan.cpp); a sink call (ekv_sink_*) tiles
 // its chunk steps by the same rule and passes true as well
-int ekv_plan_step(const ekv_bank* bank, const ekv_step* step, EkvStepPlan* P, bool long_rows = false, bool capped = false, bool no_orders = false);
+// pooled: the plan of a pooled call (ekv_pool_*; the rule is stated once, at resolve_call in ekv_plan.cpp): every in-kernel scorer tail off
+int ekv_plan_step(const ekv_bank* bank, const ekv_step* step, EkvStepPlan* P, bool long_rows = false, bool capped = false, bool no_orders = false,
+                  bool pooled = false);
 
 // ---- one call path --------------------------------------------------------------------------------------------------------------
 // A call of the step family as its entry points spell it, along two independent axes: the row format of the bank (the untyped / _typed
@@ -87,6 +89,8 @@ struct EkvCall {
   const float* sinks;      // ... the sinks, device fp32 [bank->n_layers][n_q_heads]: only tested for NULL here (an argument error)
   bool window;             // an ekv_win_* call: sliding windows (16-bit rows, one sequence, plain keys; with sinks head_dim 64, alone 128)
   const ekv_win* win;      // ... its struct (include/easykv_hip.h): NULL, NULL tok_pos / windows or a negative window are argument errors
+  bool pooled;             // an ekv_pool_* call: pooled selection (16-bit rows, one sequence, h2o_head / tova, no other variant)
+  const ekv_pool* pool;    // ... its struct: NULL, radius < 1 or an unknown op are argument errors
 };
 inline EkvCall step_call(const ekv_bank* bank, const ekv_step* st, int32_t dtype) { return {bank, st, dtype, EKV_ROWS_kv16, {}, false, nullptr, 0}; }
 inline EkvCall batch_call(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_seq* seqs, int32_t n_seq) {
@@ -102,6 +106,9 @@ inline EkvCall sink_call(const ekv_bank* bank, const ekv_step* st, int32_t dtype
 // (win->s_aux != NULL: the window joins the sink variant; the struct itself is checked in resolve_call)
 inline EkvCall win_call(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_win* win) {
   return {bank, st, dtype, EKV_ROWS_kv16, {}, false, nullptr, 0, false, false, 0.f, win != nullptr && win->s_aux != nullptr, win ? win->s_aux : nullptr, true, win};
+}
+inline EkvCall pool_call(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_pool* pool) {
+  return {bank, st, dtype, EKV_ROWS_kv16, {}, false, nullptr, 0, false, false, 0.f, false, nullptr, false, nullptr, true, pool};
 }
 // the quantised calls: the same two with a row format and its planes
 inline EkvCall kv8_call(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_kv8* q8) {

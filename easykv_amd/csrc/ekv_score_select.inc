@@ -27,6 +27,18 @@ constexpr int kNWV = kNT / 64;
 
 #include "ekv_blk_select.h"   // Blk, blk_* reductions, blk_mark_k_smallest (shared with ekv_score_long.inc)
 
+// EKV_POOL = 1 (the EKV_SCORE_SELECT_POOL lines of the manifest): the pooled build of the scorer (include/easykv_hip.h, "pooled selection").
+// The kernel takes (radius, op) as its LAST argument; EKV_POOL_ONLY(...) spells what exists only in that build and vanishes everywhere
+// else, so every other instance — and the chunk kernel's tail, which includes this body — keeps its tokens.
+#ifndef EKV_POOL
+#define EKV_POOL 0
+#endif
+#if EKV_POOL
+#define EKV_POOL_ONLY(...) __VA_ARGS__
+#else
+#define EKV_POOL_ONLY(...)
+#endif
+
 // Wide logits sweep of the scorer (see the call site): thread -> 4 consecutive columns, 8 rows (IB queries x REP heads) of
 // 16-byte loads in flight.  REP is a compile-time constant so that the per-batch arrays stay in registers.
 template <int REP>
@@ -122,7 +134,7 @@ __device__ __forceinline__ void wide_sweep(const EkvScoreArgs& a, int tid, size_
 // column: W up to ~39 000.  Same code, same arithmetic, same summation order — only where sS / sQ / sC point differs; the template
 // keeps the LDS address space provable (ds_read instead of flat loads) in the build every other shape uses.
 template <bool BIG = false>
-__device__ void ekv_score_select_body(const EkvScoreArgs& a, const int h, const int ll, char* smem) {
+__device__ void ekv_score_select_body(const EkvScoreArgs& a, const int h, const int ll, char* smem EKV_POOL_ONLY(, const EkvPoolArgs& pool)) {
   const int gl = a.layer_begin + ll;
   const int T = a.n_slots, n = a.q_len, D = a.head_dim;
   const int rep = a.n_q_heads / a.n_kv_heads;
@@ -342,6 +354,45 @@ __device__ void ekv_score_select_body(const EkvScoreArgs& a, const int h, const 
       blk_mark_k_smallest(b, sKey, W, k, sHist);
     }
   } else {  // h2o_head / tova: k smallest accumulated scores inside the candidate window
+#if EKV_POOL
+    // Pooled selection: the ranking value of a candidate j in R = [win_lo, W - win_tail) is the max / the average of the score row over
+    // [j - r, j + r] clipped to R (torch's max_pool1d / avg_pool1d on the slice s[R], stride 1, padding r: the -inf padding of max leaves
+    // an edge window fewer members, the zero padding of avg adds nothing to the sum and the divisor stays 2r + 1).  The stencil reads the
+    // score row where it sits (sS: LDS, or the L2-resident scratch of the BIG build) and writes the selection keys (sKey: LDS in every
+    // build) — the second row the stencil needs is the key row the select needs anyway, so the LDS plan is the unpooled scorer's.
+    // Thread tid owns columns tid, tid + kNT, ...: lane l of a wave reads word base + l at every tap, one bank per lane, no conflict.
+    // avg: the sum in ascending index order, one IEEE division (the library is built with -ffp-contract=off).  max: fmaxf drops a NaN,
+    // so a window that holds one is set to NaN by hand; ekv_fkey ranks NaN largest.  The pooled values rank only: sS is not modified.
+    {
+      const int lo = a.win_lo, hi = W - a.win_tail, r = pool.radius;
+      const float n_taps = (float)(2 * r + 1);
+      for (int j = b.tid; j < W; j += kNT) {
+        uint32_t key = 0xFFFFFFFFu;
+        if (j >= lo && j < hi) {
+          const int j0 = max(lo, j - r), j1 = min(hi - 1, j + r);
+          float v;
+          if (pool.op == EKV_POOL_AVG) {
+            float acc = 0.f;
+            for (int i = j0; i <= j1; ++i) acc += sS[i];
+            v = acc / n_taps;
+          } else {
+            float m = EKV_NEG_INF;
+            bool has_nan = false;
+            for (int i = j0; i <= j1; ++i) {
+              const float x = sS[i];
+              has_nan = has_nan || x != x;
+              m = fmaxf(m, x);
+            }
+            v = has_nan ? __builtin_nanf("") : m;
+          }
+          key = ekv_fkey(v);
+        }
+        sKey[j] = key;
+      }
+      __syncthreads();
+      blk_mark_k_smallest(b, sKey, W, k, sHist);
+    }
+#else
     if (k == 1) {
       unsigned long long best = ~0ull;
       for (int j = a.win_lo + b.tid; j < W - a.win_tail; j += kNT) {
@@ -355,6 +406,7 @@ __device__ void ekv_score_select_body(const EkvScoreArgs& a, const int h, const 
       __syncthreads();
       blk_mark_k_smallest(b, sKey, W, k, sHist);
     }
+#endif
   }
   const bool roco = a.policy == EKV_POLICY_ROCO;
   EKV_SS_STAMP(4);
@@ -454,7 +506,11 @@ __device__ void ekv_score_select_body(const EkvScoreArgs& a, const int h, const 
 }
 
 #ifndef EKV_SS_DEVICE_ONLY
-#if EKV_BF16   // (bf16 instances: the scorer under a tagged name; the head-mean row writes no 16-bit data and is built once)
+#if EKV_POOL && EKV_BF16      // (the pooled instances: the scorer alone, under names of its own)
+#define ekv_score_select_kernel ekv_score_select_kernel_pool_bf16
+#elif EKV_POOL
+#define ekv_score_select_kernel ekv_score_select_kernel_pool
+#elif EKV_BF16   // (bf16 instances: the scorer under a tagged name; the head-mean row writes no 16-bit data and is built once)
 #define ekv_score_select_kernel ekv_score_select_kernel_bf16
 #endif
 // EKV_SINK = 1 (the EKV_TOVA_MEAN_SINK line of the manifest): the head-mean TOVA row of a sink call (ekv_common.h, "attention sinks"), the
@@ -464,14 +520,14 @@ __device__ void ekv_score_select_body(const EkvScoreArgs& a, const int h, const 
 #define ekv_tova_headmean_kernel ekv_tova_headmean_kernel_sink
 #else
 template <bool BIG>
-__global__ void __launch_bounds__(kNT) ekv_score_select_kernel(const EkvScoreArgs a) {
+__global__ void __launch_bounds__(kNT) ekv_score_select_kernel(const EkvScoreArgs a EKV_POOL_ONLY(, const EkvPoolArgs pool)) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  ekv_score_select_body<BIG>(a, blockIdx.x, blockIdx.y, smem);
+  ekv_score_select_body<BIG>(a, blockIdx.x, blockIdx.y, smem EKV_POOL_ONLY(, pool));
 }
 
 #endif  // !EKV_SINK
 
-#if !EKV_BF16
+#if !EKV_BF16 && !EKV_POOL
 // 'tova' in encoding/ppl mode: one last-query row averaged over ALL kv heads (easykv/easykv.py:456, :847)
 __global__ void __launch_bounds__(kNT) ekv_tova_headmean_kernel(const EkvScoreArgs a EKV_SINK_ONLY(, const float* const sinks)) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -535,14 +591,18 @@ hipError_t ekv_launch_tova_headmean_sink(const EkvScoreArgs& a, const float* sin
   return hipGetLastError();
 }
 #else
+#if EKV_POOL
+hipError_t EKV_FN_SCORE_SELECT_POOL(EKV_SS_NT, EKV_ELEM)(const EkvScoreArgs& a, const EkvPoolArgs& pool, int layer_count, hipStream_t s) {
+#else
 hipError_t EKV_FN_SCORE_SELECT(EKV_SS_NT, EKV_ELEM)(const EkvScoreArgs& a, int layer_count, hipStream_t s) {
+#endif
   const size_t lds = ekv_score_lds_bytes(kNT, a);
   if (lds > 160 * 1024) return hipErrorInvalidValue;
 #if EKV_SS_NT == 1024
   if (a.big_rows != nullptr) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ekv_score_select_kernel<true>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(ekv_score_select_kernel<true>, dim3(a.n_kv_heads, layer_count), dim3(kNT), lds, s, a);
+    hipLaunchKernelGGL(ekv_score_select_kernel<true>, dim3(a.n_kv_heads, layer_count), dim3(kNT), lds, s, a EKV_POOL_ONLY(, pool));
     return hipGetLastError();
   }
 #endif
@@ -550,11 +610,11 @@ hipError_t EKV_FN_SCORE_SELECT(EKV_SS_NT, EKV_ELEM)(const EkvScoreArgs& a, int l
   if (lds > 48 * 1024)
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ekv_score_select_kernel<false>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL(ekv_score_select_kernel<false>, dim3(a.n_kv_heads, layer_count), dim3(kNT), lds, s, a);
+  hipLaunchKernelGGL(ekv_score_select_kernel<false>, dim3(a.n_kv_heads, layer_count), dim3(kNT), lds, s, a EKV_POOL_ONLY(, pool));
   return hipGetLastError();
 }
 
-#if !EKV_BF16
+#if !EKV_BF16 && !EKV_POOL
 hipError_t EKV_SS_CAT(ekv_launch_tova_headmean_nt, EKV_SS_NT)(const EkvScoreArgs& a, int layer_count, hipStream_t s) {
   const size_t lds = (size_t)a.n_q_heads * 2 * 4;
   hipLaunchKernelGGL(ekv_tova_headmean_kernel, dim3(layer_count), dim3(kNT), lds, s, a);

@@ -53,6 +53,33 @@ hipError_t ekv_launch_score_select(const EkvScoreArgs& a, int layer_count, hipSt
   }
 }
 
+// ---- the pooled instances (ekv_instances_later.def, EKV_SCORE_SELECT_POOL): 512 threads, or 1024 wherever the unpooled rule above
+// picks them (rows in scratch; one workgroup per CU).  Where that rule picks 256 threads the pooled call runs 512.
+typedef hipError_t EkvSelectPoolFn(const EkvScoreArgs&, const EkvPoolArgs&, int layer_count, hipStream_t);
+#define EKV_SCORE_SELECT_POOL(nt, elem) EkvSelectPoolFn EKV_FN_SCORE_SELECT_POOL(nt, elem);
+#include "ekv_instances.def"
+
+namespace {
+struct SelectPoolInstance {
+  int threads;
+  bool bf16;
+  EkvSelectPoolFn* fn;
+};
+const SelectPoolInstance kSelectPool[] = {
+#define EKV_SCORE_SELECT_POOL(nt, elem) {nt, EKV_IS_##elem, EKV_FN_SCORE_SELECT_POOL(nt, elem)},
+#include "ekv_instances.def"
+};
+}  // namespace
+
+hipError_t ekv_launch_score_select_pool(const EkvScoreArgs& a, const EkvPoolArgs& pool, int layer_count, hipStream_t s, bool bf16) {
+  const int64_t W = (int64_t)a.n_slots - a.score_off;      // (a pooled step is scored: h2o_head / tova)
+  const int64_t rows = a.colsum != nullptr ? 0 : (int64_t)(a.n_q_heads / a.n_kv_heads) * a.q_len;
+  const int threads = ekv_score_pool_threads((int64_t)a.n_kv_heads * layer_count, W, rows, a.big_rows != nullptr);
+  for (const SelectPoolInstance& in : kSelectPool)
+    if (in.threads == threads && in.bf16 == bf16) return in.fn(a, pool, layer_count, s);
+  return hipErrorInvalidValue;
+}
+
 hipError_t ekv_launch_tova_headmean(const EkvScoreArgs& a, int layer_count, hipStream_t s) {
   return ekv_launch_tova_headmean_nt512(a, layer_count, s);
 }

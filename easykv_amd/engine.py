@@ -37,6 +37,9 @@ class StepPlan:
     streaming: bool = False
     n_split: int = 0
     two_pass: int = 0           # scored chunk steps: 0 auto, 1 force the two-pass kernels, -1 force one pass
+    n_evict: Optional[int] = None   # prefill steps: victims per head (None: ``stride``); one-shot prompt compression evicts n - budget at once
+    pool: int = 1               # pooled selection (include/easykv_hip.h): kernel size of the pooling of the ranking values, odd; 1 = off
+    pool_op: str = "max"        # ... 'max' or 'avg'
 
 
 # The row formats of a quantised bank, by ``kv_quant`` (include/easykv_hip.h, "kv8" / "kv4" / "kv6" / "kv84" / "kv164"): everything the bank, the batch and the
@@ -302,6 +305,7 @@ class KVBank:
         self._ring_pos = 0
         self._score_done = [None] * n_layers
         self._defer = None      # deferred-scorer state of the token step in flight (attend(..., defer=True) ... flush())
+        self._pool_fams = {}    # (radius, op) -> the pooled family's calls and struct (_family)
         self.arrive = torch.zeros(n_layers, n_kv_heads, dtype=torch.int32, device=dev)     # arrival counters of the in-kernel fold
         self._bank = Bank(_ptr(self.k), _ptr(self.v), self._slot_of_pos.data_ptr(),
                           self._score_sum.data_ptr() if scored else None, self._score_sq.data_ptr() if scored else None,
@@ -575,15 +579,40 @@ class KVBank:
         check(getattr(self.lib, call)(C.byref(self._bank), *self._desc_ref, _lib.DTYPE_F32, layer, 1, self.cap, _ptr(k), _ptr(v), self._stream()), call)
         return k, v
 
-    def _step_check(self, st):
-        return self._check_fn(C.byref(self._bank), C.byref(st), self._dt, *self._desc_ref)
+    def _family(self, plan=None):
+        """(check, info, workspace, attend, leading descriptor arguments) of the call family a step of ``plan`` goes to: the bank's own,
+        or — a property of the STEP, ``plan.pool > 1`` — the pooled family (ekv_pool_*), whose struct stands behind the dtype.  There is
+        no pooled capped, sink, window, long or quantised call: such a bank raises :class:`EkvError`."""
+        if plan is None or plan.pool == 1:
+            return self._check_fn, self._info_fn, self._ws_fn, self._attend_fn, self._desc_ref
+        if not (isinstance(plan.pool, int) and not isinstance(plan.pool, bool) and plan.pool >= 3 and plan.pool % 2 == 1):
+            raise ValueError(f"StepPlan.pool is the kernel size of the pooling: 1 (off) or an odd integer >= 3, not {plan.pool!r}")
+        if plan.pool_op not in _lib.POOL_OPS:
+            raise ValueError(f"StepPlan.pool_op must be 'max' or 'avg', not {plan.pool_op!r}")
+        for what, on in (("logit_cap", self.logit_cap is not None), ("sinks", self.sinks is not None), ("windows", self.windows is not None),
+                         ("long_rows=True", self.long_rows), (f"kv_quant={self.kv_quant!r}", self._fmt is not None)):
+            if on:
+                raise _lib.EkvError(f"a pooled step (StepPlan.pool = {plan.pool}) on a bank created with {what}: there is no pooled "
+                                    f"{what.split('=')[0].replace('_', ' ')} call (pooled selection serves plain 16-bit banks)")
+        key = (plan.pool // 2, _lib.POOL_OPS[plan.pool_op])
+        fam = self._pool_fams.get(key)
+        if fam is None:
+            desc = _lib.Pool(*key)      # (kept alive with the bank: a deferred token step caches the reference)
+            fam = self._pool_fams[key] = tuple(getattr(self.lib, _lib.POOL_CALLS[what]) for what in _lib.STEP_CALLS) + ((C.byref(desc),), desc)
+        return fam[:5]
 
-    def _step_ws_bytes(self, st):
-        return self._ws_fn(C.byref(self._bank), C.byref(st), self._dt, *self._desc_ref)
+    def _step_check(self, st, fam=None):
+        fam = fam or self._family()
+        return fam[0](C.byref(self._bank), C.byref(st), self._dt, *fam[4])
 
-    def _step_attend(self, st, *args):
+    def _step_ws_bytes(self, st, fam=None):
+        fam = fam or self._family()
+        return fam[2](C.byref(self._bank), C.byref(st), self._dt, *fam[4])
+
+    def _step_attend(self, st, *args, fam=None):
+        fam = fam or self._family()
         _lib.set_resident_bytes(self.resident_bytes)
-        return self._attend_fn(C.byref(self._bank), C.byref(st), self._dt, *self._desc_ref, *args)
+        return fam[3](C.byref(self._bank), C.byref(st), self._dt, *fam[4], *args)
 
     # -- plumbing -----------------------------------------------------------------------------
     def _stream(self):
@@ -702,6 +731,38 @@ class KVBank:
         check(self.lib.ekv_gather_ordered(C.byref(self._bank), layer_begin, lc, t, _ptr(k), _ptr(v), self._stream()), "ekv_gather_ordered")
         return k, v
 
+    def hand_over(self, cap):
+        """A new bank of capacity ``cap`` that holds this bank's live rows and nothing else: step 4 of the one-shot prefill
+        (include/easykv_hip.h), where a prompt-sized bank has just been cut to the budget in one step and its ``T`` retained rows lie
+        scattered over ``extent`` = the prompt's physical rows.  In the new bank the rows of every head sit in logical order in the physical
+        rows ``[0, T)`` (``ekv_gather_ordered`` out of this bank, ``load_rows`` into the fresh one, whose slot map is the identity), so
+        ``extent == T`` and a one-launch decode step streams ``T`` rows, not the prompt's.  The score rows' first ``T`` columns, the
+        softmax scale / cap / sinks and — a window bank — the rows' token positions and the tokens seen are carried over.  Every layer must
+        hold the same number of rows; a quantised bank, a bank on the slot-indexed layout mid-capture or with an open deferred step
+        raises.  This bank is left as it is: the caller drops it."""
+        self._quant_refuse(True, "hand_over (a row move)")
+        if self._defer is not None and self._defer["pending"]:
+            raise _lib.EkvError("hand_over(): a deferred token step is open (flush() first)")
+        t = self.n_slots[0]
+        if any(n != t for n in self.n_slots):
+            raise _lib.EkvError(f"hand_over(): the layers hold different numbers of rows {sorted(set(self.n_slots))}")
+        if t < 1 or cap < t:
+            raise ValueError(f"hand_over(cap={cap}): the bank holds {t} rows per head")
+        self.join()
+        scored = self._score_sum is not None
+        extra = {k: v for k, v in (("logit_cap", self.logit_cap), ("sm_scale", self.sm_scale), ("sinks", self.sinks),
+                                   ("windows", None if self.windows is None else list(self.windows))) if v is not None}
+        new = KVBank(self.n_layers, self.n_q_heads, self.n_kv_heads, self.head_dim, cap, device=self.device, scored=scored, dtype=self.dtype,
+                     long_rows=self.long_rows, **extra)
+        new.resident_bytes = self.resident_bytes
+        k, v = self.ordered_kv()
+        new.load_rows(k, v, 0, tok_pos=None if self.windows is None else self.ordered_tok_pos())
+        if scored:
+            for name in ("_score_sum", "_score_sq", "_score_cnt"):      # (ordered layout: ordered_kv brought this bank back to it)
+                getattr(new, name)[:, :, :t].copy_(getattr(self, name)[:, :, :t])
+        new._tokens = list(self._tokens)
+        return new
+
     def compact_inplace(self, evict_ids, layer_begin=0):
         """Reference-shaped physical compaction for a bank kept in identity layout."""
         lc, _, kk = evict_ids.shape
@@ -740,9 +801,9 @@ class KVBank:
                 st.roco_k1 = plan.budget - rw
                 st.count_add, st.count_tail_step = 1.0, 0.0
             else:
-                st.n_evict = plan.stride
+                st.n_evict = plan.stride if plan.n_evict is None else plan.n_evict
                 st.win_lo, st.win_tail = plan.sink, plan.recent
-                st.roco_k1 = max(plan.budget - plan.recent - plan.sink, plan.stride)
+                st.roco_k1 = max(plan.budget - plan.recent - plan.sink, st.n_evict)
                 st.count_add, st.count_tail_step = float(plan.stride), -1.0
             if st.policy == _lib.POLICY_RANGE:
                 st.range_start = plan.range_start
@@ -752,7 +813,7 @@ class KVBank:
         """(n_split, fused) the library will use for this step."""
         st = self.make_step(plan, q_len, layer_begin, self.n_layers - layer_begin if layer_count is None else layer_count)
         st.phases = phases
-        if self._fmt is not None or self.long_rows or self.logit_cap is not None or self.sinks is not None or self.windows is not None:      # (the dry run of the bank's own family: a step the bank refuses plans as not fused)
+        if self._fmt is not None or self.long_rows or self.logit_cap is not None or self.sinks is not None or self.windows is not None or plan.pool != 1:      # (the dry run of the bank's own family / the step's: a step it refuses plans as not fused)
             info = self.step_info(plan, q_len, layer_begin, layer_count, phases)
             return info["n_split"], bool(info["fused"])
         ns, fu = C.c_int32(0), C.c_int32(0)
@@ -765,7 +826,8 @@ class KVBank:
         st.phases = phases
         n_info = _lib.LONG_INFO_N if self.long_rows else 10
         info = (C.c_int32 * n_info)()
-        check(self._info_fn(C.byref(self._bank), C.byref(st), self._dt, *self._desc_ref, info, n_info), self._info_fn.__name__)
+        fam = self._family(plan)
+        check(fam[1](C.byref(self._bank), C.byref(st), self._dt, *fam[4], info, n_info), fam[1].__name__)
         keys = ("n_split", "fused", "two_pass", "wide", "n_qblocks", "qb_rows", "n_col_parts", "fold_in_kernel", "n_launches", "fused_order",
                 "long_scorer", "long_tiles")      # (the last two: a long_rows bank only)
         return dict(zip(keys, (int(x) for x in info)))
@@ -840,15 +902,16 @@ class KVBank:
             if d is not None and d["pending"]:
                 raise _lib.EkvError("attend(defer=True): the previous step was not flushed")
             st = self.make_step(plan, n, 0, 1)
+            fam = self._family(plan)
             if plan.n_split <= 0:      # the split count of a one-layer launch, fixed for both halves of the step
                 st.phases = 1
-                st.n_split = self._planned_split(st)
+                st.n_split = self._planned_split(st, fam)
             st.defer_layers = self.n_layers
             # the scorer shape of the flush() call (phases = 8 over all layers) is validated NOW, before the first layer's
             # attention appends a row: a shape only the last call of the token would refuse must not leave the bank half-stepped
             st.layer_begin, st.layer_count, st.defer_index, st.phases = 0, self.n_layers, 0, 8
-            check(self._step_check(st), "ekv_step_check (deferred scorer)")
-            need = self._step_ws_bytes(st)
+            check(self._step_check(st, fam), "ekv_step_check (deferred scorer)")
+            need = self._step_ws_bytes(st, fam)
             ids = torch.empty(self.n_layers, self.n_kv_heads, st.n_evict, dtype=torch.int32, device=self.device) if st.n_evict > 0 else None
             ws = self._workspace(need)
             # everything that is the same for all layers of the token step is resolved once: the per-layer call below is on the
@@ -857,7 +920,7 @@ class KVBank:
                                    st_ref=C.byref(st), bank_ref=C.byref(self._bank), ws_ptr=ws.data_ptr(), ws_len=ws.numel(),
                                    stream=self._stream())
             # (the call and its leading arguments: the step of the bank's row format, a quantised one with the descriptor behind the dtype)
-            d["call"], d["head"] = self._attend_fn, (d["bank_ref"], d["st_ref"], self._dt, *self._desc_ref)
+            d["call"], d["head"], d["fam"] = fam[3], (d["bank_ref"], d["st_ref"], self._dt, *fam[4]), fam
         st = d["st"]
         st.layer_begin = st.defer_index = layer
         st.layer_count, st.phases = 1, 5
@@ -876,12 +939,13 @@ class KVBank:
         d["pending"] += 1
         return out
 
-    def _planned_split(self, st) -> int:
+    def _planned_split(self, st, fam=None) -> int:
         """The split count the library plans for ``st`` (a capped bank: by its own family — a capped chunk step is tiled in narrower
-        blocks than the plain call's)."""
-        if self.logit_cap is not None or self.sinks is not None or self.windows is not None:
+        blocks than the plain call's; a pooled step: by the pooled family)."""
+        fam = fam or self._family()
+        if self.logit_cap is not None or self.sinks is not None or self.windows is not None or fam[1] is not self._info_fn:
             info = (C.c_int32 * 10)()
-            check(self._info_fn(C.byref(self._bank), C.byref(st), self._dt, *self._desc_ref, info, 10), self._info_fn.__name__)
+            check(fam[1](C.byref(self._bank), C.byref(st), self._dt, *fam[4], info, 10), fam[1].__name__)
             return int(info[0])
         ns, fu = C.c_int32(0), C.c_int32(0)
         check(self.lib.ekv_step_plan(C.byref(self._bank), C.byref(st), C.byref(ns), C.byref(fu)), "ekv_step_plan")
@@ -891,11 +955,12 @@ class KVBank:
         """Scratch a step of ``q_len`` queries needs when the scorers of all layers are deferred to :meth:`flush` (the logits / column
         sums of every layer stay alive until then)."""
         st = self.make_step(plan, q_len, 0, 1)
+        fam = self._family(plan)
         if plan.n_split <= 0:
             st.phases = 1
-            st.n_split = self._planned_split(st)
+            st.n_split = self._planned_split(st, fam)
         st.defer_layers, st.layer_begin, st.layer_count, st.defer_index, st.phases = self.n_layers, 0, self.n_layers, 0, 8
-        return int(self._step_ws_bytes(st))
+        return int(self._step_ws_bytes(st, fam))
 
     def flush(self):
         """Scorer of every layer of the token step opened by ``attend(..., defer=True)``: accumulate, select, compact — one
@@ -910,7 +975,7 @@ class KVBank:
         st.q_token_stride = st.q_head_stride = st.kv_token_stride = st.kv_head_stride = st.out_token_stride = st.out_head_stride = 0      # (no caller tensors in this call)
         st.phys_extent = max(max(self.extent), d["t"])
         check(self._step_attend(st, ws.data_ptr(), ws.data_ptr(), ws.data_ptr(), ws.data_ptr(),
-                                _ptr(d["ids"]), d["rope"][0], d["rope"][1], ws.data_ptr(), ws.numel(), d["stream"]), "ekv_step_attend")
+                                _ptr(d["ids"]), d["rope"][0], d["rope"][1], ws.data_ptr(), ws.numel(), d["stream"], fam=d["fam"]), "ekv_step_attend")
         for l in range(self.n_layers):
             self.n_slots[l] = d["t"] - st.n_evict
         d["pending"] = 0
@@ -932,11 +997,13 @@ class KVBank:
             return self._attend_deferred(plan, q, k_new, v_new, layer_begin, out, q_pos), None
         lc, _, n, _ = q.shape
         self._quant_refuse(n > 1, "a chunk step (q_len > 1)")
+        fam = self._family(plan)      # (a pooled step on a bank that has no pooled call raises here, before anything is written)
+        pooled = fam[3] is not self._attend_fn
         self._set_q_pos(layer_begin, lc, q_pos)
         st = self.make_step(plan, n, layer_begin, lc)
         # one-launch decode steps run on the slot-indexed layout of the score rows (nothing moves on an eviction); everything else
         # on the ordered one
-        slot = n == 1 and phases == 0 and not overlap_scorer and self._enter_slot_rows(st)
+        slot = n == 1 and phases == 0 and not overlap_scorer and not pooled and self._enter_slot_rows(st)
         if not slot and any(self._slot_rows[layer_begin:layer_begin + lc]):
             self._ensure_ordered()      # (all layers in one launch: a layer-per-call caller would otherwise convert 32 times)
         st.phases = phases | (_lib.PHASE_SLOT_ROWS if slot else 0)
@@ -960,7 +1027,7 @@ class KVBank:
             evict_ids = None if slot else torch.empty(lc, self.n_kv_heads, max(st.n_evict, 1), dtype=torch.int32, device=self.device)
         elif st.n_evict > 0 and evict_ids is None:
             evict_ids = torch.empty(lc, self.n_kv_heads, st.n_evict, dtype=torch.int32, device=self.device)
-        if overlap_scorer and phases == 0 and not self.step_plan(plan, n, layer_begin, lc)[1]:
+        if overlap_scorer and phases == 0 and not pooled and not self.step_plan(plan, n, layer_begin, lc)[1]:
             self._attend_overlapped(st, q, k_new, v_new, out, evict_ids, lc, layer_begin)
             for l in range(layer_begin, layer_begin + lc):
                 self.n_slots[l] = st.n_slots - st.n_evict
@@ -969,11 +1036,11 @@ class KVBank:
             return out, (evict_ids if (st.n_evict > 0 and want_ids) else None)
         if any(ev is not None for ev in self._score_done[layer_begin:layer_begin + lc]):
             self.join()
-        need = self._step_ws_bytes(st)
+        need = self._step_ws_bytes(st, fam)
         ws = self._workspace(need)
         check(self._step_attend(st, _ptr(q), _ptr(k_new), _ptr(v_new), _ptr(out),
                                 _ptr(evict_ids) if (st.n_evict > 0 and evict_ids is not None) else None, _ptr(self.rope_cos), _ptr(self.rope_sin),
-                                _ptr(ws), ws.numel(), self._stream()), "ekv_step_attend")
+                                _ptr(ws), ws.numel(), self._stream(), fam=fam), "ekv_step_attend")
         if phases != 1:     # phases == 1 launches the attention kernel only; the slot map is untouched
             for l in range(layer_begin, layer_begin + lc):
                 self.n_slots[l] = st.n_slots - st.n_evict

@@ -632,6 +632,63 @@ int ekv_win_step_attend(const ekv_bank *bank, const ekv_step *step, int32_t dtyp
                         const void *v_new, void *out, int32_t *evict_ids, const float *rope_cos, const float *rope_sin,
                         void *workspace, size_t workspace_bytes, void *stream);
 
+/* Pooled selection (ABI 8, additive): the _typed calls with an ekv_pool struct behind the element type.  The one-shot prompt
+ * compression of the driver (SnapKV-style: prefill the prompt densely, score the keys with the last few queries, smooth, select once) is a
+ * chunk step of q_len = obs queries over n_slots = n keys with n_evict = n - budget whose scorer is pooled.
+ *
+ * Pooled selection applies to the single-stage policies EKV_POLICY_H2O_HEAD and EKV_POLICY_TOVA, for any n_evict >= 1.
+ *   s    the per-KV-head score row the unpooled scorer would rank: after accumulation, after the GQA mean, W = n_slots - score_off columns.
+ *   R    the candidate range [win_lo, W - win_tail).
+ *   r    the radius, >= 1; the kernel size is 2r + 1.
+ * The ranking value of j in R is what torch computes on the slice s[R], and nothing else:
+ *   EKV_POOL_MAX   torch.nn.functional.max_pool1d(s[R], 2r+1, stride=1, padding=r).  The padding is -inf, so an edge window simply has
+ *                  fewer members.
+ *   EKV_POOL_AVG   torch.nn.functional.avg_pool1d(s[R], 2r+1, stride=1, padding=r) with torch's default count_include_pad=True: edge
+ *                  windows add zeros and still divide by 2r+1.  The sum is taken in ascending index order, the division is one IEEE
+ *                  division by 2r+1.
+ * Columns outside R are never pooled into a window and are never victims.  The victims are the n_evict smallest pooled values; ties go
+ * to the lowest logical index (the rule of every other select of the library).  A window that holds a NaN pools to NaN and ranks
+ * largest.  Everything after the marking is the unpooled scorer's: the compaction of the score rows and of the slot map, evict_ids, the
+ * count tails.  The pooled values are used for ranking only: score_sum / score_sq / score_cnt keep the unpooled numbers.
+ * EKV_POLICY_ROCO with pooling is refused: its two-stage rule has no single row to pool.
+ *
+ * One-shot prefill (what the driver issues with generation_config['prefill'] = 'one_shot').  The prompt has n tokens, the resolved
+ * integer budget is B < n (B >= n: the key changes nothing), the observation window is obs.
+ *   1. Forward A: the tokens [0, n - obs) under the dense unscored plan (policy NONE).  The cache grows to n - obs rows in a bank whose
+ *      cap holds the whole prompt.
+ *   2. ekv_state_init(n, mode 2), as the strided prefill without keep_attention does.
+ *   3. Forward B: the last obs tokens as ONE ordinary chunk step: q_len = obs, causal inside the chunk, accumulate = 1, n_evict = n - B,
+ *      win_lo = sink, win_tail = obs (the observation tokens are always kept), count_add = obs, the run's own policy; the scorer is
+ *      pooled where score_pool > 1 (these calls), the plain call otherwise.
+ *   4. Hand-over: before the first decode step the B retained rows of every head live in a bank sized as the same mode's strided prefill
+ *      would have sized it, in logical order in the physical rows [0, B), extent == B; slot map, score rows and (a window bank) tok_pos
+ *      carried over; the prompt-sized bank is released.
+ *   5. Decode by the mode's existing rule (encoding: plain decode; auto: the decode policy over the whole cache with budget B, on the
+ *      score rows forward B left).
+ *
+ * A pooled step plans as the plain call of the same (bank, step, dtype) with every in-kernel scorer tail switched off, so that it ends in
+ * the generic scorer (whose EKV_POOL build it runs): two passes or one pass with exported logits by the plain call's rules, never the
+ * one-launch decode step, the split path's fast scorer, the logits-in-LDS kernel, the chunk kernel's tail, the wide column-sum pass's tail
+ * or the logits-resident kernel.  Deferred steps (defer_layers) work as for the plain call.  The widest pooled row is the unpooled generic
+ * scorer's: the stencil reads the score row where it sits (LDS up to ~10 000 columns, global scratch up to ~38 400) and writes the
+ * selection keys, which are in LDS either way; beyond it the step is refused like the plain one.
+ * EKV_E_ARG, behind the element type and before anything else is read: a NULL struct, radius < 1, an unknown op.  EKV_E_UNSUPPORTED with
+ * zero launches and ekv_pool_workspace_bytes = 0: any policy but H2O_HEAD / TOVA (ROCO, RANGE, NONE), rope_on_read, tova_head_mean,
+ * EKV_PHASE_SLOT_ROWS, a row beyond the pooled width.  16-bit rows and single sequences only: there is no pooled batched, quantised,
+ * long, capped, sink or window call. */
+#define EKV_POOL_MAX 0
+#define EKV_POOL_AVG 1
+typedef struct ekv_pool {
+  int32_t radius;
+  int32_t op;
+} ekv_pool;
+int ekv_pool_step_check(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const ekv_pool *pool);
+int ekv_pool_step_info(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const ekv_pool *pool, int32_t *info, int32_t n_info);
+size_t ekv_pool_workspace_bytes(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const ekv_pool *pool);
+int ekv_pool_step_attend(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const ekv_pool *pool, const void *q, const void *k_new,
+                         const void *v_new, void *out, int32_t *evict_ids, const float *rope_cos, const float *rope_sin,
+                         void *workspace, size_t workspace_bytes, void *stream);
+
 /* Batched decode steps (ABI 8, additive): ONE call, and one launch per kernel kind, serves n_seq sequences whose caches have
  * different lengths and different eviction geometry.  Each entry of the table names the bank layer it attends and carries what
  * ekv_step holds per step; entry i owns row i of the call's tensors.  The layers of a table need not be contiguous or ordered, so
