@@ -74,6 +74,10 @@ FAMILIES = {
     # pooled selection (-DEKV_POOL=1): the generic scorer with the pooling stencil in front of its select
     "EKV_SCORE_SELECT_POOL": lambda nt, elem: (
         "ekv_score_select.inc", f"ekv_score_select_pool_nt{nt}" + _tags(elem), _on(elem) + [f"-DEKV_SS_NT={nt}", "-DEKV_POOL=1"]),
+    # adaptive head budgets (-DEKV_ADA=1): the generic scorer in its rank / select phases, and the allot kernel between them
+    "EKV_SCORE_SELECT_ADA": lambda nt, elem: (
+        "ekv_score_select.inc", f"ekv_score_select_ada_nt{nt}" + _tags(elem), _on(elem) + [f"-DEKV_SS_NT={nt}", "-DEKV_ADA=1"]),
+    "EKV_SCORE_ALLOT": lambda nt: ("ekv_score_allot.inc", "ekv_score_allot", [f"-DEKV_ALLOT_NT={nt}"]),
 }
 
 
@@ -127,7 +131,7 @@ def later_instances():
 
 
 def later_objects():
-    """(object name, hipcc arguments) of the instances of ekv_instances_later.def (the kv84 decode instances, the kv164 ones, the long-row scorer, head_dim 256, the soft-capped instances, the sink instances, the window instances, the pooled scorer)."""
+    """(object name, hipcc arguments) of the instances of ekv_instances_later.def (the kv84 decode instances, the kv164 ones, the long-row scorer, head_dim 256, the soft-capped instances, the sink instances, the window instances, the pooled scorer, the adaptive scorer and its allot kernel)."""
     return _instance_objects(later_instances())
 
 

@@ -60,6 +60,9 @@ EXPORTS += tuple(WIN_CALLS[what] for what in STEP_CALLS)
 POOL_CALLS = {what: "ekv_pool_" + what for what in STEP_CALLS}
 EXPORTS += tuple(POOL_CALLS[what] for what in STEP_CALLS)
 POOL_OPS = {"max": 0, "avg": 1}      # EKV_POOL_MAX, EKV_POOL_AVG
+# the adaptive family (include/easykv_hip.h, "adaptive head budgets"): the _typed calls with an ekv_ada struct behind the dtype; 16-bit rows, one sequence
+ADA_CALLS = {what: "ekv_ada_" + what for what in STEP_CALLS}
+EXPORTS += tuple(ADA_CALLS[what] for what in STEP_CALLS)
 
 
 class Bank(C.Structure):
@@ -103,6 +106,12 @@ class Win(C.Structure):
 class Pool(C.Structure):
     """ekv_pool: radius (kernel size 2 * radius + 1) and op (POOL_OPS) of a pooled selection (include/easykv_hip.h, "pooled selection")."""
     _fields_ = [("radius", C.c_int32), ("op", C.c_int32)]
+
+
+class Ada(C.Structure):
+    """ekv_ada: pooling (radius >= 0, op) and the bounds of a head's victims of an adaptive step; n_evict_out: device int32 [layer_count][H]
+    (include/easykv_hip.h, "adaptive head budgets")."""
+    _fields_ = [("radius", C.c_int32), ("op", C.c_int32), ("evict_min", C.c_int32), ("evict_max", C.c_int32), ("n_evict_out", C.c_void_p)]
 
 
 class Step(C.Structure):
@@ -174,6 +183,7 @@ def load():
                 getattr(lib, SINK_CALLS[what]).argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, vp] + tails[what]
                 getattr(lib, WIN_CALLS[what]).argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, C.POINTER(Win)] + tails[what]
                 getattr(lib, POOL_CALLS[what]).argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, C.POINTER(Pool)] + tails[what]
+                getattr(lib, ADA_CALLS[what]).argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, C.POINTER(Ada)] + tails[what]
         if desc:
             getattr(lib, f"ekv_{rows}_quantize").argtypes = [C.POINTER(Bank), C.POINTER(desc), i32, i32, i32, i32, vp]
             getattr(lib, f"ekv_{rows}_dequantize").argtypes = [C.POINTER(Bank), C.POINTER(desc), i32, i32, i32, i32, vp, vp, vp]

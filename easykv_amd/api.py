@@ -164,8 +164,11 @@ class BudgetedKVCache:
         return self.layer_begin <= layer_idx < self.layer_begin + self.layer_count
 
     def get_seq_length(self, layer_idx: Optional[int] = None) -> int:
-        """Live slots (every owned layer holds the same number, as in the reference)."""
-        return self.bank.n_slots[0 if layer_idx is None or not self.owns(layer_idx) else layer_idx - self.layer_begin]
+        """Live slots (every owned layer holds the same number, as in the reference).  After adaptive head budgets: the mean over the
+        layer's heads, which is the uniform run's number (the heads' evictions sum to H * n_evict)."""
+        l = 0 if layer_idx is None or not self.owns(layer_idx) else layer_idx - self.layer_begin
+        heads = self.bank.head_slots[l] if self.bank.head_slots is not None else None
+        return self.bank.n_slots[l] if heads is None else sum(heads) // len(heads)
 
     def update(self, key_states, value_states, layer_idx, cache_kwargs=None):
         return key_states, value_states
@@ -247,6 +250,13 @@ class BudgetedKVCache:
             self._defer_this_forward = bool(n > 1 and plan.phase == "prefill" and plan.policy in ("roco", "h2o_head", "tova") and (plan.accumulate or plan.evict)
                                             and self.defer_chunk_scorer and self._defer_fits(plan, n))
         deferable_chunk = self._defer_this_forward
+        if n == 1 and plan.phase == "decode" and self.bank.ragged(layer_idx):
+            # heads of different lengths (adaptive head budgets): the layer's step is the batched call on the one-head view, whole —
+            # there is no deferred form of it
+            out, ids = self.bank.attend(plan, q, k, v, layer_begin=layer_idx, evict_ids=None if self._cur is not None else False)
+            if self._cur is not None and ids is not None:
+                self._cur.append(ids[0])
+            return out
         if ((n == 1 and plan.phase == "decode") or deferable_chunk) and self.layer_count > 1:
             # one layer per call (a decoder stack): attention + fold of this layer now, the scorers of all owned layers in ONE
             # launch after the last layer (KVBank.flush) — off the critical path of the stack.  Decode steps, and since round 4 the
@@ -593,6 +603,41 @@ class _Run:
             if self.obs_window > self.obs_max:
                 raise ValueError(f"{what}: obs_window = {self.obs_window} is more than one chunk step takes at this model's GQA factor {rep}; the largest "
                                  f"that works is {self.obs_max}")
+        # extension key: 'head_budgets' — None / 'uniform' (default: every KV head keeps the same number of rows, today's plans) or
+        # 'adaptive': the one-shot observation step shares a layer's H * n_evict evictions out among its heads by their pooled ranking
+        # values (include/easykv_hip.h, "adaptive head budgets"), between a floor and a ceiling of a head's keep, fractions of the
+        # uniform candidate keep K = C - n_evict: evict_max = C - floor(head_budget_floor * K), evict_min = max(0, C - ceil(head_budget_ceil * K)).
+        self.head_budgets = cfg.get("head_budgets", None)
+        if self.head_budgets not in (None, "uniform", "adaptive"):
+            raise ValueError(f"generation_config['head_budgets'] must be None, 'uniform' or 'adaptive', not {self.head_budgets!r}")
+        self.adaptive = self.head_budgets == "adaptive"
+        if self.adaptive:      # (before any bank exists)
+            what = "generation_config['head_budgets'] = 'adaptive'"
+            self.head_floor, self.head_ceil = cfg.get("head_budget_floor", 0.2), cfg.get("head_budget_ceil", 2.0)
+            isnum = lambda x: isinstance(x, (int, float)) and not isinstance(x, bool)
+            if not (isnum(self.head_floor) and 0.0 <= self.head_floor <= 1.0):
+                raise ValueError(f"generation_config['head_budget_floor'] must be a number in [0, 1], not {self.head_floor!r}")
+            if not (isnum(self.head_ceil) and self.head_ceil >= 1.0):
+                raise ValueError(f"generation_config['head_budget_ceil'] must be a number >= 1, not {self.head_ceil!r}")
+            if not self.one_shot:
+                raise ValueError(f"{what} needs generation_config['prefill'] = 'one_shot': the heads' shares are decided in the one observation step")
+            if len(prompts) != 1:
+                raise ValueError(f"{what} is not supported by generate_batch: a batch has no entries for heads of different lengths")
+            if policy not in ("h2o_head", "tova"):
+                raise ValueError(f"{what} serves kv_policy 'h2o_head' and 'tova', not {policy!r}")
+            if policy == "tova" and kv_mode == "encoding":
+                raise ValueError(f"{what} with kv_policy='tova' in mode 'encoding': encoding mode ranks one head-averaged row, the same for every head "
+                                 "(mode 'auto')")
+            for name, on in (("attention sinks", self.sinks is not None), ("generation_config['sliding_window']", self.windows is not None),
+                             (f"attn_logit_softcapping = {self.logit_cap}", self.logit_cap is not None),
+                             ("generation_config['long_rows'] = True", bool(self.long_rows)), (f"generation_config['kv_quant'] = {self.kv_quant!r}", self.kv_quant is not None),
+                             ("generation_config['hipgraph']", bool(self.use_graph)), ("a layer-sharded model (model.layer_shard)", shard is not None)):
+                if on:
+                    raise ValueError(f"{what} with {name}: there is no adaptive sink, window, capped, long or quantised call, and the decode steps over "
+                                     "heads of different lengths are neither captured nor sharded")
+            if hkv > 64 or hq // hkv > 8:
+                raise ValueError(f"{what}: the decode steps over heads of different lengths serve at most 64 KV heads and GQA factors up to 8 "
+                                 f"(this model: {hkv} KV heads, GQA factor {hq // hkv})")
         self.dev = torch.device(model.device)
         for p in prompts:
             if p.dim() != 2 or p.shape[0] != 1:
@@ -863,13 +908,24 @@ def _strided_prefill(run, cache, input_ids, budget_p, idx, r_idx, tova_head_mean
     return logits_last, all_logits, all_ids
 
 
-def _one_shot_prefill(run, input_ids, budget, cap_decode, tova_head_mean):
+def _one_shot_prefill(run, input_ids, budget, cap_decode, tova_head_mean, grow=1):
     """One-shot prompt compression (include/easykv_hip.h, "one-shot prefill"): two forwards and a hand-over.  ``budget``: the resolved
-    integer budget B < n; ``cap_decode``: the capacity the same mode's strided prefill would have given the cache.  -> (cache, last logits)"""
+    integer budget B < n; ``cap_decode``: the capacity the same mode's strided prefill would have given the cache; ``grow``: rows a head
+    gains in the decode phase (adaptive head budgets size the decode bank by the ceiling of a head's keep).  -> (cache, last logits)"""
     n, obs, sink = input_ids.shape[-1], run.obs_window, run.sink
     if obs >= n or budget < obs + sink:
         raise ValueError(f"generation_config['prefill'] = 'one_shot': obs_window = {obs} does not fit a prompt of {n} tokens cut to {budget} "
                          f"(the {sink} sink tokens and the observation window are always kept); the largest that works is {max(0, min(n - 1, budget - sink))}")
+    adaptive = None
+    if run.adaptive:      # (the bounds of a head's victims; the decode bank holds the ceiling's rows, not what a sync would report)
+        C, n_evict = n - obs - sink, n - budget
+        K = C - n_evict
+        adaptive = (max(0, C - math.ceil(run.head_ceil * K)), C - math.floor(run.head_floor * K))
+        longest = n - adaptive[0]
+        if longest + grow > 6144:
+            raise ValueError(f"generation_config['head_budgets'] = 'adaptive': a head may keep {longest} rows (+ {grow} decoded), more than the 6144 "
+                             "slots per head the decode steps over heads of different lengths take; lower head_budget_ceil or the budget")
+        cap_decode = (longest + grow + 3) // 4 * 4
     # the prefill's peak memory is the whole prompt's K/V: a bank of n rows, released at the hand-over
     cache = run.new_cache(n, n)
     dense = StepPlan(policy="full", phase="prefill", accumulate=False)
@@ -877,7 +933,7 @@ def _one_shot_prefill(run, input_ids, budget, cap_decode, tova_head_mean):
     cache.bank.state_init(n, 2, obs)
     plan = StepPlan(policy=run.policy, phase="prefill", accumulate=True, evict=True, budget=n, recent=obs, sink=sink, stride=obs,
                     tova_head_mean=tova_head_mean and run.policy == "tova",      # (the head-averaged row is tova's alone; a pooled step refuses the flag)
-                    n_evict=n - budget, pool=run.score_pool, pool_op=run.score_pool_op)
+                    n_evict=n - budget, pool=run.score_pool, pool_op=run.score_pool_op, **(dict(head_adaptive=adaptive) if adaptive else {}))
     logits = run.forward(cache, input_ids[:, n - obs:], list(range(n - obs, n)), plan).logits[:, -1, :]      # forward B: score, pool, select once
     # hand-over: the decode steps stream the physical rows [0, extent) of every head; without it that is the prompt's n rows for the rest
     # of the generation
@@ -918,7 +974,7 @@ def _prefill(run: _Run, input_ids, kv_mode) -> Prefilled:
             budget_p, idx, r_idx = geometry("encoding", length, budget, stride)
             if run.one_shot:      # (the resolved integer budget: B < length here)
                 cache, logits = _one_shot_prefill(run, input_ids, int(length * budget) if type(budget) == float else budget,
-                                                  idx + stride + run.max_new_tokens, True)
+                                                  idx + stride + run.max_new_tokens, True, run.max_new_tokens)
             else:
                 # 'full' / unknown policy strings evict nothing (the reference's cache just grows): size for the whole prompt
                 cache = run.new_cache((idx + stride if run.evicting else length) + run.max_new_tokens, length)

@@ -152,7 +152,23 @@ static int call_attend(const EkvCall& c, const void* q, const void* k_new, const
       case EKV_RUN_DECODE_SCORE: e = sinks ? ekv_launch_decode_score_sink(sa, sinks, lc, s, bf16) : ekv_launch_decode_score(sa, tb, lc, s, bf16); break;
       case EKV_RUN_TOVA_MEAN: e = sinks ? ekv_launch_tova_headmean_sink(sa, sinks, lc, s) : ekv_launch_tova_headmean(sa, lc, s); break;
       // (a pooled plan: the EKV_POOL instances of the generic scorer, the struct's two words as the kernel's last argument)
+      // (an adaptive plan: rank, allot, select — the EKV_ADA instances twice around the allot kernel.  The select phase reads the score rows
+      // the rank phase wrote back and must do none of the scorer's attention-side work again: skip_fold = 1 with accumulate = 0 makes
+      // step 0 of ekv_score_select_body fold nothing (`nothing_to_fold`: no partials read, no output written), and accumulate = 0 keeps
+      // step 2 off the logits / column sums (neither the wide sweep nor the column-sum path runs: the rows are loaded as the bank holds
+      // them, and nothing is added a second time).  A change to those two conditions must keep both true for this launch.)
       case EKV_RUN_SCORE_SELECT:
+        if (P.adaptive) {
+          EkvAdaArgs ad{c.ada->radius, c.ada->op, c.ada->evict_min, c.ada->evict_max, 0, P.t_pad, reinterpret_cast<uint32_t*>(ws + P.ada_keys),
+                        reinterpret_cast<uint8_t*>(ws + P.ada_cls), c.ada->n_evict_out};
+          e = ekv_launch_score_select_ada(sa, ad, lc, s, bf16);
+          if (e == hipSuccess) e = ekv_launch_score_allot(sa, ad, lc, s);
+          EkvScoreArgs sel = sa;
+          sel.accumulate = 0, sel.skip_fold = 1;
+          ad.phase = 1;
+          if (e == hipSuccess) e = ekv_launch_score_select_ada(sel, ad, lc, s, bf16);
+          break;
+        }
         e = P.pooled ? ekv_launch_score_select_pool(sa, EkvPoolArgs{c.pool->radius, c.pool->op}, lc, s, bf16) : ekv_launch_score_select(sa, lc, s, bf16);
         break;
       // long calls (L.passes: the plain plan keeps its rows in scratch)
@@ -273,6 +289,20 @@ int ekv_pool_step_attend(const ekv_bank* bank, const ekv_step* st, int32_t dtype
                          const void* v_new, void* out, int32_t* evict_ids, const float* rope_cos, const float* rope_sin, void* workspace,
                          size_t workspace_bytes, void* stream) {
   return call_attend(pool_call(bank, st, dtype, pool), q, k_new, v_new, out, evict_ids, rope_cos, rope_sin, workspace, workspace_bytes, stream);
+}
+
+// adaptive head budgets (include/easykv_hip.h, "adaptive head budgets"): the _typed calls with the budget struct behind the element type
+int ekv_ada_step_check(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_ada* ada) { return call_check(ada_call(bank, st, dtype, ada)); }
+int ekv_ada_step_info(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_ada* ada, int32_t* info, int32_t n_info) {
+  return call_info(ada_call(bank, st, dtype, ada), info, n_info);
+}
+size_t ekv_ada_workspace_bytes(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_ada* ada) {
+  return call_workspace_bytes(ada_call(bank, st, dtype, ada));
+}
+int ekv_ada_step_attend(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_ada* ada, const void* q, const void* k_new,
+                        const void* v_new, void* out, int32_t* evict_ids, const float* rope_cos, const float* rope_sin, void* workspace,
+                        size_t workspace_bytes, void* stream) {
+  return call_attend(ada_call(bank, st, dtype, ada), q, k_new, v_new, out, evict_ids, rope_cos, rope_sin, workspace, workspace_bytes, stream);
 }
 
 // FP8 K/V storage (include/easykv_hip.h, "kv8")

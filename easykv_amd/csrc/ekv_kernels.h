@@ -85,6 +85,11 @@ struct EkvStepPlan {
   int32_t sink;         // an ekv_sink_* call: the launches run the EKV_SINK instances (chunk steps likewise; decode steps in phase order F, no resident rows)
   int32_t window;       // an ekv_win_* call: the launches run the EKV_WINDOW instances (with sinks: the EKV_SINK + EKV_WINDOW ones); planned as the sink call
   int32_t pooled;       // an ekv_pool_* call: EKV_RUN_SCORE_SELECT runs the EKV_POOL instances of the generic scorer; every in-kernel scorer tail is off
+  // adaptive calls (ekv_ada_*, ekv_plan.cpp "adaptive head budgets"): planned as the pooled call; EKV_RUN_SCORE_SELECT runs rank + allot +
+  // select (three kernels).  Byte offsets of the exported ranking keys [layer_count][H][t_pad] uint32 and of the class bytes
+  // [layer_count][H][t_pad] uint8 (0 forced, 1 free, 2 neither), behind everything the pooled layout holds (-1 = not in the layout)
+  int32_t adaptive;
+  int64_t ada_keys, ada_cls;
 };
 // The table of a batched decode step as the kernels' batch instances receive it: BY VALUE, behind the argument structs of the uniform
 // kernel (2304 bytes of the 4 KB a launch may carry).  Workgroup (head, entry ll) shadows the per-step fields of its argument structs
@@ -217,6 +222,20 @@ struct EkvPoolArgs {
   int32_t radius, op;
 };
 hipError_t ekv_launch_score_select_pool(const EkvScoreArgs& a, const EkvPoolArgs& pool, int layer_count, hipStream_t s, bool bf16);
+// Adaptive head budgets (the ekv_ada_* calls; include/easykv_hip.h): what the EKV_ADA instances of ekv_score_select.inc and the allot kernel
+// (ekv_score_allot.inc) receive as their last argument.  phase 0 = rank: accumulate, write the score rows back, pool, export the W ranking
+// keys of the head and its class bytes.  phase 1 = select: read the score rows and the keys back, k = k_out[ll][h], then the scorer's own
+// marking, scan, write-back and compaction.  keys / cls: this launch's slices, rows `stride` elements apart, [layer_count][H][stride].
+// k_out: device int32 [layer_count][H], written by the allot kernel between the two (one workgroup per layer).
+struct EkvAdaArgs {
+  int32_t radius, op, evict_min, evict_max;
+  int32_t phase, stride;
+  uint32_t* keys;
+  uint8_t* cls;
+  int32_t* k_out;
+};
+hipError_t ekv_launch_score_select_ada(const EkvScoreArgs& a, const EkvAdaArgs& ada, int layer_count, hipStream_t s, bool bf16);
+hipError_t ekv_launch_score_allot(const EkvScoreArgs& a, const EkvAdaArgs& ada, int layer_count, hipStream_t s);
 // Attention sinks (the ekv_sink_* calls; EKV_SINK instances, ekv_common.h): the launchers of a sink step.  sinks: device fp32
 // [bank->n_layers][n_q_heads], indexed by bank layer.  16-bit rows, plain keys, one sequence; head_dim 64 / 128.  The chunk launcher runs
 // the 16x16x32 kernel in its one-tile build (pass: 0 one pass, 1 statistics pass, 2 exact pass; fuse_sc: the scorer as the one pass's tail).
@@ -385,6 +404,8 @@ __device__ __forceinline__ EkvScoreArgs ekv_batch_score_args(const EkvScoreArgs&
 #define EKV_FN_SCORE_SELECT(nt, elem) EKV_FN_SCORE_SELECT_(nt, elem)
 #define EKV_FN_SCORE_SELECT_POOL_(nt, elem) ekv_launch_score_select_pool_nt##nt##_##elem
 #define EKV_FN_SCORE_SELECT_POOL(nt, elem) EKV_FN_SCORE_SELECT_POOL_(nt, elem)
+#define EKV_FN_SCORE_SELECT_ADA_(nt, elem) ekv_launch_score_select_ada_nt##nt##_##elem
+#define EKV_FN_SCORE_SELECT_ADA(nt, elem) EKV_FN_SCORE_SELECT_ADA_(nt, elem)
 // the manifest's words as the fields of a table entry: booleans, and EKV_ROWS_<rows> above
 #define EKV_IS_plain false
 #define EKV_IS_rope true

@@ -809,6 +809,31 @@ static bool ekv_win_ok(const ekv_win* w, const ekv_bank* bank) {
   return true;
 }
 
+// the struct of an adaptive call: complete, the pooling words valid (radius 0 = no pooling), the bounds in order around the step's n_evict
+// and inside its candidate range (only the step's own integers are read)
+static bool ekv_ada_ok(const ekv_ada* a, const ekv_step* st) {
+  if (!a || !a->n_evict_out || a->radius < 0 || (a->op != EKV_POOL_MAX && a->op != EKV_POOL_AVG)) return false;
+  if (!st) return true;      // (the call reports the missing step itself)
+  const i64 C = (i64)st->n_slots - st->score_off - st->win_lo - st->win_tail;
+  return a->evict_min >= 0 && a->evict_min <= st->n_evict && st->n_evict >= 1 && st->n_evict <= a->evict_max && a->evict_max <= C;
+}
+
+// Adaptive calls: the three-kernel ending and its scratch, BEHIND everything the pooled layout holds (every other offset is the pooled
+// call's): the ranking keys, one row of t_pad words per (layer, head), then the class bytes, one row of t_pad bytes; a deferred call's
+// slices as in plan_checks
+static void plan_ada_layout(const ekv_bank* bank, const ekv_step* st, EkvStepPlan* P) {
+  for (int i = 0; i < P->n_list; ++i)
+    if (P->list[i].kind == EKV_RUN_SCORE_SELECT) P->list[i].kernel_count += 2, P->n_launches += 2;
+  const size_t LC = (size_t)(st->defer_layers > 0 ? st->defer_layers : st->layer_count), H = (size_t)bank->n_kv_heads;
+  const size_t li = st->defer_layers != 0 ? (size_t)st->defer_index : 0;
+  size_t off = P->bytes;
+  P->ada_keys = (int64_t)(off + li * H * P->t_pad * 4);
+  off += ekv_align(LC * H * P->t_pad * 4, 256);
+  P->ada_cls = (int64_t)(off + li * H * P->t_pad);
+  off += ekv_align(LC * H * P->t_pad, 256);
+  P->bytes = off;
+}
+
 int resolve_call(const EkvCall& c, EkvResolved* r) {
   EkvStepPlan* P = &r->plan;
   *P = EkvStepPlan{};
@@ -903,15 +928,26 @@ int resolve_call(const EkvCall& c, EkvResolved* r) {
   // than h2o_head / tova (roco's two-stage rule has no single row to pool; EKV_POLICY_RANGE and EKV_POLICY_NONE have no row at all),
   // RoPE-on-read, tova_head_mean, slot-indexed score rows, a row beyond the generic scorer's width.
   if (c.pooled && !(c.pool != nullptr && c.pool->radius >= 1 && (c.pool->op == EKV_POOL_MAX || c.pool->op == EKV_POOL_AVG))) return EKV_E_ARG;
-  const int variants = (c.long_rows ? 1 : 0) + (c.capped ? 1 : 0) + (c.sink || c.window ? 1 : 0) + (c.pooled ? 1 : 0);
+  // Adaptive calls (ekv_ada_*; include/easykv_hip.h, "adaptive head budgets"), likewise stated once.  "Adaptive" is one more independent
+  // variant of a call, combined with nothing else.  A NULL struct, NULL n_evict_out, a radius < 0, an unknown op and bounds out of order
+  // (ekv_ada_ok: 0 <= evict_min <= n_evict <= evict_max <= the candidates of the step, n_evict >= 1) are argument errors, behind the
+  // element type and before anything is planned.  The ONE rule: an adaptive step plans as the POOLED call of the same (bank, step, dtype)
+  // — field for field, refusals included — and where that plan ends in EKV_RUN_SCORE_SELECT the entry counts three kernels (rank, allot,
+  // select: call_attend) and the workspace grows, behind everything the pooled layout holds, by the exported ranking keys and class
+  // bytes (plan_ada_layout).  Refused on top of the pooled refusals (EKV_E_UNSUPPORTED, zero launches, zero bytes): more than 64 KV heads
+  // (the allot kernel keeps one counter pair per head in LDS).
+  if (c.adaptive && !ekv_ada_ok(c.ada, c.step)) return EKV_E_ARG;
+  const int variants = (c.long_rows ? 1 : 0) + (c.capped ? 1 : 0) + (c.sink || c.window ? 1 : 0) + (c.pooled ? 1 : 0) + (c.adaptive ? 1 : 0);
   const bool sinkish = c.sink || c.window;
   const int rc = (variants && (quant || c.batch || variants > 1))
                      ? EKV_E_UNSUPPORTED
-                     : ekv_plan_step(bank, r->step, P, c.long_rows, c.capped || sinkish, quant || c.batch || sinkish || c.capped, c.pooled);
+                     : ekv_plan_step(bank, r->step, P, c.long_rows, c.capped || sinkish, quant || c.batch || sinkish || c.capped, c.pooled || c.adaptive);
   P->capped = c.capped ? 1 : 0;
   P->sink = c.sink ? 1 : 0;
   P->window = c.window ? 1 : 0;
   P->pooled = c.pooled ? 1 : 0;
+  P->adaptive = c.adaptive ? 1 : 0;
+  P->ada_keys = P->ada_cls = -1;
   P->bf16 = c.dtype == EKV_DTYPE_BF16;
   P->rows = c.rows;
   P->batch = c.batch;
@@ -924,7 +960,7 @@ int resolve_call(const EkvCall& c, EkvResolved* r) {
       P->bytes = plain.bytes, P->big_rows = plain.big_rows, P->key_rows = -1;
     }
     P->one_launch = P->n_launches = P->n_list = P->long_rows = P->long_tiles = 0;
-    if (c.batch || c.capped || sinkish || c.pooled) P->bytes = 0;      // (nothing will run: ekv_batch_workspace_bytes of a refused table, ekv_cap_ / ekv_sink_ / ekv_pool_workspace_bytes of a refused step, is 0)
+    if (c.batch || c.capped || sinkish || c.pooled || c.adaptive) P->bytes = 0;      // (nothing will run: ekv_batch_workspace_bytes of a refused table, ekv_cap_ / ekv_sink_ / ekv_pool_workspace_bytes of a refused step, is 0)
     return code;
   };
   const ekv_step* st = c.step;
@@ -938,8 +974,12 @@ int resolve_call(const EkvCall& c, EkvResolved* r) {
   if (c.capped && (st->rope_on_read || (bank->head_dim != 128 && bank->head_dim != kChunkNarrowD))) return refuse(EKV_E_UNSUPPORTED);
   if (c.sink && (st->rope_on_read || (bank->head_dim != 64 && bank->head_dim != 128))) return refuse(EKV_E_UNSUPPORTED);
   if (c.window && (st->rope_on_read || bank->head_dim != (c.sink ? 64 : 128))) return refuse(EKV_E_UNSUPPORTED);
-  if (c.pooled && (st->rope_on_read || st->tova_head_mean || (st->policy != EKV_POLICY_H2O_HEAD && st->policy != EKV_POLICY_TOVA)))
+  if ((c.pooled || c.adaptive) && (st->rope_on_read || st->tova_head_mean || (st->policy != EKV_POLICY_H2O_HEAD && st->policy != EKV_POLICY_TOVA)))
     return refuse(EKV_E_UNSUPPORTED);
+  if (c.adaptive) {
+    if (bank->n_kv_heads > 64) return refuse(EKV_E_UNSUPPORTED);
+    plan_ada_layout(bank, st, P);
+  }
   if (quant && (st->q_len != 1 || st->rope_on_read || !ekv_rows_head_dim(c.rows, bank->head_dim) ||
                 bank->n_q_heads / bank->n_kv_heads > kRowsRules[c.rows].max_rep))
     return refuse(EKV_E_UNSUPPORTED);
@@ -983,6 +1023,7 @@ int call_info(const EkvCall& c, int32_t* info, int32_t n_info) {
   if (c.sink && c.sinks == nullptr) return EKV_E_ARG;
   if (c.window && !ekv_win_ok(c.win, r.bank)) return EKV_E_ARG;
   if (c.pooled && !(c.pool != nullptr && c.pool->radius >= 1 && (c.pool->op == EKV_POOL_MAX || c.pool->op == EKV_POOL_AVG))) return EKV_E_ARG;
+  if (c.adaptive && !ekv_ada_ok(c.ada, c.step)) return EKV_E_ARG;
   if (c.rows != EKV_ROWS_kv16 && !r.bank) return EKV_E_ARG;
   if (int e = check_bank(r.bank)) return e;
   if (!c.step || (c.batch && !c.seqs) || !info || n_info < 1) return EKV_E_ARG;

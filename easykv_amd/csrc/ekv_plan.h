@@ -53,7 +53,8 @@ EkvScoreArgs score_args(const ekv_bank* bank, const ekv_step* st, const EkvStepP
 // long_rows: the plan of a long call (ekv_long_*; the rule is stated once, at ekv_plan_step in ekv_plan.cpp)
 // capped: the plan of a capped call (ekv_cap_*; the rule is stated once, at resolve_call in ekv_plan.cpp); a sink call (ekv_sink_*) tiles
 // its chunk steps by the same rule and passes true as well
-// pooled: the plan of a pooled call (ekv_pool_*; the rule is stated once, at resolve_call in ekv_plan.cpp): every in-kernel scorer tail off
+// pooled: the plan of a pooled call (ekv_pool_*; the rule is stated once, at resolve_call in ekv_plan.cpp): every in-kernel scorer tail off;
+// an adaptive call (ekv_ada_*) plans as the pooled one and passes true as well
 int ekv_plan_step(const ekv_bank* bank, const ekv_step* step, EkvStepPlan* P, bool long_rows = false, bool capped = false, bool no_orders = false,
                   bool pooled = false);
 
@@ -91,6 +92,8 @@ struct EkvCall {
   const ekv_win* win;      // ... its struct (include/easykv_hip.h): NULL, NULL tok_pos / windows or a negative window are argument errors
   bool pooled;             // an ekv_pool_* call: pooled selection (16-bit rows, one sequence, h2o_head / tova, no other variant)
   const ekv_pool* pool;    // ... its struct: NULL, radius < 1 or an unknown op are argument errors
+  bool adaptive;           // an ekv_ada_* call: adaptive head budgets (16-bit rows, one sequence, h2o_head / tova, no other variant)
+  const ekv_ada* ada;      // ... its struct: NULL, NULL n_evict_out, radius < 0, an unknown op or bounds out of order are argument errors
 };
 inline EkvCall step_call(const ekv_bank* bank, const ekv_step* st, int32_t dtype) { return {bank, st, dtype, EKV_ROWS_kv16, {}, false, nullptr, 0}; }
 inline EkvCall batch_call(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_seq* seqs, int32_t n_seq) {
@@ -109,6 +112,9 @@ inline EkvCall win_call(const ekv_bank* bank, const ekv_step* st, int32_t dtype,
 }
 inline EkvCall pool_call(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_pool* pool) {
   return {bank, st, dtype, EKV_ROWS_kv16, {}, false, nullptr, 0, false, false, 0.f, false, nullptr, false, nullptr, true, pool};
+}
+inline EkvCall ada_call(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_ada* ada) {
+  return {bank, st, dtype, EKV_ROWS_kv16, {}, false, nullptr, 0, false, false, 0.f, false, nullptr, false, nullptr, false, nullptr, true, ada};
 }
 // the quantised calls: the same two with a row format and its planes
 inline EkvCall kv8_call(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_kv8* q8) {

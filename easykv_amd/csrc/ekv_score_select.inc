@@ -38,6 +38,22 @@ constexpr int kNWV = kNT / 64;
 #else
 #define EKV_POOL_ONLY(...)
 #endif
+// EKV_ADA = 1 (the EKV_SCORE_SELECT_ADA lines of the manifest): the adaptive build of the scorer (include/easykv_hip.h, "adaptive head
+// budgets"), one build run twice around the allot kernel (ekv_score_allot.inc).  The kernel takes an EkvAdaArgs as its LAST argument;
+// its pooling words stand where the pooled build has `pool`, and the stencil below is shared.  ada.phase 0 = rank: the accumulated score
+// rows go back to the bank, the head's W ranking keys and the class of each (forced / free / neither, by two block selects) go to the
+// workspace.  ada.phase 1 = select (launched with accumulate = 0: the rows are read back, the keys re-formed): k is the head's own, read
+// from ada.k_out.  EKV_ADA_ONLY(...) vanishes in every other build.
+#ifndef EKV_ADA
+#define EKV_ADA 0
+#endif
+#if EKV_ADA
+#define EKV_ADA_ONLY(...) __VA_ARGS__
+#define EKV_SS_IDS_PITCH ada.evict_max      // evict_ids is [layer][head][evict_max]: entries beyond a head's k are left unwritten
+#else
+#define EKV_ADA_ONLY(...)
+#define EKV_SS_IDS_PITCH k
+#endif
 
 // Wide logits sweep of the scorer (see the call site): thread -> 4 consecutive columns, 8 rows (IB queries x REP heads) of
 // 16-byte loads in flight.  REP is a compile-time constant so that the per-batch arrays stay in registers.
@@ -134,7 +150,7 @@ __device__ __forceinline__ void wide_sweep(const EkvScoreArgs& a, int tid, size_
 // column: W up to ~39 000.  Same code, same arithmetic, same summation order — only where sS / sQ / sC point differs; the template
 // keeps the LDS address space provable (ds_read instead of flat loads) in the build every other shape uses.
 template <bool BIG = false>
-__device__ void ekv_score_select_body(const EkvScoreArgs& a, const int h, const int ll, char* smem EKV_POOL_ONLY(, const EkvPoolArgs& pool)) {
+__device__ void ekv_score_select_body(const EkvScoreArgs& a, const int h, const int ll, char* smem EKV_POOL_ONLY(, const EkvPoolArgs& pool) EKV_ADA_ONLY(, const EkvAdaArgs& ada)) {
   const int gl = a.layer_begin + ll;
   const int T = a.n_slots, n = a.q_len, D = a.head_dim;
   const int rep = a.n_q_heads / a.n_kv_heads;
@@ -315,7 +331,18 @@ __device__ void ekv_score_select_body(const EkvScoreArgs& a, const int h, const 
   }
 
   EKV_SS_STAMP(3);
+#if EKV_ADA
+  const EkvPoolArgs pool{ada.radius, ada.op};
+  const size_t ada_row = ((size_t)ll * a.n_kv_heads + h) * ada.stride;
+  if (ada.phase == 0 && a.accumulate)      // (a step that does not accumulate ranks the rows as the bank holds them: nothing to write)
+    for (int j = b.tid; j < W; j += kNT) a.score_sum[head_row + j] = sS[j];
+  // rank: evict_max >= 1 carries it past the early return below, as far as the keys.  select: the head's own share; with k_h = 0 the
+  // early return below is taken with accumulate = 0 and writes nothing, which is right only because the rank phase has already put the
+  // accumulated rows into the bank and a head that evicts nothing has nothing to compact.
+  const int k = ada.phase == 0 ? ada.evict_max : ada.k_out[ll * a.n_kv_heads + h];
+#else
   const int k = a.n_evict;
+#endif
   if (k <= 0) {
     if (scored && a.accumulate) {
       for (int j = b.tid; j < W; j += kNT) {
@@ -354,7 +381,7 @@ __device__ void ekv_score_select_body(const EkvScoreArgs& a, const int h, const 
       blk_mark_k_smallest(b, sKey, W, k, sHist);
     }
   } else {  // h2o_head / tova: k smallest accumulated scores inside the candidate window
-#if EKV_POOL
+#if EKV_POOL || EKV_ADA
     // Pooled selection: the ranking value of a candidate j in R = [win_lo, W - win_tail) is the max / the average of the score row over
     // [j - r, j + r] clipped to R (torch's max_pool1d / avg_pool1d on the slice s[R], stride 1, padding r: the -inf padding of max leaves
     // an edge window fewer members, the zero padding of avg adds nothing to the sum and the divisor stays 2r + 1).  The stencil reads the
@@ -390,6 +417,27 @@ __device__ void ekv_score_select_body(const EkvScoreArgs& a, const int h, const 
         sKey[j] = key;
       }
       __syncthreads();
+#if EKV_ADA
+      if (ada.phase == 0) {
+        // the keys as the allot kernel reads them, then the two class boundaries: the evict_max smallest are forced or free, the evict_min
+        // smallest of them forced.  Thread tid reads back only what it wrote itself (columns tid, tid + kNT, ...).
+        uint32_t* const gkey = ada.keys + ada_row;
+        uint8_t* const gcls = ada.cls + ada_row;
+        for (int j = b.tid; j < W; j += kNT) gkey[j] = sKey[j];
+        blk_mark_k_smallest(b, sKey, W, ada.evict_max, sHist);
+        for (int j = b.tid; j < W; j += kNT) {
+          gcls[j] = sKey[j] ? 1 : 2;
+          sKey[j] = gkey[j];
+        }
+        __syncthreads();
+        if (ada.evict_min > 0) {
+          blk_mark_k_smallest(b, sKey, W, ada.evict_min, sHist);
+          for (int j = b.tid; j < W; j += kNT)
+            if (sKey[j]) gcls[j] = 0;
+        }
+        return;
+      }
+#endif
       blk_mark_k_smallest(b, sKey, W, k, sHist);
     }
 #else
@@ -488,7 +536,7 @@ __device__ void ekv_score_select_body(const EkvScoreArgs& a, const int h, const 
   if (a.evict_ids != nullptr) {
     for (int j = b.tid; j < W; j += kNT) {
       const int d = (int)sKey[j];
-      if (d < 0) a.evict_ids[((size_t)ll * a.n_kv_heads + h) * k + (-1 - d)] = off + j;
+      if (d < 0) a.evict_ids[((size_t)ll * a.n_kv_heads + h) * EKV_SS_IDS_PITCH + (-1 - d)] = off + j;
     }
   }
 
@@ -506,7 +554,11 @@ __device__ void ekv_score_select_body(const EkvScoreArgs& a, const int h, const 
 }
 
 #ifndef EKV_SS_DEVICE_ONLY
-#if EKV_POOL && EKV_BF16      // (the pooled instances: the scorer alone, under names of its own)
+#if EKV_ADA && EKV_BF16       // (the adaptive instances: likewise)
+#define ekv_score_select_kernel ekv_score_select_kernel_ada_bf16
+#elif EKV_ADA
+#define ekv_score_select_kernel ekv_score_select_kernel_ada
+#elif EKV_POOL && EKV_BF16      // (the pooled instances: the scorer alone, under names of its own)
 #define ekv_score_select_kernel ekv_score_select_kernel_pool_bf16
 #elif EKV_POOL
 #define ekv_score_select_kernel ekv_score_select_kernel_pool
@@ -520,14 +572,14 @@ __device__ void ekv_score_select_body(const EkvScoreArgs& a, const int h, const 
 #define ekv_tova_headmean_kernel ekv_tova_headmean_kernel_sink
 #else
 template <bool BIG>
-__global__ void __launch_bounds__(kNT) ekv_score_select_kernel(const EkvScoreArgs a EKV_POOL_ONLY(, const EkvPoolArgs pool)) {
+__global__ void __launch_bounds__(kNT) ekv_score_select_kernel(const EkvScoreArgs a EKV_POOL_ONLY(, const EkvPoolArgs pool) EKV_ADA_ONLY(, const EkvAdaArgs ada)) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  ekv_score_select_body<BIG>(a, blockIdx.x, blockIdx.y, smem EKV_POOL_ONLY(, pool));
+  ekv_score_select_body<BIG>(a, blockIdx.x, blockIdx.y, smem EKV_POOL_ONLY(, pool) EKV_ADA_ONLY(, ada));
 }
 
 #endif  // !EKV_SINK
 
-#if !EKV_BF16 && !EKV_POOL
+#if !EKV_BF16 && !EKV_POOL && !EKV_ADA
 // 'tova' in encoding/ppl mode: one last-query row averaged over ALL kv heads (easykv/easykv.py:456, :847)
 __global__ void __launch_bounds__(kNT) ekv_tova_headmean_kernel(const EkvScoreArgs a EKV_SINK_ONLY(, const float* const sinks)) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -593,6 +645,8 @@ hipError_t ekv_launch_tova_headmean_sink(const EkvScoreArgs& a, const float* sin
 #else
 #if EKV_POOL
 hipError_t EKV_FN_SCORE_SELECT_POOL(EKV_SS_NT, EKV_ELEM)(const EkvScoreArgs& a, const EkvPoolArgs& pool, int layer_count, hipStream_t s) {
+#elif EKV_ADA
+hipError_t EKV_FN_SCORE_SELECT_ADA(EKV_SS_NT, EKV_ELEM)(const EkvScoreArgs& a, const EkvAdaArgs& ada, int layer_count, hipStream_t s) {
 #else
 hipError_t EKV_FN_SCORE_SELECT(EKV_SS_NT, EKV_ELEM)(const EkvScoreArgs& a, int layer_count, hipStream_t s) {
 #endif
@@ -602,7 +656,7 @@ hipError_t EKV_FN_SCORE_SELECT(EKV_SS_NT, EKV_ELEM)(const EkvScoreArgs& a, int l
   if (a.big_rows != nullptr) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ekv_score_select_kernel<true>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(ekv_score_select_kernel<true>, dim3(a.n_kv_heads, layer_count), dim3(kNT), lds, s, a EKV_POOL_ONLY(, pool));
+    hipLaunchKernelGGL(ekv_score_select_kernel<true>, dim3(a.n_kv_heads, layer_count), dim3(kNT), lds, s, a EKV_POOL_ONLY(, pool) EKV_ADA_ONLY(, ada));
     return hipGetLastError();
   }
 #endif
@@ -610,11 +664,11 @@ hipError_t EKV_FN_SCORE_SELECT(EKV_SS_NT, EKV_ELEM)(const EkvScoreArgs& a, int l
   if (lds > 48 * 1024)
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ekv_score_select_kernel<false>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL(ekv_score_select_kernel<false>, dim3(a.n_kv_heads, layer_count), dim3(kNT), lds, s, a EKV_POOL_ONLY(, pool));
+  hipLaunchKernelGGL(ekv_score_select_kernel<false>, dim3(a.n_kv_heads, layer_count), dim3(kNT), lds, s, a EKV_POOL_ONLY(, pool) EKV_ADA_ONLY(, ada));
   return hipGetLastError();
 }
 
-#if !EKV_BF16 && !EKV_POOL
+#if !EKV_BF16 && !EKV_POOL && !EKV_ADA
 hipError_t EKV_SS_CAT(ekv_launch_tova_headmean_nt, EKV_SS_NT)(const EkvScoreArgs& a, int layer_count, hipStream_t s) {
   const size_t lds = (size_t)a.n_q_heads * 2 * 4;
   hipLaunchKernelGGL(ekv_tova_headmean_kernel, dim3(layer_count), dim3(kNT), lds, s, a);

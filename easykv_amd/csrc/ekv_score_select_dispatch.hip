@@ -80,6 +80,32 @@ hipError_t ekv_launch_score_select_pool(const EkvScoreArgs& a, const EkvPoolArgs
   return hipErrorInvalidValue;
 }
 
+// ---- the adaptive instances (ekv_instances_later.def, EKV_SCORE_SELECT_ADA): the block size of the pooled rule above, for both phases
+typedef hipError_t EkvSelectAdaFn(const EkvScoreArgs&, const EkvAdaArgs&, int layer_count, hipStream_t);
+#define EKV_SCORE_SELECT_ADA(nt, elem) EkvSelectAdaFn EKV_FN_SCORE_SELECT_ADA(nt, elem);
+#include "ekv_instances.def"
+
+namespace {
+struct SelectAdaInstance {
+  int threads;
+  bool bf16;
+  EkvSelectAdaFn* fn;
+};
+const SelectAdaInstance kSelectAda[] = {
+#define EKV_SCORE_SELECT_ADA(nt, elem) {nt, EKV_IS_##elem, EKV_FN_SCORE_SELECT_ADA(nt, elem)},
+#include "ekv_instances.def"
+};
+}  // namespace
+
+hipError_t ekv_launch_score_select_ada(const EkvScoreArgs& a, const EkvAdaArgs& ada, int layer_count, hipStream_t s, bool bf16) {
+  const int64_t W = (int64_t)a.n_slots - a.score_off;
+  const int64_t rows = a.colsum != nullptr ? 0 : (int64_t)(a.n_q_heads / a.n_kv_heads) * a.q_len;
+  const int threads = ekv_score_pool_threads((int64_t)a.n_kv_heads * layer_count, W, rows, a.big_rows != nullptr);
+  for (const SelectAdaInstance& in : kSelectAda)
+    if (in.threads == threads && in.bf16 == bf16) return in.fn(a, ada, layer_count, s);
+  return hipErrorInvalidValue;
+}
+
 hipError_t ekv_launch_tova_headmean(const EkvScoreArgs& a, int layer_count, hipStream_t s) {
   return ekv_launch_tova_headmean_nt512(a, layer_count, s);
 }

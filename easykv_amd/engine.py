@@ -40,6 +40,9 @@ class StepPlan:
     n_evict: Optional[int] = None   # prefill steps: victims per head (None: ``stride``); one-shot prompt compression evicts n - budget at once
     pool: int = 1               # pooled selection (include/easykv_hip.h): kernel size of the pooling of the ranking values, odd; 1 = off
     pool_op: str = "max"        # ... 'max' or 'avg'
+    # adaptive head budgets (include/easykv_hip.h): (evict_min, evict_max), the bounds of a head's victims around n_evict; the layer evicts
+    # H * n_evict rows and the pooled ranking values decide each head's share (pool = 1: the unpooled rows rank).  None = off
+    head_adaptive: Optional[tuple] = None
 
 
 # The row formats of a quantised bank, by ``kv_quant`` (include/easykv_hip.h, "kv8" / "kv4" / "kv6" / "kv84" / "kv164"): everything the bank, the batch and the
@@ -306,6 +309,10 @@ class KVBank:
         self._score_done = [None] * n_layers
         self._defer = None      # deferred-scorer state of the token step in flight (attend(..., defer=True) ... flush())
         self._pool_fams = {}    # (radius, op) -> the pooled family's calls and struct (_family)
+        self._ada_fams = {}     # (radius, op, evict_min, evict_max) -> the adaptive family's calls and struct (_ada_family)
+        self._ada_out = None    # device int32 [n_layers][H]: the victim count of every head after an adaptive step
+        self._view = None       # the bank as n_layers * H one-head layers, for decode steps over heads of different lengths (_attend_ragged)
+        self.head_slots = None  # [n_layers][H] ints after an adaptive step (None: every head of a layer holds n_slots rows)
         self.arrive = torch.zeros(n_layers, n_kv_heads, dtype=torch.int32, device=dev)     # arrival counters of the in-kernel fold
         self._bank = Bank(_ptr(self.k), _ptr(self.v), self._slot_of_pos.data_ptr(),
                           self._score_sum.data_ptr() if scored else None, self._score_sq.data_ptr() if scored else None,
@@ -583,6 +590,8 @@ class KVBank:
         """(check, info, workspace, attend, leading descriptor arguments) of the call family a step of ``plan`` goes to: the bank's own,
         or — a property of the STEP, ``plan.pool > 1`` — the pooled family (ekv_pool_*), whose struct stands behind the dtype.  There is
         no pooled capped, sink, window, long or quantised call: such a bank raises :class:`EkvError`."""
+        if plan is not None and plan.head_adaptive is not None:
+            return self._ada_family(plan)
         if plan is None or plan.pool == 1:
             return self._check_fn, self._info_fn, self._ws_fn, self._attend_fn, self._desc_ref
         if not (isinstance(plan.pool, int) and not isinstance(plan.pool, bool) and plan.pool >= 3 and plan.pool % 2 == 1):
@@ -600,6 +609,133 @@ class KVBank:
             desc = _lib.Pool(*key)      # (kept alive with the bank: a deferred token step caches the reference)
             fam = self._pool_fams[key] = tuple(getattr(self.lib, _lib.POOL_CALLS[what]) for what in _lib.STEP_CALLS) + ((C.byref(desc),), desc)
         return fam[:5]
+
+    def _ada_family(self, plan):
+        """The adaptive family (ekv_ada_*) of a step with ``plan.head_adaptive = (evict_min, evict_max)``: the struct carries the pooling
+        (kernel size 1 = radius 0), the bounds and the device row ``[n_layers][H]`` the step writes each head's victim count to.  There is
+        no adaptive capped, sink, window, long or quantised call: such a bank raises :class:`EkvError`."""
+        bounds = plan.head_adaptive
+        if not (isinstance(bounds, (tuple, list)) and len(bounds) == 2 and all(isinstance(x, int) and not isinstance(x, bool) for x in bounds)):
+            raise ValueError(f"StepPlan.head_adaptive is (evict_min, evict_max), two integers, not {bounds!r}")
+        if not (isinstance(plan.pool, int) and not isinstance(plan.pool, bool) and plan.pool >= 1 and plan.pool % 2 == 1):
+            raise ValueError(f"StepPlan.pool is the kernel size of the pooling: an odd integer >= 1, not {plan.pool!r}")
+        if plan.pool_op not in _lib.POOL_OPS:
+            raise ValueError(f"StepPlan.pool_op must be 'max' or 'avg', not {plan.pool_op!r}")
+        for what, on in (("logit_cap", self.logit_cap is not None), ("sinks", self.sinks is not None), ("windows", self.windows is not None),
+                         ("long_rows=True", self.long_rows), (f"kv_quant={self.kv_quant!r}", self._fmt is not None)):
+            if on:
+                raise _lib.EkvError(f"an adaptive step (StepPlan.head_adaptive) on a bank created with {what}: there is no adaptive "
+                                    f"{what.split('=')[0].replace('_', ' ')} call (adaptive head budgets serve plain 16-bit banks)")
+        if self._ada_out is None:
+            self._ada_out = torch.zeros(self.n_layers, self.n_kv_heads, dtype=torch.int32, device=self.device)
+        key = self._ada_key(plan)
+        fam = self._ada_fams.get(key)
+        if fam is None:
+            desc = _lib.Ada(*key, self._ada_out.data_ptr())      # (kept alive with the bank: a deferred token step caches the reference)
+            fam = self._ada_fams[key] = tuple(getattr(self.lib, _lib.ADA_CALLS[what]) for what in _lib.STEP_CALLS) + ((C.byref(desc),), desc)
+        return fam[:5]
+
+    @staticmethod
+    def _ada_key(plan):
+        return (plan.pool // 2, _lib.POOL_OPS[plan.pool_op], int(plan.head_adaptive[0]), int(plan.head_adaptive[1]))
+
+    def _ada_finish(self, layer_begin, lc, t):
+        """After an adaptive step of layers [layer_begin, layer_begin + lc) over ``t`` rows: ONE device-to-host copy of the heads' victim
+        counts; ``head_slots[l][h]`` = rows head h of layer l holds now, ``n_slots[l]`` their maximum (positions [head_slots, n_slots) of
+        a shorter head's slot map are its free tail)."""
+        k = self._ada_out[layer_begin:layer_begin + lc].cpu().tolist()
+        if self.head_slots is None:
+            self.head_slots = [None] * self.n_layers
+        for i, row in enumerate(k):
+            self.head_slots[layer_begin + i] = [t - x for x in row]
+            self.n_slots[layer_begin + i] = max(self.head_slots[layer_begin + i])
+
+    def _ada_row(self, plan, layer_begin):
+        """Point the n_evict_out of ``plan``'s adaptive struct at row ``layer_begin`` (row i of a call is layer layer_begin + i).  The struct
+        is shared by every step of the same pooling and bounds, so each call that launches sets it first."""
+        self._ada_fams[self._ada_key(plan)][5].n_evict_out = self._ada_out.data_ptr() + 4 * layer_begin * self.n_kv_heads
+
+    def _ada_ids(self, plan, lc, evict_ids):
+        """The evict_ids of an adaptive step: ``[lc][H][evict_max]`` int32 on the bank's device, whatever the caller wants back — the
+        scorer writes head h's entries at pitch evict_max.  A caller's tensor of any other shape, type or place is refused; a fresh one
+        is filled with -1 (entries beyond a head's own count are left unwritten)."""
+        shape = (lc, self.n_kv_heads, int(plan.head_adaptive[1]))
+        if evict_ids is None or evict_ids is False:
+            return torch.full(shape, -1, dtype=torch.int32, device=self.device)
+        dev = torch.device(self.device)
+        elsewhere = evict_ids.device.type != dev.type or (dev.index is not None and evict_ids.device.index != dev.index)
+        if tuple(evict_ids.shape) != shape or evict_ids.dtype != torch.int32 or elsewhere or not evict_ids.is_contiguous():
+            raise ValueError(f"evict_ids of an adaptive step must be a contiguous int32 tensor {list(shape)} ([layers][H][evict_max]) on {self.device}, "
+                             f"not {list(evict_ids.shape)} {evict_ids.dtype} on {evict_ids.device}")
+        return evict_ids
+
+    def _ragged(self, layer_begin, lc):
+        return self.head_slots is not None and any(r is not None for r in self.head_slots[layer_begin:layer_begin + lc])
+
+    def ragged(self, layer):
+        """Do the heads of ``layer`` hold different numbers of rows (an adaptive step ran on it)?"""
+        return self._ragged(layer, 1)
+
+    def _refuse_ragged(self, layer_begin, lc):
+        if self._ragged(layer_begin, lc):
+            raise _lib.EkvError("the heads of these layers hold different numbers of rows (an adaptive step ran): they take plain decode steps "
+                                "(attend with phase='decode', whole call, plain keys) and nothing else until reset()")
+
+    def _attend_ragged(self, plan, q, k_new, v_new, layer_begin, out, evict_ids):
+        """A decode step of layers whose heads hold different numbers of rows (after an adaptive step), with no new attention kernel: the
+        bank ``[L][H][cap]`` is byte for byte a bank of ``L * H`` layers with ONE KV head and ``rep`` query heads — K / V rows, slot
+        maps, score rows, arrival counters, births and slot states are all indexed by ``layer * H + head`` — so one layer's step is the
+        batched call (``ekv_batch_step_attend``, include/easykv_hip.h) on that view: ``H`` table entries ``{layer = l * H + h, n_slots =
+        T_h + 1}``, and the layer's ``q`` / ``out`` ``[H * rep][1][D]`` and ``k_new`` / ``v_new`` ``[H][1][D]`` are the call's own
+        ``[entries][rep][1][D]`` / ``[entries][1][1][D]``.  One call per layer.  Every entry evicts one row (every T_h stays put) or none
+        (every head grows by one), as the plan says.  The batch call's limits hold: H <= 64, GQA <= 8, at most 6144 slots per head and
+        cap % 4 == 0 for scored steps; the library refuses anything else before a launch."""
+        lc, H = q.shape[0], self.n_kv_heads
+        if any(self._slot_rows[layer_begin:layer_begin + lc]):
+            self._ensure_ordered()
+        if any(ev is not None for ev in self._score_done[layer_begin:layer_begin + lc]):
+            self.join()
+        if out is None:
+            out = torch.empty(lc, self.n_q_heads, 1, self.head_dim, dtype=self.dtype, device=self.device)
+        q, k_new, v_new = (t.to(self.device, self.dtype).contiguous() for t in (q, k_new, v_new))
+        if not out.is_contiguous():
+            raise ValueError("out of a step over heads of different lengths must be contiguous")
+        if self._view is None:      # (made once per bank: the view struct, the two library calls, one table per layer)
+            b = self._bank
+            self._view = (_lib.Bank(b.k, b.v, b.slot_of_pos, b.score_sum, b.score_sq, b.score_cnt, self.n_layers * H, self.n_q_heads // H, 1, self.head_dim,
+                                    self.cap, b.arrive, b.birth, b.slot_state),
+                          {what: getattr(self.lib, _lib.step_call_name(None, True, what)) for what in ("workspace_bytes", "step_attend")},
+                          [(_lib.Seq * H)() for _ in range(self.n_layers)])
+        view, calls, tables = self._view
+        first = self.make_step(plan, 1, layer_begin, 1)
+        want_ids = evict_ids is not False and first.n_evict > 0
+        if first.n_evict > 0 and (evict_ids is None or evict_ids is False):
+            evict_ids = torch.empty(lc, H, 1, dtype=torch.int32, device=self.device)
+        elif first.n_evict > 0 and (tuple(evict_ids.shape) != (lc, H, 1) or evict_ids.dtype != torch.int32 or not evict_ids.is_contiguous()
+                                    or evict_ids.device.type != torch.device(self.device).type):
+            raise ValueError(f"evict_ids of this decode step must be a contiguous int32 tensor [{lc}, {H}, 1] on {self.device}")
+        _lib.set_resident_bytes(self.resident_bytes)
+        for i in range(lc):
+            l = layer_begin + i
+            lens = self.head_slots[l] if self.head_slots[l] is not None else [self.n_slots[l]] * H
+            st = self.make_step(plan, 1, l, 1)
+            st.layer_begin, st.layer_count, st.n_split = 0, H, plan.n_split
+            st.q_token_stride = st.q_head_stride = st.kv_token_stride = st.kv_head_stride = st.out_token_stride = st.out_head_stride = 0
+            tb = tables[l]
+            for h, e in enumerate(tb):
+                e.layer, e.n_slots, e.score_off, e.n_evict = l * H + h, lens[h] + 1, st.score_off, st.n_evict
+                e.phys_extent = max(self.extent[l], lens[h] + 1)
+                e.win_lo, e.win_tail, e.roco_k1, e.range_start = st.win_lo, st.win_tail, st.roco_k1, st.range_start
+            if max(lens) + 1 > self.cap:
+                raise ValueError(f"layer {l}: a head holds {max(lens)} rows, the bank's capacity is {self.cap}")
+            ws = self._workspace(calls["workspace_bytes"](C.byref(view), C.byref(st), self._dt, tb, H))
+            check(calls["step_attend"](C.byref(view), C.byref(st), self._dt, tb, H, _ptr(q[i]), _ptr(k_new[i]), _ptr(v_new[i]), _ptr(out[i]),
+                                       _ptr(evict_ids[i]) if st.n_evict > 0 else None, _ptr(ws), ws.numel(), self._stream()), "ekv_batch_step_attend")
+            self.head_slots[l] = [t + 1 - st.n_evict for t in lens]
+            self.n_slots[l] = max(self.head_slots[l])
+            self.extent[l] = max(e.phys_extent for e in tb)
+            self._tokens[l] += 1
+        return out, (evict_ids if want_ids else None)
 
     def _step_check(self, st, fam=None):
         fam = fam or self._family()
@@ -633,6 +769,7 @@ class KVBank:
     def reset(self):
         check(self.lib.ekv_bank_reset(C.byref(self._bank), self._stream()), "ekv_bank_reset")
         self.n_slots = [0] * self.n_layers
+        self.head_slots = None
         self.extent = [0] * self.n_layers
         self._slot_rows = [False] * self.n_layers
         self._slot_min_tail = [1 << 30] * self.n_layers
@@ -725,7 +862,8 @@ class KVBank:
         lc = self.n_layers - layer_begin if layer_count is None else layer_count
         self._quant_refuse(True, "ordered_kv (a row move)")
         self._ensure_ordered(layer_begin, lc)
-        t = self.n_slots[layer_begin]
+        # (after an adaptive step: the longest head of these layers; a shorter head's rows [head_slots, t) are its evicted ones)
+        t = self.n_slots[layer_begin] if self.head_slots is None else max(self.n_slots[layer_begin:layer_begin + lc])
         k = torch.empty(lc, self.n_kv_heads, t, self.head_dim, dtype=self.dtype, device=self.device)
         v = torch.empty_like(k)
         check(self.lib.ekv_gather_ordered(C.byref(self._bank), layer_begin, lc, t, _ptr(k), _ptr(v), self._stream()), "ekv_gather_ordered")
@@ -738,13 +876,16 @@ class KVBank:
         rows ``[0, T)`` (``ekv_gather_ordered`` out of this bank, ``load_rows`` into the fresh one, whose slot map is the identity), so
         ``extent == T`` and a one-launch decode step streams ``T`` rows, not the prompt's.  The score rows' first ``T`` columns, the
         softmax scale / cap / sinks and — a window bank — the rows' token positions and the tokens seen are carried over.  Every layer must
-        hold the same number of rows; a quantised bank, a bank on the slot-indexed layout mid-capture or with an open deferred step
+        hold the same number of rows — unless an adaptive step left the heads with different lengths: then ``T`` is the longest head's
+        count, every head's first ``T`` positions are gathered (a shorter head's live rows come first, its free tail behind them) and
+        ``head_slots`` is carried over; a quantised bank, a bank on the slot-indexed layout mid-capture or with an open deferred step
         raises.  This bank is left as it is: the caller drops it."""
         self._quant_refuse(True, "hand_over (a row move)")
         if self._defer is not None and self._defer["pending"]:
             raise _lib.EkvError("hand_over(): a deferred token step is open (flush() first)")
-        t = self.n_slots[0]
-        if any(n != t for n in self.n_slots):
+        ragged = self._ragged(0, self.n_layers)      # (after an adaptive step: the longest head's count, of every head)
+        t = max(self.n_slots) if ragged else self.n_slots[0]
+        if not ragged and any(n != t for n in self.n_slots):
             raise _lib.EkvError(f"hand_over(): the layers hold different numbers of rows {sorted(set(self.n_slots))}")
         if t < 1 or cap < t:
             raise ValueError(f"hand_over(cap={cap}): the bank holds {t} rows per head")
@@ -761,6 +902,9 @@ class KVBank:
             for name in ("_score_sum", "_score_sq", "_score_cnt"):      # (ordered layout: ordered_kv brought this bank back to it)
                 getattr(new, name)[:, :, :t].copy_(getattr(self, name)[:, :, :t])
         new._tokens = list(self._tokens)
+        if ragged:      # (identity slot map: head h's live rows are [0, T_h), its free tail starts at T_h; the score columns past T_h are zero)
+            new.head_slots = [list(r) if r is not None else [self.n_slots[l]] * self.n_kv_heads for l, r in enumerate(self.head_slots)]
+            new.n_slots = [max(r) for r in new.head_slots]
         return new
 
     def compact_inplace(self, evict_ids, layer_begin=0):
@@ -813,7 +957,7 @@ class KVBank:
         """(n_split, fused) the library will use for this step."""
         st = self.make_step(plan, q_len, layer_begin, self.n_layers - layer_begin if layer_count is None else layer_count)
         st.phases = phases
-        if self._fmt is not None or self.long_rows or self.logit_cap is not None or self.sinks is not None or self.windows is not None or plan.pool != 1:      # (the dry run of the bank's own family / the step's: a step it refuses plans as not fused)
+        if self._fmt is not None or self.long_rows or self.logit_cap is not None or self.sinks is not None or self.windows is not None or plan.pool != 1 or plan.head_adaptive is not None:      # (the dry run of the bank's own family / the step's: a step it refuses plans as not fused)
             info = self.step_info(plan, q_len, layer_begin, layer_count, phases)
             return info["n_split"], bool(info["fused"])
         ns, fu = C.c_int32(0), C.c_int32(0)
@@ -895,6 +1039,7 @@ class KVBank:
         d = self._defer
         n = q.shape[2]
         self._quant_refuse(n > 1, "a chunk step (q_len > 1)")
+        self._refuse_ragged(layer, 1)
         t = self.n_slots[layer] + n
         if self._slot_rows[layer]:
             self._ensure_ordered()      # (all layers in one launch: the conversion ranks births by counting, ~0.2 ms per launch of <= 256 heads)
@@ -913,6 +1058,8 @@ class KVBank:
             check(self._step_check(st, fam), "ekv_step_check (deferred scorer)")
             need = self._step_ws_bytes(st, fam)
             ids = torch.empty(self.n_layers, self.n_kv_heads, st.n_evict, dtype=torch.int32, device=self.device) if st.n_evict > 0 else None
+            if ids is not None and plan.head_adaptive is not None:
+                ids = self._ada_ids(plan, self.n_layers, None)
             ws = self._workspace(need)
             # everything that is the same for all layers of the token step is resolved once: the per-layer call below is on the
             # critical path of the decoder stack (host cost per layer ~ GPU cost per layer in this regime)
@@ -974,10 +1121,15 @@ class KVBank:
         st.layer_begin, st.layer_count, st.defer_index, st.phases = 0, self.n_layers, 0, 8
         st.q_token_stride = st.q_head_stride = st.kv_token_stride = st.kv_head_stride = st.out_token_stride = st.out_head_stride = 0      # (no caller tensors in this call)
         st.phys_extent = max(max(self.extent), d["t"])
+        adaptive = d["plan"].head_adaptive is not None
+        if adaptive:
+            self._ada_row(d["plan"], 0)
         check(self._step_attend(st, ws.data_ptr(), ws.data_ptr(), ws.data_ptr(), ws.data_ptr(),
                                 _ptr(d["ids"]), d["rope"][0], d["rope"][1], ws.data_ptr(), ws.numel(), d["stream"], fam=d["fam"]), "ekv_step_attend")
         for l in range(self.n_layers):
             self.n_slots[l] = d["t"] - st.n_evict
+        if adaptive:
+            self._ada_finish(0, self.n_layers, d["t"])
         d["pending"] = 0
         d["t"] = -1
         return d["ids"] if st.n_evict > 0 else None
@@ -997,8 +1149,16 @@ class KVBank:
             return self._attend_deferred(plan, q, k_new, v_new, layer_begin, out, q_pos), None
         lc, _, n, _ = q.shape
         self._quant_refuse(n > 1, "a chunk step (q_len > 1)")
+        if self._ragged(layer_begin, lc):
+            if not (n == 1 and plan.phase == "decode" and phases == 0 and not overlap_scorer and plan.head_adaptive is None and plan.pool == 1
+                    and not plan.streaming):
+                self._refuse_ragged(layer_begin, lc)
+            return self._attend_ragged(plan, q, k_new, v_new, layer_begin, out, evict_ids)
         fam = self._family(plan)      # (a pooled step on a bank that has no pooled call raises here, before anything is written)
         pooled = fam[3] is not self._attend_fn
+        adaptive = plan.head_adaptive is not None
+        if adaptive:
+            self._ada_row(plan, layer_begin)
         self._set_q_pos(layer_begin, lc, q_pos)
         st = self.make_step(plan, n, layer_begin, lc)
         # one-launch decode steps run on the slot-indexed layout of the score rows (nothing moves on an eviction); everything else
@@ -1023,7 +1183,9 @@ class KVBank:
             out = torch.empty(lc, self.n_q_heads, n, self.head_dim, dtype=self.dtype, device=self.device)
         q, k_new, v_new = _stride_rows(st, q, k_new, v_new, out, self.dtype)
         want_ids = evict_ids is not False
-        if evict_ids is False:      # the caller has no use for the evicted order indices (the slot-indexed layout then skips ranking the victim)
+        if adaptive and st.n_evict > 0:
+            evict_ids = self._ada_ids(plan, lc, evict_ids)
+        elif evict_ids is False:      # the caller has no use for the evicted order indices (the slot-indexed layout then skips ranking the victim)
             evict_ids = None if slot else torch.empty(lc, self.n_kv_heads, max(st.n_evict, 1), dtype=torch.int32, device=self.device)
         elif st.n_evict > 0 and evict_ids is None:
             evict_ids = torch.empty(lc, self.n_kv_heads, st.n_evict, dtype=torch.int32, device=self.device)
@@ -1044,6 +1206,8 @@ class KVBank:
         if phases != 1:     # phases == 1 launches the attention kernel only; the slot map is untouched
             for l in range(layer_begin, layer_begin + lc):
                 self.n_slots[l] = st.n_slots - st.n_evict
+            if adaptive and (phases == 0 or phases & (2 | 8)):
+                self._ada_finish(layer_begin, lc, st.n_slots)
         for l in range(layer_begin, layer_begin + lc):      # the new rows are written by the attention kernel
             self.extent[l] = st.phys_extent
             if phases == 0 or phases & 1:      # (the calls that run the attention kernel, which appends the token's row)

@@ -689,6 +689,54 @@ int ekv_pool_step_attend(const ekv_bank *bank, const ekv_step *step, int32_t dty
                          const void *v_new, void *out, int32_t *evict_ids, const float *rope_cos, const float *rope_sin,
                          void *workspace, size_t workspace_bytes, void *stream);
 
+/* Adaptive head budgets (ABI 8, additive): the _typed calls with an ekv_ada struct behind the element type.  Where a pooled step evicts
+ * n_evict rows of every KV head, an adaptive step evicts H * n_evict rows of a LAYER and lets the pooled ranking values decide how many of
+ * them each head gives (Ada-KV on SnapKV-style selection): a head with peaked attention keeps few rows, a head with flat attention many.
+ *
+ * Take one layer.  W = n_slots - score_off, the candidate range is R = [win_lo, W - win_tail), C = |R|.
+ *   r_h[j]   the ranking value of candidate j of head h: exactly the pooled selection's (above) for EKV_POLICY_H2O_HEAD / EKV_POLICY_TOVA,
+ *            max or avg, radius r, the stencil clipped to R.  New here: radius = 0 means the unpooled score row.
+ *   order    the elements of a head are ordered by (key(r_h[j]), j), key = the library's order-preserving float key; NaN ranks largest.
+ * Two bounds, in victims per head: 0 <= evict_min <= n_evict <= evict_max <= C.
+ *   FORCED      the evict_min smallest elements of every head.
+ *   PROTECTED   the C - evict_max largest elements of every head.
+ *   FREE        everything else.
+ * The layer evicts H * n_evict elements in total: all forced ones, and the H * (n_evict - evict_min) smallest free elements of all heads
+ * together, ordered by (key, head, j).  k_h is head h's share of that total, and the victims of head h are exactly its own k_h smallest
+ * elements (forced is a subset of them, none is protected, by construction).  Everything behind the marking is the pooled step's:
+ * destinations, the compaction of the score rows and of the slot map, the count tails.  Only k is per head: after the step head h has
+ * n_slots - k_h rows, and the k_h of a layer sum to H * n_evict.  With evict_min = evict_max = n_evict the step equals the pooled call of
+ * the same step bit for bit; with radius = 0 it equals the plain call's generic scorer (n_evict > 1).
+ *
+ * n_evict_out: device int32 [layer_count][H], row i = layer layer_begin + i of the call; the step writes k_h there (a deferred step: the
+ * flush, for all its layers).  evict_ids is [layer_count][H][evict_max]; head h's first k_h entries are written in ascending order of
+ * position, the rest is left as it was.  The caller reads n_evict_out (one device-to-host copy) to learn each head's length.
+ *
+ * An adaptive step plans as the pooled call of the same (bank, step, dtype): every in-kernel scorer tail off, the same tiling, scheme and
+ * launches in front — and where the pooled call ends in its scorer launch, three launches: rank (the EKV_ADA build of the generic scorer:
+ * accumulates, writes the score rows back, pools, exports a head's W keys and the class of each), allot (one workgroup per layer: a radix
+ * select over the free keys of all heads finds the (key, head, j) threshold and writes k_h), select (the same build, entered at the
+ * selection with k = k_h).  n_evict never goes through the host in between.  ekv_ada_step_info reports the pooled call's fields with
+ * n_launches two higher; ekv_ada_workspace_bytes is the pooled call's plus 5 bytes per (layer, head, padded column).
+ * EKV_E_ARG, behind the element type and before anything else is read: a NULL struct, NULL n_evict_out, radius < 0, an unknown op, bounds
+ * out of order (evict_min < 0, evict_min > n_evict, n_evict < 1, n_evict > evict_max, evict_max > C).  EKV_E_UNSUPPORTED with zero
+ * launches and ekv_ada_workspace_bytes = 0: everything the pooled call refuses (any policy but H2O_HEAD / TOVA, rope_on_read,
+ * tova_head_mean, EKV_PHASE_SLOT_ROWS, a row beyond the generic scorer's width) and more than 64 KV heads.  16-bit rows and single
+ * sequences only. */
+typedef struct ekv_ada {
+  int32_t radius;
+  int32_t op;
+  int32_t evict_min;
+  int32_t evict_max;
+  int32_t *n_evict_out;
+} ekv_ada;
+int ekv_ada_step_check(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const ekv_ada *ada);
+int ekv_ada_step_info(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const ekv_ada *ada, int32_t *info, int32_t n_info);
+size_t ekv_ada_workspace_bytes(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const ekv_ada *ada);
+int ekv_ada_step_attend(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const ekv_ada *ada, const void *q, const void *k_new,
+                        const void *v_new, void *out, int32_t *evict_ids, const float *rope_cos, const float *rope_sin,
+                        void *workspace, size_t workspace_bytes, void *stream);
+
 /* Batched decode steps (ABI 8, additive): ONE call, and one launch per kernel kind, serves n_seq sequences whose caches have
  * different lengths and different eviction geometry.  Each entry of the table names the bank layer it attends and carries what
  * ekv_step holds per step; entry i owns row i of the call's tensors.  The layers of a table need not be contiguous or ordered, so
