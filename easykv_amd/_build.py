@@ -78,6 +78,10 @@ FAMILIES = {
     "EKV_SCORE_SELECT_ADA": lambda nt, elem: (
         "ekv_score_select.inc", f"ekv_score_select_ada_nt{nt}" + _tags(elem), _on(elem) + [f"-DEKV_SS_NT={nt}", "-DEKV_ADA=1"]),
     "EKV_SCORE_ALLOT": lambda nt: ("ekv_score_allot.inc", "ekv_score_allot", [f"-DEKV_ALLOT_NT={nt}"]),
+    # decode steps over KV heads of different lengths (-DEKV_HEADS=1): the split decode kernel and the scorer behind it, plain keys, 16-bit rows
+    "EKV_DECODE_HEADS": lambda elem, d: (
+        "ekv_attn_decode.inc", f"ekv_attn_decode_d{d}_heads" + _tags(elem), _on(elem) + [f"-DEKV_D={d}", "-DEKV_ROPE=false", "-DEKV_HEADS=1"]),
+    "EKV_DECODE_SCORE_HEADS": lambda elem: ("ekv_decode_score.inc", "ekv_decode_score_heads" + _tags(elem), _on(elem) + ["-DEKV_HEADS=1"]),
 }
 
 
@@ -131,7 +135,7 @@ def later_instances():
 
 
 def later_objects():
-    """(object name, hipcc arguments) of the instances of ekv_instances_later.def (the kv84 decode instances, the kv164 ones, the long-row scorer, head_dim 256, the soft-capped instances, the sink instances, the window instances, the pooled scorer, the adaptive scorer and its allot kernel)."""
+    """(object name, hipcc arguments) of the instances of ekv_instances_later.def (the kv84 decode instances, the kv164 ones, the long-row scorer, head_dim 256, the soft-capped instances, the sink instances, the window instances, the pooled scorer, the adaptive scorer and its allot kernel, the heads instances)."""
     return _instance_objects(later_instances())
 
 

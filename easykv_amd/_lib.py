@@ -63,6 +63,9 @@ POOL_OPS = {"max": 0, "avg": 1}      # EKV_POOL_MAX, EKV_POOL_AVG
 # the adaptive family (include/easykv_hip.h, "adaptive head budgets"): the _typed calls with an ekv_ada struct behind the dtype; 16-bit rows, one sequence
 ADA_CALLS = {what: "ekv_ada_" + what for what in STEP_CALLS}
 EXPORTS += tuple(ADA_CALLS[what] for what in STEP_CALLS)
+# the heads family (include/easykv_hip.h, "heads"): the _typed calls with an ekv_heads struct behind the dtype and no rope tables; 16-bit rows
+HEADS_CALLS = {what: "ekv_heads_" + what for what in STEP_CALLS}
+EXPORTS += tuple(HEADS_CALLS[what] for what in STEP_CALLS)
 
 
 class Bank(C.Structure):
@@ -112,6 +115,12 @@ class Ada(C.Structure):
     """ekv_ada: pooling (radius >= 0, op) and the bounds of a head's victims of an adaptive step; n_evict_out: device int32 [layer_count][H]
     (include/easykv_hip.h, "adaptive head budgets")."""
     _fields_ = [("radius", C.c_int32), ("op", C.c_int32), ("evict_min", C.c_int32), ("evict_max", C.c_int32), ("n_evict_out", C.c_void_p)]
+
+
+class Heads(C.Structure):
+    """ekv_heads: the row counts of a decode step over KV heads of different lengths — rows: device int32 [n_layers][H], rows_host: a host
+    copy of the same (every check and plan reads this one), grow: rows every head has gained since (include/easykv_hip.h, "heads")."""
+    _fields_ = [("rows", C.c_void_p), ("rows_host", C.c_void_p), ("grow", C.c_int32)]
 
 
 class Step(C.Structure):
@@ -184,6 +193,9 @@ def load():
                 getattr(lib, WIN_CALLS[what]).argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, C.POINTER(Win)] + tails[what]
                 getattr(lib, POOL_CALLS[what]).argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, C.POINTER(Pool)] + tails[what]
                 getattr(lib, ADA_CALLS[what]).argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, C.POINTER(Ada)] + tails[what]
+            tails["step_attend"] = [vp] * 6 + [C.c_size_t, vp]      # (the heads family: no rope tables)
+            for what in STEP_CALLS:
+                getattr(lib, HEADS_CALLS[what]).argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, C.POINTER(Heads)] + tails[what]
         if desc:
             getattr(lib, f"ekv_{rows}_quantize").argtypes = [C.POINTER(Bank), C.POINTER(desc), i32, i32, i32, i32, vp]
             getattr(lib, f"ekv_{rows}_dequantize").argtypes = [C.POINTER(Bank), C.POINTER(desc), i32, i32, i32, i32, vp, vp, vp]

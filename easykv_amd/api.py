@@ -147,6 +147,7 @@ class BudgetedKVCache:
         self.n_attend = 0        # attend() calls of the forward in flight (checked by the driver after every forward)
         self._defer_this_forward = None
         self.defer_chunk_scorer = True     # scored chunk steps of a layer-per-call model: one scorer launch per forward (round 4)
+        self.head_decode = None            # 'deferred': decode layers over heads of different lengths go through attend(defer=True) + one flush (generation_config['head_decode'])
 
     @property
     def kv_quant(self):
@@ -250,9 +251,19 @@ class BudgetedKVCache:
             self._defer_this_forward = bool(n > 1 and plan.phase == "prefill" and plan.policy in ("roco", "h2o_head", "tova") and (plan.accumulate or plan.evict)
                                             and self.defer_chunk_scorer and self._defer_fits(plan, n))
         deferable_chunk = self._defer_this_forward
+        if n == 1 and plan.phase == "decode" and self.head_decode == "deferred" and self.bank.head_slots is not None:
+            # heads of different lengths, deferred (generation_config['head_decode'] = 'deferred'): exactly like a uniform bank below —
+            # attention + fold of this layer now through the heads family (ekv_heads_*), ONE scorer launch over all owned layers and
+            # heads after the last one
+            out, _ = self.bank.attend(plan, q, k, v, layer_begin=layer_idx, defer=True, out=out)
+            if self.n_attend == self.layer_count:
+                ids = self.bank.flush()
+                if self._cur is not None and ids is not None:
+                    self._cur.extend(ids[l] for l in range(self.layer_count))
+            return out
         if n == 1 and plan.phase == "decode" and self.bank.ragged(layer_idx):
-            # heads of different lengths (adaptive head budgets): the layer's step is the batched call on the one-head view, whole —
-            # there is no deferred form of it
+            # heads of different lengths (adaptive head budgets): the layer's step is the batched call on the one-head view, whole
+            # (head_decode = 'view', the default)
             out, ids = self.bank.attend(plan, q, k, v, layer_begin=layer_idx, evict_ids=None if self._cur is not None else False)
             if self._cur is not None and ids is not None:
                 self._cur.append(ids[0])
@@ -638,6 +649,16 @@ class _Run:
             if hkv > 64 or hq // hkv > 8:
                 raise ValueError(f"{what}: the decode steps over heads of different lengths serve at most 64 KV heads and GQA factors up to 8 "
                                  f"(this model: {hkv} KV heads, GQA factor {hq // hkv})")
+        # extension key: 'head_decode' — None / 'view' (default: the decode steps of a bank whose heads differ run whole, layer by layer, through
+        # the batched call on the one-head view, KVBank._attend_ragged) or 'deferred': they run like a uniform bank's — attention + fold
+        # per layer, one scorer launch per token — through the heads family (include/easykv_hip.h, "heads").  Opt-in: other kernel kinds
+        # run, so rounding may differ.
+        self.head_decode = cfg.get("head_decode", None)
+        if self.head_decode not in (None, "view", "deferred"):
+            raise ValueError(f"generation_config['head_decode'] must be None, 'view' or 'deferred', not {self.head_decode!r}")
+        if self.head_decode is not None and not self.adaptive:      # (before any bank exists)
+            raise ValueError("generation_config['head_decode'] needs generation_config['head_budgets'] = 'adaptive': only adaptive head budgets "
+                             "leave heads of different lengths")
         self.dev = torch.device(model.device)
         for p in prompts:
             if p.dim() != 2 or p.shape[0] != 1:
@@ -694,6 +715,8 @@ class _Run:
                                 **{k: v for k, v in (("logit_cap", self.logit_cap), ("sm_scale", self.sm_scale), ("sinks", self.sinks),
                                                     ("windows", self.windows)) if v is not None})
         cache.unrotate = hf_rope if self.hf_stream else None
+        if self.head_decode == "deferred":      # (opt-in: set only when asked for)
+            cache.head_decode = "deferred"
         return cache
 
     def forward(self, cache, ids, positions, plan):

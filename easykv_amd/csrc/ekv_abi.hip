@@ -100,6 +100,9 @@ static int call_attend(const EkvCall& c, const void* q, const void* k_new, const
   // token positions; the scorers behind them read logits, partials, row statistics and column sums and are the plain / sink ones)
   const bool window = P.window != 0;
   const EkvWinArgs win = window ? EkvWinArgs{c.win->tok_pos, c.win->windows, c.win->q_pos0} : EkvWinArgs{};
+  // (a heads plan: the split kernel and the split path's scorer run the heads instances, which read each head's row count from the table)
+  const bool heads = P.heads != 0;
+  const EkvHeadsArgs hd = heads ? EkvHeadsArgs{c.hd->rows, c.hd->grow} : EkvHeadsArgs{};
   drop_stale_error();
   for (int i = 0; i < P.n_list; ++i) {
     const EkvLaunch& L = P.list[i];
@@ -112,6 +115,7 @@ static int call_attend(const EkvCall& c, const void* q, const void* k_new, const
     // (a capped plan: the decode launches and the 16x16x32 chunk kernel, the only kernels with capped instances)
     // (a sink plan likewise)
     if (sinks && (L.kind == EKV_RUN_CHUNK_LDS || L.kind == EKV_RUN_RESIDENT || L.kind == EKV_RUN_FLUSH || (L.kind == EKV_RUN_CHUNK && P.wide))) return EKV_E_UNSUPPORTED;
+    if (heads && L.kind != EKV_RUN_DECODE && L.kind != EKV_RUN_FOLD && L.kind != EKV_RUN_DECODE_SCORE) return EKV_E_UNSUPPORTED;
     if (capped && (L.kind == EKV_RUN_CHUNK_LDS || L.kind == EKV_RUN_RESIDENT || L.kind == EKV_RUN_FLUSH || (L.kind == EKV_RUN_CHUNK && P.wide))) return EKV_E_UNSUPPORTED;
     switch (L.kind) {
       case EKV_RUN_FUSED_DECODE:
@@ -123,7 +127,8 @@ static int call_attend(const EkvCall& c, const void* q, const void* k_new, const
       case EKV_RUN_CHUNK_LDS: e = ekv_launch_chunk_lds(aa, sa, D, lc, s, bf16); break;
       case EKV_RUN_RESIDENT: e = ekv_launch_attn_resident(aa, sa, lc, s, bf16); break;
       case EKV_RUN_DECODE:
-        e = window ? ekv_launch_attn_decode_win(aa, sinks, win, D, lc, s, bf16)
+        e = heads ? ekv_launch_attn_decode_heads(aa, hd, D, lc, s, bf16)
+          : window ? ekv_launch_attn_decode_win(aa, sinks, win, D, lc, s, bf16)
           : sinks ? ekv_launch_attn_decode_sink(aa, sinks, D, lc, s, bf16) : ekv_launch_attn_decode(aa, tb, D, lc, s, bf16, rows, capped);
         break;
       case EKV_RUN_CHUNK:
@@ -149,7 +154,10 @@ static int call_attend(const EkvCall& c, const void* q, const void* k_new, const
       case EKV_RUN_RANGE:
         e = ekv_launch_range_evict(bank, st, tb, evict_ids, s);
         break;
-      case EKV_RUN_DECODE_SCORE: e = sinks ? ekv_launch_decode_score_sink(sa, sinks, lc, s, bf16) : ekv_launch_decode_score(sa, tb, lc, s, bf16); break;
+      case EKV_RUN_DECODE_SCORE:
+        e = heads ? ekv_launch_decode_score_heads(sa, hd, lc, s, bf16)
+          : sinks ? ekv_launch_decode_score_sink(sa, sinks, lc, s, bf16) : ekv_launch_decode_score(sa, tb, lc, s, bf16);
+        break;
       case EKV_RUN_TOVA_MEAN: e = sinks ? ekv_launch_tova_headmean_sink(sa, sinks, lc, s) : ekv_launch_tova_headmean(sa, lc, s); break;
       // (a pooled plan: the EKV_POOL instances of the generic scorer, the struct's two words as the kernel's last argument)
       // (an adaptive plan: rank, allot, select — the EKV_ADA instances twice around the allot kernel.  The select phase reads the score rows
@@ -317,6 +325,19 @@ int ekv_kv8_step_attend(const ekv_bank* bank, const ekv_step* st, int32_t dtype,
                         const void* v_new, void* out, int32_t* evict_ids, const float* rope_cos, const float* rope_sin,
                         void* workspace, size_t workspace_bytes, void* stream) {
   return call_attend(kv8_call(bank, st, dtype, q8), q, k_new, v_new, out, evict_ids, rope_cos, rope_sin, workspace, workspace_bytes, stream);
+}
+
+// decode steps over KV heads of different lengths (include/easykv_hip.h, ekv_heads)
+int ekv_heads_step_check(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_heads* heads) { return call_check(heads_call(bank, st, dtype, heads)); }
+int ekv_heads_step_info(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_heads* heads, int32_t* info, int32_t n_info) {
+  return call_info(heads_call(bank, st, dtype, heads), info, n_info);
+}
+size_t ekv_heads_workspace_bytes(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_heads* heads) {
+  return call_workspace_bytes(heads_call(bank, st, dtype, heads));
+}
+int ekv_heads_step_attend(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_heads* heads, const void* q, const void* k_new,
+                          const void* v_new, void* out, int32_t* evict_ids, void* workspace, size_t workspace_bytes, void* stream) {
+  return call_attend(heads_call(bank, st, dtype, heads), q, k_new, v_new, out, evict_ids, nullptr, nullptr, workspace, workspace_bytes, stream);
 }
 
 // batched decode steps (include/easykv_hip.h, ekv_seq)

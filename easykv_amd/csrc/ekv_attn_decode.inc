@@ -101,6 +101,18 @@
 #define EKV_WIN_ALONE(...)
 #endif
 // Both switches at once (the batch kv8 instances) are independent: DESIGN.md §3.9, "Batches".
+// EKV_HEADS = 1 (the EKV_DECODE_HEADS lines of the manifest: 16-bit rows, plain keys): decode steps over KV heads of different lengths
+// (ekv_kernels.h, the third spelling of the shadow macros).  The split kernel alone, with its in-kernel fold: workgroup (split, head, layer)
+// takes its head's row count from the device table and is the uniform kernel from there on — a key range wholly past a short head's end
+// streams nothing and still stores (-inf, 0, 0) and arrives at the fold, as in the batch builds.  There is no one-launch heads build: the
+// objects export no launcher of the fused kernel, so none of its templates is instantiated.
+#ifndef EKV_HEADS
+#define EKV_HEADS 0
+#endif
+#if EKV_HEADS && (EKV_ROPE || EKV_KV8 || EKV_KV4 || EKV_KV6 || EKV_KV84 || EKV_KV164 || EKV_BATCH || EKV_SOFTCAP || EKV_SINK || EKV_WINDOW)
+#error "heads decode instances: 16-bit rows, plain keys, no batch table, no sinks, no window, uncapped logits"
+#endif
+#define EKV_HEAD_IDX blockIdx.y
 #define ekv_attn_decode_kernel EKV_KERNEL_NAME(ekv_attn_decode_kernel)
 #define ekv_decode_fused_kernel EKV_KERNEL_NAME(ekv_decode_fused_kernel)
 // FP8 rows: 4 rows in flight per lane group.  A lane's output slice is 16 floats per query head instead of 8, the query fragment
@@ -128,7 +140,7 @@ constexpr int kFMT = EKV_KV6 ? 6 : (EKV_KV84 ? 84 : (EKV_KV164 ? 164 : 0));     
 // SLOT_LDS = false: slot-map entries are fetched per iteration (needs 16-byte aligned map rows, cap % 4 == 0); saves the
 // staging pass and its barrier, which matters when a workgroup only streams one or two iterations.
 template <int D, int REP, bool ROPE, bool SLOT_LDS>
-__global__ void __launch_bounds__(256) ekv_attn_decode_kernel(const EkvAttnArgs EKV_ARG_A EKV_TB_PARAM EKV_SINK_ONLY(, const float* const sinks) EKV_WIN_ONLY(, const EkvWinArgs win)) {
+__global__ void __launch_bounds__(256) ekv_attn_decode_kernel(const EkvAttnArgs EKV_ARG_A EKV_TB_PARAM EKV_SINK_ONLY(, const float* const sinks) EKV_WIN_ONLY(, const EkvWinArgs win) EKV_HEADS_ONLY(, const EkvHeadsArgs heads)) {
   EKV_SHADOW_A(blockIdx.z)
   using Gm = EkvDecodeGeom<D>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -231,7 +243,7 @@ __global__ void __launch_bounds__(256) ekv_attn_decode_kernel(const EkvAttnArgs 
 #define EKV_FUSED_TWO_PER_CU(D, ROPE, ITEMS, SLOT) \
   ((D) == 128 && !(ROPE) && (SLOT) && (ITEMS) <= 5 && !EKV_G8 && !EKV_MX && !EKV_KV164 && !EKV_BATCH && !EKV_SINK && !EKV_WINDOW && !EKV_SOFTCAP)
 template <int D, int REP, bool ROPE, int ITEMS, int NW, bool SLOT>
-__global__ void __launch_bounds__(64 * NW, (NW >= 8 ? (REP == 1 ? (EKV_FUSED_TWO_PER_CU(D, ROPE, ITEMS, SLOT) ? 4 : 2) : 1) : (SLOT && ITEMS > 12 ? 2 : (REP == 1 ? (EKV_MX ? 2 : 4) : (REP == 2 ? 3 : 2))))) ekv_decode_fused_kernel(const EkvAttnArgs EKV_ARG_A, const EkvScoreArgs EKV_ARG_SC EKV_TB_PARAM EKV_SINK_ONLY(, const float* const sinks) EKV_WIN_ONLY(, const EkvWinArgs win)) {
+__global__ void __launch_bounds__(64 * NW, (NW >= 8 ? (REP == 1 ? (EKV_FUSED_TWO_PER_CU(D, ROPE, ITEMS, SLOT) ? 4 : 2) : 1) : (SLOT && ITEMS > 12 ? 2 : (REP == 1 ? (EKV_MX ? 2 : 4) : (REP == 2 ? 3 : 2))))) ekv_decode_fused_kernel(const EkvAttnArgs EKV_ARG_A, const EkvScoreArgs EKV_ARG_SC EKV_TB_PARAM EKV_SINK_ONLY(, const float* const sinks) EKV_WIN_ONLY(, const EkvWinArgs win) EKV_HEADS_ONLY(, const EkvHeadsArgs heads)) {
   EKV_SHADOW_A(blockIdx.z)
   EKV_SHADOW_SC(blockIdx.z)
   using Gm = EkvDecodeGeom<D, NW>;
@@ -548,23 +560,24 @@ __global__ void __launch_bounds__(64 * NW, (NW >= 8 ? (REP == 1 ? (EKV_FUSED_TWO
 #undef EKV_HEAD_STATE
 
 template <int REP>
-hipError_t launch(const EkvAttnArgs& a EKV_TB_DECL EKV_SINK_ONLY(, const float* sinks) EKV_WIN_ONLY(, const EkvWinArgs& win), int layer_count, hipStream_t s) {
+hipError_t launch(const EkvAttnArgs& a EKV_TB_DECL EKV_SINK_ONLY(, const float* sinks) EKV_WIN_ONLY(, const EkvWinArgs& win) EKV_HEADS_ONLY(, const EkvHeadsArgs& heads), int layer_count, hipStream_t s) {
   using Gm = EkvDecodeGeom<EKV_D>;
   const size_t part = (size_t)Gm::NP * REP * Gm::PS * 4;
   const int rep_all = a.n_q_heads / a.n_kv_heads;
   const dim3 grid(a.n_split * ((rep_all + REP - 1) / REP), a.n_kv_heads, layer_count);
   if ((a.cap & 3) == 0 && a.cap >= 16) {
-    hipLaunchKernelGGL((ekv_attn_decode_kernel<EKV_D, REP, EKV_ROPE, false>), grid, dim3(256), part, s, a EKV_TB_PASS EKV_SINK_ONLY(, sinks) EKV_WIN_ONLY(, win));
+    hipLaunchKernelGGL((ekv_attn_decode_kernel<EKV_D, REP, EKV_ROPE, false>), grid, dim3(256), part, s, a EKV_TB_PASS EKV_SINK_ONLY(, sinks) EKV_WIN_ONLY(, win) EKV_HEADS_ONLY(, heads));
   } else {
     const size_t lds = ekv_align((size_t)a.rows_per_split * 4, 16) + part;
     if (lds > 48 * 1024)
       (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ekv_attn_decode_kernel<EKV_D, REP, EKV_ROPE, true>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL((ekv_attn_decode_kernel<EKV_D, REP, EKV_ROPE, true>), grid, dim3(256), lds, s, a EKV_TB_PASS EKV_SINK_ONLY(, sinks) EKV_WIN_ONLY(, win));
+    hipLaunchKernelGGL((ekv_attn_decode_kernel<EKV_D, REP, EKV_ROPE, true>), grid, dim3(256), lds, s, a EKV_TB_PASS EKV_SINK_ONLY(, sinks) EKV_WIN_ONLY(, win) EKV_HEADS_ONLY(, heads));
   }
   return hipGetLastError();
 }
 
+#if !EKV_HEADS      // (no one-launch heads build)
 template <int REP, int NW = 8>
 size_t fused_lds(int t_pad, int l_pad, int n_state) { return ekv_fused_lds<EKV_D, REP, NW>(t_pad, l_pad, n_state); }
 
@@ -609,9 +622,23 @@ hipError_t launch_fused(const EkvAttnArgs& a, const EkvScoreArgs& sc EKV_TB_DECL
   return nw == 8 ? launch_fused_nw<REP, 8>(a, sc EKV_TB_PASS EKV_SINK_ONLY(, sinks) EKV_WIN_ONLY(, win), layer_count, s) : launch_fused_nw<REP, 4>(a, sc EKV_TB_PASS EKV_SINK_ONLY(, sinks) EKV_WIN_ONLY(, win), layer_count, s);
 }
 
+#endif
+
 }  // namespace
 
-#if EKV_WINDOW
+#if EKV_HEADS
+// the heads instances: their launcher takes the table's pointer and growth where the others take the table of a batch (EKV_FN_HEADS:
+// element type, head_dim); GQA factors up to 8, one query-head group per KV head (the planner refuses wider ones)
+hipError_t EKV_FN_HEADS(ekv_launch_attn_decode, EKV_ELEM, EKV_D)(const EkvAttnArgs& a, const EkvHeadsArgs& hd, int rep, int layer_count, hipStream_t s) {
+  if (rep < 1 || rep > 8 || hd.rows == nullptr) return hipErrorInvalidValue;
+  switch (rep) {
+    case 1: return launch<1>(a, hd, layer_count, s);
+    case 2: return launch<2>(a, hd, layer_count, s);
+    case 3: case 4: return launch<4>(a, hd, layer_count, s);
+    default: return launch<8>(a, hd, layer_count, s);
+  }
+}
+#elif EKV_WINDOW
 // the window instances (EKV_FN_WIN; with sinks EKV_FN_SINK_WIN): one signature for both, `sinks` unused (NULL) in the window-alone ones
 #if EKV_SINK
 #define EKV_WSYM(fn) EKV_FN_SINK_WIN(fn, EKV_ELEM, EKV_D)

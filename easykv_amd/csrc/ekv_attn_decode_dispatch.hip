@@ -30,6 +30,11 @@ typedef hipError_t EkvWinFusedFn(const EkvAttnArgs&, const EkvScoreArgs&, const 
 #define EKV_DECODE_SINK_WIN(elem, d)                                  \
   EkvWinDecodeFn EKV_FN_SINK_WIN(ekv_launch_attn_decode, elem, d);    \
   EkvWinFusedFn EKV_FN_SINK_WIN(ekv_launch_decode_fused, elem, d);
+// (the heads instances: 16-bit rows, plain keys; their launchers take the table's pointer and growth)
+typedef hipError_t EkvHeadsDecodeFn(const EkvAttnArgs&, const EkvHeadsArgs&, int rep, int count, hipStream_t);
+typedef hipError_t EkvHeadsScoreFn(const EkvScoreArgs&, const EkvHeadsArgs&, int count, hipStream_t);
+#define EKV_DECODE_HEADS(elem, d) EkvHeadsDecodeFn EKV_FN_HEADS(ekv_launch_attn_decode, elem, d);
+#define EKV_DECODE_SCORE_HEADS(elem) EkvHeadsScoreFn EKV_FN_ELEM(ekv_launch_decode_score_heads, elem);
 #include "ekv_instances.def"
 EkvFoldFn ekv_launch_fold_f16, ekv_launch_fold_bf16;      // (exported by the `single` scorer instances: the fold reads no per-step field)
 
@@ -93,6 +98,23 @@ const WinInstance* win_instance(const EkvAttnArgs& a, const float* sinks, const 
     if (in.head_dim == head_dim && in.bf16 == bf16 && in.sink == (sinks != nullptr)) return &in;
   return nullptr;
 }
+struct HeadsInstance {
+  int head_dim;
+  bool bf16;
+  EkvHeadsDecodeFn* attn;
+};
+const HeadsInstance kHeadsDecode[] = {
+#define EKV_DECODE_HEADS(elem, d) {d, EKV_IS_##elem, EKV_FN_HEADS(ekv_launch_attn_decode, elem, d)},
+#include "ekv_instances.def"
+};
+struct HeadsScoreInstance {
+  bool bf16;
+  EkvHeadsScoreFn* score;
+};
+const HeadsScoreInstance kHeadsScore[] = {
+#define EKV_DECODE_SCORE_HEADS(elem) {EKV_IS_##elem, EKV_FN_ELEM(ekv_launch_decode_score_heads, elem)},
+#include "ekv_instances.def"
+};
 struct ScoreInstance {
   bool bf16, batch;
   EkvScoreFn* score;
@@ -163,6 +185,20 @@ hipError_t ekv_launch_decode_fused_sink(const EkvAttnArgs& a, const EkvScoreArgs
 hipError_t ekv_launch_decode_score_sink(const EkvScoreArgs& sc, const float* sinks, int count, hipStream_t s, bool bf16) {
   for (const SinkScoreInstance& in : kSinkScore)
     if (in.bf16 == bf16) return in.score(sc, sinks, count, s);
+  return hipErrorInvalidValue;
+}
+
+// ---- KV heads of different lengths (the ekv_heads_* calls): the split kernel and the split path's scorer — their own instances, never another's
+hipError_t ekv_launch_attn_decode_heads(const EkvAttnArgs& a, const EkvHeadsArgs& hd, int head_dim, int count, hipStream_t s, bool bf16) {
+  if (a.rope_cos != nullptr) return hipErrorInvalidValue;
+  for (const HeadsInstance& in : kHeadsDecode)
+    if (in.head_dim == head_dim && in.bf16 == bf16) return in.attn(a, hd, a.n_q_heads / a.n_kv_heads, count, s);
+  return hipErrorInvalidValue;
+}
+
+hipError_t ekv_launch_decode_score_heads(const EkvScoreArgs& sc, const EkvHeadsArgs& hd, int count, hipStream_t s, bool bf16) {
+  for (const HeadsScoreInstance& in : kHeadsScore)
+    if (in.bf16 == bf16) return in.score(sc, hd, count, s);
   return hipErrorInvalidValue;
 }
 

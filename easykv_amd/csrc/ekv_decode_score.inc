@@ -18,6 +18,16 @@
 #if EKV_SINK && EKV_BATCH
 #error "sink scorer instances: one sequence"
 #endif
+// EKV_HEADS = 1 (the EKV_DECODE_SCORE_HEADS lines of the manifest): the scorer of a decode step over KV heads of different lengths —
+// workgroup (head, layer) takes its head's row count from the device table (ekv_kernels.h) and is the uniform scorer from there on.  The
+// fold kernel is the uniform one.
+#ifndef EKV_HEADS
+#define EKV_HEADS 0
+#endif
+#if EKV_HEADS && (EKV_SINK || EKV_BATCH)
+#error "heads scorer instances: no batch table, no sinks"
+#endif
+#define EKV_HEAD_IDX blockIdx.x
 #define ekv_decode_score_kernel EKV_KERNEL_NAME(ekv_decode_score_kernel)
 #define ekv_fold_kernel EKV_KERNEL_NAME(ekv_fold_kernel)
 
@@ -25,7 +35,7 @@ namespace {
 
 // (kSNW waves / kSNT threads per scorer workgroup and the LDS plan ekv_decode_score_lds: ekv_geometry.h)
 template <int REP, int ITEMS>
-__global__ void __launch_bounds__(kSNT) ekv_decode_score_kernel(const EkvScoreArgs EKV_ARG_SC EKV_TB_PARAM EKV_SINK_ONLY(, const float* const sinks)) {
+__global__ void __launch_bounds__(kSNT) ekv_decode_score_kernel(const EkvScoreArgs EKV_ARG_SC EKV_TB_PARAM EKV_SINK_ONLY(, const float* const sinks) EKV_HEADS_ONLY(, const EkvHeadsArgs heads)) {
   EKV_SHADOW_SC(blockIdx.y)
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int h = blockIdx.x, ll = blockIdx.y, tid = threadIdx.x;
@@ -80,7 +90,7 @@ __global__ void __launch_bounds__(kSNT) ekv_decode_score_kernel(const EkvScoreAr
                                     EKV_SINK_ONLY(, sinks + (size_t)(sc.layer_begin + ll) * sc.n_q_heads + (size_t)h * nrep));
 }
 
-#if !EKV_BATCH && !EKV_SINK
+#if !EKV_BATCH && !EKV_SINK && !EKV_HEADS
 // Partials of the key-range splits -> 16-bit attention output, nothing else (rows = q_len * n_q_heads per layer).
 __global__ void __launch_bounds__(128) ekv_fold_kernel(const EkvScoreArgs sc) {
   const int D = sc.head_dim, PS = D + 2;
@@ -94,42 +104,46 @@ __global__ void __launch_bounds__(128) ekv_fold_kernel(const EkvScoreArgs sc) {
 #endif
 
 template <int REP, int ITEMS>
-hipError_t launch_k(const EkvScoreArgs& sc EKV_TB_DECL EKV_SINK_ONLY(, const float* sinks), int layer_count, hipStream_t s) {
+hipError_t launch_k(const EkvScoreArgs& sc EKV_TB_DECL EKV_SINK_ONLY(, const float* sinks) EKV_HEADS_ONLY(, const EkvHeadsArgs& heads), int layer_count, hipStream_t s) {
   const size_t lds = ekv_decode_score_lds(REP, sc.t_pad, sc.policy);
   if (lds > 48 * 1024)
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ekv_decode_score_kernel<REP, ITEMS>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL((ekv_decode_score_kernel<REP, ITEMS>), dim3(sc.n_kv_heads, layer_count), dim3(kSNT), lds, s, sc EKV_TB_PASS EKV_SINK_ONLY(, sinks));
+  hipLaunchKernelGGL((ekv_decode_score_kernel<REP, ITEMS>), dim3(sc.n_kv_heads, layer_count), dim3(kSNT), lds, s, sc EKV_TB_PASS EKV_SINK_ONLY(, sinks) EKV_HEADS_ONLY(, heads));
   return hipGetLastError();
 }
 
 template <int REP>
-hipError_t launch_rep(const EkvScoreArgs& sc EKV_TB_DECL EKV_SINK_ONLY(, const float* sinks), int layer_count, hipStream_t s) {
+hipError_t launch_rep(const EkvScoreArgs& sc EKV_TB_DECL EKV_SINK_ONLY(, const float* sinks) EKV_HEADS_ONLY(, const EkvHeadsArgs& heads), int layer_count, hipStream_t s) {
   // ITEMS = ceil(row width / threads) (a floor here sent T = 2049 to the 6144-wide build: 12 items per thread instead of 5)
   constexpr int I0 = (2304 + kSNT - 1) / kSNT, I1 = (6144 + kSNT - 1) / kSNT;
-  return sc.n_slots <= kSNT * I0 ? launch_k<REP, I0>(sc EKV_TB_PASS EKV_SINK_ONLY(, sinks), layer_count, s) : launch_k<REP, I1>(sc EKV_TB_PASS EKV_SINK_ONLY(, sinks), layer_count, s);
+  return sc.n_slots <= kSNT * I0 ? launch_k<REP, I0>(sc EKV_TB_PASS EKV_SINK_ONLY(, sinks) EKV_HEADS_ONLY(, heads), layer_count, s) : launch_k<REP, I1>(sc EKV_TB_PASS EKV_SINK_ONLY(, sinks) EKV_HEADS_ONLY(, heads), layer_count, s);
 }
 
-#if !EKV_BATCH && !EKV_SINK
+#if !EKV_BATCH && !EKV_SINK && !EKV_HEADS
 hipError_t launch_fold(const EkvScoreArgs& sc, int layer_count, hipStream_t s) {
   hipLaunchKernelGGL(ekv_fold_kernel, dim3(sc.n_q_heads * sc.q_len, layer_count), dim3(128), 0, s, sc);
   return hipGetLastError();
 }
 #endif
 
-hipError_t launch_score(const EkvScoreArgs& sc EKV_TB_DECL EKV_SINK_ONLY(, const float* sinks), int layer_count, hipStream_t s) {
+hipError_t launch_score(const EkvScoreArgs& sc EKV_TB_DECL EKV_SINK_ONLY(, const float* sinks) EKV_HEADS_ONLY(, const EkvHeadsArgs& heads), int layer_count, hipStream_t s) {
   switch (sc.n_q_heads / sc.n_kv_heads) {
-    case 1: return launch_rep<1>(sc EKV_TB_PASS EKV_SINK_ONLY(, sinks), layer_count, s);
-    case 2: return launch_rep<2>(sc EKV_TB_PASS EKV_SINK_ONLY(, sinks), layer_count, s);
-    case 3: case 4: return launch_rep<4>(sc EKV_TB_PASS EKV_SINK_ONLY(, sinks), layer_count, s);
-    case 5: case 6: case 7: case 8: return launch_rep<8>(sc EKV_TB_PASS EKV_SINK_ONLY(, sinks), layer_count, s);
+    case 1: return launch_rep<1>(sc EKV_TB_PASS EKV_SINK_ONLY(, sinks) EKV_HEADS_ONLY(, heads), layer_count, s);
+    case 2: return launch_rep<2>(sc EKV_TB_PASS EKV_SINK_ONLY(, sinks) EKV_HEADS_ONLY(, heads), layer_count, s);
+    case 3: case 4: return launch_rep<4>(sc EKV_TB_PASS EKV_SINK_ONLY(, sinks) EKV_HEADS_ONLY(, heads), layer_count, s);
+    case 5: case 6: case 7: case 8: return launch_rep<8>(sc EKV_TB_PASS EKV_SINK_ONLY(, sinks) EKV_HEADS_ONLY(, heads), layer_count, s);
     default: return hipErrorInvalidValue;
   }
 }
 
 }  // namespace
 
-#if EKV_SINK
+#if EKV_HEADS
+hipError_t EKV_FN_ELEM(ekv_launch_decode_score_heads, EKV_ELEM)(const EkvScoreArgs& sc, const EkvHeadsArgs& hd, int count, hipStream_t s) {
+  return hd.rows != nullptr ? launch_score(sc, hd, count, s) : hipErrorInvalidValue;
+}
+#elif EKV_SINK
 hipError_t EKV_FN_ELEM(ekv_launch_decode_score_sink, EKV_ELEM)(const EkvScoreArgs& sc, const float* sinks, int count, hipStream_t s) {
   return sinks != nullptr ? launch_score(sc, sinks, count, s) : hipErrorInvalidValue;
 }
@@ -140,6 +154,6 @@ hipError_t EKV_FN_DECODE_SCORE(ekv_launch_decode_score, EKV_ELEM, EKV_BATCHING)(
 }
 #endif
 
-#if !EKV_BATCH && !EKV_SINK
+#if !EKV_BATCH && !EKV_SINK && !EKV_HEADS
 hipError_t EKV_FN_ELEM(ekv_launch_fold, EKV_ELEM)(const EkvScoreArgs& sc, int layer_count, hipStream_t s) { return launch_fold(sc, layer_count, s); }
 #endif

@@ -90,6 +90,7 @@ struct EkvStepPlan {
   // [layer_count][H][t_pad] uint8 (0 forced, 1 free, 2 neither), behind everything the pooled layout holds (-1 = not in the layout)
   int32_t adaptive;
   int64_t ada_keys, ada_cls;
+  int32_t heads;        // an ekv_heads_* call: the plan of the envelope; EKV_RUN_DECODE / EKV_RUN_DECODE_SCORE run the EKV_HEADS instances
 };
 // The table of a batched decode step as the kernels' batch instances receive it: BY VALUE, behind the argument structs of the uniform
 // kernel (2304 bytes of the 4 KB a launch may carry).  Workgroup (head, entry ll) shadows the per-step fields of its argument structs
@@ -292,6 +293,29 @@ __device__ __forceinline__ EkvScoreArgs ekv_batch_score_args(const EkvScoreArgs&
   sc.range_start = e.range_start;
   return sc;
 }
+// What the heads instances (EKV_HEADS = 1, below) receive as their last argument: the device table of ekv_heads and its growth.
+struct EkvHeadsArgs {
+  const int32_t* rows;      // device int32 [bank->n_layers][n_kv_heads]
+  int32_t grow;
+};
+// What workgroup (head h, layer z) of a heads instance does first: T = rows[layer][h] + grow + 1 replaces the envelope's n_slots.  Every
+// other field, the pitches among them (t_pad, l_pad, n_split, rows_per_split), stays the envelope's; everything a kernel derives from
+// n_slots it derives from its own copy.
+__device__ __forceinline__ EkvAttnArgs ekv_heads_attn_args(const EkvAttnArgs& env, const EkvHeadsArgs& hd, int h, int z) {
+  EkvAttnArgs a = env;
+  a.n_slots = hd.rows[(size_t)(env.layer_begin + z) * env.n_kv_heads + h] + hd.grow + 1;
+  return a;
+}
+__device__ __forceinline__ EkvScoreArgs ekv_heads_score_args(const EkvScoreArgs& env, const EkvHeadsArgs& hd, int h, int z) {
+  EkvScoreArgs sc = env;
+  sc.n_slots = hd.rows[(size_t)(env.layer_begin + z) * env.n_kv_heads + h] + hd.grow + 1;
+  return sc;
+}
+#if defined(EKV_HEADS) && EKV_HEADS
+#define EKV_HEADS_ONLY(...) __VA_ARGS__
+#else
+#define EKV_HEADS_ONLY(...)
+#endif
 // How a kernel source spells its batch instance (EKV_BATCH = 1, set for the batch lines of ekv_instances.def before anything is
 // included; off, the macros vanish and the source is the uniform kernel's, token for token): the argument structs arrive under the
 // names a_env / sc_env with the table behind them, and EKV_SHADOW_* declares `a` / `sc` as this workgroup's own copies.
@@ -308,6 +332,24 @@ __device__ __forceinline__ EkvScoreArgs ekv_batch_score_args(const EkvScoreArgs&
 #define EKV_ARRIVE_ROW(ll) (a.layer_begin + (ll))      // the arrival counters are the bank's: indexed by the entry's layer
 #define EKV_SHADOW_A(z) const EkvAttnArgs a = ekv_batch_attn_args(a_env, tb.e[z], (int)(z));
 #define EKV_SHADOW_SC(z) const EkvScoreArgs sc = ekv_batch_score_args(sc_env, tb.e[z], (int)(z));
+#elif defined(EKV_HEADS) && EKV_HEADS
+// The third spelling (EKV_HEADS = 1, the EKV_*_HEADS lines of the manifest): decode steps over KV heads of different lengths
+// (include/easykv_hip.h, ekv_heads).  Nothing travels by value but a pointer and a word: EkvHeadsArgs is the LAST kernel argument, spelled
+// through EKV_HEADS_ONLY like the sinks and the window struct, and workgroup (head, layer z) shadows n_slots of its argument structs with
+// rows[layer_begin + z][head] + grow + 1 (one scalar load) before anything else.  The grid is the uniform kernel's, the layers are the
+// call's own (no one-head view), the arrival counters are indexed as in the uniform kernel.  A source names its head index, EKV_HEAD_IDX,
+// before its kernels (blockIdx.y in the attention kernel, blockIdx.x in the scorer).
+#define EKV_BATCHING heads
+#define EKV_BATCH_TAG _heads
+#define EKV_ARG_A a_env
+#define EKV_ARG_SC sc_env
+#define EKV_TB_PARAM
+#define EKV_TB_DECL
+#define EKV_TB_PASS
+#define EKV_TB_DEREF
+#define EKV_ARRIVE_ROW(ll) (ll)
+#define EKV_SHADOW_A(z) const EkvAttnArgs a = ekv_heads_attn_args(a_env, heads, (int)(EKV_HEAD_IDX), (int)(z));
+#define EKV_SHADOW_SC(z) const EkvScoreArgs sc = ekv_heads_score_args(sc_env, heads, (int)(EKV_HEAD_IDX), (int)(z));
 #else
 #define EKV_BATCHING single
 #define EKV_BATCH_TAG
@@ -388,6 +430,8 @@ __device__ __forceinline__ EkvScoreArgs ekv_batch_score_args(const EkvScoreArgs&
 #define EKV_FN_SINK(fn, elem, d) EKV_FN_SINK_(fn, elem, d)      // (EKV_DECODE_SINK; EKV_DECODE_SCORE_SINK names no head_dim)
 #define EKV_FN_WIN_(fn, elem, d) fn##_win_d##d##_##elem
 #define EKV_FN_WIN(fn, elem, d) EKV_FN_WIN_(fn, elem, d)      // (EKV_DECODE_WIN)
+#define EKV_FN_HEADS_(fn, elem, d) fn##_heads_d##d##_##elem
+#define EKV_FN_HEADS(fn, elem, d) EKV_FN_HEADS_(fn, elem, d)      // (EKV_DECODE_HEADS; EKV_DECODE_SCORE_HEADS names no head_dim)
 #define EKV_FN_SINK_WIN_(fn, elem, d) fn##_sink_win_d##d##_##elem
 #define EKV_FN_SINK_WIN(fn, elem, d) EKV_FN_SINK_WIN_(fn, elem, d)      // (EKV_DECODE_SINK_WIN)
 #define EKV_FN_CHUNK_WIN_(d, m, elem) ekv_launch_attn_chunk_win_d##d##_m##m##_##elem
@@ -443,6 +487,10 @@ hipError_t ekv_launch_kv164_quantize(const ekv_bank* bank, const ekv_kv164* q164
 hipError_t ekv_launch_kv164_dequantize(const ekv_bank* bank, const ekv_kv164* q164, int out_kind, int layer_begin, int layer_count, int extent,
                                        void* v_out, hipStream_t s);
 hipError_t ekv_launch_decode_score(const EkvScoreArgs& sc, const EkvSeqTable* tb, int count, hipStream_t s, bool bf16);
+// Heads (the ekv_heads_* calls; EKV_HEADS instances): the split decode kernel with its in-kernel fold, and the scorer behind it.  `a` / `sc`
+// are the envelope's arguments of a uniform step of `count` layers.  16-bit rows, plain keys, every head_dim of the decode kernels.
+hipError_t ekv_launch_attn_decode_heads(const EkvAttnArgs& a, const EkvHeadsArgs& hd, int head_dim, int count, hipStream_t s, bool bf16);
+hipError_t ekv_launch_decode_score_heads(const EkvScoreArgs& sc, const EkvHeadsArgs& hd, int count, hipStream_t s, bool bf16);
 hipError_t ekv_launch_fold(const EkvScoreArgs& sc, int layer_count, hipStream_t s, bool bf16);
 
 // Small-row chunk step with the logits in LDS (ekv_chunk_lds.inc): whole step in one launch, K and V read once.

@@ -834,6 +834,26 @@ static void plan_ada_layout(const ekv_bank* bank, const ekv_step* st, EkvStepPla
   P->bytes = off;
 }
 
+// The envelope of a heads call (include/easykv_hip.h, ekv_heads): the largest and the smallest T = rows_host[l][h] + grow + 1 over the
+// layers the call's pitches must serve — its own, or all deferred ones.  Reads the host copy alone.  EKV_E_ARG for anything the table
+// cannot be read with (a bank or layers out of range) or holds out of range.
+static int ekv_heads_envelope(const ekv_bank* bank, const ekv_step* st, const ekv_heads* hd, int32_t* t_max, int32_t* t_min) {
+  if (!hd || !hd->rows || !hd->rows_host || hd->grow < 0 || !bank || !st) return EKV_E_ARG;
+  if (bank->n_layers <= 0 || bank->n_kv_heads <= 0 || bank->cap <= 0) return EKV_E_ARG;
+  i64 l0 = st->layer_begin, lc = st->layer_count;
+  if (st->defer_layers > 0) l0 = (i64)st->layer_begin - st->defer_index, lc = st->defer_layers;
+  if (l0 < 0 || lc < 1 || l0 + lc > bank->n_layers) return EKV_E_ARG;
+  i64 hi = 0, lo = (i64)1 << 40;
+  for (i64 i = l0 * bank->n_kv_heads; i < (l0 + lc) * bank->n_kv_heads; ++i) {
+    const i64 rows = hd->rows_host[i];
+    if (rows < 1) return EKV_E_ARG;
+    hi = std::max(hi, rows), lo = std::min(lo, rows);
+  }
+  if (hi + hd->grow + 1 > bank->cap) return EKV_E_ARG;
+  *t_max = (int32_t)(hi + hd->grow + 1), *t_min = (int32_t)(lo + hd->grow + 1);
+  return EKV_OK;
+}
+
 int resolve_call(const EkvCall& c, EkvResolved* r) {
   EkvStepPlan* P = &r->plan;
   *P = EkvStepPlan{};
@@ -937,11 +957,30 @@ int resolve_call(const EkvCall& c, EkvResolved* r) {
   // bytes (plan_ada_layout).  Refused on top of the pooled refusals (EKV_E_UNSUPPORTED, zero launches, zero bytes): more than 64 KV heads
   // (the allot kernel keeps one counter pair per head in LDS).
   if (c.adaptive && !ekv_ada_ok(c.ada, c.step)) return EKV_E_ARG;
-  const int variants = (c.long_rows ? 1 : 0) + (c.capped ? 1 : 0) + (c.sink || c.window ? 1 : 0) + (c.pooled ? 1 : 0) + (c.adaptive ? 1 : 0);
+  // Heads calls (ekv_heads_*; include/easykv_hip.h, "heads"), likewise stated once.  "Heads" is one more independent variant of a call,
+  // combined with nothing else.  A NULL struct or pointer, grow < 0, a host count < 1, a resulting T > cap and layers the table cannot be
+  // read for are argument errors, behind the element type and before anything is planned; only the HOST copy of the table is read.  The
+  // ONE rule: a heads call plans as the plain call of its ENVELOPE — the caller's step with n_slots = the largest T of the host table
+  // over the call's layers, or over all deferred layers, so that the layer calls and the flush agree on every pitch — field for field,
+  // run on instances without the phase order K; the whole-step form plans as phases = 1 | 2 of that step, because the family has no
+  // one-launch build.  EKV_RUN_DECODE and EKV_RUN_DECODE_SCORE run the EKV_HEADS instances; the fold launch is the uniform one (it reads
+  // no per-step field).  Refused with zero launches and zero bytes (EKV_E_UNSUPPORTED): q_len > 1, RoPE-on-read, slot-indexed score rows,
+  // tova_head_mean, more than one victim, a GQA factor > 8, and a plan with any other launch (the generic scorer, the range compaction).
+  int32_t heads_t_min = 0;
+  if (c.heads) {
+    int32_t t_max = 0;
+    if (int e = ekv_heads_envelope(bank, c.step, c.hd, &t_max, &heads_t_min)) return e;
+    r->env = *c.step;
+    r->env.n_slots = t_max;
+    if ((r->env.phases & ~(EKV_PHASE_SLOT_ROWS | EKV_PHASE_SLOT_TAIL_OK)) == 0) r->env.phases |= 1 | 2;
+    r->step = &r->env;
+  }
+  const int variants = (c.long_rows ? 1 : 0) + (c.capped ? 1 : 0) + (c.sink || c.window ? 1 : 0) + (c.pooled ? 1 : 0) + (c.adaptive ? 1 : 0) + (c.heads ? 1 : 0);
   const bool sinkish = c.sink || c.window;
   const int rc = (variants && (quant || c.batch || variants > 1))
                      ? EKV_E_UNSUPPORTED
-                     : ekv_plan_step(bank, r->step, P, c.long_rows, c.capped || sinkish, quant || c.batch || sinkish || c.capped, c.pooled || c.adaptive);
+                     : ekv_plan_step(bank, r->step, P, c.long_rows, c.capped || sinkish, quant || c.batch || sinkish || c.capped || c.heads, c.pooled || c.adaptive);
+  P->heads = c.heads ? 1 : 0;
   P->capped = c.capped ? 1 : 0;
   P->sink = c.sink ? 1 : 0;
   P->window = c.window ? 1 : 0;
@@ -960,7 +999,7 @@ int resolve_call(const EkvCall& c, EkvResolved* r) {
       P->bytes = plain.bytes, P->big_rows = plain.big_rows, P->key_rows = -1;
     }
     P->one_launch = P->n_launches = P->n_list = P->long_rows = P->long_tiles = 0;
-    if (c.batch || c.capped || sinkish || c.pooled || c.adaptive) P->bytes = 0;      // (nothing will run: ekv_batch_workspace_bytes of a refused table, ekv_cap_ / ekv_sink_ / ekv_pool_workspace_bytes of a refused step, is 0)
+    if (c.batch || c.capped || sinkish || c.pooled || c.adaptive || c.heads) P->bytes = 0;      // (nothing will run: ekv_batch_workspace_bytes of a refused table, ekv_cap_ / ekv_sink_ / ekv_pool_workspace_bytes of a refused step, is 0)
     return code;
   };
   const ekv_step* st = c.step;
@@ -979,6 +1018,20 @@ int resolve_call(const EkvCall& c, EkvResolved* r) {
   if (c.adaptive) {
     if (bank->n_kv_heads > 64) return refuse(EKV_E_UNSUPPORTED);
     plan_ada_layout(bank, st, P);
+  }
+  if (c.heads) {
+    const int rep = bank->n_q_heads / bank->n_kv_heads;
+    if (st->q_len != 1 || st->rope_on_read || (st->phases & EKV_PHASE_SLOT_ROWS) || st->tova_head_mean || st->n_evict > 1 || rep > 8) return refuse(EKV_E_UNSUPPORTED);
+    // the shortest head: every argument check of the uniform step that reads T is monotone in it (T < q_len, n_evict >= T, score_off >= T,
+    // a candidate range narrower than n_evict), and the envelope has passed them for the longest
+    ekv_step one = *r->step;
+    one.n_slots = heads_t_min, one.n_split = P->n_split;
+    EkvStepPlan P1;
+    if (ekv_plan_step(bank, &one, &P1) == EKV_E_ARG) return refuse(EKV_E_ARG);
+    for (int i = 0; i < P->n_list; ++i) {
+      const int kind = P->list[i].kind;
+      if (kind != EKV_RUN_DECODE && kind != EKV_RUN_FOLD && kind != EKV_RUN_DECODE_SCORE) return refuse(EKV_E_UNSUPPORTED);
+    }
   }
   if (quant && (st->q_len != 1 || st->rope_on_read || !ekv_rows_head_dim(c.rows, bank->head_dim) ||
                 bank->n_q_heads / bank->n_kv_heads > kRowsRules[c.rows].max_rep))
@@ -1024,6 +1077,10 @@ int call_info(const EkvCall& c, int32_t* info, int32_t n_info) {
   if (c.window && !ekv_win_ok(c.win, r.bank)) return EKV_E_ARG;
   if (c.pooled && !(c.pool != nullptr && c.pool->radius >= 1 && (c.pool->op == EKV_POOL_MAX || c.pool->op == EKV_POOL_AVG))) return EKV_E_ARG;
   if (c.adaptive && !ekv_ada_ok(c.ada, c.step)) return EKV_E_ARG;
+  if (c.heads) {
+    int32_t t_max, t_min;
+    if (int e = ekv_heads_envelope(r.bank, c.step, c.hd, &t_max, &t_min)) return e;
+  }
   if (c.rows != EKV_ROWS_kv16 && !r.bank) return EKV_E_ARG;
   if (int e = check_bank(r.bank)) return e;
   if (!c.step || (c.batch && !c.seqs) || !info || n_info < 1) return EKV_E_ARG;

@@ -94,6 +94,8 @@ struct EkvCall {
   const ekv_pool* pool;    // ... its struct: NULL, radius < 1 or an unknown op are argument errors
   bool adaptive;           // an ekv_ada_* call: adaptive head budgets (16-bit rows, one sequence, h2o_head / tova, no other variant)
   const ekv_ada* ada;      // ... its struct: NULL, NULL n_evict_out, radius < 0, an unknown op or bounds out of order are argument errors
+  bool heads;              // an ekv_heads_* call: decode steps over KV heads of different lengths (16-bit rows, plain keys, no other variant)
+  const ekv_heads* hd;     // ... its struct: NULL, a NULL pointer, grow < 0 or a host count out of range are argument errors; `rows` is never dereferenced here
 };
 inline EkvCall step_call(const ekv_bank* bank, const ekv_step* st, int32_t dtype) { return {bank, st, dtype, EKV_ROWS_kv16, {}, false, nullptr, 0}; }
 inline EkvCall batch_call(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_seq* seqs, int32_t n_seq) {
@@ -115,6 +117,9 @@ inline EkvCall pool_call(const ekv_bank* bank, const ekv_step* st, int32_t dtype
 }
 inline EkvCall ada_call(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_ada* ada) {
   return {bank, st, dtype, EKV_ROWS_kv16, {}, false, nullptr, 0, false, false, 0.f, false, nullptr, false, nullptr, false, nullptr, true, ada};
+}
+inline EkvCall heads_call(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_heads* hd) {
+  return {bank, st, dtype, EKV_ROWS_kv16, {}, false, nullptr, 0, false, false, 0.f, false, nullptr, false, nullptr, false, nullptr, false, nullptr, true, hd};
 }
 // the quantised calls: the same two with a row format and its planes
 inline EkvCall kv8_call(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_kv8* q8) {
@@ -153,7 +158,7 @@ bool ekv_rows_head_dim(EkvRows rows, int head_dim);
 // Everything a call needs, resolved once (resolve_call): check, info, workspace bytes and attend all read it.
 struct EkvResolved {
   const ekv_bank* bank;      // the bank planned and launched with; NULL: a quantised call without its planes
-  const ekv_step* step;      // the step actually planned: the caller's, or the envelope of a batch
+  const ekv_step* step;      // the step actually planned: the caller's, or the envelope of a batch or of a heads call
   const EkvSeqTable* tb;     // the table the batch instances receive; NULL for a uniform step
   EkvStepPlan plan;          // rows / batch / fused_order final; zero launches (a batch: zero bytes too) when the call is refused
   ekv_bank bank_q;           // storage of the above, where the call needs its own

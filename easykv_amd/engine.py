@@ -313,6 +313,8 @@ class KVBank:
         self._ada_out = None    # device int32 [n_layers][H]: the victim count of every head after an adaptive step
         self._view = None       # the bank as n_layers * H one-head layers, for decode steps over heads of different lengths (_attend_ragged)
         self.head_slots = None  # [n_layers][H] ints after an adaptive step (None: every head of a layer holds n_slots rows)
+        self._heads = None      # device table, host copy and struct of the heads family (ekv_heads_*: deferred decode steps over heads of different lengths)
+        self.head_table_uploads = 0      # times the device table of the heads family was written (lengths changed other than by uniform growth)
         self.arrive = torch.zeros(n_layers, n_kv_heads, dtype=torch.int32, device=dev)     # arrival counters of the in-kernel fold
         self._bank = Bank(_ptr(self.k), _ptr(self.v), self._slot_of_pos.data_ptr(),
                           self._score_sum.data_ptr() if scored else None, self._score_sq.data_ptr() if scored else None,
@@ -737,6 +739,117 @@ class KVBank:
             self._tokens[l] += 1
         return out, (evict_ids if want_ids else None)
 
+    # -- deferred decode steps over heads of different lengths: the heads family (ekv_heads_*, include/easykv_hip.h) ------------------
+    def _heads_sync(self):
+        """Make the device table of the heads family describe the bank's lengths now; returns (uploads, grow), the table's version.  The
+        table ``[n_layers][H]`` (a layer whose heads are alike counts with ``n_slots``) is written when the lengths are not what the last
+        step left: after an adaptive step, after a hand-over (a new bank), or when the layers' growths differ.  Uniform growth — every head
+        of every layer longer by the same count — only advances ``grow``; unchanged lengths (evicting steps) touch nothing."""
+        H = self.n_kv_heads
+        hs = self.head_slots
+        cur = [x for l in range(self.n_layers) for x in (hs[l] if hs[l] is not None else [self.n_slots[l]] * H)]
+        h = self._heads
+        if h is None:
+            n = self.n_layers * H
+            h = self._heads = dict(dev=torch.zeros(self.n_layers, H, dtype=torch.int32, device=self.device), host=(C.c_int32 * n)(), base=None, expect=None,
+                                   fam=tuple(getattr(self.lib, _lib.HEADS_CALLS[what]) for what in _lib.STEP_CALLS))
+            h["desc"] = _lib.Heads(h["dev"].data_ptr(), C.addressof(h["host"]), 0)
+            h["ref"] = C.byref(h["desc"])
+        if h["expect"] != cur:
+            base = h["base"]
+            g = cur[0] - base[0] if base is not None else -1
+            if g >= 0 and all(c - b == g for c, b in zip(cur, base)):
+                h["desc"].grow = g
+            else:
+                h["host"][:] = cur
+                h["dev"].copy_(torch.tensor(cur, dtype=torch.int32).view(self.n_layers, H))
+                h["base"], h["desc"].grow = cur, 0
+                self.head_table_uploads += 1
+            h["expect"] = cur
+        return self.head_table_uploads, h["desc"].grow
+
+    def _heads_plain(self, plan, n):
+        """The steps the heads family takes: what _attend_ragged takes — a plain decode plan on plain keys.  Anything else on ragged layers
+        keeps raising."""
+        if not (n == 1 and plan.phase == "decode" and plan.head_adaptive is None and plan.pool == 1 and not plan.streaming):
+            self._refuse_ragged(0, self.n_layers)
+
+    def _heads_step(self, plan, d):
+        """Open a token step of the heads family: everything that is the same for all its layers, resolved once per token step (as
+        _attend_deferred does for the uniform form: the step struct, the flush's check, the workspace and a fresh ``ids`` tensor are made
+        anew every token).  The flush's shape is validated before the first layer's attention appends a row."""
+        if any(self._slot_rows):
+            self._ensure_ordered()
+        if any(ev is not None for ev in self._score_done):
+            self.join()
+        version = self._heads_sync()
+        h = self._heads
+        st = self.make_step(plan, 1, 0, 1)      # (n_slots is ignored by the family: the table has every head's)
+        head = (C.byref(self._bank), C.byref(st), self._dt, h["ref"])
+        st.defer_layers = self.n_layers
+        if plan.n_split <= 0:      # the split count of a one-layer launch of the envelope (the layer of the longest head), fixed for both halves of the step
+            st.phases, st.n_split, st.defer_layers = 1, 0, 0
+            st.layer_begin = h["expect"].index(max(h["expect"])) // self.n_kv_heads
+            info = (C.c_int32 * 10)()
+            check(h["fam"][1](*head, info, 10), "ekv_heads_step_info")
+            st.n_split, st.defer_layers = int(info[0]), self.n_layers
+        st.layer_begin, st.layer_count, st.defer_index, st.phases = 0, self.n_layers, 0, 8
+        st.phys_extent = 0
+        check(h["fam"][0](*head), "ekv_heads_step_check (deferred scorer)")
+        ws = self._workspace(h["fam"][2](*head))
+        ids = torch.empty(self.n_layers, self.n_kv_heads, 1, dtype=torch.int32, device=self.device) if st.n_evict > 0 else None
+        d = self._defer = dict(plan=plan, t=-2, n=1, st=st, ws=ws, ids=ids, pending=0, heads=version, ws_ptr=ws.data_ptr(), ws_len=ws.numel(),
+                               stream=self._stream(), call=h["fam"][3], head=head)
+        return d
+
+    def _attend_heads(self, plan: StepPlan, q, k_new, v_new, layer, out):
+        """Deferred step of ONE layer of a bank whose heads hold different numbers of rows: attention + in-kernel fold of this layer now, by
+        the heads family's split kernel on the layer's own (KV head) grid — every workgroup reads its head's row count from the device
+        table — and ONE scorer launch over all layers and heads at :meth:`flush`, exactly like a uniform bank's deferred step."""
+        self._heads_plain(plan, q.shape[2])
+        d = self._defer
+        if d is not None and d["pending"] and (d.get("heads") is None or d["plan"] is not plan or d["pending"] >= self.n_layers):
+            raise _lib.EkvError("attend(defer=True): the previous step was not flushed")
+        if d is None or d["pending"] == 0:
+            d = self._heads_step(plan, d)
+        st = d["st"]
+        st.layer_begin = st.defer_index = layer
+        st.layer_count, st.phases = 1, 5
+        lens = self.head_slots[layer]
+        t = (max(lens) if lens is not None else self.n_slots[layer]) + 1
+        ext = self.extent[layer]
+        st.phys_extent = ext if ext > t else t
+        if out is None:
+            out = torch.empty(1, self.n_q_heads, 1, self.head_dim, dtype=self.dtype, device=self.device)
+        q, k_new, v_new = _stride_rows(st, q, k_new, v_new, out, self.dtype)
+        rc = d["call"](*d["head"], q.data_ptr(), k_new.data_ptr(), v_new.data_ptr(), out.data_ptr(), None, d["ws_ptr"], d["ws_len"], d["stream"])
+        if rc != 0:
+            check(rc, "ekv_heads_step_attend")
+        self.extent[layer] = st.phys_extent
+        self._tokens[layer] += 1
+        d["pending"] += 1
+        return out
+
+    def _flush_heads(self, d):
+        """The flush of a heads token step: the one scorer call over all layers; ``[L][H][1]`` ids (or None); lengths, extents and the
+        table's expectation advance as _attend_ragged advances them per layer."""
+        st, ws, H = d["st"], d["ws"], self.n_kv_heads
+        st.layer_begin, st.layer_count, st.defer_index, st.phases = 0, self.n_layers, 0, 8
+        st.q_token_stride = st.q_head_stride = st.kv_token_stride = st.kv_head_stride = st.out_token_stride = st.out_head_stride = 0
+        st.phys_extent = 0
+        p = ws.data_ptr()
+        check(d["call"](*d["head"], p, p, p, p, _ptr(d["ids"]), p, ws.numel(), d["stream"]), "ekv_heads_step_attend")
+        for l in range(self.n_layers):
+            lens = self.head_slots[l] if self.head_slots[l] is not None else [self.n_slots[l]] * H
+            self.head_slots[l] = [t + 1 - st.n_evict for t in lens]
+            self.n_slots[l] = max(self.head_slots[l])
+        h = self._heads
+        if st.n_evict == 0:      # every head grew by one row: the table stands, its growth advances
+            h["desc"].grow += 1
+            h["expect"] = [x + 1 for x in h["expect"]]
+        d["pending"] = 0
+        return d["ids"] if st.n_evict > 0 else None
+
     def _step_check(self, st, fam=None):
         fam = fam or self._family()
         return fam[0](C.byref(self._bank), C.byref(st), self._dt, *fam[4])
@@ -770,6 +883,8 @@ class KVBank:
         check(self.lib.ekv_bank_reset(C.byref(self._bank), self._stream()), "ekv_bank_reset")
         self.n_slots = [0] * self.n_layers
         self.head_slots = None
+        if self._heads is not None:
+            self._heads["base"] = self._heads["expect"] = None      # (the next ragged step writes the table anew)
         self.extent = [0] * self.n_layers
         self._slot_rows = [False] * self.n_layers
         self._slot_min_tail = [1 << 30] * self.n_layers
@@ -1117,6 +1232,8 @@ class KVBank:
             return None
         if d["pending"] != self.n_layers:
             raise _lib.EkvError(f"flush(): {d['pending']} of {self.n_layers} layers attended in this token step")
+        if d.get("heads") is not None:
+            return self._flush_heads(d)
         st, ws = d["st"], d["ws"]
         st.layer_begin, st.layer_count, st.defer_index, st.phases = 0, self.n_layers, 0, 8
         st.q_token_stride = st.q_head_stride = st.kv_token_stride = st.kv_head_stride = st.out_token_stride = st.out_head_stride = 0      # (no caller tensors in this call)
@@ -1146,6 +1263,8 @@ class KVBank:
         if defer:
             if q.shape[0] != 1 or phases != 0:
                 raise ValueError("defer=True is for one-layer calls")
+            if self._ragged(0, self.n_layers):      # (a bank with a ragged layer steps through the heads family, all layers: one flush)
+                return self._attend_heads(plan, q, k_new, v_new, layer_begin, out), None
             return self._attend_deferred(plan, q, k_new, v_new, layer_begin, out, q_pos), None
         lc, _, n, _ = q.shape
         self._quant_refuse(n > 1, "a chunk step (q_len > 1)")

@@ -737,6 +737,52 @@ int ekv_ada_step_attend(const ekv_bank *bank, const ekv_step *step, int32_t dtyp
                         const void *v_new, void *out, int32_t *evict_ids, const float *rope_cos, const float *rope_sin,
                         void *workspace, size_t workspace_bytes, void *stream);
 
+/* Decode steps over KV heads of different lengths ("heads"; ABI 8, additive): the _typed calls with an ekv_heads struct behind the
+ * element type.  A decode step of a multi-layer bank in which every (layer, KV head) holds its own number of rows, as a bank does after
+ * adaptive steps.  The counts are read by the kernels from a DEVICE-resident table, so the call has no limit on the number of heads and
+ * takes every form the uniform _typed decode call takes: the whole step, the per-layer call phases = 1 | 4 with defer_layers, and the
+ * flush phases = 8 over all deferred layers — a ragged bank steps like a uniform one, attention + fold per layer and ONE scorer launch
+ * over all heads per token.
+ *
+ *   rows       DEVICE int32 [bank->n_layers][n_kv_heads], indexed by bank layer: the rows head (l, h) held when the table was written.
+ *   rows_host  HOST copy of the same, required.  Every check and every plan reads this copy; ekv_heads_step_check, ekv_heads_step_info
+ *              and ekv_heads_workspace_bytes dereference no device pointer.  Read during the call only.
+ *   grow       rows every head of the call's layers has gained since the table was written (>= 0).
+ *
+ * Head (l, h) of the call's layers steps with T = rows[l][h] + grow + 1; the + 1 is the step's own token.  step->n_slots is IGNORED.
+ * Every other field of ekv_step keeps its meaning and is shared by the heads (score_off, the selection windows, phys_extent: an extent
+ * every head's live rows lie below, or 0 for cap).  n_evict is 0 (every head grows by one row) or 1 (every T stays put).  The call never
+ * writes the table: the caller advances `grow`, or rewrites the table when the lengths change in any other way.
+ *
+ * The launch is the uniform kernels' own (KV head, layer) grid.  Workgroup (h, ll) reads its count with one scalar load, overwrites
+ * n_slots in its copy of the argument structs, and is the uniform kernel from there on: per head the arithmetic, and therefore every
+ * output bit and every eviction decision, is that of the uniform step of its length under the same n_split and pitches.  A key-range
+ * split wholly past a short head's end contributes (m, l, o) = (-inf, 0, 0) to the fold.
+ *
+ * Planning.  The ENVELOPE is the largest T of the host table over the call's layers, or, for a deferred call, over all defer_layers
+ * layers (bank layers layer_begin - defer_index .. + defer_layers), so that the layer calls and the flush agree on every pitch.  A phased
+ * or deferred call plans as ekv_step_*_typed of the same step with n_slots = the envelope: same n_split, launch list and workspace.  The
+ * whole-step form (phases == 0) plans as that step with phases = 1 | 2 — the split kernel, then the scorer (which folds), or the fold
+ * alone where nothing is scored: there is no one-launch build of this family.
+ *
+ * Accepted: q_len == 1 with plain keys, 16-bit rows, fp16 and bf16, every head_dim of the decode kernels, GQA factors <= 8, the ordered
+ * score-row layout, any number of KV heads; scored policies within the split path's fast scorer (at most 6144 slots, cap % 4 == 0).
+ * EKV_E_UNSUPPORTED with no launch and ekv_heads_workspace_bytes = 0: q_len > 1, rope_on_read, EKV_PHASE_SLOT_ROWS, tova_head_mean,
+ * n_evict > 1, a GQA factor > 8, EKV_POLICY_RANGE with a victim, and scored shapes only the generic scorer serves.  EKV_E_ARG: a NULL
+ * struct or pointer, grow < 0, a host count < 1, a resulting T > cap, deferred layers outside the bank, and whatever the uniform step of
+ * a head's geometry refuses as EKV_E_ARG. */
+typedef struct ekv_heads {
+  const int32_t *rows;
+  const int32_t *rows_host;
+  int32_t grow;
+} ekv_heads;
+int ekv_heads_step_check(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const ekv_heads *heads);
+int ekv_heads_step_info(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const ekv_heads *heads, int32_t *info, int32_t n_info);
+size_t ekv_heads_workspace_bytes(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const ekv_heads *heads);
+int ekv_heads_step_attend(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const ekv_heads *heads, const void *q,
+                          const void *k_new, const void *v_new, void *out, int32_t *evict_ids, void *workspace, size_t workspace_bytes,
+                          void *stream);
+
 /* Batched decode steps (ABI 8, additive): ONE call, and one launch per kernel kind, serves n_seq sequences whose caches have
  * different lengths and different eviction geometry.  Each entry of the table names the bank layer it attends and carries what
  * ekv_step holds per step; entry i owns row i of the call's tensors.  The layers of a table need not be contiguous or ordered, so

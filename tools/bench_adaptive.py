@@ -14,15 +14,23 @@ prints it as one JSON line.
 (3) The decode call (`decode`).  32 layers x 32 heads at a mean of 2048 rows per head: a bank whose heads alternate 1024 / 3072 rows, one
     evicting h2o_head decode step = 32 calls of the batched call on the bank seen as L * H one-head layers, against a uniform bank of
     2048 rows per head stepped one layer per call with the scorer deferred to one flush.  Same total rows, legs interleaved.
+    A third, interleaved leg steps the same ragged bank one layer per call through the heads family (ekv_heads_*: attend(defer=True) per
+    layer, one flush); the three legs, their spreads and the ratios deferred / view and deferred / uniform also go to profiles/heads_bench.json
+    (--heads-out).  Both deferred legs take a fresh StepPlan every token, as the driver does.
 (4) The prefill (`prefill`, --model-layers > 0).  tools/bench_oneshot.py's Llama2-7B-shaped random-init HF model through the seam, a
     4096-token prompt cut to 2048 in encoding mode with h2o_head, one-shot (obs_window 32, score_pool 7), max_new_tokens = 1 (one decode
     forward in either leg): without the key and with generation_config['head_budgets'] = 'adaptive'.  Wall seconds per generate call,
     host-synchronised, legs interleaved.
 
-Usage: python tools/bench_adaptive.py [--reps 7] [--steps 5] [--warm 3] [--model-layers 32] [--prefill-reps 3] [--out profiles/adaptive_bench.json]"""
+--parts picks the parts that run (default: all of selection,decode,prefill).  A run of some parts only leaves profiles/adaptive_bench.json,
+the record of all of them, alone unless --out names a file.
+
+Usage: python tools/bench_adaptive.py [--reps 7] [--steps 5] [--warm 3] [--model-layers 32] [--prefill-reps 3] [--parts selection,decode,prefill]
+       [--out profiles/adaptive_bench.json] [--heads-out profiles/heads_bench.json]"""
 from __future__ import annotations
 
 import argparse
+import dataclasses
 import json
 import math
 import os
@@ -115,10 +123,17 @@ def decode_legs(budget=2048):
             ragged.attend(plan, q[l:l + 1], k[l:l + 1], v[l:l + 1], layer_begin=l, evict_ids=False)
 
     def step_uniform(i):
+        p = dataclasses.replace(plan)
         for l in range(L):
-            uniform.attend(plan, q[l:l + 1], k[l:l + 1], v[l:l + 1], layer_begin=l, defer=True)
+            uniform.attend(p, q[l:l + 1], k[l:l + 1], v[l:l + 1], layer_begin=l, defer=True)
         uniform.flush()
-    return {"ragged_view_per_layer": step_ragged, "uniform_deferred_per_layer": step_uniform}, lens
+
+    def step_heads(i):
+        p = dataclasses.replace(plan)
+        for l in range(L):
+            ragged.attend(p, q[l:l + 1], k[l:l + 1], v[l:l + 1], layer_begin=l, defer=True)
+        ragged.flush()
+    return {"ragged_view_per_layer": step_ragged, "uniform_deferred_per_layer": step_uniform, "ragged_heads_deferred_per_layer": step_heads}, lens, ragged
 
 
 def prefill_legs(layers, prompt, budget):
@@ -158,10 +173,32 @@ def main():
     ap.add_argument("--warm", type=int, default=3)
     ap.add_argument("--model-layers", type=int, default=32)
     ap.add_argument("--prefill-reps", type=int, default=3)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "adaptive_bench.json"))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--heads-out", default=os.path.join(ROOT, "profiles", "heads_bench.json"))
+    ap.add_argument("--parts", default="selection,decode,prefill")
     args = ap.parse_args()
+    parts = set(args.parts.split(","))
+    if args.out is None and parts >= {"selection", "decode", "prefill"}:
+        args.out = os.path.join(ROOT, "profiles", "adaptive_bench.json")
     torch.cuda.set_device(0)
     res = {"device": torch.cuda.get_device_name(0), "reps": args.reps, "steps": args.steps, "warm": args.warm}
+    if "selection" in parts:
+        selection_part(args, res)
+    if "decode" in parts:
+        decode_part(args, res)
+    if "prefill" in parts and args.model_layers > 0:
+        w = wall(prefill_legs(args.model_layers, 4096, 2048), args.prefill_reps)
+        res["prefill"] = {"shape": f"Llama2-7B-shaped random-init HF model, {args.model_layers} layers, 4096-token prompt, budget 2048, encoding mode, h2o_head, "
+                                   "one-shot (obs_window 32, score_pool 7), max_new_tokens 1; wall seconds per generate call", **w}
+        res["prefill"]["adaptive_over_uniform"] = round(w["one_shot_adaptive"]["seconds"] / w["one_shot_uniform"]["seconds"], 4)
+    if args.out is not None:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(res, f, indent=1)
+    print(json.dumps(res))
+
+
+def selection_part(args, res):
     lo, hi = bounds()
     made = {"pooled_max_7": selection_leg(None), "adaptive_floor_0.2_ceil_2.0": selection_leg((lo, hi)), "adaptive_degenerate": selection_leg((N_EVICT, N_EVICT))}
     t = _interleave({k: f for k, (f, _, _) in made.items()}, args.reps, args.steps, args.warm)
@@ -178,23 +215,29 @@ def main():
         res["kernels"] = {"unavailable": repr(e)[:200]}
     made.clear()
     torch.cuda.empty_cache()
-    legs, lens = decode_legs()
+
+
+def decode_part(args, res):
+    legs, lens, ragged = decode_legs()
     t = _interleave(legs, args.reps, args.steps, args.warm)
     res["decode"] = {"shape": f"{L} layers x {H} heads, head_dim {D}, h2o_head evicting decode step; ragged: heads alternate {lens[0]} / {lens[1]} rows, "
-                              "one batched call on the one-head view per layer; uniform: 2048 rows per head, one deferred call per layer + one flush",
+                              "one batched call on the one-head view per layer, or one deferred call of the heads family per layer + one flush; "
+                              "uniform: 2048 rows per head, one deferred call per layer + one flush",
                      **{k: dict(us_per_token_step=t[k]["us"], run_to_run_spread=t[k]["spread"]) for k in legs}}
-    res["decode"]["ragged_over_uniform"] = round(t["ragged_view_per_layer"]["us"] / t["uniform_deferred_per_layer"]["us"], 4)
+    view, uni, heads = (t[k]["us"] for k in ("ragged_view_per_layer", "uniform_deferred_per_layer", "ragged_heads_deferred_per_layer"))
+    res["decode"]["ragged_over_uniform"] = round(view / uni, 4)
+    res["decode"]["deferred_over_view"] = round(heads / view, 4)
+    res["decode"]["deferred_over_uniform"] = round(heads / uni, 4)
+    # an improvement only when the deferred median is below the view's by more than both legs' spreads
+    margin = view * t["ragged_view_per_layer"]["spread"] + heads * t["ragged_heads_deferred_per_layer"]["spread"]
+    res["decode"]["deferred_faster_than_view_beyond_both_spreads"] = bool(view - heads > margin)
+    res["decode"]["head_table_uploads"] = ragged.head_table_uploads
+    os.makedirs(os.path.dirname(os.path.abspath(args.heads_out)), exist_ok=True)
+    with open(args.heads_out, "w") as f:
+        json.dump({k: res[k] for k in ("device", "reps", "steps", "warm", "decode")}, f, indent=1)
     legs.clear()
+    del ragged
     torch.cuda.empty_cache()
-    if args.model_layers > 0:
-        w = wall(prefill_legs(args.model_layers, 4096, 2048), args.prefill_reps)
-        res["prefill"] = {"shape": f"Llama2-7B-shaped random-init HF model, {args.model_layers} layers, 4096-token prompt, budget 2048, encoding mode, h2o_head, "
-                                   "one-shot (obs_window 32, score_pool 7), max_new_tokens 1; wall seconds per generate call", **w}
-        res["prefill"]["adaptive_over_uniform"] = round(w["one_shot_adaptive"]["seconds"] / w["one_shot_uniform"]["seconds"], 4)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump(res, f, indent=1)
-    print(json.dumps(res))
 
 
 if __name__ == "__main__":
