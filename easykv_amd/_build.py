@@ -81,6 +81,8 @@ FAMILIES = {
     # decode steps over KV heads of different lengths (-DEKV_HEADS=1): the split decode kernel and the scorer behind it, plain keys, 16-bit rows
     "EKV_DECODE_HEADS": lambda elem, d: (
         "ekv_attn_decode.inc", f"ekv_attn_decode_d{d}_heads" + _tags(elem), _on(elem) + [f"-DEKV_D={d}", "-DEKV_ROPE=false", "-DEKV_HEADS=1"]),
+    # chunk steps over FP8 code rows: ekv_chunk8_kernel, a source of its own
+    "EKV_CHUNK_CODES": lambda elem, d: ("ekv_attn_chunk8.inc", f"ekv_attn_chunk8_d{d}" + _tags(elem), _on(elem) + [f"-DEKV_D={d}"]),
     "EKV_DECODE_SCORE_HEADS": lambda elem: ("ekv_decode_score.inc", "ekv_decode_score_heads" + _tags(elem), _on(elem) + ["-DEKV_HEADS=1"]),
 }
 
@@ -92,9 +94,19 @@ def instances(manifest=None):
     return [(fam, tuple(w.strip() for w in args.split(","))) for fam, args in found]
 
 
+# Translation units of the library's own added after the object list was recorded (objects() returns exactly the recorded names, and
+# later_objects() exactly one object per line of its manifest): the launch code of the FP8 chunk kernel.  Compiled and linked like the rest.
+LATER_SOURCES = ("ekv_attn_chunk8.hip",)
+
+
 def sources():
     """The library's own translation units: the .hip files, and the host-only planner (plain C++: no -x hip, no device pass)."""
-    return sorted(glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.cpp")))
+    return sorted(f for f in glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.cpp")) if os.path.basename(f) not in LATER_SOURCES)
+
+
+def later_source_objects():
+    """(object name, hipcc arguments) of LATER_SOURCES."""
+    return [(os.path.splitext(f)[0], [os.path.join(CSRC, f)]) for f in LATER_SOURCES]
 
 
 def objects():
@@ -135,7 +147,7 @@ def later_instances():
 
 
 def later_objects():
-    """(object name, hipcc arguments) of the instances of ekv_instances_later.def (the kv84 decode instances, the kv164 ones, the long-row scorer, head_dim 256, the soft-capped instances, the sink instances, the window instances, the pooled scorer, the adaptive scorer and its allot kernel, the heads instances)."""
+    """(object name, hipcc arguments) of the instances of ekv_instances_later.def (the kv84 decode instances, the kv164 ones, the long-row scorer, head_dim 256, the soft-capped instances, the sink instances, the window instances, the pooled scorer, the adaptive scorer and its allot kernel, the heads instances, the FP8 chunk kernel)."""
     return _instance_objects(later_instances())
 
 
@@ -148,7 +160,7 @@ def stale() -> bool:
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    return any(os.path.getmtime(d) > t for d in sources() + headers())
+    return any(os.path.getmtime(d) > t for d in sources() + [a[-1] for _, a in later_source_objects()] + headers())
 
 
 def build_lib(force: bool = False, verbose: bool = False, jobs: int = 0) -> str:
@@ -160,7 +172,7 @@ def build_lib(force: bool = False, verbose: bool = False, jobs: int = 0) -> str:
     os.makedirs(OBJ, exist_ok=True)
     hdr_t = max(os.path.getmtime(h) for h in headers())
     todo, objs = [], []
-    for name, args in objects() + added_objects() + later_objects():
+    for name, args in objects() + added_objects() + later_objects() + later_source_objects():
         obj = os.path.join(OBJ, name + ".o")
         objs.append(obj)
         src_t = os.path.getmtime(args[-1])

@@ -66,6 +66,9 @@ EXPORTS += tuple(ADA_CALLS[what] for what in STEP_CALLS)
 # the heads family (include/easykv_hip.h, "heads"): the _typed calls with an ekv_heads struct behind the dtype and no rope tables; 16-bit rows
 HEADS_CALLS = {what: "ekv_heads_" + what for what in STEP_CALLS}
 EXPORTS += tuple(HEADS_CALLS[what] for what in STEP_CALLS)
+# chunk steps on FP8 rows (include/easykv_hip.h, "kv8 chunks"): the signatures of the kv8 calls, for steps of any q_len; one sequence
+KV8_CHUNK_CALLS = {what: "ekv_kv8_chunk_" + what for what in STEP_CALLS}
+EXPORTS += tuple(KV8_CHUNK_CALLS[what] for what in STEP_CALLS)
 
 
 class Bank(C.Structure):
@@ -184,6 +187,10 @@ def load():
             tails["step_attend"] = [vp] * (6 if batch else 8) + [C.c_size_t, vp]      # (a batch has no rope tables)
             for what in STEP_CALLS:
                 getattr(lib, step_call_name(rows, batch, what)).argtypes = head + tails[what]
+        if rows == "kv8":      # (chunk steps on FP8 rows: the uniform kv8 signatures)
+            tails["step_attend"] = [vp] * 8 + [C.c_size_t, vp]
+            for what in STEP_CALLS:
+                getattr(lib, KV8_CHUNK_CALLS[what]).argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, C.POINTER(desc)] + tails[what]
         if rows is None:      # (the long family: the uniform 16-bit signatures)
             tails["step_attend"] = [vp] * 8 + [C.c_size_t, vp]
             for what in STEP_CALLS:

@@ -107,7 +107,7 @@ class BudgetedKVCache:
 
     def __init__(self, n_layers, n_q_heads, n_kv_heads, head_dim, cap, device, streaming=False, rope=None,
                  record=False, layer_begin=0, layer_count=None, rope_base=10000.0, dtype=None, long_rows=False, logit_cap=None, sm_scale=None,
-                 sinks=None, windows=None):
+                 sinks=None, windows=None, kv_quant=None, quant_chunks=False):
         self.layer_begin = layer_begin
         self.layer_count = n_layers - layer_begin if layer_count is None else layer_count
         if not (0 <= self.layer_begin and self.layer_count >= 1 and self.layer_begin + self.layer_count <= n_layers):
@@ -124,7 +124,9 @@ class BudgetedKVCache:
         self.logit_cap, self.sm_scale = logit_cap, sm_scale
         if windows is not None and streaming:
             raise ValueError("a cache with sliding windows has no RoPE-on-read build: streaming=True needs windows=None")
-        extra = {k: v for k, v in (("logit_cap", logit_cap), ("sm_scale", sm_scale), ("sinks", sinks), ("windows", windows)) if v is not None}      # (opt-in: named only when set)
+        extra = {k: v for k, v in (("logit_cap", logit_cap), ("sm_scale", sm_scale), ("sinks", sinks), ("windows", windows), ("kv_quant", kv_quant)) if v is not None}      # (opt-in: named only when set)
+        if quant_chunks:      # (a bank created quantised that is prefilled in place: KVBank(kv_quant='fp8', quant_chunks=True))
+            extra["quant_chunks"] = True
         self.bank = KVBank(self.layer_count, n_q_heads, n_kv_heads, head_dim, cap, device=device, dtype=dtype, long_rows=long_rows, **extra)
         self.sinks = self.bank.sinks      # (fp32 on the device, or None)
         self.windows = self.bank.windows      # (the windows of the layers this cache owns, a tuple, or None)
@@ -485,17 +487,28 @@ class _Run:
         # and exactly the eviction decisions of the unquantised run; head_dim 128, every GQA factor, batched as well).  The shapes each takes are engine.ROW_FORMATS'.  kv_dtype keeps meaning the 16-bit
         # type of q / k / v / out.
         self.kv_quant = kv_quant = cfg.get("kv_quant", None)
+        # extension key: False (default) or True, with kv_quant='fp8' only — the cache's bank is created holding FP8 rows and the prefill
+        # itself (dense prefix, strided chunks, dense_growth, their hipgraph) runs on them through the chunk calls of FP8 rows
+        # (KVBank(quant_chunks=True)): no 16-bit K/V row is ever allocated, nothing is converted at the prefill -> decode
+        # boundary, and kv_mode='ppl' runs
+        self.kv_quant_prefill = cfg.get("kv_quant_prefill", False)
+        if self.kv_quant_prefill not in (False, True):
+            raise ValueError(f"generation_config['kv_quant_prefill'] must be False or True, not {self.kv_quant_prefill!r}")
+        if self.kv_quant_prefill and kv_quant != "fp8":
+            raise ValueError(f"generation_config['kv_quant_prefill'] = True needs generation_config['kv_quant'] = 'fp8' (not {kv_quant!r}): FP8 rows are "
+                             "the only quantised rows with a chunk step")
+        kvq = f"generation_config['kv_quant'] = {kv_quant!r}" + (" with generation_config['kv_quant_prefill'] = True" if self.kv_quant_prefill else "")
         shard = getattr(model, "layer_shard", None)
         if shard is not None and shard.world == 1:
             shard = None
         fmt = row_format(kv_quant, "generation_config['kv_quant']")
         if kv_quant is not None:
             if streaming:
-                raise ValueError(f"generation_config['kv_quant'] = {kv_quant!r} with streaming=True: the quantised decode kernels have no RoPE-on-read build")
-            if kv_mode == "ppl":
-                raise ValueError(f"generation_config['kv_quant'] = {kv_quant!r} with kv_mode='ppl': there is no decode phase to quantise the bank for")
+                raise ValueError(f"{kvq} with streaming=True: the quantised decode kernels have no RoPE-on-read build")
+            if kv_mode == "ppl" and not self.kv_quant_prefill:
+                raise ValueError(f"{kvq} with kv_mode='ppl': there is no decode phase to quantise the bank for")
             if shard is not None:
-                raise ValueError(f"generation_config['kv_quant'] = {kv_quant!r} is not supported on a layer-sharded model (model.layer_shard)")
+                raise ValueError(f"{kvq} is not supported on a layer-sharded model (model.layer_shard)")
         # extension key: False (default) or True — the steps of the run's bank go to the long-row call family (KVBank(long_rows=True)):
         # scored steps of any width up to the cache's capacity, where the plain family refuses beyond about 38 400 score columns; same
         # tokens and evictions wherever both run.  16-bit rows and single sequences only (generate_batch refuses it).
@@ -503,15 +516,17 @@ class _Run:
         if self.long_rows not in (False, True):
             raise ValueError(f"generation_config['long_rows'] must be False or True, not {self.long_rows!r}")
         if self.long_rows and kv_quant is not None:
-            raise ValueError(f"generation_config['long_rows'] = True with kv_quant = {kv_quant!r}: the long-row scorer is built for 16-bit rows, "
+            raise ValueError(f"generation_config['long_rows'] = True with {kvq}: the long-row scorer is built for 16-bit rows, "
                              "and the quantised decode calls have no long form")
         self.dims = n_layers, hq, hkv, d = _dims(model)
         if streaming and d in PLAIN_KEYS_HEAD_DIMS:
             raise ValueError(f"streaming=True: RoPE-on-read has no build for head_dim {d} (plain keys only)")
         if fmt is not None and d not in fmt["head_dims"]:
-            raise ValueError(f"generation_config['kv_quant'] = {kv_quant!r} needs head_dim {' or '.join(map(str, fmt['head_dims']))} (this model: {d})")
+            raise ValueError(f"{kvq} needs head_dim {' or '.join(map(str, fmt['head_dims']))} (this model: {d})")
+        if self.kv_quant_prefill and hq // hkv > 32:      # (a chunk step on FP8 rows runs blocks of at most 32 GQA-folded rows: before any bank exists)
+            raise ValueError(f"{kvq} needs a GQA factor of at most 32 (this model: {hq // hkv}): a chunk step on FP8 rows folds a query's heads into one block")
         if fmt is not None and fmt["max_rep"] is not None and hq // hkv > fmt["max_rep"]:
-            raise ValueError(f"generation_config['kv_quant'] = {kv_quant!r} needs a GQA factor of at most {fmt['max_rep']} (this model: {hq // hkv})")
+            raise ValueError(f"{kvq} needs a GQA factor of at most {fmt['max_rep']} (this model: {hq // hkv})")
         # the model's own attention arithmetic, read where head_dim is: attn_logit_softcapping (Gemma 2; absent or None = off) becomes the
         # cache's logit_cap, query_pre_attn_scalar (Gemma 2 / 3; absent = head_dim) its softmax scale qpas ** -0.5 (None = 1 / sqrt(head_dim))
         cap_ = getattr(model.config, "attn_logit_softcapping", None)
@@ -525,7 +540,7 @@ class _Run:
             if streaming:
                 raise ValueError(f"{what} with streaming=True: RoPE-on-read has no soft-capped build")
             if kv_quant is not None:
-                raise ValueError(f"{what} with generation_config['kv_quant'] = {kv_quant!r}: there is no capped quantised decode step")
+                raise ValueError(f"{what} with {kvq}: there is no capped quantised decode step")
             if self.long_rows:
                 raise ValueError(f"{what} with generation_config['long_rows'] = True: there is no capped long call")
             if d not in CAPPED_HEAD_DIMS:
@@ -538,7 +553,7 @@ class _Run:
             if streaming:
                 raise ValueError(f"{what} with streaming=True: RoPE-on-read has no sink build")
             if kv_quant is not None:
-                raise ValueError(f"{what} with generation_config['kv_quant'] = {kv_quant!r}: there is no quantised sink decode step")
+                raise ValueError(f"{what} with {kvq}: there is no quantised sink decode step")
             if self.long_rows:
                 raise ValueError(f"{what} with generation_config['long_rows'] = True: there is no long sink call")
             if self.logit_cap is not None:
@@ -554,7 +569,7 @@ class _Run:
             if streaming:
                 raise ValueError(f"{what} with streaming=True: RoPE-on-read has no window build")
             if kv_quant is not None:
-                raise ValueError(f"{what} with generation_config['kv_quant'] = {kv_quant!r}: there is no quantised window step")
+                raise ValueError(f"{what} with {kvq}: there is no quantised window step")
             if self.long_rows:
                 raise ValueError(f"{what} with generation_config['long_rows'] = True: there is no long window call")
             if self.logit_cap is not None:
@@ -578,6 +593,8 @@ class _Run:
         self.one_shot = self.prefill == "one_shot"
         if self.one_shot:      # (before any bank exists)
             what = "generation_config['prefill'] = 'one_shot'"
+            if self.kv_quant_prefill:
+                raise ValueError(f"{what} with generation_config['kv_quant_prefill'] = True: the observation step is pooled, and there is no pooled call on FP8 rows")
             self.obs_window, self.score_pool, self.score_pool_op = cfg.get("obs_window", 32), cfg.get("score_pool", 7), cfg.get("score_pool_op", "max")
             isint = lambda x: isinstance(x, int) and not isinstance(x, bool)
             if not (isint(self.obs_window) and self.obs_window >= 1):
@@ -712,6 +729,7 @@ class _Run:
         cache = BudgetedKVCache(n_layers, hq, h, d, cap + 8, self.dev, streaming=self.streaming, record=self.record, rope=hf_rope,
                                 layer_begin=self.layers[0], layer_count=self.layers[1], rope_base=self.rope_base, dtype=self.kv_dtype,
                                 **(dict(long_rows=True) if self.long_rows else {}),      # (opt-in: named only when asked for)
+                                **(dict(kv_quant="fp8", quant_chunks=True) if self.kv_quant_prefill else {}),
                                 **{k: v for k, v in (("logit_cap", self.logit_cap), ("sm_scale", self.sm_scale), ("sinks", self.sinks),
                                                     ("windows", self.windows)) if v is not None})
         cache.unrotate = hf_rope if self.hf_stream else None
@@ -1090,7 +1108,7 @@ def generate(self, input_ids, generation_config, kv_mode="encoding", stride=1, r
     else:
         pre = _prefill(run, input_ids, kv_mode)
         cache = pre.cache
-        if run.kv_quant:      # prefill -> decode boundary: the decode steps run on quantised rows
+        if run.kv_quant and not run.kv_quant_prefill:      # prefill -> decode boundary: the decode steps run on quantised rows (kv_quant_prefill: they are already)
             cache.bank.quantize(run.kv_quant)
         out_ids, fed = _decode(run, pre, report_decoding_latency and pre.mode == "encoding")
         if pre.mode != "encoding":      # (encoding mode reports the cache the prefill left: printed there)
@@ -1150,7 +1168,7 @@ def generate_batch(self, input_ids_list, generation_config, kv_mode="encoding", 
     seqs = []
     for p in prompts:
         seqs.append(_prefill(run, p, kv_mode))
-        if run.kv_quant:
+        if run.kv_quant and not run.kv_quant_prefill:      # (kv_quant_prefill: the prompt was prefilled in an FP8 bank)
             seqs[-1].cache.bank.quantize(run.kv_quant)
     first = seqs[0].cache.bank
     rows = dict(kv_quant=run.kv_quant) if run.kv_quant else {}      # (the format's planes only: the 16-bit rows of the batch are never allocated)

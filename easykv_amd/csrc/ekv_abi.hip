@@ -136,6 +136,7 @@ static int call_attend(const EkvCall& c, const void* q, const void* k_new, const
           : sinks ? ekv_launch_attn_chunk_sink(aa, sinks, D, lc, P.two_pass, s, L.fuse ? &sa : nullptr, bf16)
                   : ekv_launch_attn_chunk(aa, D, lc, P.wide, P.two_pass, s, L.fuse ? &sa : nullptr, L.passes, L.tail ? &sa : nullptr, bf16, capped);
         break;
+      case EKV_RUN_CHUNK8: e = ekv_launch_attn_chunk8(aa, D, lc, s, L.fuse ? &sa : nullptr, bf16); break;
       case EKV_RUN_FLUSH: {
         EkvAttnArgs a2 = aa;
         a2.q = aa.q_keep;
@@ -325,6 +326,20 @@ int ekv_kv8_step_attend(const ekv_bank* bank, const ekv_step* st, int32_t dtype,
                         const void* v_new, void* out, int32_t* evict_ids, const float* rope_cos, const float* rope_sin,
                         void* workspace, size_t workspace_bytes, void* stream) {
   return call_attend(kv8_call(bank, st, dtype, q8), q, k_new, v_new, out, evict_ids, rope_cos, rope_sin, workspace, workspace_bytes, stream);
+}
+
+// chunk steps on a kv8 bank (include/easykv_hip.h, "kv8 chunks")
+int ekv_kv8_chunk_step_check(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_kv8* q8) { return call_check(kv8_chunk_call(bank, st, dtype, q8)); }
+int ekv_kv8_chunk_step_info(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_kv8* q8, int32_t* info, int32_t n_info) {
+  return call_info(kv8_chunk_call(bank, st, dtype, q8), info, n_info);
+}
+size_t ekv_kv8_chunk_workspace_bytes(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_kv8* q8) {
+  return call_workspace_bytes(kv8_chunk_call(bank, st, dtype, q8));
+}
+int ekv_kv8_chunk_step_attend(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_kv8* q8, const void* q, const void* k_new,
+                              const void* v_new, void* out, int32_t* evict_ids, const float* rope_cos, const float* rope_sin,
+                              void* workspace, size_t workspace_bytes, void* stream) {
+  return call_attend(kv8_chunk_call(bank, st, dtype, q8), q, k_new, v_new, out, evict_ids, rope_cos, rope_sin, workspace, workspace_bytes, stream);
 }
 
 // decode steps over KV heads of different lengths (include/easykv_hip.h, ekv_heads)

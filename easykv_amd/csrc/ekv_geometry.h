@@ -240,3 +240,19 @@ inline size_t ekv_chunk_step_lds(int head_dim, int qpw, bool rope, bool two_pass
   if (qpw == 4 && !rope) return ekv_chunk_kernel_lds(head_dim, 0, 1, false, 16, rows_per_split, fold);
   return ekv_chunk_kernel_lds(head_dim, 0, tiles, rope, nw, rows_per_split, fold);
 }
+
+// ---- chunk step over FP8 code rows (ekv_attn_chunk8.inc; the ekv_kv8_chunk_* calls) -----------------------------------------------------
+// One build: 4 waves, one 16-row query tile per wave (blocks of <= kChunkNarrowRows folded rows), one pass.  A lane's 16-byte piece of a
+// code row is 16 elements: a 64-position super-tile is 64 * head_dim bytes per tensor in flight (half the 16-bit kernel's).  The codes
+// are widened BEFORE the LDS store, so the LDS plan is the 16-bit one-tile build's (slot entries | K tile | V tile, 16-bit rows with the
+// same padding) plus the row scales of the tile: k_scale[64] | v_scale[64], fp32.
+constexpr int kChunk8EPL = 16;      // elements per 16-byte piece of a code row
+inline size_t ekv_chunk8_lds(int head_dim, int rows_per_split) {
+  return ekv_chunk_kernel_lds(head_dim, 0, 1, false, 4, rows_per_split, true) + 2 * kChunkKT * sizeof(float);
+}
+// (16384: the rows an unsplit chunk workgroup may walk on plain keys, ekv_plan_step's max_rows — its slot entries live in LDS)
+static_assert((size_t)16384 * 4 + (size_t)2 * kChunkKT * (128 + kChunkPadH) * 2 + 2 * kChunkKT * 4 <= 160 * 1024, "the longest unsplit key range fits one CU's LDS");
+static_assert(kChunkKT * (128 / kChunk8EPL) % 256 == 0 && kChunkKT * (64 / kChunk8EPL) % 256 == 0, "a super-tile of code rows is whole pieces per thread of 256");
+// the in-kernel fold exchanges (m, l, o[D]) of 2 x 64 lanes over the tile buffers: (D / 16 * 4 + 2) floats per lane
+static_assert((size_t)2 * 64 * (128 / 16 * 4 + 2) * 4 <= (size_t)2 * kChunkKT * (128 + kChunkPadH) * 2 &&
+              (size_t)2 * 64 * (64 / 16 * 4 + 2) * 4 <= (size_t)2 * kChunkKT * (64 + kChunkPadH) * 2, "the fold exchange fits the K/V tile buffers");

@@ -35,7 +35,8 @@ enum EkvLaunchKind : int32_t {
   EKV_RUN_FLUSH,          // ekv_launch_attn_chunk: the deferred column-sum pass of all layers, from the kept queries
   EKV_RUN_FOLD, EKV_RUN_RANGE, EKV_RUN_DECODE_SCORE, EKV_RUN_TOVA_MEAN, EKV_RUN_SCORE_SELECT,
   EKV_RUN_LONG_FOLD,      // ekv_launch_long_fold: the fold of a long call whose generic scorer would have folded the output itself
-  EKV_RUN_LONG_SCORE      // ekv_launch_score_long: sweep + select of the long-row scorer (two kernels) where the plain plan has EKV_RUN_SCORE_SELECT
+  EKV_RUN_LONG_SCORE,     // ekv_launch_score_long: sweep + select of the long-row scorer (two kernels) where the plain plan has EKV_RUN_SCORE_SELECT
+  EKV_RUN_CHUNK8          // ekv_launch_attn_chunk8: the one-pass chunk kernel over FP8 code rows (ekv_attn_chunk8.inc; the ekv_kv8_chunk_* calls)
 };
 struct EkvLaunch {
   int32_t kind, kernel_count;
@@ -212,6 +213,10 @@ hipError_t ekv_launch_attn_decode(const EkvAttnArgs& a, const EkvSeqTable* tb, i
 hipError_t ekv_launch_attn_chunk(const EkvAttnArgs& a, int head_dim, int layer_count, bool wide, bool two_pass, hipStream_t s,
                                  const EkvScoreArgs* fuse_sc, int passes, const EkvScoreArgs* tail_sc, bool bf16, bool capped = false);
 hipError_t ekv_launch_attn_resident(const EkvAttnArgs& a, const EkvScoreArgs& sc, int layer_count, hipStream_t s, bool bf16);
+// Chunk step over FP8 code rows (the ekv_kv8_chunk_* calls; ekv_attn_chunk8.inc, launch code in ekv_attn_chunk8.hip): a.k / a.v / a.k_w /
+// a.v_w are the code planes, a.k_scale / a.v_scale the row scales; one pass, blocks of <= 32 folded rows (the narrow-block rule);
+// fuse_sc: an unsplit one-block head's scorer runs as the kernel's tail.  head_dim 64 / 128, plain keys.
+hipError_t ekv_launch_attn_chunk8(const EkvAttnArgs& a, int head_dim, int layer_count, hipStream_t s, const EkvScoreArgs* fuse_sc, bool bf16);
 hipError_t ekv_launch_tova_headmean(const EkvScoreArgs& a, int layer_count, hipStream_t s);
 hipError_t ekv_launch_score_select(const EkvScoreArgs& a, int layer_count, hipStream_t s, bool bf16);
 hipError_t ekv_launch_decode_fused(const EkvAttnArgs& a, const EkvScoreArgs& sc, const EkvSeqTable* tb, int head_dim, int count, int nw,
@@ -443,7 +448,7 @@ __device__ __forceinline__ EkvScoreArgs ekv_heads_score_args(const EkvScoreArgs&
 #define EKV_FN_WIDE_(d, m, keys, elem) ekv_launch_attn_wide_d##d##_m##m##_##keys##_##elem
 #define EKV_FN_WIDE(d, m, keys, elem) EKV_FN_WIDE_(d, m, keys, elem)
 #define EKV_FN_D_ELEM_(fn, d, elem) fn##_d##d##_##elem
-#define EKV_FN_D_ELEM(fn, d, elem) EKV_FN_D_ELEM_(fn, d, elem)      // (EKV_CHUNK_LDS, EKV_RESIDENT)
+#define EKV_FN_D_ELEM(fn, d, elem) EKV_FN_D_ELEM_(fn, d, elem)      // (EKV_CHUNK_LDS, EKV_RESIDENT, EKV_CHUNK_CODES)
 #define EKV_FN_SCORE_SELECT_(nt, elem) ekv_launch_score_select_nt##nt##_##elem
 #define EKV_FN_SCORE_SELECT(nt, elem) EKV_FN_SCORE_SELECT_(nt, elem)
 #define EKV_FN_SCORE_SELECT_POOL_(nt, elem) ekv_launch_score_select_pool_nt##nt##_##elem

@@ -975,11 +975,25 @@ int resolve_call(const EkvCall& c, EkvResolved* r) {
     if ((r->env.phases & ~(EKV_PHASE_SLOT_ROWS | EKV_PHASE_SLOT_TAIL_OK)) == 0) r->env.phases |= 1 | 2;
     r->step = &r->env;
   }
+  // Chunk calls on FP8 rows (ekv_kv8_chunk_*; include/easykv_hip.h, "kv8 chunks"), likewise stated once.  "Chunks" is a flag of a kv8 call,
+  // combined with nothing else (its entry points spell one sequence and no other variant).  q_len == 1 resolves as the kv8 call, field
+  // for field.  q_len > 1 plans as the 16-bit step of the same shape by the capped call's rule (the 16x16x32 geometry alone, one-tile
+  // build, blocks of at most 32 folded rows: never the wide, the logits-in-LDS or the logits-resident kernel) with the one-pass scheme
+  // forced (two_pass = -1: exported logits, the scorer as the kernel's tail where the step is one unsplit block, else fold + generic
+  // scorer), and every EKV_RUN_CHUNK entry of that plan runs as EKV_RUN_CHUNK8 on ekv_chunk8_kernel; scorer, fold and range entries are
+  // untouched.  Refused with zero launches and zero bytes (EKV_E_UNSUPPORTED): RoPE-on-read, a head_dim other than 64 / 128, a GQA factor
+  // above a block, slot-indexed score rows.
+  const bool chunk8 = c.chunks && c.rows == EKV_ROWS_kv8 && !c.batch && c.step != nullptr && c.step->q_len > 1;
+  if (chunk8) {
+    r->env = *c.step;
+    r->env.two_pass = -1;
+    r->step = &r->env;
+  }
   const int variants = (c.long_rows ? 1 : 0) + (c.capped ? 1 : 0) + (c.sink || c.window ? 1 : 0) + (c.pooled ? 1 : 0) + (c.adaptive ? 1 : 0) + (c.heads ? 1 : 0);
   const bool sinkish = c.sink || c.window;
   const int rc = (variants && (quant || c.batch || variants > 1))
                      ? EKV_E_UNSUPPORTED
-                     : ekv_plan_step(bank, r->step, P, c.long_rows, c.capped || sinkish, quant || c.batch || sinkish || c.capped || c.heads, c.pooled || c.adaptive);
+                     : ekv_plan_step(bank, r->step, P, c.long_rows, c.capped || sinkish || chunk8, quant || c.batch || sinkish || c.capped || c.heads, c.pooled || c.adaptive);
   P->heads = c.heads ? 1 : 0;
   P->capped = c.capped ? 1 : 0;
   P->sink = c.sink ? 1 : 0;
@@ -999,7 +1013,7 @@ int resolve_call(const EkvCall& c, EkvResolved* r) {
       P->bytes = plain.bytes, P->big_rows = plain.big_rows, P->key_rows = -1;
     }
     P->one_launch = P->n_launches = P->n_list = P->long_rows = P->long_tiles = 0;
-    if (c.batch || c.capped || sinkish || c.pooled || c.adaptive || c.heads) P->bytes = 0;      // (nothing will run: ekv_batch_workspace_bytes of a refused table, ekv_cap_ / ekv_sink_ / ekv_pool_workspace_bytes of a refused step, is 0)
+    if (c.batch || c.capped || sinkish || c.pooled || c.adaptive || c.heads || chunk8) P->bytes = 0;      // (nothing will run: ekv_batch_workspace_bytes of a refused table, ekv_cap_ / ekv_sink_ / ekv_pool_workspace_bytes of a refused step, is 0)
     return code;
   };
   const ekv_step* st = c.step;
@@ -1033,9 +1047,17 @@ int resolve_call(const EkvCall& c, EkvResolved* r) {
       if (kind != EKV_RUN_DECODE && kind != EKV_RUN_FOLD && kind != EKV_RUN_DECODE_SCORE) return refuse(EKV_E_UNSUPPORTED);
     }
   }
-  if (quant && (st->q_len != 1 || st->rope_on_read || !ekv_rows_head_dim(c.rows, bank->head_dim) ||
+  if (quant && ((st->q_len != 1 && !chunk8) || st->rope_on_read || !ekv_rows_head_dim(c.rows, bank->head_dim) ||
                 bank->n_q_heads / bank->n_kv_heads > kRowsRules[c.rows].max_rep))
     return refuse(EKV_E_UNSUPPORTED);
+  if (chunk8) {      // (its LDS fits one CU under the tiling's row bound: ekv_geometry.h states it)
+    if (P->wide || P->two_pass) return refuse(EKV_E_UNSUPPORTED);
+    for (int i = 0; i < P->n_list; ++i) {
+      int32_t& kind = P->list[i].kind;
+      if (kind == EKV_RUN_CHUNK_LDS || kind == EKV_RUN_RESIDENT || kind == EKV_RUN_FLUSH) return refuse(EKV_E_UNSUPPORTED);
+      if (kind == EKV_RUN_CHUNK) kind = EKV_RUN_CHUNK8;
+    }
+  }
   if (c.batch) {
     for (int i = 0; i < c.n_seq; ++i) {      // per entry: the checks of the single-sequence step of that entry's geometry
       const ekv_seq& e = c.seqs[i];

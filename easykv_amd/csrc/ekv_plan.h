@@ -96,6 +96,7 @@ struct EkvCall {
   const ekv_ada* ada;      // ... its struct: NULL, NULL n_evict_out, radius < 0, an unknown op or bounds out of order are argument errors
   bool heads;              // an ekv_heads_* call: decode steps over KV heads of different lengths (16-bit rows, plain keys, no other variant)
   const ekv_heads* hd;     // ... its struct: NULL, a NULL pointer, grow < 0 or a host count out of range are argument errors; `rows` is never dereferenced here
+  bool chunks;             // an ekv_kv8_chunk_* call: a kv8 call that also takes q_len > 1 (FP8 rows, one sequence, plain keys, no other variant)
 };
 inline EkvCall step_call(const ekv_bank* bank, const ekv_step* st, int32_t dtype) { return {bank, st, dtype, EKV_ROWS_kv16, {}, false, nullptr, 0}; }
 inline EkvCall batch_call(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_seq* seqs, int32_t n_seq) {
@@ -124,6 +125,11 @@ inline EkvCall heads_call(const ekv_bank* bank, const ekv_step* st, int32_t dtyp
 // the quantised calls: the same two with a row format and its planes
 inline EkvCall kv8_call(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_kv8* q8) {
   return {bank, st, dtype, EKV_ROWS_kv8, ekv_planes(q8), false, nullptr, 0};
+}
+inline EkvCall kv8_chunk_call(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_kv8* q8) {
+  EkvCall c = kv8_call(bank, st, dtype, q8);
+  c.chunks = true;
+  return c;
 }
 inline EkvCall kv4_call(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_kv4* q4) {
   return {bank, st, dtype, EKV_ROWS_kv4, ekv_planes(q4), false, nullptr, 0};

@@ -177,8 +177,11 @@ class KVBank:
     tok_pos = None       # ... int32 [n_layers, H, cap]: the token position every physical row was appended at
 
     def __init__(self, n_layers, n_q_heads, n_kv_heads, head_dim, cap, device="cuda", scored=True, dtype=torch.float16, kv_quant=None, long_rows=False,
-                 logit_cap=None, sm_scale=None, sinks=None, windows=None):
-        """``windows``: ``n_layers`` integers >= 0, the sliding window of every layer (0: none; include/easykv_hip.h, "sliding windows";
+                 logit_cap=None, sm_scale=None, sinks=None, windows=None, quant_chunks=False):
+        """``quant_chunks=True`` (with ``kv_quant='fp8'``): chunk steps, the dense prefix and their deferred form run on the FP8 rows too
+        (the ``ekv_kv8_chunk_*`` calls, include/easykv_hip.h "kv8 chunks"), so a bank created empty is prefilled in place and no 16-bit
+        K/V tensor is ever allocated.  Without it a quantised bank raises "chunk step", as always.
+        ``windows``: ``n_layers`` integers >= 0, the sliding window of every layer (0: none; include/easykv_hip.h, "sliding windows";
         gpt-oss: 128 on every other layer).  A key appended ``W`` or more tokens behind the query is masked — by the token position its
         physical row carries (``tok_pos``), not by its place in the slot map, because eviction is per head.  A masked key stays live:
         it keeps its slot and score column, receives p = 0 and a count, and may be a victim.  All-zero windows are legal and still route
@@ -215,6 +218,9 @@ class KVBank:
         if dtype not in _lib.DTYPE_CODES:
             raise ValueError(f"KVBank dtype must be torch.float16 or torch.bfloat16, not {dtype}")
         fmt = row_format(kv_quant, "KVBank kv_quant")
+        if quant_chunks and kv_quant != "fp8":
+            raise ValueError(f"KVBank(quant_chunks=True) needs kv_quant='fp8' (not {kv_quant!r}): FP8 rows are the only quantised rows with a chunk step")
+        self.quant_chunks = bool(quant_chunks)
         if long_rows and fmt is not None:
             raise _lib.EkvError(f"KVBank(long_rows=True): the long-row scorer is built for 16-bit rows, not for {fmt['label']} rows "
                                 f"(kv_quant={kv_quant!r}): a quantised bank serves decode steps through its own calls, which have no long form")
@@ -424,6 +430,10 @@ class KVBank:
         return self._score_cnt
 
     # -- quantised K/V storage ("kv8" / "kv4", include/easykv_hip.h; ROW_FORMATS) ----------------------
+    def _chunk_refuse(self, n):
+        """A chunk step (q_len > 1) on quantised rows: only FP8 rows with ``quant_chunks`` take it."""
+        self._quant_refuse(n > 1 and not self.quant_chunks, "a chunk step (q_len > 1)")
+
     def _quant_refuse(self, cond, what):
         if cond and self._fmt is not None:
             raise _lib.EkvError(f"{what} is not available on a bank quantised by {self._fmt['method']}(): its K/V rows are "
@@ -472,9 +482,14 @@ class KVBank:
         self._attach(fmt, desc)
         return self
 
-    def quantize_fp8(self):
+    def quantize_fp8(self, chunks=False):
         """:meth:`quantize` to FP8 (OCP e4m3fn) K/V rows with one fp32 scale per row (``k8`` / ``v8`` / ``k_scale`` / ``v_scale``),
-        head_dim 64 and 128.  On a bank that holds FP8 rows already it does nothing."""
+        head_dim 64 and 128.  On a bank that holds FP8 rows already it does nothing.  ``chunks=True``: the bank takes chunk steps on
+        its FP8 rows from here on (``quant_chunks``, see the constructor)."""
+        if chunks and not self.quant_chunks:
+            self.quant_chunks = True
+            if self.kv_quant == "fp8":
+                self._attach(self._fmt, self._desc)
         return self if self.kv_quant == "fp8" else self.quantize("fp8")
 
     def quantize_mxfp4(self):
@@ -524,6 +539,9 @@ class KVBank:
         self._fmt, self._desc_ref = fmt, () if fmt is None else (C.byref(self._desc),)
         self._calls = {(batch, what): getattr(self.lib, _lib.step_call_name(rows, batch, what))
                        for batch in (False, True) for what in _lib.STEP_CALLS}
+        if rows == "kv8" and self.quant_chunks:      # (the kv8 calls that also take q_len > 1; q_len == 1 resolves as the kv8 call)
+            for what in _lib.STEP_CALLS:
+                self._calls[False, what] = getattr(self.lib, _lib.KV8_CHUNK_CALLS[what])
         self._check_fn, self._info_fn, self._ws_fn, self._attend_fn = (self._calls[False, what] for what in _lib.STEP_CALLS)
         if self.long_rows:      # (16-bit rows: __init__ and quantize() refuse every other format) the long family, same signatures
             self._check_fn, self._info_fn, self._ws_fn, self._attend_fn = (getattr(self.lib, _lib.LONG_CALLS[what]) for what in _lib.STEP_CALLS)
@@ -1153,7 +1171,7 @@ class KVBank:
         96-row chunk step of the Llama2-7B shape: 66 us of a 124 us layer).  Decode steps and, since round 4, chunk steps."""
         d = self._defer
         n = q.shape[2]
-        self._quant_refuse(n > 1, "a chunk step (q_len > 1)")
+        self._chunk_refuse(n)
         self._refuse_ragged(layer, 1)
         t = self.n_slots[layer] + n
         if self._slot_rows[layer]:
@@ -1205,7 +1223,7 @@ class KVBank:
         """The split count the library plans for ``st`` (a capped bank: by its own family — a capped chunk step is tiled in narrower
         blocks than the plain call's; a pooled step: by the pooled family)."""
         fam = fam or self._family()
-        if self.logit_cap is not None or self.sinks is not None or self.windows is not None or fam[1] is not self._info_fn:
+        if self.logit_cap is not None or self.sinks is not None or self.windows is not None or self.quant_chunks or fam[1] is not self._info_fn:
             info = (C.c_int32 * 10)()
             check(fam[1](C.byref(self._bank), C.byref(st), self._dt, *fam[4], info, 10), fam[1].__name__)
             return int(info[0])
@@ -1267,7 +1285,7 @@ class KVBank:
                 return self._attend_heads(plan, q, k_new, v_new, layer_begin, out), None
             return self._attend_deferred(plan, q, k_new, v_new, layer_begin, out, q_pos), None
         lc, _, n, _ = q.shape
-        self._quant_refuse(n > 1, "a chunk step (q_len > 1)")
+        self._chunk_refuse(n)
         if self._ragged(layer_begin, lc):
             if not (n == 1 and plan.phase == "decode" and phases == 0 and not overlap_scorer and plan.head_adaptive is None and plan.pool == 1
                     and not plan.streaming):

@@ -311,6 +311,32 @@ int ekv_kv8_step_attend(const ekv_bank *bank, const ekv_step *step, int32_t dtyp
                         const void *k_new, const void *v_new, void *out, int32_t *evict_ids, const float *rope_cos,
                         const float *rope_sin, void *workspace, size_t workspace_bytes, void *stream);
 
+/* Chunk steps on a kv8 bank ("kv8 chunks"; ABI 8, additive): the ekv_kv8_step_* signatures, for steps of any q_len >= 1.  The calls
+ * above keep refusing q_len > 1; these accept it, so a kv8 bank can be prefilled in place (strided chunk steps and the dense prefix,
+ * causal q_len = r_idx on an empty bank) and can take prompt chunks after decode steps.
+ *
+ * q_len == 1: resolved as ekv_kv8_step_* resolves it, field for field.  q_len > 1: planned as the 16-bit step of the same shape under
+ * the narrow-block rule of the capped calls — the 16x16x32 geometry in its one-tile build, blocks of at most 32 GQA-folded rows
+ * (larger q_len: several blocks), ONE pass with online softmax and exported raw logits (ekv_step.two_pass is not consulted), key-range
+ * splits with (m, l, o) partials, the in-kernel fold and the scorer as the kernel's tail where the 16-bit kernel has them, else the
+ * generic scorer — and run on the FP8 chunk kernel of ekv_attn_chunk8.inc: code rows are gathered through the slot map 16 elements per
+ * lane with their row scales, widened exactly to the 16-bit element type, logit = (q . codes) * k_scale[row] / sm_div in that
+ * operation order (the decode stream's), V widened exactly and p * v_scale[row] multiplied in as a 16-bit pair hi + lo.  The q_len rows a step appends arrive 16-bit in
+ * k_new / v_new; the kernel quantises them by the normative rule above, stores codes and scales into the rows the slot map names
+ * (exactly one workgroup stores a row: the one whose query block holds the row's query and whose key range holds its position) and
+ * attends them AS QUANTISED, causal mask included, every workgroup quantising the new rows it attends in registers — so the bank's
+ * contents alone determine the step, as for decode steps.
+ *
+ * EKV_E_UNSUPPORTED from the dry run, nothing launched and 0 workspace bytes (q_len > 1): rope_on_read, head_dim other than 64 / 128,
+ * a GQA factor above 32, slot-indexed score rows (EKV_PHASE_SLOT_ROWS).  There is no batch, capped, sink, window, pooled, adaptive,
+ * heads or long form of these calls.  EKV_E_ARG as for ekv_kv8_step_*. */
+int ekv_kv8_chunk_step_check(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const ekv_kv8 *kv8);
+int ekv_kv8_chunk_step_info(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const ekv_kv8 *kv8, int32_t *info, int32_t n_info);
+size_t ekv_kv8_chunk_workspace_bytes(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const ekv_kv8 *kv8);
+int ekv_kv8_chunk_step_attend(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const ekv_kv8 *kv8, const void *q,
+                              const void *k_new, const void *v_new, void *out, int32_t *evict_ids, const float *rope_cos,
+                              const float *rope_sin, void *workspace, size_t workspace_bytes, void *stream);
+
 /* MXFP4 K/V storage with block scales ("kv4"; ABI 8, additive; head_dim 128).  A bank's K/V rows may be held as
  *
  *   k_codes, v_codes   uint8 [n_layers][n_kv_heads][cap][head_dim / 2]    two e2m1 codes per byte: element 2i in the low nibble
