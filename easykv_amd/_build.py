@@ -83,6 +83,8 @@ FAMILIES = {
         "ekv_attn_decode.inc", f"ekv_attn_decode_d{d}_heads" + _tags(elem), _on(elem) + [f"-DEKV_D={d}", "-DEKV_ROPE=false", "-DEKV_HEADS=1"]),
     # chunk steps over FP8 code rows: ekv_chunk8_kernel, a source of its own
     "EKV_CHUNK_CODES": lambda elem, d: ("ekv_attn_chunk8.inc", f"ekv_attn_chunk8_d{d}" + _tags(elem), _on(elem) + [f"-DEKV_D={d}"]),
+    # MXFP4 rows at GQA factors up to 16: ekv_attn_decode_mxg_kernel, a source of its own
+    "EKV_DECODE_MXG": lambda elem, d: ("ekv_attn_decode_mxg.inc", f"ekv_attn_decode_mxg_d{d}" + _tags(elem), _on(elem) + [f"-DEKV_D={d}"]),
     "EKV_DECODE_SCORE_HEADS": lambda elem: ("ekv_decode_score.inc", "ekv_decode_score_heads" + _tags(elem), _on(elem) + ["-DEKV_HEADS=1"]),
 }
 
@@ -95,8 +97,9 @@ def instances(manifest=None):
 
 
 # Translation units of the library's own added after the object list was recorded (objects() returns exactly the recorded names, and
-# later_objects() exactly one object per line of its manifest): the launch code of the FP8 chunk kernel.  Compiled and linked like the rest.
-LATER_SOURCES = ("ekv_attn_chunk8.hip",)
+# later_objects() exactly one object per line of its manifest): the launch code of the FP8 chunk kernel and of the MFMA decode kernel for
+# MXFP4 rows.  Compiled and linked like the rest.
+LATER_SOURCES = ("ekv_attn_chunk8.hip", "ekv_attn_decode_mxg.hip")
 
 
 def sources():
@@ -147,7 +150,7 @@ def later_instances():
 
 
 def later_objects():
-    """(object name, hipcc arguments) of the instances of ekv_instances_later.def (the kv84 decode instances, the kv164 ones, the long-row scorer, head_dim 256, the soft-capped instances, the sink instances, the window instances, the pooled scorer, the adaptive scorer and its allot kernel, the heads instances, the FP8 chunk kernel)."""
+    """(object name, hipcc arguments) of the instances of ekv_instances_later.def (the kv84 decode instances, the kv164 ones, the long-row scorer, head_dim 256, the soft-capped instances, the sink instances, the window instances, the pooled scorer, the adaptive scorer and its allot kernel, the heads instances, the FP8 chunk kernel, the MFMA decode kernel for MXFP4 rows)."""
     return _instance_objects(later_instances())
 
 

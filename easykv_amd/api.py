@@ -40,7 +40,7 @@ from typing import List, Optional
 import torch
 
 from . import _lib
-from .engine import CAPPED_HEAD_DIMS, PLAIN_KEYS_HEAD_DIMS, SINK_HEAD_DIMS, WINDOW_HEAD_DIM, KVBank, KVBankBatch, StepPlan, row_format
+from .engine import CAPPED_HEAD_DIMS, GROUPED_MAX_REP, PLAIN_KEYS_HEAD_DIMS, SINK_HEAD_DIMS, WINDOW_HEAD_DIM, KVBank, KVBankBatch, StepPlan, row_format
 
 KNOWN_POLICIES = ("roco", "h2o_head", "tova", "recency", "random", "full")
 SCORED = ("roco", "h2o_head", "tova")
@@ -497,7 +497,17 @@ class _Run:
         if self.kv_quant_prefill and kv_quant != "fp8":
             raise ValueError(f"generation_config['kv_quant_prefill'] = True needs generation_config['kv_quant'] = 'fp8' (not {kv_quant!r}): FP8 rows are "
                              "the only quantised rows with a chunk step")
-        kvq = f"generation_config['kv_quant'] = {kv_quant!r}" + (" with generation_config['kv_quant_prefill'] = True" if self.kv_quant_prefill else "")
+        # extension key: False (default) or True, with kv_quant='mxfp4' only — the bank is converted by KVBank.quantize_mxfp4(grouped=True)
+        # and its decode steps go to the grouped calls (include/easykv_hip.h, "kv4 gqa"): GQA factors up to 16, factors
+        # above 4 on the MFMA decode kernel.  Same prefill, same single conversion at the prefill -> decode boundary
+        self.kv_quant_grouped = cfg.get("kv_quant_grouped", False)
+        if self.kv_quant_grouped not in (False, True):
+            raise ValueError(f"generation_config['kv_quant_grouped'] must be False or True, not {self.kv_quant_grouped!r}")
+        if self.kv_quant_grouped and kv_quant != "mxfp4":
+            raise ValueError(f"generation_config['kv_quant_grouped'] = True needs generation_config['kv_quant'] = 'mxfp4' (not {kv_quant!r}): MXFP4 rows are "
+                             "the only rows with a grouped decode step")
+        kvq = f"generation_config['kv_quant'] = {kv_quant!r}" + (" with generation_config['kv_quant_prefill'] = True" if self.kv_quant_prefill else "") + (
+            " with generation_config['kv_quant_grouped'] = True" if self.kv_quant_grouped else "")
         shard = getattr(model, "layer_shard", None)
         if shard is not None and shard.world == 1:
             shard = None
@@ -525,7 +535,10 @@ class _Run:
             raise ValueError(f"{kvq} needs head_dim {' or '.join(map(str, fmt['head_dims']))} (this model: {d})")
         if self.kv_quant_prefill and hq // hkv > 32:      # (a chunk step on FP8 rows runs blocks of at most 32 GQA-folded rows: before any bank exists)
             raise ValueError(f"{kvq} needs a GQA factor of at most 32 (this model: {hq // hkv}): a chunk step on FP8 rows folds a query's heads into one block")
-        if fmt is not None and fmt["max_rep"] is not None and hq // hkv > fmt["max_rep"]:
+        if self.kv_quant_grouped:      # (the grouped calls: the query heads of a KV head are one 16-column MFMA tile)
+            if hq // hkv > GROUPED_MAX_REP:
+                raise ValueError(f"{kvq} needs a GQA factor of at most {GROUPED_MAX_REP} (this model: {hq // hkv})")
+        elif fmt is not None and fmt["max_rep"] is not None and hq // hkv > fmt["max_rep"]:
             raise ValueError(f"{kvq} needs a GQA factor of at most {fmt['max_rep']} (this model: {hq // hkv})")
         # the model's own attention arithmetic, read where head_dim is: attn_logit_softcapping (Gemma 2; absent or None = off) becomes the
         # cache's logit_cap, query_pre_attn_scalar (Gemma 2 / 3; absent = head_dim) its softmax scale qpas ** -0.5 (None = 1 / sqrt(head_dim))
@@ -1108,7 +1121,9 @@ def generate(self, input_ids, generation_config, kv_mode="encoding", stride=1, r
     else:
         pre = _prefill(run, input_ids, kv_mode)
         cache = pre.cache
-        if run.kv_quant and not run.kv_quant_prefill:      # prefill -> decode boundary: the decode steps run on quantised rows (kv_quant_prefill: they are already)
+        if run.kv_quant_grouped:      # prefill -> decode boundary: MXFP4 rows behind the grouped calls
+            cache.bank.quantize_mxfp4(grouped=True)
+        elif run.kv_quant and not run.kv_quant_prefill:      # prefill -> decode boundary: the decode steps run on quantised rows (kv_quant_prefill: they are already)
             cache.bank.quantize(run.kv_quant)
         out_ids, fed = _decode(run, pre, report_decoding_latency and pre.mode == "encoding")
         if pre.mode != "encoding":      # (encoding mode reports the cache the prefill left: printed there)
@@ -1148,6 +1163,9 @@ def generate_batch(self, input_ids_list, generation_config, kv_mode="encoding", 
         raise ValueError("generate_batch is not supported on a layer-sharded model (model.layer_shard)")
     if cfg.get("long_rows", False):
         raise ValueError("generate_batch: generation_config['long_rows'] has no batched decode step (the long-row scorer serves single sequences)")
+    if cfg.get("kv_quant_grouped", False):
+        raise ValueError("generate_batch: generation_config['kv_quant_grouped'] with generation_config['kv_quant'] = 'mxfp4' has no batched decode step "
+                         "(the grouped calls serve single sequences)")
     if cfg.get("kv_quant", None) == "mxfp4":
         raise ValueError("generate_batch: generation_config['kv_quant'] = 'mxfp4' has no batched decode step (use 'fp8' or None)")
     if getattr(self.config, "attn_logit_softcapping", None) is not None:

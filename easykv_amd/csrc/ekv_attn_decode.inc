@@ -204,6 +204,7 @@ __global__ void __launch_bounds__(256) ekv_attn_decode_kernel(const EkvAttnArgs 
   // of every layer of a decoder stack).  Protocol (MI355X_MICROARCH.md "inter-workgroup visibility"): sc1 partial stores,
   // every wave drains its stores, barrier, ONE agent-scope atomicAdd on the head's arrival counter (bank->arrive, zeroed by
   // ekv_bank_reset; the last arriver leaves it at zero again); the last arriver reads the partials with sc1 loads.
+  // (The same sequence stands in ekv_attn_decode_mxg.inc, the MFMA kernel for MXFP4 rows: a change here goes there too.)
   // (First version: a CAS loop on an epoch-tagged word in the workspace, so that nothing had to be zero-initialised: 17 splits
   // arriving together retried for 25 us.)
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");

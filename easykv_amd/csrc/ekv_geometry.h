@@ -250,6 +250,18 @@ constexpr int kChunk8EPL = 16;      // elements per 16-byte piece of a code row
 inline size_t ekv_chunk8_lds(int head_dim, int rows_per_split) {
   return ekv_chunk_kernel_lds(head_dim, 0, 1, false, 4, rows_per_split, true) + 2 * kChunkKT * sizeof(float);
 }
+// ---- MFMA decode kernel for MXFP4 rows (ekv_attn_decode_mxg.inc): slot entries of the key range | per wave a 32-key V tile of scaled
+// bf16 rows | per wave 64 exponent words | the appended row's codes and exponent words.  The slot entries are ALWAYS staged, so one CU's
+// 160 KB bound the positions of a split: kDecodeMxgMaxRows, a multiple of the decode tiling's 128-position unit.  resolve_call
+// (ekv_plan.cpp, "grouped") raises the split count of a step whose planned range is longer.
+constexpr int kDecodeMxgKT = 32;      // keys per wave step
+constexpr size_t kDecodeMxgVTile = (size_t)kDecodeMxgKT * (128 + kChunkPadH) * 2;
+inline EKV_HD size_t ekv_decode_mxg_lds(int rows_per_split) {
+  return ekv_align((size_t)rows_per_split * 4, 16) + 4 * kDecodeMxgVTile + 4 * 64 * 4 + 34 * 4 + 8;
+}
+constexpr int kDecodeMxgMaxRows = 31360;
+static_assert(kDecodeMxgMaxRows % 128 == 0 && (size_t)kDecodeMxgMaxRows * 4 + 4 * kDecodeMxgVTile + 4 * 64 * 4 + 34 * 4 + 8 <= 160 * 1024 &&
+              (size_t)(kDecodeMxgMaxRows + 128) * 4 + 4 * kDecodeMxgVTile + 4 * 64 * 4 + 34 * 4 + 8 > 160 * 1024, "the longest key range of the MFMA decode kernel fills one CU's LDS");
 // (16384: the rows an unsplit chunk workgroup may walk on plain keys, ekv_plan_step's max_rows — its slot entries live in LDS)
 static_assert((size_t)16384 * 4 + (size_t)2 * kChunkKT * (128 + kChunkPadH) * 2 + 2 * kChunkKT * 4 <= 160 * 1024, "the longest unsplit key range fits one CU's LDS");
 static_assert(kChunkKT * (128 / kChunk8EPL) % 256 == 0 && kChunkKT * (64 / kChunk8EPL) % 256 == 0, "a super-tile of code rows is whole pieces per thread of 256");

@@ -775,6 +775,7 @@ namespace {
 struct RowsRule {
   int32_t head_dims[2], max_rep;
 };
+constexpr int32_t kGroupedMaxRep = 16;      // a grouped kv4 call (ekv_kv4_gqa_*): the query heads of a KV head are the 16 columns of one MFMA tile
 const RowsRule kRowsRules[] = {/* kv16 */ {{0, 0}, 1 << 30}, /* kv8 */ {{64, 128}, 1 << 30}, /* kv4 */ {{128, 0}, 4}, /* kv6 */ {{128, 0}, 4}, /* kv84 */ {{128, 0}, 1 << 30}, /* kv164 */ {{128, 0}, 1 << 30}};
 }  // namespace
 bool ekv_rows_head_dim(EkvRows rows, int head_dim) {
@@ -989,12 +990,36 @@ int resolve_call(const EkvCall& c, EkvResolved* r) {
     r->env.two_pass = -1;
     r->step = &r->env;
   }
+  // Grouped calls on MXFP4 rows (ekv_kv4_gqa_*; include/easykv_hip.h, "kv4 gqa"), likewise stated once.  "Grouped" is a flag of a kv4 call,
+  // combined with nothing else (its entry points spell one sequence and no other variant).  With a GQA factor of at most 4 the call IS the
+  // kv4 call of the same step: return code, info fields, workspace, launches — refusals included.  With a factor of 5 .. 16 it plans as
+  // the 16-bit call of the same step with the one-launch kernel switched off — the whole-step form plans as phases = 1 | 2 of that step,
+  // the heads family's deviation; phased and deferred forms as they are — and EKV_RUN_DECODE runs ekv_attn_decode_mxg_kernel with ONE
+  // workgroup per (split, KV head, layer) for all query heads of the head (the 16-bit plan of a factor above 8 counts two query-head
+  // groups in that grid and nowhere else); fold, fast scorer, generic scorer and range compaction read logits and partials only and are
+  // the 16-bit instances.  One deviation from that plan: the kernel keeps the slot entries of its key range in LDS, so a plan whose range
+  // exceeds kDecodeMxgMaxRows positions (ekv_geometry.h) is planned again with the fewest splits that fit, ceil(T / kDecodeMxgMaxRows) —
+  // whatever n_split the caller asked for, as chunk steps are bounded by max_rows.  Refused with zero launches and zero bytes
+  // (EKV_E_UNSUPPORTED): q_len > 1, RoPE-on-read, a head_dim other than 128, a factor above 16, and slot-indexed score rows (no check of
+  // this rule's own: with phases != 0 the 16-bit plan refuses them, they are the one-launch kernel's).  The family has no batched entry
+  // point.  Argument errors are the kv4 call's, missing planes included.
+  const bool mxg = c.grouped && c.rows == EKV_ROWS_kv4 && !c.batch && bank && bank->n_kv_heads > 0 && bank->n_q_heads / bank->n_kv_heads > 4 && c.step != nullptr;
+  if (mxg) {
+    r->env = *c.step;
+    if ((r->env.phases & ~(EKV_PHASE_SLOT_ROWS | EKV_PHASE_SLOT_TAIL_OK)) == 0) r->env.phases |= 1 | 2;
+    r->step = &r->env;
+  }
   const int variants = (c.long_rows ? 1 : 0) + (c.capped ? 1 : 0) + (c.sink || c.window ? 1 : 0) + (c.pooled ? 1 : 0) + (c.adaptive ? 1 : 0) + (c.heads ? 1 : 0);
   const bool sinkish = c.sink || c.window;
-  const int rc = (variants && (quant || c.batch || variants > 1))
+  int rc = (variants && (quant || c.batch || variants > 1))
                      ? EKV_E_UNSUPPORTED
                      : ekv_plan_step(bank, r->step, P, c.long_rows, c.capped || sinkish || chunk8, quant || c.batch || sinkish || c.capped || c.heads, c.pooled || c.adaptive);
+  if (mxg && rc == EKV_OK && P->rows_per_split > kDecodeMxgMaxRows) {      // (the rule above: the kernel's LDS bounds a split's range)
+    r->env.n_split = (int32_t)(((i64)r->env.n_slots + kDecodeMxgMaxRows - 1) / kDecodeMxgMaxRows);
+    rc = ekv_plan_step(bank, r->step, P, false, false, true, false);
+  }
   P->heads = c.heads ? 1 : 0;
+  P->grouped = mxg ? 1 : 0;
   P->capped = c.capped ? 1 : 0;
   P->sink = c.sink ? 1 : 0;
   P->window = c.window ? 1 : 0;
@@ -1013,7 +1038,7 @@ int resolve_call(const EkvCall& c, EkvResolved* r) {
       P->bytes = plain.bytes, P->big_rows = plain.big_rows, P->key_rows = -1;
     }
     P->one_launch = P->n_launches = P->n_list = P->long_rows = P->long_tiles = 0;
-    if (c.batch || c.capped || sinkish || c.pooled || c.adaptive || c.heads || chunk8) P->bytes = 0;      // (nothing will run: ekv_batch_workspace_bytes of a refused table, ekv_cap_ / ekv_sink_ / ekv_pool_workspace_bytes of a refused step, is 0)
+    if (c.batch || c.capped || sinkish || c.pooled || c.adaptive || c.heads || chunk8 || mxg) P->bytes = 0;      // (nothing will run: ekv_batch_workspace_bytes of a refused table, ekv_cap_ / ekv_sink_ / ekv_pool_workspace_bytes of a refused step, is 0)
     return code;
   };
   const ekv_step* st = c.step;
@@ -1048,7 +1073,7 @@ int resolve_call(const EkvCall& c, EkvResolved* r) {
     }
   }
   if (quant && ((st->q_len != 1 && !chunk8) || st->rope_on_read || !ekv_rows_head_dim(c.rows, bank->head_dim) ||
-                bank->n_q_heads / bank->n_kv_heads > kRowsRules[c.rows].max_rep))
+                bank->n_q_heads / bank->n_kv_heads > (mxg ? kGroupedMaxRep : kRowsRules[c.rows].max_rep)))
     return refuse(EKV_E_UNSUPPORTED);
   if (chunk8) {      // (its LDS fits one CU under the tiling's row bound: ekv_geometry.h states it)
     if (P->wide || P->two_pass) return refuse(EKV_E_UNSUPPORTED);

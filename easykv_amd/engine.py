@@ -96,11 +96,18 @@ def row_format(kind, what="kv_quant"):
     return ROW_FORMATS.get(kind)
 
 
-def _check_row_shape(fmt, head_dim, rep):
-    """EkvError unless the decode kernels of ``fmt`` are built for this head_dim and GQA factor."""
+# GQA factors a grouped MXFP4 bank takes (KVBank.quantize_mxfp4(grouped=True): the MFMA decode kernel, one 16-column tile of query heads)
+GROUPED_MAX_REP = 16
+
+
+def _check_row_shape(fmt, head_dim, rep, grouped=False):
+    """EkvError unless the decode kernels of ``fmt`` are built for this head_dim and GQA factor (``grouped``: the grouped MXFP4 calls)."""
     if head_dim not in fmt["head_dims"]:
         raise _lib.EkvError(f"{fmt['method']}(): {fmt['label']} rows are built for head_dim {' and '.join(map(str, fmt['head_dims']))}, not {head_dim}")
-    if fmt["max_rep"] is not None and rep > fmt["max_rep"]:
+    if grouped:
+        if rep > GROUPED_MAX_REP:
+            raise _lib.EkvError(f"{fmt['method']}(grouped=True): {fmt['label']} rows are built for GQA factors up to {GROUPED_MAX_REP}, not {rep}")
+    elif fmt["max_rep"] is not None and rep > fmt["max_rep"]:
         raise _lib.EkvError(f"{fmt['method']}(): {fmt['label']} rows are built for GQA factors up to {fmt['max_rep']}, not {rep}")
 
 
@@ -167,6 +174,7 @@ class KVBank:
     # library's default, 0 = every K/V load non-temporal — what a caller sets whose process streams more than the Infinity Cache holds
     # between two steps (easykv_amd.api: a model's weights)
     resident_bytes = None
+    kv_grouped = False   # quantize_mxfp4(grouped=True): the MXFP4 bank steps through the grouped calls (GQA factors up to 16)
     kv_quant = None      # quantize(): "fp8" / "mxfp4" / "mxfp6" / "fp8_mxfp4" / "k16_mxfp4" (ROW_FORMATS; _fmt is the entry, _desc the descriptor of its planes)
 
     long_rows = False    # KVBank(..., long_rows=True): the steps go to the long-row family (ekv_long_*), set per bank by __init__
@@ -463,7 +471,7 @@ class KVBank:
                                 f"for {fmt['label']} rows: {fmt['label']} rows have no long form")
         if self._fmt is not None:
             raise _lib.EkvError(f"{m}: the bank's rows are quantised already ({self._fmt['label']} already: kv_quant={self.kv_quant!r})")
-        _check_row_shape(fmt, self.head_dim, self.n_q_heads // self.n_kv_heads)
+        _check_row_shape(fmt, self.head_dim, self.n_q_heads // self.n_kv_heads, self.kv_grouped and kind == "mxfp4")
         if self.rope_cos is not None:
             raise _lib.EkvError(f"{m}: a RoPE-on-read (streaming) bank keeps un-rotated keys, which the {fmt['label']} decode kernels do not rotate")
         if self._defer is not None and self._defer["pending"]:
@@ -492,10 +500,18 @@ class KVBank:
                 self._attach(self._fmt, self._desc)
         return self if self.kv_quant == "fp8" else self.quantize("fp8")
 
-    def quantize_mxfp4(self):
+    def quantize_mxfp4(self, grouped=False):
         """:meth:`quantize` to MXFP4 K/V rows: e2m1 codes, two per byte, with one E8M0 exponent per 32-element block (``k4`` / ``v4``
-        / ``k_exp`` / ``v_exp``), head_dim 128 and GQA factors up to 4."""
-        return self.quantize("mxfp4")
+        / ``k_exp`` / ``v_exp``), head_dim 128 and GQA factors up to 4.
+        ``grouped=True``: the same conversion and planes, GQA factors up to 16, and ``attend`` / ``step_info`` / ``step_plan`` / the
+        workspace query / the deferred form go to the grouped calls (include/easykv_hip.h, "kv4 gqa"): a factor of at most 4 steps
+        exactly as without the argument; factors 5 .. 16 run the split path on the MFMA decode kernel (no one-launch step)."""
+        was, self.kv_grouped = self.kv_grouped, bool(grouped)      # (read by quantize(): the GQA check, and the calls _attach resolves)
+        try:
+            return self.quantize("mxfp4")
+        except Exception:
+            self.kv_grouped = was      # (a refused conversion leaves the bank, its flag and its calls as they were)
+            raise
 
     def quantize_mxfp6(self):
         """:meth:`quantize` to MXFP6 K/V rows: e2m3 codes, 32 per 24-byte block, with one E8M0 exponent per 32-element block (``k6`` /
@@ -539,6 +555,9 @@ class KVBank:
         self._fmt, self._desc_ref = fmt, () if fmt is None else (C.byref(self._desc),)
         self._calls = {(batch, what): getattr(self.lib, _lib.step_call_name(rows, batch, what))
                        for batch in (False, True) for what in _lib.STEP_CALLS}
+        if rows == "kv4" and self.kv_grouped:      # (the kv4 calls that also take GQA factors 5 .. 16; a factor <= 4 resolves as the kv4 call)
+            for what in _lib.STEP_CALLS:
+                self._calls[False, what] = getattr(self.lib, _lib.KV4_GQA_CALLS[what])
         if rows == "kv8" and self.quant_chunks:      # (the kv8 calls that also take q_len > 1; q_len == 1 resolves as the kv8 call)
             for what in _lib.STEP_CALLS:
                 self._calls[False, what] = getattr(self.lib, _lib.KV8_CHUNK_CALLS[what])
@@ -1223,7 +1242,7 @@ class KVBank:
         """The split count the library plans for ``st`` (a capped bank: by its own family — a capped chunk step is tiled in narrower
         blocks than the plain call's; a pooled step: by the pooled family)."""
         fam = fam or self._family()
-        if self.logit_cap is not None or self.sinks is not None or self.windows is not None or self.quant_chunks or fam[1] is not self._info_fn:
+        if self.logit_cap is not None or self.sinks is not None or self.windows is not None or self.quant_chunks or self.kv_grouped or fam[1] is not self._info_fn:
             info = (C.c_int32 * 10)()
             check(fam[1](C.byref(self._bank), C.byref(st), self._dt, *fam[4], info, 10), fam[1].__name__)
             return int(info[0])
