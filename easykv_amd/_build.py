@@ -85,6 +85,8 @@ FAMILIES = {
     "EKV_CHUNK_CODES": lambda elem, d: ("ekv_attn_chunk8.inc", f"ekv_attn_chunk8_d{d}" + _tags(elem), _on(elem) + [f"-DEKV_D={d}"]),
     # MXFP4 rows at GQA factors up to 16: ekv_attn_decode_mxg_kernel, a source of its own
     "EKV_DECODE_MXG": lambda elem, d: ("ekv_attn_decode_mxg.inc", f"ekv_attn_decode_mxg_d{d}" + _tags(elem), _on(elem) + [f"-DEKV_D={d}"]),
+    # FP8 rows at GQA factors up to 16: ekv_attn_decode_g8_kernel, a source of its own
+    "EKV_DECODE_G8": lambda elem, d: ("ekv_attn_decode_g8.inc", f"ekv_attn_decode_g8_d{d}" + _tags(elem), _on(elem) + [f"-DEKV_D={d}"]),
     "EKV_DECODE_SCORE_HEADS": lambda elem: ("ekv_decode_score.inc", "ekv_decode_score_heads" + _tags(elem), _on(elem) + ["-DEKV_HEADS=1"]),
 }
 
@@ -92,14 +94,14 @@ FAMILIES = {
 def instances(manifest=None):
     """(family, words) of every line of the manifest, in order."""
     with open(manifest or MANIFEST) as f:
-        found = re.findall(r"^(EKV_[A-Z_]+)\(([^)]*)\)", f.read(), re.M)
+        found = re.findall(r"^(EKV_[A-Z0-9_]+)\(([^)]*)\)", f.read(), re.M)      # (a family word may hold a digit: EKV_DECODE_G8)
     return [(fam, tuple(w.strip() for w in args.split(","))) for fam, args in found]
 
 
 # Translation units of the library's own added after the object list was recorded (objects() returns exactly the recorded names, and
-# later_objects() exactly one object per line of its manifest): the launch code of the FP8 chunk kernel and of the MFMA decode kernel for
-# MXFP4 rows.  Compiled and linked like the rest.
-LATER_SOURCES = ("ekv_attn_chunk8.hip", "ekv_attn_decode_mxg.hip")
+# later_objects() exactly one object per line of its manifest): the launch code of the FP8 chunk kernel and of the MFMA decode kernels for
+# MXFP4 and for FP8 rows.  Compiled and linked like the rest.
+LATER_SOURCES = ("ekv_attn_chunk8.hip", "ekv_attn_decode_mxg.hip", "ekv_attn_decode_g8.hip")
 
 
 def sources():
@@ -150,7 +152,7 @@ def later_instances():
 
 
 def later_objects():
-    """(object name, hipcc arguments) of the instances of ekv_instances_later.def (the kv84 decode instances, the kv164 ones, the long-row scorer, head_dim 256, the soft-capped instances, the sink instances, the window instances, the pooled scorer, the adaptive scorer and its allot kernel, the heads instances, the FP8 chunk kernel, the MFMA decode kernel for MXFP4 rows)."""
+    """(object name, hipcc arguments) of the instances of ekv_instances_later.def (the kv84 decode instances, the kv164 ones, the long-row scorer, head_dim 256, the soft-capped instances, the sink instances, the window instances, the pooled scorer, the adaptive scorer and its allot kernel, the heads instances, the FP8 chunk kernel, the MFMA decode kernels for MXFP4 and FP8 rows)."""
     return _instance_objects(later_instances())
 
 

@@ -72,6 +72,9 @@ EXPORTS += tuple(KV8_CHUNK_CALLS[what] for what in STEP_CALLS)
 # MXFP4 rows at GQA factors up to 16 (include/easykv_hip.h, "kv4 gqa"): the signatures of the kv4 calls; one sequence
 KV4_GQA_CALLS = {what: "ekv_kv4_gqa_" + what for what in STEP_CALLS}
 EXPORTS += tuple(KV4_GQA_CALLS[what] for what in STEP_CALLS)
+# FP8 rows at GQA factors up to 16 on the MFMA decode kernel (include/easykv_hip.h, "kv8 gqa"): the signatures of the kv8 calls; one sequence
+KV8_GQA_CALLS = {what: "ekv_kv8_gqa_" + what for what in STEP_CALLS}
+EXPORTS += tuple(KV8_GQA_CALLS[what] for what in STEP_CALLS)
 
 
 class Bank(C.Structure):
@@ -194,6 +197,7 @@ def load():
             tails["step_attend"] = [vp] * 8 + [C.c_size_t, vp]
             for what in STEP_CALLS:
                 getattr(lib, KV8_CHUNK_CALLS[what]).argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, C.POINTER(desc)] + tails[what]
+                getattr(lib, KV8_GQA_CALLS[what]).argtypes = [C.POINTER(Bank), C.POINTER(Step), i32, C.POINTER(desc)] + tails[what]      # (GQA factors up to 16 on the MFMA kernel: likewise)
         if rows == "kv4":      # (GQA factors up to 16 on MXFP4 rows: the uniform kv4 signatures)
             tails["step_attend"] = [vp] * 8 + [C.c_size_t, vp]
             for what in STEP_CALLS:

@@ -506,8 +506,21 @@ class _Run:
         if self.kv_quant_grouped and kv_quant != "mxfp4":
             raise ValueError(f"generation_config['kv_quant_grouped'] = True needs generation_config['kv_quant'] = 'mxfp4' (not {kv_quant!r}): MXFP4 rows are "
                              "the only rows with a grouped decode step")
+        # extension key: False (default) or True, with kv_quant='fp8' only — the FP8 route to the same thing, under a key of its own (the
+        # key above keeps its meaning and its message): the bank is converted by KVBank.quantize_fp8(grouped=True) and its decode steps go
+        # to the grouped calls of FP8 rows (include/easykv_hip.h, "kv8 gqa").  Decode steps only: not with kv_quant_prefill
+        self.kv_quant_gqa = cfg.get("kv_quant_gqa", False)
+        if self.kv_quant_gqa not in (False, True):
+            raise ValueError(f"generation_config['kv_quant_gqa'] must be False or True, not {self.kv_quant_gqa!r}")
+        if self.kv_quant_gqa and kv_quant != "fp8":
+            raise ValueError(f"generation_config['kv_quant_gqa'] = True needs generation_config['kv_quant'] = 'fp8' (not {kv_quant!r}): it selects the "
+                             "grouped decode step of FP8 rows (MXFP4 rows: generation_config['kv_quant_grouped'])")
+        if self.kv_quant_gqa and self.kv_quant_prefill:
+            raise ValueError("generation_config['kv_quant_gqa'] = True with generation_config['kv_quant'] = 'fp8' and generation_config['kv_quant_prefill'] "
+                             "= True: the grouped calls take decode steps only and do not combine with chunk steps on FP8 rows")
         kvq = f"generation_config['kv_quant'] = {kv_quant!r}" + (" with generation_config['kv_quant_prefill'] = True" if self.kv_quant_prefill else "") + (
-            " with generation_config['kv_quant_grouped'] = True" if self.kv_quant_grouped else "")
+            " with generation_config['kv_quant_grouped'] = True" if self.kv_quant_grouped else "") + (
+            " with generation_config['kv_quant_gqa'] = True" if self.kv_quant_gqa else "")
         shard = getattr(model, "layer_shard", None)
         if shard is not None and shard.world == 1:
             shard = None
@@ -535,7 +548,7 @@ class _Run:
             raise ValueError(f"{kvq} needs head_dim {' or '.join(map(str, fmt['head_dims']))} (this model: {d})")
         if self.kv_quant_prefill and hq // hkv > 32:      # (a chunk step on FP8 rows runs blocks of at most 32 GQA-folded rows: before any bank exists)
             raise ValueError(f"{kvq} needs a GQA factor of at most 32 (this model: {hq // hkv}): a chunk step on FP8 rows folds a query's heads into one block")
-        if self.kv_quant_grouped:      # (the grouped calls: the query heads of a KV head are one 16-column MFMA tile)
+        if self.kv_quant_grouped or self.kv_quant_gqa:      # (the grouped calls: the query heads of a KV head are one 16-column MFMA tile)
             if hq // hkv > GROUPED_MAX_REP:
                 raise ValueError(f"{kvq} needs a GQA factor of at most {GROUPED_MAX_REP} (this model: {hq // hkv})")
         elif fmt is not None and fmt["max_rep"] is not None and hq // hkv > fmt["max_rep"]:
@@ -1123,6 +1136,8 @@ def generate(self, input_ids, generation_config, kv_mode="encoding", stride=1, r
         cache = pre.cache
         if run.kv_quant_grouped:      # prefill -> decode boundary: MXFP4 rows behind the grouped calls
             cache.bank.quantize_mxfp4(grouped=True)
+        elif run.kv_quant_gqa:      # ... FP8 rows behind theirs
+            cache.bank.quantize_fp8(grouped=True)
         elif run.kv_quant and not run.kv_quant_prefill:      # prefill -> decode boundary: the decode steps run on quantised rows (kv_quant_prefill: they are already)
             cache.bank.quantize(run.kv_quant)
         out_ids, fed = _decode(run, pre, report_decoding_latency and pre.mode == "encoding")
@@ -1165,6 +1180,9 @@ def generate_batch(self, input_ids_list, generation_config, kv_mode="encoding", 
         raise ValueError("generate_batch: generation_config['long_rows'] has no batched decode step (the long-row scorer serves single sequences)")
     if cfg.get("kv_quant_grouped", False):
         raise ValueError("generate_batch: generation_config['kv_quant_grouped'] with generation_config['kv_quant'] = 'mxfp4' has no batched decode step "
+                         "(the grouped calls serve single sequences)")
+    if cfg.get("kv_quant_gqa", False):
+        raise ValueError("generate_batch: generation_config['kv_quant_gqa'] with generation_config['kv_quant'] = 'fp8' has no batched decode step "
                          "(the grouped calls serve single sequences)")
     if cfg.get("kv_quant", None) == "mxfp4":
         raise ValueError("generate_batch: generation_config['kv_quant'] = 'mxfp4' has no batched decode step (use 'fp8' or None)")

@@ -127,7 +127,8 @@ static int call_attend(const EkvCall& c, const void* q, const void* k_new, const
       case EKV_RUN_CHUNK_LDS: e = ekv_launch_chunk_lds(aa, sa, D, lc, s, bf16); break;
       case EKV_RUN_RESIDENT: e = ekv_launch_attn_resident(aa, sa, lc, s, bf16); break;
       case EKV_RUN_DECODE:
-        e = P.grouped ? ekv_launch_attn_decode_mxg(aa, D, lc, s, bf16)      // (a grouped kv4 plan of GQA factor 5 .. 16: the MFMA kernel)
+        e = P.grouped && rows == EKV_ROWS_kv8 ? ekv_launch_attn_decode_g8(aa, D, lc, s, bf16)      // (a grouped kv8 plan of GQA factor 5 .. 16: the MFMA kernel for FP8 rows)
+          : P.grouped ? ekv_launch_attn_decode_mxg(aa, D, lc, s, bf16)      // (a grouped kv4 plan of GQA factor 5 .. 16: the MFMA kernel)
           : heads ? ekv_launch_attn_decode_heads(aa, hd, D, lc, s, bf16)
           : window ? ekv_launch_attn_decode_win(aa, sinks, win, D, lc, s, bf16)
           : sinks ? ekv_launch_attn_decode_sink(aa, sinks, D, lc, s, bf16) : ekv_launch_attn_decode(aa, tb, D, lc, s, bf16, rows, capped);
@@ -371,6 +372,20 @@ int ekv_batch_step_attend(const ekv_bank* bank, const ekv_step* st, int32_t dtyp
                           const void* k_new, const void* v_new, void* out, int32_t* evict_ids, void* workspace, size_t workspace_bytes,
                           void* stream) {
   return call_attend(batch_call(bank, st, dtype, seqs, n_seq), q, k_new, v_new, out, evict_ids, nullptr, nullptr, workspace, workspace_bytes, stream);
+}
+
+// FP8 rows at GQA factors up to 16 (include/easykv_hip.h, "kv8 gqa"): the kv8 calls, the MFMA decode kernel behind factors 5 .. 16
+int ekv_kv8_gqa_step_check(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_kv8* q8) { return call_check(kv8_gqa_call(bank, st, dtype, q8)); }
+int ekv_kv8_gqa_step_info(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_kv8* q8, int32_t* info, int32_t n_info) {
+  return call_info(kv8_gqa_call(bank, st, dtype, q8), info, n_info);
+}
+size_t ekv_kv8_gqa_workspace_bytes(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_kv8* q8) {
+  return call_workspace_bytes(kv8_gqa_call(bank, st, dtype, q8));
+}
+int ekv_kv8_gqa_step_attend(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_kv8* q8, const void* q, const void* k_new,
+                            const void* v_new, void* out, int32_t* evict_ids, const float* rope_cos, const float* rope_sin, void* workspace,
+                            size_t workspace_bytes, void* stream) {
+  return call_attend(kv8_gqa_call(bank, st, dtype, q8), q, k_new, v_new, out, evict_ids, rope_cos, rope_sin, workspace, workspace_bytes, stream);
 }
 
 // batched decode steps on a kv8 bank (include/easykv_hip.h, "kv8 batches")

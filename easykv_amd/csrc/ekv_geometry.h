@@ -262,6 +262,19 @@ inline EKV_HD size_t ekv_decode_mxg_lds(int rows_per_split) {
 constexpr int kDecodeMxgMaxRows = 31360;
 static_assert(kDecodeMxgMaxRows % 128 == 0 && (size_t)kDecodeMxgMaxRows * 4 + 4 * kDecodeMxgVTile + 4 * 64 * 4 + 34 * 4 + 8 <= 160 * 1024 &&
               (size_t)(kDecodeMxgMaxRows + 128) * 4 + 4 * kDecodeMxgVTile + 4 * 64 * 4 + 34 * 4 + 8 > 160 * 1024, "the longest key range of the MFMA decode kernel fills one CU's LDS");
+// ---- MFMA decode kernel for FP8 rows (ekv_attn_decode_g8.inc), head_dim 64 / 128: slot entries of the key range | per wave a 32-key V
+// tile of bf16 rows (codes widened with scale 1; the row scales travel in P) | per wave 64 fp32 row scales | the appended row's codes
+// (K, V: 128 bytes each).  As above the slot entries are always staged and one CU's 160 KB bound a split's positions:
+// ekv_decode_g8_max_rows(head_dim), the largest multiple of the decode tiling's 128-position unit that fits (31360 at head_dim 128, 35456
+// at 64).  resolve_call (ekv_plan.cpp, "grouped") raises the split count of a step whose planned range is longer.
+constexpr int kDecodeG8KT = 32;      // keys per wave step
+constexpr size_t kDecodeG8Fixed = 4 * 64 * 4 + 2 * 128;
+constexpr size_t ekv_decode_g8_vtile(int head_dim) { return (size_t)kDecodeG8KT * (head_dim + kChunkPadH) * 2; }
+inline EKV_HD size_t ekv_decode_g8_lds(int head_dim, int rows_per_split) {
+  return ekv_align((size_t)rows_per_split * 4, 16) + 4 * ekv_decode_g8_vtile(head_dim) + kDecodeG8Fixed;
+}
+constexpr int ekv_decode_g8_max_rows(int head_dim) { return (int)((160 * 1024 - 4 * ekv_decode_g8_vtile(head_dim) - kDecodeG8Fixed) / 4 / 128 * 128); }
+static_assert(ekv_decode_g8_max_rows(128) == 31360 && ekv_decode_g8_max_rows(64) == 35456, "the longest key range of the FP8 MFMA decode kernel fills one CU's LDS");
 // (16384: the rows an unsplit chunk workgroup may walk on plain keys, ekv_plan_step's max_rows — its slot entries live in LDS)
 static_assert((size_t)16384 * 4 + (size_t)2 * kChunkKT * (128 + kChunkPadH) * 2 + 2 * kChunkKT * 4 <= 160 * 1024, "the longest unsplit key range fits one CU's LDS");
 static_assert(kChunkKT * (128 / kChunk8EPL) % 256 == 0 && kChunkKT * (64 / kChunk8EPL) % 256 == 0, "a super-tile of code rows is whole pieces per thread of 256");

@@ -92,7 +92,8 @@ struct EkvStepPlan {
   int32_t adaptive;
   int64_t ada_keys, ada_cls;
   int32_t heads;        // an ekv_heads_* call: the plan of the envelope; EKV_RUN_DECODE / EKV_RUN_DECODE_SCORE run the EKV_HEADS instances
-  int32_t grouped;      // an ekv_kv4_gqa_* call of GQA factor 5 .. 16: EKV_RUN_DECODE runs the MFMA kernel for MXFP4 rows (ekv_launch_attn_decode_mxg)
+  int32_t grouped;      // an ekv_kv4_gqa_* call of GQA factor 5 .. 16: EKV_RUN_DECODE runs the MFMA kernel for MXFP4 rows (ekv_launch_attn_decode_mxg);
+                        // an ekv_kv8_gqa_* call of GQA factor 5 .. 16 (rows == kv8): the one for FP8 rows (ekv_launch_attn_decode_g8)
 };
 // The table of a batched decode step as the kernels' batch instances receive it: BY VALUE, behind the argument structs of the uniform
 // kernel (2304 bytes of the 4 KB a launch may carry).  Workgroup (head, entry ll) shadows the per-step fields of its argument structs
@@ -223,6 +224,10 @@ hipError_t ekv_launch_attn_chunk8(const EkvAttnArgs& a, int head_dim, int layer_
 // a.v_exp the exponent bytes, logits, partials and the in-kernel fold over a.arrive — with ONE workgroup per (split, KV head, layer) for
 // all of the head's query heads.  head_dim 128, plain keys.
 hipError_t ekv_launch_attn_decode_mxg(const EkvAttnArgs& a, int head_dim, int layer_count, hipStream_t s, bool bf16);
+// ... over FP8 code rows (the ekv_kv8_gqa_* calls; ekv_attn_decode_g8.inc, launch code in ekv_attn_decode_g8.hip): the contract of
+// ekv_launch_attn_decode's kv8 instances — a.k / a.v / a.k_w / a.v_w the code planes, a.k_scale / a.v_scale the row scales — with the
+// same ONE workgroup per (split, KV head, layer).  head_dim 64 / 128, plain keys.
+hipError_t ekv_launch_attn_decode_g8(const EkvAttnArgs& a, int head_dim, int layer_count, hipStream_t s, bool bf16);
 hipError_t ekv_launch_tova_headmean(const EkvScoreArgs& a, int layer_count, hipStream_t s);
 hipError_t ekv_launch_score_select(const EkvScoreArgs& a, int layer_count, hipStream_t s, bool bf16);
 hipError_t ekv_launch_decode_fused(const EkvAttnArgs& a, const EkvScoreArgs& sc, const EkvSeqTable* tb, int head_dim, int count, int nw,

@@ -1003,7 +1003,12 @@ int resolve_call(const EkvCall& c, EkvResolved* r) {
   // (EKV_E_UNSUPPORTED): q_len > 1, RoPE-on-read, a head_dim other than 128, a factor above 16, and slot-indexed score rows (no check of
   // this rule's own: with phases != 0 the 16-bit plan refuses them, they are the one-launch kernel's).  The family has no batched entry
   // point.  Argument errors are the kv4 call's, missing planes included.
-  const bool mxg = c.grouped && c.rows == EKV_ROWS_kv4 && !c.batch && bank && bank->n_kv_heads > 0 && bank->n_q_heads / bank->n_kv_heads > 4 && c.step != nullptr;
+  // Grouped calls on FP8 rows (ekv_kv8_gqa_*; "kv8 gqa") follow THE SAME rule with the kv8 call in the kv4 call's place and
+  // ekv_attn_decode_g8_kernel (ekv_attn_decode_g8.inc) behind EKV_RUN_DECODE: head_dim 64 / 128 (the kv8 call's), and a range bound per
+  // head_dim, ekv_decode_g8_max_rows (ekv_geometry.h).  "Grouped" does not combine with "chunks": no entry point spells both.
+  const bool g8 = c.grouped && c.rows == EKV_ROWS_kv8 && !c.chunks;
+  const int32_t grouped_rows = g8 ? ekv_decode_g8_max_rows(bank && bank->head_dim == 64 ? 64 : 128) : kDecodeMxgMaxRows;
+  const bool mxg = c.grouped && (c.rows == EKV_ROWS_kv4 || g8) && !c.batch && bank && bank->n_kv_heads > 0 && bank->n_q_heads / bank->n_kv_heads > 4 && c.step != nullptr;
   if (mxg) {
     r->env = *c.step;
     if ((r->env.phases & ~(EKV_PHASE_SLOT_ROWS | EKV_PHASE_SLOT_TAIL_OK)) == 0) r->env.phases |= 1 | 2;
@@ -1014,8 +1019,8 @@ int resolve_call(const EkvCall& c, EkvResolved* r) {
   int rc = (variants && (quant || c.batch || variants > 1))
                      ? EKV_E_UNSUPPORTED
                      : ekv_plan_step(bank, r->step, P, c.long_rows, c.capped || sinkish || chunk8, quant || c.batch || sinkish || c.capped || c.heads, c.pooled || c.adaptive);
-  if (mxg && rc == EKV_OK && P->rows_per_split > kDecodeMxgMaxRows) {      // (the rule above: the kernel's LDS bounds a split's range)
-    r->env.n_split = (int32_t)(((i64)r->env.n_slots + kDecodeMxgMaxRows - 1) / kDecodeMxgMaxRows);
+  if (mxg && rc == EKV_OK && P->rows_per_split > grouped_rows) {      // (the rule above: the kernel's LDS bounds a split's range)
+    r->env.n_split = (int32_t)(((i64)r->env.n_slots + grouped_rows - 1) / grouped_rows);
     rc = ekv_plan_step(bank, r->step, P, false, false, true, false);
   }
   P->heads = c.heads ? 1 : 0;

@@ -97,7 +97,7 @@ struct EkvCall {
   bool heads;              // an ekv_heads_* call: decode steps over KV heads of different lengths (16-bit rows, plain keys, no other variant)
   const ekv_heads* hd;     // ... its struct: NULL, a NULL pointer, grow < 0 or a host count out of range are argument errors; `rows` is never dereferenced here
   bool chunks;             // an ekv_kv8_chunk_* call: a kv8 call that also takes q_len > 1 (FP8 rows, one sequence, plain keys, no other variant)
-  bool grouped;            // an ekv_kv4_gqa_* call: a kv4 call that also takes GQA factors 5 .. 16, on the MFMA decode kernel (MXFP4 rows, one sequence, no other variant)
+  bool grouped;            // an ekv_kv4_gqa_* / ekv_kv8_gqa_* call: a kv4 / kv8 call that also takes GQA factors 5 .. 16, on the format's MFMA decode kernel (one sequence, no other variant)
 };
 inline EkvCall step_call(const ekv_bank* bank, const ekv_step* st, int32_t dtype) { return {bank, st, dtype, EKV_ROWS_kv16, {}, false, nullptr, 0}; }
 inline EkvCall batch_call(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_seq* seqs, int32_t n_seq) {
@@ -137,6 +137,11 @@ inline EkvCall kv4_call(const ekv_bank* bank, const ekv_step* st, int32_t dtype,
 }
 inline EkvCall kv4_gqa_call(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_kv4* q4) {
   EkvCall c = kv4_call(bank, st, dtype, q4);
+  c.grouped = true;
+  return c;
+}
+inline EkvCall kv8_gqa_call(const ekv_bank* bank, const ekv_step* st, int32_t dtype, const ekv_kv8* q8) {
+  EkvCall c = kv8_call(bank, st, dtype, q8);
   c.grouped = true;
   return c;
 }

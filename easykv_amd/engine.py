@@ -96,12 +96,13 @@ def row_format(kind, what="kv_quant"):
     return ROW_FORMATS.get(kind)
 
 
-# GQA factors a grouped MXFP4 bank takes (KVBank.quantize_mxfp4(grouped=True): the MFMA decode kernel, one 16-column tile of query heads)
+# GQA factors a grouped MXFP4 or FP8 bank takes (KVBank.quantize_mxfp4(grouped=True) / quantize_fp8(grouped=True): the MFMA decode
+# kernels, one 16-column tile of query heads)
 GROUPED_MAX_REP = 16
 
 
 def _check_row_shape(fmt, head_dim, rep, grouped=False):
-    """EkvError unless the decode kernels of ``fmt`` are built for this head_dim and GQA factor (``grouped``: the grouped MXFP4 calls)."""
+    """EkvError unless the decode kernels of ``fmt`` are built for this head_dim and GQA factor (``grouped``: the format's grouped calls)."""
     if head_dim not in fmt["head_dims"]:
         raise _lib.EkvError(f"{fmt['method']}(): {fmt['label']} rows are built for head_dim {' and '.join(map(str, fmt['head_dims']))}, not {head_dim}")
     if grouped:
@@ -174,7 +175,7 @@ class KVBank:
     # library's default, 0 = every K/V load non-temporal — what a caller sets whose process streams more than the Infinity Cache holds
     # between two steps (easykv_amd.api: a model's weights)
     resident_bytes = None
-    kv_grouped = False   # quantize_mxfp4(grouped=True): the MXFP4 bank steps through the grouped calls (GQA factors up to 16)
+    kv_grouped = False   # quantize_mxfp4(grouped=True) / quantize_fp8(grouped=True): the bank steps through its format's grouped calls (GQA factors up to 16)
     kv_quant = None      # quantize(): "fp8" / "mxfp4" / "mxfp6" / "fp8_mxfp4" / "k16_mxfp4" (ROW_FORMATS; _fmt is the entry, _desc the descriptor of its planes)
 
     long_rows = False    # KVBank(..., long_rows=True): the steps go to the long-row family (ekv_long_*), set per bank by __init__
@@ -471,7 +472,7 @@ class KVBank:
                                 f"for {fmt['label']} rows: {fmt['label']} rows have no long form")
         if self._fmt is not None:
             raise _lib.EkvError(f"{m}: the bank's rows are quantised already ({self._fmt['label']} already: kv_quant={self.kv_quant!r})")
-        _check_row_shape(fmt, self.head_dim, self.n_q_heads // self.n_kv_heads, self.kv_grouped and kind == "mxfp4")
+        _check_row_shape(fmt, self.head_dim, self.n_q_heads // self.n_kv_heads, self.kv_grouped and kind in ("mxfp4", "fp8"))
         if self.rope_cos is not None:
             raise _lib.EkvError(f"{m}: a RoPE-on-read (streaming) bank keeps un-rotated keys, which the {fmt['label']} decode kernels do not rotate")
         if self._defer is not None and self._defer["pending"]:
@@ -490,10 +491,31 @@ class KVBank:
         self._attach(fmt, desc)
         return self
 
-    def quantize_fp8(self, chunks=False):
+    def quantize_fp8(self, chunks=False, grouped=False):
         """:meth:`quantize` to FP8 (OCP e4m3fn) K/V rows with one fp32 scale per row (``k8`` / ``v8`` / ``k_scale`` / ``v_scale``),
         head_dim 64 and 128.  On a bank that holds FP8 rows already it does nothing.  ``chunks=True``: the bank takes chunk steps on
-        its FP8 rows from here on (``quant_chunks``, see the constructor)."""
+        its FP8 rows from here on (``quant_chunks``, see the constructor).
+        ``grouped=True``: the same conversion and planes, GQA factors up to 16, and ``attend`` / ``step_info`` / ``step_plan`` / the
+        workspace query / the deferred form go to the grouped calls (include/easykv_hip.h, "kv8 gqa"): a factor of at most 4 steps
+        exactly as without the argument; factors 5 .. 16 run the split path on the MFMA decode kernel for FP8 rows (no one-launch
+        step).  It does not combine with chunk steps."""
+        if grouped:
+            if chunks or self.quant_chunks:
+                raise _lib.EkvError("quantize_fp8(grouped=True): the grouped calls take decode steps only, and do not combine with chunk "
+                                    "steps on FP8 rows (chunks=True / quant_chunks)")
+            was, self.kv_grouped = self.kv_grouped, True      # (read by quantize(): the GQA check, and the calls _attach resolves)
+            try:
+                if self.kv_quant != "fp8":
+                    return self.quantize("fp8")
+                _check_row_shape(self._fmt, self.head_dim, self.n_q_heads // self.n_kv_heads, True)
+                self._attach(self._fmt, self._desc)
+                return self
+            except Exception:
+                self.kv_grouped = was      # (a refused conversion leaves the bank, its flag and its calls as they were)
+                raise
+        if chunks and self.kv_grouped:
+            raise _lib.EkvError("quantize_fp8(chunks=True): the bank steps through the grouped calls (quantize_fp8(grouped=True)), which take "
+                                "decode steps only")
         if chunks and not self.quant_chunks:
             self.quant_chunks = True
             if self.kv_quant == "fp8":
@@ -558,6 +580,9 @@ class KVBank:
         if rows == "kv4" and self.kv_grouped:      # (the kv4 calls that also take GQA factors 5 .. 16; a factor <= 4 resolves as the kv4 call)
             for what in _lib.STEP_CALLS:
                 self._calls[False, what] = getattr(self.lib, _lib.KV4_GQA_CALLS[what])
+        if rows == "kv8" and self.kv_grouped:      # (the kv8 calls that also take GQA factors 5 .. 16 on the MFMA kernel; a factor <= 4 resolves as the kv8 call)
+            for what in _lib.STEP_CALLS:
+                self._calls[False, what] = getattr(self.lib, _lib.KV8_GQA_CALLS[what])
         if rows == "kv8" and self.quant_chunks:      # (the kv8 calls that also take q_len > 1; q_len == 1 resolves as the kv8 call)
             for what in _lib.STEP_CALLS:
                 self._calls[False, what] = getattr(self.lib, _lib.KV8_CHUNK_CALLS[what])

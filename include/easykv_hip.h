@@ -337,6 +337,36 @@ int ekv_kv8_chunk_step_attend(const ekv_bank *bank, const ekv_step *step, int32_
                               const void *k_new, const void *v_new, void *out, int32_t *evict_ids, const float *rope_cos,
                               const float *rope_sin, void *workspace, size_t workspace_bytes, void *stream);
 
+/* Decode steps on a kv8 bank at GQA factors up to 16 on an MFMA kernel ("kv8 gqa"; ABI 8, additive): the ekv_kv8_step_* signatures with
+ * the same descriptor and the same planes (ekv_kv8_quantize converts; nothing about the stored rows differs).  Opt-in: the ekv_kv8_*
+ * calls take every GQA factor as before, on the VALU stream.  The rule, normative, is the one of the "kv4 gqa" calls below:
+ *   GQA factor <= 4:    the call IS the ekv_kv8_* call of the same step — return code, info fields, workspace bytes, launches,
+ *                       refusals included.
+ *   GQA factor 5 .. 16: planned as the 16-bit call (ekv_*_typed) of the same step with the one-launch decode kernel switched off: a
+ *                       whole step (phases == 0) plans as phases = 1 | 2 of that step; the phased and the deferred forms (defer_layers,
+ *                       phases 1 | 4 then 8) as they are.  Same splits, workspace and info fields; the split attention launch runs the
+ *                       MFMA decode kernel of ekv_attn_decode_g8.inc with ONE workgroup per (key-range split, KV head, layer) for all
+ *                       query heads of the KV head, so the in-kernel fold is available wherever that plan has it.  Fold, fast scorer,
+ *                       generic scorer and range compaction are the 16-bit launches.  One deviation: that kernel keeps the slot
+ *                       entries of a split's key range in LDS, so a split covers at most 31360 positions at head_dim 128 and 35456 at
+ *                       head_dim 64; where the 16-bit plan (or the caller's n_split) leaves a longer range, the step is planned with
+ *                       ceil(n_slots / bound) splits instead, and the dry runs, the workspace size and the launches all follow that
+ *                       count.
+ * Arithmetic of that kernel: the K codes are widened exactly to the 16-bit element type, head_dim / 32 16x16x32 MFMAs accumulate
+ * q . codes of a row in fp32, and logit = (q . codes) * k_scale[row] / sm_div — the kv8 builds' rule with the MFMA's summation order.
+ * V codes are widened exactly to bf16, v_scale[row] is folded into p in fp32 and p * v_scale enters as a bf16 pair hi + lo;
+ * accumulation is fp32.  The appended row is quantised by the normative rule above (the bits of ekv_kv8_quantize), stored by exactly
+ * one workgroup of the head and attended AS QUANTISED.
+ * EKV_E_UNSUPPORTED from the dry run, nothing launched and 0 workspace bytes (factor > 4): q_len > 1, rope_on_read, head_dim other
+ * than 64 / 128, a GQA factor > 16, slot-indexed score rows.  There is no batch, chunk, one-launch, capped, sink, window, pooled,
+ * adaptive, heads or long form of these calls.  EKV_E_ARG as for ekv_kv8_step_*, a missing plane included. */
+int ekv_kv8_gqa_step_check(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const ekv_kv8 *kv8);
+int ekv_kv8_gqa_step_info(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const ekv_kv8 *kv8, int32_t *info, int32_t n_info);
+size_t ekv_kv8_gqa_workspace_bytes(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const ekv_kv8 *kv8);
+int ekv_kv8_gqa_step_attend(const ekv_bank *bank, const ekv_step *step, int32_t dtype, const ekv_kv8 *kv8, const void *q,
+                            const void *k_new, const void *v_new, void *out, int32_t *evict_ids, const float *rope_cos,
+                            const float *rope_sin, void *workspace, size_t workspace_bytes, void *stream);
+
 /* MXFP4 K/V storage with block scales ("kv4"; ABI 8, additive; head_dim 128).  A bank's K/V rows may be held as
  *
  *   k_codes, v_codes   uint8 [n_layers][n_kv_heads][cap][head_dim / 2]    two e2m1 codes per byte: element 2i in the low nibble

@@ -29,6 +29,8 @@ if ROOT not in sys.path:
 from tools.bench_kv8 import _interleave, step_bytes  # noqa: E402
 
 KINDS = ("fp16", "fp8", "fp8_mxfp4", "mxfp4_grouped")
+# the grouped legs (tools/bench_kv8_gqa.py runs the second): the row format whose rows and bytes they are
+GROUPED = {"mxfp4_grouped": "mxfp4", "fp8_grouped": "fp8"}
 
 
 def make_bank(kind, L, Hq, H, D, budget):
@@ -43,8 +45,8 @@ def make_bank(kind, L, Hq, H, D, budget):
     warm = torch.rand(L, H, budget, generator=g, device=dev) * 1e-3
     bank.score_sum[:, :, :budget] += warm
     bank.score_sq[:, :, :budget] += warm ** 2
-    if kind == "mxfp4_grouped":
-        bank.quantize_mxfp4(grouped=True)
+    if kind in GROUPED:
+        (bank.quantize_mxfp4 if GROUPED[kind] == "mxfp4" else bank.quantize_fp8)(grouped=True)
     elif kind != "fp16":
         bank.quantize(kind)
     return bank, g
@@ -91,7 +93,7 @@ def leg(maker, shape, kinds, reps, steps, warm, per=1):
     res = {}
     for k in kinds:
         T = shape["budget"] + 1
-        b = step_bytes("mxfp4" if k == "mxfp4_grouped" else k, shape["L"], shape["H"], shape["Hq"], shape["D"], T)
+        b = step_bytes(GROUPED.get(k, k), shape["L"], shape["H"], shape["Hq"], shape["D"], T)
         # (a split-path step: the logits go through the workspace, written by the attention kernel and read by the scorer; t_pad = T rounded to 64)
         logit = 0 if plans[k]["fused"] else 2 * shape["L"] * shape["Hq"] * ((T + 63) // 64 * 64) * 4
         res[k] = dict(us_per_step=round(t[k]["us"] / per, 2), run_to_run_spread=t[k]["spread"], bytes_per_step=(b["total"] + logit) // per,
